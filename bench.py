@@ -16,7 +16,11 @@ resident in HBM before the timed region. Rays are counted by the kernels (closes
 queries actually issued). With N GPUs the frame's rows are split into N strips (strong scaling of one
 frame; sunray_amd/distributed.py) and the radiance strips are all-gathered over RCCL every step.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line: `metric`, `value` (Mray/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed
+frame) and `config`. A plain run does only that: set-up, warm-up, the timed frames, the line.
+--dump-outputs DIR also writes the last timed frame's radiance image (raw_color) to DIR as .npy before the line.
+
+--full adds `roofline` and `cpu_baseline` to the line, each measured in runs of its own.
 `roofline` holds three physical bounds per pass (HBM traffic, L2-resident gather rate, VALU issue), each a fraction <= 1;
 the HBM traffic and the VALU / cache counters are measured live at N = 1: before touching the GPU the process runs four
 short `rocprofv3 --pmc` passes of this same workload as child processes (about a minute; --no-pmc skips them).
@@ -36,6 +40,7 @@ L2_GATHER_PEAK_GBS = 17800.0  # MI355X_MICROARCH.md "Indexed rows: gather into L
 N_SIMD = 1024                 # 256 CUs x 4 SIMD-32; one wave64 VALU instruction occupies a SIMD for 2 cycles
 KIND_RIS, KIND_FINAL = 0, 1
 KERNEL_OF = {KIND_RIS: "ris_kernel", KIND_FINAL: "final_kernel"}
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs writes at most this much
 
 # Counter groups of the live PMC passes (one rocprofv3 --pmc run each: FETCH_SIZE takes 3 of the 4 TCC slots, WRITE_SIZE 2,
 # MI355X_MICROARCH.md "rocprofv3 PMC slots"; GRBM has its own slots).
@@ -183,6 +188,122 @@ def cpu_baseline(desc, W, H, blue_noise, budget_s=12.0, max_frames=8):
                       % (frames, W, H, t_total)}
 
 
+def dump_outputs(d, image):
+    """--dump-outputs: the last timed frame's radiance image ([H, W, 4] float32) as d/raw_color.npy. Above DUMP_LIMIT_BYTES it
+    writes a fixed, seeded sample of its pixels instead: raw_color_sample.npy ([k, 4]) and raw_color_sample_index.npy (their
+    row-major pixel indices, float64)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    if image.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(d, "raw_color.npy"), image)
+        return
+    px = image.reshape(-1, 4)
+    k = DUMP_LIMIT_BYTES // 2 // px[0].nbytes
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=k, replace=False))
+    np.save(os.path.join(d, "raw_color_sample.npy"), px[idx])
+    np.save(os.path.join(d, "raw_color_sample_index.npy"), idx.astype(np.float64))
+
+
+def roofline(per_kind, n_own_pixels, reuse, pmc, overlapped_ms, alone_ms, launches_timed, ms_per_step, pipelined, seq_frames):
+    """`roofline` of the --full result line: three physical bounds per pass and for the whole frame. per_kind: the instrumented
+    frame's counters per pass; overlapped_ms / alone_ms: a launch's wall time inside the timed region and its undisturbed
+    duration; pmc: live_pmc()'s result or None."""
+    dom = KIND_FINAL if alone_ms[KIND_FINAL] >= alone_ms[KIND_RIS] else KIND_RIS       # dominant kernel: the longer pass
+    other = KIND_RIS if dom == KIND_FINAL else KIND_FINAL
+    names = {KIND_FINAL: "final_kernel (raytracing_final)", KIND_RIS: "ris_kernel (raytracing_ris)"}
+    req = {k: requested_bytes(per_kind[k], n_own_pixels, k, reuse) for k in (KIND_RIS, KIND_FINAL)}
+    ck = per_kind[dom]
+    nq = max(ck.closest_queries + ck.any_queries, 1)
+    pk = (pmc or {}).get("kernels", {}) if pmc and "error" not in pmc else {}
+
+    def bounds_of(kind):
+        """Fractions of the three rooflines a pass can be held against, each <= 1 by construction: per-launch counters (PMC
+        children: serialised launches) over the UNDISTURBED launch duration of this run."""
+        k = pk.get(KERNEL_OF[kind], {})
+        t = alone_ms[kind] * 1e-3
+        b = {"l2_gather": {"achieved": req[kind] / t / 1e9 if t > 0 else 0.0, "peak": L2_GATHER_PEAK_GBS, "unit": "GB/s",
+                           "what": "requested bytes (16 B per box test, 48 B per triangle test, 116 B per closest hit, frame buffers) / undisturbed launch "
+                                   "time vs the MI355X's L2-resident gather rate (16.8-18.8 TB/s)"}}
+        b["l2_gather"]["frac"] = b["l2_gather"]["achieved"] / L2_GATHER_PEAK_GBS
+        if "FETCH_SIZE" in k and "WRITE_SIZE" in k:
+            traffic = (2.0 * k["FETCH_SIZE"] + k["WRITE_SIZE"]) * 1024.0   # KiB; gfx950 FETCH_SIZE counts 128-B requests at 64 B: doubled
+            b["hbm"] = {"achieved": traffic / t / 1e9 if t > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic_bytes_per_launch": traffic,
+                        "what": "physical HBM bytes per launch (live rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, read side x2: gfx950 "
+                                "counts a 128-B request as 64 B) / undisturbed launch time vs 8 TB/s"}
+            b["hbm"]["frac"] = b["hbm"]["achieved"] / HBM_PEAK_GBS
+        if "SQ_INSTS_VALU" in k and "GRBM_GUI_ACTIVE" in k:
+            cycles = k["GRBM_GUI_ACTIVE"] / 8.0                             # summed over the 8 XCDs
+            b["valu_issue"] = {"achieved": k["SQ_INSTS_VALU"] * 2.0 / cycles if cycles > 0 else 0.0, "peak": float(N_SIMD), "unit": "SIMD-cycles per cycle",
+                               "what": "SQ_INSTS_VALU x 2 cycles (wave64 on a SIMD-32) / kernel cycles (GRBM_GUI_ACTIVE / 8) vs 1024 SIMDs; counters from "
+                                       "the same launch under rocprofv3 --pmc",
+                               "lane_utilisation": k["SQ_THREAD_CYCLES_VALU"] / 64.0 / k["SQ_ACTIVE_INST_VALU"] if k.get("SQ_ACTIVE_INST_VALU") else None,
+                               "wave_time_waiting": k["SQ_WAIT_ANY"] / k["SQ_WAVE_CYCLES"] if k.get("SQ_WAVE_CYCLES") else None}
+            b["valu_issue"]["frac"] = b["valu_issue"]["achieved"] / N_SIMD
+        if "TCC_HIT_sum" in k and "TCC_MISS_sum" in k and (k["TCC_HIT_sum"] + k["TCC_MISS_sum"]) > 0:
+            b["l2_gather"]["l2_hit_rate"] = k["TCC_HIT_sum"] / (k["TCC_HIT_sum"] + k["TCC_MISS_sum"])
+        if "TA_TA_BUSY_sum" in k and "GRBM_GUI_ACTIVE" in k and k["GRBM_GUI_ACTIVE"] > 0:
+            b["l2_gather"]["ta_busy"] = k["TA_TA_BUSY_sum"] / 256.0 / (k["GRBM_GUI_ACTIVE"] / 8.0)
+        return b
+
+    bounds = {k: bounds_of(k) for k in (KIND_RIS, KIND_FINAL)}
+    bounds_dom = bounds[dom]
+    binding_name = max(bounds_dom, key=lambda n: bounds_dom[n]["frac"])
+    binding = bounds_dom[binding_name]
+
+    # Frame level: both passes' per-launch figures summed over the frame time of the timed region (two frames in flight).
+    t_step = ms_per_step * 1e-3
+    frame_roof = {"l2_gather": {"achieved": (req[KIND_RIS] + req[KIND_FINAL]) / t_step / 1e9, "peak": L2_GATHER_PEAK_GBS, "unit": "GB/s"}}
+    frame_roof["l2_gather"]["frac"] = frame_roof["l2_gather"]["achieved"] / L2_GATHER_PEAK_GBS
+    if all("hbm" in bounds[k] for k in bounds):
+        tb = sum(bounds[k]["hbm"]["traffic_bytes_per_launch"] for k in bounds)
+        frame_roof["hbm"] = {"achieved": tb / t_step / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic_bytes_per_frame": tb}
+        frame_roof["hbm"]["frac"] = frame_roof["hbm"]["achieved"] / HBM_PEAK_GBS
+    if all("SQ_INSTS_VALU" in pk.get(KERNEL_OF[k], {}) and "GRBM_GUI_ACTIVE" in pk.get(KERNEL_OF[k], {}) for k in bounds) and sum(alone_ms.values()) > 0:
+        # shader clock of this box: cycles the two kernels took under the counters / their undisturbed durations in this run
+        cyc = sum(pk[KERNEL_OF[k]]["GRBM_GUI_ACTIVE"] / 8.0 for k in bounds)
+        clock_khz = cyc / sum(alone_ms.values())                      # cycles per ms
+        valu = sum(pk[KERNEL_OF[k]]["SQ_INSTS_VALU"] for k in bounds) * 2.0
+        frame_roof["valu_issue"] = {"achieved": valu / (ms_per_step * clock_khz), "peak": float(N_SIMD), "unit": "SIMD-cycles per cycle",
+                                    "shader_clock_mhz": clock_khz / 1e3}
+        frame_roof["valu_issue"]["frac"] = frame_roof["valu_issue"]["achieved"] / N_SIMD
+    frame_roof["what"] = ("both passes' per-launch figures (requested bytes; physical HBM bytes; VALU instructions x 2 cycles) summed and divided by "
+                          "ms_per_step of the timed region (for VALU: by the cycles of a step at the shader clock = kernel cycles under the counters / "
+                          "undisturbed kernel durations)")
+    head = git_head()
+    pmc_note = ("live: %d rocprofv3 --pmc passes of this workload run by this process before the timed region (%.0f s)%s"
+                % (len(pmc["passes"]), pmc["seconds"], ", HEAD " + head if head else "")) if pmc and "error" not in pmc else \
+               ("not measured: " + (pmc["error"] if pmc else "N > 1 or --no-pmc"))
+    return {
+        "bound": binding_name,
+        "kernel": names[dom],
+        "achieved": binding["achieved"],
+        "peak": binding["peak"],
+        "unit": binding["unit"],
+        "frac": binding["frac"],
+        "traffic": bounds_dom.get("hbm", {}).get("traffic_bytes_per_launch"),
+        "traffic_source": pmc_note,
+        "bounds": bounds_dom,
+        "avg_launch_ms": alone_ms[dom],
+        "avg_launch_ms_overlapped": overlapped_ms[dom],
+        "launches_timed": launches_timed[dom],
+        "algorithmic_bytes_per_launch": req[dom],
+        "algorithmic_bytes_per_launch_survey_formula": survey_bytes(ck, n_own_pixels, dom),
+        "boxes_per_ray": ck.boxes_tested / nq,
+        "tris_per_ray": ck.tris_tested / nq,
+        "other_pass": {"kernel": KERNEL_OF[other], "avg_launch_ms": alone_ms[other], "avg_launch_ms_overlapped": overlapped_ms[other],
+                       "algorithmic_bytes_per_launch": req[other], "bounds": bounds[other]},
+        "frame": frame_roof,
+        "launches_overlap": bool(pipelined),
+        "note": "three physical rooflines per pass, `bound` = the one with the largest fraction. avg_launch_ms is the UNDISTURBED duration of a "
+                "launch (HIP events around the launches of %d frames enqueued back to back on one stream after the timed region) and prices the "
+                "per-pass fractions; "
+                "avg_launch_ms_overlapped is its wall time inside the timed region, where two frames are in flight and a launch shares the GPU "
+                "with its neighbour; `frame` prices both passes together against ms_per_step. The passes gather 64-byte BVH nodes and "
+                "48-byte triangles that live in L2 / Infinity Cache (16.5 MB + 48 MB), so HBM is not the binding roof; none of the three "
+                "is saturated: a node step waits for the slowest of its lanes' dependent fetches (DESIGN.md section 5)" % seq_frames,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -191,8 +312,11 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--grid", type=int, default=708, help="heightfield grid: 2*(grid-1)^2 triangles")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 --pmc passes (roofline.traffic and the hbm / valu_issue bounds become null)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure `roofline` (live PMC passes, an instrumented frame, undisturbed launch durations) and `cpu_baseline`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the live rocprofv3 --pmc passes (roofline.traffic and the hbm / valu_issue bounds become null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed frame's radiance image to DIR/raw_color.npy (float32)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -201,8 +325,8 @@ def main():
     # Physical counters of this very workload, measured before this process touches the GPU (N = 1 only).
     pmc = None
     import torch      # no GPU call yet: importing pages the libraries in (1-2 minutes on a fresh box), so the children below start fast
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_pmc:
-        pmc = live_pmc(["--gpus", "1", "--steps", "3", "--warmup", "3", "--no-cpu-baseline", "--no-pmc",
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_pmc:
+        pmc = live_pmc(["--gpus", "1", "--steps", "3", "--warmup", "3", "--full", "--no-cpu-baseline", "--no-pmc",
                         "--width", str(args.width), "--height", str(args.height), "--grid", str(args.grid)])
 
     import numpy as np
@@ -303,34 +427,38 @@ def main():
         step()
     fence()
 
-    # instrumented replay of ONE frame (untimed): boxes / triangles tested per launch of each pass
-    scene.set_instrumented(True)
-    per_kind = {}
-    m_i = rt.camera_matrices(desc.camera_pos, desc.camera_target, desc.fov_y, W, H, state["prev"])
     a0, an = part.span(rank)
-    own = part.tile(a0, an)
     n_own_pixels = an * (H if axis == "cols" else W)
-    halo_cfg = copy.copy(cfg)
-    halo_cfg.flags = cfg.flags | abi.TRACE_FLAG_UNCOUNTED
-    iframe = fpipe.frames[state["frame"] & 1] if fpipe is not None else frame
-    scene.reset_counters()
-    scene.trace_ris(iframe, m_i, state["frame"], cfg, tile=own)
-    per_kind[KIND_RIS] = scene.counters()
-    if world > 1:   # keep the halo's reservoirs current: they are next frame's temporal history
-        g0, gn = part.grown(rank, sd.SPATIAL_HALO)
-        for b0, bn in ((g0, a0 - g0), (a0 + an, g0 + gn - (a0 + an))):
-            if bn > 0:
-                scene.trace_ris(iframe, m_i, state["frame"], halo_cfg, tile=part.tile(b0, bn))
-    scene.reset_counters()
-    scene.trace_final(iframe, m_i, state["frame"], cfg, tile=own)
-    per_kind[KIND_FINAL] = scene.counters()
-    state["prev"] = list(m_i.view_proj)
-    state["frame"] += 1
-    scene.set_instrumented(False)
+    if args.full:
+        # instrumented replay of ONE frame (untimed): boxes / triangles tested per launch of each pass
+        scene.set_instrumented(True)
+        per_kind = {}
+        m_i = rt.camera_matrices(desc.camera_pos, desc.camera_target, desc.fov_y, W, H, state["prev"])
+        own = part.tile(a0, an)
+        halo_cfg = copy.copy(cfg)
+        halo_cfg.flags = cfg.flags | abi.TRACE_FLAG_UNCOUNTED
+        iframe = fpipe.frames[state["frame"] & 1] if fpipe is not None else frame
+        scene.reset_counters()
+        scene.trace_ris(iframe, m_i, state["frame"], cfg, tile=own)
+        per_kind[KIND_RIS] = scene.counters()
+        if world > 1:   # keep the halo's reservoirs current: they are next frame's temporal history
+            g0, gn = part.grown(rank, sd.SPATIAL_HALO)
+            for b0, bn in ((g0, a0 - g0), (a0 + an, g0 + gn - (a0 + an))):
+                if bn > 0:
+                    scene.trace_ris(iframe, m_i, state["frame"], halo_cfg, tile=part.tile(b0, bn))
+        scene.reset_counters()
+        scene.trace_final(iframe, m_i, state["frame"], cfg, tile=own)
+        per_kind[KIND_FINAL] = scene.counters()
+        state["prev"] = list(m_i.view_proj)
+        state["frame"] += 1
+        scene.set_instrumented(False)
+    else:
+        step()      # the same frame, uninstrumented: a plain and a --full run time the same frames and print the same CRC
     fence()
 
     scene.reset_counters()
-    scene.enable_timing(os.environ.get("SUNRAY_BENCH_TIMING", "1") == "1")
+    if args.full:
+        scene.enable_timing(os.environ.get("SUNRAY_BENCH_TIMING", "1") == "1")
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -339,33 +467,38 @@ def main():
     elapsed = time.perf_counter() - t0
     scene.enable_timing(False)
     c = scene.counters()
-    ris_ms, ris_n = scene.read_timing(KIND_RIS)
-    fin_ms, fin_n = scene.read_timing(KIND_FINAL)
 
     # the last TIMED frame's full fp32 radiance image, kept on the device (the frames below reuse the buffers); its CRC is taken
     # after all measurements: N-GPU runs of the same --steps/--warmup must print the 1-GPU run's value
     final_image = (pipe.image() if world > 1 else state["last"].raw_color).clone()
 
-    # Undisturbed launch durations (outside the timed region): a few more frames of the same sequence with both passes enqueued
-    # back to back on ONE stream, so no launch shares the GPU with its neighbour and the GPU never idles in between (a host
-    # synchronisation per frame, or host work before this segment, would let the clocks drop). The per-pass roofline fractions are priced with these — what
-    # `rocprofv3 --kernel-trace` shows for SUNRAY_BENCH_PIPELINE=0 — the frame-level ones with ms_per_step of the timed region.
-    seq_frames = 8
-    fence()
-    scene.enable_timing(True)
-    for _ in range(seq_frames):
-        m = rt.camera_matrices(desc.camera_pos, desc.camera_target, desc.fov_y, W, H, state["prev"])
-        state["prev"] = list(m.view_proj)
-        fr = fpipe.frames[state["frame"] & 1] if fpipe is not None else frame
-        sd.render_strip(scene, fr, m, state["frame"], cfg, part, rank)
-        submit_gather(fr)
-        state["frame"] += 1
-    fence()
-    scene.enable_timing(False)
-    ris_seq_ms, ris_seq_n = scene.read_timing(KIND_RIS)
-    fin_seq_ms, fin_seq_n = scene.read_timing(KIND_FINAL)
+    if args.full:
+        ris_ms, ris_n = scene.read_timing(KIND_RIS)
+        fin_ms, fin_n = scene.read_timing(KIND_FINAL)
+        # Undisturbed launch durations (outside the timed region): a few more frames of the same sequence with both passes enqueued
+        # back to back on ONE stream, so no launch shares the GPU with its neighbour and the GPU never idles in between (a host
+        # synchronisation per frame, or host work before this segment, would let the clocks drop). The per-pass roofline fractions
+        # are priced with these (what `rocprofv3 --kernel-trace` shows for SUNRAY_BENCH_PIPELINE=0), the frame-level ones with
+        # ms_per_step of the timed region.
+        seq_frames = 8
+        fence()
+        scene.enable_timing(True)
+        for _ in range(seq_frames):
+            m = rt.camera_matrices(desc.camera_pos, desc.camera_target, desc.fov_y, W, H, state["prev"])
+            state["prev"] = list(m.view_proj)
+            fr = fpipe.frames[state["frame"] & 1] if fpipe is not None else frame
+            sd.render_strip(scene, fr, m, state["frame"], cfg, part, rank)
+            submit_gather(fr)
+            state["frame"] += 1
+        fence()
+        scene.enable_timing(False)
+        ris_seq_ms, ris_seq_n = scene.read_timing(KIND_RIS)
+        fin_seq_ms, fin_seq_n = scene.read_timing(KIND_FINAL)
     import zlib
-    frame_crc = "%08x" % (zlib.crc32(final_image.cpu().numpy().tobytes()) & 0xFFFFFFFF)
+    final_host = final_image.cpu().numpy()
+    frame_crc = "%08x" % (zlib.crc32(final_host.tobytes()) & 0xFFFFFFFF)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final_host.reshape(H, W, 4))
 
     red_dev = "cpu" if rehearsal else device
     t_el = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -378,78 +511,8 @@ def main():
     total_rays, total_closest, total_any, total_reused = [float(x) for x in rays.tolist()]
 
     if rank == 0:
-        # per pass: wall time of a launch inside the timed region (two frames in flight: it shares the GPU with its neighbour)
-        # and its undisturbed duration (the synchronised frames after the timed region); with N > 1 the RIS pass may be
-        # several launches per step, so it is priced per step
-        overlapped_ms = {KIND_RIS: ris_ms / max(args.steps if world > 1 else ris_n, 1), KIND_FINAL: fin_ms / max(fin_n, 1)}
-        alone_ms = {KIND_RIS: ris_seq_ms / max(seq_frames if world > 1 else ris_seq_n, 1), KIND_FINAL: fin_seq_ms / max(fin_seq_n, 1)}
-        dom = KIND_FINAL if alone_ms[KIND_FINAL] >= alone_ms[KIND_RIS] else KIND_RIS       # dominant kernel: the longer pass
-        other = KIND_RIS if dom == KIND_FINAL else KIND_FINAL
-        names = {KIND_FINAL: "final_kernel (raytracing_final)", KIND_RIS: "ris_kernel (raytracing_ris)"}
-        reuse = frame.primary is not None
-        req = {k: requested_bytes(per_kind[k], n_own_pixels, k, reuse) for k in (KIND_RIS, KIND_FINAL)}
-        ck = per_kind[dom]
-        nq = max(ck.closest_queries + ck.any_queries, 1)
         ms_per_step = elapsed / args.steps * 1e3
-        pk = (pmc or {}).get("kernels", {}) if pmc and "error" not in pmc else {}
-
-        def bounds_of(kind):
-            """Fractions of the three rooflines a pass can be held against, each <= 1 by construction: per-launch counters (PMC
-            children: serialised launches) over the UNDISTURBED launch duration of this run."""
-            k = pk.get(KERNEL_OF[kind], {})
-            t = alone_ms[kind] * 1e-3
-            b = {"l2_gather": {"achieved": req[kind] / t / 1e9 if t > 0 else 0.0, "peak": L2_GATHER_PEAK_GBS, "unit": "GB/s",
-                               "what": "requested bytes (16 B per box test, 48 B per triangle test, 116 B per closest hit, frame buffers) / undisturbed launch "
-                                       "time vs the L2-resident gather rate of MI355X_MICROARCH.md (16.8-18.8 TB/s)"}}
-            b["l2_gather"]["frac"] = b["l2_gather"]["achieved"] / L2_GATHER_PEAK_GBS
-            if "FETCH_SIZE" in k and "WRITE_SIZE" in k:
-                traffic = (2.0 * k["FETCH_SIZE"] + k["WRITE_SIZE"]) * 1024.0   # KiB; gfx950 FETCH_SIZE counts 128-B requests at 64 B: doubled
-                b["hbm"] = {"achieved": traffic / t / 1e9 if t > 0 else 0.0, "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic_bytes_per_launch": traffic,
-                            "what": "physical HBM bytes per launch (live rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, read side x2 as the guide prescribes "
-                                    "for gfx950) / undisturbed launch time vs 8 TB/s"}
-                b["hbm"]["frac"] = b["hbm"]["achieved"] / HBM_PEAK_GBS
-            if "SQ_INSTS_VALU" in k and "GRBM_GUI_ACTIVE" in k:
-                cycles = k["GRBM_GUI_ACTIVE"] / 8.0                             # summed over the 8 XCDs
-                b["valu_issue"] = {"achieved": k["SQ_INSTS_VALU"] * 2.0 / cycles if cycles > 0 else 0.0, "peak": float(N_SIMD), "unit": "SIMD-cycles per cycle",
-                                   "what": "SQ_INSTS_VALU x 2 cycles (wave64 on a SIMD-32) / kernel cycles (GRBM_GUI_ACTIVE / 8) vs 1024 SIMDs; counters from "
-                                           "the same launch under rocprofv3 --pmc",
-                                   "lane_utilisation": k["SQ_THREAD_CYCLES_VALU"] / 64.0 / k["SQ_ACTIVE_INST_VALU"] if k.get("SQ_ACTIVE_INST_VALU") else None,
-                                   "wave_time_waiting": k["SQ_WAIT_ANY"] / k["SQ_WAVE_CYCLES"] if k.get("SQ_WAVE_CYCLES") else None}
-                b["valu_issue"]["frac"] = b["valu_issue"]["achieved"] / N_SIMD
-            if "TCC_HIT_sum" in k and "TCC_MISS_sum" in k and (k["TCC_HIT_sum"] + k["TCC_MISS_sum"]) > 0:
-                b["l2_gather"]["l2_hit_rate"] = k["TCC_HIT_sum"] / (k["TCC_HIT_sum"] + k["TCC_MISS_sum"])
-            if "TA_TA_BUSY_sum" in k and "GRBM_GUI_ACTIVE" in k and k["GRBM_GUI_ACTIVE"] > 0:
-                b["l2_gather"]["ta_busy"] = k["TA_TA_BUSY_sum"] / 256.0 / (k["GRBM_GUI_ACTIVE"] / 8.0)
-            return b
-
-        bounds = {k: bounds_of(k) for k in (KIND_RIS, KIND_FINAL)}
-        bounds_dom = bounds[dom]
-        binding_name = max(bounds_dom, key=lambda n: bounds_dom[n]["frac"])
-        binding = bounds_dom[binding_name]
-
-        # Frame level: both passes' per-launch figures summed over the frame time of the timed region (two frames in flight).
-        t_step = ms_per_step * 1e-3
-        frame_roof = {"l2_gather": {"achieved": (req[KIND_RIS] + req[KIND_FINAL]) / t_step / 1e9, "peak": L2_GATHER_PEAK_GBS, "unit": "GB/s"}}
-        frame_roof["l2_gather"]["frac"] = frame_roof["l2_gather"]["achieved"] / L2_GATHER_PEAK_GBS
-        if all("hbm" in bounds[k] for k in bounds):
-            tb = sum(bounds[k]["hbm"]["traffic_bytes_per_launch"] for k in bounds)
-            frame_roof["hbm"] = {"achieved": tb / t_step / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic_bytes_per_frame": tb}
-            frame_roof["hbm"]["frac"] = frame_roof["hbm"]["achieved"] / HBM_PEAK_GBS
-        if all("SQ_INSTS_VALU" in pk.get(KERNEL_OF[k], {}) and "GRBM_GUI_ACTIVE" in pk.get(KERNEL_OF[k], {}) for k in bounds) and sum(alone_ms.values()) > 0:
-            # shader clock of this box: cycles the two kernels took under the counters / their undisturbed durations in this run
-            cyc = sum(pk[KERNEL_OF[k]]["GRBM_GUI_ACTIVE"] / 8.0 for k in bounds)
-            clock_khz = cyc / sum(alone_ms.values())                      # cycles per ms
-            valu = sum(pk[KERNEL_OF[k]]["SQ_INSTS_VALU"] for k in bounds) * 2.0
-            frame_roof["valu_issue"] = {"achieved": valu / (ms_per_step * clock_khz), "peak": float(N_SIMD), "unit": "SIMD-cycles per cycle",
-                                        "shader_clock_mhz": clock_khz / 1e3}
-            frame_roof["valu_issue"]["frac"] = frame_roof["valu_issue"]["achieved"] / N_SIMD
-        frame_roof["what"] = ("both passes' per-launch figures (requested bytes; physical HBM bytes; VALU instructions x 2 cycles) summed and divided by "
-                              "ms_per_step of the timed region (for VALU: by the cycles of a step at the shader clock = kernel cycles under the counters / "
-                              "undisturbed kernel durations)")
-        head = git_head()
-        pmc_note = ("live: %d rocprofv3 --pmc passes of this workload run by this process before the timed region (%.0f s)%s"
-                    % (len(pmc["passes"]), pmc["seconds"], ", HEAD " + head if head else "")) if pmc and "error" not in pmc else \
-                   ("not measured: " + (pmc["error"] if pmc else "N > 1 or --no-pmc"))
+        reuse = frame.primary is not None
         out = {
             "metric": "Mray/s (closest-hit + any-hit queries traversed per second), 1920x1080, 1 spp, 1M-triangle scene",
             "value": total_rays / elapsed / 1e6,
@@ -486,38 +549,17 @@ def main():
                 "bvh_build_ms_host": st.build_ms,
                 "last_frame_crc32": frame_crc,
             },
-            "roofline": {
-                "bound": binding_name,
-                "kernel": names[dom],
-                "achieved": binding["achieved"],
-                "peak": binding["peak"],
-                "unit": binding["unit"],
-                "frac": binding["frac"],
-                "traffic": bounds_dom.get("hbm", {}).get("traffic_bytes_per_launch"),
-                "traffic_source": pmc_note,
-                "bounds": bounds_dom,
-                "avg_launch_ms": alone_ms[dom],
-                "avg_launch_ms_overlapped": overlapped_ms[dom],
-                "launches_timed": fin_n if dom == KIND_FINAL else ris_n,
-                "algorithmic_bytes_per_launch": req[dom],
-                "algorithmic_bytes_per_launch_survey_formula": survey_bytes(ck, n_own_pixels, dom),
-                "boxes_per_ray": ck.boxes_tested / nq,
-                "tris_per_ray": ck.tris_tested / nq,
-                "other_pass": {"kernel": KERNEL_OF[other], "avg_launch_ms": alone_ms[other], "avg_launch_ms_overlapped": overlapped_ms[other],
-                               "algorithmic_bytes_per_launch": req[other], "bounds": bounds[other]},
-                "frame": frame_roof,
-                "launches_overlap": bool(pipelined),
-                "note": "three physical rooflines per pass, `bound` = the one with the largest fraction. avg_launch_ms is the UNDISTURBED duration of a "
-                        "launch (HIP events around the launches of %d frames enqueued back to back on one stream after the timed region) and prices the "
-                        "per-pass fractions; "
-                        "avg_launch_ms_overlapped is its wall time inside the timed region, where two frames are in flight and a launch shares the GPU "
-                        "with its neighbour; `frame` prices both passes together against ms_per_step. The passes gather 64-byte BVH nodes and "
-                        "48-byte triangles that live in L2 / Infinity Cache (16.5 MB + 48 MB), so HBM is not the binding roof; none of the three "
-                        "is saturated: a node step waits for the slowest of its lanes' dependent fetches (DESIGN.md section 5)" % seq_frames,
-            },
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(desc, W, H, blue_noise)
+        if args.full:
+            # per pass: wall time of a launch inside the timed region (two frames in flight: it shares the GPU with its neighbour)
+            # and its undisturbed duration (the synchronised frames after the timed region); with N > 1 the RIS pass may be
+            # several launches per step, so it is priced per step
+            overlapped_ms = {KIND_RIS: ris_ms / max(args.steps if world > 1 else ris_n, 1), KIND_FINAL: fin_ms / max(fin_n, 1)}
+            alone_ms = {KIND_RIS: ris_seq_ms / max(seq_frames if world > 1 else ris_seq_n, 1), KIND_FINAL: fin_seq_ms / max(fin_seq_n, 1)}
+            out["roofline"] = roofline(per_kind, n_own_pixels, reuse, pmc, overlapped_ms, alone_ms, {KIND_RIS: ris_n, KIND_FINAL: fin_n},
+                                       ms_per_step, pipelined, seq_frames)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(desc, W, H, blue_noise)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -6,7 +6,7 @@ repo=${GRAFT_REPO_ROOT:-$PWD}
 out=$repo/gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $repo/bench.py --no-cpu-baseline --no-pmc"      # the program itself after `--`; bench.py's own live PMC children are off
+B="python3 $repo/bench.py --full --no-cpu-baseline --no-pmc"      # the program itself after `--`; bench.py's own live PMC children are off
 pass() {   # name, steps, warmup, rocprofv3 arguments...
   name=$1; steps=$2; warm=$3; shift 3
   timeout -k 10 200 rocprofv3 "$@" --output-format csv -d /tmp/p_$name -o p -- $B --steps $steps --warmup $warm > $out/$name.log 2>&1 || { echo "$name FAILED"; tail -3 $out/$name.log; return 1; }

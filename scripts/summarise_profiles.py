@@ -11,7 +11,7 @@ for f in sorted(glob.glob(d + '/pmc*_counter_collection.csv')):
         k = r['Kernel_Name']
         if 'srd::' in k and ('ris_kernel<0>' in k or 'final_kernel<0>' in k):
             rows[(k.split('(')[0].replace('void srd::', ''), r['Counter_Name'])].append(float(r['Counter_Value']))
-lines = ["# rocprofv3 --pmc, mean per launch over the launches of `python3 bench.py --no-cpu-baseline --no-pmc --steps 5 --warmup 3` (1x MI355X), one counter",
+lines = ["# rocprofv3 --pmc, mean per launch over the launches of `python3 bench.py --full --no-cpu-baseline --no-pmc --steps 5 --warmup 3` (1x MI355X), one counter",
          "# group per run (scripts/profile_round.sh). SQ_* cycle counters are in quad-cycles, *_sum counters are summed over the 256 CUs, GRBM_GUI_ACTIVE over the 8 XCDs.",
          "# Under --pmc the dispatches run one after the other (no overlap of the two frames in flight), so these are per-kernel figures."]
 m = {}
