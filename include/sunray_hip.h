@@ -695,6 +695,27 @@ int sr_scene_set_instrumented(SrScene* scene, int on);
 int sr_scene_enable_timing(SrScene* scene, int enable);
 int sr_scene_read_timing(SrScene* scene, int kind, double* total_ms, uint32_t* n_launches);
 
+/* ---- One frame on several devices from one Renderer ----------------------------------
+ * A multi-device renderer is an SrRenderer with more than one device slot; every sr_renderer_* call keeps its meaning on it.
+ * Each slot holds a replica of the scene and traces its strip of the frame (sr_strip_trace_ris / _final); the temporal-history
+ * bands of sr_history_exchange_plan and the radiance / G-buffer strips move between slots as device-to-device peer copies, and
+ * the post chain runs on the gathered frame on devices[0], so the output is the single-device output bit for bit whenever
+ * sr_renderer_read_history_overflow reads 0. Two frames may be in flight, as with one device. */
+/* devices[0..n): one slot per entry; the same device may repeat (all slots on one GPU = rehearsal mode). Output, the post
+ * chain and the SrScene returned by sr_renderer_get live on devices[0]. n_devices == 1 is exactly sr_renderer_create. */
+int sr_renderer_create_multi(const int* devices, uint32_t n_devices, uint32_t width, uint32_t height, uint32_t axis,
+                             SrRenderer** out);
+/* n_devices + 1 cuts (sr_partition_create rules). Allowed only before the first frame after create / resize, else SR_ERR_STATE. */
+int sr_renderer_set_strip_bounds(SrRenderer* r, const uint32_t* bounds);
+/* Temporal-history band exchanged after every RIS pass (sr_history_exchange_plan's motion_halo). Default 32 pixels.
+ * Allowed only before the first frame after create / resize, else SR_ERR_STATE. */
+int sr_renderer_set_motion_halo(SrRenderer* r, uint32_t pixels);
+/* The replica scene of slot i (tests read per-slot ray counters through it). Slot 0's is the scene of sr_renderer_get. */
+int sr_renderer_replica_scene(SrRenderer* r, uint32_t slot, SrScene** out);
+/* Synchronising. Counts pixels, since create / resize, whose temporal-history read may have landed outside what their slot
+ * held. 0 means every frame so far equals the single-device frame. Always 0 for one slot. */
+int sr_renderer_read_history_overflow(SrRenderer* r, uint64_t* pixels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 // path, layered purely on this library's own C ABI (sr_scene_*, sr_trace_*, sr_post_*):
 //   new / resize / load_mesh / unload_mesh / render / wait_frame / render_to_host_memory
 // (src/lib.rs:212-446, 586-639, 873-973, 984-1238, 1908-1934). Keys are u64 (the reference's generic
-// ResourceKey, lib.rs:54-58). One Renderer = one GPU, one caller thread (the reference is !Send).
+// ResourceKey, lib.rs:54-58). One Renderer = one GPU, one caller thread (the reference is !Send); a renderer made by
+// sr_renderer_create_multi adds device slots (multi_renderer.cpp), to which every scene-changing call here fans out.
 #include <hip/hip_runtime.h>
 
 #include <array>
@@ -13,52 +14,8 @@
 #include <vector>
 
 #include "host.h"
+#include "renderer.h"
 
-
-struct SrRenderer {
-    int device = 0;
-    SrScene* scene = nullptr;
-    uint32_t width = 0, height = 0;
-    // frame buffers (the reference's transient G-buffer images + temporal resources, lib.rs:320-331,1492-1516)
-    // MAX_FRAMES_IN_FLIGHT = 2 (lib.rs:71): the images one frame writes and reads are double-buffered, so raytracing_ris of
-    // frame f+1 (own stream) overlaps raytracing_final + the post chain of frame f. The reservoir, accumulation and denoise
-    // ping-pongs carry history from frame to frame and stay single sets.
-    float* raw_color[2] = {nullptr, nullptr};
-    uint16_t* depth[2] = {nullptr, nullptr};
-    uint32_t *normal[2] = {nullptr, nullptr}, *diffuse[2] = {nullptr, nullptr}, *motion[2] = {nullptr, nullptr};
-    SrReservoir* reservoirs[2] = {nullptr, nullptr};
-    SrReservoirGI* reservoirs_gi[2] = {nullptr, nullptr};
-    uint32_t *accum[2] = {nullptr, nullptr}, *denoise[2] = {nullptr, nullptr};
-    uint32_t* output[2] = {nullptr, nullptr};
-    SrRayPayload* primary[2] = {nullptr, nullptr};   // primary-hit hand-off RIS -> final (SrRtParams.primary_payload), part of the per-frame set
-    int primary_reuse = 1;                           // SR_PRIMARY_REUSE=0 in the environment: the final pass traces its camera ray itself (A/B)
-    hipStream_t s_ris = nullptr, s_final = nullptr;
-    hipEvent_t ev_in = nullptr, ev_ris[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
-    int last_set = 0;
-    uint8_t* blue_noise = nullptr;
-    uint32_t noise_w = 128, noise_h = 128;
-    // per-frame state
-    float prev_view_proj[16];       // zero on the first frame (lib.rs:410), NOT reset by resize
-    uint32_t relative_frame_count = 0;
-    uint64_t absolute_frame_count = 0;
-    SrTraceConfig config;
-    std::vector<uint64_t> last_keys;
-    std::vector<uint32_t> last_counts;
-    std::vector<SrTransform> last_transforms;
-    bool instances_valid = false;
-    // asset groups of load_scene (lib.rs:802-828): group -> BLAS keys and image slots (both freed by unload_scene)
-    uint64_t next_group = 0;
-    std::map<uint64_t, std::vector<uint64_t>> scene_groups;
-    std::map<uint64_t, std::vector<uint32_t>> scene_images;
-    // frame / resize callbacks (lib.rs:537-554): (due frame, fn, user); start-of-frame and end-of-frame ones run once
-    struct FrameCb { uint64_t frame; SrFrameCallback fn; void* user; };
-    std::vector<FrameCb> start_of_frame_callbacks, end_of_frame_callbacks;
-    std::vector<std::pair<SrResizeCallback, void*>> resize_callbacks;
-    uint64_t frame_of_set[2] = {0, 0};       // absolute frame number last rendered into image set k (its completion = ev_done[k])
-    uint64_t completed_frame = 0;            // highest frame known complete on the GPU (frames complete in order)
-    std::map<std::array<uint32_t, 4>, uint32_t> sampler_slots;   // dedup like ResourceManager::sampler_slot (resource_manager.rs:491-499)
-    int default_sampler = -1;                                    // LINEAR / CLAMP_TO_EDGE (resource_manager.rs:128-136)
-};
 
 struct SrLoadedScene {
     uint64_t group = 0;
@@ -158,11 +115,12 @@ int sr_renderer_set_blue_noise(SrRenderer* r, const uint8_t* rgba8, uint32_t w, 
     if (hipMemcpy(fresh, rgba8, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(fresh); return rfail(SR_ERR_HIP, "sr_renderer_set_blue_noise: upload failed"); }
     if (r->blue_noise) (void)hipFree(r->blue_noise);
     r->blue_noise = fresh; r->noise_w = w; r->noise_h = h;
-    return SR_OK;
+    return r->multi ? srmr::set_blue_noise(r, rgba8, w, h) : SR_OK;
 }
 
 int sr_renderer_destroy(SrRenderer* r) {
     if (!r) return SR_OK;
+    if (r->multi) srmr::destroy(r);                              // synchronises and frees every other slot first
     (void)hipSetDevice(r->device);
     (void)hipDeviceSynchronize();
     free_images(r);
@@ -184,6 +142,7 @@ int sr_renderer_resize(SrRenderer* r, uint32_t width, uint32_t height) {
         free_images(r);
         int rc = alloc_images(r, width, height);
         if (rc != SR_OK) return rc;
+        if (r->multi && (rc = srmr::resize(r, width, height)) != SR_OK) return rc;
         r->relative_frame_count = 0;
     }
     for (auto& cb : r->resize_callbacks) cb.first(cb.second, width, height);   // every resize call, changed extent or not (lib.rs:590-592)
@@ -236,7 +195,11 @@ int sr_renderer_load_mesh(SrRenderer* r, uint64_t key, const SrVertex* vertices,
                           uint32_t n_indices, const SrMaterial* material) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "load_mesh: renderer is null");
     r->instances_valid = false;
-    return sr_scene_add_mesh(r->scene, key, vertices, n_vertices, indices, n_indices, material, nullptr);
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_add_mesh(sc, key, vertices, n_vertices, indices, n_indices, material, nullptr);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
 }
 
 int sr_renderer_set_config(SrRenderer* r, const SrTraceConfig* cfg) {
@@ -263,15 +226,19 @@ int sr_renderer_render(SrRenderer* r, const float cam_pos[3], const float cam_ta
                       (n_keys == 0 || (memcmp(r->last_keys.data(), keys, n_keys * 8) == 0 && memcmp(r->last_counts.data(), counts, n_keys * 4) == 0)) &&
                       (n_xf == 0 || memcmp(r->last_transforms.data(), transforms, n_xf * sizeof(SrTransform)) == 0);
     if (!same) {
-        int rc = sr_scene_set_instances(r->scene, keys, counts, n_keys, transforms);
-        if (rc != SR_OK) return rc;
+        for (SrScene* sc : srmr::scenes(r)) {                        // every replica, in slot order (host BVH build per replica)
+            int rc = sr_scene_set_instances(sc, keys, counts, n_keys, transforms);
+            if (rc != SR_OK) return rc;
+        }
         r->last_keys.assign(keys, keys + n_keys);
         r->last_counts.assign(counts, counts + n_keys);
         r->last_transforms.assign(transforms, transforms + n_xf);
         r->instances_valid = true;
     } else {
-        int rc = sr_scene_end_frame(r->scene);      // quiet frame: the heuristic may settle with a quality rebuild
-        if (rc != SR_OK) return rc;
+        for (SrScene* sc : srmr::scenes(r)) {
+            int rc = sr_scene_end_frame(sc);        // quiet frame: the heuristic may settle with a quality rebuild
+            if (rc != SR_OK) return rc;
+        }
     }
     SrMatrices m;
     int rc = sr_camera_matrices(cam_pos, cam_target, fov_y, r->width, r->height, r->prev_view_proj, &m);   // lib.rs:1017-1048
@@ -279,6 +246,15 @@ int sr_renderer_render(SrRenderer* r, const float cam_pos[3], const float cam_ta
     memcpy(r->prev_view_proj, m.view_proj, sizeof(r->prev_view_proj));                                     // history for the NEXT frame
     // image set of this frame; the orderings that remain: RIS(f) -> final(f) -> post(f), RIS(f) -> RIS(f+1) and post(f-2) -> RIS(f)
     const int k = (int)(r->relative_frame_count & 1u);
+    if (r->multi) {                                                  // N device slots: strips, exchange, gather, post on slot 0
+        if ((rc = srmr::render_frame(r, m, k, (hipStream_t)stream)) != SR_OK) return rc;
+        r->last_set = k;
+        r->relative_frame_count += 1;
+        r->absolute_frame_count += 1;
+        r->frame_of_set[k] = r->absolute_frame_count;
+        if (out_frame) *out_frame = r->absolute_frame_count;
+        return SR_OK;
+    }
     R_HIP(hipEventRecord(r->ev_in, (hipStream_t)stream));           // whatever the caller enqueued on `stream` comes first
     R_HIP(hipStreamWaitEvent(r->s_ris, r->ev_in, 0));
     R_HIP(hipStreamWaitEvent(r->s_ris, r->ev_done[k], 0));          // frame f-2 no longer reads this image set
@@ -352,7 +328,13 @@ int sampler_slot(SrRenderer* r, const SrSamplerDesc& d, uint32_t* out) {
     const std::array<uint32_t, 4> k = {d.min_filter, d.mag_filter, d.address_mode_u, d.address_mode_v};
     auto it = r->sampler_slots.find(k);
     if (it != r->sampler_slots.end()) { *out = it->second; return SR_OK; }
-    int rc = sr_scene_add_sampler(r->scene, &d, out);
+    std::vector<uint32_t> slots;
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_add_sampler(sc, &d, out);
+        if (rc != SR_OK) return rc;
+        slots.push_back(*out);
+    }
+    int rc = srmr::check_same_slots(slots, "load_scene: sampler");
     if (rc == SR_OK) r->sampler_slots[k] = *out;
     return rc;
 }
@@ -363,19 +345,31 @@ int sr_renderer_load_scene(SrRenderer* r, const SrGltf* g, SrLoadedScene** out) 
     if (!r || !g || !out) return rfail(SR_ERR_INVALID_ARG, "load_scene: null argument");
     R_HIP(hipSetDevice(r->device));
     R_HIP(hipDeviceSynchronize());                       // device_wait_idle (lib.rs:800)
+    if (r->multi) { int rc = srmr::synchronize(r); if (rc != SR_OK) return rc; }
     uint32_t n_blases = 0, n_instances = 0, n_images = 0, n_samplers = 0, n_textures = 0;
     int rc = sr_gltf_counts(g, &n_blases, &n_instances, &n_images, &n_samplers, &n_textures);
     if (rc != SR_OK) return rc;
     const uint64_t group = r->next_group++;
     std::vector<uint32_t> image_slots(n_images), smp_slots(n_samplers);
     std::vector<uint32_t>& group_images = r->scene_images[group];     // freed again by unload_scene (also after a failed load)
+    const std::vector<SrScene*> scs = srmr::scenes(r);               // parsed once, uploaded to every replica
     for (uint32_t i = 0; i < n_images; i++) {
         const uint8_t* px; uint32_t w, h, ch;
-        if ((rc = sr_gltf_image(g, i, &px, &w, &h, &ch)) != SR_OK || (rc = sr_scene_add_image(r->scene, px, w, h, ch, &image_slots[i])) != SR_OK) {
-            for (uint32_t sl : group_images) sr_scene_remove_image(r->scene, sl);
+        std::vector<uint32_t> slots;
+        if ((rc = sr_gltf_image(g, i, &px, &w, &h, &ch)) == SR_OK)
+            for (SrScene* sc : scs) {
+                uint32_t sl = 0;
+                if ((rc = sr_scene_add_image(sc, px, w, h, ch, &sl)) != SR_OK) break;
+                slots.push_back(sl);
+            }
+        if (rc == SR_OK) rc = srmr::check_same_slots(slots, "load_scene: image");
+        if (rc != SR_OK) {
+            for (size_t j = 0; j < slots.size(); j++) sr_scene_remove_image(scs[j], slots[j]);
+            for (uint32_t sl : group_images) for (SrScene* sc : scs) sr_scene_remove_image(sc, sl);
             r->scene_images.erase(group);
             return rc;
         }
+        image_slots[i] = slots[0];
         group_images.push_back(image_slots[i]);
     }
     for (uint32_t i = 0; i < n_samplers; i++) {
@@ -404,8 +398,11 @@ int sr_renderer_load_scene(SrRenderer* r, const SrGltf* g, SrLoadedScene** out) 
             slots[k + 1] = smp >= 0 ? smp_slots[smp] : (uint32_t)r->default_sampler;
         }
         const uint64_t key = (group << 32) | (uint64_t)b;   // ResourceKey{group, index}
-        if ((rc = sr_scene_add_blas(r->scene, key, v, nv, idx, ni, &m, et, ne, nullptr)) != SR_OK) {
-            for (uint64_t k : group_keys) sr_scene_remove(r->scene, k);
+        for (size_t j = 0; j < scs.size() && rc == SR_OK; j++)
+            if ((rc = sr_scene_add_blas(scs[j], key, v, nv, idx, ni, &m, et, ne, nullptr)) != SR_OK)
+                for (size_t i = 0; i < j; i++) sr_scene_remove(scs[i], key);
+        if (rc != SR_OK) {
+            for (uint64_t k : group_keys) for (SrScene* sc : scs) sr_scene_remove(sc, k);
             delete ls;
             return rc;
         }
@@ -460,14 +457,16 @@ int sr_renderer_unload_scene(SrRenderer* r, uint64_t group) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "unload_scene: renderer is null");
     R_HIP(hipSetDevice(r->device));
     R_HIP(hipDeviceSynchronize());                                   // device_wait_idle (lib.rs:850)
+    if (r->multi) { int rc = srmr::synchronize(r); if (rc != SR_OK) return rc; }
+    const std::vector<SrScene*> scs = srmr::scenes(r);
     auto it = r->scene_groups.find(group);
     if (it != r->scene_groups.end()) {
-        for (uint64_t k : it->second) { int rc = sr_scene_remove(r->scene, k); if (rc != SR_OK) return rc; }
+        for (uint64_t k : it->second) for (SrScene* sc : scs) { int rc = sr_scene_remove(sc, k); if (rc != SR_OK) return rc; }
         r->scene_groups.erase(it);
     }
     auto im = r->scene_images.find(group);
     if (im != r->scene_images.end()) {
-        for (uint32_t sl : im->second) { int rc = sr_scene_remove_image(r->scene, sl); if (rc != SR_OK) return rc; }
+        for (uint32_t sl : im->second) for (SrScene* sc : scs) { int rc = sr_scene_remove_image(sc, sl); if (rc != SR_OK) return rc; }
         r->scene_images.erase(im);
     }
     r->instances_valid = false;
@@ -479,7 +478,11 @@ int sr_renderer_unload_scene(SrRenderer* r, uint64_t group) {
 int sr_renderer_unload_mesh(SrRenderer* r, uint64_t key) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "unload_mesh: renderer is null");
     r->instances_valid = false;
-    return sr_scene_remove(r->scene, key);
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_remove(sc, key);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
 }
 
 // Access for harnesses: the scene (counters, stats), the device output image and the frame counter.

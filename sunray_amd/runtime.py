@@ -458,15 +458,75 @@ def gltf_parse(path):
         lib().sr_gltf_close(g)
 
 
+class _SceneView(Scene):
+    """A scene owned by someone else (a renderer's replica): the Scene methods without destroying it."""
+
+    def __init__(self, handle, device_index):
+        self._h = handle
+        self.device_index = device_index
+
+    def close(self):
+        self._h = None
+
+    @staticmethod
+    def _stream():
+        return None         # the null stream of the scene's own device (the library binds it): slots may sit on other devices
+
+
 class Renderer:
     """The reference's `Renderer<K>` surface for the built path (src/lib.rs:212-446, 586-639, 873-954,
     984-1238, 1908-1934), over sr_renderer_*. `camera` = (position, target, fov_y_degrees) — the
     reference's Camera (camera.rs:11-44); `instances` = [(mesh key, [3x4 row-major transform, ...]), ...]."""
 
-    def __init__(self, size, device_index=0):
+    def __init__(self, size, device_index=0, devices=None, axis="cols", bounds=None, motion_halo=None):
+        """`devices` (a list of device indices, repeats allowed) renders every frame across that many device slots
+        (sr_renderer_create_multi): column or row strips (`axis`), cut equally or at `bounds` (len(devices) + 1 cuts), with
+        temporal-history bands of `motion_halo` pixels exchanged after every RIS pass (default 32). Output on devices[0]."""
         self._h = C.c_void_p()
         self.size = (int(size[0]), int(size[1]))
-        check(lib().sr_renderer_create(C.c_int(device_index), C.c_uint32(self.size[0]), C.c_uint32(self.size[1]), C.byref(self._h)))
+        if devices is None:
+            if bounds is not None or motion_halo is not None or axis != "cols":
+                raise ValueError("axis, bounds and motion_halo need devices")
+            check(lib().sr_renderer_create(C.c_int(device_index), C.c_uint32(self.size[0]), C.c_uint32(self.size[1]), C.byref(self._h)))
+            self.devices = [int(device_index)]
+            return
+        if axis not in ("cols", "rows"):
+            raise ValueError("axis must be 'cols' or 'rows'")
+        devs = [int(d) for d in devices]
+        if bounds is not None and len(bounds) != len(devs) + 1:
+            raise ValueError("bounds must be %d cuts (one more than the devices)" % (len(devs) + 1))
+        arr = (C.c_int * max(len(devs), 1))(*devs)
+        check(lib().sr_renderer_create_multi(arr, C.c_uint32(len(devs)), C.c_uint32(self.size[0]), C.c_uint32(self.size[1]),
+                                             C.c_uint32(0 if axis == "cols" else 1), C.byref(self._h)))
+        self.devices = devs
+        if bounds is not None:
+            self.set_strip_bounds(bounds)
+        if motion_halo is not None:
+            self.set_motion_halo(motion_halo)
+
+    def set_strip_bounds(self, bounds):
+        b = [int(v) for v in bounds]
+        if len(b) != len(self.devices) + 1 or any(v < 0 for v in b):
+            raise ValueError("bounds must be %d increasing cuts" % (len(self.devices) + 1))
+        check(lib().sr_renderer_set_strip_bounds(self._h, (C.c_uint32 * len(b))(*b)))
+
+    def set_motion_halo(self, pixels):
+        if int(pixels) < 0:
+            raise ValueError("motion_halo must not be negative")
+        check(lib().sr_renderer_set_motion_halo(self._h, C.c_uint32(int(pixels))))
+
+    def replica_scene(self, i):
+        """A non-owning view of slot i's scene (ray counters, stats): valid while the renderer lives."""
+        h = C.c_void_p()
+        check(lib().sr_renderer_replica_scene(self._h, C.c_uint32(int(i)), C.byref(h)))
+        return _SceneView(h, self.devices[int(i)])
+
+    def history_overflow(self):
+        """Pixels, since create / resize, whose temporal-history read may have left what their slot held (synchronising).
+        0 means every frame so far equals the single-device frame."""
+        n = C.c_uint64()
+        check(lib().sr_renderer_read_history_overflow(self._h, C.byref(n)))
+        return n.value
 
     def close(self):
         if self._h:
