@@ -8,7 +8,10 @@
 #include "orc_scene.h"
 
 using namespace orc;
-namespace orc { void post_temporal(const SrPostParams&); void post_denoise(const SrPostParams&); void post_tonemap(const SrPostParams&); }
+namespace orc {
+void post_temporal(const SrPostParams&); void post_denoise(const SrPostParams&); void post_tonemap(const SrPostParams&);
+void post_denoise_step(const SrPostParams&, const uint32_t*, uint32_t*, int);
+}
 
 extern "C" {
 
@@ -75,6 +78,7 @@ void orc_trace_ris(void* sp, const SrRtParams* p) { trace_ris(*(Scene*)sp, *p); 
 void orc_trace_final(void* sp, const SrRtParams* p) { trace_final(*(Scene*)sp, *p); }
 void orc_post_temporal(const SrPostParams* p) { post_temporal(*p); }
 void orc_post_denoise(const SrPostParams* p) { post_denoise(*p); }
+void orc_post_denoise_step(const SrPostParams* p, const uint32_t* src, uint32_t* dst, int step_width) { post_denoise_step(*p, src, dst, step_width); }
 void orc_post_tonemap(const SrPostParams* p) { post_tonemap(*p); }
 float orc_log(float x) { return log_f(x); }
 float orc_pow(float x, float y) { return pow_f(x, y); }

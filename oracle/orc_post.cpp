@@ -29,7 +29,7 @@ void post_temporal(const SrPostParams& p) {
     const int W = (int)p.width, H = (int)p.height;
     const uint32_t* history = p.accum[(p.frame_count + 1u) % 2u];   // lib.rs:1360-1361
     uint32_t* target = p.accum[p.frame_count % 2u];
-#pragma omp parallel for schedule(static)
+#pragma omp parallel for collapse(2) schedule(static)   // over pixels, so a one-row image uses every thread too
     for (int y = 0; y < H; y++)
         for (int x = 0; x < W; x++) {
             auto tile = [&](int dx, int dy) {   // the LDS tile: clamp-to-edge reads of raw_rt_color (:82-86)
@@ -54,7 +54,7 @@ void post_temporal(const SrPostParams& p) {
             if (!off && p.frame_count > 2u) {
                 // sample_history_bilinear (:42-58)
                 const float px_ = pux * (float)W - 0.5f, py_ = puy * (float)H - 0.5f;
-                const int bx = (int)floorf(px_), by = (int)floorf(py_);
+                const int bx = px_ == px_ ? (int)floorf(px_) : 0, by = py_ == py_ ? (int)floorf(py_) : 0;   // NaN motion: DESIGN.md §3
                 const float fx = px_ - (float)bx, fy = py_ - (float)by;
                 auto hist = [&](int ix, int iy) { return load_b10g11r11(history, (size_t)clampi(iy, 0, H - 1) * W + clampi(ix, 0, W - 1)); };
                 const V3 h00 = hist(bx, by), h10 = hist(bx + 1, by), h01 = hist(bx, by + 1), h11 = hist(bx + 1, by + 1);
@@ -70,7 +70,7 @@ void post_temporal(const SrPostParams& p) {
 static void denoise_pass(const SrPostParams& p, const uint32_t* src, uint32_t* dst, int step_width) {
     const int W = (int)p.width, H = (int)p.height;
     static const float kernel[5] = {1.0f / 16.0f, 4.0f / 16.0f, 6.0f / 16.0f, 4.0f / 16.0f, 1.0f / 16.0f};
-#pragma omp parallel for schedule(static)
+#pragma omp parallel for collapse(2) schedule(static)
     for (int y = 0; y < H; y++)
         for (int x = 0; x < W; x++) {
             const size_t i = (size_t)y * W + x;
@@ -123,6 +123,8 @@ void post_denoise(const SrPostParams& p) {
         denoise_pass(p, src, dst, 1 << pass);
     }
 }
+// one a-trous pass of any step width between caller-chosen images (tests: the tap lattice of a single step)
+void post_denoise_step(const SrPostParams& p, const uint32_t* src, uint32_t* dst, int step_width) { denoise_pass(p, src, dst, step_width); }
 
 static inline float aces(float x) {   // postprocess.slang:14-18, per component
     x = clamp_f(x, 0.0f, 100.0f);

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void temporal_kernel(SrPostParams p) {
     if (!off && p.frame_count > 2u) {
         const uint32_t* history = p.accum[(p.frame_count + 1u) % 2u];
         const float px_ = pux * (float)W - 0.5f, py_ = puy * (float)H - 0.5f;   // sample_history_bilinear :42-58
-        const int bx = (int)floorf(px_), by = (int)floorf(py_);
+        const int bx = px_ == px_ ? (int)floorf(px_) : 0, by = py_ == py_ ? (int)floorf(py_) : 0;   // NaN motion: DESIGN.md §3
         const float fx = px_ - (float)bx, fy = py_ - (float)by;
         const int x0 = clampi(bx, 0, W - 1), x1 = clampi(bx + 1, 0, W - 1), y0 = clampi(by, 0, H - 1), y1 = clampi(by + 1, 0, H - 1);
         const f3 h00 = unpack_b10g11r11(history[(size_t)y0 * W + x0]), h10 = unpack_b10g11r11(history[(size_t)y0 * W + x1]);
