@@ -368,6 +368,48 @@ int sr_scene_force_next_op(SrScene* scene, uint32_t op);
 #define SR_INSTANCING_TWO_LEVEL 2u
 int sr_scene_set_instancing(SrScene* scene, uint32_t mode);
 int sr_scene_instancing(const SrScene* scene, uint32_t* mode, uint32_t* two_level_now);
+/* Where the top-level tree of the two-level form is built when the instance list of a scene ALREADY built in that form changes
+ * (the reference rebuilds its TLAS on the GPU every frame, tlas.rs:155-191). SR_TL_BUILD_DEVICE: the instance records, their padded
+ * world boxes (byte for byte the host's) and the tree (Morton sort + SR_FAST_BUILD topology + budgeted 4-wide collapse over the
+ * boxes) come from device kernels; SR_TL_BUILD_HOST: the host binned-SAH builder, always; SR_TL_BUILD_AUTO (default): the device
+ * from SrTopLevelInfo.auto_threshold instance boxes on. The first build, the settle rebuild of sr_scene_end_frame, lists with
+ * fewer than two instance boxes, lists with an instance whose transform cannot be inverted well (it gets a baked copy of its
+ * mesh) and trees outside the traversal-stack budget are built on the host in every mode. Queries give the same bits either way.
+ * SR_TL_BUILD = host | device | auto in the environment sets the initial mode (anything else: auto). */
+#define SR_TL_BUILD_AUTO 0u
+#define SR_TL_BUILD_HOST 1u
+#define SR_TL_BUILD_DEVICE 2u
+int sr_scene_set_top_level_build(SrScene* scene, uint32_t mode);
+/* Why the last top-level build ran on the host (SrTopLevelInfo.reason; SR_TL_ON_DEVICE: it did not). */
+#define SR_TL_ON_DEVICE 0u
+#define SR_TL_HOST_MODE 1u             /* SR_TL_BUILD_HOST */
+#define SR_TL_HOST_BELOW_THRESHOLD 2u  /* auto mode, fewer instance boxes than auto_threshold */
+#define SR_TL_HOST_BAKED_INSTANCE 3u   /* an instance of the list needs a baked copy of its mesh */
+#define SR_TL_HOST_STACK_BUDGET 4u     /* the device tree would need more traversal-stack entries than the mesh trees leave */
+#define SR_TL_HOST_NOT_TWO_LEVEL 5u    /* nothing stood in the two-level form: first build, form switch, meshes added or removed since */
+#define SR_TL_HOST_TOO_FEW 6u          /* fewer than two instance boxes */
+#define SR_TL_HOST_QUALITY_BUILD 7u    /* the settle rebuild of sr_scene_end_frame */
+typedef struct SrTopLevelInfo {
+    uint32_t on_device;       /* 1: the last top-level build ran on the device */
+    uint32_t reason;          /* SR_TL_ON_DEVICE or SR_TL_HOST_* */
+    uint32_t mode;            /* SR_TL_BUILD_* in force */
+    uint32_t auto_threshold;  /* instance boxes from which auto mode builds on the device */
+    uint32_t n_nodes;         /* nodes of the top-level tree */
+    uint32_t n_boxes;         /* instances with a box = entries of the leaf order */
+    uint32_t n_instances;
+    uint32_t max_stack;       /* worst-case stack entries of the top-level tree alone */
+    uint32_t blas_stack;      /* ... of the deepest mesh tree in use: max_stack + leaf size + blas_stack + 1 = SrBvhStats.max_stack */
+    uint32_t _pad;
+    double records_ms;        /* instance records + boxes (device: including the upload of the instance tables) */
+    double tree_ms;           /* top-level tree */
+    double build_ms;          /* the whole build as sr_scene_set_instances saw it */
+} SrTopLevelInfo;             /* 64 bytes */
+int sr_scene_top_level_info(const SrScene* scene, SrTopLevelInfo* out);
+/* Harness read-back of the top level of a scene built in the two-level form, whichever path built it (the counterpart of
+ * sr_scene_read_bvh): n_nodes x 16 dwords, n_boxes dwords (leaf order -> instance index), n_instances x 128 bytes (the
+ * instance records the walk reads), n_instances x 6 floats (padded world box lo, hi; a row of NaN: the instance has no box).
+ * Counts as in SrTopLevelInfo; any pointer may be NULL. */
+int sr_scene_read_top_level(const SrScene* scene, uint32_t* nodes, uint32_t* tl_inst, void* records, float* boxes);
 /* Node layout of the quantised wide BVH this build uses (csrc/bvh_layout.h): children per node, dwords per node, first
  * plane dword, first child dword. */
 int sr_bvh_layout(uint32_t* width, uint32_t* node_dwords, uint32_t* plane_offset, uint32_t* child_offset);

@@ -26,6 +26,7 @@ SYMBOLS = [
     "sr_history_exchange_plan", "sr_strip_rects", "sr_strip_trace_ris", "sr_strip_trace_final", "sr_scene_set_instancing", "sr_scene_instancing",
     "sr_renderer_create_multi", "sr_renderer_set_strip_bounds", "sr_renderer_set_motion_halo", "sr_renderer_replica_scene",
     "sr_renderer_read_history_overflow",
+    "sr_scene_set_top_level_build", "sr_scene_top_level_info", "sr_scene_read_top_level",
 ]
 
 

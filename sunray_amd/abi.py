@@ -145,6 +145,23 @@ class SrAsState(C.Structure):
 
 
 BUILD_RAPIDLY_CHANGING, BUILD_SOMETIMES_CHANGES, BUILD_STATIC = 0, 1, 2
+
+
+class SrTopLevelInfo(C.Structure):  # the last top-level build of a two-level scene (sr_scene_top_level_info)
+    _fields_ = [("on_device", C.c_uint32), ("reason", C.c_uint32), ("mode", C.c_uint32), ("auto_threshold", C.c_uint32),
+                ("n_nodes", C.c_uint32), ("n_boxes", C.c_uint32), ("n_instances", C.c_uint32), ("max_stack", C.c_uint32),
+                ("blas_stack", C.c_uint32), ("_pad", C.c_uint32), ("records_ms", C.c_double), ("tree_ms", C.c_double),
+                ("build_ms", C.c_double)]
+
+
+TL_BUILD_AUTO, TL_BUILD_HOST, TL_BUILD_DEVICE = 0, 1, 2
+(TL_ON_DEVICE, TL_HOST_MODE, TL_HOST_BELOW_THRESHOLD, TL_HOST_BAKED_INSTANCE, TL_HOST_STACK_BUDGET, TL_HOST_NOT_TWO_LEVEL,
+ TL_HOST_TOO_FEW, TL_HOST_QUALITY_BUILD) = range(8)
+TL_STACK_CAP = 47  # LDS stack entries a two-level walk may need: top level + leaf size + deepest mesh tree + 1 (csrc/api.cpp)
+# DevTlInstance (csrc/traverse.h), 128 bytes: what sr_scene_read_top_level returns per instance
+TL_INSTANCE = np.dtype([("w2o", np.float32, 12), ("o2w", np.float32, 12), ("blas_root", np.uint32), ("tri_offset", np.uint32),
+                        ("pad_a", np.float32), ("pad_b", np.float32), ("mesh_slot", np.uint32), ("prim_base", np.uint32),
+                        ("flags", np.uint32), ("_pad", np.uint32)])
 OP_NONE, OP_SLOW_BUILD, OP_FAST_BUILD, OP_UPDATE = 0, 1, 2, 3
 
 

@@ -5,6 +5,7 @@
 #include <dlfcn.h>
 
 #include <cmath>
+#include <limits>
 
 #include <algorithm>
 #include <cstdio>
@@ -143,6 +144,12 @@ struct SrScene {
     std::vector<uint32_t> tl_baked_node_base, tl_baked_tri_base;
     uint64_t tl_blas_nodes = 0, tl_blas_tris = 0;
     DeviceBuffer d_blas_nodes, d_tl_inst, d_tl_instances;
+    // top level built on the device (bvh_gpu.hip srk_tl_*): per-mesh rows the record kernel reads, the instance boxes, its result block
+    DeviceBuffer d_tl_mesh_rows, d_tl_boxes, d_tl_result;
+    bool tl_mesh_rows_current = false;      // d_tl_mesh_rows matches the concatenated mesh trees on the device
+    int tl_build_mode = SR_TL_BUILD_AUTO;   // sr_scene_set_top_level_build / SR_TL_BUILD in the environment
+    SrTopLevelInfo tl_info{};               // of the last top-level build
+    std::vector<float> tl_boxes_host;       // the instance boxes of a host-built top level (sr_scene_read_top_level)
     int instancing = SR_INSTANCING_AUTO;    // sr_scene_set_instancing / SR_INSTANCING in the environment
     bool two_level = false;                 // form of the structure that is built right now
     // acceleration-structure maintenance (update in place): per-level node lists, exact node boxes, flatten inputs
@@ -256,6 +263,7 @@ int sr_scene_create(int device, SrScene** out) {
     s->device = device;
     if (const char* ev = getenv("SR_TILE_SCHEDULING")) s->tile_scheduling = atoi(ev) != 0;
     if (const char* ev = getenv("SR_INSTANCING")) s->instancing = !strcmp(ev, "two_level") ? SR_INSTANCING_TWO_LEVEL : (!strcmp(ev, "flat") ? SR_INSTANCING_FLAT : SR_INSTANCING_AUTO);
+    if (const char* ev = getenv("SR_TL_BUILD")) s->tl_build_mode = !strcmp(ev, "host") ? SR_TL_BUILD_HOST : (!strcmp(ev, "device") ? SR_TL_BUILD_DEVICE : SR_TL_BUILD_AUTO);
     if (const char* ev = getenv("SR_FAST_BUILD")) s->fast_build_ploc = !strcmp(ev, "lbvh") ? 0 : (!strncmp(ev, "ploc", 4) && atoi(ev + 4) > 0 ? atoi(ev + 4) : 16);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cus = prop.multiProcessorCount;
@@ -278,6 +286,7 @@ int sr_scene_destroy(SrScene* s) {
     s->d_nodes.release(); s->d_tris.release(); s->d_shade.release(); s->d_mesh_const.release(); s->d_slot_of_gid.release(); s->d_instances.release();
     s->d_lights.release(); s->d_misc.release();
     s->d_blas_nodes.release(); s->d_tl_inst.release(); s->d_tl_instances.release();
+    s->d_tl_mesh_rows.release(); s->d_tl_boxes.release(); s->d_tl_result.release();
     for (auto& ts : s->schedules) { ts.cost.release(); ts.order.release(); }
     for (auto& pool : s->events) for (auto& e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     delete s;
@@ -676,13 +685,150 @@ struct BlasCat {
     }
 };
 
-int two_level_build(SrScene* s) {
+// Every live mesh's records, one after the other (cached on the host per mesh), then the baked copies of the instance list at hand.
+int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
+    int rc;
+    const size_t nm = s->meshes.size();
+    BlasCat cat;
+    for (size_t m = 0; m < nm; m++) {
+        if (s->meshes[m].n_vertices == 0) continue;
+        if (!s->blases[m].valid) { s->blases[m] = SrScene::HostBlas(); if ((rc = build_blas(s->meshes[m], (uint32_t)m, nullptr, s->blases[m])) != SR_OK) return rc; }
+        cat.textured = cat.textured || !s->blases[m].shade_tex.empty();
+    }
+    s->blas_node_base.assign(nm, 0u); s->blas_tri_base.assign(nm, 0u);
+    for (size_t m = 0; m < nm; m++) if (s->meshes[m].n_vertices) cat.append(s->blases[m], &s->blas_node_base[m], &s->blas_tri_base[m]);
+    s->tl_baked_node_base.assign(baked.size(), 0u); s->tl_baked_tri_base.assign(baked.size(), 0u);
+    for (size_t k = 0; k < baked.size(); k++) cat.append(baked[k], &s->tl_baked_node_base[k], &s->tl_baked_tri_base[k]);
+    if (cat.tris.size() / 12 >= (1ull << 28) || cat.nodes.size() / srl::kNodeDwords >= (1ull << 31)) return fail(SR_ERR_UNSUPPORTED, "the meshes together exceed 2^28 triangles (leaf reference encoding)");
+    if (cat.textured) cat.shade_tex.resize(cat.tris.size() / 12 * 24, 0.0f);
+    if (cat.slot_of_prim.empty()) cat.slot_of_prim.push_back(0u);
+    HIP_TRY(hipDeviceSynchronize());
+    if ((rc = s->d_blas_nodes.upload(cat.nodes.data(), cat.nodes.size() * 4)) != SR_OK) return rc;
+    if ((rc = s->d_tris.upload(cat.tris.data(), cat.tris.size() * 4)) != SR_OK) return rc;
+    if ((rc = s->d_shade.upload(cat.shade.data(), cat.shade.size() * 4)) != SR_OK) return rc;
+    if (cat.textured) { if ((rc = s->d_shade_tex.upload(cat.shade_tex.data(), cat.shade_tex.size() * 4)) != SR_OK) return rc; }
+    else s->d_shade_tex.release();
+    if ((rc = s->d_slot_of_gid.upload(cat.slot_of_prim.data(), cat.slot_of_prim.size() * 4)) != SR_OK) return rc;
+    s->any_textured_tl = cat.textured;
+    s->tl_blas_nodes = cat.nodes.size() / srl::kNodeDwords; s->tl_blas_tris = cat.tris.size() / 12;
+    s->blas_device_current = true;
+    s->tl_baked = !baked.empty();
+    s->tl_mesh_rows_current = false;
+    return SR_OK;
+}
+
+// Instance boxes from which SR_TL_BUILD_AUTO builds the top level on the device: the smallest measured instance count at which
+// the device build beats the host's by more than the spread of 20 calls, rounded up to a power of two. Measured on an MI355X
+// (scripts/gpu_top_level_build.py -> profiles/top_level_build.json, table in DESIGN.md section 4), sr_scene_set_instances in ms,
+// host / device: 1 000: 0.66 / 1.83, 2 048: 1.36 / 2.07, 4 096: 2.51 / 2.30, 10 000: 6.19 / 2.71, 100 000: 60 / 5.6.
+constexpr uint32_t kTlDeviceMinBoxes = 4096;
+static_assert(sizeof(SrTopLevelInfo) == 64 && sizeof(srd::TlMeshRow) == 48 && sizeof(srd::DevTlInstance) == 128, "layouts the harness and the record kernel rely on");
+
+// The changed instance list of a scene that is already built in the two-level form, on the device (bvh_gpu.hip): instance
+// records and padded boxes by srk_tl_records (the bytes of the host loop in two_level_build), the tree over the boxes by
+// srk_tl_build. *reason stays SR_TL_ON_DEVICE when the build is done; any other value: the host build below does the whole
+// job (what this function has rewritten by then, it rewrote after the device-wide wait, and the host build writes it again).
+int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0, uint32_t* reason) {
+    const uint32_t ni = (uint32_t)s->fid.instances.size();
+    if (!s->built || !s->two_level || !s->blas_device_current) { *reason = SR_TL_HOST_NOT_TWO_LEVEL; return SR_OK; }   // also: meshes added or removed since
+    if (s->tl_build_mode == SR_TL_BUILD_HOST) { *reason = SR_TL_HOST_MODE; return SR_OK; }
+    if (ni < 2) { *reason = SR_TL_HOST_TOO_FEW; return SR_OK; }
+    if (s->tl_build_mode == SR_TL_BUILD_AUTO && ni < kTlDeviceMinBoxes) { *reason = SR_TL_HOST_BELOW_THRESHOLD; return SR_OK; }
+    int rc;
+    HIP_TRY(hipDeviceSynchronize());          // frames in flight read the tables that are rewritten from here on
+    if (s->tl_baked && (rc = upload_mesh_trees(s, {})) != SR_OK) return rc;   // the previous list had baked copies behind the mesh trees
+    if (!s->tl_mesh_rows_current) {
+        std::vector<srd::TlMeshRow> rows(s->meshes.size() ? s->meshes.size() : 1);
+        memset(rows.data(), 0, rows.size() * sizeof(srd::TlMeshRow));
+        for (size_t m = 0; m < s->meshes.size(); m++) {
+            if (s->meshes[m].n_vertices == 0 || !s->blases[m].valid) continue;
+            const SrScene::HostBlas& b = s->blases[m];
+            srd::TlMeshRow& r = rows[m];
+            memcpy(r.lo, b.lo, 12); memcpy(r.hi, b.hi, 12);
+            r.max_abs_vertex = b.max_abs_vertex; r.max_edge_sum = b.max_edge_sum;
+            r.max_stack = b.max_stack; r.blas_root = s->blas_node_base[m]; r.prim_base = s->blas_tri_base[m]; r.n_tris = b.n_tris;
+        }
+        if ((rc = s->d_tl_mesh_rows.upload(rows.data(), rows.size() * sizeof(srd::TlMeshRow))) != SR_OK) return rc;
+        s->tl_mesh_rows_current = true;
+    }
+    if ((rc = upload_instance_tables(s)) != SR_OK) return rc;
+    if ((rc = s->d_tl_instances.reserve((size_t)ni * sizeof(srd::DevTlInstance))) != SR_OK || (rc = s->d_tl_boxes.reserve((size_t)ni * 24)) != SR_OK ||
+        (rc = s->d_tl_result.reserve(16)) != SR_OK) return rc;
+    int e = srk_tl_records((const srd::FlatInstance*)s->d_flat_instances.p, (const srd::TlMeshRow*)s->d_tl_mesh_rows.p, ni, kTlMaxCondition,
+                           (srd::DevTlInstance*)s->d_tl_instances.p, (float*)s->d_tl_boxes.p, (uint32_t*)s->d_tl_result.p, nullptr);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("instance record launch failed: ") + hipGetErrorString((hipError_t)e));
+    uint32_t res[3] = {0, 0, 0};              // instances the host would bake, deepest mesh tree in use, instances with a box
+    HIP_TRY(hipMemcpy(res, s->d_tl_result.p, sizeof(res), hipMemcpyDeviceToHost));
+    const auto t1 = std::chrono::steady_clock::now();
+    const uint32_t nb = res[2], blas_stack = res[1];
+    if (res[0] != 0) { *reason = SR_TL_HOST_BAKED_INSTANCE; return SR_OK; }
+    if (nb < 2) { *reason = SR_TL_HOST_TOO_FEW; return SR_OK; }
+    if (s->tl_build_mode == SR_TL_BUILD_AUTO && nb < kTlDeviceMinBoxes) { *reason = SR_TL_HOST_BELOW_THRESHOLD; return SR_OK; }
+    const uint32_t left = kTlStackCap > blas_stack + srl::kLeafMax + 1u ? kTlStackCap - blas_stack - srl::kLeafMax - 1u : 0u;
+    if (left < min_depth_for(nb)) { *reason = SR_TL_HOST_STACK_BUDGET; return SR_OK; }      // the host build reports the error
+    const uint32_t node_cap = nb + 64;        // inner nodes of a tree with >= 2 children per node and >= 1 box per leaf: < nb
+    if ((rc = s->d_nodes.reserve((size_t)node_cap * srl::kNodeBytes)) != SR_OK || (rc = s->d_node_box.reserve((size_t)node_cap * 24)) != SR_OK ||
+        (rc = s->d_tl_inst.reserve((size_t)nb * 4)) != SR_OK || (rc = s->d_scratch.reserve(srk_tl_scratch_bytes(ni, node_cap))) != SR_OK) return rc;
+    LbvhArgs a{};
+    a.n_instances = ni; a.boxes = (const float*)s->d_tl_boxes.p; a.n_boxes = nb; a.tl_inst = (uint32_t*)s->d_tl_inst.p;
+    a.nodes = (float4*)s->d_nodes.p; a.node_cap = node_cap; a.node_box = (float*)s->d_node_box.p;
+    a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
+    a.stack_floor = min_depth_for(nb); a.stack_cap = left;
+    a.ploc = s->fast_build_ploc;
+    LbvhResult r;
+    e = srk_tl_build(a, &r, nullptr);
+    if (e > 0) return fail(SR_ERR_HIP, std::string("device top-level build failed: ") + hipGetErrorString((hipError_t)e));
+    const uint32_t need = r.max_stack + srl::kLeafMax + blas_stack + 1u;     // as the host build counts it
+    if (e < 0 || need > kTlStackCap) { *reason = SR_TL_HOST_STACK_BUDGET; return SR_OK; }
+    const auto t2 = std::chrono::steady_clock::now();
+    s->blas_stack = blas_stack;
+    s->dev.nodes = (const float4*)s->d_nodes.p;
+    s->dev.blas_nodes = (const float4*)s->d_blas_nodes.p;
+    s->dev.tl_inst = (const uint32_t*)s->d_tl_inst.p;
+    s->dev.tl_instances = (const srd::DevTlInstance*)s->d_tl_instances.p;
+    s->dev.tris = (const float4*)s->d_tris.p;
+    s->dev.shade = (const float4*)s->d_shade.p;
+    s->dev.shade_tex = (const float4*)s->d_shade_tex.p;
+    s->dev.slot_of_gid = (const uint32_t*)s->d_slot_of_gid.p;
+    s->dev.counters = (unsigned long long*)s->d_misc.p;
+    s->dev.n_tris = s->fid.n_triangles;
+    s->stats.n_triangles = s->fid.n_triangles;
+    s->stats.n_nodes = r.n_nodes + s->tl_blas_nodes;
+    s->stats.node_bytes = s->stats.n_nodes * srl::kNodeBytes;
+    s->stats.tri_bytes = s->tl_blas_tris * 48;
+    s->stats.max_depth = r.max_depth;
+    s->stats.max_stack = need;
+    s->stack_entries = (int)((std::max(need, 3u) + 1u + 3u) & ~3u);
+    s->stats.sah_cost = 0.0f;
+    s->stats.build_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
+    s->shape.clear();
+    s->built = true;
+    s->two_level = true;
+    s->last_build_on_device = true;
+    s->tl_boxes_host.clear();
+    SrTopLevelInfo& info = s->tl_info;
+    info.on_device = 1u; info.reason = SR_TL_ON_DEVICE;
+    info.n_nodes = r.n_nodes; info.n_boxes = nb; info.n_instances = ni; info.max_stack = r.max_stack; info.blas_stack = blas_stack;
+    info.records_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    info.tree_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    info.build_ms = s->stats.build_ms;
+    return SR_OK;
+}
+
+int two_level_build(SrScene* s, bool list_changed) {
     const auto t0 = std::chrono::steady_clock::now();
     int rc;
     const size_t nm = s->meshes.size();
     s->blases.resize(nm);
     bool any_textured = false;
     if ((rc = upload_mesh_tables(s, &any_textured)) != SR_OK) return rc;
+    // a changed list of a scene that stands in this form: records, boxes and tree on the device where that path can take it
+    uint32_t host_reason = SR_TL_HOST_QUALITY_BUILD;
+    if (list_changed) {
+        host_reason = SR_TL_ON_DEVICE;
+        if ((rc = top_level_build_device(s, t0, &host_reason)) != SR_OK) return rc;
+        if (host_reason == SR_TL_ON_DEVICE) return SR_OK;
+    }
     // instance records + padded world-space boxes
     const size_t ni = s->fid.instances.size();
     std::vector<srd::DevTlInstance> recs(ni ? ni : 1);
@@ -765,33 +911,9 @@ int two_level_build(SrScene* s) {
         boxes.push_back(bx);
         box_inst.push_back((uint32_t)i);
     }
-    // every live mesh's records, one after the other (cached on the host per mesh), then the baked copies of this instance list
     const bool had_baked = s->tl_baked;
     if (!s->blas_device_current || !s->two_level || had_baked || !baked.empty()) {
-        BlasCat cat;
-        for (size_t m = 0; m < nm; m++) {
-            if (s->meshes[m].n_vertices == 0) continue;
-            if (!s->blases[m].valid) { s->blases[m] = SrScene::HostBlas(); if ((rc = build_blas(s->meshes[m], (uint32_t)m, nullptr, s->blases[m])) != SR_OK) return rc; }
-            cat.textured = cat.textured || !s->blases[m].shade_tex.empty();
-        }
-        s->blas_node_base.assign(nm, 0u); s->blas_tri_base.assign(nm, 0u);
-        for (size_t m = 0; m < nm; m++) if (s->meshes[m].n_vertices) cat.append(s->blases[m], &s->blas_node_base[m], &s->blas_tri_base[m]);
-        s->tl_baked_node_base.assign(baked.size(), 0u); s->tl_baked_tri_base.assign(baked.size(), 0u);
-        for (size_t k = 0; k < baked.size(); k++) cat.append(baked[k], &s->tl_baked_node_base[k], &s->tl_baked_tri_base[k]);
-        if (cat.tris.size() / 12 >= (1ull << 28) || cat.nodes.size() / srl::kNodeDwords >= (1ull << 31)) return fail(SR_ERR_UNSUPPORTED, "the meshes together exceed 2^28 triangles (leaf reference encoding)");
-        if (cat.textured) cat.shade_tex.resize(cat.tris.size() / 12 * 24, 0.0f);
-        if (cat.slot_of_prim.empty()) cat.slot_of_prim.push_back(0u);
-        HIP_TRY(hipDeviceSynchronize());
-        if ((rc = s->d_blas_nodes.upload(cat.nodes.data(), cat.nodes.size() * 4)) != SR_OK) return rc;
-        if ((rc = s->d_tris.upload(cat.tris.data(), cat.tris.size() * 4)) != SR_OK) return rc;
-        if ((rc = s->d_shade.upload(cat.shade.data(), cat.shade.size() * 4)) != SR_OK) return rc;
-        if (cat.textured) { if ((rc = s->d_shade_tex.upload(cat.shade_tex.data(), cat.shade_tex.size() * 4)) != SR_OK) return rc; }
-        else s->d_shade_tex.release();
-        if ((rc = s->d_slot_of_gid.upload(cat.slot_of_prim.data(), cat.slot_of_prim.size() * 4)) != SR_OK) return rc;
-        s->any_textured_tl = cat.textured;
-        s->tl_blas_nodes = cat.nodes.size() / srl::kNodeDwords; s->tl_blas_tris = cat.tris.size() / 12;
-        s->blas_device_current = true;
-        s->tl_baked = !baked.empty();
+        if ((rc = upload_mesh_trees(s, baked)) != SR_OK) return rc;
     }
     for (size_t i = 0; i < ni; i++) {
         srd::DevTlInstance& r = recs[i];
@@ -804,6 +926,7 @@ int two_level_build(SrScene* s) {
     // the stack budget of the top-level tree is what the deepest mesh tree leaves of the walk's LDS stack
     const uint32_t left = kTlStackCap > s->blas_stack + srl::kLeafMax + 1u ? kTlStackCap - s->blas_stack - srl::kLeafMax - 1u : 0u;
     if (left < min_depth_for(boxes.size())) return fail(SR_ERR_UNSUPPORTED, "two-level structure: instance count and mesh size together need a deeper traversal stack than the kernels provide");
+    const auto t1 = std::chrono::steady_clock::now();
     srh::BvhResult tl;
     srh::build_bvh_boxes(boxes, std::min(depth_for(boxes.size()), left), tl);
     std::vector<uint32_t> tl_inst(tl.order.size() ? tl.order.size() : 1, 0u);
@@ -838,6 +961,14 @@ int two_level_build(SrScene* s) {
     s->built = true;
     s->two_level = true;
     s->last_build_on_device = false;
+    s->tl_boxes_host.assign((ni ? ni : 1) * 6, std::numeric_limits<float>::quiet_NaN());
+    for (size_t k = 0; k < boxes.size(); k++) { memcpy(&s->tl_boxes_host[(size_t)box_inst[k] * 6], boxes[k].lo, 12); memcpy(&s->tl_boxes_host[(size_t)box_inst[k] * 6 + 3], boxes[k].hi, 12); }
+    SrTopLevelInfo& info = s->tl_info;
+    info.on_device = 0u; info.reason = host_reason;
+    info.n_nodes = tl.n_nodes; info.n_boxes = (uint32_t)boxes.size(); info.n_instances = (uint32_t)ni; info.max_stack = tl.max_stack; info.blas_stack = s->blas_stack;
+    info.records_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    info.tree_ms = tl.build_ms;
+    info.build_ms = s->stats.build_ms;
     return SR_OK;
 }
 
@@ -949,7 +1080,7 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
         const uint32_t op = s->built_once ? SR_OP_FAST_BUILD : SR_OP_SLOW_BUILD;
         s->forced_op = SR_OP_NONE;
         if (!s->two_level) s->built = false;
-        rc = two_level_build(s);
+        rc = two_level_build(s, true);
         if (rc != SR_OK) { s->built = false; return rc; }
         if (s->built_once) srh::as_state_mark_built(s->as_state, op);
         s->built_once = true;
@@ -988,7 +1119,7 @@ int sr_scene_end_frame(SrScene* s) {
     if (op == SR_OP_SLOW_BUILD) {
         int rc = bind_device(s);
         if (rc != SR_OK) return rc;
-        if ((rc = s->two_level ? two_level_build(s) : full_build(s)) != SR_OK) { s->built = false; return rc; }
+        if ((rc = s->two_level ? two_level_build(s, false) : full_build(s)) != SR_OK) { s->built = false; return rc; }
     }
     srh::as_state_mark_built(s->as_state, op);
     s->last_op = op;
@@ -1004,6 +1135,39 @@ int sr_scene_instancing(const SrScene* s, uint32_t* mode, uint32_t* two_level_no
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_instancing: scene is null");
     if (mode) *mode = (uint32_t)s->instancing;
     if (two_level_now) *two_level_now = (s->built && s->two_level) ? 1u : 0u;
+    return SR_OK;
+}
+
+int sr_scene_set_top_level_build(SrScene* s, uint32_t mode) {
+    if (!s || mode > SR_TL_BUILD_DEVICE) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_top_level_build: bad argument");
+    s->tl_build_mode = (int)mode;
+    return SR_OK;
+}
+int sr_scene_top_level_info(const SrScene* s, SrTopLevelInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_top_level_info: null argument");
+    *out = s->tl_info;
+    out->mode = (uint32_t)s->tl_build_mode;
+    out->auto_threshold = kTlDeviceMinBoxes;
+    if (!(s->built && s->two_level)) {       // nothing stands in the two-level form: the figures of an earlier build do not apply
+        const uint32_t mode = out->mode;
+        memset(out, 0, sizeof(*out));
+        out->mode = mode; out->auto_threshold = kTlDeviceMinBoxes; out->reason = SR_TL_HOST_NOT_TWO_LEVEL;
+    }
+    return SR_OK;
+}
+int sr_scene_read_top_level(const SrScene* s, uint32_t* nodes, uint32_t* tl_inst, void* records, float* boxes) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_top_level: scene is null");
+    if (!s->built || !s->two_level) return fail(SR_ERR_STATE, "sr_scene_read_top_level: the scene is not built in the two-level form");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    const SrTopLevelInfo& info = s->tl_info;
+    if (nodes && info.n_nodes) HIP_TRY(hipMemcpy(nodes, s->d_nodes.p, (size_t)info.n_nodes * srl::kNodeBytes, hipMemcpyDeviceToHost));
+    if (tl_inst && info.n_boxes) HIP_TRY(hipMemcpy(tl_inst, s->d_tl_inst.p, (size_t)info.n_boxes * 4, hipMemcpyDeviceToHost));
+    if (records && info.n_instances) HIP_TRY(hipMemcpy(records, s->d_tl_instances.p, (size_t)info.n_instances * sizeof(srd::DevTlInstance), hipMemcpyDeviceToHost));
+    if (boxes && info.n_instances) {
+        if (info.on_device) HIP_TRY(hipMemcpy(boxes, s->d_tl_boxes.p, (size_t)info.n_instances * 24, hipMemcpyDeviceToHost));
+        else memcpy(boxes, s->tl_boxes_host.data(), (size_t)info.n_instances * 24);
+    }
     return SR_OK;
 }
 

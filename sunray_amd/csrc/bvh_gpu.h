@@ -13,6 +13,12 @@ struct FlatInstance {   // 64 B: what flattening one instance needs
     float o2w[12];      // ObjectToWorld3x4, row-major (EntityTransform, rt_types.slang:101-103)
     uint32_t tri_offset, mesh_slot, _pad[2];
 };
+struct TlMeshRow {      // 48 B: what one instance record of the two-level form needs of its mesh's tree (by mesh slot)
+    float lo[3], hi[3]; // root box of the mesh's tree, object space (padded as the builder pads triangles)
+    float max_abs_vertex, max_edge_sum;
+    uint32_t max_stack, blas_root, prim_base, n_tris;
+};
+struct DevTlInstance;   // traverse.h
 }  // namespace srd
 
 int srk_launch_flatten_slots(float4* tris, const float4* shade, const SrMeshInfo* meshes, const srd::FlatInstance* instances, uint32_t n_tris,
@@ -28,6 +34,9 @@ struct LbvhArgs {
     void* scratch; size_t scratch_bytes;
     uint32_t stack_floor, stack_cap;                     // budget = max(stack_floor, binary height); fail above stack_cap
     int ploc;                                            // topology: 0 = binary radix tree (LBVH), r > 0 = PLOC with search radius r
+    // srk_tl_build only (the primitives are instance boxes; meshes .. slot_of_gid above are unused, n_tris is unused)
+    const float* boxes = nullptr; uint32_t n_boxes = 0;  // n_instances x 6 floats, n_boxes of them real (the others are NaN rows)
+    uint32_t* tl_inst = nullptr;                         // out: leaf order -> instance index, n_boxes entries
 };
 struct LbvhResult {
     uint32_t n_nodes = 0, max_stack = 0, max_depth = 0;
@@ -35,3 +44,11 @@ struct LbvhResult {
 };
 int srk_lbvh_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
 size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap);
+
+// Top level of the two-level form. srk_tl_records: DevTlInstance records and padded world boxes of all instances (the host loop
+// of two_level_build, same bytes); `result` (device, 3 dwords, zeroed by the call) receives: instances this path cannot take,
+// deepest mesh-tree stack, instances with a box. srk_tl_build: the builder above over those boxes; same return convention.
+int srk_tl_records(const srd::FlatInstance* instances, const srd::TlMeshRow* meshes, uint32_t n_instances, double max_condition,
+                   srd::DevTlInstance* records, float* boxes, uint32_t* result, hipStream_t stream);
+int srk_tl_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
+size_t srk_tl_scratch_bytes(uint32_t n_instances, uint32_t node_cap);

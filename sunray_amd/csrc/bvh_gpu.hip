@@ -15,6 +15,7 @@
 
 #include "bvh_gpu.h"
 #include "bvh_layout.h"
+#include "traverse.h"
 
 namespace srd {
 
@@ -63,13 +64,30 @@ __device__ __forceinline__ void tri_box(const float4* tris, uint32_t slot, float
     }
 }
 
-// One thread per node of one tree level (deepest level first): child boxes from the triangles (leaf children) or
+// What the builder's stages bound a primitive by: the padded box of a triangle record, or one of the instance boxes of a
+// top-level tree (`map` takes the stage's index to the box: leaf position -> instance in the refit, null where the stage
+// already holds the instance index).
+struct TriPrims {
+    const float4* tris;
+    __device__ __forceinline__ void add(uint32_t i, float lo[3], float hi[3]) const { tri_box(tris, i, lo, hi); }
+};
+struct BoxPrims {
+    const float* boxes;      // 6 floats per instance: lo, hi (a NaN row: the instance has no box)
+    const uint32_t* map;
+    __device__ __forceinline__ void add(uint32_t i, float lo[3], float hi[3]) const {
+        const float* b = boxes + (size_t)(map ? map[i] : i) * 6;
+        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], b[a]); hi[a] = fmaxf(hi[a], b[3 + a]); }
+    }
+};
+
+// One thread per node of one tree level (deepest level first): child boxes from the primitives (leaf children) or
 // from the already refitted child nodes (node_box), then the same quantisation the host collapser applies
 // (bvh_build.cpp Collapser::emit): origin = node min, per-axis power-of-two grid, planes rounded outward and
 // verified with the decode expression fmaf(q, 2^e, origin).
 constexpr double kGuardCells = 1.0 / 32.0;   // guard band around every quantised plane (see bvh_build.cpp, traverse.h)
 
-__global__ void refit_level_kernel(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, uint32_t first, uint32_t count) {
+template <class Prims>
+__global__ void refit_level_kernel(uint32_t* nodes, const Prims prims, float* node_box, const uint32_t* level_nodes, uint32_t first, uint32_t count) {
     constexpr int W = srl::kBvhWidth;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
@@ -89,7 +107,7 @@ __global__ void refit_level_kernel(uint32_t* nodes, const float4* tris, float* n
             real[c] = lo[c][0] <= hi[c][0];
         } else {
             const uint32_t v = ~(uint32_t)ref, t0 = v >> 3, cnt = v & 7u;
-            for (uint32_t t = 0; t < cnt; t++) tri_box(tris, t0 + t, lo[c], hi[c]);
+            for (uint32_t t = 0; t < cnt; t++) prims.add(t0 + t, lo[c], hi[c]);
             real[c] = cnt != 0u;
         }
         if (!real[c]) continue;
@@ -258,7 +276,8 @@ __global__ void lbvh_hierarchy_kernel(const unsigned long long* keys, int n, int
 
 // Bottom-up fit: boxes of the radix nodes and the stack height of a purely binary walk below each (0 for subtrees that
 // will become leaves), second arriver at a node continues (the first one's writes are visible after the fence).
-__global__ void lbvh_fit_kernel(const float4* W, const uint32_t* sorted_gid, int n, const int2* children, const uint32_t* parent_of_inner,
+template <class Prims>
+__global__ void lbvh_fit_kernel(const Prims prims, const uint32_t* sorted_gid, int n, const int2* children, const uint32_t* parent_of_inner,
                                 const uint32_t* parent_of_leaf, const uint2* range, float* bin_box, uint32_t* bin_height, uint32_t* bin_size,
                                 uint32_t* flags) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -273,7 +292,7 @@ __global__ void lbvh_fit_kernel(const float4* W, const uint32_t* sorted_gid, int
         uint32_t h = 0;
         const int cc[2] = {ch.x, ch.y};
         for (int c = 0; c < 2; c++) {
-            if (cc[c] < 0) tri_box(W, sorted_gid[~cc[c]], lo, hi);
+            if (cc[c] < 0) prims.add(sorted_gid[~cc[c]], lo, hi);
             else {
                 const volatile float* b = bin_box + (size_t)cc[c] * 6;
                 for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], b[a]); hi[a] = fmaxf(hi[a], b[3 + a]); }
@@ -407,29 +426,37 @@ __global__ void lbvh_leaves_kernel(const float4* W, const float4* cent, const ui
 // Build quality is close to the top-down SAH build at a small multiple of the radix tree's cost.
 // ---------------------------------------------------------------------------------------------------------------
 
-__global__ void ploc_init_kernel(const float4* W, const uint32_t* sorted_gid, uint32_t n, int* cid, float* cbox) {
+template <class Prims>
+__global__ void ploc_init_kernel(const Prims prims, const uint32_t* sorted_gid, uint32_t n, int* cid, float* cbox) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    tri_box(W, sorted_gid[i], lo, hi);
+    prims.add(sorted_gid[i], lo, hi);
     cid[i] = ~(int)i;
     float* b = cbox + (size_t)i * 6;
     for (int a = 0; a < 3; a++) { b[a] = lo[a]; b[3 + a] = hi[a]; }
 }
 
+// SPREAD_TIES (instance boxes): among candidates of equal area the nearest one in the order wins, and of the two at the same
+// distance the partner i ^ 1. The rule is symmetric in (i, j), so the best pair overall is still mutual and every iteration
+// merges; coincident boxes then pair up (0,1), (2,3), ... and halve each iteration instead of merging one pair at a time.
+template <bool SPREAD_TIES>
 __global__ void ploc_nn_kernel(const float* cbox, uint32_t m, uint32_t radius, uint32_t* nn) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const float* b = cbox + (size_t)i * 6;
     const float lo[3] = {b[0], b[1], b[2]}, hi[3] = {b[3], b[4], b[5]};
     const uint32_t j0 = i > radius ? i - radius : 0u, j1 = min(m - 1u, i + radius);
-    float best = INFINITY; uint32_t best_j = i;
+    float best = INFINITY; uint32_t best_j = i, best_rank = 0xFFFFFFFFu;
     for (uint32_t j = j0; j <= j1; j++) {
         if (j == i) continue;
         const float* c = cbox + (size_t)j * 6;
         const float dx = fmaxf(hi[0], c[3]) - fminf(lo[0], c[0]), dy = fmaxf(hi[1], c[4]) - fminf(lo[1], c[1]), dz = fmaxf(hi[2], c[5]) - fminf(lo[2], c[2]);
         const float area = dx * dy + dy * dz + dz * dx;
-        if (area < best) { best = area; best_j = j; }        // ties: the lower index (scan order)
+        if (SPREAD_TIES) {
+            const uint32_t rank = 2u * (j > i ? j - i : i - j) + (j == (i ^ 1u) ? 0u : 1u);
+            if (area < best || (area == best && rank < best_rank)) { best = area; best_j = j; best_rank = rank; }
+        } else if (area < best) { best = area; best_j = j; }        // ties: the lower index (scan order)
     }
     nn[i] = best_j;
 }
@@ -465,6 +492,129 @@ __global__ void ploc_compact_kernel(const int* cid, const float* cbox, const uin
     for (int a = 0; a < 6; a++) cbox_out[(size_t)p * 6 + a] = cbox[(size_t)i * 6 + a];
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Top level of the two-level form on the device (the reference rebuilds its TLAS on the GPU every frame, tlas.rs:155-191):
+//   records    one thread per instance: the DevTlInstance record and the padded world box, with the expressions of the host
+//              loop (api.cpp two_level_build) in the same order — fp64 where the host uses double, std::max / std::min
+//              spelled as the comparisons they are — so the bytes equal the host's and the padding proof of DESIGN.md
+//              section 3 carries over unchanged
+//   tree       the builder above over the boxes instead of triangles: Morton code of the box centre (instances without a
+//              box sort behind all others and stay out of the tree), radix tree or PLOC, fit, collapse, tl_inst, refit
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double max_d(double a, double b) { return a < b ? b : a; }   // std::max
+__device__ __forceinline__ double min_d(double a, double b) { return b < a ? b : a; }   // std::min
+
+// result: [0] instances this path cannot take (the host would bake them, or the box is not finite), [1] deepest mesh-tree stack
+// among the instances with a box, [2] instances with a box
+__global__ void tl_records_kernel(const FlatInstance* instances, const TlMeshRow* meshes, uint32_t n_inst, double max_condition, DevTlInstance* recs,
+                                  float* boxes, uint32_t* result) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bad = 0, stack = 0, has_box = 0;
+    if (i < n_inst) {
+        const FlatInstance in = instances[i];
+        const TlMeshRow b = meshes[in.mesh_slot];
+        const float* M = in.o2w;
+        DevTlInstance r;
+        for (int k = 0; k < 12; k++) { r.w2o[k] = 0.0f; r.o2w[k] = M[k]; }
+        r.blas_root = 0u; r.tri_offset = in.tri_offset; r.pad_a = 0.0f; r.pad_b = 0.0f;
+        r.mesh_slot = in.mesh_slot; r.prim_base = 0u; r.flags = 0u; r._pad = 0u;
+        float bx[6];
+        for (int k = 0; k < 6; k++) bx[k] = __uint_as_float(0x7FC00000u);
+        if (b.n_tris != 0u) {
+            const double eps = 5.9604644775390625e-08;   // 2^-24
+            const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
+            const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+            const double det = a00 * c00 + a01 * c01 + a02 * c02;
+            const double id = 1.0 / det;
+            const double R[9] = {c00 * id, (a02 * a21 - a01 * a22) * id, (a01 * a12 - a02 * a11) * id,
+                                 c01 * id, (a00 * a22 - a02 * a20) * id, (a02 * a10 - a00 * a12) * id,
+                                 c02 * id, (a01 * a20 - a00 * a21) * id, (a00 * a11 - a01 * a10) * id};
+            const double T[3] = {M[3], M[7], M[11]};
+            double r_norm = 0.0, m_norm = 0.0, t_max = 0.0;
+            bool finite = isfinite(id) && det != 0.0;
+            for (int row = 0; row < 3; row++) {
+                for (int c = 0; c < 3; c++) r.w2o[4 * row + c] = (float)R[3 * row + c];
+                r.w2o[4 * row + 3] = (float)(-(R[3 * row] * T[0] + R[3 * row + 1] * T[1] + R[3 * row + 2] * T[2]));
+                r_norm = max_d(r_norm, fabs(R[3 * row]) + fabs(R[3 * row + 1]) + fabs(R[3 * row + 2]));
+                m_norm = max_d(m_norm, fabs((double)M[4 * row]) + fabs((double)M[4 * row + 1]) + fabs((double)M[4 * row + 2]));
+                t_max = max_d(t_max, fabs(T[row]));
+                for (int c = 0; c < 4; c++) finite = finite && isfinite(r.w2o[4 * row + c]);
+            }
+            if (!finite || !(r_norm * m_norm < max_condition)) bad = 1u;      // the host gives such an instance a baked copy of its mesh
+            else {
+                double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, p_max = 0.0;
+                for (int corner = 0; corner < 8; corner++) {
+                    const double x = (corner & 1) ? b.hi[0] : b.lo[0], y = (corner & 2) ? b.hi[1] : b.lo[1], z = (corner & 4) ? b.hi[2] : b.lo[2];
+                    for (int row = 0; row < 3; row++) {
+                        const double w = (double)M[4 * row] * x + (double)M[4 * row + 1] * y + (double)M[4 * row + 2] * z + (double)M[4 * row + 3];
+                        lo[row] = min_d(lo[row], w); hi[row] = max_d(hi[row], w);
+                        p_max = max_d(p_max, fabs(w));
+                    }
+                }
+                const double pad_w = 64.0 * eps * (p_max + m_norm * b.max_abs_vertex + t_max) + 8e-6 * m_norm * b.max_edge_sum;
+                bool box_ok = true;
+                for (int a = 0; a < 3; a++) {
+                    bx[a] = nextafterf((float)(lo[a] - pad_w), -INFINITY); bx[3 + a] = nextafterf((float)(hi[a] + pad_w), INFINITY);
+                    box_ok = box_ok && isfinite(bx[a]) && isfinite(bx[3 + a]);
+                }
+                r.pad_a = (float)(64.0 * eps * r_norm);
+                r.pad_b = (float)(r_norm * (64.0 * eps * (p_max + t_max + m_norm * b.max_abs_vertex) + 8e-6 * m_norm * b.max_edge_sum));
+                r.blas_root = b.blas_root; r.prim_base = b.prim_base;
+                if (box_ok) { has_box = 1u; stack = b.max_stack; } else bad = 1u;
+            }
+        } else { r.blas_root = b.blas_root; r.prim_base = b.prim_base; }
+        recs[i] = r;
+        for (int k = 0; k < 6; k++) boxes[(size_t)i * 6 + k] = bx[k];
+    }
+    for (int o = 32; o > 0; o >>= 1) { bad += __shfl_xor(bad, o); has_box += __shfl_xor(has_box, o); stack = max(stack, __shfl_xor(stack, o)); }
+    if ((threadIdx.x & 63) == 0) {
+        if (bad) atomicAdd(result + 0, bad);
+        if (stack) atomicMax(result + 1, stack);
+        if (has_box) atomicAdd(result + 2, has_box);
+    }
+}
+
+__global__ void tl_bounds_kernel(const float* boxes, uint32_t n, uint32_t* bounds_enc) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (i < n) BoxPrims{boxes, nullptr}.add(i, lo, hi);            // fminf / fmaxf drop the NaN rows
+    for (int a = 0; a < 3; a++) {
+        float l = lo[a], h = hi[a];
+        for (int o = 32; o > 0; o >>= 1) { l = fminf(l, __shfl_xor(l, o)); h = fmaxf(h, __shfl_xor(h, o)); }
+        if ((threadIdx.x & 63) == 0) {
+            if (l <= h) { atomicMin(bounds_enc + a, enc_f(l)); atomicMax(bounds_enc + 3 + a, enc_f(h)); }
+        }
+    }
+}
+
+// Centre of the box as the host's build_bvh_boxes takes it; an instance without a box gets the largest key.
+__global__ void tl_morton_kernel(const float* boxes, const uint32_t* bounds_enc, uint32_t n, unsigned long long* keys, uint32_t* vals) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* b = boxes + (size_t)i * 6;
+    unsigned long long key = 0xFFFFFFFFFFFFFFFFull;
+    if (b[0] <= b[3]) {
+        uint32_t q[3];
+        for (int a = 0; a < 3; a++) {
+            const float lo = dec_f(bounds_enc[a]), hi = dec_f(bounds_enc[3 + a]);
+            const float ext = hi - lo;
+            float t = ext > 0.0f ? ((0.5f * b[a] + 0.5f * b[3 + a]) - lo) / ext : 0.0f;
+            t = fminf(fmaxf(t, 0.0f), 1.0f);
+            q[a] = min((uint32_t)(t * 2097152.0f), 2097151u);
+        }
+        key = spread21(q[0]) | (spread21(q[1]) << 1) | (spread21(q[2]) << 2);
+    }
+    keys[i] = key;
+    vals[i] = i;
+}
+
+// Leaf order -> instance index (the slot was assigned by the collapse).
+__global__ void tl_leaves_kernel(const uint32_t* sorted_gid, const uint32_t* slot_of_sorted, uint32_t n, uint32_t* tl_inst) {
+    const uint32_t s_idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s_idx >= n) return;
+    tl_inst[slot_of_sorted[s_idx]] = sorted_gid[s_idx];
+}
+
 }  // namespace srd
 
 using namespace srd;
@@ -480,26 +630,32 @@ int srk_launch_refit(uint32_t* nodes, const float4* tris, float* node_box, const
     for (uint32_t l = 0; l < n_levels; l++) {     // level_offsets_host[l] .. [l+1]: deepest level first
         const uint32_t first = level_offsets_host[l], count = level_offsets_host[l + 1] - first;
         if (count == 0) continue;
-        refit_level_kernel<<<dim3((count + 63) / 64), dim3(64), 0, stream>>>(nodes, tris, node_box, level_nodes, first, count);
+        refit_level_kernel<<<dim3((count + 63) / 64), dim3(64), 0, stream>>>(nodes, TriPrims{tris}, node_box, level_nodes, first, count);
     }
     return (int)hipGetLastError();
 }
 
 // Device LBVH build. All outputs are device buffers owned by the caller; `scratch` is reused across builds. Returns 0, a
 // hipError_t (> 0), or -1 when the tree does not fit the limits (caller falls back to the host builder).
-int srk_lbvh_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
-    const uint32_t n = a.n_tris;
+// BOXES: the primitives are the instance boxes of a top-level tree (srk_tl_build) instead of the instances' triangles: all
+// n_instances rows are keyed and sorted, the n_boxes real ones come first and are the tree's primitives.
+template <bool BOXES>
+static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
+    const uint32_t n_keys = BOXES ? a.n_instances : a.n_tris;   // sorted items
+    const uint32_t n = BOXES ? a.n_boxes : a.n_tris;             // primitives of the tree
+    if (BOXES && (n < 2 || n > n_keys)) return -1;
     const int B = 256;
-    const dim3 gt((n + B - 1) / B), bt(B);
+    const dim3 gk((n_keys + B - 1) / B), gt((n + B - 1) / B), bt(B);
+    const int sort_bits = BOXES ? 64 : 63;                       // the key of an instance without a box has every bit set
     // carve the scratch slab
     size_t off = 0;
     auto take = [&](size_t bytes) { void* p = (char*)a.scratch + off; off += (bytes + 255) & ~(size_t)255; return p; };
-    float4* W = (float4*)take((size_t)n * 48);
-    float4* cent = (float4*)take((size_t)n * 16);
-    unsigned long long* keys_a = (unsigned long long*)take((size_t)n * 8);
-    unsigned long long* keys_b = (unsigned long long*)take((size_t)n * 8);
-    uint32_t* vals_a = (uint32_t*)take((size_t)n * 4);
-    uint32_t* vals_b = (uint32_t*)take((size_t)n * 4);
+    float4* W = BOXES ? nullptr : (float4*)take((size_t)n * 48);
+    float4* cent = BOXES ? nullptr : (float4*)take((size_t)n * 16);
+    unsigned long long* keys_a = (unsigned long long*)take((size_t)n_keys * 8);
+    unsigned long long* keys_b = (unsigned long long*)take((size_t)n_keys * 8);
+    uint32_t* vals_a = (uint32_t*)take((size_t)n_keys * 4);
+    uint32_t* vals_b = (uint32_t*)take((size_t)n_keys * 4);
     int2* children = (int2*)take((size_t)n * 8);
     uint2* range = (uint2*)take((size_t)n * 8);             // radix tree only; PLOC: nn | valid
     uint32_t* parent_inner = (uint32_t*)take((size_t)n * 4);   // radix tree only; PLOC: scan output
@@ -518,7 +674,7 @@ int srk_lbvh_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
     int* cid[2] = {nullptr, nullptr}; float* cbox[2] = {nullptr, nullptr};
     if (a.ploc) for (int k = 0; k < 2; k++) { cid[k] = (int*)take((size_t)n * 4); cbox[k] = (float*)take((size_t)n * 24); }
     size_t cub_bytes = 0, scan_bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, keys_a, keys_b, vals_a, vals_b, (int)n, 0, 63, stream);
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, keys_a, keys_b, vals_a, vals_b, (int)n_keys, 0, sort_bits, stream);
     if (e != hipSuccess) return (int)e;
     if (a.ploc && (e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, stream)) != hipSuccess) return (int)e;
     void* cub_tmp = take(cub_bytes > scan_bytes ? cub_bytes : scan_bytes);
@@ -526,25 +682,33 @@ int srk_lbvh_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
 
     const uint32_t init[16] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     if ((e = hipMemcpyAsync(small, init, sizeof(init), hipMemcpyHostToDevice, stream)) != hipSuccess) return (int)e;
-    lbvh_prims_kernel<<<gt, bt, 0, stream>>>(a.meshes, a.instances, a.n_instances, n, W, cent, small);
-    lbvh_morton_kernel<<<gt, bt, 0, stream>>>(cent, small, n, keys_a, vals_a);
-    if ((e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys_a, keys_b, vals_a, vals_b, (int)n, 0, 63, stream)) != hipSuccess) return (int)e;
+    if constexpr (BOXES) {
+        tl_bounds_kernel<<<gk, bt, 0, stream>>>(a.boxes, n_keys, small);
+        tl_morton_kernel<<<gk, bt, 0, stream>>>(a.boxes, small, n_keys, keys_a, vals_a);
+    } else {
+        lbvh_prims_kernel<<<gt, bt, 0, stream>>>(a.meshes, a.instances, a.n_instances, n, W, cent, small);
+        lbvh_morton_kernel<<<gt, bt, 0, stream>>>(cent, small, n, keys_a, vals_a);
+    }
+    if ((e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys_a, keys_b, vals_a, vals_b, (int)n_keys, 0, sort_bits, stream)) != hipSuccess) return (int)e;
+    // what a stage bounds a primitive by: `prims` by sorted value (triangle id / instance index), `leaf_prims` by leaf position
+    auto prims = [&] { if constexpr (BOXES) return BoxPrims{a.boxes, nullptr}; else return TriPrims{W}; }();
+    auto leaf_prims = [&] { if constexpr (BOXES) return BoxPrims{a.boxes, a.tl_inst}; else return TriPrims{a.tris}; }();
     int root_bin = 0;
     if (!a.ploc) {
         if ((e = hipMemsetAsync(flags, 0, (size_t)n * 4, stream)) != hipSuccess) return (int)e;
         lbvh_hierarchy_kernel<<<gt, bt, 0, stream>>>(keys_b, (int)n, children, parent_inner, parent_leaf, range);
-        lbvh_fit_kernel<<<gt, bt, 0, stream>>>(W, vals_b, (int)n, children, parent_inner, parent_leaf, range, bin_box, bin_height, bin_size, flags);
+        lbvh_fit_kernel<<<gt, bt, 0, stream>>>(prims, vals_b, (int)n, children, parent_inner, parent_leaf, range, bin_box, bin_height, bin_size, flags);
     } else {
         uint32_t* nn = (uint32_t*)range;
         uint32_t* valid = nn + n;
         uint32_t* pos = parent_inner;
         uint32_t* node_counter = small + 12;
-        ploc_init_kernel<<<gt, bt, 0, stream>>>(W, vals_b, n, cid[0], cbox[0]);
+        ploc_init_kernel<<<gt, bt, 0, stream>>>(prims, vals_b, n, cid[0], cbox[0]);
         uint32_t m = n;
         int cur = 0, guard = 0;
         while (m > 1) {
             const dim3 gm((m + B - 1) / B);
-            ploc_nn_kernel<<<gm, bt, 0, stream>>>(cbox[cur], m, (uint32_t)a.ploc, nn);
+            ploc_nn_kernel<BOXES><<<gm, bt, 0, stream>>>(cbox[cur], m, (uint32_t)a.ploc, nn);
             ploc_merge_kernel<<<gm, bt, 0, stream>>>(nn, m, cid[cur], cbox[cur], valid, children, bin_box, bin_size, bin_height, node_counter);
             if ((e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, scan_bytes, valid, pos, (int)m, stream)) != hipSuccess) return (int)e;
             ploc_compact_kernel<<<gm, bt, 0, stream>>>(cid[cur], cbox[cur], valid, pos, m, cid[cur ^ 1], cbox[cur ^ 1]);
@@ -591,13 +755,30 @@ int srk_lbvh_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
         if (out->level_ranges.size() > 128) return -1;
     }
     out->max_depth = (uint32_t)out->level_ranges.size();
-    lbvh_leaves_kernel<<<gt, bt, 0, stream>>>(W, cent, vals_b, slot_of_sorted, n, a.meshes, a.instances, a.tris, a.shade, a.shade_tex, a.slot_of_gid);
+    if constexpr (BOXES) tl_leaves_kernel<<<gt, bt, 0, stream>>>(vals_b, slot_of_sorted, n, a.tl_inst);
+    else lbvh_leaves_kernel<<<gt, bt, 0, stream>>>(W, cent, vals_b, slot_of_sorted, n, a.meshes, a.instances, a.tris, a.shade, a.shade_tex, a.slot_of_gid);
     for (size_t l = out->level_ranges.size(); l-- > 0;)
-        refit_level_kernel<<<dim3((out->level_ranges[l].second + 63) / 64), dim3(64), 0, stream>>>((uint32_t*)a.nodes, a.tris, a.node_box, nullptr,
+        refit_level_kernel<<<dim3((out->level_ranges[l].second + 63) / 64), dim3(64), 0, stream>>>((uint32_t*)a.nodes, leaf_prims, a.node_box, nullptr,
                                                                                                      out->level_ranges[l].first, out->level_ranges[l].second);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
     return 0;
+}
+
+int srk_lbvh_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<false>(a, out, stream); }
+int srk_tl_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<true>(a, out, stream); }
+
+int srk_tl_records(const FlatInstance* instances, const TlMeshRow* meshes, uint32_t n_instances, double max_condition, DevTlInstance* records,
+                   float* boxes, uint32_t* result, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(result, 0, 12, stream);
+    if (e != hipSuccess) return (int)e;
+    if (n_instances == 0) return 0;
+    tl_records_kernel<<<dim3((n_instances + 255) / 256), dim3(256), 0, stream>>>(instances, meshes, n_instances, max_condition, records, boxes, result);
+    return (int)hipGetLastError();
+}
+
+size_t srk_tl_scratch_bytes(uint32_t n_instances, uint32_t node_cap) {    // as below without the triangle records and centroids
+    return srk_lbvh_scratch_bytes(n_instances, node_cap) - (size_t)n_instances * (48 + 16);
 }
 
 size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap) {

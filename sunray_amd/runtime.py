@@ -252,6 +252,29 @@ class Scene:
         check(lib().sr_scene_instancing(self._h, None, C.byref(now)))
         return bool(now.value)
 
+    def set_top_level_build(self, mode):
+        """Where a changed instance list of a two-level scene gets its top-level tree: "auto" | "host" | "device"
+        (sr_scene_set_top_level_build)."""
+        check(lib().sr_scene_set_top_level_build(self._h, C.c_uint32({"auto": 0, "host": 1, "device": 2}[mode])))
+        return self
+
+    def top_level_info(self):
+        """-> abi.SrTopLevelInfo of the last top-level build (path taken, reason, counts, stack, milliseconds)."""
+        info = abi.SrTopLevelInfo()
+        check(lib().sr_scene_top_level_info(self._h, C.byref(info)))
+        return info
+
+    def read_top_level(self):
+        """-> (nodes [n_nodes, 16] uint32, tl_inst [n_boxes] uint32, records [n_instances] abi.TL_INSTANCE, boxes [n_instances, 6]
+        float32, a NaN row where the instance has no box) of a scene built in the two-level form."""
+        info = self.top_level_info()
+        nodes = np.zeros((max(info.n_nodes, 1), bvh_layout()[1]), dtype=np.uint32)
+        tl_inst = np.zeros(max(info.n_boxes, 1), dtype=np.uint32)
+        records = np.zeros(max(info.n_instances, 1), dtype=abi.TL_INSTANCE)
+        boxes = np.zeros((max(info.n_instances, 1), 6), dtype=np.float32)
+        check(lib().sr_scene_read_top_level(self._h, _p(nodes), _p(tl_inst), _p(records), _p(boxes)))
+        return nodes[:info.n_nodes], tl_inst[:info.n_boxes], records[:info.n_instances], boxes[:info.n_instances]
+
     def force_next_op(self, op):
         check(lib().sr_scene_force_next_op(self._h, C.c_uint32(op)))
 
