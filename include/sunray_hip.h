@@ -425,6 +425,32 @@ int sr_scene_add_blas(SrScene* scene, uint64_t key, const SrVertex* vertices, ui
 /* ResourceManager::remove (resource_manager.rs:459-487): frees the mesh-info slot and the emissive slots of
  * `key` (later loads reuse them LIFO, as the reference's arenas do). Unknown key: no-op. Waits for the device. */
 int sr_scene_remove(SrScene* scene, uint64_t key);
+/* Blas::update (acceleration_structure/blas.rs:285-310): new vertex contents (positions, normals, tangents, every uv set) for a
+ * loaded mesh — same key, same vertex count, same indices, same material. Validated before anything is touched (unknown key,
+ * another vertex count, a non-finite position: SR_ERR_INVALID_ARG and the scene is as it was). Replaces the host copy, copies
+ * into the mesh's existing device allocation (waits for the device) and rewrites the positions of its entries of the emissive
+ * table in their slots. The structure is not reset: several meshes may be updated, then ONE sr_scene_set_instances applies them
+ * all with the operation the heuristic picks (SR_OP_UPDATE re-flattens, rewrites the per-slot shading records and refits on
+ * the device; the builds read the new vertices anyway; in the two-level form only the updated meshes' trees are rebuilt, on the
+ * host). Between the update of a mesh that the built structure instances and that sr_scene_set_instances, the tracing calls,
+ * sr_scene_read_bvh and sr_scene_end_frame return SR_ERR_STATE. `vertices` is a HOST pointer. */
+int sr_scene_update_mesh(SrScene* scene, uint64_t key, const SrVertex* vertices, uint32_t n_vertices);
+/* Figures of the last sr_scene_update_mesh and of the sr_scene_set_instances that applied it. The kernel times are taken with
+ * events only while sr_scene_enable_timing is on (0 otherwise); the other times are host wall-clock milliseconds. */
+typedef struct SrMeshUpdateInfo {
+    uint32_t dirty_meshes;     /* meshes of the built structure that were updated and that the last sr_scene_set_instances applied */
+    uint32_t reshaded;         /* 1: its SR_OP_UPDATE ran the variant that rewrites the shading records */
+    uint32_t blas_rebuilt;     /* two-level form: per-mesh trees it built, i.e. the invalidated ones: every mesh updated since its tree
+                                * was built, instanced at the time or not (baked copies of single instances not counted) */
+    uint32_t _pad;
+    double validate_copy_ms;   /* sr_scene_update_mesh: validation + host copy + emissive entries */
+    double h2d_ms;             /* sr_scene_update_mesh: device wait + copy into the device allocation */
+    double tables_ms;          /* SR_OP_UPDATE: instance tables + light table, built and uploaded */
+    double flatten_ms;         /* SR_OP_UPDATE: flatten (+ reshade) kernel */
+    double refit_ms;           /* SR_OP_UPDATE: refit kernels, all levels */
+    double blas_build_ms;      /* two-level form: host builds of the per-mesh trees counted in blas_rebuilt */
+} SrMeshUpdateInfo;
+int sr_scene_mesh_update_info(const SrScene* scene, SrMeshUpdateInfo* out);
 
 /* Image::new_from_data (image/mod.rs:82-111): `channels` = 1..4 bytes per texel; fewer than 4 are
  * widened to R8G8B8A8_UNORM with the missing channels 0x00 (utils.rs:27-43), no sRGB decode. Host
@@ -647,9 +673,15 @@ int sr_loaded_scene_destroy(SrLoadedScene* loaded);
 /* Renderer::unload_scene (lib.rs:849-857) / unload_mesh (lib.rs:965-973). */
 int sr_renderer_unload_scene(SrRenderer* renderer, uint64_t group);
 int sr_renderer_unload_mesh(SrRenderer* renderer, uint64_t key);
+/* sr_scene_update_mesh on every device slot's scene; the next sr_renderer_render re-submits its instance list, which applies
+ * the update. Each scene waits for its device, so frames in flight have finished reading the old vertices before they change. */
+int sr_renderer_update_mesh(SrRenderer* renderer, uint64_t key, const SrVertex* vertices, uint32_t n_vertices);
 
 /* Harness access: inner scene (counters, stats), device pointers of the RGBA8 output and the fp32 radiance OF THE LAST
- * SUBMITTED FRAME (valid after sr_renderer_wait_frame of that frame), and relative_frame_count. Any out pointer may be NULL. */
+ * SUBMITTED FRAME (valid after sr_renderer_wait_frame of that frame), and relative_frame_count. Any out pointer may be NULL.
+ * Meshes of a renderer are updated through sr_renderer_update_mesh: after sr_scene_update_mesh on the inner scene the renderer
+ * does not know that its instance list must be re-submitted, and sr_renderer_render with an unchanged list returns SR_ERR_STATE
+ * (from sr_scene_end_frame). */
 int sr_renderer_get(SrRenderer* renderer, SrScene** scene, const uint32_t** output_rgba8_device,
                     const float** raw_color_device, uint32_t* relative_frame_count);
 /* Stand-in for the reference's embedded 128x128 blue-noise PNG (lib.rs:281-309; an input asset, not

@@ -27,6 +27,7 @@ SYMBOLS = [
     "sr_renderer_create_multi", "sr_renderer_set_strip_bounds", "sr_renderer_set_motion_halo", "sr_renderer_replica_scene",
     "sr_renderer_read_history_overflow",
     "sr_scene_set_top_level_build", "sr_scene_top_level_info", "sr_scene_read_top_level",
+    "sr_scene_update_mesh", "sr_scene_mesh_update_info", "sr_renderer_update_mesh",
 ]
 
 

@@ -154,6 +154,12 @@ class SrTopLevelInfo(C.Structure):  # the last top-level build of a two-level sc
                 ("build_ms", C.c_double)]
 
 
+class SrMeshUpdateInfo(C.Structure):  # the last sr_scene_update_mesh and the sr_scene_set_instances that applied it
+    _fields_ = [("dirty_meshes", C.c_uint32), ("reshaded", C.c_uint32), ("blas_rebuilt", C.c_uint32), ("_pad", C.c_uint32),
+                ("validate_copy_ms", C.c_double), ("h2d_ms", C.c_double), ("tables_ms", C.c_double), ("flatten_ms", C.c_double),
+                ("refit_ms", C.c_double), ("blas_build_ms", C.c_double)]
+
+
 TL_BUILD_AUTO, TL_BUILD_HOST, TL_BUILD_DEVICE = 0, 1, 2
 (TL_ON_DEVICE, TL_HOST_MODE, TL_HOST_BELOW_THRESHOLD, TL_HOST_BAKED_INSTANCE, TL_HOST_STACK_BUDGET, TL_HOST_NOT_TWO_LEVEL,
  TL_HOST_TOO_FEW, TL_HOST_QUALITY_BUILD) = range(8)

@@ -42,6 +42,9 @@ namespace {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                             \
     } while (0)
 
+// what the calls that read the structure answer between sr_scene_update_mesh and the sr_scene_set_instances that applies it
+const char* const kStaleGeometry = "a mesh of the built structure was updated: sr_scene_set_instances must follow sr_scene_update_mesh before this call";
+
 enum PassKind { kRis = 0, kFinal = 1, kClosest = 2, kAny = 3, kNumKinds = 4 };
 
 // Named profiler ranges around every pass, the counterpart of the debug-utils label the reference's render graph puts around
@@ -170,6 +173,11 @@ struct SrScene {
     SrBvhStats stats{};
     bool built = false;
     bool built_once = false;
+    // sr_scene_update_mesh: meshes (by slot) whose vertices changed since the structure last took them, and whether the built
+    // structure instances one of them (it then shows stale geometry until the next sr_scene_set_instances)
+    std::vector<char> mesh_dirty;
+    bool geometry_stale = false;
+    SrMeshUpdateInfo mu_info{};
     int instrumented = 0;
     int timing = 0;
     int n_cus = 256;
@@ -400,10 +408,74 @@ int sr_scene_remove(SrScene* s, uint64_t key) {
     for (uint32_t es : m.emissive_slots) s->free_emissive_slots.push_back(es);
     m = srh::HostMesh();
     if (slot < s->blases.size()) s->blases[slot] = SrScene::HostBlas();
+    if (slot < s->mesh_dirty.size()) s->mesh_dirty[slot] = 0;
     s->blas_device_current = false;
     s->free_mesh_slots.push_back(slot);
     s->slots.erase(it);
     s->built = false;
+    return SR_OK;
+}
+
+// Blas::update (blas.rs:285-310) for one mesh: the vertex contents change, everything that depends on the topology stays
+// (slot, indices, material, emissive slots, device allocations, the built structure and its AsState). What follows from the
+// vertices is brought up to date by the next sr_scene_set_instances; until then a structure that instances the mesh is stale.
+int sr_scene_update_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uint32_t n_vertices) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s || !vertices) return fail(SR_ERR_INVALID_ARG, "update_mesh: null argument");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "update_mesh: no mesh is registered under this key");
+    const uint32_t slot = it->second;
+    srh::HostMesh& m = s->meshes[slot];
+    if (n_vertices != m.n_vertices) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "update_mesh: %u vertices given, the mesh was loaded with %u (the vertex count cannot change)", n_vertices, m.n_vertices);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
+    for (uint32_t i = 0; i < n_vertices; i++)
+        if (!std::isfinite(vertices[i].position[0]) || !std::isfinite(vertices[i].position[1]) || !std::isfinite(vertices[i].position[2])) {
+            char buf[120];
+            snprintf(buf, sizeof(buf), "update_mesh: vertex %u has a non-finite position", i);
+            return fail(SR_ERR_INVALID_ARG, buf);
+        }
+    // the emissive entries are one per triangle in index order (load_mesh, the glTF path) or none; any other list came from
+    // the caller of sr_scene_add_blas and cannot be re-derived from vertices
+    if (!m.emissive_slots.empty() && m.emissive_slots.size() != m.n_indices / 3)
+        return fail(SR_ERR_UNSUPPORTED, "update_mesh: the mesh was loaded with emissive triangles that are not one per triangle");
+    int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    const auto t1 = std::chrono::steady_clock::now();
+    HIP_TRY(hipDeviceSynchronize());                          // launches in flight read the old vertices (as sr_scene_remove waits)
+    HIP_TRY(hipMemcpy(m.d_vertices, vertices, sizeof(SrVertex) * (size_t)n_vertices, hipMemcpyHostToDevice));
+    const auto t2 = std::chrono::steady_clock::now();
+    m.vertices.assign(vertices, vertices + n_vertices);
+    for (size_t k = 0; k < m.emissive_slots.size(); k++) {   // positions only: emission follows the material, which stays
+        SrEmissiveTriangle& et = s->emissive_tris[m.emissive_slots[k]];
+        memcpy(et.v0, m.vertices[m.indices[3 * k]].position, 12);
+        memcpy(et.v1, m.vertices[m.indices[3 * k + 1]].position, 12);
+        memcpy(et.v2, m.vertices[m.indices[3 * k + 2]].position, 12);
+    }
+    // two-level form: this mesh's object-space tree, root box and padding numbers are stale; the other meshes keep theirs
+    if (slot < s->blases.size()) s->blases[slot].valid = false;
+    s->blas_device_current = false;
+    s->tl_mesh_rows_current = false;
+    if (s->built) {
+        bool instanced = false;
+        for (const auto& in : s->fid.instances) if (in.mesh_slot == slot) { instanced = true; break; }
+        if (instanced) {
+            if (s->mesh_dirty.size() < s->meshes.size()) s->mesh_dirty.resize(s->meshes.size(), 0);
+            s->mesh_dirty[slot] = 1;
+            s->geometry_stale = true;
+        }
+    }
+    const auto t3 = std::chrono::steady_clock::now();
+    s->mu_info.validate_copy_ms = std::chrono::duration<double, std::milli>((t1 - t0) + (t3 - t2)).count();
+    s->mu_info.h2d_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    return SR_OK;
+}
+
+int sr_scene_mesh_update_info(const SrScene* s, SrMeshUpdateInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_update_info: null argument");
+    *out = s->mu_info;
     return SR_OK;
 }
 
@@ -546,18 +618,38 @@ int upload_mesh_tables(SrScene* s, bool* any_textured_out) {
 
 // OpType::Update: same instance layout, new transforms. The triangles are re-flattened on the device into their
 // existing leaf slots and the quantised nodes are refitted bottom-up; topology, shade records and mesh tables stay.
-int update_in_place(SrScene* s) {
+// With `reshade` (a mesh of the tree was updated, sr_scene_update_mesh) the flatten also rewrites the slots' shade / shade_tex
+// records from the new vertices; the light table follows the emissive arena through upload_instance_tables either way.
+int update_in_place(SrScene* s, bool reshade) {
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipDeviceSynchronize());
     int rc = upload_instance_tables(s);
     if (rc != SR_OK) return rc;
-    int e = srk_launch_flatten_slots((float4*)s->d_tris.p, (const float4*)s->d_shade.p, (const SrMeshInfo*)s->d_mesh_infos.p,
-                                     (const srd::FlatInstance*)s->d_flat_instances.p, s->fid.n_triangles, nullptr);
-    if (e != 0) return fail(SR_ERR_HIP, std::string("flatten launch failed: ") + hipGetErrorString((hipError_t)e));
-    e = srk_launch_refit((uint32_t*)s->d_nodes.p, (const float4*)s->d_tris.p, (float*)s->d_node_box.p, (const uint32_t*)s->d_level_nodes.p,
-                         s->level_offsets.data(), (uint32_t)s->level_offsets.size() - 1, nullptr);
-    if (e != 0) return fail(SR_ERR_HIP, std::string("refit launch failed: ") + hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipDeviceSynchronize());
+    s->mu_info.tables_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};           // kernel times, only while sr_scene_enable_timing is on
+    if (s->timing) for (auto& e_ : ev) if (hipEventCreate(&e_) != hipSuccess) e_ = nullptr;
+    const bool timed = ev[0] && ev[1] && ev[2];
+    if (timed) (void)hipEventRecord(ev[0], nullptr);
+    int e = reshade ? srk_launch_flatten_reshade((float4*)s->d_tris.p, (float4*)s->d_shade.p, (float4*)s->d_shade_tex.p, (const SrMeshInfo*)s->d_mesh_infos.p,
+                                                 (const srd::FlatInstance*)s->d_flat_instances.p, s->fid.n_triangles, nullptr)
+                    : srk_launch_flatten_slots((float4*)s->d_tris.p, (const float4*)s->d_shade.p, (const SrMeshInfo*)s->d_mesh_infos.p,
+                                               (const srd::FlatInstance*)s->d_flat_instances.p, s->fid.n_triangles, nullptr);
+    if (timed) (void)hipEventRecord(ev[1], nullptr);
+    if (e == 0) {
+        e = srk_launch_refit((uint32_t*)s->d_nodes.p, (const float4*)s->d_tris.p, (float*)s->d_node_box.p, (const uint32_t*)s->d_level_nodes.p,
+                             s->level_offsets.data(), (uint32_t)s->level_offsets.size() - 1, nullptr);
+        if (e != 0) fail(SR_ERR_HIP, std::string("refit launch failed: ") + hipGetErrorString((hipError_t)e));
+    } else fail(SR_ERR_HIP, std::string("flatten launch failed: ") + hipGetErrorString((hipError_t)e));
+    if (timed) (void)hipEventRecord(ev[2], nullptr);
+    const hipError_t se = hipDeviceSynchronize();
+    if (timed && e == 0 && se == hipSuccess) {
+        float a = 0.0f, b = 0.0f;
+        if (hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) { s->mu_info.flatten_ms = a; s->mu_info.refit_ms = b; }
+    }
+    for (auto& e_ : ev) if (e_) (void)hipEventDestroy(e_);
+    if (e != 0) return SR_ERR_HIP;
+    HIP_TRY(se);
+    s->mu_info.reshaded = reshade ? 1u : 0u;
     s->stats.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SR_OK;
 }
@@ -692,7 +784,7 @@ int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
     BlasCat cat;
     for (size_t m = 0; m < nm; m++) {
         if (s->meshes[m].n_vertices == 0) continue;
-        if (!s->blases[m].valid) { s->blases[m] = SrScene::HostBlas(); if ((rc = build_blas(s->meshes[m], (uint32_t)m, nullptr, s->blases[m])) != SR_OK) return rc; }
+        if (!s->blases[m].valid) { s->blases[m] = SrScene::HostBlas(); if ((rc = build_blas(s->meshes[m], (uint32_t)m, nullptr, s->blases[m])) != SR_OK) return rc; s->mu_info.blas_rebuilt++; s->mu_info.blas_build_ms += s->blases[m].build_ms; }
         cat.textured = cat.textured || !s->blases[m].shade_tex.empty();
     }
     s->blas_node_base.assign(nm, 0u); s->blas_tri_base.assign(nm, 0u);
@@ -844,7 +936,7 @@ int two_level_build(SrScene* s, bool list_changed) {
         const srh::HostInstance& in = s->fid.instances[i];
         const srh::HostMesh& mesh = s->meshes[in.mesh_slot];
         SrScene::HostBlas& b = s->blases[in.mesh_slot];
-        if (!b.valid) { b = SrScene::HostBlas(); if ((rc = build_blas(mesh, in.mesh_slot, nullptr, b)) != SR_OK) return rc; s->blas_device_current = false; }
+        if (!b.valid) { b = SrScene::HostBlas(); if ((rc = build_blas(mesh, in.mesh_slot, nullptr, b)) != SR_OK) return rc; s->blas_device_current = false; s->mu_info.blas_rebuilt++; s->mu_info.blas_build_ms += b.build_ms; }
         srd::DevTlInstance& r = recs[i];
         const float* M = in.o2w.m;
         memcpy(r.o2w, M, 48);
@@ -1072,6 +1164,12 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     srh::FrameInstanceData fid;
     if (!srh::frame_instance_data(s->meshes, s->slots, keys, counts, n_keys, transforms, fid, err)) return fail(SR_ERR_INVALID_ARG, err);
     s->fid = std::move(fid);
+    // meshes updated since the structure last took their vertices (sr_scene_update_mesh): every path below applies them
+    const bool reshade = s->geometry_stale;
+    s->mu_info.dirty_meshes = (uint32_t)std::count(s->mesh_dirty.begin(), s->mesh_dirty.end(), (char)1);
+    s->mu_info.reshaded = 0; s->mu_info.blas_rebuilt = 0;
+    s->mu_info.tables_ms = s->mu_info.flatten_ms = s->mu_info.refit_ms = s->mu_info.blas_build_ms = 0.0;
+    auto applied = [s] { std::fill(s->mesh_dirty.begin(), s->mesh_dirty.end(), (char)0); s->geometry_stale = false; };
     s->emissive_table = s->emissive_tris;
     if (s->emissive_table.empty()) { SrEmissiveTriangle z; memset(&z, 0, sizeof(z)); s->emissive_table.push_back(z); }
     // Two-level form (a tree per mesh + a top-level tree over the instances): on request or where the flattened copy would be
@@ -1085,6 +1183,7 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
         if (s->built_once) srh::as_state_mark_built(s->as_state, op);
         s->built_once = true;
         s->last_op = op;
+        applied();
         return SR_OK;
     }
     if (s->two_level) {                       // back to the one-level form: everything is rebuilt
@@ -1104,17 +1203,19 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
         if (op == SR_OP_UPDATE && !can_update) op = SR_OP_FAST_BUILD;
     }
     if (s->forced_op != SR_OP_NONE) { op = (s->forced_op == SR_OP_UPDATE && !can_update) ? SR_OP_FAST_BUILD : s->forced_op; s->forced_op = SR_OP_NONE; }
-    rc = op == SR_OP_UPDATE ? update_in_place(s) : op == SR_OP_FAST_BUILD ? fast_build(s) : full_build(s);
+    rc = op == SR_OP_UPDATE ? update_in_place(s, reshade) : op == SR_OP_FAST_BUILD ? fast_build(s) : full_build(s);
     if (rc != SR_OK) { s->built = false; return rc; }
     if (s->built_once) srh::as_state_mark_built(s->as_state, op);
     s->built_once = true;
     s->last_op = op;
+    applied();
     return SR_OK;
 }
 
 int sr_scene_end_frame(SrScene* s) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_end_frame: scene is null");
     if (!s->built) { s->last_op = SR_OP_NONE; return SR_OK; }
+    if (s->geometry_stale) return fail(SR_ERR_STATE, std::string("sr_scene_end_frame: ") + kStaleGeometry);
     const uint32_t op = srh::as_state_next_op(s->as_state, false);
     if (op == SR_OP_SLOW_BUILD) {
         int rc = bind_device(s);
@@ -1199,6 +1300,7 @@ int sr_bvh_layout(uint32_t* width, uint32_t* node_dwords, uint32_t* plane_offset
 int sr_scene_read_bvh(const SrScene* s, uint32_t* nodes_out, float* tris_out) {
     if (!s || !s->built) return fail(SR_ERR_STATE, "sr_scene_read_bvh: scene not built");
     if (s->two_level) return fail(SR_ERR_UNSUPPORTED, "sr_scene_read_bvh: the scene is built in the two-level form");
+    if (s->geometry_stale) return fail(SR_ERR_STATE, std::string("sr_scene_read_bvh: ") + kStaleGeometry);
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());
     if (nodes_out) HIP_TRY(hipMemcpy(nodes_out, s->d_nodes.p, (size_t)s->stats.n_nodes * srl::kNodeBytes, hipMemcpyDeviceToHost));
@@ -1327,6 +1429,7 @@ int sr_scene_resolve_triangle(const SrScene* s, uint32_t tri, uint32_t* instance
 static int trace_list(SrScene* s, const SrRay* rays, uint32_t n, SrHit* hits, uint32_t* occluded, int any, void* stream) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_trace: scene is null");
     if (!s->built) return fail(SR_ERR_STATE, "sr_trace: call sr_scene_set_instances first (TLAS not built)");
+    if (s->geometry_stale) return fail(SR_ERR_STATE, std::string("sr_trace: ") + kStaleGeometry);
     if (n && (!rays || (any ? (void*)occluded : (void*)hits) == nullptr)) return fail(SR_ERR_INVALID_ARG, "sr_trace: null ray/output pointer");
     int rc = bind_device(s);
     if (rc != SR_OK) return rc;
@@ -1348,6 +1451,7 @@ int sr_trace_any(const SrScene* s, const SrRay* rays, uint32_t n, uint32_t* occl
 int sr_shade_closest_hit(const SrScene* s, const SrHit* hits, uint32_t n, SrRayPayload* payloads, void* stream) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_shade_closest_hit: scene is null");
     if (!s->built) return fail(SR_ERR_STATE, "sr_shade_closest_hit: scene not built");
+    if (s->geometry_stale) return fail(SR_ERR_STATE, std::string("sr_shade_closest_hit: ") + kStaleGeometry);
     if (n && (!hits || !payloads)) return fail(SR_ERR_INVALID_ARG, "sr_shade_closest_hit: null pointer");
     int rc = bind_device(s);
     if (rc != SR_OK) return rc;
@@ -1359,6 +1463,7 @@ int sr_shade_closest_hit(const SrScene* s, const SrHit* hits, uint32_t n, SrRayP
 int sr_any_hit_ignores(const SrScene* s, const SrHit* hits, uint32_t n, uint32_t* ignored, void* stream) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_any_hit_ignores: scene is null");
     if (!s->built) return fail(SR_ERR_STATE, "sr_any_hit_ignores: scene not built");
+    if (s->geometry_stale) return fail(SR_ERR_STATE, std::string("sr_any_hit_ignores: ") + kStaleGeometry);
     if (n && (!hits || !ignored)) return fail(SR_ERR_INVALID_ARG, "sr_any_hit_ignores: null pointer");
     int rc = bind_device(s);
     if (rc != SR_OK) return rc;
@@ -1372,6 +1477,7 @@ static int run_pass(const SrRtParams* p, int which, void* stream) {
     if (!p || !p->scene) return fail(SR_ERR_INVALID_ARG, std::string(name) + ": params or scene is null");
     SrScene* s = const_cast<SrScene*>(p->scene);
     if (!s->built) return fail(SR_ERR_STATE, std::string(name) + ": TLAS not built (call sr_scene_set_instances)");
+    if (s->geometry_stale) return fail(SR_ERR_STATE, std::string(name) + ": " + kStaleGeometry);
     if (p->width == 0 || p->height == 0) return fail(SR_ERR_INVALID_ARG, std::string(name) + ": trace_extent not set");
     if (!p->matrices) return fail(SR_ERR_INVALID_ARG, std::string(name) + ": matrices is null");
     const bool need_restir = p->config.enable_restir != 0;

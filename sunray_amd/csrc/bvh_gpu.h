@@ -23,6 +23,9 @@ struct DevTlInstance;   // traverse.h
 
 int srk_launch_flatten_slots(float4* tris, const float4* shade, const SrMeshInfo* meshes, const srd::FlatInstance* instances, uint32_t n_tris,
                              hipStream_t stream);
+// The same with the slots' shading records rewritten from the (changed) vertices; shade_tex is null where the scene has none.
+int srk_launch_flatten_reshade(float4* tris, float4* shade, float4* shade_tex, const SrMeshInfo* meshes, const srd::FlatInstance* instances,
+                               uint32_t n_tris, hipStream_t stream);
 int srk_launch_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host,
                      uint32_t n_levels, hipStream_t stream);
 

@@ -8,6 +8,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include <hipcub/hipcub.hpp>
 
@@ -19,14 +20,20 @@
 
 namespace srd {
 
-__device__ __forceinline__ void world_triangle(const SrMeshInfo* meshes, const FlatInstance& inst, uint32_t prim, float v0[3], float e1[3], float e2[3]) {
+__device__ __forceinline__ void triangle_vertices(const SrMeshInfo* meshes, const FlatInstance& inst, uint32_t prim, const SrVertex* v[3]) {
     const SrMeshInfo mi = meshes[inst.mesh_slot];
     const uint32_t* idx = (const uint32_t*)(uintptr_t)mi.indices;
     const SrVertex* vtx = (const SrVertex*)(uintptr_t)mi.vertices;
+    for (int j = 0; j < 3; j++) v[j] = vtx + idx[3 * prim + j];
+}
+
+__device__ __forceinline__ void world_triangle(const SrMeshInfo* meshes, const FlatInstance& inst, uint32_t prim, float v0[3], float e1[3], float e2[3],
+                                               const SrVertex* v[3]) {
+    triangle_vertices(meshes, inst, prim, v);
     const float* m = inst.o2w;
     float w[3][3];
     for (int j = 0; j < 3; j++) {
-        const float* q = vtx[idx[3 * prim + j]].position;
+        const float* q = v[j]->position;
         // transform_point (rt_utils.slang:278-281): rows dotted with (p, 1), left to right
         w[j][0] = ((m[0] * q[0] + m[1] * q[1]) + m[2] * q[2]) + m[3] * 1.0f;
         w[j][1] = ((m[4] * q[0] + m[5] * q[1]) + m[6] * q[2]) + m[7] * 1.0f;
@@ -35,19 +42,49 @@ __device__ __forceinline__ void world_triangle(const SrMeshInfo* meshes, const F
     for (int a = 0; a < 3; a++) { v0[a] = w[0][a]; e1[a] = w[1][a] - w[0][a]; e2[a] = w[2][a] - w[0][a]; }
 }
 
+// The per-slot shading records of one triangle: `shade` = the three object-space vertex normals + (instance, mesh slot, 0) as
+// `tail`; `shade_tex` (scenes with a textured material) = uv, normal-map uv, tangents, handedness of the first vertex
+// (closest_hit.slang:34). The one definition of the device side: the fast build's leaves and the reshading update write the
+// same bytes as the host builds (api.cpp full_build / build_blas).
+__device__ __forceinline__ void write_shade(float4* shade, const SrVertex* const v[3], float tail_y, float tail_z, float tail_w) {
+    shade[0] = make_float4(v[0]->normal[0], v[0]->normal[1], v[0]->normal[2], v[1]->normal[0]);
+    shade[1] = make_float4(v[1]->normal[1], v[1]->normal[2], v[2]->normal[0], v[2]->normal[1]);
+    shade[2] = make_float4(v[2]->normal[2], tail_y, tail_z, tail_w);
+}
+__device__ __forceinline__ void write_shade_tex(float4* q, const SrVertex* const v[3]) {
+    q[0] = make_float4(v[0]->base_color_tex_coord[0], v[0]->base_color_tex_coord[1], v[1]->base_color_tex_coord[0], v[1]->base_color_tex_coord[1]);
+    q[1] = make_float4(v[2]->base_color_tex_coord[0], v[2]->base_color_tex_coord[1], v[0]->normal_tex_coord[0], v[0]->normal_tex_coord[1]);
+    q[2] = make_float4(v[1]->normal_tex_coord[0], v[1]->normal_tex_coord[1], v[2]->normal_tex_coord[0], v[2]->normal_tex_coord[1]);
+    q[3] = make_float4(v[0]->tangent[0], v[0]->tangent[1], v[0]->tangent[2], v[0]->tangent[3] >= 0.0f ? 1.0f : -1.0f);
+    q[4] = make_float4(v[1]->tangent[0], v[1]->tangent[1], v[1]->tangent[2], v[2]->tangent[0]);
+    q[5] = make_float4(v[2]->tangent[1], v[2]->tangent[2], 0.0f, 0.0f);
+}
+
 // One thread per leaf-order slot: the slot keeps its triangle (global id), only the world-space record changes.
-__global__ void flatten_slots_kernel(float4* tris, const float4* shade, const SrMeshInfo* meshes, const FlatInstance* instances, uint32_t n_tris) {
+// RESHADE (a mesh's vertices changed, sr_scene_update_mesh): the slot's shading records are rewritten as well, from the same
+// three vertex records the positions come from (normals, uvs and tangents sit next to the position in the 96-byte SrVertex);
+// the instance and mesh-slot words of `shade` are kept. TEX: the scene has shade_tex records.
+template <bool RESHADE, bool TEX>
+__global__ void flatten_slots_kernel(float4* tris, typename std::conditional<RESHADE, float4*, const float4*>::type shade, const SrMeshInfo* meshes,
+                                     const FlatInstance* instances, uint32_t n_tris, float4* shade_tex) {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= n_tris) return;
     const uint32_t gid = __float_as_uint(tris[(size_t)slot * 3 + 2].y);   // record: (v0, e1, e2, gid, 0, 0), bvh_build.cpp
-    const uint32_t ii = __float_as_uint(shade[(size_t)slot * 3 + 2].y);
+    float4 tail = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (RESHADE) tail = shade[(size_t)slot * 3 + 2]; else tail.y = shade[(size_t)slot * 3 + 2].y;
+    const uint32_t ii = __float_as_uint(tail.y);
     const FlatInstance inst = instances[ii];
     if (gid < inst.tri_offset) return;      // cannot happen for a tree built from this layout; never index out of bounds
     float v0[3], e1[3], e2[3];
-    world_triangle(meshes, inst, gid - inst.tri_offset, v0, e1, e2);
+    const SrVertex* v[3];
+    world_triangle(meshes, inst, gid - inst.tri_offset, v0, e1, e2, v);
     tris[(size_t)slot * 3 + 0] = make_float4(v0[0], v0[1], v0[2], e1[0]);
     tris[(size_t)slot * 3 + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
     tris[(size_t)slot * 3 + 2] = make_float4(e2[2], __uint_as_float(gid), 0.0f, 0.0f);
+    if constexpr (RESHADE) {
+        write_shade(shade + (size_t)slot * 3, v, tail.y, tail.z, tail.w);
+        if constexpr (TEX) write_shade_tex(shade_tex + (size_t)slot * 6, v);
+    }
 }
 
 // Padded box of one triangle record, as the host builder bounds it (bvh_build.cpp: fattened by the triangle
@@ -194,7 +231,8 @@ __global__ void lbvh_prims_kernel(const SrMeshInfo* meshes, const FlatInstance* 
         const uint32_t ii = find_instance(instances, n_inst, gid);
         const FlatInstance inst = instances[ii];
         float v0[3], e1[3], e2[3];
-        world_triangle(meshes, inst, gid - inst.tri_offset, v0, e1, e2);
+        const SrVertex* v[3];
+        world_triangle(meshes, inst, gid - inst.tri_offset, v0, e1, e2, v);
         W[(size_t)gid * 3 + 0] = make_float4(v0[0], v0[1], v0[2], e1[0]);
         W[(size_t)gid * 3 + 1] = make_float4(e1[1], e1[2], e2[0], e2[1]);
         W[(size_t)gid * 3 + 2] = make_float4(e2[2], __uint_as_float(gid), 0.0f, 0.0f);
@@ -399,23 +437,10 @@ __global__ void lbvh_leaves_kernel(const float4* W, const float4* cent, const ui
     slot_of_gid[gid] = slot;
     const uint32_t ii = __float_as_uint(cent[gid].w);
     const FlatInstance inst = instances[ii];
-    const SrMeshInfo mi = meshes[inst.mesh_slot];
-    const uint32_t* idx = (const uint32_t*)(uintptr_t)mi.indices;
-    const SrVertex* vtx = (const SrVertex*)(uintptr_t)mi.vertices;
-    const uint32_t prim = gid - inst.tri_offset;
-    const SrVertex* v[3] = {vtx + idx[3 * prim], vtx + idx[3 * prim + 1], vtx + idx[3 * prim + 2]};
-    shade[(size_t)slot * 3 + 0] = make_float4(v[0]->normal[0], v[0]->normal[1], v[0]->normal[2], v[1]->normal[0]);
-    shade[(size_t)slot * 3 + 1] = make_float4(v[1]->normal[1], v[1]->normal[2], v[2]->normal[0], v[2]->normal[1]);
-    shade[(size_t)slot * 3 + 2] = make_float4(v[2]->normal[2], __uint_as_float(ii), __uint_as_float(inst.mesh_slot), 0.0f);
-    if (shade_tex) {
-        float4* q = shade_tex + (size_t)slot * 6;
-        q[0] = make_float4(v[0]->base_color_tex_coord[0], v[0]->base_color_tex_coord[1], v[1]->base_color_tex_coord[0], v[1]->base_color_tex_coord[1]);
-        q[1] = make_float4(v[2]->base_color_tex_coord[0], v[2]->base_color_tex_coord[1], v[0]->normal_tex_coord[0], v[0]->normal_tex_coord[1]);
-        q[2] = make_float4(v[1]->normal_tex_coord[0], v[1]->normal_tex_coord[1], v[2]->normal_tex_coord[0], v[2]->normal_tex_coord[1]);
-        q[3] = make_float4(v[0]->tangent[0], v[0]->tangent[1], v[0]->tangent[2], v[0]->tangent[3] >= 0.0f ? 1.0f : -1.0f);
-        q[4] = make_float4(v[1]->tangent[0], v[1]->tangent[1], v[1]->tangent[2], v[2]->tangent[0]);
-        q[5] = make_float4(v[2]->tangent[1], v[2]->tangent[2], 0.0f, 0.0f);
-    }
+    const SrVertex* v[3];
+    triangle_vertices(meshes, inst, gid - inst.tri_offset, v);
+    write_shade(shade + (size_t)slot * 3, v, __uint_as_float(ii), __uint_as_float(inst.mesh_slot), 0.0f);
+    if (shade_tex) write_shade_tex(shade_tex + (size_t)slot * 6, v);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -621,7 +646,16 @@ using namespace srd;
 
 int srk_launch_flatten_slots(float4* tris, const float4* shade, const SrMeshInfo* meshes, const FlatInstance* instances, uint32_t n_tris, hipStream_t stream) {
     if (n_tris == 0) return 0;
-    flatten_slots_kernel<<<dim3((n_tris + 255) / 256), dim3(256), 0, stream>>>(tris, shade, meshes, instances, n_tris);
+    flatten_slots_kernel<false, false><<<dim3((n_tris + 255) / 256), dim3(256), 0, stream>>>(tris, shade, meshes, instances, n_tris, nullptr);
+    return (int)hipGetLastError();
+}
+
+int srk_launch_flatten_reshade(float4* tris, float4* shade, float4* shade_tex, const SrMeshInfo* meshes, const FlatInstance* instances, uint32_t n_tris,
+                               hipStream_t stream) {
+    if (n_tris == 0) return 0;
+    const dim3 grid((n_tris + 255) / 256), block(256);
+    if (shade_tex) flatten_slots_kernel<true, true><<<grid, block, 0, stream>>>(tris, shade, meshes, instances, n_tris, shade_tex);
+    else flatten_slots_kernel<true, false><<<grid, block, 0, stream>>>(tris, shade, meshes, instances, n_tris, nullptr);
     return (int)hipGetLastError();
 }
 

@@ -485,6 +485,22 @@ int sr_renderer_unload_mesh(SrRenderer* r, uint64_t key) {
     return SR_OK;
 }
 
+// Blas::update (blas.rs:285-310) through the facade: every replica takes the new vertices; the next render re-submits the
+// instance list, and that sr_scene_set_instances applies the update. Frames in flight: each sr_scene_update_mesh waits for
+// its scene's device (hipDeviceSynchronize) before the device copy of the vertices changes, so the passes of the frames
+// submitted before have finished; no wait_frame is needed from the caller. The replicas hold the same meshes, so a call the
+// first one refuses on validation changes none of them (only those refusals are all-or-nothing: a device error on a later
+// replica leaves the earlier ones updated, and the instance list is re-submitted in any case).
+int sr_renderer_update_mesh(SrRenderer* r, uint64_t key, const SrVertex* vertices, uint32_t n_vertices) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "update_mesh: renderer is null");
+    r->instances_valid = false;
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_update_mesh(sc, key, vertices, n_vertices);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+
 // Access for harnesses: the scene (counters, stats), the device output image and the frame counter.
 int sr_renderer_get(SrRenderer* r, SrScene** scene, const uint32_t** output_rgba8_device, const float** raw_color_device, uint32_t* relative_frame_count) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_get: renderer is null");

@@ -201,6 +201,18 @@ class Scene:
     def remove(self, key):
         check(lib().sr_scene_remove(self._h, C.c_uint64(key)))
 
+    # Blas::update (acceleration_structure/blas.rs:285-310)
+    def update_mesh(self, key, vertices):
+        """New vertex contents for a loaded mesh (same count, indices and material); the next set_instances applies it."""
+        v = np.ascontiguousarray(vertices, dtype=abi.VERTEX)
+        check(lib().sr_scene_update_mesh(self._h, C.c_uint64(key), _p(v), C.c_uint32(len(v))))
+
+    def mesh_update_info(self):
+        """-> abi.SrMeshUpdateInfo of the last update_mesh and of the set_instances that applied it."""
+        info = abi.SrMeshUpdateInfo()
+        check(lib().sr_scene_mesh_update_info(self._h, C.byref(info)))
+        return info
+
     # Image::new_from_data (image/mod.rs:82-111) / Sampler::new (image/sampler.rs:44-67)
     def add_image(self, pixels):
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
@@ -595,6 +607,11 @@ class Renderer:
         i = np.ascontiguousarray(indices, dtype=np.uint32)
         m = np.ascontiguousarray(material, dtype=abi.MATERIAL)
         check(lib().sr_renderer_load_mesh(self._h, C.c_uint64(key), _p(v), C.c_uint32(len(v)), _p(i), C.c_uint32(len(i)), _p(m)))
+
+    def update_mesh(self, key, vertices):
+        """New vertex contents for a loaded mesh on every device slot; the next render applies it."""
+        v = np.ascontiguousarray(vertices, dtype=abi.VERTEX)
+        check(lib().sr_renderer_update_mesh(self._h, C.c_uint64(key), _p(v), C.c_uint32(len(v))))
 
     def set_config(self, config):
         check(lib().sr_renderer_set_config(self._h, C.byref(config)))

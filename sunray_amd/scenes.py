@@ -422,3 +422,49 @@ def instanced_field(n_instances=300, segments=24, rings=12, n_meshes=3, seed=5, 
     s.instances.append((ground_key, [translate(0, 0, 0)]))
     s.instances.append((lamp_key, [translate(extent * (0.6 * np.cos(2.4 * j)), 7.0 + 0.5 * j, extent * (0.6 * np.sin(2.4 * j)), 1.5) for j in range(n_lamps)]))
     return s
+
+
+# ---- deforming geometry (Scene.update_mesh / Renderer.update_mesh) ---------------------------------------
+def deform_vertices(vertices, indices, phase, amplitude=0.12, seed=77):
+    """One animation step of a mesh, deterministic in (vertices, phase): positions move along their normals by an fBm of
+    (position, phase), vertex normals are recomputed area-weighted from the displaced triangles (a vertex of degenerate
+    triangles only keeps its old one), tangents turn about the new normal by 0.2 * phase and every uv set shifts with the phase.
+    Count, order and indices stay, so the result is what update_mesh accepts."""
+    v = np.array(vertices, dtype=abi.VERTEX, copy=True)
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1, 3)
+    p, n = v["position"].astype(np.float64), v["normal"].astype(np.float64)
+    disp = 2.0 * amplitude * (fbm(1.7 * p[:, 0] + 0.9 * p[:, 2] + 0.37 * phase + 11.0, 1.3 * p[:, 1] - 0.6 * p[:, 2] + 0.23 * phase + 5.0, seed) - 0.5)
+    q = (p + n * disp[:, None]).astype(np.float32)
+    v["position"] = q
+    q = q.astype(np.float64)
+    face = np.cross(q[idx[:, 1]] - q[idx[:, 0]], q[idx[:, 2]] - q[idx[:, 0]])     # length = twice the area
+    acc = np.zeros_like(q)
+    for j in range(3):
+        np.add.at(acc, idx[:, j], face)
+    ln = np.linalg.norm(acc, axis=1)
+    ok = ln > 1e-20
+    flip = np.where(np.einsum("ij,ij->i", acc, n) < 0.0, -1.0, 1.0)              # keep the side the mesh's own normals face
+    nn = np.where(ok[:, None], acc / np.where(ok, ln, 1.0)[:, None] * flip[:, None], n)
+    v["normal"] = nn.astype(np.float32)
+    t = v["tangent"][:, :3].astype(np.float64)
+    a = 0.2 * phase                                                               # Rodrigues' rotation about the new normal
+    t = t * np.cos(a) + np.cross(nn, t) * np.sin(a) + nn * np.einsum("ij,ij->i", nn, t)[:, None] * (1.0 - np.cos(a))
+    v["tangent"][:, :3] = t.astype(np.float32)
+    shift = np.array([0.013 * phase, -0.007 * phase], dtype=np.float32)
+    for k in ("base_color", "metallic_roughness", "normal", "occlusion", "emissive"):
+        v[k + "_tex_coord"] = v[k + "_tex_coord"] + shift
+    return v
+
+
+def with_mesh_vertices(desc, key, vertices):
+    """A copy of `desc` whose mesh `key` holds `vertices` (same count); everything else is shared with `desc`."""
+    meshes = [MeshDesc(m.key, vertices, m.indices, m.material) if m.key == key else m for m in desc.meshes]
+    return SceneDesc(desc.name, meshes, desc.instances, desc.images, desc.samplers, desc.camera_pos, desc.camera_target, desc.fov_y)
+
+
+def deform(desc, keys, phase, amplitude=0.12, seed=77):
+    """A copy of `desc` whose meshes `keys` took deform_vertices(.., phase); everything else is shared with `desc`."""
+    keys = set(keys)
+    meshes = [MeshDesc(m.key, deform_vertices(m.vertices, m.indices, phase, amplitude, seed + m.key), m.indices, m.material) if m.key in keys else m
+              for m in desc.meshes]
+    return SceneDesc(desc.name, meshes, desc.instances, desc.images, desc.samplers, desc.camera_pos, desc.camera_target, desc.fov_y)
