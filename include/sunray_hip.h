@@ -754,6 +754,33 @@ int sr_strip_rects(const SrPartition* partition, uint32_t rank, SrStripRects* ou
 int sr_strip_trace_ris(const SrRtParams* params, const SrPartition* partition, uint32_t rank, void* stream);
 int sr_strip_trace_final(const SrRtParams* params, const SrPartition* partition, uint32_t rank, void* stream);
 
+/* Strip movement on its own: what a multi-device caller outside the Renderer uses to move the rectangles of sr_strip_rects and
+ * sr_history_exchange_plan between devices, and to check the exactness of its own history exchange. Device pointers and a
+ * stream, like sr_post_*; every call launches on the current device. One per-pixel plane of a full-size image: */
+typedef struct SrStripPlane {
+    void* img;      /* width * height * bpp bytes, 16-byte aligned */
+    uint32_t bpp;   /* bytes per pixel: non-zero and even */
+    uint32_t _pad;
+} SrStripPlane;
+#define SR_STRIP_MAX_PLANES 5u
+/* Packed form of a w x h rectangle of n_planes planes: plane after plane, rows in order within a plane, every plane's block
+ * padded to 16 bytes. *bytes receives its size (only bpp of every plane is read). */
+int sr_strip_packed_bytes(const SrStripPlane* planes, uint32_t n_planes, uint32_t w, uint32_t h, uint64_t* bytes);
+/* Rectangle [x0, x0 + w) x [y0, y0 + h) of images width x height pixels -> `packed` (sr_strip_packed_bytes bytes, 16-byte
+ * aligned; the padding keeps its bytes), and back: unpack writes the rectangle and nothing else. One launch each. Refused with
+ * SR_ERR_INVALID_ARG, nothing launched: n_planes outside 1..SR_STRIP_MAX_PLANES, a bpp that is zero or odd, a null pointer, a
+ * rectangle that leaves the image, an image or packed pointer that is not 16-byte aligned. w == 0 or h == 0 is a no-op. */
+int sr_strip_pack(const SrStripPlane* planes, uint32_t n_planes, uint32_t width, uint32_t height, uint32_t x0, uint32_t w,
+                  uint32_t y0, uint32_t h, void* packed, void* stream);
+int sr_strip_unpack(const SrStripPlane* planes, uint32_t n_planes, uint32_t width, uint32_t height, uint32_t x0, uint32_t w,
+                    uint32_t y0, uint32_t h, const void* packed, void* stream);
+/* After a RIS pass over [x0, x0 + w) x [y0, y0 + h): ADDS to *counter (device) the pixels whose temporal-history read, bounded
+ * from the stored motion vector (motion_vec_img, R16G16_SFLOAT), may lie outside [held_lo, held_hi) along `axis`. It may
+ * over-report near an edge of the held region and never misses. Refused as above; also held_lo > held_hi or
+ * held_hi beyond the axis length, and an axis that is neither SR_AXIS_COLS nor SR_AXIS_ROWS. */
+int sr_history_reach_check(const uint32_t* motion_vec_img, uint32_t width, uint32_t height, uint32_t axis, uint32_t x0, uint32_t w,
+                           uint32_t y0, uint32_t h, uint32_t held_lo, uint32_t held_hi, uint64_t* counter, void* stream);
+
 /* Ray counters since the last reset (device-side atomics, read back synchronously). */
 int sr_scene_reset_counters(SrScene* scene, void* stream);
 int sr_scene_read_counters(SrScene* scene, void* stream, SrRayCounters* out);
@@ -807,7 +834,7 @@ static_assert(sizeof(SrRayPayload) == 32, "T8");
 static_assert(sizeof(SrRay) == 32 && sizeof(SrHit) == 16, "ray/hit");
 static_assert(sizeof(SrTraceConfig) == 40 && sizeof(SrRtParams) == 184, "T9");
 static_assert(sizeof(SrPostParams) == 104, "post params");
-static_assert(sizeof(SrStripTransfer) == 16 && sizeof(SrStripRects) == 56, "strip plans");
+static_assert(sizeof(SrStripTransfer) == 16 && sizeof(SrStripRects) == 56 && sizeof(SrStripPlane) == 16, "strip plans");
 #endif
 
 #endif /* SUNRAY_HIP_H */

@@ -90,6 +90,9 @@ def unpack_normal(p):
     return np.array(list(out), dtype=np.float32)
 
 
+NO_READ = -2 ** 31     # read-log marker (orc_scene.h, kNoRead)
+
+
 class OracleScene:
     """Oracle counterpart of sunray_amd.Scene: same methods, numpy (host) buffers."""
 
@@ -173,6 +176,15 @@ class OracleScene:
 
     def set_brute_force(self, on):
         lib().orc_scene_set_brute_force(self._h, C.c_int(1 if on else 0))
+
+    def set_read_log(self, log):
+        """Test aid: `log`, a C-contiguous int32 array [height, width, 4], receives per pixel the temporal-history reads
+        (pcx, pcy, gx, gy) that the following trace_ris calls compute, before their in-image test, NO_READ where the temporal
+        branch is not taken; None switches the log off (the default: nothing changes)."""
+        if log is not None:
+            assert log.dtype == np.int32 and log.flags["C_CONTIGUOUS"] and log.shape[-1] == 4
+        self._read_log = log
+        lib().orc_scene_set_read_log(self._h, None if log is None else _p(log))
 
     def tables(self):
         tp, ip, ep = C.c_void_p(), C.c_void_p(), C.c_void_p()

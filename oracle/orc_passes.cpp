@@ -91,6 +91,8 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
     SrReservoirGI* reservoir_gi_cur = pc.reservoirs_gi[cur_buf];
     const SrReservoirGI* reservoir_gi_hist = pc.reservoirs_gi[hist_buf];
     const uint32_t pix = py * W + px;                                 // get_pixel_index
+    int32_t* read_log = sc.read_log ? sc.read_log + (size_t)pix * 4 : nullptr;     // test aid (orc_scene.h)
+    if (read_log) read_log[0] = read_log[1] = read_log[2] = read_log[3] = Scene::kNoRead;
 
     Rng rng = init_rng(px, py, pc.frame_count, W);                   // :42
     PrimaryRay pr = primary_ray(mat_view_inverse, mat_proj_inverse, px, py, W, H);  // :44-53
@@ -211,6 +213,7 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
             float j0 = rnd(rng), j1 = rnd(rng);
             V2 di_jitter = V2{j0 - 0.5f, j1 - 0.5f};
             int pcx = (int)(prev_pixel_f.x + di_jitter.x), pcy = (int)(prev_pixel_f.y + di_jitter.y);
+            if (read_log) { read_log[0] = pcx; read_log[1] = pcy; }
             if (pcx >= 0 && pcy >= 0 && pcx < (int)W && pcy < (int)H) {
                 SrReservoir history_r = reservoir_hist[(uint32_t)pcy * W + (uint32_t)pcx];
                 history_r.M = min_f(history_r.M, 10.0f);
@@ -312,6 +315,7 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
         float j0 = rnd(rng), j1 = rnd(rng);
         V2 gi_jitter = V2{j0 - 0.5f, j1 - 0.5f};
         int gx = (int)(prev_pixel_f_gi.x + gi_jitter.x), gy = (int)(prev_pixel_f_gi.y + gi_jitter.y);
+        if (read_log) { read_log[2] = gx; read_log[3] = gy; }
         if (gx >= 0 && gy >= 0 && gx < (int)W && gy < (int)H) {
             SrReservoirGI history_gi = reservoir_gi_hist[(uint32_t)gy * W + (uint32_t)gx];
             V3 gi_hist_normal = unpack_normal(history_gi.hit_normal_packed);

@@ -65,6 +65,11 @@ struct Scene {
     std::vector<uint32_t> order;
     bool use_brute_force = false;
     Counters counters;
+    // Test aid, not in the reference: when set (4 * width * height ints), trace_ris records per pixel the temporal-history reads
+    // it computes, (pcx, pcy) of the DI reservoir and (gx, gy) of the GI reservoir, as computed and before the in-image test;
+    // kNoRead where the temporal branch is not taken. Unset: nothing is recorded and nothing changes.
+    static constexpr int32_t kNoRead = INT32_MIN;
+    int32_t* read_log = nullptr;
 
     int add_mesh(uint64_t key, const SrVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, const SrMaterial* m);
     int add_blas(uint64_t key, const SrVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, const SrMaterial* m,

@@ -182,4 +182,8 @@ class SrStripRects(C.Structure):  # launch rectangles + counting window of one r
                 ("count_window", C.c_uint32), ("empty", C.c_uint32)]
 
 
-AXIS_COLS, AXIS_ROWS, SPATIAL_HALO = 0, 1, 30
+class SrStripPlane(C.Structure):  # one per-pixel plane of a full-size image (sr_strip_pack / sr_strip_unpack)
+    _fields_ = [("img", C.c_void_p), ("bpp", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+AXIS_COLS, AXIS_ROWS, SPATIAL_HALO, STRIP_MAX_PLANES = 0, 1, 30, 5

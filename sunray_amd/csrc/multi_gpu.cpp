@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "host.h"
+#include "strip_copy.h"
 
 struct SrPartition {
     uint32_t width = 0, height = 0, world = 0, axis = SR_AXIS_COLS;
@@ -28,6 +29,42 @@ void grown(const SrPartition& p, uint32_t rank, uint32_t grow, uint32_t& start, 
     const uint32_t lo = a0 > grow ? a0 - grow : 0u;
     const uint32_t hi = std::min<uint64_t>(p.length(), (uint64_t)a1 + grow);
     start = lo; size = hi - lo;
+}
+
+int check_rect(const std::string& name, uint32_t W, uint32_t H, uint32_t x0, uint32_t w, uint32_t y0, uint32_t h) {
+    if (W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31)) return mfail(SR_ERR_INVALID_ARG, name + ": extent not set or too large");
+    if ((uint64_t)x0 + w > W || (uint64_t)y0 + h > H) return mfail(SR_ERR_INVALID_ARG, name + ": the rectangle leaves the image");
+    return SR_OK;
+}
+
+int check_planes(const SrStripPlane* planes, uint32_t n, const std::string& name, bool pointers, SrkStripPlane* out) {
+    if (!planes) return mfail(SR_ERR_INVALID_ARG, name + ": planes is null");
+    if (n == 0 || n > srd::kStripMaxPlanes) return mfail(SR_ERR_INVALID_ARG, name + ": n_planes must be 1..5");
+    for (uint32_t p = 0; p < n; p++) {
+        if (planes[p].bpp == 0 || planes[p].bpp % 2 != 0) return mfail(SR_ERR_INVALID_ARG, name + ": bytes per pixel must be non-zero and even");
+        if (pointers && !planes[p].img) return mfail(SR_ERR_INVALID_ARG, name + ": image pointer is null");
+        if (pointers && (uintptr_t)planes[p].img % 16 != 0) return mfail(SR_ERR_INVALID_ARG, name + ": image pointer is not 16-byte aligned");
+        out[p].img = planes[p].img;
+        out[p].bpp = planes[p].bpp;
+    }
+    return SR_OK;
+}
+
+int strip_copy(bool pack, const std::string& name, const SrStripPlane* planes, uint32_t n, uint32_t W, uint32_t H, uint32_t x0,
+               uint32_t w, uint32_t y0, uint32_t h, void* packed, void* stream) {
+    SrkStripPlane k[srd::kStripMaxPlanes];
+    int rc = check_planes(planes, n, name, true, k);
+    if (rc != SR_OK) return rc;
+    if (!packed) return mfail(SR_ERR_INVALID_ARG, name + ": packed is null");
+    if ((uintptr_t)packed % 16 != 0) return mfail(SR_ERR_INVALID_ARG, name + ": packed pointer is not 16-byte aligned");
+    if ((rc = check_rect(name, W, H, x0, w, y0, h)) != SR_OK) return rc;
+    for (uint32_t p = 0; p < n; p++)                                   // the kernels count a row segment's bytes in 32 bits
+        if ((uint64_t)W * k[p].bpp >= (1ull << 32)) return mfail(SR_ERR_INVALID_ARG, name + ": an image row is 4 GiB or longer");
+    if (w == 0 || h == 0) return SR_OK;
+    int e = pack ? srk_launch_strip_pack(k, n, W, x0, w, y0, h, packed, (hipStream_t)stream)
+                 : srk_launch_strip_unpack(k, n, W, x0, w, y0, h, packed, (hipStream_t)stream);
+    if (e != 0) return mfail(SR_ERR_HIP, name + " launch: " + hipGetErrorString((hipError_t)e));
+    return SR_OK;
 }
 }  // namespace
 
@@ -198,6 +235,43 @@ int sr_strip_trace_final(const SrRtParams* params, const SrPartition* p, uint32_
     SrRtParams q = *params;
     q.tile_y0 = r.final_y0; q.tile_h = r.final_h; q.tile_x0 = r.final_x0; q.tile_w = r.final_w;
     return sr_trace_final(&q, stream);
+}
+
+// The strip kernels on their own (strip_copy.hip). The launchers trust their caller (multi_renderer.cpp derives every argument
+// from a partition); these check what the launchers assume and launch nothing on a violation.
+int sr_strip_packed_bytes(const SrStripPlane* planes, uint32_t n, uint32_t w, uint32_t h, uint64_t* bytes) {
+    SrkStripPlane k[srd::kStripMaxPlanes];
+    if (!bytes) return mfail(SR_ERR_INVALID_ARG, "sr_strip_packed_bytes: null argument");
+    int rc = check_planes(planes, n, "sr_strip_packed_bytes", false, k);
+    if (rc != SR_OK) return rc;
+    *bytes = srk_strip_packed_bytes(k, n, w, h);
+    return SR_OK;
+}
+
+int sr_strip_pack(const SrStripPlane* planes, uint32_t n, uint32_t width, uint32_t height, uint32_t x0, uint32_t w, uint32_t y0,
+                  uint32_t h, void* packed, void* stream) {
+    return strip_copy(true, "sr_strip_pack", planes, n, width, height, x0, w, y0, h, packed, stream);
+}
+
+int sr_strip_unpack(const SrStripPlane* planes, uint32_t n, uint32_t width, uint32_t height, uint32_t x0, uint32_t w, uint32_t y0,
+                    uint32_t h, const void* packed, void* stream) {
+    return strip_copy(false, "sr_strip_unpack", planes, n, width, height, x0, w, y0, h, const_cast<void*>(packed), stream);
+}
+
+int sr_history_reach_check(const uint32_t* motion, uint32_t width, uint32_t height, uint32_t axis, uint32_t x0, uint32_t w,
+                           uint32_t y0, uint32_t h, uint32_t held_lo, uint32_t held_hi, uint64_t* counter, void* stream) {
+    const std::string name = "sr_history_reach_check";
+    if (!motion || !counter) return mfail(SR_ERR_INVALID_ARG, name + ": null argument");
+    if ((uintptr_t)motion % 4 != 0 || (uintptr_t)counter % 8 != 0) return mfail(SR_ERR_INVALID_ARG, name + ": misaligned pointer");
+    if (axis != SR_AXIS_COLS && axis != SR_AXIS_ROWS) return mfail(SR_ERR_INVALID_ARG, name + ": axis must be SR_AXIS_COLS or SR_AXIS_ROWS");
+    int rc = check_rect(name, width, height, x0, w, y0, h);
+    if (rc != SR_OK) return rc;
+    if (held_lo > held_hi || held_hi > (axis == SR_AXIS_COLS ? width : height)) return mfail(SR_ERR_INVALID_ARG, name + ": held region must satisfy held_lo <= held_hi <= the axis length");
+    if (w == 0 || h == 0) return SR_OK;
+    int e = srk_launch_history_reach_check(motion, width, height, axis, x0, w, y0, h, held_lo, held_hi,
+                                           reinterpret_cast<unsigned long long*>(counter), (hipStream_t)stream);
+    if (e != 0) return mfail(SR_ERR_HIP, name + " launch: " + hipGetErrorString((hipError_t)e));
+    return SR_OK;
 }
 
 }  // extern "C"

@@ -432,6 +432,50 @@ def post_chain(frame, frame_count, exposure=1.0, denoise_passes=4):
     check(lib().sr_post_tonemap(C.byref(p), _stream()))
 
 
+def _addr(x):
+    return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
+
+
+def _strip_planes(planes):
+    """[(tensor or device address, bytes per pixel)] -> SrStripPlane array."""
+    arr = (abi.SrStripPlane * max(len(planes), 1))()
+    for i, (img, bpp) in enumerate(planes):
+        arr[i].img, arr[i].bpp = _addr(img), bpp
+    return arr
+
+
+def strip_packed_bytes(bpps, w, h):
+    """Size of the packed form of a w x h rectangle of planes with these bytes per pixel (sr_strip_packed_bytes)."""
+    n = C.c_uint64()
+    check(lib().sr_strip_packed_bytes(_strip_planes([(0, b) for b in bpps]), C.c_uint32(len(bpps)), C.c_uint32(w), C.c_uint32(h), C.byref(n)))
+    return n.value
+
+
+def _strip_copy(fn, planes, size, rect, packed, stream):
+    (W, H), (x0, w, y0, h) = size, rect
+    check(fn(_strip_planes(planes), C.c_uint32(len(planes)), C.c_uint32(W), C.c_uint32(H), C.c_uint32(x0), C.c_uint32(w),
+             C.c_uint32(y0), C.c_uint32(h), _addr(packed), _stream() if stream is None else C.c_void_p(stream)))
+
+
+def strip_pack(planes, size, rect, packed, stream=None):
+    """sr_strip_pack: rectangle (x0, w, y0, h) of the planes [(tensor or address, bpp)] of (W, H) images -> packed."""
+    _strip_copy(lib().sr_strip_pack, planes, size, rect, packed, stream)
+
+
+def strip_unpack(planes, size, rect, packed, stream=None):
+    """sr_strip_unpack: packed -> rectangle (x0, w, y0, h) of the planes."""
+    _strip_copy(lib().sr_strip_unpack, planes, size, rect, packed, stream)
+
+
+def history_reach_check(motion, size, axis, rect, held, counter, stream=None):
+    """sr_history_reach_check: adds to the device uint64 at `counter` the pixels of rectangle (x0, w, y0, h) whose history read
+    may leave held = (lo, hi) along `axis` (abi.AXIS_COLS / AXIS_ROWS)."""
+    (W, H), (x0, w, y0, h) = size, rect
+    check(lib().sr_history_reach_check(_addr(motion), C.c_uint32(W), C.c_uint32(H), C.c_uint32(axis), C.c_uint32(x0), C.c_uint32(w),
+                                       C.c_uint32(y0), C.c_uint32(h), C.c_uint32(held[0]), C.c_uint32(held[1]), _addr(counter),
+                                       _stream() if stream is None else C.c_void_p(stream)))
+
+
 def _instance_arrays(instances):
     keys = np.array([k for k, _ in instances], dtype=np.uint64)
     counts = np.array([len(t) for _, t in instances], dtype=np.uint32)

@@ -1,6 +1,8 @@
 """The round-1/2 Python implementations of the strip geometry and plans (Partition, balanced_bounds, axis_cost_from_tiles,
 history_exchange_plan), kept as the reference the C++ port behind the C ABI (csrc/multi_gpu.cpp, sr_partition_* /
-sr_balanced_bounds / sr_axis_cost_from_tiles / sr_history_exchange_plan) is checked against (tests/test_host_abi.py)."""
+sr_balanced_bounds / sr_axis_cost_from_tiles / sr_history_exchange_plan) is checked against (tests/test_host_abi.py), and the
+models of the multi-device renderer's strip kernels (csrc/strip_copy.hip): pack / unpack as numpy slice copies, the
+history-reach check restated on hand-workable scalars and, operation for operation, in vectorised fp32."""
 SPATIAL_HALO = 30
 
 
@@ -105,3 +107,122 @@ def history_exchange_plan(part, motion_halo):
                 if x1 > x0:
                     plan.append((src, dst, x0, x1 - x0))
     return plan
+
+
+# ---- strip_pack_kernel / strip_unpack_kernel (csrc/strip_copy.hip) as a byte model ---------------------------------------------
+def access_unit(W, x0, w, bpp):
+    """Widest access (16, 8, 4 or 2 bytes) every row segment of a plane is aligned to: from x0 * bpp, W * bpp and w * bpp."""
+    for u in (16, 8, 4):
+        if (x0 * bpp) % u == 0 and (W * bpp) % u == 0 and (w * bpp) % u == 0:
+            return u
+    return 2
+
+
+def packed_layout(bpps, w, h):
+    """(byte offset of every plane's block, total size): plane after plane, every block padded to 16 bytes."""
+    offs, off = [], 0
+    for bpp in bpps:
+        offs.append(off)
+        off += (w * h * bpp + 15) & ~15
+    return offs, off
+
+
+def pack_model(images, bpps, rect, packed_before):
+    """The packed buffer after packing rectangle (x0, w, y0, h) of `images` ([H, W * bpp] uint8 arrays) over `packed_before`:
+    rows in order within a plane; the padding between blocks and everything behind the last block keep their bytes."""
+    import numpy as np
+    x0, w, y0, h = rect
+    offs, total = packed_layout(bpps, w, h)
+    out = np.array(packed_before, dtype=np.uint8, copy=True)
+    assert out.size >= total
+    for img, bpp, off in zip(images, bpps, offs):
+        out[off:off + w * h * bpp] = img[y0:y0 + h, x0 * bpp:(x0 + w) * bpp].reshape(-1)
+    return out
+
+
+def unpack_model(images, bpps, rect, packed):
+    """The images after unpacking `packed` into rectangle (x0, w, y0, h): slice assignment, every other byte kept."""
+    import numpy as np
+    x0, w, y0, h = rect
+    offs, _ = packed_layout(bpps, w, h)
+    out = [np.array(img, dtype=np.uint8, copy=True) for img in images]
+    for img, bpp, off in zip(out, bpps, offs):
+        img[y0:y0 + h, x0 * bpp:(x0 + w) * bpp] = packed[off:off + w * h * bpp].reshape(h, w * bpp)
+    return out
+
+
+# ---- restatement of history_reach_check_kernel (csrc/strip_copy.hip) ----------------------------------------------------------
+def held_region(bounds, slot, motion_halo):
+    """[lo, hi) along the axis a slot holds exact history for: its strip grown by SR_SPATIAL_HALO + motion_halo, clipped."""
+    length = bounds[-1]
+    grow = SPATIAL_HALO + motion_halo
+    return max(bounds[slot] - grow, 0), min(bounds[slot + 1] + grow, length)
+
+
+def read_range(p, mv, n):
+    """Conservative [lo, hi] pixel range of the temporal read of pixel p (index along the axis) whose stored half-precision motion
+    component is mv, in an image n pixels long; None when the range lies outside the image."""
+    import math
+    import numpy as np
+    m = float(np.float32(np.float16(mv)))
+    c = (p + 0.5) - m * n
+    e = abs(m) * n / 1024.0 + 1.0
+    lo, hi = max(math.floor(c - e - 0.5), 0), min(math.ceil(c + e + 0.5), n - 1)
+    return (lo, hi) if lo <= hi else None
+
+
+def counted(p, mv, n, held):
+    r = read_range(p, mv, n)
+    return r is not None and (r[0] < held[0] or r[1] >= held[1])
+
+
+def half_bits_to_f32(bits):
+    import numpy as np
+    with np.errstate(invalid="ignore"):                       # signalling NaN patterns convert to quiet ones
+        return np.asarray(bits, dtype=np.uint16).view(np.float16).astype(np.float32)
+
+
+NO_HISTORY, NOT_A_MOTION, IN_RANGE = 0, 1, 2
+
+
+def reach_f32(motion, pos, n, cols, clip=True):
+    """The kernel's per-pixel decision up to the held test, operation for operation in fp32 (numpy rounds every operation on its
+    own: no contraction). motion: uint32 R16G16_SFLOAT words; pos: the pixels' positions along the axis; n: the axis length;
+    cols: the axis is x. Returns (kind, lo, hi): kind NO_HISTORY (the other component or this one marks an invalid reprojection:
+    skipped), NOT_A_MOTION (always counted) or IN_RANGE with the clipped integer range [lo, hi] (empty when lo > hi)."""
+    import numpy as np
+    f = np.float32
+    motion = np.asarray(motion, dtype=np.uint32)
+    mx, my = half_bits_to_f32(motion & 0xFFFF), half_bits_to_f32(motion >> 16)
+    with np.errstate(invalid="ignore", over="ignore"):
+        skip = (mx > f(1.5)) | (my > f(1.5))
+        m = mx if cols else my
+        bad = ~(np.abs(m) <= f(1.5))
+        ms = np.where(bad, f(0), m).astype(f)
+        c = (np.asarray(pos).astype(f) + f(0.5)) - ms * f(n)
+        e = np.abs(ms) * f(n) * f(1.0 / 1024.0) + f(1.0)
+        assert c.dtype == f and e.dtype == f
+        lo = np.floor(c - e - f(0.5)).astype(np.int64)
+        hi = np.ceil(c + e + f(0.5)).astype(np.int64)
+    if clip:                                                  # clip=False: the range before the clip (tests measure slack on it)
+        lo = np.maximum(lo, 0)
+        hi = np.minimum(hi, n - 1)
+    kind = np.where(skip, NO_HISTORY, np.where(bad, NOT_A_MOTION, IN_RANGE))
+    return kind, lo, hi
+
+
+def reach_counted_f32(motion, pos, n, cols, held_lo, held_hi):
+    """Per pixel: does history_reach_check_kernel count it for the held region [held_lo, held_hi)?"""
+    kind, lo, hi = reach_f32(motion, pos, n, cols)
+    return (kind == NOT_A_MOTION) | ((kind == IN_RANGE) & (lo <= hi) & ((lo < held_lo) | (hi >= held_hi)))
+
+
+def reach_counts_f32(motion, pos, n, cols, helds):
+    """The count the kernel adds for the pixels given, for each held region [lo, hi) of `helds`."""
+    import numpy as np
+    kind, lo, hi = reach_f32(motion, pos, n, cols)
+    always = int((kind == NOT_A_MOTION).sum())
+    live = (kind == IN_RANGE) & (lo <= hi)
+    lo, hi = lo[live][None, :], hi[live][None, :]
+    helds = np.asarray(helds, dtype=np.int64).reshape(-1, 2)
+    return always + ((lo < helds[:, :1]) | (hi >= helds[:, 1:])).sum(axis=1)

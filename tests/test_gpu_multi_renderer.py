@@ -248,3 +248,68 @@ def test_real_devices_equal_single_device(rt, hip, n):
         assert_equal(want[f][0], got[f][0], "frame %d output, devices 0..%d" % (f, n - 1))
         assert_equal(want[f][1], got[f][1], "frame %d raw_color, devices 0..%d" % (f, n - 1))
     assert overflow == 0 and (rays == want_rays).all()
+
+
+# ---- history_overflow() == 0 means the frames are equal: a sweep over slide and motion_halo ---------------------------------------
+def slide_camera(desc, cols, step):
+    """Slides `step` world units per frame along the axis (sideways for column strips, vertically for row strips)."""
+    def camera(_, f):
+        d = step * (f - 2)
+        off = (d, 0.0, 0.0) if cols else (0.0, d, 0.0)
+        return (tuple(p + o for p, o in zip(desc.camera_pos, off)), tuple(t + o for t, o in zip(desc.camera_target, off)), desc.fov_y)
+    return camera
+
+
+def largest_axis_motion(rt, desc, W, H, camera, frames, cols, blue_noise):
+    """Largest stored motion along the axis, in pixels, over the motion planes of frames 1 .. frames - 1 of this camera path."""
+    import strip_reference as ref
+    sc = rt.Scene(0).load(desc)
+    gf = rt.DeviceFrame(W, H, blue_noise)
+    prev, largest = None, 0.0
+    for f in range(frames):
+        pos, tgt, fov = camera(desc, f)
+        m = rt.camera_matrices(pos, tgt, fov, W, H, prev)
+        prev = list(m.view_proj)
+        sc.trace_ris(gf, m, f)
+        if f > 0:
+            words = gf.motion.cpu().numpy().view(np.uint32)
+            kind, _, _ = ref.reach_f32(words, np.zeros(words.shape), W if cols else H, cols)
+            mv = ref.half_bits_to_f32(words & 0xFFFF if cols else words >> 16)[kind == ref.IN_RANGE]
+            largest = max(largest, float(np.abs(mv).max()) * (W if cols else H))
+    sc.close()
+    return largest
+
+
+@pytest.mark.parametrize("axis,W,H", [("cols", 120, 48), ("rows", 48, 120)])
+def test_zero_history_overflow_means_equal_frames(rt, hip, blue_noise, axis, W, H):
+    desc = scenes.cornell_box()
+    cols, frames = axis == "cols", 5
+    probe = 0.1
+    per_unit = largest_axis_motion(rt, desc, W, H, slide_camera(desc, cols, probe), frames, cols, blue_noise) / probe
+    seen = []                                                # (slide, halo, overflow, differs)
+    for target in (2.0, 7.0, 13.0):
+        step = target / per_unit
+        step *= target / largest_axis_motion(rt, desc, W, H, slide_camera(desc, cols, step), frames, cols, blue_noise)
+        camera = slide_camera(desc, cols, step)
+        print("%s %dx%d: slide %.4f units per frame, largest stored motion along the axis %.2f px (aimed at %g)" % (
+            axis, W, H, step, largest_axis_motion(rt, desc, W, H, camera, frames, cols, blue_noise), target))
+        single = rt.Renderer((W, H))
+        load(single, desc)
+        want = frames_of(rt, hip, single, desc, frames, camera)
+        single.close()
+        for halo in (0, 4, 8, 16):
+            multi = rt.Renderer((W, H), devices=[0, 0, 0], axis=axis, motion_halo=halo)
+            load(multi, desc)
+            got = frames_of(rt, hip, multi, desc, frames, camera)
+            overflow = multi.history_overflow()
+            multi.close()
+            differs = any((want[f][0] != got[f][0]).any() or (want[f][1] != got[f][1]).any() for f in range(frames))
+            print("  motion_halo %2d: overflow %d, frames %s" % (halo, overflow, "differ" if differs else "equal"))
+            if overflow == 0:
+                for f in range(frames):
+                    assert_equal(want[f][0], got[f][0], "%s slide %g px halo %d: overflow 0, frame %d output" % (axis, target, halo, f))
+                    assert_equal(want[f][1], got[f][1], "%s slide %g px halo %d: overflow 0, frame %d raw_color" % (axis, target, halo, f))
+            seen.append((target, halo, overflow, differs))
+    assert any(o == 0 for _, _, o, _ in seen), seen          # not vacuous: some halo suffices for some slide ...
+    assert any(o > 0 for _, _, o, _ in seen), seen           # ... some does not ...
+    assert any(o > 0 and d for _, _, o, d in seen), seen     # ... and there the frame really differs

@@ -1,14 +1,15 @@
 """CPU-side checks of the multi-device renderer's C ABI (sr_renderer_create_multi and friends): argument errors, the no-GPU
-failure, and a restatement of the history-reach check's held region and read range (strip_copy.hip) on hand-worked cases."""
+failure, what the strip entry points (sr_strip_pack / sr_strip_unpack / sr_history_reach_check) refuse, the restatement of the
+history-reach check (strip_copy.hip; tests/strip_reference.py) on hand-worked cases, and an interval model of the RIS pass's
+temporal read that the check's formula must cover."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
-from sunray_amd import _lib, runtime as rt
-
-SPATIAL_HALO = 30
+import strip_reference as ref
+from strip_reference import counted, held_region, read_range
+from sunray_amd import _lib, abi, runtime as rt
 
 
 def has_gpu():
@@ -62,29 +63,7 @@ def test_create_multi_fails_without_gpu():
     assert _lib.lib().sr_renderer_create_multi(_devs(0, 0, 0), 3, 16, 16, 1, C.byref(h)) == -2 and not h.value
 
 
-# ---- restatement of history_reach_check_kernel (strip_copy.hip) -------------------------------------------------------------
-def held_region(bounds, slot, motion_halo):
-    """[lo, hi) along the axis a slot holds exact history for: its strip grown by SR_SPATIAL_HALO + motion_halo, clipped."""
-    length = bounds[-1]
-    grow = SPATIAL_HALO + motion_halo
-    return max(bounds[slot] - grow, 0), min(bounds[slot + 1] + grow, length)
-
-
-def read_range(p, mv, n):
-    """Conservative [lo, hi] pixel range of the temporal read of pixel p (index along the axis) whose stored half-precision motion
-    component is mv, in an image n pixels long; None when the range lies outside the image."""
-    m = float(np.float32(np.float16(mv)))
-    c = (p + 0.5) - m * n
-    e = abs(m) * n / 1024.0 + 1.0
-    lo, hi = max(math.floor(c - e - 0.5), 0), min(math.ceil(c + e + 0.5), n - 1)
-    return (lo, hi) if lo <= hi else None
-
-
-def counted(p, mv, n, held):
-    r = read_range(p, mv, n)
-    return r is not None and (r[0] < held[0] or r[1] >= held[1])
-
-
+# ---- restatement of history_reach_check_kernel (strip_copy.hip): tests/strip_reference.py --------------------------------------
 def test_held_region_hand_worked():
     b = [0, 40, 80, 120]
     assert held_region(b, 0, 16) == (0, 86)          # 40 + 30 + 16
@@ -115,3 +94,146 @@ def test_check_counts_reads_leaving_the_held_region():
     assert not counted(100, 0.0, 120, held)
     # near the edge the check may over-report (margin of one pixel and the half rounding), never under-report
     assert counted(52, 0.0, 120, (52, 120))         # the read is pixel 52 itself, but the margin reaches 51
+
+
+# ---- the formula itself: does the range the check derives from a stored motion vector cover every read the pass can make? --------
+def _all_halves():
+    bits = np.arange(65536, dtype=np.uint32)
+    with np.errstate(invalid="ignore"):                       # signalling NaN patterns
+        return bits, ref.half_bits_to_f32(bits).astype(np.float64)
+
+
+def _finite_halves_below_one():
+    bits, v = _all_halves()
+    keep = np.isfinite(v) & (np.abs(v) < 1.0)
+    return bits[keep], v[keep]
+
+
+def _rounding_interval(v):
+    """[d_lo, d_hi]: every real that rounds (to nearest) to the half value v, its two ties included."""
+    grid = np.unique(_all_halves()[1])
+    grid = grid[np.isfinite(grid)]
+    i = np.searchsorted(grid, v)
+    assert (grid[i] == v).all()
+    return (grid[i - 1] + v) / 2.0, (v + grid[i + 1]) / 2.0      # |v| < 1: both neighbours exist
+
+
+@pytest.mark.parametrize("W", [1, 2, 7, 8, 64, 120, 1920, 3840, 16384])
+def test_read_range_covers_every_read_of_the_ris_pass(W):
+    """Float64 interval model of the RIS pass's temporal read (kernels.hip; oracle/orc_passes.cpp trace_ris) against the fp32
+    restatement of the check. The pass computes prev_u in [0, 1), stores half(inUV - prev_u) with inUV = (p + 0.5) / W, and reads
+    pixel (int)(prev_u * W + (j - 0.5)), j in [0, 1). From a stored half value the true difference lies in the half's rounding
+    interval. fp32 allowance: W * 2^-21 pixels on prev_u * W, for the three fp32 roundings between the stored vector and the read
+    (inUV - prev_u, prev_u * W, the jitter sum), each at most 2^-24 relative on a value of at most W pixels: 3 * W * 2^-24 <
+    W * 2^-21. Every integer the read can produce inside the image must lie in the restatement's [lo, hi], and [lo, hi] reaches at
+    most 3 + |mv| * W * 2^-9 pixels beyond those integers."""
+    bits, v = _finite_halves_below_one()
+    d_lo, d_hi = _rounding_interval(v)
+    allowance = W * 2.0 ** -21
+    min_slack, worst_over = None, 0.0
+    for p in sorted({q for q in (0, 1, 2, W // 3, W // 2, W - 2, W - 1) if 0 <= q < W}):
+        prev_lo = np.maximum((p + 0.5) - d_hi * W - allowance, 0.0)          # prev_u * W, within [0, W]
+        prev_hi = np.minimum((p + 0.5) - d_lo * W + allowance, float(W))
+        r_lo = np.maximum(np.trunc(prev_lo - 0.5), 0.0)                      # (int) truncates: (-1, 0) reads pixel 0
+        r_hi = np.minimum(np.trunc(prev_hi + 0.5), W - 1.0)
+        reads = (prev_lo <= prev_hi) & (r_lo <= r_hi)                        # this half can be stored here and reads inside the image
+        kind, lo, hi = ref.reach_f32(bits, np.full(bits.shape, p), W, True)
+        assert (kind == ref.IN_RANGE).all()
+        missed = reads & ((lo > r_lo) | (hi < r_hi))
+        assert not missed.any(), "W %d pixel %d: reads outside [lo, hi] for half patterns %s" % (
+            W, p, ["0x%04x" % b for b in bits[missed][:8]])
+        slack = np.minimum(r_lo - lo, hi - r_hi)[reads]
+        over = (np.maximum(r_lo - lo, hi - r_hi) - (3.0 + np.abs(v) * W * 2.0 ** -9))[reads]
+        assert (over <= 0.0).all(), "W %d pixel %d: [lo, hi] over-reports by more than 3 + |mv| W 2^-9 for %s" % (
+            W, p, ["0x%04x" % b for b in bits[reads][over > 0.0][:8]])
+        if slack.size:
+            min_slack = slack.min() if min_slack is None else min(min_slack, slack.min())
+            worst_over = max(worst_over, float(np.maximum(r_lo - lo, hi - r_hi)[reads].max()))
+    print("W %d: smallest slack %s px, largest over-report %s px" % (W, min_slack, worst_over))
+    assert min_slack is not None                                             # not vacuous: some half reads inside the image
+
+
+def test_fp32_restatement_equals_hand_worked_restatement():
+    """reach_counted_f32 (what the GPU tests compare the kernel with) and the scalar read_range / counted above agree wherever
+    fp32 and float64 cannot differ: motion vectors that are multiples of 2^-7 in images 128 long (every product is exact)."""
+    n = 128
+    mvs = np.arange(-127, 128) / 128.0
+    bits = np.float16(mvs).view(np.uint16).astype(np.uint32)
+    for p in (0, 1, 63, 64, 126, 127):
+        for held in ((0, n), (0, 0), (40, 90), (0, 64), (64, n)):
+            got = ref.reach_counted_f32(bits, np.full(bits.shape, p), n, True, *held)
+            want = np.array([counted(p, m, n, held) for m in mvs])
+            assert (got == want).all(), (p, held, mvs[got != want])
+            got_rows = ref.reach_counted_f32(bits << 16, np.full(bits.shape, p), n, False, *held)
+            assert (got_rows == want).all(), (p, held)
+
+
+# ---- sr_strip_pack / sr_strip_unpack / sr_history_reach_check refuse what their launchers assume ----------------------------------
+IMG, PACKED, MOTION, COUNTER = 0x7000_0000_0000, 0x7000_0010_0000, 0x7000_0020_0000, 0x7000_0030_0000   # never dereferenced
+
+
+def _refused(call, *args, **kw):
+    with pytest.raises(_lib.SunrayError) as e:
+        call(*args, stream=0, **kw)
+    assert e.value.code == -1 and e.value.description, (args, kw)       # SR_ERR_INVALID_ARG before any launch (a launch: 0 or -2)
+    return e.value.description
+
+
+@pytest.mark.parametrize("call", [rt.strip_pack, rt.strip_unpack])
+def test_strip_copy_rejects_bad_arguments(call):
+    ok = [(IMG, 16), (IMG + 0x1000, 2)]
+    size, rect = (64, 8), (8, 16, 2, 4)
+    for n in (0, 6):
+        assert "n_planes" in _refused(call, [(IMG, 4)] * n, size, rect, PACKED)
+    for bpp in (0, 1, 3, 47):
+        assert "bytes per pixel" in _refused(call, [(IMG, 16), (IMG, bpp)], size, rect, PACKED)
+    assert "null" in _refused(call, [(IMG, 16), (0, 2)], size, rect, PACKED)
+    assert "null" in _refused(call, ok, size, rect, 0)
+    L = _lib.lib()
+    fn = L.sr_strip_pack if call is rt.strip_pack else L.sr_strip_unpack
+    assert fn(None, 2, 64, 8, 8, 16, 2, 4, C.c_void_p(PACKED), None) == -1 and b"null" in L.sr_last_error()
+    for bad in ((56, 9, 0, 8), (64, 1, 0, 1), (0, 65, 0, 8), (0, 64, 5, 4), (0, 64, 8, 1), (0, 64, 0, 9),
+                (0xFFFFFFFF, 2, 0, 1), (0, 1, 0xFFFFFFFF, 2), (0, 0, 0, 9), (65, 0, 0, 1)):
+        assert "leaves the image" in _refused(call, ok, size, bad, PACKED)
+    assert "extent" in _refused(call, ok, (0, 8), (0, 0, 0, 0), PACKED)
+    assert "extent" in _refused(call, ok, (65536, 32768), rect, PACKED)
+    for off in (2, 4, 8):
+        assert "aligned" in _refused(call, [(IMG, 16), (IMG + off, 2)], size, rect, PACKED)
+        assert "aligned" in _refused(call, ok, size, rect, PACKED + off)
+    for empty in ((8, 0, 2, 4), (8, 16, 2, 0), (64, 0, 8, 0)):              # an empty rectangle inside the image: a no-op
+        call(ok, size, empty, PACKED, stream=0)
+
+
+def test_history_reach_check_rejects_bad_arguments():
+    size, rect = (64, 8), (8, 16, 2, 4)
+    cols, rows = abi.AXIS_COLS, abi.AXIS_ROWS
+    chk = rt.history_reach_check
+    assert "null" in _refused(chk, 0, size, cols, rect, (0, 64), COUNTER)
+    assert "null" in _refused(chk, MOTION, size, cols, rect, (0, 64), 0)
+    assert "aligned" in _refused(chk, MOTION + 2, size, cols, rect, (0, 64), COUNTER)
+    assert "aligned" in _refused(chk, MOTION, size, cols, rect, (0, 64), COUNTER + 4)
+    assert "axis" in _refused(chk, MOTION, size, 2, rect, (0, 8), COUNTER)
+    for bad in ((56, 9, 0, 8), (0, 64, 5, 4), (0xFFFFFFFF, 2, 0, 1), (0, 1, 0xFFFFFFFF, 2), (65, 0, 0, 1)):
+        assert "leaves the image" in _refused(chk, MOTION, size, cols, bad, (0, 64), COUNTER)
+    assert "extent" in _refused(chk, MOTION, (64, 0), cols, (0, 0, 0, 0), (0, 0), COUNTER)
+    for axis, held in ((cols, (9, 8)), (cols, (0, 65)), (cols, (65, 65)), (rows, (0, 9)), (rows, (5, 4)), (rows, (0, 64))):
+        assert "held" in _refused(chk, MOTION, size, axis, rect, held, COUNTER)
+    for empty in ((8, 0, 2, 4), (8, 16, 2, 0)):
+        chk(MOTION, size, cols, empty, (0, 64), COUNTER, stream=0)
+        chk(MOTION, size, rows, empty, (8, 8), COUNTER, stream=0)
+
+
+def test_strip_packed_bytes_equals_the_model():
+    for bpps in ([2], [16, 2, 4, 4, 4], [48, 48], [8, 2], [4, 4, 4]):
+        for w, h in ((1, 1), (3, 1), (7, 9), (65, 3), (200, 9), (0, 5), (5, 0)):
+            assert rt.strip_packed_bytes(bpps, w, h) == ref.packed_layout(bpps, w, h)[1], (bpps, w, h)
+    L, n = _lib.lib(), C.c_uint64()
+    planes = (abi.SrStripPlane * 6)()
+    for p in planes:
+        p.bpp = 4
+    assert L.sr_strip_packed_bytes(planes, 6, 4, 4, C.byref(n)) == -1
+    assert L.sr_strip_packed_bytes(planes, 0, 4, 4, C.byref(n)) == -1
+    assert L.sr_strip_packed_bytes(planes, 2, 4, 4, None) == -1
+    assert L.sr_strip_packed_bytes(None, 2, 4, 4, C.byref(n)) == -1
+    planes[1].bpp = 3
+    assert L.sr_strip_packed_bytes(planes, 2, 4, 4, C.byref(n)) == -1 and b"bytes per pixel" in L.sr_last_error()
