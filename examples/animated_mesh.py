@@ -1,7 +1,9 @@
 """A deforming mesh through Renderer.update_mesh (the reference's Blas::update, acceleration_structure/blas.rs:285-310): the
 Cornell box's sphere ripples for a number of frames; every frame replaces the sphere's vertices in place and renders, the
 acceleration structure is updated in place (re-flatten + refit) or, after the update budget, fast-rebuilt on the device, as the
-heuristic picks; it is never torn down and rebuilt on the host. Writes the last frame as a PNG.
+heuristic picks; it is never torn down and rebuilt on the host. The sphere is declared RapidlyChanging (the reference's
+BuildType of a BLAS that is built with ALLOW_UPDATE): where the scene stands in the two-level form (SR_INSTANCING=two_level, or a
+scene large enough for the automatic choice) its own tree is then refitted on the device as well. Writes the last frame as a PNG.
 
     python examples/animated_mesh.py [out.png] [--frames 24] [--size 640x480]
 
@@ -22,13 +24,14 @@ def main():
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--size", default="640x480")
     args = ap.parse_args()
-    from sunray_amd import runtime as rt, scenes
+    from sunray_amd import abi, runtime as rt, scenes
     w, h = (int(v) for v in args.size.split("x"))
     desc = scenes.cornell_box()
     sphere = next(m for m in desc.meshes if m.key == 7)
     r = rt.Renderer((w, h))
     for m in desc.meshes:
         r.load_mesh(m.key, m.vertices, m.indices, m.material)
+    r.set_mesh_build_type(sphere.key, abi.BUILD_RAPIDLY_CHANGING)
     camera = (desc.camera_pos, desc.camera_target, desc.fov_y)
     for f in range(args.frames):
         if f:

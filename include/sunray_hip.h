@@ -431,8 +431,8 @@ int sr_scene_remove(SrScene* scene, uint64_t key);
  * into the mesh's existing device allocation (waits for the device) and rewrites the positions of its entries of the emissive
  * table in their slots. The structure is not reset: several meshes may be updated, then ONE sr_scene_set_instances applies them
  * all with the operation the heuristic picks (SR_OP_UPDATE re-flattens, rewrites the per-slot shading records and refits on
- * the device; the builds read the new vertices anyway; in the two-level form only the updated meshes' trees are rebuilt, on the
- * host). Between the update of a mesh that the built structure instances and that sr_scene_set_instances, the tracing calls,
+ * the device; the builds read the new vertices anyway; in the two-level form the trees of the updated meshes are refitted on the
+ * device where sr_scene_set_mesh_build_type allows it and rebuilt on the host otherwise). Between the update of a mesh that the built structure instances and that sr_scene_set_instances, the tracing calls,
  * sr_scene_read_bvh and sr_scene_end_frame return SR_ERR_STATE. `vertices` is a HOST pointer. */
 int sr_scene_update_mesh(SrScene* scene, uint64_t key, const SrVertex* vertices, uint32_t n_vertices);
 /* Figures of the last sr_scene_update_mesh and of the sr_scene_set_instances that applied it. The kernel times are taken with
@@ -442,15 +442,43 @@ typedef struct SrMeshUpdateInfo {
     uint32_t reshaded;         /* 1: its SR_OP_UPDATE ran the variant that rewrites the shading records */
     uint32_t blas_rebuilt;     /* two-level form: per-mesh trees it built, i.e. the invalidated ones: every mesh updated since its tree
                                 * was built, instanced at the time or not (baked copies of single instances not counted) */
-    uint32_t _pad;
+    uint32_t blas_refitted;    /* two-level form: per-mesh trees it refitted on the device (sr_scene_set_mesh_build_type) */
     double validate_copy_ms;   /* sr_scene_update_mesh: validation + host copy + emissive entries */
     double h2d_ms;             /* sr_scene_update_mesh: device wait + copy into the device allocation */
     double tables_ms;          /* SR_OP_UPDATE: instance tables + light table, built and uploaded */
-    double flatten_ms;         /* SR_OP_UPDATE: flatten (+ reshade) kernel */
-    double refit_ms;           /* SR_OP_UPDATE: refit kernels, all levels */
+    double flatten_ms;         /* SR_OP_UPDATE: flatten (+ reshade) kernel; mesh-tree refit: the record-rewrite kernel */
+    double refit_ms;           /* SR_OP_UPDATE: refit kernels, all levels; mesh-tree refit: its refit launches */
     double blas_build_ms;      /* two-level form: host builds of the per-mesh trees counted in blas_rebuilt */
 } SrMeshUpdateInfo;
 int sr_scene_mesh_update_info(const SrScene* scene, SrMeshUpdateInfo* out);
+/* BuildType of one mesh's tree (blas.rs:149-161: RapidlyChanging and SometimesChanges are built with ALLOW_UPDATE, Static is not).
+ * Every loaded mesh starts as SR_BUILD_STATIC (Renderer::load_mesh, lib.rs:937): it is never refitted, every update rebuilds its
+ * tree on the host. An updatable mesh holds an SrAsState of its own (reset to sr_as_state_initial(build_type) by this call), driven
+ * as Blas::plan_op / mark_built drive it. In the two-level form the sr_scene_set_instances that applies an update refits the
+ * mesh's tree on the device (Blas::update, blas.rs:292-310) while the state asks for SR_OP_UPDATE: leaf-order records, root box
+ * and padding numbers are rewritten from the new vertices with the bytes a host build writes, the quantised nodes are refitted
+ * bottom-up; topology, leaf order and stack need stay, and the top level may then be built on the device (SR_TL_BUILD_*). After
+ * more than 8 updates since its last rebuild the state asks for SR_OP_FAST_BUILD: that is the host build (there is no device
+ * builder for mesh trees). The host build also takes over, silently and counted in blas_rebuilt, where the scene does not stand
+ * in the two-level form with its mesh trees resident, where the previous or the new instance list holds an instance that needs a
+ * baked copy of its mesh, and for every refitted mesh whenever the mesh trees are uploaded again (a host build, a mesh added or
+ * removed, a form switch): refits and rebuilds do not mix within one call. sr_scene_end_frame counts a quiet frame for every
+ * updatable mesh and rebuilds the tree of one that asks for its settle build. sr_scene_force_next_op(SR_OP_UPDATE) forces the
+ * refit of the updated updatable meshes whatever their counters say, a forced build forces the host rebuild. The type has no
+ * effect in the one-level form, which updates in place whatever the type: it is accepted and remembered there. Unknown key or a
+ * type above SR_BUILD_STATIC: SR_ERR_INVALID_ARG. */
+int sr_scene_set_mesh_build_type(SrScene* scene, uint64_t key, uint32_t build_type);
+/* The mesh's build type, its own heuristic state and the operation the last sr_scene_set_instances / sr_scene_end_frame performed
+ * on its tree in the two-level form (SR_OP_UPDATE: device refit, SR_OP_FAST_BUILD / SR_OP_SLOW_BUILD: host build). Any pointer
+ * may be NULL. */
+int sr_scene_mesh_as_state(const SrScene* scene, uint64_t key, uint32_t* build_type, SrAsState* state, uint32_t* last_op);
+/* Harness read-back of one mesh's part of the concatenated device arrays of a scene built in the two-level form (the counterpart
+ * of sr_scene_read_top_level): n_nodes x 16 dwords with references local to the mesh, then per leaf-order slot 12 floats
+ * (v0, v1, v2, primitive, 0, 0), 12 floats of `shade`, 24 floats of `shade_tex` (zeros where the scene has no textured
+ * records), and per primitive its slot. Any pointer may be NULL (the counts alone size the arrays). SR_ERR_STATE when the scene
+ * is not built in the two-level form or an update of the mesh is pending. */
+int sr_scene_read_mesh_tree(const SrScene* scene, uint64_t key, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* nodes, float* tris,
+                            float* shade, float* shade_tex, uint32_t* slot_of_prim);
 
 /* Image::new_from_data (image/mod.rs:82-111): `channels` = 1..4 bytes per texel; fewer than 4 are
  * widened to R8G8B8A8_UNORM with the missing channels 0x00 (utils.rs:27-43), no sRGB decode. Host
@@ -676,6 +704,8 @@ int sr_renderer_unload_mesh(SrRenderer* renderer, uint64_t key);
 /* sr_scene_update_mesh on every device slot's scene; the next sr_renderer_render re-submits its instance list, which applies
  * the update. Each scene waits for its device, so frames in flight have finished reading the old vertices before they change. */
 int sr_renderer_update_mesh(SrRenderer* renderer, uint64_t key, const SrVertex* vertices, uint32_t n_vertices);
+/* sr_scene_set_mesh_build_type on every device slot's scene. */
+int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t build_type);
 
 /* Harness access: inner scene (counters, stats), device pointers of the RGBA8 output and the fp32 radiance OF THE LAST
  * SUBMITTED FRAME (valid after sr_renderer_wait_frame of that frame), and relative_frame_count. Any out pointer may be NULL.

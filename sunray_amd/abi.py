@@ -155,7 +155,7 @@ class SrTopLevelInfo(C.Structure):  # the last top-level build of a two-level sc
 
 
 class SrMeshUpdateInfo(C.Structure):  # the last sr_scene_update_mesh and the sr_scene_set_instances that applied it
-    _fields_ = [("dirty_meshes", C.c_uint32), ("reshaded", C.c_uint32), ("blas_rebuilt", C.c_uint32), ("_pad", C.c_uint32),
+    _fields_ = [("dirty_meshes", C.c_uint32), ("reshaded", C.c_uint32), ("blas_rebuilt", C.c_uint32), ("blas_refitted", C.c_uint32),
                 ("validate_copy_ms", C.c_double), ("h2d_ms", C.c_double), ("tables_ms", C.c_double), ("flatten_ms", C.c_double),
                 ("refit_ms", C.c_double), ("blas_build_ms", C.c_double)]
 

@@ -137,8 +137,25 @@ struct SrScene {
         float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // root box, object space
         float max_edge_sum = 0.0f, max_abs_vertex = 0.0f;
         double build_ms = 0.0;
+        bool host_stale = false;            // refitted on the device since: nodes / tris / shade / shade_tex above hold the old vertices
+                                            // (topology, slot_of_prim, counts, max_stack and the read-back lo, hi, max_* are current)
     };
     std::vector<HostBlas> blases;           // by mesh slot
+    // per-mesh maintenance (Blas::plan_op / mark_built, blas.rs:245-310): build type, heuristic state, what the last
+    // sr_scene_set_instances / sr_scene_end_frame did to the mesh's tree
+    struct MeshAs {
+        uint32_t build_type = SR_BUILD_STATIC;   // Renderer::load_mesh builds Static (lib.rs:937)
+        SrAsState state{0, 0, 0, 0};
+        uint32_t last_op = SR_OP_NONE;
+        bool refit_pending = false;         // updated (sr_scene_update_mesh) while its tree was valid: the next sr_scene_set_instances refits or rebuilds it
+        bool built_once = false, rebuilt_now = false, refit_now = false;
+    };
+    std::vector<MeshAs> mesh_as;            // by mesh slot
+    // device refit of mesh trees: box scratch over d_blas_nodes (allocated at the first refit), and what belongs to the set of
+    // meshes refitted last (an animation refits the same set every frame): rewrite-kernel rows, node lists by level, accumulators
+    DeviceBuffer d_blas_node_box, d_refit_meshes, d_refit_nodes, d_refit_acc, d_refit_acc_init, d_refit_out;
+    std::vector<uint32_t> refit_set, refit_level_offsets;
+    uint32_t refit_threads = 0;
     std::vector<uint32_t> blas_node_base, blas_tri_base;   // of the concatenated device arrays, by mesh slot
     bool blas_device_current = false;       // the concatenated arrays match the current set of meshes
     bool any_textured_tl = false;
@@ -295,6 +312,7 @@ int sr_scene_destroy(SrScene* s) {
     s->d_lights.release(); s->d_misc.release();
     s->d_blas_nodes.release(); s->d_tl_inst.release(); s->d_tl_instances.release();
     s->d_tl_mesh_rows.release(); s->d_tl_boxes.release(); s->d_tl_result.release();
+    s->d_blas_node_box.release(); s->d_refit_meshes.release(); s->d_refit_nodes.release(); s->d_refit_acc.release(); s->d_refit_acc_init.release(); s->d_refit_out.release();
     for (auto& ts : s->schedules) { ts.cost.release(); ts.order.release(); }
     for (auto& pool : s->events) for (auto& e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     delete s;
@@ -374,6 +392,8 @@ int sr_scene_add_blas(SrScene* s, uint64_t key, const SrVertex* vertices, uint32
     s->built = false;
     if (s->blases.size() < s->meshes.size()) s->blases.resize(s->meshes.size());
     s->blases[slot] = SrScene::HostBlas();
+    if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
+    s->mesh_as[slot] = SrScene::MeshAs();
     s->blas_device_current = false;
     if (out_slot) *out_slot = slot;
     return SR_OK;
@@ -408,6 +428,7 @@ int sr_scene_remove(SrScene* s, uint64_t key) {
     for (uint32_t es : m.emissive_slots) s->free_emissive_slots.push_back(es);
     m = srh::HostMesh();
     if (slot < s->blases.size()) s->blases[slot] = SrScene::HostBlas();
+    if (slot < s->mesh_as.size()) s->mesh_as[slot] = SrScene::MeshAs();
     if (slot < s->mesh_dirty.size()) s->mesh_dirty[slot] = 0;
     s->blas_device_current = false;
     s->free_mesh_slots.push_back(slot);
@@ -454,10 +475,16 @@ int sr_scene_update_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uin
         memcpy(et.v1, m.vertices[m.indices[3 * k + 1]].position, 12);
         memcpy(et.v2, m.vertices[m.indices[3 * k + 2]].position, 12);
     }
-    // two-level form: this mesh's object-space tree, root box and padding numbers are stale; the other meshes keep theirs
-    if (slot < s->blases.size()) s->blases[slot].valid = false;
-    s->blas_device_current = false;
-    s->tl_mesh_rows_current = false;
+    // two-level form: this mesh's object-space tree, root box and padding numbers are stale; the other meshes keep theirs. An
+    // updatable mesh (sr_scene_set_mesh_build_type) with a valid tree keeps it: the next sr_scene_set_instances refits it on the
+    // device where it can (refit_mesh_trees) and invalidates it otherwise
+    if (slot < s->mesh_as.size() && s->mesh_as[slot].build_type != SR_BUILD_STATIC && slot < s->blases.size() && s->blases[slot].valid)
+        s->mesh_as[slot].refit_pending = true;
+    else {
+        if (slot < s->blases.size()) s->blases[slot].valid = false;
+        s->blas_device_current = false;
+        s->tl_mesh_rows_current = false;
+    }
     if (s->built) {
         bool instanced = false;
         for (const auto& in : s->fid.instances) if (in.mesh_slot == slot) { instanced = true; break; }
@@ -748,6 +775,17 @@ int build_blas(const srh::HostMesh& mesh, uint32_t mesh_slot, const SrTransform*
     return SR_OK;
 }
 
+// The host build of one mesh's tree (the only mesh-tree build there is: the project has no device builder for mesh trees).
+int rebuild_mesh_tree(SrScene* s, uint32_t m) {
+    s->blases[m] = SrScene::HostBlas();
+    int rc = build_blas(s->meshes[m], m, nullptr, s->blases[m]);
+    if (rc != SR_OK) return rc;
+    s->mu_info.blas_rebuilt++; s->mu_info.blas_build_ms += s->blases[m].build_ms;
+    if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
+    s->mesh_as[m].rebuilt_now = true; s->mesh_as[m].refit_pending = false;
+    return SR_OK;
+}
+
 // Appends one tree with its triangle / shade / primitive -> slot records to the concatenated host arrays (references become global).
 struct BlasCat {
     std::vector<uint32_t> nodes, slot_of_prim;
@@ -784,7 +822,8 @@ int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
     BlasCat cat;
     for (size_t m = 0; m < nm; m++) {
         if (s->meshes[m].n_vertices == 0) continue;
-        if (!s->blases[m].valid) { s->blases[m] = SrScene::HostBlas(); if ((rc = build_blas(s->meshes[m], (uint32_t)m, nullptr, s->blases[m])) != SR_OK) return rc; s->mu_info.blas_rebuilt++; s->mu_info.blas_build_ms += s->blases[m].build_ms; }
+        // a host copy that a device refit left behind holds the old vertices: it is rebuilt before it is uploaded again
+        if (!s->blases[m].valid || s->blases[m].host_stale || (m < s->mesh_as.size() && s->mesh_as[m].refit_pending)) { if ((rc = rebuild_mesh_tree(s, (uint32_t)m)) != SR_OK) return rc; }
         cat.textured = cat.textured || !s->blases[m].shade_tex.empty();
     }
     s->blas_node_base.assign(nm, 0u); s->blas_tri_base.assign(nm, 0u);
@@ -806,6 +845,7 @@ int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
     s->blas_device_current = true;
     s->tl_baked = !baked.empty();
     s->tl_mesh_rows_current = false;
+    s->refit_set.clear();                     // node and triangle bases moved
     return SR_OK;
 }
 
@@ -907,6 +947,153 @@ int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0,
     return SR_OK;
 }
 
+// Whether two_level_build gives an instance with this transform a baked copy of its mesh: its test, with its expressions.
+bool instance_is_baked(const float* M) {
+    const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
+    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+    const double det = a00 * c00 + a01 * c01 + a02 * c02;
+    const double id = 1.0 / det;
+    const double R[9] = {c00 * id, (a02 * a21 - a01 * a22) * id, (a01 * a12 - a02 * a11) * id,
+                         c01 * id, (a00 * a22 - a02 * a20) * id, (a02 * a10 - a00 * a12) * id,
+                         c02 * id, (a01 * a20 - a00 * a21) * id, (a00 * a11 - a01 * a10) * id};
+    const double T[3] = {M[3], M[7], M[11]};
+    double r_norm = 0.0, m_norm = 0.0;
+    bool finite = std::isfinite(id) && det != 0.0;
+    for (int row = 0; row < 3; row++) {
+        for (int c = 0; c < 3; c++) finite = finite && std::isfinite((float)R[3 * row + c]);
+        finite = finite && std::isfinite((float)(-(R[3 * row] * T[0] + R[3 * row + 1] * T[1] + R[3 * row + 2] * T[2])));
+        r_norm = std::max(r_norm, std::fabs(R[3 * row]) + std::fabs(R[3 * row + 1]) + std::fabs(R[3 * row + 2]));
+        m_norm = std::max(m_norm, std::fabs((double)M[4 * row]) + std::fabs((double)M[4 * row + 1]) + std::fabs((double)M[4 * row + 2]));
+    }
+    return !finite || !(r_norm * m_norm < kTlMaxCondition);
+}
+
+// Blas::update (blas.rs:292-310) for the meshes updated since the last sr_scene_set_instances whose build type allows it
+// (refit_pending): where every one of them may be refitted, the device rewrites their leaf-order records and root boxes and
+// refits their nodes in place (bvh_gpu.hip), and the concatenated arrays stay current. Otherwise their trees are invalidated
+// and the build that follows rebuilds them on the host, as it does for a Static mesh. A host rebuild re-concatenates and
+// re-uploads every mesh's host copy, so it also takes the meshes an earlier refit left with a stale host copy (and a refit next
+// to a rebuild would be wasted: it is all or nothing per call). Runs before two_level_build, which then sees current root boxes.
+int refit_mesh_trees(SrScene* s, uint32_t forced) {
+    const size_t nm = s->meshes.size();
+    if (s->mesh_as.size() < nm) s->mesh_as.resize(nm);
+    if (s->blases.size() < nm) s->blases.resize(nm);
+    s->mu_info.blas_refitted = 0;
+    std::vector<uint32_t> set;
+    bool any_stale = false;
+    for (size_t m = 0; m < nm; m++) {
+        s->mesh_as[m].rebuilt_now = s->mesh_as[m].refit_now = false;
+        if (s->meshes[m].n_vertices == 0) continue;
+        if (s->mesh_as[m].refit_pending) set.push_back((uint32_t)m);
+        any_stale = any_stale || s->blases[m].host_stale;
+    }
+    if (set.empty() && !any_stale) return SR_OK;
+    // anything that makes the build re-concatenate the mesh trees: the form, meshes added or removed, baked copies behind the mesh
+    // trees now or in the new list
+    bool host = !s->built || !s->two_level || !s->blas_device_current || s->tl_baked;
+    for (size_t i = 0; !host && i < s->fid.instances.size(); i++) host = instance_is_baked(s->fid.instances[i].o2w.m);
+    for (size_t k = 0; !host && k < set.size(); k++) {
+        const uint32_t op = forced != SR_OP_NONE ? forced : srh::as_state_next_op(s->mesh_as[set[k]].state, true);
+        host = op != SR_OP_UPDATE || !s->blases[set[k]].valid;      // more than 8 updates since its rebuild: the host build (there is no device fast build for mesh trees)
+    }
+    if (host) {
+        for (size_t m = 0; m < nm; m++)
+            if (s->mesh_as[m].refit_pending || s->blases[m].host_stale) {
+                s->blases[m].valid = false; s->blases[m].host_stale = false; s->mesh_as[m].refit_pending = false;
+                s->blas_device_current = false; s->tl_mesh_rows_current = false;
+            }
+        return SR_OK;
+    }
+    if (set.empty()) return SR_OK;
+    int rc;
+    if (set != s->refit_set) {                // another set of meshes than last time: its rows and node lists
+        std::vector<srd::BlasRefitMesh> rows(set.size());
+        std::vector<std::vector<uint32_t>> by_depth;
+        uint32_t threads = 0;
+        for (size_t k = 0; k < set.size(); k++) {
+            const uint32_t m = set[k];
+            const SrScene::HostBlas& b = s->blases[m];
+            srd::BlasRefitMesh& r = rows[k];
+            r.vertices = (uint64_t)(uintptr_t)s->meshes[m].d_vertices; r.indices = (uint64_t)(uintptr_t)s->meshes[m].d_indices;
+            r.tri_base = s->blas_tri_base[m]; r.n_tris = b.n_tris; r.n_vertices = s->meshes[m].n_vertices;
+            r.first_thread = threads; r.mesh_slot = m; r.textured = b.shade_tex.empty() ? 0u : 1u;
+            threads += (b.n_tris + 63u) & ~63u;
+            std::vector<uint32_t> nodes, offsets;       // deepest level first; the topology of the host copy is never stale
+            srh::tree_levels(b.nodes, nodes, offsets);
+            const size_t levels = offsets.size() - 1;
+            if (by_depth.size() < levels) by_depth.resize(levels);
+            for (size_t l = 0; l < levels; l++)
+                for (uint32_t q = offsets[l]; q < offsets[l + 1]; q++) by_depth[levels - 1 - l].push_back(s->blas_node_base[m] + nodes[q]);
+        }
+        std::vector<uint32_t> list;
+        s->refit_level_offsets.assign(1, 0u);
+        for (size_t d = by_depth.size(); d-- > 0;) { list.insert(list.end(), by_depth[d].begin(), by_depth[d].end()); s->refit_level_offsets.push_back((uint32_t)list.size()); }
+        std::vector<uint32_t> init(set.size() * 8);
+        for (size_t k = 0; k < set.size(); k++) {       // order-preserving encoding (bvh_gpu.hip enc_f) of +inf x 3, -inf x 3, 0, 0
+            uint32_t* q = &init[k * 8];
+            q[0] = q[1] = q[2] = 0xFF800000u; q[3] = q[4] = q[5] = 0x007FFFFFu; q[6] = q[7] = 0x80000000u;
+        }
+        if ((rc = s->d_refit_meshes.upload(rows.data(), rows.size() * sizeof(srd::BlasRefitMesh))) != SR_OK ||
+            (rc = s->d_refit_nodes.upload(list.data(), list.size() * 4)) != SR_OK ||
+            (rc = s->d_refit_acc_init.upload(init.data(), init.size() * 4)) != SR_OK ||
+            (rc = s->d_refit_acc.reserve(init.size() * 4)) != SR_OK || (rc = s->d_refit_out.reserve(init.size() * 4)) != SR_OK) return rc;
+        s->refit_set = set;
+        s->refit_threads = threads;
+    }
+    if ((rc = s->d_blas_node_box.reserve((size_t)s->tl_blas_nodes * 24)) != SR_OK) return rc;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};           // kernel times, only while sr_scene_enable_timing is on
+    if (s->timing) for (auto& e_ : ev) if (hipEventCreate(&e_) != hipSuccess) e_ = nullptr;
+    const bool timed = ev[0] && ev[1] && ev[2];
+    if (timed) (void)hipEventRecord(ev[0], nullptr);
+    srd::TlMeshRow* rows_dev = (s->tl_mesh_rows_current && s->d_tl_mesh_rows.bytes >= nm * sizeof(srd::TlMeshRow)) ? (srd::TlMeshRow*)s->d_tl_mesh_rows.p : nullptr;
+    int e = srk_blas_records((const srd::BlasRefitMesh*)s->d_refit_meshes.p, (uint32_t)set.size(), s->refit_threads, (float4*)s->d_tris.p, (float4*)s->d_shade.p,
+                             s->any_textured_tl ? (float4*)s->d_shade_tex.p : nullptr, (uint32_t*)s->d_refit_acc.p, (const uint32_t*)s->d_refit_acc_init.p,
+                             rows_dev, (float*)s->d_refit_out.p, nullptr);
+    if (timed) (void)hipEventRecord(ev[1], nullptr);
+    if (e == 0) e = srk_blas_refit((uint32_t*)s->d_blas_nodes.p, (const float4*)s->d_tris.p, (float*)s->d_blas_node_box.p, (const uint32_t*)s->d_refit_nodes.p,
+                                   s->refit_level_offsets.data(), (uint32_t)s->refit_level_offsets.size() - 1, nullptr);
+    if (timed) (void)hipEventRecord(ev[2], nullptr);
+    std::vector<float> out(set.size() * 8);
+    const hipError_t ce = e == 0 ? hipMemcpy(out.data(), s->d_refit_out.p, out.size() * 4, hipMemcpyDeviceToHost) : hipSuccess;   // 32 bytes per mesh; waits for the launches above
+    if (timed && e == 0 && ce == hipSuccess) {
+        float a = 0.0f, b = 0.0f;
+        if (hipEventSynchronize(ev[2]) == hipSuccess && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) { s->mu_info.flatten_ms = a; s->mu_info.refit_ms = b; }
+    }
+    for (auto& e_ : ev) if (e_) (void)hipEventDestroy(e_);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("mesh-tree refit launch failed: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(ce);
+    for (size_t k = 0; k < set.size(); k++) {
+        SrScene::HostBlas& b = s->blases[set[k]];
+        SrScene::MeshAs& a = s->mesh_as[set[k]];
+        const float* f = &out[k * 8];
+        memcpy(b.lo, f, 12); memcpy(b.hi, f + 3, 12);
+        b.max_abs_vertex = f[6]; b.max_edge_sum = f[7];
+        b.host_stale = true;
+        a.refit_pending = false; a.refit_now = true; a.last_op = SR_OP_UPDATE;
+        srh::as_state_mark_built(a.state, SR_OP_UPDATE);
+        s->mu_info.blas_refitted++;
+    }
+    return SR_OK;
+}
+
+// What the build of a sr_scene_set_instances in the two-level form did to every mesh's tree, into the per-mesh heuristic states.
+void mark_mesh_trees(SrScene* s, uint32_t forced) {
+    if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
+    for (size_t m = 0; m < s->meshes.size(); m++) {
+        if (s->meshes[m].n_vertices == 0) continue;
+        SrScene::MeshAs& a = s->mesh_as[m];
+        if (a.rebuilt_now) {
+            const uint32_t op = (!a.built_once || forced == SR_OP_SLOW_BUILD) ? SR_OP_SLOW_BUILD : SR_OP_FAST_BUILD;
+            if (a.build_type != SR_BUILD_STATIC && a.built_once) srh::as_state_mark_built(a.state, op);
+            a.last_op = op; a.built_once = true;
+        } else if (!a.refit_now) {
+            if (a.build_type != SR_BUILD_STATIC) srh::as_state_mark_built(a.state, SR_OP_NONE);
+            a.last_op = SR_OP_NONE;
+        }
+        a.rebuilt_now = a.refit_now = false;
+    }
+}
+
 int two_level_build(SrScene* s, bool list_changed) {
     const auto t0 = std::chrono::steady_clock::now();
     int rc;
@@ -936,7 +1123,7 @@ int two_level_build(SrScene* s, bool list_changed) {
         const srh::HostInstance& in = s->fid.instances[i];
         const srh::HostMesh& mesh = s->meshes[in.mesh_slot];
         SrScene::HostBlas& b = s->blases[in.mesh_slot];
-        if (!b.valid) { b = SrScene::HostBlas(); if ((rc = build_blas(mesh, in.mesh_slot, nullptr, b)) != SR_OK) return rc; s->blas_device_current = false; s->mu_info.blas_rebuilt++; s->mu_info.blas_build_ms += b.build_ms; }
+        if (!b.valid) { if ((rc = rebuild_mesh_tree(s, in.mesh_slot)) != SR_OK) return rc; s->blas_device_current = false; }
         srd::DevTlInstance& r = recs[i];
         const float* M = in.o2w.m;
         memcpy(r.o2w, M, 48);
@@ -1167,7 +1354,7 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     // meshes updated since the structure last took their vertices (sr_scene_update_mesh): every path below applies them
     const bool reshade = s->geometry_stale;
     s->mu_info.dirty_meshes = (uint32_t)std::count(s->mesh_dirty.begin(), s->mesh_dirty.end(), (char)1);
-    s->mu_info.reshaded = 0; s->mu_info.blas_rebuilt = 0;
+    s->mu_info.reshaded = 0; s->mu_info.blas_rebuilt = 0; s->mu_info.blas_refitted = 0;
     s->mu_info.tables_ms = s->mu_info.flatten_ms = s->mu_info.refit_ms = s->mu_info.blas_build_ms = 0.0;
     auto applied = [s] { std::fill(s->mesh_dirty.begin(), s->mesh_dirty.end(), (char)0); s->geometry_stale = false; };
     s->emissive_table = s->emissive_tris;
@@ -1176,16 +1363,24 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     // large. A changed instance list is then a top-level rebuild, reported as a fast build (Tlas::queue_build rebuilds in kind).
     if (wants_two_level(s) || s->fid.n_triangles >= (1u << 28)) {
         const uint32_t op = s->built_once ? SR_OP_FAST_BUILD : SR_OP_SLOW_BUILD;
+        const uint32_t forced = s->forced_op;
         s->forced_op = SR_OP_NONE;
         if (!s->two_level) s->built = false;
+        if ((rc = refit_mesh_trees(s, forced)) != SR_OK) { s->built = false; return rc; }      // updatable meshes: Blas::update on the device
         rc = two_level_build(s, true);
         if (rc != SR_OK) { s->built = false; return rc; }
+        mark_mesh_trees(s, forced);
         if (s->built_once) srh::as_state_mark_built(s->as_state, op);
         s->built_once = true;
         s->last_op = op;
         applied();
         return SR_OK;
     }
+    for (size_t m = 0; m < s->mesh_as.size() && m < s->blases.size(); m++)      // the one-level form has no mesh trees to refit
+        if (s->mesh_as[m].refit_pending || s->blases[m].host_stale) {
+            s->blases[m].valid = false; s->blases[m].host_stale = false; s->mesh_as[m].refit_pending = false;
+            s->blas_device_current = false; s->tl_mesh_rows_current = false;
+        }
     if (s->two_level) {                       // back to the one-level form: everything is rebuilt
         s->two_level = false; s->built = false;
         s->dev.blas_nodes = nullptr; s->dev.tl_inst = nullptr; s->dev.tl_instances = nullptr;
@@ -1217,10 +1412,41 @@ int sr_scene_end_frame(SrScene* s) {
     if (!s->built) { s->last_op = SR_OP_NONE; return SR_OK; }
     if (s->geometry_stale) return fail(SR_ERR_STATE, std::string("sr_scene_end_frame: ") + kStaleGeometry);
     const uint32_t op = srh::as_state_next_op(s->as_state, false);
-    if (op == SR_OP_SLOW_BUILD) {
+    // two-level form: a quiet frame for every updatable mesh as well (Blas::plan_op with inputs_changed = false); one that asks
+    // for its settle rebuild has its tree invalidated, and the build below rebuilds it on the host
+    bool mesh_settles = false;
+    std::vector<uint32_t> mesh_ops;
+    if (s->two_level) {
+        if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
+        mesh_ops.assign(s->meshes.size(), SR_OP_NONE);
+        for (size_t m = 0; m < s->meshes.size(); m++) {
+            SrScene::MeshAs& a = s->mesh_as[m];
+            a.rebuilt_now = a.refit_now = false;
+            if (s->meshes[m].n_vertices == 0 || a.build_type == SR_BUILD_STATIC || !a.built_once || a.refit_pending) continue;
+            mesh_ops[m] = srh::as_state_next_op(a.state, false);
+            if (mesh_ops[m] == SR_OP_SLOW_BUILD) {
+                s->blases[m].valid = false; s->blases[m].host_stale = false;
+                s->blas_device_current = false; s->tl_mesh_rows_current = false;
+                mesh_settles = true;
+            }
+        }
+    }
+    if (op == SR_OP_SLOW_BUILD || mesh_settles) {
         int rc = bind_device(s);
         if (rc != SR_OK) return rc;
+        if (s->two_level && !s->blas_device_current)      // the re-concatenation takes the stale host copies of refitted meshes along
+            for (auto& b : s->blases) if (b.host_stale) { b.valid = false; b.host_stale = false; }
         if ((rc = s->two_level ? two_level_build(s, false) : full_build(s)) != SR_OK) { s->built = false; return rc; }
+    }
+    for (size_t m = 0; m < mesh_ops.size(); m++) {
+        SrScene::MeshAs& a = s->mesh_as[m];
+        if (s->meshes[m].n_vertices == 0) continue;
+        if (a.build_type != SR_BUILD_STATIC && a.built_once && !a.refit_pending) {
+            const uint32_t done = a.rebuilt_now ? SR_OP_SLOW_BUILD : mesh_ops[m];     // rebuilt along with a settling mesh: a quality build too
+            srh::as_state_mark_built(a.state, done);
+            a.last_op = done;
+        } else a.last_op = a.rebuilt_now ? SR_OP_SLOW_BUILD : SR_OP_NONE;
+        a.rebuilt_now = false;
     }
     srh::as_state_mark_built(s->as_state, op);
     s->last_op = op;
@@ -1282,6 +1508,74 @@ int sr_scene_as_state(const SrScene* s, SrAsState* state, uint32_t* last_op) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_as_state: scene is null");
     if (state) *state = s->as_state;
     if (last_op) *last_op = s->last_op;
+    return SR_OK;
+}
+
+int sr_scene_set_mesh_build_type(SrScene* s, uint64_t key, uint32_t build_type) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_build_type: scene is null");
+    if (build_type > SR_BUILD_STATIC) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_build_type: build type must be SR_BUILD_RAPIDLY_CHANGING, SR_BUILD_SOMETIMES_CHANGES or SR_BUILD_STATIC");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_build_type: no mesh is registered under this key");
+    const uint32_t slot = it->second;
+    if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
+    SrScene::MeshAs& a = s->mesh_as[slot];
+    if (build_type == SR_BUILD_STATIC && a.refit_pending) {       // a Static mesh is never refitted: its pending update becomes a rebuild
+        a.refit_pending = false;
+        if (slot < s->blases.size()) s->blases[slot].valid = false;
+        s->blas_device_current = false; s->tl_mesh_rows_current = false;
+    }
+    a.build_type = build_type;
+    srh::as_state_initial(build_type, &a.state);
+    return SR_OK;
+}
+
+int sr_scene_mesh_as_state(const SrScene* s, uint64_t key, uint32_t* build_type, SrAsState* state, uint32_t* last_op) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_as_state: scene is null");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_as_state: no mesh is registered under this key");
+    const SrScene::MeshAs a = it->second < s->mesh_as.size() ? s->mesh_as[it->second] : SrScene::MeshAs();
+    if (build_type) *build_type = a.build_type;
+    if (state) *state = a.state;
+    if (last_op) *last_op = a.last_op;
+    return SR_OK;
+}
+
+int sr_scene_read_mesh_tree(const SrScene* s, uint64_t key, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* nodes, float* tris, float* shade,
+                            float* shade_tex, uint32_t* slot_of_prim) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_mesh_tree: scene is null");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_mesh_tree: no mesh is registered under this key");
+    if (!s->built || !s->two_level) return fail(SR_ERR_STATE, "sr_scene_read_mesh_tree: the scene is not built in the two-level form");
+    const uint32_t slot = it->second;
+    if (!s->blas_device_current || slot >= s->blases.size() || !s->blases[slot].valid || slot >= s->blas_node_base.size())
+        return fail(SR_ERR_STATE, "sr_scene_read_mesh_tree: the mesh's tree is not on the device (sr_scene_set_instances builds it)");
+    if (s->geometry_stale || (slot < s->mesh_as.size() && s->mesh_as[slot].refit_pending)) return fail(SR_ERR_STATE, std::string("sr_scene_read_mesh_tree: ") + kStaleGeometry);
+    const SrScene::HostBlas& b = s->blases[slot];
+    const uint32_t nb = s->blas_node_base[slot], tb = s->blas_tri_base[slot], nn = b.n_nodes, nt = b.n_tris;
+    if (n_nodes) *n_nodes = nn;
+    if (n_tris) *n_tris = nt;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (nodes && nn) {
+        HIP_TRY(hipMemcpy(nodes, (const char*)s->d_blas_nodes.p + (size_t)nb * srl::kNodeBytes, (size_t)nn * srl::kNodeBytes, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < nn; i++)         // references local to the mesh (the inverse of the concatenation)
+            for (int c = 0; c < srl::kBvhWidth; c++) {
+                uint32_t& q = nodes[(size_t)i * srl::kNodeDwords + srl::kChildOffset + c];
+                const int ref = (int)q;
+                if (ref >= 0) q = (uint32_t)(ref - (int)nb);
+                else { const uint32_t lv = ~(uint32_t)ref; const uint32_t cnt = lv & 7u; if (cnt) q = ~((((lv >> 3) - tb) << 3) | cnt); }
+            }
+    }
+    if (tris && nt) HIP_TRY(hipMemcpy(tris, (const char*)s->d_tris.p + (size_t)tb * 48, (size_t)nt * 48, hipMemcpyDeviceToHost));
+    if (shade && nt) HIP_TRY(hipMemcpy(shade, (const char*)s->d_shade.p + (size_t)tb * 48, (size_t)nt * 48, hipMemcpyDeviceToHost));
+    if (shade_tex && nt) {
+        if (s->any_textured_tl) HIP_TRY(hipMemcpy(shade_tex, (const char*)s->d_shade_tex.p + (size_t)tb * 96, (size_t)nt * 96, hipMemcpyDeviceToHost));
+        else memset(shade_tex, 0, (size_t)nt * 96);       // the scene has no textured records
+    }
+    if (slot_of_prim && nt) {
+        HIP_TRY(hipMemcpy(slot_of_prim, (const char*)s->d_slot_of_gid.p + (size_t)tb * 4, (size_t)nt * 4, hipMemcpyDeviceToHost));
+        for (uint32_t p = 0; p < nt; p++) slot_of_prim[p] -= tb;
+    }
     return SR_OK;
 }
 

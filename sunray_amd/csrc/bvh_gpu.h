@@ -18,6 +18,13 @@ struct TlMeshRow {      // 48 B: what one instance record of the two-level form 
     float max_abs_vertex, max_edge_sum;
     uint32_t max_stack, blas_root, prim_base, n_tris;
 };
+struct BlasRefitMesh {  // 40 B: one dirty mesh of a mesh-tree refit (two-level form)
+    uint64_t vertices, indices;      // device addresses: SrVertex[n_vertices], uint32_t[3 * n_tris]
+    uint32_t tri_base, n_tris;       // the mesh's range of the concatenated leaf-order records
+    uint32_t n_vertices;
+    uint32_t first_thread;           // of blas_records_kernel, a multiple of 64
+    uint32_t mesh_slot, textured;    // row of the TlMeshRow table; 1: the mesh has shade_tex records
+};
 struct DevTlInstance;   // traverse.h
 }  // namespace srd
 
@@ -55,3 +62,13 @@ int srk_tl_records(const srd::FlatInstance* instances, const srd::TlMeshRow* mes
                    srd::DevTlInstance* records, float* boxes, uint32_t* result, hipStream_t stream);
 int srk_tl_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
 size_t srk_tl_scratch_bytes(uint32_t n_instances, uint32_t node_cap);
+
+// Mesh trees of the two-level form after sr_scene_update_mesh. srk_blas_records: the leaf-order records of the dirty meshes
+// rewritten from their vertex / index buffers (the bytes of api.cpp build_blas) and, per mesh, root box lo, hi, max_abs_vertex,
+// max_edge_sum (build_blas's values, bit for bit) into `out` (8 floats per mesh) and, where `rows` is not null, into the mesh's
+// row; `acc` is n_meshes x 8 dwords of scratch, `acc_init` its initial contents (the encoded +inf x 3, -inf x 3, 0, 0 per mesh).
+// srk_blas_refit: the quantised nodes of those meshes, one launch per level (lists of global node indices, deepest level first).
+int srk_blas_records(const srd::BlasRefitMesh* meshes, uint32_t n_meshes, uint32_t n_threads, float4* tris, float4* shade, float4* shade_tex,
+                     uint32_t* acc, const uint32_t* acc_init, srd::TlMeshRow* rows, float* out, hipStream_t stream);
+int srk_blas_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host,
+                   uint32_t n_levels, hipStream_t stream);

@@ -117,6 +117,26 @@ struct BoxPrims {
     }
 };
 
+// The (v0, v1, v2, prim) records of the mesh trees of the two-level form (api.cpp build_blas): tri_box with e1 = v1 - v0 and
+// e2 = v2 - v0, the edges the host builder bounds the same triangle with; the vertices themselves are added as well, so the box
+// also holds what build_blas takes for the mesh's root box (v1 and v0 + (v1 - v0) can differ in the last place).
+struct VertPrims {
+    const float4* tris;
+    __device__ __forceinline__ void add(uint32_t i, float lo[3], float hi[3]) const {
+        const float4 a = tris[(size_t)i * 3 + 0], b = tris[(size_t)i * 3 + 1], c = tris[(size_t)i * 3 + 2];
+        const float v0[3] = {a.x, a.y, a.z}, v1[3] = {a.w, b.x, b.y}, v2[3] = {b.z, b.w, c.x};
+        for (int k = 0; k < 3; k++) {
+            const float e1 = v1[k] - v0[k], e2 = v2[k] - v0[k];
+            const float p1 = v0[k] + e1, p2 = v0[k] + e2;
+            const float pad = 4e-6f * (fabsf(e1) + fabsf(e2));
+            const float l = fminf(fminf(v0[k], fminf(p1, p2)), fminf(v1[k], v2[k])) - pad;
+            const float h = fmaxf(fmaxf(v0[k], fmaxf(p1, p2)), fmaxf(v1[k], v2[k])) + pad;
+            lo[k] = fminf(lo[k], nextafterf(l, -INFINITY));
+            hi[k] = fmaxf(hi[k], nextafterf(h, INFINITY));
+        }
+    }
+};
+
 // One thread per node of one tree level (deepest level first): child boxes from the primitives (leaf children) or
 // from the already refitted child nodes (node_box), then the same quantisation the host collapser applies
 // (bvh_build.cpp Collapser::emit): origin = node min, per-axis power-of-two grid, planes rounded outward and
@@ -640,6 +660,75 @@ __global__ void tl_leaves_kernel(const uint32_t* sorted_gid, const uint32_t* slo
     tl_inst[slot_of_sorted[s_idx]] = sorted_gid[s_idx];
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Refit of the mesh trees of the two-level form after sr_scene_update_mesh (Blas::update, blas.rs:292-310, for a BLAS built
+// with ALLOW_UPDATE). Topology, leaf order and slot_of_prim stay; what follows from the vertices is rewritten in place:
+//   records    one thread per leaf-order slot of the dirty meshes (every mesh's thread range starts at a multiple of 64, so a
+//              wave works on one mesh): the slot keeps its primitive, the (v0, v1, v2, prim) record, `shade` and, for a textured
+//              mesh, `shade_tex` get the bytes build_blas writes; the mesh's root box and padding numbers are reduced in the
+//              wave and leave it as one atomic per value on the order-preserving encoding
+//   finish     one thread per dirty mesh: the eight floats go into the mesh's TlMeshRow and into the read-back block
+//   refit      refit_level_kernel over VertPrims, one launch per level for all dirty meshes together
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void blas_records_kernel(const BlasRefitMesh* meshes, uint32_t n_meshes, uint32_t n_threads, float4* tris, float4* shade, float4* shade_tex,
+                                    uint32_t* acc) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t lo_m = 0, hi_m = n_meshes;       // last mesh whose first_thread <= t (wave-uniform: ranges start at multiples of 64)
+    while (hi_m - lo_m > 1) { const uint32_t mid = (lo_m + hi_m) >> 1; if (meshes[mid].first_thread <= t) lo_m = mid; else hi_m = mid; }
+    const BlasRefitMesh m = meshes[lo_m];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    float max_abs = 0.0f, max_edge = 0.0f;
+    const uint32_t local = t - m.first_thread;
+    if (t < n_threads && local < m.n_tris) {
+        const size_t slot = (size_t)m.tri_base + local;
+        const uint32_t prim = __float_as_uint(tris[slot * 3 + 2].y);
+        if (prim < m.n_tris) {                 // always, for records build_blas wrote; never index out of bounds
+            const uint32_t* idx = (const uint32_t*)(uintptr_t)m.indices;
+            const SrVertex* vtx = (const SrVertex*)(uintptr_t)m.vertices;
+            const SrVertex* v[3];
+            for (int j = 0; j < 3; j++) { const uint32_t vi = idx[3 * (size_t)prim + j]; v[j] = vtx + (vi < m.n_vertices ? vi : 0u); }
+            const float* w[3] = {v[0]->position, v[1]->position, v[2]->position};
+            tris[slot * 3 + 0] = make_float4(w[0][0], w[0][1], w[0][2], w[1][0]);
+            tris[slot * 3 + 1] = make_float4(w[1][1], w[1][2], w[2][0], w[2][1]);
+            tris[slot * 3 + 2] = make_float4(w[2][2], __uint_as_float(prim), 0.0f, 0.0f);
+            const float4 tail = shade[slot * 3 + 2];
+            write_shade(shade + slot * 3, v, tail.y, tail.z, tail.w);
+            if (m.textured && shade_tex) write_shade_tex(shade_tex + slot * 6, v);
+            for (int a = 0; a < 3; a++) {      // build_blas: the padded triangle box and the two padding numbers
+                const float e1 = w[1][a] - w[0][a], e2 = w[2][a] - w[0][a];
+                max_edge = fmaxf(max_edge, fabsf(e1) + fabsf(e2));
+                for (int j = 0; j < 3; j++) max_abs = fmaxf(max_abs, fabsf(w[j][a]));
+                const float pad = 4e-6f * (fabsf(e1) + fabsf(e2));
+                const float l = fminf(w[0][a], fminf(w[1][a], w[2][a])) - pad;
+                const float h = fmaxf(w[0][a], fmaxf(w[1][a], w[2][a])) + pad;
+                lo[a] = nextafterf(l, -INFINITY); hi[a] = nextafterf(h, INFINITY);
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o)); }
+        max_abs = fmaxf(max_abs, __shfl_xor(max_abs, o)); max_edge = fmaxf(max_edge, __shfl_xor(max_edge, o));
+    }
+    if ((threadIdx.x & 63) == 0 && t < n_threads && lo[0] <= hi[0]) {
+        uint32_t* q = acc + (size_t)lo_m * 8;
+        for (int a = 0; a < 3; a++) { atomicMin(q + a, enc_f(lo[a])); atomicMax(q + 3 + a, enc_f(hi[a])); }
+        atomicMax(q + 6, enc_f(max_abs)); atomicMax(q + 7, enc_f(max_edge));
+    }
+}
+
+__global__ void blas_finish_kernel(const BlasRefitMesh* meshes, uint32_t n_meshes, const uint32_t* acc, TlMeshRow* rows, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_meshes) return;
+    float f[8];
+    for (int k = 0; k < 8; k++) f[k] = dec_f(acc[(size_t)i * 8 + k]);
+    for (int k = 0; k < 8; k++) out[(size_t)i * 8 + k] = f[k];
+    if (rows) {
+        TlMeshRow* r = rows + meshes[i].mesh_slot;
+        for (int a = 0; a < 3; a++) { r->lo[a] = f[a]; r->hi[a] = f[3 + a]; }
+        r->max_abs_vertex = f[6]; r->max_edge_sum = f[7];
+    }
+}
+
 }  // namespace srd
 
 using namespace srd;
@@ -665,6 +754,26 @@ int srk_launch_refit(uint32_t* nodes, const float4* tris, float* node_box, const
         const uint32_t first = level_offsets_host[l], count = level_offsets_host[l + 1] - first;
         if (count == 0) continue;
         refit_level_kernel<<<dim3((count + 63) / 64), dim3(64), 0, stream>>>(nodes, TriPrims{tris}, node_box, level_nodes, first, count);
+    }
+    return (int)hipGetLastError();
+}
+
+int srk_blas_records(const BlasRefitMesh* meshes, uint32_t n_meshes, uint32_t n_threads, float4* tris, float4* shade, float4* shade_tex, uint32_t* acc,
+                     const uint32_t* acc_init, TlMeshRow* rows, float* out, hipStream_t stream) {
+    if (n_meshes == 0 || n_threads == 0) return 0;
+    hipError_t e = hipMemcpyAsync(acc, acc_init, (size_t)n_meshes * 32, hipMemcpyDeviceToDevice, stream);
+    if (e != hipSuccess) return (int)e;
+    blas_records_kernel<<<dim3((n_threads + 255) / 256), dim3(256), 0, stream>>>(meshes, n_meshes, n_threads, tris, shade, shade_tex, acc);
+    blas_finish_kernel<<<dim3((n_meshes + 63) / 64), dim3(64), 0, stream>>>(meshes, n_meshes, acc, rows, out);
+    return (int)hipGetLastError();
+}
+
+int srk_blas_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host, uint32_t n_levels,
+                   hipStream_t stream) {
+    for (uint32_t l = 0; l < n_levels; l++) {     // level_offsets_host[l] .. [l+1]: deepest level first, all dirty meshes together
+        const uint32_t first = level_offsets_host[l], count = level_offsets_host[l + 1] - first;
+        if (count == 0) continue;
+        refit_level_kernel<<<dim3((count + 63) / 64), dim3(64), 0, stream>>>(nodes, VertPrims{tris}, node_box, level_nodes, first, count);
     }
     return (int)hipGetLastError();
 }

@@ -501,6 +501,16 @@ int sr_renderer_update_mesh(SrRenderer* r, uint64_t key, const SrVertex* vertice
     return SR_OK;
 }
 
+// BuildType of a mesh's tree on every replica (the replicas hold the same meshes: one that refuses, refuses first).
+int sr_renderer_set_mesh_build_type(SrRenderer* r, uint64_t key, uint32_t build_type) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_build_type: renderer is null");
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_set_mesh_build_type(sc, key, build_type);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+
 // Access for harnesses: the scene (counters, stats), the device output image and the frame counter.
 int sr_renderer_get(SrRenderer* r, SrScene** scene, const uint32_t** output_rgba8_device, const float** raw_color_device, uint32_t* relative_frame_count) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_get: renderer is null");

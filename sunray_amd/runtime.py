@@ -213,6 +213,30 @@ class Scene:
         check(lib().sr_scene_mesh_update_info(self._h, C.byref(info)))
         return info
 
+    def set_mesh_build_type(self, key, build_type):
+        """abi.BUILD_* of one mesh's tree: an updatable mesh (not BUILD_STATIC, the default) is refitted on the device by the
+        set_instances that applies its update_mesh in the two-level form (sr_scene_set_mesh_build_type)."""
+        check(lib().sr_scene_set_mesh_build_type(self._h, C.c_uint64(key), C.c_uint32(build_type)))
+        return self
+
+    def mesh_as_state(self, key):
+        """-> (build type, SrAsState, last op) of one mesh's tree."""
+        bt, st, op = C.c_uint32(), abi.SrAsState(), C.c_uint32()
+        check(lib().sr_scene_mesh_as_state(self._h, C.c_uint64(key), C.byref(bt), C.byref(st), C.byref(op)))
+        return bt.value, st, op.value
+
+    def read_mesh_tree(self, key):
+        """-> dict of one mesh's part of the device arrays of a two-level scene: nodes [n_nodes, 16] uint32 (references local to the
+        mesh), tris / shade [n_tris, 12] float32, shade_tex [n_tris, 24] float32 (leaf order), slot_of_prim [n_tris] uint32."""
+        nn, nt = C.c_uint32(), C.c_uint32()
+        check(lib().sr_scene_read_mesh_tree(self._h, C.c_uint64(key), C.byref(nn), C.byref(nt), None, None, None, None, None))
+        nodes = np.zeros((max(nn.value, 1), bvh_layout()[1]), dtype=np.uint32)
+        tris, shade = np.zeros((max(nt.value, 1), 12), dtype=np.float32), np.zeros((max(nt.value, 1), 12), dtype=np.float32)
+        shade_tex, slot_of_prim = np.zeros((max(nt.value, 1), 24), dtype=np.float32), np.zeros(max(nt.value, 1), dtype=np.uint32)
+        check(lib().sr_scene_read_mesh_tree(self._h, C.c_uint64(key), None, None, _p(nodes), _p(tris), _p(shade), _p(shade_tex), _p(slot_of_prim)))
+        return {"nodes": nodes[:nn.value], "tris": tris[:nt.value], "shade": shade[:nt.value], "shade_tex": shade_tex[:nt.value],
+                "slot_of_prim": slot_of_prim[:nt.value]}
+
     # Image::new_from_data (image/mod.rs:82-111) / Sampler::new (image/sampler.rs:44-67)
     def add_image(self, pixels):
         a = np.ascontiguousarray(pixels, dtype=np.uint8)
@@ -656,6 +680,10 @@ class Renderer:
         """New vertex contents for a loaded mesh on every device slot; the next render applies it."""
         v = np.ascontiguousarray(vertices, dtype=abi.VERTEX)
         check(lib().sr_renderer_update_mesh(self._h, C.c_uint64(key), _p(v), C.c_uint32(len(v))))
+
+    def set_mesh_build_type(self, key, build_type):
+        """abi.BUILD_* of a loaded mesh's tree on every device slot (sr_renderer_set_mesh_build_type)."""
+        check(lib().sr_renderer_set_mesh_build_type(self._h, C.c_uint64(key), C.c_uint32(build_type)))
 
     def set_config(self, config):
         check(lib().sr_renderer_set_config(self._h, C.byref(config)))
