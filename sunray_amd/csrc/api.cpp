@@ -20,6 +20,7 @@
 #include "bvh_gpu.h"
 #include "bvh_layout.h"
 #include "kernels.h"
+#include "tl_record.h"
 
 namespace {
 
@@ -80,30 +81,55 @@ struct PassLabel {
     ~PassLabel() { if (pop) pop(); }
 };
 
+// One device allocation: grows on demand, frees itself, moves (TileSchedule lives in a std::vector) and cannot be copied.
 struct DeviceBuffer {
     void* p = nullptr;
     size_t bytes = 0;
-    int upload(const void* src, size_t n) {
-        if (n > bytes || p == nullptr) {
-            if (p) (void)hipFree(p);
-            p = nullptr; bytes = 0;
-            HIP_TRY(hipMalloc(&p, n ? n : 16));
-            bytes = n ? n : 16;
-        }
-        if (n) HIP_TRY(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
-        return SR_OK;
-    }
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DeviceBuffer& operator=(DeviceBuffer&& o) noexcept { if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { release(); }
     int reserve(size_t n) {
         if (n > bytes || p == nullptr) {
-            if (p) (void)hipFree(p);
-            p = nullptr; bytes = 0;
+            release();
             HIP_TRY(hipMalloc(&p, n ? n : 16));
             bytes = n ? n : 16;
         }
+        return SR_OK;
+    }
+    int upload(const void* src, size_t n) {
+        const int rc = reserve(n);
+        if (rc != SR_OK) return rc;
+        if (n) HIP_TRY(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
         return SR_OK;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
+
+double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+// First vertex with a non-finite position / first index out of range; the count where there is none.
+uint32_t first_non_finite_vertex(const SrVertex* v, uint32_t n) {
+    uint32_t i = 0;
+    while (i < n && std::isfinite(v[i].position[0]) && std::isfinite(v[i].position[1]) && std::isfinite(v[i].position[2])) i++;
+    return i;
+}
+uint32_t first_index_out_of_range(const uint32_t* indices, uint32_t n_indices, uint32_t n_vertices) {
+    uint32_t i = 0;
+    while (i < n_indices && indices[i] < n_vertices) i++;
+    return i;
+}
+
+// The 24-float textured shade record of one triangle (uv, normal-map uv, tangents), as bvh_gpu.hip write_shade_tex writes it.
+void pack_shade_tex(float* q, const SrVertex* const v[3]) {
+    for (int j = 0; j < 3; j++) { memcpy(q + 2 * j, v[j]->base_color_tex_coord, 8); memcpy(q + 6 + 2 * j, v[j]->normal_tex_coord, 8); }
+    memcpy(q + 12, v[0]->tangent, 12);
+    q[15] = v[0]->tangent[3] >= 0.0f ? 1.0f : -1.0f;   // handedness from the first vertex only (closest_hit.slang:34)
+    memcpy(q + 16, v[1]->tangent, 12);
+    memcpy(q + 19, v[2]->tangent, 12);
+}
 
 }  // namespace
 
@@ -140,23 +166,25 @@ struct SrScene {
         bool host_stale = false;            // refitted on the device since: nodes / tris / shade / shade_tex above hold the old vertices
                                             // (topology, slot_of_prim, counts, max_stack and the read-back lo, hi, max_* are current)
     };
-    std::vector<HostBlas> blases;           // by mesh slot
-    // per-mesh maintenance (Blas::plan_op / mark_built, blas.rs:245-310): build type, heuristic state, what the last
-    // sr_scene_set_instances / sr_scene_end_frame did to the mesh's tree
-    struct MeshAs {
+    // Everything the scene keeps per mesh slot beside the mesh itself: its tree, where the tree sits in the concatenated device
+    // arrays, and its maintenance (Blas::plan_op / mark_built, blas.rs:245-310): build type, heuristic state, what the last
+    // sr_scene_set_instances / sr_scene_end_frame did to the tree
+    struct MeshState {
+        HostBlas tree;
+        uint32_t node_base = 0, tri_base = 0;    // of the concatenated device arrays (upload_mesh_trees)
         uint32_t build_type = SR_BUILD_STATIC;   // Renderer::load_mesh builds Static (lib.rs:937)
         SrAsState state{0, 0, 0, 0};
         uint32_t last_op = SR_OP_NONE;
         bool refit_pending = false;         // updated (sr_scene_update_mesh) while its tree was valid: the next sr_scene_set_instances refits or rebuilds it
         bool built_once = false, rebuilt_now = false, refit_now = false;
+        bool dirty = false;                 // sr_scene_update_mesh: vertices changed since the built structure, which instances it, last took them
     };
-    std::vector<MeshAs> mesh_as;            // by mesh slot
+    std::vector<MeshState> mesh_state;      // by mesh slot, one per entry of `meshes`: grows in sr_scene_add_blas only
     // device refit of mesh trees: box scratch over d_blas_nodes (allocated at the first refit), and what belongs to the set of
     // meshes refitted last (an animation refits the same set every frame): rewrite-kernel rows, node lists by level, accumulators
     DeviceBuffer d_blas_node_box, d_refit_meshes, d_refit_nodes, d_refit_acc, d_refit_acc_init, d_refit_out;
     std::vector<uint32_t> refit_set, refit_level_offsets;
     uint32_t refit_threads = 0;
-    std::vector<uint32_t> blas_node_base, blas_tri_base;   // of the concatenated device arrays, by mesh slot
     bool blas_device_current = false;       // the concatenated arrays match the current set of meshes
     bool any_textured_tl = false;
     uint32_t blas_stack = 0;
@@ -190,10 +218,7 @@ struct SrScene {
     SrBvhStats stats{};
     bool built = false;
     bool built_once = false;
-    // sr_scene_update_mesh: meshes (by slot) whose vertices changed since the structure last took them, and whether the built
-    // structure instances one of them (it then shows stale geometry until the next sr_scene_set_instances)
-    std::vector<char> mesh_dirty;
-    bool geometry_stale = false;
+    bool geometry_stale = false;            // the built structure instances a dirty mesh: it shows stale geometry until the next sr_scene_set_instances
     SrMeshUpdateInfo mu_info{};
     int instrumented = 0;
     int timing = 0;
@@ -201,6 +226,7 @@ struct SrScene {
     int stack_entries = 8;   // LDS traversal-stack entries per lane this scene's tree needs (multiple of 4)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events[kNumKinds];
     size_t events_used[kNumKinds] = {0, 0, 0, 0};
+    ~SrScene() { for (auto& pool : events) for (auto& e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } }
 };
 
 namespace {
@@ -228,6 +254,35 @@ struct ScopedTiming {
     }
     ~ScopedTiming() { if (stop) (void)hipEventRecord(stop, stream); }
 };
+
+// Times of two consecutive stretches of kernels on the null stream, only while sr_scene_enable_timing is on: mark() before,
+// between and after them, then read() the two intervals (it waits for the last mark).
+struct ThreeMarkTimer {
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    int marks = 0;
+    bool on = false;
+    explicit ThreeMarkTimer(const SrScene* s) {
+        if (s->timing) for (auto& e : ev) if (hipEventCreate(&e) != hipSuccess) e = nullptr;
+        on = ev[0] && ev[1] && ev[2];
+    }
+    ~ThreeMarkTimer() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
+    void mark() { if (on) (void)hipEventRecord(ev[marks], nullptr); marks++; }
+    void read(double* first_ms, double* second_ms) {
+        float a = 0.0f, b = 0.0f;
+        if (on && hipEventSynchronize(ev[2]) == hipSuccess && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) { *first_ms = a; *second_ms = b; }
+    }
+};
+
+// This mesh's tree no longer matches its vertices: the next build rebuilds it on the host (upload_mesh_trees) and
+// re-concatenates the device arrays; a pending refit is dropped with it. Every caller gets all five assignments, also where
+// one is a no-op there, because of what holds everywhere: refit_pending implies a valid tree of an updatable mesh; a tree that
+// is not valid is rebuilt into a fresh HostBlas (host_stale = false, refit_pending = false) before anything reads it; and
+// tl_mesh_rows_current is read only behind blas_device_current, which only upload_mesh_trees sets, clearing the former.
+void invalidate_mesh_tree(SrScene* s, uint32_t slot) {
+    SrScene::MeshState& ms = s->mesh_state[slot];
+    ms.tree.valid = false; ms.tree.host_stale = false; ms.refit_pending = false;
+    s->blas_device_current = false; s->tl_mesh_rows_current = false;
+}
 
 }  // namespace
 
@@ -259,8 +314,7 @@ int sr_emissive_triangles_from_mesh(const SrVertex* vertices, uint32_t n_vertice
                                     uint32_t cap, uint32_t* out_count) {
     if (!vertices || !indices || !material || !out_count) return fail(SR_ERR_INVALID_ARG, "sr_emissive_triangles_from_mesh: null argument");
     if (!out && cap > 0) return fail(SR_ERR_INVALID_ARG, "sr_emissive_triangles_from_mesh: out is null but cap > 0 (pass cap = 0 to query the count)");
-    for (uint32_t i = 0; i < n_indices; i++)
-        if (indices[i] >= n_vertices) return fail(SR_ERR_INVALID_ARG, "sr_emissive_triangles_from_mesh: index out of range");
+    if (first_index_out_of_range(indices, n_indices, n_vertices) < n_indices) return fail(SR_ERR_INVALID_ARG, "sr_emissive_triangles_from_mesh: index out of range");
     std::vector<SrEmissiveTriangle> v;
     srh::emissive_triangles_from_mesh(vertices, indices, n_indices, *material, v);
     *out_count = (uint32_t)v.size();
@@ -306,15 +360,6 @@ int sr_scene_destroy(SrScene* s) {
     (void)hipDeviceSynchronize();
     for (auto& m : s->meshes) { if (m.d_vertices) (void)hipFree(m.d_vertices); if (m.d_indices) (void)hipFree(m.d_indices); }
     for (auto& im : s->images) if (im.d_texels) (void)hipFree(im.d_texels);
-    s->d_shade_tex.release(); s->d_mesh_tex.release(); s->d_textures.release();
-    s->d_level_nodes.release(); s->d_node_box.release(); s->d_mesh_infos.release(); s->d_flat_instances.release(); s->d_scratch.release();
-    s->d_nodes.release(); s->d_tris.release(); s->d_shade.release(); s->d_mesh_const.release(); s->d_slot_of_gid.release(); s->d_instances.release();
-    s->d_lights.release(); s->d_misc.release();
-    s->d_blas_nodes.release(); s->d_tl_inst.release(); s->d_tl_instances.release();
-    s->d_tl_mesh_rows.release(); s->d_tl_boxes.release(); s->d_tl_result.release();
-    s->d_blas_node_box.release(); s->d_refit_meshes.release(); s->d_refit_nodes.release(); s->d_refit_acc.release(); s->d_refit_acc_init.release(); s->d_refit_out.release();
-    for (auto& ts : s->schedules) { ts.cost.release(); ts.order.release(); }
-    for (auto& pool : s->events) for (auto& e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     delete s;
     return SR_OK;
 }
@@ -331,20 +376,18 @@ int sr_scene_add_blas(SrScene* s, uint64_t key, const SrVertex* vertices, uint32
         snprintf(buf, sizeof(buf), "load_mesh: invalid mesh (%u vertices, %u indices — need non-empty vertices and a triangle-list index count)", n_vertices, n_indices);
         return fail(SR_ERR_INVALID_ARG, buf);
     }
-    for (uint32_t i = 0; i < n_indices; i++)
-        if (indices[i] >= n_vertices) {
-            char buf[120];
-            snprintf(buf, sizeof(buf), "load_mesh: index %u out of range for %u vertices", indices[i], n_vertices);
-            return fail(SR_ERR_INVALID_ARG, buf);
-        }
+    if (const uint32_t i = first_index_out_of_range(indices, n_indices, n_vertices); i < n_indices) {
+        char buf[120];
+        snprintf(buf, sizeof(buf), "load_mesh: index %u out of range for %u vertices", indices[i], n_vertices);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
     // Vulkan treats a triangle with a NaN position as inactive; the builders quantise positions (a non-finite one would
     // be undefined behaviour there), so such meshes are refused instead
-    for (uint32_t i = 0; i < n_vertices; i++)
-        if (!std::isfinite(vertices[i].position[0]) || !std::isfinite(vertices[i].position[1]) || !std::isfinite(vertices[i].position[2])) {
-            char buf[120];
-            snprintf(buf, sizeof(buf), "load_mesh: vertex %u has a non-finite position", i);
-            return fail(SR_ERR_INVALID_ARG, buf);
-        }
+    if (const uint32_t i = first_non_finite_vertex(vertices, n_vertices); i < n_vertices) {
+        char buf[120];
+        snprintf(buf, sizeof(buf), "load_mesh: vertex %u has a non-finite position", i);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
     const uint32_t* tex = &material->base_color_image;   // five (image, sampler) slot pairs (resources/material.rs:33-42)
     for (int i = 0; i < 10; i += 2)
         if (tex[i] != SR_NULL_TEXTURE && (tex[i] >= s->images.size() || tex[i + 1] >= s->samplers.size() || !s->images[tex[i]].d_texels))
@@ -387,13 +430,11 @@ int sr_scene_add_blas(SrScene* s, uint64_t key, const SrVertex* vertices, uint32
         slot = (uint32_t)s->meshes.size();
         s->mesh_infos.push_back(mi);
         s->meshes.push_back(std::move(m));
+        s->mesh_state.emplace_back();
     }
     s->slots[key] = slot;
     s->built = false;
-    if (s->blases.size() < s->meshes.size()) s->blases.resize(s->meshes.size());
-    s->blases[slot] = SrScene::HostBlas();
-    if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
-    s->mesh_as[slot] = SrScene::MeshAs();
+    s->mesh_state[slot] = SrScene::MeshState();
     s->blas_device_current = false;
     if (out_slot) *out_slot = slot;
     return SR_OK;
@@ -404,9 +445,7 @@ int sr_scene_add_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uint32
     if (!s || !vertices || !indices || !material) return fail(SR_ERR_INVALID_ARG, "load_mesh: null argument");
     std::vector<SrEmissiveTriangle> et;
     if (n_indices % 3 == 0) {
-        bool in_range = true;
-        for (uint32_t i = 0; i < n_indices && in_range; i++) in_range = indices[i] < n_vertices;
-        if (in_range) srh::emissive_triangles_from_mesh(vertices, indices, n_indices, *material, et);   // lib.rs:901-925
+        if (first_index_out_of_range(indices, n_indices, n_vertices) == n_indices) srh::emissive_triangles_from_mesh(vertices, indices, n_indices, *material, et);   // lib.rs:901-925
     }
     return sr_scene_add_blas(s, key, vertices, n_vertices, indices, n_indices, material, et.data(), (uint32_t)et.size(), out_slot);
 }
@@ -427,9 +466,7 @@ int sr_scene_remove(SrScene* s, uint64_t key) {
     if (m.d_indices) (void)hipFree(m.d_indices);
     for (uint32_t es : m.emissive_slots) s->free_emissive_slots.push_back(es);
     m = srh::HostMesh();
-    if (slot < s->blases.size()) s->blases[slot] = SrScene::HostBlas();
-    if (slot < s->mesh_as.size()) s->mesh_as[slot] = SrScene::MeshAs();
-    if (slot < s->mesh_dirty.size()) s->mesh_dirty[slot] = 0;
+    s->mesh_state[slot] = SrScene::MeshState();
     s->blas_device_current = false;
     s->free_mesh_slots.push_back(slot);
     s->slots.erase(it);
@@ -452,12 +489,11 @@ int sr_scene_update_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uin
         snprintf(buf, sizeof(buf), "update_mesh: %u vertices given, the mesh was loaded with %u (the vertex count cannot change)", n_vertices, m.n_vertices);
         return fail(SR_ERR_INVALID_ARG, buf);
     }
-    for (uint32_t i = 0; i < n_vertices; i++)
-        if (!std::isfinite(vertices[i].position[0]) || !std::isfinite(vertices[i].position[1]) || !std::isfinite(vertices[i].position[2])) {
-            char buf[120];
-            snprintf(buf, sizeof(buf), "update_mesh: vertex %u has a non-finite position", i);
-            return fail(SR_ERR_INVALID_ARG, buf);
-        }
+    if (const uint32_t i = first_non_finite_vertex(vertices, n_vertices); i < n_vertices) {
+        char buf[120];
+        snprintf(buf, sizeof(buf), "update_mesh: vertex %u has a non-finite position", i);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
     // the emissive entries are one per triangle in index order (load_mesh, the glTF path) or none; any other list came from
     // the caller of sr_scene_add_blas and cannot be re-derived from vertices
     if (!m.emissive_slots.empty() && m.emissive_slots.size() != m.n_indices / 3)
@@ -478,25 +514,16 @@ int sr_scene_update_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uin
     // two-level form: this mesh's object-space tree, root box and padding numbers are stale; the other meshes keep theirs. An
     // updatable mesh (sr_scene_set_mesh_build_type) with a valid tree keeps it: the next sr_scene_set_instances refits it on the
     // device where it can (refit_mesh_trees) and invalidates it otherwise
-    if (slot < s->mesh_as.size() && s->mesh_as[slot].build_type != SR_BUILD_STATIC && slot < s->blases.size() && s->blases[slot].valid)
-        s->mesh_as[slot].refit_pending = true;
-    else {
-        if (slot < s->blases.size()) s->blases[slot].valid = false;
-        s->blas_device_current = false;
-        s->tl_mesh_rows_current = false;
-    }
+    if (s->mesh_state[slot].build_type != SR_BUILD_STATIC && s->mesh_state[slot].tree.valid) s->mesh_state[slot].refit_pending = true;
+    else invalidate_mesh_tree(s, slot);
     if (s->built) {
         bool instanced = false;
         for (const auto& in : s->fid.instances) if (in.mesh_slot == slot) { instanced = true; break; }
-        if (instanced) {
-            if (s->mesh_dirty.size() < s->meshes.size()) s->mesh_dirty.resize(s->meshes.size(), 0);
-            s->mesh_dirty[slot] = 1;
-            s->geometry_stale = true;
-        }
+        if (instanced) { s->mesh_state[slot].dirty = true; s->geometry_stale = true; }
     }
     const auto t3 = std::chrono::steady_clock::now();
-    s->mu_info.validate_copy_ms = std::chrono::duration<double, std::milli>((t1 - t0) + (t3 - t2)).count();
-    s->mu_info.h2d_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
+    s->mu_info.h2d_ms = ms_between(t1, t2);
     return SR_OK;
 }
 
@@ -652,36 +679,67 @@ int update_in_place(SrScene* s, bool reshade) {
     HIP_TRY(hipDeviceSynchronize());
     int rc = upload_instance_tables(s);
     if (rc != SR_OK) return rc;
-    s->mu_info.tables_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};           // kernel times, only while sr_scene_enable_timing is on
-    if (s->timing) for (auto& e_ : ev) if (hipEventCreate(&e_) != hipSuccess) e_ = nullptr;
-    const bool timed = ev[0] && ev[1] && ev[2];
-    if (timed) (void)hipEventRecord(ev[0], nullptr);
+    s->mu_info.tables_ms = ms_between(t0, std::chrono::steady_clock::now());
+    ThreeMarkTimer timer(s);
+    timer.mark();
     int e = reshade ? srk_launch_flatten_reshade((float4*)s->d_tris.p, (float4*)s->d_shade.p, (float4*)s->d_shade_tex.p, (const SrMeshInfo*)s->d_mesh_infos.p,
                                                  (const srd::FlatInstance*)s->d_flat_instances.p, s->fid.n_triangles, nullptr)
                     : srk_launch_flatten_slots((float4*)s->d_tris.p, (const float4*)s->d_shade.p, (const SrMeshInfo*)s->d_mesh_infos.p,
                                                (const srd::FlatInstance*)s->d_flat_instances.p, s->fid.n_triangles, nullptr);
-    if (timed) (void)hipEventRecord(ev[1], nullptr);
+    timer.mark();
     if (e == 0) {
         e = srk_launch_refit((uint32_t*)s->d_nodes.p, (const float4*)s->d_tris.p, (float*)s->d_node_box.p, (const uint32_t*)s->d_level_nodes.p,
                              s->level_offsets.data(), (uint32_t)s->level_offsets.size() - 1, nullptr);
         if (e != 0) fail(SR_ERR_HIP, std::string("refit launch failed: ") + hipGetErrorString((hipError_t)e));
     } else fail(SR_ERR_HIP, std::string("flatten launch failed: ") + hipGetErrorString((hipError_t)e));
-    if (timed) (void)hipEventRecord(ev[2], nullptr);
+    timer.mark();
     const hipError_t se = hipDeviceSynchronize();
-    if (timed && e == 0 && se == hipSuccess) {
-        float a = 0.0f, b = 0.0f;
-        if (hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) { s->mu_info.flatten_ms = a; s->mu_info.refit_ms = b; }
-    }
-    for (auto& e_ : ev) if (e_) (void)hipEventDestroy(e_);
+    if (e == 0 && se == hipSuccess) timer.read(&s->mu_info.flatten_ms, &s->mu_info.refit_ms);
     if (e != 0) return SR_ERR_HIP;
     HIP_TRY(se);
     s->mu_info.reshaded = reshade ? 1u : 0u;
-    s->stats.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    s->stats.build_ms = ms_between(t0, std::chrono::steady_clock::now());
     return SR_OK;
 }
 
 int full_build(SrScene* s);
+
+// What a builder hands over once its arrays are on the device.
+struct BuiltStructure {
+    uint64_t n_nodes = 0;        // all nodes: of the one tree, or of the top-level tree and the mesh trees together
+    uint64_t tri_bytes = 0;
+    uint32_t max_depth = 0;
+    uint32_t stack_need = 0;     // worst-case traversal stack entries
+    float sah_cost = 0.0f;
+    double build_ms = 0.0;
+    bool two_level = false, on_device = false;
+};
+
+// The built structure becomes the one the kernels see: device pointers, statistics, LDS stack size, form.
+void publish(SrScene* s, const BuiltStructure& b) {
+    s->dev.nodes = (const float4*)s->d_nodes.p;
+    s->dev.blas_nodes = b.two_level ? (const float4*)s->d_blas_nodes.p : nullptr;
+    s->dev.tl_inst = b.two_level ? (const uint32_t*)s->d_tl_inst.p : nullptr;
+    s->dev.tl_instances = b.two_level ? (const srd::DevTlInstance*)s->d_tl_instances.p : nullptr;
+    s->dev.tris = (const float4*)s->d_tris.p;
+    s->dev.shade = (const float4*)s->d_shade.p;
+    s->dev.shade_tex = (const float4*)s->d_shade_tex.p;
+    s->dev.slot_of_gid = (const uint32_t*)s->d_slot_of_gid.p;
+    s->dev.counters = (unsigned long long*)s->d_misc.p;
+    s->dev.n_tris = s->fid.n_triangles;
+    s->stats.n_triangles = s->fid.n_triangles;
+    s->stats.n_nodes = b.n_nodes;
+    s->stats.node_bytes = b.n_nodes * srl::kNodeBytes;
+    s->stats.tri_bytes = b.tri_bytes;
+    s->stats.max_depth = b.max_depth;
+    s->stats.max_stack = b.stack_need;
+    s->stack_entries = (int)((std::max(b.stack_need, 3u) + 1u + 3u) & ~3u);   // + the spare level of the branch-free push, a multiple of 4
+    s->stats.sah_cost = b.sah_cost;
+    s->stats.build_ms = b.build_ms;
+    s->built = true;
+    s->two_level = b.two_level;
+    s->last_build_on_device = b.on_device;
+}
 
 // ---- two-level form -------------------------------------------------------------------------------------------------
 // The reference instances BLASes through a TLAS it rebuilds or updates every frame (tlas.rs:155-191,
@@ -754,14 +812,7 @@ int build_blas(const srh::HostMesh& mesh, uint32_t mesh_slot, const SrTransform*
         float* sh = &b.shade[(size_t)sl * 12];
         for (int j = 0; j < 3; j++) memcpy(sh + 3 * j, v[j]->normal, 12);
         memcpy(sh + 10, &mesh_slot, 4);                                             // mesh slot; the instance comes from the walk
-        if (textured) {
-            float* tx = &b.shade_tex[(size_t)sl * 24];
-            for (int j = 0; j < 3; j++) { memcpy(tx + 2 * j, v[j]->base_color_tex_coord, 8); memcpy(tx + 6 + 2 * j, v[j]->normal_tex_coord, 8); }
-            memcpy(tx + 12, v[0]->tangent, 12);
-            tx[15] = v[0]->tangent[3] >= 0.0f ? 1.0f : -1.0f;
-            memcpy(tx + 16, v[1]->tangent, 12);
-            memcpy(tx + 19, v[2]->tangent, 12);
-        }
+        if (textured) pack_shade_tex(&b.shade_tex[(size_t)sl * 24], v);
         b.slot_of_prim[p] = sl;
         const srh::BuildTri& t = tris[p];
         for (int a = 0; a < 3; a++) {                                               // the padded triangle box, as the builder bounds it
@@ -777,12 +828,12 @@ int build_blas(const srh::HostMesh& mesh, uint32_t mesh_slot, const SrTransform*
 
 // The host build of one mesh's tree (the only mesh-tree build there is: the project has no device builder for mesh trees).
 int rebuild_mesh_tree(SrScene* s, uint32_t m) {
-    s->blases[m] = SrScene::HostBlas();
-    int rc = build_blas(s->meshes[m], m, nullptr, s->blases[m]);
+    SrScene::MeshState& ms = s->mesh_state[m];
+    ms.tree = SrScene::HostBlas();
+    int rc = build_blas(s->meshes[m], m, nullptr, ms.tree);
     if (rc != SR_OK) return rc;
-    s->mu_info.blas_rebuilt++; s->mu_info.blas_build_ms += s->blases[m].build_ms;
-    if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
-    s->mesh_as[m].rebuilt_now = true; s->mesh_as[m].refit_pending = false;
+    s->mu_info.blas_rebuilt++; s->mu_info.blas_build_ms += ms.tree.build_ms;
+    ms.rebuilt_now = true; ms.refit_pending = false;
     return SR_OK;
 }
 
@@ -823,11 +874,11 @@ int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
     for (size_t m = 0; m < nm; m++) {
         if (s->meshes[m].n_vertices == 0) continue;
         // a host copy that a device refit left behind holds the old vertices: it is rebuilt before it is uploaded again
-        if (!s->blases[m].valid || s->blases[m].host_stale || (m < s->mesh_as.size() && s->mesh_as[m].refit_pending)) { if ((rc = rebuild_mesh_tree(s, (uint32_t)m)) != SR_OK) return rc; }
-        cat.textured = cat.textured || !s->blases[m].shade_tex.empty();
+        const SrScene::MeshState& ms = s->mesh_state[m];
+        if (!ms.tree.valid || ms.tree.host_stale || ms.refit_pending) { if ((rc = rebuild_mesh_tree(s, (uint32_t)m)) != SR_OK) return rc; }
+        cat.textured = cat.textured || !ms.tree.shade_tex.empty();
     }
-    s->blas_node_base.assign(nm, 0u); s->blas_tri_base.assign(nm, 0u);
-    for (size_t m = 0; m < nm; m++) if (s->meshes[m].n_vertices) cat.append(s->blases[m], &s->blas_node_base[m], &s->blas_tri_base[m]);
+    for (size_t m = 0; m < nm; m++) if (s->meshes[m].n_vertices) cat.append(s->mesh_state[m].tree, &s->mesh_state[m].node_base, &s->mesh_state[m].tri_base);
     s->tl_baked_node_base.assign(baked.size(), 0u); s->tl_baked_tri_base.assign(baked.size(), 0u);
     for (size_t k = 0; k < baked.size(); k++) cat.append(baked[k], &s->tl_baked_node_base[k], &s->tl_baked_tri_base[k]);
     if (cat.tris.size() / 12 >= (1ull << 28) || cat.nodes.size() / srl::kNodeDwords >= (1ull << 31)) return fail(SR_ERR_UNSUPPORTED, "the meshes together exceed 2^28 triangles (leaf reference encoding)");
@@ -857,7 +908,7 @@ constexpr uint32_t kTlDeviceMinBoxes = 4096;
 static_assert(sizeof(SrTopLevelInfo) == 64 && sizeof(srd::TlMeshRow) == 48 && sizeof(srd::DevTlInstance) == 128, "layouts the harness and the record kernel rely on");
 
 // The changed instance list of a scene that is already built in the two-level form, on the device (bvh_gpu.hip): instance
-// records and padded boxes by srk_tl_records (the bytes of the host loop in two_level_build), the tree over the boxes by
+// records and padded boxes by srk_tl_records (tl_record.h, as the host loop in two_level_build), the tree over the boxes by
 // srk_tl_build. *reason stays SR_TL_ON_DEVICE when the build is done; any other value: the host build below does the whole
 // job (what this function has rewritten by then, it rewrote after the device-wide wait, and the host build writes it again).
 int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0, uint32_t* reason) {
@@ -873,12 +924,12 @@ int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0,
         std::vector<srd::TlMeshRow> rows(s->meshes.size() ? s->meshes.size() : 1);
         memset(rows.data(), 0, rows.size() * sizeof(srd::TlMeshRow));
         for (size_t m = 0; m < s->meshes.size(); m++) {
-            if (s->meshes[m].n_vertices == 0 || !s->blases[m].valid) continue;
-            const SrScene::HostBlas& b = s->blases[m];
+            if (s->meshes[m].n_vertices == 0 || !s->mesh_state[m].tree.valid) continue;
+            const SrScene::HostBlas& b = s->mesh_state[m].tree;
             srd::TlMeshRow& r = rows[m];
             memcpy(r.lo, b.lo, 12); memcpy(r.hi, b.hi, 12);
             r.max_abs_vertex = b.max_abs_vertex; r.max_edge_sum = b.max_edge_sum;
-            r.max_stack = b.max_stack; r.blas_root = s->blas_node_base[m]; r.prim_base = s->blas_tri_base[m]; r.n_tris = b.n_tris;
+            r.max_stack = b.max_stack; r.blas_root = s->mesh_state[m].node_base; r.prim_base = s->mesh_state[m].tri_base; r.n_tris = b.n_tris;
         }
         if ((rc = s->d_tl_mesh_rows.upload(rows.data(), rows.size() * sizeof(srd::TlMeshRow))) != SR_OK) return rc;
         s->tl_mesh_rows_current = true;
@@ -914,58 +965,28 @@ int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0,
     if (e < 0 || need > kTlStackCap) { *reason = SR_TL_HOST_STACK_BUDGET; return SR_OK; }
     const auto t2 = std::chrono::steady_clock::now();
     s->blas_stack = blas_stack;
-    s->dev.nodes = (const float4*)s->d_nodes.p;
-    s->dev.blas_nodes = (const float4*)s->d_blas_nodes.p;
-    s->dev.tl_inst = (const uint32_t*)s->d_tl_inst.p;
-    s->dev.tl_instances = (const srd::DevTlInstance*)s->d_tl_instances.p;
-    s->dev.tris = (const float4*)s->d_tris.p;
-    s->dev.shade = (const float4*)s->d_shade.p;
-    s->dev.shade_tex = (const float4*)s->d_shade_tex.p;
-    s->dev.slot_of_gid = (const uint32_t*)s->d_slot_of_gid.p;
-    s->dev.counters = (unsigned long long*)s->d_misc.p;
-    s->dev.n_tris = s->fid.n_triangles;
-    s->stats.n_triangles = s->fid.n_triangles;
-    s->stats.n_nodes = r.n_nodes + s->tl_blas_nodes;
-    s->stats.node_bytes = s->stats.n_nodes * srl::kNodeBytes;
-    s->stats.tri_bytes = s->tl_blas_tris * 48;
-    s->stats.max_depth = r.max_depth;
-    s->stats.max_stack = need;
-    s->stack_entries = (int)((std::max(need, 3u) + 1u + 3u) & ~3u);
-    s->stats.sah_cost = 0.0f;
-    s->stats.build_ms = std::chrono::duration<double, std::milli>(t2 - t0).count();
+    BuiltStructure built;
+    built.n_nodes = r.n_nodes + s->tl_blas_nodes; built.tri_bytes = s->tl_blas_tris * 48;
+    built.max_depth = r.max_depth; built.stack_need = need;
+    built.build_ms = ms_between(t0, t2);
+    built.two_level = true; built.on_device = true;
+    publish(s, built);
     s->shape.clear();
-    s->built = true;
-    s->two_level = true;
-    s->last_build_on_device = true;
     s->tl_boxes_host.clear();
     SrTopLevelInfo& info = s->tl_info;
     info.on_device = 1u; info.reason = SR_TL_ON_DEVICE;
     info.n_nodes = r.n_nodes; info.n_boxes = nb; info.n_instances = ni; info.max_stack = r.max_stack; info.blas_stack = blas_stack;
-    info.records_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    info.tree_ms = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    info.records_ms = ms_between(t0, t1);
+    info.tree_ms = ms_between(t1, t2);
     info.build_ms = s->stats.build_ms;
     return SR_OK;
 }
 
-// Whether two_level_build gives an instance with this transform a baked copy of its mesh: its test, with its expressions.
+// Whether two_level_build gives an instance with this transform a baked copy of its mesh (the test comes before anything that reads the mesh).
 bool instance_is_baked(const float* M) {
-    const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
-    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-    const double det = a00 * c00 + a01 * c01 + a02 * c02;
-    const double id = 1.0 / det;
-    const double R[9] = {c00 * id, (a02 * a21 - a01 * a22) * id, (a01 * a12 - a02 * a11) * id,
-                         c01 * id, (a00 * a22 - a02 * a20) * id, (a02 * a10 - a00 * a12) * id,
-                         c02 * id, (a01 * a20 - a00 * a21) * id, (a00 * a11 - a01 * a10) * id};
-    const double T[3] = {M[3], M[7], M[11]};
-    double r_norm = 0.0, m_norm = 0.0;
-    bool finite = std::isfinite(id) && det != 0.0;
-    for (int row = 0; row < 3; row++) {
-        for (int c = 0; c < 3; c++) finite = finite && std::isfinite((float)R[3 * row + c]);
-        finite = finite && std::isfinite((float)(-(R[3 * row] * T[0] + R[3 * row + 1] * T[1] + R[3 * row + 2] * T[2])));
-        r_norm = std::max(r_norm, std::fabs(R[3 * row]) + std::fabs(R[3 * row + 1]) + std::fabs(R[3 * row + 2]));
-        m_norm = std::max(m_norm, std::fabs((double)M[4 * row]) + std::fabs((double)M[4 * row + 1]) + std::fabs((double)M[4 * row + 2]));
-    }
-    return !finite || !(r_norm * m_norm < kTlMaxCondition);
+    const float unit_lo[3] = {0.0f, 0.0f, 0.0f}, unit_hi[3] = {1.0f, 1.0f, 1.0f};
+    float w2o[12], lo[3], hi[3], pad_a, pad_b;
+    return srd::tl_record(M, unit_lo, unit_hi, 0.0f, 0.0f, kTlMaxCondition, w2o, lo, hi, &pad_a, &pad_b) == srd::kTlRecordBaked;
 }
 
 // Blas::update (blas.rs:292-310) for the meshes updated since the last sr_scene_set_instances whose build type allows it
@@ -976,16 +997,15 @@ bool instance_is_baked(const float* M) {
 // to a rebuild would be wasted: it is all or nothing per call). Runs before two_level_build, which then sees current root boxes.
 int refit_mesh_trees(SrScene* s, uint32_t forced) {
     const size_t nm = s->meshes.size();
-    if (s->mesh_as.size() < nm) s->mesh_as.resize(nm);
-    if (s->blases.size() < nm) s->blases.resize(nm);
     s->mu_info.blas_refitted = 0;
     std::vector<uint32_t> set;
     bool any_stale = false;
     for (size_t m = 0; m < nm; m++) {
-        s->mesh_as[m].rebuilt_now = s->mesh_as[m].refit_now = false;
+        SrScene::MeshState& ms = s->mesh_state[m];
+        ms.rebuilt_now = ms.refit_now = false;
         if (s->meshes[m].n_vertices == 0) continue;
-        if (s->mesh_as[m].refit_pending) set.push_back((uint32_t)m);
-        any_stale = any_stale || s->blases[m].host_stale;
+        if (ms.refit_pending) set.push_back((uint32_t)m);
+        any_stale = any_stale || ms.tree.host_stale;
     }
     if (set.empty() && !any_stale) return SR_OK;
     // anything that makes the build re-concatenate the mesh trees: the form, meshes added or removed, baked copies behind the mesh
@@ -993,15 +1013,12 @@ int refit_mesh_trees(SrScene* s, uint32_t forced) {
     bool host = !s->built || !s->two_level || !s->blas_device_current || s->tl_baked;
     for (size_t i = 0; !host && i < s->fid.instances.size(); i++) host = instance_is_baked(s->fid.instances[i].o2w.m);
     for (size_t k = 0; !host && k < set.size(); k++) {
-        const uint32_t op = forced != SR_OP_NONE ? forced : srh::as_state_next_op(s->mesh_as[set[k]].state, true);
-        host = op != SR_OP_UPDATE || !s->blases[set[k]].valid;      // more than 8 updates since its rebuild: the host build (there is no device fast build for mesh trees)
+        const uint32_t op = forced != SR_OP_NONE ? forced : srh::as_state_next_op(s->mesh_state[set[k]].state, true);
+        host = op != SR_OP_UPDATE || !s->mesh_state[set[k]].tree.valid;      // more than 8 updates since its rebuild: the host build (there is no device fast build for mesh trees)
     }
     if (host) {
         for (size_t m = 0; m < nm; m++)
-            if (s->mesh_as[m].refit_pending || s->blases[m].host_stale) {
-                s->blases[m].valid = false; s->blases[m].host_stale = false; s->mesh_as[m].refit_pending = false;
-                s->blas_device_current = false; s->tl_mesh_rows_current = false;
-            }
+            if (s->mesh_state[m].refit_pending || s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
         return SR_OK;
     }
     if (set.empty()) return SR_OK;
@@ -1012,10 +1029,10 @@ int refit_mesh_trees(SrScene* s, uint32_t forced) {
         uint32_t threads = 0;
         for (size_t k = 0; k < set.size(); k++) {
             const uint32_t m = set[k];
-            const SrScene::HostBlas& b = s->blases[m];
+            const SrScene::HostBlas& b = s->mesh_state[m].tree;
             srd::BlasRefitMesh& r = rows[k];
             r.vertices = (uint64_t)(uintptr_t)s->meshes[m].d_vertices; r.indices = (uint64_t)(uintptr_t)s->meshes[m].d_indices;
-            r.tri_base = s->blas_tri_base[m]; r.n_tris = b.n_tris; r.n_vertices = s->meshes[m].n_vertices;
+            r.tri_base = s->mesh_state[m].tri_base; r.n_tris = b.n_tris; r.n_vertices = s->meshes[m].n_vertices;
             r.first_thread = threads; r.mesh_slot = m; r.textured = b.shade_tex.empty() ? 0u : 1u;
             threads += (b.n_tris + 63u) & ~63u;
             std::vector<uint32_t> nodes, offsets;       // deepest level first; the topology of the host copy is never stale
@@ -1023,7 +1040,7 @@ int refit_mesh_trees(SrScene* s, uint32_t forced) {
             const size_t levels = offsets.size() - 1;
             if (by_depth.size() < levels) by_depth.resize(levels);
             for (size_t l = 0; l < levels; l++)
-                for (uint32_t q = offsets[l]; q < offsets[l + 1]; q++) by_depth[levels - 1 - l].push_back(s->blas_node_base[m] + nodes[q]);
+                for (uint32_t q = offsets[l]; q < offsets[l + 1]; q++) by_depth[levels - 1 - l].push_back(s->mesh_state[m].node_base + nodes[q]);
         }
         std::vector<uint32_t> list;
         s->refit_level_offsets.assign(1, 0u);
@@ -1041,30 +1058,24 @@ int refit_mesh_trees(SrScene* s, uint32_t forced) {
         s->refit_threads = threads;
     }
     if ((rc = s->d_blas_node_box.reserve((size_t)s->tl_blas_nodes * 24)) != SR_OK) return rc;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};           // kernel times, only while sr_scene_enable_timing is on
-    if (s->timing) for (auto& e_ : ev) if (hipEventCreate(&e_) != hipSuccess) e_ = nullptr;
-    const bool timed = ev[0] && ev[1] && ev[2];
-    if (timed) (void)hipEventRecord(ev[0], nullptr);
+    ThreeMarkTimer timer(s);
+    timer.mark();
     srd::TlMeshRow* rows_dev = (s->tl_mesh_rows_current && s->d_tl_mesh_rows.bytes >= nm * sizeof(srd::TlMeshRow)) ? (srd::TlMeshRow*)s->d_tl_mesh_rows.p : nullptr;
     int e = srk_blas_records((const srd::BlasRefitMesh*)s->d_refit_meshes.p, (uint32_t)set.size(), s->refit_threads, (float4*)s->d_tris.p, (float4*)s->d_shade.p,
                              s->any_textured_tl ? (float4*)s->d_shade_tex.p : nullptr, (uint32_t*)s->d_refit_acc.p, (const uint32_t*)s->d_refit_acc_init.p,
                              rows_dev, (float*)s->d_refit_out.p, nullptr);
-    if (timed) (void)hipEventRecord(ev[1], nullptr);
+    timer.mark();
     if (e == 0) e = srk_blas_refit((uint32_t*)s->d_blas_nodes.p, (const float4*)s->d_tris.p, (float*)s->d_blas_node_box.p, (const uint32_t*)s->d_refit_nodes.p,
                                    s->refit_level_offsets.data(), (uint32_t)s->refit_level_offsets.size() - 1, nullptr);
-    if (timed) (void)hipEventRecord(ev[2], nullptr);
+    timer.mark();
     std::vector<float> out(set.size() * 8);
     const hipError_t ce = e == 0 ? hipMemcpy(out.data(), s->d_refit_out.p, out.size() * 4, hipMemcpyDeviceToHost) : hipSuccess;   // 32 bytes per mesh; waits for the launches above
-    if (timed && e == 0 && ce == hipSuccess) {
-        float a = 0.0f, b = 0.0f;
-        if (hipEventSynchronize(ev[2]) == hipSuccess && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[1], ev[2]) == hipSuccess) { s->mu_info.flatten_ms = a; s->mu_info.refit_ms = b; }
-    }
-    for (auto& e_ : ev) if (e_) (void)hipEventDestroy(e_);
+    if (e == 0 && ce == hipSuccess) timer.read(&s->mu_info.flatten_ms, &s->mu_info.refit_ms);
     if (e != 0) return fail(SR_ERR_HIP, std::string("mesh-tree refit launch failed: ") + hipGetErrorString((hipError_t)e));
     HIP_TRY(ce);
     for (size_t k = 0; k < set.size(); k++) {
-        SrScene::HostBlas& b = s->blases[set[k]];
-        SrScene::MeshAs& a = s->mesh_as[set[k]];
+        SrScene::MeshState& a = s->mesh_state[set[k]];
+        SrScene::HostBlas& b = a.tree;
         const float* f = &out[k * 8];
         memcpy(b.lo, f, 12); memcpy(b.hi, f + 3, 12);
         b.max_abs_vertex = f[6]; b.max_edge_sum = f[7];
@@ -1078,10 +1089,9 @@ int refit_mesh_trees(SrScene* s, uint32_t forced) {
 
 // What the build of a sr_scene_set_instances in the two-level form did to every mesh's tree, into the per-mesh heuristic states.
 void mark_mesh_trees(SrScene* s, uint32_t forced) {
-    if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
     for (size_t m = 0; m < s->meshes.size(); m++) {
         if (s->meshes[m].n_vertices == 0) continue;
-        SrScene::MeshAs& a = s->mesh_as[m];
+        SrScene::MeshState& a = s->mesh_state[m];
         if (a.rebuilt_now) {
             const uint32_t op = (!a.built_once || forced == SR_OP_SLOW_BUILD) ? SR_OP_SLOW_BUILD : SR_OP_FAST_BUILD;
             if (a.build_type != SR_BUILD_STATIC && a.built_once) srh::as_state_mark_built(a.state, op);
@@ -1097,8 +1107,6 @@ void mark_mesh_trees(SrScene* s, uint32_t forced) {
 int two_level_build(SrScene* s, bool list_changed) {
     const auto t0 = std::chrono::steady_clock::now();
     int rc;
-    const size_t nm = s->meshes.size();
-    s->blases.resize(nm);
     bool any_textured = false;
     if ((rc = upload_mesh_tables(s, &any_textured)) != SR_OK) return rc;
     // a changed list of a scene that stands in this form: records, boxes and tree on the device where that path can take it
@@ -1117,12 +1125,11 @@ int two_level_build(SrScene* s, bool list_changed) {
     boxes.reserve(ni); box_inst.reserve(ni);
     std::vector<SrScene::HostBlas> baked;     // private world-space copies: instances whose transform cannot be inverted (well)
     std::vector<uint32_t> baked_inst;
-    const double eps = std::ldexp(1.0, -24);
     uint32_t blas_stack = 0;
     for (size_t i = 0; i < ni; i++) {
         const srh::HostInstance& in = s->fid.instances[i];
         const srh::HostMesh& mesh = s->meshes[in.mesh_slot];
-        SrScene::HostBlas& b = s->blases[in.mesh_slot];
+        const SrScene::HostBlas& b = s->mesh_state[in.mesh_slot].tree;
         if (!b.valid) { if ((rc = rebuild_mesh_tree(s, in.mesh_slot)) != SR_OK) return rc; s->blas_device_current = false; }
         srd::DevTlInstance& r = recs[i];
         const float* M = in.o2w.m;
@@ -1130,31 +1137,10 @@ int two_level_build(SrScene* s, bool list_changed) {
         r.tri_offset = in.tri_offset;
         r.mesh_slot = in.mesh_slot;
         if (b.n_tris == 0) continue;
-        // inverse of the affine transform, in double
-        const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
-        const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-        const double det = a00 * c00 + a01 * c01 + a02 * c02;
-        const double id = 1.0 / det;
-        const double R[9] = {c00 * id, (a02 * a21 - a01 * a22) * id, (a01 * a12 - a02 * a11) * id,
-                             c01 * id, (a00 * a22 - a02 * a20) * id, (a02 * a10 - a00 * a12) * id,
-                             c02 * id, (a01 * a20 - a00 * a21) * id, (a00 * a11 - a01 * a10) * id};
-        const double T[3] = {M[3], M[7], M[11]};
-        double r_norm = 0.0, m_norm = 0.0, t_max = 0.0;
-        bool finite = std::isfinite(id) && det != 0.0;
-        for (int row = 0; row < 3; row++) {
-            for (int c = 0; c < 3; c++) r.w2o[4 * row + c] = (float)R[3 * row + c];
-            r.w2o[4 * row + 3] = (float)(-(R[3 * row] * T[0] + R[3 * row + 1] * T[1] + R[3 * row + 2] * T[2]));
-            r_norm = std::max(r_norm, std::fabs(R[3 * row]) + std::fabs(R[3 * row + 1]) + std::fabs(R[3 * row + 2]));
-            m_norm = std::max(m_norm, std::fabs((double)M[4 * row]) + std::fabs((double)M[4 * row + 1]) + std::fabs((double)M[4 * row + 2]));
-            t_max = std::max(t_max, std::fabs(T[row]));
-            for (int c = 0; c < 4; c++) finite = finite && std::isfinite(r.w2o[4 * row + c]);
-        }
-        // A transform of rank 2 still yields real (flat) world-space triangles, and a badly conditioned one stretches object space
-        // against world space: whatever the fp32 triangle test's own rounding moves a hit by in world space (on sliver triangles
-        // that is far more than a box's padding: the round-3 fuzzer found hits 8e-3 off their triangle) is multiplied by
-        // ||W2O|| on the way into the mesh's boxes. Such an instance gets a private world-space copy of its mesh's tree and is walked
-        // without a ray transform: there the boxes see exactly what the one-level form's boxes see.
-        if (!finite || !(r_norm * m_norm < kTlMaxCondition)) {
+        srh::BuildBox bx;
+        // the record's arithmetic is tl_record.h's, shared with the device build. An instance whose transform cannot be inverted
+        // (well) gets a private world-space copy of its mesh's tree and is walked without a ray transform
+        if (srd::tl_record(M, b.lo, b.hi, b.max_abs_vertex, b.max_edge_sum, kTlMaxCondition, r.w2o, bx.lo, bx.hi, &r.pad_a, &r.pad_b) == srd::kTlRecordBaked) {
             memset(r.w2o, 0, sizeof(r.w2o));
             r.w2o[0] = r.w2o[5] = r.w2o[10] = 1.0f;
             r.flags = 1u;
@@ -1163,30 +1149,13 @@ int two_level_build(SrScene* s, bool list_changed) {
             baked_inst.push_back((uint32_t)i);
             const SrScene::HostBlas& wb = baked.back();
             bool box_ok = true;
-            srh::BuildBox bx;
             for (int a = 0; a < 3; a++) { bx.lo[a] = wb.lo[a]; bx.hi[a] = wb.hi[a]; box_ok = box_ok && std::isfinite(bx.lo[a]) && std::isfinite(bx.hi[a]); }
             blas_stack = std::max(blas_stack, wb.max_stack);
             if (box_ok) { boxes.push_back(bx); box_inst.push_back((uint32_t)i); }
             continue;
         }
         blas_stack = std::max(blas_stack, b.max_stack);
-        // world box: the 8 corners of the mesh's (already padded) box, then padding for the rounding of the transformed vertices
-        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, p_max = 0.0;
-        for (int corner = 0; corner < 8; corner++) {
-            const double x = (corner & 1) ? b.hi[0] : b.lo[0], y = (corner & 2) ? b.hi[1] : b.lo[1], z = (corner & 4) ? b.hi[2] : b.lo[2];
-            for (int row = 0; row < 3; row++) {
-                const double w = (double)M[4 * row] * x + (double)M[4 * row + 1] * y + (double)M[4 * row + 2] * z + (double)M[4 * row + 3];
-                lo[row] = std::min(lo[row], w); hi[row] = std::max(hi[row], w);
-                p_max = std::max(p_max, std::fabs(w));
-            }
-        }
-        const double pad_w = 64.0 * eps * (p_max + m_norm * b.max_abs_vertex + t_max) + 8e-6 * m_norm * b.max_edge_sum;
-        srh::BuildBox bx;
-        for (int a = 0; a < 3; a++) { bx.lo[a] = std::nextafter((float)(lo[a] - pad_w), -INFINITY); bx.hi[a] = std::nextafter((float)(hi[a] + pad_w), INFINITY); }
-        // widening of the mesh's object-space boxes: rounding of the ray transform (grows with the ray origin) and of the world-space
-        // vertices, plus the barycentric slack of the world-space triangle test seen from object space
-        r.pad_a = (float)(64.0 * eps * r_norm);
-        r.pad_b = (float)(r_norm * (64.0 * eps * (p_max + t_max + m_norm * b.max_abs_vertex) + 8e-6 * m_norm * b.max_edge_sum));
+        // a box that is not finite goes to the builder like any other (the device path leaves such a list to this loop)
         boxes.push_back(bx);
         box_inst.push_back((uint32_t)i);
     }
@@ -1197,8 +1166,8 @@ int two_level_build(SrScene* s, bool list_changed) {
     for (size_t i = 0; i < ni; i++) {
         srd::DevTlInstance& r = recs[i];
         if (r.flags & 1u) continue;
-        r.blas_root = s->blas_node_base[r.mesh_slot];
-        r.prim_base = s->blas_tri_base[r.mesh_slot];
+        r.blas_root = s->mesh_state[r.mesh_slot].node_base;
+        r.prim_base = s->mesh_state[r.mesh_slot].tri_base;
     }
     for (size_t k = 0; k < baked.size(); k++) { recs[baked_inst[k]].blas_root = s->tl_baked_node_base[k]; recs[baked_inst[k]].prim_base = s->tl_baked_tri_base[k]; }
     s->blas_stack = blas_stack;
@@ -1217,35 +1186,19 @@ int two_level_build(SrScene* s, bool list_changed) {
     if ((rc = s->d_nodes.upload(tl.nodes.data(), tl.nodes.size() * 4)) != SR_OK) return rc;
     if ((rc = s->d_tl_inst.upload(tl_inst.data(), tl_inst.size() * 4)) != SR_OK) return rc;
     if ((rc = s->d_tl_instances.upload(recs.data(), recs.size() * sizeof(srd::DevTlInstance))) != SR_OK) return rc;
-    s->dev.nodes = (const float4*)s->d_nodes.p;
-    s->dev.blas_nodes = (const float4*)s->d_blas_nodes.p;
-    s->dev.tl_inst = (const uint32_t*)s->d_tl_inst.p;
-    s->dev.tl_instances = (const srd::DevTlInstance*)s->d_tl_instances.p;
-    s->dev.tris = (const float4*)s->d_tris.p;
-    s->dev.shade = (const float4*)s->d_shade.p;
-    s->dev.shade_tex = (const float4*)s->d_shade_tex.p;
-    s->dev.slot_of_gid = (const uint32_t*)s->d_slot_of_gid.p;
-    s->dev.counters = (unsigned long long*)s->d_misc.p;
-    s->dev.n_tris = s->fid.n_triangles;
-    s->stats.n_triangles = s->fid.n_triangles;
-    s->stats.n_nodes = tl.n_nodes + s->tl_blas_nodes;
-    s->stats.node_bytes = s->stats.n_nodes * srl::kNodeBytes;
-    s->stats.tri_bytes = s->tl_blas_tris * 48;
-    s->stats.max_depth = tl.max_depth;
-    s->stats.max_stack = need;
-    s->stack_entries = (int)((std::max(need, 3u) + 1u + 3u) & ~3u);
-    s->stats.sah_cost = tl.sah_cost;
-    s->stats.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    BuiltStructure built;
+    built.n_nodes = tl.n_nodes + s->tl_blas_nodes; built.tri_bytes = s->tl_blas_tris * 48;
+    built.max_depth = tl.max_depth; built.stack_need = need; built.sah_cost = tl.sah_cost;
+    built.build_ms = ms_between(t0, std::chrono::steady_clock::now());
+    built.two_level = true;
+    publish(s, built);
     s->shape.clear();
-    s->built = true;
-    s->two_level = true;
-    s->last_build_on_device = false;
     s->tl_boxes_host.assign((ni ? ni : 1) * 6, std::numeric_limits<float>::quiet_NaN());
     for (size_t k = 0; k < boxes.size(); k++) { memcpy(&s->tl_boxes_host[(size_t)box_inst[k] * 6], boxes[k].lo, 12); memcpy(&s->tl_boxes_host[(size_t)box_inst[k] * 6 + 3], boxes[k].hi, 12); }
     SrTopLevelInfo& info = s->tl_info;
     info.on_device = 0u; info.reason = host_reason;
     info.n_nodes = tl.n_nodes; info.n_boxes = (uint32_t)boxes.size(); info.n_instances = (uint32_t)ni; info.max_stack = tl.max_stack; info.blas_stack = s->blas_stack;
-    info.records_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    info.records_ms = ms_between(t0, t1);
     info.tree_ms = tl.build_ms;
     info.build_ms = s->stats.build_ms;
     return SR_OK;
@@ -1306,24 +1259,12 @@ int fast_build(SrScene* s) {
     if ((rc = s->d_level_nodes.upload(level_nodes.data(), level_nodes.size() * 4)) != SR_OK) return rc;
     s->shape.resize(s->fid.instances.size());
     for (size_t i = 0; i < s->shape.size(); i++) s->shape[i] = s->fid.instances[i].mesh_slot;
-    s->dev.nodes = (const float4*)s->d_nodes.p;
-    s->dev.tris = (const float4*)s->d_tris.p;
-    s->dev.shade = (const float4*)s->d_shade.p;
-    s->dev.shade_tex = (const float4*)s->d_shade_tex.p;
-    s->dev.slot_of_gid = (const uint32_t*)s->d_slot_of_gid.p;
-    s->dev.counters = (unsigned long long*)s->d_misc.p;
-    s->dev.n_tris = n;
-    s->stats.n_triangles = n;
-    s->stats.n_nodes = r.n_nodes;
-    s->stats.node_bytes = (uint64_t)r.n_nodes * srl::kNodeBytes;
-    s->stats.tri_bytes = (uint64_t)n * 48;
-    s->stats.max_depth = r.max_depth;
-    s->stats.max_stack = r.max_stack;
-    s->stack_entries = (int)((std::max(r.max_stack, 3u) + 1u + 3u) & ~3u);
-    s->stats.sah_cost = 0.0f;
-    s->stats.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    s->built = true;
-    s->last_build_on_device = true;
+    BuiltStructure built;
+    built.n_nodes = r.n_nodes; built.tri_bytes = (uint64_t)n * 48;
+    built.max_depth = r.max_depth; built.stack_need = r.max_stack;
+    built.build_ms = ms_between(t0, std::chrono::steady_clock::now());
+    built.on_device = true;
+    publish(s, built);
     return SR_OK;
 }
 
@@ -1353,10 +1294,10 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     s->fid = std::move(fid);
     // meshes updated since the structure last took their vertices (sr_scene_update_mesh): every path below applies them
     const bool reshade = s->geometry_stale;
-    s->mu_info.dirty_meshes = (uint32_t)std::count(s->mesh_dirty.begin(), s->mesh_dirty.end(), (char)1);
+    s->mu_info.dirty_meshes = (uint32_t)std::count_if(s->mesh_state.begin(), s->mesh_state.end(), [](const SrScene::MeshState& ms) { return ms.dirty; });
     s->mu_info.reshaded = 0; s->mu_info.blas_rebuilt = 0; s->mu_info.blas_refitted = 0;
     s->mu_info.tables_ms = s->mu_info.flatten_ms = s->mu_info.refit_ms = s->mu_info.blas_build_ms = 0.0;
-    auto applied = [s] { std::fill(s->mesh_dirty.begin(), s->mesh_dirty.end(), (char)0); s->geometry_stale = false; };
+    auto applied = [s] { for (auto& ms : s->mesh_state) ms.dirty = false; s->geometry_stale = false; };
     s->emissive_table = s->emissive_tris;
     if (s->emissive_table.empty()) { SrEmissiveTriangle z; memset(&z, 0, sizeof(z)); s->emissive_table.push_back(z); }
     // Two-level form (a tree per mesh + a top-level tree over the instances): on request or where the flattened copy would be
@@ -1376,14 +1317,10 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
         applied();
         return SR_OK;
     }
-    for (size_t m = 0; m < s->mesh_as.size() && m < s->blases.size(); m++)      // the one-level form has no mesh trees to refit
-        if (s->mesh_as[m].refit_pending || s->blases[m].host_stale) {
-            s->blases[m].valid = false; s->blases[m].host_stale = false; s->mesh_as[m].refit_pending = false;
-            s->blas_device_current = false; s->tl_mesh_rows_current = false;
-        }
+    for (size_t m = 0; m < s->mesh_state.size(); m++)      // the one-level form has no mesh trees to refit
+        if (s->mesh_state[m].refit_pending || s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
     if (s->two_level) {                       // back to the one-level form: everything is rebuilt
         s->two_level = false; s->built = false;
-        s->dev.blas_nodes = nullptr; s->dev.tl_inst = nullptr; s->dev.tl_instances = nullptr;
         s->forced_op = s->forced_op == SR_OP_NONE ? SR_OP_SLOW_BUILD : s->forced_op;
     }
     // Tlas::queue_build (tlas.rs:155-191): the instance data is new, so the heuristic is asked with inputs_changed =
@@ -1417,29 +1354,24 @@ int sr_scene_end_frame(SrScene* s) {
     bool mesh_settles = false;
     std::vector<uint32_t> mesh_ops;
     if (s->two_level) {
-        if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
         mesh_ops.assign(s->meshes.size(), SR_OP_NONE);
         for (size_t m = 0; m < s->meshes.size(); m++) {
-            SrScene::MeshAs& a = s->mesh_as[m];
+            SrScene::MeshState& a = s->mesh_state[m];
             a.rebuilt_now = a.refit_now = false;
             if (s->meshes[m].n_vertices == 0 || a.build_type == SR_BUILD_STATIC || !a.built_once || a.refit_pending) continue;
             mesh_ops[m] = srh::as_state_next_op(a.state, false);
-            if (mesh_ops[m] == SR_OP_SLOW_BUILD) {
-                s->blases[m].valid = false; s->blases[m].host_stale = false;
-                s->blas_device_current = false; s->tl_mesh_rows_current = false;
-                mesh_settles = true;
-            }
+            if (mesh_ops[m] == SR_OP_SLOW_BUILD) { invalidate_mesh_tree(s, (uint32_t)m); mesh_settles = true; }
         }
     }
     if (op == SR_OP_SLOW_BUILD || mesh_settles) {
         int rc = bind_device(s);
         if (rc != SR_OK) return rc;
         if (s->two_level && !s->blas_device_current)      // the re-concatenation takes the stale host copies of refitted meshes along
-            for (auto& b : s->blases) if (b.host_stale) { b.valid = false; b.host_stale = false; }
+            for (size_t m = 0; m < s->mesh_state.size(); m++) if (s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
         if ((rc = s->two_level ? two_level_build(s, false) : full_build(s)) != SR_OK) { s->built = false; return rc; }
     }
     for (size_t m = 0; m < mesh_ops.size(); m++) {
-        SrScene::MeshAs& a = s->mesh_as[m];
+        SrScene::MeshState& a = s->mesh_state[m];
         if (s->meshes[m].n_vertices == 0) continue;
         if (a.build_type != SR_BUILD_STATIC && a.built_once && !a.refit_pending) {
             const uint32_t done = a.rebuilt_now ? SR_OP_SLOW_BUILD : mesh_ops[m];     // rebuilt along with a settling mesh: a quality build too
@@ -1517,13 +1449,8 @@ int sr_scene_set_mesh_build_type(SrScene* s, uint64_t key, uint32_t build_type) 
     auto it = s->slots.find(key);
     if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_build_type: no mesh is registered under this key");
     const uint32_t slot = it->second;
-    if (s->mesh_as.size() < s->meshes.size()) s->mesh_as.resize(s->meshes.size());
-    SrScene::MeshAs& a = s->mesh_as[slot];
-    if (build_type == SR_BUILD_STATIC && a.refit_pending) {       // a Static mesh is never refitted: its pending update becomes a rebuild
-        a.refit_pending = false;
-        if (slot < s->blases.size()) s->blases[slot].valid = false;
-        s->blas_device_current = false; s->tl_mesh_rows_current = false;
-    }
+    SrScene::MeshState& a = s->mesh_state[slot];
+    if (build_type == SR_BUILD_STATIC && a.refit_pending) invalidate_mesh_tree(s, slot);       // a Static mesh is never refitted: its pending update becomes a rebuild
     a.build_type = build_type;
     srh::as_state_initial(build_type, &a.state);
     return SR_OK;
@@ -1533,7 +1460,7 @@ int sr_scene_mesh_as_state(const SrScene* s, uint64_t key, uint32_t* build_type,
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_as_state: scene is null");
     auto it = s->slots.find(key);
     if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_as_state: no mesh is registered under this key");
-    const SrScene::MeshAs a = it->second < s->mesh_as.size() ? s->mesh_as[it->second] : SrScene::MeshAs();
+    const SrScene::MeshState& a = s->mesh_state[it->second];
     if (build_type) *build_type = a.build_type;
     if (state) *state = a.state;
     if (last_op) *last_op = a.last_op;
@@ -1547,11 +1474,11 @@ int sr_scene_read_mesh_tree(const SrScene* s, uint64_t key, uint32_t* n_nodes, u
     if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_mesh_tree: no mesh is registered under this key");
     if (!s->built || !s->two_level) return fail(SR_ERR_STATE, "sr_scene_read_mesh_tree: the scene is not built in the two-level form");
     const uint32_t slot = it->second;
-    if (!s->blas_device_current || slot >= s->blases.size() || !s->blases[slot].valid || slot >= s->blas_node_base.size())
+    const SrScene::MeshState& ms = s->mesh_state[slot];
+    if (!s->blas_device_current || !ms.tree.valid)
         return fail(SR_ERR_STATE, "sr_scene_read_mesh_tree: the mesh's tree is not on the device (sr_scene_set_instances builds it)");
-    if (s->geometry_stale || (slot < s->mesh_as.size() && s->mesh_as[slot].refit_pending)) return fail(SR_ERR_STATE, std::string("sr_scene_read_mesh_tree: ") + kStaleGeometry);
-    const SrScene::HostBlas& b = s->blases[slot];
-    const uint32_t nb = s->blas_node_base[slot], tb = s->blas_tri_base[slot], nn = b.n_nodes, nt = b.n_tris;
+    if (s->geometry_stale || ms.refit_pending) return fail(SR_ERR_STATE, std::string("sr_scene_read_mesh_tree: ") + kStaleGeometry);
+    const uint32_t nb = ms.node_base, tb = ms.tri_base, nn = ms.tree.n_nodes, nt = ms.tree.n_tris;
     if (n_nodes) *n_nodes = nn;
     if (n_tris) *n_tris = nt;
     HIP_TRY(hipSetDevice(s->device));
@@ -1633,17 +1560,9 @@ int full_build(SrScene* s) {
         for (uint32_t slot = 0; slot < n_tris; slot++) {
             const srh::BuildTri& t = s->world_tris[bvh.order[slot]];
             const srh::HostMesh& mesh = s->meshes[s->fid.instances[t.inst].mesh_slot];
-            float* q = &shade_tex[(size_t)slot * 24];
             const SrVertex* v[3];
             for (int j = 0; j < 3; j++) v[j] = &mesh.vertices[mesh.indices[3 * t.prim + j]];
-            for (int j = 0; j < 3; j++) {
-                memcpy(q + 2 * j, v[j]->base_color_tex_coord, 8);
-                memcpy(q + 6 + 2 * j, v[j]->normal_tex_coord, 8);
-            }
-            memcpy(q + 12, v[0]->tangent, 12);
-            q[15] = v[0]->tangent[3] >= 0.0f ? 1.0f : -1.0f;   // handedness from the first vertex only (closest_hit.slang:34)
-            memcpy(q + 16, v[1]->tangent, 12);
-            memcpy(q + 19, v[2]->tangent, 12);
+            pack_shade_tex(&shade_tex[(size_t)slot * 24], v);
         }
     }
     // device upload (synchronous, like the reference's scene-load BLAS build: blas.rs:178)
@@ -1664,24 +1583,11 @@ int full_build(SrScene* s) {
     if ((rc = s->d_slot_of_gid.upload(slot_of_gid.data(), slot_of_gid.size() * 4)) != SR_OK) return rc;
     if (any_textured) { if ((rc = s->d_shade_tex.upload(shade_tex.data(), shade_tex.size() * 4)) != SR_OK) return rc; }
     else s->d_shade_tex.release();
-    s->dev.nodes = (const float4*)s->d_nodes.p;
-    s->dev.tris = (const float4*)s->d_tris.p;
-    s->dev.shade = (const float4*)s->d_shade.p;
-    s->dev.shade_tex = (const float4*)s->d_shade_tex.p;
-    s->dev.slot_of_gid = (const uint32_t*)s->d_slot_of_gid.p;
-    s->dev.counters = (unsigned long long*)s->d_misc.p;
-    s->dev.n_tris = s->fid.n_triangles;
-    s->stats.n_triangles = s->fid.n_triangles;
-    s->stats.n_nodes = bvh.n_nodes;
-    s->stats.node_bytes = (uint64_t)bvh.n_nodes * srl::kNodeBytes;
-    s->stats.tri_bytes = (uint64_t)s->fid.n_triangles * 48;
-    s->stats.max_depth = bvh.max_depth;
-    s->stats.max_stack = bvh.max_stack;
-    s->stack_entries = (int)((std::max(bvh.max_stack, 3u) + 1u + 3u) & ~3u);   // + the spare level of the branch-free push
-    s->stats.sah_cost = bvh.sah_cost;
-    s->stats.build_ms = bvh.build_ms;
-    s->built = true;
-    s->last_build_on_device = false;
+    BuiltStructure built;
+    built.n_nodes = bvh.n_nodes; built.tri_bytes = (uint64_t)s->fid.n_triangles * 48;
+    built.max_depth = bvh.max_depth; built.stack_need = bvh.max_stack; built.sah_cost = bvh.sah_cost;
+    built.build_ms = bvh.build_ms;
+    publish(s, built);
     return SR_OK;
 }
 }  // namespace

@@ -55,8 +55,8 @@ struct LbvhResult {
 int srk_lbvh_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
 size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap);
 
-// Top level of the two-level form. srk_tl_records: DevTlInstance records and padded world boxes of all instances (the host loop
-// of two_level_build, same bytes); `result` (device, 3 dwords, zeroed by the call) receives: instances this path cannot take,
+// Top level of the two-level form. srk_tl_records: DevTlInstance records and padded world boxes of all instances (tl_record.h, as
+// the host loop of two_level_build computes them); `result` (device, 3 dwords, zeroed by the call) receives: instances this path cannot take,
 // deepest mesh-tree stack, instances with a box. srk_tl_build: the builder above over those boxes; same return convention.
 int srk_tl_records(const srd::FlatInstance* instances, const srd::TlMeshRow* meshes, uint32_t n_instances, double max_condition,
                    srd::DevTlInstance* records, float* boxes, uint32_t* result, hipStream_t stream);

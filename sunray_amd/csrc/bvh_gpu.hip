@@ -16,6 +16,7 @@
 
 #include "bvh_gpu.h"
 #include "bvh_layout.h"
+#include "tl_record.h"
 #include "traverse.h"
 
 namespace srd {
@@ -539,16 +540,11 @@ __global__ void ploc_compact_kernel(const int* cid, const float* cbox, const uin
 
 // ---------------------------------------------------------------------------------------------------------------
 // Top level of the two-level form on the device (the reference rebuilds its TLAS on the GPU every frame, tlas.rs:155-191):
-//   records    one thread per instance: the DevTlInstance record and the padded world box, with the expressions of the host
-//              loop (api.cpp two_level_build) in the same order — fp64 where the host uses double, std::max / std::min
-//              spelled as the comparisons they are — so the bytes equal the host's and the padding proof of DESIGN.md
-//              section 3 carries over unchanged
+//   records    one thread per instance: the DevTlInstance record and the padded world box, by the function the host loop
+//              (api.cpp two_level_build) calls as well: tl_record.h holds the one definition of that arithmetic
 //   tree       the builder above over the boxes instead of triangles: Morton code of the box centre (instances without a
 //              box sort behind all others and stay out of the tree), radix tree or PLOC, fit, collapse, tl_inst, refit
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double max_d(double a, double b) { return a < b ? b : a; }   // std::max
-__device__ __forceinline__ double min_d(double a, double b) { return b < a ? b : a; }   // std::min
-
 // result: [0] instances this path cannot take (the host would bake them, or the box is not finite), [1] deepest mesh-tree stack
 // among the instances with a box, [2] instances with a box
 __global__ void tl_records_kernel(const FlatInstance* instances, const TlMeshRow* meshes, uint32_t n_inst, double max_condition, DevTlInstance* recs,
@@ -565,49 +561,12 @@ __global__ void tl_records_kernel(const FlatInstance* instances, const TlMeshRow
         r.mesh_slot = in.mesh_slot; r.prim_base = 0u; r.flags = 0u; r._pad = 0u;
         float bx[6];
         for (int k = 0; k < 6; k++) bx[k] = __uint_as_float(0x7FC00000u);
+        TlRecordResult res = kTlRecordOk;
         if (b.n_tris != 0u) {
-            const double eps = 5.9604644775390625e-08;   // 2^-24
-            const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
-            const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
-            const double det = a00 * c00 + a01 * c01 + a02 * c02;
-            const double id = 1.0 / det;
-            const double R[9] = {c00 * id, (a02 * a21 - a01 * a22) * id, (a01 * a12 - a02 * a11) * id,
-                                 c01 * id, (a00 * a22 - a02 * a20) * id, (a02 * a10 - a00 * a12) * id,
-                                 c02 * id, (a01 * a20 - a00 * a21) * id, (a00 * a11 - a01 * a10) * id};
-            const double T[3] = {M[3], M[7], M[11]};
-            double r_norm = 0.0, m_norm = 0.0, t_max = 0.0;
-            bool finite = isfinite(id) && det != 0.0;
-            for (int row = 0; row < 3; row++) {
-                for (int c = 0; c < 3; c++) r.w2o[4 * row + c] = (float)R[3 * row + c];
-                r.w2o[4 * row + 3] = (float)(-(R[3 * row] * T[0] + R[3 * row + 1] * T[1] + R[3 * row + 2] * T[2]));
-                r_norm = max_d(r_norm, fabs(R[3 * row]) + fabs(R[3 * row + 1]) + fabs(R[3 * row + 2]));
-                m_norm = max_d(m_norm, fabs((double)M[4 * row]) + fabs((double)M[4 * row + 1]) + fabs((double)M[4 * row + 2]));
-                t_max = max_d(t_max, fabs(T[row]));
-                for (int c = 0; c < 4; c++) finite = finite && isfinite(r.w2o[4 * row + c]);
-            }
-            if (!finite || !(r_norm * m_norm < max_condition)) bad = 1u;      // the host gives such an instance a baked copy of its mesh
-            else {
-                double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, p_max = 0.0;
-                for (int corner = 0; corner < 8; corner++) {
-                    const double x = (corner & 1) ? b.hi[0] : b.lo[0], y = (corner & 2) ? b.hi[1] : b.lo[1], z = (corner & 4) ? b.hi[2] : b.lo[2];
-                    for (int row = 0; row < 3; row++) {
-                        const double w = (double)M[4 * row] * x + (double)M[4 * row + 1] * y + (double)M[4 * row + 2] * z + (double)M[4 * row + 3];
-                        lo[row] = min_d(lo[row], w); hi[row] = max_d(hi[row], w);
-                        p_max = max_d(p_max, fabs(w));
-                    }
-                }
-                const double pad_w = 64.0 * eps * (p_max + m_norm * b.max_abs_vertex + t_max) + 8e-6 * m_norm * b.max_edge_sum;
-                bool box_ok = true;
-                for (int a = 0; a < 3; a++) {
-                    bx[a] = nextafterf((float)(lo[a] - pad_w), -INFINITY); bx[3 + a] = nextafterf((float)(hi[a] + pad_w), INFINITY);
-                    box_ok = box_ok && isfinite(bx[a]) && isfinite(bx[3 + a]);
-                }
-                r.pad_a = (float)(64.0 * eps * r_norm);
-                r.pad_b = (float)(r_norm * (64.0 * eps * (p_max + t_max + m_norm * b.max_abs_vertex) + 8e-6 * m_norm * b.max_edge_sum));
-                r.blas_root = b.blas_root; r.prim_base = b.prim_base;
-                if (box_ok) { has_box = 1u; stack = b.max_stack; } else bad = 1u;
-            }
-        } else { r.blas_root = b.blas_root; r.prim_base = b.prim_base; }
+            res = tl_record(M, b.lo, b.hi, b.max_abs_vertex, b.max_edge_sum, max_condition, r.w2o, bx, bx + 3, &r.pad_a, &r.pad_b);
+            if (res == kTlRecordOk) { has_box = 1u; stack = b.max_stack; } else bad = 1u;
+        }
+        if (res != kTlRecordBaked) { r.blas_root = b.blas_root; r.prim_base = b.prim_base; }      // the host gives a baked instance a copy of its mesh
         recs[i] = r;
         for (int k = 0; k < 6; k++) boxes[(size_t)i * 6 + k] = bx[k];
     }

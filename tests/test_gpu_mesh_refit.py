@@ -468,6 +468,49 @@ def test_fallbacks_end_in_a_host_rebuild_and_equal_the_oracle(rt, oracle):
     gsc.close()
 
 
+def test_per_mesh_state_follows_the_slot(rt, oracle):
+    """A refitted mesh with a stale host copy and a pending refit is removed and another mesh takes its slot: the newcomer starts
+    as a Static mesh that was never built, nothing of it is refitted, it traces like the oracle in both forms, and its tree is a
+    fresh two-level scene's byte for byte."""
+    desc = three_meshes()
+    gsc = rt.Scene(0, instancing="two_level")
+    slots = {m.key: gsc.add_mesh(m.key, m.vertices, m.indices, m.material) for m in desc.meshes}
+    gsc.set_instances(desc.instances)
+    gsc.set_mesh_build_type(3, SOMETIMES)
+    desc = scenes.deform(desc, [3], 1.0, amplitude=0.2)
+    push(gsc, desc, [3])
+    assert (gsc.mesh_update_info().blas_refitted, gsc.mesh_update_info().blas_rebuilt) == (1, 0)      # refitted: its host copy is stale
+    gsc.update_mesh(3, mesh_of(scenes.deform(desc, [3], 2.0, amplitude=0.2), 3).vertices)              # and a refit is pending
+    gsc.remove(3)
+    sv, si = scenes.uv_sphere(1.2, 10, 5)
+    new = scenes.MeshDesc(9, sv, si, mesh_of(desc, 3).material)
+    assert gsc.add_mesh(9, sv, si, new.material) == slots[3]                                            # LIFO slot reuse
+    bt, st, last = gsc.mesh_as_state(9)
+    assert (bt, state_fields(st), last) == (STATIC, (0, 0, 0), NONE)
+    desc = dataclasses.replace(desc, meshes=[m for m in desc.meshes if m.key != 3] + [new],
+                               instances=[(9 if k == 3 else k, xs) for k, xs in desc.instances])
+    rays = ray_set(oracle, desc, THREE_BOX, 5)
+    rd = rt.rays_to_device(rays)
+    gsc.set_instances(desc.instances)
+    assert gsc.mesh_update_info().blas_refitted == 0
+    traces_equal_brute_force(rt, oracle, gsc, desc, rays, rd, "new mesh in a reused slot")
+    gsc.set_instancing("flat")
+    gsc.set_instances(desc.instances)
+    assert not gsc.two_level()
+    traces_equal_brute_force(rt, oracle, gsc, desc, rays, rd, "reused slot, one-level form")
+    gsc.set_instancing("two_level")
+    gsc.set_instances(desc.instances)
+    assert gsc.two_level()
+    traces_equal_brute_force(rt, oracle, gsc, desc, rays, rd, "reused slot, two-level form again")
+    tree = gsc.read_mesh_tree(9)
+    fresh = rt.Scene(0, instancing="two_level").load(desc)
+    want = fresh.read_mesh_tree(9)
+    fresh.close()
+    for part in ("nodes", "tris", "shade", "shade_tex", "slot_of_prim"):
+        assert_bits_equal(want[part], tree[part], "mesh tree in a reused slot: %s" % part)
+    gsc.close()
+
+
 def test_refit_cycles_do_not_grow_hbm(rt):
     """Free device memory is constant over 40 update + set_instances cycles (refits, every ninth a host rebuild); ten cycles come
     first, as in test_update_cycles_do_not_grow_hbm: the refit's scratch and the rebuild's re-upload have then both run."""
