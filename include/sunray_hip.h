@@ -440,8 +440,9 @@ int sr_scene_update_mesh(SrScene* scene, uint64_t key, const SrVertex* vertices,
 typedef struct SrMeshUpdateInfo {
     uint32_t dirty_meshes;     /* meshes of the built structure that were updated and that the last sr_scene_set_instances applied */
     uint32_t reshaded;         /* 1: its SR_OP_UPDATE ran the variant that rewrites the shading records */
-    uint32_t blas_rebuilt;     /* two-level form: per-mesh trees it built, i.e. the invalidated ones: every mesh updated since its tree
-                                * was built, instanced at the time or not (baked copies of single instances not counted) */
+    uint32_t blas_rebuilt;     /* two-level form: per-mesh trees it built, on the host (the invalidated ones: every mesh updated since its
+                                * tree was built, instanced at the time or not; baked copies of single instances not counted) or on the
+                                * device (SrMeshTreeInfo) */
     uint32_t blas_refitted;    /* two-level form: per-mesh trees it refitted on the device (sr_scene_set_mesh_build_type) */
     double validate_copy_ms;   /* sr_scene_update_mesh: validation + host copy + emissive entries */
     double h2d_ms;             /* sr_scene_update_mesh: device wait + copy into the device allocation */
@@ -458,20 +459,59 @@ int sr_scene_mesh_update_info(const SrScene* scene, SrMeshUpdateInfo* out);
  * mesh's tree on the device (Blas::update, blas.rs:292-310) while the state asks for SR_OP_UPDATE: leaf-order records, root box
  * and padding numbers are rewritten from the new vertices with the bytes a host build writes, the quantised nodes are refitted
  * bottom-up; topology, leaf order and stack need stay, and the top level may then be built on the device (SR_TL_BUILD_*). After
- * more than 8 updates since its last rebuild the state asks for SR_OP_FAST_BUILD: that is the host build (there is no device
- * builder for mesh trees). The host build also takes over, silently and counted in blas_rebuilt, where the scene does not stand
- * in the two-level form with its mesh trees resident, where the previous or the new instance list holds an instance that needs a
- * baked copy of its mesh, and for every refitted mesh whenever the mesh trees are uploaded again (a host build, a mesh added or
- * removed, a form switch): refits and rebuilds do not mix within one call. sr_scene_end_frame counts a quiet frame for every
- * updatable mesh and rebuilds the tree of one that asks for its settle build. sr_scene_force_next_op(SR_OP_UPDATE) forces the
- * refit of the updated updatable meshes whatever their counters say, a forced build forces the host rebuild. The type has no
- * effect in the one-level form, which updates in place whatever the type: it is accepted and remembered there. Unknown key or a
- * type above SR_BUILD_STATIC: SR_ERR_INVALID_ARG. */
+ * more than 8 updates since its last rebuild the state asks for SR_OP_FAST_BUILD: the device builds the mesh's tree anew
+ * (Blas::rebuild; SR_MESH_TREE_BUILD_* below) or the host does. Refits and device builds of different meshes run in one call. The
+ * host build takes over, silently and counted in blas_rebuilt, where the scene does not stand in the two-level form with its
+ * mesh trees resident, where the previous or the new instance list holds an instance that needs a baked copy of its mesh, where
+ * a pending mesh asks for SR_OP_SLOW_BUILD or its device build is not taken (SrMeshTreeInfo.reason), and for every refitted or
+ * device-built mesh whenever the mesh trees are uploaded again (a host build, a mesh added or removed, a form switch): device
+ * work and host rebuilds do not mix within one call. sr_scene_end_frame counts a quiet frame for every updatable mesh and
+ * rebuilds the tree of one that asks for its settle build, on the host (the quality build). sr_scene_force_next_op(SR_OP_UPDATE)
+ * forces the refit of the updated updatable meshes whatever their counters say, SR_OP_FAST_BUILD their fast build, SR_OP_SLOW_BUILD
+ * the host rebuild. The type has no effect in the one-level form, which updates in place whatever the type: it is accepted and
+ * remembered there. Unknown key or a type above SR_BUILD_STATIC: SR_ERR_INVALID_ARG. */
 int sr_scene_set_mesh_build_type(SrScene* scene, uint64_t key, uint32_t build_type);
 /* The mesh's build type, its own heuristic state and the operation the last sr_scene_set_instances / sr_scene_end_frame performed
- * on its tree in the two-level form (SR_OP_UPDATE: device refit, SR_OP_FAST_BUILD / SR_OP_SLOW_BUILD: host build). Any pointer
- * may be NULL. */
+ * on its tree in the two-level form (SR_OP_UPDATE: device refit, SR_OP_FAST_BUILD: device or host build, SR_OP_SLOW_BUILD: host
+ * build). Any pointer may be NULL. */
 int sr_scene_mesh_as_state(const SrScene* scene, uint64_t key, uint32_t* build_type, SrAsState* state, uint32_t* last_op);
+/* Where the tree of an updatable mesh of the two-level form is built when its SrAsState asks for SR_OP_FAST_BUILD (the ninth update
+ * since its last rebuild, or sr_scene_force_next_op; the reference rebuilds a BLAS on the GPU, blas.rs:285-310).
+ * SR_MESH_TREE_BUILD_DEVICE: device kernels build it from the mesh's device vertex / index buffers (Morton sort + SR_FAST_BUILD
+ * topology + budgeted 4-wide collapse, as the one-level fast build) into the mesh's part of the resident arrays: leaf-order
+ * records, shading records, root box and padding numbers are byte for byte a host build's, the topology is not (the settle
+ * rebuild restores the SAH tree). SR_MESH_TREE_BUILD_HOST: the host binned-SAH builder, always, followed by the upload of every
+ * mesh's records. SR_MESH_TREE_BUILD_AUTO (default): the device from SrMeshTreeInfo.auto_threshold triangles per mesh on;
+ * as measured no size qualifies and the threshold is 0xFFFFFFFF, never: auto is the host build. A device
+ * tree deeper than 26 stack entries is refused (measured under the default topology: spheres of 65 536 triangles and more), so in
+ * mode DEVICE too the fast build of a large mesh is the host's, with its cost. The first build, the settle rebuild, Static meshes and whatever sr_scene_set_mesh_build_type lists go to
+ * the host in every mode. Queries give the same bits either way. SR_BLAS_BUILD = host | device | auto in the environment sets the
+ * initial mode (anything else: auto). A mode above SR_MESH_TREE_BUILD_DEVICE: SR_ERR_INVALID_ARG. */
+#define SR_MESH_TREE_BUILD_AUTO 0u
+#define SR_MESH_TREE_BUILD_HOST 1u
+#define SR_MESH_TREE_BUILD_DEVICE 2u
+int sr_scene_set_mesh_tree_build(SrScene* scene, uint32_t mode);
+/* Why the pending mesh trees of the last sr_scene_set_instances went to the host (SrMeshTreeInfo.reason). */
+#define SR_MESH_TREE_ON_DEVICE 0u             /* they did not (or nothing was pending) */
+#define SR_MESH_TREE_HOST_MODE 1u             /* SR_MESH_TREE_BUILD_HOST */
+#define SR_MESH_TREE_HOST_BELOW_THRESHOLD 2u  /* auto mode, a mesh with fewer triangles than auto_threshold */
+#define SR_MESH_TREE_HOST_SLOW_BUILD 3u       /* a mesh asked for SR_OP_SLOW_BUILD */
+#define SR_MESH_TREE_HOST_BAKED_INSTANCE 4u   /* the previous or the new instance list needs a baked copy of a mesh */
+#define SR_MESH_TREE_HOST_NOT_RESIDENT 5u     /* the mesh trees on the device do not match the set of meshes: first build, form switch, mesh added or removed */
+#define SR_MESH_TREE_HOST_STACK_BUDGET 6u     /* the device tree would be deeper than the traversal stack allows a mesh tree (remembered per mesh: tried once) */
+#define SR_MESH_TREE_HOST_STATIC_MESH 7u      /* a Static mesh was updated */
+typedef struct SrMeshTreeInfo {
+    uint32_t mode;             /* SR_MESH_TREE_BUILD_* in force */
+    uint32_t auto_threshold;   /* triangles of a mesh from which auto mode builds on the device */
+    uint32_t built_on_device;  /* mesh trees the last sr_scene_set_instances built on the device ... */
+    uint32_t built_on_host;    /* ... and on the host: together SrMeshUpdateInfo.blas_rebuilt */
+    uint32_t reason;           /* SR_MESH_TREE_ON_DEVICE or SR_MESH_TREE_HOST_* */
+    uint32_t n_nodes;          /* nodes ... */
+    uint32_t max_stack;        /* ... and worst-case stack entries of the last device-built tree */
+    uint32_t _pad;
+    double device_build_ms;    /* the device builds of that call, launch to completion (only while sr_scene_enable_timing is on) */
+} SrMeshTreeInfo;              /* 40 bytes */
+int sr_scene_mesh_tree_info(const SrScene* scene, SrMeshTreeInfo* out);
 /* Harness read-back of one mesh's part of the concatenated device arrays of a scene built in the two-level form (the counterpart
  * of sr_scene_read_top_level): n_nodes x 16 dwords with references local to the mesh, then per leaf-order slot 12 floats
  * (v0, v1, v2, primitive, 0, 0), 12 floats of `shade`, 24 floats of `shade_tex` (zeros where the scene has no textured
@@ -706,6 +746,8 @@ int sr_renderer_unload_mesh(SrRenderer* renderer, uint64_t key);
 int sr_renderer_update_mesh(SrRenderer* renderer, uint64_t key, const SrVertex* vertices, uint32_t n_vertices);
 /* sr_scene_set_mesh_build_type on every device slot's scene. */
 int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t build_type);
+/* sr_scene_set_mesh_tree_build on every device slot's scene. */
+int sr_renderer_set_mesh_tree_build(SrRenderer* renderer, uint32_t mode);
 
 /* Harness access: inner scene (counters, stats), device pointers of the RGBA8 output and the fp32 radiance OF THE LAST
  * SUBMITTED FRAME (valid after sr_renderer_wait_frame of that frame), and relative_frame_count. Any out pointer may be NULL.

@@ -1,9 +1,12 @@
 #!/bin/bash
 # Register / scratch / occupancy figures of the pass kernels as the compiler reports them (no GPU needed).
-# usage: scripts/kernel_resources.sh [extra -D flags]
+# usage: scripts/kernel_resources.sh [FILE.hip] [extra -D flags]     FILE: a source of sunray_amd/csrc (default kernels.hip, the pass
+#        kernels; bvh_gpu.hip: the builders and refits)
 cd "$(dirname "$0")/.."
+SRC=kernels.hip
+case "$1" in *.hip) SRC="$1"; shift ;; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-fast-math \
-    -fno-slp-vectorize --cuda-device-only -Rpass-analysis=kernel-resource-usage "$@" -x hip -c sunray_amd/csrc/kernels.hip -o /dev/null 2>&1 |
+    -fno-slp-vectorize --cuda-device-only -Rpass-analysis=kernel-resource-usage "$@" -x hip -c "sunray_amd/csrc/$SRC" -o /dev/null 2>&1 |
   python3 -c '
 import sys, re
 cur = None

@@ -30,6 +30,7 @@ SYMBOLS = [
     "sr_scene_set_top_level_build", "sr_scene_top_level_info", "sr_scene_read_top_level",
     "sr_scene_update_mesh", "sr_scene_mesh_update_info", "sr_renderer_update_mesh",
     "sr_scene_set_mesh_build_type", "sr_scene_mesh_as_state", "sr_scene_read_mesh_tree", "sr_renderer_set_mesh_build_type",
+    "sr_scene_set_mesh_tree_build", "sr_scene_mesh_tree_info", "sr_renderer_set_mesh_tree_build",
 ]
 
 

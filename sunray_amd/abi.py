@@ -160,6 +160,15 @@ class SrMeshUpdateInfo(C.Structure):  # the last sr_scene_update_mesh and the sr
                 ("refit_ms", C.c_double), ("blas_build_ms", C.c_double)]
 
 
+class SrMeshTreeInfo(C.Structure):  # the mesh-tree builds of the last sr_scene_set_instances (sr_scene_mesh_tree_info)
+    _fields_ = [("mode", C.c_uint32), ("auto_threshold", C.c_uint32), ("built_on_device", C.c_uint32), ("built_on_host", C.c_uint32),
+                ("reason", C.c_uint32), ("n_nodes", C.c_uint32), ("max_stack", C.c_uint32), ("_pad", C.c_uint32), ("device_build_ms", C.c_double)]
+
+
+MESH_TREE_BUILD_AUTO, MESH_TREE_BUILD_HOST, MESH_TREE_BUILD_DEVICE = 0, 1, 2
+(MESH_TREE_ON_DEVICE, MESH_TREE_HOST_MODE, MESH_TREE_HOST_BELOW_THRESHOLD, MESH_TREE_HOST_SLOW_BUILD, MESH_TREE_HOST_BAKED_INSTANCE,
+ MESH_TREE_HOST_NOT_RESIDENT, MESH_TREE_HOST_STACK_BUDGET, MESH_TREE_HOST_STATIC_MESH) = range(8)
+MESH_TREE_STACK_CAP = 26  # stack entries a mesh tree of the two-level form may need (csrc/api.cpp)
 TL_BUILD_AUTO, TL_BUILD_HOST, TL_BUILD_DEVICE = 0, 1, 2
 (TL_ON_DEVICE, TL_HOST_MODE, TL_HOST_BELOW_THRESHOLD, TL_HOST_BAKED_INSTANCE, TL_HOST_STACK_BUDGET, TL_HOST_NOT_TWO_LEVEL,
  TL_HOST_TOO_FEW, TL_HOST_QUALITY_BUILD) = range(8)

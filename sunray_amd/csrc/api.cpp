@@ -105,6 +105,19 @@ struct DeviceBuffer {
         if (n) HIP_TRY(hipMemcpy(p, src, n, hipMemcpyHostToDevice));
         return SR_OK;
     }
+    // Grows to n bytes and keeps the first `keep` bytes (device-to-device); the caller has waited for whatever reads the old allocation.
+    int grow_keep(size_t n, size_t keep) {
+        if (p && n <= bytes) return SR_OK;
+        void* q = nullptr;
+        HIP_TRY(hipMalloc(&q, n ? n : 16));
+        if (p && keep) {
+            const hipError_t e = hipMemcpy(q, p, std::min(keep, bytes), hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) { (void)hipFree(q); return fail(SR_ERR_HIP, std::string("device-to-device copy of a growing buffer: ") + hipGetErrorString(e)); }
+        }
+        release();
+        p = q; bytes = n ? n : 16;
+        return SR_OK;
+    }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 };
 
@@ -163,8 +176,11 @@ struct SrScene {
         float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // root box, object space
         float max_edge_sum = 0.0f, max_abs_vertex = 0.0f;
         double build_ms = 0.0;
-        bool host_stale = false;            // refitted on the device since: nodes / tris / shade / shade_tex above hold the old vertices
-                                            // (topology, slot_of_prim, counts, max_stack and the read-back lo, hi, max_* are current)
+        bool host_stale = false;            // refitted or built on the device since: nodes / tris / shade / shade_tex above hold the old vertices
+                                            // (after a refit, topology, slot_of_prim, counts, max_stack and the read-back lo, hi, max_* are current)
+        bool device_built = false;          // built on the device since (implies host_stale): nodes' topology and slot_of_prim above are stale too;
+                                            // n_nodes, max_stack, max_depth, lo, hi, max_* are the read-back, the levels are level_ranges
+        std::vector<std::pair<uint32_t, uint32_t>> level_ranges;   // of a device-built tree: (first node, count) per level, root level first, local to the mesh
     };
     // Everything the scene keeps per mesh slot beside the mesh itself: its tree, where the tree sits in the concatenated device
     // arrays, and its maintenance (Blas::plan_op / mark_built, blas.rs:245-310): build type, heuristic state, what the last
@@ -172,6 +188,10 @@ struct SrScene {
     struct MeshState {
         HostBlas tree;
         uint32_t node_base = 0, tri_base = 0;    // of the concatenated device arrays (upload_mesh_trees)
+        int device_refused = -1;                 // >= 0: the device build refused this mesh's tree for depth under that SR_FAST_BUILD topology
+                                                 // (fast_build_ploc): later fast builds go to the host without another attempt
+        uint32_t node_cap = 0;                   // > 0: the mesh owns the node range [node_base, node_base + node_cap) behind the concatenation, taken
+                                                 // at its first device build and kept for later ones; 0: the compact range the concatenation gave it
         uint32_t build_type = SR_BUILD_STATIC;   // Renderer::load_mesh builds Static (lib.rs:937)
         SrAsState state{0, 0, 0, 0};
         uint32_t last_op = SR_OP_NONE;
@@ -191,6 +211,11 @@ struct SrScene {
     bool tl_baked = false;                  // the device arrays hold baked (world-space) copies of some instances' meshes
     std::vector<uint32_t> tl_baked_node_base, tl_baked_tri_base;
     uint64_t tl_blas_nodes = 0, tl_blas_tris = 0;
+    uint64_t blas_node_end = 0;             // nodes of d_blas_nodes in use, the ranges of device-built meshes included (d_blas_node_box has as many rows)
+    int blas_build_mode = SR_MESH_TREE_BUILD_AUTO;   // sr_scene_set_mesh_tree_build / SR_BLAS_BUILD in the environment
+    SrMeshTreeInfo mt_info{};               // mesh-tree builds of the last sr_scene_set_instances
+    bool static_mesh_updated = false;       // a Static mesh was updated since the last sr_scene_set_instances (its tree goes to the host)
+    DeviceBuffer d_blas_build_out;          // read-back block of a device mesh-tree build
     DeviceBuffer d_blas_nodes, d_tl_inst, d_tl_instances;
     // top level built on the device (bvh_gpu.hip srk_tl_*): per-mesh rows the record kernel reads, the instance boxes, its result block
     DeviceBuffer d_tl_mesh_rows, d_tl_boxes, d_tl_result;
@@ -343,6 +368,7 @@ int sr_scene_create(int device, SrScene** out) {
     if (const char* ev = getenv("SR_TILE_SCHEDULING")) s->tile_scheduling = atoi(ev) != 0;
     if (const char* ev = getenv("SR_INSTANCING")) s->instancing = !strcmp(ev, "two_level") ? SR_INSTANCING_TWO_LEVEL : (!strcmp(ev, "flat") ? SR_INSTANCING_FLAT : SR_INSTANCING_AUTO);
     if (const char* ev = getenv("SR_TL_BUILD")) s->tl_build_mode = !strcmp(ev, "host") ? SR_TL_BUILD_HOST : (!strcmp(ev, "device") ? SR_TL_BUILD_DEVICE : SR_TL_BUILD_AUTO);
+    if (const char* ev = getenv("SR_BLAS_BUILD")) s->blas_build_mode = !strcmp(ev, "host") ? SR_MESH_TREE_BUILD_HOST : (!strcmp(ev, "device") ? SR_MESH_TREE_BUILD_DEVICE : SR_MESH_TREE_BUILD_AUTO);
     if (const char* ev = getenv("SR_FAST_BUILD")) s->fast_build_ploc = !strcmp(ev, "lbvh") ? 0 : (!strncmp(ev, "ploc", 4) && atoi(ev + 4) > 0 ? atoi(ev + 4) : 16);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cus = prop.multiProcessorCount;
@@ -513,9 +539,9 @@ int sr_scene_update_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uin
     }
     // two-level form: this mesh's object-space tree, root box and padding numbers are stale; the other meshes keep theirs. An
     // updatable mesh (sr_scene_set_mesh_build_type) with a valid tree keeps it: the next sr_scene_set_instances refits it on the
-    // device where it can (refit_mesh_trees) and invalidates it otherwise
+    // or builds it on the device where it can (maintain_mesh_trees) and invalidates it otherwise
     if (s->mesh_state[slot].build_type != SR_BUILD_STATIC && s->mesh_state[slot].tree.valid) s->mesh_state[slot].refit_pending = true;
-    else invalidate_mesh_tree(s, slot);
+    else { invalidate_mesh_tree(s, slot); s->static_mesh_updated = s->static_mesh_updated || s->mesh_state[slot].build_type == SR_BUILD_STATIC; }
     if (s->built) {
         bool instanced = false;
         for (const auto& in : s->fid.instances) if (in.mesh_slot == slot) { instanced = true; break; }
@@ -826,7 +852,8 @@ int build_blas(const srh::HostMesh& mesh, uint32_t mesh_slot, const SrTransform*
     return SR_OK;
 }
 
-// The host build of one mesh's tree (the only mesh-tree build there is: the project has no device builder for mesh trees).
+// The host build of one mesh's tree: the first build, the settle rebuild, every build of a Static mesh, and whatever the device
+// build (build_mesh_trees_device) does not take.
 int rebuild_mesh_tree(SrScene* s, uint32_t m) {
     SrScene::MeshState& ms = s->mesh_state[m];
     ms.tree = SrScene::HostBlas();
@@ -878,7 +905,10 @@ int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
         if (!ms.tree.valid || ms.tree.host_stale || ms.refit_pending) { if ((rc = rebuild_mesh_tree(s, (uint32_t)m)) != SR_OK) return rc; }
         cat.textured = cat.textured || !ms.tree.shade_tex.empty();
     }
-    for (size_t m = 0; m < nm; m++) if (s->meshes[m].n_vertices) cat.append(s->mesh_state[m].tree, &s->mesh_state[m].node_base, &s->mesh_state[m].tri_base);
+    for (size_t m = 0; m < nm; m++) {
+        s->mesh_state[m].node_cap = 0;        // the ranges behind the concatenation are given up: a later device build takes a new one
+        if (s->meshes[m].n_vertices) cat.append(s->mesh_state[m].tree, &s->mesh_state[m].node_base, &s->mesh_state[m].tri_base);
+    }
     s->tl_baked_node_base.assign(baked.size(), 0u); s->tl_baked_tri_base.assign(baked.size(), 0u);
     for (size_t k = 0; k < baked.size(); k++) cat.append(baked[k], &s->tl_baked_node_base[k], &s->tl_baked_tri_base[k]);
     if (cat.tris.size() / 12 >= (1ull << 28) || cat.nodes.size() / srl::kNodeDwords >= (1ull << 31)) return fail(SR_ERR_UNSUPPORTED, "the meshes together exceed 2^28 triangles (leaf reference encoding)");
@@ -893,6 +923,7 @@ int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
     if ((rc = s->d_slot_of_gid.upload(cat.slot_of_prim.data(), cat.slot_of_prim.size() * 4)) != SR_OK) return rc;
     s->any_textured_tl = cat.textured;
     s->tl_blas_nodes = cat.nodes.size() / srl::kNodeDwords; s->tl_blas_tris = cat.tris.size() / 12;
+    s->blas_node_end = s->tl_blas_nodes;
     s->blas_device_current = true;
     s->tl_baked = !baked.empty();
     s->tl_mesh_rows_current = false;
@@ -989,40 +1020,130 @@ bool instance_is_baked(const float* M) {
     return srd::tl_record(M, unit_lo, unit_hi, 0.0f, 0.0f, kTlMaxCondition, w2o, lo, hi, &pad_a, &pad_b) == srd::kTlRecordBaked;
 }
 
-// Blas::update (blas.rs:292-310) for the meshes updated since the last sr_scene_set_instances whose build type allows it
-// (refit_pending): where every one of them may be refitted, the device rewrites their leaf-order records and root boxes and
-// refits their nodes in place (bvh_gpu.hip), and the concatenated arrays stay current. Otherwise their trees are invalidated
+// Triangles of a mesh from which SR_MESH_TREE_BUILD_AUTO builds its tree on the device: the smallest measured size at which the
+// device build beats both the host build and the library before this path by more than the two spreads of 20 calls combined,
+// rounded up to a power of two (the rule kTlDeviceMinBoxes was set by), provided the device takes a measured size at or above
+// that threshold. Measured on an MI355X (scripts/gpu_mesh_tree_build.py -> profiles/mesh_tree_build.json, table in DESIGN.md
+// section 4): the device loses at 1 024 and 4 096 triangles (launch-bound: a stream wait per PLOC iteration and per collapse level),
+// wins at 20 992 (3.6 against 10.4 ms), and the default PLOC trees of the 65 536-, 250 000- and 1 000 000-triangle spheres are deeper
+// than kBlasStackCap and are refused. The rule's threshold would be 32 768, and no measured size from there on is built on the
+// device: no size qualifies, so AUTO stays on the host everywhere (0xFFFFFFFF = never); the device build runs in mode DEVICE only.
+constexpr uint32_t kBlasDeviceMinTris = 0xFFFFFFFFu;
+constexpr uint32_t kBlasStackCap = 26;       // build_blas's limit: leaves the top-level tree at least 18 of the kTlStackCap entries
+static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshUpdateInfo) == 64, "layouts the harness relies on");
+
+// Blas::rebuild (blas.rs:285-310) on the device for the meshes of `set` (pending updatable meshes whose state asked for
+// SR_OP_FAST_BUILD): srk_blas_build writes each tree into the mesh's ranges of the concatenated arrays, which stay resident.
+// The triangle-side ranges stay where they are (only the leaf order inside them changes). A device-built tree has another node
+// count than the tree it replaces, and references are indices into d_blas_nodes, so at its first device build a mesh takes a node
+// range of the builder's proven bound (fewer inner nodes than triangles) behind everything in use, and keeps it for later builds;
+// the buffer grows by a device-to-device copy. *reason != SR_MESH_TREE_ON_DEVICE: a tree was refused and the host builds them all.
+int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32_t* reason) {
+    int rc;
+    uint64_t end = s->blas_node_end;
+    for (uint32_t m : set) if (s->mesh_state[m].node_cap == 0) end += (uint64_t)s->mesh_state[m].tree.n_tris + 64u;
+    if (end >= (1ull << 31)) return fail(SR_ERR_UNSUPPORTED, "the mesh trees together exceed 2^31 nodes");
+    HIP_TRY(hipDeviceSynchronize());          // frames in flight read the arrays that are rewritten (and may move) from here on
+    if ((rc = s->d_blas_nodes.grow_keep((size_t)end * srl::kNodeBytes, (size_t)s->blas_node_end * srl::kNodeBytes)) != SR_OK ||
+        (rc = s->d_blas_node_box.reserve((size_t)end * 24)) != SR_OK || (rc = s->d_blas_build_out.reserve(64)) != SR_OK) return rc;
+    const size_t nm = s->meshes.size();
+    srd::TlMeshRow* rows_dev = (s->tl_mesh_rows_current && s->d_tl_mesh_rows.bytes >= nm * sizeof(srd::TlMeshRow)) ? (srd::TlMeshRow*)s->d_tl_mesh_rows.p : nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t m : set) {
+        SrScene::MeshState& ms = s->mesh_state[m];
+        SrScene::HostBlas& b = ms.tree;
+        const uint32_t n = b.n_tris;
+        if (ms.node_cap == 0) { ms.node_base = (uint32_t)s->blas_node_end; ms.node_cap = n + 64u; s->blas_node_end += ms.node_cap; }
+        if ((rc = s->d_scratch.reserve(srk_lbvh_scratch_bytes(n, ms.node_cap))) != SR_OK) return rc;
+        LbvhArgs a{};
+        a.n_tris = n;
+        a.vertices = (const SrVertex*)s->meshes[m].d_vertices; a.indices = (const uint32_t*)s->meshes[m].d_indices; a.n_vertices = s->meshes[m].n_vertices;
+        a.mesh_slot = m; a.textured = b.shade_tex.empty() ? 0u : 1u;
+        a.nodes = (float4*)s->d_blas_nodes.p; a.node_base = ms.node_base; a.node_cap = ms.node_cap; a.node_box = (float*)s->d_blas_node_box.p;
+        a.tris = (float4*)s->d_tris.p; a.shade = (float4*)s->d_shade.p; a.shade_tex = s->any_textured_tl ? (float4*)s->d_shade_tex.p : nullptr;
+        a.slot_of_gid = (uint32_t*)s->d_slot_of_gid.p; a.tri_base = ms.tri_base;
+        a.rows = rows_dev; a.out = (uint32_t*)s->d_blas_build_out.p;
+        a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
+        a.stack_floor = std::min(depth_for(n), kBlasStackCap); a.stack_cap = kBlasStackCap;
+        a.ploc = s->fast_build_ploc;
+        LbvhResult r;
+        const int e = srk_blas_build(a, &r, nullptr);
+        if (e > 0) return fail(SR_ERR_HIP, std::string("device mesh-tree build failed: ") + hipGetErrorString((hipError_t)e));
+        if (e < 0 || r.max_stack > kBlasStackCap) {           // deeper than the host's limit for mesh trees: remembered, the attempt is not repeated
+            ms.device_refused = s->fast_build_ploc;
+            *reason = SR_MESH_TREE_HOST_STACK_BUDGET;
+            return SR_OK;
+        }
+        uint32_t out[10];
+        HIP_TRY(hipMemcpy(out, s->d_blas_build_out.p, sizeof(out), hipMemcpyDeviceToHost));
+        s->tl_blas_nodes = s->tl_blas_nodes - b.n_nodes + out[8];
+        memcpy(b.lo, out, 12); memcpy(b.hi, out + 3, 12); memcpy(&b.max_abs_vertex, out + 6, 4); memcpy(&b.max_edge_sum, out + 7, 4);
+        b.n_nodes = out[8]; b.max_stack = out[9]; b.max_depth = r.max_depth;
+        b.level_ranges = r.level_ranges;
+        b.host_stale = true; b.device_built = true;
+        s->mt_info.n_nodes = b.n_nodes; s->mt_info.max_stack = b.max_stack;
+    }
+    if (s->timing) s->mt_info.device_build_ms = ms_between(t0, std::chrono::steady_clock::now());   // every build ends with a wait for its stream
+    for (uint32_t m : set) {                  // all were taken: they count as built (mark_mesh_trees: SR_OP_FAST_BUILD)
+        SrScene::MeshState& ms = s->mesh_state[m];
+        ms.refit_pending = false; ms.rebuilt_now = true;
+        s->mu_info.blas_rebuilt++; s->mt_info.built_on_device++;
+    }
+    s->refit_set.clear();                     // node lists of these meshes changed
+    return SR_OK;
+}
+
+// Blas::update / Blas::rebuild (blas.rs:285-310) for the meshes updated since the last sr_scene_set_instances whose build type
+// allows it (refit_pending). The op each mesh's own SrAsState picks (or the forced one) decides: SR_OP_UPDATE: the device rewrites
+// its leaf-order records and root box and refits its nodes in place; SR_OP_FAST_BUILD: the device builds its tree anew
+// (build_mesh_trees_device); both kinds may run in one call, and the concatenated arrays stay current. All or nothing remains
+// only towards the HOST: if anything in the call needs it (a slow build, a baked instance in the old or new list, arrays that
+// are not resident, mode HOST or a mesh below the auto threshold, a refused device build) every pending mesh's tree is invalidated
 // and the build that follows rebuilds them on the host, as it does for a Static mesh. A host rebuild re-concatenates and
-// re-uploads every mesh's host copy, so it also takes the meshes an earlier refit left with a stale host copy (and a refit next
-// to a rebuild would be wasted: it is all or nothing per call). Runs before two_level_build, which then sees current root boxes.
-int refit_mesh_trees(SrScene* s, uint32_t forced) {
+// re-uploads every mesh's host copy, so it also takes the meshes an earlier refit or device build left with a stale host copy.
+// Runs before two_level_build, which then sees current root boxes and stack needs.
+int maintain_mesh_trees(SrScene* s, uint32_t forced) {
     const size_t nm = s->meshes.size();
     s->mu_info.blas_refitted = 0;
-    std::vector<uint32_t> set;
-    bool any_stale = false;
+    SrMeshTreeInfo& ti = s->mt_info;
+    ti.built_on_device = ti.built_on_host = 0; ti.reason = SR_MESH_TREE_ON_DEVICE; ti.device_build_ms = 0.0;
+    std::vector<uint32_t> set, builds;        // refits, device builds
+    bool any_stale = false, any_pending = false, slow = false;
     for (size_t m = 0; m < nm; m++) {
         SrScene::MeshState& ms = s->mesh_state[m];
         ms.rebuilt_now = ms.refit_now = false;
         if (s->meshes[m].n_vertices == 0) continue;
-        if (ms.refit_pending) set.push_back((uint32_t)m);
         any_stale = any_stale || ms.tree.host_stale;
+        if (!ms.refit_pending) continue;
+        any_pending = true;
+        const uint32_t op = forced != SR_OP_NONE ? forced : srh::as_state_next_op(ms.state, true);
+        if (op == SR_OP_UPDATE) set.push_back((uint32_t)m);
+        else if (op == SR_OP_FAST_BUILD) builds.push_back((uint32_t)m);     // more than 8 updates since its rebuild
+        else slow = true;
     }
-    if (set.empty() && !any_stale) return SR_OK;
-    // anything that makes the build re-concatenate the mesh trees: the form, meshes added or removed, baked copies behind the mesh
-    // trees now or in the new list
-    bool host = !s->built || !s->two_level || !s->blas_device_current || s->tl_baked;
-    for (size_t i = 0; !host && i < s->fid.instances.size(); i++) host = instance_is_baked(s->fid.instances[i].o2w.m);
-    for (size_t k = 0; !host && k < set.size(); k++) {
-        const uint32_t op = forced != SR_OP_NONE ? forced : srh::as_state_next_op(s->mesh_state[set[k]].state, true);
-        host = op != SR_OP_UPDATE || !s->mesh_state[set[k]].tree.valid;      // more than 8 updates since its rebuild: the host build (there is no device fast build for mesh trees)
+    if (!any_pending && !any_stale) { if (s->static_mesh_updated) ti.reason = SR_MESH_TREE_HOST_STATIC_MESH; return SR_OK; }
+    // anything that makes the build re-concatenate the mesh trees: the form, meshes added or removed, an updated Static mesh, baked
+    // copies behind the mesh trees now or in the new list; then what the pending meshes themselves ask for
+    uint32_t reason = SR_MESH_TREE_ON_DEVICE;
+    if (!s->built || !s->two_level || !s->blas_device_current) reason = s->static_mesh_updated ? SR_MESH_TREE_HOST_STATIC_MESH : SR_MESH_TREE_HOST_NOT_RESIDENT;
+    else if (s->tl_baked) reason = SR_MESH_TREE_HOST_BAKED_INSTANCE;
+    for (size_t i = 0; reason == SR_MESH_TREE_ON_DEVICE && i < s->fid.instances.size(); i++)
+        if (instance_is_baked(s->fid.instances[i].o2w.m)) reason = SR_MESH_TREE_HOST_BAKED_INSTANCE;
+    if (reason == SR_MESH_TREE_ON_DEVICE && slow) reason = SR_MESH_TREE_HOST_SLOW_BUILD;
+    for (size_t k = 0; reason == SR_MESH_TREE_ON_DEVICE && k < builds.size(); k++) {
+        if (s->blas_build_mode == SR_MESH_TREE_BUILD_HOST) reason = SR_MESH_TREE_HOST_MODE;
+        else if (s->blas_build_mode == SR_MESH_TREE_BUILD_AUTO && s->mesh_state[builds[k]].tree.n_tris < kBlasDeviceMinTris) reason = SR_MESH_TREE_HOST_BELOW_THRESHOLD;
+        else if (s->mesh_state[builds[k]].device_refused == s->fast_build_ploc) reason = SR_MESH_TREE_HOST_STACK_BUDGET;     // refused before
     }
-    if (host) {
+    int rc;
+    if (reason == SR_MESH_TREE_ON_DEVICE && !builds.empty() && (rc = build_mesh_trees_device(s, builds, &reason)) != SR_OK) return rc;
+    if (reason != SR_MESH_TREE_ON_DEVICE) {
         for (size_t m = 0; m < nm; m++)
             if (s->mesh_state[m].refit_pending || s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
+        ti.reason = reason;
         return SR_OK;
     }
     if (set.empty()) return SR_OK;
-    int rc;
     if (set != s->refit_set) {                // another set of meshes than last time: its rows and node lists
         std::vector<srd::BlasRefitMesh> rows(set.size());
         std::vector<std::vector<uint32_t>> by_depth;
@@ -1035,12 +1156,19 @@ int refit_mesh_trees(SrScene* s, uint32_t forced) {
             r.tri_base = s->mesh_state[m].tri_base; r.n_tris = b.n_tris; r.n_vertices = s->meshes[m].n_vertices;
             r.first_thread = threads; r.mesh_slot = m; r.textured = b.shade_tex.empty() ? 0u : 1u;
             threads += (b.n_tris + 63u) & ~63u;
-            std::vector<uint32_t> nodes, offsets;       // deepest level first; the topology of the host copy is never stale
+            const uint32_t nb = s->mesh_state[m].node_base;
+            if (b.device_built) {             // the host copy's topology is stale: the levels the device build returned
+                if (by_depth.size() < b.level_ranges.size()) by_depth.resize(b.level_ranges.size());
+                for (size_t d = 0; d < b.level_ranges.size(); d++)
+                    for (uint32_t q = 0; q < b.level_ranges[d].second; q++) by_depth[d].push_back(nb + b.level_ranges[d].first + q);
+                continue;
+            }
+            std::vector<uint32_t> nodes, offsets;       // deepest level first
             srh::tree_levels(b.nodes, nodes, offsets);
             const size_t levels = offsets.size() - 1;
             if (by_depth.size() < levels) by_depth.resize(levels);
             for (size_t l = 0; l < levels; l++)
-                for (uint32_t q = offsets[l]; q < offsets[l + 1]; q++) by_depth[levels - 1 - l].push_back(s->mesh_state[m].node_base + nodes[q]);
+                for (uint32_t q = offsets[l]; q < offsets[l + 1]; q++) by_depth[levels - 1 - l].push_back(nb + nodes[q]);
         }
         std::vector<uint32_t> list;
         s->refit_level_offsets.assign(1, 0u);
@@ -1057,7 +1185,7 @@ int refit_mesh_trees(SrScene* s, uint32_t forced) {
         s->refit_set = set;
         s->refit_threads = threads;
     }
-    if ((rc = s->d_blas_node_box.reserve((size_t)s->tl_blas_nodes * 24)) != SR_OK) return rc;
+    if ((rc = s->d_blas_node_box.reserve((size_t)s->blas_node_end * 24)) != SR_OK) return rc;
     ThreeMarkTimer timer(s);
     timer.mark();
     srd::TlMeshRow* rows_dev = (s->tl_mesh_rows_current && s->d_tl_mesh_rows.bytes >= nm * sizeof(srd::TlMeshRow)) ? (srd::TlMeshRow*)s->d_tl_mesh_rows.p : nullptr;
@@ -1297,7 +1425,7 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     s->mu_info.dirty_meshes = (uint32_t)std::count_if(s->mesh_state.begin(), s->mesh_state.end(), [](const SrScene::MeshState& ms) { return ms.dirty; });
     s->mu_info.reshaded = 0; s->mu_info.blas_rebuilt = 0; s->mu_info.blas_refitted = 0;
     s->mu_info.tables_ms = s->mu_info.flatten_ms = s->mu_info.refit_ms = s->mu_info.blas_build_ms = 0.0;
-    auto applied = [s] { for (auto& ms : s->mesh_state) ms.dirty = false; s->geometry_stale = false; };
+    auto applied = [s] { for (auto& ms : s->mesh_state) ms.dirty = false; s->geometry_stale = false; s->static_mesh_updated = false; };
     s->emissive_table = s->emissive_tris;
     if (s->emissive_table.empty()) { SrEmissiveTriangle z; memset(&z, 0, sizeof(z)); s->emissive_table.push_back(z); }
     // Two-level form (a tree per mesh + a top-level tree over the instances): on request or where the flattened copy would be
@@ -1307,10 +1435,11 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
         const uint32_t forced = s->forced_op;
         s->forced_op = SR_OP_NONE;
         if (!s->two_level) s->built = false;
-        if ((rc = refit_mesh_trees(s, forced)) != SR_OK) { s->built = false; return rc; }      // updatable meshes: Blas::update on the device
+        if ((rc = maintain_mesh_trees(s, forced)) != SR_OK) { s->built = false; return rc; }      // updatable meshes: Blas::update / Blas::rebuild on the device
         rc = two_level_build(s, true);
         if (rc != SR_OK) { s->built = false; return rc; }
         mark_mesh_trees(s, forced);
+        s->mt_info.built_on_host = s->mu_info.blas_rebuilt - s->mt_info.built_on_device;
         if (s->built_once) srh::as_state_mark_built(s->as_state, op);
         s->built_once = true;
         s->last_op = op;
@@ -1412,6 +1541,19 @@ int sr_scene_top_level_info(const SrScene* s, SrTopLevelInfo* out) {
         memset(out, 0, sizeof(*out));
         out->mode = mode; out->auto_threshold = kTlDeviceMinBoxes; out->reason = SR_TL_HOST_NOT_TWO_LEVEL;
     }
+    return SR_OK;
+}
+int sr_scene_set_mesh_tree_build(SrScene* s, uint32_t mode) {
+    if (mode > SR_MESH_TREE_BUILD_DEVICE) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_tree_build: mode must be SR_MESH_TREE_BUILD_AUTO, _HOST or _DEVICE");
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_tree_build: scene is null");
+    s->blas_build_mode = (int)mode;
+    return SR_OK;
+}
+int sr_scene_mesh_tree_info(const SrScene* s, SrMeshTreeInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_tree_info: null argument");
+    *out = s->mt_info;
+    out->mode = (uint32_t)s->blas_build_mode;
+    out->auto_threshold = kBlasDeviceMinTris;
     return SR_OK;
 }
 int sr_scene_read_top_level(const SrScene* s, uint32_t* nodes, uint32_t* tl_inst, void* records, float* boxes) {

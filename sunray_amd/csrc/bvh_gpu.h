@@ -47,6 +47,14 @@ struct LbvhArgs {
     // srk_tl_build only (the primitives are instance boxes; meshes .. slot_of_gid above are unused, n_tris is unused)
     const float* boxes = nullptr; uint32_t n_boxes = 0;  // n_instances x 6 floats, n_boxes of them real (the others are NaN rows)
     uint32_t* tl_inst = nullptr;                         // out: leaf order -> instance index, n_boxes entries
+    // srk_blas_build only (the primitives are ONE mesh's object-space triangles; meshes, instances and n_instances above are unused).
+    // nodes, node_box, tris, shade, shade_tex and slot_of_gid are the concatenated arrays of all meshes: the tree takes the nodes
+    // [node_base, node_base + node_cap) and the leaf-order slots [tri_base, tri_base + n_tris)
+    const SrVertex* vertices = nullptr; const uint32_t* indices = nullptr; uint32_t n_vertices = 0;
+    uint32_t mesh_slot = 0, textured = 0;                // shade_tex is written only for a textured mesh
+    uint32_t node_base = 0, tri_base = 0;
+    srd::TlMeshRow* rows = nullptr;                      // out (may be null): the mesh's row of the top-level record table
+    uint32_t* out = nullptr;                             // out, 10 dwords: root box lo, hi, max_abs_vertex, max_edge_sum (floats), nodes, stack need
 };
 struct LbvhResult {
     uint32_t n_nodes = 0, max_stack = 0, max_depth = 0;
@@ -70,5 +78,9 @@ size_t srk_tl_scratch_bytes(uint32_t n_instances, uint32_t node_cap);
 // srk_blas_refit: the quantised nodes of those meshes, one launch per level (lists of global node indices, deepest level first).
 int srk_blas_records(const srd::BlasRefitMesh* meshes, uint32_t n_meshes, uint32_t n_threads, float4* tris, float4* shade, float4* shade_tex,
                      uint32_t* acc, const uint32_t* acc_init, srd::TlMeshRow* rows, float* out, hipStream_t stream);
+// srk_blas_build: the device fast build of one mesh's tree into its ranges of those arrays (SrAsState asked for SR_OP_FAST_BUILD):
+// records, shade, shade_tex and primitive -> slot entries with the bytes of build_blas, references global as the concatenation
+// makes them, the eight floats as above. Return convention and scratch size of srk_lbvh_build (n_tris, node_cap).
+int srk_blas_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
 int srk_blas_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host,
                    uint32_t n_levels, hipStream_t stream);

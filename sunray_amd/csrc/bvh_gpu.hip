@@ -688,6 +688,101 @@ __global__ void blas_finish_kernel(const BlasRefitMesh* meshes, uint32_t n_meshe
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// FastBuild of ONE mesh's tree of the two-level form on the device (Blas::rebuild, blas.rs:285-310): the builder above over
+// the mesh's object-space triangles, written into the mesh's ranges of the concatenated arrays.
+//   prims      one thread per primitive: the (v0, v1, v2, prim) record straight from the positions (the vertex's bits: no
+//              identity transform, which would turn -0.0 into +0.0), the centroid of its padded box, the bounds of the Morton
+//              grid, and the mesh's root box and padding numbers by blas_records_kernel's expressions and encoding
+//   tree       sort, radix tree or PLOC, collapse: unchanged, with references local to the mesh (nodes from the range's start)
+//   leaves     one thread per sorted primitive: record, shade, shade_tex at tri_base + slot, primitive -> slot (global)
+//   place      one thread per built node: references become global as BlasCat::append (api.cpp) makes them
+//   refit      refit_level_kernel over VertPrims on the global arrays, deepest level first
+//   finish     the eight floats, stack need, root and node count into the mesh's TlMeshRow and the read-back block
+// ---------------------------------------------------------------------------------------------------------------
+__global__ void blas_prims_kernel(const SrVertex* vtx, const uint32_t* idx, uint32_t n_vertices, uint32_t n_tris, float4* W, float4* cent,
+                                  uint32_t* bounds_enc, uint32_t* acc) {
+    const uint32_t prim = blockIdx.x * blockDim.x + threadIdx.x;
+    float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};   // what the tree bounds the primitive by
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};     // build_blas's root box
+    float max_abs = 0.0f, max_edge = 0.0f;
+    if (prim < n_tris) {
+        const float* w[3];
+        for (int j = 0; j < 3; j++) { const uint32_t vi = idx[3 * (size_t)prim + j]; w[j] = vtx[vi < n_vertices ? vi : 0u].position; }
+        W[(size_t)prim * 3 + 0] = make_float4(w[0][0], w[0][1], w[0][2], w[1][0]);
+        W[(size_t)prim * 3 + 1] = make_float4(w[1][1], w[1][2], w[2][0], w[2][1]);
+        W[(size_t)prim * 3 + 2] = make_float4(w[2][2], __uint_as_float(prim), 0.0f, 0.0f);
+        VertPrims{W}.add(prim, blo, bhi);
+        cent[prim] = make_float4(0.5f * blo[0] + 0.5f * bhi[0], 0.5f * blo[1] + 0.5f * bhi[1], 0.5f * blo[2] + 0.5f * bhi[2], 0.0f);
+        for (int a = 0; a < 3; a++) {      // build_blas: the padded triangle box and the two padding numbers
+            const float e1 = w[1][a] - w[0][a], e2 = w[2][a] - w[0][a];
+            max_edge = fmaxf(max_edge, fabsf(e1) + fabsf(e2));
+            for (int j = 0; j < 3; j++) max_abs = fmaxf(max_abs, fabsf(w[j][a]));
+            const float pad = 4e-6f * (fabsf(e1) + fabsf(e2));
+            const float l = fminf(w[0][a], fminf(w[1][a], w[2][a])) - pad;
+            const float h = fmaxf(w[0][a], fmaxf(w[1][a], w[2][a])) + pad;
+            lo[a] = nextafterf(l, -INFINITY); hi[a] = nextafterf(h, INFINITY);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        for (int a = 0; a < 3; a++) {
+            blo[a] = fminf(blo[a], __shfl_xor(blo[a], o)); bhi[a] = fmaxf(bhi[a], __shfl_xor(bhi[a], o));
+            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o));
+        }
+        max_abs = fmaxf(max_abs, __shfl_xor(max_abs, o)); max_edge = fmaxf(max_edge, __shfl_xor(max_edge, o));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        for (int a = 0; a < 3; a++)
+            if (blo[a] <= bhi[a]) { atomicMin(bounds_enc + a, enc_f(blo[a])); atomicMax(bounds_enc + 3 + a, enc_f(bhi[a])); }
+        if (lo[0] <= hi[0]) {
+            for (int a = 0; a < 3; a++) { atomicMin(acc + a, enc_f(lo[a])); atomicMax(acc + 3 + a, enc_f(hi[a])); }
+            atomicMax(acc + 6, enc_f(max_abs)); atomicMax(acc + 7, enc_f(max_edge));
+        }
+    }
+}
+
+__global__ void blas_leaves_kernel(const float4* W, const uint32_t* sorted_gid, const uint32_t* slot_of_sorted, uint32_t n_tris, const SrVertex* vtx,
+                                   const uint32_t* idx, uint32_t n_vertices, uint32_t mesh_slot, uint32_t tri_base, float4* tris, float4* shade,
+                                   float4* shade_tex, uint32_t* slot_of_gid) {
+    const uint32_t s_idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s_idx >= n_tris) return;
+    const uint32_t local = slot_of_sorted[s_idx], prim = sorted_gid[s_idx];
+    if (local >= n_tris || prim >= n_tris) return;      // cannot happen for a tree the collapse finished; never index out of the mesh's range
+    const size_t slot = (size_t)tri_base + local;
+    for (int k = 0; k < 3; k++) tris[slot * 3 + k] = W[(size_t)prim * 3 + k];
+    slot_of_gid[(size_t)tri_base + prim] = tri_base + local;
+    const SrVertex* v[3];
+    for (int j = 0; j < 3; j++) { const uint32_t vi = idx[3 * (size_t)prim + j]; v[j] = vtx + (vi < n_vertices ? vi : 0u); }
+    write_shade(shade + slot * 3, v, 0.0f, __uint_as_float(mesh_slot), 0.0f);      // no instance: it comes from the walk (build_blas)
+    if (shade_tex) write_shade_tex(shade_tex + slot * 6, v);
+}
+
+__global__ void blas_place_kernel(uint32_t* nodes, uint32_t n_nodes, uint32_t node_base, uint32_t tri_base) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_nodes) return;
+    uint32_t* q = nodes + ((size_t)node_base + i) * srl::kNodeDwords + srl::kChildOffset;
+    for (int c = 0; c < srl::kBvhWidth; c++) {
+        const int ref = (int)q[c];
+        if (ref >= 0) q[c] = (uint32_t)ref + node_base;
+        else { const uint32_t lv = ~(uint32_t)ref, cnt = lv & 7u; if (cnt) q[c] = ~((((lv >> 3) + tri_base) << 3) | cnt); }
+    }
+}
+
+// counters: the collapse's ([0] nodes allocated, [1] max stack). out: 8 floats, then node count and stack need as dwords.
+__global__ void blas_build_finish_kernel(const uint32_t* acc, const uint32_t* counters, uint32_t mesh_slot, uint32_t node_base, uint32_t tri_base,
+                                         uint32_t n_tris, TlMeshRow* rows, uint32_t* out) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float f[8];
+    for (int k = 0; k < 8; k++) { f[k] = dec_f(acc[k]); out[k] = __float_as_uint(f[k]); }
+    out[8] = counters[0]; out[9] = counters[1];
+    if (rows) {
+        TlMeshRow* r = rows + mesh_slot;
+        for (int a = 0; a < 3; a++) { r->lo[a] = f[a]; r->hi[a] = f[3 + a]; }
+        r->max_abs_vertex = f[6]; r->max_edge_sum = f[7];
+        r->max_stack = counters[1]; r->blas_root = node_base; r->prim_base = tri_base; r->n_tris = n_tris;
+    }
+}
+
 }  // namespace srd
 
 using namespace srd;
@@ -739,13 +834,19 @@ int srk_blas_refit(uint32_t* nodes, const float4* tris, float* node_box, const u
 
 // Device LBVH build. All outputs are device buffers owned by the caller; `scratch` is reused across builds. Returns 0, a
 // hipError_t (> 0), or -1 when the tree does not fit the limits (caller falls back to the host builder).
-// BOXES: the primitives are the instance boxes of a top-level tree (srk_tl_build) instead of the instances' triangles: all
-// n_instances rows are keyed and sorted, the n_boxes real ones come first and are the tree's primitives.
-template <bool BOXES>
+// KIND kBuildBoxes: the primitives are the instance boxes of a top-level tree (srk_tl_build) instead of the instances' triangles:
+// all n_instances rows are keyed and sorted, the n_boxes real ones come first and are the tree's primitives.
+// KIND kBuildMesh: the primitives are the object-space triangles of one mesh of the two-level form (srk_blas_build); nodes and
+// records go to the mesh's ranges of the concatenated arrays (node_base, tri_base), with global references.
+enum { kBuildTris = 0, kBuildBoxes = 1, kBuildMesh = 2 };
+template <int KIND>
 static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
+    constexpr bool BOXES = KIND == kBuildBoxes, MESH = KIND == kBuildMesh;
     const uint32_t n_keys = BOXES ? a.n_instances : a.n_tris;   // sorted items
     const uint32_t n = BOXES ? a.n_boxes : a.n_tris;             // primitives of the tree
     if (BOXES && (n < 2 || n > n_keys)) return -1;
+    if (MESH && (n < 1 || a.node_cap < 1)) return -1;
+    uint32_t* const tree_nodes = (uint32_t*)a.nodes + (MESH ? (size_t)a.node_base * srl::kNodeDwords : 0);   // the collapse's node 0
     const int B = 256;
     const dim3 gk((n_keys + B - 1) / B), gt((n + B - 1) / B), bt(B);
     const int sort_bits = BOXES ? 64 : 63;                       // the key of an instance without a box has every bit set
@@ -782,21 +883,35 @@ static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
     void* cub_tmp = take(cub_bytes > scan_bytes ? cub_bytes : scan_bytes);
     if (off > a.scratch_bytes) return (int)hipErrorOutOfMemory;
 
-    const uint32_t init[16] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    // [16..23] (srk_blas_build): the encoded +inf x 3, -inf x 3, 0, 0 the mesh's root box and padding numbers start from
+    const uint32_t init[24] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u,
+                               0xFF800000u, 0xFF800000u, 0xFF800000u, 0x007FFFFFu, 0x007FFFFFu, 0x007FFFFFu, 0x80000000u, 0x80000000u};
+    uint32_t* const acc = small + 16;
+    uint32_t* const counters = small + 8;
     if ((e = hipMemcpyAsync(small, init, sizeof(init), hipMemcpyHostToDevice, stream)) != hipSuccess) return (int)e;
     if constexpr (BOXES) {
         tl_bounds_kernel<<<gk, bt, 0, stream>>>(a.boxes, n_keys, small);
         tl_morton_kernel<<<gk, bt, 0, stream>>>(a.boxes, small, n_keys, keys_a, vals_a);
     } else {
-        lbvh_prims_kernel<<<gt, bt, 0, stream>>>(a.meshes, a.instances, a.n_instances, n, W, cent, small);
+        if constexpr (MESH) blas_prims_kernel<<<gt, bt, 0, stream>>>(a.vertices, a.indices, a.n_vertices, n, W, cent, small, acc);
+        else lbvh_prims_kernel<<<gt, bt, 0, stream>>>(a.meshes, a.instances, a.n_instances, n, W, cent, small);
         lbvh_morton_kernel<<<gt, bt, 0, stream>>>(cent, small, n, keys_a, vals_a);
     }
     if ((e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys_a, keys_b, vals_a, vals_b, (int)n_keys, 0, sort_bits, stream)) != hipSuccess) return (int)e;
     // what a stage bounds a primitive by: `prims` by sorted value (triangle id / instance index), `leaf_prims` by leaf position
-    auto prims = [&] { if constexpr (BOXES) return BoxPrims{a.boxes, nullptr}; else return TriPrims{W}; }();
-    auto leaf_prims = [&] { if constexpr (BOXES) return BoxPrims{a.boxes, a.tl_inst}; else return TriPrims{a.tris}; }();
+    auto prims = [&] { if constexpr (BOXES) return BoxPrims{a.boxes, nullptr}; else if constexpr (MESH) return VertPrims{W}; else return TriPrims{W}; }();
+    auto leaf_prims = [&] { if constexpr (BOXES) return BoxPrims{a.boxes, a.tl_inst}; else if constexpr (MESH) return VertPrims{a.tris}; else return TriPrims{a.tris}; }();
     int root_bin = 0;
-    if (!a.ploc) {
+    const bool single = MESH && n == 1;       // one triangle: no binary tree; the root is one node with one leaf child
+    if (single) {
+        uint32_t node[srl::kNodeDwords];
+        for (int k = 0; k < srl::kNodeDwords; k++) node[k] = k >= srl::kChildOffset ? 0xFFFFFFFFu : 0u;
+        node[srl::kChildOffset] = ~((0u << 3) | 1u);
+        if ((e = hipMemcpyAsync(tree_nodes, node, sizeof(node), hipMemcpyHostToDevice, stream)) != hipSuccess) return (int)e;
+        if ((e = hipMemsetAsync(slot_of_sorted, 0, 4, stream)) != hipSuccess) return (int)e;
+        out->level_ranges.assign(1, std::make_pair(0u, 1u));
+        out->n_nodes = 1; out->max_stack = 0;
+    } else if (!a.ploc) {
         if ((e = hipMemsetAsync(flags, 0, (size_t)n * 4, stream)) != hipSuccess) return (int)e;
         lbvh_hierarchy_kernel<<<gt, bt, 0, stream>>>(keys_b, (int)n, children, parent_inner, parent_leaf, range);
         lbvh_fit_kernel<<<gt, bt, 0, stream>>>(prims, vals_b, (int)n, children, parent_inner, parent_leaf, range, bin_box, bin_height, bin_size, flags);
@@ -827,23 +942,25 @@ static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
         if (root_bin < 0) return -1;
     }
-    // root of the 4-wide tree = the binary root; its budget is the binary height, at least the regular stack size
-    uint32_t root_height = 0;
-    if ((e = hipMemcpyAsync(&root_height, bin_height + root_bin, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
-    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
-    if (root_height > a.stack_cap) return -1;
-    const uint32_t budget = root_height > a.stack_floor ? root_height : a.stack_floor;
-    const uint32_t zero = 0;
-    (void)hipMemcpyAsync(bin_of_node, &root_bin, 4, hipMemcpyHostToDevice, stream);
-    (void)hipMemcpyAsync(budget_of_node, &budget, 4, hipMemcpyHostToDevice, stream);
-    (void)hipMemcpyAsync(prefix_of_node, &zero, 4, hipMemcpyHostToDevice, stream);
-    (void)hipMemcpyAsync(first_of_node, &zero, 4, hipMemcpyHostToDevice, stream);
-    out->level_ranges.clear();
-    uint32_t level_first = 0, level_count = 1;
-    uint32_t* counters = small + 8;
+    uint32_t level_first = 0, level_count = 0;
+    if (!single) {
+        // root of the 4-wide tree = the binary root; its budget is the binary height, at least the regular stack size
+        uint32_t root_height = 0;
+        if ((e = hipMemcpyAsync(&root_height, bin_height + root_bin, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
+        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
+        if (root_height > a.stack_cap) return -1;
+        const uint32_t budget = root_height > a.stack_floor ? root_height : a.stack_floor;
+        const uint32_t zero = 0;
+        (void)hipMemcpyAsync(bin_of_node, &root_bin, 4, hipMemcpyHostToDevice, stream);
+        (void)hipMemcpyAsync(budget_of_node, &budget, 4, hipMemcpyHostToDevice, stream);
+        (void)hipMemcpyAsync(prefix_of_node, &zero, 4, hipMemcpyHostToDevice, stream);
+        (void)hipMemcpyAsync(first_of_node, &zero, 4, hipMemcpyHostToDevice, stream);
+        out->level_ranges.clear();
+        level_count = 1;
+    }
     while (level_count) {
         out->level_ranges.emplace_back(level_first, level_count);
-        lbvh_collapse_kernel<<<dim3((level_count + 63) / 64), dim3(64), 0, stream>>>((uint32_t*)a.nodes, level_first, level_count, a.node_cap, bin_of_node,
+        lbvh_collapse_kernel<<<dim3((level_count + 63) / 64), dim3(64), 0, stream>>>(tree_nodes, level_first, level_count, a.node_cap, bin_of_node,
                                                                                        budget_of_node, prefix_of_node, first_of_node, children, bin_size, bin_box,
                                                                                        bin_height, slot_of_sorted, counters);
         uint32_t c[3];
@@ -857,18 +974,25 @@ static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
         if (out->level_ranges.size() > 128) return -1;
     }
     out->max_depth = (uint32_t)out->level_ranges.size();
+    const uint32_t node_base = MESH ? a.node_base : 0u;       // the levels' nodes in the array the refit walks
     if constexpr (BOXES) tl_leaves_kernel<<<gt, bt, 0, stream>>>(vals_b, slot_of_sorted, n, a.tl_inst);
-    else lbvh_leaves_kernel<<<gt, bt, 0, stream>>>(W, cent, vals_b, slot_of_sorted, n, a.meshes, a.instances, a.tris, a.shade, a.shade_tex, a.slot_of_gid);
+    else if constexpr (MESH) {
+        blas_leaves_kernel<<<gt, bt, 0, stream>>>(W, vals_b, slot_of_sorted, n, a.vertices, a.indices, a.n_vertices, a.mesh_slot, a.tri_base, a.tris, a.shade,
+                                                  a.textured ? a.shade_tex : nullptr, a.slot_of_gid);
+        blas_place_kernel<<<dim3((out->n_nodes + 255) / 256), bt, 0, stream>>>((uint32_t*)a.nodes, out->n_nodes, a.node_base, a.tri_base);
+    } else lbvh_leaves_kernel<<<gt, bt, 0, stream>>>(W, cent, vals_b, slot_of_sorted, n, a.meshes, a.instances, a.tris, a.shade, a.shade_tex, a.slot_of_gid);
     for (size_t l = out->level_ranges.size(); l-- > 0;)
         refit_level_kernel<<<dim3((out->level_ranges[l].second + 63) / 64), dim3(64), 0, stream>>>((uint32_t*)a.nodes, leaf_prims, a.node_box, nullptr,
-                                                                                                     out->level_ranges[l].first, out->level_ranges[l].second);
+                                                                                                     node_base + out->level_ranges[l].first, out->level_ranges[l].second);
+    if constexpr (MESH) blas_build_finish_kernel<<<dim3(1), dim3(64), 0, stream>>>(acc, counters, a.mesh_slot, a.node_base, a.tri_base, n, a.rows, a.out);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
     return 0;
 }
 
-int srk_lbvh_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<false>(a, out, stream); }
-int srk_tl_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<true>(a, out, stream); }
+int srk_lbvh_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<kBuildTris>(a, out, stream); }
+int srk_tl_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<kBuildBoxes>(a, out, stream); }
+int srk_blas_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<kBuildMesh>(a, out, stream); }
 
 int srk_tl_records(const FlatInstance* instances, const TlMeshRow* meshes, uint32_t n_instances, double max_condition, DevTlInstance* records,
                    float* boxes, uint32_t* result, hipStream_t stream) {

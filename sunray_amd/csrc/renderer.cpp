@@ -511,6 +511,17 @@ int sr_renderer_set_mesh_build_type(SrRenderer* r, uint64_t key, uint32_t build_
     return SR_OK;
 }
 
+// Where updatable meshes' trees are built (SR_MESH_TREE_BUILD_*), on every replica.
+int sr_renderer_set_mesh_tree_build(SrRenderer* r, uint32_t mode) {
+    if (mode > SR_MESH_TREE_BUILD_DEVICE) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_tree_build: mode must be SR_MESH_TREE_BUILD_AUTO, _HOST or _DEVICE");
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_tree_build: renderer is null");
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_set_mesh_tree_build(sc, mode);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+
 // Access for harnesses: the scene (counters, stats), the device output image and the frame counter.
 int sr_renderer_get(SrRenderer* r, SrScene** scene, const uint32_t** output_rgba8_device, const float** raw_color_device, uint32_t* relative_frame_count) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_get: renderer is null");

@@ -219,6 +219,18 @@ class Scene:
         check(lib().sr_scene_set_mesh_build_type(self._h, C.c_uint64(key), C.c_uint32(build_type)))
         return self
 
+    def set_mesh_tree_build(self, mode):
+        """Where an updatable mesh's tree is built when its state asks for the fast build: "auto" | "host" | "device"
+        (sr_scene_set_mesh_tree_build)."""
+        check(lib().sr_scene_set_mesh_tree_build(self._h, C.c_uint32({"auto": 0, "host": 1, "device": 2}[mode])))
+        return self
+
+    def mesh_tree_info(self):
+        """-> abi.SrMeshTreeInfo: the mesh-tree builds of the last set_instances (device / host counts, reason, milliseconds)."""
+        info = abi.SrMeshTreeInfo()
+        check(lib().sr_scene_mesh_tree_info(self._h, C.byref(info)))
+        return info
+
     def mesh_as_state(self, key):
         """-> (build type, SrAsState, last op) of one mesh's tree."""
         bt, st, op = C.c_uint32(), abi.SrAsState(), C.c_uint32()
@@ -684,6 +696,14 @@ class Renderer:
     def set_mesh_build_type(self, key, build_type):
         """abi.BUILD_* of a loaded mesh's tree on every device slot (sr_renderer_set_mesh_build_type)."""
         check(lib().sr_renderer_set_mesh_build_type(self._h, C.c_uint64(key), C.c_uint32(build_type)))
+
+    def set_mesh_tree_build(self, mode):
+        """Scene.set_mesh_tree_build on every device slot (sr_renderer_set_mesh_tree_build)."""
+        check(lib().sr_renderer_set_mesh_tree_build(self._h, C.c_uint32({"auto": 0, "host": 1, "device": 2}[mode])))
+
+    def mesh_tree_info(self, slot=0):
+        """Scene.mesh_tree_info of one device slot's scene."""
+        return self.replica_scene(slot).mesh_tree_info()
 
     def set_config(self, config):
         check(lib().sr_renderer_set_config(self._h, C.byref(config)))
