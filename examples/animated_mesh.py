@@ -5,7 +5,10 @@ heuristic picks; it is never torn down and rebuilt on the host. The sphere is de
 BuildType of a BLAS that is built with ALLOW_UPDATE): where the scene stands in the two-level form (SR_INSTANCING=two_level, or a
 scene large enough for the automatic choice) its own tree is then refitted on the device as well. Writes the last frame as a PNG.
 
-    python examples/animated_mesh.py [out.png] [--frames 24] [--size 640x480]
+    python examples/animated_mesh.py [out.png] [--frames 24] [--size 640x480] [--height-bound rebalance]
+
+--height-bound rebalance: a device fast build whose tree comes out taller than the traversal stack allows is rebalanced on the
+device instead of going to the host builder (Renderer.set_tree_height_bound; the default, refuse, is the library's).
 
 Needs a GPU: the product path has no CPU fallback.
 """
@@ -23,12 +26,14 @@ def main():
     ap.add_argument("out", nargs="?", default="animated.png")
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--size", default="640x480")
+    ap.add_argument("--height-bound", choices=["refuse", "rebalance"], default="refuse")
     args = ap.parse_args()
     from sunray_amd import abi, runtime as rt, scenes
     w, h = (int(v) for v in args.size.split("x"))
     desc = scenes.cornell_box()
     sphere = next(m for m in desc.meshes if m.key == 7)
     r = rt.Renderer((w, h))
+    r.set_tree_height_bound(args.height_bound)
     for m in desc.meshes:
         r.load_mesh(m.key, m.vertices, m.indices, m.material)
     r.set_mesh_build_type(sphere.key, abi.BUILD_RAPIDLY_CHANGING)

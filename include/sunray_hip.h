@@ -385,7 +385,7 @@ int sr_scene_set_top_level_build(SrScene* scene, uint32_t mode);
 #define SR_TL_HOST_MODE 1u             /* SR_TL_BUILD_HOST */
 #define SR_TL_HOST_BELOW_THRESHOLD 2u  /* auto mode, fewer instance boxes than auto_threshold */
 #define SR_TL_HOST_BAKED_INSTANCE 3u   /* an instance of the list needs a baked copy of its mesh */
-#define SR_TL_HOST_STACK_BUDGET 4u     /* the device tree would need more traversal-stack entries than the mesh trees leave */
+#define SR_TL_HOST_STACK_BUDGET 4u     /* the device tree would need more traversal-stack entries than the mesh trees leave (SR_HEIGHT_BOUND_REBALANCE below bounds it instead) */
 #define SR_TL_HOST_NOT_TWO_LEVEL 5u    /* nothing stood in the two-level form: first build, form switch, meshes added or removed since */
 #define SR_TL_HOST_TOO_FEW 6u          /* fewer than two instance boxes */
 #define SR_TL_HOST_QUALITY_BUILD 7u    /* the settle rebuild of sr_scene_end_frame */
@@ -484,7 +484,8 @@ int sr_scene_mesh_as_state(const SrScene* scene, uint64_t key, uint32_t* build_t
  * mesh's records. SR_MESH_TREE_BUILD_AUTO (default): the device from SrMeshTreeInfo.auto_threshold triangles per mesh on;
  * as measured no size qualifies and the threshold is 0xFFFFFFFF, never: auto is the host build. A device
  * tree deeper than 26 stack entries is refused (measured under the default topology: spheres of 65 536 triangles and more), so in
- * mode DEVICE too the fast build of a large mesh is the host's, with its cost. The first build, the settle rebuild, Static meshes and whatever sr_scene_set_mesh_build_type lists go to
+ * mode DEVICE too the fast build of a large mesh is the host's, with its cost, unless the height bound is switched on
+ * (SR_HEIGHT_BOUND_REBALANCE below: the device then makes such a tree fit instead of refusing it). The first build, the settle rebuild, Static meshes and whatever sr_scene_set_mesh_build_type lists go to
  * the host in every mode. Queries give the same bits either way. SR_BLAS_BUILD = host | device | auto in the environment sets the
  * initial mode (anything else: auto). A mode above SR_MESH_TREE_BUILD_DEVICE: SR_ERR_INVALID_ARG. */
 #define SR_MESH_TREE_BUILD_AUTO 0u
@@ -512,6 +513,30 @@ typedef struct SrMeshTreeInfo {
     double device_build_ms;    /* the device builds of that call, launch to completion (only while sr_scene_enable_timing is on) */
 } SrMeshTreeInfo;              /* 40 bytes */
 int sr_scene_mesh_tree_info(const SrScene* scene, SrMeshTreeInfo* out);
+/* What a device fast build does with a binary tree that is taller than its stack cap (26 entries for a mesh tree, what the mesh
+ * trees leave of 47 for the top level, 47 for the one-level form). SR_HEIGHT_BOUND_REFUSE (default): the build is refused and the
+ * host builds (SR_MESH_TREE_HOST_STACK_BUDGET, SR_TL_HOST_STACK_BUDGET, the host SAH build of the one-level form).
+ * SR_HEIGHT_BOUND_REBALANCE: between the topology and the 4-wide collapse the device rebuilds the deepest, smallest offending
+ * subtrees as median-split trees over their own leaves, so that the tree fits; the rest of the topology is kept, a tree that fits
+ * costs nothing extra, and queries give the same bits either way. A build is then refused only where no tree over the primitives
+ * fits the cap. mesh_tree_cap: 0 = the library's 26, or 1..26: the cap device builds of mesh trees are held to (the host builder
+ * keeps 26); under REBALANCE SR_MESH_TREE_BUILD_AUTO uses a threshold of its own (SrMeshTreeInfo.auto_threshold reports the one in
+ * force). The call forgets every remembered refusal. SR_FAST_BUILD_HEIGHT = refuse | rebalance in the environment sets the initial
+ * mode (anything else: refuse). SR_ERR_INVALID_ARG: a mode above 1, a cap above 26, a non-zero cap under REFUSE. */
+#define SR_HEIGHT_BOUND_REFUSE 0u
+#define SR_HEIGHT_BOUND_REBALANCE 1u
+int sr_scene_set_tree_height_bound(SrScene* scene, uint32_t mode, uint32_t mesh_tree_cap);
+#define SR_TREE_KIND_ONE_LEVEL 0u
+#define SR_TREE_KIND_TOP_LEVEL 1u
+#define SR_TREE_KIND_MESH 2u
+typedef struct SrTreeHeightInfo {      /* the last device fast build of that kind */
+    uint32_t mode, mesh_tree_cap;      /* in force */
+    uint32_t on_device;                /* 1: it produced the tree in use; 0: none yet, or the host took over */
+    uint32_t cap;                      /* stack_cap it was held to */
+    uint32_t height_before, height_after;   /* binary walk height of the topology / of what was collapsed */
+    uint32_t subtrees_rebuilt, prims_rebuilt; /* 0, 0 when the tree fitted */
+} SrTreeHeightInfo;                    /* 32 bytes */
+int sr_scene_tree_height_info(const SrScene* scene, uint32_t kind, SrTreeHeightInfo* out);
 /* Harness read-back of one mesh's part of the concatenated device arrays of a scene built in the two-level form (the counterpart
  * of sr_scene_read_top_level): n_nodes x 16 dwords with references local to the mesh, then per leaf-order slot 12 floats
  * (v0, v1, v2, primitive, 0, 0), 12 floats of `shade`, 24 floats of `shade_tex` (zeros where the scene has no textured
@@ -748,6 +773,8 @@ int sr_renderer_update_mesh(SrRenderer* renderer, uint64_t key, const SrVertex* 
 int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t build_type);
 /* sr_scene_set_mesh_tree_build on every device slot's scene. */
 int sr_renderer_set_mesh_tree_build(SrRenderer* renderer, uint32_t mode);
+/* sr_scene_set_tree_height_bound on every device slot's scene. */
+int sr_renderer_set_tree_height_bound(SrRenderer* renderer, uint32_t mode, uint32_t mesh_tree_cap);
 
 /* Harness access: inner scene (counters, stats), device pointers of the RGBA8 output and the fp32 radiance OF THE LAST
  * SUBMITTED FRAME (valid after sr_renderer_wait_frame of that frame), and relative_frame_count. Any out pointer may be NULL.

@@ -13,7 +13,11 @@ Cases: one deforming sphere of 1 k, 4 k, 21 k, 65 k, 250 k and 1 M triangles (fo
 of 1 k triangles each, all at their ninth update. Median (min-max) of 20 calls after 3 warm-ups, every step in a fresh child
 process under its own time limit; stops at the first step that fails.
 
-  python scripts/gpu_mesh_tree_build.py [--out profiles/mesh_tree_build.json] [--label NAME] [--only CASE]
+  python scripts/gpu_mesh_tree_build.py [--out profiles/mesh_tree_build.json] [--label NAME] [--only CASE] [--leg rebalance]
+
+--leg rebalance (-> profiles/mesh_tree_rebalance.json): the device steps run under SR_HEIGHT_BOUND_REBALANCE (MODE = rebalance:
+a tree taller than 26 entries is made to fit on the device instead of going to the host) and record height before / after and what
+was rebuilt; the threshold derived is the one SR_MESH_TREE_BUILD_AUTO uses under that switch (kBlasDeviceMinTrisBounded).
 
 A library without sr_scene_set_mesh_tree_build (SUNRAY_HIP_LIB pointing at a build of an older commit) runs the host steps only;
 --label keeps its figures apart (e.g. --label parent) in the same output file. With the labels `this` and `parent` both present
@@ -40,6 +44,11 @@ def has_tree_build():
     return hasattr(lib(), "sr_scene_set_mesh_tree_build")
 
 
+def has_height_bound():
+    from sunray_amd._lib import lib
+    return hasattr(lib(), "sr_scene_set_tree_height_bound")
+
+
 def tree_info(sc):
     import ctypes as C
     from sunray_amd import abi
@@ -56,7 +65,9 @@ def scene_for(case, mode):
     for k in keys:
         sc.set_mesh_build_type(k, abi.BUILD_RAPIDLY_CHANGING)
     if has_tree_build():
-        sc.set_mesh_tree_build(mode)
+        sc.set_mesh_tree_build("device" if mode == "rebalance" else mode)
+        if mode == "rebalance":
+            sc.set_tree_height_bound("rebalance")
     else:
         assert mode == "host"
     return desc, keys, sc
@@ -82,8 +93,8 @@ def step_case(case, mode):
             dev_ms = 0.0
             if has_tree_build():
                 ti = tree_info(sc)
-                refused = mode == "device" and ti.reason == abi.MESH_TREE_HOST_STACK_BUDGET      # deeper than a mesh tree may be: the host took over
-                assert (ti.built_on_device, ti.built_on_host) == ((len(keys), 0) if mode == "device" and not refused else (0, len(keys))), (ti.built_on_device, ti.built_on_host, ti.reason)
+                refused = mode != "host" and ti.reason == abi.MESH_TREE_HOST_STACK_BUDGET      # deeper than a mesh tree may be: the host took over
+                assert (ti.built_on_device, ti.built_on_host) == ((len(keys), 0) if mode != "host" and not refused else (0, len(keys))), (ti.built_on_device, ti.built_on_host, ti.reason)
                 dev_ms = ti.device_build_ms
             if k < WARMUP:
                 continue
@@ -94,18 +105,22 @@ def step_case(case, mode):
     out = {"set_instances_ms": base.stats(wall)}
     out.update({n: base.stats([r[j] for r in rows]) for j, n in enumerate(("host_tree_build_ms", "device_tree_build_ms", "top_level_ms"))})
     out["mesh_triangles"], out["meshes"], out["calls"] = len(m.indices) // 3, len(keys), REPS
-    if has_tree_build() and mode == "device":
+    if has_tree_build() and mode != "host":
         ti = tree_info(sc)
         out["built_on_device"], out["host_reason"] = int(ti.built_on_device), int(ti.reason)
         if ti.built_on_device:
             out["device_tree_nodes"], out["device_tree_stack"] = int(ti.n_nodes), int(ti.max_stack)
+        if mode == "rebalance":           # of the last mesh built
+            hi = sc.tree_height_info(abi.TREE_KIND_MESH)
+            out.update(height_before=int(hi.height_before), height_after=int(hi.height_after), subtrees_rebuilt=int(hi.subtrees_rebuilt),
+                       prims_rebuilt=int(hi.prims_rebuilt), cap=int(hi.cap))
     return out
 
 
-def step_quality(case):
+def step_quality(case, mode="device"):
     from sunray_amd import abi, runtime as rt, scenes
     from sunray_amd.runtime import _instance_arrays
-    desc, keys, sc = scene_for(case, "device")
+    desc, keys, sc = scene_for(case, mode)
     m = desc.meshes[0]
     arrays = _instance_arrays(desc.instances)
     W, H = 1920, 1080
@@ -146,9 +161,10 @@ def run_step(args, limit):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-def derive_threshold(doc):
+def derive_threshold(doc, device="device"):
     """-> (threshold or None, text): the rule kTlDeviceMinBoxes was set by, over the single-mesh cases in ascending size."""
     this, parent = doc.get("this", {}), doc.get("parent", {})
+    this = {c: dict(v, device=v[device]) if device in v else {k: x for k, x in v.items() if k != "device"} for c, v in this.items() if isinstance(v, dict)}
     spread = lambda s: s["max"] - s["min"]      # noqa: E731
     for case in ORDER[:-1]:
         try:
@@ -170,9 +186,10 @@ def derive_threshold(doc):
 def main():
     argv = sys.argv[1:]
     if argv[:1] == ["--step"]:
-        print(json.dumps(step_quality(argv[2]) if argv[1] == "quality" else step_case(argv[1], argv[2])))
+        print(json.dumps(step_quality(*argv[2:4]) if argv[1] == "quality" else step_case(argv[1], argv[2])))
         return
-    out_path = argv[argv.index("--out") + 1] if "--out" in argv else os.path.join(ROOT, "profiles", "mesh_tree_build.json")
+    device = "rebalance" if "--leg" in argv and argv[argv.index("--leg") + 1] == "rebalance" else "device"
+    out_path = argv[argv.index("--out") + 1] if "--out" in argv else os.path.join(ROOT, "profiles", "mesh_tree_rebalance.json" if device == "rebalance" else "mesh_tree_build.json")
     label = argv[argv.index("--label") + 1] if "--label" in argv else "this"
     doc = json.load(open(out_path)) if os.path.exists(out_path) else {}
     doc["workload"] = ("two-level form, sr_scene_set_instances after sr_scene_update_mesh + a forced SR_OP_FAST_BUILD of one deforming sphere (four instances) "
@@ -180,24 +197,25 @@ def main():
     res = doc.setdefault(label, {})
 
     def save():                                                    # after every step: a later failure keeps what was measured
-        doc["auto_threshold"], doc["auto_threshold_rule"] = derive_threshold(doc)
+        doc["auto_threshold"], doc["auto_threshold_rule"] = derive_threshold(doc, device)
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         with open(out_path, "w") as f:
             json.dump(doc, f, indent=1, sort_keys=True)
             f.write("\n")
     steps = []
+    on_device = has_tree_build() and (device == "device" or has_height_bound())      # an older library runs the host steps only
     for case in ORDER:
-        steps += [[case, "host"]] + ([[case, "device"]] if has_tree_build() else [])
-    if has_tree_build():
+        steps += [[case, "host"]] + ([[case, device]] if on_device else [])
+    if on_device:
         steps.append(["quality"])
     if "--only" in argv:
         steps = [x for x in steps if x[0] == argv[argv.index("--only") + 1]]
     for args in steps:
         if args == ["quality"]:         # on the 250 k sphere, or the largest measured sphere whose device tree fits the stack budget
-            taken = [c for c in ORDER[:-1] if res.get(c, {}).get("device", {}).get("built_on_device")]
+            taken = [c for c in ORDER[:-1] if res.get(c, {}).get(device, {}).get("built_on_device")]
             if not taken:
                 continue
-            r = run_step(["quality", "250k" if "250k" in taken else taken[-1]], 300)
+            r = run_step(["quality", "250k" if "250k" in taken else taken[-1], device], 300)
         else:
             r = run_step(args, 300)
         node = res

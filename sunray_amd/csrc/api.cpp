@@ -233,6 +233,8 @@ struct SrScene {
     uint64_t schedule_clock = 0;
     int tile_scheduling = 1;                // SR_TILE_SCHEDULING=0 in the environment disables it (A/B)
     int fast_build_ploc = 16;               // device fast build: PLOC with this search radius (default), 0 = radix tree (SR_FAST_BUILD=lbvh | ploc<r>)
+    uint32_t height_bound = SR_HEIGHT_BOUND_REFUSE, mesh_tree_cap = 0;   // sr_scene_set_tree_height_bound / SR_FAST_BUILD_HEIGHT in the environment
+    SrTreeHeightInfo height_info[3]{};      // the last device fast build of each SR_TREE_KIND_*
     uint32_t forced_op = SR_OP_NONE;        // sr_scene_force_next_op (test / bench hook)
     bool last_build_on_device = false;
     std::vector<uint32_t> level_offsets;
@@ -369,6 +371,7 @@ int sr_scene_create(int device, SrScene** out) {
     if (const char* ev = getenv("SR_INSTANCING")) s->instancing = !strcmp(ev, "two_level") ? SR_INSTANCING_TWO_LEVEL : (!strcmp(ev, "flat") ? SR_INSTANCING_FLAT : SR_INSTANCING_AUTO);
     if (const char* ev = getenv("SR_TL_BUILD")) s->tl_build_mode = !strcmp(ev, "host") ? SR_TL_BUILD_HOST : (!strcmp(ev, "device") ? SR_TL_BUILD_DEVICE : SR_TL_BUILD_AUTO);
     if (const char* ev = getenv("SR_BLAS_BUILD")) s->blas_build_mode = !strcmp(ev, "host") ? SR_MESH_TREE_BUILD_HOST : (!strcmp(ev, "device") ? SR_MESH_TREE_BUILD_DEVICE : SR_MESH_TREE_BUILD_AUTO);
+    if (const char* ev = getenv("SR_FAST_BUILD_HEIGHT")) s->height_bound = !strcmp(ev, "rebalance") ? SR_HEIGHT_BOUND_REBALANCE : SR_HEIGHT_BOUND_REFUSE;
     if (const char* ev = getenv("SR_FAST_BUILD")) s->fast_build_ploc = !strcmp(ev, "lbvh") ? 0 : (!strncmp(ev, "ploc", 4) && atoi(ev + 4) > 0 ? atoi(ev + 4) : 16);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cus = prop.multiProcessorCount;
@@ -765,6 +768,17 @@ void publish(SrScene* s, const BuiltStructure& b) {
     s->built = true;
     s->two_level = b.two_level;
     s->last_build_on_device = b.on_device;
+    // the tree in use is of one form; a host build leaves no device-built tree of its kind in use
+    s->height_info[b.two_level ? SR_TREE_KIND_ONE_LEVEL : SR_TREE_KIND_TOP_LEVEL].on_device = 0u;
+    if (!b.on_device) s->height_info[b.two_level ? SR_TREE_KIND_TOP_LEVEL : SR_TREE_KIND_ONE_LEVEL].on_device = 0u;
+}
+
+// What sr_scene_tree_height_info reports of one device fast build (mode and cap in force are filled in by the query).
+void note_tree_height(SrScene* s, uint32_t kind, uint32_t cap, const LbvhResult& r, bool taken) {
+    SrTreeHeightInfo& h = s->height_info[kind];
+    h.on_device = taken ? 1u : 0u; h.cap = cap;
+    h.height_before = r.height_before; h.height_after = r.height_after;
+    h.subtrees_rebuilt = r.subtrees_rebuilt; h.prims_rebuilt = r.prims_rebuilt;
 }
 
 // ---- two-level form -------------------------------------------------------------------------------------------------
@@ -989,10 +1003,12 @@ int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0,
     a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
     a.stack_floor = min_depth_for(nb); a.stack_cap = left;
     a.ploc = s->fast_build_ploc;
+    a.rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
     LbvhResult r;
     e = srk_tl_build(a, &r, nullptr);
     if (e > 0) return fail(SR_ERR_HIP, std::string("device top-level build failed: ") + hipGetErrorString((hipError_t)e));
     const uint32_t need = r.max_stack + srl::kLeafMax + blas_stack + 1u;     // as the host build counts it
+    note_tree_height(s, SR_TREE_KIND_TOP_LEVEL, left, r, e == 0 && need <= kTlStackCap);
     if (e < 0 || need > kTlStackCap) { *reason = SR_TL_HOST_STACK_BUDGET; return SR_OK; }
     const auto t2 = std::chrono::steady_clock::now();
     s->blas_stack = blas_stack;
@@ -1029,8 +1045,14 @@ bool instance_is_baked(const float* M) {
 // than kBlasStackCap and are refused. The rule's threshold would be 32 768, and no measured size from there on is built on the
 // device: no size qualifies, so AUTO stays on the host everywhere (0xFFFFFFFF = never); the device build runs in mode DEVICE only.
 constexpr uint32_t kBlasDeviceMinTris = 0xFFFFFFFFu;
+// The same under SR_HEIGHT_BOUND_REBALANCE (scripts/gpu_mesh_tree_build.py --leg rebalance -> profiles/mesh_tree_rebalance.json, table
+// in DESIGN.md section 4), host / parent commit / device in ms: 4 096: 2.13 / 2.10 / 2.79, 20 992: 11.0 / 10.5 / 3.61, 65 536: 69.6 / 69.6 / 5.25,
+// 250 000: 129 / 129 / 8.34, 1 000 000: 406 / 416 / 17.3. The device wins by more than the combined spreads from 20 992 triangles on,
+// which rounds up to 32 768, and every measured size above that is now built on the device: the rule yields 32 768.
+constexpr uint32_t kBlasDeviceMinTrisBounded = 32768;
 constexpr uint32_t kBlasStackCap = 26;       // build_blas's limit: leaves the top-level tree at least 18 of the kTlStackCap entries
-static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshUpdateInfo) == 64, "layouts the harness relies on");
+static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshUpdateInfo) == 64 && sizeof(SrTreeHeightInfo) == 32, "layouts the harness relies on");
+uint32_t blas_device_min_tris(const SrScene* s) { return s->height_bound == SR_HEIGHT_BOUND_REBALANCE ? kBlasDeviceMinTrisBounded : kBlasDeviceMinTris; }
 
 // Blas::rebuild (blas.rs:285-310) on the device for the meshes of `set` (pending updatable meshes whose state asked for
 // SR_OP_FAST_BUILD): srk_blas_build writes each tree into the mesh's ranges of the concatenated arrays, which stay resident.
@@ -1064,12 +1086,16 @@ int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32
         a.slot_of_gid = (uint32_t*)s->d_slot_of_gid.p; a.tri_base = ms.tri_base;
         a.rows = rows_dev; a.out = (uint32_t*)s->d_blas_build_out.p;
         a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
-        a.stack_floor = std::min(depth_for(n), kBlasStackCap); a.stack_cap = kBlasStackCap;
+        const bool rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
+        const uint32_t cap = rebalance && s->mesh_tree_cap ? s->mesh_tree_cap : kBlasStackCap;      // binds device builds only
+        a.stack_floor = std::min(depth_for(n), cap); a.stack_cap = cap;
         a.ploc = s->fast_build_ploc;
+        a.rebalance = rebalance;
         LbvhResult r;
         const int e = srk_blas_build(a, &r, nullptr);
         if (e > 0) return fail(SR_ERR_HIP, std::string("device mesh-tree build failed: ") + hipGetErrorString((hipError_t)e));
-        if (e < 0 || r.max_stack > kBlasStackCap) {           // deeper than the host's limit for mesh trees: remembered, the attempt is not repeated
+        note_tree_height(s, SR_TREE_KIND_MESH, cap, r, e == 0 && r.max_stack <= cap);
+        if (e < 0 || r.max_stack > cap) {           // deeper than the host's limit for mesh trees: remembered, the attempt is not repeated
             ms.device_refused = s->fast_build_ploc;
             *reason = SR_MESH_TREE_HOST_STACK_BUDGET;
             return SR_OK;
@@ -1132,7 +1158,7 @@ int maintain_mesh_trees(SrScene* s, uint32_t forced) {
     if (reason == SR_MESH_TREE_ON_DEVICE && slow) reason = SR_MESH_TREE_HOST_SLOW_BUILD;
     for (size_t k = 0; reason == SR_MESH_TREE_ON_DEVICE && k < builds.size(); k++) {
         if (s->blas_build_mode == SR_MESH_TREE_BUILD_HOST) reason = SR_MESH_TREE_HOST_MODE;
-        else if (s->blas_build_mode == SR_MESH_TREE_BUILD_AUTO && s->mesh_state[builds[k]].tree.n_tris < kBlasDeviceMinTris) reason = SR_MESH_TREE_HOST_BELOW_THRESHOLD;
+        else if (s->blas_build_mode == SR_MESH_TREE_BUILD_AUTO && s->mesh_state[builds[k]].tree.n_tris < blas_device_min_tris(s)) reason = SR_MESH_TREE_HOST_BELOW_THRESHOLD;
         else if (s->mesh_state[builds[k]].device_refused == s->fast_build_ploc) reason = SR_MESH_TREE_HOST_STACK_BUDGET;     // refused before
     }
     int rc;
@@ -1141,6 +1167,7 @@ int maintain_mesh_trees(SrScene* s, uint32_t forced) {
         for (size_t m = 0; m < nm; m++)
             if (s->mesh_state[m].refit_pending || s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
         ti.reason = reason;
+        if (!builds.empty()) s->height_info[SR_TREE_KIND_MESH].on_device = 0u;      // the host takes the trees that asked for a fast build
         return SR_OK;
     }
     if (set.empty()) return SR_OK;
@@ -1374,9 +1401,11 @@ int fast_build(SrScene* s) {
     a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
     a.stack_floor = (uint32_t)srd::kStackMax; a.stack_cap = kDeviceStackCap;
     a.ploc = s->fast_build_ploc;
+    a.rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
     LbvhResult r;
     const int e = srk_lbvh_build(a, &r, nullptr);
     if (e > 0) return fail(SR_ERR_HIP, std::string("device BVH build failed: ") + hipGetErrorString((hipError_t)e));
+    note_tree_height(s, SR_TREE_KIND_ONE_LEVEL, kDeviceStackCap, r, e == 0);
     if (e < 0) return full_build(s);                      // tree outside the limits: quality build on the host instead
     std::vector<uint32_t> level_nodes;
     s->level_offsets.assign(1, 0u);
@@ -1553,7 +1582,24 @@ int sr_scene_mesh_tree_info(const SrScene* s, SrMeshTreeInfo* out) {
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_tree_info: null argument");
     *out = s->mt_info;
     out->mode = (uint32_t)s->blas_build_mode;
-    out->auto_threshold = kBlasDeviceMinTris;
+    out->auto_threshold = blas_device_min_tris(s);
+    return SR_OK;
+}
+int sr_scene_set_tree_height_bound(SrScene* s, uint32_t mode, uint32_t mesh_tree_cap) {
+    if (mode > SR_HEIGHT_BOUND_REBALANCE) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_tree_height_bound: mode must be SR_HEIGHT_BOUND_REFUSE or SR_HEIGHT_BOUND_REBALANCE");
+    if (mesh_tree_cap > kBlasStackCap) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_tree_height_bound: mesh_tree_cap must be 0 (the library's 26) or 1..26");
+    if (mesh_tree_cap != 0 && mode == SR_HEIGHT_BOUND_REFUSE) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_tree_height_bound: a mesh_tree_cap needs SR_HEIGHT_BOUND_REBALANCE");
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_tree_height_bound: scene is null");
+    s->height_bound = mode; s->mesh_tree_cap = mesh_tree_cap;
+    for (SrScene::MeshState& ms : s->mesh_state) ms.device_refused = -1;      // a refusal held for the mode and cap it was made under
+    return SR_OK;
+}
+int sr_scene_tree_height_info(const SrScene* s, uint32_t kind, SrTreeHeightInfo* out) {
+    if (kind > SR_TREE_KIND_MESH) return fail(SR_ERR_INVALID_ARG, "sr_scene_tree_height_info: kind must be SR_TREE_KIND_ONE_LEVEL, _TOP_LEVEL or _MESH");
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_tree_height_info: null argument");
+    *out = s->height_info[kind];
+    out->mode = s->height_bound; out->mesh_tree_cap = s->mesh_tree_cap;
+    if (!s->built) out->on_device = 0u;
     return SR_OK;
 }
 int sr_scene_read_top_level(const SrScene* s, uint32_t* nodes, uint32_t* tl_inst, void* records, float* boxes) {

@@ -43,6 +43,7 @@ struct LbvhArgs {
     uint32_t* slot_of_gid; float* node_box;              // n_tris / node_cap x 6 floats
     void* scratch; size_t scratch_bytes;
     uint32_t stack_floor, stack_cap;                     // budget = max(stack_floor, binary height); fail above stack_cap
+    int rebalance = 0;                                   // 1: a binary tree taller than stack_cap is rebalanced to fit it instead of refused
     int ploc;                                            // topology: 0 = binary radix tree (LBVH), r > 0 = PLOC with search radius r
     // srk_tl_build only (the primitives are instance boxes; meshes .. slot_of_gid above are unused, n_tris is unused)
     const float* boxes = nullptr; uint32_t n_boxes = 0;  // n_instances x 6 floats, n_boxes of them real (the others are NaN rows)
@@ -59,6 +60,9 @@ struct LbvhArgs {
 struct LbvhResult {
     uint32_t n_nodes = 0, max_stack = 0, max_depth = 0;
     std::vector<std::pair<uint32_t, uint32_t>> level_ranges;   // (first node, count) per level, root level first
+    // binary walk height of the topology the builder chose / of what was collapsed (set on a refusal for height as well), and what
+    // the height bound rebuilt (0, 0 when the tree fitted)
+    uint32_t height_before = 0, height_after = 0, subtrees_rebuilt = 0, prims_rebuilt = 0;
 };
 int srk_lbvh_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
 size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap);

@@ -334,7 +334,8 @@ __global__ void lbvh_hierarchy_kernel(const unsigned long long* keys, int n, int
 }
 
 // Bottom-up fit: boxes of the radix nodes and the stack height of a purely binary walk below each (0 for subtrees that
-// will become leaves), second arriver at a node continues (the first one's writes are visible after the fence).
+// will become leaves), second arriver at a node continues (the first one's writes are visible after the fence). A node's size is
+// its Morton range where the tree has one (`range`, the radix tree), the sum of its children's otherwise (a rebalanced tree).
 template <class Prims>
 __global__ void lbvh_fit_kernel(const Prims prims, const uint32_t* sorted_gid, int n, const int2* children, const uint32_t* parent_of_inner,
                                 const uint32_t* parent_of_leaf, const uint2* range, float* bin_box, uint32_t* bin_height, uint32_t* bin_size,
@@ -348,23 +349,160 @@ __global__ void lbvh_fit_kernel(const Prims prims, const uint32_t* sorted_gid, i
         __threadfence();
         const int2 ch = children[node];
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        uint32_t h = 0;
+        uint32_t h = 0, size = 0;
         const int cc[2] = {ch.x, ch.y};
         for (int c = 0; c < 2; c++) {
-            if (cc[c] < 0) prims.add(sorted_gid[~cc[c]], lo, hi);
+            if (cc[c] < 0) { prims.add(sorted_gid[~cc[c]], lo, hi); size += 1u; }
             else {
                 const volatile float* b = bin_box + (size_t)cc[c] * 6;
                 for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], b[a]); hi[a] = fmaxf(hi[a], b[3 + a]); }
                 h = max(h, ((const volatile uint32_t*)bin_height)[cc[c]]);
+                if (!range) size += ((const volatile uint32_t*)bin_size)[cc[c]];
             }
         }
-        const uint2 r = range[node];
+        if (range) { const uint2 r = range[node]; size = r.y - r.x + 1u; }      // radix tree: the node's Morton range
         float* b = bin_box + (size_t)node * 6;
         for (int a = 0; a < 3; a++) { b[a] = lo[a]; b[3 + a] = hi[a]; }
-        bin_size[node] = r.y - r.x + 1u;
-        bin_height[node] = (r.y - r.x + 1u <= srl::kLeafMax) ? 0u : h + 1u;
+        bin_size[node] = size;
+        bin_height[node] = (size <= srl::kLeafMax) ? 0u : h + 1u;
         node = parent_of_inner[node];
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Height bound (LbvhArgs::rebalance): a binary tree whose walk height h(root) exceeds the stack cap is rewritten so that it
+// fits, between the topology stage and the collapse. H(k) is the walk height of a median-split tree over k primitives. The
+// root's allowance is A = stack_cap, a child's its parent's minus one. At a node v: h(v) <= A(v): the subtree is kept whole;
+// otherwise, if both children c have H(size(c)) <= A(v) - 1, v's split is kept and the rule goes on in the children; otherwise
+// v's subtree is rebuilt as a median-split tree over its own leaves in depth-first order, on its own inner node ids. By
+// induction H(size(v)) <= A(v) wherever the rule arrives, so afterwards h(root) <= stack_cap, and the builder's topology
+// survives everywhere except below the deepest, smallest offending nodes. Every kernel reads only what an earlier launch wrote:
+//   links      one thread per inner node: parent, left-sibling size of both children; own h, 1 + max H(size(child)), left size
+//   walk       one thread per leaf and per inner node, twice up the parent links (depth first, then the rule with the depths
+//              known): the topmost ancestor the rule rebuilds, the node's depth-first position (leaf) or in-order gap (inner
+//              node: position of the last leaf of its left subtree) -> leaf_at_pos, inner_at_gap, the subtree's range
+//   rebuild    one thread per inner node of a rebuilt subtree: down the implicit median tree over the range to the node whose
+//              split gap is its own (<= 32 steps), children from the two arrays alone (never from children[], which it writes);
+//              the subtree's old root re-points its parent's reference, or the root id, to the holder of the median gap
+//   parents    parent arrays of the rewritten tree for lbvh_fit_kernel, which then recomputes box, size and height of every node
+// ---------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kNoNode = 0xFFFFFFFFu;
+constexpr int kMaxBinaryWalk = 4096 + 64;      // a radix tree is < 100 levels tall, a PLOC tree at most its iteration count (4096)
+
+__device__ __forceinline__ bool binary_ref_ok(int ref, uint32_t n) { return ref < 0 ? (uint32_t)~ref < n : (uint32_t)ref + 1u < n; }
+
+__host__ __device__ __forceinline__ uint32_t median_height(uint32_t k) {      // H(k)
+    uint32_t h = 0;
+    for (int i = 0; i < 32 && k > srl::kLeafMax; i++) { k = (k + 1u) >> 1; h++; }
+    return h;
+}
+
+// link[u] = (parent, h(u) | (1 + max H(size(child))) << 16, size of u's left sibling (0: u is a left child or the root), size of
+// u's left child); leaf_link[k] = (parent, size of the left sibling). A thread writes .y and .w of its own node and .x and .z
+// of its children: every word has one writer.
+__global__ void rebalance_links_kernel(const int2* children, const uint32_t* bin_size, const uint32_t* bin_height, uint32_t n, uint32_t root, uint4* link,
+                                       uint2* leaf_link) {
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u + 1u >= n) return;
+    const int2 ch = children[u];
+    if (!binary_ref_ok(ch.x, n) || !binary_ref_ok(ch.y, n)) return;      // cannot happen; the walk then reports the broken chain
+    const uint32_t sl = ch.x < 0 ? 1u : bin_size[ch.x], sr = ch.y < 0 ? 1u : bin_size[ch.y];
+    if (ch.x < 0) leaf_link[~ch.x] = make_uint2(u, 0u); else { link[ch.x].x = u; link[ch.x].z = 0u; }
+    if (ch.y < 0) leaf_link[~ch.y] = make_uint2(u, sl); else { link[ch.y].x = u; link[ch.y].z = sl; }
+    link[u].y = min(bin_height[u], 0xFFFFu) | (1u + max(median_height(sl), median_height(sr))) << 16;
+    link[u].w = sl;
+    if (u == root) { link[u].x = kNoNode; link[u].z = 0u; }
+}
+
+// rb_range[x] = (first position, size) of the rebuilt subtree inner node x lies in ((0, 0): none); rb_gap[x] = its in-order gap,
+// bit 31 set for the subtree's root.
+__global__ void rebalance_walk_kernel(const uint4* link, const uint2* leaf_link, const uint32_t* bin_size, uint32_t n, int cap, uint32_t* leaf_at_pos,
+                                      uint32_t* inner_at_gap, uint2* rb_range, uint32_t* rb_gap, uint32_t* error) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2u * n - 1u) return;
+    const bool leaf = t < n;
+    const uint32_t x = leaf ? t : t - n;
+    const uint32_t u0 = leaf ? leaf_link[x].x : x;      // first inner node of the chain to the root
+    if (!leaf) rb_range[x] = make_uint2(0u, 0u);
+    int depth = 0;                                       // of u0
+    uint32_t cur = u0;
+    for (; depth < kMaxBinaryWalk; depth++) {
+        if (cur >= n - 1u) { atomicExch(error, 1u); return; }
+        const uint32_t p = link[cur].x;
+        if (p == kNoNode) break;
+        cur = p;
+    }
+    if (depth >= kMaxBinaryWalk) { atomicExch(error, 1u); return; }
+    // second walk: `acc` = first position of x relative to the first leaf of `cur`'s subtree
+    uint32_t acc = leaf ? leaf_link[x].y : 0u, r = kNoNode, rel = 0u;
+    cur = u0;
+    for (int d = depth; d >= 0; d--) {
+        const uint4 L = link[cur];
+        const int allowance = cap - d, h = (int)(L.y & 0xFFFFu), need = (int)(L.y >> 16);
+        if (h <= allowance) r = kNoNode;                 // kept whole, with everything below
+        else if (need > allowance) { r = cur; rel = acc; }
+        acc += L.z;
+        cur = L.x;
+    }
+    if (r == kNoNode) return;
+    if (leaf) { if (acc < n) leaf_at_pos[acc] = x; return; }
+    const uint32_t gap = acc + link[x].w - 1u;
+    if (gap >= n - 1u) { atomicExch(error, 1u); return; }
+    inner_at_gap[gap] = x;
+    rb_range[x] = make_uint2(acc - rel, bin_size[r]);
+    rb_gap[x] = gap | (r == x ? 0x80000000u : 0u);
+}
+
+// The node of the median tree over the positions [lo, hi) (hi - lo >= 2) splits behind position lo + ceil((hi - lo) / 2) - 1.
+__device__ __forceinline__ uint32_t median_gap(uint32_t lo, uint32_t hi) { return lo + ((hi - lo + 1u) >> 1) - 1u; }
+__device__ __forceinline__ int median_child(uint32_t lo, uint32_t hi, const uint32_t* leaf_at_pos, const uint32_t* inner_at_gap) {
+    return hi - lo == 1u ? ~(int)leaf_at_pos[lo] : (int)inner_at_gap[median_gap(lo, hi)];
+}
+
+// stat: [0] root id (rewritten if the root's subtree is rebuilt), [1] subtrees rebuilt, [2] primitives in them, [4] error flag
+__global__ void rebalance_rebuild_kernel(const uint4* link, const uint2* rb_range, const uint32_t* rb_gap, const uint32_t* leaf_at_pos,
+                                         const uint32_t* inner_at_gap, uint32_t n, int2* children, uint32_t* stat) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x + 1u >= n) return;
+    const uint2 R = rb_range[x];
+    if (R.y < 2u || (uint64_t)R.x + R.y > n) return;
+    const uint32_t g = rb_gap[x] & 0x7FFFFFFFu;
+    uint32_t lo = R.x, hi = R.x + R.y;
+    for (int i = 0; i < 64 && hi - lo >= 2u; i++) {
+        const uint32_t m = median_gap(lo, hi);
+        if (g == m) break;
+        if (g < m) hi = m + 1u; else lo = m + 1u;
+    }
+    if (hi - lo < 2u || median_gap(lo, hi) != g) return;      // cannot happen: every gap of the range is some node's split
+    const uint32_t mid = g + 1u;
+    const int2 ch = make_int2(median_child(lo, mid, leaf_at_pos, inner_at_gap), median_child(mid, hi, leaf_at_pos, inner_at_gap));
+    if (!binary_ref_ok(ch.x, n) || !binary_ref_ok(ch.y, n)) { atomicExch(stat + 4, 1u); return; }
+    children[x] = ch;
+    if (rb_gap[x] & 0x80000000u) {                             // the subtree's old root: hand the new one to the parent
+        const uint32_t top = inner_at_gap[median_gap(R.x, R.x + R.y)];
+        const uint4 L = link[x];
+        if (top + 1u >= n || (L.x != kNoNode && L.x + 1u >= n)) { atomicExch(stat + 4, 1u); return; }
+        if (L.x == kNoNode) stat[0] = top;
+        else ((int*)children)[2 * (size_t)L.x + (L.z ? 1 : 0)] = (int)top;
+        atomicAdd(stat + 1, 1u);
+        atomicAdd(stat + 2, R.y);
+    }
+}
+
+__global__ void rebalance_parents_kernel(const int2* children, uint32_t n, const uint32_t* root, uint32_t* parent_of_inner, uint32_t* parent_of_leaf) {
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u + 1u >= n) return;
+    const int2 ch = children[u];
+    if (!binary_ref_ok(ch.x, n) || !binary_ref_ok(ch.y, n)) return;
+    if (ch.x >= 0) parent_of_inner[ch.x] = u; else parent_of_leaf[~ch.x] = u;
+    if (ch.y >= 0) parent_of_inner[ch.y] = u; else parent_of_leaf[~ch.y] = u;
+    if (u == *root) parent_of_inner[u] = kNoNode;
+}
+
+// stat[3] = walk height of the rewritten tree
+__global__ void rebalance_finish_kernel(const uint32_t* bin_height, uint32_t n, uint32_t* stat) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    stat[3] = stat[0] + 1u < n ? bin_height[stat[0]] : kNoNode;
 }
 
 // A child of a 4-wide node during the collapse: `ref` is a binary-tree reference (>= 0: binary node, < 0: single triangle
@@ -872,10 +1010,17 @@ static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
     uint32_t* budget_of_node = (uint32_t*)take((size_t)a.node_cap * 4);
     uint32_t* prefix_of_node = (uint32_t*)take((size_t)a.node_cap * 4);
     uint32_t* first_of_node = (uint32_t*)take((size_t)a.node_cap * 4);
-    uint32_t* small = (uint32_t*)take(256);          // [0..5] bounds, [8..10] counters, [12] PLOC node counter
+    uint32_t* small = (uint32_t*)take(256);          // [0..5] bounds, [8..10] counters, [12] PLOC node counter, [16..23] mesh box, [32..36] height bound
     // PLOC cluster arrays (double-buffered)
     int* cid[2] = {nullptr, nullptr}; float* cbox[2] = {nullptr, nullptr};
     if (a.ploc) for (int k = 0; k < 2; k++) { cid[k] = (int*)take((size_t)n * 4); cbox[k] = (float*)take((size_t)n * 24); }
+    // the height bound's own arrays; its per-node range and gap live in the sort's input buffers, which are dead by then
+    uint4* link = (uint4*)take((size_t)n * 16);
+    uint2* leaf_link = (uint2*)take((size_t)n * 8);
+    uint32_t* leaf_at_pos = (uint32_t*)take((size_t)n * 4);
+    uint32_t* inner_at_gap = (uint32_t*)take((size_t)n * 4);
+    uint2* rb_range = (uint2*)keys_a;
+    uint32_t* rb_gap = vals_a;
     size_t cub_bytes = 0, scan_bytes = 0;
     hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, keys_a, keys_b, vals_a, vals_b, (int)n_keys, 0, sort_bits, stream);
     if (e != hipSuccess) return (int)e;
@@ -948,8 +1093,29 @@ static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
         uint32_t root_height = 0;
         if ((e = hipMemcpyAsync(&root_height, bin_height + root_bin, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
         if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
-        if (root_height > a.stack_cap) return -1;
-        const uint32_t budget = root_height > a.stack_floor ? root_height : a.stack_floor;
+        out->height_before = out->height_after = root_height;
+        if (root_height > a.stack_cap) {
+            if (!a.rebalance || median_height(n) > a.stack_cap) return -1;      // refused; no tree over n primitives fits
+            uint32_t* const stat = small + 32;
+            uint32_t st[5] = {(uint32_t)root_bin, 0u, 0u, 0u, 0u};
+            const dim3 gw((2 * n - 1 + B - 1) / B);
+            if ((e = hipMemcpyAsync(stat, st, sizeof(st), hipMemcpyHostToDevice, stream)) != hipSuccess) return (int)e;
+            rebalance_links_kernel<<<gt, bt, 0, stream>>>(children, bin_size, bin_height, n, (uint32_t)root_bin, link, leaf_link);
+            rebalance_walk_kernel<<<gw, bt, 0, stream>>>(link, leaf_link, bin_size, n, (int)a.stack_cap, leaf_at_pos, inner_at_gap, rb_range, rb_gap, stat + 4);
+            rebalance_rebuild_kernel<<<gt, bt, 0, stream>>>(link, rb_range, rb_gap, leaf_at_pos, inner_at_gap, n, children, stat);
+            rebalance_parents_kernel<<<gt, bt, 0, stream>>>(children, n, stat, parent_inner, parent_leaf);
+            if ((e = hipMemsetAsync(flags, 0, (size_t)n * 4, stream)) != hipSuccess) return (int)e;
+            lbvh_fit_kernel<<<gt, bt, 0, stream>>>(prims, vals_b, (int)n, children, parent_inner, parent_leaf, (const uint2*)nullptr, bin_box, bin_height, bin_size, flags);
+            rebalance_finish_kernel<<<dim3(1), dim3(64), 0, stream>>>(bin_height, n, stat);
+            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+            if ((e = hipMemcpyAsync(st, stat, sizeof(st), hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
+            if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
+            if (st[4] || st[0] + 1u >= n || st[3] > a.stack_cap) return -1;     // cannot happen for a tree the topology stage finished
+            root_bin = (int)st[0]; root_height = st[3];
+            out->height_after = st[3]; out->subtrees_rebuilt = st[1]; out->prims_rebuilt = st[2];
+        }
+        const uint32_t floor = a.rebalance ? (a.stack_floor < a.stack_cap ? a.stack_floor : a.stack_cap) : a.stack_floor;
+        const uint32_t budget = root_height > floor ? root_height : floor;
         const uint32_t zero = 0;
         (void)hipMemcpyAsync(bin_of_node, &root_bin, 4, hipMemcpyHostToDevice, stream);
         (void)hipMemcpyAsync(budget_of_node, &budget, 4, hipMemcpyHostToDevice, stream);
@@ -1012,5 +1178,5 @@ size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap) {
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
                                              (uint32_t*)nullptr, (int)n_tris, 0, 63, nullptr);
     (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n_tris, nullptr);
-    return (size_t)n_tris * (48 + 16 + 16 + 8 + 8 + 8 + 4 + 4 + 24 + 4 + 4 + 4 + 4 + 2 * (4 + 24)) + (size_t)node_cap * 16 + std::max(cub_bytes, scan_bytes) + 96 * 256;
+    return (size_t)n_tris * (48 + 16 + 16 + 8 + 8 + 8 + 4 + 4 + 24 + 4 + 4 + 4 + 4 + 2 * (4 + 24) + 16 + 8 + 4 + 4) + (size_t)node_cap * 16 + std::max(cub_bytes, scan_bytes) + 100 * 256;
 }

@@ -522,6 +522,18 @@ int sr_renderer_set_mesh_tree_build(SrRenderer* r, uint32_t mode) {
     return SR_OK;
 }
 
+// What a device fast build does with a tree taller than its stack cap (SR_HEIGHT_BOUND_*), on every replica.
+int sr_renderer_set_tree_height_bound(SrRenderer* r, uint32_t mode, uint32_t mesh_tree_cap) {
+    if (mode > SR_HEIGHT_BOUND_REBALANCE || mesh_tree_cap > 26u || (mesh_tree_cap != 0 && mode == SR_HEIGHT_BOUND_REFUSE))
+        return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_tree_height_bound: mode must be SR_HEIGHT_BOUND_REFUSE or _REBALANCE, mesh_tree_cap 0 or, under _REBALANCE, 1..26");
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_tree_height_bound: renderer is null");
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_set_tree_height_bound(sc, mode, mesh_tree_cap);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+
 // Access for harnesses: the scene (counters, stats), the device output image and the frame counter.
 int sr_renderer_get(SrRenderer* r, SrScene** scene, const uint32_t** output_rgba8_device, const float** raw_color_device, uint32_t* relative_frame_count) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_get: renderer is null");

@@ -231,6 +231,18 @@ class Scene:
         check(lib().sr_scene_mesh_tree_info(self._h, C.byref(info)))
         return info
 
+    def set_tree_height_bound(self, mode, cap=0):
+        """What a device fast build does with a tree taller than its stack cap: "refuse" (the host builds) | "rebalance" (the
+        device makes it fit); cap: 0 = the library's 26, or 1..26 for device-built mesh trees (sr_scene_set_tree_height_bound)."""
+        check(lib().sr_scene_set_tree_height_bound(self._h, C.c_uint32({"refuse": 0, "rebalance": 1}[mode]), C.c_uint32(cap)))
+        return self
+
+    def tree_height_info(self, kind):
+        """-> abi.SrTreeHeightInfo of the last device fast build of one abi.TREE_KIND_*."""
+        info = abi.SrTreeHeightInfo()
+        check(lib().sr_scene_tree_height_info(self._h, C.c_uint32(kind), C.byref(info)))
+        return info
+
     def mesh_as_state(self, key):
         """-> (build type, SrAsState, last op) of one mesh's tree."""
         bt, st, op = C.c_uint32(), abi.SrAsState(), C.c_uint32()
@@ -700,6 +712,11 @@ class Renderer:
     def set_mesh_tree_build(self, mode):
         """Scene.set_mesh_tree_build on every device slot (sr_renderer_set_mesh_tree_build)."""
         check(lib().sr_renderer_set_mesh_tree_build(self._h, C.c_uint32({"auto": 0, "host": 1, "device": 2}[mode])))
+
+    def set_tree_height_bound(self, mode, cap=0):
+        """Scene.set_tree_height_bound on every device slot (sr_renderer_set_tree_height_bound)."""
+        check(lib().sr_renderer_set_tree_height_bound(self._h, C.c_uint32({"refuse": 0, "rebalance": 1}[mode]), C.c_uint32(cap)))
+        return self
 
     def mesh_tree_info(self, slot=0):
         """Scene.mesh_tree_info of one device slot's scene."""
