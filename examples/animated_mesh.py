@@ -5,10 +5,13 @@ heuristic picks; it is never torn down and rebuilt on the host. The sphere is de
 BuildType of a BLAS that is built with ALLOW_UPDATE): where the scene stands in the two-level form (SR_INSTANCING=two_level, or a
 scene large enough for the automatic choice) its own tree is then refitted on the device as well. Writes the last frame as a PNG.
 
-    python examples/animated_mesh.py [out.png] [--frames 24] [--size 640x480] [--height-bound rebalance]
+    python examples/animated_mesh.py [out.png] [--frames 24] [--size 640x480] [--height-bound rebalance] [--device-vertices]
 
 --height-bound rebalance: a device fast build whose tree comes out taller than the traversal stack allows is rebalanced on the
 device instead of going to the host builder (Renderer.set_tree_height_bound; the default, refuse, is the library's).
+
+--device-vertices: the sphere is deformed with torch ops on the GPU and handed over as a tensor (Renderer.update_mesh_device):
+the vertices never visit the host, the library validates them on the device and copies device to device.
 
 Needs a GPU: the product path has no CPU fallback.
 """
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--size", default="640x480")
     ap.add_argument("--height-bound", choices=["refuse", "rebalance"], default="refuse")
+    ap.add_argument("--device-vertices", action="store_true")
     args = ap.parse_args()
     from sunray_amd import abi, runtime as rt, scenes
     w, h = (int(v) for v in args.size.split("x"))
@@ -38,8 +42,18 @@ def main():
         r.load_mesh(m.key, m.vertices, m.indices, m.material)
     r.set_mesh_build_type(sphere.key, abi.BUILD_RAPIDLY_CHANGING)
     camera = (desc.camera_pos, desc.camera_target, desc.fov_y)
+    if args.device_vertices:
+        import torch
+        rest = torch.from_numpy(sphere.vertices.view("<f4").reshape(len(sphere.vertices), -1).copy()).to("cuda:0")   # [n, 24] floats: 96-byte records
     for f in range(args.frames):
-        if f:
+        if f and args.device_vertices:
+            # a ripple along the rest normal, computed where the vertices live; the normals keep their rest direction
+            pos, nrm = rest[:, 0:3], rest[:, 4:7]
+            wave = 0.08 * torch.sin(9.0 * pos[:, 1:2] + 5.0 * pos[:, 0:1] + 0.25 * f)
+            posed = rest.clone()
+            posed[:, 0:3] = pos + wave * nrm
+            r.update_mesh_device(sphere.key, posed)
+        elif f:
             r.update_mesh(sphere.key, scenes.deform_vertices(sphere.vertices, sphere.indices, 0.25 * f, amplitude=0.08))
         r.wait_frame(r.render(camera, desc.instances))
     image = r.render_to_host_memory(camera, desc.instances)       # lets the temporal accumulation settle on the last pose

@@ -452,6 +452,31 @@ typedef struct SrMeshUpdateInfo {
     double blas_build_ms;      /* two-level form: host builds of the per-mesh trees counted in blas_rebuilt */
 } SrMeshUpdateInfo;
 int sr_scene_mesh_update_info(const SrScene* scene, SrMeshUpdateInfo* out);
+/* sr_scene_update_mesh for vertices that already are in device memory of the scene's GPU (a skinning or simulation kernel, a
+ * torch tensor): `d_vertices` holds n_vertices SrVertex records, is 16-byte aligned, and was produced by work on `stream`. The
+ * contract is sr_scene_update_mesh's, with these differences. Refused on the host before anything is launched: a null scene or
+ * pointer, an unknown key, another vertex count, a misaligned pointer, a range that overlaps the mesh's own device allocation
+ * (SrMeshInfo.vertices of sr_scene_get_tables), a pointer the HIP runtime does not report as device memory of the scene's
+ * device for that many vertices (all SR_ERR_INVALID_ARG; such a pointer is never dereferenced), an emissive list that is not
+ * one per triangle (SR_ERR_UNSUPPORTED). The positions are then validated ON THE DEVICE under the host call's rule (x, y, z
+ * finite; nothing else is looked at): the lowest offending index is reported with the host call's text and status, and the
+ * scene is exactly as it was, since the mesh's buffer is written only afterwards (check, 4-byte read-back, device wait,
+ * device-to-device copy). The library's HOST copy of the vertices is not touched and becomes stale; host code that needs it (a
+ * host build of the mesh's tree or of the one-level tree) fetches it with one device-to-host copy, the device paths (SR_OP_UPDATE,
+ * the device fast build, the device refit and device build of an updatable mesh's tree) never do. A mesh with emissive entries
+ * fetches inside the call. A later sr_scene_update_mesh replaces the copy. SrMeshUpdateInfo.validate_copy_ms / h2d_ms: host
+ * wall clock of the call without, and of, its wait-and-copy section. */
+int sr_scene_update_mesh_device(SrScene* scene, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, void* stream);
+typedef struct SrMeshVertexInfo {
+    uint32_t host_stale;       /* 1: the host copy is older than the device buffer */
+    uint32_t last_from_device; /* 1: the last update of this mesh came through the device entry point */
+    uint32_t host_fetches;     /* device-to-host refreshes of the host copy since the mesh was loaded */
+    uint32_t _pad;
+    double check_ms;           /* last device update: validation kernel + read-back (events, only while sr_scene_enable_timing is on) */
+    double copy_ms;            /* last device update: the device-to-device copy (events, only while sr_scene_enable_timing is on) */
+    double fetch_ms;           /* the last host fetch (wall clock) */
+} SrMeshVertexInfo;            /* 40 bytes */
+int sr_scene_mesh_vertex_info(const SrScene* scene, uint64_t key, SrMeshVertexInfo* out);
 /* BuildType of one mesh's tree (blas.rs:149-161: RapidlyChanging and SometimesChanges are built with ALLOW_UPDATE, Static is not).
  * Every loaded mesh starts as SR_BUILD_STATIC (Renderer::load_mesh, lib.rs:937): it is never refitted, every update rebuilds its
  * tree on the host. An updatable mesh holds an SrAsState of its own (reset to sr_as_state_initial(build_type) by this call), driven
@@ -769,6 +794,10 @@ int sr_renderer_unload_mesh(SrRenderer* renderer, uint64_t key);
 /* sr_scene_update_mesh on every device slot's scene; the next sr_renderer_render re-submits its instance list, which applies
  * the update. Each scene waits for its device, so frames in flight have finished reading the old vertices before they change. */
 int sr_renderer_update_mesh(SrRenderer* renderer, uint64_t key, const SrVertex* vertices, uint32_t n_vertices);
+/* sr_scene_update_mesh_device through the facade: `d_vertices` lives on the first device slot's GPU and is validated once,
+ * there; every further slot's replica takes the vertices by a device-to-device (peer) copy into its own allocation and ends in
+ * the same state. A refusal changes no replica. */
+int sr_renderer_update_mesh_device(SrRenderer* renderer, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, void* stream);
 /* sr_scene_set_mesh_build_type on every device slot's scene. */
 int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t build_type);
 /* sr_scene_set_mesh_tree_build on every device slot's scene. */

@@ -160,6 +160,11 @@ class SrMeshUpdateInfo(C.Structure):  # the last sr_scene_update_mesh and the sr
                 ("refit_ms", C.c_double), ("blas_build_ms", C.c_double)]
 
 
+class SrMeshVertexInfo(C.Structure):  # one mesh's host copy against its device buffer (sr_scene_mesh_vertex_info), 40 B
+    _fields_ = [("host_stale", C.c_uint32), ("last_from_device", C.c_uint32), ("host_fetches", C.c_uint32), ("_pad", C.c_uint32),
+                ("check_ms", C.c_double), ("copy_ms", C.c_double), ("fetch_ms", C.c_double)]
+
+
 class SrMeshTreeInfo(C.Structure):  # the mesh-tree builds of the last sr_scene_set_instances (sr_scene_mesh_tree_info)
     _fields_ = [("mode", C.c_uint32), ("auto_threshold", C.c_uint32), ("built_on_device", C.c_uint32), ("built_on_host", C.c_uint32),
                 ("reason", C.c_uint32), ("n_nodes", C.c_uint32), ("max_stack", C.c_uint32), ("_pad", C.c_uint32), ("device_build_ms", C.c_double)]

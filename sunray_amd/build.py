@@ -17,6 +17,11 @@ LIB = os.path.join(HERE, "libsunray_hip.so")
 SOURCES = ["kernels.hip", "post.hip", "bvh_gpu.hip", "api.cpp", "renderer.cpp", "multi_renderer.cpp", "strip_copy.hip", "multi_gpu.cpp", "gltf_load.cpp", "jpeg_decode.cpp", "host_prep.cpp", "bvh_build.cpp"]
 HEADERS = ["rt_device.h", "traverse.h", "bvh_layout.h", "kernels.h", "host.h", "bvh_gpu.h", "tl_record.h", "renderer.h", "strip_copy.h", os.path.join("..", "..", "include", "sunray_hip.h")]
 RESOURCES = os.path.join(HERE, "_obj", "kernels.hip.resources.txt")     # the compiler's per-kernel register / scratch report
+REPORTED = ("kernels.hip", "bvh_gpu.hip")       # sources whose report is kept: the pass kernels, the builder kernels
+
+
+def resources_path(source):
+    return os.path.join(HERE, "_obj", source + ".resources.txt")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-fno-slp-vectorize", "-Wall", "-Wno-unused-function",
          "-pthread"]
@@ -41,13 +46,13 @@ def build(force=False, verbose=False):
         cmd = [hipcc] + FLAGS + (["-x", "hip"] if src.endswith(".cpp") else []) + ["-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
-        if src == "kernels.hip":        # keep the register / spill figures of the pass kernels next to the object (kernel_resources())
+        if src in REPORTED:             # keep the register / spill figures of these kernels next to the object (kernel_resources())
             r = subprocess.run(cmd + ["-Rpass-analysis=kernel-resource-usage"], stderr=subprocess.PIPE, text=True)
             remarks = [ln for ln in r.stderr.splitlines() if "-Rpass-analysis=kernel-resource-usage" in ln]
             sys.stderr.write("\n".join(ln for ln in r.stderr.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in ln))
             if r.returncode != 0:
                 raise subprocess.CalledProcessError(r.returncode, cmd)
-            with open(RESOURCES, "w") as f:
+            with open(resources_path(src), "w") as f:
                 f.write("\n".join(remarks) + "\n")
         else:
             subprocess.check_call(cmd)
@@ -59,16 +64,18 @@ def build(force=False, verbose=False):
     return LIB
 
 
-def kernel_resources():
-    """{kernel name: {"vgprs", "sgprs", "scratch", "occupancy", "sgpr_spills", "vgpr_spills"}} of kernels.hip as the compiler
-    reported them at the last build (builds if there is no report yet)."""
+def kernel_resources(source="kernels.hip"):
+    """{kernel name: {"vgprs", "sgprs", "lds", "scratch", "occupancy", "sgpr_spills", "vgpr_spills"}} of one of REPORTED as the
+    compiler reported them at the last build (builds if there is no report yet)."""
     import re
-    if not os.path.exists(RESOURCES) or needs_build():
+    if source not in REPORTED:
+        raise ValueError("no resource report is kept for %s" % source)
+    if not os.path.exists(resources_path(source)) or needs_build():
         build(force=True)
     keys = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "occupancy",
-            "SGPRs Spill": "sgpr_spills", "VGPRs Spill": "vgpr_spills"}
+            "SGPRs Spill": "sgpr_spills", "VGPRs Spill": "vgpr_spills", "LDS Size [bytes/block]": "lds"}
     out, cur = {}, None
-    for ln in open(RESOURCES):
+    for ln in open(resources_path(source)):
         m = re.search(r"remark:\s+(.*?):\s+(\S+) \[-Rpass", ln)
         if not m:
             continue

@@ -216,6 +216,7 @@ struct SrScene {
     SrMeshTreeInfo mt_info{};               // mesh-tree builds of the last sr_scene_set_instances
     bool static_mesh_updated = false;       // a Static mesh was updated since the last sr_scene_set_instances (its tree goes to the host)
     DeviceBuffer d_blas_build_out;          // read-back block of a device mesh-tree build
+    DeviceBuffer d_vertex_check;            // the word sr_scene_update_mesh_device's validation kernel answers in
     DeviceBuffer d_blas_nodes, d_tl_inst, d_tl_instances;
     // top level built on the device (bvh_gpu.hip srk_tl_*): per-mesh rows the record kernel reads, the instance boxes, its result block
     DeviceBuffer d_tl_mesh_rows, d_tl_boxes, d_tl_result;
@@ -309,6 +310,92 @@ void invalidate_mesh_tree(SrScene* s, uint32_t slot) {
     SrScene::MeshState& ms = s->mesh_state[slot];
     ms.tree.valid = false; ms.tree.host_stale = false; ms.refit_pending = false;
     s->blas_device_current = false; s->tl_mesh_rows_current = false;
+}
+
+// The host copy of a mesh's vertices, brought up to date where sr_scene_update_mesh_device left it behind: one device-to-host
+// copy of the mesh's buffer. Everything on the host that reads HostMesh::vertices calls this first; the device paths (in-place
+// update, device fast build, mesh-tree refit and device build of a mesh without emissive entries) never do.
+int fetch_host_vertices(SrScene* s, uint32_t slot) {
+    srh::HostMesh& m = s->meshes[slot];
+    if (!m.host_stale) return SR_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(m.vertices.data(), m.d_vertices, sizeof(SrVertex) * (size_t)m.n_vertices, hipMemcpyDeviceToHost));
+    m.host_stale = false;
+    m.host_fetches++;
+    m.fetch_ms = ms_between(t0, std::chrono::steady_clock::now());
+    return SR_OK;
+}
+
+// What the two update calls refuse before anything else happens, with one text each: the slot of `key` into *slot.
+int check_mesh_update(SrScene* s, uint64_t key, const void* vertices, uint32_t n_vertices, uint32_t* slot) {
+    if (!s || !vertices) return fail(SR_ERR_INVALID_ARG, "update_mesh: null argument");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "update_mesh: no mesh is registered under this key");
+    *slot = it->second;
+    const srh::HostMesh& m = s->meshes[*slot];
+    if (n_vertices != m.n_vertices) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "update_mesh: %u vertices given, the mesh was loaded with %u (the vertex count cannot change)", n_vertices, m.n_vertices);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
+    return SR_OK;
+}
+int fail_non_finite_vertex(uint32_t i) {
+    char buf[120];
+    snprintf(buf, sizeof(buf), "update_mesh: vertex %u has a non-finite position", i);
+    return fail(SR_ERR_INVALID_ARG, buf);
+}
+// the emissive entries are one per triangle in index order (load_mesh, the glTF path) or none; any other list came from
+// the caller of sr_scene_add_blas and cannot be re-derived from vertices
+int check_emissive_list(const srh::HostMesh& m) {
+    if (!m.emissive_slots.empty() && m.emissive_slots.size() != m.n_indices / 3)
+        return fail(SR_ERR_UNSUPPORTED, "update_mesh: the mesh was loaded with emissive triangles that are not one per triangle");
+    return SR_OK;
+}
+
+// What follows a mesh's new vertices once they are in its device allocation (and, for a mesh with emissive entries, in the
+// host copy): the positions of its arena slots, then which trees and structures are stale.
+void mesh_vertices_changed(SrScene* s, uint32_t slot) {
+    const srh::HostMesh& m = s->meshes[slot];
+    for (size_t k = 0; k < m.emissive_slots.size(); k++) {   // positions only: emission follows the material, which stays
+        SrEmissiveTriangle& et = s->emissive_tris[m.emissive_slots[k]];
+        memcpy(et.v0, m.vertices[m.indices[3 * k]].position, 12);
+        memcpy(et.v1, m.vertices[m.indices[3 * k + 1]].position, 12);
+        memcpy(et.v2, m.vertices[m.indices[3 * k + 2]].position, 12);
+    }
+    // two-level form: this mesh's object-space tree, root box and padding numbers are stale; the other meshes keep theirs. An
+    // updatable mesh (sr_scene_set_mesh_build_type) with a valid tree keeps it: the next sr_scene_set_instances refits it on the
+    // or builds it on the device where it can (maintain_mesh_trees) and invalidates it otherwise
+    if (s->mesh_state[slot].build_type != SR_BUILD_STATIC && s->mesh_state[slot].tree.valid) s->mesh_state[slot].refit_pending = true;
+    else { invalidate_mesh_tree(s, slot); s->static_mesh_updated = s->static_mesh_updated || s->mesh_state[slot].build_type == SR_BUILD_STATIC; }
+    if (s->built) {
+        bool instanced = false;
+        for (const auto& in : s->fid.instances) if (in.mesh_slot == slot) { instanced = true; break; }
+        if (instanced) { s->mesh_state[slot].dirty = true; s->geometry_stale = true; }
+    }
+}
+
+// The copy of validated device vertices into a mesh's allocation (sr_scene_update_mesh_device and the replicas of a renderer):
+// the device wait (frames in flight read the old vertices), the copy on the null stream, the host copy left behind, and for a
+// mesh with emissive entries the fetch at once (the light table is host arithmetic on every sr_scene_set_instances).
+int take_device_vertices(SrScene* s, uint32_t slot, const SrVertex* d_vertices, int src_device) {
+    srh::HostMesh& m = s->meshes[slot];
+    const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
+    HIP_TRY(hipDeviceSynchronize());
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = s->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    if (timed) (void)hipEventRecord(ev[0], nullptr);
+    hipError_t e = src_device == s->device ? hipMemcpyAsync(m.d_vertices, d_vertices, bytes, hipMemcpyDeviceToDevice, nullptr)
+                                           : hipMemcpyPeerAsync(m.d_vertices, s->device, d_vertices, src_device, bytes, nullptr);
+    if (timed) (void)hipEventRecord(ev[1], nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    float ms = 0.0f;
+    m.copy_ms = (timed && e == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ? (double)ms : 0.0;
+    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    HIP_TRY(e);
+    m.host_stale = true; m.last_from_device = true;
+    return m.emissive_slots.empty() ? SR_OK : fetch_host_vertices(s, slot);
 }
 
 }  // namespace
@@ -508,51 +595,90 @@ int sr_scene_remove(SrScene* s, uint64_t key) {
 // vertices is brought up to date by the next sr_scene_set_instances; until then a structure that instances the mesh is stale.
 int sr_scene_update_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uint32_t n_vertices) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!s || !vertices) return fail(SR_ERR_INVALID_ARG, "update_mesh: null argument");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "update_mesh: no mesh is registered under this key");
-    const uint32_t slot = it->second;
-    srh::HostMesh& m = s->meshes[slot];
-    if (n_vertices != m.n_vertices) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "update_mesh: %u vertices given, the mesh was loaded with %u (the vertex count cannot change)", n_vertices, m.n_vertices);
-        return fail(SR_ERR_INVALID_ARG, buf);
-    }
-    if (const uint32_t i = first_non_finite_vertex(vertices, n_vertices); i < n_vertices) {
-        char buf[120];
-        snprintf(buf, sizeof(buf), "update_mesh: vertex %u has a non-finite position", i);
-        return fail(SR_ERR_INVALID_ARG, buf);
-    }
-    // the emissive entries are one per triangle in index order (load_mesh, the glTF path) or none; any other list came from
-    // the caller of sr_scene_add_blas and cannot be re-derived from vertices
-    if (!m.emissive_slots.empty() && m.emissive_slots.size() != m.n_indices / 3)
-        return fail(SR_ERR_UNSUPPORTED, "update_mesh: the mesh was loaded with emissive triangles that are not one per triangle");
-    int rc = bind_device(s);
+    uint32_t slot = 0;
+    int rc = check_mesh_update(s, key, vertices, n_vertices, &slot);
     if (rc != SR_OK) return rc;
+    srh::HostMesh& m = s->meshes[slot];
+    if (const uint32_t i = first_non_finite_vertex(vertices, n_vertices); i < n_vertices) return fail_non_finite_vertex(i);
+    if ((rc = check_emissive_list(m)) != SR_OK) return rc;
+    if ((rc = bind_device(s)) != SR_OK) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     HIP_TRY(hipDeviceSynchronize());                          // launches in flight read the old vertices (as sr_scene_remove waits)
     HIP_TRY(hipMemcpy(m.d_vertices, vertices, sizeof(SrVertex) * (size_t)n_vertices, hipMemcpyHostToDevice));
     const auto t2 = std::chrono::steady_clock::now();
     m.vertices.assign(vertices, vertices + n_vertices);
-    for (size_t k = 0; k < m.emissive_slots.size(); k++) {   // positions only: emission follows the material, which stays
-        SrEmissiveTriangle& et = s->emissive_tris[m.emissive_slots[k]];
-        memcpy(et.v0, m.vertices[m.indices[3 * k]].position, 12);
-        memcpy(et.v1, m.vertices[m.indices[3 * k + 1]].position, 12);
-        memcpy(et.v2, m.vertices[m.indices[3 * k + 2]].position, 12);
-    }
-    // two-level form: this mesh's object-space tree, root box and padding numbers are stale; the other meshes keep theirs. An
-    // updatable mesh (sr_scene_set_mesh_build_type) with a valid tree keeps it: the next sr_scene_set_instances refits it on the
-    // or builds it on the device where it can (maintain_mesh_trees) and invalidates it otherwise
-    if (s->mesh_state[slot].build_type != SR_BUILD_STATIC && s->mesh_state[slot].tree.valid) s->mesh_state[slot].refit_pending = true;
-    else { invalidate_mesh_tree(s, slot); s->static_mesh_updated = s->static_mesh_updated || s->mesh_state[slot].build_type == SR_BUILD_STATIC; }
-    if (s->built) {
-        bool instanced = false;
-        for (const auto& in : s->fid.instances) if (in.mesh_slot == slot) { instanced = true; break; }
-        if (instanced) { s->mesh_state[slot].dirty = true; s->geometry_stale = true; }
-    }
+    m.host_stale = false; m.last_from_device = false;         // the host copy is the device buffer's contents again
+    mesh_vertices_changed(s, slot);
     const auto t3 = std::chrono::steady_clock::now();
     s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
     s->mu_info.h2d_ms = ms_between(t1, t2);
+    return SR_OK;
+}
+
+// The same for vertices that are already on the scene's device (work on `stream` produced them): no host round trip. Every
+// refusal the host can decide comes before anything is launched, and a pointer the runtime does not report as memory of this
+// device, `n_vertices` records long, is never handed to a kernel. The positions are validated on the device (vertex_check_kernel,
+// the host call's rule), and only then is the mesh's buffer written: check, 4-byte read-back, copy. The host copy is left
+// behind (HostMesh::host_stale) and fetched by whatever host code reads it next.
+int sr_scene_update_mesh_device(SrScene* s, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, void* stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t slot = 0;
+    int rc = check_mesh_update(s, key, d_vertices, n_vertices, &slot);
+    if (rc != SR_OK) return rc;
+    srh::HostMesh& m = s->meshes[slot];
+    const size_t bytes = sizeof(SrVertex) * (size_t)n_vertices;
+    const uintptr_t a = (uintptr_t)d_vertices, own = (uintptr_t)m.d_vertices;
+    if (a & 15u) return fail(SR_ERR_INVALID_ARG, "update_mesh: the device vertex pointer is not 16-byte aligned");
+    if (a < own + bytes && own < a + bytes) return fail(SR_ERR_INVALID_ARG, "update_mesh: the device vertices overlap the mesh's own vertex buffer");
+    if ((rc = check_emissive_list(m)) != SR_OK) return rc;
+    if ((rc = bind_device(s)) != SR_OK) return rc;
+    {
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof(attr));
+        void* base = nullptr;
+        size_t size = 0;
+        bool ok = hipPointerGetAttributes(&attr, d_vertices) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == s->device;
+        ok = ok && hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)d_vertices) == hipSuccess &&
+             a >= (uintptr_t)base && a - (uintptr_t)base <= size && bytes <= size - (a - (uintptr_t)base);
+        if (!ok) {
+            (void)hipGetLastError();                          // an address the runtime does not know leaves its error behind
+            return fail(SR_ERR_INVALID_ARG, "update_mesh: the vertex pointer is not device memory of the scene's device for that many vertices");
+        }
+    }
+    if ((rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = s->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    if (timed) (void)hipEventRecord(ev[0], st);
+    uint32_t first_bad = 0xFFFFFFFFu;
+    int e = srk_vertex_check(d_vertices, n_vertices, (uint32_t*)s->d_vertex_check.p, st);
+    if (e == 0) e = (int)hipMemcpyAsync(&first_bad, s->d_vertex_check.p, 4, hipMemcpyDeviceToHost, st);
+    if (timed) (void)hipEventRecord(ev[1], st);
+    if (e == 0) e = (int)hipStreamSynchronize(st);
+    float ms = 0.0f;
+    const double check_ms = (timed && e == 0 && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ? (double)ms : 0.0;
+    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("update_mesh: vertex validation failed: ") + hipGetErrorString((hipError_t)e));
+    if (first_bad < n_vertices) return fail_non_finite_vertex(first_bad);
+    m.check_ms = check_ms;
+    const auto t1 = std::chrono::steady_clock::now();
+    if ((rc = take_device_vertices(s, slot, d_vertices, s->device)) != SR_OK) return rc;
+    const auto t2 = std::chrono::steady_clock::now();
+    mesh_vertices_changed(s, slot);
+    const auto t3 = std::chrono::steady_clock::now();
+    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
+    s->mu_info.h2d_ms = ms_between(t1, t2);
+    return SR_OK;
+}
+
+int sr_scene_mesh_vertex_info(const SrScene* s, uint64_t key, SrMeshVertexInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_vertex_info: null argument");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_vertex_info: no mesh is registered under this key");
+    const srh::HostMesh& m = s->meshes[it->second];
+    memset(out, 0, sizeof(*out));
+    out->host_stale = m.host_stale ? 1u : 0u; out->last_from_device = m.last_from_device ? 1u : 0u; out->host_fetches = m.host_fetches;
+    out->check_ms = m.check_ms; out->copy_ms = m.copy_ms; out->fetch_ms = m.fetch_ms;
     return SR_OK;
 }
 
@@ -804,7 +930,10 @@ uint32_t depth_for(uint64_t n_items) {       // ... with slack for SAH splits (t
 // Object-space tree of one mesh (OpType::SlowBuild of a BLAS, blas.rs:178): same builder, same triangle padding. With `bake` the
 // positions are first taken to world space by that transform (transform_point's operation order, as the one-level form flattens):
 // the private copy an instance gets whose transform cannot be inverted (see two_level_build).
-int build_blas(const srh::HostMesh& mesh, uint32_t mesh_slot, const SrTransform* bake, SrScene::HostBlas& b) {
+int build_blas(SrScene* s, uint32_t mesh_slot, const SrTransform* bake, SrScene::HostBlas& b) {
+    const int rc = fetch_host_vertices(s, mesh_slot);
+    if (rc != SR_OK) return rc;
+    const srh::HostMesh& mesh = s->meshes[mesh_slot];
     const uint32_t n = mesh.n_indices / 3;
     std::vector<float> pos((size_t)mesh.n_vertices * 3);
     for (uint32_t i = 0; i < mesh.n_vertices; i++) {
@@ -871,7 +1000,7 @@ int build_blas(const srh::HostMesh& mesh, uint32_t mesh_slot, const SrTransform*
 int rebuild_mesh_tree(SrScene* s, uint32_t m) {
     SrScene::MeshState& ms = s->mesh_state[m];
     ms.tree = SrScene::HostBlas();
-    int rc = build_blas(s->meshes[m], m, nullptr, ms.tree);
+    int rc = build_blas(s, m, nullptr, ms.tree);
     if (rc != SR_OK) return rc;
     s->mu_info.blas_rebuilt++; s->mu_info.blas_build_ms += ms.tree.build_ms;
     ms.rebuilt_now = true; ms.refit_pending = false;
@@ -1051,7 +1180,7 @@ constexpr uint32_t kBlasDeviceMinTris = 0xFFFFFFFFu;
 // which rounds up to 32 768, and every measured size above that is now built on the device: the rule yields 32 768.
 constexpr uint32_t kBlasDeviceMinTrisBounded = 32768;
 constexpr uint32_t kBlasStackCap = 26;       // build_blas's limit: leaves the top-level tree at least 18 of the kTlStackCap entries
-static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshUpdateInfo) == 64 && sizeof(SrTreeHeightInfo) == 32, "layouts the harness relies on");
+static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshUpdateInfo) == 64 && sizeof(SrTreeHeightInfo) == 32 && sizeof(SrMeshVertexInfo) == 40, "layouts the harness relies on");
 uint32_t blas_device_min_tris(const SrScene* s) { return s->height_bound == SR_HEIGHT_BOUND_REBALANCE ? kBlasDeviceMinTrisBounded : kBlasDeviceMinTris; }
 
 // Blas::rebuild (blas.rs:285-310) on the device for the meshes of `set` (pending updatable meshes whose state asked for
@@ -1283,7 +1412,6 @@ int two_level_build(SrScene* s, bool list_changed) {
     uint32_t blas_stack = 0;
     for (size_t i = 0; i < ni; i++) {
         const srh::HostInstance& in = s->fid.instances[i];
-        const srh::HostMesh& mesh = s->meshes[in.mesh_slot];
         const SrScene::HostBlas& b = s->mesh_state[in.mesh_slot].tree;
         if (!b.valid) { if ((rc = rebuild_mesh_tree(s, in.mesh_slot)) != SR_OK) return rc; s->blas_device_current = false; }
         srd::DevTlInstance& r = recs[i];
@@ -1300,7 +1428,7 @@ int two_level_build(SrScene* s, bool list_changed) {
             r.w2o[0] = r.w2o[5] = r.w2o[10] = 1.0f;
             r.flags = 1u;
             baked.emplace_back();
-            if ((rc = build_blas(mesh, in.mesh_slot, &in.o2w, baked.back())) != SR_OK) return rc;
+            if ((rc = build_blas(s, in.mesh_slot, &in.o2w, baked.back())) != SR_OK) return rc;
             baked_inst.push_back((uint32_t)i);
             const SrScene::HostBlas& wb = baked.back();
             bool box_ok = true;
@@ -1722,6 +1850,8 @@ namespace {
 int full_build(SrScene* s) {
     int rc;
     HIP_TRY(hipDeviceSynchronize());
+    for (const auto& in : s->fid.instances)       // the flatten and the record packing below read the host copies
+        if ((rc = fetch_host_vertices(s, in.mesh_slot)) != SR_OK) return rc;
     srh::flatten_instances(s->meshes, s->fid, s->world_tris);
     srh::BvhResult bvh;
     srh::build_bvh(s->world_tris, (uint32_t)srd::kMaxBinaryDepth, bvh);
@@ -2112,3 +2242,18 @@ int sr_host_bvh_get(const SrHostBvh* bvh, const uint32_t** nodes, uint32_t* n_no
 int sr_host_bvh_destroy(SrHostBvh* bvh) { delete reinterpret_cast<SrHostBvhImpl*>(bvh); return SR_OK; }
 
 }  // extern "C"
+
+int srh::scene_take_device_vertices(SrScene* s, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, int src_device) {
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t slot = 0;
+    int rc = check_mesh_update(s, key, d_vertices, n_vertices, &slot);
+    if (rc != SR_OK || (rc = check_emissive_list(s->meshes[slot])) != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
+    const auto t1 = std::chrono::steady_clock::now();
+    if ((rc = take_device_vertices(s, slot, d_vertices, src_device)) != SR_OK) return rc;
+    const auto t2 = std::chrono::steady_clock::now();
+    s->meshes[slot].check_ms = 0.0;                          // validated once, on the first slot
+    mesh_vertices_changed(s, slot);
+    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, std::chrono::steady_clock::now());
+    s->mu_info.h2d_ms = ms_between(t1, t2);
+    return SR_OK;
+}

@@ -88,3 +88,7 @@ int srk_blas_records(const srd::BlasRefitMesh* meshes, uint32_t n_meshes, uint32
 int srk_blas_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
 int srk_blas_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host,
                    uint32_t n_levels, hipStream_t stream);
+
+// sr_scene_update_mesh_device: the lowest index of a vertex with a non-finite position (the host's rule: x, y, z only) into
+// *first_bad (one device word; 0xFFFFFFFF: none), enqueued on `stream`. `vertices` is 16-byte aligned device memory, read once.
+int srk_vertex_check(const SrVertex* vertices, uint32_t n_vertices, uint32_t* first_bad, hipStream_t stream);

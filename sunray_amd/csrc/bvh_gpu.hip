@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <type_traits>
 
@@ -921,9 +922,45 @@ __global__ void blas_build_finish_kernel(const uint32_t* acc, const uint32_t* co
     }
 }
 
+// sr_scene_update_mesh_device's validation: the lowest vertex whose position is not finite under the host's rule (std::isfinite
+// of x, y and z; normals, tangents, uv sets and pad words are free), as the exponent-bits test on the raw words. The source is
+// read once as 16-byte pieces, six per 96-byte vertex, consecutive lanes on consecutive pieces (coalesced dwordx4); the lane
+// whose piece opens a vertex tests its first three words. The grid is a multiple of three blocks of 256, so the stride is a
+// multiple of six pieces: a thread keeps its place inside the vertex over the whole loop and its vertex index advances by a
+// constant. Piece indices are 64-bit (n_vertices * 6 need not fit 32). Every lane keeps its own minimum, the wave reduces once
+// after the loop (cross-lane moves, no LDS) and at most one atomicMin per wave reaches `first_bad` (preset to 0xFFFFFFFF).
+constexpr uint32_t kVertexPieces = sizeof(SrVertex) / 16;
+constexpr uint32_t kVertexCheckBlock = 256, kVertexCheckMaxBlocks = 2046;     // about eight blocks per CU; a multiple of three
+static_assert(sizeof(SrVertex) == 96 && offsetof(SrVertex, position) == 0 && (kVertexCheckBlock * 3) % kVertexPieces == 0 && kVertexCheckMaxBlocks % 3 == 0,
+              "vertex_check_kernel: six pieces per vertex, the position in the first, a stride of whole vertices");
+__global__ void __launch_bounds__(kVertexCheckBlock) vertex_check_kernel(const uint4* pieces, uint64_t n_pieces, uint32_t* first_bad) {
+    const uint32_t t = blockIdx.x * kVertexCheckBlock + threadIdx.x;          // < 2046 * 256
+    const uint32_t stride = gridDim.x * kVertexCheckBlock, v_step = stride / kVertexPieces;
+    const uint32_t exponent = t % kVertexPieces == 0 ? 0x7F800000u : 0u;      // a piece inside a vertex never matches: no branch in the loop
+    uint32_t v = t / kVertexPieces, bad = 0xFFFFFFFFu;
+    for (uint64_t p = t; p < n_pieces; p += stride, v += v_step) {
+        const uint4 w = pieces[p];
+        const bool hit = ((w.x & exponent) == 0x7F800000u) | ((w.y & exponent) == 0x7F800000u) | ((w.z & exponent) == 0x7F800000u);
+        bad = hit ? min(bad, v) : bad;
+    }
+    for (int o = 32; o > 0; o >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, o, 64));
+    if ((threadIdx.x & 63u) == 0 && bad != 0xFFFFFFFFu) atomicMin(first_bad, bad);
+}
+
 }  // namespace srd
 
 using namespace srd;
+
+int srk_vertex_check(const SrVertex* vertices, uint32_t n_vertices, uint32_t* first_bad, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(first_bad, 0xFF, 4, stream);
+    if (e != hipSuccess) return (int)e;
+    if (n_vertices == 0) return 0;
+    const uint64_t n_pieces = (uint64_t)n_vertices * kVertexPieces;
+    const uint64_t want = (n_pieces + kVertexCheckBlock - 1) / kVertexCheckBlock;
+    const uint32_t blocks = want >= kVertexCheckMaxBlocks ? kVertexCheckMaxBlocks : (uint32_t)((want + 2) / 3 * 3);
+    vertex_check_kernel<<<dim3(blocks), dim3(kVertexCheckBlock), 0, stream>>>((const uint4*)vertices, n_pieces, first_bad);
+    return (int)hipGetLastError();
+}
 
 int srk_launch_flatten_slots(float4* tris, const float4* shade, const SrMeshInfo* meshes, const FlatInstance* instances, uint32_t n_tris, hipStream_t stream) {
     if (n_tris == 0) return 0;

@@ -28,6 +28,10 @@ struct HostMesh {
     std::vector<uint32_t> emissive_slots;  // resource_manager.rs:437-446
     void* d_vertices = nullptr;
     void* d_indices = nullptr;
+    // sr_scene_update_mesh_device: `vertices` above is older than d_vertices until fetch_host_vertices (api.cpp) refreshes it
+    bool host_stale = false, last_from_device = false;
+    uint32_t host_fetches = 0;
+    double check_ms = 0.0, copy_ms = 0.0, fetch_ms = 0.0;   // SrMeshVertexInfo
 };
 
 struct HostInstance {
@@ -100,4 +104,7 @@ bool decode_image_rgba8(const uint8_t* data, size_t n, uint32_t& width, uint32_t
 
 // the one thread-local error slot of the library (api.cpp); returns `code`
 int set_error(int code, const std::string& msg);
+// A further replica of a renderer takes vertices that sr_scene_update_mesh_device has validated on `src_device` (api.cpp): the
+// copy into the mesh's allocation (peer copy across devices) and the state of that call, without a second pass over the bytes.
+int scene_take_device_vertices(SrScene* scene, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, int src_device);
 }  // namespace srh

@@ -501,6 +501,18 @@ int sr_renderer_update_mesh(SrRenderer* r, uint64_t key, const SrVertex* vertice
     return SR_OK;
 }
 
+// The same for vertices on the first slot's device: sr_scene_update_mesh_device validates them there, once; the further replicas
+// take the validated bytes straight from the caller's buffer (srh::scene_take_device_vertices: device-to-device or peer copy,
+// the same state), with no host staging. The replicas hold the same meshes, so what the first scene refuses changes none.
+int sr_renderer_update_mesh_device(SrRenderer* r, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "update_mesh: renderer is null");
+    r->instances_valid = false;
+    const std::vector<SrScene*> scenes = srmr::scenes(r);
+    int rc = sr_scene_update_mesh_device(scenes[0], key, d_vertices, n_vertices, stream);
+    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_take_device_vertices(scenes[i], key, d_vertices, n_vertices, r->device);
+    return rc;
+}
+
 // BuildType of a mesh's tree on every replica (the replicas hold the same meshes: one that refuses, refuses first).
 int sr_renderer_set_mesh_build_type(SrRenderer* r, uint64_t key, uint32_t build_type) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_build_type: renderer is null");

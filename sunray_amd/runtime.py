@@ -20,6 +20,21 @@ def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
 
+def _device_vertices(tensor, device_index):
+    """(address, vertex count) of a torch tensor that holds abi.VERTEX records on cuda:`device_index`; ValueError for anything
+    the library would have to refuse or could not read (a CPU tensor, another device, gaps, a size that is no whole vertices)."""
+    if not getattr(tensor, "is_cuda", False):
+        raise ValueError("update_mesh_device: the vertices must be a tensor on the scene's GPU, not host memory")
+    if tensor.device.index != device_index:
+        raise ValueError("update_mesh_device: the tensor is on %s, the scene on cuda:%d" % (tensor.device, device_index))
+    if not tensor.is_contiguous():
+        raise ValueError("update_mesh_device: the tensor must be contiguous")
+    nbytes = tensor.numel() * tensor.element_size()
+    if nbytes == 0 or nbytes % abi.VERTEX.itemsize:
+        raise ValueError("update_mesh_device: %d bytes are not a whole number of %d-byte vertices" % (nbytes, abi.VERTEX.itemsize))
+    return C.c_void_p(tensor.data_ptr()), nbytes // abi.VERTEX.itemsize
+
+
 def camera_matrices(pos, target, fov_y, width, height, prev_view_proj=None):
     """Camera::as_matrices + transposed upload (camera.rs:33-63, lib.rs:1017-1048). Host only."""
     m = abi.SrMatrices()
@@ -206,6 +221,21 @@ class Scene:
         """New vertex contents for a loaded mesh (same count, indices and material); the next set_instances applies it."""
         v = np.ascontiguousarray(vertices, dtype=abi.VERTEX)
         check(lib().sr_scene_update_mesh(self._h, C.c_uint64(key), _p(v), C.c_uint32(len(v))))
+
+    def update_mesh_device(self, key, tensor):
+        """update_mesh for vertices that are on the GPU already: a contiguous torch tensor on the scene's device, of any dtype,
+        whose bytes are the mesh's abi.VERTEX records, produced on torch's current stream (sr_scene_update_mesh_device)."""
+        import torch
+        ptr, n = _device_vertices(tensor, self.device_index)
+        check(lib().sr_scene_update_mesh_device(self._h, C.c_uint64(key), ptr, C.c_uint32(n),
+                                                C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)))
+
+    def mesh_vertex_info(self, key):
+        """-> abi.SrMeshVertexInfo: whether the library's host copy of the mesh's vertices is behind its device buffer, how
+        often it was fetched, and the times of the last update_mesh_device."""
+        info = abi.SrMeshVertexInfo()
+        check(lib().sr_scene_mesh_vertex_info(self._h, C.c_uint64(key), C.byref(info)))
+        return info
 
     def mesh_update_info(self):
         """-> abi.SrMeshUpdateInfo of the last update_mesh and of the set_instances that applied it."""
@@ -704,6 +734,14 @@ class Renderer:
         """New vertex contents for a loaded mesh on every device slot; the next render applies it."""
         v = np.ascontiguousarray(vertices, dtype=abi.VERTEX)
         check(lib().sr_renderer_update_mesh(self._h, C.c_uint64(key), _p(v), C.c_uint32(len(v))))
+
+    def update_mesh_device(self, key, tensor):
+        """update_mesh for a torch tensor on the first slot's GPU (Scene.update_mesh_device): validated once there, copied
+        device to device into every slot's replica (sr_renderer_update_mesh_device)."""
+        import torch
+        ptr, n = _device_vertices(tensor, self.devices[0])
+        check(lib().sr_renderer_update_mesh_device(self._h, C.c_uint64(key), ptr, C.c_uint32(n),
+                                                   C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)))
 
     def set_mesh_build_type(self, key, build_type):
         """abi.BUILD_* of a loaded mesh's tree on every device slot (sr_renderer_set_mesh_build_type)."""
