@@ -830,6 +830,21 @@ int sr_scene_read_tile_row_costs(SrScene* scene, int which, uint32_t width, uint
 int sr_scene_read_tile_costs(SrScene* scene, int which, uint32_t width, uint32_t y0, uint32_t rows, uint32_t* out,
                              uint32_t cap, uint32_t* n_tiles);
 
+/* Test hook: puts a cost map of the caller's in place of the measured one of pass `which` and the launch rectangle of `width`
+ * columns from x0 and `rows` rows from y0 (what the passes clip tile_* of SrRtParams to), and derives the tile schedule from it,
+ * so that the next launch of that pass with that rectangle runs in the order these costs give. costs: n host values, one per
+ * 8x8 tile, row-major as above; n must be the rectangle's tile count. Needs no frame and no earlier launch (the schedule entry
+ * is created as a launch would create it); does not count as a launch for the cadence at which launches re-derive the order.
+ * Waits for the device. */
+int sr_scene_set_tile_costs(SrScene* scene, int which, uint32_t x0, uint32_t width, uint32_t y0, uint32_t rows,
+                            const uint32_t* costs, uint32_t n);
+/* Test hook: the tile order the next launch of pass `which` with that rectangle would run in: 8 lists (one per XCD, i.e. per
+ * column band) of *order_cap entries each, absolute tile indices (tile row * tiles per row + tile column), 0xFFFFFFFF after a
+ * list's last tile. out: cap values, at least 8 * *order_cap (*order_cap is set before that is checked). SR_ERR_STATE while no
+ * order has been derived for that geometry (no launch, no sr_scene_set_tile_costs). Waits for the device. */
+int sr_scene_read_tile_order(SrScene* scene, int which, uint32_t x0, uint32_t width, uint32_t y0, uint32_t rows, uint32_t* out,
+                             uint32_t cap, uint32_t* order_cap);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Tile-parallel rendering across the GPUs of a node                               */
 /* ------------------------------------------------------------------------------------------ */

@@ -11,6 +11,7 @@ NULL_TEXTURE = 0xFFFFFFFF
 TRACE_FLAG_UNCOUNTED = 1
 TRACE_FLAG_TRACE_EVERY_QUERY = 2
 MAX_BOUNCES = 8192          # SR_MAX_BOUNCES
+TILE_ORDER_NONE = 0xFFFFFFFF  # entry of a tile list past its last tile (sr_scene_read_tile_order)
 
 # T1 VertexAttributes (rt_types.slang:24-36) — 96 B
 VERTEX = np.dtype([

@@ -1990,6 +1990,27 @@ int sr_any_hit_ignores(const SrScene* s, const SrHit* hits, uint32_t n, uint32_t
     return SR_OK;
 }
 
+// The tile-schedule entry of pass `which` and launch rectangle (x0, cols, y0 .. y1): the one this geometry already has, or a
+// new one in a free slot / in place of the least recently used entry (costs zeroed on `st`, no order yet). Marks it used now.
+static int schedule_entry(SrScene* s, int which, uint32_t x0, uint32_t cols, uint32_t y0, uint32_t y1, hipStream_t st, SrScene::TileSchedule** out) {
+    SrScene::TileSchedule* sched = nullptr;
+    for (auto& ts : s->schedules) if (ts.which == which && ts.width == cols && ts.x0 == x0 && ts.y0 == y0 && ts.y1 == y1) sched = &ts;
+    if (!sched) {
+        if (s->schedules.size() < 8) s->schedules.emplace_back();
+        sched = &s->schedules[0];
+        for (auto& ts : s->schedules) if (ts.which < 0 || ts.last_use < sched->last_use) sched = &ts;
+        if (sched->which >= 0) HIP_TRY(hipDeviceSynchronize());            // recycling an entry a launch on ANY stream may still read
+        const size_t bytes = (size_t)srk_pass_tile_count(cols, y1 - y0) * 4;
+        int rc;
+        if ((rc = sched->cost.reserve(bytes)) != SR_OK || (rc = sched->order.reserve((size_t)srk_pass_order_cap(cols, y1 - y0) * 8 * 4)) != SR_OK) return rc;
+        HIP_TRY(hipMemsetAsync(sched->cost.p, 0, bytes, st));
+        sched->which = which; sched->width = cols; sched->x0 = x0; sched->y0 = y0; sched->y1 = y1; sched->have_order = false; sched->uses = 0;
+    }
+    sched->last_use = ++s->schedule_clock;
+    *out = sched;
+    return SR_OK;
+}
+
 static int run_pass(const SrRtParams* p, int which, void* stream) {
     const char* name = which == 0 ? "raytracing_ris" : "raytracing_final";
     if (!p || !p->scene) return fail(SR_ERR_INVALID_ARG, std::string(name) + ": params or scene is null");
@@ -2047,18 +2068,7 @@ static int run_pass(const SrRtParams* p, int which, void* stream) {
     // tile schedule of this launch geometry: order from the previous launch's costs, costs of this launch for the next
     SrScene::TileSchedule* sched = nullptr;
     if (s->tile_scheduling) {
-        for (auto& ts : s->schedules) if (ts.which == which && ts.width == cols && ts.x0 == x0 && ts.y0 == y0 && ts.y1 == y1) sched = &ts;
-        if (!sched) {
-            if (s->schedules.size() < 8) s->schedules.emplace_back();
-            sched = &s->schedules[0];
-            for (auto& ts : s->schedules) if (ts.which < 0 || ts.last_use < sched->last_use) sched = &ts;
-            if (sched->which >= 0) HIP_TRY(hipDeviceSynchronize());            // recycling an entry a launch on ANY stream may still read
-            const size_t bytes = (size_t)srk_pass_tile_count(cols, y1 - y0) * 4;
-            if ((rc = sched->cost.reserve(bytes)) != SR_OK || (rc = sched->order.reserve((size_t)srk_pass_order_cap(cols, y1 - y0) * 8 * 4)) != SR_OK) return rc;
-            HIP_TRY(hipMemsetAsync(sched->cost.p, 0, bytes, st));
-            sched->which = which; sched->width = cols; sched->x0 = x0; sched->y0 = y0; sched->y1 = y1; sched->have_order = false; sched->uses = 0;
-        }
-        sched->last_use = ++s->schedule_clock;
+        if ((rc = schedule_entry(s, which, x0, cols, y0, y1, st, &sched)) != SR_OK) return rc;
         a.tile_cost = (uint32_t*)sched->cost.p;
         a.tile_order = sched->have_order ? (const uint32_t*)sched->order.p : nullptr;
     }
@@ -2117,6 +2127,51 @@ int sr_scene_read_tile_costs(SrScene* s, int which, uint32_t width, uint32_t y0,
     if (rc != SR_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, sched->cost.p, (size_t)n_tiles * 4, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+// Test hooks of the tile schedule: the pass path's only input the caller cannot steer is the measured cost the order is derived
+// from. The first puts a cost map of the caller's in its place (and derives the order from it, as run_pass does after a launch),
+// the second reads the order the next launch of that geometry would run in. Neither needs a frame or a pass launch.
+static int check_schedule_rect(const char* name, SrScene* s, int which, uint32_t x0, uint32_t width, uint32_t y0, uint32_t rows) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, std::string(name) + ": scene is null");
+    if (which != 0 && which != 1) return fail(SR_ERR_INVALID_ARG, std::string(name) + ": which must be 0 (raytracing_ris) or 1 (raytracing_final)");
+    if (width == 0 || rows == 0) return fail(SR_ERR_INVALID_ARG, std::string(name) + ": empty launch rectangle");
+    // run_pass clips its rectangle to an image of fewer than 2^31 pixels
+    if (((uint64_t)x0 + width) * ((uint64_t)y0 + rows) >= (1ull << 31)) return fail(SR_ERR_INVALID_ARG, std::string(name) + ": launch rectangle outside any image the passes accept");
+    if (!s->tile_scheduling) return fail(SR_ERR_STATE, std::string(name) + ": tile scheduling is disabled (SR_TILE_SCHEDULING=0)");
+    return SR_OK;
+}
+
+int sr_scene_set_tile_costs(SrScene* s, int which, uint32_t x0, uint32_t width, uint32_t y0, uint32_t rows, const uint32_t* costs, uint32_t n) {
+    int rc = check_schedule_rect("sr_scene_set_tile_costs", s, which, x0, width, y0, rows);
+    if (rc != SR_OK) return rc;
+    if (!costs) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_tile_costs: costs is null");
+    if (n != srk_pass_tile_count(width, rows)) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_tile_costs: n is not the number of 8x8 tiles of the rectangle");
+    if ((rc = bind_device(s)) != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());                                    // a launch on any stream may still write the costs or read the order
+    SrScene::TileSchedule* sched = nullptr;
+    if ((rc = schedule_entry(s, which, x0, width, y0, y0 + rows, nullptr, &sched)) != SR_OK) return rc;
+    HIP_TRY(hipMemcpy(sched->cost.p, costs, (size_t)n * 4, hipMemcpyHostToDevice));
+    int e = srk_launch_tile_order((const uint32_t*)sched->cost.p, (uint32_t*)sched->order.p, width, rows, nullptr);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("sr_scene_set_tile_costs tile schedule: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipDeviceSynchronize());                                    // ... and the next launch may be on any stream
+    sched->have_order = true;                                           // sched->uses stays: an injected map is no launch
+    return SR_OK;
+}
+
+int sr_scene_read_tile_order(SrScene* s, int which, uint32_t x0, uint32_t width, uint32_t y0, uint32_t rows, uint32_t* out, uint32_t cap, uint32_t* order_cap) {
+    int rc = check_schedule_rect("sr_scene_read_tile_order", s, which, x0, width, y0, rows);
+    if (rc != SR_OK) return rc;
+    if (!out || !order_cap) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_tile_order: null argument");
+    SrScene::TileSchedule* sched = nullptr;
+    for (auto& ts : s->schedules) if (ts.which == which && ts.width == width && ts.x0 == x0 && ts.y0 == y0 && ts.y1 == y0 + rows) sched = &ts;
+    if (!sched || !sched->have_order) return fail(SR_ERR_STATE, "sr_scene_read_tile_order: no order derived for this pass and geometry yet");
+    *order_cap = srk_pass_order_cap(width, rows);
+    if (cap < (uint64_t)*order_cap * 8) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_tile_order: output too small");
+    if ((rc = bind_device(s)) != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, sched->order.p, (size_t)*order_cap * 8 * 4, hipMemcpyDeviceToHost));
     return SR_OK;
 }
 

@@ -331,6 +331,25 @@ class Scene:
                                              C.c_uint32(len(out)), C.byref(n)))
         return out[:n.value]
 
+    def set_tile_costs(self, which, x0, width, y0, rows, costs):
+        """Test hook: injects per-tile costs (uint32, row-major, one per 8x8 tile) for pass `which` and the launch rectangle of
+        `width` columns from x0 and `rows` rows from y0; the next launch of that geometry runs in the order derived from them
+        (sr_scene_set_tile_costs)."""
+        c = None if costs is None else np.ascontiguousarray(costs, dtype=np.uint32).reshape(-1)
+        check(lib().sr_scene_set_tile_costs(self._h, C.c_int(which), C.c_uint32(x0), C.c_uint32(width), C.c_uint32(y0), C.c_uint32(rows),
+                                            None if c is None else _p(c), C.c_uint32(0 if c is None else len(c))))
+        return self
+
+    def tile_order(self, which, x0, width, y0, rows):
+        """Test hook -> ([8, order_cap] uint32, order_cap): the tile lists of the eight column bands the next launch of that
+        geometry would read, abi.TILE_ORDER_NONE after a list's last tile (sr_scene_read_tile_order)."""
+        tiles_x, tiles_y = (width + 7) // 8, (rows + 7) // 8
+        out = np.zeros(8 * max(tiles_x, 1) * max(tiles_y, 1), dtype=np.uint32)      # a band is never wider than the rectangle
+        cap = C.c_uint32()
+        check(lib().sr_scene_read_tile_order(self._h, C.c_int(which), C.c_uint32(x0), C.c_uint32(width), C.c_uint32(y0), C.c_uint32(rows),
+                                             _p(out), C.c_uint32(len(out)), C.byref(cap)))
+        return out[:8 * cap.value].reshape(8, cap.value).copy(), cap.value
+
     def set_instancing(self, mode):
         """Form of the acceleration structure at the next set_instances: "auto" | "flat" | "two_level" (sr_scene_set_instancing)."""
         check(lib().sr_scene_set_instancing(self._h, C.c_uint32({"auto": 0, "flat": 1, "two_level": 2}[mode])))
