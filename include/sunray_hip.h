@@ -477,6 +477,51 @@ typedef struct SrMeshVertexInfo {
     double fetch_ms;           /* the last host fetch (wall clock) */
 } SrMeshVertexInfo;            /* 40 bytes */
 int sr_scene_mesh_vertex_info(const SrScene* scene, uint64_t key, SrMeshVertexInfo* out);
+/* Skinning (glTF 2.0 linear blend): the producer of sr_scene_update_mesh_device's vertices that lives in the library. One
+ * influence record per vertex: up to four joints and their weights, used as given (no renormalisation). */
+typedef struct SrSkinInfluence {
+    uint16_t joint[4];
+    float weight[4];
+} SrSkinInfluence;             /* 24 bytes */
+/* Attaches a rig to a loaded mesh: snapshots the mesh's CURRENT device vertices as the bind pose (a device-to-device copy the
+ * mesh owns; waits for the device) and uploads `influences` (HOST pointer, n_vertices records). Refused with
+ * SR_ERR_INVALID_ARG before anything is touched: a null scene, an unknown key, another vertex count than the mesh's,
+ * n_joints == 0, and, with a message that names the lowest offending vertex, a joint index >= n_joints on an influence whose
+ * weight is not 0, a weight that is negative or not finite, a vertex whose four weights are all 0. influences == NULL detaches
+ * the skin and frees its buffers (n_vertices and n_joints are not looked at); sr_scene_remove frees them too. Later
+ * sr_scene_update_mesh* calls do not move the bind pose; attaching again snapshots it anew. */
+int sr_scene_set_mesh_skin(SrScene* scene, uint64_t key, const SrSkinInfluence* influences, uint32_t n_vertices, uint32_t n_joints);
+/* Poses a skinned mesh: uploads `joint_matrices` (HOST pointer, n_joints rows of 3x4, object space of the mesh) asynchronously
+ * on `stream`, runs the skinning kernel from the bind pose and the influences into a scratch buffer the scene owns, and hands
+ * that buffer on as sr_scene_update_mesh_device does its caller's: the posed vertices are applied by the next
+ * sr_scene_set_instances, with the same SR_ERR_STATE window, the same stale host copy and the same emissive handling. The
+ * finite-position check (x, y, z of the posed position; nothing else is looked at) is part of the kernel: on a bad vertex the
+ * call returns sr_scene_update_mesh's status and text with the lowest offending index, and the scene is exactly as it was
+ * (only SrMeshSkinInfo.first_bad tells). Refused on the host before anything is launched: a null scene or matrices, an unknown
+ * key, a mesh with no skin, another n_joints than the skin's (SR_ERR_INVALID_ARG), an emissive list that is not one per
+ * triangle (SR_ERR_UNSUPPORTED).
+ * The arithmetic, fp32 under the numerics contract (no contraction, correctly rounded divide and sqrt, left to right), per
+ * vertex with bind position (x, y, z), bind normal n, bind tangent (t, w), joints j_k and weights w_k, k = 0..3:
+ *   B[r][c]   = 0.0f, then for k = 0, 1, 2, 3 in order, where w_k != 0:  B[r][c] = B[r][c] + w_k * M[j_k][r][c]      (r < 3, c < 4;
+ *               an influence with w_k == 0 is skipped: its matrix is never read, so a NaN in it or an index past the rig is free)
+ *   position' = ((B[r][0] * x + B[r][1] * y) + B[r][2] * z) + B[r][3]
+ *   C         = the cofactor matrix of B's 3x3 part, its rows the cross products a1 x a2, a2 x a0, a0 x a1 of B's rows a_r, with
+ *               a x b = (a.y * b.z - a.z * b.y,  a.z * b.x - a.x * b.z,  a.x * b.y - a.y * b.x)
+ *   normal'   = normalise((C[r][0] * n.x + C[r][1] * n.y) + C[r][2] * n.z)       (correct under non-uniform scale; a reflection
+ *               turns the normal with the winding)
+ *   tangent'  = (normalise((B[r][0] * t.x + B[r][1] * t.y) + B[r][2] * t.z), w)
+ *   normalise(v) = v * (1.0f / sqrt((v.x * v.x + v.y * v.y) + v.z * v.z)); where that squared length is 0 or not finite, the
+ *               bind pose's bytes are written for that vector.
+ * Every other byte of the record (the five uv sets, the pads) is the bind pose's. */
+int sr_scene_skin_mesh(SrScene* scene, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream);
+typedef struct SrMeshSkinInfo {
+    uint32_t n_joints;         /* joints of the attached skin; 0: the mesh has none */
+    uint32_t skinned;          /* poses taken since the skin was attached */
+    uint32_t first_bad;        /* the last sr_scene_skin_mesh: lowest vertex posed to a non-finite position, 0xFFFFFFFF: none */
+    uint32_t _pad;
+    double skin_ms;            /* the last accepted pose: kernel + 4-byte read-back (events, only while sr_scene_enable_timing is on) */
+} SrMeshSkinInfo;              /* 24 bytes */
+int sr_scene_mesh_skin_info(const SrScene* scene, uint64_t key, SrMeshSkinInfo* out);
 /* BuildType of one mesh's tree (blas.rs:149-161: RapidlyChanging and SometimesChanges are built with ALLOW_UPDATE, Static is not).
  * Every loaded mesh starts as SR_BUILD_STATIC (Renderer::load_mesh, lib.rs:937): it is never refitted, every update rebuilds its
  * tree on the host. An updatable mesh holds an SrAsState of its own (reset to sr_as_state_initial(build_type) by this call), driven
@@ -779,6 +824,47 @@ int sr_gltf_sampler(const SrGltf* gltf, uint32_t i, SrSamplerDesc* out);
  * resource_manager.rs:128-136,393), source image}. */
 int sr_gltf_texture(const SrGltf* gltf, uint32_t i, int32_t* sampler, uint32_t* source);
 
+/* Rig and animation of the file (glTF 2.0 skins and animations). sr_gltf_open returns for every file what it returned before
+ * these existed; skins and animations are parsed and validated when one of the calls below first asks for them, and a malformed
+ * one is reported by that call (SR_ERR_INVALID_ARG, or SR_ERR_UNSUPPORTED where stated), never by sr_gltf_open. Pointers handed
+ * out stay valid until sr_gltf_close. */
+int sr_gltf_rig_counts(const SrGltf* gltf, uint32_t* n_skins, uint32_t* n_animations);
+/* The skin of blas i: that of the first node that instances it (*skin_index = -1, *influences = NULL: none), and one
+ * SrSkinInfluence per vertex of sr_gltf_blas, in its order, from JOINTS_0 (u8 / u16) and WEIGHTS_0 (f32, or normalised u8 / u16
+ * divided by 255 / 65535 in fp32), as given: nothing is renormalised or checked against the skin's joint count
+ * (sr_scene_set_mesh_skin does that). SR_ERR_UNSUPPORTED: a primitive instanced by nodes with different skins, JOINTS_1 /
+ * WEIGHTS_1 present, WEIGHTS_0 without JOINTS_0 or the reverse. */
+int sr_gltf_blas_skin(const SrGltf* gltf, uint32_t blas_index, int32_t* skin_index, const SrSkinInfluence** influences, uint32_t* n_vertices);
+/* Skin i: its joint count, the inverse bind matrices (n_joints rows of 3x4; identity where the file has no accessor) and the
+ * node index of every joint. */
+int sr_gltf_skin(const SrGltf* gltf, uint32_t i, uint32_t* n_joints, const SrTransform** inverse_bind, const uint32_t** joint_nodes);
+/* Animation i: its name ("" when the file gives none), the last key time of its samplers, and the number of channels the file
+ * lists. `weights` channels (morph targets) are among them but are not sampled: sr_gltf_animation_ignored_channels counts them. */
+int sr_gltf_animation(const SrGltf* gltf, uint32_t i, const char** name, float* duration_seconds, uint32_t* n_channels);
+int sr_gltf_animation_ignored_channels(const SrGltf* gltf, uint32_t i, uint32_t* n_weights_channels);
+/* The file's nodes at `time_seconds` of animation `animation` (-1: the file's static pose, time ignored): the world transform
+ * of every instance of sr_gltf_instance, in its order, into instance_transforms (n_instances, may be NULL), and the joint matrices
+ * of skin `skin` into joint_matrices (that skin's n_joints, may be NULL; `skin` is not looked at then).
+ * Sampling: every translation / rotation / scale channel at time_seconds clamped to its sampler's first / last key; STEP and LINEAR
+ * (rotations: spherical linear interpolation along the shorter arc between the normalised keys, the result normalised), computed
+ * in double from the fp32 keys and rounded once to fp32 TRS; a CUBICSPLINE sampler anywhere in the animation: SR_ERR_UNSUPPORTED.
+ * Composition: a node with an animated channel composes from its TRS (the file's, or the glTF defaults) even if the file gave it a
+ * `matrix`; local and world matrices are composed as the load composes them, in fp32 and in the same order, so the static pose
+ * returns the transforms of sr_gltf_instance bit for bit.
+ * Joint matrices: inverse(world(mesh node)) * world(joint node) * inverseBind, multiplied left to right in fp32 by the load's
+ * matrix product, where the mesh node is the first instanced node that names the skin and the inverse is the double-precision
+ * inverse of the two-level form's instance records rounded to fp32 (a singular mesh-node transform: SR_ERR_UNSUPPORTED). Posing
+ * the mesh's vertices with them and keeping the instance's own transform gives the world-space result of the glTF specification,
+ * in which a skinned mesh's node transform does not count. */
+int sr_gltf_pose(const SrGltf* gltf, int32_t animation, float time_seconds, SrTransform* instance_transforms, uint32_t skin,
+                 SrTransform* joint_matrices);
+/* The translation, rotation (x, y, z, w) and scale that sr_gltf_pose composes node `node` from at that time: the sampled values
+ * of its animated channels (*animated: bit 0 translation, bit 1 rotation, bit 2 scale; may be NULL), the file's (or the glTF
+ * defaults) for the others. For a node without an animated channel that is informative only: such a node composes from its
+ * `matrix` where the file gives one. */
+int sr_gltf_sample_node(const SrGltf* gltf, int32_t animation, float time_seconds, uint32_t node, float translation[3], float rotation[4],
+                        float scale[3], uint32_t* animated);
+
 /* What Renderer::load_gltf / load_scene return (lib.rs:779-846): the asset group and the scene's instances
  * grouped per BLAS key in BLAS order. Keys are ResourceKey{group, index} packed as group << 32 | index
  * (lib.rs:54-58); BLASes take indices 0..n-1, images the following ones (resource_manager.rs:400-410). */
@@ -798,6 +884,20 @@ int sr_renderer_update_mesh(SrRenderer* renderer, uint64_t key, const SrVertex* 
  * there; every further slot's replica takes the vertices by a device-to-device (peer) copy into its own allocation and ends in
  * the same state. A refusal changes no replica. */
 int sr_renderer_update_mesh_device(SrRenderer* renderer, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, void* stream);
+/* sr_scene_set_mesh_skin / sr_scene_skin_mesh through the facade: the rig is attached on the first device slot's scene only and
+ * the mesh is posed there, once; every further slot's replica takes the validated posed vertices from that scene's scratch
+ * buffer by a device-to-device (peer) copy, as with sr_renderer_update_mesh_device. A refusal changes no replica. */
+int sr_renderer_set_mesh_skin(SrRenderer* renderer, uint64_t key, const SrSkinInfluence* influences, uint32_t n_vertices, uint32_t n_joints);
+int sr_renderer_skin_mesh(SrRenderer* renderer, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream);
+/* Attaches the rig of every skinned blas of a loaded scene (sr_gltf_blas_skin, sr_gltf_skin -> sr_renderer_set_mesh_skin) and
+ * declares those meshes SR_BUILD_RAPIDLY_CHANGING. `gltf` is the file `loaded` was loaded from. sr_renderer_load_scene itself
+ * attaches nothing. */
+int sr_renderer_attach_skins(SrRenderer* renderer, const SrGltf* gltf, const SrLoadedScene* loaded);
+/* One frame of an animation for a loaded scene: for every skinned blas the joint matrices of sr_gltf_pose and
+ * sr_renderer_skin_mesh, then the posed instance transforms into instance_transforms_out (the order and count of
+ * sr_loaded_scene_get's transforms; may be NULL) for the caller's next sr_renderer_render. */
+int sr_renderer_pose_scene(SrRenderer* renderer, const SrGltf* gltf, const SrLoadedScene* loaded, int32_t animation, float time_seconds,
+                           SrTransform* instance_transforms_out, void* stream);
 /* sr_scene_set_mesh_build_type on every device slot's scene. */
 int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t build_type);
 /* sr_scene_set_mesh_tree_build on every device slot's scene. */

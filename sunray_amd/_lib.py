@@ -33,6 +33,9 @@ SYMBOLS = [
     "sr_scene_set_mesh_tree_build", "sr_scene_mesh_tree_info", "sr_renderer_set_mesh_tree_build",
     "sr_scene_set_tree_height_bound", "sr_scene_tree_height_info", "sr_renderer_set_tree_height_bound",
     "sr_scene_update_mesh_device", "sr_scene_mesh_vertex_info", "sr_renderer_update_mesh_device",
+    "sr_scene_set_mesh_skin", "sr_scene_skin_mesh", "sr_scene_mesh_skin_info", "sr_renderer_set_mesh_skin", "sr_renderer_skin_mesh",
+    "sr_gltf_rig_counts", "sr_gltf_blas_skin", "sr_gltf_skin", "sr_gltf_animation", "sr_gltf_animation_ignored_channels", "sr_gltf_pose", "sr_gltf_sample_node",
+    "sr_renderer_attach_skins", "sr_renderer_pose_scene",
 ]
 
 

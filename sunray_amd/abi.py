@@ -166,6 +166,18 @@ class SrMeshVertexInfo(C.Structure):  # one mesh's host copy against its device 
                 ("check_ms", C.c_double), ("copy_ms", C.c_double), ("fetch_ms", C.c_double)]
 
 
+class SrSkinInfluence(C.Structure):  # one vertex's joints and weights (sr_scene_set_mesh_skin), 24 B
+    _fields_ = [("joint", C.c_uint16 * 4), ("weight", C.c_float * 4)]
+
+
+SKIN_INFLUENCE = np.dtype([("joint", "<u2", 4), ("weight", "<f4", 4)])
+assert SKIN_INFLUENCE.itemsize == 24 == C.sizeof(SrSkinInfluence)
+
+
+class SrMeshSkinInfo(C.Structure):  # one mesh's skin and its last pose (sr_scene_mesh_skin_info), 24 B
+    _fields_ = [("n_joints", C.c_uint32), ("skinned", C.c_uint32), ("first_bad", C.c_uint32), ("_pad", C.c_uint32), ("skin_ms", C.c_double)]
+
+
 class SrMeshTreeInfo(C.Structure):  # the mesh-tree builds of the last sr_scene_set_instances (sr_scene_mesh_tree_info)
     _fields_ = [("mode", C.c_uint32), ("auto_threshold", C.c_uint32), ("built_on_device", C.c_uint32), ("built_on_host", C.c_uint32),
                 ("reason", C.c_uint32), ("n_nodes", C.c_uint32), ("max_stack", C.c_uint32), ("_pad", C.c_uint32), ("device_build_ms", C.c_double)]

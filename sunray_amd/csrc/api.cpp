@@ -20,6 +20,7 @@
 #include "bvh_gpu.h"
 #include "bvh_layout.h"
 #include "kernels.h"
+#include "skin.h"
 #include "tl_record.h"
 
 namespace {
@@ -198,6 +199,10 @@ struct SrScene {
         bool refit_pending = false;         // updated (sr_scene_update_mesh) while its tree was valid: the next sr_scene_set_instances refits or rebuilds it
         bool built_once = false, rebuilt_now = false, refit_now = false;
         bool dirty = false;                 // sr_scene_update_mesh: vertices changed since the built structure, which instances it, last took them
+        // sr_scene_set_mesh_skin: the bind pose (a snapshot of the mesh's vertices at the attach) and one SrSkinInfluence per vertex,
+        // owned by the mesh (freed with this record: detach, sr_scene_remove, sr_scene_destroy); n_joints == 0: no skin
+        struct Skin { DeviceBuffer d_bind, d_influences; uint32_t n_joints = 0, skinned = 0, first_bad = 0xFFFFFFFFu; double skin_ms = 0.0; };
+        Skin skin;
     };
     std::vector<MeshState> mesh_state;      // by mesh slot, one per entry of `meshes`: grows in sr_scene_add_blas only
     // device refit of mesh trees: box scratch over d_blas_nodes (allocated at the first refit), and what belongs to the set of
@@ -216,7 +221,8 @@ struct SrScene {
     SrMeshTreeInfo mt_info{};               // mesh-tree builds of the last sr_scene_set_instances
     bool static_mesh_updated = false;       // a Static mesh was updated since the last sr_scene_set_instances (its tree goes to the host)
     DeviceBuffer d_blas_build_out;          // read-back block of a device mesh-tree build
-    DeviceBuffer d_vertex_check;            // the word sr_scene_update_mesh_device's validation kernel answers in
+    DeviceBuffer d_vertex_check;            // the word sr_scene_update_mesh_device's validation kernel and the skinning kernel answer in
+    DeviceBuffer d_skin_out, d_skin_matrices;   // sr_scene_skin_mesh: the posed vertices of the last call (scratch) and its joint matrices
     DeviceBuffer d_blas_nodes, d_tl_inst, d_tl_instances;
     // top level built on the device (bvh_gpu.hip srk_tl_*): per-mesh rows the record kernel reads, the instance boxes, its result block
     DeviceBuffer d_tl_mesh_rows, d_tl_boxes, d_tl_result;
@@ -679,6 +685,117 @@ int sr_scene_mesh_vertex_info(const SrScene* s, uint64_t key, SrMeshVertexInfo* 
     memset(out, 0, sizeof(*out));
     out->host_stale = m.host_stale ? 1u : 0u; out->last_from_device = m.last_from_device ? 1u : 0u; out->host_fetches = m.host_fetches;
     out->check_ms = m.check_ms; out->copy_ms = m.copy_ms; out->fetch_ms = m.fetch_ms;
+    return SR_OK;
+}
+
+// Attaches (or, with influences == NULL, detaches) a mesh's rig. Everything is validated and both buffers are filled before the
+// mesh's record changes, so a refusal or a failed allocation leaves an earlier skin in place.
+int sr_scene_set_mesh_skin(SrScene* s, uint64_t key, const SrSkinInfluence* influences, uint32_t n_vertices, uint32_t n_joints) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "set_mesh_skin: null argument (the scene)");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "set_mesh_skin: no mesh is registered under this key");
+    const uint32_t slot = it->second;
+    const srh::HostMesh& m = s->meshes[slot];
+    int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    if (!influences) {
+        HIP_TRY(hipDeviceSynchronize());
+        s->mesh_state[slot].skin = SrScene::MeshState::Skin();
+        return SR_OK;
+    }
+    char buf[200];
+    if (n_vertices != m.n_vertices) {
+        snprintf(buf, sizeof(buf), "set_mesh_skin: %u influences given, the mesh was loaded with %u vertices", n_vertices, m.n_vertices);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
+    if (n_joints == 0) return fail(SR_ERR_INVALID_ARG, "set_mesh_skin: a skin needs at least one joint (n_joints is 0)");
+    for (uint32_t i = 0; i < n_vertices; i++) {
+        const SrSkinInfluence& f = influences[i];
+        bool any = false;
+        for (int k = 0; k < 4; k++) {
+            if (!std::isfinite(f.weight[k]) || f.weight[k] < 0.0f) {
+                snprintf(buf, sizeof(buf), "set_mesh_skin: vertex %u has a weight that is negative or not finite (weight %d)", i, k);
+                return fail(SR_ERR_INVALID_ARG, buf);
+            }
+            if (f.weight[k] == 0.0f) continue;
+            any = true;
+            if (f.joint[k] >= n_joints) {
+                snprintf(buf, sizeof(buf), "set_mesh_skin: vertex %u names joint %u with a weight that is not 0, the skin has %u joints", i, (unsigned)f.joint[k], n_joints);
+                return fail(SR_ERR_INVALID_ARG, buf);
+            }
+        }
+        if (!any) {
+            snprintf(buf, sizeof(buf), "set_mesh_skin: vertex %u has four weights of 0", i);
+            return fail(SR_ERR_INVALID_ARG, buf);
+        }
+    }
+    SrScene::MeshState::Skin skin;
+    const size_t bytes = sizeof(SrVertex) * (size_t)n_vertices;
+    if ((rc = skin.d_bind.reserve(bytes)) != SR_OK || (rc = skin.d_influences.upload(influences, sizeof(SrSkinInfluence) * (size_t)n_vertices)) != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());                          // whatever still writes the mesh's vertices has finished
+    HIP_TRY(hipMemcpy(skin.d_bind.p, m.d_vertices, bytes, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    skin.n_joints = n_joints;
+    s->mesh_state[slot].skin = std::move(skin);
+    return SR_OK;
+}
+
+// sr_scene_update_mesh_device with the library's own producer in front: matrices up, the kernel (posing and the finite-position
+// check in one pass over the bytes) into the scene's scratch buffer, 4-byte read-back, and from there the path of that call.
+int sr_scene_skin_mesh(SrScene* s, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s || !joint_matrices) return fail(SR_ERR_INVALID_ARG, "skin_mesh: null argument");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "skin_mesh: no mesh is registered under this key");
+    const uint32_t slot = it->second;
+    srh::HostMesh& m = s->meshes[slot];
+    SrScene::MeshState::Skin& skin = s->mesh_state[slot].skin;
+    if (skin.n_joints == 0) return fail(SR_ERR_INVALID_ARG, "skin_mesh: the mesh has no skin (sr_scene_set_mesh_skin attaches one)");
+    if (n_joints != skin.n_joints) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "skin_mesh: %u joint matrices given, the skin was attached with %u joints", n_joints, skin.n_joints);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
+    int rc = check_emissive_list(m);
+    if (rc != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
+    if ((rc = s->d_skin_out.reserve(sizeof(SrVertex) * (size_t)m.n_vertices)) != SR_OK || (rc = s->d_skin_matrices.reserve(sizeof(SrTransform) * (size_t)n_joints)) != SR_OK ||
+        (rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = s->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    int e = (int)hipMemcpyAsync(s->d_skin_matrices.p, joint_matrices, sizeof(SrTransform) * (size_t)n_joints, hipMemcpyHostToDevice, st);
+    if (timed) (void)hipEventRecord(ev[0], st);
+    uint32_t first_bad = 0xFFFFFFFFu;
+    if (e == 0) e = srk_skin((const SrVertex*)skin.d_bind.p, (const SrSkinInfluence*)skin.d_influences.p, (const SrTransform*)s->d_skin_matrices.p,
+                             (SrVertex*)s->d_skin_out.p, m.n_vertices, (uint32_t*)s->d_vertex_check.p, st);
+    if (e == 0) e = (int)hipMemcpyAsync(&first_bad, s->d_vertex_check.p, 4, hipMemcpyDeviceToHost, st);
+    if (timed) (void)hipEventRecord(ev[1], st);
+    if (e == 0) e = (int)hipStreamSynchronize(st);
+    float ms = 0.0f;
+    const double skin_ms = (timed && e == 0 && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ? (double)ms : 0.0;
+    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("skin_mesh: the skinning kernel failed: ") + hipGetErrorString((hipError_t)e));
+    skin.first_bad = first_bad < m.n_vertices ? first_bad : 0xFFFFFFFFu;
+    if (first_bad < m.n_vertices) return fail_non_finite_vertex(first_bad);
+    const auto t1 = std::chrono::steady_clock::now();
+    if ((rc = take_device_vertices(s, slot, (const SrVertex*)s->d_skin_out.p, s->device)) != SR_OK) return rc;
+    const auto t2 = std::chrono::steady_clock::now();
+    m.check_ms = 0.0;                                         // the check is part of the skinning kernel: SrMeshSkinInfo.skin_ms
+    skin.skin_ms = skin_ms; skin.skinned++;
+    mesh_vertices_changed(s, slot);
+    const auto t3 = std::chrono::steady_clock::now();
+    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
+    s->mu_info.h2d_ms = ms_between(t1, t2);
+    return SR_OK;
+}
+
+int sr_scene_mesh_skin_info(const SrScene* s, uint64_t key, SrMeshSkinInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_skin_info: null argument");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_skin_info: no mesh is registered under this key");
+    const SrScene::MeshState::Skin& skin = s->mesh_state[it->second].skin;
+    memset(out, 0, sizeof(*out));
+    out->n_joints = skin.n_joints; out->skinned = skin.skinned; out->first_bad = skin.first_bad; out->skin_ms = skin.skin_ms;
     return SR_OK;
 }
 
@@ -2311,4 +2428,10 @@ int srh::scene_take_device_vertices(SrScene* s, uint64_t key, const SrVertex* d_
     s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, std::chrono::steady_clock::now());
     s->mu_info.h2d_ms = ms_between(t1, t2);
     return SR_OK;
+}
+
+const SrVertex* srh::scene_skinned_vertices(const SrScene* s, uint64_t key, uint32_t* n_vertices) {
+    auto it = s->slots.find(key);
+    *n_vertices = it == s->slots.end() ? 0u : s->meshes[it->second].n_vertices;
+    return (const SrVertex*)s->d_skin_out.p;
 }

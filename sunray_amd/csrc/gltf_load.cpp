@@ -290,6 +290,8 @@ struct GltfTexture { int32_t sampler; uint32_t source; };
 struct GltfScene {
     std::vector<GltfBlas> blases;
     std::vector<std::pair<uint32_t, SrTransform>> instances;   // (blas index, world transform), scene.rs:31-33
+    struct InstanceSource { long node, mesh, primitive; };      // where an instance came from: node, its mesh, index into that mesh's `primitives`
+    std::vector<InstanceSource> instance_sources;               // one per entry of `instances` (the rig read-outs and sr_gltf_pose)
     std::vector<GltfTexture> textures;
     std::vector<SrSamplerDesc> samplers;
     std::vector<DecodedImage> images;
@@ -516,7 +518,7 @@ struct GltfLoader {
         return r;
     }
 
-    struct Primitive { PrimKey key; SrMaterial material; std::vector<SrEmissiveTriangle> local_emissive; };
+    struct Primitive { PrimKey key; SrMaterial material; std::vector<SrEmissiveTriangle> local_emissive; long index = 0; };
 
     bool process_mesh(long mesh_index, std::vector<Primitive>& prims) {
         const Json* mesh = element("meshes", mesh_index);
@@ -531,6 +533,7 @@ struct GltfLoader {
             if (pos_acc < 0) return fail("primitive without POSITION");              // .unwrap() in the reference (:203)
             const long idx_acc = prim.index("indices");
             Primitive p;
+            p.index = (long)pi;
             p.key = PrimKey(pos_acc, idx_acc >= 0 ? idx_acc : i);                    // :207-212
             MaterialInfo mi = material_of(prim);
             p.material = mi.m;
@@ -592,21 +595,19 @@ struct GltfLoader {
         return true;
     }
 
-    static Mat4 node_matrix(const Json& node) {
-        Mat4 r = identity();
-        const Json* m = node.get("matrix");
-        if (m && m->kind == Json::Arr && m->arr.size() == 16) {                      // column-major in the file
-            for (int c = 0; c < 4; c++) for (int row = 0; row < 4; row++) r.m[row * 4 + c] = (float)m->arr[c * 4 + row].num;
-            return r;
-        }
-        float t[3] = {0, 0, 0}, q[4] = {0, 0, 0, 1}, s[3] = {1, 1, 1};
+    // translation, rotation (x, y, z, w) and scale of a node as the file gives them, the glTF defaults where it does not
+    static void node_trs(const Json& node, float t[3], float q[4], float s[3]) {
+        t[0] = t[1] = t[2] = 0.0f; q[0] = q[1] = q[2] = 0.0f; q[3] = 1.0f; s[0] = s[1] = s[2] = 1.0f;
         auto rd = [&](const char* key, float* dst, int n) {
             const Json* a = node.get(key);
             if (a && a->kind == Json::Arr && (int)a->arr.size() == n) for (int i = 0; i < n; i++) dst[i] = (float)a->arr[i].num;
         };
         rd("translation", t, 3); rd("rotation", q, 4); rd("scale", s, 3);
-        // matrix = translation * rotation * scale (gltf/mod.rs:170-172). Quaternion (x,y,z,w) -> rotation as in the
-        // gltf crate's math (cgmath's formula): x2 = x+x, ... ; fp32 throughout.
+    }
+    // matrix = translation * rotation * scale (gltf/mod.rs:170-172). Quaternion (x,y,z,w) -> rotation as in the
+    // gltf crate's math (cgmath's formula): x2 = x+x, ... ; fp32 throughout.
+    static Mat4 trs_matrix(const float t[3], const float q[4], const float s[3]) {
+        Mat4 r = identity();
         const float x = q[0], y = q[1], z = q[2], w = q[3];
         const float x2 = x + x, y2 = y + y, z2 = z + z;
         const float xx2 = x2 * x, xy2 = x2 * y, xz2 = x2 * z, yy2 = y2 * y, yz2 = y2 * z, zz2 = z2 * z;
@@ -616,6 +617,17 @@ struct GltfLoader {
                             xz2 - sy2, yz2 + sx2, 1.0f - xx2 - yy2};
         for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) r.m[i * 4 + j] = R[i * 3 + j] * s[j]; r.m[i * 4 + 3] = t[i]; }
         return r;
+    }
+    static Mat4 node_matrix(const Json& node) {
+        const Json* m = node.get("matrix");
+        if (m && m->kind == Json::Arr && m->arr.size() == 16) {                      // column-major in the file
+            Mat4 r = identity();
+            for (int c = 0; c < 4; c++) for (int row = 0; row < 4; row++) r.m[row * 4 + c] = (float)m->arr[c * 4 + row].num;
+            return r;
+        }
+        float t[3], q[4], s[3];
+        node_trs(node, t, q, s);
+        return trs_matrix(t, q, s);
     }
 
     bool explore(long node_index, const Mat4& parent, int depth) {
@@ -649,11 +661,293 @@ struct GltfLoader {
                 SrTransform t;
                 memcpy(t.m, transform.m, 48);                                        // na_mat4_to_vk_transform (utils.rs:67-74)
                 out.instances.emplace_back(blas_index, t);
+                out.instance_sources.push_back(GltfScene::InstanceSource{node_index, mesh_index, p.index});
             }
         }
         const Json* children = node->get("children");
         for (size_t c = 0; children && c < children->size(); c++)
             if (!explore(children->arr[c].kind == Json::Num && children->arr[c].num >= 0.0 && children->arr[c].num < 2147483648.0 ? (long)children->arr[c].num : -1, transform, depth + 1)) return false;
+        return true;
+    }
+
+    // ---- rig and animation: read when first asked for (sr_gltf_blas_skin, sr_gltf_skin, sr_gltf_animation, sr_gltf_pose) -------
+    // Nothing here runs in sr_gltf_open: a file whose skins or animations are malformed opens as it always did and the call
+    // that asks for them reports the error. The results are kept (the pointers the getters hand out live until sr_gltf_close).
+    struct SkinData { std::vector<SrTransform> inverse_bind; std::vector<uint32_t> joint_nodes; };
+    struct BlasSkin { int32_t skin = -1; std::vector<SrSkinInfluence> influences; };
+    enum { kPathTranslation = 0, kPathRotation = 1, kPathScale = 2 };
+    enum { kLinear = 0, kStep = 1, kCubicSpline = 2 };
+    struct Channel { long node = -1; int path = 0, interpolation = 0; std::vector<float> times, values; };   // values: 3 or 4 floats per key
+    struct Animation { std::string name; float duration = 0.0f; uint32_t n_channels = 0, n_weights_channels = 0; bool cubic = false; std::vector<Channel> channels; };
+    std::map<uint32_t, SkinData> skins;
+    std::map<uint32_t, BlasSkin> blas_skins;
+    std::map<uint32_t, Animation> animations;
+
+    size_t n_nodes() const { const Json* a = doc.get("nodes"); return a ? a->size() : 0; }
+    static long as_index(const Json& j) { return j.kind == Json::Num && j.num >= 0.0 && j.num < 2147483648.0 && j.num == (double)(long)j.num ? (long)j.num : -1; }
+
+    const SkinData* skin_data(uint32_t i) {
+        auto it = skins.find(i);
+        if (it != skins.end()) return &it->second;
+        const Json* sk = element("skins", (long)i);
+        if (!sk) { fail("skin index out of range"); return nullptr; }
+        const Json* joints = sk->get("joints");
+        if (!joints || joints->size() == 0) { fail("skin without joints"); return nullptr; }
+        if (joints->size() > 65536) { fail("skin with more than 65536 joints (JOINTS_0 holds 16-bit indices)", SR_ERR_UNSUPPORTED); return nullptr; }
+        SkinData d;
+        for (const Json& j : joints->arr) {
+            const long n = as_index(j);
+            if (n < 0 || (size_t)n >= n_nodes()) { fail("skin names a joint node that does not exist"); return nullptr; }
+            d.joint_nodes.push_back((uint32_t)n);
+        }
+        SrTransform id;
+        memset(&id, 0, sizeof(id));
+        id.m[0] = id.m[5] = id.m[10] = 1.0f;
+        d.inverse_bind.assign(d.joint_nodes.size(), id);
+        if (sk->has("inverseBindMatrices")) {
+            std::vector<float> m; size_t n = 0;
+            const long acc = sk->index("inverseBindMatrices");
+            const Json* a = element("accessors", acc);
+            if (!a || (int)a->number("componentType", 0) != 5126) { fail("inverseBindMatrices must be a float MAT4 accessor"); return nullptr; }
+            if (!read_floats(acc, 16, m, &n)) return nullptr;
+            if (n < d.joint_nodes.size()) { fail("inverseBindMatrices holds fewer matrices than the skin has joints"); return nullptr; }
+            for (size_t k = 0; k < d.joint_nodes.size(); k++)                    // column-major in the file; the last row (0, 0, 0, 1) is dropped
+                for (int row = 0; row < 3; row++) for (int c = 0; c < 4; c++) d.inverse_bind[k].m[row * 4 + c] = m[k * 16 + c * 4 + row];
+        }
+        return &skins.emplace(i, std::move(d)).first->second;
+    }
+
+    // The skin of a blas is that of the first node that instances it; every other node that instances it must name the same one.
+    const BlasSkin* blas_skin(uint32_t blas) {
+        auto it = blas_skins.find(blas);
+        if (it != blas_skins.end()) return &it->second;
+        if (blas >= out.blases.size()) { fail("blas index out of range"); return nullptr; }
+        BlasSkin r;
+        const GltfScene::InstanceSource* first = nullptr;
+        for (size_t i = 0; i < out.instances.size(); i++) {
+            if (out.instances[i].first != blas) continue;
+            const GltfScene::InstanceSource& src = out.instance_sources[i];
+            const Json* node = element("nodes", src.node);
+            const long sk = node && node->has("skin") ? node->index("skin") : -1;
+            if (node && node->has("skin") && sk < 0) { fail("node with a malformed skin index"); return nullptr; }
+            if (!first) { first = &src; r.skin = (int32_t)sk; }
+            else if (sk != r.skin) { fail("a primitive instanced by nodes with different skins is not supported", SR_ERR_UNSUPPORTED); return nullptr; }
+        }
+        if (!first || r.skin < 0) return &blas_skins.emplace(blas, std::move(r)).first->second;
+        const SkinData* sd = skin_data((uint32_t)r.skin);
+        if (!sd) return nullptr;
+        const Json* mesh = element("meshes", first->mesh);
+        const Json* plist = mesh ? mesh->get("primitives") : nullptr;
+        const Json* attrs = plist && (size_t)first->primitive < plist->size() ? plist->arr[first->primitive].get("attributes") : nullptr;
+        if (!attrs) { fail("skinned primitive without attributes"); return nullptr; }
+        if (attrs->has("JOINTS_1") || attrs->has("WEIGHTS_1")) { fail("more than four influences per vertex (JOINTS_1) are not supported", SR_ERR_UNSUPPORTED); return nullptr; }
+        if (attrs->has("JOINTS_0") != attrs->has("WEIGHTS_0")) { fail("JOINTS_0 and WEIGHTS_0 must come together", SR_ERR_UNSUPPORTED); return nullptr; }
+        if (!attrs->has("JOINTS_0")) { fail("a skinned node's primitive has no JOINTS_0 / WEIGHTS_0"); return nullptr; }
+        const size_t nv = out.blases[blas].vertices.size();
+        View jv;
+        if (!accessor_view(attrs->index("JOINTS_0"), jv)) return nullptr;
+        if (jv.comps != 4 || (jv.comp_type != 5121 && jv.comp_type != 5123)) { fail("JOINTS_0 must be a u8 / u16 VEC4"); return nullptr; }
+        if (jv.count < nv) { fail("JOINTS_0 shorter than POSITION"); return nullptr; }
+        const Json* wa = element("accessors", attrs->index("WEIGHTS_0"));
+        const int wct = wa ? (int)wa->number("componentType", 0) : 0;
+        const Json* wn = wa ? wa->get("normalized") : nullptr;
+        if (wct != 5126 && !((wct == 5121 || wct == 5123) && wn && wn->kind == Json::Bool && wn->b)) { fail("WEIGHTS_0 must be a float or a normalised u8 / u16 VEC4"); return nullptr; }
+        std::vector<float> w; size_t nw = 0;
+        if (!read_floats(attrs->index("WEIGHTS_0"), 4, w, &nw)) return nullptr;       // u8 / 255.0f, u16 / 65535.0f
+        if (nw < nv) { fail("WEIGHTS_0 shorter than POSITION"); return nullptr; }
+        r.influences.resize(nv);
+        for (size_t k = 0; k < nv; k++)
+            for (int c = 0; c < 4; c++) {
+                const uint8_t* p = jv.base + k * jv.stride + (size_t)c * (jv.comp_type == 5121 ? 1 : 2);
+                uint16_t j = p[0];
+                if (jv.comp_type == 5123) memcpy(&j, p, 2);
+                r.influences[k].joint[c] = j;
+                r.influences[k].weight[c] = w[4 * k + c];
+            }
+        return &blas_skins.emplace(blas, std::move(r)).first->second;
+    }
+
+    const Animation* animation(uint32_t i) {
+        auto it = animations.find(i);
+        if (it != animations.end()) return &it->second;
+        const Json* an = element("animations", (long)i);
+        if (!an) { fail("animation index out of range"); return nullptr; }
+        Animation r;
+        const Json* name = an->get("name");
+        if (name && name->kind == Json::Str) r.name = name->str;
+        const Json* chans = an->get("channels");
+        const Json* samps = an->get("samplers");
+        r.n_channels = (uint32_t)(chans ? chans->size() : 0);
+        for (size_t c = 0; chans && c < chans->size(); c++) {
+            const Json& ch = chans->arr[c];
+            const Json* target = ch.get("target");
+            const Json* path = target ? target->get("path") : nullptr;
+            if (!target || !path || path->kind != Json::Str) { fail("animation channel without a target path"); return nullptr; }
+            Channel k;
+            if (path->str == "weights") { r.n_weights_channels++; continue; }       // morph targets: ignored, counted
+            if (path->str == "translation") k.path = kPathTranslation;
+            else if (path->str == "rotation") k.path = kPathRotation;
+            else if (path->str == "scale") k.path = kPathScale;
+            else { fail("animation channel with an unknown target path '" + path->str + "'"); return nullptr; }
+            const long si = ch.index("sampler");
+            if (!samps || si < 0 || (size_t)si >= samps->size()) { fail("animation channel refers to a missing sampler"); return nullptr; }
+            const Json& smp = samps->arr[si];
+            const Json* ip = smp.get("interpolation");
+            const std::string mode = ip && ip->kind == Json::Str ? ip->str : "LINEAR";
+            if (mode == "LINEAR") k.interpolation = kLinear;
+            else if (mode == "STEP") k.interpolation = kStep;
+            else if (mode == "CUBICSPLINE") { k.interpolation = kCubicSpline; r.cubic = true; }
+            else { fail("animation sampler with an unknown interpolation '" + mode + "'"); return nullptr; }
+            const Json* ia = element("accessors", smp.index("input"));
+            if (!ia || (int)ia->number("componentType", 0) != 5126) { fail("animation sampler input must be a float SCALAR accessor"); return nullptr; }
+            size_t nt = 0, nv = 0;
+            if (!read_floats(smp.index("input"), 1, k.times, &nt)) return nullptr;
+            if (nt == 0) { fail("animation sampler without keys"); return nullptr; }
+            for (size_t t = 0; t < nt; t++)
+                if (!std::isfinite(k.times[t]) || k.times[t] < 0.0f || (t && !(k.times[t] > k.times[t - 1]))) { fail("animation key times must be finite, not negative and strictly increasing"); return nullptr; }
+            const int comps = k.path == kPathRotation ? 4 : 3;
+            const Json* oa = element("accessors", smp.index("output"));
+            const int oct = oa ? (int)oa->number("componentType", 0) : 0;
+            if (oct != 5126 && k.path != kPathRotation) { fail("animation sampler output of a translation / scale channel must be float"); return nullptr; }
+            if (!read_floats(smp.index("output"), comps, k.values, &nv)) return nullptr;
+            if (nv < nt * (k.interpolation == kCubicSpline ? 3 : 1)) { fail("animation sampler output holds fewer values than its input has keys"); return nullptr; }
+            for (size_t v = 0; v < nt * (size_t)comps * (k.interpolation == kCubicSpline ? 3 : 1); v++)
+                if (!std::isfinite(k.values[v])) { fail("animation sampler output holds a non-finite value"); return nullptr; }
+            r.duration = std::fmax(r.duration, k.times[nt - 1]);
+            if (!target->has("node")) continue;                                   // a channel without a target node is ignored (glTF 2.0 §5.6)
+            k.node = target->index("node");
+            if (k.node < 0 || (size_t)k.node >= n_nodes()) { fail("animation channel targets a node that does not exist"); return nullptr; }
+            r.channels.push_back(std::move(k));
+        }
+        return &animations.emplace(i, std::move(r)).first->second;
+    }
+
+    // One channel at `time` (clamped to the first / last key), in double from the fp32 keys, rounded once: out[3] or out[4].
+    // Rotations: spherical linear interpolation along the shorter arc between the normalised keys; every sampled rotation is normalised.
+    static void sample_channel(const Channel& k, double time, float* out) {
+        const int comps = k.path == kPathRotation ? 4 : 3;
+        const size_t n = k.times.size();
+        size_t i = 0;
+        double u = 0.0;
+        if (time <= (double)k.times[0]) i = 0;
+        else if (time >= (double)k.times[n - 1]) i = n - 1;
+        else {
+            size_t lo = 0, hi = n - 1;                                            // times[lo] <= time < times[hi]
+            while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if ((double)k.times[mid] <= time) lo = mid; else hi = mid; }
+            i = lo;
+            if (k.interpolation == kLinear) u = (time - (double)k.times[i]) / ((double)k.times[i + 1] - (double)k.times[i]);
+        }
+        double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, r[4];
+        for (int c = 0; c < comps; c++) { a[c] = k.values[i * comps + c]; b[c] = k.values[(u > 0.0 ? i + 1 : i) * comps + c]; }
+        if (k.path != kPathRotation) {
+            for (int c = 0; c < comps; c++) out[c] = (float)(u > 0.0 ? a[c] + u * (b[c] - a[c]) : a[c]);
+            return;
+        }
+        auto normalise = [](double* q) {
+            const double len = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+            if (len > 0.0) for (int c = 0; c < 4; c++) q[c] /= len;
+        };
+        normalise(a);
+        for (int c = 0; c < 4; c++) r[c] = a[c];
+        if (u > 0.0) {
+            normalise(b);
+            if (a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] < 0.0) for (int c = 0; c < 4; c++) b[c] = -b[c];
+            double d2 = 0.0, s2 = 0.0;
+            for (int c = 0; c < 4; c++) { d2 += (a[c] - b[c]) * (a[c] - b[c]); s2 += (a[c] + b[c]) * (a[c] + b[c]); }
+            const double theta = 2.0 * std::atan2(std::sqrt(d2), std::sqrt(s2));  // the angle between the two unit quaternions, well conditioned at 0
+            if (theta < 1e-9) for (int c = 0; c < 4; c++) r[c] = a[c] + u * (b[c] - a[c]);
+            else {
+                const double wa = std::sin((1.0 - u) * theta) / std::sin(theta), wb = std::sin(u * theta) / std::sin(theta);
+                for (int c = 0; c < 4; c++) r[c] = wa * a[c] + wb * b[c];
+            }
+            normalise(r);
+        }
+        for (int c = 0; c < 4; c++) out[c] = (float)r[c];
+    }
+
+    // The inverse of an affine 3x4 transform as the two-level form inverts instance transforms (tl_record.h): cofactors and
+    // determinant in double, rounded once to fp32. false: singular or not finite.
+    static bool invert_affine(const float* M, float* inv) {
+        const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
+        const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+        const double det = a00 * c00 + a01 * c01 + a02 * c02;
+        const double id = 1.0 / det;
+        const double R[9] = {c00 * id, (a02 * a21 - a01 * a22) * id, (a01 * a12 - a02 * a11) * id,
+                             c01 * id, (a00 * a22 - a02 * a20) * id, (a02 * a10 - a00 * a12) * id,
+                             c02 * id, (a01 * a20 - a00 * a21) * id, (a00 * a11 - a01 * a10) * id};
+        const double T[3] = {M[3], M[7], M[11]};
+        bool finite = std::isfinite(id) && det != 0.0;
+        for (int row = 0; row < 3; row++) {
+            for (int c = 0; c < 3; c++) inv[4 * row + c] = (float)R[3 * row + c];
+            inv[4 * row + 3] = (float)(-(R[3 * row] * T[0] + R[3 * row + 1] * T[1] + R[3 * row + 2] * T[2]));
+            for (int c = 0; c < 4; c++) finite = finite && std::isfinite(inv[4 * row + c]);
+        }
+        return finite;
+    }
+
+    struct NodeTrs { bool animated = false; float t[3], q[4], s[3]; };
+    // The TRS every node composes from at `time_seconds` of animation `anim` (-1: nothing is animated): animated nodes only.
+    bool sample_nodes(long anim, float time_seconds, std::vector<NodeTrs>& trs, std::vector<uint32_t>* masks) {
+        trs.assign(n_nodes(), NodeTrs());
+        if (masks) masks->assign(n_nodes(), 0u);
+        if (anim < 0) return true;
+        const Animation* a = animation((uint32_t)anim);
+        if (!a) return false;
+        if (a->cubic) return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED);
+        if (!std::isfinite(time_seconds)) return fail("the time of a pose must be finite");
+        for (const Channel& k : a->channels) {
+            NodeTrs& n = trs[k.node];
+            if (!n.animated) { node_trs(*element("nodes", k.node), n.t, n.q, n.s); n.animated = true; }   // from TRS even where the file gave a matrix
+            sample_channel(k, (double)time_seconds, k.path == kPathTranslation ? n.t : k.path == kPathRotation ? n.q : n.s);
+            if (masks) (*masks)[k.node] |= 1u << k.path;
+        }
+        return true;
+    }
+    bool globals_from(long node_index, const Mat4& parent, int depth, const std::vector<NodeTrs>& trs, std::vector<Mat4>& global, std::vector<char>& seen) {
+        if (depth > 256) return fail("node hierarchy too deep (cycle?)");
+        const Json* node = element("nodes", node_index);
+        if (!node) return fail("scene refers to a missing node");
+        const Mat4 transform = mul(parent, trs[node_index].animated ? trs_matrix(trs[node_index].t, trs[node_index].q, trs[node_index].s) : node_matrix(*node));
+        global[node_index] = transform; seen[node_index] = 1;
+        const Json* children = node->get("children");
+        for (size_t c = 0; children && c < children->size(); c++)
+            if (!globals_from(as_index(children->arr[c]), transform, depth + 1, trs, global, seen)) return false;
+        return true;
+    }
+
+    // sr_gltf_pose. The hierarchy is walked as `explore` walks it, with the loader's own node_matrix and mul, so the static pose
+    // reproduces the instance transforms of the load bit for bit.
+    bool pose(long anim, float time_seconds, SrTransform* instance_transforms, uint32_t skin, SrTransform* joint_matrices) {
+        std::vector<NodeTrs> trs;
+        if (!sample_nodes(anim, time_seconds, trs, nullptr)) return false;
+        std::vector<Mat4> global(n_nodes(), identity());
+        std::vector<char> seen(n_nodes(), 0);
+        long scene_index = doc.index("scene");
+        if (scene_index < 0) scene_index = 0;
+        const Json* scene = element("scenes", scene_index);
+        const Json* roots = scene ? scene->get("nodes") : nullptr;
+        for (size_t i = 0; roots && i < roots->size(); i++)
+            if (!globals_from(as_index(roots->arr[i]), identity(), 0, trs, global, seen)) return false;
+        if (instance_transforms)
+            for (size_t i = 0; i < out.instance_sources.size(); i++) memcpy(instance_transforms[i].m, global[out.instance_sources[i].node].m, 48);
+        if (!joint_matrices) return true;
+        const SkinData* sd = skin_data(skin);
+        if (!sd) return false;
+        long mesh_node = -1;                                                      // the first instanced node that wears this skin
+        for (size_t i = 0; i < out.instance_sources.size() && mesh_node < 0; i++) {
+            const Json* node = element("nodes", out.instance_sources[i].node);
+            if (node && node->has("skin") && node->index("skin") == (long)skin) mesh_node = out.instance_sources[i].node;
+        }
+        if (mesh_node < 0) return fail("no instanced mesh uses this skin");
+        Mat4 inv = identity();
+        if (!invert_affine(global[mesh_node].m, inv.m)) return fail("the transform of the skinned mesh's node is singular", SR_ERR_UNSUPPORTED);
+        for (size_t k = 0; k < sd->joint_nodes.size(); k++) {
+            if (!seen[sd->joint_nodes[k]]) return fail("a joint node of the skin is not part of the scene");
+            Mat4 ibm = identity();
+            memcpy(ibm.m, sd->inverse_bind[k].m, 48);
+            const Mat4 j = mul(mul(inv, global[sd->joint_nodes[k]]), ibm);      // inverse(global(mesh node)) * global(joint node) * inverseBind
+            memcpy(joint_matrices[k].m, j.m, 48);
+        }
         return true;
     }
 
@@ -717,7 +1011,9 @@ struct GltfLoader {
 
 }  // namespace srh
 
-struct SrGltf { srh::GltfScene scene; };
+// `loader` stays for the rig read-outs and sr_gltf_pose, which parse skins and animations when first asked for: the document
+// always (node hierarchy), the buffers only where the file has skins or animations.
+struct SrGltf { srh::GltfScene& scene; std::unique_ptr<srh::GltfLoader> loader; explicit SrGltf(std::unique_ptr<srh::GltfLoader> l) : scene(l->out), loader(std::move(l)) {} };
 
 namespace srh {
 bool decode_image(const uint8_t* data, size_t n, uint32_t& width, uint32_t& height, uint32_t& channels, std::vector<uint8_t>& pixels, std::string& err) {
@@ -782,11 +1078,12 @@ int sr_decode_image_rgba8(const uint8_t* data, size_t n, uint32_t* width, uint32
 // Gltf::new + create_default_scene + the CPU side of Scene::load_into_gpu
 int sr_gltf_open(const char* path, SrGltf** out) {
     if (!path || !out) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_open: null argument");
-    srh::GltfLoader L;
-    if (!L.open(path) || !L.build()) return srh::set_error(L.err_code, L.err);
-    SrGltf* g = new SrGltf();
-    g->scene = std::move(L.out);
-    *out = g;
+    std::unique_ptr<srh::GltfLoader> L(new srh::GltfLoader());
+    if (!L->open(path) || !L->build()) return srh::set_error(L->err_code, L->err);
+    L->primitive_data_map.clear();
+    L->glb_bin = std::vector<uint8_t>();
+    if (!L->doc.has("skins") && !L->doc.has("animations")) L->buffers = std::vector<std::vector<uint8_t>>();
+    *out = new SrGltf(std::move(L));
     return SR_OK;
 }
 
@@ -843,6 +1140,84 @@ int sr_gltf_texture(const SrGltf* g, uint32_t i, int32_t* sampler, uint32_t* sou
     if (!g || i >= g->scene.textures.size()) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_texture: index out of range");
     if (sampler) *sampler = g->scene.textures[i].sampler;
     if (source) *source = g->scene.textures[i].source;
+    return SR_OK;
+}
+
+// ---- rig and animation read-outs: validated here, when first asked for, never in sr_gltf_open -----------------------------------
+namespace {
+srh::GltfLoader* rig_loader(const SrGltf* g) { g->loader->err.clear(); g->loader->err_code = SR_ERR_INVALID_ARG; return g->loader.get(); }
+}
+
+int sr_gltf_rig_counts(const SrGltf* g, uint32_t* n_skins, uint32_t* n_animations) {
+    if (!g) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_rig_counts: null argument");
+    const Json* sk = g->loader->doc.get("skins");
+    const Json* an = g->loader->doc.get("animations");
+    if (n_skins) *n_skins = (uint32_t)(sk ? sk->size() : 0);
+    if (n_animations) *n_animations = (uint32_t)(an ? an->size() : 0);
+    return SR_OK;
+}
+
+int sr_gltf_blas_skin(const SrGltf* g, uint32_t blas, int32_t* skin_index, const SrSkinInfluence** influences, uint32_t* n_vertices) {
+    if (!g) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_blas_skin: null argument");
+    srh::GltfLoader* L = rig_loader(g);
+    const srh::GltfLoader::BlasSkin* b = L->blas_skin(blas);
+    if (!b) return srh::set_error(L->err_code, "sr_gltf_blas_skin: " + L->err);
+    if (skin_index) *skin_index = b->skin;
+    if (influences) *influences = b->skin >= 0 ? b->influences.data() : nullptr;
+    if (n_vertices) *n_vertices = (uint32_t)g->scene.blases[blas].vertices.size();
+    return SR_OK;
+}
+
+int sr_gltf_skin(const SrGltf* g, uint32_t i, uint32_t* n_joints, const SrTransform** inverse_bind, const uint32_t** joint_nodes) {
+    if (!g) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_skin: null argument");
+    srh::GltfLoader* L = rig_loader(g);
+    const srh::GltfLoader::SkinData* d = L->skin_data(i);
+    if (!d) return srh::set_error(L->err_code, "sr_gltf_skin: " + L->err);
+    if (n_joints) *n_joints = (uint32_t)d->joint_nodes.size();
+    if (inverse_bind) *inverse_bind = d->inverse_bind.data();
+    if (joint_nodes) *joint_nodes = d->joint_nodes.data();
+    return SR_OK;
+}
+
+int sr_gltf_animation(const SrGltf* g, uint32_t i, const char** name, float* duration_seconds, uint32_t* n_channels) {
+    if (!g) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_animation: null argument");
+    srh::GltfLoader* L = rig_loader(g);
+    const srh::GltfLoader::Animation* a = L->animation(i);
+    if (!a) return srh::set_error(L->err_code, "sr_gltf_animation: " + L->err);
+    if (name) *name = a->name.c_str();
+    if (duration_seconds) *duration_seconds = a->duration;
+    if (n_channels) *n_channels = a->n_channels;
+    return SR_OK;
+}
+
+int sr_gltf_animation_ignored_channels(const SrGltf* g, uint32_t i, uint32_t* n_weights_channels) {
+    if (!g || !n_weights_channels) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_animation_ignored_channels: null argument");
+    srh::GltfLoader* L = rig_loader(g);
+    const srh::GltfLoader::Animation* a = L->animation(i);
+    if (!a) return srh::set_error(L->err_code, "sr_gltf_animation_ignored_channels: " + L->err);
+    *n_weights_channels = a->n_weights_channels;
+    return SR_OK;
+}
+
+int sr_gltf_sample_node(const SrGltf* g, int32_t animation, float time_seconds, uint32_t node, float translation[3], float rotation[4], float scale[3], uint32_t* animated) {
+    if (!g || !translation || !rotation || !scale) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_sample_node: null argument");
+    if (animation < -1) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_sample_node: the animation is an index, or -1 for the file's static pose");
+    srh::GltfLoader* L = rig_loader(g);
+    if (node >= L->n_nodes()) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_sample_node: node index out of range");
+    std::vector<srh::GltfLoader::NodeTrs> trs;
+    std::vector<uint32_t> masks;
+    if (!L->sample_nodes(animation, time_seconds, trs, &masks)) return srh::set_error(L->err_code, "sr_gltf_sample_node: " + L->err);
+    if (!trs[node].animated) srh::GltfLoader::node_trs(*L->element("nodes", (long)node), trs[node].t, trs[node].q, trs[node].s);
+    memcpy(translation, trs[node].t, 12); memcpy(rotation, trs[node].q, 16); memcpy(scale, trs[node].s, 12);
+    if (animated) *animated = masks[node];
+    return SR_OK;
+}
+
+int sr_gltf_pose(const SrGltf* g, int32_t animation, float time_seconds, SrTransform* instance_transforms, uint32_t skin, SrTransform* joint_matrices) {
+    if (!g) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_pose: null argument");
+    if (animation < -1) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_pose: the animation is an index, or -1 for the file's static pose");
+    srh::GltfLoader* L = rig_loader(g);
+    if (!L->pose(animation, time_seconds, instance_transforms, skin, joint_matrices)) return srh::set_error(L->err_code, "sr_gltf_pose: " + L->err);
     return SR_OK;
 }
 

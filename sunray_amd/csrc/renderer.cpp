@@ -513,6 +513,73 @@ int sr_renderer_update_mesh_device(SrRenderer* r, uint64_t key, const SrVertex* 
     return rc;
 }
 
+// A mesh's rig lives on the first slot's scene only: that scene poses, the further replicas take the posed vertices.
+int sr_renderer_set_mesh_skin(SrRenderer* r, uint64_t key, const SrSkinInfluence* influences, uint32_t n_vertices, uint32_t n_joints) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "set_mesh_skin: null argument (the renderer)");
+    return sr_scene_set_mesh_skin(srmr::scenes(r)[0], key, influences, n_vertices, n_joints);
+}
+
+// sr_scene_skin_mesh on the first slot's scene, which poses and validates once; the further replicas take the validated bytes from
+// that scene's scratch buffer as they take a caller's in sr_renderer_update_mesh_device. What the first scene refuses changes none.
+int sr_renderer_skin_mesh(SrRenderer* r, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "skin_mesh: null argument (the renderer)");
+    const std::vector<SrScene*> scenes = srmr::scenes(r);
+    int rc = sr_scene_skin_mesh(scenes[0], key, joint_matrices, n_joints, stream);
+    if (rc != SR_OK) return rc;
+    r->instances_valid = false;
+    uint32_t n_vertices = 0;
+    const SrVertex* posed = srh::scene_skinned_vertices(scenes[0], key, &n_vertices);
+    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_take_device_vertices(scenes[i], key, posed, n_vertices, r->device);
+    return rc;
+}
+
+// The rigs of a loaded scene: keys are in blas order (sr_renderer_load_scene), so blas b of the file is loaded->keys[b].
+int sr_renderer_attach_skins(SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls) {
+    if (!r || !g || !ls) return rfail(SR_ERR_INVALID_ARG, "attach_skins: null argument");
+    uint32_t n_blases = 0;
+    int rc = sr_gltf_counts(g, &n_blases, nullptr, nullptr, nullptr, nullptr);
+    if (rc != SR_OK) return rc;
+    if (n_blases != ls->keys.size()) return rfail(SR_ERR_INVALID_ARG, "attach_skins: the loaded scene does not come from this file (another number of meshes)");
+    for (uint32_t b = 0; b < n_blases; b++) {
+        int32_t skin = -1; const SrSkinInfluence* inf = nullptr; uint32_t nv = 0, n_joints = 0;
+        if ((rc = sr_gltf_blas_skin(g, b, &skin, &inf, &nv)) != SR_OK) return rc;
+        if (skin < 0) continue;
+        if ((rc = sr_gltf_skin(g, (uint32_t)skin, &n_joints, nullptr, nullptr)) != SR_OK) return rc;
+        if ((rc = sr_renderer_set_mesh_skin(r, ls->keys[b], inf, nv, n_joints)) != SR_OK) return rc;
+        if ((rc = sr_renderer_set_mesh_build_type(r, ls->keys[b], SR_BUILD_RAPIDLY_CHANGING)) != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+
+int sr_renderer_pose_scene(SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls, int32_t animation, float time_seconds, SrTransform* instance_transforms_out, void* stream) {
+    if (!r || !g || !ls) return rfail(SR_ERR_INVALID_ARG, "pose_scene: null argument");
+    uint32_t n_blases = 0, n_instances = 0;
+    int rc = sr_gltf_counts(g, &n_blases, &n_instances, nullptr, nullptr, nullptr);
+    if (rc != SR_OK) return rc;
+    if (n_blases != ls->keys.size() || n_instances != ls->transforms.size()) return rfail(SR_ERR_INVALID_ARG, "pose_scene: the loaded scene does not come from this file (another number of meshes or instances)");
+    std::vector<SrTransform> posed(n_instances), joints;
+    if ((rc = sr_gltf_pose(g, animation, time_seconds, posed.data(), 0, nullptr)) != SR_OK) return rc;
+    for (uint32_t b = 0; b < n_blases; b++) {
+        int32_t skin = -1; uint32_t n_joints = 0;
+        if ((rc = sr_gltf_blas_skin(g, b, &skin, nullptr, nullptr)) != SR_OK) return rc;
+        if (skin < 0) continue;
+        if ((rc = sr_gltf_skin(g, (uint32_t)skin, &n_joints, nullptr, nullptr)) != SR_OK) return rc;
+        joints.resize(n_joints);
+        if ((rc = sr_gltf_pose(g, animation, time_seconds, nullptr, (uint32_t)skin, joints.data())) != SR_OK) return rc;
+        if ((rc = sr_renderer_skin_mesh(r, ls->keys[b], joints.data(), n_joints, stream)) != SR_OK) return rc;
+    }
+    if (instance_transforms_out) {              // grouped by blas, the order of the file kept within a group (sr_renderer_load_scene)
+        size_t o = 0;
+        for (uint32_t b = 0; b < n_blases; b++)
+            for (uint32_t i = 0; i < n_instances; i++) {
+                uint32_t bi = 0;
+                if ((rc = sr_gltf_instance(g, i, &bi, nullptr)) != SR_OK) return rc;
+                if (bi == b) instance_transforms_out[o++] = posed[i];
+            }
+    }
+    return SR_OK;
+}
+
 // BuildType of a mesh's tree on every replica (the replicas hold the same meshes: one that refuses, refuses first).
 int sr_renderer_set_mesh_build_type(SrRenderer* r, uint64_t key, uint32_t build_type) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_build_type: renderer is null");

@@ -35,6 +35,30 @@ def _device_vertices(tensor, device_index):
     return C.c_void_p(tensor.data_ptr()), nbytes // abi.VERTEX.itemsize
 
 
+def _skin_influences(influences):
+    """The influences of set_mesh_skin as a contiguous abi.SKIN_INFLUENCE array; ValueError for anything else (no conversion: a
+    float array read as records would attach nonsense)."""
+    if not isinstance(influences, np.ndarray) or influences.dtype != abi.SKIN_INFLUENCE:
+        raise ValueError("set_mesh_skin: the influences must be a numpy array of abi.SKIN_INFLUENCE records")
+    if influences.ndim != 1 or len(influences) == 0:
+        raise ValueError("set_mesh_skin: the influences must be one record per vertex, in one dimension (shape %s given)" % (influences.shape,))
+    return np.ascontiguousarray(influences)
+
+
+def _joint_matrices(matrices):
+    """The joint matrices of skin_mesh as a contiguous float32 array of n_joints rows of 3x4 -> (array, n_joints); ValueError for
+    another dtype (no silent narrowing of float64) or shape."""
+    if not isinstance(matrices, np.ndarray) or matrices.dtype not in (np.dtype(np.float32), abi.TRANSFORM):
+        raise ValueError("skin_mesh: the joint matrices must be a numpy float32 array (or abi.TRANSFORM records)")
+    if matrices.dtype == abi.TRANSFORM:
+        ok = matrices.ndim == 1
+    else:
+        ok = (matrices.ndim == 2 and matrices.shape[1] == 12) or (matrices.ndim == 3 and matrices.shape[1:] == (3, 4))
+    if not ok or len(matrices) == 0:
+        raise ValueError("skin_mesh: the joint matrices must be (n_joints, 12) or (n_joints, 3, 4), row-major 3x4 (shape %s given)" % (matrices.shape,))
+    return np.ascontiguousarray(matrices), len(matrices)
+
+
 def camera_matrices(pos, target, fov_y, width, height, prev_view_proj=None):
     """Camera::as_matrices + transposed upload (camera.rs:33-63, lib.rs:1017-1048). Host only."""
     m = abi.SrMatrices()
@@ -235,6 +259,27 @@ class Scene:
         often it was fetched, and the times of the last update_mesh_device."""
         info = abi.SrMeshVertexInfo()
         check(lib().sr_scene_mesh_vertex_info(self._h, C.c_uint64(key), C.byref(info)))
+        return info
+
+    def set_mesh_skin(self, key, influences, n_joints):
+        """Attaches a rig to a loaded mesh: `influences` is one abi.SKIN_INFLUENCE record per vertex; the mesh's current vertices
+        become the bind pose. influences=None detaches it (sr_scene_set_mesh_skin)."""
+        if influences is None:
+            check(lib().sr_scene_set_mesh_skin(self._h, C.c_uint64(key), None, C.c_uint32(0), C.c_uint32(0)))
+            return
+        a = _skin_influences(influences)
+        check(lib().sr_scene_set_mesh_skin(self._h, C.c_uint64(key), _p(a), C.c_uint32(len(a)), C.c_uint32(int(n_joints))))
+
+    def skin_mesh(self, key, joint_matrices):
+        """Poses a skinned mesh on the GPU from its bind pose: `joint_matrices` is a float32 array of the skin's n_joints 3x4
+        matrices. From there on it is an update_mesh_device: the next set_instances applies it (sr_scene_skin_mesh)."""
+        m, n = _joint_matrices(joint_matrices)
+        check(lib().sr_scene_skin_mesh(self._h, C.c_uint64(key), _p(m), C.c_uint32(n), self._stream()))
+
+    def mesh_skin_info(self, key):
+        """-> abi.SrMeshSkinInfo: the joints of the mesh's skin (0: none), the poses taken, the last refusal and kernel time."""
+        info = abi.SrMeshSkinInfo()
+        check(lib().sr_scene_mesh_skin_info(self._h, C.c_uint64(key), C.byref(info)))
         return info
 
     def mesh_update_info(self):
@@ -634,6 +679,105 @@ def gltf_parse(path):
         lib().sr_gltf_close(g)
 
 
+class Gltf:
+    """An open glTF file (sr_gltf_open) for the calls that need it beyond the load: the rig read-outs and pose()."""
+
+    def __init__(self, path):
+        self._h = C.c_void_p()
+        check(lib().sr_gltf_open(path.encode(), C.byref(self._h)))
+        nb, ni = C.c_uint32(), C.c_uint32()
+        check(lib().sr_gltf_counts(self._h, C.byref(nb), C.byref(ni), None, None, None))
+        self.n_blases, self.n_instances = nb.value, ni.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sr_gltf_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def rig_counts(self):
+        """-> (skins, animations) of the file."""
+        ns, na = C.c_uint32(), C.c_uint32()
+        check(lib().sr_gltf_rig_counts(self._h, C.byref(ns), C.byref(na)))
+        return ns.value, na.value
+
+    def blas_skin(self, blas):
+        """-> (skin index or -1, abi.SKIN_INFLUENCE array with one record per vertex of the blas, or None)."""
+        sk, ip, nv = C.c_int32(), C.c_void_p(), C.c_uint32()
+        check(lib().sr_gltf_blas_skin(self._h, C.c_uint32(blas), C.byref(sk), C.byref(ip), C.byref(nv)))
+        return sk.value, (_np_from(ip, nv.value, abi.SKIN_INFLUENCE) if sk.value >= 0 else None)
+
+    def skin(self, i):
+        """-> (inverse bind matrices [n_joints, 12] float32, joint node indices [n_joints] uint32)."""
+        nj, mp, jp = C.c_uint32(), C.c_void_p(), C.c_void_p()
+        check(lib().sr_gltf_skin(self._h, C.c_uint32(i), C.byref(nj), C.byref(mp), C.byref(jp)))
+        return _np_from(mp, nj.value * 12, np.float32).reshape(-1, 12), _np_from(jp, nj.value, np.uint32)
+
+    def animation(self, i):
+        """-> (name, duration in seconds, channels the file lists, of which `weights` channels that are not sampled)."""
+        name, dur, nc, nw = C.c_char_p(), C.c_float(), C.c_uint32(), C.c_uint32()
+        check(lib().sr_gltf_animation(self._h, C.c_uint32(i), C.byref(name), C.byref(dur), C.byref(nc)))
+        check(lib().sr_gltf_animation_ignored_channels(self._h, C.c_uint32(i), C.byref(nw)))
+        return (name.value or b"").decode("utf-8", "replace"), dur.value, nc.value, nw.value
+
+    def pose(self, animation, time_seconds, skin=None):
+        """The file at `time_seconds` of `animation` (-1: its static pose) -> (instance transforms [n_instances, 12] float32, joint
+        matrices [n_joints, 12] float32 of `skin`, or None without one) (sr_gltf_pose)."""
+        xf = np.zeros((max(self.n_instances, 1), 12), dtype=np.float32)
+        joints = None
+        if skin is not None:
+            joints = np.zeros((len(self.skin(skin)[1]), 12), dtype=np.float32)
+        check(lib().sr_gltf_pose(self._h, C.c_int32(animation), C.c_float(time_seconds), _p(xf), C.c_uint32(skin or 0),
+                                 None if joints is None else _p(joints)))
+        return xf[:self.n_instances], joints
+
+
+    def sample_node(self, animation, time_seconds, node):
+        """-> (translation [3], rotation [4], scale [3] float32, mask of the animated channels) node `node` composes from in pose()."""
+        t, q, s, m = np.zeros(3, np.float32), np.zeros(4, np.float32), np.zeros(3, np.float32), C.c_uint32()
+        check(lib().sr_gltf_sample_node(self._h, C.c_int32(animation), C.c_float(time_seconds), C.c_uint32(node), _p(t), _p(q), _p(s), C.byref(m)))
+        return t, q, s, m.value
+
+
+class LoadedScene:
+    """What Renderer.load_scene returns (sr_renderer_load_scene): .group, .instances = [(key, [3x4 transforms])]; kept for
+    Renderer.attach_skins / pose_scene."""
+
+    def __init__(self, handle):
+        self._h = handle
+        group, nk, nt = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        kp, cp, tp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sr_loaded_scene_get(self._h, C.byref(group), C.byref(kp), C.byref(cp), C.byref(nk), C.byref(tp), C.byref(nt)))
+        self.group = group.value
+        self.keys, self.counts = _np_from(kp, nk.value, np.uint64), _np_from(cp, nk.value, np.uint32)
+        self.n_transforms = nt.value
+        self.instances = self.grouped(_np_from(tp, nt.value * 12, np.float32).reshape(-1, 12))
+
+    def grouped(self, transforms):
+        """[n_transforms, 12] in the loaded scene's order -> [(key, [3x4 transforms])], what Renderer.render takes."""
+        inst, o = [], 0
+        for k, c in zip(self.keys, self.counts):
+            inst.append((int(k), [transforms[o + j].copy() for j in range(int(c))]))
+            o += int(c)
+        return inst
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sr_loaded_scene_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _SceneView(Scene):
     """A scene owned by someone else (a renderer's replica): the Scene methods without destroying it."""
 
@@ -762,6 +906,20 @@ class Renderer:
         check(lib().sr_renderer_update_mesh_device(self._h, C.c_uint64(key), ptr, C.c_uint32(n),
                                                    C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)))
 
+    def set_mesh_skin(self, key, influences, n_joints):
+        """Scene.set_mesh_skin on the first device slot's scene, which poses for every slot (sr_renderer_set_mesh_skin)."""
+        if influences is None:
+            check(lib().sr_renderer_set_mesh_skin(self._h, C.c_uint64(key), None, C.c_uint32(0), C.c_uint32(0)))
+            return
+        a = _skin_influences(influences)
+        check(lib().sr_renderer_set_mesh_skin(self._h, C.c_uint64(key), _p(a), C.c_uint32(len(a)), C.c_uint32(int(n_joints))))
+
+    def skin_mesh(self, key, joint_matrices):
+        """Scene.skin_mesh on the first device slot; every further slot takes the posed vertices by a device copy; the next render
+        applies them (sr_renderer_skin_mesh)."""
+        m, n = _joint_matrices(joint_matrices)
+        check(lib().sr_renderer_skin_mesh(self._h, C.c_uint64(key), _p(m), C.c_uint32(n), None))
+
     def set_mesh_build_type(self, key, build_type):
         """abi.BUILD_* of a loaded mesh's tree on every device slot (sr_renderer_set_mesh_build_type)."""
         check(lib().sr_renderer_set_mesh_build_type(self._h, C.c_uint64(key), C.c_uint32(build_type)))
@@ -799,6 +957,24 @@ class Renderer:
             return group.value, inst
         finally:
             lib().sr_loaded_scene_destroy(ls)
+
+    def load_scene(self, gltf):
+        """Renderer::load_scene for an open Gltf -> LoadedScene (sr_renderer_load_scene)."""
+        ls = C.c_void_p()
+        check(lib().sr_renderer_load_scene(self._h, gltf._h, C.byref(ls)))
+        return LoadedScene(ls)
+
+    def attach_skins(self, gltf, loaded):
+        """Attaches the rig of every skinned mesh of a loaded scene and makes those meshes BUILD_RAPIDLY_CHANGING
+        (sr_renderer_attach_skins)."""
+        check(lib().sr_renderer_attach_skins(self._h, gltf._h, loaded._h))
+
+    def pose_scene(self, gltf, loaded, animation, time_seconds):
+        """Poses every skinned mesh of a loaded scene at `time_seconds` of `animation` on the GPU and returns the posed instances,
+        [(key, [3x4 transforms])], for the next render (sr_renderer_pose_scene)."""
+        xf = np.zeros((max(loaded.n_transforms, 1), 12), dtype=np.float32)
+        check(lib().sr_renderer_pose_scene(self._h, gltf._h, loaded._h, C.c_int32(animation), C.c_float(time_seconds), _p(xf), None))
+        return loaded.grouped(xf[:loaded.n_transforms])
 
     def unload_scene(self, group):
         check(lib().sr_renderer_unload_scene(self._h, C.c_uint64(group)))
