@@ -210,7 +210,7 @@ struct Builder {
 // children, then repeatedly replaces the inner child with the largest surface area by that child's two
 // children until it has four (or only leaves are left). Traversal is bound by vector-L1 tag lookups
 // (one per 16-byte gather per lane), so a node is packed into 64 bytes = 4 gathers per step:
-//   [0]  origin.x origin.y origin.z | exponents ex | ey<<8 | ez<<16   (the node's own lower corner, per-axis 2^e grid)
+//   [0]  origin.x origin.y origin.z | 2^ex   (the node's own lower corner, per-axis 2^e grid; 2^ey, 2^ez: last two dwords of [32])
 //   [16] LX LY LZ HX   one dword per plane set: byte c = child c's plane, in grid steps from the origin
 //   [32] HY HZ - -
 //   [48] child[4]      >= 0: node index; < 0: leaf, ~child = (first_triangle << 3) | count
@@ -290,7 +290,7 @@ struct Collapser {
         max_depth = std::max(max_depth, depth);
         uint32_t plane[6 * srl::kPlaneDwords];   // LX LY LZ HX HY HZ, kPlaneDwords dwords each
         for (auto& v : plane) v = 0u;
-        uint32_t exps = 0;
+        uint32_t scale_bits[3] = {0u, 0u, 0u};   // the fp32 number 2^e per axis
         float origin[3] = {0.0f, 0.0f, 0.0f};
         if (n_real > 0) {
             for (int a = 0; a < 3; a++) {
@@ -312,7 +312,7 @@ struct Collapser {
                     e++;
                 }
                 const float scale = std::ldexp(1.0f, e);
-                exps |= (uint32_t)(e + 127) << (8 * a);
+                scale_bits[a] = (uint32_t)(e + 127) << 23;   // e in [-126, 127]: a normal number, the bits of `scale`
                 for (int i = 0; i < W; i++) {
                     uint32_t ql = 255u, qh = 0u;   // inverted box for unused children
                     if (i < nk && real[i]) {
@@ -331,7 +331,7 @@ struct Collapser {
         } else {
             for (int a = 0; a < 3; a++) {
                 for (int d = 0; d < srl::kPlaneDwords; d++) { plane[a * srl::kPlaneDwords + d] = 0xFFFFFFFFu; plane[(3 + a) * srl::kPlaneDwords + d] = 0u; }
-                exps |= 127u << (8 * a);
+                scale_bits[a] = 127u << 23;
             }
         }
         uint32_t below = 0;
@@ -347,7 +347,8 @@ struct Collapser {
             }
         }
         uint32_t* q = &out[self];
-        memcpy(q + 0, origin, 12); q[3] = exps;
+        memcpy(q + 0, origin, 12);
+        for (int a = 0; a < 3; a++) q[srl::kScaleOffset[a]] = scale_bits[a];
         memcpy(q + srl::kPlaneOffset, plane, sizeof(plane));
         memcpy(q + srl::kChildOffset, refs, sizeof(refs));
         return below + (uint32_t)std::max(n_real - 1, 0);

@@ -173,7 +173,7 @@ __global__ void refit_level_kernel(uint32_t* nodes, const Prims prims, float* no
         n_real++;
         for (int a = 0; a < 3; a++) { lo_n[a] = fminf(lo_n[a], lo[c][a]); hi_n[a] = fmaxf(hi_n[a], hi[c][a]); }
     }
-    uint32_t plane[6 * srl::kPlaneDwords], exps = 0;
+    uint32_t plane[6 * srl::kPlaneDwords], scale_bits[3] = {0u, 0u, 0u};   // the fp32 number 2^e per axis
     for (int k = 0; k < 6 * srl::kPlaneDwords; k++) plane[k] = 0u;
     float origin[3] = {0.0f, 0.0f, 0.0f};
     if (n_real > 0) {
@@ -196,7 +196,7 @@ __global__ void refit_level_kernel(uint32_t* nodes, const Prims prims, float* no
                 if (ok) break;
             }
             const float scale = ldexpf(1.0f, e);
-            exps |= (uint32_t)(e + 127) << (8 * a);
+            scale_bits[a] = (uint32_t)(e + 127) << 23;   // e in [-126, 127]: a normal number, the bits of `scale`
             for (int c = 0; c < W; c++) {
                 uint32_t ql = 255u, qh = 0u;   // inverted box for unused children
                 if (real[c]) {
@@ -215,10 +215,11 @@ __global__ void refit_level_kernel(uint32_t* nodes, const Prims prims, float* no
     } else {
         for (int a = 0; a < 3; a++) {
             for (int d = 0; d < srl::kPlaneDwords; d++) { plane[a * srl::kPlaneDwords + d] = 0xFFFFFFFFu; plane[(3 + a) * srl::kPlaneDwords + d] = 0u; }
-            exps |= 127u << (8 * a);
+            scale_bits[a] = 127u << 23;
         }
     }
-    q[0] = __float_as_uint(origin[0]); q[1] = __float_as_uint(origin[1]); q[2] = __float_as_uint(origin[2]); q[3] = exps;
+    q[0] = __float_as_uint(origin[0]); q[1] = __float_as_uint(origin[1]); q[2] = __float_as_uint(origin[2]);
+    q[srl::kScaleOffset[0]] = scale_bits[0]; q[srl::kScaleOffset[1]] = scale_bits[1]; q[srl::kScaleOffset[2]] = scale_bits[2];
     for (int k = 0; k < 6 * srl::kPlaneDwords; k++) q[srl::kPlaneOffset + k] = plane[k];
     float* b = node_box + (size_t)node * 6;
     for (int a = 0; a < 3; a++) { b[a] = lo_n[a]; b[3 + a] = hi_n[a]; }

@@ -137,15 +137,17 @@ constexpr uint32_t kCountAny = 1u, kCountClosest = 1u << 16, kCountReusedAny = 1
 SRD uint32_t counted_any(uint32_t n_q) { return n_q & 0xFFFFu; }
 SRD uint32_t counted_closest(uint32_t n_q) { return (n_q >> 16) & 0x7FFFu; }
 
-// TraceRay of the passes: V bit 0 = traversal statistics, V bit 2 = the two-level form of the structure
+// TraceRay of the passes: V bit 0 = traversal statistics, V bit 2 = the two-level form of the structure. Every query of the passes
+// has tmin = kPassTmin (0.001) and every closest-hit query tmax = kPassTmax (10000): compile-time constants of the traversal, so
+// only an existence query has a bound of its own (`tmax`, ignored for closest-hit queries).
 template <int V, bool ANY>
-SRD bool trace_ray(PixelCtx& cx, bool want, f3 o, f3 d, float tmin, float tmax, TravHit& h) {
-    return traverse_ws<ANY, (V & 1) != 0, (V & 4) != 0>(cx.a.sc, want, o, d, tmin, tmax, h, cx.stack, kPassBlock, cx.st);
+SRD bool trace_ray(PixelCtx& cx, bool want, f3 o, f3 d, float tmax, TravHit& h) {
+    return traverse_ws<ANY, (V & 1) != 0, (V & 4) != 0, true, !ANY>(cx.a.sc, want, o, d, kPassTmin, ANY ? tmax : kPassTmax, h, cx.stack, kPassBlock, cx.st);
 }
 template <int V>
-SRD Payload trace_closest_shaded(PixelCtx& cx, f3 o, f3 d, float tmin, float tmax) {
+SRD Payload trace_closest_shaded(PixelCtx& cx, f3 o, f3 d) {
     TravHit h;
-    trace_ray<V, false>(cx, true, o, d, tmin, tmax, h);
+    trace_ray<V, false>(cx, true, o, d, kPassTmax, h);
     cx.n_q += kCountClosest;
     return shade_hit<(V & 2) != 0, (V & 4) != 0>(cx.a.sc, h);
 }
@@ -156,7 +158,7 @@ SRD float trace_shadow(PixelCtx& cx, f3 o, f3 d, float dist) {
     if (dist > 0.002f) {
         TravHit h;
         cx.n_q += kCountAny;
-        return trace_ray<V, true>(cx, true, o, d, 0.001f, dist - 0.001f, h) ? 1.0f : -1.0f;
+        return trace_ray<V, true>(cx, true, o, d, dist - 0.001f, h) ? 1.0f : -1.0f;
     }
     return -1.0f;
 }
@@ -378,9 +380,9 @@ __global__ void tile_order_kernel(const uint32_t* __restrict__ cost, uint32_t* _
 // One query of the flattened passes: reached by every lane of the wave, `want` = this lane has a ray (counted as the
 // TraceRay it stands for). Returns found / occluded for the lane's own ray.
 template <int V, bool ANY>
-SRD bool ws_query(PixelCtx& cx, bool want, f3 o, f3 d, float tmin, float tmax, TravHit& h) {
+SRD bool ws_query(PixelCtx& cx, bool want, f3 o, f3 d, float tmax, TravHit& h) {
     if (want) cx.n_q += ANY ? kCountAny : kCountClosest;
-    return trace_ray<V, ANY>(cx, want, o, d, tmin, tmax, h);
+    return trace_ray<V, ANY>(cx, want, o, d, tmax, h);
 }
 
 template <int V>
@@ -415,7 +417,7 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void ris_kernel(const Pa
         float virtual_distance = 0.0f;
 
         for (uint32_t vb = 0; vb < a.cfg.virtual_bounces; vb++) {
-            prd = trace_closest_shaded<V>(cx, rayOrigin, rayDir, 0.001f, 10000.0f);
+            prd = trace_closest_shaded<V>(cx, rayOrigin, rayDir);
             // the camera ray's payload, for the final pass: ray_gen_final.slang:80 at bounce 0 is this very query
             if (vb == 0u && a.primary_payload) store_payload(a.primary_payload + pix, prd);
             if (prd.dist < 0.0f) break;
@@ -475,6 +477,11 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void ris_kernel(const Pa
             SrReservoir current_r; zero_reservoir(current_r);
             const uint32_t num_lights = sc.num_lights;
             if (num_lights > 0 && roughness > 0.2f) {
+                // Target function (max component of the unshadowed contribution) of the sample the reservoir holds. The reservoir
+                // weights below need it for a sample whose contribution was evaluated a moment ago from the very same operands
+                // (position and normal as stored, emission of the same light): it is carried along instead of evaluated again.
+                // No sample yet: position and normal are zero, for which eval_unshadowed_light gives exactly 0.
+                float p_hat_held = 0.0f;
                 for (uint32_t i = 0; i < a.cfg.ris_candidates; i++) {
                     uint32_t cand_idx = (uint32_t)(rnd(rng) * (float)num_lights);
                     if (cand_idx > num_lights - 1) cand_idx = num_lights - 1;
@@ -495,13 +502,10 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void ris_kernel(const Pa
                         current_r.light_idx = cand_idx;
                         st3(current_r.light_pos, cand_pos);
                         st3(current_r.light_normal, cand_normal);
+                        p_hat_held = p_hat;
                     }
                 }
-                if (current_r.w_sum > 0.0f) {
-                    const f3 fw = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
-                                                        light_emission(sc, current_r.light_idx), ld3(current_r.light_pos), ld3(current_r.light_normal));
-                    current_r.W = current_r.w_sum / fmaxf(current_r.M * maxc(fw), 0.0001f);
-                }
+                if (current_r.w_sum > 0.0f) current_r.W = current_r.w_sum / fmaxf(current_r.M * p_hat_held, 0.0001f);
                 if (a.frame_count > 0 && prev_valid) {
                     const float ppx = prev_u * (float)W, ppy = prev_v * (float)H;
                     const float j0 = rnd(rng), j1 = rnd(rng);
@@ -521,10 +525,10 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void ris_kernel(const Pa
                             const f3 fh = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
                                                                 light_emission(sc, history_r.light_idx), ld3(history_r.light_pos), ld3(history_r.light_normal));
                             const float hist_rand = rnd(rng);
-                            merge_reservoirs(current_r, history_r, maxc(fh), hist_rand);
-                            const f3 fm = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
-                                                                light_emission(sc, current_r.light_idx), ld3(current_r.light_pos), ld3(current_r.light_normal));
-                            current_r.W = current_r.w_sum / fmaxf(current_r.M * maxc(fm), 0.0001f);
+                            // the merged reservoir holds the history's sample (fh, evaluated with the clamped light index the merge
+                            // copies) or still its own
+                            if (merge_reservoirs(current_r, history_r, maxc(fh), hist_rand)) p_hat_held = maxc(fh);
+                            current_r.W = current_r.w_sum / fmaxf(current_r.M * p_hat_held, 0.0001f);
                         }
                     }
                 }
@@ -550,7 +554,7 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void ris_kernel(const Pa
             const float gi_NdotL = fmaxf(dot3(hit_normal, gi_dir), 0.0f);
             if (gi_NdotL > 0.0f) {
                 const f3 gi_origin = hitPos + hit_normal * 0.001f;
-                prd = trace_closest_shaded<V>(cx, gi_origin, gi_dir, 0.001f, 10000.0f);
+                prd = trace_closest_shaded<V>(cx, gi_origin, gi_dir);
                 f3 sample_pos = splat(0.0f), sample_normal = splat(0.0f), sample_radiance = splat(0.0f);
                 if (prd.dist > 0.0f) {
                     sample_pos = gi_origin + gi_dir * prd.dist;
@@ -667,7 +671,7 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void final_kernel(const 
         // bounce 0 is the query the RIS pass answered for this pixel a moment ago (same camera ray, same structure): with the
         // hand-off buffer the payload is read back instead of traversed and shaded again (launch-uniform condition)
         const bool reuse_primary = bounce == 0 && a.primary_payload != nullptr;
-        if (!reuse_primary) ws_query<V, false>(cx, in_loop, rayOrigin, rayDir, 0.001f, 10000.0f, h);
+        if (!reuse_primary) ws_query<V, false>(cx, in_loop, rayOrigin, rayDir, kPassTmax, h);
         bool do_restir = false, do_nee = false, do_bounce = false;
         f3 hit_normal = splat(0.0f), hit_albedo = splat(0.0f), hitPos = splat(0.0f), V_view = splat(0.0f);
         float roughness = 0.5f, metallic = 0.0f;
@@ -733,7 +737,7 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void final_kernel(const 
                     const f3 fc = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
                                                         light_emission(sc, center_r.light_idx), ld3(center_r.light_pos), ld3(center_r.light_normal));
                     const float cr = rnd(rng);
-                    merge_reservoirs(spatial_r, center_r, maxc(fc), cr);
+                    if (merge_reservoirs(spatial_r, center_r, maxc(fc), cr)) f_y_winner = fc;
                 }
                 const float current_depth = len3(hitPos - origin);                     // :162
                 for (int s = 0; s < 5; s++) {                                          // :164-188 SPATIAL_SAMPLES = 5, RADIUS = 30
@@ -755,12 +759,12 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void final_kernel(const 
                         const f3 fn = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
                                                             light_emission(sc, nr.light_idx), ld3(nr.light_pos), ld3(nr.light_normal));
                         const float nrnd = rnd(rng);
-                        merge_reservoirs(spatial_r, nr, maxc(fn), nrnd);
+                        if (merge_reservoirs(spatial_r, nr, maxc(fn), nrnd)) f_y_winner = fn;
                     }
                 }
                 if (spatial_r.w_sum > 0.0f) {                                          // :190-205
-                    f_y_winner = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
-                                                       light_emission(sc, spatial_r.light_idx), ld3(spatial_r.light_pos), ld3(spatial_r.light_normal));
+                    // f_y_winner: the contribution of the sample spatial_r holds was evaluated when it was merged (fc / fn: same
+                    // operands, light index clamped as the merge copied it); no sample taken = the zero sample, which evaluates to 0
                     spatial_r.W = spatial_r.w_sum / fmaxf(spatial_r.M * maxc(f_y_winner), 1e-3f);
                     spatial_r.W = fminf(spatial_r.W, 50.0f);
                     shadow_dir = ld3(spatial_r.light_pos) - hitPos;
@@ -769,7 +773,7 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void final_kernel(const 
                     if (dot3(hit_normal, shadow_dir) > 0.0f) { di_pending = true; want_di = shadow_dist > 0.002f; }
                 }
             }
-            occ = ws_query<V, true>(cx, want_di, hitPos, shadow_dir, 0.001f, shadow_dist - 0.001f, h);   // :206-212 (origin = bare hitPos)
+            occ = ws_query<V, true>(cx, want_di, hitPos, shadow_dir, shadow_dist - 0.001f, h);   // :206-212 (origin = bare hitPos)
             if (di_pending) {
                 prd.dist = want_di ? (occ ? 1.0f : -1.0f) : -1.0f;
                 if (prd.dist < 0.0f) radiance = radiance + f_y_winner * throughput * spatial_r.W;             // :217-219
@@ -833,7 +837,7 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void final_kernel(const 
                         }
                     }
                 }
-                occ = ws_query<V, true>(cx, want_g, hitPos, gi_spatial_dir, 0.001f, d_new - 0.001f, h);   // :276-286
+                occ = ws_query<V, true>(cx, want_g, hitPos, gi_spatial_dir, d_new - 0.001f, h);   // :276-286
                 if (cand) {
                     prd.dist = want_g ? (occ ? 1.0f : -1.0f) : -1.0f;
                     if (!(prd.dist >= 0.0f)) {                                         // :287
@@ -867,7 +871,7 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void final_kernel(const 
                     }
                 }
             }
-            occ = ws_query<V, true>(cx, want_gif, hitPos, gi_x2_dir, 0.001f, gi_x2_dist - 0.001f, h);   // :309-316
+            occ = ws_query<V, true>(cx, want_gif, hitPos, gi_x2_dir, gi_x2_dist - 0.001f, h);   // :309-316
             if (gif_pending) {
                 prd.dist = want_gif ? (occ ? 1.0f : -1.0f) : -1.0f;
                 if (prd.dist < 0.0f) {                                                 // :321-324
@@ -904,7 +908,7 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void final_kernel(const 
                 cos_theta_surface = fmaxf(dot3(hit_normal, shadow_ray_dir), 0.0f);
                 if (cos_theta_light > 0.0f && cos_theta_surface > 0.0f) { nee_pending = true; want_nee = light_dist > 0.002f; }
             }
-            occ = ws_query<V, true>(cx, want_nee, hitPos, shadow_ray_dir, 0.001f, light_dist - 0.001f, h);   // :363-370
+            occ = ws_query<V, true>(cx, want_nee, hitPos, shadow_ray_dir, light_dist - 0.001f, h);   // :363-370
             if (nee_pending) {
                 prd.dist = want_nee ? (occ ? 1.0f : -1.0f) : -1.0f;
                 if (prd.dist < 0.0f) {                                                 // :375-379

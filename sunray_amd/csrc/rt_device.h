@@ -326,17 +326,20 @@ SRD float gi_target_pdf(f3 shade_pos, f3 shade_normal, f3 albedo, float metallic
     f3 contrib = sample_radiance * f_diffuse * NdotL;
     return maxc(contrib);
 }
-SRD void merge_reservoirs(SrReservoir& r, const SrReservoir& nr, float p_hat_new, float random_val) {
+// (both merges return whether the new sample was taken: the callers then know whose sample the reservoir ends up with, and with it
+// the value of the target function they already evaluated for that sample)
+SRD bool merge_reservoirs(SrReservoir& r, const SrReservoir& nr, float p_hat_new, float random_val) {
     r.M += nr.M;
     float weight = p_hat_new * nr.W * nr.M;
     r.w_sum += weight;
-    if (random_val < (weight / fmaxf(r.w_sum, 0.0001f))) {
+    const bool taken = random_val < (weight / fmaxf(r.w_sum, 0.0001f));
+    if (taken) {
         r.light_idx = nr.light_idx;
         r.light_pos[0] = nr.light_pos[0]; r.light_pos[1] = nr.light_pos[1]; r.light_pos[2] = nr.light_pos[2];
         r.light_normal[0] = nr.light_normal[0]; r.light_normal[1] = nr.light_normal[1]; r.light_normal[2] = nr.light_normal[2];
     }
+    return taken;
 }
-// (returns whether the new sample was taken: the final pass wants to know whose sample its combined reservoir ends up with)
 SRD bool merge_reservoirs_gi(SrReservoirGI& r, const SrReservoirGI& nr, float p_hat_new, float jacobian, float random_val) {
     r.M += nr.M;
     float weight = p_hat_new * nr.W * nr.M * jacobian;

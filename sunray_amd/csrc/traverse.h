@@ -6,9 +6,9 @@
 //   nodes : 4-wide BVH with quantised child boxes, 64 bytes per node = 4 x 16-byte gathers per step
 //           (a step lasts as long as the slowest of its lanes' gathers — under load one of them nearly always misses L2 —
 //           not as long as its tag lookups or its arithmetic: DESIGN.md §5, round-2 experiments):
-//           [0]  origin.xyz | exponents ex | ey<<8 | ez<<16     plane = fmaf(q, 2^e, origin)
+//           [0]  origin.xyz | 2^ex (fp32)                       plane = fmaf(q, 2^e, origin)
 //           [16] LX LY LZ HX   one dword per plane set, byte c = child c
-//           [32] HY HZ - -
+//           [32] HY HZ | 2^ey 2^ez (fp32)
 //           [48] child[4]      >= 0: node index; < 0: leaf, ~child = (first_triangle << 3) | count
 //           The builder rounds lower planes down / upper planes up and verifies them with the same
 //           fmaf, so a decoded box always contains the exact one; unused children decode inverted.
@@ -236,9 +236,20 @@ SRD bool child_hit_tl(const NodePlanesTl& p, float t_lo, float t_hi, float& tnea
     return t0 <= fminf(far, t_hi);
 }
 
+// Lane mask of a condition. A conjunction is spelled ballot(a) & ballot(b): each comparison then lands in a scalar mask and the SALU
+// combines them, while ballot(a && b) makes the compiler turn its combined mask into a 0/1 VGPR and compare that again
+// (v_cndmask + v_cmp_ne per ballot). A ballot only reports active lanes, so the masks are the same under partial exec.
+SRD unsigned long long ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 // Every lane of the wave that is active at the call site takes part; `want` = this lane has a ray of its own.
-template <bool ANY, bool STATS, bool TL = false>
+// FIXED_TMIN / FIXED_TMAX: every ray of the wave has tmin == kPassTmin / tmax == kPassTmax (the caller passes exactly these), as all
+// queries of the two passes / their closest-hit queries do. The bounds (and t_lo) are then literals: they take no registers and do
+// not travel with a stolen ray. The ray-list tracers take both per ray.
+constexpr float kPassTmin = 0.001f, kPassTmax = 10000.0f;
+template <bool ANY, bool STATS, bool TL = false, bool FIXED_TMIN = false, bool FIXED_TMAX = false>
 SRD bool traverse_ws(const DevScene& sc, bool want, f3 o, f3 d, float tmin, float tmax, TravHit& hit, int* lds_col, int stride, TravStats& st) {
+    if (FIXED_TMIN) tmin = kPassTmin;
+    if (FIXED_TMAX) tmax = kPassTmax;
     const float4* __restrict__ nodes = sc.nodes;
     const float4* __restrict__ tris = sc.tris;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -285,17 +296,17 @@ SRD bool traverse_ws(const DevScene& sc, bool want, f3 o, f3 d, float tmin, floa
             // postponed leaf and has arrived at a second one) and only a few lanes still walk: the blocked lanes would wait for them.
             // Progress: an early exit needs a blocked lane, and the triangle phase consumes its leaf.
             {
-                const unsigned long long walking = __builtin_amdgcn_ballot_w64(inner && leaf == 0);
+                const unsigned long long walking = ballot(inner) & ballot(leaf == 0);
                 if (walking == 0ull) break;
                 if ((int)__popcll(walking) <= kEarlyTriWalking &&
-                    (int)__popcll(__builtin_amdgcn_ballot_w64(node != kSentinel && node < 0 && leaf != 0 && (!TL || in_blas))) >= kEarlyTriBlocked) break;
+                    (int)__popcll(ballot(node != kSentinel && node < 0 && (!TL || in_blas)) & ballot(leaf != 0)) >= kEarlyTriBlocked) break;
             }
             const bool idle = node == kSentinel && leaf == 0;
-            const unsigned long long idle_mask = __builtin_amdgcn_ballot_w64(idle);
+            const unsigned long long idle_mask = ballot(node == kSentinel) & ballot(leaf == 0);
             if (idle_mask != 0ull) {
                 // donors: every lane with a node or leaf in hand and a spare stack entry — blocked lanes too (they wait, their subtrees need not)
                 const bool can_give = node != kSentinel && sp > sb;
-                const unsigned long long donor_mask = __builtin_amdgcn_ballot_w64(can_give);
+                const unsigned long long donor_mask = ballot(node != kSentinel) & ballot(sp > sb);
                 if (donor_mask != 0ull) {
                     const uint32_t n = min((uint32_t)__popcll(idle_mask), (uint32_t)__popcll(donor_mask));
                     const uint32_t drank = lanes_below(donor_mask), irank = lanes_below(idle_mask);
@@ -307,7 +318,8 @@ SRD bool traverse_ws(const DevScene& sc, bool want, f3 o, f3 d, float tmin, floa
                     const uint32_t d_root = (uint32_t)__shfl((int)root, dl);
                     const float ox = __shfl(o.x, dl), oy = __shfl(o.y, dl), oz = __shfl(o.z, dl);
                     const float dx = __shfl(d.x, dl), dy = __shfl(d.y, dl), dz = __shfl(d.z, dl);
-                    const float d_tmin = __shfl(tmin, dl), d_tmax = __shfl(tmax, dl), d_cull = __shfl(cull, dl);
+                    const float d_tmin = FIXED_TMIN ? kPassTmin : __shfl(tmin, dl), d_tmax = FIXED_TMAX ? kPassTmax : __shfl(tmax, dl);
+                    const float d_cull = __shfl(cull, dl);
                     // the donor's 1/d comes along as well: three more shuffles instead of three correctly rounded divisions (and
                     // the zero-direction fix-ups) that the WHOLE wave would issue whenever one lane takes work — the exchange runs
                     // in 28 % / 46 % of the node-loop iterations of the RIS / final pass
@@ -370,7 +382,7 @@ SRD bool traverse_ws(const DevScene& sc, bool want, f3 o, f3 d, float tmin, floa
                 const float4 h0 = n[0], q1 = n[1], q2 = n[2], qc = n[3];
                 const int4 child = make_int4(__float_as_int(qc.x), __float_as_int(qc.y), __float_as_int(qc.z), __float_as_int(qc.w));
                 if (STATS) st.boxes += 4;
-                const uint32_t ex = __float_as_uint(h0.w);
+                const float sx = h0.w, sy = q2.z, sz = q2.w;   // the grid scales 2^e
                 const uint32_t LX = __float_as_uint(q1.x), LY = __float_as_uint(q1.y), LZ = __float_as_uint(q1.z);
                 const uint32_t HX = __float_as_uint(q1.w), HY = __float_as_uint(q2.x), HZ = __float_as_uint(q2.y);
                 // The ray's direction signs (the NEAR plane of a slab is the upper one for a negative direction) are re-derived
@@ -384,8 +396,7 @@ SRD bool traverse_ws(const DevScene& sc, bool want, f3 o, f3 d, float tmin, floa
                     p.nx = sgx ? HX : LX; p.fx = sgx ? LX : HX;
                     p.ny = sgy ? HY : LY; p.fy = sgy ? LY : HY;
                     p.nz = sgz ? HZ : LZ; p.fz = sgz ? LZ : HZ;
-                    p.ax = __uint_as_float((ex & 0xFFu) << 23) * rs.inv.x; p.ay = __uint_as_float(((ex >> 8) & 0xFFu) << 23) * rs.inv.y;
-                    p.az = __uint_as_float(((ex >> 16) & 0xFFu) << 23) * rs.inv.z;
+                    p.ax = sx * rs.inv.x; p.ay = sy * rs.inv.y; p.az = sz * rs.inv.z;
                     const float bx = (h0.x - ro.x) * rs.inv.x, by = (h0.y - ro.y) * rs.inv.y, bz = (h0.z - ro.z) * rs.inv.z;
                     p.bnx = bx - pad.x; p.bfx = bx + pad.x; p.bny = by - pad.y; p.bfy = by + pad.y; p.bnz = bz - pad.z; p.bfz = bz + pad.z;
                     // An unused child decodes to an inverted box, which nothing can hit — unless the padding exceeds the node's own
@@ -400,8 +411,7 @@ SRD bool traverse_ws(const DevScene& sc, bool want, f3 o, f3 d, float tmin, floa
                     p.nx = sgx ? HX : LX; p.fx = sgx ? LX : HX;
                     p.ny = sgy ? HY : LY; p.fy = sgy ? LY : HY;
                     p.nz = sgz ? HZ : LZ; p.fz = sgz ? LZ : HZ;
-                    p.ax = __uint_as_float((ex & 0xFFu) << 23) * rs.inv.x; p.ay = __uint_as_float(((ex >> 8) & 0xFFu) << 23) * rs.inv.y;
-                    p.az = __uint_as_float(((ex >> 16) & 0xFFu) << 23) * rs.inv.z;
+                    p.ax = sx * rs.inv.x; p.ay = sy * rs.inv.y; p.az = sz * rs.inv.z;
                     p.bx = (h0.x - o.x) * rs.inv.x; p.by = (h0.y - o.y) * rs.inv.y; p.bz = (h0.z - o.z) * rs.inv.z;
                     b0 = child_hit<0>(p, t_lo, cull, n0);
                     b1 = child_hit<1>(p, t_lo, cull, n1);

@@ -135,8 +135,7 @@ def decode_node(node):
     W, _, po, co = bvh_layout()
     n = np.asarray(node, dtype=np.uint32)
     origin = n[0:3].view(np.float32)
-    ex = int(n[3])
-    scale = np.array([np.uint32(((ex >> (8 * a)) & 0xFF) << 23) for a in range(3)], dtype=np.uint32).view(np.float32)
+    scale = n[[3, 10, 11]].view(np.float32)      # the grid scales 2^e per axis, stored as fp32 (csrc/bvh_layout.h)
     pd = W // 4                      # dwords per plane; planes LX LY LZ HX HY HZ
     lo = np.zeros((W, 3), np.float32)
     hi = np.zeros((W, 3), np.float32)
