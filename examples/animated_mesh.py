@@ -5,13 +5,16 @@ heuristic picks; it is never torn down and rebuilt on the host. The sphere is de
 BuildType of a BLAS that is built with ALLOW_UPDATE): where the scene stands in the two-level form (SR_INSTANCING=two_level, or a
 scene large enough for the automatic choice) its own tree is then refitted on the device as well. Writes the last frame as a PNG.
 
-    python examples/animated_mesh.py [out.png] [--frames 24] [--size 640x480] [--height-bound rebalance] [--device-vertices]
+    python examples/animated_mesh.py [out.png] [--frames 24] [--size 640x480] [--height-bound rebalance] [--device-vertices [--device-lights]]
 
 --height-bound rebalance: a device fast build whose tree comes out taller than the traversal stack allows is rebalanced on the
 device instead of going to the host builder (Renderer.set_tree_height_bound; the default, refuse, is the library's).
 
 --device-vertices: the sphere is deformed with torch ops on the GPU and handed over as a tensor (Renderer.update_mesh_device):
 the vertices never visit the host, the library validates them on the device and copies device to device.
+
+--device-lights (with --device-vertices): the ceiling light ripples too, and the frame's light table is built on the device
+(Renderer.set_light_table_build("device")): the emissive mesh's vertices never visit the host either.
 
 Needs a GPU: the product path has no CPU fallback.
 """
@@ -31,13 +34,18 @@ def main():
     ap.add_argument("--size", default="640x480")
     ap.add_argument("--height-bound", choices=["refuse", "rebalance"], default="refuse")
     ap.add_argument("--device-vertices", action="store_true")
+    ap.add_argument("--device-lights", action="store_true")
     args = ap.parse_args()
+    if args.device_lights and not args.device_vertices:
+        ap.error("--device-lights goes with --device-vertices")
     from sunray_amd import abi, runtime as rt, scenes
     w, h = (int(v) for v in args.size.split("x"))
     desc = scenes.cornell_box()
     sphere = next(m for m in desc.meshes if m.key == 7)
     r = rt.Renderer((w, h))
     r.set_tree_height_bound(args.height_bound)
+    if args.device_lights:
+        r.set_light_table_build("device")
     for m in desc.meshes:
         r.load_mesh(m.key, m.vertices, m.indices, m.material)
     r.set_mesh_build_type(sphere.key, abi.BUILD_RAPIDLY_CHANGING)
@@ -45,7 +53,13 @@ def main():
     if args.device_vertices:
         import torch
         rest = torch.from_numpy(sphere.vertices.view("<f4").reshape(len(sphere.vertices), -1).copy()).to("cuda:0")   # [n, 24] floats: 96-byte records
+        lamp = next(m for m in desc.meshes if m.key == 6)
+        lamp_rest = torch.from_numpy(lamp.vertices.view("<f4").reshape(len(lamp.vertices), -1).copy()).to("cuda:0")
     for f in range(args.frames):
+        if f and args.device_lights:
+            posed = lamp_rest.clone()
+            posed[:, 1] = lamp_rest[:, 1] - 0.05 * (1.0 + torch.sin(lamp_rest[:, 0] * 4.0 + 0.3 * f))      # the light's corners bob below the ceiling
+            r.update_mesh_device(lamp.key, posed)
         if f and args.device_vertices:
             # a ripple along the rest normal, computed where the vertices live; the normals keep their rest direction
             pos, nrm = rest[:, 0:3], rest[:, 4:7]

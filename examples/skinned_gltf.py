@@ -3,7 +3,10 @@ Renderer.attach_skins gives every skinned mesh its bind pose and influences, and
 animation, skins the meshes with the library's kernel (the posed vertices never visit the host) and returns the instance
 transforms for the frame. Writes the last frame as a PNG.
 
-    python examples/skinned_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out skinned.png]
+    python examples/skinned_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out skinned.png] [--device-lights]
+
+--device-lights: the frame's light table is built on the device (Renderer.set_light_table_build("device")), so that a skinned
+mesh with an emissive material never visits the host either.
 
 Default file: tests/golden/skinned_bar.glb. Needs a GPU: the product path has no CPU fallback.
 """
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--size", default="640x480")
     ap.add_argument("--out", default="skinned.png")
     ap.add_argument("--camera", default="0.8,1.4,7.0,0.8,1.0,0.0,45", help="position, target, vertical field of view in degrees")
+    ap.add_argument("--device-lights", action="store_true")
     args = ap.parse_args()
     from sunray_amd import runtime as rt
     w, h = (int(v) for v in args.size.split("x"))
@@ -38,6 +42,8 @@ def main():
     print("%s: %d skin(s), animation %d '%s': %.3f s, %d channel(s)%s" % (
         args.file, n_skins, args.animation, name, duration, n_channels, ", %d morph-target channel(s) ignored" % n_ignored if n_ignored else ""))
     r = rt.Renderer((w, h))
+    if args.device_lights:
+        r.set_light_table_build("device")
     loaded = r.load_scene(gltf)
     r.attach_skins(gltf, loaded)
     instances = loaded.instances

@@ -464,7 +464,8 @@ int sr_scene_mesh_update_info(const SrScene* scene, SrMeshUpdateInfo* out);
  * device-to-device copy). The library's HOST copy of the vertices is not touched and becomes stale; host code that needs it (a
  * host build of the mesh's tree or of the one-level tree) fetches it with one device-to-host copy, the device paths (SR_OP_UPDATE,
  * the device fast build, the device refit and device build of an updatable mesh's tree) never do. A mesh with emissive entries
- * fetches inside the call. A later sr_scene_update_mesh replaces the copy. SrMeshUpdateInfo.validate_copy_ms / h2d_ms: host
+ * fetches inside the call while the scene builds its light table on the host (SR_LIGHTS_HOST, the default), and never under
+ * SR_LIGHTS_DEVICE (sr_scene_set_light_table_build). A later sr_scene_update_mesh replaces the copy. SrMeshUpdateInfo.validate_copy_ms / h2d_ms: host
  * wall clock of the call without, and of, its wait-and-copy section. */
 int sr_scene_update_mesh_device(SrScene* scene, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, void* stream);
 typedef struct SrMeshVertexInfo {
@@ -477,6 +478,48 @@ typedef struct SrMeshVertexInfo {
     double fetch_ms;           /* the last host fetch (wall clock) */
 } SrMeshVertexInfo;            /* 40 bytes */
 int sr_scene_mesh_vertex_info(const SrScene* scene, uint64_t key, SrMeshVertexInfo* out);
+/* Where sr_scene_set_instances builds the frame's light table (one 64-byte record per emissive triangle x instance: the world
+ * vertices, area, normal and emission the passes sample). SR_LIGHTS_HOST (default; SR_LIGHT_TABLE=host|device in the environment
+ * sets the initial mode): host arithmetic over the emissive arena, uploaded whole. SR_LIGHTS_DEVICE: the arena has a device
+ * mirror, the indirection entries are uploaded only when they changed, and a kernel writes the table with the host's arithmetic
+ * operation for operation (the records are equal bit for bit wherever the host's words are not NaN; a zero-area triangle has NaN
+ * normals on both, with the payload of each machine). Under it sr_scene_update_mesh_device and sr_scene_skin_mesh never fetch
+ * the vertices of a mesh with emissive entries: a kernel rewrites the positions of its arena slots from the mesh's device
+ * vertices at the next sr_scene_set_instances. sr_scene_get_tables and a switch back to SR_LIGHTS_HOST read the device arena
+ * back where the host's is older (64 bytes per arena entry, counted in SrLightTableInfo.arena_fetches, not in
+ * SrMeshVertexInfo.host_fetches). A scene whose arena is empty, or that has no instance, builds its one dummy record on the
+ * host in either mode. Unknown mode: SR_ERR_INVALID_ARG. */
+#define SR_LIGHTS_HOST 0u
+#define SR_LIGHTS_DEVICE 1u
+int sr_scene_set_light_table_build(SrScene* scene, uint32_t mode);
+/* The light table of the last sr_scene_set_instances. The kernel times are taken with events, the host time with the wall
+ * clock, all three only while sr_scene_enable_timing is on (0 otherwise). */
+typedef struct SrLightTableInfo {
+    uint32_t mode;               /* SR_LIGHTS_* in force */
+    uint32_t on_device;          /* 1: the table was built by the kernel */
+    uint32_t num_lights;         /* records of the table (the dummy record included) */
+    uint32_t arena_entries;      /* entries of the emissive arena */
+    uint32_t positions_rewritten;/* arena triangles whose positions the device rewrote from device vertices */
+    uint32_t entries_uploaded;   /* 1: the indirection entries differed from the device's copy and were uploaded */
+    uint32_t arena_uploads;      /* 1: host-side changes of the arena (add, remove, sr_scene_update_mesh) were uploaded */
+    uint32_t arena_fetches;      /* device-to-host reads of the device arena since the scene was created (running count) */
+    double positions_ms;         /* the arena-position kernels */
+    double table_ms;             /* the table kernel */
+    double host_ms;              /* the host path: arithmetic + upload */
+} SrLightTableInfo;              /* 56 bytes */
+int sr_scene_light_table_info(const SrScene* scene, SrLightTableInfo* out);
+/* Debug read-back of the device light table (next to sr_scene_read_bvh), whichever mode built it: *n_lights records, of which
+ * the first min(cap_lights, *n_lights) are copied to `out` (may be NULL with cap_lights == 0), 16 floats each in the order the
+ * passes read them:
+ *   [0..2] world v0   [3]  area = 0.5 * |(v1 - v0) x (v2 - v0)|
+ *   [4..6] world v1   [7]  unit normal x
+ *   [8..10] world v2  [11] unit normal y
+ *   [12..14] emission rgb (factor * strength)   [15] unit normal z */
+int sr_scene_read_lights(const SrScene* scene, float* out, uint32_t cap_lights, uint32_t* n_lights);
+/* The host arithmetic of the light table on its own (no scene, no device): out[16 * i ..] from entries[i] = (slot into
+ * `triangles`, index into `transforms`). An entry out of range: SR_ERR_INVALID_ARG, nothing written. */
+int sr_light_table(const SrTransform* transforms, uint32_t n_transforms, const SrEmissiveIndirectionEntry* entries, uint32_t n_entries,
+                   const SrEmissiveTriangle* triangles, uint32_t n_triangles, float* out);
 /* Skinning (glTF 2.0 linear blend): the producer of sr_scene_update_mesh_device's vertices that lives in the library. One
  * influence record per vertex: up to four joints and their weights, used as given (no renormalisation). */
 typedef struct SrSkinInfluence {
@@ -904,6 +947,9 @@ int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t
 int sr_renderer_set_mesh_tree_build(SrRenderer* renderer, uint32_t mode);
 /* sr_scene_set_tree_height_bound on every device slot's scene. */
 int sr_renderer_set_tree_height_bound(SrRenderer* renderer, uint32_t mode, uint32_t mesh_tree_cap);
+/* sr_scene_set_light_table_build on every device slot's scene, and sr_scene_light_table_info of one slot's scene. */
+int sr_renderer_set_light_table_build(SrRenderer* renderer, uint32_t mode);
+int sr_renderer_light_table_info(SrRenderer* renderer, uint32_t slot, SrLightTableInfo* out);
 
 /* Harness access: inner scene (counters, stats), device pointers of the RGBA8 output and the fp32 radiance OF THE LAST
  * SUBMITTED FRAME (valid after sr_renderer_wait_frame of that frame), and relative_frame_count. Any out pointer may be NULL.

@@ -166,6 +166,15 @@ class SrMeshVertexInfo(C.Structure):  # one mesh's host copy against its device 
                 ("check_ms", C.c_double), ("copy_ms", C.c_double), ("fetch_ms", C.c_double)]
 
 
+class SrLightTableInfo(C.Structure):  # the light table of the last sr_scene_set_instances (sr_scene_light_table_info), 56 B
+    _fields_ = [("mode", C.c_uint32), ("on_device", C.c_uint32), ("num_lights", C.c_uint32), ("arena_entries", C.c_uint32),
+                ("positions_rewritten", C.c_uint32), ("entries_uploaded", C.c_uint32), ("arena_uploads", C.c_uint32), ("arena_fetches", C.c_uint32),
+                ("positions_ms", C.c_double), ("table_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+LIGHTS_HOST, LIGHTS_DEVICE = 0, 1
+
+
 class SrSkinInfluence(C.Structure):  # one vertex's joints and weights (sr_scene_set_mesh_skin), 24 B
     _fields_ = [("joint", C.c_uint16 * 4), ("weight", C.c_float * 4)]
 

@@ -20,6 +20,7 @@
 #include "bvh_gpu.h"
 #include "bvh_layout.h"
 #include "kernels.h"
+#include "lights.h"
 #include "skin.h"
 #include "tl_record.h"
 
@@ -203,6 +204,11 @@ struct SrScene {
         // owned by the mesh (freed with this record: detach, sr_scene_remove, sr_scene_destroy); n_joints == 0: no skin
         struct Skin { DeviceBuffer d_bind, d_influences; uint32_t n_joints = 0, skinned = 0, first_bad = 0xFFFFFFFFu; double skin_ms = 0.0; };
         Skin skin;
+        // light table on the device (SR_LIGHTS_DEVICE). arena_stale: the newest positions of this mesh's arena slots exist only on
+        // the device (its d_vertices, and the device arena once arena_pending is served); emissive_tris holds older ones.
+        // arena_pending: emissive_positions_kernel has to rewrite its slots of the device arena before the next table is built.
+        bool arena_stale = false, arena_pending = false;
+        DeviceBuffer d_emissive_slots;      // the mesh's emissive_slots, uploaded at the first such rewrite
     };
     std::vector<MeshState> mesh_state;      // by mesh slot, one per entry of `meshes`: grows in sr_scene_add_blas only
     // device refit of mesh trees: box scratch over d_blas_nodes (allocated at the first refit), and what belongs to the set of
@@ -254,6 +260,20 @@ struct SrScene {
     bool built_once = false;
     bool geometry_stale = false;            // the built structure instances a dirty mesh: it shows stale geometry until the next sr_scene_set_instances
     SrMeshUpdateInfo mu_info{};
+    // Light table on the device. d_arena mirrors emissive_tris (arena_device_entries records). The invariant that keeps an older
+    // host value from overwriting a newer device one: a mesh whose arena_stale is set has its newest vertices in its d_vertices,
+    // so its slots of d_arena are a function of device memory alone; arena_host_dirty (anything wrote emissive_tris since the last
+    // upload: add, host update) re-uploads the WHOLE arena, which also serves a reallocation, and every upload sets arena_pending
+    // on every arena_stale mesh, so the kernel rewrites their slots afterwards. Host code reads the positions of an arena_stale
+    // mesh from emissive_tris only behind refresh_host_arena, which clears the flag.
+    int light_mode = SR_LIGHTS_HOST;        // sr_scene_set_light_table_build / SR_LIGHT_TABLE in the environment
+    DeviceBuffer d_arena, d_light_entries;
+    uint32_t arena_device_entries = 0;
+    bool arena_host_dirty = true;
+    std::vector<SrEmissiveIndirectionEntry> entries_on_device;   // what d_light_entries holds
+    bool lights_on_device = false;          // the last sr_scene_set_instances chose the kernel: upload_instance_tables builds the table from d_arena
+    bool emissive_table_stale = false;      // ... and emissive_table has not been read back from d_arena since (sr_scene_get_tables does)
+    SrLightTableInfo lt_info{};
     int instrumented = 0;
     int timing = 0;
     int n_cus = 256;
@@ -360,11 +380,106 @@ int check_emissive_list(const srh::HostMesh& m) {
     return SR_OK;
 }
 
-// What follows a mesh's new vertices once they are in its device allocation (and, for a mesh with emissive entries, in the
-// host copy): the positions of its arena slots, then which trees and structures are stale.
+// ---- light table on the device (SR_LIGHTS_DEVICE; the invariant is stated at SrScene::light_mode) ---------------------------
+// The device arena brought up to date on the null stream: host-side changes first (the whole arena, which also serves a grown
+// one), then the positions of every pending mesh from its device vertices. The caller has bound the device and synchronises.
+int sync_device_arena(SrScene* s, uint32_t* rewritten, uint32_t* uploaded) {
+    const uint32_t n = (uint32_t)s->emissive_tris.size();
+    int rc;
+    if (s->arena_host_dirty || s->arena_device_entries != n) {
+        if ((rc = s->d_arena.upload(s->emissive_tris.data(), sizeof(SrEmissiveTriangle) * (size_t)n)) != SR_OK) return rc;
+        s->arena_device_entries = n; s->arena_host_dirty = false;
+        for (SrScene::MeshState& ms : s->mesh_state) if (ms.arena_stale) ms.arena_pending = true;   // the upload put older positions in their slots
+        if (uploaded) *uploaded += 1;
+    }
+    for (size_t slot = 0; slot < s->mesh_state.size(); slot++) {
+        SrScene::MeshState& ms = s->mesh_state[slot];
+        if (!ms.arena_pending) continue;
+        const srh::HostMesh& m = s->meshes[slot];
+        const uint32_t n_tris = (uint32_t)m.emissive_slots.size();             // one per triangle in index order (check_emissive_list)
+        if (!ms.d_emissive_slots.p && (rc = ms.d_emissive_slots.upload(m.emissive_slots.data(), sizeof(uint32_t) * (size_t)n_tris)) != SR_OK) return rc;
+        const int e = srk_emissive_positions((const SrVertex*)m.d_vertices, m.n_vertices, (const uint32_t*)m.d_indices, (const uint32_t*)ms.d_emissive_slots.p,
+                                             n_tris, (SrEmissiveTriangle*)s->d_arena.p, n, nullptr);
+        if (e != 0) return fail(SR_ERR_HIP, std::string("arena position launch failed: ") + hipGetErrorString((hipError_t)e));
+        ms.arena_pending = false;
+        if (rewritten) *rewritten += n_tris;
+    }
+    return SR_OK;
+}
+
+// sr_scene_get_tables returns the arena the last sr_scene_set_instances saw: where that table was built on the device, this is
+// the device arena as it stands until something writes it again, read back once (64 bytes per entry, not the vertices).
+int fetch_emissive_table(SrScene* s) {
+    if (!s->emissive_table_stale) return SR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    s->emissive_table.resize(s->arena_device_entries);
+    HIP_TRY(hipMemcpy(s->emissive_table.data(), s->d_arena.p, sizeof(SrEmissiveTriangle) * (size_t)s->arena_device_entries, hipMemcpyDeviceToHost));
+    s->emissive_table_stale = false;
+    s->lt_info.arena_fetches++;
+    return SR_OK;
+}
+
+// Before host code reads emissive_tris (the host light table, a switch to SR_LIGHTS_HOST) or a mesh's slots are freed: the
+// slots of every arena_stale mesh from the device arena, brought up to date first. Nothing to do where no mesh is stale.
+int refresh_host_arena(SrScene* s) {
+    bool any = false;
+    for (const SrScene::MeshState& ms : s->mesh_state) any = any || ms.arena_stale;
+    if (!any) return SR_OK;
+    int rc = fetch_emissive_table(s);                        // what the last sr_scene_set_instances saw, before the arena moves on
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    if ((rc = sync_device_arena(s, nullptr, nullptr)) != SR_OK) return rc;
+    std::vector<SrEmissiveTriangle> dev(s->arena_device_entries);
+    HIP_TRY(hipMemcpy(dev.data(), s->d_arena.p, sizeof(SrEmissiveTriangle) * dev.size(), hipMemcpyDeviceToHost));   // null stream: behind the kernels
+    s->lt_info.arena_fetches++;
+    for (size_t slot = 0; slot < s->mesh_state.size(); slot++) {
+        if (!s->mesh_state[slot].arena_stale) continue;
+        for (uint32_t es : s->meshes[slot].emissive_slots) s->emissive_tris[es] = dev[es];
+        s->mesh_state[slot].arena_stale = false;
+    }
+    return SR_OK;
+}
+
+// The frame's light table by the kernel: arena, entries (only where they differ from the device's copy), table. Null stream,
+// like the other kernels of sr_scene_set_instances, and waited for here: the passes run on streams of their own.
+int device_light_table(SrScene* s) {
+    SrLightTableInfo& li = s->lt_info;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool timed = s->timing != 0;
+    for (hipEvent_t& x : ev) timed = timed && hipEventCreate(&x) == hipSuccess;
+    struct Free { hipEvent_t* ev; ~Free() { for (int i = 0; i < 4; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } free_events{ev};
+    if (timed) (void)hipEventRecord(ev[0], nullptr);
+    int rc = sync_device_arena(s, &li.positions_rewritten, &li.arena_uploads);
+    if (rc != SR_OK) return rc;
+    if (timed) (void)hipEventRecord(ev[1], nullptr);
+    const std::vector<SrEmissiveIndirectionEntry>& entries = s->fid.emissive_entries;
+    const size_t entry_bytes = sizeof(SrEmissiveIndirectionEntry) * entries.size();
+    if (s->entries_on_device.size() != entries.size() || memcmp(s->entries_on_device.data(), entries.data(), entry_bytes) != 0) {
+        if ((rc = s->d_light_entries.upload(entries.data(), entry_bytes)) != SR_OK) return rc;
+        s->entries_on_device = entries;
+        li.entries_uploaded = 1;
+    }
+    if ((rc = s->d_lights.reserve(entries.size() * 64)) != SR_OK) return rc;
+    if (timed) (void)hipEventRecord(ev[2], nullptr);
+    const int e = srk_light_table((const SrEmissiveIndirectionEntry*)s->d_light_entries.p, (uint32_t)entries.size(), (const SrEmissiveTriangle*)s->d_arena.p,
+                                  s->arena_device_entries, (const srd::FlatInstance*)s->d_flat_instances.p, (uint32_t)s->fid.instances.size(),
+                                  (float*)s->d_lights.p, nullptr);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("light table launch failed: ") + hipGetErrorString((hipError_t)e));
+    if (timed) (void)hipEventRecord(ev[3], nullptr);
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    float a = 0.0f, b = 0.0f;
+    if (timed && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[2], ev[3]) == hipSuccess) { li.positions_ms += a; li.table_ms += b; }
+    li.on_device = 1;
+    return SR_OK;
+}
+
+// What follows a mesh's new vertices once they are in its device allocation (and, for a mesh with emissive entries whose arena
+// slots the host keeps, in the host copy): the positions of its arena slots, then which trees and structures are stale.
 void mesh_vertices_changed(SrScene* s, uint32_t slot) {
     const srh::HostMesh& m = s->meshes[slot];
-    for (size_t k = 0; k < m.emissive_slots.size(); k++) {   // positions only: emission follows the material, which stays
+    const bool host_positions = !s->mesh_state[slot].arena_stale;       // arena_stale: the host copy is old, the device rewrites the slots
+    if (host_positions && !m.emissive_slots.empty()) s->arena_host_dirty = true;
+    for (size_t k = 0; host_positions && k < m.emissive_slots.size(); k++) {   // positions only: emission follows the material, which stays
         SrEmissiveTriangle& et = s->emissive_tris[m.emissive_slots[k]];
         memcpy(et.v0, m.vertices[m.indices[3 * k]].position, 12);
         memcpy(et.v1, m.vertices[m.indices[3 * k + 1]].position, 12);
@@ -384,7 +499,8 @@ void mesh_vertices_changed(SrScene* s, uint32_t slot) {
 
 // The copy of validated device vertices into a mesh's allocation (sr_scene_update_mesh_device and the replicas of a renderer):
 // the device wait (frames in flight read the old vertices), the copy on the null stream, the host copy left behind, and for a
-// mesh with emissive entries the fetch at once (the light table is host arithmetic on every sr_scene_set_instances).
+// mesh with emissive entries the fetch at once under SR_LIGHTS_HOST (the light table is then host arithmetic on every
+// sr_scene_set_instances) or, under SR_LIGHTS_DEVICE, the mark that its arena slots are to be rewritten on the device.
 int take_device_vertices(SrScene* s, uint32_t slot, const SrVertex* d_vertices, int src_device) {
     srh::HostMesh& m = s->meshes[slot];
     const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
@@ -401,7 +517,12 @@ int take_device_vertices(SrScene* s, uint32_t slot, const SrVertex* d_vertices, 
     for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
     HIP_TRY(e);
     m.host_stale = true; m.last_from_device = true;
-    return m.emissive_slots.empty() ? SR_OK : fetch_host_vertices(s, slot);
+    if (m.emissive_slots.empty()) return SR_OK;
+    if (s->light_mode == SR_LIGHTS_DEVICE) {                 // the arena positions follow on the device (sync_device_arena): no fetch
+        s->mesh_state[slot].arena_stale = true; s->mesh_state[slot].arena_pending = true;
+        return SR_OK;
+    }
+    return fetch_host_vertices(s, slot);
 }
 
 }  // namespace
@@ -464,6 +585,7 @@ int sr_scene_create(int device, SrScene** out) {
     if (const char* ev = getenv("SR_INSTANCING")) s->instancing = !strcmp(ev, "two_level") ? SR_INSTANCING_TWO_LEVEL : (!strcmp(ev, "flat") ? SR_INSTANCING_FLAT : SR_INSTANCING_AUTO);
     if (const char* ev = getenv("SR_TL_BUILD")) s->tl_build_mode = !strcmp(ev, "host") ? SR_TL_BUILD_HOST : (!strcmp(ev, "device") ? SR_TL_BUILD_DEVICE : SR_TL_BUILD_AUTO);
     if (const char* ev = getenv("SR_BLAS_BUILD")) s->blas_build_mode = !strcmp(ev, "host") ? SR_MESH_TREE_BUILD_HOST : (!strcmp(ev, "device") ? SR_MESH_TREE_BUILD_DEVICE : SR_MESH_TREE_BUILD_AUTO);
+    if (const char* ev = getenv("SR_LIGHT_TABLE")) s->light_mode = !strcmp(ev, "device") ? SR_LIGHTS_DEVICE : SR_LIGHTS_HOST;
     if (const char* ev = getenv("SR_FAST_BUILD_HEIGHT")) s->height_bound = !strcmp(ev, "rebalance") ? SR_HEIGHT_BOUND_REBALANCE : SR_HEIGHT_BOUND_REFUSE;
     if (const char* ev = getenv("SR_FAST_BUILD")) s->fast_build_ploc = !strcmp(ev, "lbvh") ? 0 : (!strncmp(ev, "ploc", 4) && atoi(ev + 4) > 0 ? atoi(ev + 4) : 16);
     hipDeviceProp_t prop;
@@ -539,6 +661,7 @@ int sr_scene_add_blas(SrScene* s, uint64_t key, const SrVertex* vertices, uint32
         else { es = (uint32_t)s->emissive_tris.size(); s->emissive_tris.push_back(emissive[i]); }
         m.emissive_slots.push_back(es);
     }
+    if (n_emissive) s->arena_host_dirty = true;
     SrMeshInfo mi;
     mi.vertices = (uint64_t)(uintptr_t)m.d_vertices;
     mi.indices = (uint64_t)(uintptr_t)m.d_indices;
@@ -583,6 +706,7 @@ int sr_scene_remove(SrScene* s, uint64_t key) {
     if (rc != SR_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     const uint32_t slot = it->second;
+    if (s->mesh_state[slot].arena_stale && (rc = refresh_host_arena(s)) != SR_OK) return rc;   // the freed slots keep the mesh's newest positions
     srh::HostMesh& m = s->meshes[slot];
     if (m.d_vertices) (void)hipFree(m.d_vertices);
     if (m.d_indices) (void)hipFree(m.d_indices);
@@ -614,6 +738,7 @@ int sr_scene_update_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uin
     const auto t2 = std::chrono::steady_clock::now();
     m.vertices.assign(vertices, vertices + n_vertices);
     m.host_stale = false; m.last_from_device = false;         // the host copy is the device buffer's contents again
+    s->mesh_state[slot].arena_stale = s->mesh_state[slot].arena_pending = false;   // and the arena slots are the host's again
     mesh_vertices_changed(s, slot);
     const auto t3 = std::chrono::steady_clock::now();
     s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
@@ -881,9 +1006,17 @@ int upload_instance_tables(SrScene* s) {
     }
     if ((rc = s->d_instances.upload(dinst.data(), dinst.size() * sizeof(srd::DevInstance))) != SR_OK) return rc;
     if ((rc = s->d_flat_instances.upload(flat.data(), flat.size() * sizeof(srd::FlatInstance))) != SR_OK) return rc;
-    std::vector<float> lights;
-    srh::light_table(s->fid, s->emissive_table, lights);
-    if ((rc = s->d_lights.upload(lights.data(), lights.size() * 4)) != SR_OK) return rc;
+    SrLightTableInfo& li = s->lt_info;                        // reset by sr_scene_set_instances: a path that comes here twice adds up
+    li.num_lights = (uint32_t)s->fid.emissive_entries.size(); li.arena_entries = (uint32_t)s->emissive_tris.size();
+    if (s->lights_on_device) {
+        if ((rc = device_light_table(s)) != SR_OK) return rc;
+    } else {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<float> lights;
+        srh::light_table(s->fid, s->emissive_table, lights);
+        if ((rc = s->d_lights.upload(lights.data(), lights.size() * 4)) != SR_OK) return rc;
+        if (s->timing) li.host_ms += ms_between(t0, std::chrono::steady_clock::now());
+    }
     s->dev.instances = (const srd::DevInstance*)s->d_instances.p;
     s->dev.lights = (const srd::DevLight*)s->d_lights.p;
     s->dev.num_lights = (uint32_t)s->fid.emissive_entries.size();
@@ -1297,7 +1430,7 @@ constexpr uint32_t kBlasDeviceMinTris = 0xFFFFFFFFu;
 // which rounds up to 32 768, and every measured size above that is now built on the device: the rule yields 32 768.
 constexpr uint32_t kBlasDeviceMinTrisBounded = 32768;
 constexpr uint32_t kBlasStackCap = 26;       // build_blas's limit: leaves the top-level tree at least 18 of the kTlStackCap entries
-static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshUpdateInfo) == 64 && sizeof(SrTreeHeightInfo) == 32 && sizeof(SrMeshVertexInfo) == 40, "layouts the harness relies on");
+static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshUpdateInfo) == 64 && sizeof(SrTreeHeightInfo) == 32 && sizeof(SrMeshVertexInfo) == 40 && sizeof(SrLightTableInfo) == 56, "layouts the harness relies on");
 uint32_t blas_device_min_tris(const SrScene* s) { return s->height_bound == SR_HEIGHT_BOUND_REBALANCE ? kBlasDeviceMinTrisBounded : kBlasDeviceMinTris; }
 
 // Blas::rebuild (blas.rs:285-310) on the device for the meshes of `set` (pending updatable meshes whose state asked for
@@ -1700,8 +1833,16 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     s->mu_info.reshaded = 0; s->mu_info.blas_rebuilt = 0; s->mu_info.blas_refitted = 0;
     s->mu_info.tables_ms = s->mu_info.flatten_ms = s->mu_info.refit_ms = s->mu_info.blas_build_ms = 0.0;
     auto applied = [s] { for (auto& ms : s->mesh_state) ms.dirty = false; s->geometry_stale = false; s->static_mesh_updated = false; };
-    s->emissive_table = s->emissive_tris;
-    if (s->emissive_table.empty()) { SrEmissiveTriangle z; memset(&z, 0, sizeof(z)); s->emissive_table.push_back(z); }
+    // the light table's source: the device arena (SR_LIGHTS_DEVICE; upload_instance_tables builds the table with the kernel, and
+    // the copy below is skipped: sr_scene_get_tables reads the device arena back when asked) or this frame's copy of the host
+    // arena. The one dummy record of an empty arena, and of a scene without instances, is host arithmetic in either mode.
+    s->lights_on_device = s->emissive_table_stale = s->light_mode == SR_LIGHTS_DEVICE && !s->emissive_tris.empty() && !s->fid.instances.empty();
+    { const uint32_t fetches = s->lt_info.arena_fetches; memset(&s->lt_info, 0, sizeof(s->lt_info)); s->lt_info.arena_fetches = fetches; }
+    if (!s->lights_on_device) {
+        if ((rc = refresh_host_arena(s)) != SR_OK) return rc;
+        s->emissive_table = s->emissive_tris;
+        if (s->emissive_table.empty()) { SrEmissiveTriangle z; memset(&z, 0, sizeof(z)); s->emissive_table.push_back(z); }
+    }
     // Two-level form (a tree per mesh + a top-level tree over the instances): on request or where the flattened copy would be
     // large. A changed instance list is then a top-level rebuild, reported as a fast build (Tlas::queue_build rebuilds in kind).
     if (wants_two_level(s) || s->fid.n_triangles >= (1u << 28)) {
@@ -1769,6 +1910,7 @@ int sr_scene_end_frame(SrScene* s) {
     if (op == SR_OP_SLOW_BUILD || mesh_settles) {
         int rc = bind_device(s);
         if (rc != SR_OK) return rc;
+        if (s->lights_on_device && (rc = fetch_emissive_table(s)) != SR_OK) return rc;   // the rebuild may move the device arena on (a pending mesh)
         if (s->two_level && !s->blas_device_current)      // the re-concatenation takes the stale host copies of refitted meshes along
             for (size_t m = 0; m < s->mesh_state.size(); m++) if (s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
         if ((rc = s->two_level ? two_level_build(s, false) : full_build(s)) != SR_OK) { s->built = false; return rc; }
@@ -1828,6 +1970,53 @@ int sr_scene_mesh_tree_info(const SrScene* s, SrMeshTreeInfo* out) {
     *out = s->mt_info;
     out->mode = (uint32_t)s->blas_build_mode;
     out->auto_threshold = blas_device_min_tris(s);
+    return SR_OK;
+}
+int sr_scene_set_light_table_build(SrScene* s, uint32_t mode) {
+    if (mode > SR_LIGHTS_DEVICE) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_light_table_build: mode must be SR_LIGHTS_HOST or SR_LIGHTS_DEVICE");
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_light_table_build: scene is null");
+    if (mode == SR_LIGHTS_HOST && s->light_mode == SR_LIGHTS_DEVICE) {      // the host arena takes over: its stale slots from the device arena
+        int rc = bind_device(s);
+        if (rc != SR_OK || (rc = fetch_emissive_table(s)) != SR_OK || (rc = refresh_host_arena(s)) != SR_OK) return rc;
+        s->lights_on_device = false;                          // a rebuild by sr_scene_end_frame reads emissive_table, which is current now
+    }
+    s->light_mode = (int)mode;
+    return SR_OK;
+}
+int sr_scene_light_table_info(const SrScene* s, SrLightTableInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_light_table_info: null argument");
+    *out = s->lt_info;
+    out->mode = (uint32_t)s->light_mode;
+    return SR_OK;
+}
+int sr_scene_read_lights(const SrScene* s, float* out, uint32_t cap_lights, uint32_t* n_lights) {
+    if (!s || !n_lights || (!out && cap_lights)) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_lights: null argument");
+    if (!s->built) return fail(SR_ERR_STATE, "sr_scene_read_lights: call sr_scene_set_instances first");
+    *n_lights = s->dev.num_lights;
+    const size_t n = std::min(cap_lights, s->dev.num_lights);
+    if (n == 0) return SR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, s->d_lights.p, n * 64, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+int sr_light_table(const SrTransform* transforms, uint32_t n_transforms, const SrEmissiveIndirectionEntry* entries, uint32_t n_entries,
+                   const SrEmissiveTriangle* triangles, uint32_t n_triangles, float* out) {
+    if (!transforms || !entries || !triangles || !out) return fail(SR_ERR_INVALID_ARG, "sr_light_table: null argument");
+    for (uint32_t i = 0; i < n_entries; i++)
+        if (entries[i].blas_tri_index >= n_triangles || entries[i].entity_id >= n_transforms) {
+            char buf[200];
+            snprintf(buf, sizeof(buf), "sr_light_table: entry %u names triangle %u of %u, transform %u of %u", i, entries[i].blas_tri_index, n_triangles,
+                     entries[i].entity_id, n_transforms);
+            return fail(SR_ERR_INVALID_ARG, buf);
+        }
+    srh::FrameInstanceData fid;
+    fid.transforms.assign(transforms, transforms + n_transforms);
+    fid.emissive_entries.assign(entries, entries + n_entries);
+    const std::vector<SrEmissiveTriangle> tris(triangles, triangles + n_triangles);
+    std::vector<float> lights;
+    srh::light_table(fid, tris, lights);
+    memcpy(out, lights.data(), lights.size() * 4);
     return SR_OK;
 }
 int sr_scene_set_tree_height_bound(SrScene* s, uint32_t mode, uint32_t mesh_tree_cap) {
@@ -2033,6 +2222,7 @@ int sr_scene_get_tables(const SrScene* s, const SrTransform** transforms, uint32
                         const SrMeshInfo** meshes_info, uint32_t* n_meshes) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_get_tables: scene is null");
     if (!s->built) return fail(SR_ERR_STATE, "sr_scene_get_tables: call sr_scene_set_instances first");
+    if (emissive_triangles || n_emissive) { const int rc = fetch_emissive_table(const_cast<SrScene*>(s)); if (rc != SR_OK) return rc; }
     if (transforms) *transforms = s->fid.transforms.data();
     if (n_instances) *n_instances = (uint32_t)s->fid.transforms.size();
     if (indirection) *indirection = s->fid.emissive_entries.data();

@@ -613,6 +613,23 @@ int sr_renderer_set_tree_height_bound(SrRenderer* r, uint32_t mode, uint32_t mes
     return SR_OK;
 }
 
+// Where the light table is built (SR_LIGHTS_*), on every replica; the figures of one replica's last sr_scene_set_instances.
+int sr_renderer_set_light_table_build(SrRenderer* r, uint32_t mode) {
+    if (mode > SR_LIGHTS_DEVICE) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_light_table_build: mode must be SR_LIGHTS_HOST or SR_LIGHTS_DEVICE");
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_light_table_build: renderer is null");
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_set_light_table_build(sc, mode);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+int sr_renderer_light_table_info(SrRenderer* r, uint32_t slot, SrLightTableInfo* out) {
+    if (!r || !out) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_light_table_info: null argument");
+    const std::vector<SrScene*> scs = srmr::scenes(r);
+    if (slot >= scs.size()) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_light_table_info: no such slot");
+    return sr_scene_light_table_info(scs[slot], out);
+}
+
 // Access for harnesses: the scene (counters, stats), the device output image and the frame counter.
 int sr_renderer_get(SrRenderer* r, SrScene** scene, const uint32_t** output_rgba8_device, const float** raw_color_device, uint32_t* relative_frame_count) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_get: renderer is null");

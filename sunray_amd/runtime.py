@@ -106,6 +106,18 @@ def emissive_triangles_from_mesh(vertices, indices, material):
     return out[: n.value].copy()
 
 
+def light_table(transforms, entries, triangles):
+    """The host arithmetic of the frame's light table (sr_light_table): transforms (n, 12) float32, entries abi.EMISSIVE_INDIRECTION,
+    triangles abi.EMISSIVE_TRIANGLE -> (len(entries), 16) float32 in the order Scene.read_lights documents."""
+    t = np.asarray(transforms)
+    t = np.ascontiguousarray(t["m"] if t.dtype.names else t, dtype=np.float32).reshape(-1, 12)
+    e = np.ascontiguousarray(entries, dtype=abi.EMISSIVE_INDIRECTION)
+    tr = np.ascontiguousarray(triangles, dtype=abi.EMISSIVE_TRIANGLE)
+    out = np.zeros((len(e), 16), dtype=np.float32)
+    check(lib().sr_light_table(_p(t), C.c_uint32(len(t)), _p(e), C.c_uint32(len(e)), _p(tr), C.c_uint32(len(tr)), _p(out)))
+    return out
+
+
 def bvh_layout():
     """(children per node, dwords per node, first plane dword, first child dword) of this build's BVH (csrc/bvh_layout.h)."""
     w, nd, po, co = (C.c_uint32() for _ in range(4))
@@ -446,6 +458,25 @@ class Scene:
         tris = np.zeros((max(st.n_triangles, 1), 12), dtype=np.float32)
         check(lib().sr_scene_read_bvh(self._h, _p(nodes), _p(tris)))
         return nodes, tris[:st.n_triangles]
+
+    def set_light_table_build(self, mode):
+        """Where set_instances builds the light table: "host" (default) | "device" (sr_scene_set_light_table_build)."""
+        check(lib().sr_scene_set_light_table_build(self._h, C.c_uint32({"host": abi.LIGHTS_HOST, "device": abi.LIGHTS_DEVICE}[mode])))
+        return self
+
+    def light_table_info(self):
+        """-> abi.SrLightTableInfo: the light table of the last set_instances (where it was built, uploads, fetches, milliseconds)."""
+        info = abi.SrLightTableInfo()
+        check(lib().sr_scene_light_table_info(self._h, C.byref(info)))
+        return info
+
+    def read_lights(self):
+        """The device light table, (num_lights, 16) float32: world v0 + area, v1 + normal x, v2 + normal y, emission + normal z."""
+        n = C.c_uint32()
+        check(lib().sr_scene_read_lights(self._h, None, C.c_uint32(0), C.byref(n)))
+        out = np.zeros((n.value, 16), dtype=np.float32)
+        check(lib().sr_scene_read_lights(self._h, _p(out), C.c_uint32(n.value), C.byref(n)))
+        return out
 
     def load(self, desc):
         for img in desc.images:
@@ -931,6 +962,17 @@ class Renderer:
         """Scene.set_tree_height_bound on every device slot (sr_renderer_set_tree_height_bound)."""
         check(lib().sr_renderer_set_tree_height_bound(self._h, C.c_uint32({"refuse": 0, "rebalance": 1}[mode]), C.c_uint32(cap)))
         return self
+
+    def set_light_table_build(self, mode):
+        """Scene.set_light_table_build on every device slot (sr_renderer_set_light_table_build)."""
+        check(lib().sr_renderer_set_light_table_build(self._h, C.c_uint32({"host": abi.LIGHTS_HOST, "device": abi.LIGHTS_DEVICE}[mode])))
+        return self
+
+    def light_table_info(self, slot=0):
+        """Scene.light_table_info of one device slot's scene (sr_renderer_light_table_info)."""
+        info = abi.SrLightTableInfo()
+        check(lib().sr_renderer_light_table_info(self._h, C.c_uint32(int(slot)), C.byref(info)))
+        return info
 
     def mesh_tree_info(self, slot=0):
         """Scene.mesh_tree_info of one device slot's scene."""
