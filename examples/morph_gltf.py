@@ -1,0 +1,67 @@
+"""A glTF file with morph targets (blend shapes) and a rig played on the GPU: the loader hands out the targets and the rig and
+evaluates the animation, Renderer.attach_skins and Renderer.attach_morphs give every mesh its influences and its deltas, and every
+frame Renderer.pose_scene samples the joint and the weight channels, blends the targets and then skins the result with the
+library's kernels (morph first, then skin; the posed vertices never visit the host) and returns the instance transforms for the
+frame. Writes the last frame as a PNG.
+
+    python examples/morph_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out morph.png] [--device-lights]
+
+--device-lights: the frame's light table is built on the device (Renderer.set_light_table_build("device")), so that a posed mesh
+with an emissive material never visits the host either.
+
+Default file: tests/golden/morph_bar.glb. Needs a GPU: the product path has no CPU fallback.
+"""
+import argparse
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
+from png import write_png  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("file", nargs="?", default=os.path.join(os.path.dirname(HERE), "tests", "golden", "morph_bar.glb"))
+    ap.add_argument("--animation", type=int, default=0)
+    ap.add_argument("--frames", type=int, default=48)
+    ap.add_argument("--size", default="640x480")
+    ap.add_argument("--out", default="morph.png")
+    ap.add_argument("--camera", default="0.8,1.4,7.0,0.8,1.0,0.0,45", help="position, target, vertical field of view in degrees")
+    ap.add_argument("--device-lights", action="store_true")
+    args = ap.parse_args()
+    from sunray_amd import runtime as rt
+    w, h = (int(v) for v in args.size.split("x"))
+    c = [float(v) for v in args.camera.split(",")]
+    camera = (tuple(c[0:3]), tuple(c[3:6]), c[6])
+    gltf = rt.Gltf(args.file)
+    n_skins, n_animations = gltf.rig_counts()
+    if not 0 <= args.animation < n_animations:
+        sys.exit("%s has %d animation(s); --animation %d is not one of them" % (args.file, n_animations, args.animation))
+    name, duration, n_channels, n_ignored = gltf.animation(args.animation)
+    morphed = [(b, gltf.blas_morph(b)[0]) for b in range(gltf.n_blases)]
+    n_targets = sum(len(d) for _, d in morphed if d is not None)
+    print("%s: %d skin(s), %d morph target(s) on %d mesh(es), animation %d '%s': %.3f s, %d channel(s), %d of them weights" % (
+        args.file, n_skins, n_targets, sum(d is not None for _, d in morphed), args.animation, name, duration, n_channels, n_ignored))
+    r = rt.Renderer((w, h))
+    if args.device_lights:
+        r.set_light_table_build("device")
+    loaded = r.load_scene(gltf)
+    r.attach_skins(gltf, loaded)
+    r.attach_morphs(gltf, loaded)
+    instances = loaded.instances
+    for f in range(args.frames):
+        instances = r.pose_scene(gltf, loaded, args.animation, duration * f / max(args.frames - 1, 1))
+        r.wait_frame(r.render(camera, instances))
+    for b, d in morphed:
+        if d is not None:
+            info = r.replica_scene(0).mesh_morph_info(int(loaded.keys[b]))
+            print("mesh %d: %d target(s), %d active in the last pose, %d pose(s)" % (b, info.n_targets, info.n_active, info.posed))
+    image = r.render_to_host_memory(camera, instances)       # lets the temporal accumulation settle on the last pose
+    write_png(args.out, image)
+    print("You can find your render here: %s" % args.out)
+
+
+if __name__ == "__main__":
+    main()

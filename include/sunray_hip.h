@@ -565,6 +565,59 @@ typedef struct SrMeshSkinInfo {
     double skin_ms;            /* the last accepted pose: kernel + 4-byte read-back (events, only while sr_scene_enable_timing is on) */
 } SrMeshSkinInfo;              /* 24 bytes */
 int sr_scene_mesh_skin_info(const SrScene* scene, uint64_t key, SrMeshSkinInfo* out);
+/* Morph targets (glTF 2.0 blend shapes): the other producer of posed vertices that lives in the library. One delta record per
+ * (target, vertex): three 16-byte pieces laid out like the first three of SrVertex; the pads are never read. */
+typedef struct SrMorphDelta {
+    float position[3], _pad0;
+    float normal[3], _pad1;
+    float tangent[3], _pad2;
+} SrMorphDelta;                /* 48 bytes */
+/* Attaches morph targets to a loaded mesh: snapshots the mesh's CURRENT device vertices as the morph base (a device-to-device
+ * copy the mesh owns; waits for the device) and uploads `deltas` (HOST pointer, n_targets * n_vertices records, target-major:
+ * target k's records for vertices 0..n_vertices-1 are contiguous). Refused with SR_ERR_INVALID_ARG before anything is touched: a
+ * null scene, an unknown key, another vertex count than the mesh's, n_targets == 0, and, with a message that names the lowest
+ * (target, vertex), a delta component (position, normal or tangent; not the pads) that is not finite. A failed allocation
+ * returns SR_ERR_OOM and leaves an earlier morph in place. deltas == NULL detaches the morph and frees its buffers (n_vertices
+ * and n_targets are not looked at); sr_scene_remove and sr_scene_destroy free them too. Later sr_scene_update_mesh* calls do not
+ * move the base; attaching again snapshots it anew. A mesh may carry a morph and a skin: attach both while the mesh holds its
+ * rest vertices, in either order. */
+int sr_scene_set_mesh_morph(SrScene* scene, uint64_t key, const SrMorphDelta* deltas, uint32_t n_vertices, uint32_t n_targets);
+/* The one per-frame call of a mesh that has a morph, a skin or both, in glTF's order: morph first, then skin.
+ * weights == NULL skips the morph stage: the call is then exactly sr_scene_skin_mesh(scene, key, joint_matrices, n_joints, stream).
+ * joint_matrices == NULL skips the skin stage. Both NULL: SR_ERR_INVALID_ARG.
+ * The morph stage compacts the weights that are not 0 into an active list (ascending target order; a target of weight 0 costs
+ * no traffic) and runs the morph kernel from the morph base. With a skin stage it writes a scratch buffer the scene owns, which
+ * the skinning kernel of sr_scene_skin_mesh takes as its bind pose (the snapshot of sr_scene_set_mesh_skin is not read then); the
+ * last stage writes the scratch buffer of sr_scene_skin_mesh, and the result goes the way of sr_scene_update_mesh_device: applied
+ * by the next sr_scene_set_instances, with the same SR_ERR_STATE window, the same stale host copy and the same emissive
+ * handling. Each stage has a finite-position check word of its own (x, y, z of the stage's position; nothing else is looked at);
+ * both are read back once, after the last kernel: on a bad vertex the call returns sr_scene_update_mesh's status and text with the
+ * lowest offending index of either stage, and the scene is exactly as it was (only SrMeshMorphInfo.first_bad and
+ * SrMeshSkinInfo.first_bad tell). Refused on the host before anything is launched: a null scene, an unknown key, a stage asked
+ * for that the mesh has nothing attached for, another n_targets or n_joints than attached, a weight that is not finite (the
+ * message names the lowest index) (SR_ERR_INVALID_ARG), an emissive list that is not one per triangle (SR_ERR_UNSUPPORTED).
+ * The morph arithmetic, fp32 under the numerics contract (no contraction, correctly rounded divide and sqrt, left to right), for
+ * each of the three vectors (position, normal, tangent) of a vertex, with base vector b (tangent: b.xyz and b.w), the active
+ * targets k in ascending order, their weights w_k and their delta vectors d_k:
+ *   s = (0.0f, 0.0f, 0.0f), then for each active k in order:  s = s + w_k * d_k                          (per component)
+ *   where every component of s is +0 or -0, the base's bytes are written for that vector (all 16 of its piece); otherwise
+ *   position' = b + s
+ *   normal'   = normalise(b + s)
+ *   tangent'  = (normalise(b.xyz + s), b.w)
+ *   normalise(v) = v * (1.0f / sqrt((v.x * v.x + v.y * v.y) + v.z * v.z)); where that squared length is 0 or not finite, the
+ *               base's bytes are written for that vector.
+ * Every other byte of the record (the fourth word of the three pieces, the five uv sets, the pads) is the base's; with all
+ * weights 0 the output is the base byte for byte. */
+int sr_scene_pose_mesh(SrScene* scene, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints,
+                       void* stream);
+typedef struct SrMeshMorphInfo {
+    uint32_t n_targets;        /* targets of the attached morph; 0: the mesh has none */
+    uint32_t posed;            /* accepted sr_scene_pose_mesh calls with a morph stage since the morph was attached */
+    uint32_t n_active;         /* the last morph stage: weights that were not 0 */
+    uint32_t first_bad;        /* the last morph stage: lowest vertex morphed to a non-finite position, 0xFFFFFFFF: none */
+    double morph_ms;           /* the last accepted pose: its kernels (morph, and skin where asked) + read-back (events, only while sr_scene_enable_timing is on) */
+} SrMeshMorphInfo;             /* 24 bytes */
+int sr_scene_mesh_morph_info(const SrScene* scene, uint64_t key, SrMeshMorphInfo* out);
 /* BuildType of one mesh's tree (blas.rs:149-161: RapidlyChanging and SometimesChanges are built with ALLOW_UPDATE, Static is not).
  * Every loaded mesh starts as SR_BUILD_STATIC (Renderer::load_mesh, lib.rs:937): it is never refitted, every update rebuilds its
  * tree on the host. An updatable mesh holds an SrAsState of its own (reset to sr_as_state_initial(build_type) by this call), driven
@@ -882,7 +935,8 @@ int sr_gltf_blas_skin(const SrGltf* gltf, uint32_t blas_index, int32_t* skin_ind
  * node index of every joint. */
 int sr_gltf_skin(const SrGltf* gltf, uint32_t i, uint32_t* n_joints, const SrTransform** inverse_bind, const uint32_t** joint_nodes);
 /* Animation i: its name ("" when the file gives none), the last key time of its samplers, and the number of channels the file
- * lists. `weights` channels (morph targets) are among them but are not sampled: sr_gltf_animation_ignored_channels counts them. */
+ * lists. `weights` channels (morph targets) are among them but are not sampled by sr_gltf_pose (sr_gltf_morph_weights samples
+ * them): sr_gltf_animation_ignored_channels counts them. */
 int sr_gltf_animation(const SrGltf* gltf, uint32_t i, const char** name, float* duration_seconds, uint32_t* n_channels);
 int sr_gltf_animation_ignored_channels(const SrGltf* gltf, uint32_t i, uint32_t* n_weights_channels);
 /* The file's nodes at `time_seconds` of animation `animation` (-1: the file's static pose, time ignored): the world transform
@@ -907,6 +961,24 @@ int sr_gltf_pose(const SrGltf* gltf, int32_t animation, float time_seconds, SrTr
  * `matrix` where the file gives one. */
 int sr_gltf_sample_node(const SrGltf* gltf, int32_t animation, float time_seconds, uint32_t node, float translation[3], float rotation[4],
                         float scale[3], uint32_t* animated);
+/* Morph targets of the file, parsed and validated like the rig: when one of the two calls below first asks, never by
+ * sr_gltf_open; sr_gltf_animation and sr_gltf_animation_ignored_channels return what they returned before these existed.
+ * The targets of blas i: those of the primitive of the first node that instances it. *deltas is target-major (n_targets *
+ * n_vertices records, sr_scene_set_mesh_morph's layout) in the vertex order of sr_gltf_blas, from the POSITION, NORMAL and TANGENT
+ * accessors of every target (float VEC3; sparse accessors resolved; an absent attribute gives zeros; the pads are 0);
+ * *default_weights is node.weights of that first node, else mesh.weights, else zeros. *n_targets == 0 with NULL pointers: the
+ * blas has no targets. SR_ERR_UNSUPPORTED: another component type than float, a target attribute other than those three
+ * (TEXCOORD_n, COLOR_n), nodes instancing the blas whose weights differ. SR_ERR_INVALID_ARG: an accessor shorter than POSITION,
+ * accessors of the primitive's targets whose counts disagree, a `weights` array that is not n_targets finite numbers. */
+int sr_gltf_blas_morph(const SrGltf* gltf, uint32_t blas_index, uint32_t* n_targets, const SrMorphDelta** deltas, uint32_t* n_vertices,
+                       const float** default_weights);
+/* The weights of blas i's targets at `time_seconds` of animation `animation` into weights_out (n_targets must be the blas's):
+ * the first `weights` channel that targets the blas's first instancing node, under sr_gltf_pose's sampling rules: time clamped to
+ * the sampler's first / last key, STEP and LINEAR, computed in double from the fp32 keys and rounded once to fp32; a CUBICSPLINE
+ * sampler on that channel: SR_ERR_UNSUPPORTED. The output accessor holds n_keys * n_targets float scalars; a shorter one, key
+ * times that are not finite, negative or not strictly increasing, a value that is not finite: SR_ERR_INVALID_ARG. animation == -1,
+ * or no such channel: the default weights of sr_gltf_blas_morph. */
+int sr_gltf_morph_weights(const SrGltf* gltf, int32_t animation, float time_seconds, uint32_t blas_index, float* weights_out, uint32_t n_targets);
 
 /* What Renderer::load_gltf / load_scene return (lib.rs:779-846): the asset group and the scene's instances
  * grouped per BLAS key in BLAS order. Keys are ResourceKey{group, index} packed as group << 32 | index
@@ -941,6 +1013,18 @@ int sr_renderer_attach_skins(SrRenderer* renderer, const SrGltf* gltf, const SrL
  * sr_loaded_scene_get's transforms; may be NULL) for the caller's next sr_renderer_render. */
 int sr_renderer_pose_scene(SrRenderer* renderer, const SrGltf* gltf, const SrLoadedScene* loaded, int32_t animation, float time_seconds,
                            SrTransform* instance_transforms_out, void* stream);
+/* sr_scene_set_mesh_morph / sr_scene_pose_mesh through the facade, as the skin calls above: the morph is attached on the first
+ * device slot's scene only and the mesh is posed there, once (morph, then skin where joint matrices are given); every further
+ * slot's replica takes the validated posed vertices by a device-to-device (peer) copy. A refusal changes no replica. */
+int sr_renderer_set_mesh_morph(SrRenderer* renderer, uint64_t key, const SrMorphDelta* deltas, uint32_t n_vertices, uint32_t n_targets);
+int sr_renderer_pose_mesh(SrRenderer* renderer, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices,
+                          uint32_t n_joints, void* stream);
+/* Attaches the morph targets of every blas of a loaded scene that has some (sr_gltf_blas_morph -> sr_renderer_set_mesh_morph) and
+ * declares those meshes SR_BUILD_RAPIDLY_CHANGING. From then on sr_renderer_pose_scene poses them too: the weights of
+ * sr_gltf_morph_weights into sr_renderer_pose_mesh, with the joint matrices where the mesh is skinned as well. A scene on which
+ * this was never called is posed by sr_renderer_pose_scene as before. Call it, like sr_renderer_attach_skins, while the meshes
+ * hold the vertices they were loaded with. */
+int sr_renderer_attach_morphs(SrRenderer* renderer, const SrGltf* gltf, const SrLoadedScene* loaded);
 /* sr_scene_set_mesh_build_type on every device slot's scene. */
 int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t build_type);
 /* sr_scene_set_mesh_tree_build on every device slot's scene. */

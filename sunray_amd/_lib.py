@@ -36,6 +36,8 @@ SYMBOLS = [
     "sr_scene_set_mesh_skin", "sr_scene_skin_mesh", "sr_scene_mesh_skin_info", "sr_renderer_set_mesh_skin", "sr_renderer_skin_mesh",
     "sr_gltf_rig_counts", "sr_gltf_blas_skin", "sr_gltf_skin", "sr_gltf_animation", "sr_gltf_animation_ignored_channels", "sr_gltf_pose", "sr_gltf_sample_node",
     "sr_renderer_attach_skins", "sr_renderer_pose_scene",
+    "sr_scene_set_mesh_morph", "sr_scene_pose_mesh", "sr_scene_mesh_morph_info", "sr_renderer_set_mesh_morph", "sr_renderer_pose_mesh",
+    "sr_gltf_blas_morph", "sr_gltf_morph_weights", "sr_renderer_attach_morphs",
     "sr_scene_set_light_table_build", "sr_scene_light_table_info", "sr_scene_read_lights", "sr_light_table",
     "sr_renderer_set_light_table_build", "sr_renderer_light_table_info",
 ]

@@ -187,6 +187,19 @@ class SrMeshSkinInfo(C.Structure):  # one mesh's skin and its last pose (sr_scen
     _fields_ = [("n_joints", C.c_uint32), ("skinned", C.c_uint32), ("first_bad", C.c_uint32), ("_pad", C.c_uint32), ("skin_ms", C.c_double)]
 
 
+class SrMorphDelta(C.Structure):  # one (target, vertex) record of sr_scene_set_mesh_morph: the first three pieces of a vertex, 48 B
+    _fields_ = [("position", C.c_float * 3), ("_pad0", C.c_float), ("normal", C.c_float * 3), ("_pad1", C.c_float),
+                ("tangent", C.c_float * 3), ("_pad2", C.c_float)]
+
+
+MORPH_DELTA = np.dtype([("position", "<f4", 3), ("_pad0", "<f4"), ("normal", "<f4", 3), ("_pad1", "<f4"), ("tangent", "<f4", 3), ("_pad2", "<f4")])
+assert MORPH_DELTA.itemsize == 48 == C.sizeof(SrMorphDelta)
+
+
+class SrMeshMorphInfo(C.Structure):  # one mesh's morph and its last pose (sr_scene_mesh_morph_info), 24 B
+    _fields_ = [("n_targets", C.c_uint32), ("posed", C.c_uint32), ("n_active", C.c_uint32), ("first_bad", C.c_uint32), ("morph_ms", C.c_double)]
+
+
 class SrMeshTreeInfo(C.Structure):  # the mesh-tree builds of the last sr_scene_set_instances (sr_scene_mesh_tree_info)
     _fields_ = [("mode", C.c_uint32), ("auto_threshold", C.c_uint32), ("built_on_device", C.c_uint32), ("built_on_host", C.c_uint32),
                 ("reason", C.c_uint32), ("n_nodes", C.c_uint32), ("max_stack", C.c_uint32), ("_pad", C.c_uint32), ("device_build_ms", C.c_double)]

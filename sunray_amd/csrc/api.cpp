@@ -21,6 +21,7 @@
 #include "bvh_layout.h"
 #include "kernels.h"
 #include "lights.h"
+#include "morph.h"
 #include "skin.h"
 #include "tl_record.h"
 
@@ -204,6 +205,10 @@ struct SrScene {
         // owned by the mesh (freed with this record: detach, sr_scene_remove, sr_scene_destroy); n_joints == 0: no skin
         struct Skin { DeviceBuffer d_bind, d_influences; uint32_t n_joints = 0, skinned = 0, first_bad = 0xFFFFFFFFu; double skin_ms = 0.0; };
         Skin skin;
+        // sr_scene_set_mesh_morph: the morph base (a snapshot of the mesh's vertices at the attach) and the target-major delta records,
+        // owned by the mesh like the skin's buffers; n_targets == 0: no morph
+        struct Morph { DeviceBuffer d_base, d_deltas; uint32_t n_targets = 0, posed = 0, n_active = 0, first_bad = 0xFFFFFFFFu; double morph_ms = 0.0; };
+        Morph morph;
         // light table on the device (SR_LIGHTS_DEVICE). arena_stale: the newest positions of this mesh's arena slots exist only on
         // the device (its d_vertices, and the device arena once arena_pending is served); emissive_tris holds older ones.
         // arena_pending: emissive_positions_kernel has to rewrite its slots of the device arena before the next table is built.
@@ -229,6 +234,9 @@ struct SrScene {
     DeviceBuffer d_blas_build_out;          // read-back block of a device mesh-tree build
     DeviceBuffer d_vertex_check;            // the word sr_scene_update_mesh_device's validation kernel and the skinning kernel answer in
     DeviceBuffer d_skin_out, d_skin_matrices;   // sr_scene_skin_mesh: the posed vertices of the last call (scratch) and its joint matrices
+    // sr_scene_pose_mesh: the morphed vertices where a skin stage follows (scratch: srk_skin's `bind`; without one the morph stage
+    // writes d_skin_out itself), the active list of the last call (n indices, then n weights) and the two stages' check words
+    DeviceBuffer d_morph_out, d_morph_active, d_pose_check;
     DeviceBuffer d_blas_nodes, d_tl_inst, d_tl_instances;
     // top level built on the device (bvh_gpu.hip srk_tl_*): per-mesh rows the record kernel reads, the instance boxes, its result block
     DeviceBuffer d_tl_mesh_rows, d_tl_boxes, d_tl_result;
@@ -921,6 +929,142 @@ int sr_scene_mesh_skin_info(const SrScene* s, uint64_t key, SrMeshSkinInfo* out)
     const SrScene::MeshState::Skin& skin = s->mesh_state[it->second].skin;
     memset(out, 0, sizeof(*out));
     out->n_joints = skin.n_joints; out->skinned = skin.skinned; out->first_bad = skin.first_bad; out->skin_ms = skin.skin_ms;
+    return SR_OK;
+}
+
+// Attaches (or, with deltas == NULL, detaches) a mesh's morph targets, as sr_scene_set_mesh_skin attaches a rig: everything is
+// validated and both buffers are filled before the mesh's record changes, so a refusal or a failed allocation leaves an earlier
+// morph in place.
+int sr_scene_set_mesh_morph(SrScene* s, uint64_t key, const SrMorphDelta* deltas, uint32_t n_vertices, uint32_t n_targets) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "set_mesh_morph: null argument (the scene)");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "set_mesh_morph: no mesh is registered under this key");
+    const uint32_t slot = it->second;
+    const srh::HostMesh& m = s->meshes[slot];
+    if (!deltas) {
+        int rc = bind_device(s);
+        if (rc != SR_OK) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        s->mesh_state[slot].morph = SrScene::MeshState::Morph();
+        return SR_OK;
+    }
+    char buf[200];
+    if (n_vertices != m.n_vertices) {
+        snprintf(buf, sizeof(buf), "set_mesh_morph: targets of %u vertices given, the mesh was loaded with %u vertices", n_vertices, m.n_vertices);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
+    if (n_targets == 0) return fail(SR_ERR_INVALID_ARG, "set_mesh_morph: a morph needs at least one target (n_targets is 0)");
+    for (uint32_t k = 0; k < n_targets; k++)
+        for (uint32_t i = 0; i < n_vertices; i++) {
+            const SrMorphDelta& d = deltas[(size_t)k * n_vertices + i];
+            bool ok = true;
+            for (int c = 0; c < 3; c++) ok = ok && std::isfinite(d.position[c]) && std::isfinite(d.normal[c]) && std::isfinite(d.tangent[c]);
+            if (!ok) {
+                snprintf(buf, sizeof(buf), "set_mesh_morph: target %u has a delta component that is not finite at vertex %u", k, i);
+                return fail(SR_ERR_INVALID_ARG, buf);
+            }
+        }
+    int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    SrScene::MeshState::Morph morph;
+    const size_t bytes = sizeof(SrVertex) * (size_t)n_vertices;
+    if ((rc = morph.d_base.reserve(bytes)) != SR_OK || (rc = morph.d_deltas.upload(deltas, sizeof(SrMorphDelta) * (size_t)n_vertices * n_targets)) != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());                          // whatever still writes the mesh's vertices has finished
+    HIP_TRY(hipMemcpy(morph.d_base.p, m.d_vertices, bytes, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    morph.n_targets = n_targets;
+    s->mesh_state[slot].morph = std::move(morph);
+    return SR_OK;
+}
+
+// The one per-frame call of a mesh with a morph, a skin or both: glTF's order, morph first, then skin. The morph kernel reads the
+// morph base; with a skin stage it writes the scene's morph scratch, which the unchanged skinning kernel takes as its `bind`, and
+// the skinning kernel writes d_skin_out; without one the morph kernel writes d_skin_out itself. Each stage answers in a check word
+// of its own; both come back in one read after the last kernel, and from there it is the path of sr_scene_skin_mesh.
+int sr_scene_pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_mesh: null argument (the scene)");
+    if (!weights && !joint_matrices) return fail(SR_ERR_INVALID_ARG, "pose_mesh: neither weights nor joint matrices given (one stage at least)");
+    if (!weights) return sr_scene_skin_mesh(s, key, joint_matrices, n_joints, stream);
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "pose_mesh: no mesh is registered under this key");
+    const uint32_t slot = it->second;
+    srh::HostMesh& m = s->meshes[slot];
+    SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
+    SrScene::MeshState::Skin& skin = s->mesh_state[slot].skin;
+    char buf[200];
+    if (morph.n_targets == 0) return fail(SR_ERR_INVALID_ARG, "pose_mesh: the mesh has no morph targets (sr_scene_set_mesh_morph attaches them)");
+    if (n_targets != morph.n_targets) {
+        snprintf(buf, sizeof(buf), "pose_mesh: %u weights given, the morph was attached with %u targets", n_targets, morph.n_targets);
+        return fail(SR_ERR_INVALID_ARG, buf);
+    }
+    if (joint_matrices) {
+        if (skin.n_joints == 0) return fail(SR_ERR_INVALID_ARG, "pose_mesh: the mesh has no skin (sr_scene_set_mesh_skin attaches one)");
+        if (n_joints != skin.n_joints) {
+            snprintf(buf, sizeof(buf), "pose_mesh: %u joint matrices given, the skin was attached with %u joints", n_joints, skin.n_joints);
+            return fail(SR_ERR_INVALID_ARG, buf);
+        }
+    }
+    // the active list: the targets whose weight is not 0, in ascending order (indices, then weights: one upload)
+    std::vector<uint32_t> active(2 * (size_t)n_targets);
+    uint32_t n_active = 0;
+    for (uint32_t k = 0; k < n_targets; k++) {
+        if (!std::isfinite(weights[k])) {
+            snprintf(buf, sizeof(buf), "pose_mesh: weight %u is not finite", k);
+            return fail(SR_ERR_INVALID_ARG, buf);
+        }
+        if (weights[k] != 0.0f) { active[n_active] = k; memcpy(&active[(size_t)n_targets + n_active], &weights[k], 4); n_active++; }
+    }
+    int rc = check_emissive_list(m);
+    if (rc != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
+    const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
+    if ((rc = s->d_skin_out.reserve(bytes)) != SR_OK || (rc = s->d_morph_active.reserve(8 * (size_t)n_targets)) != SR_OK || (rc = s->d_pose_check.reserve(16)) != SR_OK) return rc;
+    if (joint_matrices && ((rc = s->d_morph_out.reserve(bytes)) != SR_OK || (rc = s->d_skin_matrices.reserve(sizeof(SrTransform) * (size_t)n_joints)) != SR_OK)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    const bool timed = s->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
+    uint32_t* const check = (uint32_t*)s->d_pose_check.p;    // word 0: the morph stage, word 1: the skin stage
+    uint32_t bad[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+    int e = (int)hipMemsetAsync(check, 0xFF, 8, st);
+    if (e == 0) e = (int)hipMemcpyAsync(s->d_morph_active.p, active.data(), 8 * (size_t)n_targets, hipMemcpyHostToDevice, st);
+    if (e == 0 && joint_matrices) e = (int)hipMemcpyAsync(s->d_skin_matrices.p, joint_matrices, sizeof(SrTransform) * (size_t)n_joints, hipMemcpyHostToDevice, st);
+    if (timed) (void)hipEventRecord(ev[0], st);
+    SrVertex* const morphed = (SrVertex*)(joint_matrices ? s->d_morph_out.p : s->d_skin_out.p);
+    if (e == 0) e = srk_morph((const SrVertex*)morph.d_base.p, (const SrMorphDelta*)morph.d_deltas.p, (const uint32_t*)s->d_morph_active.p,
+                              (const float*)s->d_morph_active.p + n_targets, n_active, morphed, m.n_vertices, check, st);
+    if (e == 0 && joint_matrices) e = srk_skin(morphed, (const SrSkinInfluence*)skin.d_influences.p, (const SrTransform*)s->d_skin_matrices.p,
+                                               (SrVertex*)s->d_skin_out.p, m.n_vertices, check + 1, st);
+    if (e == 0) e = (int)hipMemcpyAsync(bad, check, 8, hipMemcpyDeviceToHost, st);
+    if (timed) (void)hipEventRecord(ev[1], st);
+    if (e == 0) e = (int)hipStreamSynchronize(st);
+    float ms = 0.0f;
+    const double pose_ms = (timed && e == 0 && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ? (double)ms : 0.0;
+    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("pose_mesh: a posing kernel failed: ") + hipGetErrorString((hipError_t)e));
+    morph.first_bad = bad[0] < m.n_vertices ? bad[0] : 0xFFFFFFFFu;
+    morph.n_active = n_active;
+    if (joint_matrices) skin.first_bad = bad[1] < m.n_vertices ? bad[1] : 0xFFFFFFFFu;
+    if (const uint32_t first_bad = std::min(bad[0], bad[1]); first_bad < m.n_vertices) return fail_non_finite_vertex(first_bad);
+    const auto t1 = std::chrono::steady_clock::now();
+    if ((rc = take_device_vertices(s, slot, (const SrVertex*)s->d_skin_out.p, s->device)) != SR_OK) return rc;
+    const auto t2 = std::chrono::steady_clock::now();
+    m.check_ms = 0.0;                                         // the check is part of the posing kernels: SrMeshMorphInfo.morph_ms
+    morph.morph_ms = pose_ms; morph.posed++;
+    if (joint_matrices) { skin.skin_ms = 0.0; skin.skinned++; }    // the two kernels are timed as one: morph_ms
+    mesh_vertices_changed(s, slot);
+    const auto t3 = std::chrono::steady_clock::now();
+    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
+    s->mu_info.h2d_ms = ms_between(t1, t2);
+    return SR_OK;
+}
+
+int sr_scene_mesh_morph_info(const SrScene* s, uint64_t key, SrMeshMorphInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_morph_info: null argument");
+    auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_morph_info: no mesh is registered under this key");
+    const SrScene::MeshState::Morph& morph = s->mesh_state[it->second].morph;
+    memset(out, 0, sizeof(*out));
+    out->n_targets = morph.n_targets; out->posed = morph.posed; out->n_active = morph.n_active; out->first_bad = morph.first_bad; out->morph_ms = morph.morph_ms;
     return SR_OK;
 }
 

@@ -822,6 +822,144 @@ struct GltfLoader {
         return &animations.emplace(i, std::move(r)).first->second;
     }
 
+    // ---- morph targets: read when first asked for (sr_gltf_blas_morph, sr_gltf_morph_weights), never by sr_gltf_open -------------
+    // animation() above still only counts `weights` channels; the channel of a blas's node is parsed here, by the call that samples it.
+    struct BlasMorph { long node = -1; uint32_t n_targets = 0; std::vector<SrMorphDelta> deltas; std::vector<float> default_weights; };
+    std::map<uint32_t, BlasMorph> blas_morphs;
+
+    // The weights a node instantiates a mesh's targets with: node.weights, then mesh.weights, then zeros.
+    bool instance_weights(const Json* node, const Json* mesh, uint32_t n_targets, std::vector<float>& w) {
+        const Json* src = node && node->has("weights") ? node->get("weights") : mesh && mesh->has("weights") ? mesh->get("weights") : nullptr;
+        w.assign(n_targets, 0.0f);
+        if (!src) return true;
+        if (src->kind != Json::Arr || src->size() != n_targets) return fail("`weights` must be an array with one number per morph target");
+        for (uint32_t k = 0; k < n_targets; k++) {
+            const Json& j = src->arr[k];
+            if (j.kind != Json::Num || !std::isfinite((float)j.num)) return fail("`weights` holds a value that is not a finite number");
+            w[k] = (float)j.num;
+        }
+        return true;
+    }
+
+    // The targets of a blas are those of the primitive of the first node that instances it; every other node that instances it
+    // must give the same weights.
+    const BlasMorph* blas_morph(uint32_t blas) {
+        auto it = blas_morphs.find(blas);
+        if (it != blas_morphs.end()) return &it->second;
+        if (blas >= out.blases.size()) { fail("blas index out of range"); return nullptr; }
+        BlasMorph r;
+        const GltfScene::InstanceSource* first = nullptr;
+        for (size_t i = 0; i < out.instances.size() && !first; i++)
+            if (out.instances[i].first == blas) first = &out.instance_sources[i];
+        if (!first) return &blas_morphs.emplace(blas, std::move(r)).first->second;
+        const Json* mesh = element("meshes", first->mesh);
+        const Json* plist = mesh ? mesh->get("primitives") : nullptr;
+        const Json* prim = plist && (size_t)first->primitive < plist->size() ? &plist->arr[first->primitive] : nullptr;
+        const Json* targets = prim ? prim->get("targets") : nullptr;
+        if (!targets) return &blas_morphs.emplace(blas, std::move(r)).first->second;
+        if (targets->kind != Json::Arr) { fail("a primitive's `targets` must be an array"); return nullptr; }
+        if (targets->size() == 0) return &blas_morphs.emplace(blas, std::move(r)).first->second;
+        if (targets->size() > 65536) { fail("more than 65536 morph targets on a primitive are not supported", SR_ERR_UNSUPPORTED); return nullptr; }
+        const size_t nv = out.blases[blas].vertices.size();
+        r.node = first->node;
+        r.n_targets = (uint32_t)targets->size();
+        SrMorphDelta zero;
+        memset(&zero, 0, sizeof(zero));
+        r.deltas.assign((size_t)r.n_targets * nv, zero);
+        size_t common = 0; bool have_common = false;
+        for (uint32_t k = 0; k < r.n_targets; k++) {
+            const Json& t = targets->arr[k];
+            if (t.kind != Json::Obj) { fail("a morph target must be an object of attribute accessors"); return nullptr; }
+            for (const auto& kv : t.obj) {
+                const std::string& name = kv.first;
+                const size_t at = name == "POSITION" ? offsetof(SrMorphDelta, position) : name == "NORMAL" ? offsetof(SrMorphDelta, normal)
+                                : name == "TANGENT" ? offsetof(SrMorphDelta, tangent) : (size_t)-1;
+                if (at == (size_t)-1) { fail("morph target attribute '" + name + "' is not supported (POSITION, NORMAL and TANGENT are)", SR_ERR_UNSUPPORTED); return nullptr; }
+                const long acc = as_index(kv.second);
+                const Json* a = element("accessors", acc);
+                if (!a) { fail("morph target names an accessor that does not exist"); return nullptr; }
+                if ((int)a->number("componentType", 0) != 5126) { fail("morph target " + name + " must be a float VEC3 accessor (another component type is not supported)", SR_ERR_UNSUPPORTED); return nullptr; }
+                std::vector<float> d; size_t n = 0;
+                if (!read_floats(acc, 3, d, &n)) return nullptr;
+                if (n < nv) { fail("morph target " + name + " shorter than POSITION"); return nullptr; }
+                if (have_common && n != common) { fail("the accessors of a primitive's morph targets disagree in their counts"); return nullptr; }
+                common = n; have_common = true;
+                for (size_t v = 0; v < nv; v++) memcpy((uint8_t*)&r.deltas[(size_t)k * nv + v] + at, &d[3 * v], 12);
+            }
+        }
+        if (!instance_weights(element("nodes", first->node), mesh, r.n_targets, r.default_weights)) return nullptr;
+        for (size_t i = 0; i < out.instances.size(); i++) {
+            if (out.instances[i].first != blas) continue;
+            const GltfScene::InstanceSource& src = out.instance_sources[i];
+            std::vector<float> w;
+            if (!instance_weights(element("nodes", src.node), element("meshes", src.mesh), r.n_targets, w)) return nullptr;
+            if (memcmp(w.data(), r.default_weights.data(), 4 * (size_t)r.n_targets) != 0) {
+                fail("a primitive with morph targets instanced by nodes with different weights is not supported", SR_ERR_UNSUPPORTED);
+                return nullptr;
+            }
+        }
+        return &blas_morphs.emplace(blas, std::move(r)).first->second;
+    }
+
+    // The weights of a blas's targets at `time_seconds` of animation `anim` (-1, or no `weights` channel for the blas's node: the
+    // default weights), under the sampling rules of sample_channel: clamped, STEP and LINEAR, in double from the fp32 keys, rounded once.
+    bool morph_weights(long anim, float time_seconds, uint32_t blas, float* weights_out, uint32_t n_targets) {
+        const BlasMorph* bm = blas_morph(blas);
+        if (!bm) return false;
+        if (n_targets != bm->n_targets) return fail("another number of weights asked for than the blas has morph targets");
+        if (n_targets == 0) return true;
+        memcpy(weights_out, bm->default_weights.data(), 4 * (size_t)n_targets);
+        if (anim < 0) return true;
+        const Json* an = element("animations", anim);
+        if (!an) return fail("animation index out of range");
+        if (!std::isfinite(time_seconds)) return fail("the time of a pose must be finite");
+        const Json* chans = an->get("channels");
+        const Json* samps = an->get("samplers");
+        for (size_t c = 0; chans && c < chans->size(); c++) {
+            const Json* target = chans->arr[c].get("target");
+            const Json* path = target ? target->get("path") : nullptr;
+            if (!target || !path || path->kind != Json::Str || path->str != "weights" || !target->has("node") || target->index("node") != bm->node) continue;
+            const long si = chans->arr[c].index("sampler");
+            if (!samps || si < 0 || (size_t)si >= samps->size()) return fail("animation channel refers to a missing sampler");
+            const Json& smp = samps->arr[si];
+            const Json* ip = smp.get("interpolation");
+            const std::string mode = ip && ip->kind == Json::Str ? ip->str : "LINEAR";
+            if (mode == "CUBICSPLINE") return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED);
+            if (mode != "LINEAR" && mode != "STEP") return fail("animation sampler with an unknown interpolation '" + mode + "'");
+            const Json* ia = element("accessors", smp.index("input"));
+            if (!ia || (int)ia->number("componentType", 0) != 5126) return fail("animation sampler input must be a float SCALAR accessor");
+            std::vector<float> times, values;
+            size_t nt = 0, nv = 0;
+            if (!read_floats(smp.index("input"), 1, times, &nt)) return false;
+            if (nt == 0) return fail("animation sampler without keys");
+            for (size_t t = 0; t < nt; t++)
+                if (!std::isfinite(times[t]) || times[t] < 0.0f || (t && !(times[t] > times[t - 1]))) return fail("animation key times must be finite, not negative and strictly increasing");
+            const Json* oa = element("accessors", smp.index("output"));
+            if (!oa || (int)oa->number("componentType", 0) != 5126) return fail("animation sampler output of a weights channel must be a float SCALAR accessor");
+            if (!read_floats(smp.index("output"), 1, values, &nv)) return false;
+            if (nv < nt * (size_t)n_targets) return fail("animation sampler output holds fewer values than its input has keys times the morph targets");
+            for (size_t v = 0; v < nt * (size_t)n_targets; v++)
+                if (!std::isfinite(values[v])) return fail("animation sampler output holds a non-finite value");
+            const double time = (double)time_seconds;
+            size_t i = 0;
+            double u = 0.0;
+            if (time <= (double)times[0]) i = 0;
+            else if (time >= (double)times[nt - 1]) i = nt - 1;
+            else {
+                size_t lo = 0, hi = nt - 1;                                          // times[lo] <= time < times[hi]
+                while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if ((double)times[mid] <= time) lo = mid; else hi = mid; }
+                i = lo;
+                if (mode == "LINEAR") u = (time - (double)times[i]) / ((double)times[i + 1] - (double)times[i]);
+            }
+            for (uint32_t k = 0; k < n_targets; k++) {
+                const double a = values[i * n_targets + k], b = values[(u > 0.0 ? i + 1 : i) * n_targets + k];
+                weights_out[k] = (float)(u > 0.0 ? a + u * (b - a) : a);
+            }
+            return true;
+        }
+        return true;
+    }
+
     // One channel at `time` (clamped to the first / last key), in double from the fp32 keys, rounded once: out[3] or out[4].
     // Rotations: spherical linear interpolation along the shorter arc between the normalised keys; every sampled rotation is normalised.
     static void sample_channel(const Channel& k, double time, float* out) {
@@ -1218,6 +1356,26 @@ int sr_gltf_pose(const SrGltf* g, int32_t animation, float time_seconds, SrTrans
     if (animation < -1) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_pose: the animation is an index, or -1 for the file's static pose");
     srh::GltfLoader* L = rig_loader(g);
     if (!L->pose(animation, time_seconds, instance_transforms, skin, joint_matrices)) return srh::set_error(L->err_code, "sr_gltf_pose: " + L->err);
+    return SR_OK;
+}
+
+int sr_gltf_blas_morph(const SrGltf* g, uint32_t blas, uint32_t* n_targets, const SrMorphDelta** deltas, uint32_t* n_vertices, const float** default_weights) {
+    if (!g) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_blas_morph: null argument");
+    srh::GltfLoader* L = rig_loader(g);
+    const srh::GltfLoader::BlasMorph* b = L->blas_morph(blas);
+    if (!b) return srh::set_error(L->err_code, "sr_gltf_blas_morph: " + L->err);
+    if (n_targets) *n_targets = b->n_targets;
+    if (deltas) *deltas = b->n_targets ? b->deltas.data() : nullptr;
+    if (n_vertices) *n_vertices = (uint32_t)g->scene.blases[blas].vertices.size();
+    if (default_weights) *default_weights = b->n_targets ? b->default_weights.data() : nullptr;
+    return SR_OK;
+}
+
+int sr_gltf_morph_weights(const SrGltf* g, int32_t animation, float time_seconds, uint32_t blas, float* weights_out, uint32_t n_targets) {
+    if (!g || (!weights_out && n_targets)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_morph_weights: null argument");
+    if (animation < -1) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_morph_weights: the animation is an index, or -1 for the file's default weights");
+    srh::GltfLoader* L = rig_loader(g);
+    if (!L->morph_weights(animation, time_seconds, blas, weights_out, n_targets)) return srh::set_error(L->err_code, "sr_gltf_morph_weights: " + L->err);
     return SR_OK;
 }
 

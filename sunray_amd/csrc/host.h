@@ -107,8 +107,8 @@ int set_error(int code, const std::string& msg);
 // A further replica of a renderer takes vertices that sr_scene_update_mesh_device has validated on `src_device` (api.cpp): the
 // copy into the mesh's allocation (peer copy across devices) and the state of that call, without a second pass over the bytes.
 int scene_take_device_vertices(SrScene* scene, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, int src_device);
-// The scratch buffer on the scene's device that the last accepted sr_scene_skin_mesh posed into (api.cpp): what the further
-// replicas of a renderer take through scene_take_device_vertices, and the vertex count of the mesh `key` that was posed. Valid until
-// the scene's next sr_scene_skin_mesh.
+// The scratch buffer on the scene's device that the last accepted sr_scene_skin_mesh or sr_scene_pose_mesh posed into (api.cpp):
+// what the further replicas of a renderer take through scene_take_device_vertices, and the vertex count of the mesh `key` that was
+// posed. Valid until the scene's next sr_scene_skin_mesh or sr_scene_pose_mesh.
 const SrVertex* scene_skinned_vertices(const SrScene* scene, uint64_t key, uint32_t* n_vertices);
 }  // namespace srh

@@ -533,6 +533,43 @@ int sr_renderer_skin_mesh(SrRenderer* r, uint64_t key, const SrTransform* joint_
     return rc;
 }
 
+// A mesh's morph lives on the first slot's scene only, like its rig.
+int sr_renderer_set_mesh_morph(SrRenderer* r, uint64_t key, const SrMorphDelta* deltas, uint32_t n_vertices, uint32_t n_targets) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "set_mesh_morph: null argument (the renderer)");
+    return sr_scene_set_mesh_morph(srmr::scenes(r)[0], key, deltas, n_vertices, n_targets);
+}
+
+// sr_scene_pose_mesh on the first slot's scene, which morphs, skins and validates once; the further replicas take the validated
+// bytes from that scene's scratch buffer as in sr_renderer_skin_mesh. What the first scene refuses changes none.
+int sr_renderer_pose_mesh(SrRenderer* r, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "pose_mesh: null argument (the renderer)");
+    const std::vector<SrScene*> scenes = srmr::scenes(r);
+    int rc = sr_scene_pose_mesh(scenes[0], key, weights, n_targets, joint_matrices, n_joints, stream);
+    if (rc != SR_OK) return rc;
+    r->instances_valid = false;
+    uint32_t n_vertices = 0;
+    const SrVertex* posed = srh::scene_skinned_vertices(scenes[0], key, &n_vertices);
+    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_take_device_vertices(scenes[i], key, posed, n_vertices, r->device);
+    return rc;
+}
+
+// The morph targets of a loaded scene, as sr_renderer_attach_skins attaches its rigs.
+int sr_renderer_attach_morphs(SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls) {
+    if (!r || !g || !ls) return rfail(SR_ERR_INVALID_ARG, "attach_morphs: null argument");
+    uint32_t n_blases = 0;
+    int rc = sr_gltf_counts(g, &n_blases, nullptr, nullptr, nullptr, nullptr);
+    if (rc != SR_OK) return rc;
+    if (n_blases != ls->keys.size()) return rfail(SR_ERR_INVALID_ARG, "attach_morphs: the loaded scene does not come from this file (another number of meshes)");
+    for (uint32_t b = 0; b < n_blases; b++) {
+        const SrMorphDelta* deltas = nullptr; uint32_t nv = 0, n_targets = 0;
+        if ((rc = sr_gltf_blas_morph(g, b, &n_targets, &deltas, &nv, nullptr)) != SR_OK) return rc;
+        if (n_targets == 0) continue;
+        if ((rc = sr_renderer_set_mesh_morph(r, ls->keys[b], deltas, nv, n_targets)) != SR_OK) return rc;
+        if ((rc = sr_renderer_set_mesh_build_type(r, ls->keys[b], SR_BUILD_RAPIDLY_CHANGING)) != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+
 // The rigs of a loaded scene: keys are in blas order (sr_renderer_load_scene), so blas b of the file is loaded->keys[b].
 int sr_renderer_attach_skins(SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls) {
     if (!r || !g || !ls) return rfail(SR_ERR_INVALID_ARG, "attach_skins: null argument");
@@ -559,14 +596,28 @@ int sr_renderer_pose_scene(SrRenderer* r, const SrGltf* g, const SrLoadedScene* 
     if (n_blases != ls->keys.size() || n_instances != ls->transforms.size()) return rfail(SR_ERR_INVALID_ARG, "pose_scene: the loaded scene does not come from this file (another number of meshes or instances)");
     std::vector<SrTransform> posed(n_instances), joints;
     if ((rc = sr_gltf_pose(g, animation, time_seconds, posed.data(), 0, nullptr)) != SR_OK) return rc;
+    std::vector<float> weights;
     for (uint32_t b = 0; b < n_blases; b++) {
+        // a mesh with a morph attached (sr_renderer_attach_morphs) is posed by sr_renderer_pose_mesh, with its joint matrices where
+        // it is skinned too; the file's targets are not even parsed for a mesh without one, so a scene on which attach_morphs
+        // was never called is posed as before
+        SrMeshMorphInfo mi;
+        if ((rc = sr_scene_mesh_morph_info(srmr::scenes(r)[0], ls->keys[b], &mi)) != SR_OK) return rc;
         int32_t skin = -1; uint32_t n_joints = 0;
         if ((rc = sr_gltf_blas_skin(g, b, &skin, nullptr, nullptr)) != SR_OK) return rc;
-        if (skin < 0) continue;
-        if ((rc = sr_gltf_skin(g, (uint32_t)skin, &n_joints, nullptr, nullptr)) != SR_OK) return rc;
-        joints.resize(n_joints);
-        if ((rc = sr_gltf_pose(g, animation, time_seconds, nullptr, (uint32_t)skin, joints.data())) != SR_OK) return rc;
-        if ((rc = sr_renderer_skin_mesh(r, ls->keys[b], joints.data(), n_joints, stream)) != SR_OK) return rc;
+        if (skin < 0 && mi.n_targets == 0) continue;
+        if (skin >= 0) {
+            if ((rc = sr_gltf_skin(g, (uint32_t)skin, &n_joints, nullptr, nullptr)) != SR_OK) return rc;
+            joints.resize(n_joints);
+            if ((rc = sr_gltf_pose(g, animation, time_seconds, nullptr, (uint32_t)skin, joints.data())) != SR_OK) return rc;
+        }
+        if (mi.n_targets == 0) {
+            if ((rc = sr_renderer_skin_mesh(r, ls->keys[b], joints.data(), n_joints, stream)) != SR_OK) return rc;
+            continue;
+        }
+        weights.resize(mi.n_targets);
+        if ((rc = sr_gltf_morph_weights(g, animation, time_seconds, b, weights.data(), mi.n_targets)) != SR_OK) return rc;
+        if ((rc = sr_renderer_pose_mesh(r, ls->keys[b], weights.data(), mi.n_targets, skin >= 0 ? joints.data() : nullptr, n_joints, stream)) != SR_OK) return rc;
     }
     if (instance_transforms_out) {              // grouped by blas, the order of the file kept within a group (sr_renderer_load_scene)
         size_t o = 0;

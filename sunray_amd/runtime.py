@@ -59,6 +59,35 @@ def _joint_matrices(matrices):
     return np.ascontiguousarray(matrices), len(matrices)
 
 
+def _morph_deltas(deltas):
+    """The deltas of set_mesh_morph as a contiguous abi.MORPH_DELTA array of shape (n_targets, n_vertices) -> (array, n_targets,
+    n_vertices); ValueError for anything else (no conversion: a float array read as records would attach nonsense)."""
+    if not isinstance(deltas, np.ndarray) or deltas.dtype != abi.MORPH_DELTA:
+        raise ValueError("set_mesh_morph: the deltas must be a numpy array of abi.MORPH_DELTA records")
+    if deltas.ndim != 2 or deltas.shape[0] == 0 or deltas.shape[1] == 0:
+        raise ValueError("set_mesh_morph: the deltas must be target-major, shape (n_targets, n_vertices) (shape %s given)" % (deltas.shape,))
+    return np.ascontiguousarray(deltas), deltas.shape[0], deltas.shape[1]
+
+
+def _morph_weights(weights):
+    """The weights of pose_mesh as a contiguous float32 array, one per target -> (array, n_targets); ValueError for another dtype
+    (no silent narrowing of float64) or shape."""
+    if not isinstance(weights, np.ndarray) or weights.dtype != np.dtype(np.float32):
+        raise ValueError("pose_mesh: the weights must be a numpy float32 array")
+    if weights.ndim != 1 or len(weights) == 0:
+        raise ValueError("pose_mesh: the weights must be one per target, in one dimension (shape %s given)" % (weights.shape,))
+    return np.ascontiguousarray(weights), len(weights)
+
+
+def _pose_args(weights, joint_matrices):
+    """(weights pointer, n_targets, matrices pointer, n_joints, the arrays kept alive) of a pose_mesh call; either may be None."""
+    if weights is None and joint_matrices is None:
+        raise ValueError("pose_mesh: neither weights nor joint matrices given")
+    w, nt = _morph_weights(weights) if weights is not None else (None, 0)
+    m, nj = _joint_matrices(joint_matrices) if joint_matrices is not None else (None, 0)
+    return (None if w is None else _p(w)), C.c_uint32(nt), (None if m is None else _p(m)), C.c_uint32(nj), (w, m)
+
+
 def camera_matrices(pos, target, fov_y, width, height, prev_view_proj=None):
     """Camera::as_matrices + transposed upload (camera.rs:33-63, lib.rs:1017-1048). Host only."""
     m = abi.SrMatrices()
@@ -286,6 +315,29 @@ class Scene:
         matrices. From there on it is an update_mesh_device: the next set_instances applies it (sr_scene_skin_mesh)."""
         m, n = _joint_matrices(joint_matrices)
         check(lib().sr_scene_skin_mesh(self._h, C.c_uint64(key), _p(m), C.c_uint32(n), self._stream()))
+
+    def set_mesh_morph(self, key, deltas):
+        """Attaches morph targets to a loaded mesh: `deltas` is a numpy array of abi.MORPH_DELTA records of shape (n_targets,
+        n_vertices); the mesh's current vertices become the morph base. deltas=None detaches them (sr_scene_set_mesh_morph)."""
+        if deltas is None:
+            check(lib().sr_scene_set_mesh_morph(self._h, C.c_uint64(key), None, C.c_uint32(0), C.c_uint32(0)))
+            return
+        a, nt, nv = _morph_deltas(deltas)
+        check(lib().sr_scene_set_mesh_morph(self._h, C.c_uint64(key), _p(a), C.c_uint32(nv), C.c_uint32(nt)))
+
+    def pose_mesh(self, key, weights=None, joint_matrices=None):
+        """Poses a mesh on the GPU: its morph targets blended with `weights` (float32, one per target; None: no morph stage), then
+        skinned with `joint_matrices` (as skin_mesh; None: no skin stage). From there on it is an update_mesh_device: the next
+        set_instances applies it (sr_scene_pose_mesh)."""
+        wp, nt, mp, nj, keep = _pose_args(weights, joint_matrices)
+        check(lib().sr_scene_pose_mesh(self._h, C.c_uint64(key), wp, nt, mp, nj, self._stream()))
+
+    def mesh_morph_info(self, key):
+        """-> abi.SrMeshMorphInfo: the targets of the mesh's morph (0: none), the poses taken, the active targets, the refusal and
+        the kernel time of the last one."""
+        info = abi.SrMeshMorphInfo()
+        check(lib().sr_scene_mesh_morph_info(self._h, C.c_uint64(key), C.byref(info)))
+        return info
 
     def mesh_skin_info(self, key):
         """-> abi.SrMeshSkinInfo: the joints of the mesh's skin (0: none), the poses taken, the last refusal and kernel time."""
@@ -748,6 +800,24 @@ class Gltf:
         check(lib().sr_gltf_skin(self._h, C.c_uint32(i), C.byref(nj), C.byref(mp), C.byref(jp)))
         return _np_from(mp, nj.value * 12, np.float32).reshape(-1, 12), _np_from(jp, nj.value, np.uint32)
 
+    def blas_morph(self, blas):
+        """-> (abi.MORPH_DELTA array of shape (n_targets, n_vertices), default weights [n_targets] float32) of the blas's morph
+        targets, or (None, None) where it has none (sr_gltf_blas_morph)."""
+        nt, dp, nv, wp = C.c_uint32(), C.c_void_p(), C.c_uint32(), C.c_void_p()
+        check(lib().sr_gltf_blas_morph(self._h, C.c_uint32(blas), C.byref(nt), C.byref(dp), C.byref(nv), C.byref(wp)))
+        if nt.value == 0:
+            return None, None
+        return _np_from(dp, nt.value * nv.value, abi.MORPH_DELTA).reshape(nt.value, nv.value), _np_from(wp, nt.value, np.float32)
+
+    def morph_weights(self, animation, time_seconds, blas):
+        """-> the weights [n_targets] float32 of the blas's morph targets at `time_seconds` of `animation` (-1: the file's default
+        weights) (sr_gltf_morph_weights)."""
+        nt = C.c_uint32()
+        check(lib().sr_gltf_blas_morph(self._h, C.c_uint32(blas), C.byref(nt), None, None, None))
+        w = np.zeros(max(nt.value, 1), dtype=np.float32)
+        check(lib().sr_gltf_morph_weights(self._h, C.c_int32(animation), C.c_float(time_seconds), C.c_uint32(blas), _p(w), nt))
+        return w[:nt.value]
+
     def animation(self, i):
         """-> (name, duration in seconds, channels the file lists, of which `weights` channels that are not sampled)."""
         name, dur, nc, nw = C.c_char_p(), C.c_float(), C.c_uint32(), C.c_uint32()
@@ -950,6 +1020,20 @@ class Renderer:
         m, n = _joint_matrices(joint_matrices)
         check(lib().sr_renderer_skin_mesh(self._h, C.c_uint64(key), _p(m), C.c_uint32(n), None))
 
+    def set_mesh_morph(self, key, deltas):
+        """Scene.set_mesh_morph on the first device slot's scene, which poses for every slot (sr_renderer_set_mesh_morph)."""
+        if deltas is None:
+            check(lib().sr_renderer_set_mesh_morph(self._h, C.c_uint64(key), None, C.c_uint32(0), C.c_uint32(0)))
+            return
+        a, nt, nv = _morph_deltas(deltas)
+        check(lib().sr_renderer_set_mesh_morph(self._h, C.c_uint64(key), _p(a), C.c_uint32(nv), C.c_uint32(nt)))
+
+    def pose_mesh(self, key, weights=None, joint_matrices=None):
+        """Scene.pose_mesh on the first device slot; every further slot takes the posed vertices by a device copy; the next render
+        applies them (sr_renderer_pose_mesh)."""
+        wp, nt, mp, nj, keep = _pose_args(weights, joint_matrices)
+        check(lib().sr_renderer_pose_mesh(self._h, C.c_uint64(key), wp, nt, mp, nj, None))
+
     def set_mesh_build_type(self, key, build_type):
         """abi.BUILD_* of a loaded mesh's tree on every device slot (sr_renderer_set_mesh_build_type)."""
         check(lib().sr_renderer_set_mesh_build_type(self._h, C.c_uint64(key), C.c_uint32(build_type)))
@@ -1009,6 +1093,11 @@ class Renderer:
         """Attaches the rig of every skinned mesh of a loaded scene and makes those meshes BUILD_RAPIDLY_CHANGING
         (sr_renderer_attach_skins)."""
         check(lib().sr_renderer_attach_skins(self._h, gltf._h, loaded._h))
+
+    def attach_morphs(self, gltf, loaded):
+        """Attaches the morph targets of every mesh of a loaded scene that has some and makes those meshes
+        BUILD_RAPIDLY_CHANGING; pose_scene then plays their weight animations too (sr_renderer_attach_morphs)."""
+        check(lib().sr_renderer_attach_morphs(self._h, gltf._h, loaded._h))
 
     def pose_scene(self, gltf, loaded, animation, time_seconds):
         """Poses every skinned mesh of a loaded scene at `time_seconds` of `animation` on the GPU and returns the posed instances,
