@@ -30,6 +30,7 @@ def main():
     ap.add_argument("--out", default="morph.png")
     ap.add_argument("--camera", default="0.8,1.4,7.0,0.8,1.0,0.0,45", help="position, target, vertical field of view in degrees")
     ap.add_argument("--device-lights", action="store_true")
+    ap.add_argument("--batch-trees", action="store_true", help="build the small meshes' trees in one batched device launch when their ninth update asks for a fast build")
     args = ap.parse_args()
     from sunray_amd import runtime as rt
     w, h = (int(v) for v in args.size.split("x"))
@@ -47,6 +48,8 @@ def main():
     r = rt.Renderer((w, h))
     if args.device_lights:
         r.set_light_table_build("device")
+    if args.batch_trees:
+        r.set_mesh_tree_batch("on")
     loaded = r.load_scene(gltf)
     r.attach_skins(gltf, loaded)
     r.attach_morphs(gltf, loaded)

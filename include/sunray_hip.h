@@ -679,6 +679,33 @@ typedef struct SrMeshTreeInfo {
     double device_build_ms;    /* the device builds of that call, launch to completion (only while sr_scene_enable_timing is on) */
 } SrMeshTreeInfo;              /* 40 bytes */
 int sr_scene_mesh_tree_info(const SrScene* scene, SrMeshTreeInfo* out);
+
+/* Batched device build of small mesh trees (off by default). After eight refits an updatable mesh's ninth update is a fast build;
+ * the per-mesh device build above runs a launch per stage and a stream wait per PLOC iteration and collapse level, which makes
+ * it the slowest path for a small mesh. With SR_BLAS_BATCH_ON the pending meshes of at most SR_BLAS_BATCH_MAX_TRIS triangles
+ * are built by one launch, one workgroup per mesh (a few launches where the batch's scratch exceeds 256 MiB), with one
+ * read-back for all of them: the same sort, the SR_FAST_BUILD topology, collapse, records and refit as the per-mesh build, so
+ * the trees are the same up to node numbering. A mesh the kernel hands back (its binary tree is taller than the stack cap, or a
+ * guard tripped) and every larger mesh go through the per-mesh build in the same call and behave as without the batch (refused
+ * and remembered, or rebalanced under SR_HEIGHT_BOUND_REBALANCE). With the batch on, SR_MESH_TREE_BUILD_AUTO sends meshes of
+ * at most SR_BLAS_BATCH_MAX_TRIS triangles to the device (larger ones below auto_threshold still send the call to the host);
+ * SR_MESH_TREE_BUILD_HOST ignores the batch. SR_BLAS_BATCH=on|off in the environment sets the initial mode when the scene is
+ * created (anything else: off). SrMeshTreeInfo.built_on_device counts batched and per-mesh builds together. mode > 1:
+ * SR_ERR_INVALID_ARG, checked before the handle. */
+#define SR_BLAS_BATCH_OFF 0u
+#define SR_BLAS_BATCH_ON 1u
+#define SR_BLAS_BATCH_MAX_TRIS 4096u
+int sr_scene_set_mesh_tree_batch(SrScene* scene, uint32_t mode);
+typedef struct SrMeshTreeBatchInfo {
+    uint32_t mode;        /* SR_BLAS_BATCH_* in force */
+    uint32_t max_tris;    /* SR_BLAS_BATCH_MAX_TRIS */
+    uint32_t batched;     /* mesh trees the last sr_scene_set_instances built in batched launches */
+    uint32_t passed_on;   /* meshes small enough for the batch that it handed to the per-mesh build (too tall, failed) */
+    uint32_t launches;    /* batched launches of that call */
+    uint32_t reserved;
+    double batch_ms;      /* upload + launches + read-back, with timing on */
+} SrMeshTreeBatchInfo;    /* 32 bytes */
+int sr_scene_mesh_tree_batch_info(const SrScene* scene, SrMeshTreeBatchInfo* out);
 /* What a device fast build does with a binary tree that is taller than its stack cap (26 entries for a mesh tree, what the mesh
  * trees leave of 47 for the top level, 47 for the one-level form). SR_HEIGHT_BOUND_REFUSE (default): the build is refused and the
  * host builds (SR_MESH_TREE_HOST_STACK_BUDGET, SR_TL_HOST_STACK_BUDGET, the host SAH build of the one-level form).
@@ -1029,6 +1056,8 @@ int sr_renderer_attach_morphs(SrRenderer* renderer, const SrGltf* gltf, const Sr
 int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t build_type);
 /* sr_scene_set_mesh_tree_build on every device slot's scene. */
 int sr_renderer_set_mesh_tree_build(SrRenderer* renderer, uint32_t mode);
+/* sr_scene_set_mesh_tree_batch on every device slot's scene. */
+int sr_renderer_set_mesh_tree_batch(SrRenderer* renderer, uint32_t mode);
 /* sr_scene_set_tree_height_bound on every device slot's scene. */
 int sr_renderer_set_tree_height_bound(SrRenderer* renderer, uint32_t mode, uint32_t mesh_tree_cap);
 /* sr_scene_set_light_table_build on every device slot's scene, and sr_scene_light_table_info of one slot's scene. */

@@ -13,11 +13,16 @@ Cases: one deforming sphere of 1 k, 4 k, 21 k, 65 k, 250 k and 1 M triangles (fo
 of 1 k triangles each, all at their ninth update. Median (min-max) of 20 calls after 3 warm-ups, every step in a fresh child
 process under its own time limit; stops at the first step that fails.
 
-  python scripts/gpu_mesh_tree_build.py [--out profiles/mesh_tree_build.json] [--label NAME] [--only CASE] [--leg rebalance]
+  python scripts/gpu_mesh_tree_build.py [--out profiles/mesh_tree_build.json] [--label NAME] [--only CASE] [--leg rebalance | batch]
 
 --leg rebalance (-> profiles/mesh_tree_rebalance.json): the device steps run under SR_HEIGHT_BOUND_REBALANCE (MODE = rebalance:
 a tree taller than 26 entries is made to fit on the device instead of going to the host) and record height before / after and what
 was rebuilt; the threshold derived is the one SR_MESH_TREE_BUILD_AUTO uses under that switch (kBlasDeviceMinTrisBounded).
+
+--leg batch (-> profiles/mesh_tree_batch.json): the small-mesh cases 1k, 4k, 100x1k, 100x4k and 1000x256, each on the host, on the
+device per mesh (MODE = device) and on the device through the batched build (MODE = batch: sr_scene_set_mesh_tree_batch, one launch,
+a workgroup per mesh); the batched steps record how many meshes the batch built, handed on, and in how many launches. The claim it
+tests: batched beats both the host and the parent commit by more than the two spreads combined (`batch_verdict` per case).
 
 A library without sr_scene_set_mesh_tree_build (SUNRAY_HIP_LIB pointing at a build of an older commit) runs the host steps only;
 --label keeps its figures apart (e.g. --label parent) in the same output file. With the labels `this` and `parent` both present
@@ -36,12 +41,20 @@ import gpu_mesh_refit as base  # noqa: E402  (the scenes, the statistics and the
 REPS, WARMUP = base.REPS, base.WARMUP
 base.CASES["4k"] = (64, 33, 1)
 base.CASES["65k"] = (256, 129, 1)
+base.CASES["100x4k"] = (64, 33, 100)
+base.CASES["1000x256"] = (16, 9, 1000)
 ORDER = ["1k", "4k", "21k", "65k", "250k", "1m", "100x1k"]
+BATCH_ORDER = ["1k", "4k", "100x1k", "100x4k", "1000x256"]
 
 
 def has_tree_build():
     from sunray_amd._lib import lib
     return hasattr(lib(), "sr_scene_set_mesh_tree_build")
+
+
+def has_batch():
+    from sunray_amd._lib import lib
+    return hasattr(lib(), "sr_scene_set_mesh_tree_batch")
 
 
 def has_height_bound():
@@ -65,7 +78,9 @@ def scene_for(case, mode):
     for k in keys:
         sc.set_mesh_build_type(k, abi.BUILD_RAPIDLY_CHANGING)
     if has_tree_build():
-        sc.set_mesh_tree_build("device" if mode == "rebalance" else mode)
+        sc.set_mesh_tree_build("device" if mode in ("rebalance", "batch") else mode)
+        if mode == "batch":
+            sc.set_mesh_tree_batch("on")
         if mode == "rebalance":
             sc.set_tree_height_bound("rebalance")
     else:
@@ -90,20 +105,28 @@ def step_case(case, mode):
             t_set = base.set_list(sc, arrays)
             i, tl = sc.mesh_update_info(), sc.top_level_info()
             assert sc.two_level() and (i.blas_refitted, i.blas_rebuilt) == (0, len(keys)), (i.blas_refitted, i.blas_rebuilt)
-            dev_ms = 0.0
+            dev_ms = batch_ms = 0.0
             if has_tree_build():
                 ti = tree_info(sc)
                 refused = mode != "host" and ti.reason == abi.MESH_TREE_HOST_STACK_BUDGET      # deeper than a mesh tree may be: the host took over
                 assert (ti.built_on_device, ti.built_on_host) == ((len(keys), 0) if mode != "host" and not refused else (0, len(keys))), (ti.built_on_device, ti.built_on_host, ti.reason)
                 dev_ms = ti.device_build_ms
+            if mode == "batch":
+                bi = sc.mesh_tree_batch_info()
+                assert bi.batched + bi.passed_on == len(keys) and bi.launches >= 1, (bi.batched, bi.passed_on, bi.launches)
+                batch_ms = bi.batch_ms
             if k < WARMUP:
                 continue
             if not timing:
                 wall.append(t_set)
             else:
-                rows.append((i.blas_build_ms, dev_ms, tl.build_ms))
+                rows.append((i.blas_build_ms, dev_ms, tl.build_ms, batch_ms))
     out = {"set_instances_ms": base.stats(wall)}
     out.update({n: base.stats([r[j] for r in rows]) for j, n in enumerate(("host_tree_build_ms", "device_tree_build_ms", "top_level_ms"))})
+    if mode == "batch":
+        bi = sc.mesh_tree_batch_info()
+        out["batch_ms"] = base.stats([r[3] for r in rows])
+        out["batched"], out["passed_on"], out["launches"] = int(bi.batched), int(bi.passed_on), int(bi.launches)
     out["mesh_triangles"], out["meshes"], out["calls"] = len(m.indices) // 3, len(keys), REPS
     if has_tree_build() and mode != "host":
         ti = tree_info(sc)
@@ -183,30 +206,58 @@ def derive_threshold(doc, device="device"):
     return None, "no measured size qualifies: auto mode stays on the host"
 
 
+def batch_verdicts(doc):
+    """-> {case: text}: whether the batched step beats the host, the parent commit's host and the per-mesh device step by more than
+    the two spreads of 20 calls combined."""
+    this, parent = doc.get("this", {}), doc.get("parent", {})
+    spread = lambda s: s["max"] - s["min"]      # noqa: E731
+    out = {}
+    for case in BATCH_ORDER:
+        try:
+            b = this[case]["batch"]["set_instances_ms"]
+        except KeyError:
+            continue
+        said = []
+        for name, other in (("host", this.get(case, {}).get("host")), ("parent", parent.get(case, {}).get("host")), ("device per mesh", this.get(case, {}).get("device"))):
+            if not other:
+                said.append("%s: not measured" % name)
+                continue
+            o = other["set_instances_ms"]
+            gap, both = o["median"] - b["median"], spread(o) + spread(b)
+            said.append("%s: %s (%.3g against %.3g ms, spreads %.3g)" % (name, "wins" if gap > both else "loses" if -gap > both else "within the spreads", b["median"], o["median"], both))
+        out[case] = "; ".join(said)
+    return out
+
+
 def main():
     argv = sys.argv[1:]
     if argv[:1] == ["--step"]:
         print(json.dumps(step_quality(*argv[2:4]) if argv[1] == "quality" else step_case(argv[1], argv[2])))
         return
-    device = "rebalance" if "--leg" in argv and argv[argv.index("--leg") + 1] == "rebalance" else "device"
-    out_path = argv[argv.index("--out") + 1] if "--out" in argv else os.path.join(ROOT, "profiles", "mesh_tree_rebalance.json" if device == "rebalance" else "mesh_tree_build.json")
+    leg = argv[argv.index("--leg") + 1] if "--leg" in argv else ""
+    device = "rebalance" if leg == "rebalance" else "device"
+    default_out = {"rebalance": "mesh_tree_rebalance.json", "batch": "mesh_tree_batch.json"}.get(leg, "mesh_tree_build.json")
+    out_path = argv[argv.index("--out") + 1] if "--out" in argv else os.path.join(ROOT, "profiles", default_out)
     label = argv[argv.index("--label") + 1] if "--label" in argv else "this"
     doc = json.load(open(out_path)) if os.path.exists(out_path) else {}
     doc["workload"] = ("two-level form, sr_scene_set_instances after sr_scene_update_mesh + a forced SR_OP_FAST_BUILD of one deforming sphere (four instances) "
-                       "or of 100 spheres; median (min-max) of %d calls after %d warm-ups, wall clock with the event timing off, the split with it on" % (REPS, WARMUP))
+                       "or of 100 or 1000 spheres; median (min-max) of %d calls after %d warm-ups, wall clock with the event timing off, the split with it on" % (REPS, WARMUP))
     res = doc.setdefault(label, {})
 
     def save():                                                    # after every step: a later failure keeps what was measured
-        doc["auto_threshold"], doc["auto_threshold_rule"] = derive_threshold(doc, device)
+        if leg == "batch":
+            doc["batch_verdict"] = batch_verdicts(doc)
+        else:
+            doc["auto_threshold"], doc["auto_threshold_rule"] = derive_threshold(doc, device)
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         with open(out_path, "w") as f:
             json.dump(doc, f, indent=1, sort_keys=True)
             f.write("\n")
     steps = []
     on_device = has_tree_build() and (device == "device" or has_height_bound())      # an older library runs the host steps only
-    for case in ORDER:
-        steps += [[case, "host"]] + ([[case, device]] if on_device else [])
-    if on_device:
+    for case in (BATCH_ORDER if leg == "batch" else ORDER):
+        steps += [[case, "host"]] + ([[case, device]] if on_device else []) + ([[case, "batch"]] if leg == "batch" and on_device and has_batch() else [])
+    if on_device and leg != "batch":
         steps.append(["quality"])
     if "--only" in argv:
         steps = [x for x in steps if x[0] == argv[argv.index("--only") + 1]]

@@ -31,6 +31,7 @@ SYMBOLS = [
     "sr_scene_update_mesh", "sr_scene_mesh_update_info", "sr_renderer_update_mesh",
     "sr_scene_set_mesh_build_type", "sr_scene_mesh_as_state", "sr_scene_read_mesh_tree", "sr_renderer_set_mesh_build_type",
     "sr_scene_set_mesh_tree_build", "sr_scene_mesh_tree_info", "sr_renderer_set_mesh_tree_build",
+    "sr_scene_set_mesh_tree_batch", "sr_scene_mesh_tree_batch_info", "sr_renderer_set_mesh_tree_batch",
     "sr_scene_set_tree_height_bound", "sr_scene_tree_height_info", "sr_renderer_set_tree_height_bound",
     "sr_scene_update_mesh_device", "sr_scene_mesh_vertex_info", "sr_renderer_update_mesh_device",
     "sr_scene_set_mesh_skin", "sr_scene_skin_mesh", "sr_scene_mesh_skin_info", "sr_renderer_set_mesh_skin", "sr_renderer_skin_mesh",

@@ -205,6 +205,11 @@ class SrMeshTreeInfo(C.Structure):  # the mesh-tree builds of the last sr_scene_
                 ("reason", C.c_uint32), ("n_nodes", C.c_uint32), ("max_stack", C.c_uint32), ("_pad", C.c_uint32), ("device_build_ms", C.c_double)]
 
 
+class SrMeshTreeBatchInfo(C.Structure):  # the batched mesh-tree builds of the last sr_scene_set_instances (sr_scene_mesh_tree_batch_info)
+    _fields_ = [("mode", C.c_uint32), ("max_tris", C.c_uint32), ("batched", C.c_uint32), ("passed_on", C.c_uint32), ("launches", C.c_uint32),
+                ("reserved", C.c_uint32), ("batch_ms", C.c_double)]
+
+
 class SrTreeHeightInfo(C.Structure):  # the last device fast build of one kind of tree (sr_scene_tree_height_info)
     _fields_ = [("mode", C.c_uint32), ("mesh_tree_cap", C.c_uint32), ("on_device", C.c_uint32), ("cap", C.c_uint32),
                 ("height_before", C.c_uint32), ("height_after", C.c_uint32), ("subtrees_rebuilt", C.c_uint32), ("prims_rebuilt", C.c_uint32)]
@@ -213,6 +218,7 @@ class SrTreeHeightInfo(C.Structure):  # the last device fast build of one kind o
 HEIGHT_BOUND_REFUSE, HEIGHT_BOUND_REBALANCE = 0, 1
 TREE_KIND_ONE_LEVEL, TREE_KIND_TOP_LEVEL, TREE_KIND_MESH = 0, 1, 2
 MESH_TREE_BUILD_AUTO, MESH_TREE_BUILD_HOST, MESH_TREE_BUILD_DEVICE = 0, 1, 2
+BLAS_BATCH_OFF, BLAS_BATCH_ON, BLAS_BATCH_MAX_TRIS = 0, 1, 4096  # sr_scene_set_mesh_tree_batch
 (MESH_TREE_ON_DEVICE, MESH_TREE_HOST_MODE, MESH_TREE_HOST_BELOW_THRESHOLD, MESH_TREE_HOST_SLOW_BUILD, MESH_TREE_HOST_BAKED_INSTANCE,
  MESH_TREE_HOST_NOT_RESIDENT, MESH_TREE_HOST_STACK_BUDGET, MESH_TREE_HOST_STATIC_MESH) = range(8)
 MESH_TREE_STACK_CAP = 26  # stack entries a mesh tree of the two-level form may need (csrc/api.cpp)

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "host.h"
+#include "blas_batch.h"
 #include "bvh_gpu.h"
 #include "bvh_layout.h"
 #include "kernels.h"
@@ -232,6 +233,9 @@ struct SrScene {
     SrMeshTreeInfo mt_info{};               // mesh-tree builds of the last sr_scene_set_instances
     bool static_mesh_updated = false;       // a Static mesh was updated since the last sr_scene_set_instances (its tree goes to the host)
     DeviceBuffer d_blas_build_out;          // read-back block of a device mesh-tree build
+    uint32_t blas_batch_mode = SR_BLAS_BATCH_OFF;    // sr_scene_set_mesh_tree_batch / SR_BLAS_BATCH in the environment
+    SrMeshTreeBatchInfo batch_info{};       // the batched builds of the last sr_scene_set_instances
+    DeviceBuffer d_batch_rows, d_batch_results;      // rows and result rows of a batched mesh-tree build (blas_batch.hip)
     DeviceBuffer d_vertex_check;            // the word sr_scene_update_mesh_device's validation kernel and the skinning kernel answer in
     DeviceBuffer d_skin_out, d_skin_matrices;   // sr_scene_skin_mesh: the posed vertices of the last call (scratch) and its joint matrices
     // sr_scene_pose_mesh: the morphed vertices where a skin stage follows (scratch: srk_skin's `bind`; without one the morph stage
@@ -592,6 +596,7 @@ int sr_scene_create(int device, SrScene** out) {
     if (const char* ev = getenv("SR_TILE_SCHEDULING")) s->tile_scheduling = atoi(ev) != 0;
     if (const char* ev = getenv("SR_INSTANCING")) s->instancing = !strcmp(ev, "two_level") ? SR_INSTANCING_TWO_LEVEL : (!strcmp(ev, "flat") ? SR_INSTANCING_FLAT : SR_INSTANCING_AUTO);
     if (const char* ev = getenv("SR_TL_BUILD")) s->tl_build_mode = !strcmp(ev, "host") ? SR_TL_BUILD_HOST : (!strcmp(ev, "device") ? SR_TL_BUILD_DEVICE : SR_TL_BUILD_AUTO);
+    if (const char* ev = getenv("SR_BLAS_BATCH")) s->blas_batch_mode = !strcmp(ev, "on") ? SR_BLAS_BATCH_ON : SR_BLAS_BATCH_OFF;
     if (const char* ev = getenv("SR_BLAS_BUILD")) s->blas_build_mode = !strcmp(ev, "host") ? SR_MESH_TREE_BUILD_HOST : (!strcmp(ev, "device") ? SR_MESH_TREE_BUILD_DEVICE : SR_MESH_TREE_BUILD_AUTO);
     if (const char* ev = getenv("SR_LIGHT_TABLE")) s->light_mode = !strcmp(ev, "device") ? SR_LIGHTS_DEVICE : SR_LIGHTS_HOST;
     if (const char* ev = getenv("SR_FAST_BUILD_HEIGHT")) s->height_bound = !strcmp(ev, "rebalance") ? SR_HEIGHT_BOUND_REBALANCE : SR_HEIGHT_BOUND_REFUSE;
@@ -1573,8 +1578,11 @@ constexpr uint32_t kBlasDeviceMinTris = 0xFFFFFFFFu;
 // 250 000: 129 / 129 / 8.34, 1 000 000: 406 / 416 / 17.3. The device wins by more than the combined spreads from 20 992 triangles on,
 // which rounds up to 32 768, and every measured size above that is now built on the device: the rule yields 32 768.
 constexpr uint32_t kBlasDeviceMinTrisBounded = 32768;
+// Bytes of scratch slabs one batched launch may hold (sr_scene_set_mesh_tree_batch): 256 MiB, some 220 meshes of
+// SR_BLAS_BATCH_MAX_TRIS triangles or thousands of smaller ones; a larger batch takes ceil(bytes / limit) launches.
+constexpr size_t kBlasBatchScratchBytes = (size_t)256 << 20;
 constexpr uint32_t kBlasStackCap = 26;       // build_blas's limit: leaves the top-level tree at least 18 of the kTlStackCap entries
-static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshUpdateInfo) == 64 && sizeof(SrTreeHeightInfo) == 32 && sizeof(SrMeshVertexInfo) == 40 && sizeof(SrLightTableInfo) == 56, "layouts the harness relies on");
+static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshTreeBatchInfo) == 32 && sizeof(SrMeshUpdateInfo) == 64 && sizeof(SrTreeHeightInfo) == 32 && sizeof(SrMeshVertexInfo) == 40 && sizeof(SrLightTableInfo) == 56, "layouts the harness relies on");
 uint32_t blas_device_min_tris(const SrScene* s) { return s->height_bound == SR_HEIGHT_BOUND_REBALANCE ? kBlasDeviceMinTrisBounded : kBlasDeviceMinTris; }
 
 // Blas::rebuild (blas.rs:285-310) on the device for the meshes of `set` (pending updatable meshes whose state asked for
@@ -1583,6 +1591,9 @@ uint32_t blas_device_min_tris(const SrScene* s) { return s->height_bound == SR_H
 // count than the tree it replaces, and references are indices into d_blas_nodes, so at its first device build a mesh takes a node
 // range of the builder's proven bound (fewer inner nodes than triangles) behind everything in use, and keeps it for later builds;
 // the buffer grows by a device-to-device copy. *reason != SR_MESH_TREE_ON_DEVICE: a tree was refused and the host builds them all.
+// With the batch on (sr_scene_set_mesh_tree_batch) the meshes of at most SR_BLAS_BATCH_MAX_TRIS triangles are first built by
+// srk_blas_batch_build, one workgroup per mesh, with one read-back of all result rows; what is larger, and what the batch hands back
+// (too tall, failed: its ranges are as they were), then goes through srk_blas_build as without the batch.
 int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32_t* reason) {
     int rc;
     uint64_t end = s->blas_node_end;
@@ -1594,7 +1605,79 @@ int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32
     const size_t nm = s->meshes.size();
     srd::TlMeshRow* rows_dev = (s->tl_mesh_rows_current && s->d_tl_mesh_rows.bytes >= nm * sizeof(srd::TlMeshRow)) ? (srd::TlMeshRow*)s->d_tl_mesh_rows.p : nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t m : set) {
+    const bool rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
+    const uint32_t cap = rebalance && s->mesh_tree_cap ? s->mesh_tree_cap : kBlasStackCap;      // binds device builds only
+    // the host's book-keeping of one tree the device built, from the ten-word block and the level ranges
+    auto note_built = [&](SrScene::HostBlas& b, const uint32_t* out, uint32_t max_depth) {
+        s->tl_blas_nodes = s->tl_blas_nodes - b.n_nodes + out[8];
+        memcpy(b.lo, out, 12); memcpy(b.hi, out + 3, 12); memcpy(&b.max_abs_vertex, out + 6, 4); memcpy(&b.max_edge_sum, out + 7, 4);
+        b.n_nodes = out[8]; b.max_stack = out[9]; b.max_depth = max_depth;
+        b.host_stale = true; b.device_built = true;
+    };
+    std::vector<uint32_t> rest;               // what the per-mesh build takes: everything, or what the batch does not take or hands back
+    if (s->blas_batch_mode == SR_BLAS_BATCH_ON) {
+        std::vector<uint32_t> small;
+        for (uint32_t m : set) if (s->mesh_state[m].tree.n_tris >= 1u && s->mesh_state[m].tree.n_tris <= SR_BLAS_BATCH_MAX_TRIS) small.push_back(m);
+        std::vector<srd::BlasBatchResult> results(small.size());
+        if (!small.empty()) {
+            // one launch per kBlasBatchScratchBytes of slabs (a mesh's slab is ~0.3 KB per triangle: a launch holds hundreds of
+            // the largest meshes), all enqueued behind each other on one stream, so they may share the scratch buffer
+            std::vector<srd::BlasBatchRow> rows(small.size());
+            std::vector<uint32_t> launch_first(1, 0u);
+            size_t used = 0, most = 0;
+            for (size_t k = 0; k < small.size(); k++) {
+                const uint32_t m = small[k];
+                SrScene::MeshState& ms = s->mesh_state[m];
+                const uint32_t n = ms.tree.n_tris;
+                if (ms.node_cap == 0) { ms.node_base = (uint32_t)s->blas_node_end; ms.node_cap = n + 64u; s->blas_node_end += ms.node_cap; }
+                const size_t slab = srk_blas_batch_slab_bytes(n, ms.node_cap);
+                if (used != 0 && used + slab > kBlasBatchScratchBytes) { launch_first.push_back((uint32_t)k); used = 0; }
+                srd::BlasBatchRow& r = rows[k];
+                r.vertices = (uint64_t)(uintptr_t)s->meshes[m].d_vertices; r.indices = (uint64_t)(uintptr_t)s->meshes[m].d_indices;
+                r.scratch = (uint64_t)used;                   // offset for now: the buffer may still move
+                r.n_tris = n; r.n_vertices = s->meshes[m].n_vertices;
+                r.mesh_slot = m; r.textured = ms.tree.shade_tex.empty() ? 0u : 1u;
+                r.node_base = ms.node_base; r.node_cap = ms.node_cap; r.tri_base = ms.tri_base;
+                r.stack_floor = std::min(depth_for(n), cap); r.stack_cap = cap; r._pad = 0u;
+                used += slab; most = std::max(most, used);
+            }
+            launch_first.push_back((uint32_t)small.size());
+            if ((rc = s->d_scratch.reserve(most)) != SR_OK || (rc = s->d_batch_rows.reserve(rows.size() * sizeof(srd::BlasBatchRow))) != SR_OK ||
+                (rc = s->d_batch_results.reserve(results.size() * sizeof(srd::BlasBatchResult))) != SR_OK) return rc;
+            for (srd::BlasBatchRow& r : rows) r.scratch += (uint64_t)(uintptr_t)s->d_scratch.p;
+            srd::BlasBatchArrays arrays{};
+            arrays.nodes = (uint32_t*)s->d_blas_nodes.p; arrays.node_box = (float*)s->d_blas_node_box.p;
+            arrays.tris = (float4*)s->d_tris.p; arrays.shade = (float4*)s->d_shade.p; arrays.shade_tex = s->any_textured_tl ? (float4*)s->d_shade_tex.p : nullptr;
+            arrays.slot_of_gid = (uint32_t*)s->d_slot_of_gid.p; arrays.rows = rows_dev;
+            HIP_TRY(hipMemcpyAsync(s->d_batch_rows.p, rows.data(), rows.size() * sizeof(srd::BlasBatchRow), hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemsetAsync(s->d_batch_results.p, 0xFF, results.size() * sizeof(srd::BlasBatchResult), nullptr));      // a status no workgroup writes
+            for (size_t l = 0; l + 1 < launch_first.size(); l++) {
+                const int e = srk_blas_batch_build((const srd::BlasBatchRow*)s->d_batch_rows.p + launch_first[l], launch_first[l + 1] - launch_first[l], arrays,
+                                                   (srd::BlasBatchResult*)s->d_batch_results.p + launch_first[l], s->fast_build_ploc, nullptr);
+                if (e != 0) return fail(SR_ERR_HIP, std::string("batched mesh-tree build failed: ") + hipGetErrorString((hipError_t)e));
+            }
+            HIP_TRY(hipMemcpy(results.data(), s->d_batch_results.p, results.size() * sizeof(srd::BlasBatchResult), hipMemcpyDeviceToHost));   // the only wait
+            s->batch_info.launches = (uint32_t)launch_first.size() - 1u;
+            if (s->timing) s->batch_info.batch_ms = ms_between(t0, std::chrono::steady_clock::now());
+        }
+        size_t k = 0;
+        for (uint32_t m : set) {              // in the set's order, so that the per-mesh builds keep theirs
+            if (k >= small.size() || small[k] != m) { rest.push_back(m); continue; }
+            const srd::BlasBatchResult& r = results[k++];
+            SrScene::HostBlas& b = s->mesh_state[m].tree;
+            if (r.status != srd::kBlasBatchBuilt || r.n_levels == 0u || r.n_levels > srd::kBlasBatchMaxLevels || r.out[9] > cap) {
+                s->batch_info.passed_on++; rest.push_back(m); continue;      // too tall or failed: its ranges are as they were
+            }
+            LbvhResult h;
+            h.height_before = h.height_after = r.height;
+            note_tree_height(s, SR_TREE_KIND_MESH, cap, h, true);
+            note_built(b, r.out, r.n_levels);
+            b.level_ranges.clear();
+            for (uint32_t l = 0; l < r.n_levels; l++) b.level_ranges.emplace_back(r.levels[2 * l], r.levels[2 * l + 1]);
+            s->batch_info.batched++;
+        }
+    } else rest = set;
+    for (uint32_t m : rest) {
         SrScene::MeshState& ms = s->mesh_state[m];
         SrScene::HostBlas& b = ms.tree;
         const uint32_t n = b.n_tris;
@@ -1609,8 +1692,6 @@ int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32
         a.slot_of_gid = (uint32_t*)s->d_slot_of_gid.p; a.tri_base = ms.tri_base;
         a.rows = rows_dev; a.out = (uint32_t*)s->d_blas_build_out.p;
         a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
-        const bool rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
-        const uint32_t cap = rebalance && s->mesh_tree_cap ? s->mesh_tree_cap : kBlasStackCap;      // binds device builds only
         a.stack_floor = std::min(depth_for(n), cap); a.stack_cap = cap;
         a.ploc = s->fast_build_ploc;
         a.rebalance = rebalance;
@@ -1625,13 +1706,10 @@ int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32
         }
         uint32_t out[10];
         HIP_TRY(hipMemcpy(out, s->d_blas_build_out.p, sizeof(out), hipMemcpyDeviceToHost));
-        s->tl_blas_nodes = s->tl_blas_nodes - b.n_nodes + out[8];
-        memcpy(b.lo, out, 12); memcpy(b.hi, out + 3, 12); memcpy(&b.max_abs_vertex, out + 6, 4); memcpy(&b.max_edge_sum, out + 7, 4);
-        b.n_nodes = out[8]; b.max_stack = out[9]; b.max_depth = r.max_depth;
+        note_built(b, out, r.max_depth);
         b.level_ranges = r.level_ranges;
-        b.host_stale = true; b.device_built = true;
-        s->mt_info.n_nodes = b.n_nodes; s->mt_info.max_stack = b.max_stack;
     }
+    if (!set.empty()) { s->mt_info.n_nodes = s->mesh_state[set.back()].tree.n_nodes; s->mt_info.max_stack = s->mesh_state[set.back()].tree.max_stack; }
     if (s->timing) s->mt_info.device_build_ms = ms_between(t0, std::chrono::steady_clock::now());   // every build ends with a wait for its stream
     for (uint32_t m : set) {                  // all were taken: they count as built (mark_mesh_trees: SR_OP_FAST_BUILD)
         SrScene::MeshState& ms = s->mesh_state[m];
@@ -1656,6 +1734,7 @@ int maintain_mesh_trees(SrScene* s, uint32_t forced) {
     s->mu_info.blas_refitted = 0;
     SrMeshTreeInfo& ti = s->mt_info;
     ti.built_on_device = ti.built_on_host = 0; ti.reason = SR_MESH_TREE_ON_DEVICE; ti.device_build_ms = 0.0;
+    s->batch_info.batched = s->batch_info.passed_on = s->batch_info.launches = 0u; s->batch_info.batch_ms = 0.0;
     std::vector<uint32_t> set, builds;        // refits, device builds
     bool any_stale = false, any_pending = false, slow = false;
     for (size_t m = 0; m < nm; m++) {
@@ -1681,7 +1760,8 @@ int maintain_mesh_trees(SrScene* s, uint32_t forced) {
     if (reason == SR_MESH_TREE_ON_DEVICE && slow) reason = SR_MESH_TREE_HOST_SLOW_BUILD;
     for (size_t k = 0; reason == SR_MESH_TREE_ON_DEVICE && k < builds.size(); k++) {
         if (s->blas_build_mode == SR_MESH_TREE_BUILD_HOST) reason = SR_MESH_TREE_HOST_MODE;
-        else if (s->blas_build_mode == SR_MESH_TREE_BUILD_AUTO && s->mesh_state[builds[k]].tree.n_tris < blas_device_min_tris(s)) reason = SR_MESH_TREE_HOST_BELOW_THRESHOLD;
+        else if (s->blas_build_mode == SR_MESH_TREE_BUILD_AUTO && s->mesh_state[builds[k]].tree.n_tris < blas_device_min_tris(s) &&
+                 !(s->blas_batch_mode == SR_BLAS_BATCH_ON && s->mesh_state[builds[k]].tree.n_tris <= SR_BLAS_BATCH_MAX_TRIS)) reason = SR_MESH_TREE_HOST_BELOW_THRESHOLD;      // the batch is an opt-in for small meshes
         else if (s->mesh_state[builds[k]].device_refused == s->fast_build_ploc) reason = SR_MESH_TREE_HOST_STACK_BUDGET;     // refused before
     }
     int rc;
@@ -2103,6 +2183,20 @@ int sr_scene_top_level_info(const SrScene* s, SrTopLevelInfo* out) {
     }
     return SR_OK;
 }
+int sr_scene_set_mesh_tree_batch(SrScene* s, uint32_t mode) {
+    if (mode > SR_BLAS_BATCH_ON) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_tree_batch: mode must be SR_BLAS_BATCH_OFF or SR_BLAS_BATCH_ON");
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_tree_batch: scene is null");
+    s->blas_batch_mode = mode;
+    return SR_OK;
+}
+
+int sr_scene_mesh_tree_batch_info(const SrScene* s, SrMeshTreeBatchInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_tree_batch_info: scene or out is null");
+    *out = s->batch_info;
+    out->mode = s->blas_batch_mode; out->max_tris = SR_BLAS_BATCH_MAX_TRIS; out->reserved = 0u;
+    return SR_OK;
+}
+
 int sr_scene_set_mesh_tree_build(SrScene* s, uint32_t mode) {
     if (mode > SR_MESH_TREE_BUILD_DEVICE) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_tree_build: mode must be SR_MESH_TREE_BUILD_AUTO, _HOST or _DEVICE");
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_tree_build: scene is null");

@@ -652,6 +652,17 @@ int sr_renderer_set_mesh_tree_build(SrRenderer* r, uint32_t mode) {
     return SR_OK;
 }
 
+// Whether small pending meshes are built by one batched launch (SR_BLAS_BATCH_*), on every replica.
+int sr_renderer_set_mesh_tree_batch(SrRenderer* r, uint32_t mode) {
+    if (mode > SR_BLAS_BATCH_ON) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_tree_batch: mode must be SR_BLAS_BATCH_OFF or SR_BLAS_BATCH_ON");
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_tree_batch: renderer is null");
+    for (SrScene* sc : srmr::scenes(r)) {
+        int rc = sr_scene_set_mesh_tree_batch(sc, mode);
+        if (rc != SR_OK) return rc;
+    }
+    return SR_OK;
+}
+
 // What a device fast build does with a tree taller than its stack cap (SR_HEIGHT_BOUND_*), on every replica.
 int sr_renderer_set_tree_height_bound(SrRenderer* r, uint32_t mode, uint32_t mesh_tree_cap) {
     if (mode > SR_HEIGHT_BOUND_REBALANCE || mesh_tree_cap > 26u || (mesh_tree_cap != 0 && mode == SR_HEIGHT_BOUND_REFUSE))

@@ -363,6 +363,18 @@ class Scene:
         check(lib().sr_scene_set_mesh_tree_build(self._h, C.c_uint32({"auto": 0, "host": 1, "device": 2}[mode])))
         return self
 
+    def set_mesh_tree_batch(self, mode):
+        """"on" | "off": whether pending meshes of at most abi.BLAS_BATCH_MAX_TRIS triangles that ask for a fast build are built by one
+        batched device launch, a workgroup per mesh (sr_scene_set_mesh_tree_batch). Off by default."""
+        check(lib().sr_scene_set_mesh_tree_batch(self._h, C.c_uint32({"off": 0, "on": 1}[mode])))
+        return self
+
+    def mesh_tree_batch_info(self):
+        """-> abi.SrMeshTreeBatchInfo: the batched mesh-tree builds of the last set_instances (built, passed on, launches, milliseconds)."""
+        info = abi.SrMeshTreeBatchInfo()
+        check(lib().sr_scene_mesh_tree_batch_info(self._h, C.byref(info)))
+        return info
+
     def mesh_tree_info(self):
         """-> abi.SrMeshTreeInfo: the mesh-tree builds of the last set_instances (device / host counts, reason, milliseconds)."""
         info = abi.SrMeshTreeInfo()
@@ -1057,6 +1069,11 @@ class Renderer:
         info = abi.SrLightTableInfo()
         check(lib().sr_renderer_light_table_info(self._h, C.c_uint32(int(slot)), C.byref(info)))
         return info
+
+    def set_mesh_tree_batch(self, mode):
+        """Scene.set_mesh_tree_batch on every device slot (sr_renderer_set_mesh_tree_batch)."""
+        check(lib().sr_renderer_set_mesh_tree_batch(self._h, C.c_uint32({"off": 0, "on": 1}[mode])))
+        return self
 
     def mesh_tree_info(self, slot=0):
         """Scene.mesh_tree_info of one device slot's scene."""
