@@ -236,11 +236,11 @@ struct SrScene {
     uint32_t blas_batch_mode = SR_BLAS_BATCH_OFF;    // sr_scene_set_mesh_tree_batch / SR_BLAS_BATCH in the environment
     SrMeshTreeBatchInfo batch_info{};       // the batched builds of the last sr_scene_set_instances
     DeviceBuffer d_batch_rows, d_batch_results;      // rows and result rows of a batched mesh-tree build (blas_batch.hip)
-    DeviceBuffer d_vertex_check;            // the word sr_scene_update_mesh_device's validation kernel and the skinning kernel answer in
+    DeviceBuffer d_vertex_check;            // the check words the validation kernel and the posing kernels answer in (checked_launch)
     DeviceBuffer d_skin_out, d_skin_matrices;   // sr_scene_skin_mesh: the posed vertices of the last call (scratch) and its joint matrices
     // sr_scene_pose_mesh: the morphed vertices where a skin stage follows (scratch: srk_skin's `bind`; without one the morph stage
-    // writes d_skin_out itself), the active list of the last call (n indices, then n weights) and the two stages' check words
-    DeviceBuffer d_morph_out, d_morph_active, d_pose_check;
+    // writes d_skin_out itself), and the active list of the last call (n indices, then n weights)
+    DeviceBuffer d_morph_out, d_morph_active;
     DeviceBuffer d_blas_nodes, d_tl_inst, d_tl_instances;
     // top level built on the device (bvh_gpu.hip srk_tl_*): per-mesh rows the record kernel reads, the instance boxes, its result block
     DeviceBuffer d_tl_mesh_rows, d_tl_boxes, d_tl_result;
@@ -339,6 +339,28 @@ struct ThreeMarkTimer {
     }
 };
 
+// A start / stop event pair that exists only while sr_scene_enable_timing is on. begin() and end() record on the stream the timed
+// work goes to; ms() is read once that stream has been waited for and is 0.0 while timing is off or where an event call failed.
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit EventPair(const SrScene* s) { if (s->timing && (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess)) release(); }
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+    ~EventPair() { release(); }
+    void release() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); a = b = nullptr; }
+    void begin(hipStream_t st) { if (b) (void)hipEventRecord(a, st); }
+    void end(hipStream_t st) { if (b) (void)hipEventRecord(b, st); }
+    double ms() const { float t = 0.0f; return b && hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
+};
+
+// The slot of `key` into *slot, or the refusal in the words of the entry point `who`.
+int find_mesh(const SrScene* s, uint64_t key, const char* who, uint32_t* slot) {
+    const auto it = s->slots.find(key);
+    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, std::string(who) + ": no mesh is registered under this key");
+    *slot = it->second;
+    return SR_OK;
+}
+
 // This mesh's tree no longer matches its vertices: the next build rebuilds it on the host (upload_mesh_trees) and
 // re-concatenates the device arrays; a pending refit is dropped with it. Every caller gets all five assignments, also where
 // one is a no-op there, because of what holds everywhere: refit_pending implies a valid tree of an updatable mesh; a tree that
@@ -368,9 +390,7 @@ int fetch_host_vertices(SrScene* s, uint32_t slot) {
 // What the two update calls refuse before anything else happens, with one text each: the slot of `key` into *slot.
 int check_mesh_update(SrScene* s, uint64_t key, const void* vertices, uint32_t n_vertices, uint32_t* slot) {
     if (!s || !vertices) return fail(SR_ERR_INVALID_ARG, "update_mesh: null argument");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "update_mesh: no mesh is registered under this key");
-    *slot = it->second;
+    if (const int rc = find_mesh(s, key, "update_mesh", slot); rc != SR_OK) return rc;
     const srh::HostMesh& m = s->meshes[*slot];
     if (n_vertices != m.n_vertices) {
         char buf[160];
@@ -456,14 +476,11 @@ int refresh_host_arena(SrScene* s) {
 // like the other kernels of sr_scene_set_instances, and waited for here: the passes run on streams of their own.
 int device_light_table(SrScene* s) {
     SrLightTableInfo& li = s->lt_info;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    bool timed = s->timing != 0;
-    for (hipEvent_t& x : ev) timed = timed && hipEventCreate(&x) == hipSuccess;
-    struct Free { hipEvent_t* ev; ~Free() { for (int i = 0; i < 4; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } free_events{ev};
-    if (timed) (void)hipEventRecord(ev[0], nullptr);
+    EventPair positions(s), table(s);
+    positions.begin(nullptr);
     int rc = sync_device_arena(s, &li.positions_rewritten, &li.arena_uploads);
     if (rc != SR_OK) return rc;
-    if (timed) (void)hipEventRecord(ev[1], nullptr);
+    positions.end(nullptr);
     const std::vector<SrEmissiveIndirectionEntry>& entries = s->fid.emissive_entries;
     const size_t entry_bytes = sizeof(SrEmissiveIndirectionEntry) * entries.size();
     if (s->entries_on_device.size() != entries.size() || memcmp(s->entries_on_device.data(), entries.data(), entry_bytes) != 0) {
@@ -472,15 +489,14 @@ int device_light_table(SrScene* s) {
         li.entries_uploaded = 1;
     }
     if ((rc = s->d_lights.reserve(entries.size() * 64)) != SR_OK) return rc;
-    if (timed) (void)hipEventRecord(ev[2], nullptr);
+    table.begin(nullptr);
     const int e = srk_light_table((const SrEmissiveIndirectionEntry*)s->d_light_entries.p, (uint32_t)entries.size(), (const SrEmissiveTriangle*)s->d_arena.p,
                                   s->arena_device_entries, (const srd::FlatInstance*)s->d_flat_instances.p, (uint32_t)s->fid.instances.size(),
                                   (float*)s->d_lights.p, nullptr);
     if (e != 0) return fail(SR_ERR_HIP, std::string("light table launch failed: ") + hipGetErrorString((hipError_t)e));
-    if (timed) (void)hipEventRecord(ev[3], nullptr);
+    table.end(nullptr);
     HIP_TRY(hipStreamSynchronize(nullptr));
-    float a = 0.0f, b = 0.0f;
-    if (timed && hipEventElapsedTime(&a, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&b, ev[2], ev[3]) == hipSuccess) { li.positions_ms += a; li.table_ms += b; }
+    li.positions_ms += positions.ms(); li.table_ms += table.ms();
     li.on_device = 1;
     return SR_OK;
 }
@@ -517,16 +533,13 @@ int take_device_vertices(SrScene* s, uint32_t slot, const SrVertex* d_vertices, 
     srh::HostMesh& m = s->meshes[slot];
     const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
     HIP_TRY(hipDeviceSynchronize());
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = s->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    if (timed) (void)hipEventRecord(ev[0], nullptr);
+    EventPair timer(s);
+    timer.begin(nullptr);
     hipError_t e = src_device == s->device ? hipMemcpyAsync(m.d_vertices, d_vertices, bytes, hipMemcpyDeviceToDevice, nullptr)
                                            : hipMemcpyPeerAsync(m.d_vertices, s->device, d_vertices, src_device, bytes, nullptr);
-    if (timed) (void)hipEventRecord(ev[1], nullptr);
+    timer.end(nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    float ms = 0.0f;
-    m.copy_ms = (timed && e == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ? (double)ms : 0.0;
-    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    m.copy_ms = e == hipSuccess ? timer.ms() : 0.0;
     HIP_TRY(e);
     m.host_stale = true; m.last_from_device = true;
     if (m.emissive_slots.empty()) return SR_OK;
@@ -535,6 +548,63 @@ int take_device_vertices(SrScene* s, uint32_t slot, const SrVertex* d_vertices, 
         return SR_OK;
     }
     return fetch_host_vertices(s, slot);
+}
+
+// SrMeshUpdateInfo of an update that entered at t0, copied between t1 and t2 and ends now.
+void note_update_times(SrScene* s, std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1, std::chrono::steady_clock::time_point t2) {
+    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, std::chrono::steady_clock::now());
+    s->mu_info.h2d_ms = ms_between(t1, t2);
+}
+
+// The middle of a device producer. `upload()` puts what the kernels read on `st`, `enqueue(check)` the producer's kernels; each
+// answers in a word of `check` (the srk_* launches preset theirs to 0xFFFFFFFF). Both return a hipError_t as int: not 0, nothing
+// more is enqueued. The timing pair brackets the kernels and the one read-back of `n_words` words into `bad`, the stream is
+// waited for, and *ms is the bracketed time (0.0 with timing off). A HIP failure is refused in the caller's words `what`.
+template <class Upload, class Enqueue>
+int checked_launch(SrScene* s, hipStream_t st, uint32_t n_words, uint32_t* bad, double* ms, const char* what, Upload upload, Enqueue enqueue) {
+    EventPair timer(s);
+    int e = upload();
+    timer.begin(st);
+    if (e == 0) e = enqueue((uint32_t*)s->d_vertex_check.p);
+    if (e == 0) e = (int)hipMemcpyAsync(bad, s->d_vertex_check.p, 4 * (size_t)n_words, hipMemcpyDeviceToHost, st);
+    timer.end(st);
+    if (e == 0) e = (int)hipStreamSynchronize(st);
+    if (e != 0) return fail(SR_ERR_HIP, std::string(what) + hipGetErrorString((hipError_t)e));
+    *ms = timer.ms();
+    return SR_OK;
+}
+
+// The tail of every path that hands a mesh vertices already validated on a device (sr_scene_update_mesh_device, the pose path,
+// the replicas of a renderer): the copy into the mesh's allocation, check_ms (the time of a validation kernel of its own, 0.0
+// where the check was part of the producer or ran on another scene), what follows from new vertices, and SrMeshUpdateInfo of a
+// call that entered at t0. The next device producer is its own refusals and kernels, checked_launch and this.
+int finish_device_update(SrScene* s, uint32_t slot, const SrVertex* d_vertices, int src_device, double check_ms, std::chrono::steady_clock::time_point t0) {
+    const auto t1 = std::chrono::steady_clock::now();
+    const int rc = take_device_vertices(s, slot, d_vertices, src_device);
+    if (rc != SR_OK) return rc;
+    const auto t2 = std::chrono::steady_clock::now();
+    s->meshes[slot].check_ms = check_ms;
+    mesh_vertices_changed(s, slot);
+    note_update_times(s, t0, t1, t2);
+    return SR_OK;
+}
+
+// What sr_scene_set_mesh_skin and sr_scene_set_mesh_morph share. Detaching waits for whatever reads the record's buffers.
+template <class Record>
+int detach_record(Record& r) {
+    HIP_TRY(hipDeviceSynchronize());
+    r = Record();
+    return SR_OK;
+}
+// The snapshot of a mesh's vertices as they stand on the device (the bind pose, the morph base) into a buffer not yet attached.
+int snapshot_vertices(const srh::HostMesh& m, DeviceBuffer& dst) {
+    const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
+    const int rc = dst.reserve(bytes);
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());                          // whatever still writes the mesh's vertices has finished
+    HIP_TRY(hipMemcpy(dst.p, m.d_vertices, bytes, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    return SR_OK;
 }
 
 }  // namespace
@@ -753,9 +823,7 @@ int sr_scene_update_mesh(SrScene* s, uint64_t key, const SrVertex* vertices, uin
     m.host_stale = false; m.last_from_device = false;         // the host copy is the device buffer's contents again
     s->mesh_state[slot].arena_stale = s->mesh_state[slot].arena_pending = false;   // and the arena slots are the host's again
     mesh_vertices_changed(s, slot);
-    const auto t3 = std::chrono::steady_clock::now();
-    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
-    s->mu_info.h2d_ms = ms_between(t1, t2);
+    note_update_times(s, t0, t1, t2);
     return SR_OK;
 }
 
@@ -791,35 +859,20 @@ int sr_scene_update_mesh_device(SrScene* s, uint64_t key, const SrVertex* d_vert
     }
     if ((rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = s->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    if (timed) (void)hipEventRecord(ev[0], st);
     uint32_t first_bad = 0xFFFFFFFFu;
-    int e = srk_vertex_check(d_vertices, n_vertices, (uint32_t*)s->d_vertex_check.p, st);
-    if (e == 0) e = (int)hipMemcpyAsync(&first_bad, s->d_vertex_check.p, 4, hipMemcpyDeviceToHost, st);
-    if (timed) (void)hipEventRecord(ev[1], st);
-    if (e == 0) e = (int)hipStreamSynchronize(st);
-    float ms = 0.0f;
-    const double check_ms = (timed && e == 0 && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ? (double)ms : 0.0;
-    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-    if (e != 0) return fail(SR_ERR_HIP, std::string("update_mesh: vertex validation failed: ") + hipGetErrorString((hipError_t)e));
+    double check_ms = 0.0;
+    rc = checked_launch(s, st, 1, &first_bad, &check_ms, "update_mesh: vertex validation failed: ", [] { return 0; },
+                        [&](uint32_t* check) { return srk_vertex_check(d_vertices, n_vertices, check, st); });
+    if (rc != SR_OK) return rc;
     if (first_bad < n_vertices) return fail_non_finite_vertex(first_bad);
-    m.check_ms = check_ms;
-    const auto t1 = std::chrono::steady_clock::now();
-    if ((rc = take_device_vertices(s, slot, d_vertices, s->device)) != SR_OK) return rc;
-    const auto t2 = std::chrono::steady_clock::now();
-    mesh_vertices_changed(s, slot);
-    const auto t3 = std::chrono::steady_clock::now();
-    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
-    s->mu_info.h2d_ms = ms_between(t1, t2);
-    return SR_OK;
+    return finish_device_update(s, slot, d_vertices, s->device, check_ms, t0);
 }
 
 int sr_scene_mesh_vertex_info(const SrScene* s, uint64_t key, SrMeshVertexInfo* out) {
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_vertex_info: null argument");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_vertex_info: no mesh is registered under this key");
-    const srh::HostMesh& m = s->meshes[it->second];
+    uint32_t slot = 0;
+    if (const int rc = find_mesh(s, key, "sr_scene_mesh_vertex_info", &slot); rc != SR_OK) return rc;
+    const srh::HostMesh& m = s->meshes[slot];
     memset(out, 0, sizeof(*out));
     out->host_stale = m.host_stale ? 1u : 0u; out->last_from_device = m.last_from_device ? 1u : 0u; out->host_fetches = m.host_fetches;
     out->check_ms = m.check_ms; out->copy_ms = m.copy_ms; out->fetch_ms = m.fetch_ms;
@@ -830,17 +883,11 @@ int sr_scene_mesh_vertex_info(const SrScene* s, uint64_t key, SrMeshVertexInfo* 
 // mesh's record changes, so a refusal or a failed allocation leaves an earlier skin in place.
 int sr_scene_set_mesh_skin(SrScene* s, uint64_t key, const SrSkinInfluence* influences, uint32_t n_vertices, uint32_t n_joints) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "set_mesh_skin: null argument (the scene)");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "set_mesh_skin: no mesh is registered under this key");
-    const uint32_t slot = it->second;
+    uint32_t slot = 0;
+    int rc = find_mesh(s, key, "set_mesh_skin", &slot);
+    if (rc != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
     const srh::HostMesh& m = s->meshes[slot];
-    int rc = bind_device(s);
-    if (rc != SR_OK) return rc;
-    if (!influences) {
-        HIP_TRY(hipDeviceSynchronize());
-        s->mesh_state[slot].skin = SrScene::MeshState::Skin();
-        return SR_OK;
-    }
+    if (!influences) return detach_record(s->mesh_state[slot].skin);
     char buf[200];
     if (n_vertices != m.n_vertices) {
         snprintf(buf, sizeof(buf), "set_mesh_skin: %u influences given, the mesh was loaded with %u vertices", n_vertices, m.n_vertices);
@@ -868,70 +915,105 @@ int sr_scene_set_mesh_skin(SrScene* s, uint64_t key, const SrSkinInfluence* infl
         }
     }
     SrScene::MeshState::Skin skin;
-    const size_t bytes = sizeof(SrVertex) * (size_t)n_vertices;
-    if ((rc = skin.d_bind.reserve(bytes)) != SR_OK || (rc = skin.d_influences.upload(influences, sizeof(SrSkinInfluence) * (size_t)n_vertices)) != SR_OK) return rc;
-    HIP_TRY(hipDeviceSynchronize());                          // whatever still writes the mesh's vertices has finished
-    HIP_TRY(hipMemcpy(skin.d_bind.p, m.d_vertices, bytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipDeviceSynchronize());
+    if ((rc = skin.d_influences.upload(influences, sizeof(SrSkinInfluence) * (size_t)n_vertices)) != SR_OK || (rc = snapshot_vertices(m, skin.d_bind)) != SR_OK) return rc;
     skin.n_joints = n_joints;
     s->mesh_state[slot].skin = std::move(skin);
     return SR_OK;
 }
 
-// sr_scene_update_mesh_device with the library's own producer in front: matrices up, the kernel (posing and the finite-position
-// check in one pass over the bytes) into the scene's scratch buffer, 4-byte read-back, and from there the path of that call.
-int sr_scene_skin_mesh(SrScene* s, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
+namespace {
+
+// sr_scene_skin_mesh and sr_scene_pose_mesh, whose texts begin with `who`: sr_scene_update_mesh_device with the library's own
+// producers in front, in glTF's order, a morph stage (`weights`), a skin stage (`joint_matrices`) or both. The morph kernel reads
+// the morph base; with a skin stage it writes the scene's morph scratch, which the skinning kernel takes as its `bind` in place of
+// the bind pose, and the skinning kernel writes d_skin_out; without one the morph kernel writes d_skin_out itself. Posing and the
+// finite-position check are one pass over the bytes: each stage answers in a check word of its own (the morph stage in word 0,
+// the skin stage in the next), and all come back in one read after the last kernel.
+int pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream, const char* who) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!s || !joint_matrices) return fail(SR_ERR_INVALID_ARG, "skin_mesh: null argument");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "skin_mesh: no mesh is registered under this key");
-    const uint32_t slot = it->second;
+    uint32_t slot = 0;
+    int rc = find_mesh(s, key, who, &slot);
+    if (rc != SR_OK) return rc;
     srh::HostMesh& m = s->meshes[slot];
+    SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
     SrScene::MeshState::Skin& skin = s->mesh_state[slot].skin;
-    if (skin.n_joints == 0) return fail(SR_ERR_INVALID_ARG, "skin_mesh: the mesh has no skin (sr_scene_set_mesh_skin attaches one)");
-    if (n_joints != skin.n_joints) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "skin_mesh: %u joint matrices given, the skin was attached with %u joints", n_joints, skin.n_joints);
-        return fail(SR_ERR_INVALID_ARG, buf);
+    char buf[200];
+    if (weights) {
+        if (morph.n_targets == 0) return fail(SR_ERR_INVALID_ARG, "pose_mesh: the mesh has no morph targets (sr_scene_set_mesh_morph attaches them)");
+        if (n_targets != morph.n_targets) {
+            snprintf(buf, sizeof(buf), "pose_mesh: %u weights given, the morph was attached with %u targets", n_targets, morph.n_targets);
+            return fail(SR_ERR_INVALID_ARG, buf);
+        }
     }
-    int rc = check_emissive_list(m);
-    if (rc != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
-    if ((rc = s->d_skin_out.reserve(sizeof(SrVertex) * (size_t)m.n_vertices)) != SR_OK || (rc = s->d_skin_matrices.reserve(sizeof(SrTransform) * (size_t)n_joints)) != SR_OK ||
-        (rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
+    if (joint_matrices) {
+        if (skin.n_joints == 0) return fail(SR_ERR_INVALID_ARG, std::string(who) + ": the mesh has no skin (sr_scene_set_mesh_skin attaches one)");
+        if (n_joints != skin.n_joints) {
+            snprintf(buf, sizeof(buf), "%s: %u joint matrices given, the skin was attached with %u joints", who, n_joints, skin.n_joints);
+            return fail(SR_ERR_INVALID_ARG, buf);
+        }
+    }
+    // the active list: the targets whose weight is not 0, in ascending order (indices, then weights: one upload)
+    std::vector<uint32_t> active(weights ? 2 * (size_t)n_targets : 0);
+    uint32_t n_active = 0;
+    for (uint32_t k = 0; weights && k < n_targets; k++) {
+        if (!std::isfinite(weights[k])) {
+            snprintf(buf, sizeof(buf), "pose_mesh: weight %u is not finite", k);
+            return fail(SR_ERR_INVALID_ARG, buf);
+        }
+        if (weights[k] != 0.0f) { active[n_active] = k; memcpy(&active[(size_t)n_targets + n_active], &weights[k], 4); n_active++; }
+    }
+    if ((rc = check_emissive_list(m)) != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
+    const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
+    if ((rc = s->d_skin_out.reserve(bytes)) != SR_OK || (rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
+    if (weights && (rc = s->d_morph_active.reserve(8 * (size_t)n_targets)) != SR_OK) return rc;
+    if (weights && joint_matrices && (rc = s->d_morph_out.reserve(bytes)) != SR_OK) return rc;
+    if (joint_matrices && (rc = s->d_skin_matrices.reserve(sizeof(SrTransform) * (size_t)n_joints)) != SR_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = s->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    int e = (int)hipMemcpyAsync(s->d_skin_matrices.p, joint_matrices, sizeof(SrTransform) * (size_t)n_joints, hipMemcpyHostToDevice, st);
-    if (timed) (void)hipEventRecord(ev[0], st);
-    uint32_t first_bad = 0xFFFFFFFFu;
-    if (e == 0) e = srk_skin((const SrVertex*)skin.d_bind.p, (const SrSkinInfluence*)skin.d_influences.p, (const SrTransform*)s->d_skin_matrices.p,
-                             (SrVertex*)s->d_skin_out.p, m.n_vertices, (uint32_t*)s->d_vertex_check.p, st);
-    if (e == 0) e = (int)hipMemcpyAsync(&first_bad, s->d_vertex_check.p, 4, hipMemcpyDeviceToHost, st);
-    if (timed) (void)hipEventRecord(ev[1], st);
-    if (e == 0) e = (int)hipStreamSynchronize(st);
-    float ms = 0.0f;
-    const double skin_ms = (timed && e == 0 && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ? (double)ms : 0.0;
-    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-    if (e != 0) return fail(SR_ERR_HIP, std::string("skin_mesh: the skinning kernel failed: ") + hipGetErrorString((hipError_t)e));
-    skin.first_bad = first_bad < m.n_vertices ? first_bad : 0xFFFFFFFFu;
-    if (first_bad < m.n_vertices) return fail_non_finite_vertex(first_bad);
-    const auto t1 = std::chrono::steady_clock::now();
-    if ((rc = take_device_vertices(s, slot, (const SrVertex*)s->d_skin_out.p, s->device)) != SR_OK) return rc;
-    const auto t2 = std::chrono::steady_clock::now();
-    m.check_ms = 0.0;                                         // the check is part of the skinning kernel: SrMeshSkinInfo.skin_ms
-    skin.skin_ms = skin_ms; skin.skinned++;
-    mesh_vertices_changed(s, slot);
-    const auto t3 = std::chrono::steady_clock::now();
-    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
-    s->mu_info.h2d_ms = ms_between(t1, t2);
+    const uint32_t skin_word = weights ? 1 : 0;
+    uint32_t bad[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+    double ms = 0.0;
+    rc = checked_launch(s, st, 1 + skin_word, bad, &ms, weights ? "pose_mesh: a posing kernel failed: " : "skin_mesh: the skinning kernel failed: ", [&] {
+        int e = 0;
+        if (weights) e = (int)hipMemsetAsync(s->d_vertex_check.p, 0xFF, 8, st);     // the skin stage's word where there is none
+        if (e == 0 && weights) e = (int)hipMemcpyAsync(s->d_morph_active.p, active.data(), 8 * (size_t)n_targets, hipMemcpyHostToDevice, st);
+        if (e == 0 && joint_matrices) e = (int)hipMemcpyAsync(s->d_skin_matrices.p, joint_matrices, sizeof(SrTransform) * (size_t)n_joints, hipMemcpyHostToDevice, st);
+        return e;
+    }, [&](uint32_t* check) {
+        const SrVertex* bind = (const SrVertex*)skin.d_bind.p;
+        int k = 0;
+        if (weights) {
+            SrVertex* const morphed = (SrVertex*)(joint_matrices ? s->d_morph_out.p : s->d_skin_out.p);
+            k = srk_morph((const SrVertex*)morph.d_base.p, (const SrMorphDelta*)morph.d_deltas.p, (const uint32_t*)s->d_morph_active.p,
+                          (const float*)s->d_morph_active.p + n_targets, n_active, morphed, m.n_vertices, check, st);
+            bind = morphed;
+        }
+        if (k == 0 && joint_matrices) k = srk_skin(bind, (const SrSkinInfluence*)skin.d_influences.p, (const SrTransform*)s->d_skin_matrices.p,
+                                                   (SrVertex*)s->d_skin_out.p, m.n_vertices, check + skin_word, st);
+        return k;
+    });
+    if (rc != SR_OK) return rc;
+    if (weights) { morph.first_bad = bad[0] < m.n_vertices ? bad[0] : 0xFFFFFFFFu; morph.n_active = n_active; }
+    if (joint_matrices) skin.first_bad = bad[skin_word] < m.n_vertices ? bad[skin_word] : 0xFFFFFFFFu;
+    if (const uint32_t first_bad = std::min(bad[0], bad[1]); first_bad < m.n_vertices) return fail_non_finite_vertex(first_bad);
+    // check_ms 0.0: the check is part of the posing kernels, whose time is SrMeshMorphInfo.morph_ms or SrMeshSkinInfo.skin_ms
+    if ((rc = finish_device_update(s, slot, (const SrVertex*)s->d_skin_out.p, s->device, 0.0, t0)) != SR_OK) return rc;
+    if (weights) { morph.morph_ms = ms; morph.posed++; }
+    if (joint_matrices) { skin.skin_ms = weights ? 0.0 : ms; skin.skinned++; }     // two kernels are timed as one: morph_ms
     return SR_OK;
+}
+
+}  // namespace
+
+int sr_scene_skin_mesh(SrScene* s, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
+    if (!s || !joint_matrices) return fail(SR_ERR_INVALID_ARG, "skin_mesh: null argument");
+    return pose_mesh(s, key, nullptr, 0, joint_matrices, n_joints, stream, "skin_mesh");
 }
 
 int sr_scene_mesh_skin_info(const SrScene* s, uint64_t key, SrMeshSkinInfo* out) {
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_skin_info: null argument");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_skin_info: no mesh is registered under this key");
-    const SrScene::MeshState::Skin& skin = s->mesh_state[it->second].skin;
+    uint32_t slot = 0;
+    if (const int rc = find_mesh(s, key, "sr_scene_mesh_skin_info", &slot); rc != SR_OK) return rc;
+    const SrScene::MeshState::Skin& skin = s->mesh_state[slot].skin;
     memset(out, 0, sizeof(*out));
     out->n_joints = skin.n_joints; out->skinned = skin.skinned; out->first_bad = skin.first_bad; out->skin_ms = skin.skin_ms;
     return SR_OK;
@@ -942,17 +1024,11 @@ int sr_scene_mesh_skin_info(const SrScene* s, uint64_t key, SrMeshSkinInfo* out)
 // morph in place.
 int sr_scene_set_mesh_morph(SrScene* s, uint64_t key, const SrMorphDelta* deltas, uint32_t n_vertices, uint32_t n_targets) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "set_mesh_morph: null argument (the scene)");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "set_mesh_morph: no mesh is registered under this key");
-    const uint32_t slot = it->second;
+    uint32_t slot = 0;
+    int rc = find_mesh(s, key, "set_mesh_morph", &slot);
+    if (rc != SR_OK) return rc;
     const srh::HostMesh& m = s->meshes[slot];
-    if (!deltas) {
-        int rc = bind_device(s);
-        if (rc != SR_OK) return rc;
-        HIP_TRY(hipDeviceSynchronize());
-        s->mesh_state[slot].morph = SrScene::MeshState::Morph();
-        return SR_OK;
-    }
+    if (!deltas) return (rc = bind_device(s)) != SR_OK ? rc : detach_record(s->mesh_state[slot].morph);
     char buf[200];
     if (n_vertices != m.n_vertices) {
         snprintf(buf, sizeof(buf), "set_mesh_morph: targets of %u vertices given, the mesh was loaded with %u vertices", n_vertices, m.n_vertices);
@@ -969,105 +1045,27 @@ int sr_scene_set_mesh_morph(SrScene* s, uint64_t key, const SrMorphDelta* deltas
                 return fail(SR_ERR_INVALID_ARG, buf);
             }
         }
-    int rc = bind_device(s);
-    if (rc != SR_OK) return rc;
+    if ((rc = bind_device(s)) != SR_OK) return rc;
     SrScene::MeshState::Morph morph;
-    const size_t bytes = sizeof(SrVertex) * (size_t)n_vertices;
-    if ((rc = morph.d_base.reserve(bytes)) != SR_OK || (rc = morph.d_deltas.upload(deltas, sizeof(SrMorphDelta) * (size_t)n_vertices * n_targets)) != SR_OK) return rc;
-    HIP_TRY(hipDeviceSynchronize());                          // whatever still writes the mesh's vertices has finished
-    HIP_TRY(hipMemcpy(morph.d_base.p, m.d_vertices, bytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipDeviceSynchronize());
+    if ((rc = morph.d_deltas.upload(deltas, sizeof(SrMorphDelta) * (size_t)n_vertices * n_targets)) != SR_OK || (rc = snapshot_vertices(m, morph.d_base)) != SR_OK) return rc;
     morph.n_targets = n_targets;
     s->mesh_state[slot].morph = std::move(morph);
     return SR_OK;
 }
 
-// The one per-frame call of a mesh with a morph, a skin or both: glTF's order, morph first, then skin. The morph kernel reads the
-// morph base; with a skin stage it writes the scene's morph scratch, which the unchanged skinning kernel takes as its `bind`, and
-// the skinning kernel writes d_skin_out; without one the morph kernel writes d_skin_out itself. Each stage answers in a check word
-// of its own; both come back in one read after the last kernel, and from there it is the path of sr_scene_skin_mesh.
+// The one per-frame call of a mesh with a morph, a skin or both (pose_mesh above); without weights it is sr_scene_skin_mesh.
 int sr_scene_pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
-    const auto t0 = std::chrono::steady_clock::now();
     if (!s) return fail(SR_ERR_INVALID_ARG, "pose_mesh: null argument (the scene)");
     if (!weights && !joint_matrices) return fail(SR_ERR_INVALID_ARG, "pose_mesh: neither weights nor joint matrices given (one stage at least)");
     if (!weights) return sr_scene_skin_mesh(s, key, joint_matrices, n_joints, stream);
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "pose_mesh: no mesh is registered under this key");
-    const uint32_t slot = it->second;
-    srh::HostMesh& m = s->meshes[slot];
-    SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
-    SrScene::MeshState::Skin& skin = s->mesh_state[slot].skin;
-    char buf[200];
-    if (morph.n_targets == 0) return fail(SR_ERR_INVALID_ARG, "pose_mesh: the mesh has no morph targets (sr_scene_set_mesh_morph attaches them)");
-    if (n_targets != morph.n_targets) {
-        snprintf(buf, sizeof(buf), "pose_mesh: %u weights given, the morph was attached with %u targets", n_targets, morph.n_targets);
-        return fail(SR_ERR_INVALID_ARG, buf);
-    }
-    if (joint_matrices) {
-        if (skin.n_joints == 0) return fail(SR_ERR_INVALID_ARG, "pose_mesh: the mesh has no skin (sr_scene_set_mesh_skin attaches one)");
-        if (n_joints != skin.n_joints) {
-            snprintf(buf, sizeof(buf), "pose_mesh: %u joint matrices given, the skin was attached with %u joints", n_joints, skin.n_joints);
-            return fail(SR_ERR_INVALID_ARG, buf);
-        }
-    }
-    // the active list: the targets whose weight is not 0, in ascending order (indices, then weights: one upload)
-    std::vector<uint32_t> active(2 * (size_t)n_targets);
-    uint32_t n_active = 0;
-    for (uint32_t k = 0; k < n_targets; k++) {
-        if (!std::isfinite(weights[k])) {
-            snprintf(buf, sizeof(buf), "pose_mesh: weight %u is not finite", k);
-            return fail(SR_ERR_INVALID_ARG, buf);
-        }
-        if (weights[k] != 0.0f) { active[n_active] = k; memcpy(&active[(size_t)n_targets + n_active], &weights[k], 4); n_active++; }
-    }
-    int rc = check_emissive_list(m);
-    if (rc != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
-    const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
-    if ((rc = s->d_skin_out.reserve(bytes)) != SR_OK || (rc = s->d_morph_active.reserve(8 * (size_t)n_targets)) != SR_OK || (rc = s->d_pose_check.reserve(16)) != SR_OK) return rc;
-    if (joint_matrices && ((rc = s->d_morph_out.reserve(bytes)) != SR_OK || (rc = s->d_skin_matrices.reserve(sizeof(SrTransform) * (size_t)n_joints)) != SR_OK)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    const bool timed = s->timing && hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-    uint32_t* const check = (uint32_t*)s->d_pose_check.p;    // word 0: the morph stage, word 1: the skin stage
-    uint32_t bad[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
-    int e = (int)hipMemsetAsync(check, 0xFF, 8, st);
-    if (e == 0) e = (int)hipMemcpyAsync(s->d_morph_active.p, active.data(), 8 * (size_t)n_targets, hipMemcpyHostToDevice, st);
-    if (e == 0 && joint_matrices) e = (int)hipMemcpyAsync(s->d_skin_matrices.p, joint_matrices, sizeof(SrTransform) * (size_t)n_joints, hipMemcpyHostToDevice, st);
-    if (timed) (void)hipEventRecord(ev[0], st);
-    SrVertex* const morphed = (SrVertex*)(joint_matrices ? s->d_morph_out.p : s->d_skin_out.p);
-    if (e == 0) e = srk_morph((const SrVertex*)morph.d_base.p, (const SrMorphDelta*)morph.d_deltas.p, (const uint32_t*)s->d_morph_active.p,
-                              (const float*)s->d_morph_active.p + n_targets, n_active, morphed, m.n_vertices, check, st);
-    if (e == 0 && joint_matrices) e = srk_skin(morphed, (const SrSkinInfluence*)skin.d_influences.p, (const SrTransform*)s->d_skin_matrices.p,
-                                               (SrVertex*)s->d_skin_out.p, m.n_vertices, check + 1, st);
-    if (e == 0) e = (int)hipMemcpyAsync(bad, check, 8, hipMemcpyDeviceToHost, st);
-    if (timed) (void)hipEventRecord(ev[1], st);
-    if (e == 0) e = (int)hipStreamSynchronize(st);
-    float ms = 0.0f;
-    const double pose_ms = (timed && e == 0 && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) ? (double)ms : 0.0;
-    for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
-    if (e != 0) return fail(SR_ERR_HIP, std::string("pose_mesh: a posing kernel failed: ") + hipGetErrorString((hipError_t)e));
-    morph.first_bad = bad[0] < m.n_vertices ? bad[0] : 0xFFFFFFFFu;
-    morph.n_active = n_active;
-    if (joint_matrices) skin.first_bad = bad[1] < m.n_vertices ? bad[1] : 0xFFFFFFFFu;
-    if (const uint32_t first_bad = std::min(bad[0], bad[1]); first_bad < m.n_vertices) return fail_non_finite_vertex(first_bad);
-    const auto t1 = std::chrono::steady_clock::now();
-    if ((rc = take_device_vertices(s, slot, (const SrVertex*)s->d_skin_out.p, s->device)) != SR_OK) return rc;
-    const auto t2 = std::chrono::steady_clock::now();
-    m.check_ms = 0.0;                                         // the check is part of the posing kernels: SrMeshMorphInfo.morph_ms
-    morph.morph_ms = pose_ms; morph.posed++;
-    if (joint_matrices) { skin.skin_ms = 0.0; skin.skinned++; }    // the two kernels are timed as one: morph_ms
-    mesh_vertices_changed(s, slot);
-    const auto t3 = std::chrono::steady_clock::now();
-    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, t3);
-    s->mu_info.h2d_ms = ms_between(t1, t2);
-    return SR_OK;
+    return pose_mesh(s, key, weights, n_targets, joint_matrices, n_joints, stream, "pose_mesh");
 }
 
 int sr_scene_mesh_morph_info(const SrScene* s, uint64_t key, SrMeshMorphInfo* out) {
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_morph_info: null argument");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_morph_info: no mesh is registered under this key");
-    const SrScene::MeshState::Morph& morph = s->mesh_state[it->second].morph;
+    uint32_t slot = 0;
+    if (const int rc = find_mesh(s, key, "sr_scene_mesh_morph_info", &slot); rc != SR_OK) return rc;
+    const SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
     memset(out, 0, sizeof(*out));
     out->n_targets = morph.n_targets; out->posed = morph.posed; out->n_active = morph.n_active; out->first_bad = morph.first_bad; out->morph_ms = morph.morph_ms;
     return SR_OK;
@@ -2306,9 +2304,8 @@ int sr_scene_as_state(const SrScene* s, SrAsState* state, uint32_t* last_op) {
 int sr_scene_set_mesh_build_type(SrScene* s, uint64_t key, uint32_t build_type) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_build_type: scene is null");
     if (build_type > SR_BUILD_STATIC) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_build_type: build type must be SR_BUILD_RAPIDLY_CHANGING, SR_BUILD_SOMETIMES_CHANGES or SR_BUILD_STATIC");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_set_mesh_build_type: no mesh is registered under this key");
-    const uint32_t slot = it->second;
+    uint32_t slot = 0;
+    if (const int rc = find_mesh(s, key, "sr_scene_set_mesh_build_type", &slot); rc != SR_OK) return rc;
     SrScene::MeshState& a = s->mesh_state[slot];
     if (build_type == SR_BUILD_STATIC && a.refit_pending) invalidate_mesh_tree(s, slot);       // a Static mesh is never refitted: its pending update becomes a rebuild
     a.build_type = build_type;
@@ -2318,9 +2315,9 @@ int sr_scene_set_mesh_build_type(SrScene* s, uint64_t key, uint32_t build_type) 
 
 int sr_scene_mesh_as_state(const SrScene* s, uint64_t key, uint32_t* build_type, SrAsState* state, uint32_t* last_op) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_as_state: scene is null");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_as_state: no mesh is registered under this key");
-    const SrScene::MeshState& a = s->mesh_state[it->second];
+    uint32_t slot = 0;
+    if (const int rc = find_mesh(s, key, "sr_scene_mesh_as_state", &slot); rc != SR_OK) return rc;
+    const SrScene::MeshState& a = s->mesh_state[slot];
     if (build_type) *build_type = a.build_type;
     if (state) *state = a.state;
     if (last_op) *last_op = a.last_op;
@@ -2330,10 +2327,9 @@ int sr_scene_mesh_as_state(const SrScene* s, uint64_t key, uint32_t* build_type,
 int sr_scene_read_mesh_tree(const SrScene* s, uint64_t key, uint32_t* n_nodes, uint32_t* n_tris, uint32_t* nodes, float* tris, float* shade,
                             float* shade_tex, uint32_t* slot_of_prim) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_mesh_tree: scene is null");
-    auto it = s->slots.find(key);
-    if (it == s->slots.end()) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_mesh_tree: no mesh is registered under this key");
+    uint32_t slot = 0;
+    if (const int rc = find_mesh(s, key, "sr_scene_read_mesh_tree", &slot); rc != SR_OK) return rc;
     if (!s->built || !s->two_level) return fail(SR_ERR_STATE, "sr_scene_read_mesh_tree: the scene is not built in the two-level form");
-    const uint32_t slot = it->second;
     const SrScene::MeshState& ms = s->mesh_state[slot];
     if (!s->blas_device_current || !ms.tree.valid)
         return fail(SR_ERR_STATE, "sr_scene_read_mesh_tree: the mesh's tree is not on the device (sr_scene_set_instances builds it)");
@@ -2848,14 +2844,7 @@ int srh::scene_take_device_vertices(SrScene* s, uint64_t key, const SrVertex* d_
     uint32_t slot = 0;
     int rc = check_mesh_update(s, key, d_vertices, n_vertices, &slot);
     if (rc != SR_OK || (rc = check_emissive_list(s->meshes[slot])) != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    if ((rc = take_device_vertices(s, slot, d_vertices, src_device)) != SR_OK) return rc;
-    const auto t2 = std::chrono::steady_clock::now();
-    s->meshes[slot].check_ms = 0.0;                          // validated once, on the first slot
-    mesh_vertices_changed(s, slot);
-    s->mu_info.validate_copy_ms = ms_between(t0, t1) + ms_between(t2, std::chrono::steady_clock::now());
-    s->mu_info.h2d_ms = ms_between(t1, t2);
-    return SR_OK;
+    return finish_device_update(s, slot, d_vertices, src_device, 0.0, t0);      // check_ms 0.0: validated once, on the first scene
 }
 
 const SrVertex* srh::scene_skinned_vertices(const SrScene* s, uint64_t key, uint32_t* n_vertices) {

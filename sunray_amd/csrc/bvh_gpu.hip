@@ -20,6 +20,7 @@
 #include "bvh_layout.h"
 #include "tl_record.h"
 #include "traverse.h"
+#include "vertex_tile.h"
 
 namespace srd {
 
@@ -556,8 +557,7 @@ __global__ void blas_build_finish_kernel(const uint32_t* acc, const uint32_t* co
 // whose piece opens a vertex tests its first three words. The grid is a multiple of three blocks of 256, so the stride is a
 // multiple of six pieces: a thread keeps its place inside the vertex over the whole loop and its vertex index advances by a
 // constant. Piece indices are 64-bit (n_vertices * 6 need not fit 32). Every lane keeps its own minimum, the wave reduces once
-// after the loop (cross-lane moves, no LDS) and at most one atomicMin per wave reaches `first_bad` (preset to 0xFFFFFFFF).
-constexpr uint32_t kVertexPieces = sizeof(SrVertex) / 16;
+// after the loop (report_first_bad, vertex_tile.h).
 constexpr uint32_t kVertexCheckBlock = 256, kVertexCheckMaxBlocks = 2046;     // about eight blocks per CU; a multiple of three
 static_assert(sizeof(SrVertex) == 96 && offsetof(SrVertex, position) == 0 && (kVertexCheckBlock * 3) % kVertexPieces == 0 && kVertexCheckMaxBlocks % 3 == 0,
               "vertex_check_kernel: six pieces per vertex, the position in the first, a stride of whole vertices");
@@ -571,8 +571,7 @@ __global__ void __launch_bounds__(kVertexCheckBlock) vertex_check_kernel(const u
         const bool hit = ((w.x & exponent) == 0x7F800000u) | ((w.y & exponent) == 0x7F800000u) | ((w.z & exponent) == 0x7F800000u);
         bad = hit ? min(bad, v) : bad;
     }
-    for (int o = 32; o > 0; o >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, o, 64));
-    if ((threadIdx.x & 63u) == 0 && bad != 0xFFFFFFFFu) atomicMin(first_bad, bad);
+    report_first_bad(bad, first_bad);
 }
 
 }  // namespace srd

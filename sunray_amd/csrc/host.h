@@ -104,8 +104,9 @@ bool decode_image_rgba8(const uint8_t* data, size_t n, uint32_t& width, uint32_t
 
 // the one thread-local error slot of the library (api.cpp); returns `code`
 int set_error(int code, const std::string& msg);
-// A further replica of a renderer takes vertices that sr_scene_update_mesh_device has validated on `src_device` (api.cpp): the
-// copy into the mesh's allocation (peer copy across devices) and the state of that call, without a second pass over the bytes.
+// A further replica of a renderer takes vertices that sr_scene_update_mesh_device has validated on `src_device` (api.cpp
+// finish_device_update): the copy into the mesh's allocation (peer copy across devices) and the state of that call, without a
+// second pass over the bytes.
 int scene_take_device_vertices(SrScene* scene, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, int src_device);
 // The scratch buffer on the scene's device that the last accepted sr_scene_skin_mesh or sr_scene_pose_mesh posed into (api.cpp):
 // what the further replicas of a renderer take through scene_take_device_vertices, and the vertex count of the mesh `key` that was

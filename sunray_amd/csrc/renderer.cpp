@@ -60,6 +60,43 @@ int alloc_images(SrRenderer* r, uint32_t w, uint32_t h) {
     return SR_OK;
 }
 
+// `call` on every replica scene in slot order, stopping at the first refusal. The replicas hold the same meshes and settings,
+// so what one refuses on validation the first one refuses, and none has changed.
+template <class Call>
+int each_scene(SrRenderer* r, Call call) {
+    for (SrScene* sc : srmr::scenes(r))
+        if (const int rc = call(sc); rc != SR_OK) return rc;
+    return SR_OK;
+}
+
+// Device-produced vertices for every replica: `produce` runs on the first slot's scene, which validates once; the further
+// replicas take the validated bytes (srh::scene_take_device_vertices: device-to-device or peer copy, the same state, no host
+// staging) from `src`, or with src == NULL from that scene's scratch buffer, where the library's own producers leave them.
+// What the first scene refuses changes none, and leaves the instance list as valid as it was.
+template <class Produce>
+int first_scene_produces(SrRenderer* r, uint64_t key, const SrVertex* src, uint32_t n_vertices, Produce produce) {
+    const std::vector<SrScene*> scenes = srmr::scenes(r);
+    int rc = produce(scenes[0]);
+    if (rc != SR_OK) return rc;
+    r->instances_valid = false;
+    if (!src) src = srh::scene_skinned_vertices(scenes[0], key, &n_vertices);
+    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_take_device_vertices(scenes[i], key, src, n_vertices, r->device);
+    return rc;
+}
+
+// What attach_skins, attach_morphs and pose_scene (`who`) refuse first: a loaded scene that does not come from this file. The
+// file's mesh count into *n_blases; its instance count is compared, and given, only where n_instances is not NULL.
+int check_scene_of_file(const SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls, const char* who, uint32_t* n_blases, uint32_t* n_instances) {
+    if (!r || !g || !ls) return rfail(SR_ERR_INVALID_ARG, std::string(who) + ": null argument");
+    uint32_t ni = 0;
+    const int rc = sr_gltf_counts(g, n_blases, &ni, nullptr, nullptr, nullptr);
+    if (rc != SR_OK) return rc;
+    if (*n_blases != ls->keys.size() || (n_instances && ni != ls->transforms.size()))
+        return rfail(SR_ERR_INVALID_ARG, std::string(who) + ": the loaded scene does not come from this file (another number of meshes" + (n_instances ? " or instances)" : ")"));
+    if (n_instances) *n_instances = ni;
+    return SR_OK;
+}
+
 uint32_t pcg_hash(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
 
 }  // namespace
@@ -195,11 +232,7 @@ int sr_renderer_load_mesh(SrRenderer* r, uint64_t key, const SrVertex* vertices,
                           uint32_t n_indices, const SrMaterial* material) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "load_mesh: renderer is null");
     r->instances_valid = false;
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_add_mesh(sc, key, vertices, n_vertices, indices, n_indices, material, nullptr);
-        if (rc != SR_OK) return rc;
-    }
-    return SR_OK;
+    return each_scene(r, [&](SrScene* sc) { return sr_scene_add_mesh(sc, key, vertices, n_vertices, indices, n_indices, material, nullptr); });
 }
 
 int sr_renderer_set_config(SrRenderer* r, const SrTraceConfig* cfg) {
@@ -226,19 +259,14 @@ int sr_renderer_render(SrRenderer* r, const float cam_pos[3], const float cam_ta
                       (n_keys == 0 || (memcmp(r->last_keys.data(), keys, n_keys * 8) == 0 && memcmp(r->last_counts.data(), counts, n_keys * 4) == 0)) &&
                       (n_xf == 0 || memcmp(r->last_transforms.data(), transforms, n_xf * sizeof(SrTransform)) == 0);
     if (!same) {
-        for (SrScene* sc : srmr::scenes(r)) {                        // every replica, in slot order (host BVH build per replica)
-            int rc = sr_scene_set_instances(sc, keys, counts, n_keys, transforms);
-            if (rc != SR_OK) return rc;
-        }
+        // every replica, in slot order (host BVH build per replica)
+        if (const int rc = each_scene(r, [&](SrScene* sc) { return sr_scene_set_instances(sc, keys, counts, n_keys, transforms); }); rc != SR_OK) return rc;
         r->last_keys.assign(keys, keys + n_keys);
         r->last_counts.assign(counts, counts + n_keys);
         r->last_transforms.assign(transforms, transforms + n_xf);
         r->instances_valid = true;
     } else {
-        for (SrScene* sc : srmr::scenes(r)) {
-            int rc = sr_scene_end_frame(sc);        // quiet frame: the heuristic may settle with a quality rebuild
-            if (rc != SR_OK) return rc;
-        }
+        if (const int rc = each_scene(r, sr_scene_end_frame); rc != SR_OK) return rc;    // quiet frame: the heuristic may settle with a quality rebuild
     }
     SrMatrices m;
     int rc = sr_camera_matrices(cam_pos, cam_target, fov_y, r->width, r->height, r->prev_view_proj, &m);   // lib.rs:1017-1048
@@ -478,11 +506,7 @@ int sr_renderer_unload_scene(SrRenderer* r, uint64_t group) {
 int sr_renderer_unload_mesh(SrRenderer* r, uint64_t key) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "unload_mesh: renderer is null");
     r->instances_valid = false;
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_remove(sc, key);
-        if (rc != SR_OK) return rc;
-    }
-    return SR_OK;
+    return each_scene(r, [&](SrScene* sc) { return sr_scene_remove(sc, key); });
 }
 
 // Blas::update (blas.rs:285-310) through the facade: every replica takes the new vertices; the next render re-submits the
@@ -494,23 +518,15 @@ int sr_renderer_unload_mesh(SrRenderer* r, uint64_t key) {
 int sr_renderer_update_mesh(SrRenderer* r, uint64_t key, const SrVertex* vertices, uint32_t n_vertices) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "update_mesh: renderer is null");
     r->instances_valid = false;
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_update_mesh(sc, key, vertices, n_vertices);
-        if (rc != SR_OK) return rc;
-    }
-    return SR_OK;
+    return each_scene(r, [&](SrScene* sc) { return sr_scene_update_mesh(sc, key, vertices, n_vertices); });
 }
 
-// The same for vertices on the first slot's device: sr_scene_update_mesh_device validates them there, once; the further replicas
-// take the validated bytes straight from the caller's buffer (srh::scene_take_device_vertices: device-to-device or peer copy,
-// the same state), with no host staging. The replicas hold the same meshes, so what the first scene refuses changes none.
+// The same for vertices on the first slot's device: sr_scene_update_mesh_device validates them there, once, and the further
+// replicas take them straight from the caller's buffer. This call re-submits the instance list also where it refuses.
 int sr_renderer_update_mesh_device(SrRenderer* r, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, void* stream) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "update_mesh: renderer is null");
     r->instances_valid = false;
-    const std::vector<SrScene*> scenes = srmr::scenes(r);
-    int rc = sr_scene_update_mesh_device(scenes[0], key, d_vertices, n_vertices, stream);
-    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_take_device_vertices(scenes[i], key, d_vertices, n_vertices, r->device);
-    return rc;
+    return first_scene_produces(r, key, d_vertices, n_vertices, [&](SrScene* sc) { return sr_scene_update_mesh_device(sc, key, d_vertices, n_vertices, stream); });
 }
 
 // A mesh's rig lives on the first slot's scene only: that scene poses, the further replicas take the posed vertices.
@@ -519,18 +535,10 @@ int sr_renderer_set_mesh_skin(SrRenderer* r, uint64_t key, const SrSkinInfluence
     return sr_scene_set_mesh_skin(srmr::scenes(r)[0], key, influences, n_vertices, n_joints);
 }
 
-// sr_scene_skin_mesh on the first slot's scene, which poses and validates once; the further replicas take the validated bytes from
-// that scene's scratch buffer as they take a caller's in sr_renderer_update_mesh_device. What the first scene refuses changes none.
+// sr_scene_skin_mesh on the first slot's scene, which poses and validates once (first_scene_produces).
 int sr_renderer_skin_mesh(SrRenderer* r, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "skin_mesh: null argument (the renderer)");
-    const std::vector<SrScene*> scenes = srmr::scenes(r);
-    int rc = sr_scene_skin_mesh(scenes[0], key, joint_matrices, n_joints, stream);
-    if (rc != SR_OK) return rc;
-    r->instances_valid = false;
-    uint32_t n_vertices = 0;
-    const SrVertex* posed = srh::scene_skinned_vertices(scenes[0], key, &n_vertices);
-    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_take_device_vertices(scenes[i], key, posed, n_vertices, r->device);
-    return rc;
+    return first_scene_produces(r, key, nullptr, 0, [&](SrScene* sc) { return sr_scene_skin_mesh(sc, key, joint_matrices, n_joints, stream); });
 }
 
 // A mesh's morph lives on the first slot's scene only, like its rig.
@@ -539,27 +547,17 @@ int sr_renderer_set_mesh_morph(SrRenderer* r, uint64_t key, const SrMorphDelta* 
     return sr_scene_set_mesh_morph(srmr::scenes(r)[0], key, deltas, n_vertices, n_targets);
 }
 
-// sr_scene_pose_mesh on the first slot's scene, which morphs, skins and validates once; the further replicas take the validated
-// bytes from that scene's scratch buffer as in sr_renderer_skin_mesh. What the first scene refuses changes none.
+// sr_scene_pose_mesh on the first slot's scene, which morphs, skins and validates once (first_scene_produces).
 int sr_renderer_pose_mesh(SrRenderer* r, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "pose_mesh: null argument (the renderer)");
-    const std::vector<SrScene*> scenes = srmr::scenes(r);
-    int rc = sr_scene_pose_mesh(scenes[0], key, weights, n_targets, joint_matrices, n_joints, stream);
-    if (rc != SR_OK) return rc;
-    r->instances_valid = false;
-    uint32_t n_vertices = 0;
-    const SrVertex* posed = srh::scene_skinned_vertices(scenes[0], key, &n_vertices);
-    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_take_device_vertices(scenes[i], key, posed, n_vertices, r->device);
-    return rc;
+    return first_scene_produces(r, key, nullptr, 0, [&](SrScene* sc) { return sr_scene_pose_mesh(sc, key, weights, n_targets, joint_matrices, n_joints, stream); });
 }
 
 // The morph targets of a loaded scene, as sr_renderer_attach_skins attaches its rigs.
 int sr_renderer_attach_morphs(SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls) {
-    if (!r || !g || !ls) return rfail(SR_ERR_INVALID_ARG, "attach_morphs: null argument");
     uint32_t n_blases = 0;
-    int rc = sr_gltf_counts(g, &n_blases, nullptr, nullptr, nullptr, nullptr);
+    int rc = check_scene_of_file(r, g, ls, "attach_morphs", &n_blases, nullptr);
     if (rc != SR_OK) return rc;
-    if (n_blases != ls->keys.size()) return rfail(SR_ERR_INVALID_ARG, "attach_morphs: the loaded scene does not come from this file (another number of meshes)");
     for (uint32_t b = 0; b < n_blases; b++) {
         const SrMorphDelta* deltas = nullptr; uint32_t nv = 0, n_targets = 0;
         if ((rc = sr_gltf_blas_morph(g, b, &n_targets, &deltas, &nv, nullptr)) != SR_OK) return rc;
@@ -572,11 +570,9 @@ int sr_renderer_attach_morphs(SrRenderer* r, const SrGltf* g, const SrLoadedScen
 
 // The rigs of a loaded scene: keys are in blas order (sr_renderer_load_scene), so blas b of the file is loaded->keys[b].
 int sr_renderer_attach_skins(SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls) {
-    if (!r || !g || !ls) return rfail(SR_ERR_INVALID_ARG, "attach_skins: null argument");
     uint32_t n_blases = 0;
-    int rc = sr_gltf_counts(g, &n_blases, nullptr, nullptr, nullptr, nullptr);
+    int rc = check_scene_of_file(r, g, ls, "attach_skins", &n_blases, nullptr);
     if (rc != SR_OK) return rc;
-    if (n_blases != ls->keys.size()) return rfail(SR_ERR_INVALID_ARG, "attach_skins: the loaded scene does not come from this file (another number of meshes)");
     for (uint32_t b = 0; b < n_blases; b++) {
         int32_t skin = -1; const SrSkinInfluence* inf = nullptr; uint32_t nv = 0, n_joints = 0;
         if ((rc = sr_gltf_blas_skin(g, b, &skin, &inf, &nv)) != SR_OK) return rc;
@@ -589,11 +585,9 @@ int sr_renderer_attach_skins(SrRenderer* r, const SrGltf* g, const SrLoadedScene
 }
 
 int sr_renderer_pose_scene(SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls, int32_t animation, float time_seconds, SrTransform* instance_transforms_out, void* stream) {
-    if (!r || !g || !ls) return rfail(SR_ERR_INVALID_ARG, "pose_scene: null argument");
     uint32_t n_blases = 0, n_instances = 0;
-    int rc = sr_gltf_counts(g, &n_blases, &n_instances, nullptr, nullptr, nullptr);
+    int rc = check_scene_of_file(r, g, ls, "pose_scene", &n_blases, &n_instances);
     if (rc != SR_OK) return rc;
-    if (n_blases != ls->keys.size() || n_instances != ls->transforms.size()) return rfail(SR_ERR_INVALID_ARG, "pose_scene: the loaded scene does not come from this file (another number of meshes or instances)");
     std::vector<SrTransform> posed(n_instances), joints;
     if ((rc = sr_gltf_pose(g, animation, time_seconds, posed.data(), 0, nullptr)) != SR_OK) return rc;
     std::vector<float> weights;
@@ -634,33 +628,21 @@ int sr_renderer_pose_scene(SrRenderer* r, const SrGltf* g, const SrLoadedScene* 
 // BuildType of a mesh's tree on every replica (the replicas hold the same meshes: one that refuses, refuses first).
 int sr_renderer_set_mesh_build_type(SrRenderer* r, uint64_t key, uint32_t build_type) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_build_type: renderer is null");
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_set_mesh_build_type(sc, key, build_type);
-        if (rc != SR_OK) return rc;
-    }
-    return SR_OK;
+    return each_scene(r, [&](SrScene* sc) { return sr_scene_set_mesh_build_type(sc, key, build_type); });
 }
 
 // Where updatable meshes' trees are built (SR_MESH_TREE_BUILD_*), on every replica.
 int sr_renderer_set_mesh_tree_build(SrRenderer* r, uint32_t mode) {
     if (mode > SR_MESH_TREE_BUILD_DEVICE) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_tree_build: mode must be SR_MESH_TREE_BUILD_AUTO, _HOST or _DEVICE");
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_tree_build: renderer is null");
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_set_mesh_tree_build(sc, mode);
-        if (rc != SR_OK) return rc;
-    }
-    return SR_OK;
+    return each_scene(r, [&](SrScene* sc) { return sr_scene_set_mesh_tree_build(sc, mode); });
 }
 
 // Whether small pending meshes are built by one batched launch (SR_BLAS_BATCH_*), on every replica.
 int sr_renderer_set_mesh_tree_batch(SrRenderer* r, uint32_t mode) {
     if (mode > SR_BLAS_BATCH_ON) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_tree_batch: mode must be SR_BLAS_BATCH_OFF or SR_BLAS_BATCH_ON");
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_mesh_tree_batch: renderer is null");
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_set_mesh_tree_batch(sc, mode);
-        if (rc != SR_OK) return rc;
-    }
-    return SR_OK;
+    return each_scene(r, [&](SrScene* sc) { return sr_scene_set_mesh_tree_batch(sc, mode); });
 }
 
 // What a device fast build does with a tree taller than its stack cap (SR_HEIGHT_BOUND_*), on every replica.
@@ -668,22 +650,14 @@ int sr_renderer_set_tree_height_bound(SrRenderer* r, uint32_t mode, uint32_t mes
     if (mode > SR_HEIGHT_BOUND_REBALANCE || mesh_tree_cap > 26u || (mesh_tree_cap != 0 && mode == SR_HEIGHT_BOUND_REFUSE))
         return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_tree_height_bound: mode must be SR_HEIGHT_BOUND_REFUSE or _REBALANCE, mesh_tree_cap 0 or, under _REBALANCE, 1..26");
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_tree_height_bound: renderer is null");
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_set_tree_height_bound(sc, mode, mesh_tree_cap);
-        if (rc != SR_OK) return rc;
-    }
-    return SR_OK;
+    return each_scene(r, [&](SrScene* sc) { return sr_scene_set_tree_height_bound(sc, mode, mesh_tree_cap); });
 }
 
 // Where the light table is built (SR_LIGHTS_*), on every replica; the figures of one replica's last sr_scene_set_instances.
 int sr_renderer_set_light_table_build(SrRenderer* r, uint32_t mode) {
     if (mode > SR_LIGHTS_DEVICE) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_light_table_build: mode must be SR_LIGHTS_HOST or SR_LIGHTS_DEVICE");
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_light_table_build: renderer is null");
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_set_light_table_build(sc, mode);
-        if (rc != SR_OK) return rc;
-    }
-    return SR_OK;
+    return each_scene(r, [&](SrScene* sc) { return sr_scene_set_light_table_build(sc, mode); });
 }
 int sr_renderer_light_table_info(SrRenderer* r, uint32_t slot, SrLightTableInfo* out) {
     if (!r || !out) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_light_table_info: null argument");

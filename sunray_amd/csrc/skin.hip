@@ -2,48 +2,23 @@
 // fp32 under the numerics contract of DESIGN.md §3: no contraction, correctly rounded divide and sqrt, left to right.
 #include "skin.h"
 
-#include <cstddef>
+#include "vertex_tile.h"
 
 namespace srd {
 
-// One block poses a tile of 256 vertices, one vertex per thread. The kernel is memory-bound (96 + 24 bytes in, 96 out per
-// vertex), so the records cross global memory as 16-byte pieces, six per vertex, consecutive lanes on consecutive pieces
-// (coalesced dwordx4, the walk of vertex_check_kernel), and are turned by the LDS: a thread reads the three pieces of its own
-// vertex that skinning changes (position, normal, tangent), writes them back in place, and the tile leaves as it came. The uv
-// sets and the pads are never in a register of the posing thread: every byte that is not rewritten is the bind pose's. A row of
-// the tile is seven pieces, not six: lanes 28 dwords apart fall on sixteen different 16-byte slots of the LDS in every group
-// of 16 lanes that one ds_read_b128 serves (24 dwords apart they would share slots in pairs). 28 KiB per block: five blocks a CU.
-// The joint matrices are gathered from global memory (three dwordx4 per non-zero weight): a rig is a few KiB that the
-// vector L1 and the L2 hold, and a rig of 65536 joints would fit no LDS.
-constexpr uint32_t kSkinBlock = 256, kSkinPieces = sizeof(SrVertex) / 16, kSkinRow = kSkinPieces + 1;
-static_assert(sizeof(SrVertex) == 96 && offsetof(SrVertex, position) == 0 && offsetof(SrVertex, normal) == 16 && offsetof(SrVertex, tangent) == 32,
-              "skin_kernel: position, normal and tangent are the first three 16-byte pieces of a vertex");
+// One vertex per thread on the tile of vertex_tile.h (96 + 24 bytes in, 96 out per vertex). The joint matrices are gathered from
+// global memory (three dwordx4 per non-zero weight): a rig is a few KiB that the vector L1 and the L2 hold, and a rig of 65536
+// joints would fit no LDS.
 static_assert(sizeof(SrSkinInfluence) == 24 && offsetof(SrSkinInfluence, weight) == 8 && sizeof(SrTransform) == 48,
               "skin_kernel: an influence is three 8-byte pieces, a joint matrix three rows of 16 bytes");
 
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
-// v * (1 / sqrt(dot(v, v))) into the first three words of *piece; a squared length that is 0 or not finite leaves the piece alone
-__device__ __forceinline__ void store_normalised(uint4* piece, float x, float y, float z) {
-    const float len2 = (x * x + y * y) + z * z;
-    if (len2 == 0.0f || !finite_bits(len2)) return;
-    const float r = 1.0f / sqrtf(len2);
-    piece->x = __float_as_uint(x * r); piece->y = __float_as_uint(y * r); piece->z = __float_as_uint(z * r);
-}
-
-__global__ void __launch_bounds__(kSkinBlock) skin_kernel(const uint4* __restrict__ bind, const uint2* __restrict__ influences,
+__global__ void __launch_bounds__(kTileBlock) skin_kernel(const uint4* __restrict__ bind, const uint2* __restrict__ influences,
                                                           const float4* __restrict__ matrices, uint4* __restrict__ out, uint32_t n_vertices,
                                                           uint32_t* first_bad) {
-    __shared__ uint4 tile[kSkinBlock * kSkinRow];
-    const uint32_t t = threadIdx.x, v0 = blockIdx.x * kSkinBlock;        // v0 < n_vertices: the grid is ceil(n_vertices / 256)
-    const uint32_t nv = min(kSkinBlock, n_vertices - v0), np = nv * kSkinPieces;
-    const uint64_t p0 = (uint64_t)v0 * kSkinPieces;                      // piece indices are 64-bit (n_vertices * 6 need not fit 32)
-#pragma unroll
-    for (uint32_t k = 0; k < kSkinPieces; k++) {
-        const uint32_t p = k * kSkinBlock + t;
-        if (p < np) tile[p + p / kSkinPieces] = bind[p0 + p];
-    }
-    __syncthreads();
+    __shared__ uint4 tile[kTileBlock * kTileRow];
+    const VertexTile vt(n_vertices);
+    const uint32_t t = threadIdx.x, v0 = vt.v0, nv = vt.nv;
+    vt.load(tile, bind);
     uint32_t bad = 0xFFFFFFFFu;
     if (t < nv) {
         const uint2* inf = influences + (size_t)(v0 + t) * 3;
@@ -64,7 +39,7 @@ __global__ void __launch_bounds__(kSkinBlock) skin_kernel(const uint4* __restric
                 }
             }
         }
-        uint4* row = tile + t * kSkinRow;
+        uint4* row = VertexTile::row(tile, t);
         const uint4 P = row[0], N = row[1], T = row[2];
         const float x = __uint_as_float(P.x), y = __uint_as_float(P.y), z = __uint_as_float(P.z);
         const float px = ((B[0][0] * x + B[0][1] * y) + B[0][2] * z) + B[0][3];
@@ -82,15 +57,8 @@ __global__ void __launch_bounds__(kSkinBlock) skin_kernel(const uint4* __restric
         store_normalised(row + 2, (B[0][0] * tx + B[0][1] * ty) + B[0][2] * tz, (B[1][0] * tx + B[1][1] * ty) + B[1][2] * tz,
                          (B[2][0] * tx + B[2][1] * ty) + B[2][2] * tz);
     }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < kSkinPieces; k++) {
-        const uint32_t p = k * kSkinBlock + t;
-        if (p < np) out[p0 + p] = tile[p + p / kSkinPieces];
-    }
-    // the lowest offending vertex: one reduction per wave (cross-lane moves), at most one atomicMin per wave
-    for (int o = 32; o > 0; o >>= 1) bad = min(bad, (uint32_t)__shfl_xor((int)bad, o, 64));
-    if ((t & 63u) == 0 && bad != 0xFFFFFFFFu) atomicMin(first_bad, bad);
+    vt.store(tile, out);
+    report_first_bad(bad, first_bad);
 }
 
 }  // namespace srd
@@ -100,8 +68,8 @@ int srk_skin(const SrVertex* bind, const SrSkinInfluence* influences, const SrTr
     hipError_t e = hipMemsetAsync(first_bad, 0xFF, 4, stream);
     if (e != hipSuccess) return (int)e;
     if (n_vertices == 0) return 0;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n_vertices + srd::kSkinBlock - 1) / srd::kSkinBlock);
-    srd::skin_kernel<<<dim3(blocks), dim3(srd::kSkinBlock), 0, stream>>>((const uint4*)bind, (const uint2*)influences, (const float4*)joint_matrices,
+    const uint32_t blocks = (uint32_t)(((uint64_t)n_vertices + srd::kTileBlock - 1) / srd::kTileBlock);
+    srd::skin_kernel<<<dim3(blocks), dim3(srd::kTileBlock), 0, stream>>>((const uint4*)bind, (const uint2*)influences, (const float4*)joint_matrices,
                                                                        (uint4*)out, n_vertices, first_bad);
     return (int)hipGetLastError();
 }
