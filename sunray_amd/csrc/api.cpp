@@ -177,8 +177,10 @@ struct SrScene {
         std::vector<float> tris, shade, shade_tex;   // 12 / 12 / 24 floats per triangle, leaf order
         std::vector<uint32_t> slot_of_prim;
         uint32_t n_tris = 0, n_nodes = 0, max_stack = 0, max_depth = 0;
-        float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};   // root box, object space
-        float max_edge_sum = 0.0f, max_abs_vertex = 0.0f;
+        // The root block, eight words: root box (object space) and the padding numbers. The device build's ten-word result and a
+        // srd::TlMeshRow begin with it, and the refit reads back one per mesh: it is copied as a whole in either direction.
+        struct RootBlock { float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, max_abs_vertex = 0.0f, max_edge_sum = 0.0f; };
+        RootBlock root;
         double build_ms = 0.0;
         bool host_stale = false;            // refitted or built on the device since: nodes / tris / shade / shade_tex above hold the old vertices
                                             // (after a refit, topology, slot_of_prim, counts, max_stack and the read-back lo, hi, max_* are current)
@@ -217,18 +219,27 @@ struct SrScene {
         DeviceBuffer d_emissive_slots;      // the mesh's emissive_slots, uploaded at the first such rewrite
     };
     std::vector<MeshState> mesh_state;      // by mesh slot, one per entry of `meshes`: grows in sr_scene_add_blas only
-    // device refit of mesh trees: box scratch over d_blas_nodes (allocated at the first refit), and what belongs to the set of
-    // meshes refitted last (an animation refits the same set every frame): rewrite-kernel rows, node lists by level, accumulators
-    DeviceBuffer d_blas_node_box, d_refit_meshes, d_refit_nodes, d_refit_acc, d_refit_acc_init, d_refit_out;
-    std::vector<uint32_t> refit_set, refit_level_offsets;
-    uint32_t refit_threads = 0;
-    bool blas_device_current = false;       // the concatenated arrays match the current set of meshes
-    bool any_textured_tl = false;
-    uint32_t blas_stack = 0;
-    bool tl_baked = false;                  // the device arrays hold baked (world-space) copies of some instances' meshes
-    std::vector<uint32_t> tl_baked_node_base, tl_baked_tri_base;
-    uint64_t tl_blas_nodes = 0, tl_blas_tris = 0;
-    uint64_t blas_node_end = 0;             // nodes of d_blas_nodes in use, the ranges of device-built meshes included (d_blas_node_box has as many rows)
+    // The concatenated mesh trees on the device: every live mesh's tree, then the baked copies of the instance list at hand
+    // (upload_mesh_trees), then the node ranges device-built meshes took (MeshState::node_cap); d_tris, d_shade, d_shade_tex and
+    // d_slot_of_gid are the triangle side. blas_device_current (the arrays match the current set of meshes) is set by
+    // upload_mesh_trees alone and cleared by what adds, removes or invalidates a tree; the rest is read only behind it.
+    // blas_node_end covers every node range handed out (d_blas_node_box, allocated at the first refit or device build, has as many
+    // rows), tl_blas_nodes the nodes really in use. While tl_mesh_rows_current, d_tl_mesh_rows (srd::TlMeshRow by mesh slot) holds
+    // every tree's root block, stack need and bases: device refits and builds write their rows, upload_mesh_trees moves the bases and
+    // clears it, top_level_build_device uploads them anew. Where bases move or a node list changes (a device build), `refit` is void.
+    struct MeshTrees {
+        DeviceBuffer d_blas_nodes, d_blas_node_box, d_tl_mesh_rows;
+        uint64_t blas_node_end = 0, tl_blas_nodes = 0, tl_blas_tris = 0;
+        bool blas_device_current = false, tl_mesh_rows_current = false, any_textured_tl = false, tl_baked = false;
+        std::vector<uint32_t> tl_baked_node_base, tl_baked_tri_base;
+        // the builder's bound on a device-built tree's nodes; a mesh's own range of that size, at its first device build; the rows a writer keeps current, or null
+        static uint32_t range_bound(uint32_t n_tris) { return n_tris + 64u; }
+        void take_range(MeshState& ms) { if (ms.node_cap == 0) { ms.node_base = (uint32_t)blas_node_end; ms.node_cap = range_bound(ms.tree.n_tris); blas_node_end += ms.node_cap; } }
+        srd::TlMeshRow* rows_dev(size_t n_meshes) const { return (tl_mesh_rows_current && d_tl_mesh_rows.bytes >= n_meshes * sizeof(srd::TlMeshRow)) ? (srd::TlMeshRow*)d_tl_mesh_rows.p : nullptr; }
+    } trees;
+    // The set of meshes the device refitted last (an animation refits the same set every frame) with its rewrite-kernel rows, node
+    // lists by level (global indices, deepest level first) and accumulators. An empty `set` is void.
+    struct RefitSet { DeviceBuffer d_meshes, d_nodes, d_acc, d_acc_init, d_out; std::vector<uint32_t> set, level_offsets; uint32_t threads = 0; } refit;
     int blas_build_mode = SR_MESH_TREE_BUILD_AUTO;   // sr_scene_set_mesh_tree_build / SR_BLAS_BUILD in the environment
     SrMeshTreeInfo mt_info{};               // mesh-tree builds of the last sr_scene_set_instances
     bool static_mesh_updated = false;       // a Static mesh was updated since the last sr_scene_set_instances (its tree goes to the host)
@@ -241,10 +252,9 @@ struct SrScene {
     // sr_scene_pose_mesh: the morphed vertices where a skin stage follows (scratch: srk_skin's `bind`; without one the morph stage
     // writes d_skin_out itself), and the active list of the last call (n indices, then n weights)
     DeviceBuffer d_morph_out, d_morph_active;
-    DeviceBuffer d_blas_nodes, d_tl_inst, d_tl_instances;
-    // top level built on the device (bvh_gpu.hip srk_tl_*): per-mesh rows the record kernel reads, the instance boxes, its result block
-    DeviceBuffer d_tl_mesh_rows, d_tl_boxes, d_tl_result;
-    bool tl_mesh_rows_current = false;      // d_tl_mesh_rows matches the concatenated mesh trees on the device
+    DeviceBuffer d_tl_inst, d_tl_instances;
+    // top level built on the device (bvh_gpu.hip srk_tl_*): the instance boxes, its result block (the per-mesh rows are trees.d_tl_mesh_rows)
+    DeviceBuffer d_tl_boxes, d_tl_result;
     int tl_build_mode = SR_TL_BUILD_AUTO;   // sr_scene_set_top_level_build / SR_TL_BUILD in the environment
     SrTopLevelInfo tl_info{};               // of the last top-level build
     std::vector<float> tl_boxes_host;       // the instance boxes of a host-built top level (sr_scene_read_top_level)
@@ -369,7 +379,11 @@ int find_mesh(const SrScene* s, uint64_t key, const char* who, uint32_t* slot) {
 void invalidate_mesh_tree(SrScene* s, uint32_t slot) {
     SrScene::MeshState& ms = s->mesh_state[slot];
     ms.tree.valid = false; ms.tree.host_stale = false; ms.refit_pending = false;
-    s->blas_device_current = false; s->tl_mesh_rows_current = false;
+    s->trees.blas_device_current = false; s->trees.tl_mesh_rows_current = false;
+}
+void invalidate_mesh_trees(SrScene* s, bool pending) {     // every mesh with a stale host copy and, with `pending`, every mesh with a pending update
+    for (size_t m = 0; m < s->mesh_state.size(); m++)
+        if ((pending && s->mesh_state[m].refit_pending) || s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
 }
 
 // The host copy of a mesh's vertices, brought up to date where sr_scene_update_mesh_device left it behind: one device-to-host
@@ -763,7 +777,7 @@ int sr_scene_add_blas(SrScene* s, uint64_t key, const SrVertex* vertices, uint32
     s->slots[key] = slot;
     s->built = false;
     s->mesh_state[slot] = SrScene::MeshState();
-    s->blas_device_current = false;
+    s->trees.blas_device_current = false;
     if (out_slot) *out_slot = slot;
     return SR_OK;
 }
@@ -796,7 +810,7 @@ int sr_scene_remove(SrScene* s, uint64_t key) {
     for (uint32_t es : m.emissive_slots) s->free_emissive_slots.push_back(es);
     m = srh::HostMesh();
     s->mesh_state[slot] = SrScene::MeshState();
-    s->blas_device_current = false;
+    s->trees.blas_device_current = false;
     s->free_mesh_slots.push_back(slot);
     s->slots.erase(it);
     s->built = false;
@@ -1270,7 +1284,7 @@ struct BuiltStructure {
 // The built structure becomes the one the kernels see: device pointers, statistics, LDS stack size, form.
 void publish(SrScene* s, const BuiltStructure& b) {
     s->dev.nodes = (const float4*)s->d_nodes.p;
-    s->dev.blas_nodes = b.two_level ? (const float4*)s->d_blas_nodes.p : nullptr;
+    s->dev.blas_nodes = b.two_level ? (const float4*)s->trees.d_blas_nodes.p : nullptr;
     s->dev.tl_inst = b.two_level ? (const uint32_t*)s->d_tl_inst.p : nullptr;
     s->dev.tl_instances = b.two_level ? (const srd::DevTlInstance*)s->d_tl_instances.p : nullptr;
     s->dev.tris = (const float4*)s->d_tris.p;
@@ -1312,6 +1326,9 @@ void note_tree_height(SrScene* s, uint32_t kind, uint32_t cap, const LbvhResult&
 // per instance, whatever the meshes hold. Hits are those of the one-level form bit for bit (traverse.h: traverse_ws with TL = true).
 constexpr uint32_t kTlStackCap = 47;     // LDS stack entries a two-level walk may need (top-level + pending instances of a leaf + marker + mesh
                                          // tree): with the spare level and the 8 work rows, 56 rows = 56 KB for the 256-thread queue tracers
+// what a walk needs (top-level entries + pending instances of a leaf + mesh tree + 1), and what the deepest mesh tree leaves the top-level tree
+uint32_t tl_stack_need(uint32_t max_stack, uint32_t blas_stack) { return max_stack + srl::kLeafMax + blas_stack + 1u; }
+uint32_t tl_stack_left(uint32_t blas_stack) { return kTlStackCap > blas_stack + srl::kLeafMax + 1u ? kTlStackCap - blas_stack - srl::kLeafMax - 1u : 0u; }
 
 constexpr double kTlMaxCondition = 100.0;    // ||W2O||_inf * ||O2W||_inf above which an instance is baked (rotation + uniform scale: <= 3)
 
@@ -1360,13 +1377,13 @@ int build_blas(SrScene* s, uint32_t mesh_slot, const SrTransform* bake, SrScene:
     srh::build_bvh(tris, std::min(depth_for(n), 26u), bvh);          // leaves the top-level tree at least 18 of the kTlStackCap entries
     b.nodes.swap(bvh.nodes);
     b.n_tris = n; b.n_nodes = bvh.n_nodes; b.max_stack = bvh.max_stack; b.max_depth = bvh.max_depth; b.build_ms = bvh.build_ms;
-    b.max_edge_sum = max_edge; b.max_abs_vertex = max_abs;
+    b.root.max_edge_sum = max_edge; b.root.max_abs_vertex = max_abs;
     b.tris.assign((size_t)n * 12, 0.0f);
     b.shade.assign((size_t)n * 12, 0.0f);
     b.slot_of_prim.assign(n ? n : 1, 0u);
     const bool textured = [&] { const uint32_t* tex = &mesh.material.base_color_image; for (int i = 0; i < 10; i += 2) if (tex[i] != SR_NULL_TEXTURE) return true; return false; }();
     if (textured) b.shade_tex.assign((size_t)n * 24, 0.0f); else b.shade_tex.clear();
-    for (int a = 0; a < 3; a++) { b.lo[a] = INFINITY; b.hi[a] = -INFINITY; }
+    for (int a = 0; a < 3; a++) { b.root.lo[a] = INFINITY; b.root.hi[a] = -INFINITY; }
     for (uint32_t sl = 0; sl < n; sl++) {
         const uint32_t p = bvh.order[sl];
         const SrVertex* v[3];
@@ -1385,7 +1402,7 @@ int build_blas(SrScene* s, uint32_t mesh_slot, const SrTransform* bake, SrScene:
             const float pad = 4e-6f * (std::fabs(t.e1[a]) + std::fabs(t.e2[a]));
             const float lo = std::min(w[0][a], std::min(w[1][a], w[2][a])) - pad;
             const float hi = std::max(w[0][a], std::max(w[1][a], w[2][a])) + pad;
-            b.lo[a] = std::min(b.lo[a], std::nextafter(lo, -INFINITY)); b.hi[a] = std::max(b.hi[a], std::nextafter(hi, INFINITY));
+            b.root.lo[a] = std::min(b.root.lo[a], std::nextafter(lo, -INFINITY)); b.root.hi[a] = std::max(b.root.hi[a], std::nextafter(hi, INFINITY));
         }
     }
     b.valid = true;
@@ -1449,25 +1466,25 @@ int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
         s->mesh_state[m].node_cap = 0;        // the ranges behind the concatenation are given up: a later device build takes a new one
         if (s->meshes[m].n_vertices) cat.append(s->mesh_state[m].tree, &s->mesh_state[m].node_base, &s->mesh_state[m].tri_base);
     }
-    s->tl_baked_node_base.assign(baked.size(), 0u); s->tl_baked_tri_base.assign(baked.size(), 0u);
-    for (size_t k = 0; k < baked.size(); k++) cat.append(baked[k], &s->tl_baked_node_base[k], &s->tl_baked_tri_base[k]);
+    s->trees.tl_baked_node_base.assign(baked.size(), 0u); s->trees.tl_baked_tri_base.assign(baked.size(), 0u);
+    for (size_t k = 0; k < baked.size(); k++) cat.append(baked[k], &s->trees.tl_baked_node_base[k], &s->trees.tl_baked_tri_base[k]);
     if (cat.tris.size() / 12 >= (1ull << 28) || cat.nodes.size() / srl::kNodeDwords >= (1ull << 31)) return fail(SR_ERR_UNSUPPORTED, "the meshes together exceed 2^28 triangles (leaf reference encoding)");
     if (cat.textured) cat.shade_tex.resize(cat.tris.size() / 12 * 24, 0.0f);
     if (cat.slot_of_prim.empty()) cat.slot_of_prim.push_back(0u);
     HIP_TRY(hipDeviceSynchronize());
-    if ((rc = s->d_blas_nodes.upload(cat.nodes.data(), cat.nodes.size() * 4)) != SR_OK) return rc;
+    if ((rc = s->trees.d_blas_nodes.upload(cat.nodes.data(), cat.nodes.size() * 4)) != SR_OK) return rc;
     if ((rc = s->d_tris.upload(cat.tris.data(), cat.tris.size() * 4)) != SR_OK) return rc;
     if ((rc = s->d_shade.upload(cat.shade.data(), cat.shade.size() * 4)) != SR_OK) return rc;
     if (cat.textured) { if ((rc = s->d_shade_tex.upload(cat.shade_tex.data(), cat.shade_tex.size() * 4)) != SR_OK) return rc; }
     else s->d_shade_tex.release();
     if ((rc = s->d_slot_of_gid.upload(cat.slot_of_prim.data(), cat.slot_of_prim.size() * 4)) != SR_OK) return rc;
-    s->any_textured_tl = cat.textured;
-    s->tl_blas_nodes = cat.nodes.size() / srl::kNodeDwords; s->tl_blas_tris = cat.tris.size() / 12;
-    s->blas_node_end = s->tl_blas_nodes;
-    s->blas_device_current = true;
-    s->tl_baked = !baked.empty();
-    s->tl_mesh_rows_current = false;
-    s->refit_set.clear();                     // node and triangle bases moved
+    s->trees.any_textured_tl = cat.textured;
+    s->trees.tl_blas_nodes = cat.nodes.size() / srl::kNodeDwords; s->trees.tl_blas_tris = cat.tris.size() / 12;
+    s->trees.blas_node_end = s->trees.tl_blas_nodes;
+    s->trees.blas_device_current = true;
+    s->trees.tl_baked = !baked.empty();
+    s->trees.tl_mesh_rows_current = false;
+    s->refit.set.clear();                     // void: the bases moved (MeshTrees)
     return SR_OK;
 }
 
@@ -1477,6 +1494,26 @@ int upload_mesh_trees(SrScene* s, const std::vector<SrScene::HostBlas>& baked) {
 // host / device: 1 000: 0.66 / 1.83, 2 048: 1.36 / 2.07, 4 096: 2.51 / 2.30, 10 000: 6.19 / 2.71, 100 000: 60 / 5.6.
 constexpr uint32_t kTlDeviceMinBoxes = 4096;
 static_assert(sizeof(SrTopLevelInfo) == 64 && sizeof(srd::TlMeshRow) == 48 && sizeof(srd::DevTlInstance) == 128, "layouts the harness and the record kernel rely on");
+using RootBlock = SrScene::HostBlas::RootBlock;      // copied whole: both sides hold lo, hi, max_abs_vertex, max_edge_sum in this order
+static_assert(sizeof(RootBlock) == 32 && offsetof(RootBlock, hi) == 12 && offsetof(RootBlock, max_abs_vertex) == 24 && offsetof(RootBlock, max_edge_sum) == 28 &&
+              offsetof(srd::TlMeshRow, hi) == 12 && offsetof(srd::TlMeshRow, max_abs_vertex) == 24 && offsetof(srd::TlMeshRow, max_edge_sum) == 28, "a TlMeshRow begins with the root block");
+
+// Why the top-level choice leaves this many instances (or instance boxes) to the host, or SR_TL_ON_DEVICE.
+uint32_t tl_count_reason(const SrScene* s, uint32_t count) {
+    return count < 2 ? SR_TL_HOST_TOO_FEW : s->tl_build_mode == SR_TL_BUILD_AUTO && count < kTlDeviceMinBoxes ? SR_TL_HOST_BELOW_THRESHOLD : SR_TL_ON_DEVICE;
+}
+// What both top-level builders end in: the structure becomes the one the kernels see, and `info` (but for build_ms) what sr_scene_top_level_info reports.
+void publish_two_level(SrScene* s, SrTopLevelInfo info, uint32_t max_depth, float sah_cost, std::chrono::steady_clock::time_point t0) {
+    BuiltStructure built;
+    built.n_nodes = info.n_nodes + s->trees.tl_blas_nodes; built.tri_bytes = s->trees.tl_blas_tris * 48;
+    built.max_depth = max_depth; built.stack_need = tl_stack_need(info.max_stack, info.blas_stack); built.sah_cost = sah_cost;
+    built.build_ms = ms_between(t0, std::chrono::steady_clock::now());
+    built.two_level = true; built.on_device = info.on_device != 0u;
+    publish(s, built);
+    s->shape.clear();
+    info.build_ms = s->stats.build_ms;
+    s->tl_info = info;
+}
 
 // The changed instance list of a scene that is already built in the two-level form, on the device (bvh_gpu.hip): instance
 // records and padded boxes by srk_tl_records (tl_record.h, as the host loop in two_level_build), the tree over the boxes by
@@ -1484,31 +1521,29 @@ static_assert(sizeof(SrTopLevelInfo) == 64 && sizeof(srd::TlMeshRow) == 48 && si
 // job (what this function has rewritten by then, it rewrote after the device-wide wait, and the host build writes it again).
 int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0, uint32_t* reason) {
     const uint32_t ni = (uint32_t)s->fid.instances.size();
-    if (!s->built || !s->two_level || !s->blas_device_current) { *reason = SR_TL_HOST_NOT_TWO_LEVEL; return SR_OK; }   // also: meshes added or removed since
+    if (!s->built || !s->two_level || !s->trees.blas_device_current) { *reason = SR_TL_HOST_NOT_TWO_LEVEL; return SR_OK; }   // also: meshes added or removed since
     if (s->tl_build_mode == SR_TL_BUILD_HOST) { *reason = SR_TL_HOST_MODE; return SR_OK; }
-    if (ni < 2) { *reason = SR_TL_HOST_TOO_FEW; return SR_OK; }
-    if (s->tl_build_mode == SR_TL_BUILD_AUTO && ni < kTlDeviceMinBoxes) { *reason = SR_TL_HOST_BELOW_THRESHOLD; return SR_OK; }
+    if ((*reason = tl_count_reason(s, ni)) != SR_TL_ON_DEVICE) return SR_OK;
     int rc;
     HIP_TRY(hipDeviceSynchronize());          // frames in flight read the tables that are rewritten from here on
-    if (s->tl_baked && (rc = upload_mesh_trees(s, {})) != SR_OK) return rc;   // the previous list had baked copies behind the mesh trees
-    if (!s->tl_mesh_rows_current) {
+    if (s->trees.tl_baked && (rc = upload_mesh_trees(s, {})) != SR_OK) return rc;   // the previous list had baked copies behind the mesh trees
+    if (!s->trees.tl_mesh_rows_current) {
         std::vector<srd::TlMeshRow> rows(s->meshes.size() ? s->meshes.size() : 1);
         memset(rows.data(), 0, rows.size() * sizeof(srd::TlMeshRow));
         for (size_t m = 0; m < s->meshes.size(); m++) {
             if (s->meshes[m].n_vertices == 0 || !s->mesh_state[m].tree.valid) continue;
             const SrScene::HostBlas& b = s->mesh_state[m].tree;
             srd::TlMeshRow& r = rows[m];
-            memcpy(r.lo, b.lo, 12); memcpy(r.hi, b.hi, 12);
-            r.max_abs_vertex = b.max_abs_vertex; r.max_edge_sum = b.max_edge_sum;
+            memcpy(&r, &b.root, sizeof(RootBlock));
             r.max_stack = b.max_stack; r.blas_root = s->mesh_state[m].node_base; r.prim_base = s->mesh_state[m].tri_base; r.n_tris = b.n_tris;
         }
-        if ((rc = s->d_tl_mesh_rows.upload(rows.data(), rows.size() * sizeof(srd::TlMeshRow))) != SR_OK) return rc;
-        s->tl_mesh_rows_current = true;
+        if ((rc = s->trees.d_tl_mesh_rows.upload(rows.data(), rows.size() * sizeof(srd::TlMeshRow))) != SR_OK) return rc;
+        s->trees.tl_mesh_rows_current = true;
     }
     if ((rc = upload_instance_tables(s)) != SR_OK) return rc;
     if ((rc = s->d_tl_instances.reserve((size_t)ni * sizeof(srd::DevTlInstance))) != SR_OK || (rc = s->d_tl_boxes.reserve((size_t)ni * 24)) != SR_OK ||
         (rc = s->d_tl_result.reserve(16)) != SR_OK) return rc;
-    int e = srk_tl_records((const srd::FlatInstance*)s->d_flat_instances.p, (const srd::TlMeshRow*)s->d_tl_mesh_rows.p, ni, kTlMaxCondition,
+    int e = srk_tl_records((const srd::FlatInstance*)s->d_flat_instances.p, (const srd::TlMeshRow*)s->trees.d_tl_mesh_rows.p, ni, kTlMaxCondition,
                            (srd::DevTlInstance*)s->d_tl_instances.p, (float*)s->d_tl_boxes.p, (uint32_t*)s->d_tl_result.p, nullptr);
     if (e != 0) return fail(SR_ERR_HIP, std::string("instance record launch failed: ") + hipGetErrorString((hipError_t)e));
     uint32_t res[3] = {0, 0, 0};              // instances the host would bake, deepest mesh tree in use, instances with a box
@@ -1516,9 +1551,8 @@ int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0,
     const auto t1 = std::chrono::steady_clock::now();
     const uint32_t nb = res[2], blas_stack = res[1];
     if (res[0] != 0) { *reason = SR_TL_HOST_BAKED_INSTANCE; return SR_OK; }
-    if (nb < 2) { *reason = SR_TL_HOST_TOO_FEW; return SR_OK; }
-    if (s->tl_build_mode == SR_TL_BUILD_AUTO && nb < kTlDeviceMinBoxes) { *reason = SR_TL_HOST_BELOW_THRESHOLD; return SR_OK; }
-    const uint32_t left = kTlStackCap > blas_stack + srl::kLeafMax + 1u ? kTlStackCap - blas_stack - srl::kLeafMax - 1u : 0u;
+    if ((*reason = tl_count_reason(s, nb)) != SR_TL_ON_DEVICE) return SR_OK;
+    const uint32_t left = tl_stack_left(blas_stack);
     if (left < min_depth_for(nb)) { *reason = SR_TL_HOST_STACK_BUDGET; return SR_OK; }      // the host build reports the error
     const uint32_t node_cap = nb + 64;        // inner nodes of a tree with >= 2 children per node and >= 1 box per leaf: < nb
     if ((rc = s->d_nodes.reserve((size_t)node_cap * srl::kNodeBytes)) != SR_OK || (rc = s->d_node_box.reserve((size_t)node_cap * 24)) != SR_OK ||
@@ -1533,25 +1567,16 @@ int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0,
     LbvhResult r;
     e = srk_tl_build(a, &r, nullptr);
     if (e > 0) return fail(SR_ERR_HIP, std::string("device top-level build failed: ") + hipGetErrorString((hipError_t)e));
-    const uint32_t need = r.max_stack + srl::kLeafMax + blas_stack + 1u;     // as the host build counts it
+    const uint32_t need = tl_stack_need(r.max_stack, blas_stack);            // as the host build counts it
     note_tree_height(s, SR_TREE_KIND_TOP_LEVEL, left, r, e == 0 && need <= kTlStackCap);
     if (e < 0 || need > kTlStackCap) { *reason = SR_TL_HOST_STACK_BUDGET; return SR_OK; }
-    const auto t2 = std::chrono::steady_clock::now();
-    s->blas_stack = blas_stack;
-    BuiltStructure built;
-    built.n_nodes = r.n_nodes + s->tl_blas_nodes; built.tri_bytes = s->tl_blas_tris * 48;
-    built.max_depth = r.max_depth; built.stack_need = need;
-    built.build_ms = ms_between(t0, t2);
-    built.two_level = true; built.on_device = true;
-    publish(s, built);
-    s->shape.clear();
-    s->tl_boxes_host.clear();
-    SrTopLevelInfo& info = s->tl_info;
+    SrTopLevelInfo info{};
     info.on_device = 1u; info.reason = SR_TL_ON_DEVICE;
     info.n_nodes = r.n_nodes; info.n_boxes = nb; info.n_instances = ni; info.max_stack = r.max_stack; info.blas_stack = blas_stack;
     info.records_ms = ms_between(t0, t1);
-    info.tree_ms = ms_between(t1, t2);
-    info.build_ms = s->stats.build_ms;
+    info.tree_ms = ms_between(t1, std::chrono::steady_clock::now());
+    publish_two_level(s, info, r.max_depth, 0.0f, t0);
+    s->tl_boxes_host.clear();
     return SR_OK;
 }
 
@@ -1583,6 +1608,115 @@ constexpr uint32_t kBlasStackCap = 26;       // build_blas's limit: leaves the t
 static_assert(sizeof(SrMeshTreeInfo) == 40 && sizeof(SrMeshTreeBatchInfo) == 32 && sizeof(SrMeshUpdateInfo) == 64 && sizeof(SrTreeHeightInfo) == 32 && sizeof(SrMeshVertexInfo) == 40 && sizeof(SrLightTableInfo) == 56, "layouts the harness relies on");
 uint32_t blas_device_min_tris(const SrScene* s) { return s->height_bound == SR_HEIGHT_BOUND_REBALANCE ? kBlasDeviceMinTrisBounded : kBlasDeviceMinTris; }
 
+// Where a mesh-tree writer (batched build, per-mesh build, the refit's record kernel) writes; read once the call has grown the buffers.
+srd::BlasBatchArrays mesh_tree_arrays(const SrScene* s) {     // nodes, node_box, tris, shade, shade_tex, slot_of_gid, rows
+    return {(uint32_t*)s->trees.d_blas_nodes.p, (float*)s->trees.d_blas_node_box.p, (float4*)s->d_tris.p, (float4*)s->d_shade.p,
+            s->trees.any_textured_tl ? (float4*)s->d_shade_tex.p : nullptr, (uint32_t*)s->d_slot_of_gid.p, s->trees.rows_dev(s->meshes.size())};
+}
+// The host's book-keeping of one tree the device built, from the ten-word block (root block, nodes, stack need); the caller sets the level ranges.
+void note_built(SrScene* s, SrScene::HostBlas& b, const uint32_t* out, uint32_t max_depth) {
+    s->trees.tl_blas_nodes = s->trees.tl_blas_nodes - b.n_nodes + out[8];
+    memcpy(&b.root, out, sizeof(b.root));
+    b.n_nodes = out[8]; b.max_stack = out[9]; b.max_depth = max_depth;
+    b.host_stale = true; b.device_built = true;
+}
+
+// The batched step of build_mesh_trees_device. *rest receives what the batch does not take and what it hands back, in the set's
+// order, so that the per-mesh builds keep theirs.
+int batch_build_mesh_trees(SrScene* s, const std::vector<uint32_t>& set, const srd::BlasBatchArrays& arrays, uint32_t cap,
+                           std::chrono::steady_clock::time_point t0, std::vector<uint32_t>* rest) {
+    int rc;
+    std::vector<uint32_t> small;
+    for (uint32_t m : set) if (s->mesh_state[m].tree.n_tris >= 1u && s->mesh_state[m].tree.n_tris <= SR_BLAS_BATCH_MAX_TRIS) small.push_back(m);
+    std::vector<srd::BlasBatchResult> results(small.size());
+    if (!small.empty()) {
+        // one launch per kBlasBatchScratchBytes of slabs (a mesh's slab is ~0.3 KB per triangle: a launch holds hundreds of
+        // the largest meshes), all enqueued behind each other on one stream, so they may share the scratch buffer
+        std::vector<srd::BlasBatchRow> rows(small.size());
+        std::vector<uint32_t> launch_first(1, 0u);
+        size_t used = 0, most = 0;
+        for (size_t k = 0; k < small.size(); k++) {
+            const uint32_t m = small[k];
+            SrScene::MeshState& ms = s->mesh_state[m];
+            const uint32_t n = ms.tree.n_tris;
+            s->trees.take_range(ms);
+            const size_t slab = srk_blas_batch_slab_bytes(n, ms.node_cap);
+            if (used != 0 && used + slab > kBlasBatchScratchBytes) { launch_first.push_back((uint32_t)k); used = 0; }
+            srd::BlasBatchRow& r = rows[k];
+            r.vertices = (uint64_t)(uintptr_t)s->meshes[m].d_vertices; r.indices = (uint64_t)(uintptr_t)s->meshes[m].d_indices;
+            r.scratch = (uint64_t)used;                   // offset for now: the buffer may still move
+            r.n_tris = n; r.n_vertices = s->meshes[m].n_vertices;
+            r.mesh_slot = m; r.textured = ms.tree.shade_tex.empty() ? 0u : 1u;
+            r.node_base = ms.node_base; r.node_cap = ms.node_cap; r.tri_base = ms.tri_base;
+            r.stack_floor = std::min(depth_for(n), cap); r.stack_cap = cap; r._pad = 0u;
+            used += slab; most = std::max(most, used);
+        }
+        launch_first.push_back((uint32_t)small.size());
+        if ((rc = s->d_scratch.reserve(most)) != SR_OK || (rc = s->d_batch_rows.reserve(rows.size() * sizeof(srd::BlasBatchRow))) != SR_OK ||
+            (rc = s->d_batch_results.reserve(results.size() * sizeof(srd::BlasBatchResult))) != SR_OK) return rc;
+        for (srd::BlasBatchRow& r : rows) r.scratch += (uint64_t)(uintptr_t)s->d_scratch.p;
+        HIP_TRY(hipMemcpyAsync(s->d_batch_rows.p, rows.data(), rows.size() * sizeof(srd::BlasBatchRow), hipMemcpyHostToDevice, nullptr));
+        HIP_TRY(hipMemsetAsync(s->d_batch_results.p, 0xFF, results.size() * sizeof(srd::BlasBatchResult), nullptr));      // a status no workgroup writes
+        for (size_t l = 0; l + 1 < launch_first.size(); l++) {
+            const int e = srk_blas_batch_build((const srd::BlasBatchRow*)s->d_batch_rows.p + launch_first[l], launch_first[l + 1] - launch_first[l], arrays,
+                                               (srd::BlasBatchResult*)s->d_batch_results.p + launch_first[l], s->fast_build_ploc, nullptr);
+            if (e != 0) return fail(SR_ERR_HIP, std::string("batched mesh-tree build failed: ") + hipGetErrorString((hipError_t)e));
+        }
+        HIP_TRY(hipMemcpy(results.data(), s->d_batch_results.p, results.size() * sizeof(srd::BlasBatchResult), hipMemcpyDeviceToHost));   // the only wait
+        s->batch_info.launches = (uint32_t)launch_first.size() - 1u;
+        if (s->timing) s->batch_info.batch_ms = ms_between(t0, std::chrono::steady_clock::now());
+    }
+    size_t k = 0;
+    for (uint32_t m : set) {
+        if (k >= small.size() || small[k] != m) { rest->push_back(m); continue; }
+        const srd::BlasBatchResult& r = results[k++];
+        SrScene::HostBlas& b = s->mesh_state[m].tree;
+        if (r.status != srd::kBlasBatchBuilt || r.n_levels == 0u || r.n_levels > srd::kBlasBatchMaxLevels || r.out[9] > cap) {
+            s->batch_info.passed_on++; rest->push_back(m); continue;      // too tall or failed: its ranges are as they were
+        }
+        LbvhResult h;
+        h.height_before = h.height_after = r.height;
+        note_tree_height(s, SR_TREE_KIND_MESH, cap, h, true);
+        note_built(s, b, r.out, r.n_levels);
+        b.level_ranges.clear();
+        for (uint32_t l = 0; l < r.n_levels; l++) b.level_ranges.emplace_back(r.levels[2 * l], r.levels[2 * l + 1]);
+        s->batch_info.batched++;
+    }
+    return SR_OK;
+}
+
+// The per-mesh step of build_mesh_trees_device. A tree deeper than `cap` is refused through *reason and remembered with the topology it
+// was refused under (the attempt is not repeated); the mesh's book-keeping is then as it was.
+int build_mesh_tree_device(SrScene* s, uint32_t m, const srd::BlasBatchArrays& arrays, uint32_t cap, uint32_t* reason) {
+    SrScene::MeshState& ms = s->mesh_state[m];
+    SrScene::HostBlas& b = ms.tree;
+    const uint32_t n = b.n_tris;
+    s->trees.take_range(ms);
+    if (const int rc = s->d_scratch.reserve(srk_lbvh_scratch_bytes(n, ms.node_cap)); rc != SR_OK) return rc;
+    LbvhArgs a{};
+    a.n_tris = n;
+    a.vertices = (const SrVertex*)s->meshes[m].d_vertices; a.indices = (const uint32_t*)s->meshes[m].d_indices; a.n_vertices = s->meshes[m].n_vertices;
+    a.mesh_slot = m; a.textured = b.shade_tex.empty() ? 0u : 1u;
+    a.nodes = (float4*)arrays.nodes; a.node_box = arrays.node_box; a.tris = arrays.tris; a.shade = arrays.shade; a.shade_tex = arrays.shade_tex;
+    a.slot_of_gid = arrays.slot_of_gid; a.rows = arrays.rows;
+    a.node_base = ms.node_base; a.node_cap = ms.node_cap; a.tri_base = ms.tri_base;
+    a.out = (uint32_t*)s->d_blas_build_out.p;
+    a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
+    a.stack_floor = std::min(depth_for(n), cap); a.stack_cap = cap;
+    a.ploc = s->fast_build_ploc;
+    a.rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
+    LbvhResult r;
+    const int e = srk_blas_build(a, &r, nullptr);
+    if (e > 0) return fail(SR_ERR_HIP, std::string("device mesh-tree build failed: ") + hipGetErrorString((hipError_t)e));
+    note_tree_height(s, SR_TREE_KIND_MESH, cap, r, e == 0 && r.max_stack <= cap);
+    if (e < 0 || r.max_stack > cap) { ms.device_refused = s->fast_build_ploc; *reason = SR_MESH_TREE_HOST_STACK_BUDGET; return SR_OK; }
+    uint32_t out[10];
+    HIP_TRY(hipMemcpy(out, s->d_blas_build_out.p, sizeof(out), hipMemcpyDeviceToHost));
+    note_built(s, b, out, r.max_depth);
+    b.level_ranges = r.level_ranges;
+    return SR_OK;
+}
+
 // Blas::rebuild (blas.rs:285-310) on the device for the meshes of `set` (pending updatable meshes whose state asked for
 // SR_OP_FAST_BUILD): srk_blas_build writes each tree into the mesh's ranges of the concatenated arrays, which stay resident.
 // The triangle-side ranges stay where they are (only the leaf order inside them changes). A device-built tree has another node
@@ -1594,119 +1728,20 @@ uint32_t blas_device_min_tris(const SrScene* s) { return s->height_bound == SR_H
 // (too tall, failed: its ranges are as they were), then goes through srk_blas_build as without the batch.
 int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32_t* reason) {
     int rc;
-    uint64_t end = s->blas_node_end;
-    for (uint32_t m : set) if (s->mesh_state[m].node_cap == 0) end += (uint64_t)s->mesh_state[m].tree.n_tris + 64u;
+    uint64_t end = s->trees.blas_node_end;
+    for (uint32_t m : set) if (s->mesh_state[m].node_cap == 0) end += SrScene::MeshTrees::range_bound(s->mesh_state[m].tree.n_tris);
     if (end >= (1ull << 31)) return fail(SR_ERR_UNSUPPORTED, "the mesh trees together exceed 2^31 nodes");
     HIP_TRY(hipDeviceSynchronize());          // frames in flight read the arrays that are rewritten (and may move) from here on
-    if ((rc = s->d_blas_nodes.grow_keep((size_t)end * srl::kNodeBytes, (size_t)s->blas_node_end * srl::kNodeBytes)) != SR_OK ||
-        (rc = s->d_blas_node_box.reserve((size_t)end * 24)) != SR_OK || (rc = s->d_blas_build_out.reserve(64)) != SR_OK) return rc;
-    const size_t nm = s->meshes.size();
-    srd::TlMeshRow* rows_dev = (s->tl_mesh_rows_current && s->d_tl_mesh_rows.bytes >= nm * sizeof(srd::TlMeshRow)) ? (srd::TlMeshRow*)s->d_tl_mesh_rows.p : nullptr;
+    if ((rc = s->trees.d_blas_nodes.grow_keep((size_t)end * srl::kNodeBytes, (size_t)s->trees.blas_node_end * srl::kNodeBytes)) != SR_OK ||
+        (rc = s->trees.d_blas_node_box.reserve((size_t)end * 24)) != SR_OK || (rc = s->d_blas_build_out.reserve(64)) != SR_OK) return rc;
+    const srd::BlasBatchArrays arrays = mesh_tree_arrays(s);
     const auto t0 = std::chrono::steady_clock::now();
-    const bool rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
-    const uint32_t cap = rebalance && s->mesh_tree_cap ? s->mesh_tree_cap : kBlasStackCap;      // binds device builds only
-    // the host's book-keeping of one tree the device built, from the ten-word block and the level ranges
-    auto note_built = [&](SrScene::HostBlas& b, const uint32_t* out, uint32_t max_depth) {
-        s->tl_blas_nodes = s->tl_blas_nodes - b.n_nodes + out[8];
-        memcpy(b.lo, out, 12); memcpy(b.hi, out + 3, 12); memcpy(&b.max_abs_vertex, out + 6, 4); memcpy(&b.max_edge_sum, out + 7, 4);
-        b.n_nodes = out[8]; b.max_stack = out[9]; b.max_depth = max_depth;
-        b.host_stale = true; b.device_built = true;
-    };
+    const uint32_t cap = s->height_bound == SR_HEIGHT_BOUND_REBALANCE && s->mesh_tree_cap ? s->mesh_tree_cap : kBlasStackCap;      // binds device builds only
     std::vector<uint32_t> rest;               // what the per-mesh build takes: everything, or what the batch does not take or hands back
-    if (s->blas_batch_mode == SR_BLAS_BATCH_ON) {
-        std::vector<uint32_t> small;
-        for (uint32_t m : set) if (s->mesh_state[m].tree.n_tris >= 1u && s->mesh_state[m].tree.n_tris <= SR_BLAS_BATCH_MAX_TRIS) small.push_back(m);
-        std::vector<srd::BlasBatchResult> results(small.size());
-        if (!small.empty()) {
-            // one launch per kBlasBatchScratchBytes of slabs (a mesh's slab is ~0.3 KB per triangle: a launch holds hundreds of
-            // the largest meshes), all enqueued behind each other on one stream, so they may share the scratch buffer
-            std::vector<srd::BlasBatchRow> rows(small.size());
-            std::vector<uint32_t> launch_first(1, 0u);
-            size_t used = 0, most = 0;
-            for (size_t k = 0; k < small.size(); k++) {
-                const uint32_t m = small[k];
-                SrScene::MeshState& ms = s->mesh_state[m];
-                const uint32_t n = ms.tree.n_tris;
-                if (ms.node_cap == 0) { ms.node_base = (uint32_t)s->blas_node_end; ms.node_cap = n + 64u; s->blas_node_end += ms.node_cap; }
-                const size_t slab = srk_blas_batch_slab_bytes(n, ms.node_cap);
-                if (used != 0 && used + slab > kBlasBatchScratchBytes) { launch_first.push_back((uint32_t)k); used = 0; }
-                srd::BlasBatchRow& r = rows[k];
-                r.vertices = (uint64_t)(uintptr_t)s->meshes[m].d_vertices; r.indices = (uint64_t)(uintptr_t)s->meshes[m].d_indices;
-                r.scratch = (uint64_t)used;                   // offset for now: the buffer may still move
-                r.n_tris = n; r.n_vertices = s->meshes[m].n_vertices;
-                r.mesh_slot = m; r.textured = ms.tree.shade_tex.empty() ? 0u : 1u;
-                r.node_base = ms.node_base; r.node_cap = ms.node_cap; r.tri_base = ms.tri_base;
-                r.stack_floor = std::min(depth_for(n), cap); r.stack_cap = cap; r._pad = 0u;
-                used += slab; most = std::max(most, used);
-            }
-            launch_first.push_back((uint32_t)small.size());
-            if ((rc = s->d_scratch.reserve(most)) != SR_OK || (rc = s->d_batch_rows.reserve(rows.size() * sizeof(srd::BlasBatchRow))) != SR_OK ||
-                (rc = s->d_batch_results.reserve(results.size() * sizeof(srd::BlasBatchResult))) != SR_OK) return rc;
-            for (srd::BlasBatchRow& r : rows) r.scratch += (uint64_t)(uintptr_t)s->d_scratch.p;
-            srd::BlasBatchArrays arrays{};
-            arrays.nodes = (uint32_t*)s->d_blas_nodes.p; arrays.node_box = (float*)s->d_blas_node_box.p;
-            arrays.tris = (float4*)s->d_tris.p; arrays.shade = (float4*)s->d_shade.p; arrays.shade_tex = s->any_textured_tl ? (float4*)s->d_shade_tex.p : nullptr;
-            arrays.slot_of_gid = (uint32_t*)s->d_slot_of_gid.p; arrays.rows = rows_dev;
-            HIP_TRY(hipMemcpyAsync(s->d_batch_rows.p, rows.data(), rows.size() * sizeof(srd::BlasBatchRow), hipMemcpyHostToDevice, nullptr));
-            HIP_TRY(hipMemsetAsync(s->d_batch_results.p, 0xFF, results.size() * sizeof(srd::BlasBatchResult), nullptr));      // a status no workgroup writes
-            for (size_t l = 0; l + 1 < launch_first.size(); l++) {
-                const int e = srk_blas_batch_build((const srd::BlasBatchRow*)s->d_batch_rows.p + launch_first[l], launch_first[l + 1] - launch_first[l], arrays,
-                                                   (srd::BlasBatchResult*)s->d_batch_results.p + launch_first[l], s->fast_build_ploc, nullptr);
-                if (e != 0) return fail(SR_ERR_HIP, std::string("batched mesh-tree build failed: ") + hipGetErrorString((hipError_t)e));
-            }
-            HIP_TRY(hipMemcpy(results.data(), s->d_batch_results.p, results.size() * sizeof(srd::BlasBatchResult), hipMemcpyDeviceToHost));   // the only wait
-            s->batch_info.launches = (uint32_t)launch_first.size() - 1u;
-            if (s->timing) s->batch_info.batch_ms = ms_between(t0, std::chrono::steady_clock::now());
-        }
-        size_t k = 0;
-        for (uint32_t m : set) {              // in the set's order, so that the per-mesh builds keep theirs
-            if (k >= small.size() || small[k] != m) { rest.push_back(m); continue; }
-            const srd::BlasBatchResult& r = results[k++];
-            SrScene::HostBlas& b = s->mesh_state[m].tree;
-            if (r.status != srd::kBlasBatchBuilt || r.n_levels == 0u || r.n_levels > srd::kBlasBatchMaxLevels || r.out[9] > cap) {
-                s->batch_info.passed_on++; rest.push_back(m); continue;      // too tall or failed: its ranges are as they were
-            }
-            LbvhResult h;
-            h.height_before = h.height_after = r.height;
-            note_tree_height(s, SR_TREE_KIND_MESH, cap, h, true);
-            note_built(b, r.out, r.n_levels);
-            b.level_ranges.clear();
-            for (uint32_t l = 0; l < r.n_levels; l++) b.level_ranges.emplace_back(r.levels[2 * l], r.levels[2 * l + 1]);
-            s->batch_info.batched++;
-        }
-    } else rest = set;
-    for (uint32_t m : rest) {
-        SrScene::MeshState& ms = s->mesh_state[m];
-        SrScene::HostBlas& b = ms.tree;
-        const uint32_t n = b.n_tris;
-        if (ms.node_cap == 0) { ms.node_base = (uint32_t)s->blas_node_end; ms.node_cap = n + 64u; s->blas_node_end += ms.node_cap; }
-        if ((rc = s->d_scratch.reserve(srk_lbvh_scratch_bytes(n, ms.node_cap))) != SR_OK) return rc;
-        LbvhArgs a{};
-        a.n_tris = n;
-        a.vertices = (const SrVertex*)s->meshes[m].d_vertices; a.indices = (const uint32_t*)s->meshes[m].d_indices; a.n_vertices = s->meshes[m].n_vertices;
-        a.mesh_slot = m; a.textured = b.shade_tex.empty() ? 0u : 1u;
-        a.nodes = (float4*)s->d_blas_nodes.p; a.node_base = ms.node_base; a.node_cap = ms.node_cap; a.node_box = (float*)s->d_blas_node_box.p;
-        a.tris = (float4*)s->d_tris.p; a.shade = (float4*)s->d_shade.p; a.shade_tex = s->any_textured_tl ? (float4*)s->d_shade_tex.p : nullptr;
-        a.slot_of_gid = (uint32_t*)s->d_slot_of_gid.p; a.tri_base = ms.tri_base;
-        a.rows = rows_dev; a.out = (uint32_t*)s->d_blas_build_out.p;
-        a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
-        a.stack_floor = std::min(depth_for(n), cap); a.stack_cap = cap;
-        a.ploc = s->fast_build_ploc;
-        a.rebalance = rebalance;
-        LbvhResult r;
-        const int e = srk_blas_build(a, &r, nullptr);
-        if (e > 0) return fail(SR_ERR_HIP, std::string("device mesh-tree build failed: ") + hipGetErrorString((hipError_t)e));
-        note_tree_height(s, SR_TREE_KIND_MESH, cap, r, e == 0 && r.max_stack <= cap);
-        if (e < 0 || r.max_stack > cap) {           // deeper than the host's limit for mesh trees: remembered, the attempt is not repeated
-            ms.device_refused = s->fast_build_ploc;
-            *reason = SR_MESH_TREE_HOST_STACK_BUDGET;
-            return SR_OK;
-        }
-        uint32_t out[10];
-        HIP_TRY(hipMemcpy(out, s->d_blas_build_out.p, sizeof(out), hipMemcpyDeviceToHost));
-        note_built(b, out, r.max_depth);
-        b.level_ranges = r.level_ranges;
-    }
+    if (s->blas_batch_mode != SR_BLAS_BATCH_ON) rest = set;
+    else if ((rc = batch_build_mesh_trees(s, set, arrays, cap, t0, &rest)) != SR_OK) return rc;
+    for (uint32_t m : rest)                   // a refusal returns at once: the caller's invalidation also takes what was built so far
+        if ((rc = build_mesh_tree_device(s, m, arrays, cap, reason)) != SR_OK || *reason != SR_MESH_TREE_ON_DEVICE) return rc;
     if (!set.empty()) { s->mt_info.n_nodes = s->mesh_state[set.back()].tree.n_nodes; s->mt_info.max_stack = s->mesh_state[set.back()].tree.max_stack; }
     if (s->timing) s->mt_info.device_build_ms = ms_between(t0, std::chrono::steady_clock::now());   // every build ends with a wait for its stream
     for (uint32_t m : set) {                  // all were taken: they count as built (mark_mesh_trees: SR_OP_FAST_BUILD)
@@ -1714,7 +1749,117 @@ int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32
         ms.refit_pending = false; ms.rebuilt_now = true;
         s->mu_info.blas_rebuilt++; s->mt_info.built_on_device++;
     }
-    s->refit_set.clear();                     // node lists of these meshes changed
+    s->refit.set.clear();                     // void: the node lists of these meshes changed (MeshTrees)
+    return SR_OK;
+}
+
+struct PendingMeshTrees {                     // the classification of maintain_mesh_trees
+    std::vector<uint32_t> refits, builds;     // pending meshes that ask for SR_OP_UPDATE / SR_OP_FAST_BUILD (more than 8 updates since its rebuild)
+    bool slow = false, any_pending = false, any_stale = false;    // one asks for anything else; any is pending; any has a stale host copy
+};
+void classify_pending_mesh_trees(SrScene* s, uint32_t forced, PendingMeshTrees& p) {
+    for (size_t m = 0; m < s->meshes.size(); m++) {
+        SrScene::MeshState& ms = s->mesh_state[m];
+        ms.rebuilt_now = ms.refit_now = false;
+        if (s->meshes[m].n_vertices == 0) continue;
+        p.any_stale = p.any_stale || ms.tree.host_stale;
+        if (!ms.refit_pending) continue;
+        p.any_pending = true;
+        const uint32_t op = forced != SR_OP_NONE ? forced : srh::as_state_next_op(ms.state, true);
+        if (op == SR_OP_UPDATE) p.refits.push_back((uint32_t)m);
+        else if (op == SR_OP_FAST_BUILD) p.builds.push_back((uint32_t)m);
+        else p.slow = true;
+    }
+}
+
+// SR_MESH_TREE_ON_DEVICE or why the host takes all. First anything that makes the build re-concatenate the mesh trees: the form, meshes added or
+// removed, an updated Static mesh, baked copies behind the mesh trees now or in the new list; then what the pending meshes themselves ask for.
+uint32_t mesh_tree_host_reason(const SrScene* s, const PendingMeshTrees& p) {
+    if (!s->built || !s->two_level || !s->trees.blas_device_current) return s->static_mesh_updated ? SR_MESH_TREE_HOST_STATIC_MESH : SR_MESH_TREE_HOST_NOT_RESIDENT;
+    if (s->trees.tl_baked) return SR_MESH_TREE_HOST_BAKED_INSTANCE;
+    for (const srh::HostInstance& in : s->fid.instances) if (instance_is_baked(in.o2w.m)) return SR_MESH_TREE_HOST_BAKED_INSTANCE;
+    if (p.slow) return SR_MESH_TREE_HOST_SLOW_BUILD;
+    for (uint32_t m : p.builds) {
+        const uint32_t n = s->mesh_state[m].tree.n_tris;
+        if (s->blas_build_mode == SR_MESH_TREE_BUILD_HOST) return SR_MESH_TREE_HOST_MODE;
+        if (s->blas_build_mode == SR_MESH_TREE_BUILD_AUTO && n < blas_device_min_tris(s) &&
+            !(s->blas_batch_mode == SR_BLAS_BATCH_ON && n <= SR_BLAS_BATCH_MAX_TRIS)) return SR_MESH_TREE_HOST_BELOW_THRESHOLD;      // the batch is an opt-in for small meshes
+        if (s->mesh_state[m].device_refused == s->fast_build_ploc) return SR_MESH_TREE_HOST_STACK_BUDGET;     // refused before
+    }
+    return SR_MESH_TREE_ON_DEVICE;
+}
+
+// Another set of meshes than the device refitted last: its rows, node lists and accumulator init into the cached refit set.
+int prepare_refit_set(SrScene* s, const std::vector<uint32_t>& set) {
+    std::vector<srd::BlasRefitMesh> rows(set.size());
+    std::vector<std::vector<uint32_t>> by_depth;
+    uint32_t threads = 0;
+    for (size_t k = 0; k < set.size(); k++) {
+        const uint32_t m = set[k];
+        const SrScene::HostBlas& b = s->mesh_state[m].tree;
+        srd::BlasRefitMesh& r = rows[k];
+        r.vertices = (uint64_t)(uintptr_t)s->meshes[m].d_vertices; r.indices = (uint64_t)(uintptr_t)s->meshes[m].d_indices;
+        r.tri_base = s->mesh_state[m].tri_base; r.n_tris = b.n_tris; r.n_vertices = s->meshes[m].n_vertices;
+        r.first_thread = threads; r.mesh_slot = m; r.textured = b.shade_tex.empty() ? 0u : 1u;
+        threads += (b.n_tris + 63u) & ~63u;
+        const uint32_t nb = s->mesh_state[m].node_base;
+        if (b.device_built) {             // the host copy's topology is stale: the levels the device build returned
+            if (by_depth.size() < b.level_ranges.size()) by_depth.resize(b.level_ranges.size());
+            for (size_t d = 0; d < b.level_ranges.size(); d++)
+                for (uint32_t q = 0; q < b.level_ranges[d].second; q++) by_depth[d].push_back(nb + b.level_ranges[d].first + q);
+            continue;
+        }
+        std::vector<uint32_t> nodes, offsets;       // deepest level first
+        srh::tree_levels(b.nodes, nodes, offsets);
+        const size_t levels = offsets.size() - 1;
+        if (by_depth.size() < levels) by_depth.resize(levels);
+        for (size_t l = 0; l < levels; l++)
+            for (uint32_t q = offsets[l]; q < offsets[l + 1]; q++) by_depth[levels - 1 - l].push_back(nb + nodes[q]);
+    }
+    std::vector<uint32_t> list;
+    s->refit.level_offsets.assign(1, 0u);
+    for (size_t d = by_depth.size(); d-- > 0;) { list.insert(list.end(), by_depth[d].begin(), by_depth[d].end()); s->refit.level_offsets.push_back((uint32_t)list.size()); }
+    std::vector<uint32_t> init(set.size() * 8);
+    for (size_t k = 0; k < set.size(); k++) {       // order-preserving encoding (bvh_gpu.hip enc_f) of +inf x 3, -inf x 3, 0, 0
+        uint32_t* q = &init[k * 8];
+        q[0] = q[1] = q[2] = 0xFF800000u; q[3] = q[4] = q[5] = 0x007FFFFFu; q[6] = q[7] = 0x80000000u;
+    }
+    int rc;
+    if ((rc = s->refit.d_meshes.upload(rows.data(), rows.size() * sizeof(srd::BlasRefitMesh))) != SR_OK ||
+        (rc = s->refit.d_nodes.upload(list.data(), list.size() * 4)) != SR_OK ||
+        (rc = s->refit.d_acc_init.upload(init.data(), init.size() * 4)) != SR_OK ||
+        (rc = s->refit.d_acc.reserve(init.size() * 4)) != SR_OK || (rc = s->refit.d_out.reserve(init.size() * 4)) != SR_OK) return rc;
+    s->refit.set = set;
+    s->refit.threads = threads;
+    return SR_OK;
+}
+
+// The device refit of the cached set: two kinds of launch, one read-back of the root blocks (32 bytes per mesh), the per-mesh marks.
+int refit_mesh_trees(SrScene* s) {
+    const std::vector<uint32_t>& set = s->refit.set;
+    if (const int rc = s->trees.d_blas_node_box.reserve((size_t)s->trees.blas_node_end * 24); rc != SR_OK) return rc;
+    const srd::BlasBatchArrays arrays = mesh_tree_arrays(s);
+    ThreeMarkTimer timer(s);
+    timer.mark();
+    int e = srk_blas_records((const srd::BlasRefitMesh*)s->refit.d_meshes.p, (uint32_t)set.size(), s->refit.threads, arrays.tris, arrays.shade, arrays.shade_tex,
+                             (uint32_t*)s->refit.d_acc.p, (const uint32_t*)s->refit.d_acc_init.p, arrays.rows, (float*)s->refit.d_out.p, nullptr);
+    timer.mark();
+    if (e == 0) e = srk_blas_refit(arrays.nodes, arrays.tris, arrays.node_box, (const uint32_t*)s->refit.d_nodes.p,
+                                   s->refit.level_offsets.data(), (uint32_t)s->refit.level_offsets.size() - 1, nullptr);
+    timer.mark();
+    std::vector<float> out(set.size() * 8);
+    const hipError_t ce = e == 0 ? hipMemcpy(out.data(), s->refit.d_out.p, out.size() * 4, hipMemcpyDeviceToHost) : hipSuccess;   // waits for the launches above
+    if (e == 0 && ce == hipSuccess) timer.read(&s->mu_info.flatten_ms, &s->mu_info.refit_ms);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("mesh-tree refit launch failed: ") + hipGetErrorString((hipError_t)e));
+    HIP_TRY(ce);
+    for (size_t k = 0; k < set.size(); k++) {
+        SrScene::MeshState& a = s->mesh_state[set[k]];
+        memcpy(&a.tree.root, &out[k * 8], sizeof(a.tree.root));
+        a.tree.host_stale = true;
+        a.refit_pending = false; a.refit_now = true; a.last_op = SR_OP_UPDATE;
+        srh::as_state_mark_built(a.state, SR_OP_UPDATE);
+        s->mu_info.blas_refitted++;
+    }
     return SR_OK;
 }
 
@@ -1728,119 +1873,25 @@ int build_mesh_trees_device(SrScene* s, const std::vector<uint32_t>& set, uint32
 // re-uploads every mesh's host copy, so it also takes the meshes an earlier refit or device build left with a stale host copy.
 // Runs before two_level_build, which then sees current root boxes and stack needs.
 int maintain_mesh_trees(SrScene* s, uint32_t forced) {
-    const size_t nm = s->meshes.size();
     s->mu_info.blas_refitted = 0;
     SrMeshTreeInfo& ti = s->mt_info;
     ti.built_on_device = ti.built_on_host = 0; ti.reason = SR_MESH_TREE_ON_DEVICE; ti.device_build_ms = 0.0;
     s->batch_info.batched = s->batch_info.passed_on = s->batch_info.launches = 0u; s->batch_info.batch_ms = 0.0;
-    std::vector<uint32_t> set, builds;        // refits, device builds
-    bool any_stale = false, any_pending = false, slow = false;
-    for (size_t m = 0; m < nm; m++) {
-        SrScene::MeshState& ms = s->mesh_state[m];
-        ms.rebuilt_now = ms.refit_now = false;
-        if (s->meshes[m].n_vertices == 0) continue;
-        any_stale = any_stale || ms.tree.host_stale;
-        if (!ms.refit_pending) continue;
-        any_pending = true;
-        const uint32_t op = forced != SR_OP_NONE ? forced : srh::as_state_next_op(ms.state, true);
-        if (op == SR_OP_UPDATE) set.push_back((uint32_t)m);
-        else if (op == SR_OP_FAST_BUILD) builds.push_back((uint32_t)m);     // more than 8 updates since its rebuild
-        else slow = true;
-    }
-    if (!any_pending && !any_stale) { if (s->static_mesh_updated) ti.reason = SR_MESH_TREE_HOST_STATIC_MESH; return SR_OK; }
-    // anything that makes the build re-concatenate the mesh trees: the form, meshes added or removed, an updated Static mesh, baked
-    // copies behind the mesh trees now or in the new list; then what the pending meshes themselves ask for
-    uint32_t reason = SR_MESH_TREE_ON_DEVICE;
-    if (!s->built || !s->two_level || !s->blas_device_current) reason = s->static_mesh_updated ? SR_MESH_TREE_HOST_STATIC_MESH : SR_MESH_TREE_HOST_NOT_RESIDENT;
-    else if (s->tl_baked) reason = SR_MESH_TREE_HOST_BAKED_INSTANCE;
-    for (size_t i = 0; reason == SR_MESH_TREE_ON_DEVICE && i < s->fid.instances.size(); i++)
-        if (instance_is_baked(s->fid.instances[i].o2w.m)) reason = SR_MESH_TREE_HOST_BAKED_INSTANCE;
-    if (reason == SR_MESH_TREE_ON_DEVICE && slow) reason = SR_MESH_TREE_HOST_SLOW_BUILD;
-    for (size_t k = 0; reason == SR_MESH_TREE_ON_DEVICE && k < builds.size(); k++) {
-        if (s->blas_build_mode == SR_MESH_TREE_BUILD_HOST) reason = SR_MESH_TREE_HOST_MODE;
-        else if (s->blas_build_mode == SR_MESH_TREE_BUILD_AUTO && s->mesh_state[builds[k]].tree.n_tris < blas_device_min_tris(s) &&
-                 !(s->blas_batch_mode == SR_BLAS_BATCH_ON && s->mesh_state[builds[k]].tree.n_tris <= SR_BLAS_BATCH_MAX_TRIS)) reason = SR_MESH_TREE_HOST_BELOW_THRESHOLD;      // the batch is an opt-in for small meshes
-        else if (s->mesh_state[builds[k]].device_refused == s->fast_build_ploc) reason = SR_MESH_TREE_HOST_STACK_BUDGET;     // refused before
-    }
+    PendingMeshTrees p;
+    classify_pending_mesh_trees(s, forced, p);
+    if (!p.any_pending && !p.any_stale) { if (s->static_mesh_updated) ti.reason = SR_MESH_TREE_HOST_STATIC_MESH; return SR_OK; }
     int rc;
-    if (reason == SR_MESH_TREE_ON_DEVICE && !builds.empty() && (rc = build_mesh_trees_device(s, builds, &reason)) != SR_OK) return rc;
+    uint32_t reason = mesh_tree_host_reason(s, p);
+    if (reason == SR_MESH_TREE_ON_DEVICE && !p.builds.empty() && (rc = build_mesh_trees_device(s, p.builds, &reason)) != SR_OK) return rc;
     if (reason != SR_MESH_TREE_ON_DEVICE) {
-        for (size_t m = 0; m < nm; m++)
-            if (s->mesh_state[m].refit_pending || s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
+        invalidate_mesh_trees(s, true);
         ti.reason = reason;
-        if (!builds.empty()) s->height_info[SR_TREE_KIND_MESH].on_device = 0u;      // the host takes the trees that asked for a fast build
+        if (!p.builds.empty()) s->height_info[SR_TREE_KIND_MESH].on_device = 0u;      // the host takes the trees that asked for a fast build
         return SR_OK;
     }
-    if (set.empty()) return SR_OK;
-    if (set != s->refit_set) {                // another set of meshes than last time: its rows and node lists
-        std::vector<srd::BlasRefitMesh> rows(set.size());
-        std::vector<std::vector<uint32_t>> by_depth;
-        uint32_t threads = 0;
-        for (size_t k = 0; k < set.size(); k++) {
-            const uint32_t m = set[k];
-            const SrScene::HostBlas& b = s->mesh_state[m].tree;
-            srd::BlasRefitMesh& r = rows[k];
-            r.vertices = (uint64_t)(uintptr_t)s->meshes[m].d_vertices; r.indices = (uint64_t)(uintptr_t)s->meshes[m].d_indices;
-            r.tri_base = s->mesh_state[m].tri_base; r.n_tris = b.n_tris; r.n_vertices = s->meshes[m].n_vertices;
-            r.first_thread = threads; r.mesh_slot = m; r.textured = b.shade_tex.empty() ? 0u : 1u;
-            threads += (b.n_tris + 63u) & ~63u;
-            const uint32_t nb = s->mesh_state[m].node_base;
-            if (b.device_built) {             // the host copy's topology is stale: the levels the device build returned
-                if (by_depth.size() < b.level_ranges.size()) by_depth.resize(b.level_ranges.size());
-                for (size_t d = 0; d < b.level_ranges.size(); d++)
-                    for (uint32_t q = 0; q < b.level_ranges[d].second; q++) by_depth[d].push_back(nb + b.level_ranges[d].first + q);
-                continue;
-            }
-            std::vector<uint32_t> nodes, offsets;       // deepest level first
-            srh::tree_levels(b.nodes, nodes, offsets);
-            const size_t levels = offsets.size() - 1;
-            if (by_depth.size() < levels) by_depth.resize(levels);
-            for (size_t l = 0; l < levels; l++)
-                for (uint32_t q = offsets[l]; q < offsets[l + 1]; q++) by_depth[levels - 1 - l].push_back(nb + nodes[q]);
-        }
-        std::vector<uint32_t> list;
-        s->refit_level_offsets.assign(1, 0u);
-        for (size_t d = by_depth.size(); d-- > 0;) { list.insert(list.end(), by_depth[d].begin(), by_depth[d].end()); s->refit_level_offsets.push_back((uint32_t)list.size()); }
-        std::vector<uint32_t> init(set.size() * 8);
-        for (size_t k = 0; k < set.size(); k++) {       // order-preserving encoding (bvh_gpu.hip enc_f) of +inf x 3, -inf x 3, 0, 0
-            uint32_t* q = &init[k * 8];
-            q[0] = q[1] = q[2] = 0xFF800000u; q[3] = q[4] = q[5] = 0x007FFFFFu; q[6] = q[7] = 0x80000000u;
-        }
-        if ((rc = s->d_refit_meshes.upload(rows.data(), rows.size() * sizeof(srd::BlasRefitMesh))) != SR_OK ||
-            (rc = s->d_refit_nodes.upload(list.data(), list.size() * 4)) != SR_OK ||
-            (rc = s->d_refit_acc_init.upload(init.data(), init.size() * 4)) != SR_OK ||
-            (rc = s->d_refit_acc.reserve(init.size() * 4)) != SR_OK || (rc = s->d_refit_out.reserve(init.size() * 4)) != SR_OK) return rc;
-        s->refit_set = set;
-        s->refit_threads = threads;
-    }
-    if ((rc = s->d_blas_node_box.reserve((size_t)s->blas_node_end * 24)) != SR_OK) return rc;
-    ThreeMarkTimer timer(s);
-    timer.mark();
-    srd::TlMeshRow* rows_dev = (s->tl_mesh_rows_current && s->d_tl_mesh_rows.bytes >= nm * sizeof(srd::TlMeshRow)) ? (srd::TlMeshRow*)s->d_tl_mesh_rows.p : nullptr;
-    int e = srk_blas_records((const srd::BlasRefitMesh*)s->d_refit_meshes.p, (uint32_t)set.size(), s->refit_threads, (float4*)s->d_tris.p, (float4*)s->d_shade.p,
-                             s->any_textured_tl ? (float4*)s->d_shade_tex.p : nullptr, (uint32_t*)s->d_refit_acc.p, (const uint32_t*)s->d_refit_acc_init.p,
-                             rows_dev, (float*)s->d_refit_out.p, nullptr);
-    timer.mark();
-    if (e == 0) e = srk_blas_refit((uint32_t*)s->d_blas_nodes.p, (const float4*)s->d_tris.p, (float*)s->d_blas_node_box.p, (const uint32_t*)s->d_refit_nodes.p,
-                                   s->refit_level_offsets.data(), (uint32_t)s->refit_level_offsets.size() - 1, nullptr);
-    timer.mark();
-    std::vector<float> out(set.size() * 8);
-    const hipError_t ce = e == 0 ? hipMemcpy(out.data(), s->d_refit_out.p, out.size() * 4, hipMemcpyDeviceToHost) : hipSuccess;   // 32 bytes per mesh; waits for the launches above
-    if (e == 0 && ce == hipSuccess) timer.read(&s->mu_info.flatten_ms, &s->mu_info.refit_ms);
-    if (e != 0) return fail(SR_ERR_HIP, std::string("mesh-tree refit launch failed: ") + hipGetErrorString((hipError_t)e));
-    HIP_TRY(ce);
-    for (size_t k = 0; k < set.size(); k++) {
-        SrScene::MeshState& a = s->mesh_state[set[k]];
-        SrScene::HostBlas& b = a.tree;
-        const float* f = &out[k * 8];
-        memcpy(b.lo, f, 12); memcpy(b.hi, f + 3, 12);
-        b.max_abs_vertex = f[6]; b.max_edge_sum = f[7];
-        b.host_stale = true;
-        a.refit_pending = false; a.refit_now = true; a.last_op = SR_OP_UPDATE;
-        srh::as_state_mark_built(a.state, SR_OP_UPDATE);
-        s->mu_info.blas_refitted++;
-    }
-    return SR_OK;
+    if (p.refits.empty()) return SR_OK;
+    if (p.refits != s->refit.set && (rc = prepare_refit_set(s, p.refits)) != SR_OK) return rc;
+    return refit_mesh_trees(s);
 }
 
 // What the build of a sr_scene_set_instances in the two-level form did to every mesh's tree, into the per-mesh heuristic states.
@@ -1860,33 +1911,24 @@ void mark_mesh_trees(SrScene* s, uint32_t forced) {
     }
 }
 
-int two_level_build(SrScene* s, bool list_changed) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc;
-    bool any_textured = false;
-    if ((rc = upload_mesh_tables(s, &any_textured)) != SR_OK) return rc;
-    // a changed list of a scene that stands in this form: records, boxes and tree on the device where that path can take it
-    uint32_t host_reason = SR_TL_HOST_QUALITY_BUILD;
-    if (list_changed) {
-        host_reason = SR_TL_ON_DEVICE;
-        if ((rc = top_level_build_device(s, t0, &host_reason)) != SR_OK) return rc;
-        if (host_reason == SR_TL_ON_DEVICE) return SR_OK;
-    }
-    // instance records + padded world-space boxes
-    const size_t ni = s->fid.instances.size();
-    std::vector<srd::DevTlInstance> recs(ni ? ni : 1);
-    memset(recs.data(), 0, recs.size() * sizeof(srd::DevTlInstance));
-    std::vector<srh::BuildBox> boxes;
-    std::vector<uint32_t> box_inst;
-    boxes.reserve(ni); box_inst.reserve(ni);
+struct HostTlRecords {                        // what the host record loop computes of an instance list
+    std::vector<srd::DevTlInstance> recs;     // one per instance
+    std::vector<srh::BuildBox> boxes;         // padded world-space boxes of the instances that have one
     std::vector<SrScene::HostBlas> baked;     // private world-space copies: instances whose transform cannot be inverted (well)
-    std::vector<uint32_t> baked_inst;
-    uint32_t blas_stack = 0;
+    std::vector<uint32_t> box_inst, baked_inst;   // the instance of every box / baked copy
+    uint32_t blas_stack = 0;                  // stack need of the deepest mesh tree or baked copy in use
+};
+int host_tl_records(SrScene* s, HostTlRecords& h) {
+    int rc;
+    const size_t ni = s->fid.instances.size();
+    h.recs.resize(ni ? ni : 1);
+    memset(h.recs.data(), 0, h.recs.size() * sizeof(srd::DevTlInstance));
+    h.boxes.reserve(ni); h.box_inst.reserve(ni);
     for (size_t i = 0; i < ni; i++) {
         const srh::HostInstance& in = s->fid.instances[i];
         const SrScene::HostBlas& b = s->mesh_state[in.mesh_slot].tree;
-        if (!b.valid) { if ((rc = rebuild_mesh_tree(s, in.mesh_slot)) != SR_OK) return rc; s->blas_device_current = false; }
-        srd::DevTlInstance& r = recs[i];
+        if (!b.valid) { if ((rc = rebuild_mesh_tree(s, in.mesh_slot)) != SR_OK) return rc; s->trees.blas_device_current = false; }
+        srd::DevTlInstance& r = h.recs[i];
         const float* M = in.o2w.m;
         memcpy(r.o2w, M, 48);
         r.tri_offset = in.tri_offset;
@@ -1895,67 +1937,77 @@ int two_level_build(SrScene* s, bool list_changed) {
         srh::BuildBox bx;
         // the record's arithmetic is tl_record.h's, shared with the device build. An instance whose transform cannot be inverted
         // (well) gets a private world-space copy of its mesh's tree and is walked without a ray transform
-        if (srd::tl_record(M, b.lo, b.hi, b.max_abs_vertex, b.max_edge_sum, kTlMaxCondition, r.w2o, bx.lo, bx.hi, &r.pad_a, &r.pad_b) == srd::kTlRecordBaked) {
+        if (srd::tl_record(M, b.root.lo, b.root.hi, b.root.max_abs_vertex, b.root.max_edge_sum, kTlMaxCondition, r.w2o, bx.lo, bx.hi, &r.pad_a, &r.pad_b) == srd::kTlRecordBaked) {
             memset(r.w2o, 0, sizeof(r.w2o));
             r.w2o[0] = r.w2o[5] = r.w2o[10] = 1.0f;
             r.flags = 1u;
-            baked.emplace_back();
-            if ((rc = build_blas(s, in.mesh_slot, &in.o2w, baked.back())) != SR_OK) return rc;
-            baked_inst.push_back((uint32_t)i);
-            const SrScene::HostBlas& wb = baked.back();
+            h.baked.emplace_back();
+            if ((rc = build_blas(s, in.mesh_slot, &in.o2w, h.baked.back())) != SR_OK) return rc;
+            h.baked_inst.push_back((uint32_t)i);
+            const SrScene::HostBlas& wb = h.baked.back();
             bool box_ok = true;
-            for (int a = 0; a < 3; a++) { bx.lo[a] = wb.lo[a]; bx.hi[a] = wb.hi[a]; box_ok = box_ok && std::isfinite(bx.lo[a]) && std::isfinite(bx.hi[a]); }
-            blas_stack = std::max(blas_stack, wb.max_stack);
-            if (box_ok) { boxes.push_back(bx); box_inst.push_back((uint32_t)i); }
+            for (int a = 0; a < 3; a++) { bx.lo[a] = wb.root.lo[a]; bx.hi[a] = wb.root.hi[a]; box_ok = box_ok && std::isfinite(bx.lo[a]) && std::isfinite(bx.hi[a]); }
+            h.blas_stack = std::max(h.blas_stack, wb.max_stack);
+            if (box_ok) { h.boxes.push_back(bx); h.box_inst.push_back((uint32_t)i); }
             continue;
         }
-        blas_stack = std::max(blas_stack, b.max_stack);
+        h.blas_stack = std::max(h.blas_stack, b.max_stack);
         // a box that is not finite goes to the builder like any other (the device path leaves such a list to this loop)
-        boxes.push_back(bx);
-        box_inst.push_back((uint32_t)i);
+        h.boxes.push_back(bx);
+        h.box_inst.push_back((uint32_t)i);
     }
-    const bool had_baked = s->tl_baked;
-    if (!s->blas_device_current || !s->two_level || had_baked || !baked.empty()) {
-        if ((rc = upload_mesh_trees(s, baked)) != SR_OK) return rc;
-    }
-    for (size_t i = 0; i < ni; i++) {
-        srd::DevTlInstance& r = recs[i];
+    return SR_OK;
+}
+// Where each record's tree starts in the concatenated arrays, once these stand as the build leaves them.
+void patch_tl_records(const SrScene* s, HostTlRecords& h) {
+    for (size_t i = 0; i < s->fid.instances.size(); i++) {
+        srd::DevTlInstance& r = h.recs[i];
         if (r.flags & 1u) continue;
         r.blas_root = s->mesh_state[r.mesh_slot].node_base;
         r.prim_base = s->mesh_state[r.mesh_slot].tri_base;
     }
-    for (size_t k = 0; k < baked.size(); k++) { recs[baked_inst[k]].blas_root = s->tl_baked_node_base[k]; recs[baked_inst[k]].prim_base = s->tl_baked_tri_base[k]; }
-    s->blas_stack = blas_stack;
-    // the stack budget of the top-level tree is what the deepest mesh tree leaves of the walk's LDS stack
-    const uint32_t left = kTlStackCap > s->blas_stack + srl::kLeafMax + 1u ? kTlStackCap - s->blas_stack - srl::kLeafMax - 1u : 0u;
-    if (left < min_depth_for(boxes.size())) return fail(SR_ERR_UNSUPPORTED, "two-level structure: instance count and mesh size together need a deeper traversal stack than the kernels provide");
-    const auto t1 = std::chrono::steady_clock::now();
+    for (size_t k = 0; k < h.baked.size(); k++) { h.recs[h.baked_inst[k]].blas_root = s->trees.tl_baked_node_base[k]; h.recs[h.baked_inst[k]].prim_base = s->trees.tl_baked_tri_base[k]; }
+}
+
+// The two-level structure of the instance list at hand: on the device where top_level_build_device takes a changed list; else the host's
+// records, the concatenated mesh trees anew where they are not current or hold (or get) baked copies, and the host's top-level tree.
+int two_level_build(SrScene* s, bool list_changed) {
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc;
+    bool any_textured = false;
+    if ((rc = upload_mesh_tables(s, &any_textured)) != SR_OK) return rc;
+    SrTopLevelInfo info{};
+    info.reason = SR_TL_HOST_QUALITY_BUILD;
+    if (list_changed) {
+        info.reason = SR_TL_ON_DEVICE;
+        if ((rc = top_level_build_device(s, t0, &info.reason)) != SR_OK) return rc;
+        if (info.reason == SR_TL_ON_DEVICE) return SR_OK;
+    }
+    HostTlRecords h;
+    if ((rc = host_tl_records(s, h)) != SR_OK) return rc;
+    if (!s->trees.blas_device_current || !s->two_level || s->trees.tl_baked || !h.baked.empty()) {
+        if ((rc = upload_mesh_trees(s, h.baked)) != SR_OK) return rc;
+    }
+    patch_tl_records(s, h);
+    const uint32_t left = tl_stack_left(h.blas_stack);
+    if (left < min_depth_for(h.boxes.size())) return fail(SR_ERR_UNSUPPORTED, "two-level structure: instance count and mesh size together need a deeper traversal stack than the kernels provide");
+    info.records_ms = ms_between(t0, std::chrono::steady_clock::now());
     srh::BvhResult tl;
-    srh::build_bvh_boxes(boxes, std::min(depth_for(boxes.size()), left), tl);
+    srh::build_bvh_boxes(h.boxes, std::min(depth_for(h.boxes.size()), left), tl);
     std::vector<uint32_t> tl_inst(tl.order.size() ? tl.order.size() : 1, 0u);
-    for (size_t k = 0; k < tl.order.size(); k++) tl_inst[k] = box_inst[tl.order[k]];
-    const uint32_t need = tl.max_stack + srl::kLeafMax + s->blas_stack + 1u;     // top-level entries + pending instances of a leaf + mesh tree + 1
-    if (need > kTlStackCap) return fail(SR_ERR_STATE, "two-level structure needs a deeper traversal stack than the kernels provide");
+    for (size_t k = 0; k < tl.order.size(); k++) tl_inst[k] = h.box_inst[tl.order[k]];
+    if (tl_stack_need(tl.max_stack, h.blas_stack) > kTlStackCap) return fail(SR_ERR_STATE, "two-level structure needs a deeper traversal stack than the kernels provide");
     HIP_TRY(hipDeviceSynchronize());
     if ((rc = upload_instance_tables(s)) != SR_OK) return rc;
     if ((rc = s->d_nodes.upload(tl.nodes.data(), tl.nodes.size() * 4)) != SR_OK) return rc;
     if ((rc = s->d_tl_inst.upload(tl_inst.data(), tl_inst.size() * 4)) != SR_OK) return rc;
-    if ((rc = s->d_tl_instances.upload(recs.data(), recs.size() * sizeof(srd::DevTlInstance))) != SR_OK) return rc;
-    BuiltStructure built;
-    built.n_nodes = tl.n_nodes + s->tl_blas_nodes; built.tri_bytes = s->tl_blas_tris * 48;
-    built.max_depth = tl.max_depth; built.stack_need = need; built.sah_cost = tl.sah_cost;
-    built.build_ms = ms_between(t0, std::chrono::steady_clock::now());
-    built.two_level = true;
-    publish(s, built);
-    s->shape.clear();
-    s->tl_boxes_host.assign((ni ? ni : 1) * 6, std::numeric_limits<float>::quiet_NaN());
-    for (size_t k = 0; k < boxes.size(); k++) { memcpy(&s->tl_boxes_host[(size_t)box_inst[k] * 6], boxes[k].lo, 12); memcpy(&s->tl_boxes_host[(size_t)box_inst[k] * 6 + 3], boxes[k].hi, 12); }
-    SrTopLevelInfo& info = s->tl_info;
-    info.on_device = 0u; info.reason = host_reason;
-    info.n_nodes = tl.n_nodes; info.n_boxes = (uint32_t)boxes.size(); info.n_instances = (uint32_t)ni; info.max_stack = tl.max_stack; info.blas_stack = s->blas_stack;
-    info.records_ms = ms_between(t0, t1);
+    if ((rc = s->d_tl_instances.upload(h.recs.data(), h.recs.size() * sizeof(srd::DevTlInstance))) != SR_OK) return rc;
+    const size_t ni = s->fid.instances.size();
+    info.n_nodes = tl.n_nodes; info.n_boxes = (uint32_t)h.boxes.size(); info.n_instances = (uint32_t)ni; info.max_stack = tl.max_stack; info.blas_stack = h.blas_stack;
     info.tree_ms = tl.build_ms;
-    info.build_ms = s->stats.build_ms;
+    publish_two_level(s, info, tl.max_depth, tl.sah_cost, t0);
+    s->tl_boxes_host.assign((ni ? ni : 1) * 6, std::numeric_limits<float>::quiet_NaN());
+    for (size_t k = 0; k < h.boxes.size(); k++) { memcpy(&s->tl_boxes_host[(size_t)h.box_inst[k] * 6], h.boxes[k].lo, 12); memcpy(&s->tl_boxes_host[(size_t)h.box_inst[k] * 6 + 3], h.boxes[k].hi, 12); }
     return SR_OK;
 }
 
@@ -2054,7 +2106,13 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     s->mu_info.dirty_meshes = (uint32_t)std::count_if(s->mesh_state.begin(), s->mesh_state.end(), [](const SrScene::MeshState& ms) { return ms.dirty; });
     s->mu_info.reshaded = 0; s->mu_info.blas_rebuilt = 0; s->mu_info.blas_refitted = 0;
     s->mu_info.tables_ms = s->mu_info.flatten_ms = s->mu_info.refit_ms = s->mu_info.blas_build_ms = 0.0;
-    auto applied = [s] { for (auto& ms : s->mesh_state) ms.dirty = false; s->geometry_stale = false; s->static_mesh_updated = false; };
+    auto built_with = [s](uint32_t op) {      // how either form ends: the scene's heuristic state takes the op, the updates count as applied
+        if (s->built_once) srh::as_state_mark_built(s->as_state, op);
+        s->built_once = true; s->last_op = op;
+        for (auto& ms : s->mesh_state) ms.dirty = false;
+        s->geometry_stale = false; s->static_mesh_updated = false;
+        return SR_OK;
+    };
     // the light table's source: the device arena (SR_LIGHTS_DEVICE; upload_instance_tables builds the table with the kernel, and
     // the copy below is skipped: sr_scene_get_tables reads the device arena back when asked) or this frame's copy of the host
     // arena. The one dummy record of an empty arena, and of a scene without instances, is host arithmetic in either mode.
@@ -2077,14 +2135,9 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
         if (rc != SR_OK) { s->built = false; return rc; }
         mark_mesh_trees(s, forced);
         s->mt_info.built_on_host = s->mu_info.blas_rebuilt - s->mt_info.built_on_device;
-        if (s->built_once) srh::as_state_mark_built(s->as_state, op);
-        s->built_once = true;
-        s->last_op = op;
-        applied();
-        return SR_OK;
+        return built_with(op);
     }
-    for (size_t m = 0; m < s->mesh_state.size(); m++)      // the one-level form has no mesh trees to refit
-        if (s->mesh_state[m].refit_pending || s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
+    invalidate_mesh_trees(s, true);           // the one-level form has no mesh trees to refit
     if (s->two_level) {                       // back to the one-level form: everything is rebuilt
         s->two_level = false; s->built = false;
         s->forced_op = s->forced_op == SR_OP_NONE ? SR_OP_SLOW_BUILD : s->forced_op;
@@ -2103,11 +2156,7 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     if (s->forced_op != SR_OP_NONE) { op = (s->forced_op == SR_OP_UPDATE && !can_update) ? SR_OP_FAST_BUILD : s->forced_op; s->forced_op = SR_OP_NONE; }
     rc = op == SR_OP_UPDATE ? update_in_place(s, reshade) : op == SR_OP_FAST_BUILD ? fast_build(s) : full_build(s);
     if (rc != SR_OK) { s->built = false; return rc; }
-    if (s->built_once) srh::as_state_mark_built(s->as_state, op);
-    s->built_once = true;
-    s->last_op = op;
-    applied();
-    return SR_OK;
+    return built_with(op);
 }
 
 int sr_scene_end_frame(SrScene* s) {
@@ -2133,8 +2182,7 @@ int sr_scene_end_frame(SrScene* s) {
         int rc = bind_device(s);
         if (rc != SR_OK) return rc;
         if (s->lights_on_device && (rc = fetch_emissive_table(s)) != SR_OK) return rc;   // the rebuild may move the device arena on (a pending mesh)
-        if (s->two_level && !s->blas_device_current)      // the re-concatenation takes the stale host copies of refitted meshes along
-            for (size_t m = 0; m < s->mesh_state.size(); m++) if (s->mesh_state[m].tree.host_stale) invalidate_mesh_tree(s, (uint32_t)m);
+        if (s->two_level && !s->trees.blas_device_current) invalidate_mesh_trees(s, false);      // the re-concatenation takes the stale host copies of refitted meshes along
         if ((rc = s->two_level ? two_level_build(s, false) : full_build(s)) != SR_OK) { s->built = false; return rc; }
     }
     for (size_t m = 0; m < mesh_ops.size(); m++) {
@@ -2331,7 +2379,7 @@ int sr_scene_read_mesh_tree(const SrScene* s, uint64_t key, uint32_t* n_nodes, u
     if (const int rc = find_mesh(s, key, "sr_scene_read_mesh_tree", &slot); rc != SR_OK) return rc;
     if (!s->built || !s->two_level) return fail(SR_ERR_STATE, "sr_scene_read_mesh_tree: the scene is not built in the two-level form");
     const SrScene::MeshState& ms = s->mesh_state[slot];
-    if (!s->blas_device_current || !ms.tree.valid)
+    if (!s->trees.blas_device_current || !ms.tree.valid)
         return fail(SR_ERR_STATE, "sr_scene_read_mesh_tree: the mesh's tree is not on the device (sr_scene_set_instances builds it)");
     if (s->geometry_stale || ms.refit_pending) return fail(SR_ERR_STATE, std::string("sr_scene_read_mesh_tree: ") + kStaleGeometry);
     const uint32_t nb = ms.node_base, tb = ms.tri_base, nn = ms.tree.n_nodes, nt = ms.tree.n_tris;
@@ -2340,7 +2388,7 @@ int sr_scene_read_mesh_tree(const SrScene* s, uint64_t key, uint32_t* n_nodes, u
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipDeviceSynchronize());
     if (nodes && nn) {
-        HIP_TRY(hipMemcpy(nodes, (const char*)s->d_blas_nodes.p + (size_t)nb * srl::kNodeBytes, (size_t)nn * srl::kNodeBytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(nodes, (const char*)s->trees.d_blas_nodes.p + (size_t)nb * srl::kNodeBytes, (size_t)nn * srl::kNodeBytes, hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < nn; i++)         // references local to the mesh (the inverse of the concatenation)
             for (int c = 0; c < srl::kBvhWidth; c++) {
                 uint32_t& q = nodes[(size_t)i * srl::kNodeDwords + srl::kChildOffset + c];
@@ -2352,7 +2400,7 @@ int sr_scene_read_mesh_tree(const SrScene* s, uint64_t key, uint32_t* n_nodes, u
     if (tris && nt) HIP_TRY(hipMemcpy(tris, (const char*)s->d_tris.p + (size_t)tb * 48, (size_t)nt * 48, hipMemcpyDeviceToHost));
     if (shade && nt) HIP_TRY(hipMemcpy(shade, (const char*)s->d_shade.p + (size_t)tb * 48, (size_t)nt * 48, hipMemcpyDeviceToHost));
     if (shade_tex && nt) {
-        if (s->any_textured_tl) HIP_TRY(hipMemcpy(shade_tex, (const char*)s->d_shade_tex.p + (size_t)tb * 96, (size_t)nt * 96, hipMemcpyDeviceToHost));
+        if (s->trees.any_textured_tl) HIP_TRY(hipMemcpy(shade_tex, (const char*)s->d_shade_tex.p + (size_t)tb * 96, (size_t)nt * 96, hipMemcpyDeviceToHost));
         else memset(shade_tex, 0, (size_t)nt * 96);       // the scene has no textured records
     }
     if (slot_of_prim && nt) {
