@@ -18,6 +18,7 @@
 
 #include "host.h"
 #include "blas_batch.h"
+#include "bvh_device.h"
 #include "bvh_gpu.h"
 #include "bvh_layout.h"
 #include "kernels.h"
@@ -1556,14 +1557,10 @@ int top_level_build_device(SrScene* s, std::chrono::steady_clock::time_point t0,
     if (left < min_depth_for(nb)) { *reason = SR_TL_HOST_STACK_BUDGET; return SR_OK; }      // the host build reports the error
     const uint32_t node_cap = nb + 64;        // inner nodes of a tree with >= 2 children per node and >= 1 box per leaf: < nb
     if ((rc = s->d_nodes.reserve((size_t)node_cap * srl::kNodeBytes)) != SR_OK || (rc = s->d_node_box.reserve((size_t)node_cap * 24)) != SR_OK ||
-        (rc = s->d_tl_inst.reserve((size_t)nb * 4)) != SR_OK || (rc = s->d_scratch.reserve(srk_tl_scratch_bytes(ni, node_cap))) != SR_OK) return rc;
-    LbvhArgs a{};
-    a.n_instances = ni; a.boxes = (const float*)s->d_tl_boxes.p; a.n_boxes = nb; a.tl_inst = (uint32_t*)s->d_tl_inst.p;
-    a.nodes = (float4*)s->d_nodes.p; a.node_cap = node_cap; a.node_box = (float*)s->d_node_box.p;
-    a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
-    a.stack_floor = min_depth_for(nb); a.stack_cap = left;
-    a.ploc = s->fast_build_ploc;
-    a.rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
+        (rc = s->d_tl_inst.reserve((size_t)nb * 4)) != SR_OK || (rc = s->d_scratch.reserve(srk_tl_scratch_bytes(ni, nb, node_cap, s->fast_build_ploc))) != SR_OK) return rc;
+    const TreeBuildTarget target((float4*)s->d_nodes.p, node_cap, (float*)s->d_node_box.p, s->d_scratch.p, s->d_scratch.bytes, min_depth_for(nb), left,
+                                 s->height_bound == SR_HEIGHT_BOUND_REBALANCE, s->fast_build_ploc);
+    const BoxesBuildArgs a(target, (const float*)s->d_tl_boxes.p, ni, nb, (uint32_t*)s->d_tl_inst.p);
     LbvhResult r;
     e = srk_tl_build(a, &r, nullptr);
     if (e > 0) return fail(SR_ERR_HIP, std::string("device top-level build failed: ") + hipGetErrorString((hipError_t)e));
@@ -1692,19 +1689,10 @@ int build_mesh_tree_device(SrScene* s, uint32_t m, const srd::BlasBatchArrays& a
     SrScene::HostBlas& b = ms.tree;
     const uint32_t n = b.n_tris;
     s->trees.take_range(ms);
-    if (const int rc = s->d_scratch.reserve(srk_lbvh_scratch_bytes(n, ms.node_cap)); rc != SR_OK) return rc;
-    LbvhArgs a{};
-    a.n_tris = n;
-    a.vertices = (const SrVertex*)s->meshes[m].d_vertices; a.indices = (const uint32_t*)s->meshes[m].d_indices; a.n_vertices = s->meshes[m].n_vertices;
-    a.mesh_slot = m; a.textured = b.shade_tex.empty() ? 0u : 1u;
-    a.nodes = (float4*)arrays.nodes; a.node_box = arrays.node_box; a.tris = arrays.tris; a.shade = arrays.shade; a.shade_tex = arrays.shade_tex;
-    a.slot_of_gid = arrays.slot_of_gid; a.rows = arrays.rows;
-    a.node_base = ms.node_base; a.node_cap = ms.node_cap; a.tri_base = ms.tri_base;
-    a.out = (uint32_t*)s->d_blas_build_out.p;
-    a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
-    a.stack_floor = std::min(depth_for(n), cap); a.stack_cap = cap;
-    a.ploc = s->fast_build_ploc;
-    a.rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
+    if (const int rc = s->d_scratch.reserve(srk_lbvh_scratch_bytes(n, ms.node_cap, s->fast_build_ploc)); rc != SR_OK) return rc;
+    const MeshBuildArgs a(arrays, ms.node_base, ms.node_cap, ms.tri_base, s->d_scratch.p, s->d_scratch.bytes, std::min(depth_for(n), cap), cap,
+                          s->height_bound == SR_HEIGHT_BOUND_REBALANCE, s->fast_build_ploc, (const SrVertex*)s->meshes[m].d_vertices,
+                          (const uint32_t*)s->meshes[m].d_indices, s->meshes[m].n_vertices, n, m, b.shade_tex.empty() ? 0u : 1u, (uint32_t*)s->d_blas_build_out.p);
     LbvhResult r;
     const int e = srk_blas_build(a, &r, nullptr);
     if (e > 0) return fail(SR_ERR_HIP, std::string("device mesh-tree build failed: ") + hipGetErrorString((hipError_t)e));
@@ -1820,10 +1808,7 @@ int prepare_refit_set(SrScene* s, const std::vector<uint32_t>& set) {
     s->refit.level_offsets.assign(1, 0u);
     for (size_t d = by_depth.size(); d-- > 0;) { list.insert(list.end(), by_depth[d].begin(), by_depth[d].end()); s->refit.level_offsets.push_back((uint32_t)list.size()); }
     std::vector<uint32_t> init(set.size() * 8);
-    for (size_t k = 0; k < set.size(); k++) {       // order-preserving encoding (bvh_gpu.hip enc_f) of +inf x 3, -inf x 3, 0, 0
-        uint32_t* q = &init[k * 8];
-        q[0] = q[1] = q[2] = 0xFF800000u; q[3] = q[4] = q[5] = 0x007FFFFFu; q[6] = q[7] = 0x80000000u;
-    }
+    for (size_t k = 0; k < init.size(); k++) init[k] = srd::mesh_acc_seed((int)(k & 7));
     int rc;
     if ((rc = s->refit.d_meshes.upload(rows.data(), rows.size() * sizeof(srd::BlasRefitMesh))) != SR_OK ||
         (rc = s->refit.d_nodes.upload(list.data(), list.size() * 4)) != SR_OK ||
@@ -2042,18 +2027,11 @@ int fast_build(SrScene* s) {
         (rc = s->d_slot_of_gid.reserve((size_t)n * 4)) != SR_OK) return rc;
     if (any_textured) { if ((rc = s->d_shade_tex.reserve((size_t)n * 96)) != SR_OK) return rc; }
     else s->d_shade_tex.release();
-    const size_t scratch = srk_lbvh_scratch_bytes(n, node_cap);
-    if ((rc = s->d_scratch.reserve(scratch)) != SR_OK) return rc;
-    LbvhArgs a;
-    a.meshes = (const SrMeshInfo*)s->d_mesh_infos.p; a.instances = (const srd::FlatInstance*)s->d_flat_instances.p;
-    a.n_instances = (uint32_t)s->fid.instances.size(); a.n_tris = n;
-    a.nodes = (float4*)s->d_nodes.p; a.node_cap = node_cap;
-    a.tris = (float4*)s->d_tris.p; a.shade = (float4*)s->d_shade.p; a.shade_tex = (float4*)s->d_shade_tex.p;
-    a.slot_of_gid = (uint32_t*)s->d_slot_of_gid.p; a.node_box = (float*)s->d_node_box.p;
-    a.scratch = s->d_scratch.p; a.scratch_bytes = s->d_scratch.bytes;
-    a.stack_floor = (uint32_t)srd::kStackMax; a.stack_cap = kDeviceStackCap;
-    a.ploc = s->fast_build_ploc;
-    a.rebalance = s->height_bound == SR_HEIGHT_BOUND_REBALANCE;
+    if ((rc = s->d_scratch.reserve(srk_lbvh_scratch_bytes(n, node_cap, s->fast_build_ploc))) != SR_OK) return rc;
+    const TreeBuildTarget target((float4*)s->d_nodes.p, node_cap, (float*)s->d_node_box.p, s->d_scratch.p, s->d_scratch.bytes, (uint32_t)srd::kStackMax,
+                                 kDeviceStackCap, s->height_bound == SR_HEIGHT_BOUND_REBALANCE, s->fast_build_ploc);
+    const TrisBuildArgs a(target, (const SrMeshInfo*)s->d_mesh_infos.p, (const srd::FlatInstance*)s->d_flat_instances.p, (uint32_t)s->fid.instances.size(), n,
+                          (float4*)s->d_tris.p, (float4*)s->d_shade.p, (float4*)s->d_shade_tex.p, (uint32_t*)s->d_slot_of_gid.p);
     LbvhResult r;
     const int e = srk_lbvh_build(a, &r, nullptr);
     if (e > 0) return fail(SR_ERR_HIP, std::string("device BVH build failed: ") + hipGetErrorString((hipError_t)e));

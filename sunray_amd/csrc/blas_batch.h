@@ -38,18 +38,11 @@ struct BlasBatchResult {    // 320 B: what the host reads back per mesh
     uint32_t levels[2 * kBlasBatchMaxLevels];     // (first node, count) per level, root level first, local to the mesh's node range
 };
 static_assert(sizeof(BlasBatchRow) == 64 && sizeof(BlasBatchResult) == 320, "rows the host packs and reads back");
-
-struct BlasBatchArrays {    // the resident concatenated arrays of all meshes (LbvhArgs' of srk_blas_build)
-    uint32_t* nodes; float* node_box;
-    float4 *tris, *shade, *shade_tex;             // shade_tex may be null
-    uint32_t* slot_of_gid;
-    TlMeshRow* rows;                              // may be null
-};
 }  // namespace srd
 
 // Bytes of one mesh's scratch slab (a multiple of 256).
 size_t srk_blas_batch_slab_bytes(uint32_t n_tris, uint32_t node_cap);
-// Builds rows[0 .. n_rows) (device memory), one workgroup each, and fills results[0 .. n_rows) (device memory). `ploc` as LbvhArgs.
+// Builds rows[0 .. n_rows) (device memory), one workgroup each, and fills results[0 .. n_rows) (device memory). `ploc` as TreeBuildTarget's.
 // The call only enqueues; every result row is written by its workgroup (the caller presets `status` to something else than built).
 int srk_blas_batch_build(const srd::BlasBatchRow* rows, uint32_t n_rows, const srd::BlasBatchArrays& arrays, srd::BlasBatchResult* results, int ploc,
                          hipStream_t stream);

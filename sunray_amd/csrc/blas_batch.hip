@@ -1,4 +1,4 @@
-// Batched device fast build of small mesh trees of the two-level form (sr_scene_set_mesh_tree_batch): what build_tree<kBuildMesh>
+// Batched device fast build of small mesh trees of the two-level form (sr_scene_set_mesh_tree_batch): what build_tree over MeshBuildArgs
 // (bvh_gpu.hip) does with a launch per stage and a stream wait per PLOC iteration and collapse level, done for every mesh of the
 // batch by ONE workgroup inside ONE launch. A mesh of at most SR_BLAS_BATCH_MAX_TRIS triangles fits one workgroup: a launch boundary
 // or host read-back of the per-mesh path is a __syncthreads() here, the counters the host read back live in LDS. The arithmetic of
@@ -28,7 +28,8 @@ namespace srd {
 
 constexpr uint32_t kBatchMaxRounds = kBlasBatchMaxTris;      // every PLOC round merges at least one pair: fewer rounds than clusters
 
-// The arrays of one mesh's slab, in the order build_tree carves its scratch.
+// The arrays of one mesh's slab. The layout is this kernel's own: defined together with the per-stage builder's (bvh_gpu.hip TreeScratch)
+// it changed this kernel's register allocation (SGPR spills 32 -> 23 and 13 -> 11), so the two stay apart.
 struct BatchSlab {
     float4 *W, *cent;
     unsigned long long* keys; uint32_t* vals;           // sorted
@@ -91,8 +92,7 @@ __global__ void __launch_bounds__(kBlasBatchBlock) blas_batch_build_kernel(const
     const uint32_t n = row.n_tris, node_cap = row.node_cap;
     if (tid == 0) {
         s.bounds[0] = s.bounds[1] = s.bounds[2] = 0xFFFFFFFFu; s.bounds[3] = s.bounds[4] = s.bounds[5] = 0u;
-        // the encoded +inf x 3, -inf x 3, 0, 0 the mesh's root box and padding numbers start from (build_tree's init block)
-        s.acc[0] = s.acc[1] = s.acc[2] = 0xFF800000u; s.acc[3] = s.acc[4] = s.acc[5] = 0x007FFFFFu; s.acc[6] = s.acc[7] = 0x80000000u;
+        for (int k = 0; k < 8; k++) s.acc[k] = mesh_acc_seed(k);
         s.counters[0] = 1u; s.counters[1] = 0u; s.counters[2] = 0u;
         s.ploc_nodes = 0u; s.m = n; s.cur = 0u; s.status = kBlasBatchBuilt; s.height = 0u; s.root_bin = 0;
         s.level_first = 0u; s.level_count = 0u; s.n_levels = 0u;

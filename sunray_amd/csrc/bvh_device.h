@@ -168,6 +168,8 @@ __device__ __forceinline__ void refit_node(uint32_t* nodes, const Prims prims, f
 // Order-preserving encoding of a float as an unsigned word: atomicMin / atomicMax on the encoding are fminf / fmaxf.
 __device__ __forceinline__ uint32_t enc_f(float f) { const uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
 __device__ __forceinline__ float dec_f(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7FFFFFFFu) : ~e); }
+// Word k of the eight a mesh's root box and padding numbers start from: the encoded +inf x 3, -inf x 3, 0, 0.
+__host__ __device__ constexpr uint32_t mesh_acc_seed(int k) { return k < 3 ? 0xFF800000u : k < 6 ? 0x007FFFFFu : 0x80000000u; }
 
 // ---- primitives of one mesh (srk_blas_build, the batched build) ------------------------------------------------------------
 // What a thread accumulates over its primitives: the box the tree bounds them by (the Morton grid), build_blas's root box and the

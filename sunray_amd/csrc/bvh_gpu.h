@@ -36,26 +36,60 @@ int srk_launch_flatten_reshade(float4* tris, float4* shade, float4* shade_tex, c
 int srk_launch_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host,
                      uint32_t n_levels, hipStream_t stream);
 
-struct LbvhArgs {
-    const SrMeshInfo* meshes; const srd::FlatInstance* instances; uint32_t n_instances, n_tris;
+// The resident concatenated arrays of all mesh trees of the two-level form: where a mesh-tree writer (srk_blas_build, the batched
+// build, the refit's record kernel) writes.
+namespace srd {
+struct BlasBatchArrays {
+    uint32_t* nodes; float* node_box;
+    float4 *tris, *shade, *shade_tex;             // shade_tex may be null
+    uint32_t* slot_of_gid;
+    TlMeshRow* rows;                              // may be null
+};
+}  // namespace srd
+
+// Arguments of the three device tree builders. A struct is built by its constructor alone, which takes every field: a value a
+// call site leaves out is a compile error.
+struct TreeBuildTarget {          // what the three builders share
     float4* nodes; uint32_t node_cap;                    // node_cap x 64 B
-    float4 *tris, *shade, *shade_tex;                    // leaf-order records (shade_tex may be null)
-    uint32_t* slot_of_gid; float* node_box;              // n_tris / node_cap x 6 floats
-    void* scratch; size_t scratch_bytes;
+    float* node_box;                                     // node_cap x 6 floats
+    void* scratch; size_t scratch_bytes;                 // srk_*_scratch_bytes of the same sizes and topology
     uint32_t stack_floor, stack_cap;                     // budget = max(stack_floor, binary height); fail above stack_cap
-    int rebalance = 0;                                   // 1: a binary tree taller than stack_cap is rebalanced to fit it instead of refused
+    int rebalance;                                       // 1: a binary tree taller than stack_cap is rebalanced to fit it instead of refused
     int ploc;                                            // topology: 0 = binary radix tree (LBVH), r > 0 = PLOC with search radius r
-    // srk_tl_build only (the primitives are instance boxes; meshes .. slot_of_gid above are unused, n_tris is unused)
-    const float* boxes = nullptr; uint32_t n_boxes = 0;  // n_instances x 6 floats, n_boxes of them real (the others are NaN rows)
-    uint32_t* tl_inst = nullptr;                         // out: leaf order -> instance index, n_boxes entries
-    // srk_blas_build only (the primitives are ONE mesh's object-space triangles; meshes, instances and n_instances above are unused).
-    // nodes, node_box, tris, shade, shade_tex and slot_of_gid are the concatenated arrays of all meshes: the tree takes the nodes
-    // [node_base, node_base + node_cap) and the leaf-order slots [tri_base, tri_base + n_tris)
-    const SrVertex* vertices = nullptr; const uint32_t* indices = nullptr; uint32_t n_vertices = 0;
-    uint32_t mesh_slot = 0, textured = 0;                // shade_tex is written only for a textured mesh
-    uint32_t node_base = 0, tri_base = 0;
-    srd::TlMeshRow* rows = nullptr;                      // out (may be null): the mesh's row of the top-level record table
-    uint32_t* out = nullptr;                             // out, 10 dwords: root box lo, hi, max_abs_vertex, max_edge_sum (floats), nodes, stack need
+    TreeBuildTarget(float4* nodes, uint32_t node_cap, float* node_box, void* scratch, size_t scratch_bytes, uint32_t stack_floor, uint32_t stack_cap,
+                    int rebalance, int ploc)
+        : nodes(nodes), node_cap(node_cap), node_box(node_box), scratch(scratch), scratch_bytes(scratch_bytes), stack_floor(stack_floor),
+          stack_cap(stack_cap), rebalance(rebalance), ploc(ploc) {}
+};
+struct TrisBuildArgs : TreeBuildTarget {      // srk_lbvh_build: the primitives are the instances' world-space triangles
+    const SrMeshInfo* meshes; const srd::FlatInstance* instances; uint32_t n_instances, n_tris;
+    float4 *tris, *shade, *shade_tex;                    // out: leaf-order records, n_tris each (shade_tex null: the scene has none)
+    uint32_t* slot_of_gid;                               // out: n_tris
+    TrisBuildArgs(const TreeBuildTarget& target, const SrMeshInfo* meshes, const srd::FlatInstance* instances, uint32_t n_instances, uint32_t n_tris,
+                  float4* tris, float4* shade, float4* shade_tex, uint32_t* slot_of_gid)
+        : TreeBuildTarget(target), meshes(meshes), instances(instances), n_instances(n_instances), n_tris(n_tris), tris(tris), shade(shade),
+          shade_tex(shade_tex), slot_of_gid(slot_of_gid) {}
+};
+struct BoxesBuildArgs : TreeBuildTarget {     // srk_tl_build: the primitives are the instance boxes of a top-level tree
+    const float* boxes; uint32_t n_instances, n_boxes;   // n_instances x 6 floats, n_boxes of them real (the others are NaN rows)
+    uint32_t* tl_inst;                                   // out: leaf order -> instance index, n_boxes entries
+    BoxesBuildArgs(const TreeBuildTarget& target, const float* boxes, uint32_t n_instances, uint32_t n_boxes, uint32_t* tl_inst)
+        : TreeBuildTarget(target), boxes(boxes), n_instances(n_instances), n_boxes(n_boxes), tl_inst(tl_inst) {}
+};
+// srk_blas_build: the primitives are ONE mesh's object-space triangles. The tree takes the nodes [node_base, node_base + node_cap)
+// and the leaf-order slots [tri_base, tri_base + n_tris) of `arrays`, whose nodes and node_box are the target's.
+struct MeshBuildArgs : TreeBuildTarget {
+    srd::BlasBatchArrays arrays;
+    const SrVertex* vertices; const uint32_t* indices; uint32_t n_vertices, n_tris;
+    uint32_t mesh_slot, textured;                        // shade_tex is written only for a textured mesh
+    uint32_t node_base, tri_base;
+    uint32_t* out;                                       // out, 10 dwords: root box lo, hi, max_abs_vertex, max_edge_sum (floats), nodes, stack need
+    MeshBuildArgs(const srd::BlasBatchArrays& arrays, uint32_t node_base, uint32_t node_cap, uint32_t tri_base, void* scratch, size_t scratch_bytes,
+                  uint32_t stack_floor, uint32_t stack_cap, int rebalance, int ploc, const SrVertex* vertices, const uint32_t* indices, uint32_t n_vertices,
+                  uint32_t n_tris, uint32_t mesh_slot, uint32_t textured, uint32_t* out)
+        : TreeBuildTarget((float4*)arrays.nodes, node_cap, arrays.node_box, scratch, scratch_bytes, stack_floor, stack_cap, rebalance, ploc), arrays(arrays),
+          vertices(vertices), indices(indices), n_vertices(n_vertices), n_tris(n_tris), mesh_slot(mesh_slot), textured(textured), node_base(node_base),
+          tri_base(tri_base), out(out) {}
 };
 struct LbvhResult {
     uint32_t n_nodes = 0, max_stack = 0, max_depth = 0;
@@ -64,16 +98,18 @@ struct LbvhResult {
     // the height bound rebuilt (0, 0 when the tree fitted)
     uint32_t height_before = 0, height_after = 0, subtrees_rebuilt = 0, prims_rebuilt = 0;
 };
-int srk_lbvh_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
-size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap);
+// Return 0, a hipError_t (> 0), or -1 when the tree does not fit the limits (the caller falls back to the host builder). The scratch
+// sizes are exact: the end of the one carve the build itself uses (bvh_gpu.hip TreeScratch), for the same sizes and topology.
+int srk_lbvh_build(const TrisBuildArgs& args, LbvhResult* out, hipStream_t stream);
+size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap, int ploc);
 
 // Top level of the two-level form. srk_tl_records: DevTlInstance records and padded world boxes of all instances (tl_record.h, as
 // the host loop of two_level_build computes them); `result` (device, 3 dwords, zeroed by the call) receives: instances this path cannot take,
 // deepest mesh-tree stack, instances with a box. srk_tl_build: the builder above over those boxes; same return convention.
 int srk_tl_records(const srd::FlatInstance* instances, const srd::TlMeshRow* meshes, uint32_t n_instances, double max_condition,
                    srd::DevTlInstance* records, float* boxes, uint32_t* result, hipStream_t stream);
-int srk_tl_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
-size_t srk_tl_scratch_bytes(uint32_t n_instances, uint32_t node_cap);
+int srk_tl_build(const BoxesBuildArgs& args, LbvhResult* out, hipStream_t stream);
+size_t srk_tl_scratch_bytes(uint32_t n_instances, uint32_t n_boxes, uint32_t node_cap, int ploc);
 
 // Mesh trees of the two-level form after sr_scene_update_mesh. srk_blas_records: the leaf-order records of the dirty meshes
 // rewritten from their vertex / index buffers (the bytes of api.cpp build_blas) and, per mesh, root box lo, hi, max_abs_vertex,
@@ -84,8 +120,8 @@ int srk_blas_records(const srd::BlasRefitMesh* meshes, uint32_t n_meshes, uint32
                      uint32_t* acc, const uint32_t* acc_init, srd::TlMeshRow* rows, float* out, hipStream_t stream);
 // srk_blas_build: the device fast build of one mesh's tree into its ranges of those arrays (SrAsState asked for SR_OP_FAST_BUILD):
 // records, shade, shade_tex and primitive -> slot entries with the bytes of build_blas, references global as the concatenation
-// makes them, the eight floats as above. Return convention and scratch size of srk_lbvh_build (n_tris, node_cap).
-int srk_blas_build(const LbvhArgs& args, LbvhResult* out, hipStream_t stream);
+// makes them, the eight floats as above. Return convention and scratch size of srk_lbvh_build (n_tris, node_cap, ploc).
+int srk_blas_build(const MeshBuildArgs& args, LbvhResult* out, hipStream_t stream);
 int srk_blas_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host,
                    uint32_t n_levels, hipStream_t stream);
 

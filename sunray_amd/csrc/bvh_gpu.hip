@@ -9,7 +9,9 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include <hipcub/hipcub.hpp>
 
@@ -156,7 +158,7 @@ __global__ void lbvh_fit_kernel(const Prims prims, const uint32_t* sorted_gid, i
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Height bound (LbvhArgs::rebalance): a binary tree whose walk height h(root) exceeds the stack cap is rewritten so that it
+// Height bound (TreeBuildTarget::rebalance): a binary tree whose walk height h(root) exceeds the stack cap is rewritten so that it
 // fits, between the topology stage and the collapse. H(k) is the walk height of a median-split tree over k primitives. The
 // root's allowance is A = stack_cap, a child's its parent's minus one. At a node v: h(v) <= A(v): the subtree is kept whole;
 // otherwise, if both children c have H(size(c)) <= A(v) - 1, v's split is kept and the rule goes on in the children; otherwise
@@ -604,14 +606,30 @@ int srk_launch_flatten_reshade(float4* tris, float4* shade, float4* shade_tex, c
     return (int)hipGetLastError();
 }
 
+// One launch per tree level, deepest level first. level(l) -> (first, count) of level l in that order: a range of the list
+// `level_nodes`, or of the node indices themselves where the list is null.
+template <class Prims, class Level>
+static void refit_levels(uint32_t* nodes, const Prims prims, float* node_box, const uint32_t* level_nodes, uint32_t n_levels, Level level, hipStream_t stream) {
+    for (uint32_t l = 0; l < n_levels; l++) {
+        const std::pair<uint32_t, uint32_t> r = level(l);
+        if (r.second == 0) continue;
+        refit_level_kernel<<<dim3((r.second + 63) / 64), dim3(64), 0, stream>>>(nodes, prims, node_box, level_nodes, r.first, r.second);
+    }
+}
+template <class Prims>      // level_offsets_host[l] .. [l+1]: deepest level first (srk_blas_refit: all dirty meshes together)
+static int refit_listed_levels(uint32_t* nodes, const Prims prims, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host,
+                               uint32_t n_levels, hipStream_t stream) {
+    refit_levels(nodes, prims, node_box, level_nodes, n_levels,
+                 [&](uint32_t l) { return std::make_pair(level_offsets_host[l], level_offsets_host[l + 1] - level_offsets_host[l]); }, stream);
+    return (int)hipGetLastError();
+}
 int srk_launch_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host,
                      uint32_t n_levels, hipStream_t stream) {
-    for (uint32_t l = 0; l < n_levels; l++) {     // level_offsets_host[l] .. [l+1]: deepest level first
-        const uint32_t first = level_offsets_host[l], count = level_offsets_host[l + 1] - first;
-        if (count == 0) continue;
-        refit_level_kernel<<<dim3((count + 63) / 64), dim3(64), 0, stream>>>(nodes, TriPrims{tris}, node_box, level_nodes, first, count);
-    }
-    return (int)hipGetLastError();
+    return refit_listed_levels(nodes, TriPrims{tris}, node_box, level_nodes, level_offsets_host, n_levels, stream);
+}
+int srk_blas_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host, uint32_t n_levels,
+                   hipStream_t stream) {
+    return refit_listed_levels(nodes, VertPrims{tris}, node_box, level_nodes, level_offsets_host, n_levels, stream);
 }
 
 int srk_blas_records(const BlasRefitMesh* meshes, uint32_t n_meshes, uint32_t n_threads, float4* tris, float4* shade, float4* shade_tex, uint32_t* acc,
@@ -624,178 +642,235 @@ int srk_blas_records(const BlasRefitMesh* meshes, uint32_t n_meshes, uint32_t n_
     return (int)hipGetLastError();
 }
 
-int srk_blas_refit(uint32_t* nodes, const float4* tris, float* node_box, const uint32_t* level_nodes, const uint32_t* level_offsets_host, uint32_t n_levels,
-                   hipStream_t stream) {
-    for (uint32_t l = 0; l < n_levels; l++) {     // level_offsets_host[l] .. [l+1]: deepest level first, all dirty meshes together
-        const uint32_t first = level_offsets_host[l], count = level_offsets_host[l + 1] - first;
-        if (count == 0) continue;
-        refit_level_kernel<<<dim3((count + 63) / 64), dim3(64), 0, stream>>>(nodes, VertPrims{tris}, node_box, level_nodes, first, count);
-    }
-    return (int)hipGetLastError();
+// ---------------------------------------------------------------------------------------------------------------
+// The device tree build. All outputs are device buffers owned by the caller; `scratch` is reused across builds. Three kinds of
+// primitive go through the same stages (build_tree):
+//   TrisBuildArgs   the instances' world-space triangles (srk_lbvh_build)
+//   BoxesBuildArgs  the instance boxes of a top-level tree (srk_tl_build): all n_instances rows are keyed and sorted, the n_boxes
+//                   real ones come first and are the tree's primitives
+//   MeshBuildArgs   the object-space triangles of one mesh of the two-level form (srk_blas_build); nodes and records go to the
+//                   mesh's ranges of the concatenated arrays (node_base, tri_base), with global references
+// ---------------------------------------------------------------------------------------------------------------
+enum { kBuildTris = 0, kBuildBoxes = 1, kBuildMesh = 2 };
+template <class Args>
+constexpr int kind_of = std::is_same<Args, BoxesBuildArgs>::value ? kBuildBoxes : std::is_same<Args, MeshBuildArgs>::value ? kBuildMesh : kBuildTris;
+
+// The words of the scratch that kernels reduce and count in. Every wave of blas_prims_kernel reduces into `bounds` and into `acc`:
+// the two sit in cache lines of their own (in one line the atomics of a 1M-triangle mesh cost its build 0.7 ms of 17).
+struct TreeSmall {
+    uint32_t bounds[6];                   // Morton grid: lo, hi, encoded
+    alignas(32) uint32_t counters[3];     // the collapse's: nodes allocated (the root is), max stack, overflow flag
+    alignas(16) uint32_t ploc_nodes;      // binary nodes PLOC allocated
+    alignas(64) uint32_t acc[8];          // srk_blas_build: the mesh's root box lo, hi, max_abs_vertex, max_edge_sum, encoded
+    alignas(64) uint32_t stat[5];         // the height bound's (rebalance_rebuild_kernel); set when the pass runs, not by the seed
+};
+static TreeSmall small_seed() {
+    TreeSmall s{};
+    for (int k = 0; k < 3; k++) s.bounds[k] = 0xFFFFFFFFu;
+    s.counters[0] = 1u;
+    for (int k = 0; k < 8; k++) s.acc[k] = mesh_acc_seed(k);
+    return s;
+}
+static const TreeSmall kSmallSeed = small_seed();
+
+// Every array of the builder's scratch. carve_tree_scratch is the one definition of the layout: build_tree carves the caller's
+// buffer with it, the srk_*_scratch_bytes functions return its end for a null base.
+struct TreeScratch {
+    uint32_t n_keys, n;                                  // sorted items; primitives of the tree
+    float4 *W, *cent;                                    // records and centroids of the triangles (null for boxes)
+    unsigned long long *keys_a, *keys_b; uint32_t *vals_a, *vals_b;      // the sort's input and output
+    int2* children; uint2* range;                        // range: radix tree only; PLOC: nn | valid
+    uint32_t *parent_inner, *parent_leaf;                // radix tree and height bound; parent_inner under PLOC: scan output
+    float* bin_box; uint32_t *bin_height, *bin_size, *flags, *slot_of_sorted;
+    int* bin_of_node; uint32_t *budget_of_node, *prefix_of_node, *first_of_node;      // the collapse's queues, by 4-wide node
+    TreeSmall* small;
+    int* cid[2]; float* cbox[2];                         // PLOC clusters, double-buffered (null without PLOC)
+    uint4* link; uint2* leaf_link; uint32_t *leaf_at_pos, *inner_at_gap;    // the height bound's own arrays
+    uint2* rb_range; uint32_t* rb_gap;                   // ... its per-node range and gap live in the sort's input, which is dead by then
+    char* tmp; size_t sort_bytes, scan_bytes;            // hipCUB's temporary storage, shared by the sort and PLOC's scan
+};
+static size_t carve_tree_scratch(void* base, int kind, uint32_t n_keys, uint32_t n, uint32_t node_cap, bool ploc, size_t sort_bytes, size_t scan_bytes,
+                                 TreeScratch* s) {
+    size_t off = 0;      // consecutive 256-byte aligned arrays; with a null base only the offsets count
+    auto take = [&](auto** p, size_t count) { *p = (std::remove_reference_t<decltype(**p)>*)((uintptr_t)base + off); off += (count * sizeof(**p) + 255) & ~(size_t)255; };
+    s->n_keys = n_keys; s->n = n;
+    s->W = s->cent = nullptr;
+    if (kind != kBuildBoxes) { take(&s->W, (size_t)n * 3); take(&s->cent, n); }
+    take(&s->keys_a, n_keys); take(&s->keys_b, n_keys); take(&s->vals_a, n_keys); take(&s->vals_b, n_keys);
+    take(&s->children, n); take(&s->range, n); take(&s->parent_inner, n); take(&s->parent_leaf, n);
+    take(&s->bin_box, (size_t)n * 6); take(&s->bin_height, n); take(&s->bin_size, n); take(&s->flags, n); take(&s->slot_of_sorted, n);
+    take(&s->bin_of_node, node_cap); take(&s->budget_of_node, node_cap); take(&s->prefix_of_node, node_cap); take(&s->first_of_node, node_cap);
+    take(&s->small, 1);
+    for (int k = 0; k < 2; k++) { s->cid[k] = nullptr; s->cbox[k] = nullptr; if (ploc) { take(&s->cid[k], n); take(&s->cbox[k], (size_t)n * 6); } }
+    take(&s->link, n); take(&s->leaf_link, n); take(&s->leaf_at_pos, n); take(&s->inner_at_gap, n);
+    s->rb_range = (uint2*)s->keys_a; s->rb_gap = s->vals_a;
+    s->sort_bytes = sort_bytes; s->scan_bytes = scan_bytes;
+    take(&s->tmp, sort_bytes > scan_bytes ? sort_bytes : scan_bytes);
+    return off;
+}
+// The key of an instance without a box has every bit set; a Morton code has 63.
+static hipError_t tree_temp_bytes(int kind, uint32_t n_keys, uint32_t n, bool ploc, size_t* sort_bytes, size_t* scan_bytes, hipStream_t stream) {
+    *sort_bytes = *scan_bytes = 0;
+    const hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, *sort_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                                            (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n_keys, 0, kind == kBuildBoxes ? 64 : 63, stream);
+    if (e != hipSuccess || !ploc) return e;
+    return hipcub::DeviceScan::ExclusiveSum(nullptr, *scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, stream);
+}
+static size_t tree_scratch_bytes(int kind, uint32_t n_keys, uint32_t n, uint32_t node_cap, int ploc) {
+    size_t sort_bytes, scan_bytes;
+    (void)tree_temp_bytes(kind, n_keys, n, ploc != 0, &sort_bytes, &scan_bytes, nullptr);     // a failure shows in the build, which asks again
+    TreeScratch s;
+    return carve_tree_scratch(nullptr, kind, n_keys, n, node_cap, ploc != 0, sort_bytes, scan_bytes, &s);
+}
+size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap, int ploc) { return tree_scratch_bytes(kBuildTris, n_tris, n_tris, node_cap, ploc); }
+size_t srk_tl_scratch_bytes(uint32_t n_instances, uint32_t n_boxes, uint32_t node_cap, int ploc) {
+    return tree_scratch_bytes(kBuildBoxes, n_instances, n_boxes, node_cap, ploc);
 }
 
-// Device LBVH build. All outputs are device buffers owned by the caller; `scratch` is reused across builds. Returns 0, a
-// hipError_t (> 0), or -1 when the tree does not fit the limits (caller falls back to the host builder).
-// KIND kBuildBoxes: the primitives are the instance boxes of a top-level tree (srk_tl_build) instead of the instances' triangles:
-// all n_instances rows are keyed and sorted, the n_boxes real ones come first and are the tree's primitives.
-// KIND kBuildMesh: the primitives are the object-space triangles of one mesh of the two-level form (srk_blas_build); nodes and
-// records go to the mesh's ranges of the concatenated arrays (node_base, tri_base), with global references.
-enum { kBuildTris = 0, kBuildBoxes = 1, kBuildMesh = 2 };
-template <int KIND>
-static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
-    constexpr bool BOXES = KIND == kBuildBoxes, MESH = KIND == kBuildMesh;
-    const uint32_t n_keys = BOXES ? a.n_instances : a.n_tris;   // sorted items
-    const uint32_t n = BOXES ? a.n_boxes : a.n_tris;             // primitives of the tree
-    if (BOXES && (n < 2 || n > n_keys)) return -1;
-    if (MESH && (n < 1 || a.node_cap < 1)) return -1;
-    uint32_t* const tree_nodes = (uint32_t*)a.nodes + (MESH ? (size_t)a.node_base * srl::kNodeDwords : 0);   // the collapse's node 0
-    const int B = 256;
-    const dim3 gk((n_keys + B - 1) / B), gt((n + B - 1) / B), bt(B);
-    const int sort_bits = BOXES ? 64 : 63;                       // the key of an instance without a box has every bit set
-    // carve the scratch slab
-    size_t off = 0;
-    auto take = [&](size_t bytes) { void* p = (char*)a.scratch + off; off += (bytes + 255) & ~(size_t)255; return p; };
-    float4* W = BOXES ? nullptr : (float4*)take((size_t)n * 48);
-    float4* cent = BOXES ? nullptr : (float4*)take((size_t)n * 16);
-    unsigned long long* keys_a = (unsigned long long*)take((size_t)n_keys * 8);
-    unsigned long long* keys_b = (unsigned long long*)take((size_t)n_keys * 8);
-    uint32_t* vals_a = (uint32_t*)take((size_t)n_keys * 4);
-    uint32_t* vals_b = (uint32_t*)take((size_t)n_keys * 4);
-    int2* children = (int2*)take((size_t)n * 8);
-    uint2* range = (uint2*)take((size_t)n * 8);             // radix tree only; PLOC: nn | valid
-    uint32_t* parent_inner = (uint32_t*)take((size_t)n * 4);   // radix tree only; PLOC: scan output
-    uint32_t* parent_leaf = (uint32_t*)take((size_t)n * 4);
-    float* bin_box = (float*)take((size_t)n * 24);
-    uint32_t* bin_height = (uint32_t*)take((size_t)n * 4);
-    uint32_t* bin_size = (uint32_t*)take((size_t)n * 4);
-    uint32_t* flags = (uint32_t*)take((size_t)n * 4);
-    uint32_t* slot_of_sorted = (uint32_t*)take((size_t)n * 4);
-    int* bin_of_node = (int*)take((size_t)a.node_cap * 4);
-    uint32_t* budget_of_node = (uint32_t*)take((size_t)a.node_cap * 4);
-    uint32_t* prefix_of_node = (uint32_t*)take((size_t)a.node_cap * 4);
-    uint32_t* first_of_node = (uint32_t*)take((size_t)a.node_cap * 4);
-    uint32_t* small = (uint32_t*)take(256);          // [0..5] bounds, [8..10] counters, [12] PLOC node counter, [16..23] mesh box, [32..36] height bound
-    // PLOC cluster arrays (double-buffered)
-    int* cid[2] = {nullptr, nullptr}; float* cbox[2] = {nullptr, nullptr};
-    if (a.ploc) for (int k = 0; k < 2; k++) { cid[k] = (int*)take((size_t)n * 4); cbox[k] = (float*)take((size_t)n * 24); }
-    // the height bound's own arrays; its per-node range and gap live in the sort's input buffers, which are dead by then
-    uint4* link = (uint4*)take((size_t)n * 16);
-    uint2* leaf_link = (uint2*)take((size_t)n * 8);
-    uint32_t* leaf_at_pos = (uint32_t*)take((size_t)n * 4);
-    uint32_t* inner_at_gap = (uint32_t*)take((size_t)n * 4);
-    uint2* rb_range = (uint2*)keys_a;
-    uint32_t* rb_gap = vals_a;
-    size_t cub_bytes = 0, scan_bytes = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, keys_a, keys_b, vals_a, vals_b, (int)n_keys, 0, sort_bits, stream);
-    if (e != hipSuccess) return (int)e;
-    if (a.ploc && (e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, stream)) != hipSuccess) return (int)e;
-    void* cub_tmp = take(cub_bytes > scan_bytes ? cub_bytes : scan_bytes);
-    if (off > a.scratch_bytes) return (int)hipErrorOutOfMemory;
+#define TREE_TRY(call) do { const int rc_ = (int)(call); if (rc_ != 0) return rc_; } while (0)
 
-    // [16..23] (srk_blas_build): the encoded +inf x 3, -inf x 3, 0, 0 the mesh's root box and padding numbers start from
-    const uint32_t init[24] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u, 1u, 0u, 0u, 0u, 0u, 0u, 0u, 0u,
-                               0xFF800000u, 0xFF800000u, 0xFF800000u, 0x007FFFFFu, 0x007FFFFFu, 0x007FFFFFu, 0x80000000u, 0x80000000u};
-    uint32_t* const acc = small + 16;
-    uint32_t* const counters = small + 8;
-    if ((e = hipMemcpyAsync(small, init, sizeof(init), hipMemcpyHostToDevice, stream)) != hipSuccess) return (int)e;
-    if constexpr (BOXES) {
-        tl_bounds_kernel<<<gk, bt, 0, stream>>>(a.boxes, n_keys, small);
-        tl_morton_kernel<<<gk, bt, 0, stream>>>(a.boxes, small, n_keys, keys_a, vals_a);
+// "Copy these words to the host and wait": every value the host steers the build by comes through here.
+struct HostCopy { void* dst; const void* src; size_t bytes; };
+static hipError_t read_back(hipStream_t stream, std::initializer_list<HostCopy> copies) {
+    for (const HostCopy& c : copies)
+        if (const hipError_t e = hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, stream); e != hipSuccess) return e;
+    return hipStreamSynchronize(stream);
+}
+
+static const dim3 kBuildBlock(256);
+static dim3 build_grid(uint32_t n) { return dim3((n + 255) / 256); }
+
+// What a stage bounds a primitive by: prims_of by sorted value (triangle id / instance index), leaf_prims_of by leaf position.
+static TriPrims prims_of(const TrisBuildArgs&, const TreeScratch& s) { return TriPrims{s.W}; }
+static BoxPrims prims_of(const BoxesBuildArgs& a, const TreeScratch&) { return BoxPrims{a.boxes, nullptr}; }
+static VertPrims prims_of(const MeshBuildArgs&, const TreeScratch& s) { return VertPrims{s.W}; }
+static TriPrims leaf_prims_of(const TrisBuildArgs& a) { return TriPrims{a.tris}; }
+static BoxPrims leaf_prims_of(const BoxesBuildArgs& a) { return BoxPrims{a.boxes, a.tl_inst}; }
+static VertPrims leaf_prims_of(const MeshBuildArgs& a) { return VertPrims{a.arrays.tris}; }
+static uint32_t node_base_of(const TreeBuildTarget&) { return 0u; }      // the collapse's node 0 in the caller's node array
+static uint32_t node_base_of(const MeshBuildArgs& a) { return a.node_base; }
+
+// ---- keys and sort: the seed of the small block, primitives (records, centroids) and the bounds of the Morton grid, keys, the sort
+template <class Args>
+static int stage_keys_and_sort(const Args& a, const TreeScratch& s, hipStream_t stream) {
+    constexpr int KIND = kind_of<Args>;
+    const dim3 gk = build_grid(s.n_keys), gt = build_grid(s.n);
+    TREE_TRY(hipMemcpyAsync(s.small, &kSmallSeed, offsetof(TreeSmall, stat), hipMemcpyHostToDevice, stream));
+    if constexpr (KIND == kBuildBoxes) {
+        tl_bounds_kernel<<<gk, kBuildBlock, 0, stream>>>(a.boxes, s.n_keys, s.small->bounds);
+        tl_morton_kernel<<<gk, kBuildBlock, 0, stream>>>(a.boxes, s.small->bounds, s.n_keys, s.keys_a, s.vals_a);
     } else {
-        if constexpr (MESH) blas_prims_kernel<<<gt, bt, 0, stream>>>(a.vertices, a.indices, a.n_vertices, n, W, cent, small, acc);
-        else lbvh_prims_kernel<<<gt, bt, 0, stream>>>(a.meshes, a.instances, a.n_instances, n, W, cent, small);
-        lbvh_morton_kernel<<<gt, bt, 0, stream>>>(cent, small, n, keys_a, vals_a);
+        if constexpr (KIND == kBuildMesh) blas_prims_kernel<<<gt, kBuildBlock, 0, stream>>>(a.vertices, a.indices, a.n_vertices, s.n, s.W, s.cent, s.small->bounds, s.small->acc);
+        else lbvh_prims_kernel<<<gt, kBuildBlock, 0, stream>>>(a.meshes, a.instances, a.n_instances, s.n, s.W, s.cent, s.small->bounds);
+        lbvh_morton_kernel<<<gt, kBuildBlock, 0, stream>>>(s.cent, s.small->bounds, s.n, s.keys_a, s.vals_a);
     }
-    if ((e = hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, keys_a, keys_b, vals_a, vals_b, (int)n_keys, 0, sort_bits, stream)) != hipSuccess) return (int)e;
-    // what a stage bounds a primitive by: `prims` by sorted value (triangle id / instance index), `leaf_prims` by leaf position
-    auto prims = [&] { if constexpr (BOXES) return BoxPrims{a.boxes, nullptr}; else if constexpr (MESH) return VertPrims{W}; else return TriPrims{W}; }();
-    auto leaf_prims = [&] { if constexpr (BOXES) return BoxPrims{a.boxes, a.tl_inst}; else if constexpr (MESH) return VertPrims{a.tris}; else return TriPrims{a.tris}; }();
-    int root_bin = 0;
-    const bool single = MESH && n == 1;       // one triangle: no binary tree; the root is one node with one leaf child
-    if (single) {
-        uint32_t node[srl::kNodeDwords];
-        for (int k = 0; k < srl::kNodeDwords; k++) node[k] = k >= srl::kChildOffset ? 0xFFFFFFFFu : 0u;
-        node[srl::kChildOffset] = ~((0u << 3) | 1u);
-        if ((e = hipMemcpyAsync(tree_nodes, node, sizeof(node), hipMemcpyHostToDevice, stream)) != hipSuccess) return (int)e;
-        if ((e = hipMemsetAsync(slot_of_sorted, 0, 4, stream)) != hipSuccess) return (int)e;
-        out->level_ranges.assign(1, std::make_pair(0u, 1u));
-        out->n_nodes = 1; out->max_stack = 0;
-    } else if (!a.ploc) {
-        if ((e = hipMemsetAsync(flags, 0, (size_t)n * 4, stream)) != hipSuccess) return (int)e;
-        lbvh_hierarchy_kernel<<<gt, bt, 0, stream>>>(keys_b, (int)n, children, parent_inner, parent_leaf, range);
-        lbvh_fit_kernel<<<gt, bt, 0, stream>>>(prims, vals_b, (int)n, children, parent_inner, parent_leaf, range, bin_box, bin_height, bin_size, flags);
-    } else {
-        uint32_t* nn = (uint32_t*)range;
-        uint32_t* valid = nn + n;
-        uint32_t* pos = parent_inner;
-        uint32_t* node_counter = small + 12;
-        ploc_init_kernel<<<gt, bt, 0, stream>>>(prims, vals_b, n, cid[0], cbox[0]);
-        uint32_t m = n;
-        int cur = 0, guard = 0;
-        while (m > 1) {
-            const dim3 gm((m + B - 1) / B);
-            ploc_nn_kernel<BOXES><<<gm, bt, 0, stream>>>(cbox[cur], m, (uint32_t)a.ploc, nn);
-            ploc_merge_kernel<<<gm, bt, 0, stream>>>(nn, m, cid[cur], cbox[cur], valid, children, bin_box, bin_size, bin_height, node_counter);
-            if ((e = hipcub::DeviceScan::ExclusiveSum(cub_tmp, scan_bytes, valid, pos, (int)m, stream)) != hipSuccess) return (int)e;
-            ploc_compact_kernel<<<gm, bt, 0, stream>>>(cid[cur], cbox[cur], valid, pos, m, cid[cur ^ 1], cbox[cur ^ 1]);
-            uint32_t tail[2];      // new count = pos[m-1] + valid[m-1]
-            if ((e = hipMemcpyAsync(&tail[0], pos + (m - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
-            if ((e = hipMemcpyAsync(&tail[1], valid + (m - 1), 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
-            if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
-            const uint32_t m_new = tail[0] + tail[1];
-            if (m_new >= m || ++guard > 4096) return -1;     // no progress: cannot happen (the closest pair is always mutual)
-            m = m_new;
-            cur ^= 1;
-        }
-        if ((e = hipMemcpyAsync(&root_bin, cid[cur], 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
-        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
-        if (root_bin < 0) return -1;
+    size_t sort_bytes = s.sort_bytes;
+    return (int)hipcub::DeviceRadixSort::SortPairs(s.tmp, sort_bytes, s.keys_a, s.keys_b, s.vals_a, s.vals_b, (int)s.n_keys, 0, KIND == kBuildBoxes ? 64 : 63, stream);
+}
+
+// ---- binary topology. One triangle (a mesh): no binary tree; the root is one node with one leaf child.
+static int topology_single_triangle(uint32_t* tree_nodes, const TreeScratch& s, LbvhResult* out, hipStream_t stream) {
+    uint32_t node[srl::kNodeDwords];
+    for (int k = 0; k < srl::kNodeDwords; k++) node[k] = k >= srl::kChildOffset ? 0xFFFFFFFFu : 0u;
+    node[srl::kChildOffset] = ~((0u << 3) | 1u);
+    TREE_TRY(hipMemcpyAsync(tree_nodes, node, sizeof(node), hipMemcpyHostToDevice, stream));
+    TREE_TRY(hipMemsetAsync(s.slot_of_sorted, 0, 4, stream));
+    out->level_ranges.assign(1, std::make_pair(0u, 1u));
+    out->n_nodes = 1; out->max_stack = 0;
+    return 0;
+}
+template <class Prims>      // the radix tree over the sorted keys; its root is binary node 0
+static int topology_radix_tree(const Prims prims, const TreeScratch& s, hipStream_t stream) {
+    const dim3 gt = build_grid(s.n);
+    TREE_TRY(hipMemsetAsync(s.flags, 0, (size_t)s.n * 4, stream));
+    lbvh_hierarchy_kernel<<<gt, kBuildBlock, 0, stream>>>(s.keys_b, (int)s.n, s.children, s.parent_inner, s.parent_leaf, s.range);
+    lbvh_fit_kernel<<<gt, kBuildBlock, 0, stream>>>(prims, s.vals_b, (int)s.n, s.children, s.parent_inner, s.parent_leaf, s.range, s.bin_box, s.bin_height, s.bin_size, s.flags);
+    return 0;
+}
+template <bool SPREAD_TIES, class Prims>      // PLOC: one stream wait per iteration (the number of clusters left), one for the root
+static int topology_ploc(const Prims prims, uint32_t radius, const TreeScratch& s, int* root_bin, hipStream_t stream) {
+    uint32_t* const nn = (uint32_t*)s.range;
+    uint32_t* const valid = nn + s.n;
+    uint32_t* const pos = s.parent_inner;
+    int* const* cid = s.cid;
+    float* const* cbox = s.cbox;
+    ploc_init_kernel<<<build_grid(s.n), kBuildBlock, 0, stream>>>(prims, s.vals_b, s.n, cid[0], cbox[0]);
+    uint32_t m = s.n;
+    int cur = 0, guard = 0;
+    while (m > 1) {
+        const dim3 gm = build_grid(m);
+        ploc_nn_kernel<SPREAD_TIES><<<gm, kBuildBlock, 0, stream>>>(cbox[cur], m, radius, nn);
+        ploc_merge_kernel<<<gm, kBuildBlock, 0, stream>>>(nn, m, cid[cur], cbox[cur], valid, s.children, s.bin_box, s.bin_size, s.bin_height, &s.small->ploc_nodes);
+        size_t scan_bytes = s.scan_bytes;
+        TREE_TRY(hipcub::DeviceScan::ExclusiveSum(s.tmp, scan_bytes, valid, pos, (int)m, stream));
+        ploc_compact_kernel<<<gm, kBuildBlock, 0, stream>>>(cid[cur], cbox[cur], valid, pos, m, cid[cur ^ 1], cbox[cur ^ 1]);
+        uint32_t tail[2];      // new count = pos[m-1] + valid[m-1]
+        TREE_TRY(read_back(stream, {{&tail[0], pos + (m - 1), 4}, {&tail[1], valid + (m - 1), 4}}));
+        const uint32_t m_new = tail[0] + tail[1];
+        if (m_new >= m || ++guard > 4096) return -1;     // no progress: cannot happen (the closest pair is always mutual)
+        m = m_new;
+        cur ^= 1;
     }
-    uint32_t level_first = 0, level_count = 0;
-    if (!single) {
-        // root of the 4-wide tree = the binary root; its budget is the binary height, at least the regular stack size
-        uint32_t root_height = 0;
-        if ((e = hipMemcpyAsync(&root_height, bin_height + root_bin, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
-        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
-        out->height_before = out->height_after = root_height;
-        if (root_height > a.stack_cap) {
-            if (!a.rebalance || median_height(n) > a.stack_cap) return -1;      // refused; no tree over n primitives fits
-            uint32_t* const stat = small + 32;
-            uint32_t st[5] = {(uint32_t)root_bin, 0u, 0u, 0u, 0u};
-            const dim3 gw((2 * n - 1 + B - 1) / B);
-            if ((e = hipMemcpyAsync(stat, st, sizeof(st), hipMemcpyHostToDevice, stream)) != hipSuccess) return (int)e;
-            rebalance_links_kernel<<<gt, bt, 0, stream>>>(children, bin_size, bin_height, n, (uint32_t)root_bin, link, leaf_link);
-            rebalance_walk_kernel<<<gw, bt, 0, stream>>>(link, leaf_link, bin_size, n, (int)a.stack_cap, leaf_at_pos, inner_at_gap, rb_range, rb_gap, stat + 4);
-            rebalance_rebuild_kernel<<<gt, bt, 0, stream>>>(link, rb_range, rb_gap, leaf_at_pos, inner_at_gap, n, children, stat);
-            rebalance_parents_kernel<<<gt, bt, 0, stream>>>(children, n, stat, parent_inner, parent_leaf);
-            if ((e = hipMemsetAsync(flags, 0, (size_t)n * 4, stream)) != hipSuccess) return (int)e;
-            lbvh_fit_kernel<<<gt, bt, 0, stream>>>(prims, vals_b, (int)n, children, parent_inner, parent_leaf, (const uint2*)nullptr, bin_box, bin_height, bin_size, flags);
-            rebalance_finish_kernel<<<dim3(1), dim3(64), 0, stream>>>(bin_height, n, stat);
-            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-            if ((e = hipMemcpyAsync(st, stat, sizeof(st), hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
-            if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
-            if (st[4] || st[0] + 1u >= n || st[3] > a.stack_cap) return -1;     // cannot happen for a tree the topology stage finished
-            root_bin = (int)st[0]; root_height = st[3];
-            out->height_after = st[3]; out->subtrees_rebuilt = st[1]; out->prims_rebuilt = st[2];
-        }
-        const uint32_t floor = a.rebalance ? (a.stack_floor < a.stack_cap ? a.stack_floor : a.stack_cap) : a.stack_floor;
-        const uint32_t budget = root_height > floor ? root_height : floor;
-        const uint32_t zero = 0;
-        (void)hipMemcpyAsync(bin_of_node, &root_bin, 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(budget_of_node, &budget, 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(prefix_of_node, &zero, 4, hipMemcpyHostToDevice, stream);
-        (void)hipMemcpyAsync(first_of_node, &zero, 4, hipMemcpyHostToDevice, stream);
-        out->level_ranges.clear();
-        level_count = 1;
-    }
+    TREE_TRY(read_back(stream, {{root_bin, cid[cur], 4}}));
+    return *root_bin < 0 ? -1 : 0;
+}
+template <class Args>
+static int stage_topology(const Args& a, const TreeScratch& s, bool single, LbvhResult* out, int* root_bin, hipStream_t stream) {
+    *root_bin = 0;
+    if (single) return topology_single_triangle((uint32_t*)a.nodes + (size_t)node_base_of(a) * srl::kNodeDwords, s, out, stream);
+    if (!a.ploc) return topology_radix_tree(prims_of(a, s), s, stream);
+    return topology_ploc<kind_of<Args> == kBuildBoxes>(prims_of(a, s), (uint32_t)a.ploc, s, root_bin, stream);
+}
+
+// ---- height bound: the binary root's walk height (one stream wait); above the cap the tree is refused or, under `rebalance`,
+// rewritten to fit (the pass described above rebalance_links_kernel; one more stream wait)
+template <class Args>
+static int stage_height_bound(const Args& a, const TreeScratch& s, int* root_bin, uint32_t* root_height, LbvhResult* out, hipStream_t stream) {
+    const uint32_t n = s.n;
+    TREE_TRY(read_back(stream, {{root_height, s.bin_height + *root_bin, 4}}));
+    out->height_before = out->height_after = *root_height;
+    if (*root_height <= a.stack_cap) return 0;
+    if (!a.rebalance || median_height(n) > a.stack_cap) return -1;      // refused; no tree over n primitives fits
+    const auto prims = prims_of(a, s);
+    uint32_t* const stat = s.small->stat;
+    uint32_t st[5] = {(uint32_t)*root_bin, 0u, 0u, 0u, 0u};
+    const dim3 gt = build_grid(n), gw = build_grid(2 * n - 1);
+    TREE_TRY(hipMemcpyAsync(stat, st, sizeof(st), hipMemcpyHostToDevice, stream));
+    rebalance_links_kernel<<<gt, kBuildBlock, 0, stream>>>(s.children, s.bin_size, s.bin_height, n, (uint32_t)*root_bin, s.link, s.leaf_link);
+    rebalance_walk_kernel<<<gw, kBuildBlock, 0, stream>>>(s.link, s.leaf_link, s.bin_size, n, (int)a.stack_cap, s.leaf_at_pos, s.inner_at_gap, s.rb_range, s.rb_gap, stat + 4);
+    rebalance_rebuild_kernel<<<gt, kBuildBlock, 0, stream>>>(s.link, s.rb_range, s.rb_gap, s.leaf_at_pos, s.inner_at_gap, n, s.children, stat);
+    rebalance_parents_kernel<<<gt, kBuildBlock, 0, stream>>>(s.children, n, stat, s.parent_inner, s.parent_leaf);
+    TREE_TRY(hipMemsetAsync(s.flags, 0, (size_t)n * 4, stream));
+    lbvh_fit_kernel<<<gt, kBuildBlock, 0, stream>>>(prims, s.vals_b, (int)n, s.children, s.parent_inner, s.parent_leaf, (const uint2*)nullptr, s.bin_box, s.bin_height, s.bin_size, s.flags);
+    rebalance_finish_kernel<<<dim3(1), dim3(64), 0, stream>>>(s.bin_height, n, stat);
+    TREE_TRY(hipGetLastError());
+    TREE_TRY(read_back(stream, {{st, stat, sizeof(st)}}));
+    if (st[4] || st[0] + 1u >= n || st[3] > a.stack_cap) return -1;     // cannot happen for a tree the topology stage finished
+    *root_bin = (int)st[0]; *root_height = st[3];
+    out->height_after = st[3]; out->subtrees_rebuilt = st[1]; out->prims_rebuilt = st[2];
+    return 0;
+}
+
+// ---- collapse levels: the root of the 4-wide tree is the binary root, its budget the binary height, at least the regular stack
+// size; then one launch and one stream wait per level (the nodes the level allocated are the next one)
+static int stage_collapse(const TreeBuildTarget& a, const TreeScratch& s, uint32_t* tree_nodes, int root_bin, uint32_t root_height, LbvhResult* out,
+                          hipStream_t stream) {
+    const uint32_t floor = a.rebalance ? (a.stack_floor < a.stack_cap ? a.stack_floor : a.stack_cap) : a.stack_floor;
+    const uint32_t budget = root_height > floor ? root_height : floor;
+    const uint32_t zero = 0;
+    TREE_TRY(hipMemcpyAsync(s.bin_of_node, &root_bin, 4, hipMemcpyHostToDevice, stream));
+    TREE_TRY(hipMemcpyAsync(s.budget_of_node, &budget, 4, hipMemcpyHostToDevice, stream));
+    TREE_TRY(hipMemcpyAsync(s.prefix_of_node, &zero, 4, hipMemcpyHostToDevice, stream));
+    TREE_TRY(hipMemcpyAsync(s.first_of_node, &zero, 4, hipMemcpyHostToDevice, stream));
+    out->level_ranges.clear();
+    uint32_t level_first = 0, level_count = 1;
     while (level_count) {
         out->level_ranges.emplace_back(level_first, level_count);
-        lbvh_collapse_kernel<<<dim3((level_count + 63) / 64), dim3(64), 0, stream>>>(tree_nodes, level_first, level_count, a.node_cap, bin_of_node,
-                                                                                       budget_of_node, prefix_of_node, first_of_node, children, bin_size, bin_box,
-                                                                                       bin_height, slot_of_sorted, counters);
+        lbvh_collapse_kernel<<<dim3((level_count + 63) / 64), dim3(64), 0, stream>>>(tree_nodes, level_first, level_count, a.node_cap, s.bin_of_node,
+                                                                                       s.budget_of_node, s.prefix_of_node, s.first_of_node, s.children, s.bin_size,
+                                                                                       s.bin_box, s.bin_height, s.slot_of_sorted, s.small->counters);
         uint32_t c[3];
-        if ((e = hipMemcpyAsync(c, counters, 12, hipMemcpyDeviceToHost, stream)) != hipSuccess) return (int)e;
-        if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
+        TREE_TRY(read_back(stream, {{c, s.small->counters, sizeof(c)}}));
         if (c[2] || c[0] > a.node_cap) return -1;
         level_first += level_count;
         level_count = c[0] - level_first;
@@ -803,26 +878,70 @@ static int build_tree(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) {
         out->max_stack = c[1];
         if (out->level_ranges.size() > 128) return -1;
     }
-    out->max_depth = (uint32_t)out->level_ranges.size();
-    const uint32_t node_base = MESH ? a.node_base : 0u;       // the levels' nodes in the array the refit walks
-    if constexpr (BOXES) tl_leaves_kernel<<<gt, bt, 0, stream>>>(vals_b, slot_of_sorted, n, a.tl_inst);
-    else if constexpr (MESH) {
-        blas_leaves_kernel<<<gt, bt, 0, stream>>>(W, vals_b, slot_of_sorted, n, a.vertices, a.indices, a.n_vertices, a.mesh_slot, a.tri_base, a.tris, a.shade,
-                                                  a.textured ? a.shade_tex : nullptr, a.slot_of_gid);
-        blas_place_kernel<<<dim3((out->n_nodes + 255) / 256), bt, 0, stream>>>((uint32_t*)a.nodes, out->n_nodes, a.node_base, a.tri_base);
-    } else lbvh_leaves_kernel<<<gt, bt, 0, stream>>>(W, cent, vals_b, slot_of_sorted, n, a.meshes, a.instances, a.tris, a.shade, a.shade_tex, a.slot_of_gid);
-    for (size_t l = out->level_ranges.size(); l-- > 0;)
-        refit_level_kernel<<<dim3((out->level_ranges[l].second + 63) / 64), dim3(64), 0, stream>>>((uint32_t*)a.nodes, leaf_prims, a.node_box, nullptr,
-                                                                                                     node_base + out->level_ranges[l].first, out->level_ranges[l].second);
-    if constexpr (MESH) blas_build_finish_kernel<<<dim3(1), dim3(64), 0, stream>>>(acc, counters, a.mesh_slot, a.node_base, a.tri_base, n, a.rows, a.out);
-    if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return (int)e;
     return 0;
 }
 
-int srk_lbvh_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<kBuildTris>(a, out, stream); }
-int srk_tl_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<kBuildBoxes>(a, out, stream); }
-int srk_blas_build(const LbvhArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree<kBuildMesh>(a, out, stream); }
+// ---- leaves and placing: the leaf-order outputs of the kind; a mesh's node references become global
+template <class Args>
+static void stage_leaves(const Args& a, const TreeScratch& s, const LbvhResult& out, hipStream_t stream) {
+    constexpr int KIND = kind_of<Args>;
+    const dim3 gt = build_grid(s.n);
+    if constexpr (KIND == kBuildBoxes) tl_leaves_kernel<<<gt, kBuildBlock, 0, stream>>>(s.vals_b, s.slot_of_sorted, s.n, a.tl_inst);
+    else if constexpr (KIND == kBuildMesh) {
+        const BlasBatchArrays& A = a.arrays;
+        blas_leaves_kernel<<<gt, kBuildBlock, 0, stream>>>(s.W, s.vals_b, s.slot_of_sorted, s.n, a.vertices, a.indices, a.n_vertices, a.mesh_slot, a.tri_base, A.tris,
+                                                            A.shade, a.textured ? A.shade_tex : nullptr, A.slot_of_gid);
+        blas_place_kernel<<<build_grid(out.n_nodes), kBuildBlock, 0, stream>>>(A.nodes, out.n_nodes, a.node_base, a.tri_base);
+    } else lbvh_leaves_kernel<<<gt, kBuildBlock, 0, stream>>>(s.W, s.cent, s.vals_b, s.slot_of_sorted, s.n, a.meshes, a.instances, a.tris, a.shade, a.shade_tex, a.slot_of_gid);
+}
+
+// ---- finish: a mesh's row and read-back block; the launches' errors; the build's last stream wait
+template <class Args>
+static int stage_finish(const Args& a, const TreeScratch& s, hipStream_t stream) {
+    if constexpr (kind_of<Args> == kBuildMesh)
+        blas_build_finish_kernel<<<dim3(1), dim3(64), 0, stream>>>(s.small->acc, s.small->counters, a.mesh_slot, a.node_base, a.tri_base, s.n, a.arrays.rows, a.out);
+    TREE_TRY(hipGetLastError());
+    return (int)hipStreamSynchronize(stream);
+}
+
+// Launches and stream waits of one build, with I PLOC iterations (radix tree: none) and L collapse levels. Host-to-device copies:
+// the small block's seed, the four words of the collapse's root. Launches: 2 (primitives, keys), the sort's, the topology's (radix
+// tree: a memset and 2; PLOC: 1 + I x (3 and the scan's)), L collapses, the leaves (a mesh: and 1 placing), L refits, a mesh's
+// finish. Stream waits: I + 1 under PLOC, 1 for the root height, L, and the last one: L + 2 with the radix tree, I + L + 3 with PLOC.
+// A rebalanced tree adds one copy, a memset, six launches and one wait; a mesh of one triangle is two copies, a memset, three
+// launches, its refit and finish, and one wait.
+template <class Args>
+static int build_tree(const Args& a, uint32_t n_keys, uint32_t n, LbvhResult* out, hipStream_t stream) {
+    constexpr int KIND = kind_of<Args>;
+    if (KIND == kBuildBoxes && (n < 2 || n > n_keys)) return -1;
+    if (KIND == kBuildMesh && (n < 1 || a.node_cap < 1)) return -1;
+    const uint32_t node_base = node_base_of(a);
+    uint32_t* const tree_nodes = (uint32_t*)a.nodes + (size_t)node_base * srl::kNodeDwords;
+    size_t sort_bytes, scan_bytes;
+    TREE_TRY(tree_temp_bytes(KIND, n_keys, n, a.ploc != 0, &sort_bytes, &scan_bytes, stream));
+    TreeScratch s;
+    if (carve_tree_scratch(a.scratch, KIND, n_keys, n, a.node_cap, a.ploc != 0, sort_bytes, scan_bytes, &s) > a.scratch_bytes) return (int)hipErrorOutOfMemory;
+
+    const bool single = KIND == kBuildMesh && n == 1;
+    int root_bin = 0;
+    uint32_t root_height = 0;
+    TREE_TRY(stage_keys_and_sort(a, s, stream));
+    TREE_TRY(stage_topology(a, s, single, out, &root_bin, stream));
+    if (!single) {
+        TREE_TRY(stage_height_bound(a, s, &root_bin, &root_height, out, stream));
+        TREE_TRY(stage_collapse(a, s, tree_nodes, root_bin, root_height, out, stream));
+    }
+    out->max_depth = (uint32_t)out->level_ranges.size();
+    stage_leaves(a, s, *out, stream);
+    const std::vector<std::pair<uint32_t, uint32_t>>& levels = out->level_ranges;      // root level first, local to the tree
+    refit_levels((uint32_t*)a.nodes, leaf_prims_of(a), a.node_box, nullptr, (uint32_t)levels.size(),
+                 [&](uint32_t l) { const auto& r = levels[levels.size() - 1 - l]; return std::make_pair(node_base + r.first, r.second); }, stream);
+    return stage_finish(a, s, stream);
+}
+
+int srk_lbvh_build(const TrisBuildArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree(a, a.n_tris, a.n_tris, out, stream); }
+int srk_tl_build(const BoxesBuildArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree(a, a.n_instances, a.n_boxes, out, stream); }
+int srk_blas_build(const MeshBuildArgs& a, LbvhResult* out, hipStream_t stream) { return build_tree(a, a.n_tris, a.n_tris, out, stream); }
 
 int srk_tl_records(const FlatInstance* instances, const TlMeshRow* meshes, uint32_t n_instances, double max_condition, DevTlInstance* records,
                    float* boxes, uint32_t* result, hipStream_t stream) {
@@ -831,16 +950,4 @@ int srk_tl_records(const FlatInstance* instances, const TlMeshRow* meshes, uint3
     if (n_instances == 0) return 0;
     tl_records_kernel<<<dim3((n_instances + 255) / 256), dim3(256), 0, stream>>>(instances, meshes, n_instances, max_condition, records, boxes, result);
     return (int)hipGetLastError();
-}
-
-size_t srk_tl_scratch_bytes(uint32_t n_instances, uint32_t node_cap) {    // as below without the triangle records and centroids
-    return srk_lbvh_scratch_bytes(n_instances, node_cap) - (size_t)n_instances * (48 + 16);
-}
-
-size_t srk_lbvh_scratch_bytes(uint32_t n_tris, uint32_t node_cap) {
-    size_t cub_bytes = 0, scan_bytes = 0;
-    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, cub_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (uint32_t*)nullptr,
-                                             (uint32_t*)nullptr, (int)n_tris, 0, 63, nullptr);
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n_tris, nullptr);
-    return (size_t)n_tris * (48 + 16 + 16 + 8 + 8 + 8 + 4 + 4 + 24 + 4 + 4 + 4 + 4 + 2 * (4 + 24) + 16 + 8 + 4 + 4) + (size_t)node_cap * 16 + std::max(cub_bytes, scan_bytes) + 100 * 256;
 }
