@@ -618,6 +618,80 @@ typedef struct SrMeshMorphInfo {
     double morph_ms;           /* the last accepted pose: its kernels (morph, and skin where asked) + read-back (events, only while sr_scene_enable_timing is on) */
 } SrMeshMorphInfo;             /* 24 bytes */
 int sr_scene_mesh_morph_info(const SrScene* scene, uint64_t key, SrMeshMorphInfo* out);
+/* The mesh frame: the third producer of device vertices that lives in the library, for callers that know only the new POSITIONS
+ * (a simulation, any torch code). It recomputes area-weighted normals, and uv-aligned tangents where asked, from the positions
+ * and the mesh's own topology, and hands the records on as sr_scene_update_mesh_device does its caller's. The pose path
+ * (sr_scene_skin_mesh, sr_scene_pose_mesh) is untouched and does not consult the frame: a mesh may carry a skin, a morph and a
+ * frame, three independent producers, and the last accepted call of any of them is what the next sr_scene_set_instances applies.
+ * The rule, fp32 under the numerics contract (no contraction, correctly rounded divide and sqrt, grouping as written). The
+ * REFERENCE RECORDS are the mesh's vertices as they stand at the attach.
+ *   Smoothing groups (fixed at the attach): two vertices belong to one group iff the 12 bytes of their reference position and the
+ *     12 bytes of their reference normal are equal. Equal position and normal with another uv is a uv seam and is smoothed across;
+ *     equal position with another normal is an authored hard edge and stays hard.
+ *   Entries of vertex v: the corners (t, c) of the index buffer whose vertex is in v's group, in ascending (t, c) order, one entry
+ *     per corner (a triangle with two corners in the group appears twice); the entry stores t.
+ *   Face vectors of triangle t with indices i0, i1, i2 in index-buffer order (the same bits whichever vertex asks):
+ *     e1 = p[i1] - p[i0], e2 = p[i2] - p[i0], F = e1 x e2 with a x b as written under sr_scene_skin_mesh;
+ *     a = uv[i1] - uv[i0], b = uv[i2] - uv[i0] over the reference records' normal_tex_coord, det = a.x * b.y - b.x * a.y;
+ *     det 0 or not finite: T = (+0, +0, +0); otherwise T.c = s * (e1.c * b.y - e2.c * a.y), s = +1.0f where det > 0, else -1.0f.
+ *   Per vertex: N = (0, 0, 0), then N = N + F[t] over its entries in order; A likewise from the T[t].
+ *     side = -1.0f where (N_ref.x * n.x + N_ref.y * n.y) + N_ref.z * n.z < 0 for N_ref, this same sum over the reference positions,
+ *     and the reference normal n; else +1.0f. Computed once at the attach: the face side the mesh's own normals chose, whatever
+ *     its winding.
+ *     position' = x, y, z of the input
+ *     normal'   = normalise(side * N)
+ *     d         = (n'.x * A.x + n'.y * A.y) + n'.z * A.z, with n' the reference normal where the normal fell back
+ *     tangent'  = (normalise(A.c - n'.c * d), reference w)
+ *     normalise(v) = v * (1.0f / sqrt((v.x * v.x + v.y * v.y) + v.z * v.z)); where that squared length is 0 or not finite, the
+ *     reference record's 16-byte piece is written for that vector.
+ *   Every other byte of the record (the fourth word of the three pieces, the five uv sets, the pads) is the reference record's.
+ *   Without SR_FRAME_TANGENTS the tangent piece is the reference's, byte for byte. */
+#define SR_FRAME_NORMALS 1u
+#define SR_FRAME_TANGENTS 2u  /* needs SR_FRAME_NORMALS: flags of 2 alone are refused */
+/* The groups, runs and sides of the rule on their own (no scene, no device), as CSR: offsets_out takes n_vertices + 1 words,
+ * entries_out *n_entries_out triangle indices (the sum over the vertices of their group's corner count: n_indices where every
+ * group is one vertex), side_out n_vertices floats. Any out pointer may be NULL; with all three NULL the call only counts.
+ * SR_ERR_INVALID_ARG: n_indices % 3 != 0, an index >= n_vertices (the text names the lowest offender), a null array that is not
+ * empty. SR_ERR_OOM: more than 2^32 - 1 entries. */
+int sr_mesh_frame_adjacency(const SrVertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices, uint32_t* offsets_out,
+                            uint32_t* entries_out, float* side_out, uint32_t* n_entries_out);
+/* The whole rule on the host, operation for operation the device's (the bytes are equal): `vertices` are the reference records,
+ * `positions` n_vertices tight float[3], out_vertices n_vertices records. A position that is not finite: SR_ERR_INVALID_ARG, the
+ * lowest such vertex in *first_bad_out (0xFFFFFFFF otherwise; may be NULL), out_vertices not written. Also refused: what
+ * sr_mesh_frame_adjacency refuses, flags of 0, unknown flag bits, SR_FRAME_TANGENTS alone. */
+int sr_mesh_frame_host(const SrVertex* vertices, uint32_t n_vertices, const uint32_t* indices, uint32_t n_indices, const float* positions,
+                       uint32_t flags, SrVertex* out_vertices, uint32_t* first_bad_out);
+/* Attaches a frame to a loaded mesh: fetches the host copy of its vertices where it is stale, builds groups, runs, sides and the
+ * per-triangle uv terms from them, uploads those and snapshots the mesh's CURRENT device vertices as the reference records (a
+ * device-to-device copy the mesh owns; waits for the device). Refused with SR_ERR_INVALID_ARG before anything is touched: a null
+ * scene, an unknown key, unknown flag bits, SR_FRAME_TANGENTS without SR_FRAME_NORMALS. A failed allocation returns SR_ERR_OOM and
+ * leaves an earlier frame in place. flags == 0 detaches the frame and frees its buffers; sr_scene_remove and sr_scene_destroy free
+ * them too. Later sr_scene_update_mesh* calls do not move the reference records; attaching again snapshots them anew. */
+int sr_scene_set_mesh_frame(SrScene* scene, uint64_t key, uint32_t flags);
+/* New positions for a mesh with a frame, already in device memory of the scene's GPU: `d_positions` holds n_vertices tightly
+ * packed float[3] (a contiguous [n, 3] float32 torch tensor), is 4-byte aligned, and was produced by work on `stream`. Two
+ * kernels on `stream` write the new records into a scratch buffer the scene owns, which goes the way of
+ * sr_scene_update_mesh_device: applied by the next sr_scene_set_instances, with the same SR_ERR_STATE window, the same stale host
+ * copy and the same emissive handling. Refused on the host before anything is launched: a null scene or pointer, an unknown key,
+ * a mesh with no frame, another vertex count, a misaligned pointer, a range that overlaps the mesh's own device allocation, a
+ * pointer the HIP runtime does not report as device memory of the scene's device for that many positions (all
+ * SR_ERR_INVALID_ARG; such a pointer is never dereferenced), an emissive list that is not one per triangle (SR_ERR_UNSUPPORTED).
+ * The finite-position check (x, y, z) is part of the vertex kernel: on a bad position the call returns sr_scene_update_mesh's
+ * status and text with the lowest offending index, and the scene is exactly as it was (only SrMeshFrameInfo.first_bad tells). */
+int sr_scene_update_mesh_positions_device(SrScene* scene, uint64_t key, const float* d_positions, uint32_t n_vertices, void* stream);
+/* The same with a HOST pointer: 12 bytes a vertex are uploaded asynchronously on `stream` into a scratch buffer of the scene
+ * (sr_scene_update_mesh uploads 96), then the same kernels run. The bytes are those of the device call. */
+int sr_scene_update_mesh_positions(SrScene* scene, uint64_t key, const float* positions, uint32_t n_vertices, void* stream);
+typedef struct SrMeshFrameInfo {
+    uint32_t flags;            /* SR_FRAME_* of the attached frame; 0: the mesh has none */
+    uint32_t n_groups;         /* smoothing groups */
+    uint32_t n_entries;        /* entries of all runs together */
+    uint32_t max_valence;      /* the longest run */
+    uint32_t updates;          /* accepted sr_scene_update_mesh_positions* calls since the frame was attached */
+    uint32_t first_bad;        /* the last such call: lowest vertex with a non-finite position, 0xFFFFFFFF: none */
+    double frame_ms;           /* the last accepted call: both kernels + 4-byte read-back (events, only while sr_scene_enable_timing is on) */
+} SrMeshFrameInfo;             /* 32 bytes */
+int sr_scene_mesh_frame_info(const SrScene* scene, uint64_t key, SrMeshFrameInfo* out);
 /* BuildType of one mesh's tree (blas.rs:149-161: RapidlyChanging and SometimesChanges are built with ALLOW_UPDATE, Static is not).
  * Every loaded mesh starts as SR_BUILD_STATIC (Renderer::load_mesh, lib.rs:937): it is never refitted, every update rebuilds its
  * tree on the host. An updatable mesh holds an SrAsState of its own (reset to sr_as_state_initial(build_type) by this call), driven
@@ -1052,6 +1126,13 @@ int sr_renderer_pose_mesh(SrRenderer* renderer, uint64_t key, const float* weigh
  * this was never called is posed by sr_renderer_pose_scene as before. Call it, like sr_renderer_attach_skins, while the meshes
  * hold the vertices they were loaded with. */
 int sr_renderer_attach_morphs(SrRenderer* renderer, const SrGltf* gltf, const SrLoadedScene* loaded);
+/* sr_scene_set_mesh_frame / sr_scene_update_mesh_positions_device / sr_scene_update_mesh_positions through the facade, as the
+ * skin calls above: the frame is attached on the first device slot's scene only and the records are produced there, once
+ * (`d_positions` lives on that slot's GPU); every further slot's replica takes the validated records by a device-to-device (peer)
+ * copy. A refusal changes no replica. */
+int sr_renderer_set_mesh_frame(SrRenderer* renderer, uint64_t key, uint32_t flags);
+int sr_renderer_update_mesh_positions_device(SrRenderer* renderer, uint64_t key, const float* d_positions, uint32_t n_vertices, void* stream);
+int sr_renderer_update_mesh_positions(SrRenderer* renderer, uint64_t key, const float* positions, uint32_t n_vertices, void* stream);
 /* sr_scene_set_mesh_build_type on every device slot's scene. */
 int sr_renderer_set_mesh_build_type(SrRenderer* renderer, uint64_t key, uint32_t build_type);
 /* sr_scene_set_mesh_tree_build on every device slot's scene. */

@@ -39,6 +39,8 @@ SYMBOLS = [
     "sr_renderer_attach_skins", "sr_renderer_pose_scene",
     "sr_scene_set_mesh_morph", "sr_scene_pose_mesh", "sr_scene_mesh_morph_info", "sr_renderer_set_mesh_morph", "sr_renderer_pose_mesh",
     "sr_gltf_blas_morph", "sr_gltf_morph_weights", "sr_renderer_attach_morphs",
+    "sr_mesh_frame_adjacency", "sr_mesh_frame_host", "sr_scene_set_mesh_frame", "sr_scene_update_mesh_positions_device", "sr_scene_update_mesh_positions",
+    "sr_scene_mesh_frame_info", "sr_renderer_set_mesh_frame", "sr_renderer_update_mesh_positions_device", "sr_renderer_update_mesh_positions",
     "sr_scene_set_light_table_build", "sr_scene_light_table_info", "sr_scene_read_lights", "sr_light_table",
     "sr_renderer_set_light_table_build", "sr_renderer_light_table_info",
 ]

@@ -200,6 +200,14 @@ class SrMeshMorphInfo(C.Structure):  # one mesh's morph and its last pose (sr_sc
     _fields_ = [("n_targets", C.c_uint32), ("posed", C.c_uint32), ("n_active", C.c_uint32), ("first_bad", C.c_uint32), ("morph_ms", C.c_double)]
 
 
+class SrMeshFrameInfo(C.Structure):  # one mesh's frame and its last position update (sr_scene_mesh_frame_info), 32 B
+    _fields_ = [("flags", C.c_uint32), ("n_groups", C.c_uint32), ("n_entries", C.c_uint32), ("max_valence", C.c_uint32),
+                ("updates", C.c_uint32), ("first_bad", C.c_uint32), ("frame_ms", C.c_double)]
+
+
+FRAME_NORMALS, FRAME_TANGENTS = 1, 2  # sr_scene_set_mesh_frame: tangents need normals
+
+
 class SrMeshTreeInfo(C.Structure):  # the mesh-tree builds of the last sr_scene_set_instances (sr_scene_mesh_tree_info)
     _fields_ = [("mode", C.c_uint32), ("auto_threshold", C.c_uint32), ("built_on_device", C.c_uint32), ("built_on_host", C.c_uint32),
                 ("reason", C.c_uint32), ("n_nodes", C.c_uint32), ("max_stack", C.c_uint32), ("_pad", C.c_uint32), ("device_build_ms", C.c_double)]

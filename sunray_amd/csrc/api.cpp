@@ -24,6 +24,7 @@
 #include "kernels.h"
 #include "lights.h"
 #include "morph.h"
+#include "normals.h"
 #include "skin.h"
 #include "tl_record.h"
 
@@ -213,6 +214,14 @@ struct SrScene {
         // owned by the mesh like the skin's buffers; n_targets == 0: no morph
         struct Morph { DeviceBuffer d_base, d_deltas; uint32_t n_targets = 0, posed = 0, n_active = 0, first_bad = 0xFFFFFFFFu; double morph_ms = 0.0; };
         Morph morph;
+        // sr_scene_set_mesh_frame: the reference records (a snapshot of the mesh's vertices at the attach), the runs (offsets, entries),
+        // the sides and the per-triangle uv terms of mesh_frame.h, owned by the mesh like the skin's buffers; flags == 0: no frame
+        struct Frame {
+            DeviceBuffer d_reference, d_offsets, d_entries, d_side, d_tri_uv;
+            uint32_t flags = 0, n_groups = 0, n_entries = 0, max_valence = 0, updates = 0, first_bad = 0xFFFFFFFFu;
+            double frame_ms = 0.0;
+        };
+        Frame frame;
         // light table on the device (SR_LIGHTS_DEVICE). arena_stale: the newest positions of this mesh's arena slots exist only on
         // the device (its d_vertices, and the device arena once arena_pending is served); emissive_tris holds older ones.
         // arena_pending: emissive_positions_kernel has to rewrite its slots of the device arena before the next table is built.
@@ -253,6 +262,9 @@ struct SrScene {
     // sr_scene_pose_mesh: the morphed vertices where a skin stage follows (scratch: srk_skin's `bind`; without one the morph stage
     // writes d_skin_out itself), and the active list of the last call (n indices, then n weights)
     DeviceBuffer d_morph_out, d_morph_active;
+    // sr_scene_update_mesh_positions*: the face vectors of the last call (one or two 16-byte pieces per triangle) and the uploaded
+    // positions of the host-pointer form; the records go to d_skin_out, the scratch every library producer leaves its result in
+    DeviceBuffer d_frame_faces, d_frame_positions;
     DeviceBuffer d_tl_inst, d_tl_instances;
     // top level built on the device (bvh_gpu.hip srk_tl_*): the instance boxes, its result block (the per-mesh rows are trees.d_tl_mesh_rows)
     DeviceBuffer d_tl_boxes, d_tl_result;
@@ -413,6 +425,20 @@ int check_mesh_update(SrScene* s, uint64_t key, const void* vertices, uint32_t n
         return fail(SR_ERR_INVALID_ARG, buf);
     }
     return SR_OK;
+}
+// Whether the HIP runtime reports [p, p + bytes) as device memory of the scene's device (bound by the caller). A pointer it does not
+// is never handed to a kernel.
+bool device_range_of_scene(const SrScene* s, const void* p, size_t bytes) {
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    void* base = nullptr;
+    size_t size = 0;
+    const uintptr_t a = (uintptr_t)p;
+    bool ok = hipPointerGetAttributes(&attr, p) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == s->device;
+    ok = ok && hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) == hipSuccess &&
+         a >= (uintptr_t)base && a - (uintptr_t)base <= size && bytes <= size - (a - (uintptr_t)base);
+    if (!ok) (void)hipGetLastError();                         // an address the runtime does not know leaves its error behind
+    return ok;
 }
 int fail_non_finite_vertex(uint32_t i) {
     char buf[120];
@@ -859,19 +885,7 @@ int sr_scene_update_mesh_device(SrScene* s, uint64_t key, const SrVertex* d_vert
     if (a < own + bytes && own < a + bytes) return fail(SR_ERR_INVALID_ARG, "update_mesh: the device vertices overlap the mesh's own vertex buffer");
     if ((rc = check_emissive_list(m)) != SR_OK) return rc;
     if ((rc = bind_device(s)) != SR_OK) return rc;
-    {
-        hipPointerAttribute_t attr;
-        memset(&attr, 0, sizeof(attr));
-        void* base = nullptr;
-        size_t size = 0;
-        bool ok = hipPointerGetAttributes(&attr, d_vertices) == hipSuccess && attr.type == hipMemoryTypeDevice && attr.device == s->device;
-        ok = ok && hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)d_vertices) == hipSuccess &&
-             a >= (uintptr_t)base && a - (uintptr_t)base <= size && bytes <= size - (a - (uintptr_t)base);
-        if (!ok) {
-            (void)hipGetLastError();                          // an address the runtime does not know leaves its error behind
-            return fail(SR_ERR_INVALID_ARG, "update_mesh: the vertex pointer is not device memory of the scene's device for that many vertices");
-        }
-    }
+    if (!device_range_of_scene(s, d_vertices, bytes)) return fail(SR_ERR_INVALID_ARG, "update_mesh: the vertex pointer is not device memory of the scene's device for that many vertices");
     if ((rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     uint32_t first_bad = 0xFFFFFFFFu;
@@ -1083,6 +1097,96 @@ int sr_scene_mesh_morph_info(const SrScene* s, uint64_t key, SrMeshMorphInfo* ou
     const SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
     memset(out, 0, sizeof(*out));
     out->n_targets = morph.n_targets; out->posed = morph.posed; out->n_active = morph.n_active; out->first_bad = morph.first_bad; out->morph_ms = morph.morph_ms;
+    return SR_OK;
+}
+
+// Attaches (or, with flags == 0, detaches) a mesh's frame, as sr_scene_set_mesh_skin attaches a rig: every buffer is filled before
+// the mesh's record changes, so a refusal or a failed allocation leaves an earlier frame in place. The groups come from the host
+// copy, which is the device buffer's contents once fetched: the reference records snapshotted below are those same bytes.
+int sr_scene_set_mesh_frame(SrScene* s, uint64_t key, uint32_t flags) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "set_mesh_frame: null argument (the scene)");
+    uint32_t slot = 0;
+    int rc = find_mesh(s, key, "set_mesh_frame", &slot);
+    if (rc != SR_OK) return rc;
+    if (flags & ~(SR_FRAME_NORMALS | SR_FRAME_TANGENTS)) return fail(SR_ERR_INVALID_ARG, "set_mesh_frame: unknown flag bits (SR_FRAME_NORMALS and SR_FRAME_TANGENTS are the flags)");
+    if (flags == SR_FRAME_TANGENTS) return fail(SR_ERR_INVALID_ARG, "set_mesh_frame: SR_FRAME_TANGENTS needs SR_FRAME_NORMALS (the tangent is made orthogonal to the new normal)");
+    if ((rc = bind_device(s)) != SR_OK) return rc;
+    if (flags == 0) return detach_record(s->mesh_state[slot].frame);
+    if ((rc = fetch_host_vertices(s, slot)) != SR_OK) return rc;
+    const srh::HostMesh& m = s->meshes[slot];
+    srh::MeshFrame f;
+    if ((rc = srh::mesh_frame_build(m.vertices.data(), m.n_vertices, m.indices.data(), m.n_indices, false, f, nullptr, "set_mesh_frame")) != SR_OK) return rc;
+    SrScene::MeshState::Frame frame;
+    if ((rc = frame.d_offsets.upload(f.offsets.data(), 4 * f.offsets.size())) != SR_OK || (rc = frame.d_entries.upload(f.entries.data(), 4 * f.entries.size())) != SR_OK ||
+        (rc = frame.d_side.upload(f.side.data(), 4 * f.side.size())) != SR_OK || (rc = frame.d_tri_uv.upload(f.tri_uv.data(), sizeof(srh::FrameTriUv) * f.tri_uv.size())) != SR_OK ||
+        (rc = snapshot_vertices(m, frame.d_reference)) != SR_OK) return rc;
+    frame.flags = flags; frame.n_groups = f.n_groups; frame.n_entries = (uint32_t)f.entries.size(); frame.max_valence = f.max_valence;
+    s->mesh_state[slot].frame = std::move(frame);
+    return SR_OK;
+}
+
+namespace {
+
+// sr_scene_update_mesh_positions_device and sr_scene_update_mesh_positions (`on_device`: where `positions` lives):
+// sr_scene_update_mesh_device with the frame kernels in front. The host form uploads its 12 bytes a vertex on the stream first.
+int update_mesh_positions(SrScene* s, uint64_t key, const float* positions, uint32_t n_vertices, void* stream, bool on_device) {
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t slot = 0;
+    int rc = check_mesh_update(s, key, positions, n_vertices, &slot);
+    if (rc != SR_OK) return rc;
+    srh::HostMesh& m = s->meshes[slot];
+    SrScene::MeshState::Frame& frame = s->mesh_state[slot].frame;
+    if (frame.flags == 0) return fail(SR_ERR_INVALID_ARG, "update_mesh_positions: the mesh has no frame (sr_scene_set_mesh_frame attaches one)");
+    const size_t bytes = 12 * (size_t)n_vertices, record_bytes = sizeof(SrVertex) * (size_t)n_vertices;
+    const uintptr_t a = (uintptr_t)positions, own = (uintptr_t)m.d_vertices;
+    if (a & 3u) return fail(SR_ERR_INVALID_ARG, "update_mesh_positions: the position pointer is not 4-byte aligned");
+    if (on_device && a < own + record_bytes && own < a + bytes) return fail(SR_ERR_INVALID_ARG, "update_mesh_positions: the device positions overlap the mesh's own vertex buffer");
+    if ((rc = check_emissive_list(m)) != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
+    if (on_device && !device_range_of_scene(s, positions, bytes))
+        return fail(SR_ERR_INVALID_ARG, "update_mesh_positions: the position pointer is not device memory of the scene's device for that many vertices");
+    const bool tangents = (frame.flags & SR_FRAME_TANGENTS) != 0;
+    const uint32_t n_triangles = m.n_indices / 3;
+    if ((rc = s->d_skin_out.reserve(record_bytes)) != SR_OK || (rc = s->d_vertex_check.reserve(16)) != SR_OK ||
+        (rc = s->d_frame_faces.reserve(16 * (size_t)n_triangles * (tangents ? 2 : 1))) != SR_OK) return rc;
+    if (!on_device && (rc = s->d_frame_positions.reserve(bytes)) != SR_OK) return rc;
+    const float* d_positions = on_device ? positions : (const float*)s->d_frame_positions.p;
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t bad = 0xFFFFFFFFu;
+    double ms = 0.0;
+    rc = checked_launch(s, st, 1, &bad, &ms, "update_mesh_positions: a frame kernel failed: ",
+                        [&] { return on_device ? 0 : (int)hipMemcpyAsync(s->d_frame_positions.p, positions, bytes, hipMemcpyHostToDevice, st); },
+                        [&](uint32_t* check) {
+                            return srk_mesh_frame((const SrVertex*)frame.d_reference.p, d_positions, (const uint32_t*)m.d_indices, (const srh::FrameTriUv*)frame.d_tri_uv.p,
+                                                  (const uint32_t*)frame.d_offsets.p, (const uint32_t*)frame.d_entries.p, (const float*)frame.d_side.p, frame.flags,
+                                                  (float4*)s->d_frame_faces.p, (SrVertex*)s->d_skin_out.p, n_vertices, n_triangles, check, st);
+                        });
+    if (rc != SR_OK) return rc;
+    frame.first_bad = bad < n_vertices ? bad : 0xFFFFFFFFu;
+    if (bad < n_vertices) return fail_non_finite_vertex(bad);
+    // check_ms 0.0: the check is part of the vertex kernel, whose time is SrMeshFrameInfo.frame_ms
+    if ((rc = finish_device_update(s, slot, (const SrVertex*)s->d_skin_out.p, s->device, 0.0, t0)) != SR_OK) return rc;
+    frame.frame_ms = ms; frame.updates++;
+    return SR_OK;
+}
+
+}  // namespace
+
+int sr_scene_update_mesh_positions_device(SrScene* s, uint64_t key, const float* d_positions, uint32_t n_vertices, void* stream) {
+    return update_mesh_positions(s, key, d_positions, n_vertices, stream, true);
+}
+
+int sr_scene_update_mesh_positions(SrScene* s, uint64_t key, const float* positions, uint32_t n_vertices, void* stream) {
+    return update_mesh_positions(s, key, positions, n_vertices, stream, false);
+}
+
+int sr_scene_mesh_frame_info(const SrScene* s, uint64_t key, SrMeshFrameInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_frame_info: null argument");
+    uint32_t slot = 0;
+    if (const int rc = find_mesh(s, key, "sr_scene_mesh_frame_info", &slot); rc != SR_OK) return rc;
+    const SrScene::MeshState::Frame& frame = s->mesh_state[slot].frame;
+    memset(out, 0, sizeof(*out));
+    out->flags = frame.flags; out->n_groups = frame.n_groups; out->n_entries = frame.n_entries; out->max_valence = frame.max_valence;
+    out->updates = frame.updates; out->first_bad = frame.first_bad; out->frame_ms = frame.frame_ms;
     return SR_OK;
 }
 

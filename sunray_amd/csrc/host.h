@@ -108,8 +108,8 @@ int set_error(int code, const std::string& msg);
 // finish_device_update): the copy into the mesh's allocation (peer copy across devices) and the state of that call, without a
 // second pass over the bytes.
 int scene_take_device_vertices(SrScene* scene, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, int src_device);
-// The scratch buffer on the scene's device that the last accepted sr_scene_skin_mesh or sr_scene_pose_mesh posed into (api.cpp):
-// what the further replicas of a renderer take through scene_take_device_vertices, and the vertex count of the mesh `key` that was
-// posed. Valid until the scene's next sr_scene_skin_mesh or sr_scene_pose_mesh.
+// The scratch buffer on the scene's device that the last accepted call of a library producer (sr_scene_skin_mesh, sr_scene_pose_mesh,
+// sr_scene_update_mesh_positions*) wrote its records into (api.cpp): what the further replicas of a renderer take through
+// scene_take_device_vertices, and the vertex count of the mesh `key` that was produced. Valid until the scene's next such call.
 const SrVertex* scene_skinned_vertices(const SrScene* scene, uint64_t key, uint32_t* n_vertices);
 }  // namespace srh

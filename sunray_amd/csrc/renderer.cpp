@@ -553,6 +553,22 @@ int sr_renderer_pose_mesh(SrRenderer* r, uint64_t key, const float* weights, uin
     return first_scene_produces(r, key, nullptr, 0, [&](SrScene* sc) { return sr_scene_pose_mesh(sc, key, weights, n_targets, joint_matrices, n_joints, stream); });
 }
 
+// A mesh's frame lives on the first slot's scene only, like its rig.
+int sr_renderer_set_mesh_frame(SrRenderer* r, uint64_t key, uint32_t flags) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "set_mesh_frame: null argument (the renderer)");
+    return sr_scene_set_mesh_frame(srmr::scenes(r)[0], key, flags);
+}
+
+// sr_scene_update_mesh_positions* on the first slot's scene, which produces the records and validates once (first_scene_produces).
+int sr_renderer_update_mesh_positions_device(SrRenderer* r, uint64_t key, const float* d_positions, uint32_t n_vertices, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "update_mesh_positions: null argument (the renderer)");
+    return first_scene_produces(r, key, nullptr, 0, [&](SrScene* sc) { return sr_scene_update_mesh_positions_device(sc, key, d_positions, n_vertices, stream); });
+}
+int sr_renderer_update_mesh_positions(SrRenderer* r, uint64_t key, const float* positions, uint32_t n_vertices, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "update_mesh_positions: null argument (the renderer)");
+    return first_scene_produces(r, key, nullptr, 0, [&](SrScene* sc) { return sr_scene_update_mesh_positions(sc, key, positions, n_vertices, stream); });
+}
+
 // The morph targets of a loaded scene, as sr_renderer_attach_skins attaches its rigs.
 int sr_renderer_attach_morphs(SrRenderer* r, const SrGltf* g, const SrLoadedScene* ls) {
     uint32_t n_blases = 0;

@@ -35,6 +35,67 @@ def _device_vertices(tensor, device_index):
     return C.c_void_p(tensor.data_ptr()), nbytes // abi.VERTEX.itemsize
 
 
+def _frame_flags(normals, tangents):
+    """abi.FRAME_* of set_mesh_frame's two switches; ValueError for tangents without normals (the library would refuse it)."""
+    if tangents and not normals:
+        raise ValueError("set_mesh_frame: tangents need normals (the tangent is made orthogonal to the new normal)")
+    return (abi.FRAME_NORMALS if normals else 0) | (abi.FRAME_TANGENTS if tangents else 0)
+
+
+def _mesh_positions(positions, device_index):
+    """The positions of update_mesh_positions -> (on_device, address, vertex count, stream or None, what keeps the memory alive):
+    a contiguous float32 [n, 3] torch tensor on cuda:`device_index` goes to the device call (with torch's current stream), a
+    float32 [n, 3] numpy array to the host call. ValueError for anything else: another dtype (no silent narrowing of float64),
+    another shape, gaps, a CPU tensor, another device."""
+    who = "update_mesh_positions"
+    if isinstance(positions, np.ndarray):
+        if positions.dtype != np.dtype(np.float32):
+            raise ValueError("%s: the positions must be float32 (%s given)" % (who, positions.dtype))
+        if positions.ndim != 2 or positions.shape[1] != 3 or len(positions) == 0:
+            raise ValueError("%s: the positions must have shape (n_vertices, 3) (shape %s given)" % (who, positions.shape))
+        a = np.ascontiguousarray(positions)
+        return False, _p(a), len(a), None, a
+    if not hasattr(positions, "data_ptr") or not hasattr(positions, "is_cuda"):
+        raise ValueError("%s: the positions must be a torch tensor on the scene's GPU or a numpy array" % who)
+    import torch
+    if positions.dtype != torch.float32:
+        raise ValueError("%s: the positions must be float32 (%s given)" % (who, positions.dtype))
+    if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] == 0:
+        raise ValueError("%s: the positions must have shape (n_vertices, 3) (shape %s given)" % (who, tuple(positions.shape)))
+    if not positions.is_cuda:
+        raise ValueError("%s: a torch tensor must be on the scene's GPU (a numpy array goes to the host call)" % who)
+    if positions.device.index != device_index:
+        raise ValueError("%s: the tensor is on %s, the scene on cuda:%d" % (who, positions.device, device_index))
+    if not positions.is_contiguous():
+        raise ValueError("%s: the tensor must be contiguous" % who)
+    return True, C.c_void_p(positions.data_ptr()), positions.shape[0], C.c_void_p(torch.cuda.current_stream(positions.device).cuda_stream), positions
+
+
+def mesh_frame_adjacency(vertices, indices):
+    """The smoothing groups of a mesh as the runs set_mesh_frame uploads -> (offsets [n + 1] uint32, entries uint32, side [n]
+    float32) (sr_mesh_frame_adjacency). Host only."""
+    v = np.ascontiguousarray(vertices, dtype=abi.VERTEX)
+    i = np.ascontiguousarray(indices, dtype=np.uint32)
+    n = C.c_uint32()
+    check(lib().sr_mesh_frame_adjacency(_p(v), C.c_uint32(len(v)), _p(i), C.c_uint32(len(i)), None, None, None, C.byref(n)))
+    offsets, entries, side = np.zeros(len(v) + 1, dtype=np.uint32), np.zeros(max(n.value, 1), dtype=np.uint32), np.zeros(max(len(v), 1), dtype=np.float32)
+    check(lib().sr_mesh_frame_adjacency(_p(v), C.c_uint32(len(v)), _p(i), C.c_uint32(len(i)), _p(offsets), _p(entries), _p(side), C.byref(n)))
+    return offsets, entries[: n.value], side[: len(v)]
+
+
+def mesh_frame_host(vertices, indices, positions, normals=True, tangents=False):
+    """update_mesh_positions on the host: the records a mesh with `vertices` as reference records takes from `positions` (float32
+    [n, 3]), byte for byte the device's (sr_mesh_frame_host). Host only."""
+    v = np.ascontiguousarray(vertices, dtype=abi.VERTEX)
+    i = np.ascontiguousarray(indices, dtype=np.uint32)
+    if not isinstance(positions, np.ndarray) or positions.dtype != np.dtype(np.float32) or positions.shape != (len(v), 3):
+        raise ValueError("mesh_frame_host: the positions must be a float32 numpy array of shape (%d, 3)" % len(v))
+    p = np.ascontiguousarray(positions)
+    out = np.zeros(len(v), dtype=abi.VERTEX)
+    check(lib().sr_mesh_frame_host(_p(v), C.c_uint32(len(v)), _p(i), C.c_uint32(len(i)), _p(p), C.c_uint32(_frame_flags(normals, tangents)), _p(out), None))
+    return out
+
+
 def _skin_influences(influences):
     """The influences of set_mesh_skin as a contiguous abi.SKIN_INFLUENCE array; ValueError for anything else (no conversion: a
     float array read as records would attach nonsense)."""
@@ -337,6 +398,30 @@ class Scene:
         the kernel time of the last one."""
         info = abi.SrMeshMorphInfo()
         check(lib().sr_scene_mesh_morph_info(self._h, C.c_uint64(key), C.byref(info)))
+        return info
+
+    def set_mesh_frame(self, key, normals=True, tangents=False):
+        """Attaches a frame to a loaded mesh: from then on update_mesh_positions recomputes its normals (and its tangents where
+        asked) from new positions alone; the mesh's current vertices become the reference records. normals=False detaches it
+        (sr_scene_set_mesh_frame)."""
+        flags = _frame_flags(normals, tangents)
+        check(lib().sr_scene_set_mesh_frame(self._h, C.c_uint64(key), C.c_uint32(flags)))
+
+    def update_mesh_positions(self, key, positions):
+        """New positions for a mesh with a frame, float32 [n_vertices, 3]: a torch tensor on the scene's GPU, produced on torch's
+        current stream, stays on the device (sr_scene_update_mesh_positions_device); a numpy array is uploaded, 12 bytes a vertex
+        (sr_scene_update_mesh_positions). From there on it is an update_mesh_device: the next set_instances applies it."""
+        on_device, ptr, n, stream, keep = _mesh_positions(positions, self.device_index)
+        if on_device:
+            check(lib().sr_scene_update_mesh_positions_device(self._h, C.c_uint64(key), ptr, C.c_uint32(n), stream))
+        else:
+            check(lib().sr_scene_update_mesh_positions(self._h, C.c_uint64(key), ptr, C.c_uint32(n), self._stream()))
+
+    def mesh_frame_info(self, key):
+        """-> abi.SrMeshFrameInfo: the flags of the mesh's frame (0: none), its groups, entries and longest run, the updates
+        taken, the last refusal and kernel time."""
+        info = abi.SrMeshFrameInfo()
+        check(lib().sr_scene_mesh_frame_info(self._h, C.c_uint64(key), C.byref(info)))
         return info
 
     def mesh_skin_info(self, key):
@@ -1045,6 +1130,25 @@ class Renderer:
         applies them (sr_renderer_pose_mesh)."""
         wp, nt, mp, nj, keep = _pose_args(weights, joint_matrices)
         check(lib().sr_renderer_pose_mesh(self._h, C.c_uint64(key), wp, nt, mp, nj, None))
+
+    def set_mesh_frame(self, key, normals=True, tangents=False):
+        """Scene.set_mesh_frame on the first device slot's scene, which produces for every slot (sr_renderer_set_mesh_frame)."""
+        flags = _frame_flags(normals, tangents)
+        check(lib().sr_renderer_set_mesh_frame(self._h, C.c_uint64(key), C.c_uint32(flags)))
+
+    def update_mesh_positions(self, key, positions):
+        """Scene.update_mesh_positions on the first device slot (a torch tensor lives on its GPU); every further slot takes the
+        records by a device copy; the next render applies them (sr_renderer_update_mesh_positions_device /
+        sr_renderer_update_mesh_positions)."""
+        on_device, ptr, n, stream, keep = _mesh_positions(positions, self.devices[0])
+        if on_device:
+            check(lib().sr_renderer_update_mesh_positions_device(self._h, C.c_uint64(key), ptr, C.c_uint32(n), stream))
+        else:
+            check(lib().sr_renderer_update_mesh_positions(self._h, C.c_uint64(key), ptr, C.c_uint32(n), None))
+
+    def mesh_frame_info(self, key):
+        """Scene.mesh_frame_info of the first device slot's scene, where the frame lives."""
+        return self.replica_scene(0).mesh_frame_info(key)
 
     def set_mesh_build_type(self, key, build_type):
         """abi.BUILD_* of a loaded mesh's tree on every device slot (sr_renderer_set_mesh_build_type)."""
