@@ -833,6 +833,59 @@ int sr_scene_add_sampler(SrScene* scene, const SrSamplerDesc* desc, uint32_t* ou
  * Unknown key -> SR_ERR_INVALID_ARG (resource_manager.rs:227-231). */
 int sr_scene_set_instances(SrScene* scene, const uint64_t* keys, const uint32_t* counts,
                            uint32_t n_keys, const SrTransform* transforms);
+/* The same for transforms that are already in device memory of the scene's device (work on `stream` produced them: rigid
+ * bodies, particles, a crowd, a [n, 3, 4] tensor): no host round trip. `keys` and `counts` are host arrays as above;
+ * `d_transforms` holds sum(counts) transforms. Refused before anything is launched, the pointer never dereferenced, with
+ * SR_ERR_INVALID_ARG: a null scene or null arrays, an unknown key (the text of sr_scene_set_instances), a pointer that is not
+ * 16-byte aligned, a pointer the HIP runtime does not report as device memory of the scene's device for that many bytes; and
+ * with the statuses and texts of sr_scene_set_instances its size limits. One kernel (instances.hip) then writes the
+ * per-instance device tables (WorldToObject by the host's arithmetic, operation for operation) into a second set of tables
+ * and validates in the same pass: a component that is not finite is SR_ERR_INVALID_ARG with the text of
+ * sr_scene_set_instances, the lowest such instance in SrInstanceUpdateInfo.bad_index, and the scene exactly as it was. Only
+ * after the answer is read back and the device has been waited for do the two sets change places. What follows is what
+ * sr_scene_set_instances does, with the same SrAsState accounting and the same reports: mesh-tree maintenance and the
+ * top-level build in the two-level form; update in place, device fast build or host build in the one-level form; the light
+ * table. The layout (mesh slot and triangle offset of each instance, the emissive entries) is built on the host and uploaded
+ * only when keys or counts differ from the last successful call through either entry point: an unchanged layout costs
+ * O(n_keys) on the host. The host copy of the transforms is left behind (SrInstanceUpdateInfo.host_stale) and fetched by
+ * whatever host code reads it next: the host top-level records, a host one-level build, the host light table of a
+ * non-empty arena, the baked-instance test of mesh-tree maintenance while a mesh has a pending update, the settle rebuild of
+ * sr_scene_end_frame, sr_scene_get_tables when it is asked for transforms. The device paths never fetch; the first transform
+ * alone (48 bytes, for the dummy light record of an empty arena) comes back with the validation word. */
+int sr_scene_set_instances_device(SrScene* scene, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys,
+                                  const SrTransform* d_transforms, void* stream);
+/* Why the host copy of the transforms was fetched last (SrInstanceUpdateInfo.fetch_reason). */
+enum {
+    SR_INST_FETCH_NONE = 0,
+    SR_INST_FETCH_HOST_TOP_LEVEL = 1,     /* host_tl_records: any SR_TL_HOST_* outcome, a baked instance included */
+    SR_INST_FETCH_HOST_BUILD = 2,         /* the host one-level build (also below the device fast build's threshold) */
+    SR_INST_FETCH_HOST_LIGHT_TABLE = 3,   /* SR_LIGHTS_HOST with a non-empty arena */
+    SR_INST_FETCH_SETTLE = 4,             /* the settle rebuild of sr_scene_end_frame */
+    SR_INST_FETCH_GET_TABLES = 5,         /* sr_scene_get_tables asked for transforms */
+    SR_INST_FETCH_MESH_TREES = 6          /* mesh-tree maintenance with a pending or stale mesh looks for baked instances */
+};
+/* The last sr_scene_set_instances / sr_scene_set_instances_device and the fetches since. tables_ms is taken with events and
+ * only while sr_scene_enable_timing is on (the kernel and its read-back); fetch_ms is wall clock. A refused device call
+ * changes bad_index alone. */
+typedef struct SrInstanceUpdateInfo {
+    uint32_t from_device;      /* 1: the transforms came from device memory */
+    uint32_t host_stale;       /* 1: the host copy of the transforms is older than the device tables */
+    uint32_t host_fetches;     /* fetches of the host copy since that call (at most one) */
+    uint32_t fetch_reason;     /* SR_INST_FETCH_* of the last one */
+    uint32_t layout_rebuilt;   /* 1: the call built the layout on the host and / or uploaded it */
+    uint32_t n_instances;
+    uint32_t bad_index;        /* lowest instance with a non-finite component of the last refused device call; 0xFFFFFFFF: none */
+    uint32_t _pad;
+    double tables_ms, fetch_ms;
+} SrInstanceUpdateInfo;          /* 48 bytes */
+int sr_scene_instance_update_info(const SrScene* scene, SrInstanceUpdateInfo* out);
+/* Harness read-back of the per-instance device tables, whichever path wrote them: n x 96 bytes (DevInstance: w2o[12],
+ * o2w[12], the 3x3 parts in words 0..8) and n x 64 bytes (FlatInstance: the transform, tri_offset, mesh_slot, two pad words),
+ * n = n_instances of sr_scene_get_tables; either pointer may be null. Waits for the device. */
+int sr_scene_read_instance_tables(const SrScene* scene, void* dev_instances, void* flat_instances);
+/* The host rule of the first of those tables on its own (no scene, no device): n x 96 bytes from n transforms. The host
+ * entry point fills its table with it, and instances.hip restates it. */
+int sr_instance_tables_host(const SrTransform* transforms, uint32_t n, void* dev_instances);
 
 /* Introspection of the tables frame_instance_data produced (host copies; pointers valid until the
  * next sr_scene_set_instances / destroy). num_lights is the emissive_indirection length the
@@ -980,6 +1033,13 @@ int sr_renderer_set_config(SrRenderer* renderer, const SrTraceConfig* config);
 int sr_renderer_render(SrRenderer* renderer, const float cam_pos[3], const float cam_target[3], float fov_y_degrees,
                        const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* transforms,
                        void* stream, uint64_t* out_frame);
+/* sr_renderer_render with the instance list taken from device memory on the first device slot's GPU (work on `stream` produced
+ * it): sr_scene_set_instances_device there, which validates the transforms once; the further replicas take them by a
+ * device-to-device (peer) copy, as with sr_renderer_update_mesh_device. The list always counts as changed (there is no host
+ * copy to compare with, and the one a later sr_renderer_render compares against is void). A refusal changes no replica. */
+int sr_renderer_render_device_transforms(SrRenderer* renderer, const float cam_pos[3], const float cam_target[3], float fov_y_degrees,
+                                         const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* d_transforms,
+                                         void* stream, uint64_t* out_frame);
 /* Renderer::wait_frame (lib.rs:1234-1238). */
 int sr_renderer_wait_frame(SrRenderer* renderer, uint64_t frame);
 /* Renderer::render_to_host_memory (lib.rs:1908-1934): 16 x (render + wait_frame), then the RGBA8 image

@@ -43,6 +43,8 @@ SYMBOLS = [
     "sr_scene_mesh_frame_info", "sr_renderer_set_mesh_frame", "sr_renderer_update_mesh_positions_device", "sr_renderer_update_mesh_positions",
     "sr_scene_set_light_table_build", "sr_scene_light_table_info", "sr_scene_read_lights", "sr_light_table",
     "sr_renderer_set_light_table_build", "sr_renderer_light_table_info",
+    "sr_scene_set_instances_device", "sr_scene_instance_update_info", "sr_scene_read_instance_tables", "sr_instance_tables_host",
+    "sr_renderer_render_device_transforms",
 ]
 
 

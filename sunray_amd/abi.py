@@ -175,6 +175,19 @@ class SrLightTableInfo(C.Structure):  # the light table of the last sr_scene_set
 LIGHTS_HOST, LIGHTS_DEVICE = 0, 1
 
 
+class SrInstanceUpdateInfo(C.Structure):  # the last set_instances / set_instances_device and the fetches since (sr_scene_instance_update_info), 48 B
+    _fields_ = [("from_device", C.c_uint32), ("host_stale", C.c_uint32), ("host_fetches", C.c_uint32), ("fetch_reason", C.c_uint32),
+                ("layout_rebuilt", C.c_uint32), ("n_instances", C.c_uint32), ("bad_index", C.c_uint32), ("_pad", C.c_uint32),
+                ("tables_ms", C.c_double), ("fetch_ms", C.c_double)]
+
+
+# SrInstanceUpdateInfo.fetch_reason
+INST_FETCH_NONE, INST_FETCH_HOST_TOP_LEVEL, INST_FETCH_HOST_BUILD, INST_FETCH_HOST_LIGHT_TABLE, INST_FETCH_SETTLE, INST_FETCH_GET_TABLES, INST_FETCH_MESH_TREES = range(7)
+# the per-instance device tables (sr_scene_read_instance_tables): DevInstance 96 B, FlatInstance 64 B
+DEV_INSTANCE = np.dtype([("w2o", np.float32, (12,)), ("o2w", np.float32, (12,))])
+FLAT_INSTANCE = np.dtype([("o2w", np.float32, (12,)), ("tri_offset", np.uint32), ("mesh_slot", np.uint32), ("_pad", np.uint32, (2,))])
+
+
 class SrSkinInfluence(C.Structure):  # one vertex's joints and weights (sr_scene_set_mesh_skin), 24 B
     _fields_ = [("joint", C.c_uint16 * 4), ("weight", C.c_float * 4)]
 

@@ -22,6 +22,7 @@
 #include "bvh_gpu.h"
 #include "bvh_layout.h"
 #include "kernels.h"
+#include "instances.h"
 #include "lights.h"
 #include "morph.h"
 #include "normals.h"
@@ -295,6 +296,18 @@ struct SrScene {
     bool built_once = false;
     bool geometry_stale = false;            // the built structure instances a dirty mesh: it shows stale geometry until the next sr_scene_set_instances
     SrMeshUpdateInfo mu_info{};
+    // sr_scene_set_instances_device. keys / counts: the layout `fid` holds (the last successful call through either entry point;
+    // layout_valid is cleared by what adds or removes a mesh, since a key may then name another mesh). d_layout: that layout's
+    // srd::InstanceLayout records while layout_on_device. d_instances_next / d_flat_next: the set of tables the kernel writes, which
+    // changes places with d_instances / d_flat_instances once the call is accepted. host_stale: the transforms of fid.transforms and
+    // fid.instances[].o2w are older than d_flat_instances, which fetch_host_transforms reads back.
+    struct InstanceSource {
+        std::vector<uint64_t> keys;
+        std::vector<uint32_t> counts;
+        bool layout_valid = false, layout_on_device = false, host_stale = false;
+        DeviceBuffer d_layout, d_instances_next, d_flat_next, d_replica_transforms;
+        SrInstanceUpdateInfo info{0, 0, 0, SR_INST_FETCH_NONE, 0, 0, 0xFFFFFFFFu, 0, 0.0, 0.0};
+    } inst;
     // Light table on the device. d_arena mirrors emissive_tris (arena_device_entries records). The invariant that keeps an older
     // host value from overwriting a newer device one: a mesh whose arena_stale is set has its newest vertices in its d_vertices,
     // so its slots of d_arena are a function of device memory alone; arena_host_dirty (anything wrote emissive_tris since the last
@@ -411,6 +424,24 @@ int fetch_host_vertices(SrScene* s, uint32_t slot) {
     m.host_stale = false;
     m.host_fetches++;
     m.fetch_ms = ms_between(t0, std::chrono::steady_clock::now());
+    return SR_OK;
+}
+
+// The host copy of the instance transforms, brought up to date where sr_scene_set_instances_device left it behind: one
+// device-to-host copy out of the FlatInstance table (48 of every 64 bytes). Everything on the host that reads fid.transforms
+// or an instance's o2w calls this first, with the SR_INST_FETCH_* it is; the device paths (the top-level build on the device,
+// in-place update, device fast build, the device light table) never do.
+int fetch_host_transforms(SrScene* s, uint32_t reason) {
+    if (!s->inst.host_stale) return SR_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n = s->fid.instances.size();
+    HIP_TRY(hipSetDevice(s->device));
+    if (n) HIP_TRY(hipMemcpy2D(s->fid.transforms.data(), sizeof(SrTransform), s->d_flat_instances.p, sizeof(srd::FlatInstance), sizeof(SrTransform), n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++) s->fid.instances[i].o2w = s->fid.transforms[i];
+    s->inst.host_stale = false;
+    SrInstanceUpdateInfo& ii = s->inst.info;
+    ii.host_stale = 0; ii.host_fetches++; ii.fetch_reason = reason;
+    ii.fetch_ms = ms_between(t0, std::chrono::steady_clock::now());
     return SR_OK;
 }
 
@@ -803,6 +834,7 @@ int sr_scene_add_blas(SrScene* s, uint64_t key, const SrVertex* vertices, uint32
     }
     s->slots[key] = slot;
     s->built = false;
+    s->inst.layout_valid = false;             // a key may name another mesh from here on
     s->mesh_state[slot] = SrScene::MeshState();
     s->trees.blas_device_current = false;
     if (out_slot) *out_slot = slot;
@@ -841,6 +873,7 @@ int sr_scene_remove(SrScene* s, uint64_t key) {
     s->free_mesh_slots.push_back(slot);
     s->slots.erase(it);
     s->built = false;
+    s->inst.layout_valid = false;
     return SR_OK;
 }
 
@@ -1256,27 +1289,33 @@ namespace {
 
 // Per-instance device tables (closest_hit's WorldToObject / ObjectToWorld, the flatten inputs) and the light table:
 // everything that follows the instance transforms without touching the tree.
+// The two tables themselves are the host's to fill unless sr_scene_set_instances_device's kernel has written them and the host
+// copy of the transforms is still behind (a host copy that was fetched since fills them again, with the same bytes).
 int upload_instance_tables(SrScene* s) {
     int rc;
-    std::vector<srd::DevInstance> dinst(s->fid.instances.size() ? s->fid.instances.size() : 1);
-    memset(dinst.data(), 0, dinst.size() * sizeof(srd::DevInstance));
-    std::vector<srd::FlatInstance> flat(dinst.size());
-    memset(flat.data(), 0, flat.size() * sizeof(srd::FlatInstance));
-    for (size_t i = 0; i < s->fid.instances.size(); i++) {
-        memcpy(dinst[i].w2o, s->fid.instances[i].w2o, 36);
-        const float* M = s->fid.instances[i].o2w.m;   // (float3x3)ObjectToWorld3x4
-        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) dinst[i].o2w[3 * r + c] = M[4 * r + c];
-        memcpy(flat[i].o2w, M, 48);
-        flat[i].tri_offset = s->fid.instances[i].tri_offset;
-        flat[i].mesh_slot = s->fid.instances[i].mesh_slot;
+    if (!s->inst.host_stale) {
+        const size_t ni = s->fid.instances.size();
+        std::vector<srd::DevInstance> dinst(ni ? ni : 1);
+        static_assert(sizeof(srd::DevInstance) == 96, "srh::instance_tables_host writes 24 floats per instance");
+        srh::instance_tables_host(s->fid.transforms.data(), ni, (float*)dinst.data());
+        if (ni == 0) memset(dinst.data(), 0, sizeof(srd::DevInstance));
+        std::vector<srd::FlatInstance> flat(dinst.size());
+        memset(flat.data(), 0, flat.size() * sizeof(srd::FlatInstance));
+        for (size_t i = 0; i < ni; i++) {
+            memcpy(flat[i].o2w, s->fid.instances[i].o2w.m, 48);
+            flat[i].tri_offset = s->fid.instances[i].tri_offset;
+            flat[i].mesh_slot = s->fid.instances[i].mesh_slot;
+        }
+        if ((rc = s->d_instances.upload(dinst.data(), dinst.size() * sizeof(srd::DevInstance))) != SR_OK) return rc;
+        if ((rc = s->d_flat_instances.upload(flat.data(), flat.size() * sizeof(srd::FlatInstance))) != SR_OK) return rc;
     }
-    if ((rc = s->d_instances.upload(dinst.data(), dinst.size() * sizeof(srd::DevInstance))) != SR_OK) return rc;
-    if ((rc = s->d_flat_instances.upload(flat.data(), flat.size() * sizeof(srd::FlatInstance))) != SR_OK) return rc;
     SrLightTableInfo& li = s->lt_info;                        // reset by sr_scene_set_instances: a path that comes here twice adds up
     li.num_lights = (uint32_t)s->fid.emissive_entries.size(); li.arena_entries = (uint32_t)s->emissive_tris.size();
     if (s->lights_on_device) {
         if ((rc = device_light_table(s)) != SR_OK) return rc;
     } else {
+        // the one dummy record of an empty arena reads the first transform alone, which a device call brings along
+        if (!s->emissive_tris.empty() && (rc = fetch_host_transforms(s, SR_INST_FETCH_HOST_LIGHT_TABLE)) != SR_OK) return rc;
         const auto t0 = std::chrono::steady_clock::now();
         std::vector<float> lights;
         srh::light_table(s->fid, s->emissive_table, lights);
@@ -1970,6 +2009,7 @@ int maintain_mesh_trees(SrScene* s, uint32_t forced) {
     classify_pending_mesh_trees(s, forced, p);
     if (!p.any_pending && !p.any_stale) { if (s->static_mesh_updated) ti.reason = SR_MESH_TREE_HOST_STATIC_MESH; return SR_OK; }
     int rc;
+    if ((rc = fetch_host_transforms(s, SR_INST_FETCH_MESH_TREES)) != SR_OK) return rc;     // mesh_tree_host_reason tests every instance's transform
     uint32_t reason = mesh_tree_host_reason(s, p);
     if (reason == SR_MESH_TREE_ON_DEVICE && !p.builds.empty() && (rc = build_mesh_trees_device(s, p.builds, &reason)) != SR_OK) return rc;
     if (reason != SR_MESH_TREE_ON_DEVICE) {
@@ -2009,6 +2049,7 @@ struct HostTlRecords {                        // what the host record loop compu
 };
 int host_tl_records(SrScene* s, HostTlRecords& h) {
     int rc;
+    if ((rc = fetch_host_transforms(s, SR_INST_FETCH_HOST_TOP_LEVEL)) != SR_OK) return rc;
     const size_t ni = s->fid.instances.size();
     h.recs.resize(ni ? ni : 1);
     memset(h.recs.data(), 0, h.recs.size() * sizeof(srd::DevTlInstance));
@@ -2159,30 +2200,119 @@ int fast_build(SrScene* s) {
     return SR_OK;
 }
 
+const char* const kNonFiniteTransform = "frame_instance_data: instance transform holds a non-finite value";
+
+// What both sr_scene_set_instances entry points refuse first, with one text each, sizes in 64 bits: the instance count into *n_inst.
+int check_instance_list(const SrScene* s, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const void* transforms, uint64_t* n_inst) {
+    if (!s || (n_keys && (!keys || !counts))) return fail(SR_ERR_INVALID_ARG, "frame_instance_data: null argument");
+    uint64_t n_tri = 0;
+    srh::instance_list_sizes(s->meshes, s->slots, keys, counts, n_keys, n_inst, &n_tri);
+    if (*n_inst && !transforms) return fail(SR_ERR_INVALID_ARG, "frame_instance_data: transforms is null but instances were given");
+    std::string err;
+    const int rc = srh::instance_list_limits(*n_inst, n_tri, s->instancing == SR_INSTANCING_FLAT, err);
+    return rc == SR_OK ? SR_OK : fail(rc, err);
+}
+
+bool same_instance_layout(const SrScene* s, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys) {
+    const SrScene::InstanceSource& in = s->inst;
+    return in.layout_valid && in.keys.size() == n_keys && (n_keys == 0 || (memcmp(in.keys.data(), keys, 8 * (size_t)n_keys) == 0 && memcmp(in.counts.data(), counts, 4 * (size_t)n_keys) == 0));
+}
+// `fid` now holds the layout of these keys and counts: what the device's copy of the layout is worth, and the record of it.
+void note_instance_layout(SrScene* s, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys) {
+    if (same_instance_layout(s, keys, counts, n_keys)) return;
+    s->inst.keys.assign(keys, keys + n_keys); s->inst.counts.assign(counts, counts + n_keys);
+    s->inst.layout_valid = true; s->inst.layout_on_device = false;
+}
+
+int apply_instance_list(SrScene* s);
+
 }  // namespace
 
 int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* transforms) {
-    if (!s || (n_keys && (!keys || !counts))) return fail(SR_ERR_INVALID_ARG, "frame_instance_data: null argument");
-    // sizes first, in 64 bits: the per-instance triangle offsets are 32-bit sums and a leaf reference holds 28 bits
-    uint64_t n_inst = 0, n_tri = 0;
-    for (uint32_t k = 0; k < n_keys; k++) {
-        n_inst += counts[k];
-        auto it = s->slots.find(keys[k]);
-        if (it != s->slots.end()) n_tri += (uint64_t)counts[k] * (s->meshes[it->second].n_indices / 3);
-    }
-    if (n_inst && !transforms) return fail(SR_ERR_INVALID_ARG, "frame_instance_data: transforms is null but instances were given");
-    if (n_tri >= 0xFFFFFFFFull) return fail(SR_ERR_UNSUPPORTED, "scene exceeds 2^32 - 1 triangles (32-bit global triangle index)");
-    if (n_tri >= (1ull << 28) && s->instancing == SR_INSTANCING_FLAT) return fail(SR_ERR_UNSUPPORTED, "scene exceeds 2^28 triangles (leaf reference encoding of the one-level form)");
-    if (n_inst >= (1ull << 28)) return fail(SR_ERR_UNSUPPORTED, "scene exceeds 2^28 instances");
+    uint64_t n_inst = 0;
+    int rc = check_instance_list(s, keys, counts, n_keys, transforms, &n_inst);
+    if (rc != SR_OK) return rc;
     for (uint64_t i = 0; i < n_inst; i++)
         for (int c = 0; c < 12; c++)
-            if (!std::isfinite(transforms[i].m[c])) return fail(SR_ERR_INVALID_ARG, "frame_instance_data: instance transform holds a non-finite value");
-    int rc = bind_device(s);
-    if (rc != SR_OK) return rc;
+            if (!std::isfinite(transforms[i].m[c])) return fail(SR_ERR_INVALID_ARG, kNonFiniteTransform);
+    if ((rc = bind_device(s)) != SR_OK) return rc;
     std::string err;
     srh::FrameInstanceData fid;
     if (!srh::frame_instance_data(s->meshes, s->slots, keys, counts, n_keys, transforms, fid, err)) return fail(SR_ERR_INVALID_ARG, err);
     s->fid = std::move(fid);
+    note_instance_layout(s, keys, counts, n_keys);
+    s->inst.host_stale = false;
+    s->inst.info = SrInstanceUpdateInfo{0, 0, 0, SR_INST_FETCH_NONE, 0, (uint32_t)n_inst, 0xFFFFFFFFu, 0, 0.0, 0.0};
+    return apply_instance_list(s);
+}
+
+// sr_scene_set_instances for transforms in device memory (header): the host's refusals, the layout where it changed, the kernel
+// into the second set of tables with its answer, and only for an accepted call the wait, the exchange of the two sets, the new
+// layout into `fid` and everything sr_scene_set_instances does from there (apply_instance_list).
+namespace {
+int set_instances_device(SrScene* s, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* d_transforms, hipStream_t st) {
+    uint64_t n_inst = 0;
+    int rc = check_instance_list(s, keys, counts, n_keys, d_transforms, &n_inst);
+    if (rc != SR_OK) return rc;
+    if ((uintptr_t)d_transforms & 15u) return fail(SR_ERR_INVALID_ARG, "frame_instance_data: the device transform pointer is not 16-byte aligned");
+    const bool new_layout = !same_instance_layout(s, keys, counts, n_keys);
+    std::string err;
+    srh::FrameInstanceData staged;
+    if (new_layout && !srh::frame_instance_layout(s->meshes, s->slots, keys, counts, n_keys, staged, err)) return fail(SR_ERR_INVALID_ARG, err);
+    if ((rc = bind_device(s)) != SR_OK) return rc;
+    if (n_inst && !device_range_of_scene(s, d_transforms, sizeof(SrTransform) * (size_t)n_inst))
+        return fail(SR_ERR_INVALID_ARG, "frame_instance_data: the transform pointer is not device memory of the scene's device for that many instances");
+    SrScene::InstanceSource& in = s->inst;
+    const uint32_t n = (uint32_t)n_inst;
+    const bool upload_layout = new_layout || !in.layout_on_device;
+    if (upload_layout) {                      // d_layout is read by the kernel alone: a refused call leaves it marked as not current
+        const std::vector<srh::HostInstance>& from = new_layout ? staged.instances : s->fid.instances;
+        std::vector<srd::InstanceLayout> layout(n);
+        for (uint32_t i = 0; i < n; i++) layout[i] = srd::InstanceLayout{from[i].tri_offset, from[i].mesh_slot};
+        in.layout_on_device = false;
+        if ((rc = in.d_layout.upload(layout.data(), sizeof(srd::InstanceLayout) * (size_t)n)) != SR_OK) return rc;
+    }
+    const size_t slots = n ? n : 1;           // a list without instances keeps one zero record, as the host's tables do
+    if ((rc = in.d_instances_next.reserve(slots * sizeof(srd::DevInstance))) != SR_OK || (rc = in.d_flat_next.reserve(slots * sizeof(srd::FlatInstance))) != SR_OK ||
+        (rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
+    uint32_t first_bad = 0xFFFFFFFFu;
+    double tables_ms = 0.0;
+    SrTransform first{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
+    rc = checked_launch(s, st, 1, &first_bad, &tables_ms, "frame_instance_data: instance table kernel failed: ", [] { return 0; }, [&](uint32_t* check) {
+        int e = 0;
+        if (n == 0) {
+            e = (int)hipMemsetAsync(in.d_instances_next.p, 0, sizeof(srd::DevInstance), st);
+            if (e == 0) e = (int)hipMemsetAsync(in.d_flat_next.p, 0, sizeof(srd::FlatInstance), st);
+        }
+        if (e == 0) e = srk_instance_tables(d_transforms, (const srd::InstanceLayout*)in.d_layout.p, n, (srd::DevInstance*)in.d_instances_next.p, (srd::FlatInstance*)in.d_flat_next.p, check, st);
+        if (e == 0 && n) e = (int)hipMemcpyAsync(&first, d_transforms, sizeof(first), hipMemcpyDeviceToHost, st);   // the dummy light record's
+        return e;
+    });
+    if (rc != SR_OK) return rc;
+    if (first_bad < n) { in.info.bad_index = first_bad; return fail(SR_ERR_INVALID_ARG, kNonFiniteTransform); }
+    HIP_TRY(hipDeviceSynchronize());          // frames in flight read the tables that change places here
+    std::swap(s->d_instances, in.d_instances_next);
+    std::swap(s->d_flat_instances, in.d_flat_next);
+    s->dev.instances = (const srd::DevInstance*)s->d_instances.p;
+    if (new_layout) s->fid = std::move(staged);
+    note_instance_layout(s, keys, counts, n_keys);
+    in.layout_on_device = true;
+    if (n) { s->fid.transforms[0] = first; s->fid.instances[0].o2w = first; }
+    in.host_stale = n > 0;
+    in.info = SrInstanceUpdateInfo{1, n > 0 ? 1u : 0u, 0, SR_INST_FETCH_NONE, upload_layout ? 1u : 0u, n, 0xFFFFFFFFu, 0, tables_ms, 0.0};
+    return apply_instance_list(s);
+}
+}  // namespace
+
+int sr_scene_set_instances_device(SrScene* s, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* d_transforms, void* stream) {
+    return set_instances_device(s, keys, counts, n_keys, d_transforms, (hipStream_t)stream);
+}
+
+namespace {
+// Everything that follows the instance list in `fid`, whichever entry point put it there: the light table's source, the form,
+// mesh-tree maintenance and the top-level build, or the one-level op the heuristic picks.
+int apply_instance_list(SrScene* s) {
+    int rc;
     // meshes updated since the structure last took their vertices (sr_scene_update_mesh): every path below applies them
     const bool reshade = s->geometry_stale;
     s->mu_info.dirty_meshes = (uint32_t)std::count_if(s->mesh_state.begin(), s->mesh_state.end(), [](const SrScene::MeshState& ms) { return ms.dirty; });
@@ -2240,6 +2370,30 @@ int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* cou
     if (rc != SR_OK) { s->built = false; return rc; }
     return built_with(op);
 }
+}  // namespace
+
+int sr_scene_instance_update_info(const SrScene* s, SrInstanceUpdateInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_instance_update_info: null argument");
+    *out = s->inst.info;
+    return SR_OK;
+}
+
+int sr_scene_read_instance_tables(const SrScene* s, void* dev_instances, void* flat_instances) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_read_instance_tables: scene is null");
+    if (!s->built) return fail(SR_ERR_STATE, "sr_scene_read_instance_tables: call sr_scene_set_instances first");
+    const size_t n = s->fid.instances.size();
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (dev_instances && n) HIP_TRY(hipMemcpy(dev_instances, s->d_instances.p, n * sizeof(srd::DevInstance), hipMemcpyDeviceToHost));
+    if (flat_instances && n) HIP_TRY(hipMemcpy(flat_instances, s->d_flat_instances.p, n * sizeof(srd::FlatInstance), hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_instance_tables_host(const SrTransform* transforms, uint32_t n, void* dev_instances) {
+    if (n && (!transforms || !dev_instances)) return fail(SR_ERR_INVALID_ARG, "sr_instance_tables_host: null argument");
+    srh::instance_tables_host(transforms, n, (float*)dev_instances);
+    return SR_OK;
+}
 
 int sr_scene_end_frame(SrScene* s) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_end_frame: scene is null");
@@ -2264,6 +2418,7 @@ int sr_scene_end_frame(SrScene* s) {
         int rc = bind_device(s);
         if (rc != SR_OK) return rc;
         if (s->lights_on_device && (rc = fetch_emissive_table(s)) != SR_OK) return rc;   // the rebuild may move the device arena on (a pending mesh)
+        if ((rc = fetch_host_transforms(s, SR_INST_FETCH_SETTLE)) != SR_OK) return rc;   // both rebuilds are the host's
         if (s->two_level && !s->trees.blas_device_current) invalidate_mesh_trees(s, false);      // the re-concatenation takes the stale host copies of refitted meshes along
         if ((rc = s->two_level ? two_level_build(s, false) : full_build(s)) != SR_OK) { s->built = false; return rc; }
     }
@@ -2520,6 +2675,7 @@ namespace {
 int full_build(SrScene* s) {
     int rc;
     HIP_TRY(hipDeviceSynchronize());
+    if ((rc = fetch_host_transforms(s, SR_INST_FETCH_HOST_BUILD)) != SR_OK) return rc;
     for (const auto& in : s->fid.instances)       // the flatten and the record packing below read the host copies
         if ((rc = fetch_host_vertices(s, in.mesh_slot)) != SR_OK) return rc;
     srh::flatten_instances(s->meshes, s->fid, s->world_tris);
@@ -2587,6 +2743,7 @@ int sr_scene_get_tables(const SrScene* s, const SrTransform** transforms, uint32
     if (!s) return fail(SR_ERR_INVALID_ARG, "sr_scene_get_tables: scene is null");
     if (!s->built) return fail(SR_ERR_STATE, "sr_scene_get_tables: call sr_scene_set_instances first");
     if (emissive_triangles || n_emissive) { const int rc = fetch_emissive_table(const_cast<SrScene*>(s)); if (rc != SR_OK) return rc; }
+    if (transforms) { const int rc = fetch_host_transforms(const_cast<SrScene*>(s), SR_INST_FETCH_GET_TABLES); if (rc != SR_OK) return rc; }
     if (transforms) *transforms = s->fid.transforms.data();
     if (n_instances) *n_instances = (uint32_t)s->fid.transforms.size();
     if (indirection) *indirection = s->fid.emissive_entries.data();
@@ -2981,4 +3138,18 @@ const SrVertex* srh::scene_skinned_vertices(const SrScene* s, uint64_t key, uint
     auto it = s->slots.find(key);
     *n_vertices = it == s->slots.end() ? 0u : s->meshes[it->second].n_vertices;
     return (const SrVertex*)s->d_skin_out.p;
+}
+
+// A further replica of a renderer takes transforms that sr_scene_set_instances_device has accepted on `src_device`: a copy into a
+// buffer of its own (peer copy across devices), then the same call on the null stream.
+int srh::scene_set_instances_from(SrScene* s, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* d_transforms, int src_device) {
+    uint64_t n_inst = 0;
+    int rc = check_instance_list(s, keys, counts, n_keys, d_transforms, &n_inst);
+    if (rc != SR_OK) return rc;
+    if ((rc = bind_device(s)) != SR_OK) return rc;
+    const size_t bytes = sizeof(SrTransform) * (size_t)n_inst;
+    if ((rc = s->inst.d_replica_transforms.reserve(bytes)) != SR_OK) return rc;
+    if (bytes) HIP_TRY(src_device == s->device ? hipMemcpyAsync(s->inst.d_replica_transforms.p, d_transforms, bytes, hipMemcpyDeviceToDevice, nullptr)
+                                               : hipMemcpyPeerAsync(s->inst.d_replica_transforms.p, s->device, d_transforms, src_device, bytes, nullptr));
+    return set_instances_device(s, keys, counts, n_keys, (const SrTransform*)s->inst.d_replica_transforms.p, nullptr);
 }

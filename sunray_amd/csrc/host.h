@@ -36,8 +36,7 @@ struct HostMesh {
 
 struct HostInstance {
     uint32_t mesh_slot;   // instance custom index (resource_manager.rs:239-246)
-    SrTransform o2w;
-    float w2o[9];
+    SrTransform o2w;      // WorldToObject is a function of it (instance_tables_host), computed where the device table is written
     uint32_t tri_offset;
 };
 
@@ -61,6 +60,22 @@ void light_table(const FrameInstanceData& fid, const std::vector<SrEmissiveTrian
 bool frame_instance_data(const std::vector<HostMesh>& meshes, const std::map<uint64_t, uint32_t>& slots,
                          const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* xforms,
                          FrameInstanceData& out, std::string& err);
+// The two halves of frame_instance_data. The layout is everything that follows from keys and counts alone: mesh_slot and
+// tri_offset of every instance, the emissive entries, n_triangles, and `transforms` at its final length (the dummy of an empty
+// list is the identity; every other transform, and every o2w, is left zero). The transforms are the rest: they fill a layout
+// of out.instances.size() instances from `xforms`.
+bool frame_instance_layout(const std::vector<HostMesh>& meshes, const std::map<uint64_t, uint32_t>& slots,
+                           const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, FrameInstanceData& out, std::string& err);
+void frame_instance_transforms(const SrTransform* xforms, FrameInstanceData& out);
+// Instances and triangles of an instance list in 64 bits (an unknown key counts no triangles: the layout refuses it), and the
+// limits both sr_scene_set_instances entry points apply to them: SR_OK, or SR_ERR_UNSUPPORTED with the text in `err`.
+void instance_list_sizes(const std::vector<HostMesh>& meshes, const std::map<uint64_t, uint32_t>& slots, const uint64_t* keys,
+                         const uint32_t* counts, uint32_t n_keys, uint64_t* n_instances, uint64_t* n_triangles);
+int instance_list_limits(uint64_t n_instances, uint64_t n_triangles, bool one_level_only, std::string& err);
+// The 96-byte DevInstance records (traverse.h) of `n` transforms into `out`, 24 floats each: w2o[0..8] by world_to_object_3x3,
+// o2w[0..8] the 3x3 part at float 12, the other words 0. The one host definition (sr_instance_tables_host); instances.hip
+// restates it for the device.
+void instance_tables_host(const SrTransform* xforms, size_t n, float* out);
 
 // ---- BVH (bvh_build.cpp) ------------------------------------------------------------------------
 // One world-space triangle in the canonical form the kernels intersect.
@@ -108,6 +123,9 @@ int set_error(int code, const std::string& msg);
 // finish_device_update): the copy into the mesh's allocation (peer copy across devices) and the state of that call, without a
 // second pass over the bytes.
 int scene_take_device_vertices(SrScene* scene, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, int src_device);
+// A further replica of a renderer takes an instance list whose transforms sr_scene_set_instances_device has accepted on
+// `src_device` (api.cpp): a copy into a buffer of the replica's own (peer copy across devices) and the same call there.
+int scene_set_instances_from(SrScene* scene, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* d_transforms, int src_device);
 // The scratch buffer on the scene's device that the last accepted call of a library producer (sr_scene_skin_mesh, sr_scene_pose_mesh,
 // sr_scene_update_mesh_positions*) wrote its records into (api.cpp): what the further replicas of a renderer take through
 // scene_take_device_vertices, and the vertex count of the mesh `key` that was produced. Valid until the scene's next such call.

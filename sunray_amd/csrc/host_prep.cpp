@@ -154,15 +154,44 @@ static uint32_t half_bits(float f) {
 }
 uint32_t pack_half_2x16(float x, float y) { return half_bits(x) | (half_bits(y) << 16); }
 
+void instance_tables_host(const SrTransform* xforms, size_t n, float* out) {
+    memset(out, 0, n * 96);
+    for (size_t i = 0; i < n; i++) {
+        float* q = out + i * 24;
+        world_to_object_3x3(xforms[i], q);
+        const float* M = xforms[i].m;   // (float3x3)ObjectToWorld3x4
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) q[12 + 3 * r + c] = M[4 * r + c];
+    }
+}
+
+void instance_list_sizes(const std::vector<HostMesh>& meshes, const std::map<uint64_t, uint32_t>& slots, const uint64_t* keys,
+                         const uint32_t* counts, uint32_t n_keys, uint64_t* n_instances, uint64_t* n_triangles) {
+    uint64_t n_inst = 0, n_tri = 0;
+    for (uint32_t k = 0; k < n_keys; k++) {
+        n_inst += counts[k];
+        auto it = slots.find(keys[k]);
+        if (it != slots.end()) n_tri += (uint64_t)counts[k] * (meshes[it->second].n_indices / 3);
+    }
+    *n_instances = n_inst; *n_triangles = n_tri;
+}
+
+// the per-instance triangle offsets are 32-bit sums and a leaf reference holds 28 bits
+int instance_list_limits(uint64_t n_instances, uint64_t n_triangles, bool one_level_only, std::string& err) {
+    if (n_triangles >= 0xFFFFFFFFull) err = "scene exceeds 2^32 - 1 triangles (32-bit global triangle index)";
+    else if (n_triangles >= (1ull << 28) && one_level_only) err = "scene exceeds 2^28 triangles (leaf reference encoding of the one-level form)";
+    else if (n_instances >= (1ull << 28)) err = "scene exceeds 2^28 instances";
+    else return SR_OK;
+    return SR_ERR_UNSUPPORTED;
+}
+
 // ResourceManager::frame_instance_data (resource_manager.rs:216-267) followed by the dummy-entry
-// padding of Renderer::render (lib.rs:1058-1081).
-bool frame_instance_data(const std::vector<HostMesh>& meshes, const std::map<uint64_t, uint32_t>& slots,
-                         const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* xforms,
-                         FrameInstanceData& out, std::string& err) {
+// padding of Renderer::render (lib.rs:1058-1081), in two halves: what keys and counts decide, then the transforms.
+bool frame_instance_layout(const std::vector<HostMesh>& meshes, const std::map<uint64_t, uint32_t>& slots,
+                           const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, FrameInstanceData& out, std::string& err) {
     out.instances.clear();
     out.transforms.clear();
     out.emissive_entries.clear();
-    uint32_t next = 0, tri_offset = 0;
+    uint32_t tri_offset = 0;
     for (uint32_t k = 0; k < n_keys; k++) {
         auto it = slots.find(keys[k]);
         if (it == slots.end()) {
@@ -172,13 +201,9 @@ bool frame_instance_data(const std::vector<HostMesh>& meshes, const std::map<uin
         const uint32_t mesh_info_slot = it->second;
         const HostMesh& mesh = meshes[mesh_info_slot];
         for (uint32_t c = 0; c < counts[k]; c++) {
-            const uint32_t instance_index = (uint32_t)out.transforms.size();
-            const SrTransform& xf = xforms[next++];
-            out.transforms.push_back(xf);
-            HostInstance inst;
+            const uint32_t instance_index = (uint32_t)out.instances.size();
+            HostInstance inst{};
             inst.mesh_slot = mesh_info_slot;
-            inst.o2w = xf;
-            world_to_object_3x3(xf, inst.w2o);
             inst.tri_offset = tri_offset;
             tri_offset += mesh.n_indices / 3;
             out.instances.push_back(inst);
@@ -187,8 +212,21 @@ bool frame_instance_data(const std::vector<HostMesh>& meshes, const std::map<uin
         }
     }
     out.n_triangles = tri_offset;
+    out.transforms.resize(out.instances.size());                 // zero until frame_instance_transforms or the device's copy fills them
     if (out.transforms.empty()) out.transforms.push_back(SrTransform{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}});
     if (out.emissive_entries.empty()) out.emissive_entries.push_back(SrEmissiveIndirectionEntry{0, 0});
+    return true;
+}
+
+void frame_instance_transforms(const SrTransform* xforms, FrameInstanceData& out) {
+    for (size_t i = 0; i < out.instances.size(); i++) { out.transforms[i] = xforms[i]; out.instances[i].o2w = xforms[i]; }
+}
+
+bool frame_instance_data(const std::vector<HostMesh>& meshes, const std::map<uint64_t, uint32_t>& slots,
+                         const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* xforms,
+                         FrameInstanceData& out, std::string& err) {
+    if (!frame_instance_layout(meshes, slots, keys, counts, n_keys, out, err)) return false;
+    frame_instance_transforms(xforms, out);
     return true;
 }
 

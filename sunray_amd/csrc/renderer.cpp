@@ -241,6 +241,10 @@ int sr_renderer_set_config(SrRenderer* r, const SrTraceConfig* cfg) {
     return SR_OK;
 }
 
+namespace {
+int render_passes(SrRenderer* r, const float cam_pos[3], const float cam_target[3], float fov_y, void* stream, uint64_t* out_frame);
+}
+
 // Renderer::render (lib.rs:984-1232): one frame = TLAS (re)build when the instance list changed ->
 // raytracing_ris -> raytracing_final -> temporal_accumulation -> denoise_0..3 -> postprocess, enqueued on the
 // renderer's own two streams after whatever the caller has enqueued on `stream`; returns the frame number to wait
@@ -268,6 +272,30 @@ int sr_renderer_render(SrRenderer* r, const float cam_pos[3], const float cam_ta
     } else {
         if (const int rc = each_scene(r, sr_scene_end_frame); rc != SR_OK) return rc;    // quiet frame: the heuristic may settle with a quality rebuild
     }
+    return render_passes(r, cam_pos, cam_target, fov_y, stream, out_frame);
+}
+
+// sr_renderer_render with the instance list taken from device memory on the first slot's GPU: that slot's scene validates the
+// transforms once (sr_scene_set_instances_device), the further replicas take them device to device. The list always counts as
+// changed: there is no host copy to compare, and the cached one is void.
+int sr_renderer_render_device_transforms(SrRenderer* r, const float cam_pos[3], const float cam_target[3], float fov_y, const uint64_t* keys,
+                                         const uint32_t* counts, uint32_t n_keys, const SrTransform* d_transforms, void* stream, uint64_t* out_frame) {
+    if (!r || !cam_pos || !cam_target) return rfail(SR_ERR_INVALID_ARG, "Renderer::render: null argument");
+    R_HIP(hipSetDevice(r->device));
+    run_frame_callbacks(r, r->absolute_frame_count + 1);
+    r->instances_valid = false;
+    r->last_transforms.clear();
+    const std::vector<SrScene*> scenes = srmr::scenes(r);
+    int rc = sr_scene_set_instances_device(scenes[0], keys, counts, n_keys, d_transforms, stream);
+    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_set_instances_from(scenes[i], keys, counts, n_keys, d_transforms, r->device);
+    if (rc != SR_OK) return rc;
+    R_HIP(hipSetDevice(r->device));
+    return render_passes(r, cam_pos, cam_target, fov_y, stream, out_frame);
+}
+
+namespace {
+// The frame behind its instance list: camera, the two ray-tracing passes, the post chain (the rest of Renderer::render).
+int render_passes(SrRenderer* r, const float cam_pos[3], const float cam_target[3], float fov_y, void* stream, uint64_t* out_frame) {
     SrMatrices m;
     int rc = sr_camera_matrices(cam_pos, cam_target, fov_y, r->width, r->height, r->prev_view_proj, &m);   // lib.rs:1017-1048
     if (rc != SR_OK) return rc;
@@ -321,6 +349,7 @@ int sr_renderer_render(SrRenderer* r, const float cam_pos[3], const float cam_ta
     if (out_frame) *out_frame = r->absolute_frame_count;
     return SR_OK;
 }
+}  // namespace
 
 // Renderer::wait_frame (lib.rs:1234-1238): frames complete in order; waits for the latest submitted one.
 int sr_renderer_wait_frame(SrRenderer* r, uint64_t frame) {

@@ -35,6 +35,24 @@ def _device_vertices(tensor, device_index):
     return C.c_void_p(tensor.data_ptr()), nbytes // abi.VERTEX.itemsize
 
 
+def _device_transforms(layout, tensor, device_index):
+    """(keys, counts, address) of an instance list whose transforms are a torch tensor on cuda:`device_index`: `layout` is
+    [(key, count), ...], `tensor` contiguous float32 with sum(counts) x 12 elements (row-major 3x4); ValueError for anything the
+    library would have to refuse or could not read."""
+    keys = np.array([k for k, _ in layout], dtype=np.uint64)
+    counts = np.array([c for _, c in layout], dtype=np.uint32)
+    n = int(counts.sum())
+    if not getattr(tensor, "is_cuda", False):
+        raise ValueError("set_instances_device: the transforms must be a tensor on the scene's GPU, not host memory")
+    if tensor.device.index != device_index:
+        raise ValueError("set_instances_device: the tensor is on %s, the scene on cuda:%d" % (tensor.device, device_index))
+    if str(tensor.dtype) != "torch.float32" or not tensor.is_contiguous():
+        raise ValueError("set_instances_device: the tensor must be contiguous float32")
+    if tensor.numel() != n * 12:
+        raise ValueError("set_instances_device: %d elements are not %d transforms of 12" % (tensor.numel(), n))
+    return keys, counts, C.c_void_p(tensor.data_ptr() if n else 0)
+
+
 def _frame_flags(normals, tangents):
     """abi.FRAME_* of set_mesh_frame's two switches; ValueError for tangents without normals (the library would refuse it)."""
     if tangents and not normals:
@@ -519,6 +537,29 @@ class Scene:
         if len(xf) == 0:
             xf = np.zeros((1, 12), dtype=np.float32)
         check(lib().sr_scene_set_instances(self._h, _p(keys), _p(counts), C.c_uint32(len(keys)), _p(np.ascontiguousarray(xf))))
+
+    def set_instances_device(self, layout, tensor):
+        """set_instances for transforms that are on the GPU already: `layout` is [(key, count), ...], `tensor` a contiguous
+        float32 torch tensor on the scene's device with sum(counts) x 12 elements (row-major 3x4 each), produced on torch's
+        current stream (sr_scene_set_instances_device)."""
+        import torch
+        keys, counts, ptr = _device_transforms(layout, tensor, self.device_index)
+        check(lib().sr_scene_set_instances_device(self._h, _p(keys), _p(counts), C.c_uint32(len(keys)), ptr,
+                                                  C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)))
+
+    def instance_update_info(self):
+        """-> abi.SrInstanceUpdateInfo: where the last instance list came from, whether the library's host copy of the transforms
+        is behind the device tables, the fetches since and why, and the kernel's milliseconds."""
+        info = abi.SrInstanceUpdateInfo()
+        check(lib().sr_scene_instance_update_info(self._h, C.byref(info)))
+        return info
+
+    def read_instance_tables(self):
+        """-> (abi.DEV_INSTANCE [n], abi.FLAT_INSTANCE [n]): the per-instance device tables, whichever path wrote them."""
+        n = self.instance_update_info().n_instances
+        dev, flat = np.zeros(max(n, 1), dtype=abi.DEV_INSTANCE), np.zeros(max(n, 1), dtype=abi.FLAT_INSTANCE)
+        check(lib().sr_scene_read_instance_tables(self._h, _p(dev), _p(flat)))
+        return dev[:n], flat[:n]
 
     def tile_row_costs(self, which, width, y0, rows):
         """Measured cycles per 8-pixel tile row of the last launch of pass `which` (0 ris, 1 final) with this geometry."""
@@ -1239,6 +1280,17 @@ class Renderer:
         frame = C.c_uint64()
         check(lib().sr_renderer_render(self._h, _f3(pos), _f3(tgt), C.c_float(fov), _p(keys), _p(counts), C.c_uint32(len(keys)), _p(xf),
                                        None, C.byref(frame)))
+        return frame.value
+
+    def render_device_transforms(self, camera, layout, tensor):
+        """render with the instance list taken from the GPU: `layout` is [(key, count), ...], `tensor` as for
+        Scene.set_instances_device, on the first device slot's GPU (sr_renderer_render_device_transforms)."""
+        import torch
+        pos, tgt, fov = camera
+        keys, counts, ptr = _device_transforms(layout, tensor, self.devices[0])
+        frame = C.c_uint64()
+        check(lib().sr_renderer_render_device_transforms(self._h, _f3(pos), _f3(tgt), C.c_float(fov), _p(keys), _p(counts), C.c_uint32(len(keys)), ptr,
+                                                         C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream), C.byref(frame)))
         return frame.value
 
     def wait_frame(self, frame):
