@@ -92,6 +92,60 @@ def unpack_normal(p):
 
 NO_READ = -2 ** 31     # read-log marker (orc_scene.h, kNoRead)
 
+# Branch log (OracleScene.set_branch_log): bit k of a pixel's word is set when the pass took the outcome named k-th here.
+# Word 0, trace_ris (ray_gen_ris.slang; the numbers are lines of oracle/orc_passes.cpp as it stood before the log was added):
+RIS_BITS = (
+    "prev_behind",           # :150 prev_clip.w <= 0.01
+    "prev_x_neg", "prev_y_neg", "prev_x_high", "prev_y_high",    # :155, each side of the screen the reprojection can leave by
+    "prev_valid",            # :155 reprojection on screen
+    "di_hist_neg",           # :217 pcx < 0 or pcy < 0 (unreachable: (int)(x) of an x > -1 is 0)
+    "di_hist_x_high", "di_hist_y_high", "di_hist_inside",        # :217
+    "gi_hist_neg",           # :319 gx < 0 or gy < 0 (unreachable, as di_hist_neg)
+    "gi_hist_x_high", "gi_hist_y_high", "gi_hist_inside",        # :319
+    "no_lights",             # :176 / :272 num_lights == 0 (unreachable: the instance tables always hold the dummy record)
+    "audition",              # :176 lights and a rough surface: the candidates are drawn
+    "idx_clamped", "idx_in_range",                               # :179 candidate index, rnd() == 1.0f or less
+    "first_not_taken",       # :199 the first candidate with a weight is not taken: the reservoir holds no sample yet has w_sum > 0
+    "taken",                 # :199
+    "gi_ndotl_zero", "gi_ndotl_pos",                             # :261
+    "nee_idx_clamped", "nee_idx_in_range",                       # :274
+    "tir",                   # :139 total internal reflection
+    "no_diffuse",            # :165 every virtual bounce was glass or mirror
+    # to_ufloat (orc_utils.h:208-234) of the stored denoiser albedo, any of its three channels:
+    "uf_zero",               # :222 below the smallest denormal's half
+    "uf_down", "uf_up",      # :231 denormal range, rounded down / up
+    "uf_tie_down", "uf_tie_up",                                  # :231 denormal range, exact tie to the even neighbour below / above
+    "uf_normal",             # :216
+)
+# Word 1, trace_final (ray_gen_final.slang):
+FINAL_BITS = (
+    "tir", "reflect", "refract_in", "refract_out",               # :405-413 glass: total internal reflection; the three ways on
+    "bright_break",          # :394 brightness > 1
+    "throughput_break",      # :596 p < 0.001
+    "rr_survive", "rr_die",  # :598 Russian roulette
+    "vndf_below", "vndf_above",                                  # :582 VNDF sample under the horizon or not
+    "vndf_head_on",          # orc_utils.h:116 lensq == 0
+    "diffuse_bounce",        # :591
+    "no_lights",             # :419 num_lights == 0 (unreachable, as in RIS_BITS)
+    "center_idx_out", "center_merged",                           # :424 W > 0 and light_idx >= num_lights, or merged
+    "neighbor_idx_out", "neighbor_merged",                       # :448
+    "neighbor_depth_reject",                                     # :444
+    "di_zero_sample",        # :456 w_sum > 0 and no merge took its sample: the held sample is all zeros
+    "di_behind", "di_query",                                     # :465
+    "gi_self",               # :481 GI neighbour is the own pixel
+    "gi_cos_zero",           # :502
+    "gi_jacobian_clamped",   # :504 above 10
+    "gi_short",              # :507 segment to the neighbour's sample <= 0.002: no query is issued
+    "gi_merged",             # :510
+    "gif_behind", "gif_query",                                   # :520
+    "gif_repeat",            # :521 asks about the segment :507 asked about (the sample came from a neighbour)
+    "gif_short",             # :521 segment <= 0.002: no query is issued
+    "nee_idx_clamped", "nee_idx_in_range",                       # :531
+)
+RIS_BIT = {name: 1 << k for k, name in enumerate(RIS_BITS)}
+FINAL_BIT = {name: 1 << k for k, name in enumerate(FINAL_BITS)}
+assert len(RIS_BITS) <= 32 and len(FINAL_BITS) <= 32
+
 
 class OracleScene:
     """Oracle counterpart of sunray_amd.Scene: same methods, numpy (host) buffers."""
@@ -185,6 +239,15 @@ class OracleScene:
             assert log.dtype == np.int32 and log.flags["C_CONTIGUOUS"] and log.shape[-1] == 4
         self._read_log = log
         lib().orc_scene_set_read_log(self._h, None if log is None else _p(log))
+
+    def set_branch_log(self, log):
+        """Test aid: `log`, a C-contiguous uint32 array [height, width, 2], receives per pixel the branch outcomes the following
+        trace_ris (word 0, RIS_BITS) and trace_final (word 1, FINAL_BITS) calls take; each pass clears its word of a pixel before
+        it starts on it. None switches the log off (the default: nothing changes)."""
+        if log is not None:
+            assert log.dtype == np.uint32 and log.flags["C_CONTIGUOUS"] and log.shape[-1] == 2
+        self._branch_log = log
+        lib().orc_scene_set_branch_log(self._h, None if log is None else _p(log))
 
     def tables(self):
         tp, ip, ep = C.c_void_p(), C.c_void_p(), C.c_void_p()

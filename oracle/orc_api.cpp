@@ -42,6 +42,8 @@ int orc_scene_set_instances(void* s, const uint64_t* keys, const uint32_t* count
 void orc_scene_set_brute_force(void* s, int on) { ((Scene*)s)->use_brute_force = on != 0; }
 // Test aid: 4 * width * height ints that the following orc_trace_ris calls fill (orc_scene.h, read_log); NULL switches it off.
 void orc_scene_set_read_log(void* s, int32_t* log) { ((Scene*)s)->read_log = log; }
+// Test aid: 2 * width * height words that the following orc_trace_ris / orc_trace_final calls fill (orc_scene.h, branch_log); NULL switches it off.
+void orc_scene_set_branch_log(void* s, uint32_t* log) { ((Scene*)s)->branch_log = log; }
 void orc_scene_get_tables(void* sp, const SrTransform** transforms, uint32_t* n_instances,
                           const SrEmissiveIndirectionEntry** indirection, uint32_t* num_lights,
                           const SrEmissiveTriangle** emissive, uint32_t* n_emissive, uint32_t* n_triangles) {

@@ -61,6 +61,43 @@ inline PrimaryRay primary_ray(const Mat4& vi, const Mat4& pi, uint32_t px, uint3
     return PrimaryRay{xyz(origin), xyz(direction), inUV};
 }
 
+// Branch log (test aid, Scene::branch_log): bit numbers of the two words, in the order of RIS_BITS / FINAL_BITS of
+// oracle/binding.py, which names them.
+enum RisBit : uint32_t {
+    R_PREV_BEHIND, R_PREV_X_NEG, R_PREV_Y_NEG, R_PREV_X_HIGH, R_PREV_Y_HIGH, R_PREV_VALID,
+    R_DI_HIST_NEG, R_DI_HIST_X_HIGH, R_DI_HIST_Y_HIGH, R_DI_HIST_INSIDE,
+    R_GI_HIST_NEG, R_GI_HIST_X_HIGH, R_GI_HIST_Y_HIGH, R_GI_HIST_INSIDE,
+    R_NO_LIGHTS, R_AUDITION, R_IDX_CLAMPED, R_IDX_IN_RANGE, R_FIRST_NOT_TAKEN, R_TAKEN,
+    R_GI_NDOTL_ZERO, R_GI_NDOTL_POS, R_NEE_IDX_CLAMPED, R_NEE_IDX_IN_RANGE, R_TIR, R_NO_DIFFUSE,
+    R_UF_ZERO, R_UF_DOWN, R_UF_UP, R_UF_TIE_DOWN, R_UF_TIE_UP, R_UF_NORMAL
+};
+enum FinalBit : uint32_t {
+    F_TIR, F_REFLECT, F_REFRACT_IN, F_REFRACT_OUT, F_BRIGHT_BREAK, F_THROUGHPUT_BREAK, F_RR_SURVIVE, F_RR_DIE,
+    F_VNDF_BELOW, F_VNDF_ABOVE, F_VNDF_HEAD_ON, F_DIFFUSE_BOUNCE, F_NO_LIGHTS,
+    F_CENTER_IDX_OUT, F_CENTER_MERGED, F_NEIGHBOR_IDX_OUT, F_NEIGHBOR_MERGED, F_NEIGHBOR_DEPTH_REJECT,
+    F_DI_ZERO_SAMPLE, F_DI_BEHIND, F_DI_QUERY,
+    F_GI_SELF, F_GI_COS_ZERO, F_GI_JACOBIAN_CLAMPED, F_GI_SHORT, F_GI_MERGED,
+    F_GIF_BEHIND, F_GIF_QUERY, F_GIF_REPEAT, F_GIF_SHORT, F_NEE_IDX_CLAMPED, F_NEE_IDX_IN_RANGE
+};
+struct BranchLog {
+    uint32_t* word;
+    void operator()(uint32_t bit) const { if (word) *word |= 1u << bit; }
+};
+// Which way to_ufloat (orc_utils.h) takes for a value the G-buffer stores: the value is lerp(albedo, 1, metallic) of an
+// albedo and a metallic in [0, 1], or the literal 0 of a sky pixel, so the negative, >= 65536, infinity and NaN exits are
+// not classified: nothing a material holds leads there.
+inline void log_ufloat(const BranchLog& log, float f, int MANT) {
+    if (!log.word) return;
+    uint32_t u = f2u(f);
+    if (u >= 0x38800000u) { log(R_UF_NORMAL); return; }
+    if (u < 0x30000000u) { log(R_UF_ZERO); return; }
+    uint32_t m = (u & 0x7fffffu) | 0x800000u, s = 136u - (uint32_t)MANT - (u >> 23);
+    if (s > 31u) { log(R_UF_ZERO); return; }
+    uint32_t lower = m & ((1u << s) - 1u), half = 1u << (s - 1u);
+    if (lower == half) log(((m >> s) & 1u) ? R_UF_TIE_UP : R_UF_TIE_DOWN);
+    else log(lower > half ? R_UF_UP : R_UF_DOWN);
+}
+
 inline SrReservoir empty_reservoir() { SrReservoir r; memset(&r, 0, sizeof(r)); return r; }
 inline SrReservoirGI empty_reservoir_gi() { SrReservoirGI r; memset(&r, 0, sizeof(r)); return r; }
 
@@ -93,6 +130,9 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
     const uint32_t pix = py * W + px;                                 // get_pixel_index
     int32_t* read_log = sc.read_log ? sc.read_log + (size_t)pix * 4 : nullptr;     // test aid (orc_scene.h)
     if (read_log) read_log[0] = read_log[1] = read_log[2] = read_log[3] = Scene::kNoRead;
+    const BranchLog blog{sc.branch_log ? sc.branch_log + (size_t)pix * 2 : nullptr};   // test aid (orc_scene.h)
+    if (blog.word) *blog.word = 0u;
+    bool walk_missed = false;
 
     Rng rng = init_rng(px, py, pc.frame_count, W);                   // :42
     PrimaryRay pr = primary_ray(mat_view_inverse, mat_proj_inverse, px, py, W, H);  // :44-53
@@ -113,7 +153,7 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
         // not in the reference: the camera ray's payload, exposed so that tests can check what the HIP path's RIS pass
         // hands to its final pass (SrRtParams.primary_payload). The oracle's own final pass never reads it.
         if (virtual_bounce == 0 && pc.primary_payload) pc.primary_payload[pix] = prd;
-        if (prd.dist < 0.0f) break;                                  // :77-79
+        if (prd.dist < 0.0f) { walk_missed = true; break; }          // :77-79
         hitPos = rayOrigin + rayDir * prd.dist;                      // :81
         hit_normal = unpack_normal(prd.normal_packed);
         V4 alb = unpack_unorm_4x8(prd.albedo_packed);
@@ -136,7 +176,7 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
             R0 = R0 * R0;
             float fresnel = R0 + (1.0f - R0) * pow5(1.0f - cos_theta);
             V3 refracted = refract(rayDir, N, eta);
-            if (length(refracted) < 0.01f) fresnel = 1.0f;
+            if (length(refracted) < 0.01f) { fresnel = 1.0f; blog(R_TIR); }
             if (rnd(rng) < fresnel) rayDir = reflect(rayDir, N);
             else rayDir = refracted;
             rayOrigin = hitPos + rayDir * 0.001f;                    // :114
@@ -148,14 +188,21 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
             V4 prev_clip = mul(mat_prev_view_proj, V4{virtual_world_pos.x, virtual_world_pos.y, virtual_world_pos.z, 1.0f});
             const float MIN_PREV_W = 0.01f;
             prev_valid = prev_clip.w > MIN_PREV_W;
+            if (!prev_valid) blog(R_PREV_BEHIND);
             if (prev_valid) {
                 float iw = 1.0f / prev_clip.w;                       // float2 / scalar
                 V2 prev_ndc = V2{prev_clip.x * iw, prev_clip.y * iw};
                 prev_uv = V2{prev_ndc.x * 0.5f + 0.5f, prev_ndc.y * 0.5f + 0.5f};
                 prev_valid = (prev_uv.x >= 0.0f && prev_uv.y >= 0.0f) && (prev_uv.x < 1.0f && prev_uv.y < 1.0f);
+                if (!(prev_uv.x >= 0.0f)) blog(R_PREV_X_NEG);
+                if (!(prev_uv.y >= 0.0f)) blog(R_PREV_Y_NEG);
+                if (!(prev_uv.x < 1.0f)) blog(R_PREV_X_HIGH);
+                if (!(prev_uv.y < 1.0f)) blog(R_PREV_Y_HIGH);
+                if (prev_valid) blog(R_PREV_VALID);
             }
             V2 motion_vector = prev_valid ? V2{inUV.x - prev_uv.x, inUV.y - prev_uv.y} : V2{inUV.x + 2.0f, inUV.y + 2.0f};
             V3 denoiser_albedo = lerp3(hit_albedo, v3(1.0f), metallic);
+            log_ufloat(blog, denoiser_albedo.x, 6); log_ufloat(blog, denoiser_albedo.y, 6); log_ufloat(blog, denoiser_albedo.z, 5);
             store_gbuffer(pc, pix, virtual_distance, hit_normal, roughness, denoiser_albedo, motion_vector);  // :133-136
             found_diffuse_surface = true;
             break;
@@ -163,6 +210,7 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
     }
 
     if (!found_diffuse_surface) {                                    // :143-172
+        if (!walk_missed && pc.config.virtual_bounces > 0) blog(R_NO_DIFFUSE);   // every bounce was glass or mirror
         // (sky_motion is computed by the shader, :145-154, but never stored: motion gets 0.)
         store_gbuffer(pc, pix, 100000.0f, v3(0.0f), 0.0f, v3(0.0f), V2{0.0f, 0.0f});
         reservoir_cur[pix] = empty_reservoir();
@@ -173,9 +221,12 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
     SrReservoir current_r = empty_reservoir();
     const uint32_t num_lights = cx.num_lights;                       // :185-186
     const int RIS_CANDIDATES = (int)pc.config.ris_candidates;
+    if (num_lights == 0) blog(R_NO_LIGHTS);
     if (num_lights > 0 && roughness > 0.2f) {                        // :189
+        blog(R_AUDITION);
         for (int i = 0; i < RIS_CANDIDATES; i++) {
             uint32_t cand_idx = (uint32_t)(rnd(rng) * (float)num_lights);
+            blog(cand_idx > num_lights - 1 ? R_IDX_CLAMPED : R_IDX_IN_RANGE);
             if (cand_idx > num_lights - 1) cand_idx = num_lights - 1;
             const SrEmissiveIndirectionEntry& entry = sc.indirection[cand_idx];
             const SrEmissiveTriangle& cand_light = sc.emissive_tris[entry.blas_tri_index];
@@ -196,7 +247,11 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
             float p_y = 1.0f / max_f((float)num_lights * cand_area, 0.0001f);
             current_r.w_sum += (p_hat / p_y);
             current_r.M += 1.0f;
-            if (rnd(rng) < ((p_hat / p_y) / max_f(current_r.w_sum, 0.0001f))) {
+            const bool take = rnd(rng) < ((p_hat / p_y) / max_f(current_r.w_sum, 0.0001f));
+            // the first candidate that contributes (it alone makes up w_sum) and is not taken: the reservoir goes on holding no sample
+            if (!take && (p_hat / p_y) > 0.0f && current_r.w_sum == (p_hat / p_y)) blog(R_FIRST_NOT_TAKEN);
+            if (take) blog(R_TAKEN);
+            if (take) {
                 current_r.light_idx = cand_idx;
                 S3(current_r.light_pos, cand_pos);
                 S3(current_r.light_normal, cand_normal);
@@ -214,7 +269,11 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
             V2 di_jitter = V2{j0 - 0.5f, j1 - 0.5f};
             int pcx = (int)(prev_pixel_f.x + di_jitter.x), pcy = (int)(prev_pixel_f.y + di_jitter.y);
             if (read_log) { read_log[0] = pcx; read_log[1] = pcy; }
+            if (pcx < 0 || pcy < 0) blog(R_DI_HIST_NEG);
+            if (pcx >= (int)W) blog(R_DI_HIST_X_HIGH);
+            if (pcy >= (int)H) blog(R_DI_HIST_Y_HIGH);
             if (pcx >= 0 && pcy >= 0 && pcx < (int)W && pcy < (int)H) {
+                blog(R_DI_HIST_INSIDE);
                 SrReservoir history_r = reservoir_hist[(uint32_t)pcy * W + (uint32_t)pcx];
                 history_r.M = min_f(history_r.M, 10.0f);
                 history_r.W = min_f(history_r.W, 20.0f);
@@ -258,6 +317,7 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
     float gr1 = rnd(rng), gr2 = rnd(rng);                            // argument order of :322
     V3 gi_dir = get_random_bounce(hit_normal, gr1, gr2);
     float gi_NdotL = max_f(dot(hit_normal, gi_dir), 0.0f);
+    blog(gi_NdotL > 0.0f ? R_GI_NDOTL_POS : R_GI_NDOTL_ZERO);
     if (gi_NdotL > 0.0f) {
         V3 gi_origin = hitPos + hit_normal * 0.001f;
         cx.trace(gi_origin, gi_dir, 0.001f, 10000.0f, prd);          // :327-332
@@ -269,8 +329,10 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
             V3 x2_albedo = v3(a2.x, a2.y, a2.z);
             sample_radiance = A3(prd.emission);
             uint32_t nee_num_lights = num_lights;
+            if (nee_num_lights == 0) blog(R_NO_LIGHTS);
             if (nee_num_lights > 0) {
                 uint32_t nee_idx = (uint32_t)(rnd(rng) * (float)nee_num_lights);
+                blog(nee_idx > nee_num_lights - 1 ? R_NEE_IDX_CLAMPED : R_NEE_IDX_IN_RANGE);
                 if (nee_idx > nee_num_lights - 1) nee_idx = nee_num_lights - 1;
                 const SrEmissiveIndirectionEntry& nee_entry = sc.indirection[nee_idx];
                 const SrEmissiveTriangle& nee_light = sc.emissive_tris[nee_entry.blas_tri_index];
@@ -316,7 +378,11 @@ void ris_pixel(Ctx& cx, uint32_t px, uint32_t py) {
         V2 gi_jitter = V2{j0 - 0.5f, j1 - 0.5f};
         int gx = (int)(prev_pixel_f_gi.x + gi_jitter.x), gy = (int)(prev_pixel_f_gi.y + gi_jitter.y);
         if (read_log) { read_log[2] = gx; read_log[3] = gy; }
+        if (gx < 0 || gy < 0) blog(R_GI_HIST_NEG);
+        if (gx >= (int)W) blog(R_GI_HIST_X_HIGH);
+        if (gy >= (int)H) blog(R_GI_HIST_Y_HIGH);
         if (gx >= 0 && gy >= 0 && gx < (int)W && gy < (int)H) {
+            blog(R_GI_HIST_INSIDE);
             SrReservoirGI history_gi = reservoir_gi_hist[(uint32_t)gy * W + (uint32_t)gx];
             V3 gi_hist_normal = unpack_normal(history_gi.hit_normal_packed);
             float normal_conf = smoothstep(0.8f, 0.95f, dot(hit_normal, gi_hist_normal));
@@ -350,6 +416,8 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
     const SrReservoirGI* reservoir_gi_cur = pc.reservoirs_gi[cur_buf];
     const uint32_t pix = py * W + px;
     const int ipx = (int)px, ipy = (int)py;
+    const BranchLog blog{sc.branch_log ? sc.branch_log + (size_t)pix * 2 + 1 : nullptr};   // test aid (orc_scene.h)
+    if (blog.word) *blog.word = 0u;
 
     Rng rng = init_rng(px, py, pc.frame_count, W);                   // :37
     V3 total_radiance = v3(0.0f);
@@ -391,7 +459,7 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
             if (!prev_did_nee) radiance += emission * throughput;    // :99-101
             prev_did_nee = false;
             float brightness = max_comp(emission);
-            if (brightness > 1.0f) break;                            // :104
+            if (brightness > 1.0f) { blog(F_BRIGHT_BREAK); break; }  // :104
 
             if (transmission > 0.5f) {                               // :106-133
                 bool is_inside = dot(rayDir, hit_normal) > 0.0f;
@@ -402,8 +470,10 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                 R0 = R0 * R0;
                 float fresnel = R0 + (1.0f - R0) * pow5(1.0f - cos_theta);
                 V3 refracted = refract(rayDir, N, eta);
-                if (length(refracted) < 0.01f) fresnel = 1.0f;
-                if (rnd(rng) < fresnel) rayDir = reflect(rayDir, N);
+                if (length(refracted) < 0.01f) { fresnel = 1.0f; blog(F_TIR); }
+                const bool reflects = rnd(rng) < fresnel;
+                blog(reflects ? F_REFLECT : (is_inside ? F_REFRACT_OUT : F_REFRACT_IN));
+                if (reflects) rayDir = reflect(rayDir, N);
                 else {
                     rayDir = refracted;
                     if (is_inside) {
@@ -416,17 +486,21 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                 continue;
             }
 
+            if (num_lights == 0) blog(F_NO_LIGHTS);
             if (num_lights > 0 && bounce < SHADOW_BOUNCES) {         // :135
                 if (!restir_evaluated && roughness > 0.2f) {         // :136
                     restir_evaluated = true;
                     SrReservoir center_r = reservoir_cur[pix];       // :139-140
                     SrReservoir spatial_r = empty_reservoir();
+                    bool di_sample_taken = false;
+                    if (center_r.W > 0.0f && !(center_r.light_idx < num_lights)) blog(F_CENTER_IDX_OUT);
                     if (center_r.W > 0.0f && center_r.light_idx < num_lights) {  // :151-158
+                        blog(F_CENTER_MERGED);
                         center_r.light_idx = center_r.light_idx < num_lights - 1 ? center_r.light_idx : num_lights - 1;
                         V3 f_y_center = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
                                                               A3(cx.light_of(center_r.light_idx).emission), A3(center_r.light_pos), A3(center_r.light_normal));
                         float p_hat_center = max_comp(f_y_center);
-                        merge_reservoirs(spatial_r, center_r, p_hat_center, rnd(rng));
+                        if (merge_reservoirs(spatial_r, center_r, p_hat_center, rnd(rng))) di_sample_taken = true;
                     }
                     const int SPATIAL_SAMPLES = 5;
                     const float SPATIAL_RADIUS = 30.0f;
@@ -441,19 +515,22 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                         V3 neighbor_normal = load_normal(pc, pi_n);
                         float neighbor_depth = load_depth(pc, pi_n);
                         if (dot(hit_normal, neighbor_normal) < 0.9f) continue;
-                        if (fabsf(current_depth - neighbor_depth) > 0.1f * current_depth) continue;
+                        if (fabsf(current_depth - neighbor_depth) > 0.1f * current_depth) { blog(F_NEIGHBOR_DEPTH_REJECT); continue; }
                         SrReservoir neighbor_r = reservoir_cur[pi_n];
                         neighbor_r.W = min_f(neighbor_r.W, 20.0f);
                         neighbor_r.M = min_f(neighbor_r.M, 10.0f);
+                        if (neighbor_r.W > 0.0f && !(neighbor_r.light_idx < num_lights)) blog(F_NEIGHBOR_IDX_OUT);
                         if (neighbor_r.W > 0.0f && neighbor_r.light_idx < num_lights) {
+                            blog(F_NEIGHBOR_MERGED);
                             neighbor_r.light_idx = neighbor_r.light_idx < num_lights - 1 ? neighbor_r.light_idx : num_lights - 1;
                             V3 f_y_neighbor = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
                                                                     A3(cx.light_of(neighbor_r.light_idx).emission), A3(neighbor_r.light_pos), A3(neighbor_r.light_normal));
                             float p_hat_neighbor = max_comp(f_y_neighbor);
-                            merge_reservoirs(spatial_r, neighbor_r, p_hat_neighbor, rnd(rng));
+                            if (merge_reservoirs(spatial_r, neighbor_r, p_hat_neighbor, rnd(rng))) di_sample_taken = true;
                         }
                     }
                     if (spatial_r.w_sum > 0.0f) {                    // :190-222
+                        if (!di_sample_taken) blog(F_DI_ZERO_SAMPLE);   // weights were merged, no sample was: position and normal are still zero
                         V3 f_y_winner = eval_unshadowed_light(hitPos, hit_normal, V_view, hit_albedo, roughness, metallic,
                                                               A3(cx.light_of(spatial_r.light_idx).emission), A3(spatial_r.light_pos), A3(spatial_r.light_normal));
                         float p_hat_winner = max_comp(f_y_winner);
@@ -462,6 +539,7 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                         V3 shadow_dir = A3(spatial_r.light_pos) - hitPos;
                         float shadow_dist = max_f(length(shadow_dir), 0.0001f);
                         shadow_dir /= shadow_dist;
+                        blog(dot(hit_normal, shadow_dir) > 0.0f ? F_DI_QUERY : F_DI_BEHIND);
                         if (dot(hit_normal, shadow_dir) > 0.0f) {
                             prd.dist = cx.shadow(hitPos, shadow_dir, shadow_dist);  // origin = bare hitPos (:208)
                             if (prd.dist < 0.0f) radiance += f_y_winner * throughput * spatial_r.W;
@@ -470,6 +548,7 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                     }
                     // ReSTIR GI spatial reuse (:224-327)
                     SrReservoirGI combined = reservoir_gi_cur[pix];
+                    bool gi_sample_from_neighbor = false;
                     const int GI_SPATIAL_SAMPLES = 3;
                     const float GI_SPATIAL_RADIUS = 20.0f;
                     float gi_current_depth = length(hitPos - origin);
@@ -478,7 +557,7 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                         float gi_radius = sqrtf(rnd(rng)) * GI_SPATIAL_RADIUS;
                         float sa, ca; sincos_f(gi_angle, &sa, &ca);
                         int ncx = ipx + (int)(ca * gi_radius), ncy = ipy + (int)(sa * gi_radius);
-                        if (ncx == ipx && ncy == ipy) continue;      // :237
+                        if (ncx == ipx && ncy == ipy) { blog(F_GI_SELF); continue; }   // :237
                         if (ncx < 0 || ncy < 0 || ncx >= (int)W || ncy >= (int)H) continue;
                         uint32_t pi_nn = (uint32_t)ncy * W + (uint32_t)ncx;
                         V3 neighbor_normal = load_normal(pc, pi_nn);
@@ -499,15 +578,18 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                         V3 n_x2 = unpack_normal(neighbor_r.sample_normal_packed);
                         float cos_new = max_f(dot(n_x2, -w_new / d_new), 0.0f);
                         float cos_old = max_f(dot(n_x2, -w_old / d_old), 0.0f);
-                        if (cos_new <= 0.0f || cos_old <= 0.0f) continue;
+                        if (cos_new <= 0.0f || cos_old <= 0.0f) { blog(F_GI_COS_ZERO); continue; }
                         float jacobian = (cos_new * d_old * d_old) / max_f(cos_old * d_new * d_new, 1e-4f);
+                        if (jacobian > 10.0f) blog(F_GI_JACOBIAN_CLAMPED);
                         jacobian = clamp_f(jacobian, 0.0f, 10.0f);
                         V3 gi_spatial_dir = w_new / d_new;
                         if (dot(hit_normal, gi_spatial_dir) <= 0.0f) continue;
+                        if (!(d_new > 0.002f)) blog(F_GI_SHORT);
                         prd.dist = cx.shadow(hitPos, gi_spatial_dir, d_new);  // :276-286
                         if (prd.dist >= 0.0f) continue;
                         float p_hat_neighbor = gi_target_pdf(hitPos, hit_normal, hit_albedo, metallic, A3(neighbor_r.sample_pos), A3(neighbor_r.sample_radiance));
-                        merge_reservoirs_gi(combined, neighbor_r, p_hat_neighbor, jacobian, rnd(rng));
+                        blog(F_GI_MERGED);
+                        if (merge_reservoirs_gi(combined, neighbor_r, p_hat_neighbor, jacobian, rnd(rng))) gi_sample_from_neighbor = true;
                     }
                     float p_hat_final = gi_target_pdf(hitPos, hit_normal, hit_albedo, metallic, A3(combined.sample_pos), A3(combined.sample_radiance));
                     combined.W = (p_hat_final > 1e-3f) ? (combined.w_sum / max_f(combined.M, 1.0f) / p_hat_final) : 0.0f;
@@ -517,7 +599,10 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                         float gi_x2_dist = max_f(length(gi_x2_dir), 0.0001f);
                         gi_x2_dir /= gi_x2_dist;
                         float gi_NdotL = max_f(dot(hit_normal, gi_x2_dir), 0.0f);
+                        blog(gi_NdotL > 0.0f ? F_GIF_QUERY : F_GIF_BEHIND);
                         if (gi_NdotL > 0.0f) {
+                            if (gi_sample_from_neighbor) blog(F_GIF_REPEAT);   // the segment :276-286 asked about a moment ago
+                            if (!(gi_x2_dist > 0.002f)) blog(F_GIF_SHORT);
                             prd.dist = cx.shadow(hitPos, gi_x2_dir, gi_x2_dist);
                             if (prd.dist < 0.0f) {
                                 V3 gi_f_diffuse = hit_albedo * (1.0f - metallic) / 3.14159f;
@@ -528,6 +613,7 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                     break;  // :327
                 } else if (restir_evaluated && roughness > 0.2f) {   // :328-382 plain NEE
                     uint32_t light_idx = (uint32_t)(rnd(rng) * (float)num_lights);
+                    blog(light_idx > num_lights - 1 ? F_NEE_IDX_CLAMPED : F_NEE_IDX_IN_RANGE);
                     if (light_idx > num_lights - 1) light_idx = num_lights - 1;
                     const SrEmissiveIndirectionEntry& entry = sc.indirection[light_idx];
                     const SrEmissiveTriangle& light = sc.emissive_tris[entry.blas_tri_index];
@@ -577,8 +663,11 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                 r2 = rnd(rng);
             }
             if (rnd(rng) < p_specular) {
-                V3 Hh = sample_ggx_vndf(N, V_view, roughness, r1, r2);
+                bool head_on = false;
+                V3 Hh = sample_ggx_vndf(N, V_view, roughness, r1, r2, blog.word ? &head_on : nullptr);
+                if (head_on) blog(F_VNDF_HEAD_ON);
                 rayDir = reflect(-V_view, Hh);
+                blog(dot(N, rayDir) <= 0.0f ? F_VNDF_BELOW : F_VNDF_ABOVE);
                 if (dot(N, rayDir) <= 0.0f) {
                     rayDir = get_random_bounce(N, r1, r2);
                     throughput *= hit_albedo * (1.0f - metallic) * (1.0f - F) / (1.0f - p_specular);
@@ -589,13 +678,16 @@ void final_pixel(Ctx& cx, uint32_t px, uint32_t py) {
                     throughput *= (F * G1_L) / p_specular;
                 }
             } else {
+                blog(F_DIFFUSE_BOUNCE);
                 rayDir = get_random_bounce(N, r1, r2);
                 throughput *= hit_albedo * (1.0f - metallic) * (1.0f - F) / (1.0f - p_specular);
             }
             float p = max_comp(throughput);
-            if (p < 0.001f) break;
+            if (p < 0.001f) { blog(F_THROUGHPUT_BREAK); break; }
             if (bounce > 2) {
-                if (rnd(rng) > p) break;
+                const bool dies = rnd(rng) > p;
+                blog(dies ? F_RR_DIE : F_RR_SURVIVE);
+                if (dies) break;
                 throughput /= p;
             }
             rayOrigin = hitPos + hit_normal * 0.001f;                // :427

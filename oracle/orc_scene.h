@@ -70,6 +70,10 @@ struct Scene {
     // kNoRead where the temporal branch is not taken. Unset: nothing is recorded and nothing changes.
     static constexpr int32_t kNoRead = INT32_MIN;
     int32_t* read_log = nullptr;
+    // Test aid, not in the reference: when set (2 * width * height words), each pass ORs into its word of the pixel (trace_ris word
+    // 0, trace_final word 1, cleared when the pixel starts) one bit per branch outcome it takes; the bits are named in
+    // oracle/binding.py (RIS_BITS, FINAL_BITS) in the order of the enums below. Unset: nothing is recorded and nothing changes.
+    uint32_t* branch_log = nullptr;
 
     int add_mesh(uint64_t key, const SrVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, const SrMaterial* m);
     int add_blas(uint64_t key, const SrVertex* v, uint32_t nv, const uint32_t* idx, uint32_t ni, const SrMaterial* m,

@@ -106,13 +106,15 @@ static inline V3 get_random_bounce(V3 normal, float r1, float r2) {
     return normalize(u * c * r + v * s * r + normal * sqrtf(1.0f - r2));
 }
 // rt_utils.slang:179-201
-static inline V3 sample_ggx_vndf(V3 normal, V3 V_world, float roughness, float r1, float r2) {
+// `head_on` (test aid, may be null): receives whether the view vector had no tangential part (lensq == 0).
+static inline V3 sample_ggx_vndf(V3 normal, V3 V_world, float roughness, float r1, float r2, bool* head_on = nullptr) {
     V3 T, B;
     build_onb(normal, T, B);
     V3 Vl = v3(dot(V_world, T), dot(V_world, B), dot(V_world, normal));
     float a = max_f(roughness * roughness, 0.001f);
     V3 Vh = normalize(v3(a * Vl.x, a * Vl.y, Vl.z));
     float lensq = Vh.x * Vh.x + Vh.y * Vh.y;
+    if (head_on) *head_on = !(lensq > 0.0f);
     V3 T1 = lensq > 0.0f ? v3(-Vh.y, Vh.x, 0.0f) * (1.0f / sqrtf(lensq)) : v3(1.0f, 0.0f, 0.0f);
     V3 T2 = cross(Vh, T1);
     float rr = sqrtf(r1);
@@ -153,15 +155,17 @@ static inline V3 eval_unshadowed_light(V3 hit_pos, V3 hit_normal, V3 V_view, V3 
     float geometry = (NdotL * cos_light) / max_f(dist * dist, 0.0001f);
     return emission * (diffuse_brdf + specular_brdf) * geometry;
 }
-// rt_utils.slang:244-253
-static inline void merge_reservoirs(SrReservoir& r, const SrReservoir& new_r, float p_hat_new, float random_val) {
+// rt_utils.slang:244-253. Returns whether the new sample was taken (the shader's function returns nothing; the branch log asks).
+static inline bool merge_reservoirs(SrReservoir& r, const SrReservoir& new_r, float p_hat_new, float random_val) {
     r.M += new_r.M;
     float weight = p_hat_new * new_r.W * new_r.M;
     r.w_sum += weight;
     if (random_val < (weight / max_f(r.w_sum, 0.0001f))) {
         r.light_idx = new_r.light_idx;
         for (int i = 0; i < 3; i++) { r.light_pos[i] = new_r.light_pos[i]; r.light_normal[i] = new_r.light_normal[i]; }
+        return true;
     }
+    return false;
 }
 // rt_utils.slang:255-263
 static inline float gi_target_pdf(V3 shade_pos, V3 shade_normal, V3 albedo, float metallic, V3 sample_pos, V3 sample_radiance) {
@@ -173,15 +177,17 @@ static inline float gi_target_pdf(V3 shade_pos, V3 shade_normal, V3 albedo, floa
     V3 contrib = sample_radiance * f_diffuse * NdotL;
     return max_comp(contrib);
 }
-// rt_utils.slang:265-274
-static inline void merge_reservoirs_gi(SrReservoirGI& r, const SrReservoirGI& new_r, float p_hat_new, float jacobian, float random_val) {
+// rt_utils.slang:265-274. Returns whether the new sample was taken, as merge_reservoirs does.
+static inline bool merge_reservoirs_gi(SrReservoirGI& r, const SrReservoirGI& new_r, float p_hat_new, float jacobian, float random_val) {
     r.M += new_r.M;
     float weight = p_hat_new * new_r.W * new_r.M * jacobian;
     r.w_sum += weight;
     if (random_val < (weight / max_f(r.w_sum, 0.0001f))) {
         for (int i = 0; i < 3; i++) { r.sample_pos[i] = new_r.sample_pos[i]; r.sample_radiance[i] = new_r.sample_radiance[i]; }
         r.sample_normal_packed = new_r.sample_normal_packed;
+        return true;
     }
+    return false;
 }
 // rt_utils.slang:278-281: rows of a 3x4 row-major transform dotted with (p,1).
 static inline V3 transform_point(const SrTransform& x, V3 p) {
