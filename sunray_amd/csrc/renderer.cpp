@@ -2,8 +2,10 @@
 // path, layered purely on this library's own C ABI (sr_scene_*, sr_trace_*, sr_post_*):
 //   new / resize / load_mesh / unload_mesh / render / wait_frame / render_to_host_memory
 // (src/lib.rs:212-446, 586-639, 873-973, 984-1238, 1908-1934). Keys are u64 (the reference's generic
-// ResourceKey, lib.rs:54-58). One Renderer = one GPU, one caller thread (the reference is !Send); a renderer made by
-// sr_renderer_create_multi adds device slots (multi_renderer.cpp), to which every scene-changing call here fans out.
+// ResourceKey, lib.rs:54-58). One Renderer = one caller thread (the reference is !Send) and one device slot per GPU it
+// renders on (renderer.h): one from sr_renderer_create, one per device from sr_renderer_create_multi.
+// Here: the lifetime of the renderer and its slots, the scene-changing calls fanned out to every slot, frame submission and its
+// bookkeeping (multi_renderer.cpp: the frame itself on the slots).
 #include <hip/hip_runtime.h>
 
 #include <array>
@@ -26,18 +28,8 @@ struct SrLoadedScene {
 
 namespace {
 
-int rfail(int code, const std::string& msg) { return srh::set_error(code, msg); }
-#define R_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return rfail(e_ == hipErrorOutOfMemory ? SR_ERR_OOM : SR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-
-void free_images(SrRenderer* r) {
-    void* ptrs[] = {r->raw_color[0], r->raw_color[1], r->depth[0], r->depth[1], r->normal[0], r->normal[1], r->diffuse[0], r->diffuse[1],
-                    r->motion[0], r->motion[1], r->reservoirs[0], r->reservoirs[1], r->reservoirs_gi[0], r->reservoirs_gi[1], r->accum[0],
-                    r->accum[1], r->denoise[0], r->denoise[1], r->output[0], r->output[1], r->primary[0], r->primary[1]};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (int k = 0; k < 2; k++) { r->primary[k] = nullptr; r->raw_color[k] = nullptr; r->depth[k] = nullptr; r->normal[k] = r->diffuse[k] = r->motion[k] = nullptr; r->output[k] = nullptr; }
-    r->reservoirs[0] = r->reservoirs[1] = nullptr; r->reservoirs_gi[0] = r->reservoirs_gi[1] = nullptr;
-    r->accum[0] = r->accum[1] = r->denoise[0] = r->denoise[1] = nullptr;
-}
+template <typename T>
+void free_ptr(T*& p) { if (p) (void)hipFree(p); p = nullptr; }
 
 template <typename T>
 int alloc_zero(T** p, size_t n) {
@@ -46,26 +38,154 @@ int alloc_zero(T** p, size_t n) {
     return SR_OK;
 }
 
-int alloc_images(SrRenderer* r, uint32_t w, uint32_t h) {
+// The frame buffers of slot `s`: what the two passes write and read; with slot 0, the renderer's post-chain images.
+void free_images(SrRenderer* r, Slot& s) {
+    for (int k = 0; k < 2; k++) {
+        free_ptr(s.raw_color[k]); free_ptr(s.depth[k]); free_ptr(s.normal[k]); free_ptr(s.diffuse[k]); free_ptr(s.motion[k]);
+        free_ptr(s.reservoirs[k]); free_ptr(s.reservoirs_gi[k]); free_ptr(s.primary[k]);
+        if (&s == &r->slot[0]) { free_ptr(r->accum[k]); free_ptr(r->denoise[k]); free_ptr(r->output[k]); }
+    }
+}
+
+int alloc_images(SrRenderer* r, Slot& s, uint32_t w, uint32_t h) {
     const size_t n = (size_t)w * h;
-    int rc;
-    for (int i = 0; i < 2; i++)
-        if ((rc = alloc_zero(&r->raw_color[i], n * 4)) || (rc = alloc_zero(&r->depth[i], n)) || (rc = alloc_zero(&r->normal[i], n)) ||
-            (rc = alloc_zero(&r->diffuse[i], n)) || (rc = alloc_zero(&r->motion[i], n)) || (rc = alloc_zero(&r->output[i], n)) ||
-            (r->primary_reuse && (rc = alloc_zero(&r->primary[i], n)))) return rc;
-    for (int i = 0; i < 2; i++)
-        if ((rc = alloc_zero(&r->reservoirs[i], n)) || (rc = alloc_zero(&r->reservoirs_gi[i], n)) ||
-            (rc = alloc_zero(&r->accum[i], n)) || (rc = alloc_zero(&r->denoise[i], n))) return rc;
-    r->width = w; r->height = h;
+    const bool post = &s == &r->slot[0];
+    R_HIP(hipSetDevice(s.device));
+    for (int k = 0; k < 2; k++) {                                  // the two per-frame sets ...
+        R_RC(alloc_zero(&s.raw_color[k], n * 4)); R_RC(alloc_zero(&s.depth[k], n)); R_RC(alloc_zero(&s.normal[k], n));
+        R_RC(alloc_zero(&s.diffuse[k], n)); R_RC(alloc_zero(&s.motion[k], n));
+        if (post) R_RC(alloc_zero(&r->output[k], n));
+        if (r->primary_reuse) R_RC(alloc_zero(&s.primary[k], n));
+    }
+    for (int k = 0; k < 2; k++) {                                  // ... then the ping-pongs that carry history
+        R_RC(alloc_zero(&s.reservoirs[k], n)); R_RC(alloc_zero(&s.reservoirs_gi[k], n));
+        if (post) { R_RC(alloc_zero(&r->accum[k], n)); R_RC(alloc_zero(&r->denoise[k], n)); }
+    }
     return SR_OK;
 }
 
-// `call` on every replica scene in slot order, stopping at the first refusal. The replicas hold the same meshes and settings,
+// A noise texture of the caller's (host memory) in place of the one slot `s` holds; s.device is the current device.
+int upload_noise(Slot& s, const uint8_t* rgba8, uint32_t w, uint32_t h) {
+    uint8_t* fresh = nullptr;
+    const size_t bytes = (size_t)w * h * 4;
+    R_HIP(hipMalloc((void**)&fresh, bytes));
+    if (hipMemcpy(fresh, rgba8, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(fresh); return rfail(SR_ERR_HIP, "Renderer: blue-noise upload failed"); }
+    free_ptr(s.blue_noise);
+    s.blue_noise = fresh; s.noise_w = w; s.noise_h = h;
+    return SR_OK;
+}
+
+// Slot `s` on s.device: its scene, frame buffers at the renderer's extent, the noise texture, streams and events.
+int create_slot(SrRenderer* r, Slot& s, const std::vector<uint8_t>& noise) {
+    R_RC(sr_scene_create(s.device, &s.scene));
+    R_RC(alloc_images(r, s, r->width, r->height));
+    R_RC(upload_noise(s, noise.data(), 128, 128));
+    R_HIP(hipStreamCreateWithFlags(&s.s_ris, hipStreamNonBlocking));
+    R_HIP(hipStreamCreateWithFlags(&s.s_final, hipStreamNonBlocking));
+    for (int k = 0; k < 2; k++) {
+        R_HIP(hipEventCreateWithFlags(&s.ev_ris[k], hipEventDisableTiming));
+        R_HIP(hipEventCreateWithFlags(&s.ev_done[k], hipEventDisableTiming));
+    }
+    return SR_OK;
+}
+
+// Everything create_slot and create_strip_extras made, or as much of it as there is; the slot's device is idle.
+void destroy_slot(SrRenderer* r, Slot& s) {
+    (void)hipSetDevice(s.device);
+    free_images(r, s);
+    free_ptr(s.blue_noise);
+    free_ptr(s.overflow);
+    for (hipEvent_t e : {s.ev_ris[0], s.ev_ris[1], s.ev_done[0], s.ev_done[1], s.ev_copy[0], s.ev_copy[1]}) if (e) (void)hipEventDestroy(e);
+    if (s.s_ris) (void)hipStreamDestroy(s.s_ris);
+    if (s.s_final) (void)hipStreamDestroy(s.s_final);
+    sr_scene_destroy(s.scene);
+}
+
+// Peer access between every pair of distinct devices the slots use, where the platform allows it ("already enabled" is fine).
+int enable_peer_access(const SrRenderer* r) {
+    for (const Slot& sa : r->slot)
+        for (const Slot& sb : r->slot) {
+            const int a = sa.device, b = sb.device;
+            if (a == b) continue;
+            int can = 0;
+            R_HIP(hipDeviceCanAccessPeer(&can, a, b));
+            if (!can) continue;
+            R_HIP(hipSetDevice(a));
+            const hipError_t e = hipDeviceEnablePeerAccess(b, 0);
+            if (e == hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+            else if (e != hipSuccess) return rfail(SR_ERR_HIP, std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
+        }
+    return SR_OK;
+}
+
+// The history-reach counters of a renderer with several slots start again from zero (create, resize).
+int reset_overflow(SrRenderer* r) {
+    for (Slot& s : r->slot) {
+        if (!s.overflow) continue;
+        R_HIP(hipSetDevice(s.device));
+        R_HIP(hipMemset(s.overflow, 0, sizeof(unsigned long long)));
+    }
+    return SR_OK;
+}
+
+// What only a renderer with several slots needs of each: the history-reach counter and the gather-copy events.
+int create_strip_extras(SrRenderer* r) {
+    for (Slot& s : r->slot) {
+        R_HIP(hipSetDevice(s.device));
+        R_HIP(hipMalloc((void**)&s.overflow, sizeof(unsigned long long)));
+        for (int k = 0; k < 2; k++) R_HIP(hipEventCreateWithFlags(&s.ev_copy[k], hipEventDisableTiming));
+    }
+    return reset_overflow(r);
+}
+
+// All of a new renderer that can fail, slot 0 first; what a failure leaves half made, sr_renderer_destroy takes down.
+int create_slots(SrRenderer* r) {
+    std::vector<uint8_t> noise(128 * 128 * 4);
+    sr_default_noise_texture(128, 128, 7, noise.data());
+    R_RC(create_slot(r, r->slot[0], noise));
+    R_HIP(hipEventCreateWithFlags(&r->ev_in, hipEventDisableTiming));
+    R_RC(enable_peer_access(r));
+    for (size_t i = 1; i < r->slot.size(); i++) R_RC(create_slot(r, r->slot[i], noise));
+    if (r->slot.size() > 1) R_RC(create_strip_extras(r));
+    R_RC(sr_partition_create(r->width, r->height, (uint32_t)r->slot.size(), r->strip_axis, nullptr, &r->part));
+    R_HIP(hipSetDevice(r->device));
+    return SR_OK;
+}
+
+// Renderer::new((w, h), RGBA8_UNORM) (lib.rs:212-446) on one slot per entry of `devices` (the same device may hold several).
+int create_renderer(const int* devices, uint32_t n_devices, uint32_t width, uint32_t height, uint32_t axis, SrRenderer** out) {
+    SrRenderer* r = new SrRenderer();
+    r->device = devices[0];
+    r->width = width; r->height = height;
+    r->strip_axis = axis;
+    r->slot.resize(n_devices);
+    for (uint32_t i = 0; i < n_devices; i++) r->slot[i].device = devices[i];
+    memset(r->prev_view_proj, 0, sizeof(r->prev_view_proj));
+    sr_trace_config_default(&r->config);
+    if (const char* ev = getenv("SR_PRIMARY_REUSE")) r->primary_reuse = atoi(ev) != 0;
+    const int rc = create_slots(r);
+    if (rc != SR_OK) {
+        const std::string msg = sr_last_error();
+        sr_renderer_destroy(r);
+        return rfail(rc, msg);
+    }
+    *out = r;
+    return SR_OK;
+}
+
+// After a call that handed out an image / sampler slot on every scene: SR_ERR_STATE unless they are all equal.
+int check_same_slots(const std::vector<uint32_t>& slots, const char* what) {
+    for (uint32_t s : slots)
+        if (s != slots[0]) return rfail(SR_ERR_STATE, std::string(what) + " slots differ between the replicas");
+    return SR_OK;
+}
+
+// `call` on every slot's scene in slot order, stopping at the first refusal. The replicas hold the same meshes and settings,
 // so what one refuses on validation the first one refuses, and none has changed.
 template <class Call>
 int each_scene(SrRenderer* r, Call call) {
-    for (SrScene* sc : srmr::scenes(r))
-        if (const int rc = call(sc); rc != SR_OK) return rc;
+    for (Slot& s : r->slot)
+        if (const int rc = call(s.scene); rc != SR_OK) return rc;
     return SR_OK;
 }
 
@@ -75,12 +195,11 @@ int each_scene(SrRenderer* r, Call call) {
 // What the first scene refuses changes none, and leaves the instance list as valid as it was.
 template <class Produce>
 int first_scene_produces(SrRenderer* r, uint64_t key, const SrVertex* src, uint32_t n_vertices, Produce produce) {
-    const std::vector<SrScene*> scenes = srmr::scenes(r);
-    int rc = produce(scenes[0]);
+    int rc = produce(r->slot[0].scene);
     if (rc != SR_OK) return rc;
     r->instances_valid = false;
-    if (!src) src = srh::scene_skinned_vertices(scenes[0], key, &n_vertices);
-    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_take_device_vertices(scenes[i], key, src, n_vertices, r->device);
+    if (!src) src = srh::scene_skinned_vertices(r->slot[0].scene, key, &n_vertices);
+    for (size_t i = 1; rc == SR_OK && i < r->slot.size(); i++) rc = srh::scene_take_device_vertices(r->slot[i].scene, key, src, n_vertices, r->device);
     return rc;
 }
 
@@ -100,6 +219,14 @@ int check_scene_of_file(const SrRenderer* r, const SrGltf* g, const SrLoadedScen
 uint32_t pcg_hash(uint32_t x) { x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16; return x; }
 
 }  // namespace
+
+int srr::sync_all(SrRenderer* r) {
+    for (const Slot& s : r->slot) {
+        R_HIP(hipSetDevice(s.device));
+        R_HIP(hipDeviceSynchronize());
+    }
+    return SR_OK;
+}
 
 extern "C" {
 
@@ -121,65 +248,60 @@ int sr_default_noise_texture(uint32_t w, uint32_t h, uint32_t seed, uint8_t* out
 // Renderer::new((w, h), RGBA8_UNORM) (lib.rs:212-446)
 int sr_renderer_create(int device, uint32_t width, uint32_t height, SrRenderer** out) {
     if (!out || width == 0 || height == 0) return rfail(SR_ERR_INVALID_ARG, "Renderer::new: empty extent or null out");
-    SrRenderer* r = new SrRenderer();
-    r->device = device;
-    memset(r->prev_view_proj, 0, sizeof(r->prev_view_proj));
-    sr_trace_config_default(&r->config);
-    if (const char* ev = getenv("SR_PRIMARY_REUSE")) r->primary_reuse = atoi(ev) != 0;
-    int rc = sr_scene_create(device, &r->scene);
-    if (rc != SR_OK) { delete r; return rc; }
-    if ((rc = alloc_images(r, width, height)) != SR_OK) { free_images(r); sr_scene_destroy(r->scene); delete r; return rc; }
-    std::vector<uint8_t> noise(128 * 128 * 4);
-    sr_default_noise_texture(128, 128, 7, noise.data());
-    if (hipMalloc((void**)&r->blue_noise, noise.size()) != hipSuccess || hipMemcpy(r->blue_noise, noise.data(), noise.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipStreamCreateWithFlags(&r->s_ris, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&r->s_final, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&r->ev_in, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&r->ev_ris[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&r->ev_ris[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&r->ev_done[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&r->ev_done[1], hipEventDisableTiming) != hipSuccess) {
-        free_images(r); sr_scene_destroy(r->scene); delete r;
-        return rfail(SR_ERR_HIP, "Renderer::new: blue-noise upload failed");
-    }
-    *out = r;
-    return SR_OK;
+    return create_renderer(&device, 1, width, height, SR_AXIS_COLS, out);
+}
+
+// The same on one slot per entry of `devices`, the frame cut into strips along `axis`.
+int sr_renderer_create_multi(const int* devices, uint32_t n_devices, uint32_t width, uint32_t height, uint32_t axis, SrRenderer** out) {
+    if (!devices || !out || n_devices == 0 || width == 0 || height == 0)
+        return rfail(SR_ERR_INVALID_ARG, "sr_renderer_create_multi: null argument, no devices or empty extent");
+    if (axis != SR_AXIS_COLS && axis != SR_AXIS_ROWS) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_create_multi: axis must be SR_AXIS_COLS or SR_AXIS_ROWS");
+    for (uint32_t i = 0; i < n_devices; i++)
+        if (devices[i] < 0) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_create_multi: negative device index");
+    return create_renderer(devices, n_devices, width, height, axis, out);
 }
 
 int sr_renderer_set_blue_noise(SrRenderer* r, const uint8_t* rgba8, uint32_t w, uint32_t h) {
     if (!r || !rgba8 || w == 0 || h == 0 || w > 16384 || h > 16384) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_blue_noise: bad argument");
-    if (hipSetDevice(r->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return rfail(SR_ERR_HIP, "sr_renderer_set_blue_noise: device");
-    uint8_t* fresh = nullptr;
-    const size_t bytes = (size_t)w * h * 4;
-    if (hipMalloc((void**)&fresh, bytes) != hipSuccess) return rfail(SR_ERR_HIP, "sr_renderer_set_blue_noise: out of device memory");
-    if (hipMemcpy(fresh, rgba8, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(fresh); return rfail(SR_ERR_HIP, "sr_renderer_set_blue_noise: upload failed"); }
-    if (r->blue_noise) (void)hipFree(r->blue_noise);
-    r->blue_noise = fresh; r->noise_w = w; r->noise_h = h;
-    return r->multi ? srmr::set_blue_noise(r, rgba8, w, h) : SR_OK;
+    for (Slot& s : r->slot) {
+        if (hipSetDevice(s.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return rfail(SR_ERR_HIP, "sr_renderer_set_blue_noise: device");
+        R_RC(upload_noise(s, rgba8, w, h));
+    }
+    R_HIP(hipSetDevice(r->device));
+    return SR_OK;
 }
 
 int sr_renderer_destroy(SrRenderer* r) {
     if (!r) return SR_OK;
-    if (r->multi) srmr::destroy(r);                              // synchronises and frees every other slot first
-    (void)hipSetDevice(r->device);
-    (void)hipDeviceSynchronize();
-    free_images(r);
-    if (r->blue_noise) (void)hipFree(r->blue_noise);
-    for (hipEvent_t e : {r->ev_in, r->ev_ris[0], r->ev_ris[1], r->ev_done[0], r->ev_done[1]}) if (e) (void)hipEventDestroy(e);
-    if (r->s_ris) (void)hipStreamDestroy(r->s_ris);
-    if (r->s_final) (void)hipStreamDestroy(r->s_final);
-    sr_scene_destroy(r->scene);
+    for (const Slot& s : r->slot)
+        if (hipSetDevice(s.device) == hipSuccess) (void)hipDeviceSynchronize();
+    srr::free_transfers(r);
+    for (Slot& s : r->slot) destroy_slot(r, s);
+    if (r->ev_in) (void)hipEventDestroy(r->ev_in);
+    sr_partition_destroy(r->part);
     delete r;
     return SR_OK;
 }
 
-// Renderer::resize (lib.rs:586-639): new temporal resources, relative_frame_count = 0
+// Renderer::resize (lib.rs:586-639): new temporal resources, relative_frame_count = 0; the strips are cut equally again
 int sr_renderer_resize(SrRenderer* r, uint32_t width, uint32_t height) {
     if (!r || width == 0 || height == 0) return rfail(SR_ERR_INVALID_ARG, "Renderer::resize: bad argument");
     if (!(width == r->width && height == r->height)) {            // resize_internal_images returns early for an unchanged extent (lib.rs:598-600)
+        R_RC(srr::sync_all(r));                                   // device_wait_idle (lib.rs:604), on every slot's device
+        srr::free_transfers(r);
+        r->width = r->height = 0;                                 // a failure below leaves no extent: nothing renders until a resize succeeds
+        for (Slot& s : r->slot) {
+            free_images(r, s);
+            R_RC(alloc_images(r, s, width, height));
+        }
+        SrPartition* p = nullptr;
+        R_RC(sr_partition_create(width, height, (uint32_t)r->slot.size(), r->strip_axis, nullptr, &p));
+        sr_partition_destroy(r->part);
+        r->part = p;
+        r->plan_dirty = true;
+        r->width = width; r->height = height;
+        R_RC(reset_overflow(r));
         R_HIP(hipSetDevice(r->device));
-        R_HIP(hipDeviceSynchronize());                            // device_wait_idle (lib.rs:604)
-        free_images(r);
-        int rc = alloc_images(r, width, height);
-        if (rc != SR_OK) return rc;
-        if (r->multi && (rc = srmr::resize(r, width, height)) != SR_OK) return rc;
         r->relative_frame_count = 0;
     }
     for (auto& cb : r->resize_callbacks) cb.first(cb.second, width, height);   // every resize call, changed extent or not (lib.rs:590-592)
@@ -216,7 +338,7 @@ void run_frame_callbacks(SrRenderer* r, uint64_t upcoming_frame) {
     }
     // the frame timeline: frames complete in order; a set's ev_done is the completion of the frame last rendered into it
     for (int k = 0; k < 2; k++)
-        if (r->frame_of_set[k] > r->completed_frame && hipEventQuery(r->ev_done[k]) == hipSuccess) r->completed_frame = r->frame_of_set[k];
+        if (r->frame_of_set[k] > r->completed_frame && hipEventQuery(r->slot[0].ev_done[k]) == hipSuccess) r->completed_frame = r->frame_of_set[k];
     for (size_t i = 0; i < r->end_of_frame_callbacks.size();) {
         if (r->end_of_frame_callbacks[i].frame <= r->completed_frame) {
             const SrRenderer::FrameCb cb = r->end_of_frame_callbacks[i];
@@ -247,7 +369,7 @@ int render_passes(SrRenderer* r, const float cam_pos[3], const float cam_target[
 
 // Renderer::render (lib.rs:984-1232): one frame = TLAS (re)build when the instance list changed ->
 // raytracing_ris -> raytracing_final -> temporal_accumulation -> denoise_0..3 -> postprocess, enqueued on the
-// renderer's own two streams after whatever the caller has enqueued on `stream`; returns the frame number to wait
+// renderer's own streams (two per slot, srr::render_frame) after whatever the caller has enqueued on `stream`; returns the frame number to wait
 // on. Two frames may be in flight (MAX_FRAMES_IN_FLIGHT, lib.rs:71): submit frame f+1 before waiting for frame f and
 // its RIS pass overlaps frame f's final pass and post chain. Results equal back-to-back execution.
 int sr_renderer_render(SrRenderer* r, const float cam_pos[3], const float cam_target[3], float fov_y, const uint64_t* keys,
@@ -285,63 +407,22 @@ int sr_renderer_render_device_transforms(SrRenderer* r, const float cam_pos[3], 
     run_frame_callbacks(r, r->absolute_frame_count + 1);
     r->instances_valid = false;
     r->last_transforms.clear();
-    const std::vector<SrScene*> scenes = srmr::scenes(r);
-    int rc = sr_scene_set_instances_device(scenes[0], keys, counts, n_keys, d_transforms, stream);
-    for (size_t i = 1; rc == SR_OK && i < scenes.size(); i++) rc = srh::scene_set_instances_from(scenes[i], keys, counts, n_keys, d_transforms, r->device);
+    int rc = sr_scene_set_instances_device(r->slot[0].scene, keys, counts, n_keys, d_transforms, stream);
+    for (size_t i = 1; rc == SR_OK && i < r->slot.size(); i++) rc = srh::scene_set_instances_from(r->slot[i].scene, keys, counts, n_keys, d_transforms, r->device);
     if (rc != SR_OK) return rc;
     R_HIP(hipSetDevice(r->device));
     return render_passes(r, cam_pos, cam_target, fov_y, stream, out_frame);
 }
 
 namespace {
-// The frame behind its instance list: camera, the two ray-tracing passes, the post chain (the rest of Renderer::render).
+// The frame behind its instance list (the rest of Renderer::render): camera, the passes on every slot (srr::render_frame), frame counters.
 int render_passes(SrRenderer* r, const float cam_pos[3], const float cam_target[3], float fov_y, void* stream, uint64_t* out_frame) {
     SrMatrices m;
     int rc = sr_camera_matrices(cam_pos, cam_target, fov_y, r->width, r->height, r->prev_view_proj, &m);   // lib.rs:1017-1048
     if (rc != SR_OK) return rc;
     memcpy(r->prev_view_proj, m.view_proj, sizeof(r->prev_view_proj));                                     // history for the NEXT frame
-    // image set of this frame; the orderings that remain: RIS(f) -> final(f) -> post(f), RIS(f) -> RIS(f+1) and post(f-2) -> RIS(f)
-    const int k = (int)(r->relative_frame_count & 1u);
-    if (r->multi) {                                                  // N device slots: strips, exchange, gather, post on slot 0
-        if ((rc = srmr::render_frame(r, m, k, (hipStream_t)stream)) != SR_OK) return rc;
-        r->last_set = k;
-        r->relative_frame_count += 1;
-        r->absolute_frame_count += 1;
-        r->frame_of_set[k] = r->absolute_frame_count;
-        if (out_frame) *out_frame = r->absolute_frame_count;
-        return SR_OK;
-    }
-    R_HIP(hipEventRecord(r->ev_in, (hipStream_t)stream));           // whatever the caller enqueued on `stream` comes first
-    R_HIP(hipStreamWaitEvent(r->s_ris, r->ev_in, 0));
-    R_HIP(hipStreamWaitEvent(r->s_ris, r->ev_done[k], 0));          // frame f-2 no longer reads this image set
-    SrRtParams p;
-    memset(&p, 0, sizeof(p));
-    p.scene = r->scene;
-    p.raw_color = r->raw_color[k]; p.depth_img = r->depth[k]; p.normal_img = r->normal[k]; p.diffuse_img = r->diffuse[k]; p.motion_vec_img = r->motion[k];
-    p.matrices = &m;
-    p.blue_noise_tex = r->blue_noise; p.blue_noise_w = r->noise_w; p.blue_noise_h = r->noise_h;
-    p.reservoirs[0] = r->reservoirs[0]; p.reservoirs[1] = r->reservoirs[1];
-    p.reservoirs_gi[0] = r->reservoirs_gi[0]; p.reservoirs_gi[1] = r->reservoirs_gi[1];
-    p.primary_payload = r->primary[k];
-    p.frame_count = r->relative_frame_count;
-    p.width = r->width; p.height = r->height;
-    p.config = r->config;
-    if (p.config.enable_restir && (rc = sr_trace_ris(&p, r->s_ris)) != SR_OK) return rc;
-    R_HIP(hipEventRecord(r->ev_ris[k], r->s_ris));
-    R_HIP(hipStreamWaitEvent(r->s_final, r->ev_ris[k], 0));
-    if ((rc = sr_trace_final(&p, r->s_final)) != SR_OK) return rc;
-    SrPostParams q;
-    memset(&q, 0, sizeof(q));
-    q.raw_color = r->raw_color[k]; q.motion_vec_img = r->motion[k]; q.depth_img = r->depth[k]; q.normal_img = r->normal[k]; q.diffuse_img = r->diffuse[k];
-    q.accum[0] = r->accum[0]; q.accum[1] = r->accum[1]; q.denoise[0] = r->denoise[0]; q.denoise[1] = r->denoise[1];
-    q.output_rgba8 = r->output[k];
-    q.frame_count = r->relative_frame_count; q.width = r->width; q.height = r->height;
-    q.exposure = 1.0f;        // EXPOSURE (lib.rs:44)
-    q.denoise_passes = 4;     // DENOISE_PASSES (lib.rs:42)
-    if ((rc = sr_post_temporal(&q, r->s_final)) != SR_OK) return rc;
-    if ((rc = sr_post_denoise(&q, r->s_final)) != SR_OK) return rc;
-    if ((rc = sr_post_tonemap(&q, r->s_final)) != SR_OK) return rc;
-    R_HIP(hipEventRecord(r->ev_done[k], r->s_final));
+    const int k = (int)(r->relative_frame_count & 1u);              // image set of this frame
+    if ((rc = srr::render_frame(r, m, k, (hipStream_t)stream)) != SR_OK) return rc;
     r->last_set = k;
     r->relative_frame_count += 1;                                    // lib.rs:1438-1439
     r->absolute_frame_count += 1;
@@ -358,7 +439,7 @@ int sr_renderer_wait_frame(SrRenderer* r, uint64_t frame) {
     if (frame + 1 >= r->absolute_frame_count && r->absolute_frame_count > 0) {
         // the last submitted frame used image set last_set, the one before it the other set; older frames are long done
         const int k = frame == r->absolute_frame_count ? r->last_set : (r->last_set ^ 1);
-        R_HIP(hipEventSynchronize(r->ev_done[k]));
+        R_HIP(hipEventSynchronize(r->slot[0].ev_done[k]));
     }
     return SR_OK;
 }
@@ -386,12 +467,12 @@ int sampler_slot(SrRenderer* r, const SrSamplerDesc& d, uint32_t* out) {
     auto it = r->sampler_slots.find(k);
     if (it != r->sampler_slots.end()) { *out = it->second; return SR_OK; }
     std::vector<uint32_t> slots;
-    for (SrScene* sc : srmr::scenes(r)) {
-        int rc = sr_scene_add_sampler(sc, &d, out);
+    for (Slot& s : r->slot) {
+        int rc = sr_scene_add_sampler(s.scene, &d, out);
         if (rc != SR_OK) return rc;
         slots.push_back(*out);
     }
-    int rc = srmr::check_same_slots(slots, "load_scene: sampler");
+    int rc = check_same_slots(slots, "load_scene: sampler");
     if (rc == SR_OK) r->sampler_slots[k] = *out;
     return rc;
 }
@@ -400,29 +481,27 @@ int sampler_slot(SrRenderer* r, const SrSamplerDesc& d, uint32_t* out) {
 // Renderer::load_scene: uploads the parsed scene's images, samplers and BLASes under fresh keys of a new group.
 int sr_renderer_load_scene(SrRenderer* r, const SrGltf* g, SrLoadedScene** out) {
     if (!r || !g || !out) return rfail(SR_ERR_INVALID_ARG, "load_scene: null argument");
-    R_HIP(hipSetDevice(r->device));
-    R_HIP(hipDeviceSynchronize());                       // device_wait_idle (lib.rs:800)
-    if (r->multi) { int rc = srmr::synchronize(r); if (rc != SR_OK) return rc; }
+    R_RC(srr::sync_all(r));                              // device_wait_idle (lib.rs:800), on every slot's device
     uint32_t n_blases = 0, n_instances = 0, n_images = 0, n_samplers = 0, n_textures = 0;
     int rc = sr_gltf_counts(g, &n_blases, &n_instances, &n_images, &n_samplers, &n_textures);
     if (rc != SR_OK) return rc;
     const uint64_t group = r->next_group++;
     std::vector<uint32_t> image_slots(n_images), smp_slots(n_samplers);
     std::vector<uint32_t>& group_images = r->scene_images[group];     // freed again by unload_scene (also after a failed load)
-    const std::vector<SrScene*> scs = srmr::scenes(r);               // parsed once, uploaded to every replica
+    std::vector<Slot>& scs = r->slot;                                // parsed once, uploaded to every replica
     for (uint32_t i = 0; i < n_images; i++) {
         const uint8_t* px; uint32_t w, h, ch;
         std::vector<uint32_t> slots;
         if ((rc = sr_gltf_image(g, i, &px, &w, &h, &ch)) == SR_OK)
-            for (SrScene* sc : scs) {
+            for (Slot& s : scs) {
                 uint32_t sl = 0;
-                if ((rc = sr_scene_add_image(sc, px, w, h, ch, &sl)) != SR_OK) break;
+                if ((rc = sr_scene_add_image(s.scene, px, w, h, ch, &sl)) != SR_OK) break;
                 slots.push_back(sl);
             }
-        if (rc == SR_OK) rc = srmr::check_same_slots(slots, "load_scene: image");
+        if (rc == SR_OK) rc = check_same_slots(slots, "load_scene: image");
         if (rc != SR_OK) {
-            for (size_t j = 0; j < slots.size(); j++) sr_scene_remove_image(scs[j], slots[j]);
-            for (uint32_t sl : group_images) for (SrScene* sc : scs) sr_scene_remove_image(sc, sl);
+            for (size_t j = 0; j < slots.size(); j++) sr_scene_remove_image(scs[j].scene, slots[j]);
+            for (uint32_t sl : group_images) for (Slot& s : scs) sr_scene_remove_image(s.scene, sl);
             r->scene_images.erase(group);
             return rc;
         }
@@ -456,10 +535,10 @@ int sr_renderer_load_scene(SrRenderer* r, const SrGltf* g, SrLoadedScene** out) 
         }
         const uint64_t key = (group << 32) | (uint64_t)b;   // ResourceKey{group, index}
         for (size_t j = 0; j < scs.size() && rc == SR_OK; j++)
-            if ((rc = sr_scene_add_blas(scs[j], key, v, nv, idx, ni, &m, et, ne, nullptr)) != SR_OK)
-                for (size_t i = 0; i < j; i++) sr_scene_remove(scs[i], key);
+            if ((rc = sr_scene_add_blas(scs[j].scene, key, v, nv, idx, ni, &m, et, ne, nullptr)) != SR_OK)
+                for (size_t i = 0; i < j; i++) sr_scene_remove(scs[i].scene, key);
         if (rc != SR_OK) {
-            for (uint64_t k : group_keys) for (SrScene* sc : scs) sr_scene_remove(sc, k);
+            for (uint64_t k : group_keys) for (Slot& s : scs) sr_scene_remove(s.scene, k);
             delete ls;
             return rc;
         }
@@ -512,18 +591,15 @@ int sr_loaded_scene_destroy(SrLoadedScene* ls) { delete ls; return SR_OK; }
 // passed to render. Loading and unloading a scene repeatedly leaks no HBM.
 int sr_renderer_unload_scene(SrRenderer* r, uint64_t group) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "unload_scene: renderer is null");
-    R_HIP(hipSetDevice(r->device));
-    R_HIP(hipDeviceSynchronize());                                   // device_wait_idle (lib.rs:850)
-    if (r->multi) { int rc = srmr::synchronize(r); if (rc != SR_OK) return rc; }
-    const std::vector<SrScene*> scs = srmr::scenes(r);
+    R_RC(srr::sync_all(r));                                          // device_wait_idle (lib.rs:850), on every slot's device
     auto it = r->scene_groups.find(group);
     if (it != r->scene_groups.end()) {
-        for (uint64_t k : it->second) for (SrScene* sc : scs) { int rc = sr_scene_remove(sc, k); if (rc != SR_OK) return rc; }
+        for (uint64_t k : it->second) R_RC(each_scene(r, [&](SrScene* sc) { return sr_scene_remove(sc, k); }));
         r->scene_groups.erase(it);
     }
     auto im = r->scene_images.find(group);
     if (im != r->scene_images.end()) {
-        for (uint32_t sl : im->second) for (SrScene* sc : scs) { int rc = sr_scene_remove_image(sc, sl); if (rc != SR_OK) return rc; }
+        for (uint32_t sl : im->second) R_RC(each_scene(r, [&](SrScene* sc) { return sr_scene_remove_image(sc, sl); }));
         r->scene_images.erase(im);
     }
     r->instances_valid = false;
@@ -561,7 +637,7 @@ int sr_renderer_update_mesh_device(SrRenderer* r, uint64_t key, const SrVertex* 
 // A mesh's rig lives on the first slot's scene only: that scene poses, the further replicas take the posed vertices.
 int sr_renderer_set_mesh_skin(SrRenderer* r, uint64_t key, const SrSkinInfluence* influences, uint32_t n_vertices, uint32_t n_joints) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "set_mesh_skin: null argument (the renderer)");
-    return sr_scene_set_mesh_skin(srmr::scenes(r)[0], key, influences, n_vertices, n_joints);
+    return sr_scene_set_mesh_skin(r->slot[0].scene, key, influences, n_vertices, n_joints);
 }
 
 // sr_scene_skin_mesh on the first slot's scene, which poses and validates once (first_scene_produces).
@@ -573,7 +649,7 @@ int sr_renderer_skin_mesh(SrRenderer* r, uint64_t key, const SrTransform* joint_
 // A mesh's morph lives on the first slot's scene only, like its rig.
 int sr_renderer_set_mesh_morph(SrRenderer* r, uint64_t key, const SrMorphDelta* deltas, uint32_t n_vertices, uint32_t n_targets) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "set_mesh_morph: null argument (the renderer)");
-    return sr_scene_set_mesh_morph(srmr::scenes(r)[0], key, deltas, n_vertices, n_targets);
+    return sr_scene_set_mesh_morph(r->slot[0].scene, key, deltas, n_vertices, n_targets);
 }
 
 // sr_scene_pose_mesh on the first slot's scene, which morphs, skins and validates once (first_scene_produces).
@@ -585,7 +661,7 @@ int sr_renderer_pose_mesh(SrRenderer* r, uint64_t key, const float* weights, uin
 // A mesh's frame lives on the first slot's scene only, like its rig.
 int sr_renderer_set_mesh_frame(SrRenderer* r, uint64_t key, uint32_t flags) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "set_mesh_frame: null argument (the renderer)");
-    return sr_scene_set_mesh_frame(srmr::scenes(r)[0], key, flags);
+    return sr_scene_set_mesh_frame(r->slot[0].scene, key, flags);
 }
 
 // sr_scene_update_mesh_positions* on the first slot's scene, which produces the records and validates once (first_scene_produces).
@@ -641,7 +717,7 @@ int sr_renderer_pose_scene(SrRenderer* r, const SrGltf* g, const SrLoadedScene* 
         // it is skinned too; the file's targets are not even parsed for a mesh without one, so a scene on which attach_morphs
         // was never called is posed as before
         SrMeshMorphInfo mi;
-        if ((rc = sr_scene_mesh_morph_info(srmr::scenes(r)[0], ls->keys[b], &mi)) != SR_OK) return rc;
+        if ((rc = sr_scene_mesh_morph_info(r->slot[0].scene, ls->keys[b], &mi)) != SR_OK) return rc;
         int32_t skin = -1; uint32_t n_joints = 0;
         if ((rc = sr_gltf_blas_skin(g, b, &skin, nullptr, nullptr)) != SR_OK) return rc;
         if (skin < 0 && mi.n_targets == 0) continue;
@@ -706,17 +782,16 @@ int sr_renderer_set_light_table_build(SrRenderer* r, uint32_t mode) {
 }
 int sr_renderer_light_table_info(SrRenderer* r, uint32_t slot, SrLightTableInfo* out) {
     if (!r || !out) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_light_table_info: null argument");
-    const std::vector<SrScene*> scs = srmr::scenes(r);
-    if (slot >= scs.size()) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_light_table_info: no such slot");
-    return sr_scene_light_table_info(scs[slot], out);
+    if (slot >= r->slot.size()) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_light_table_info: no such slot");
+    return sr_scene_light_table_info(r->slot[slot].scene, out);
 }
 
 // Access for harnesses: the scene (counters, stats), the device output image and the frame counter.
 int sr_renderer_get(SrRenderer* r, SrScene** scene, const uint32_t** output_rgba8_device, const float** raw_color_device, uint32_t* relative_frame_count) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_get: renderer is null");
-    if (scene) *scene = r->scene;
+    if (scene) *scene = r->slot[0].scene;
     if (output_rgba8_device) *output_rgba8_device = r->output[r->last_set];     // of the last submitted frame
-    if (raw_color_device) *raw_color_device = r->raw_color[r->last_set];
+    if (raw_color_device) *raw_color_device = r->slot[0].raw_color[r->last_set];
     if (relative_frame_count) *relative_frame_count = r->relative_frame_count;
     return SR_OK;
 }

@@ -176,6 +176,22 @@ def test_state_rules_of_bounds_and_halo(rt):
     r.resize((80, 48))                                        # a new extent: a new (equal) cut may be set again
     r.set_strip_bounds([0, 70, 80])
     r.close()
+    r = rt.Renderer((64, 48))                                 # one slot: the same rules, one strip, nothing to overflow
+    r.set_strip_bounds([0, 64])
+    r.set_motion_halo(8)
+    assert r.history_overflow() == 0
+    r.replica_scene(0)
+    with pytest.raises(SunrayError):
+        r.replica_scene(1)
+    load(r, desc)
+    r.wait_frame(r.render(static_camera(desc, 0), desc.instances))
+    with pytest.raises(SunrayError) as e:
+        r.set_strip_bounds([0, 64])
+    assert e.value.code == -4
+    with pytest.raises(SunrayError) as e:
+        r.set_motion_halo(8)
+    assert e.value.code == -4
+    r.close()
 
 
 def test_scene_changes_resize_and_gltf(rt, hip):
