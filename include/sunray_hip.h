@@ -951,6 +951,55 @@ int sr_shade_closest_hit(const SrScene* scene, const SrHit* hits, uint32_t n, Sr
  * counterpart with a parity test. Misses (t < 0) give 0. Device pointers. */
 int sr_any_hit_ignores(const SrScene* scene, const SrHit* hits, uint32_t n, uint32_t* ignored, void* stream);
 
+/* The inline helpers under the passes (the pinned transcendentals, the pack / unpack routines, the RNG, the BRDF and reservoir
+ * helpers, the triangle test), one at a time on raw rows — this hook exists so that each of them has a device counterpart
+ * with a parity test of its own, on inputs no frame reaches. Row i of `in` holds helper `fn`'s arguments as dwords (floats by
+ * their bits, vectors as x y z, records as they lie in memory), row i of `out` receives its results; the widths of both rows
+ * come from sr_probe_helper_layout. in / out are device pointers to n rows; an unknown fn, or a null pointer with n > 0, is
+ * SR_ERR_INVALID_ARG and nothing is written. */
+typedef enum SrProbeHelper {
+    SR_PROBE_SINCOS = 0,        /* x -> sin, cos */
+    SR_PROBE_EXP,
+    SR_PROBE_LOG,
+    SR_PROBE_POW,               /* x, y */
+    SR_PROBE_POW5,
+    SR_PROBE_SMOOTHSTEP,        /* a, b, x */
+    SR_PROBE_F32_TO_F16,        /* float -> half bits */
+    SR_PROBE_F16_TO_F32,        /* half bits -> float */
+    SR_PROBE_PACK_HALF_2X16,
+    SR_PROBE_UNPACK_HALF_2X16,
+    SR_PROBE_PACK_SNORM_2X16,
+    SR_PROBE_UNPACK_SNORM_2X16,
+    SR_PROBE_PACK_UNORM_4X8,
+    SR_PROBE_UNPACK_UNORM_RGB,
+    SR_PROBE_PACK_NORMAL,
+    SR_PROBE_UNPACK_NORMAL,
+    SR_PROBE_PACK_RGBA8_SNORM,
+    SR_PROBE_UNSNORM8,
+    SR_PROBE_PACK_B10G11R11,
+    SR_PROBE_UNPACK_B10G11R11,
+    SR_PROBE_PCG_HASH,
+    SR_PROBE_INIT_RNG,          /* px, py, frame, launch width -> seed */
+    SR_PROBE_RND,               /* seed -> new seed, float */
+    SR_PROBE_NORM3,
+    SR_PROBE_REFLECT3,          /* i, n */
+    SR_PROBE_REFRACT3,          /* i, n, eta */
+    SR_PROBE_BUILD_ONB,         /* n -> t, b */
+    SR_PROBE_SMITH_V_GGX,       /* NdotV, NdotL, alpha */
+    SR_PROBE_SMITH_G1_GGX,      /* NdotX, alpha */
+    SR_PROBE_RANDOM_BOUNCE,     /* normal, r1, r2 */
+    SR_PROBE_SAMPLE_GGX_VNDF,   /* normal, V, roughness, r1, r2 */
+    SR_PROBE_EVAL_LIGHT,        /* hit_pos, hit_normal, V, albedo, roughness, metallic, emission, light_pos, light_normal */
+    SR_PROBE_GI_TARGET_PDF,     /* shade_pos, shade_normal, albedo, metallic, sample_pos, sample_radiance */
+    SR_PROBE_MERGE,             /* SrReservoir r, SrReservoir new, p_hat, random -> r, taken */
+    SR_PROBE_MERGE_GI,          /* SrReservoirGI r, SrReservoirGI new, p_hat, jacobian, random -> r, taken */
+    SR_PROBE_TRANSFORM_POINT,   /* m[12], p */
+    SR_PROBE_INTERSECT_TRI,     /* o, d, v0, e1, e2, tmin, tmax -> hit, t, u, v */
+    SR_PROBE_COUNT
+} SrProbeHelper;
+int sr_probe_helper(uint32_t fn, const uint32_t* in, uint32_t n, uint32_t* out, void* stream);
+int sr_probe_helper_layout(uint32_t fn, uint32_t* in_dwords, uint32_t* out_dwords);
+
 /* The "raytracing_ris" pass (lib.rs:1662-1705): one ray_gen_ris invocation per pixel
  * (ray_gen_ris.slang:12-440): G-buffer + ReSTIR-DI reservoir + ReSTIR-GI initial reservoir. */
 int sr_trace_ris(const SrRtParams* params, void* stream);

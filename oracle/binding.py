@@ -90,7 +90,28 @@ def unpack_normal(p):
     return np.array(list(out), dtype=np.float32)
 
 
-NO_READ = -2 ** 31     # read-log marker (orc_scene.h, kNoRead)
+def probe_helper_layout(fn):
+    """(input dwords, output dwords) of one row of helper `fn` (the SrProbeHelper ids of include/sunray_hip.h), None if unknown."""
+    i, o = C.c_uint32(), C.c_uint32()
+    if lib().orc_probe_helper_layout(C.c_uint32(fn), C.byref(i), C.byref(o)) != 0:
+        return None
+    return i.value, o.value
+
+
+def probe_helper(fn, rows):
+    """orc_probe_helper: helper `fn` of the oracle on every row of `rows` (uint32, n x input dwords) -> uint32, n x output dwords."""
+    layout = probe_helper_layout(fn)
+    if layout is None:
+        raise ValueError("orc_probe_helper knows no helper %d" % fn)
+    iw, ow = layout
+    rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, iw)
+    out = np.zeros((rows.shape[0], ow), dtype=np.uint32)
+    if lib().orc_probe_helper(C.c_uint32(fn), _p(rows), C.c_uint32(rows.shape[0]), _p(out)) != 0:
+        raise ValueError("orc_probe_helper refused helper %d" % fn)
+    return out
+
+
+NO_READ = -2 ** 31    # read-log marker (orc_scene.h, kNoRead)
 
 # Branch log (OracleScene.set_branch_log): bit k of a pixel's word is set when the pass took the outcome named k-th here.
 # Word 0, trace_ris (ray_gen_ris.slang; the numbers are lines of oracle/orc_passes.cpp as it stood before the log was added):

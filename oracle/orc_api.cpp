@@ -174,4 +174,96 @@ int orc_intersect_tri(const float* o, const float* d, const float* v0, const flo
     return intersect_tri(v3(o[0], o[1], o[2]), v3(d[0], d[1], d[2]), t, tmin, tmax, tuv[0], tuv[1], tuv[2]) ? 1 : 0;
 }
 
+
+// ---- helper probe: the CPU side of sr_probe_helper (include/sunray_hip.h) ------------------------------------------------
+// Same ids, same rows of dwords; each case calls the oracle's own function of orc_math.h / orc_utils.h / orc_scene.h.
+static const uint32_t kProbeWidth[SR_PROBE_COUNT][2] = {
+    {1, 2}, {1, 1}, {1, 1}, {2, 1}, {1, 1}, {3, 1},                     // sincos exp log pow pow5 smoothstep
+    {1, 1}, {1, 1}, {2, 1}, {1, 2}, {2, 1}, {1, 2}, {4, 1}, {1, 3},     // f32->f16 f16->f32 half2x16 snorm2x16 unorm4x8
+    {3, 1}, {1, 3}, {4, 1}, {1, 1}, {3, 1}, {1, 3},                     // normal rgba8_snorm unsnorm8 b10g11r11
+    {1, 1}, {4, 1}, {1, 2},                                             // pcg_hash init_rng rnd
+    {3, 3}, {6, 3}, {7, 3}, {3, 6}, {3, 1}, {2, 1}, {5, 3}, {9, 3},     // norm3 reflect refract onb smith_v smith_g1 bounce vndf
+    {23, 3}, {16, 1}, {26, 13}, {27, 13}, {15, 3}, {17, 4},             // eval_light gi_pdf merge merge_gi transform_point intersect_tri
+};
+int orc_probe_helper_layout(uint32_t fn, uint32_t* in_dwords, uint32_t* out_dwords) {
+    if (fn >= SR_PROBE_COUNT) return -1;
+    *in_dwords = kProbeWidth[fn][0]; *out_dwords = kProbeWidth[fn][1];
+    return 0;
+}
+static void probe_row(uint32_t fn, const uint32_t* a, uint32_t* o) {
+#define F(k) u2f(a[k])
+#define V(k) v3(F(k), F((k) + 1), F((k) + 2))
+#define OF(k, val) o[k] = f2u(val)
+#define O3(k, vec) do { V3 v_ = (vec); OF(k, v_.x); OF((k) + 1, v_.y); OF((k) + 2, v_.z); } while (0)
+    switch (fn) {
+        case SR_PROBE_SINCOS: { float s, c; sincos_f(F(0), &s, &c); OF(0, s); OF(1, c); break; }
+        case SR_PROBE_EXP: OF(0, exp_f(F(0))); break;
+        case SR_PROBE_LOG: OF(0, log_f(F(0))); break;
+        case SR_PROBE_POW: OF(0, pow_f(F(0), F(1))); break;
+        case SR_PROBE_POW5: OF(0, pow5(F(0))); break;
+        case SR_PROBE_SMOOTHSTEP: OF(0, smoothstep(F(0), F(1), F(2))); break;
+        case SR_PROBE_F32_TO_F16: o[0] = f32_to_f16(F(0)); break;
+        case SR_PROBE_F16_TO_F32: OF(0, f16_to_f32(a[0] & 0xFFFFu)); break;
+        case SR_PROBE_PACK_HALF_2X16: o[0] = pack_half_2x16(F(0), F(1)); break;
+        case SR_PROBE_UNPACK_HALF_2X16: { V2 r = unpack_half_2x16(a[0]); OF(0, r.x); OF(1, r.y); break; }
+        case SR_PROBE_PACK_SNORM_2X16: o[0] = pack_snorm_2x16(F(0), F(1)); break;
+        case SR_PROBE_UNPACK_SNORM_2X16: { V2 r = unpack_snorm_2x16(a[0]); OF(0, r.x); OF(1, r.y); break; }
+        case SR_PROBE_PACK_UNORM_4X8: o[0] = pack_unorm_4x8(F(0), F(1), F(2), F(3)); break;
+        case SR_PROBE_UNPACK_UNORM_RGB: { V4 r = unpack_unorm_4x8(a[0]); OF(0, r.x); OF(1, r.y); OF(2, r.z); break; }
+        case SR_PROBE_PACK_NORMAL: o[0] = pack_normal(V(0)); break;
+        case SR_PROBE_UNPACK_NORMAL: O3(0, unpack_normal(a[0])); break;
+        case SR_PROBE_PACK_RGBA8_SNORM: o[0] = pack_rgba8_snorm(F(0), F(1), F(2), F(3)); break;
+        case SR_PROBE_UNSNORM8: OF(0, unsnorm8(a[0])); break;
+        case SR_PROBE_PACK_B10G11R11: o[0] = pack_b10g11r11(F(0), F(1), F(2)); break;
+        case SR_PROBE_UNPACK_B10G11R11: OF(0, from_ufloat(a[0] & 0x7ffu, 6)); OF(1, from_ufloat((a[0] >> 11) & 0x7ffu, 6)); OF(2, from_ufloat(a[0] >> 22, 5)); break;
+        case SR_PROBE_PCG_HASH: o[0] = pcg_hash(a[0]); break;
+        case SR_PROBE_INIT_RNG: o[0] = init_rng(a[0], a[1], a[2], a[3]).seed; break;
+        case SR_PROBE_RND: { Rng r{a[0]}; float x = rnd(r); o[0] = r.seed; OF(1, x); break; }
+        case SR_PROBE_NORM3: O3(0, normalize(V(0))); break;
+        case SR_PROBE_REFLECT3: O3(0, reflect(V(0), V(3))); break;
+        case SR_PROBE_REFRACT3: O3(0, refract(V(0), V(3), F(6))); break;
+        case SR_PROBE_BUILD_ONB: { V3 t, b; build_onb(V(0), t, b); O3(0, t); O3(3, b); break; }
+        case SR_PROBE_SMITH_V_GGX: OF(0, smith_v_ggx(F(0), F(1), F(2))); break;
+        case SR_PROBE_SMITH_G1_GGX: OF(0, smith_g1_ggx(F(0), F(1))); break;
+        case SR_PROBE_RANDOM_BOUNCE: O3(0, get_random_bounce(V(0), F(3), F(4))); break;
+        case SR_PROBE_SAMPLE_GGX_VNDF: O3(0, sample_ggx_vndf(V(0), V(3), F(6), F(7), F(8))); break;
+        case SR_PROBE_EVAL_LIGHT: O3(0, eval_unshadowed_light(V(0), V(3), V(6), V(9), F(12), F(13), V(14), V(17), V(20))); break;
+        case SR_PROBE_GI_TARGET_PDF: OF(0, gi_target_pdf(V(0), V(3), V(6), F(9), V(10), V(13))); break;
+        case SR_PROBE_MERGE: {
+            SrReservoir r, nr;
+            memcpy(&r, a, sizeof r); memcpy(&nr, a + 12, sizeof nr);
+            const bool taken = merge_reservoirs(r, nr, F(24), F(25));
+            memcpy(o, &r, sizeof r); o[12] = taken ? 1u : 0u;
+            break;
+        }
+        case SR_PROBE_MERGE_GI: {
+            SrReservoirGI r, nr;
+            memcpy(&r, a, sizeof r); memcpy(&nr, a + 12, sizeof nr);
+            const bool taken = merge_reservoirs_gi(r, nr, F(24), F(25), F(26));
+            memcpy(o, &r, sizeof r); o[12] = taken ? 1u : 0u;
+            break;
+        }
+        case SR_PROBE_TRANSFORM_POINT: { SrTransform x; memcpy(x.m, a, sizeof x.m); O3(0, transform_point(x, V(12))); break; }
+        case SR_PROBE_INTERSECT_TRI: {
+            WTri tr{V(6), V(9), V(12), 0, 0};
+            float t, u, v;
+            const bool hit = intersect_tri(V(0), V(3), tr, F(15), F(16), t, u, v);
+            o[0] = hit ? 1u : 0u; OF(1, t); OF(2, u); OF(3, v);
+            break;
+        }
+        default: break;
+    }
+#undef F
+#undef V
+#undef OF
+#undef O3
+}
+int orc_probe_helper(uint32_t fn, const uint32_t* in, uint32_t n, uint32_t* out) {
+    if (fn >= SR_PROBE_COUNT || (n && (!in || !out))) return -1;
+    const size_t iw = kProbeWidth[fn][0], ow = kProbeWidth[fn][1];
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < (int64_t)n; i++) probe_row(fn, in + (size_t)i * iw, out + (size_t)i * ow);
+    return 0;
+}
+
 }  // extern "C"

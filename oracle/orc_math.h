@@ -46,11 +46,14 @@ static inline float length(V3 a) { return sqrtf(dot(a, a)); }
 // normalize(0) = 0 * inf = NaN, the behaviour the shaders rely on for sky normals.
 static inline V3 normalize(V3 a) { float inv = 1.0f / sqrtf(dot(a, a)); return a * inv; }
 
-static inline float min_f(float a, float b) { return fminf(a, b); }
-static inline float max_f(float a, float b) { return fmaxf(a, b); }
-static inline float clamp_f(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-static inline V3 min3(V3 a, V3 b) { return V3{fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z)}; }
-static inline float max_comp(V3 a) { return fmaxf(a.x, fmaxf(a.y, a.z)); }  // max(r, max(g, b))
+// min / max drop a NaN operand, quiet or signalling: what the device's v_min_f32 / v_max_f32 give once the compiler has
+// canonicalised their operands. glibc's fminf / fmaxf drop only a quiet NaN and return NaN for a signalling one, which a raw bit
+// pattern can carry into pack_snorm_2x16 / pack_unorm_4x8 (tests/test_gpu_helper_probe.py), so the NaN test is spelled out.
+static inline float min_f(float a, float b) { return a != a ? b : (b != b ? a : fminf(a, b)); }
+static inline float max_f(float a, float b) { return a != a ? b : (b != b ? a : fmaxf(a, b)); }
+static inline float clamp_f(float x, float lo, float hi) { return min_f(max_f(x, lo), hi); }
+static inline V3 min3(V3 a, V3 b) { return V3{min_f(a.x, b.x), min_f(a.y, b.y), min_f(a.z, b.z)}; }
+static inline float max_comp(V3 a) { return max_f(a.x, max_f(a.y, a.z)); }  // max(r, max(g, b))
 static inline V3 lerp3(V3 a, V3 b, float t) { return a + (b - a) * t; }     // HLSL lerp
 static inline float frac(float x) { return x - floorf(x); }
 static inline float smoothstep(float a, float b, float x) {

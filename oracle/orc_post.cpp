@@ -22,7 +22,7 @@ inline V3 load_raw_color(const float* raw, size_t i) {
 }
 inline float luminance(V3 c) { return dot(c, v3(0.2126f, 0.7152f, 0.0722f)); }
 inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-inline V3 max3v(V3 a, V3 b) { return V3{fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z)}; }
+inline V3 max3v(V3 a, V3 b) { return V3{max_f(a.x, b.x), max_f(a.y, b.y), max_f(a.z, b.z)}; }
 }  // namespace
 
 void post_temporal(const SrPostParams& p) {

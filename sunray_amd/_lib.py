@@ -45,6 +45,7 @@ SYMBOLS = [
     "sr_renderer_set_light_table_build", "sr_renderer_light_table_info",
     "sr_scene_set_instances_device", "sr_scene_instance_update_info", "sr_scene_read_instance_tables", "sr_instance_tables_host",
     "sr_renderer_render_device_transforms",
+    "sr_probe_helper", "sr_probe_helper_layout",
 ]
 
 

@@ -270,3 +270,10 @@ class SrStripPlane(C.Structure):  # one per-pixel plane of a full-size image (sr
 
 
 AXIS_COLS, AXIS_ROWS, SPATIAL_HALO, STRIP_MAX_PLANES = 0, 1, 30, 5
+
+# SrProbeHelper, in the header's order: the id of a helper is its index (sr_probe_helper / sr_probe_helper_layout)
+PROBE_HELPERS = ("sincos", "exp", "log", "pow", "pow5", "smoothstep", "f32_to_f16", "f16_to_f32", "pack_half_2x16", "unpack_half_2x16",
+                 "pack_snorm_2x16", "unpack_snorm_2x16", "pack_unorm_4x8", "unpack_unorm_rgb", "pack_normal", "unpack_normal",
+                 "pack_rgba8_snorm", "unsnorm8", "pack_b10g11r11", "unpack_b10g11r11", "pcg_hash", "init_rng", "rnd", "norm3", "reflect3",
+                 "refract3", "build_onb", "smith_v_ggx", "smith_g1_ggx", "random_bounce", "sample_ggx_vndf", "eval_light", "gi_target_pdf",
+                 "merge", "merge_gi", "transform_point", "intersect_tri")

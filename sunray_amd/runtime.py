@@ -786,6 +786,23 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def probe_helper_layout(fn):
+    """(input dwords, output dwords) of one row of helper `fn` (abi.PROBE_HELPERS index); raises for an unknown id. Host only."""
+    i, o = C.c_uint32(), C.c_uint32()
+    check(lib().sr_probe_helper_layout(C.c_uint32(fn), C.byref(i), C.byref(o)))
+    return i.value, o.value
+
+
+def probe_helper(fn, rows, out):
+    """sr_probe_helper on the current stream: helper `fn` on the first len(rows) / width rows of the int32 device tensor `rows`,
+    results into the int32 device tensor `out` (test hook: tests/test_gpu_helper_probe.py)."""
+    iw, ow = probe_helper_layout(fn)
+    n = rows.numel() // iw
+    assert out.numel() >= n * ow
+    check(lib().sr_probe_helper(C.c_uint32(fn), C.c_void_p(rows.data_ptr()), C.c_uint32(n), C.c_void_p(out.data_ptr()), _stream()))
+    return n
+
+
 def post_chain(frame, frame_count, exposure=1.0, denoise_passes=4):
     """temporal_accumulation -> denoise_0..N-1 -> postprocess on the current stream (lib.rs:1576-1615)."""
     p = abi.post_params(frame, frame_count, lambda t: t.data_ptr(), exposure, denoise_passes)
