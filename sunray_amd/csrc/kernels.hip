@@ -932,8 +932,8 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void final_kernel(const 
                 const int bw = (int)a.blue_noise_w, bh = (int)a.blue_noise_h;      // :44-50
                 const int n1x = ipx % bw, n1y = ipy % bh;
                 const int n2x = (ipx + 47) % bw, n2y = (ipy + 71) % bh;
-                const float bn_1 = (float)a.blue_noise_tex[((size_t)n1y * bw + n1x) * 4] / 255.0f;
-                const float bn_2 = (float)a.blue_noise_tex[((size_t)n2y * bw + n2x) * 4] / 255.0f;
+                const float bn_1 = div_small_int_exact<255>((float)a.blue_noise_tex[((size_t)n1y * bw + n1x) * 4]);
+                const float bn_2 = div_small_int_exact<255>((float)a.blue_noise_tex[((size_t)n2y * bw + n2x) * 4]);
                 r1 = fracf(bn_1 + (float)(a.frame_count % 1024u) * 0.75487766f);
                 r2 = fracf(bn_2 + (float)(a.frame_count % 1024u) * 0.56984029f);
             } else {

@@ -147,6 +147,19 @@ SRD float rnd(uint32_t& seed) {
     return (float)result * 2.3283064365386963e-10f;  // / 2^32, exact (the fp32 value of 4294967295.0)
 }
 
+// x / C for a SMALL INTEGER x and C one of 255, 127, 32767 — exact on those inputs only. With r = RN(1/C) (folded at compile time),
+// one multiply and one Newton step on the remainder (which is exact: q is within an ulp of x/C) give the correctly rounded
+// quotient for every byte / 255, signed byte / 127 and signed half / 32767: the bits of the division, in 3 VALU instructions
+// instead of the 10 of the correctly rounded expansion. Checked over the full domains on the host (tests/test_const_division_host.py)
+// and on the device (tests/test_gpu_const_division.py). NOT valid for general floats: those sites keep the division.
+template <int C>
+SRD float div_small_int_exact(float x) {
+    static_assert(C == 255 || C == 127 || C == 32767, "the identity is only checked for these divisors");
+    constexpr float c = (float)C, r = 1.0f / c;
+    const float q = x * r;
+    return fmaf(fmaf(-c, q, x), r, q);
+}
+
 // ---- rt_utils.slang:68-114 pack / unpack ----------------------------------------------------
 SRD uint32_t pack_snorm_2x16(float x, float y) {
     int ix = (int)rintf(clampf(x, -1.0f, 1.0f) * 32767.0f);
@@ -157,8 +170,8 @@ SRD f2 unpack_snorm_2x16(uint32_t p) {
     int x = (int)(p << 16) >> 16;
     int y = (int)p >> 16;
     f2 r;
-    r.x = clampf((float)x / 32767.0f, -1.0f, 1.0f);
-    r.y = clampf((float)y / 32767.0f, -1.0f, 1.0f);
+    r.x = clampf(div_small_int_exact<32767>((float)x), -1.0f, 1.0f);
+    r.y = clampf(div_small_int_exact<32767>((float)y), -1.0f, 1.0f);
     return r;
 }
 SRD uint32_t pack_unorm_4x8(float x, float y, float z, float w) {
@@ -169,7 +182,7 @@ SRD uint32_t pack_unorm_4x8(float x, float y, float z, float w) {
     return cx | (cy << 8) | (cz << 16) | (cw << 24);
 }
 SRD f3 unpack_unorm_rgb(uint32_t p) {
-    return mk3((float)(p & 0xFFu) / 255.0f, (float)((p >> 8) & 0xFFu) / 255.0f, (float)((p >> 16) & 0xFFu) / 255.0f);
+    return mk3(div_small_int_exact<255>((float)(p & 0xFFu)), div_small_int_exact<255>((float)((p >> 8) & 0xFFu)), div_small_int_exact<255>((float)((p >> 16) & 0xFFu)));
 }
 SRD uint32_t pack_half_2x16(float x, float y) { return f32_to_f16_bits(x) | (f32_to_f16_bits(y) << 16); }
 SRD f2 unpack_half_2x16(uint32_t p) { f2 r; r.x = f16_bits_to_f32(p & 0xFFFFu); r.y = f16_bits_to_f32(p >> 16); return r; }
@@ -202,7 +215,7 @@ SRD uint32_t snorm8(float x) {
 SRD uint32_t pack_rgba8_snorm(float x, float y, float z, float w) {
     return snorm8(x) | (snorm8(y) << 8) | (snorm8(z) << 16) | (snorm8(w) << 24);
 }
-SRD float unsnorm8(uint32_t b) { int i = (int)(int8_t)(b & 0xFFu); return fmaxf((float)i / 127.0f, -1.0f); }
+SRD float unsnorm8(uint32_t b) { int i = (int)(int8_t)(b & 0xFFu); return fmaxf(div_small_int_exact<127>((float)i), -1.0f); }
 // unsigned small float (5-bit exponent, MANT-bit mantissa), round-to-nearest-even
 template <int MANT>
 SRD uint32_t to_ufloat(float f) {

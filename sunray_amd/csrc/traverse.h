@@ -240,6 +240,14 @@ SRD bool child_hit_tl(const NodePlanesTl& p, float t_lo, float t_hi, float& tnea
 // combines them, while ballot(a && b) makes the compiler turn its combined mask into a 0/1 VGPR and compare that again
 // (v_cndmask + v_cmp_ne per ballot). A ballot only reports active lanes, so the masks are the same under partial exec.
 SRD unsigned long long ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// Lanes in a mask as a 32-bit count that stays on the scalar unit: one s_bcnt1_i32_b64, then scalar arithmetic. The compiler
+// widens __popcll's result to 64 bits and compares it with a 64-bit VECTOR compare of a scalar (v_cmp_*_u64 + s_and exec +
+// s_cbranch_vcc*); the sum of two 32-bit popcounts stays scalar but is three instructions per count.
+SRD uint32_t mask_count(unsigned long long m) {
+    uint32_t n;
+    asm("s_bcnt1_i32_b64 %0, %1" : "=s"(n) : "s"(m) : "scc");
+    return n;
+}
 
 // Every lane of the wave that is active at the call site takes part; `want` = this lane has a ray of its own.
 // FIXED_TMIN / FIXED_TMAX: every ray of the wave has tmin == kPassTmin / tmax == kPassTmax (the caller passes exactly these), as all
@@ -290,23 +298,30 @@ SRD bool traverse_ws(const DevScene& sc, bool want, f3 o, f3 d, float tmin, floa
         if (__builtin_amdgcn_ballot_w64(node != kSentinel || (TL && leaf != 0)) == 0ull) break;
         // ---- node phase: wave-uniform loop, so that lanes without work stay in step and can be handed some ----
         for (;;) {
-            // `inner`: the lane has a node-phase step to do — an inner node, or (two-level) a top-level leaf to enter
-            const bool inner = node != kSentinel && (node >= 0 || (TL && !in_blas));
+            // A lane WALKS when it has a node-phase step to do — an inner node, or (two-level) a top-level leaf to enter, i.e.
+            // node != kSentinel && (node >= 0 || (TL && !in_blas)) — and no postponed leaf.
             // On to the triangles when every walking lane holds a (postponed) leaf — or already when most of the wave is BLOCKED (holds a
             // postponed leaf and has arrived at a second one) and only a few lanes still walk: the blocked lanes would wait for them.
             // Progress: an early exit needs a blocked lane, and the triangle phase consumes its leaf.
+            // Three comparisons per iteration feed every lane set of the loop top; the sets themselves are combined on the scalar
+            // unit. Each one contains a plain ballot, which reports active lanes only, so a complement never lets in a lane that
+            // is not here. kSentinel is positive: `node < 0` already excludes it. The two-level form adds `in_blas` as a fourth mask.
+            const unsigned long long m_sent = ballot(node == kSentinel), m_neg = ballot(node < 0), m_leaf0 = ballot(leaf == 0);
+            const unsigned long long m_leafnode = TL ? (m_neg & ballot(in_blas)) : m_neg;    // holds a triangle leaf as its node
             {
-                const unsigned long long walking = ballot(inner) & ballot(leaf == 0);
-                if (walking == 0ull) break;
-                if ((int)__popcll(walking) <= kEarlyTriWalking &&
-                    (int)__popcll(ballot(node != kSentinel && node < 0 && (!TL || in_blas)) & ballot(leaf != 0)) >= kEarlyTriBlocked) break;
+                const unsigned long long walking = m_leaf0 & ~m_sent & ~m_leafnode;         // = ballot(inner && leaf == 0)
+                // One scalar test, one exit: nobody walks, or few walk and many are blocked. As int32 each term is negative exactly
+                // when its threshold fails (counts are at most 64), so their OR is non-negative when both hold.
+                const uint32_t n_walk = mask_count(walking), n_blocked = mask_count(m_leafnode & ~m_leaf0);
+                const uint32_t few_walk = (uint32_t)kEarlyTriWalking - n_walk, many_blocked = n_walk ? n_blocked - (uint32_t)kEarlyTriBlocked : 0u;
+                if ((int32_t)(few_walk | many_blocked) >= 0) break;
             }
             const bool idle = node == kSentinel && leaf == 0;
-            const unsigned long long idle_mask = ballot(node == kSentinel) & ballot(leaf == 0);
+            const unsigned long long idle_mask = m_sent & m_leaf0;
             if (idle_mask != 0ull) {
                 // donors: every lane with a node or leaf in hand and a spare stack entry — blocked lanes too (they wait, their subtrees need not)
                 const bool can_give = node != kSentinel && sp > sb;
-                const unsigned long long donor_mask = ballot(node != kSentinel) & ballot(sp > sb);
+                const unsigned long long donor_mask = ballot(sp > sb) & ~m_sent;
                 if (donor_mask != 0ull) {
                     const uint32_t n = min((uint32_t)__popcll(idle_mask), (uint32_t)__popcll(donor_mask));
                     const uint32_t drank = lanes_below(donor_mask), irank = lanes_below(idle_mask);
@@ -557,8 +572,8 @@ SRD uint32_t wrap_index(int i, int n, uint32_t mode) {
     return (uint32_t)(i < 0 ? 0 : (i > n - 1 ? n - 1 : i));
 }
 SRD float4 texel_unorm(uint32_t p) {
-    return make_float4((float)(p & 0xFFu) / 255.0f, (float)((p >> 8) & 0xFFu) / 255.0f, (float)((p >> 16) & 0xFFu) / 255.0f,
-                       (float)(p >> 24) / 255.0f);
+    return make_float4(div_small_int_exact<255>((float)(p & 0xFFu)), div_small_int_exact<255>((float)((p >> 8) & 0xFFu)),
+                       div_small_int_exact<255>((float)((p >> 16) & 0xFFu)), div_small_int_exact<255>((float)(p >> 24)));
 }
 SRD float4 sample_texture(const DevScene& sc, uint32_t image_slot, uint32_t sampler_code, float s, float t, float4 fallback) {
     if (image_slot == 0xFFFFFFFFu) return fallback;
