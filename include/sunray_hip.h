@@ -618,6 +618,49 @@ typedef struct SrMeshMorphInfo {
     double morph_ms;           /* the last accepted pose: its kernels (morph, and skin where asked) + read-back (events, only while sr_scene_enable_timing is on) */
 } SrMeshMorphInfo;             /* 24 bytes */
 int sr_scene_mesh_morph_info(const SrScene* scene, uint64_t key, SrMeshMorphInfo* out);
+/* Batched posing: many meshes posed by one upload, one launch and one read-back (a crowd of small deforming meshes, in front of
+ * the batched tree build of SR_BLAS_BATCH_ON). For each item the result is exactly what
+ * sr_scene_pose_mesh(scene, key, weights, n_targets, joint_matrices, n_joints, stream) would leave: the same bytes in the mesh's
+ * device vertices, the same mesh state, the same posed / skinned / n_active / first_bad figures. What differs:
+ *   - Every host refusal of sr_scene_pose_mesh is decided for ALL items before any device work, with its status and its text
+ *     behind "pose_meshes: item <i>: ". Refused as well (SR_ERR_INVALID_ARG): items == NULL with n_items > 0, a key named by two
+ *     items, an item with neither stage; SR_ERR_UNSUPPORTED: a batch sr_pose_batch_plan refuses. n_items == 0 is SR_OK and does
+ *     nothing.
+ *   - One staging block (item rows, block table, all joint matrices, all active-target lists) is uploaded on `stream`, the check
+ *     words (two per item: morph stage, skin stage) are preset once, ONE kernel poses every tile of every item into a scratch
+ *     buffer the scene owns, and all check words come back in one read. An item with both stages keeps its morphed position,
+ *     normal and tangent on chip between the stages; the bytes are those of morph-then-skin through memory.
+ *   - All or nothing: if any item posed a vertex to a non-finite position the call returns sr_scene_update_mesh's status and text
+ *     (behind the item prefix) for the lowest such item and that item's lowest such vertex of either stage, and no mesh of the
+ *     batch has changed: neither bytes nor state nor counters. Only the first_bad of every stage that reported is recorded.
+ *   - Accepted: one device wait (frames in flight read the old vertices), one scatter launch that copies every item's records
+ *     from the scratch into its mesh's allocation, one wait, then, per item in item order, what sr_scene_update_mesh_device leaves
+ *     behind on the host (stale host copy, the emissive handling of either SR_LIGHTS_* mode, the tree and structure marks).
+ *     SrMeshMorphInfo.morph_ms / SrMeshSkinInfo.skin_ms of every item take the time of the one posing launch. */
+typedef struct SrPoseItem {            /* one mesh of a batch; what sr_scene_pose_mesh takes, by value */
+    uint64_t key;
+    const float* weights;              /* host, n_targets floats, or NULL: no morph stage */
+    const SrTransform* joint_matrices; /* host, n_joints x 48 bytes, or NULL: no skin stage */
+    uint32_t n_targets, n_joints;
+} SrPoseItem;                          /* 32 bytes */
+int sr_scene_pose_meshes(SrScene* scene, const SrPoseItem* items, uint32_t n_items, void* stream);
+typedef struct SrPoseBatchInfo {       /* the last sr_scene_pose_meshes that reached the device (a host refusal leaves it alone) */
+    uint32_t items, blocks;            /* items of the call; blocks of the posing launch (256 vertices a block) */
+    uint64_t vertices;                 /* records posed */
+    uint32_t morph_only, skin_only, fused;   /* items by their stages */
+    uint32_t launches;                 /* kernel launches: 2 accepted (pose, scatter), 1 refused */
+    uint32_t read_backs;               /* device-to-host copies: 1 (all check words) */
+    uint32_t calls;                    /* calls that reached the device since the scene was created */
+    uint32_t refused_item, refused_vertex;   /* a non-finite refusal: the item and vertex named; 0xFFFFFFFF: accepted */
+    uint64_t upload_bytes;             /* the staging block */
+    double pose_ms, scatter_ms;        /* posing launch + read-back, scatter launch (events, only while sr_scene_enable_timing is on) */
+    double host_ms;                    /* the whole call, wall clock */
+} SrPoseBatchInfo;                     /* 80 bytes */
+int sr_scene_pose_batch_info(const SrScene* scene, SrPoseBatchInfo* out);
+/* The layout of a batch, host only: item i's first block of the posing launch (ceil(n_vertices[i] / 256) blocks an item, in item
+ * order), its first record in the scratch, and the number of blocks in all. SR_ERR_UNSUPPORTED, with nothing written: 2^31
+ * blocks or more, else 2^32 vertices or more. */
+int sr_pose_batch_plan(const uint32_t* n_vertices, uint32_t n_items, uint32_t* first_block, uint64_t* vertex_base, uint32_t* n_blocks);
 /* The mesh frame: the third producer of device vertices that lives in the library, for callers that know only the new POSITIONS
  * (a simulation, any torch code). It recomputes area-weighted normals, and uv-aligned tangents where asked, from the positions
  * and the mesh's own topology, and hands the records on as sr_scene_update_mesh_device does its caller's. The pose path
@@ -1235,6 +1278,16 @@ int sr_renderer_pose_mesh(SrRenderer* renderer, uint64_t key, const float* weigh
  * this was never called is posed by sr_renderer_pose_scene as before. Call it, like sr_renderer_attach_skins, while the meshes
  * hold the vertices they were loaded with. */
 int sr_renderer_attach_morphs(SrRenderer* renderer, const SrGltf* gltf, const SrLoadedScene* loaded);
+/* sr_scene_pose_meshes through the facade: the first device slot's scene poses and validates the whole batch once; every further
+ * slot's replica takes each item's posed records from that scene's batch scratch by a device-to-device (peer) copy, mesh by mesh.
+ * A refusal changes no replica. */
+int sr_renderer_pose_meshes(SrRenderer* renderer, const SrPoseItem* items, uint32_t n_items, void* stream);
+/* How sr_renderer_pose_scene poses a loaded scene's rigged and morphed meshes: SR_POSE_BATCH_OFF (the default), one
+ * sr_renderer_skin_mesh / sr_renderer_pose_mesh per mesh; SR_POSE_BATCH_ON, all of them by one sr_renderer_pose_meshes.
+ * SR_POSE_BATCH=on|off in the environment sets the initial mode when the renderer is created. */
+#define SR_POSE_BATCH_OFF 0u
+#define SR_POSE_BATCH_ON 1u
+int sr_renderer_set_pose_batch(SrRenderer* renderer, uint32_t mode);
 /* sr_scene_set_mesh_frame / sr_scene_update_mesh_positions_device / sr_scene_update_mesh_positions through the facade, as the
  * skin calls above: the frame is attached on the first device slot's scene only and the records are produced there, once
  * (`d_positions` lives on that slot's GPU); every further slot's replica takes the validated records by a device-to-device (peer)

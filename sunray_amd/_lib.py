@@ -46,6 +46,7 @@ SYMBOLS = [
     "sr_scene_set_instances_device", "sr_scene_instance_update_info", "sr_scene_read_instance_tables", "sr_instance_tables_host",
     "sr_renderer_render_device_transforms",
     "sr_probe_helper", "sr_probe_helper_layout",
+    "sr_scene_pose_meshes", "sr_scene_pose_batch_info", "sr_pose_batch_plan", "sr_renderer_pose_meshes", "sr_renderer_set_pose_batch",
 ]
 
 

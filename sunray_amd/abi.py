@@ -213,6 +213,19 @@ class SrMeshMorphInfo(C.Structure):  # one mesh's morph and its last pose (sr_sc
     _fields_ = [("n_targets", C.c_uint32), ("posed", C.c_uint32), ("n_active", C.c_uint32), ("first_bad", C.c_uint32), ("morph_ms", C.c_double)]
 
 
+class SrPoseItem(C.Structure):  # one mesh of a batch (sr_scene_pose_meshes): the arguments of sr_scene_pose_mesh by value, 32 B
+    _fields_ = [("key", C.c_uint64), ("weights", C.c_void_p), ("joint_matrices", C.c_void_p), ("n_targets", C.c_uint32), ("n_joints", C.c_uint32)]
+
+
+class SrPoseBatchInfo(C.Structure):  # the last sr_scene_pose_meshes that reached the device (sr_scene_pose_batch_info), 80 B
+    _fields_ = [("items", C.c_uint32), ("blocks", C.c_uint32), ("vertices", C.c_uint64), ("morph_only", C.c_uint32), ("skin_only", C.c_uint32),
+                ("fused", C.c_uint32), ("launches", C.c_uint32), ("read_backs", C.c_uint32), ("calls", C.c_uint32), ("refused_item", C.c_uint32),
+                ("refused_vertex", C.c_uint32), ("upload_bytes", C.c_uint64), ("pose_ms", C.c_double), ("scatter_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+POSE_BATCH_OFF, POSE_BATCH_ON, POSE_BATCH_TILE = 0, 1, 256  # sr_renderer_set_pose_batch; vertices a block of the posing launch
+
+
 class SrMeshFrameInfo(C.Structure):  # one mesh's frame and its last position update (sr_scene_mesh_frame_info), 32 B
     _fields_ = [("flags", C.c_uint32), ("n_groups", C.c_uint32), ("n_entries", C.c_uint32), ("max_valence", C.c_uint32),
                 ("updates", C.c_uint32), ("first_bad", C.c_uint32), ("frame_ms", C.c_double)]

@@ -26,6 +26,7 @@
 #include "lights.h"
 #include "morph.h"
 #include "normals.h"
+#include "pose_batch.h"
 #include "skin.h"
 #include "tl_record.h"
 
@@ -263,6 +264,12 @@ struct SrScene {
     // sr_scene_pose_mesh: the morphed vertices where a skin stage follows (scratch: srk_skin's `bind`; without one the morph stage
     // writes d_skin_out itself), and the active list of the last call (n indices, then n weights)
     DeviceBuffer d_morph_out, d_morph_active;
+    // sr_scene_pose_meshes: the staging block of the last call (pose_batch_plan.h lays it out), its check words (two per item) and
+    // the scratch every item's posed records go to; the keys and scratch offsets of the last accepted batch (the replicas of a
+    // renderer take the records from there), and the figures of the last call that reached the device
+    DeviceBuffer d_pose_stage, d_pose_check, d_pose_scratch;
+    std::vector<uint64_t> pose_batch_keys, pose_batch_vertex_base;
+    SrPoseBatchInfo pose_info{0, 0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0.0, 0.0, 0.0};
     // sr_scene_update_mesh_positions*: the face vectors of the last call (one or two 16-byte pieces per triangle) and the uploaded
     // positions of the host-pointer form; the records go to d_skin_out, the scratch every library producer leaves its result in
     DeviceBuffer d_frame_faces, d_frame_positions;
@@ -985,20 +992,15 @@ int sr_scene_set_mesh_skin(SrScene* s, uint64_t key, const SrSkinInfluence* infl
 
 namespace {
 
-// sr_scene_skin_mesh and sr_scene_pose_mesh, whose texts begin with `who`: sr_scene_update_mesh_device with the library's own
-// producers in front, in glTF's order, a morph stage (`weights`), a skin stage (`joint_matrices`) or both. The morph kernel reads
-// the morph base; with a skin stage it writes the scene's morph scratch, which the skinning kernel takes as its `bind` in place of
-// the bind pose, and the skinning kernel writes d_skin_out; without one the morph kernel writes d_skin_out itself. Posing and the
-// finite-position check are one pass over the bytes: each stage answers in a check word of its own (the morph stage in word 0,
-// the skin stage in the next), and all come back in one read after the last kernel.
-int pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream, const char* who) {
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t slot = 0;
-    int rc = find_mesh(s, key, who, &slot);
+// What the pose path refuses on the host, before any device work, in the words of the entry point `who`: the mesh's slot into
+// *slot and the active list into `active` (2 * n_targets words: the indices of the targets whose weight is not 0, ascending,
+// then from word n_targets on their weights) and *n_active.
+int check_pose_args(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, const char* who,
+                    uint32_t* slot, std::vector<uint32_t>& active, uint32_t* n_active) {
+    int rc = find_mesh(s, key, who, slot);
     if (rc != SR_OK) return rc;
-    srh::HostMesh& m = s->meshes[slot];
-    SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
-    SrScene::MeshState::Skin& skin = s->mesh_state[slot].skin;
+    const SrScene::MeshState::Morph& morph = s->mesh_state[*slot].morph;
+    const SrScene::MeshState::Skin& skin = s->mesh_state[*slot].skin;
     char buf[200];
     if (weights) {
         if (morph.n_targets == 0) return fail(SR_ERR_INVALID_ARG, "pose_mesh: the mesh has no morph targets (sr_scene_set_mesh_morph attaches them)");
@@ -1014,17 +1016,33 @@ int pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets
             return fail(SR_ERR_INVALID_ARG, buf);
         }
     }
-    // the active list: the targets whose weight is not 0, in ascending order (indices, then weights: one upload)
-    std::vector<uint32_t> active(weights ? 2 * (size_t)n_targets : 0);
-    uint32_t n_active = 0;
+    active.assign(weights ? 2 * (size_t)n_targets : 0, 0u);
+    *n_active = 0;
     for (uint32_t k = 0; weights && k < n_targets; k++) {
         if (!std::isfinite(weights[k])) {
             snprintf(buf, sizeof(buf), "pose_mesh: weight %u is not finite", k);
             return fail(SR_ERR_INVALID_ARG, buf);
         }
-        if (weights[k] != 0.0f) { active[n_active] = k; memcpy(&active[(size_t)n_targets + n_active], &weights[k], 4); n_active++; }
+        if (weights[k] != 0.0f) { active[*n_active] = k; memcpy(&active[(size_t)n_targets + *n_active], &weights[k], 4); (*n_active)++; }
     }
-    if ((rc = check_emissive_list(m)) != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
+    return check_emissive_list(s->meshes[*slot]);
+}
+
+// sr_scene_skin_mesh and sr_scene_pose_mesh, whose texts begin with `who`: sr_scene_update_mesh_device with the library's own
+// producers in front, in glTF's order, a morph stage (`weights`), a skin stage (`joint_matrices`) or both. The morph kernel reads
+// the morph base; with a skin stage it writes the scene's morph scratch, which the skinning kernel takes as its `bind` in place of
+// the bind pose, and the skinning kernel writes d_skin_out; without one the morph kernel writes d_skin_out itself. Posing and the
+// finite-position check are one pass over the bytes: each stage answers in a check word of its own (the morph stage in word 0,
+// the skin stage in the next), and all come back in one read after the last kernel.
+int pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream, const char* who) {
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t slot = 0, n_active = 0;
+    std::vector<uint32_t> active;
+    int rc = check_pose_args(s, key, weights, n_targets, joint_matrices, n_joints, who, &slot, active, &n_active);
+    if (rc != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
+    srh::HostMesh& m = s->meshes[slot];
+    SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
+    SrScene::MeshState::Skin& skin = s->mesh_state[slot].skin;
     const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
     if ((rc = s->d_skin_out.reserve(bytes)) != SR_OK || (rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
     if (weights && (rc = s->d_morph_active.reserve(8 * (size_t)n_targets)) != SR_OK) return rc;
@@ -1130,6 +1148,139 @@ int sr_scene_mesh_morph_info(const SrScene* s, uint64_t key, SrMeshMorphInfo* ou
     const SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
     memset(out, 0, sizeof(*out));
     out->n_targets = morph.n_targets; out->posed = morph.posed; out->n_active = morph.n_active; out->first_bad = morph.first_bad; out->morph_ms = morph.morph_ms;
+    return SR_OK;
+}
+
+// Many meshes posed by one upload, one launch and one read-back (the header states the contract). Host checks for every item
+// first (check_pose_args, in the per-mesh call's words behind the item prefix), then the plan and the staging block, the posing
+// launch into the batch scratch, and for an accepted batch the device wait, the scatter launch and the per-mesh host tail.
+int sr_scene_pose_meshes(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_meshes: null argument (the scene)");
+    if (n_items == 0) return SR_OK;
+    if (!items) return fail(SR_ERR_INVALID_ARG, "pose_meshes: null argument (items, with n_items > 0)");
+    const auto prefix = [](uint32_t i) { return "pose_meshes: item " + std::to_string(i) + ": "; };
+    std::vector<uint32_t> slots(n_items), counts(n_items), n_active(n_items), active_index, active;
+    std::vector<float> active_weight;
+    std::map<uint64_t, uint32_t> seen;
+    uint64_t n_matrices = 0;
+    int rc;
+    for (uint32_t i = 0; i < n_items; i++) {
+        const SrPoseItem& it = items[i];
+        if (!it.weights && !it.joint_matrices) return fail(SR_ERR_INVALID_ARG, prefix(i) + "pose_mesh: neither weights nor joint matrices given (one stage at least)");
+        rc = check_pose_args(s, it.key, it.weights, it.n_targets, it.joint_matrices, it.n_joints, it.weights ? "pose_mesh" : "skin_mesh", &slots[i], active, &n_active[i]);
+        if (rc != SR_OK) return fail(rc, prefix(i) + g_last_error);
+        const auto first = seen.emplace(it.key, i);
+        if (!first.second) return fail(SR_ERR_INVALID_ARG, prefix(i) + "the key is named twice in the batch (first by item " + std::to_string(first.first->second) + ")");
+        counts[i] = s->meshes[slots[i]].n_vertices;
+        active_index.insert(active_index.end(), active.begin(), active.begin() + n_active[i]);
+        for (uint32_t a = 0; a < n_active[i]; a++) { float w; memcpy(&w, &active[(size_t)it.n_targets + a], 4); active_weight.push_back(w); }
+        if (it.joint_matrices) n_matrices += it.n_joints;
+    }
+    if (n_matrices >= (1ull << 32) || active_index.size() >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_meshes: the batch holds 2^32 joint matrices or active targets or more");
+    std::vector<uint32_t> first_block(n_items);
+    std::vector<uint64_t> vertex_base(n_items);
+    uint32_t n_blocks = 0;
+    if ((rc = sr_pose_batch_plan(counts.data(), n_items, first_block.data(), vertex_base.data(), &n_blocks)) != SR_OK) return rc;
+    const uint64_t n_vertices = vertex_base[n_items - 1] + counts[n_items - 1];
+    const srh::PoseBatchLayout lay = srh::pose_batch_layout(n_items, n_blocks, n_matrices, active_index.size());
+    if ((rc = bind_device(s)) != SR_OK) return rc;
+    if ((rc = s->d_pose_stage.reserve(lay.bytes)) != SR_OK || (rc = s->d_pose_check.reserve(8 * (size_t)n_items)) != SR_OK ||
+        (rc = s->d_pose_scratch.reserve(sizeof(SrVertex) * (size_t)n_vertices)) != SR_OK) return rc;
+    // the staging block: rows, block table, matrices, active lists
+    std::vector<unsigned char> stage(lay.bytes, 0);
+    srd::PoseBatchItem* rows = (srd::PoseBatchItem*)(stage.data() + lay.items);
+    SrPoseBatchInfo info{n_items, n_blocks, n_vertices, 0, 0, 0, 0, 0, s->pose_info.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, lay.bytes, 0.0, 0.0, 0.0};
+    uint32_t matrix_base = 0, active_base = 0;
+    for (uint32_t i = 0; i < n_items; i++) {
+        const SrPoseItem& it = items[i];
+        const SrScene::MeshState& ms = s->mesh_state[slots[i]];
+        srd::PoseBatchItem& row = rows[i];
+        row.src = it.weights ? ms.morph.d_base.p : ms.skin.d_bind.p;
+        row.deltas = it.weights ? ms.morph.d_deltas.p : nullptr;
+        row.influences = it.joint_matrices ? ms.skin.d_influences.p : nullptr;
+        row.dst = s->meshes[slots[i]].d_vertices;
+        row.vertex_base = vertex_base[i];
+        row.n_vertices = counts[i]; row.first_block = first_block[i];
+        row.n_active = n_active[i]; row.active_base = active_base;
+        row.matrix_base = matrix_base;
+        row.stages = (it.weights ? srd::kPoseMorph : 0u) | (it.joint_matrices ? srd::kPoseSkin : 0u);
+        if (it.joint_matrices) { memcpy(stage.data() + lay.matrices + sizeof(SrTransform) * (size_t)matrix_base, it.joint_matrices, sizeof(SrTransform) * (size_t)it.n_joints); matrix_base += it.n_joints; }
+        active_base += n_active[i];
+        (row.stages == 3u ? info.fused : it.weights ? info.morph_only : info.skin_only)++;
+    }
+    srh::pose_batch_block_table(first_block.data(), n_items, n_blocks, (uint32_t*)(stage.data() + lay.block_table));
+    if (!active_index.empty()) {
+        memcpy(stage.data() + lay.active_index, active_index.data(), 4 * active_index.size());
+        memcpy(stage.data() + lay.active_weight, active_weight.data(), 4 * active_weight.size());
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned char* d_stage = (const unsigned char*)s->d_pose_stage.p;
+    const srd::PoseBatchItem* d_rows = (const srd::PoseBatchItem*)(d_stage + lay.items);
+    const uint32_t* d_table = (const uint32_t*)(d_stage + lay.block_table);
+    std::vector<uint32_t> bad(2 * (size_t)n_items, 0xFFFFFFFFu);
+    EventPair pose_timer(s), scatter_timer(s);
+    int e = (int)hipMemsetAsync(s->d_pose_check.p, 0xFF, 8 * (size_t)n_items, st);
+    if (e == 0) e = (int)hipMemcpyAsync(s->d_pose_stage.p, stage.data(), lay.bytes, hipMemcpyHostToDevice, st);
+    pose_timer.begin(st);
+    if (e == 0) e = srk_pose_batch(d_rows, d_table, n_blocks, (const SrTransform*)(d_stage + lay.matrices), (const uint32_t*)(d_stage + lay.active_index),
+                                   (const float*)(d_stage + lay.active_weight), (SrVertex*)s->d_pose_scratch.p, (uint32_t*)s->d_pose_check.p, st);
+    if (e == 0) e = (int)hipMemcpyAsync(bad.data(), s->d_pose_check.p, 8 * (size_t)n_items, hipMemcpyDeviceToHost, st);
+    pose_timer.end(st);
+    if (e == 0) e = (int)hipStreamSynchronize(st);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("pose_meshes: the posing kernel failed: ") + hipGetErrorString((hipError_t)e));
+    info.launches = 1; info.read_backs = 1; info.pose_ms = pose_timer.ms();
+    // all or nothing: the lowest item with a bad vertex refuses the batch; only the first_bad of the stages that reported is kept
+    for (uint32_t i = 0; i < n_items; i++) {
+        const uint32_t bm = bad[2 * (size_t)i], bs = bad[2 * (size_t)i + 1];
+        if (std::min(bm, bs) < counts[i] && info.refused_item == 0xFFFFFFFFu) { info.refused_item = i; info.refused_vertex = std::min(bm, bs); }
+    }
+    if (info.refused_item != 0xFFFFFFFFu) {
+        for (uint32_t i = 0; i < n_items; i++) {
+            SrScene::MeshState& ms = s->mesh_state[slots[i]];
+            if (bad[2 * (size_t)i] < counts[i]) ms.morph.first_bad = bad[2 * (size_t)i];
+            if (bad[2 * (size_t)i + 1] < counts[i]) ms.skin.first_bad = bad[2 * (size_t)i + 1];
+        }
+        s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();      // the scratch holds a refused batch
+        info.host_ms = ms_between(t0, std::chrono::steady_clock::now());
+        s->pose_info = info;
+        fail_non_finite_vertex(info.refused_vertex);
+        return fail(SR_ERR_INVALID_ARG, prefix(info.refused_item) + g_last_error);
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();
+    HIP_TRY(hipDeviceSynchronize());                          // frames in flight read the old vertices
+    scatter_timer.begin(nullptr);
+    e = srk_pose_batch_scatter(d_rows, d_table, n_blocks, (const SrVertex*)s->d_pose_scratch.p, nullptr);
+    scatter_timer.end(nullptr);
+    if (e == 0) e = (int)hipStreamSynchronize(nullptr);
+    if (e != 0) return fail(SR_ERR_HIP, std::string("pose_meshes: the scatter kernel failed: ") + hipGetErrorString((hipError_t)e));
+    info.launches = 2; info.scatter_ms = scatter_timer.ms();
+    const auto t2 = std::chrono::steady_clock::now();
+    for (uint32_t i = 0; i < n_items; i++) {                   // the tail of take_device_vertices and finish_device_update, item by item
+        const uint32_t slot = slots[i];
+        srh::HostMesh& m = s->meshes[slot];
+        SrScene::MeshState& ms = s->mesh_state[slot];
+        m.copy_ms = info.scatter_ms; m.check_ms = 0.0;
+        m.host_stale = true; m.last_from_device = true;
+        if (!m.emissive_slots.empty()) {
+            if (s->light_mode == SR_LIGHTS_DEVICE) { ms.arena_stale = true; ms.arena_pending = true; }
+            else if ((rc = fetch_host_vertices(s, slot)) != SR_OK) return rc;
+        }
+        mesh_vertices_changed(s, slot);
+        if (items[i].weights) { ms.morph.first_bad = 0xFFFFFFFFu; ms.morph.n_active = n_active[i]; ms.morph.morph_ms = info.pose_ms; ms.morph.posed++; }
+        if (items[i].joint_matrices) { ms.skin.first_bad = 0xFFFFFFFFu; ms.skin.skin_ms = items[i].weights ? 0.0 : info.pose_ms; ms.skin.skinned++; }
+        s->pose_batch_keys.push_back(items[i].key); s->pose_batch_vertex_base.push_back(vertex_base[i]);
+    }
+    note_update_times(s, t0, t1, t2);
+    info.host_ms = ms_between(t0, std::chrono::steady_clock::now());
+    s->pose_info = info;
+    return SR_OK;
+}
+
+int sr_scene_pose_batch_info(const SrScene* s, SrPoseBatchInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_pose_batch_info: null argument");
+    *out = s->pose_info;
     return SR_OK;
 }
 
@@ -3138,6 +3289,12 @@ const SrVertex* srh::scene_skinned_vertices(const SrScene* s, uint64_t key, uint
     auto it = s->slots.find(key);
     *n_vertices = it == s->slots.end() ? 0u : s->meshes[it->second].n_vertices;
     return (const SrVertex*)s->d_skin_out.p;
+}
+
+const SrVertex* srh::scene_pose_batch_vertices(const SrScene* s, uint32_t item, uint32_t* n_vertices) {
+    if (item >= s->pose_batch_keys.size()) { *n_vertices = 0; return nullptr; }
+    *n_vertices = s->meshes[s->slots.at(s->pose_batch_keys[item])].n_vertices;
+    return (const SrVertex*)s->d_pose_scratch.p + s->pose_batch_vertex_base[item];
 }
 
 // A further replica of a renderer takes transforms that sr_scene_set_instances_device has accepted on `src_device`: a copy into a

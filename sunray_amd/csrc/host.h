@@ -130,4 +130,7 @@ int scene_set_instances_from(SrScene* scene, const uint64_t* keys, const uint32_
 // sr_scene_update_mesh_positions*) wrote its records into (api.cpp): what the further replicas of a renderer take through
 // scene_take_device_vertices, and the vertex count of the mesh `key` that was produced. Valid until the scene's next such call.
 const SrVertex* scene_skinned_vertices(const SrScene* scene, uint64_t key, uint32_t* n_vertices);
+// The same for item `item` of the last accepted sr_scene_pose_meshes: its records in the batch scratch and their count (NULL and 0
+// where the last batch was refused or had fewer items). Valid until the scene's next sr_scene_pose_meshes.
+const SrVertex* scene_pose_batch_vertices(const SrScene* scene, uint32_t item, uint32_t* n_vertices);
 }  // namespace srh

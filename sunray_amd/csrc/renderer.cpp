@@ -163,6 +163,7 @@ int create_renderer(const int* devices, uint32_t n_devices, uint32_t width, uint
     memset(r->prev_view_proj, 0, sizeof(r->prev_view_proj));
     sr_trace_config_default(&r->config);
     if (const char* ev = getenv("SR_PRIMARY_REUSE")) r->primary_reuse = atoi(ev) != 0;
+    if (const char* ev = getenv("SR_POSE_BATCH")) r->pose_batch = !strcmp(ev, "on") ? SR_POSE_BATCH_ON : SR_POSE_BATCH_OFF;
     const int rc = create_slots(r);
     if (rc != SR_OK) {
         const std::string msg = sr_last_error();
@@ -658,6 +659,30 @@ int sr_renderer_pose_mesh(SrRenderer* r, uint64_t key, const float* weights, uin
     return first_scene_produces(r, key, nullptr, 0, [&](SrScene* sc) { return sr_scene_pose_mesh(sc, key, weights, n_targets, joint_matrices, n_joints, stream); });
 }
 
+// sr_scene_pose_meshes on the first slot's scene, which poses and validates the whole batch once; the further replicas take each
+// item's records from that scene's batch scratch, mesh by mesh (first_scene_produces does the same for one mesh).
+int sr_renderer_pose_meshes(SrRenderer* r, const SrPoseItem* items, uint32_t n_items, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "pose_meshes: null argument (the renderer)");
+    int rc = sr_scene_pose_meshes(r->slot[0].scene, items, n_items, stream);
+    if (rc != SR_OK || n_items == 0) return rc;
+    r->instances_valid = false;
+    for (size_t i = 1; i < r->slot.size(); i++)
+        for (uint32_t k = 0; k < n_items; k++) {
+            uint32_t n_vertices = 0;
+            const SrVertex* src = srh::scene_pose_batch_vertices(r->slot[0].scene, k, &n_vertices);
+            if ((rc = srh::scene_take_device_vertices(r->slot[i].scene, items[k].key, src, n_vertices, r->device)) != SR_OK) return rc;
+        }
+    return SR_OK;
+}
+
+// How sr_renderer_pose_scene poses (SR_POSE_BATCH_*).
+int sr_renderer_set_pose_batch(SrRenderer* r, uint32_t mode) {
+    if (mode > SR_POSE_BATCH_ON) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_pose_batch: mode must be SR_POSE_BATCH_OFF or SR_POSE_BATCH_ON");
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_pose_batch: renderer is null");
+    r->pose_batch = mode;
+    return SR_OK;
+}
+
 // A mesh's frame lives on the first slot's scene only, like its rig.
 int sr_renderer_set_mesh_frame(SrRenderer* r, uint64_t key, uint32_t flags) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "set_mesh_frame: null argument (the renderer)");
@@ -712,6 +737,11 @@ int sr_renderer_pose_scene(SrRenderer* r, const SrGltf* g, const SrLoadedScene* 
     std::vector<SrTransform> posed(n_instances), joints;
     if ((rc = sr_gltf_pose(g, animation, time_seconds, posed.data(), 0, nullptr)) != SR_OK) return rc;
     std::vector<float> weights;
+    // SR_POSE_BATCH_ON: the same meshes with the same arguments, collected (the arrays stay alive until the call) and posed at once
+    const bool batch = r->pose_batch == SR_POSE_BATCH_ON;
+    std::vector<std::vector<SrTransform>> item_joints;
+    std::vector<std::vector<float>> item_weights;
+    std::vector<SrPoseItem> items;
     for (uint32_t b = 0; b < n_blases; b++) {
         // a mesh with a morph attached (sr_renderer_attach_morphs) is posed by sr_renderer_pose_mesh, with its joint matrices where
         // it is skinned too; the file's targets are not even parsed for a mesh without one, so a scene on which attach_morphs
@@ -726,6 +756,13 @@ int sr_renderer_pose_scene(SrRenderer* r, const SrGltf* g, const SrLoadedScene* 
             joints.resize(n_joints);
             if ((rc = sr_gltf_pose(g, animation, time_seconds, nullptr, (uint32_t)skin, joints.data())) != SR_OK) return rc;
         }
+        if (batch) {
+            item_joints.emplace_back(skin >= 0 ? joints : std::vector<SrTransform>());
+            item_weights.emplace_back(mi.n_targets);
+            if (mi.n_targets && (rc = sr_gltf_morph_weights(g, animation, time_seconds, b, item_weights.back().data(), mi.n_targets)) != SR_OK) return rc;
+            items.push_back(SrPoseItem{ls->keys[b], nullptr, nullptr, mi.n_targets, n_joints});      // the pointers once the vectors stand still
+            continue;
+        }
         if (mi.n_targets == 0) {
             if ((rc = sr_renderer_skin_mesh(r, ls->keys[b], joints.data(), n_joints, stream)) != SR_OK) return rc;
             continue;
@@ -734,6 +771,11 @@ int sr_renderer_pose_scene(SrRenderer* r, const SrGltf* g, const SrLoadedScene* 
         if ((rc = sr_gltf_morph_weights(g, animation, time_seconds, b, weights.data(), mi.n_targets)) != SR_OK) return rc;
         if ((rc = sr_renderer_pose_mesh(r, ls->keys[b], weights.data(), mi.n_targets, skin >= 0 ? joints.data() : nullptr, n_joints, stream)) != SR_OK) return rc;
     }
+    for (size_t k = 0; k < items.size(); k++) {
+        items[k].weights = items[k].n_targets ? item_weights[k].data() : nullptr;
+        items[k].joint_matrices = items[k].n_joints ? item_joints[k].data() : nullptr;
+    }
+    if (!items.empty() && (rc = sr_renderer_pose_meshes(r, items.data(), (uint32_t)items.size(), stream)) != SR_OK) return rc;
     if (instance_transforms_out) {              // grouped by blas, the order of the file kept within a group (sr_renderer_load_scene)
         size_t o = 0;
         for (uint32_t b = 0; b < n_blases; b++)

@@ -56,6 +56,7 @@ struct SrRenderer {
     uint32_t *accum[2] = {nullptr, nullptr}, *denoise[2] = {nullptr, nullptr};
     uint32_t* output[2] = {nullptr, nullptr};
     int primary_reuse = 1;                           // SR_PRIMARY_REUSE=0 in the environment: the final pass traces its camera ray itself (A/B)
+    uint32_t pose_batch = SR_POSE_BATCH_OFF;         // sr_renderer_set_pose_batch / SR_POSE_BATCH in the environment: pose_scene poses by one sr_renderer_pose_meshes
     hipEvent_t ev_in = nullptr;
     int last_set = 0;
     // per-frame state

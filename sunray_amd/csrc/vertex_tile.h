@@ -1,5 +1,5 @@
 // The tile scaffold of the kernels that produce or check a mesh's vertices on the device (skin_kernel, morph_kernel,
-// vertex_check_kernel): constants, the turn of a tile of records through the LDS, and the report of the lowest bad vertex.
+// pose_batch_kernel, vertex_check_kernel): constants, the turn of a tile of records through the LDS, and the report of the lowest bad vertex.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,12 +31,15 @@ __device__ __forceinline__ void store_normalised(uint4* piece, float x, float y,
     piece->x = __float_as_uint(x * r); piece->y = __float_as_uint(y * r); piece->z = __float_as_uint(z * r);
 }
 
-// The block's tile of a kTileBlock-wide launch over ceil(n_vertices / 256) blocks: `tile` is kTileBlock * kTileRow pieces of LDS.
+// A block's tile of a mesh, by default tile blockIdx.x of a kTileBlock-wide launch over ceil(n_vertices / 256) blocks: `tile` is
+// kTileBlock * kTileRow pieces of LDS.
 struct VertexTile {
     uint32_t v0, nv, np;        // first vertex (v0 < n_vertices), vertices and pieces in this tile
     uint64_t p0;                // first piece: 64-bit (n_vertices * 6 need not fit 32)
-    __device__ __forceinline__ explicit VertexTile(uint32_t n_vertices)
-        : v0(blockIdx.x * kTileBlock), nv(min(kTileBlock, n_vertices - v0)), np(nv * kVertexPieces), p0((uint64_t)v0 * kVertexPieces) {}
+    __device__ __forceinline__ explicit VertexTile(uint32_t n_vertices) : VertexTile(n_vertices, blockIdx.x) {}
+    // tile `tile_index` of a mesh of n_vertices, for a block that serves one of many meshes (pose_batch_kernel)
+    __device__ __forceinline__ VertexTile(uint32_t n_vertices, uint32_t tile_index)
+        : v0(tile_index * kTileBlock), nv(min(kTileBlock, n_vertices - v0)), np(nv * kVertexPieces), p0((uint64_t)v0 * kVertexPieces) {}
     // thread t's own row, valid between load() and store() while t < nv
     __device__ __forceinline__ static uint4* row(uint4* tile, uint32_t t) { return tile + t * kTileRow; }
     __device__ __forceinline__ void load(uint4* tile, const uint4* __restrict__ src) const {

@@ -167,6 +167,38 @@ def _pose_args(weights, joint_matrices):
     return (None if w is None else _p(w)), C.c_uint32(nt), (None if m is None else _p(m)), C.c_uint32(nj), (w, m)
 
 
+def _pose_items(items):
+    """The items of pose_meshes, a sequence of (key, weights or None, joint matrices or None), as an abi.SrPoseItem array ->
+    (array, n_items, the arrays kept alive); each item goes through _pose_args, whose ValueErrors name the item."""
+    try:
+        items = [tuple(it) for it in items]
+    except TypeError:
+        raise ValueError("pose_meshes: the items must be a sequence of (key, weights, joint_matrices)")
+    rows, keep = (abi.SrPoseItem * max(len(items), 1))(), []
+    for i, it in enumerate(items):
+        if len(it) != 3:
+            raise ValueError("pose_meshes: item %d: an item is (key, weights, joint_matrices), %d values given" % (i, len(it)))
+        try:
+            wp, nt, mp, nj, arrays = _pose_args(it[1], it[2])
+        except ValueError as e:
+            raise ValueError("pose_meshes: item %d: %s" % (i, e))
+        rows[i].key = int(it[0])
+        rows[i].weights = None if wp is None else wp.value
+        rows[i].joint_matrices = None if mp is None else mp.value
+        rows[i].n_targets, rows[i].n_joints = nt.value, nj.value
+        keep.append(arrays)
+    return rows, C.c_uint32(len(items)), keep
+
+
+def pose_batch_plan(n_vertices):
+    """The layout of a batch of meshes of these vertex counts -> (first_block uint32[n], vertex_base uint64[n], n_blocks): host
+    only (sr_pose_batch_plan)."""
+    counts = np.ascontiguousarray(n_vertices, dtype=np.uint32)
+    first, base, blocks = np.zeros(len(counts), np.uint32), np.zeros(len(counts), np.uint64), C.c_uint32(0)
+    check(lib().sr_pose_batch_plan(_p(counts), C.c_uint32(len(counts)), _p(first), _p(base), C.byref(blocks)))
+    return first, base, blocks.value
+
+
 def camera_matrices(pos, target, fov_y, width, height, prev_view_proj=None):
     """Camera::as_matrices + transposed upload (camera.rs:33-63, lib.rs:1017-1048). Host only."""
     m = abi.SrMatrices()
@@ -410,6 +442,18 @@ class Scene:
         set_instances applies it (sr_scene_pose_mesh)."""
         wp, nt, mp, nj, keep = _pose_args(weights, joint_matrices)
         check(lib().sr_scene_pose_mesh(self._h, C.c_uint64(key), wp, nt, mp, nj, self._stream()))
+
+    def pose_meshes(self, items):
+        """Poses many meshes at once: `items` is a sequence of (key, weights or None, joint matrices or None), each what pose_mesh
+        takes. One upload, one launch and one read-back for the whole batch; all or nothing (sr_scene_pose_meshes)."""
+        rows, n, keep = _pose_items(items)
+        check(lib().sr_scene_pose_meshes(self._h, rows, n, self._stream()))
+
+    def pose_batch_info(self):
+        """-> abi.SrPoseBatchInfo: the last pose_meshes that reached the device (sr_scene_pose_batch_info)."""
+        info = abi.SrPoseBatchInfo()
+        check(lib().sr_scene_pose_batch_info(self._h, C.byref(info)))
+        return info
 
     def mesh_morph_info(self, key):
         """-> abi.SrMeshMorphInfo: the targets of the mesh's morph (0: none), the poses taken, the active targets, the refusal and
@@ -1231,6 +1275,17 @@ class Renderer:
         info = abi.SrLightTableInfo()
         check(lib().sr_renderer_light_table_info(self._h, C.c_uint32(int(slot)), C.byref(info)))
         return info
+
+    def pose_meshes(self, items):
+        """Scene.pose_meshes on the first device slot; every further slot takes each item's posed vertices by a device copy; the
+        next render applies them (sr_renderer_pose_meshes)."""
+        rows, n, keep = _pose_items(items)
+        check(lib().sr_renderer_pose_meshes(self._h, rows, n, None))
+
+    def set_pose_batch(self, on):
+        """Whether pose_scene poses the file's rigged and morphed meshes by one pose_meshes (sr_renderer_set_pose_batch). Off by
+        default; SR_POSE_BATCH=on in the environment turns it on at creation."""
+        check(lib().sr_renderer_set_pose_batch(self._h, C.c_uint32(abi.POSE_BATCH_ON if on else abi.POSE_BATCH_OFF)))
 
     def set_mesh_tree_batch(self, mode):
         """Scene.set_mesh_tree_batch on every device slot (sr_renderer_set_mesh_tree_batch)."""
