@@ -534,9 +534,10 @@ typedef struct SrSkinInfluence {
  * the skin and frees its buffers (n_vertices and n_joints are not looked at); sr_scene_remove frees them too. Later
  * sr_scene_update_mesh* calls do not move the bind pose; attaching again snapshots it anew. */
 int sr_scene_set_mesh_skin(SrScene* scene, uint64_t key, const SrSkinInfluence* influences, uint32_t n_vertices, uint32_t n_joints);
-/* Poses a skinned mesh: uploads `joint_matrices` (HOST pointer, n_joints rows of 3x4, object space of the mesh) asynchronously
- * on `stream`, runs the skinning kernel from the bind pose and the influences into a scratch buffer the scene owns, and hands
- * that buffer on as sr_scene_update_mesh_device does its caller's: the posed vertices are applied by the next
+/* Poses a skinned mesh. The call is a batch of one item on the path of sr_scene_pose_meshes (below): `joint_matrices` (HOST
+ * pointer, n_joints rows of 3x4, object space of the mesh) go up asynchronously on `stream` in the staging block, the posing
+ * kernel skins the bind pose with the influences into a scratch buffer the scene owns, and a scatter launch copies the records
+ * into the mesh's allocation, which leaves what sr_scene_update_mesh_device leaves: the posed vertices are applied by the next
  * sr_scene_set_instances, with the same SR_ERR_STATE window, the same stale host copy and the same emissive handling. The
  * finite-position check (x, y, z of the posed position; nothing else is looked at) is part of the kernel: on a bad vertex the
  * call returns sr_scene_update_mesh's status and text with the lowest offending index, and the scene is exactly as it was
@@ -562,7 +563,7 @@ typedef struct SrMeshSkinInfo {
     uint32_t skinned;          /* poses taken since the skin was attached */
     uint32_t first_bad;        /* the last sr_scene_skin_mesh: lowest vertex posed to a non-finite position, 0xFFFFFFFF: none */
     uint32_t _pad;
-    double skin_ms;            /* the last accepted pose: kernel + 4-byte read-back (events, only while sr_scene_enable_timing is on) */
+    double skin_ms;            /* the last accepted pose: the posing kernel + read-back; 0.0 where a morph stage ran: morph_ms has it (events, only while sr_scene_enable_timing is on) */
 } SrMeshSkinInfo;              /* 24 bytes */
 int sr_scene_mesh_skin_info(const SrScene* scene, uint64_t key, SrMeshSkinInfo* out);
 /* Morph targets (glTF 2.0 blend shapes): the other producer of posed vertices that lives in the library. One delta record per
@@ -585,15 +586,16 @@ int sr_scene_set_mesh_morph(SrScene* scene, uint64_t key, const SrMorphDelta* de
 /* The one per-frame call of a mesh that has a morph, a skin or both, in glTF's order: morph first, then skin.
  * weights == NULL skips the morph stage: the call is then exactly sr_scene_skin_mesh(scene, key, joint_matrices, n_joints, stream).
  * joint_matrices == NULL skips the skin stage. Both NULL: SR_ERR_INVALID_ARG.
- * The morph stage compacts the weights that are not 0 into an active list (ascending target order; a target of weight 0 costs
- * no traffic) and runs the morph kernel from the morph base. With a skin stage it writes a scratch buffer the scene owns, which
- * the skinning kernel of sr_scene_skin_mesh takes as its bind pose (the snapshot of sr_scene_set_mesh_skin is not read then); the
- * last stage writes the scratch buffer of sr_scene_skin_mesh, and the result goes the way of sr_scene_update_mesh_device: applied
- * by the next sr_scene_set_instances, with the same SR_ERR_STATE window, the same stale host copy and the same emissive
- * handling. Each stage has a finite-position check word of its own (x, y, z of the stage's position; nothing else is looked at);
- * both are read back once, after the last kernel: on a bad vertex the call returns sr_scene_update_mesh's status and text with the
- * lowest offending index of either stage, and the scene is exactly as it was (only SrMeshMorphInfo.first_bad and
- * SrMeshSkinInfo.first_bad tell). Refused on the host before anything is launched: a null scene, an unknown key, a stage asked
+ * Like sr_scene_skin_mesh the call is a batch of one item on the path of sr_scene_pose_meshes (below). The morph stage compacts
+ * the weights that are not 0 into an active list (ascending target order; a target of weight 0 costs no traffic) and starts
+ * from the morph base. With a skin stage the one posing kernel keeps the morphed position, normal and tangent on chip and skins
+ * them in place of the bind pose (the snapshot of sr_scene_set_mesh_skin is not read then); the bytes are those of
+ * morph-then-skin through memory. The result goes the way of sr_scene_skin_mesh's: applied by the next sr_scene_set_instances,
+ * with the same SR_ERR_STATE window, the same stale host copy and the same emissive handling. Each stage has a finite-position
+ * check word of its own (x, y, z of the stage's position; nothing else is looked at); both are read back once, after the
+ * kernel: on a bad vertex the call returns sr_scene_update_mesh's status and text with the lowest offending index of either
+ * stage, and the scene is exactly as it was (only SrMeshMorphInfo / SrMeshSkinInfo tell: first_bad of every stage that ran,
+ * 0xFFFFFFFF where that stage found none, and n_active). Refused on the host before anything is launched: a null scene, an unknown key, a stage asked
  * for that the mesh has nothing attached for, another n_targets or n_joints than attached, a weight that is not finite (the
  * message names the lowest index) (SR_ERR_INVALID_ARG), an emissive list that is not one per triangle (SR_ERR_UNSUPPORTED).
  * The morph arithmetic, fp32 under the numerics contract (no contraction, correctly rounded divide and sqrt, left to right), for
@@ -615,7 +617,7 @@ typedef struct SrMeshMorphInfo {
     uint32_t posed;            /* accepted sr_scene_pose_mesh calls with a morph stage since the morph was attached */
     uint32_t n_active;         /* the last morph stage: weights that were not 0 */
     uint32_t first_bad;        /* the last morph stage: lowest vertex morphed to a non-finite position, 0xFFFFFFFF: none */
-    double morph_ms;           /* the last accepted pose: its kernels (morph, and skin where asked) + read-back (events, only while sr_scene_enable_timing is on) */
+    double morph_ms;           /* the last accepted pose: the posing kernel (morph, and skin where asked) + read-back (events, only while sr_scene_enable_timing is on) */
 } SrMeshMorphInfo;             /* 24 bytes */
 int sr_scene_mesh_morph_info(const SrScene* scene, uint64_t key, SrMeshMorphInfo* out);
 /* Batched posing: many meshes posed by one upload, one launch and one read-back (a crowd of small deforming meshes, in front of
@@ -632,7 +634,8 @@ int sr_scene_mesh_morph_info(const SrScene* scene, uint64_t key, SrMeshMorphInfo
  *     normal and tangent on chip between the stages; the bytes are those of morph-then-skin through memory.
  *   - All or nothing: if any item posed a vertex to a non-finite position the call returns sr_scene_update_mesh's status and text
  *     (behind the item prefix) for the lowest such item and that item's lowest such vertex of either stage, and no mesh of the
- *     batch has changed: neither bytes nor state nor counters. Only the first_bad of every stage that reported is recorded.
+ *     batch has changed: neither bytes nor state nor counters. Only the first_bad of every stage that reported is recorded
+ *     (the single calls record every stage that ran, as said above).
  *   - Accepted: one device wait (frames in flight read the old vertices), one scatter launch that copies every item's records
  *     from the scratch into its mesh's allocation, one wait, then, per item in item order, what sr_scene_update_mesh_device leaves
  *     behind on the host (stale host copy, the emissive handling of either SR_LIGHTS_* mode, the tree and structure marks).
@@ -644,7 +647,8 @@ typedef struct SrPoseItem {            /* one mesh of a batch; what sr_scene_pos
     uint32_t n_targets, n_joints;
 } SrPoseItem;                          /* 32 bytes */
 int sr_scene_pose_meshes(SrScene* scene, const SrPoseItem* items, uint32_t n_items, void* stream);
-typedef struct SrPoseBatchInfo {       /* the last sr_scene_pose_meshes that reached the device (a host refusal leaves it alone) */
+typedef struct SrPoseBatchInfo {       /* the last sr_scene_pose_meshes that reached the device (a host refusal leaves it alone, and
+                                        * so do sr_scene_skin_mesh and sr_scene_pose_mesh) */
     uint32_t items, blocks;            /* items of the call; blocks of the posing launch (256 vertices a block) */
     uint64_t vertices;                 /* records posed */
     uint32_t morph_only, skin_only, fused;   /* items by their stages */
@@ -1253,8 +1257,8 @@ int sr_renderer_update_mesh(SrRenderer* renderer, uint64_t key, const SrVertex* 
  * the same state. A refusal changes no replica. */
 int sr_renderer_update_mesh_device(SrRenderer* renderer, uint64_t key, const SrVertex* d_vertices, uint32_t n_vertices, void* stream);
 /* sr_scene_set_mesh_skin / sr_scene_skin_mesh through the facade: the rig is attached on the first device slot's scene only and
- * the mesh is posed there, once; every further slot's replica takes the validated posed vertices from that scene's scratch
- * buffer by a device-to-device (peer) copy, as with sr_renderer_update_mesh_device. A refusal changes no replica. */
+ * the mesh is posed there, once; every further slot's replica takes the validated posed vertices from that scene's batch
+ * scratch by a device-to-device (peer) copy, as with sr_renderer_pose_meshes. A refusal changes no replica. */
 int sr_renderer_set_mesh_skin(SrRenderer* renderer, uint64_t key, const SrSkinInfluence* influences, uint32_t n_vertices, uint32_t n_joints);
 int sr_renderer_skin_mesh(SrRenderer* renderer, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream);
 /* Attaches the rig of every skinned blas of a loaded scene (sr_gltf_blas_skin, sr_gltf_skin -> sr_renderer_set_mesh_skin) and
@@ -1268,7 +1272,8 @@ int sr_renderer_pose_scene(SrRenderer* renderer, const SrGltf* gltf, const SrLoa
                            SrTransform* instance_transforms_out, void* stream);
 /* sr_scene_set_mesh_morph / sr_scene_pose_mesh through the facade, as the skin calls above: the morph is attached on the first
  * device slot's scene only and the mesh is posed there, once (morph, then skin where joint matrices are given); every further
- * slot's replica takes the validated posed vertices by a device-to-device (peer) copy. A refusal changes no replica. */
+ * slot's replica takes the validated posed vertices from that scene's batch scratch by a device-to-device (peer) copy. A refusal
+ * changes no replica. */
 int sr_renderer_set_mesh_morph(SrRenderer* renderer, uint64_t key, const SrMorphDelta* deltas, uint32_t n_vertices, uint32_t n_targets);
 int sr_renderer_pose_mesh(SrRenderer* renderer, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices,
                           uint32_t n_joints, void* stream);
@@ -1283,7 +1288,7 @@ int sr_renderer_attach_morphs(SrRenderer* renderer, const SrGltf* gltf, const Sr
  * A refusal changes no replica. */
 int sr_renderer_pose_meshes(SrRenderer* renderer, const SrPoseItem* items, uint32_t n_items, void* stream);
 /* How sr_renderer_pose_scene poses a loaded scene's rigged and morphed meshes: SR_POSE_BATCH_OFF (the default), one
- * sr_renderer_skin_mesh / sr_renderer_pose_mesh per mesh; SR_POSE_BATCH_ON, all of them by one sr_renderer_pose_meshes.
+ * sr_renderer_skin_mesh / sr_renderer_pose_mesh per mesh (each a batch of one item); SR_POSE_BATCH_ON, all of them by one sr_renderer_pose_meshes.
  * SR_POSE_BATCH=on|off in the environment sets the initial mode when the renderer is created. */
 #define SR_POSE_BATCH_OFF 0u
 #define SR_POSE_BATCH_ON 1u

@@ -1,6 +1,6 @@
-"""Cost of one posing step of a crowd of small rigged meshes: the per-mesh loop (one sr_scene_pose_mesh per mesh: per mesh an
-upload or two, one or two memsets, one or two kernels, a read-back and three waits) against sr_scene_pose_meshes (one upload, one
-posing launch, one read-back, one scatter launch) in the same build.
+"""Cost of one posing step of a crowd of small rigged meshes: the per-mesh loop (one sr_scene_pose_mesh per mesh: each a batch
+of one item, with its own upload, memset, posing launch, read-back, scatter launch and three waits) against sr_scene_pose_meshes
+(one of each for the whole crowd) in the same build.
 
 Cases: 1, 10, 100 and 1 000 copies of a rigged sphere of 256 triangles (16 x 9, 130 vertices) and of 1 024 triangles (32 x 17, 514
 vertices), the sizes of the batched tree build's table, skinned with four joints; and 100 copies of the 1 024-triangle sphere with
@@ -9,7 +9,11 @@ beforehand, so that neither pays for Python's packing. Wall clock of the step wi
 device time: pose_ms + scatter_ms of the batch, the sum of the per-mesh skin_ms / morph_ms and copy_ms of the loop. Median
 (min - max) of REPS steps after WARMUP, the two paths alternating.
 
-  python scripts/gpu_pose_batch.py [--out profiles/pose_batch.json] [--only CASE] [--add-resources]
+  python scripts/gpu_pose_batch.py [--out profiles/pose_batch.json] [--only CASE]... [--label NAME] [--add-resources]
+
+--label NAME keeps the run under "runs"[NAME] of the output file next to the runs already there: two builds of the library
+(SUNRAY_HIP_LIB selects one) measured in one session, as profiles/pose_one_path.json holds the commit that made the single calls
+batches of one and its parent.
 """
 import argparse
 import ctypes as C
@@ -148,7 +152,8 @@ def measure(case):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pose_batch.json"))
-    ap.add_argument("--only")
+    ap.add_argument("--only", action="append", help="a case to run (may be given several times); default: all")
+    ap.add_argument("--label", help="keep this run under runs[LABEL] of the output file, next to the runs already there")
     ap.add_argument("--add-resources", action="store_true", help="add the compiler's resource report of pose_batch.hip to an existing file; no GPU")
     args = ap.parse_args()
     if args.add_resources:                               # on the machine that built the library: the compiler's report into the file
@@ -161,8 +166,11 @@ def main():
         return
     result = {"what": "one posing step: per-mesh sr_scene_pose_mesh loop against sr_scene_pose_meshes, wall clock and device (event) milliseconds",
               "reps": REPS, "warmup": WARMUP, "cases": {}}
+    if args.label:
+        whole = json.load(open(args.out)) if os.path.exists(args.out) else {"what": result["what"], "reps": REPS, "warmup": WARMUP, "runs": {}}
+        result = whole["runs"][args.label] = {"library": os.path.basename(os.environ.get("SUNRAY_HIP_LIB", "the product library")), "cases": {}}
     for case in CASES:
-        if args.only and case != args.only:
+        if args.only and case not in args.only:
             continue
         result["cases"][case] = measure(case)
         c = result["cases"][case]
@@ -170,7 +178,7 @@ def main():
             case, c["wall_ms"]["loop"]["median"], c["wall_ms"]["loop"]["min"], c["wall_ms"]["loop"]["max"],
             c["wall_ms"]["batch"]["median"], c["wall_ms"]["batch"]["min"], c["wall_ms"]["batch"]["max"], c["verdict"]), flush=True)
         with open(args.out, "w") as f:
-            json.dump(result, f, indent=1)
+            json.dump(whole if args.label else result, f, indent=1)
             f.write("\n")
     print(args.out)
 

@@ -24,10 +24,8 @@
 #include "kernels.h"
 #include "instances.h"
 #include "lights.h"
-#include "morph.h"
 #include "normals.h"
 #include "pose_batch.h"
-#include "skin.h"
 #include "tl_record.h"
 
 namespace {
@@ -259,20 +257,18 @@ struct SrScene {
     uint32_t blas_batch_mode = SR_BLAS_BATCH_OFF;    // sr_scene_set_mesh_tree_batch / SR_BLAS_BATCH in the environment
     SrMeshTreeBatchInfo batch_info{};       // the batched builds of the last sr_scene_set_instances
     DeviceBuffer d_batch_rows, d_batch_results;      // rows and result rows of a batched mesh-tree build (blas_batch.hip)
-    DeviceBuffer d_vertex_check;            // the check words the validation kernel and the posing kernels answer in (checked_launch)
-    DeviceBuffer d_skin_out, d_skin_matrices;   // sr_scene_skin_mesh: the posed vertices of the last call (scratch) and its joint matrices
-    // sr_scene_pose_mesh: the morphed vertices where a skin stage follows (scratch: srk_skin's `bind`; without one the morph stage
-    // writes d_skin_out itself), and the active list of the last call (n indices, then n weights)
-    DeviceBuffer d_morph_out, d_morph_active;
-    // sr_scene_pose_meshes: the staging block of the last call (pose_batch_plan.h lays it out), its check words (two per item) and
-    // the scratch every item's posed records go to; the keys and scratch offsets of the last accepted batch (the replicas of a
-    // renderer take the records from there), and the figures of the last call that reached the device
+    DeviceBuffer d_vertex_check;            // the check word the validation kernel and the frame kernels answer in (checked_launch)
+    // the pose path (sr_scene_skin_mesh, sr_scene_pose_mesh: one item; sr_scene_pose_meshes): the staging block of the last call
+    // (pose_batch_plan.h lays it out), its check words (two per item) and the scratch every item's posed records go to; the keys
+    // and scratch offsets of the last accepted call (the replicas of a renderer take the records from there; empty after a
+    // refused one), and the figures of the last sr_scene_pose_meshes that reached the device
     DeviceBuffer d_pose_stage, d_pose_check, d_pose_scratch;
     std::vector<uint64_t> pose_batch_keys, pose_batch_vertex_base;
     SrPoseBatchInfo pose_info{0, 0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0.0, 0.0, 0.0};
-    // sr_scene_update_mesh_positions*: the face vectors of the last call (one or two 16-byte pieces per triangle) and the uploaded
-    // positions of the host-pointer form; the records go to d_skin_out, the scratch every library producer leaves its result in
-    DeviceBuffer d_frame_faces, d_frame_positions;
+    // sr_scene_update_mesh_positions*: the face vectors of the last call (one or two 16-byte pieces per triangle), the uploaded
+    // positions of the host-pointer form, and the records the mesh-frame producer wrote (scratch: the replicas of a renderer take
+    // them from there)
+    DeviceBuffer d_frame_faces, d_frame_positions, d_frame_out;
     DeviceBuffer d_tl_inst, d_tl_instances;
     // top level built on the device (bvh_gpu.hip srk_tl_*): the instance boxes, its result block (the per-mesh rows are trees.d_tl_mesh_rows)
     DeviceBuffer d_tl_boxes, d_tl_result;
@@ -604,10 +600,25 @@ void mesh_vertices_changed(SrScene* s, uint32_t slot) {
     }
 }
 
-// The copy of validated device vertices into a mesh's allocation (sr_scene_update_mesh_device and the replicas of a renderer):
-// the device wait (frames in flight read the old vertices), the copy on the null stream, the host copy left behind, and for a
-// mesh with emissive entries the fetch at once under SR_LIGHTS_HOST (the light table is then host arithmetic on every
-// sr_scene_set_instances) or, under SR_LIGHTS_DEVICE, the mark that its arena slots are to be rewritten on the device.
+// What follows validated vertices that a copy or a kernel has just put into a mesh's device allocation in `copy_ms`: the host
+// copy left behind, and for a mesh with emissive entries the fetch at once under SR_LIGHTS_HOST (the light table is then host
+// arithmetic on every sr_scene_set_instances) or, under SR_LIGHTS_DEVICE, the mark that its arena slots are to be rewritten on
+// the device. mesh_vertices_changed comes after it.
+int device_vertices_taken(SrScene* s, uint32_t slot, double copy_ms) {
+    srh::HostMesh& m = s->meshes[slot];
+    m.copy_ms = copy_ms;
+    m.host_stale = true; m.last_from_device = true;
+    if (m.emissive_slots.empty()) return SR_OK;
+    if (s->light_mode == SR_LIGHTS_DEVICE) {                 // the arena positions follow on the device (sync_device_arena): no fetch
+        s->mesh_state[slot].arena_stale = true; s->mesh_state[slot].arena_pending = true;
+        return SR_OK;
+    }
+    return fetch_host_vertices(s, slot);
+}
+
+// The copy of validated device vertices into a mesh's allocation (sr_scene_update_mesh_device, the mesh frame and the replicas
+// of a renderer): the device wait (frames in flight read the old vertices), the copy on the null stream, then
+// device_vertices_taken.
 int take_device_vertices(SrScene* s, uint32_t slot, const SrVertex* d_vertices, int src_device) {
     srh::HostMesh& m = s->meshes[slot];
     const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
@@ -618,15 +629,9 @@ int take_device_vertices(SrScene* s, uint32_t slot, const SrVertex* d_vertices, 
                                            : hipMemcpyPeerAsync(m.d_vertices, s->device, d_vertices, src_device, bytes, nullptr);
     timer.end(nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    m.copy_ms = e == hipSuccess ? timer.ms() : 0.0;
+    if (e != hipSuccess) m.copy_ms = 0.0;
     HIP_TRY(e);
-    m.host_stale = true; m.last_from_device = true;
-    if (m.emissive_slots.empty()) return SR_OK;
-    if (s->light_mode == SR_LIGHTS_DEVICE) {                 // the arena positions follow on the device (sync_device_arena): no fetch
-        s->mesh_state[slot].arena_stale = true; s->mesh_state[slot].arena_pending = true;
-        return SR_OK;
-    }
-    return fetch_host_vertices(s, slot);
+    return device_vertices_taken(s, slot, timer.ms());
 }
 
 // SrMeshUpdateInfo of an update that entered at t0, copied between t1 and t2 and ends now.
@@ -653,7 +658,7 @@ int checked_launch(SrScene* s, hipStream_t st, uint32_t n_words, uint32_t* bad, 
     return SR_OK;
 }
 
-// The tail of every path that hands a mesh vertices already validated on a device (sr_scene_update_mesh_device, the pose path,
+// The tail of every path that hands a mesh vertices already validated on a device (sr_scene_update_mesh_device, the mesh frame,
 // the replicas of a renderer): the copy into the mesh's allocation, check_ms (the time of a validation kernel of its own, 0.0
 // where the check was part of the producer or ran on another scene), what follows from new vertices, and SrMeshUpdateInfo of a
 // call that entered at t0. The next device producer is its own refusals and kernels, checked_launch and this.
@@ -1028,66 +1033,7 @@ int check_pose_args(SrScene* s, uint64_t key, const float* weights, uint32_t n_t
     return check_emissive_list(s->meshes[*slot]);
 }
 
-// sr_scene_skin_mesh and sr_scene_pose_mesh, whose texts begin with `who`: sr_scene_update_mesh_device with the library's own
-// producers in front, in glTF's order, a morph stage (`weights`), a skin stage (`joint_matrices`) or both. The morph kernel reads
-// the morph base; with a skin stage it writes the scene's morph scratch, which the skinning kernel takes as its `bind` in place of
-// the bind pose, and the skinning kernel writes d_skin_out; without one the morph kernel writes d_skin_out itself. Posing and the
-// finite-position check are one pass over the bytes: each stage answers in a check word of its own (the morph stage in word 0,
-// the skin stage in the next), and all come back in one read after the last kernel.
-int pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream, const char* who) {
-    const auto t0 = std::chrono::steady_clock::now();
-    uint32_t slot = 0, n_active = 0;
-    std::vector<uint32_t> active;
-    int rc = check_pose_args(s, key, weights, n_targets, joint_matrices, n_joints, who, &slot, active, &n_active);
-    if (rc != SR_OK || (rc = bind_device(s)) != SR_OK) return rc;
-    srh::HostMesh& m = s->meshes[slot];
-    SrScene::MeshState::Morph& morph = s->mesh_state[slot].morph;
-    SrScene::MeshState::Skin& skin = s->mesh_state[slot].skin;
-    const size_t bytes = sizeof(SrVertex) * (size_t)m.n_vertices;
-    if ((rc = s->d_skin_out.reserve(bytes)) != SR_OK || (rc = s->d_vertex_check.reserve(16)) != SR_OK) return rc;
-    if (weights && (rc = s->d_morph_active.reserve(8 * (size_t)n_targets)) != SR_OK) return rc;
-    if (weights && joint_matrices && (rc = s->d_morph_out.reserve(bytes)) != SR_OK) return rc;
-    if (joint_matrices && (rc = s->d_skin_matrices.reserve(sizeof(SrTransform) * (size_t)n_joints)) != SR_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t skin_word = weights ? 1 : 0;
-    uint32_t bad[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
-    double ms = 0.0;
-    rc = checked_launch(s, st, 1 + skin_word, bad, &ms, weights ? "pose_mesh: a posing kernel failed: " : "skin_mesh: the skinning kernel failed: ", [&] {
-        int e = 0;
-        if (weights) e = (int)hipMemsetAsync(s->d_vertex_check.p, 0xFF, 8, st);     // the skin stage's word where there is none
-        if (e == 0 && weights) e = (int)hipMemcpyAsync(s->d_morph_active.p, active.data(), 8 * (size_t)n_targets, hipMemcpyHostToDevice, st);
-        if (e == 0 && joint_matrices) e = (int)hipMemcpyAsync(s->d_skin_matrices.p, joint_matrices, sizeof(SrTransform) * (size_t)n_joints, hipMemcpyHostToDevice, st);
-        return e;
-    }, [&](uint32_t* check) {
-        const SrVertex* bind = (const SrVertex*)skin.d_bind.p;
-        int k = 0;
-        if (weights) {
-            SrVertex* const morphed = (SrVertex*)(joint_matrices ? s->d_morph_out.p : s->d_skin_out.p);
-            k = srk_morph((const SrVertex*)morph.d_base.p, (const SrMorphDelta*)morph.d_deltas.p, (const uint32_t*)s->d_morph_active.p,
-                          (const float*)s->d_morph_active.p + n_targets, n_active, morphed, m.n_vertices, check, st);
-            bind = morphed;
-        }
-        if (k == 0 && joint_matrices) k = srk_skin(bind, (const SrSkinInfluence*)skin.d_influences.p, (const SrTransform*)s->d_skin_matrices.p,
-                                                   (SrVertex*)s->d_skin_out.p, m.n_vertices, check + skin_word, st);
-        return k;
-    });
-    if (rc != SR_OK) return rc;
-    if (weights) { morph.first_bad = bad[0] < m.n_vertices ? bad[0] : 0xFFFFFFFFu; morph.n_active = n_active; }
-    if (joint_matrices) skin.first_bad = bad[skin_word] < m.n_vertices ? bad[skin_word] : 0xFFFFFFFFu;
-    if (const uint32_t first_bad = std::min(bad[0], bad[1]); first_bad < m.n_vertices) return fail_non_finite_vertex(first_bad);
-    // check_ms 0.0: the check is part of the posing kernels, whose time is SrMeshMorphInfo.morph_ms or SrMeshSkinInfo.skin_ms
-    if ((rc = finish_device_update(s, slot, (const SrVertex*)s->d_skin_out.p, s->device, 0.0, t0)) != SR_OK) return rc;
-    if (weights) { morph.morph_ms = ms; morph.posed++; }
-    if (joint_matrices) { skin.skin_ms = weights ? 0.0 : ms; skin.skinned++; }     // two kernels are timed as one: morph_ms
-    return SR_OK;
-}
-
 }  // namespace
-
-int sr_scene_skin_mesh(SrScene* s, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
-    if (!s || !joint_matrices) return fail(SR_ERR_INVALID_ARG, "skin_mesh: null argument");
-    return pose_mesh(s, key, nullptr, 0, joint_matrices, n_joints, stream, "skin_mesh");
-}
 
 int sr_scene_mesh_skin_info(const SrScene* s, uint64_t key, SrMeshSkinInfo* out) {
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_skin_info: null argument");
@@ -1133,14 +1079,6 @@ int sr_scene_set_mesh_morph(SrScene* s, uint64_t key, const SrMorphDelta* deltas
     return SR_OK;
 }
 
-// The one per-frame call of a mesh with a morph, a skin or both (pose_mesh above); without weights it is sr_scene_skin_mesh.
-int sr_scene_pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
-    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_mesh: null argument (the scene)");
-    if (!weights && !joint_matrices) return fail(SR_ERR_INVALID_ARG, "pose_mesh: neither weights nor joint matrices given (one stage at least)");
-    if (!weights) return sr_scene_skin_mesh(s, key, joint_matrices, n_joints, stream);
-    return pose_mesh(s, key, weights, n_targets, joint_matrices, n_joints, stream, "pose_mesh");
-}
-
 int sr_scene_mesh_morph_info(const SrScene* s, uint64_t key, SrMeshMorphInfo* out) {
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_mesh_morph_info: null argument");
     uint32_t slot = 0;
@@ -1151,15 +1089,21 @@ int sr_scene_mesh_morph_info(const SrScene* s, uint64_t key, SrMeshMorphInfo* ou
     return SR_OK;
 }
 
+namespace {
+
+// The one posing path: sr_scene_pose_meshes (`batch`) and, with a list of one item, sr_scene_skin_mesh and sr_scene_pose_mesh.
 // Many meshes posed by one upload, one launch and one read-back (the header states the contract). Host checks for every item
-// first (check_pose_args, in the per-mesh call's words behind the item prefix), then the plan and the staging block, the posing
-// launch into the batch scratch, and for an accepted batch the device wait, the scatter launch and the per-mesh host tail.
-int sr_scene_pose_meshes(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream) {
+// first (check_pose_args), then the plan and the staging block, the posing launch into the batch scratch, and for an accepted
+// call the device wait, the scatter launch and the per-mesh host tail. *out takes the figures of a call that reached the
+// device (calls: one more than it held) and is left alone otherwise. What differs between the callers is stated here:
+//   - the words: the batch puts "pose_meshes: item <i>: " before every refusal of an item and names itself for a HIP failure; a
+//     single call refuses with no prefix and in the entry point's own words;
+//   - what a refusal for a non-finite vertex records: the batch the first_bad of the stages that reported, and no more; a single
+//     call the first_bad of every stage that ran (0xFFFFFFFF where that stage did not report) and n_active.
+int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream, bool batch, SrPoseBatchInfo* out) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_meshes: null argument (the scene)");
-    if (n_items == 0) return SR_OK;
-    if (!items) return fail(SR_ERR_INVALID_ARG, "pose_meshes: null argument (items, with n_items > 0)");
-    const auto prefix = [](uint32_t i) { return "pose_meshes: item " + std::to_string(i) + ": "; };
+    const auto prefix = [batch](uint32_t i) { return batch ? "pose_meshes: item " + std::to_string(i) + ": " : std::string(); };
+    const std::string who = batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
     std::vector<uint32_t> slots(n_items), counts(n_items), n_active(n_items), active_index, active;
     std::vector<float> active_weight;
     std::map<uint64_t, uint32_t> seen;
@@ -1190,7 +1134,7 @@ int sr_scene_pose_meshes(SrScene* s, const SrPoseItem* items, uint32_t n_items, 
     // the staging block: rows, block table, matrices, active lists
     std::vector<unsigned char> stage(lay.bytes, 0);
     srd::PoseBatchItem* rows = (srd::PoseBatchItem*)(stage.data() + lay.items);
-    SrPoseBatchInfo info{n_items, n_blocks, n_vertices, 0, 0, 0, 0, 0, s->pose_info.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, lay.bytes, 0.0, 0.0, 0.0};
+    SrPoseBatchInfo info{n_items, n_blocks, n_vertices, 0, 0, 0, 0, 0, out->calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, lay.bytes, 0.0, 0.0, 0.0};
     uint32_t matrix_base = 0, active_base = 0;
     for (uint32_t i = 0; i < n_items; i++) {
         const SrPoseItem& it = items[i];
@@ -1228,22 +1172,25 @@ int sr_scene_pose_meshes(SrScene* s, const SrPoseItem* items, uint32_t n_items, 
     if (e == 0) e = (int)hipMemcpyAsync(bad.data(), s->d_pose_check.p, 8 * (size_t)n_items, hipMemcpyDeviceToHost, st);
     pose_timer.end(st);
     if (e == 0) e = (int)hipStreamSynchronize(st);
-    if (e != 0) return fail(SR_ERR_HIP, std::string("pose_meshes: the posing kernel failed: ") + hipGetErrorString((hipError_t)e));
+    if (e != 0) return fail(SR_ERR_HIP, who + (batch ? ": the posing kernel failed: " : items[0].weights ? ": a posing kernel failed: " : ": the skinning kernel failed: ") +
+                                        hipGetErrorString((hipError_t)e));
     info.launches = 1; info.read_backs = 1; info.pose_ms = pose_timer.ms();
-    // all or nothing: the lowest item with a bad vertex refuses the batch; only the first_bad of the stages that reported is kept
+    // all or nothing: the lowest item with a bad vertex refuses the call
     for (uint32_t i = 0; i < n_items; i++) {
         const uint32_t bm = bad[2 * (size_t)i], bs = bad[2 * (size_t)i + 1];
         if (std::min(bm, bs) < counts[i] && info.refused_item == 0xFFFFFFFFu) { info.refused_item = i; info.refused_vertex = std::min(bm, bs); }
     }
     if (info.refused_item != 0xFFFFFFFFu) {
-        for (uint32_t i = 0; i < n_items; i++) {
+        for (uint32_t i = 0; i < n_items; i++) {                  // the two rules of the comment above
             SrScene::MeshState& ms = s->mesh_state[slots[i]];
-            if (bad[2 * (size_t)i] < counts[i]) ms.morph.first_bad = bad[2 * (size_t)i];
-            if (bad[2 * (size_t)i + 1] < counts[i]) ms.skin.first_bad = bad[2 * (size_t)i + 1];
+            const uint32_t bm = bad[2 * (size_t)i], bs = bad[2 * (size_t)i + 1];
+            if (bm < counts[i] || (!batch && items[i].weights)) ms.morph.first_bad = bm < counts[i] ? bm : 0xFFFFFFFFu;
+            if (bs < counts[i] || (!batch && items[i].joint_matrices)) ms.skin.first_bad = bs < counts[i] ? bs : 0xFFFFFFFFu;
+            if (!batch && items[i].weights) ms.morph.n_active = n_active[i];
         }
-        s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();      // the scratch holds a refused batch
+        s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();      // the scratch holds a refused call
         info.host_ms = ms_between(t0, std::chrono::steady_clock::now());
-        s->pose_info = info;
+        *out = info;
         fail_non_finite_vertex(info.refused_vertex);
         return fail(SR_ERR_INVALID_ARG, prefix(info.refused_item) + g_last_error);
     }
@@ -1254,19 +1201,15 @@ int sr_scene_pose_meshes(SrScene* s, const SrPoseItem* items, uint32_t n_items, 
     e = srk_pose_batch_scatter(d_rows, d_table, n_blocks, (const SrVertex*)s->d_pose_scratch.p, nullptr);
     scatter_timer.end(nullptr);
     if (e == 0) e = (int)hipStreamSynchronize(nullptr);
-    if (e != 0) return fail(SR_ERR_HIP, std::string("pose_meshes: the scatter kernel failed: ") + hipGetErrorString((hipError_t)e));
+    if (e != 0) return fail(SR_ERR_HIP, who + ": the scatter kernel failed: " + hipGetErrorString((hipError_t)e));
     info.launches = 2; info.scatter_ms = scatter_timer.ms();
     const auto t2 = std::chrono::steady_clock::now();
-    for (uint32_t i = 0; i < n_items; i++) {                   // the tail of take_device_vertices and finish_device_update, item by item
+    for (uint32_t i = 0; i < n_items; i++) {                   // the tail of finish_device_update, item by item
         const uint32_t slot = slots[i];
-        srh::HostMesh& m = s->meshes[slot];
         SrScene::MeshState& ms = s->mesh_state[slot];
-        m.copy_ms = info.scatter_ms; m.check_ms = 0.0;
-        m.host_stale = true; m.last_from_device = true;
-        if (!m.emissive_slots.empty()) {
-            if (s->light_mode == SR_LIGHTS_DEVICE) { ms.arena_stale = true; ms.arena_pending = true; }
-            else if ((rc = fetch_host_vertices(s, slot)) != SR_OK) return rc;
-        }
+        // check_ms 0.0: the check is part of the posing kernel, whose time is SrMeshMorphInfo.morph_ms or SrMeshSkinInfo.skin_ms
+        if ((rc = device_vertices_taken(s, slot, info.scatter_ms)) != SR_OK) return rc;
+        s->meshes[slot].check_ms = 0.0;
         mesh_vertices_changed(s, slot);
         if (items[i].weights) { ms.morph.first_bad = 0xFFFFFFFFu; ms.morph.n_active = n_active[i]; ms.morph.morph_ms = info.pose_ms; ms.morph.posed++; }
         if (items[i].joint_matrices) { ms.skin.first_bad = 0xFFFFFFFFu; ms.skin.skin_ms = items[i].weights ? 0.0 : info.pose_ms; ms.skin.skinned++; }
@@ -1274,8 +1217,34 @@ int sr_scene_pose_meshes(SrScene* s, const SrPoseItem* items, uint32_t n_items, 
     }
     note_update_times(s, t0, t1, t2);
     info.host_ms = ms_between(t0, std::chrono::steady_clock::now());
-    s->pose_info = info;
+    *out = info;
     return SR_OK;
+}
+
+// A single call is a batch of one item whose figures are dropped: sr_scene_pose_batch_info reads as before it.
+int pose_one(SrScene* s, const SrPoseItem& item, void* stream) {
+    SrPoseBatchInfo dropped{};
+    return pose_items(s, &item, 1, stream, false, &dropped);
+}
+
+}  // namespace
+
+int sr_scene_skin_mesh(SrScene* s, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
+    if (!s || !joint_matrices) return fail(SR_ERR_INVALID_ARG, "skin_mesh: null argument");
+    return pose_one(s, SrPoseItem{key, nullptr, joint_matrices, 0, n_joints}, stream);
+}
+
+// The one per-frame call of a mesh with a morph, a skin or both; without weights it is sr_scene_skin_mesh.
+int sr_scene_pose_mesh(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_mesh: null argument (the scene)");
+    return pose_one(s, SrPoseItem{key, weights, joint_matrices, n_targets, n_joints}, stream);
+}
+
+int sr_scene_pose_meshes(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_meshes: null argument (the scene)");
+    if (n_items == 0) return SR_OK;
+    if (!items) return fail(SR_ERR_INVALID_ARG, "pose_meshes: null argument (items, with n_items > 0)");
+    return pose_items(s, items, n_items, stream, true, &s->pose_info);
 }
 
 int sr_scene_pose_batch_info(const SrScene* s, SrPoseBatchInfo* out) {
@@ -1330,7 +1299,7 @@ int update_mesh_positions(SrScene* s, uint64_t key, const float* positions, uint
         return fail(SR_ERR_INVALID_ARG, "update_mesh_positions: the position pointer is not device memory of the scene's device for that many vertices");
     const bool tangents = (frame.flags & SR_FRAME_TANGENTS) != 0;
     const uint32_t n_triangles = m.n_indices / 3;
-    if ((rc = s->d_skin_out.reserve(record_bytes)) != SR_OK || (rc = s->d_vertex_check.reserve(16)) != SR_OK ||
+    if ((rc = s->d_frame_out.reserve(record_bytes)) != SR_OK || (rc = s->d_vertex_check.reserve(16)) != SR_OK ||
         (rc = s->d_frame_faces.reserve(16 * (size_t)n_triangles * (tangents ? 2 : 1))) != SR_OK) return rc;
     if (!on_device && (rc = s->d_frame_positions.reserve(bytes)) != SR_OK) return rc;
     const float* d_positions = on_device ? positions : (const float*)s->d_frame_positions.p;
@@ -1342,13 +1311,13 @@ int update_mesh_positions(SrScene* s, uint64_t key, const float* positions, uint
                         [&](uint32_t* check) {
                             return srk_mesh_frame((const SrVertex*)frame.d_reference.p, d_positions, (const uint32_t*)m.d_indices, (const srh::FrameTriUv*)frame.d_tri_uv.p,
                                                   (const uint32_t*)frame.d_offsets.p, (const uint32_t*)frame.d_entries.p, (const float*)frame.d_side.p, frame.flags,
-                                                  (float4*)s->d_frame_faces.p, (SrVertex*)s->d_skin_out.p, n_vertices, n_triangles, check, st);
+                                                  (float4*)s->d_frame_faces.p, (SrVertex*)s->d_frame_out.p, n_vertices, n_triangles, check, st);
                         });
     if (rc != SR_OK) return rc;
     frame.first_bad = bad < n_vertices ? bad : 0xFFFFFFFFu;
     if (bad < n_vertices) return fail_non_finite_vertex(bad);
     // check_ms 0.0: the check is part of the vertex kernel, whose time is SrMeshFrameInfo.frame_ms
-    if ((rc = finish_device_update(s, slot, (const SrVertex*)s->d_skin_out.p, s->device, 0.0, t0)) != SR_OK) return rc;
+    if ((rc = finish_device_update(s, slot, (const SrVertex*)s->d_frame_out.p, s->device, 0.0, t0)) != SR_OK) return rc;
     frame.frame_ms = ms; frame.updates++;
     return SR_OK;
 }
@@ -3285,10 +3254,10 @@ int srh::scene_take_device_vertices(SrScene* s, uint64_t key, const SrVertex* d_
     return finish_device_update(s, slot, d_vertices, src_device, 0.0, t0);      // check_ms 0.0: validated once, on the first scene
 }
 
-const SrVertex* srh::scene_skinned_vertices(const SrScene* s, uint64_t key, uint32_t* n_vertices) {
+const SrVertex* srh::scene_mesh_frame_vertices(const SrScene* s, uint64_t key, uint32_t* n_vertices) {
     auto it = s->slots.find(key);
     *n_vertices = it == s->slots.end() ? 0u : s->meshes[it->second].n_vertices;
-    return (const SrVertex*)s->d_skin_out.p;
+    return (const SrVertex*)s->d_frame_out.p;
 }
 
 const SrVertex* srh::scene_pose_batch_vertices(const SrScene* s, uint32_t item, uint32_t* n_vertices) {

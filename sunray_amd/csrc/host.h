@@ -126,11 +126,12 @@ int scene_take_device_vertices(SrScene* scene, uint64_t key, const SrVertex* d_v
 // A further replica of a renderer takes an instance list whose transforms sr_scene_set_instances_device has accepted on
 // `src_device` (api.cpp): a copy into a buffer of the replica's own (peer copy across devices) and the same call there.
 int scene_set_instances_from(SrScene* scene, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* d_transforms, int src_device);
-// The scratch buffer on the scene's device that the last accepted call of a library producer (sr_scene_skin_mesh, sr_scene_pose_mesh,
-// sr_scene_update_mesh_positions*) wrote its records into (api.cpp): what the further replicas of a renderer take through
-// scene_take_device_vertices, and the vertex count of the mesh `key` that was produced. Valid until the scene's next such call.
-const SrVertex* scene_skinned_vertices(const SrScene* scene, uint64_t key, uint32_t* n_vertices);
-// The same for item `item` of the last accepted sr_scene_pose_meshes: its records in the batch scratch and their count (NULL and 0
-// where the last batch was refused or had fewer items). Valid until the scene's next sr_scene_pose_meshes.
+// The scratch buffer on the scene's device that the last accepted sr_scene_update_mesh_positions* wrote its records into
+// (api.cpp): what the further replicas of a renderer take through scene_take_device_vertices, and the vertex count of the mesh
+// `key` that was produced. Valid until the scene's next such call.
+const SrVertex* scene_mesh_frame_vertices(const SrScene* scene, uint64_t key, uint32_t* n_vertices);
+// The same for item `item` of the scene's last accepted pose call (sr_scene_pose_meshes; sr_scene_skin_mesh and sr_scene_pose_mesh
+// leave one item): its records in the batch scratch and their count (NULL and 0 where the last call was refused or had fewer
+// items). Valid until the scene's next pose call.
 const SrVertex* scene_pose_batch_vertices(const SrScene* scene, uint32_t item, uint32_t* n_vertices);
 }  // namespace srh

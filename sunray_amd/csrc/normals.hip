@@ -33,7 +33,7 @@ __global__ void __launch_bounds__(kTileBlock) face_frame_kernel(const float* __r
     faces[(uint64_t)t * 2 + 1] = T;
 }
 
-// One vertex per thread on the tile of vertex_tile.h, like skin_kernel and morph_kernel: the reference records are turned by the
+// One vertex per thread on the tile of vertex_tile.h, like pose_batch_kernel: the reference records are turned by the
 // LDS and every byte this kernel does not write is the reference's. A thread reads its own position (12 bytes, the lanes of a wave
 // together whole cache lines), walks its run and gathers one or two dwordx4 per entry. The sums are the thread's own, in run order.
 template <bool kTangents>

@@ -1,5 +1,6 @@
-// Posing of many skinned and morphed meshes in one launch (sr_scene_pose_meshes): every tile of every item of a batch is one
-// block of one grid. The arithmetic is that of skin_kernel and morph_kernel (pose_device.h), the tile that of vertex_tile.h.
+// Posing of skinned and morphed meshes in one launch (sr_scene_pose_meshes; sr_scene_skin_mesh and sr_scene_pose_mesh with one
+// item): every tile of every item of a batch is one block of one grid. The arithmetic is skin_vertex and morph_vertex of
+// pose_device.h, the tile that of vertex_tile.h.
 // fp32 under the numerics contract of DESIGN.md §3: no contraction, correctly rounded divide and sqrt, left to right.
 #include "pose_batch.h"
 

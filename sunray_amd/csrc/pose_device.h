@@ -1,5 +1,5 @@
-// The per-vertex arithmetic of posing on the device, defined once: skin_kernel (skin.hip), morph_kernel (morph.hip) and
-// pose_batch_kernel (pose_batch.hip) call these bodies on a thread's own row of the tile of vertex_tile.h. include/sunray_hip.h
+// The per-vertex arithmetic of posing on the device, defined once: pose_batch_kernel (pose_batch.hip), the one
+// posing kernel, calls these bodies on a thread's own row of the tile of vertex_tile.h. include/sunray_hip.h
 // states the arithmetic to the letter (sr_scene_skin_mesh, sr_scene_pose_mesh). fp32 under the numerics contract of DESIGN.md §3:
 // no contraction, correctly rounded divide and sqrt, left to right.
 #pragma once

@@ -192,16 +192,32 @@ int each_scene(SrRenderer* r, Call call) {
 
 // Device-produced vertices for every replica: `produce` runs on the first slot's scene, which validates once; the further
 // replicas take the validated bytes (srh::scene_take_device_vertices: device-to-device or peer copy, the same state, no host
-// staging) from `src`, or with src == NULL from that scene's scratch buffer, where the library's own producers leave them.
+// staging) from `src`, or with src == NULL from that scene's scratch buffer, where the mesh-frame producer leaves them.
 // What the first scene refuses changes none, and leaves the instance list as valid as it was.
 template <class Produce>
 int first_scene_produces(SrRenderer* r, uint64_t key, const SrVertex* src, uint32_t n_vertices, Produce produce) {
     int rc = produce(r->slot[0].scene);
     if (rc != SR_OK) return rc;
     r->instances_valid = false;
-    if (!src) src = srh::scene_skinned_vertices(r->slot[0].scene, key, &n_vertices);
+    if (!src) src = srh::scene_mesh_frame_vertices(r->slot[0].scene, key, &n_vertices);
     for (size_t i = 1; rc == SR_OK && i < r->slot.size(); i++) rc = srh::scene_take_device_vertices(r->slot[i].scene, key, src, n_vertices, r->device);
     return rc;
+}
+
+// The same for the pose calls: `pose` runs on the first slot's scene, which poses and validates every item once; the further
+// replicas take item k's records (the mesh key_of(k)) from that scene's batch scratch, mesh by mesh.
+template <class KeyOf, class Pose>
+int first_scene_poses(SrRenderer* r, uint32_t n_items, KeyOf key_of, Pose pose) {
+    int rc = pose(r->slot[0].scene);
+    if (rc != SR_OK || n_items == 0) return rc;
+    r->instances_valid = false;
+    for (size_t i = 1; i < r->slot.size(); i++)
+        for (uint32_t k = 0; k < n_items; k++) {
+            uint32_t n_vertices = 0;
+            const SrVertex* src = srh::scene_pose_batch_vertices(r->slot[0].scene, k, &n_vertices);
+            if ((rc = srh::scene_take_device_vertices(r->slot[i].scene, key_of(k), src, n_vertices, r->device)) != SR_OK) return rc;
+        }
+    return SR_OK;
 }
 
 // What attach_skins, attach_morphs and pose_scene (`who`) refuse first: a loaded scene that does not come from this file. The
@@ -641,10 +657,10 @@ int sr_renderer_set_mesh_skin(SrRenderer* r, uint64_t key, const SrSkinInfluence
     return sr_scene_set_mesh_skin(r->slot[0].scene, key, influences, n_vertices, n_joints);
 }
 
-// sr_scene_skin_mesh on the first slot's scene, which poses and validates once (first_scene_produces).
+// sr_scene_skin_mesh on the first slot's scene, which poses and validates once (first_scene_poses, one item).
 int sr_renderer_skin_mesh(SrRenderer* r, uint64_t key, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "skin_mesh: null argument (the renderer)");
-    return first_scene_produces(r, key, nullptr, 0, [&](SrScene* sc) { return sr_scene_skin_mesh(sc, key, joint_matrices, n_joints, stream); });
+    return first_scene_poses(r, 1, [&](uint32_t) { return key; }, [&](SrScene* sc) { return sr_scene_skin_mesh(sc, key, joint_matrices, n_joints, stream); });
 }
 
 // A mesh's morph lives on the first slot's scene only, like its rig.
@@ -653,26 +669,17 @@ int sr_renderer_set_mesh_morph(SrRenderer* r, uint64_t key, const SrMorphDelta* 
     return sr_scene_set_mesh_morph(r->slot[0].scene, key, deltas, n_vertices, n_targets);
 }
 
-// sr_scene_pose_mesh on the first slot's scene, which morphs, skins and validates once (first_scene_produces).
+// sr_scene_pose_mesh on the first slot's scene, which morphs, skins and validates once (first_scene_poses, one item).
 int sr_renderer_pose_mesh(SrRenderer* r, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, void* stream) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "pose_mesh: null argument (the renderer)");
-    return first_scene_produces(r, key, nullptr, 0, [&](SrScene* sc) { return sr_scene_pose_mesh(sc, key, weights, n_targets, joint_matrices, n_joints, stream); });
+    return first_scene_poses(r, 1, [&](uint32_t) { return key; }, [&](SrScene* sc) { return sr_scene_pose_mesh(sc, key, weights, n_targets, joint_matrices, n_joints, stream); });
 }
 
 // sr_scene_pose_meshes on the first slot's scene, which poses and validates the whole batch once; the further replicas take each
-// item's records from that scene's batch scratch, mesh by mesh (first_scene_produces does the same for one mesh).
+// item's records from that scene's batch scratch, mesh by mesh (first_scene_poses).
 int sr_renderer_pose_meshes(SrRenderer* r, const SrPoseItem* items, uint32_t n_items, void* stream) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "pose_meshes: null argument (the renderer)");
-    int rc = sr_scene_pose_meshes(r->slot[0].scene, items, n_items, stream);
-    if (rc != SR_OK || n_items == 0) return rc;
-    r->instances_valid = false;
-    for (size_t i = 1; i < r->slot.size(); i++)
-        for (uint32_t k = 0; k < n_items; k++) {
-            uint32_t n_vertices = 0;
-            const SrVertex* src = srh::scene_pose_batch_vertices(r->slot[0].scene, k, &n_vertices);
-            if ((rc = srh::scene_take_device_vertices(r->slot[i].scene, items[k].key, src, n_vertices, r->device)) != SR_OK) return rc;
-        }
-    return SR_OK;
+    return first_scene_poses(r, n_items, [&](uint32_t k) { return items[k].key; }, [&](SrScene* sc) { return sr_scene_pose_meshes(sc, items, n_items, stream); });
 }
 
 // How sr_renderer_pose_scene poses (SR_POSE_BATCH_*).

@@ -1,5 +1,5 @@
-// The tile scaffold of the kernels that produce or check a mesh's vertices on the device (skin_kernel, morph_kernel,
-// pose_batch_kernel, vertex_check_kernel): constants, the turn of a tile of records through the LDS, and the report of the lowest bad vertex.
+// The tile scaffold of the kernels that produce or check a mesh's vertices on the device (pose_batch_kernel,
+// vertex_frame_kernel, vertex_check_kernel): constants, the turn of a tile of records through the LDS, and the report of the lowest bad vertex.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,7 @@
 """Scene.set_mesh_morph / Scene.pose_mesh / Renderer.attach_morphs / Renderer.pose_scene (sr_scene_pose_mesh: a mesh's morph targets
-blended on the device by morph_kernel, its finite-position check fused, the result handed to the unchanged skinning kernel where
-the mesh is rigged too and then on as sr_scene_update_mesh_device hands on its caller's vertices). The reference is
+blended on the device by the morph stage of pose_batch_kernel (the call is a batch of one item), its finite-position check fused,
+the skin stage following in the same kernel where the mesh is rigged too, and the result handed on as sr_scene_update_mesh_device
+hands on its caller's vertices). The reference is
 tests/morph_reference.py: the header's arithmetic restated in numpy float32, composed with tests/skin_reference.py's model where
 a skin follows. Equal means byte for byte."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """Scene.set_mesh_skin / Scene.skin_mesh / Renderer.attach_skins / Renderer.pose_scene (sr_scene_skin_mesh: a rigged mesh posed on
-the device by skin_kernel, its finite-position check fused, the result handed on as sr_scene_update_mesh_device hands on its
+the device by the skin stage of pose_batch_kernel (the call is a batch of one item), its finite-position check fused, the result handed on as sr_scene_update_mesh_device hands on its
 caller's vertices). The reference is tests/skin_reference.py: the header's arithmetic restated in numpy float32. Equal means
 byte for byte."""
 import ctypes as C

@@ -1,7 +1,8 @@
 """Scene.pose_meshes / Renderer.pose_meshes / Renderer.set_pose_batch (sr_scene_pose_meshes: many skinned and morphed meshes posed
-by one upload, one launch of pose_batch_kernel and one read-back). The references are tests/skin_reference.py and
-tests/morph_reference.py, the header's arithmetic restated in numpy float32, and a twin scene posed mesh by mesh with pose_mesh.
-Equal means byte for byte."""
+by one upload, one launch of pose_batch_kernel and one read-back; Scene.skin_mesh and Scene.pose_mesh are batches of one item on
+the same path). The references are tests/skin_reference.py and tests/morph_reference.py, the header's arithmetic restated in numpy
+float32; a twin scene posed mesh by mesh with pose_mesh runs the same kernel and shows only that the book-keeping agrees. Equal
+means byte for byte."""
 import ctypes as C
 import functools
 import os
@@ -420,6 +421,144 @@ def test_pose_scene_with_the_batch_equals_pose_scene_without(rt, hip, devices, f
         assert_equal(xo, yo, "frame %d output" % f)
     assert min((x[0] & 0xFFFFFF != 0).mean() for x in want) > 0.05
     assert not np.array_equal(want[0][0], want[2][0])
+
+
+# ---- 8. the single entry points are batches of one -------------------------------------------------------------------------------------------
+EDGE_SIZES = (3, 255, 256, 257, 513)            # below a tile, one short of it, exactly one, one over, one over two
+
+
+@functools.lru_cache(maxsize=None)
+def edge_meshes():
+    """Meshes of EDGE_SIZES vertices, keys 1..5, made as test_gpu_mesh_morph.base_meshes makes its own (scattered positions, unit
+    normals and tangents, uv sets, pad canaries; the triangles (i, i + 1, i + 2)), with two morph targets and a rig of two joints
+    each -> (desc, {key: (deltas, influences)})."""
+    desc = scenes.SceneDesc("tile_edges")
+    grey = abi.material(base_color=(0.8, 0.8, 0.8, 1.0), roughness=0.5)
+    for k, n in enumerate(EDGE_SIZES, start=1):
+        i = np.arange(n)
+        v = np.zeros(n, dtype=abi.VERTEX)
+        v["position"] = np.stack([_hash01(i, 31 + k) * 2 - 1, _hash01(i, 32 + k) * 2 - 1, _hash01(i, 33 + k) - 0.5], axis=1)
+        for name, salt in (("normal", 40), ("tangent", 50)):
+            d = np.stack([_hash01(i, salt) - 0.5, _hash01(i, salt + 1) - 0.5, _hash01(i, salt + 2) + 0.25], axis=1).astype(np.float32)
+            v[name][:, :3] = d / np.sqrt((d * d).sum(axis=1, dtype=np.float32))[:, None]
+        v["tangent"][:, 3] = np.where(i % 3 == 0, -1.0, 1.0)
+        for c, name in enumerate(("base_color", "metallic_roughness", "normal", "occlusion", "emissive")):
+            v[name + "_tex_coord"] = np.stack([_hash01(i, 10 + c), _hash01(i, 20 + c)], axis=1)
+        w = v.view(np.uint32).reshape(n, -1)
+        w[:, 3], w[:, 7], w[:, 22], w[:, 23] = 0x7FC00000 + i, 0xFF800000, 0xDEADBEEF, i
+        idx = np.stack([i[:-2], i[:-2] + 1, i[:-2] + 2], axis=1).ravel().astype(np.uint32)
+        desc.meshes.append(scenes.MeshDesc(k, v, idx, grey))
+        desc.instances.append((k, [scenes.translate(3.0 * (k - 1), 0.0, 0.0)]))
+    data = {m.key: (targets(m.vertices, 2, 3 * k), rig(len(m.vertices), 2, k)) for k, m in enumerate(desc.meshes)}
+    return desc, data
+
+
+def test_single_calls_equal_the_models_at_tile_edges(rt, hip):
+    """skin_mesh, pose_mesh(weights) and pose_mesh(weights, matrices) are batches of one item on pose_batch_kernel: at every vertex
+    count around the tile of 256 the device bytes are the numpy models', record for record, the per-mesh figures are those of a
+    single call, and sr_scene_pose_batch_info never hears of them."""
+    desc, data = edge_meshes()
+    sc = rt.Scene(0).load(desc)
+    w, M = np.array([0.625, 0.0], np.float32), matrices(2)
+    for slot, m in enumerate(desc.meshes):
+        n, (d, inf) = len(m.vertices), data[m.key]
+        sc.set_mesh_skin(m.key, inf, 2)
+        sc.set_mesh_morph(m.key, d)
+        morphed, bad, _ = mref.morph_model(m.vertices, d, w)
+        assert bad is None
+        ways = (("skin_mesh", lambda: sc.skin_mesh(m.key, M), sref.skin_model(m.vertices, inf, M), (0, 0, 1)),
+                ("pose_mesh, morph", lambda: sc.pose_mesh(m.key, w), (morphed, None), (1, 1, 1)),
+                ("pose_mesh, morph and skin", lambda: sc.pose_mesh(m.key, w, M), sref.skin_model(morphed, inf, M), (2, 1, 2)))
+        for what, call, model, (posed, n_active, skinned) in ways:
+            what = "%d vertices, %s" % (n, what)
+            assert model[1] is None, what
+            call()
+            assert_records_equal(device_vertices(hip, sc, slot, n), model[0], what)
+            assert device_vertices(hip, sc, slot, n).tobytes() != m.vertices.tobytes(), what
+            assert flags(sc, m.key) == (1, 1, 0), what
+            mi, si = sc.mesh_morph_info(m.key), sc.mesh_skin_info(m.key)
+            assert (mi.n_targets, mi.posed, mi.n_active, mi.first_bad) == (2, posed, n_active, NONE), what
+            assert (si.n_joints, si.skinned, si.first_bad) == (2, skinned, NONE), what
+            assert sc.pose_batch_info().calls == 0, what
+    sc.close()
+
+
+def test_single_calls_and_batches_interleave_like_batches_alone(rt, hip):
+    """One scene takes pose_mesh(A), pose_meshes([B, C]), a pose_mesh(C) refused for a non-finite vertex and skin_mesh(B); its twin
+    takes the same poses through pose_meshes alone. After every step the device bytes of all meshes, the per-mesh figures and the
+    flags are the twin's and the posed meshes are the models'; the refusal is the single call's, with the model's vertex; only the
+    batch of step 2 shows in pose_batch_info; and both scenes build and trace alike."""
+    full, _ = mesh_set()
+    A, B, C = 6, 8, 9                                                # 257, 256 and 512 vertices
+    desc = scenes.SceneDesc("interleaved")
+    desc.meshes = [m for m in full.meshes if m.key in (A, B, C)]
+    desc.instances = [(key, [scenes.translate(3.0 * k, 0.0, 0.0)]) for k, key in enumerate((A, B, C))]
+    keys = [m.key for m in desc.meshes]
+    assert keys == [A, B, C] and max(len(m.vertices) for m in desc.meshes) <= 600
+    verts = {m.key: m.vertices for m in desc.meshes}
+    lean = (300, 450)                                                # two vertices of every mesh lean on joint 2, nothing else does
+    rigs, morphs = {}, {}
+    for k, key in enumerate(keys):
+        inf = rig(len(verts[key]), 2, k).copy()
+        inf["joint"][inf["weight"] == 0] = 0
+        for v in lean if key == C else ():
+            inf["joint"][v], inf["weight"][v] = (2, 0, 0, 0), (1.0, 0, 0, 0)
+        rigs[key], morphs[key] = inf, targets(verts[key], 2, 3 * k)
+    w = np.array([0.0, -0.75], np.float32)
+    M = np.concatenate([matrices(2), matrices(2)[:1]])
+    bad_M = M.copy()
+    bad_M[2, 1, 3] = np.inf
+    sc, tw = rt.Scene(0).load(desc), rt.Scene(0).load(desc)
+    for s in (sc, tw):
+        for key in keys:
+            s.set_mesh_skin(key, rigs[key], 3)
+            s.set_mesh_morph(key, morphs[key])
+        s.set_instances(desc.instances)
+
+    def model(key, morph, skin, matrices_=M):
+        v, bad = verts[key], None
+        if morph:
+            v, bad, _ = mref.morph_model(v, morphs[key], w)
+            assert bad is None
+        if skin:
+            v, bad, _ = sref.skin_model(v, rigs[key], matrices_)
+        return v, bad
+
+    def state(s):
+        return ([device_vertices(hip, s, slot, len(m.vertices)).tobytes() for slot, m in enumerate(desc.meshes)], pose_infos(s, keys),
+                [flags(s, k) for k in keys])
+
+    def same(what, posed):
+        assert state(sc) == state(tw), what
+        for key, morph, skin in posed:
+            want, bad = model(key, morph, skin)
+            assert bad is None
+            assert_records_equal(device_vertices(hip, sc, keys.index(key), len(want)), want, "%s: key %d against the model" % (what, key))
+
+    fresh = info_tuple(sc.pose_batch_info(), times=True)
+    assert fresh[8] == 0
+    sc.pose_mesh(A, w, M); tw.pose_meshes([(A, w, M)])
+    same("step 1, pose_mesh(A)", [(A, True, True)])
+    assert info_tuple(sc.pose_batch_info(), times=True) == fresh
+    sc.pose_meshes([(B, w, None), (C, w, M)]); tw.pose_meshes([(B, w, None), (C, w, M)])
+    same("step 2, pose_meshes([B, C])", [(A, True, True), (B, True, False), (C, True, True)])
+    batch = info_tuple(sc.pose_batch_info(), times=True)
+    assert batch[:3] + batch[6:11] == (2, 3, 256 + 512, 2, 1, 1, NONE, NONE)
+    worst = model(C, True, True, bad_M)[1]
+    assert worst == lean[0]
+    assert refused(rt, sc, lambda: sc.pose_mesh(C, w, bad_M)) == (ERR_INVALID_ARG, "update_mesh: vertex %d has a non-finite position" % worst)
+    assert refused(rt, tw, lambda: tw.pose_meshes([(C, w, bad_M)])) == (ERR_INVALID_ARG, "pose_meshes: item 0: update_mesh: vertex %d has a non-finite position" % worst)
+    same("step 3, a refused pose_mesh(C)", [(A, True, True), (B, True, False), (C, True, True)])
+    assert sc.mesh_skin_info(C).first_bad == worst and sc.mesh_morph_info(C).first_bad == NONE
+    assert info_tuple(sc.pose_batch_info(), times=True) == batch
+    sc.skin_mesh(B, M); tw.pose_meshes([(B, None, M)])
+    same("step 4, skin_mesh(B)", [(A, True, True), (B, False, True), (C, True, True)])
+    assert info_tuple(sc.pose_batch_info(), times=True) == batch
+    rays = ray_grid((-1.5, -1.5), (3.0 * 2 + 1.5, 1.5), 96, 24)
+    rd = rt.rays_to_device(rays)
+    sc.set_instances(desc.instances); tw.set_instances(desc.instances)
+    assert_scenes_equal(rt, tw, sc, rays, rd, keys, "after the interleaved calls")
+    sc.close(); tw.close()
 
 
 CHILD = """

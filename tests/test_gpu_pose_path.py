@@ -1,5 +1,5 @@
-"""What the device producers of a mesh's vertices share (api.cpp checked_launch / finish_device_update, renderer.cpp
-first_scene_produces) and no other suite pins: which timing field each call writes, and that pose_mesh without weights is
+"""What the device producers of a mesh's vertices share (api.cpp pose_items / finish_device_update, renderer.cpp
+first_scene_poses / first_scene_produces) and no other suite pins: which timing field each call writes, and that pose_mesh without weights is
 skin_mesh. Times are compared with 0.0 only, never by magnitude. The meshes are the tile and wave edges of the posing kernels."""
 import os
 import sys

@@ -305,4 +305,4 @@ def test_frame_kernels_are_in_the_resource_report():
     for r in face + vertex:
         assert r["scratch"] == 0 and r["vgpr_spills"] == 0 and r["sgpr_spills"] == 0, r
     assert all(r["lds"] == 256 * 7 * 16 and r["occupancy"] >= 4 for r in vertex) and all(r["lds"] == 0 for r in face)
-    assert any("morph_kernel" in name for name in build.kernel_resources("morph.hip"))     # that report is still its own
+    assert any("pose_batch_kernel" in name for name in build.kernel_resources("pose_batch.hip"))     # that report is still its own

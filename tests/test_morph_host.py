@@ -120,12 +120,12 @@ def test_pose_mesh_wrappers_refuse_before_the_library_is_called(monkeypatch, met
 
 
 def test_morph_kernel_is_in_the_resource_report():
-    """The compiler's report for morph.hip is kept next to the object: the kernel needs no scratch and spills nothing; its LDS is
-    the tile of 256 vertices, seven 16-byte slots each."""
+    """The compiler's report for pose_batch.hip, whose pose_batch_kernel morphs (sr_scene_pose_mesh is a batch of one item), is kept
+    next to the object: the kernel needs no scratch and spills nothing; its LDS is the tile of 256 vertices, seven 16-byte slots each."""
     from sunray_amd import build
-    res = build.kernel_resources("morph.hip")
-    mine = [r for name, r in res.items() if "morph_kernel" in name]
+    res = build.kernel_resources("pose_batch.hip")
+    mine = [r for name, r in res.items() if "pose_batch_kernel" in name]
     assert len(mine) == 1, sorted(res)
     assert mine[0]["scratch"] == 0 and mine[0]["vgpr_spills"] == 0 and mine[0]["sgpr_spills"] == 0, mine[0]
     assert mine[0]["lds"] == 256 * 7 * 16 and mine[0]["occupancy"] >= 4, mine[0]
-    assert any("skin_kernel" in name for name in build.kernel_resources("skin.hip"))      # that report is still its own
+    assert any("vertex_frame_kernel" in name for name in build.kernel_resources("normals.hip"))      # that report is still its own
