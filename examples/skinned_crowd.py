@@ -3,7 +3,11 @@ are evaluated at its own time offset into the animation (Gltf.pose, host arithme
 skinned meshes go to the GPU in a single Renderer.pose_meshes: one upload, one posing kernel over every tile of every mesh, one
 read-back. The trees of the small meshes are built by the batched device build (set_mesh_tree_batch). Writes the last frame as a PNG.
 
-    python examples/skinned_crowd.py [--copies 64] [--frames 24] [--size 640x480] [--out crowd.png]
+With --device-clips the animation is evaluated on the GPU too: the clip is baked once (Gltf.bake_clip) and attached once
+(Renderer.attach_clip); a frame then sets every copy's time and calls Renderer.pose_actors, whose clip kernel writes the joint
+matrices where the posing kernel reads them and the instance transforms into a tensor that render_device_transforms takes.
+
+    python examples/skinned_crowd.py [--copies 64] [--frames 24] [--size 640x480] [--out crowd.png] [--device-clips]
 
 Needs a GPU: the product path has no CPU fallback.
 """
@@ -24,6 +28,7 @@ def main():
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--size", default="640x480")
     ap.add_argument("--out", default="crowd.png")
+    ap.add_argument("--device-clips", action="store_true", help="evaluate the animation on the GPU from a baked clip")
     args = ap.parse_args()
     from sunray_amd import runtime as rt
     w, h = (int(v) for v in args.size.split("x"))
@@ -42,6 +47,8 @@ def main():
     print("%d copies of '%s' (%.3f s): %d skinned meshes posed per frame by one launch" % (args.copies, name, duration, len(skinned) * args.copies))
     camera = ((0.8, 2.5 + 0.9 * side, 7.0 + 1.5 * side), (0.8, 1.0, -1.5 * side), 45.0)
     instances = []
+    if args.device_clips:
+        return device_clips(args, rt, gltf, r, copies, skinned, duration, camera)
     for f in range(args.frames):
         items, instances = [], []
         for c, (loaded, dx, dz) in enumerate(copies):
@@ -57,6 +64,36 @@ def main():
     info = r.replica_scene(0).pose_batch_info()
     print("last batch: %d items, %d vertices in %d blocks, %d bytes uploaded, %d launches, %d read-back, %.3f ms on the host" % (
         info.items, info.vertices, info.blocks, info.upload_bytes, info.launches, info.read_backs, info.host_ms))
+    write_png(args.out, r.render_to_host_memory(camera, instances))
+    print("You can find your render here: %s" % args.out)
+
+
+def device_clips(args, rt, gltf, r, copies, skinned, duration, camera):
+    """The frames of --device-clips: bake once, attach once; per frame the times, one pose_actors, one render."""
+    import numpy as np
+    import torch
+    clip = gltf.bake_clip(0)
+    cid = r.attach_clip(clip)
+    n = copies[0][0].n_transforms
+    layout, actors, items = [], [], []
+    for c, (loaded, dx, dz) in enumerate(copies):
+        placement = np.array([1, 0, 0, dx, 0, 1, 0, 0, 0, 0, 1, dz], np.float32)
+        actors.append((cid, 0.0, placement, loaded.instance_rows(c * n), 0))
+        items += [(int(loaded.keys[b]), c, skin, None) for b, skin in skinned]
+        layout += loaded.layout()
+    packed = rt.ActorArgs(actors, items)                      # packed once: a frame rewrites the times in place
+    transforms = torch.zeros((len(copies) * n, 12), dtype=torch.float32, device="cuda:%d" % r.devices[0])
+    for f in range(args.frames):
+        packed.set_times([(duration * f / max(args.frames - 1, 1) + duration * c / args.copies) % duration for c in range(len(copies))])
+        r.pose_actors(packed, tensor=transforms)
+        r.wait_frame(r.render_device_transforms(camera, layout, transforms))
+    info = r.actor_pose_info()
+    print("last call: %d actors, %d items, %d nodes and %d channels evaluated, %d bytes uploaded, %d launches, %d read-back, %.3f ms on the host" % (
+        info.actors, info.items, info.nodes, info.channels, info.upload_bytes, info.launches, info.read_backs, info.host_ms))
+    instances = []
+    xf = transforms.cpu().numpy()
+    for c, (loaded, _, _) in enumerate(copies):
+        instances += loaded.grouped(xf[c * n:(c + 1) * n])
     write_png(args.out, r.render_to_host_memory(camera, instances))
     print("You can find your render here: %s" % args.out)
 

@@ -1237,6 +1237,112 @@ int sr_gltf_blas_morph(const SrGltf* gltf, uint32_t blas_index, uint32_t* n_targ
  * or no such channel: the default weights of sr_gltf_blas_morph. */
 int sr_gltf_morph_weights(const SrGltf* gltf, int32_t animation, float time_seconds, uint32_t blas_index, float* weights_out, uint32_t n_targets);
 
+/* A baked clip: an immutable flat form of everything sr_gltf_pose re-derives from the document on every call, for one animation
+ * of the file (-1: the file's static pose). It does not refer to `gltf` afterwards. It holds
+ *   nodes      the nodes sr_gltf_pose reaches from the default scene's roots, parent before child, grouped by depth level (a
+ *              level table): parent, glTF node index, animated mask, the file's TRS, and the node's matrix as the load reads it;
+ *   channels   the translation / rotation / scale channels that target such a node: clip node, path, interpolation, and their
+ *              slice of the key times and values (the file's fp32 bytes). Of two channels on one node and path the later one
+ *              is kept, which is what sr_gltf_pose's loop leaves;
+ *   skins      every skin an instanced node wears, in file order: joint nodes, inverse bind matrices, the mesh node (the first
+ *              instanced node wearing it) and its offset in the clip's concatenated joint list;
+ *   instances  the clip node of every instance, in sr_gltf_instance order.
+ * Refused in sr_gltf_pose's statuses and words behind "sr_gltf_bake_clip: ": a CUBICSPLINE sampler (SR_ERR_UNSUPPORTED), a joint
+ * node that is not part of the scene, a hierarchy that is too deep, every sampler error the loader reports. Refused as well
+ * (SR_ERR_UNSUPPORTED): a node the roots reach twice, and a clip of more than SR_CLIP_MAX_NODES nodes (the text gives both
+ * counts): the device kernel keeps a clip's nodes in static LDS. */
+#define SR_CLIP_MAX_NODES 384u
+typedef struct SrClip SrClip;
+typedef struct SrClipInfo {
+    int32_t animation;                 /* as baked; -1: the static pose */
+    uint32_t n_nodes, n_levels, n_channels, n_skins, n_joints /* of all skins */, n_instances, n_keys /* of all channels */;
+    float duration_seconds;            /* the last key time of the kept channels; 0 without channels */
+    uint32_t device_bytes;             /* the one block sr_scene_attach_clip uploads */
+} SrClipInfo;                          /* 40 bytes */
+typedef struct SrClipNodeInfo { uint32_t parent /* clip node, 0xFFFFFFFF: a root */, gltf_node, animated, level; } SrClipNodeInfo;
+typedef struct SrClipChannelInfo { uint32_t node /* clip node */, path /* 0 translation, 1 rotation, 2 scale */, interpolation /* 0 LINEAR, 1 STEP */, n_keys; } SrClipChannelInfo;
+int sr_gltf_bake_clip(const SrGltf* gltf, int32_t animation, SrClip** out);
+int sr_clip_destroy(SrClip* clip);
+int sr_clip_info(const SrClip* clip, SrClipInfo* out);
+/* Skin `skin` (the file's index) of the clip: its first matrix in the clip's concatenated joint list, and its joint count.
+ * SR_ERR_INVALID_ARG: no instanced node wears that skin. */
+int sr_clip_skin(const SrClip* clip, uint32_t skin, uint32_t* first_matrix, uint32_t* n_joints);
+/* The layout, for inspection: n_nodes node records, n_channels channel records, the clip node of every instance (any may be NULL). */
+int sr_clip_layout(const SrClip* clip, SrClipNodeInfo* nodes, SrClipChannelInfo* channels, uint32_t* instance_nodes);
+/* Channel `channel`'s keys as the clip holds them: n_keys times and n_keys x 3 (rotation: x 4) values; valid until sr_clip_destroy. */
+int sr_clip_channel_keys(const SrClip* clip, uint32_t channel, const float** times, const float** values);
+/* The host rule: sr_gltf_pose restated over the baked clip, held to it bit for bit. The device kernel includes the same
+ * arithmetic (csrc/clip_rule.h); host and device are built without contraction.
+ * sr_clip_sample_host: n_nodes records, clip-node order: every node's TRS at time_seconds (sr_gltf_sample_node's values for the
+ * node's glTF index) and its animated mask. A time that is not finite: SR_ERR_INVALID_ARG, unless the clip is the static pose.
+ * sr_clip_compose_host: from such records, the joint matrices of all skins (n_joints of SrClipInfo, each skin at its
+ * sr_clip_skin offset; may be NULL) and the instance transforms (n_instances; may be NULL), premultiplied by *placement where
+ * given (the joint matrices are not). A singular mesh-node transform, looked for only where joint matrices are asked for:
+ * SR_ERR_UNSUPPORTED in sr_gltf_pose's words, with the lowest such skin (position in the clip) in *singular_skin (may be NULL;
+ * 0xFFFFFFFF otherwise); the instance transforms and the other skins' matrices are written all the same. sr_clip_pose_host
+ * runs both. */
+typedef struct SrNodeTrs { float translation[3], rotation[4], scale[3]; uint32_t animated, reserved; } SrNodeTrs;   /* 48 bytes */
+int sr_clip_sample_host(const SrClip* clip, float time_seconds, SrNodeTrs* out);
+int sr_clip_compose_host(const SrClip* clip, const SrNodeTrs* trs, const SrTransform* placement, SrTransform* joint_matrices,
+                         SrTransform* instance_transforms, uint32_t* singular_skin);
+int sr_clip_pose_host(const SrClip* clip, float time_seconds, const SrTransform* placement, SrTransform* joint_matrices,
+                      SrTransform* instance_transforms);
+/* Clips on a scene. sr_scene_attach_clip uploads the clip's tables once, as one device block, and hands out an id; ids count up
+ * and are not handed out again while the scene lives. sr_scene_detach_clip frees the block (it waits for the device).
+ * sr_scene_pose_actors is sr_scene_pose_meshes with the joint matrices named rather than given: one kernel in front of the posing
+ * kernel (clip_pose_kernel, one block per actor) samples every actor's clip at the actor's own time, composes the hierarchy, and
+ * writes the joint matrices where the posing kernel reads them and the instance transforms into d_instance_transforms (DEVICE
+ * memory, or NULL: none are written), which sr_scene_set_instances_device takes. Opt-in: nothing selects it.
+ * On `stream`: the check words are preset; ONE upload (item rows, block table, active lists, actor rows, instance rows; no joint
+ * matrices: the region the clip kernel writes lies outside the uploaded bytes); clip_pose_kernel; the posing kernel; ONE
+ * read-back (two words per item, one per actor).
+ * Numerics: translation, scale and STEP samples, samples at clamped and exact key times and everything composed from a TRS are
+ * bit equal to sr_clip_pose_host. An interpolated rotation passes through atan2 and sin, where the device's libm and the host's
+ * are not bit-identical: a component is the host's, its neighbouring fp32 value, or within 2^-44 of it.
+ * Refused on the host before any device work, behind "pose_actors: actor <i>: " or "pose_actors: item <i>: ": an unknown clip id,
+ * a time that is not finite (sr_gltf_pose's words), instance_rows or instance_base without d_instance_transforms, an actor or
+ * skin index out of range, a skin whose joint count is not that of the mesh's attached rig, a key named twice, an item with
+ * neither stage, and everything sr_scene_pose_meshes refuses for an item. The instance rows are the caller's to keep inside
+ * d_instance_transforms.
+ * Refused on the device, all or nothing: a singular mesh-node transform (the actor's check word): sr_gltf_pose's status and
+ * words for the lowest such actor; no mesh has changed. d_instance_transforms MAY HAVE BEEN WRITTEN by then: do not hand it to
+ * sr_scene_set_instances_device after a refusal. A non-finite posed vertex refuses as in sr_scene_pose_meshes. */
+typedef struct SrClipActor {           /* one character: a clip at a time. 32 bytes */
+    uint32_t clip_id; float time_seconds;
+    const SrTransform* placement;      /* host, or NULL; premultiplied onto the instance transforms only */
+    const uint32_t* instance_rows;     /* host, the clip's n_instances rows of d_instance_transforms, or NULL: instance_base + i */
+    uint32_t instance_base, reserved;
+} SrClipActor;
+typedef struct SrActorPoseItem {       /* one mesh: what SrPoseItem is, with the joint matrices named rather than given. 32 bytes */
+    uint64_t key; uint32_t actor, skin;        /* skin: the file's skin index, or SR_ACTOR_NO_SKIN: no skin stage */
+    const float* weights; uint32_t n_targets, reserved;   /* morph stage as in SrPoseItem: host weights, or NULL */
+} SrActorPoseItem;
+#define SR_ACTOR_NO_SKIN 0xFFFFFFFFu
+#define SR_ACTORS_KEEP_NODES 1u        /* flags: also store every actor's sampled TRS and global matrices (sr_scene_read_actor_nodes) */
+typedef struct SrActorPoseInfo {       /* the last sr_scene_pose_actors that reached the device (a host refusal leaves it alone) */
+    uint32_t actors, items;
+    uint64_t nodes, channels;          /* nodes evaluated, channels sampled, over all actors */
+    uint64_t upload_bytes;             /* the one upload */
+    uint32_t launches;                 /* 3 accepted (clip, pose, scatter), 2 refused */
+    uint32_t read_backs;               /* 1 */
+    uint32_t calls;                    /* calls that reached the device since the scene was created */
+    uint32_t refused_actor, refused_item, reserved;   /* 0xFFFFFFFF: none */
+    double clip_ms, pose_ms, scatter_ms;   /* events, only while sr_scene_enable_timing is on; pose_ms includes the read-back */
+    double host_ms;                    /* the whole call, wall clock */
+} SrActorPoseInfo;                     /* 88 bytes */
+int sr_scene_attach_clip(SrScene* scene, const SrClip* clip, uint32_t* clip_id);
+int sr_scene_detach_clip(SrScene* scene, uint32_t clip_id);
+int sr_scene_pose_actors(SrScene* scene, const SrClipActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
+                         SrTransform* d_instance_transforms, uint32_t flags, void* stream);
+int sr_scene_actor_pose_info(const SrScene* scene, SrActorPoseInfo* out);
+/* After a call with SR_ACTORS_KEEP_NODES that reached the device: actor `actor`'s sampled TRS (n_nodes records) and global
+ * matrices (n_nodes x 16 floats, row-major), clip-node order. Either may be NULL. SR_ERR_STATE: the last call kept no nodes.
+ * sr_scene_read_actor_matrices: after any call that reached the device, the actor's joint matrices as the posing kernel read
+ * them (the clip's n_joints, each skin at its sr_clip_skin offset). SR_ERR_STATE: another pose call has used the staging
+ * block since. Both wait for the device. */
+int sr_scene_read_actor_nodes(const SrScene* scene, uint32_t actor, SrNodeTrs* trs, float* globals16);
+int sr_scene_read_actor_matrices(const SrScene* scene, uint32_t actor, SrTransform* joint_matrices);
+
 /* What Renderer::load_gltf / load_scene return (lib.rs:779-846): the asset group and the scene's instances
  * grouped per BLAS key in BLAS order. Keys are ResourceKey{group, index} packed as group << 32 | index
  * (lib.rs:54-58); BLASes take indices 0..n-1, images the following ones (resource_manager.rs:400-410). */
@@ -1287,6 +1393,15 @@ int sr_renderer_attach_morphs(SrRenderer* renderer, const SrGltf* gltf, const Sr
  * slot's replica takes each item's posed records from that scene's batch scratch by a device-to-device (peer) copy, mesh by mesh.
  * A refusal changes no replica. */
 int sr_renderer_pose_meshes(SrRenderer* renderer, const SrPoseItem* items, uint32_t n_items, void* stream);
+/* sr_scene_attach_clip / sr_scene_detach_clip / sr_scene_pose_actors / sr_scene_actor_pose_info through the facade. The clip is
+ * attached to the first device slot's scene, which suffices: that scene poses and validates once, and every further slot's
+ * replica takes each item's posed records from its batch scratch, as with sr_renderer_pose_meshes. d_instance_transforms lives
+ * on the first slot's device; sr_renderer_render_device_transforms takes it from there. A refusal changes no replica. */
+int sr_renderer_attach_clip(SrRenderer* renderer, const SrClip* clip, uint32_t* clip_id);
+int sr_renderer_detach_clip(SrRenderer* renderer, uint32_t clip_id);
+int sr_renderer_pose_actors(SrRenderer* renderer, const SrClipActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
+                            SrTransform* d_instance_transforms, uint32_t flags, void* stream);
+int sr_renderer_actor_pose_info(const SrRenderer* renderer, SrActorPoseInfo* out);
 /* How sr_renderer_pose_scene poses a loaded scene's rigged and morphed meshes: SR_POSE_BATCH_OFF (the default), one
  * sr_renderer_skin_mesh / sr_renderer_pose_mesh per mesh (each a batch of one item); SR_POSE_BATCH_ON, all of them by one sr_renderer_pose_meshes.
  * SR_POSE_BATCH=on|off in the environment sets the initial mode when the renderer is created. */

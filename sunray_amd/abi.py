@@ -226,6 +226,36 @@ class SrPoseBatchInfo(C.Structure):  # the last sr_scene_pose_meshes that reache
 POSE_BATCH_OFF, POSE_BATCH_ON, POSE_BATCH_TILE = 0, 1, 256  # sr_renderer_set_pose_batch; vertices a block of the posing launch
 
 
+class SrClipInfo(C.Structure):  # a baked clip (sr_clip_info), 40 B
+    _fields_ = [("animation", C.c_int32), ("n_nodes", C.c_uint32), ("n_levels", C.c_uint32), ("n_channels", C.c_uint32), ("n_skins", C.c_uint32),
+                ("n_joints", C.c_uint32), ("n_instances", C.c_uint32), ("n_keys", C.c_uint32), ("duration_seconds", C.c_float), ("device_bytes", C.c_uint32)]
+
+
+CLIP_NODE_INFO = np.dtype([("parent", "<u4"), ("gltf_node", "<u4"), ("animated", "<u4"), ("level", "<u4")])  # sr_clip_layout
+CLIP_CHANNEL_INFO = np.dtype([("node", "<u4"), ("path", "<u4"), ("interpolation", "<u4"), ("n_keys", "<u4")])
+NODE_TRS = np.dtype([("translation", "<f4", 3), ("rotation", "<f4", 4), ("scale", "<f4", 3), ("animated", "<u4"), ("reserved", "<u4")])  # SrNodeTrs, 48 B
+assert NODE_TRS.itemsize == 48
+CLIP_MAX_NODES, CLIP_NO_NODE, ACTOR_NO_SKIN, ACTORS_KEEP_NODES = 384, 0xFFFFFFFF, 0xFFFFFFFF, 1
+
+
+class SrClipActor(C.Structure):  # one character of sr_scene_pose_actors: a clip at a time, 32 B
+    _fields_ = [("clip_id", C.c_uint32), ("time_seconds", C.c_float), ("placement", C.c_void_p), ("instance_rows", C.c_void_p),
+                ("instance_base", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SrActorPoseItem(C.Structure):  # one mesh of sr_scene_pose_actors: SrPoseItem with the joint matrices named, 32 B
+    _fields_ = [("key", C.c_uint64), ("actor", C.c_uint32), ("skin", C.c_uint32), ("weights", C.c_void_p), ("n_targets", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SrActorPoseInfo(C.Structure):  # the last sr_scene_pose_actors that reached the device (sr_scene_actor_pose_info), 88 B
+    _fields_ = [("actors", C.c_uint32), ("items", C.c_uint32), ("nodes", C.c_uint64), ("channels", C.c_uint64), ("upload_bytes", C.c_uint64),
+                ("launches", C.c_uint32), ("read_backs", C.c_uint32), ("calls", C.c_uint32), ("refused_actor", C.c_uint32), ("refused_item", C.c_uint32),
+                ("reserved", C.c_uint32), ("clip_ms", C.c_double), ("pose_ms", C.c_double), ("scatter_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+assert C.sizeof(SrClipInfo) == 40 and C.sizeof(SrClipActor) == 32 and C.sizeof(SrActorPoseItem) == 32 and C.sizeof(SrActorPoseInfo) == 88
+
+
 class SrMeshFrameInfo(C.Structure):  # one mesh's frame and its last position update (sr_scene_mesh_frame_info), 32 B
     _fields_ = [("flags", C.c_uint32), ("n_groups", C.c_uint32), ("n_entries", C.c_uint32), ("max_valence", C.c_uint32),
                 ("updates", C.c_uint32), ("first_bad", C.c_uint32), ("frame_ms", C.c_double)]

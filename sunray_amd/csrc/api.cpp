@@ -26,6 +26,8 @@
 #include "lights.h"
 #include "normals.h"
 #include "pose_batch.h"
+#include "clip.h"
+#include "clip_pose.h"
 #include "tl_record.h"
 
 namespace {
@@ -265,6 +267,18 @@ struct SrScene {
     DeviceBuffer d_pose_stage, d_pose_check, d_pose_scratch;
     std::vector<uint64_t> pose_batch_keys, pose_batch_vertex_base;
     SrPoseBatchInfo pose_info{0, 0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0.0, 0.0, 0.0};
+    // clips on the device (sr_scene_attach_clip, sr_scene_pose_actors): every attached clip's host copy and its one device block,
+    // by id (ids count up and are never handed out again); the figures of the last sr_scene_pose_actors that reached the device;
+    // where that call left each actor's joint matrices in the staging block (while actor_stage_current: no other pose call has
+    // used the block since) and, after SR_ACTORS_KEEP_NODES, its nodes in the kept-nodes buffers
+    struct AttachedClip { SrClip host; DeviceBuffer d_block; };
+    std::map<uint32_t, AttachedClip> clips;
+    uint32_t next_clip_id = 1;
+    SrActorPoseInfo actor_info{0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0.0, 0.0, 0.0, 0.0};
+    struct ActorRecord { uint64_t matrix_byte; uint32_t n_joints, node_base, n_nodes; };
+    std::vector<ActorRecord> actor_records;
+    bool actor_stage_current = false, actor_nodes_kept = false;
+    DeviceBuffer d_actor_trs, d_actor_globals;
     // sr_scene_update_mesh_positions*: the face vectors of the last call (one or two 16-byte pieces per triangle), the uploaded
     // positions of the host-pointer form, and the records the mesh-frame producer wrote (scratch: the replicas of a renderer take
     // them from there)
@@ -1000,7 +1014,7 @@ namespace {
 // What the pose path refuses on the host, before any device work, in the words of the entry point `who`: the mesh's slot into
 // *slot and the active list into `active` (2 * n_targets words: the indices of the targets whose weight is not 0, ascending,
 // then from word n_targets on their weights) and *n_active.
-int check_pose_args(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, const SrTransform* joint_matrices, uint32_t n_joints, const char* who,
+int check_pose_args(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, bool joint_matrices, uint32_t n_joints, const char* who,
                     uint32_t* slot, std::vector<uint32_t>& active, uint32_t* n_active) {
     int rc = find_mesh(s, key, who, slot);
     if (rc != SR_OK) return rc;
@@ -1091,6 +1105,19 @@ int sr_scene_mesh_morph_info(const SrScene* s, uint64_t key, SrMeshMorphInfo* ou
 
 namespace {
 
+// What sr_scene_pose_actors adds to a batch: the actors' rows for clip_pose_kernel (matrix_base counted from the first matrix the
+// kernel writes; pose_items moves it behind the upload), the instance rows of the actors that gave some, and per item its first
+// matrix among those the kernel writes (0xFFFFFFFF: the item has no skin stage).
+static_assert(sizeof(SrClipActor) == 32 && sizeof(SrActorPoseItem) == 32 && sizeof(SrActorPoseInfo) == 88 && sizeof(SrClipInfo) == 40, "the header states these sizes");
+struct ActorFeed {
+    uint32_t n_actors = 0, flags = 0;
+    std::vector<srd::ClipActorRow> rows;
+    std::vector<uint32_t> instance_rows, item_matrix, actor_joints, actor_nodes;
+    uint64_t n_matrices = 0, n_nodes = 0, n_channels = 0;
+    SrTransform* d_instance_transforms = nullptr;
+    SrActorPoseInfo* info = nullptr;
+};
+
 // The one posing path: sr_scene_pose_meshes (`batch`) and, with a list of one item, sr_scene_skin_mesh and sr_scene_pose_mesh.
 // Many meshes posed by one upload, one launch and one read-back (the header states the contract). Host checks for every item
 // first (check_pose_args), then the plan and the staging block, the posing launch into the batch scratch, and for an accepted
@@ -1100,10 +1127,18 @@ namespace {
 //     single call refuses with no prefix and in the entry point's own words;
 //   - what a refusal for a non-finite vertex records: the batch the first_bad of the stages that reported, and no more; a single
 //     call the first_bad of every stage that ran (0xFFFFFFFF where that stage did not report) and n_active.
-int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream, bool batch, SrPoseBatchInfo* out) {
+// With a `feed` (sr_scene_pose_actors) the call is a batch whose words say "pose_actors", whose items may take their matrices
+// from the slice clip_pose_kernel writes instead of a host pointer, and which may have no item at all: the actors' rows and
+// instance rows travel behind the batch's parts in the one upload, the clip kernel runs in front of the posing kernel, one more
+// check word per actor comes back in the one read-back (a singular mesh-node transform refuses like a non-finite vertex, before
+// it), and *feed->info takes the call's figures where *out takes the batch's.
+int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream, bool batch, SrPoseBatchInfo* out, ActorFeed* feed = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
-    const auto prefix = [batch](uint32_t i) { return batch ? "pose_meshes: item " + std::to_string(i) + ": " : std::string(); };
-    const std::string who = batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
+    const std::string who = feed ? "pose_actors" : batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
+    const auto prefix = [batch, &who](uint32_t i) { return batch ? who + ": item " + std::to_string(i) + ": " : std::string(); };
+    // an item's skin stage: its matrices come from the caller's host pointer, or from the slice the clip kernel writes
+    const auto fed = [feed](uint32_t i) { return feed && feed->item_matrix[i] != 0xFFFFFFFFu; };
+    const auto skin_stage = [items, &fed](uint32_t i) { return items[i].joint_matrices != nullptr || fed(i); };
     std::vector<uint32_t> slots(n_items), counts(n_items), n_active(n_items), active_index, active;
     std::vector<float> active_weight;
     std::map<uint64_t, uint32_t> seen;
@@ -1111,8 +1146,8 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     int rc;
     for (uint32_t i = 0; i < n_items; i++) {
         const SrPoseItem& it = items[i];
-        if (!it.weights && !it.joint_matrices) return fail(SR_ERR_INVALID_ARG, prefix(i) + "pose_mesh: neither weights nor joint matrices given (one stage at least)");
-        rc = check_pose_args(s, it.key, it.weights, it.n_targets, it.joint_matrices, it.n_joints, it.weights ? "pose_mesh" : "skin_mesh", &slots[i], active, &n_active[i]);
+        if (!it.weights && !skin_stage(i)) return fail(SR_ERR_INVALID_ARG, prefix(i) + "pose_mesh: neither weights nor joint matrices given (one stage at least)");
+        rc = check_pose_args(s, it.key, it.weights, it.n_targets, skin_stage(i), it.n_joints, it.weights ? "pose_mesh" : "skin_mesh", &slots[i], active, &n_active[i]);
         if (rc != SR_OK) return fail(rc, prefix(i) + g_last_error);
         const auto first = seen.emplace(it.key, i);
         if (!first.second) return fail(SR_ERR_INVALID_ARG, prefix(i) + "the key is named twice in the batch (first by item " + std::to_string(first.first->second) + ")");
@@ -1126,13 +1161,24 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     std::vector<uint64_t> vertex_base(n_items);
     uint32_t n_blocks = 0;
     if ((rc = sr_pose_batch_plan(counts.data(), n_items, first_block.data(), vertex_base.data(), &n_blocks)) != SR_OK) return rc;
-    const uint64_t n_vertices = vertex_base[n_items - 1] + counts[n_items - 1];
+    const uint64_t n_vertices = n_items ? vertex_base[n_items - 1] + counts[n_items - 1] : 0;
     const srh::PoseBatchLayout lay = srh::pose_batch_layout(n_items, n_blocks, n_matrices, active_index.size());
+    // Actors add their rows and their instance rows behind the batch's parts: that is the upload. The matrices the clip kernel
+    // writes follow it, outside the uploaded bytes, a whole number of matrices from lay.matrices so that matrix_base reaches them.
+    const uint32_t n_actors = feed ? feed->n_actors : 0;
+    const size_t actor_rows_at = lay.bytes, inst_rows_at = actor_rows_at + sizeof(srd::ClipActorRow) * (size_t)n_actors;
+    const size_t upload_bytes = inst_rows_at + ((4 * (feed ? feed->instance_rows.size() : 0) + 15u) & ~(size_t)15u);
+    const uint64_t fed_first = (upload_bytes - lay.matrices + sizeof(SrTransform) - 1) / sizeof(SrTransform);
+    const size_t stage_bytes = feed ? lay.matrices + sizeof(SrTransform) * (size_t)(fed_first + feed->n_matrices) : lay.bytes;
+    if (feed && fed_first + feed->n_matrices >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_actors: the call holds 2^32 joint matrices or more");
+    const size_t n_check = 2 * (size_t)n_items + n_actors;
     if ((rc = bind_device(s)) != SR_OK) return rc;
-    if ((rc = s->d_pose_stage.reserve(lay.bytes)) != SR_OK || (rc = s->d_pose_check.reserve(8 * (size_t)n_items)) != SR_OK ||
+    if ((rc = s->d_pose_stage.reserve(stage_bytes)) != SR_OK || (rc = s->d_pose_check.reserve(4 * n_check)) != SR_OK ||
         (rc = s->d_pose_scratch.reserve(sizeof(SrVertex) * (size_t)n_vertices)) != SR_OK) return rc;
-    // the staging block: rows, block table, matrices, active lists
-    std::vector<unsigned char> stage(lay.bytes, 0);
+    const bool keep_nodes = feed && (feed->flags & SR_ACTORS_KEEP_NODES);
+    if (keep_nodes && ((rc = s->d_actor_trs.reserve(sizeof(SrNodeTrs) * (size_t)feed->n_nodes)) != SR_OK || (rc = s->d_actor_globals.reserve(64 * (size_t)feed->n_nodes)) != SR_OK)) return rc;
+    // the staging block: rows, block table, matrices, active lists; then the actors' rows and instance rows
+    std::vector<unsigned char> stage(upload_bytes, 0);
     srd::PoseBatchItem* rows = (srd::PoseBatchItem*)(stage.data() + lay.items);
     SrPoseBatchInfo info{n_items, n_blocks, n_vertices, 0, 0, 0, 0, 0, out->calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, lay.bytes, 0.0, 0.0, 0.0};
     uint32_t matrix_base = 0, active_base = 0;
@@ -1142,13 +1188,13 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         srd::PoseBatchItem& row = rows[i];
         row.src = it.weights ? ms.morph.d_base.p : ms.skin.d_bind.p;
         row.deltas = it.weights ? ms.morph.d_deltas.p : nullptr;
-        row.influences = it.joint_matrices ? ms.skin.d_influences.p : nullptr;
+        row.influences = skin_stage(i) ? ms.skin.d_influences.p : nullptr;
         row.dst = s->meshes[slots[i]].d_vertices;
         row.vertex_base = vertex_base[i];
         row.n_vertices = counts[i]; row.first_block = first_block[i];
         row.n_active = n_active[i]; row.active_base = active_base;
-        row.matrix_base = matrix_base;
-        row.stages = (it.weights ? srd::kPoseMorph : 0u) | (it.joint_matrices ? srd::kPoseSkin : 0u);
+        row.matrix_base = fed(i) ? (uint32_t)fed_first + feed->item_matrix[i] : matrix_base;
+        row.stages = (it.weights ? srd::kPoseMorph : 0u) | (skin_stage(i) ? srd::kPoseSkin : 0u);
         if (it.joint_matrices) { memcpy(stage.data() + lay.matrices + sizeof(SrTransform) * (size_t)matrix_base, it.joint_matrices, sizeof(SrTransform) * (size_t)it.n_joints); matrix_base += it.n_joints; }
         active_base += n_active[i];
         (row.stages == 3u ? info.fused : it.weights ? info.morph_only : info.skin_only)++;
@@ -1162,19 +1208,47 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     const unsigned char* d_stage = (const unsigned char*)s->d_pose_stage.p;
     const srd::PoseBatchItem* d_rows = (const srd::PoseBatchItem*)(d_stage + lay.items);
     const uint32_t* d_table = (const uint32_t*)(d_stage + lay.block_table);
-    std::vector<uint32_t> bad(2 * (size_t)n_items, 0xFFFFFFFFu);
-    EventPair pose_timer(s), scatter_timer(s);
-    int e = (int)hipMemsetAsync(s->d_pose_check.p, 0xFF, 8 * (size_t)n_items, st);
-    if (e == 0) e = (int)hipMemcpyAsync(s->d_pose_stage.p, stage.data(), lay.bytes, hipMemcpyHostToDevice, st);
+    std::vector<uint32_t> bad(n_check, 0xFFFFFFFFu);
+    EventPair pose_timer(s), scatter_timer(s), clip_timer(s);
+    if (feed) {
+        for (uint32_t a = 0; a < n_actors; a++) feed->rows[a].matrix_base += (uint32_t)fed_first;
+        memcpy(stage.data() + actor_rows_at, feed->rows.data(), sizeof(srd::ClipActorRow) * (size_t)n_actors);
+        if (!feed->instance_rows.empty()) memcpy(stage.data() + inst_rows_at, feed->instance_rows.data(), 4 * feed->instance_rows.size());
+    }
+    s->actor_stage_current = false;                          // the block changes hands
+    int e = (int)hipMemsetAsync(s->d_pose_check.p, 0xFF, 4 * n_check, st);
+    if (e == 0) e = (int)hipMemcpyAsync(s->d_pose_stage.p, stage.data(), upload_bytes, hipMemcpyHostToDevice, st);
+    if (feed) {
+        clip_timer.begin(st);
+        if (e == 0) e = srk_clip_pose((const srd::ClipActorRow*)(d_stage + actor_rows_at), n_actors, (const uint32_t*)(d_stage + inst_rows_at),
+                                      (SrTransform*)(s->d_pose_stage.p ? (unsigned char*)s->d_pose_stage.p + lay.matrices : nullptr), feed->d_instance_transforms,
+                                      (uint32_t*)s->d_pose_check.p + 2 * (size_t)n_items, keep_nodes ? (SrNodeTrs*)s->d_actor_trs.p : nullptr,
+                                      keep_nodes ? (float*)s->d_actor_globals.p : nullptr, st);
+        clip_timer.end(st);
+    }
     pose_timer.begin(st);
     if (e == 0) e = srk_pose_batch(d_rows, d_table, n_blocks, (const SrTransform*)(d_stage + lay.matrices), (const uint32_t*)(d_stage + lay.active_index),
                                    (const float*)(d_stage + lay.active_weight), (SrVertex*)s->d_pose_scratch.p, (uint32_t*)s->d_pose_check.p, st);
-    if (e == 0) e = (int)hipMemcpyAsync(bad.data(), s->d_pose_check.p, 8 * (size_t)n_items, hipMemcpyDeviceToHost, st);
+    if (e == 0) e = (int)hipMemcpyAsync(bad.data(), s->d_pose_check.p, 4 * n_check, hipMemcpyDeviceToHost, st);
     pose_timer.end(st);
     if (e == 0) e = (int)hipStreamSynchronize(st);
     if (e != 0) return fail(SR_ERR_HIP, who + (batch ? ": the posing kernel failed: " : items[0].weights ? ": a posing kernel failed: " : ": the skinning kernel failed: ") +
                                         hipGetErrorString((hipError_t)e));
     info.launches = 1; info.read_backs = 1; info.pose_ms = pose_timer.ms();
+    if (feed) {                                               // what the read-outs find, and the figures of a call that reached the device
+        s->actor_records.clear();
+        for (uint32_t a = 0; a < n_actors; a++)
+            s->actor_records.push_back(SrScene::ActorRecord{lay.matrices + sizeof(SrTransform) * (uint64_t)feed->rows[a].matrix_base, feed->actor_joints[a], feed->rows[a].node_base, feed->actor_nodes[a]});
+        s->actor_stage_current = true; s->actor_nodes_kept = keep_nodes;
+        SrActorPoseInfo& ai = *feed->info;
+        ai = SrActorPoseInfo{n_actors, n_items, feed->n_nodes, feed->n_channels, upload_bytes, 2, 1, ai.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, clip_timer.ms(), info.pose_ms, 0.0, 0.0};
+        for (uint32_t a = 0; a < n_actors && ai.refused_actor == 0xFFFFFFFFu; a++) if (bad[2 * (size_t)n_items + a] != 0xFFFFFFFFu) ai.refused_actor = a;
+        if (ai.refused_actor != 0xFFFFFFFFu) {                // a singular mesh-node transform: nothing has changed but the scratch
+            s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();
+            ai.host_ms = ms_between(t0, std::chrono::steady_clock::now());
+            return fail(SR_ERR_UNSUPPORTED, "pose_actors: actor " + std::to_string(ai.refused_actor) + ": gltf: the transform of the skinned mesh's node is singular");
+        }
+    }
     // all or nothing: the lowest item with a bad vertex refuses the call
     for (uint32_t i = 0; i < n_items; i++) {
         const uint32_t bm = bad[2 * (size_t)i], bs = bad[2 * (size_t)i + 1];
@@ -1185,12 +1259,13 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
             SrScene::MeshState& ms = s->mesh_state[slots[i]];
             const uint32_t bm = bad[2 * (size_t)i], bs = bad[2 * (size_t)i + 1];
             if (bm < counts[i] || (!batch && items[i].weights)) ms.morph.first_bad = bm < counts[i] ? bm : 0xFFFFFFFFu;
-            if (bs < counts[i] || (!batch && items[i].joint_matrices)) ms.skin.first_bad = bs < counts[i] ? bs : 0xFFFFFFFFu;
+            if (bs < counts[i] || (!batch && skin_stage(i))) ms.skin.first_bad = bs < counts[i] ? bs : 0xFFFFFFFFu;
             if (!batch && items[i].weights) ms.morph.n_active = n_active[i];
         }
         s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();      // the scratch holds a refused call
         info.host_ms = ms_between(t0, std::chrono::steady_clock::now());
         *out = info;
+        if (feed) { feed->info->refused_item = info.refused_item; feed->info->host_ms = info.host_ms; }
         fail_non_finite_vertex(info.refused_vertex);
         return fail(SR_ERR_INVALID_ARG, prefix(info.refused_item) + g_last_error);
     }
@@ -1212,12 +1287,13 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         s->meshes[slot].check_ms = 0.0;
         mesh_vertices_changed(s, slot);
         if (items[i].weights) { ms.morph.first_bad = 0xFFFFFFFFu; ms.morph.n_active = n_active[i]; ms.morph.morph_ms = info.pose_ms; ms.morph.posed++; }
-        if (items[i].joint_matrices) { ms.skin.first_bad = 0xFFFFFFFFu; ms.skin.skin_ms = items[i].weights ? 0.0 : info.pose_ms; ms.skin.skinned++; }
+        if (skin_stage(i)) { ms.skin.first_bad = 0xFFFFFFFFu; ms.skin.skin_ms = items[i].weights ? 0.0 : info.pose_ms; ms.skin.skinned++; }
         s->pose_batch_keys.push_back(items[i].key); s->pose_batch_vertex_base.push_back(vertex_base[i]);
     }
     note_update_times(s, t0, t1, t2);
     info.host_ms = ms_between(t0, std::chrono::steady_clock::now());
     *out = info;
+    if (feed) { feed->info->launches = 3; feed->info->scatter_ms = info.scatter_ms; feed->info->host_ms = info.host_ms; }
     return SR_OK;
 }
 
@@ -1250,6 +1326,117 @@ int sr_scene_pose_meshes(SrScene* s, const SrPoseItem* items, uint32_t n_items, 
 int sr_scene_pose_batch_info(const SrScene* s, SrPoseBatchInfo* out) {
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_pose_batch_info: null argument");
     *out = s->pose_info;
+    return SR_OK;
+}
+
+// ---- clips on the device ---------------------------------------------------------------------------------------------------------
+int sr_scene_attach_clip(SrScene* s, const SrClip* clip, uint32_t* clip_id) {
+    if (!s || !clip || !clip_id) return fail(SR_ERR_INVALID_ARG, "attach_clip: null argument");
+    if (s->next_clip_id == 0xFFFFFFFFu) return fail(SR_ERR_UNSUPPORTED, "attach_clip: the scene has handed out 2^32 - 2 clip ids");
+    int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    SrScene::AttachedClip a;
+    a.host = *clip;
+    if ((rc = a.d_block.upload(clip->block.data(), 4 * clip->block.size())) != SR_OK) return rc;
+    *clip_id = s->next_clip_id++;
+    s->clips.emplace(*clip_id, std::move(a));
+    return SR_OK;
+}
+
+int sr_scene_detach_clip(SrScene* s, uint32_t clip_id) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "detach_clip: null argument (the scene)");
+    const auto it = s->clips.find(clip_id);
+    if (it == s->clips.end()) return fail(SR_ERR_INVALID_ARG, "detach_clip: no clip is attached under this id");
+    const int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());                          // a clip kernel in flight reads the block
+    s->clips.erase(it);
+    return SR_OK;
+}
+
+// sr_scene_pose_meshes with the joint matrices named rather than given: the actors and what they name are checked here, on the
+// host; the rest is pose_items, which takes an actor-driven item's matrices from the slice clip_pose_kernel writes.
+int sr_scene_pose_actors(SrScene* s, const SrClipActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items, SrTransform* d_instance_transforms,
+                         uint32_t flags, void* stream) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_actors: null argument (the scene)");
+    if (flags & ~SR_ACTORS_KEEP_NODES) return fail(SR_ERR_INVALID_ARG, "pose_actors: unknown flag bits (SR_ACTORS_KEEP_NODES is the flag)");
+    if (n_actors == 0 && n_items == 0) return SR_OK;
+    if ((n_actors && !actors) || (n_items && !items)) return fail(SR_ERR_INVALID_ARG, "pose_actors: null argument (actors or items, with a count > 0)");
+    if (((uintptr_t)d_instance_transforms & 15u) != 0) return fail(SR_ERR_INVALID_ARG, "pose_actors: the instance transforms are not 16-byte aligned");
+    ActorFeed feed;
+    feed.n_actors = n_actors; feed.flags = flags; feed.d_instance_transforms = d_instance_transforms; feed.info = &s->actor_info;
+    std::vector<const SrScene::AttachedClip*> clip_of(n_actors);
+    std::vector<uint32_t> first_matrix(n_actors);
+    for (uint32_t a = 0; a < n_actors; a++) {
+        const SrClipActor& ac = actors[a];
+        const auto prefix = [a](const char* text) { return "pose_actors: actor " + std::to_string(a) + ": " + text; };
+        const auto it = s->clips.find(ac.clip_id);
+        if (it == s->clips.end()) return fail(SR_ERR_INVALID_ARG, prefix("no clip is attached under this id"));
+        const SrClip& clip = it->second.host;
+        const srd::ClipHeader& h = clip.header();
+        if (clip.animation >= 0 && !std::isfinite(ac.time_seconds)) return fail(SR_ERR_INVALID_ARG, prefix("gltf: the time of a pose must be finite"));
+        if (!d_instance_transforms && (ac.instance_rows || ac.instance_base)) return fail(SR_ERR_INVALID_ARG, prefix("instance rows or an instance base given without device instance transforms"));
+        for (int c = 0; ac.placement && c < 12; c++)
+            if (!std::isfinite(ac.placement->m[c])) return fail(SR_ERR_INVALID_ARG, prefix("the placement has a component that is not finite"));
+        if (!ac.instance_rows && (uint64_t)ac.instance_base + h.n_instances > 0xFFFFFFFFull) return fail(SR_ERR_INVALID_ARG, prefix("the instance base plus the clip's instances passes 2^32 rows"));
+        srd::ClipActorRow row{};
+        row.clip = it->second.d_block.p; row.time_seconds = ac.time_seconds;
+        row.flags = (ac.placement ? 1u : 0u) | (ac.instance_rows ? 2u : 0u);
+        row.matrix_base = (uint32_t)feed.n_matrices; row.instance_base = ac.instance_base; row.rows_base = (uint32_t)feed.instance_rows.size();
+        row.node_base = (uint32_t)feed.n_nodes;
+        if (ac.placement) memcpy(row.placement, ac.placement->m, 48);
+        if (ac.instance_rows) feed.instance_rows.insert(feed.instance_rows.end(), ac.instance_rows, ac.instance_rows + h.n_instances);
+        feed.rows.push_back(row);
+        feed.actor_joints.push_back(h.n_joints); feed.actor_nodes.push_back(h.n_nodes);
+        clip_of[a] = &it->second; first_matrix[a] = (uint32_t)feed.n_matrices;
+        feed.n_matrices += h.n_joints; feed.n_nodes += h.n_nodes; feed.n_channels += h.n_channels;
+        if (feed.n_matrices >= (1ull << 32) || feed.n_nodes >= (1ull << 32) || feed.instance_rows.size() >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_actors: the call holds 2^32 joint matrices, nodes or instance rows or more");
+    }
+    std::vector<SrPoseItem> pose(n_items);
+    feed.item_matrix.assign(n_items, 0xFFFFFFFFu);
+    for (uint32_t i = 0; i < n_items; i++) {
+        const SrActorPoseItem& it = items[i];
+        const auto prefix = [i]() { return "pose_actors: item " + std::to_string(i) + ": "; };
+        pose[i] = SrPoseItem{it.key, it.weights, nullptr, it.n_targets, 0};
+        if (it.skin == SR_ACTOR_NO_SKIN) continue;
+        if (it.actor >= n_actors) return fail(SR_ERR_INVALID_ARG, prefix() + "actor " + std::to_string(it.actor) + " named, the call has " + std::to_string(n_actors) + " actors");
+        uint32_t first = 0, n_joints = 0;
+        if (sr_clip_skin(&clip_of[it.actor]->host, it.skin, &first, &n_joints) != SR_OK) return fail(SR_ERR_INVALID_ARG, prefix() + "skin " + std::to_string(it.skin) + " named, no instanced mesh of the actor's clip wears it");
+        pose[i].n_joints = n_joints;
+        feed.item_matrix[i] = first_matrix[it.actor] + first;
+    }
+    SrPoseBatchInfo dropped{};                                // sr_scene_pose_batch_info reads as before the call
+    return pose_items(s, pose.data(), n_items, stream, true, &dropped, &feed);
+}
+
+int sr_scene_actor_pose_info(const SrScene* s, SrActorPoseInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_actor_pose_info: null argument");
+    *out = s->actor_info;
+    return SR_OK;
+}
+
+int sr_scene_read_actor_nodes(const SrScene* s, uint32_t actor, SrNodeTrs* trs, float* globals16) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "read_actor_nodes: null argument (the scene)");
+    if (!s->actor_nodes_kept) return fail(SR_ERR_STATE, "read_actor_nodes: the last sr_scene_pose_actors kept no nodes (SR_ACTORS_KEEP_NODES)");
+    if (actor >= s->actor_records.size()) return fail(SR_ERR_INVALID_ARG, "read_actor_nodes: actor index out of range");
+    const SrScene::ActorRecord& r = s->actor_records[actor];
+    const int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (trs && r.n_nodes) HIP_TRY(hipMemcpy(trs, (const SrNodeTrs*)s->d_actor_trs.p + r.node_base, sizeof(SrNodeTrs) * (size_t)r.n_nodes, hipMemcpyDeviceToHost));
+    if (globals16 && r.n_nodes) HIP_TRY(hipMemcpy(globals16, (const float*)s->d_actor_globals.p + 16 * (size_t)r.node_base, 64 * (size_t)r.n_nodes, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_scene_read_actor_matrices(const SrScene* s, uint32_t actor, SrTransform* joint_matrices) {
+    if (!s || !joint_matrices) return fail(SR_ERR_INVALID_ARG, "read_actor_matrices: null argument");
+    if (!s->actor_stage_current) return fail(SR_ERR_STATE, "read_actor_matrices: the staging block does not hold a sr_scene_pose_actors call");
+    if (actor >= s->actor_records.size()) return fail(SR_ERR_INVALID_ARG, "read_actor_matrices: actor index out of range");
+    const SrScene::ActorRecord& r = s->actor_records[actor];
+    const int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (r.n_joints) HIP_TRY(hipMemcpy(joint_matrices, (const unsigned char*)s->d_pose_stage.p + r.matrix_byte, sizeof(SrTransform) * (size_t)r.n_joints, hipMemcpyDeviceToHost));
     return SR_OK;
 }
 

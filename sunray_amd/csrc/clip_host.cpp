@@ -1,0 +1,117 @@
+// Baked clips: the read-outs and the host rule (sr_clip_sample_host, sr_clip_compose_host, sr_clip_pose_host), which
+// restates sr_gltf_pose over the flat tables with the arithmetic of clip_rule.h. No HIP in this file.
+#include "clip.h"
+
+#include <cmath>
+#include <cstring>
+
+extern "C" {
+
+int sr_clip_destroy(SrClip* clip) { delete clip; return SR_OK; }
+
+int sr_clip_info(const SrClip* clip, SrClipInfo* out) {
+    if (!clip || !out) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_info: null argument");
+    const srd::ClipHeader& h = clip->header();
+    *out = SrClipInfo{clip->animation, h.n_nodes, h.n_levels, h.n_channels, h.n_skins, h.n_joints, h.n_instances, h.n_keys, clip->duration, h.bytes};
+    return SR_OK;
+}
+
+int sr_clip_skin(const SrClip* clip, uint32_t skin, uint32_t* first_matrix, uint32_t* n_joints) {
+    if (!clip) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_skin: null argument");
+    for (uint32_t k = 0; k < clip->header().n_skins; k++) {
+        const srd::ClipSkin& s = clip->skins()[k];
+        if (s.skin != skin) continue;
+        if (first_matrix) *first_matrix = s.first_joint;
+        if (n_joints) *n_joints = s.n_joints;
+        return SR_OK;
+    }
+    return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_skin: no instanced mesh uses this skin");
+}
+
+int sr_clip_layout(const SrClip* clip, SrClipNodeInfo* nodes, SrClipChannelInfo* channels, uint32_t* instance_nodes) {
+    if (!clip) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_layout: null argument");
+    const srd::ClipHeader& h = clip->header();
+    for (uint32_t n = 0; nodes && n < h.n_nodes; n++) { const srd::ClipNode& c = clip->nodes()[n]; nodes[n] = SrClipNodeInfo{c.parent, c.gltf_node, c.animated, c.level}; }
+    for (uint32_t k = 0; channels && k < h.n_channels; k++) { const srd::ClipChannel& c = clip->channels()[k]; channels[k] = SrClipChannelInfo{c.node, c.path, c.interpolation, c.n_keys}; }
+    if (instance_nodes && h.n_instances) memcpy(instance_nodes, clip->instances(), 4 * (size_t)h.n_instances);
+    return SR_OK;
+}
+
+int sr_clip_channel_keys(const SrClip* clip, uint32_t channel, const float** times, const float** values) {
+    if (!clip) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_channel_keys: null argument");
+    if (channel >= clip->header().n_channels) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_channel_keys: channel index out of range");
+    const srd::ClipChannel& c = clip->channels()[channel];
+    if (times) *times = clip->times() + c.first_time;
+    if (values) *values = clip->values() + c.first_value;
+    return SR_OK;
+}
+
+int sr_clip_sample_host(const SrClip* clip, float time_seconds, SrNodeTrs* out) {
+    if (!clip || !out) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_sample_host: null argument");
+    if (clip->animation >= 0 && !std::isfinite(time_seconds)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_sample_host: gltf: the time of a pose must be finite");
+    const srd::ClipHeader& h = clip->header();
+    for (uint32_t n = 0; n < h.n_nodes; n++) memcpy(&out[n], clip->nodes()[n].trs, sizeof(SrNodeTrs));
+    for (uint32_t k = 0; k < h.n_channels; k++) {
+        const srd::ClipChannel& c = clip->channels()[k];
+        SrNodeTrs& t = out[c.node];
+        const float* times = clip->times() + c.first_time;
+        const float* values = clip->values() + c.first_value;
+        if (c.path == srd::kClipRotation) srd::clip_sample_channel<4>(times, values, c.n_keys, c.interpolation, (double)time_seconds, t.rotation);
+        else srd::clip_sample_channel<3>(times, values, c.n_keys, c.interpolation, (double)time_seconds, c.path == srd::kClipTranslation ? t.translation : t.scale);
+    }
+    return SR_OK;
+}
+
+int sr_clip_compose_host(const SrClip* clip, const SrNodeTrs* trs, const SrTransform* placement, SrTransform* joint_matrices, SrTransform* instance_transforms,
+                         uint32_t* singular_skin) {
+    if (!clip || !trs) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_compose_host: null argument");
+    const srd::ClipHeader& h = clip->header();
+    if (singular_skin) *singular_skin = 0xFFFFFFFFu;
+    std::vector<float> global(16 * (size_t)h.n_nodes);
+    float ident[16], local[16];
+    srd::clip_identity(ident);
+    for (uint32_t n = 0; n < h.n_nodes; n++) {                  // parents come first, level by level
+        const srd::ClipNode& c = clip->nodes()[n];
+        if (c.animated) srd::clip_trs_matrix(trs[n].translation, trs[n].rotation, trs[n].scale, local);
+        else memcpy(local, c.matrix, 64);
+        srd::clip_mul(c.parent == srd::kClipNoNode ? ident : &global[16 * (size_t)c.parent], local, &global[16 * (size_t)n]);
+    }
+    if (instance_transforms) {
+        float place[16], m[16];
+        if (placement) srd::clip_widen(placement->m, place);
+        for (uint32_t i = 0; i < h.n_instances; i++) {
+            const float* g = &global[16 * (size_t)clip->instances()[i]];
+            if (placement) { srd::clip_mul(place, g, m); g = m; }
+            memcpy(instance_transforms[i].m, g, 48);
+        }
+    }
+    uint32_t bad = 0xFFFFFFFFu;
+    for (uint32_t k = 0; joint_matrices && k < h.n_skins; k++) {       // as sr_gltf_pose: nobody inverts where no joint matrices are asked for
+        const srd::ClipSkin& s = clip->skins()[k];
+        float inv[16], ibm[16], a[16], j[16];
+        srd::clip_identity(inv);
+        if (!srd::clip_invert_affine(&global[16 * (size_t)s.mesh_node], inv)) { if (bad == 0xFFFFFFFFu) bad = k; continue; }
+        for (uint32_t q = 0; q < s.n_joints; q++) {
+            srd::clip_widen(clip->inverse_bind() + 12 * (size_t)(s.first_joint + q), ibm);
+            srd::clip_mul(inv, &global[16 * (size_t)clip->joint_nodes()[s.first_joint + q]], a);
+            srd::clip_mul(a, ibm, j);
+            memcpy(joint_matrices[s.first_joint + q].m, j, 48);
+        }
+    }
+    if (singular_skin) *singular_skin = bad;
+    if (bad != 0xFFFFFFFFu) return srh::set_error(SR_ERR_UNSUPPORTED, "sr_clip_compose_host: gltf: the transform of the skinned mesh's node is singular");
+    return SR_OK;
+}
+
+int sr_clip_pose_host(const SrClip* clip, float time_seconds, const SrTransform* placement, SrTransform* joint_matrices, SrTransform* instance_transforms) {
+    if (!clip) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_pose_host: null argument");
+    if (clip->animation >= 0 && !std::isfinite(time_seconds)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_pose_host: gltf: the time of a pose must be finite");
+    std::vector<SrNodeTrs> trs(clip->header().n_nodes);
+    int rc = sr_clip_sample_host(clip, time_seconds, trs.data());
+    if (rc != SR_OK) return rc;
+    rc = sr_clip_compose_host(clip, trs.data(), placement, joint_matrices, instance_transforms, nullptr);
+    if (rc == SR_ERR_UNSUPPORTED) return srh::set_error(rc, "sr_clip_pose_host: gltf: the transform of the skinned mesh's node is singular");
+    return rc;
+}
+
+}  // extern "C"

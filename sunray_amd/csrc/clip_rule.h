@@ -1,0 +1,149 @@
+// Baked clips: the flat tables of a clip and the arithmetic of its evaluation, shared by the host rule (clip_host.cpp) and the
+// device kernel (clip_pose.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
+// (gltf_load.cpp) term for term; host and device are built with -ffp-contract=off, so +, -, *, / and sqrt give the same bits on
+// both. atan2 and sin (interpolated rotations only) come from each side's own libm.
+// No HIP here beyond the function qualifiers.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define SR_CLIP_HD __host__ __device__ inline
+#else
+#define SR_CLIP_HD inline
+#endif
+
+namespace srd {
+
+constexpr uint32_t kClipMaxNodes = 384;     // SR_CLIP_MAX_NODES: clip_pose_kernel keeps 12 + 16 floats a node in static LDS (42 KiB)
+constexpr uint32_t kClipNoNode = 0xFFFFFFFFu;
+constexpr uint32_t kClipTranslation = 0, kClipRotation = 1, kClipScale = 2;
+constexpr uint32_t kClipLinear = 0, kClipStep = 1;
+constexpr uint32_t kClipTrsWords = 12;      // SrNodeTrs: t[3] q[4] s[3] animated reserved
+
+// One block, as the device holds it: the header, then the tables at the header's byte offsets (each 16-byte aligned).
+struct ClipHeader {
+    uint32_t n_nodes, n_levels, n_channels, n_skins;
+    uint32_t n_joints, n_instances, n_keys, n_values;
+    uint32_t nodes, levels, channels, skins;            // ClipNode[n_nodes]; uint32_t[n_levels + 1]: first node of a level; ClipChannel[]; ClipSkin[]
+    uint32_t joint_nodes, joint_skins, inverse_bind, instances;   // per joint: clip node, skin (position in `skins`), 12 floats; per instance: clip node
+    uint32_t times, values, bytes, reserved;            // float[n_keys], float[n_values]
+};
+static_assert(sizeof(ClipHeader) == 80, "five 16-byte pieces");
+struct ClipNode {
+    uint32_t parent, gltf_node, animated, level;        // parent: clip node or kClipNoNode; animated: bit 0 translation, 1 rotation, 2 scale
+    float trs[kClipTrsWords];                           // node_trs of the file: t[3] q[4] s[3], then the animated mask's bits and 0
+    float matrix[16];                                   // node_matrix of the file, row-major (a node no channel animates composes from it)
+};
+static_assert(sizeof(ClipNode) == 128, "eight 16-byte pieces");
+struct ClipChannel { uint32_t node, path, interpolation, n_keys, first_time, first_value, reserved[2]; };
+static_assert(sizeof(ClipChannel) == 32, "two 16-byte pieces");
+struct ClipSkin { uint32_t skin, mesh_node, n_joints, first_joint; };   // the file's skin index; clip node; its slice of the joint list
+static_assert(sizeof(ClipSkin) == 16, "one 16-byte piece");
+
+// One actor of a call as clip_pose_kernel reads it, at wave-uniform addresses.
+struct ClipActorRow {
+    const void* clip;           // device: the clip's block
+    float time_seconds;
+    uint32_t flags;             // bit 0: placement given; bit 1: its instance rows are rows[rows_base + i], else instance_base + i
+    uint32_t matrix_base;       // first of its n_joints matrices, in matrices of 48 bytes from the kernel's `matrices`
+    uint32_t instance_base, rows_base;
+    uint32_t node_base;         // first of its n_nodes records in the kept-nodes buffers
+    float placement[12];
+};
+static_assert(sizeof(ClipActorRow) == 80, "five 16-byte pieces");
+
+// sample_channel: one channel at `time` (clamped to the first / last key), in double from the fp32 keys, rounded once.
+// COMPS 3: translation / scale. COMPS 4: a rotation, slerp along the shorter arc between the normalised keys, normalised.
+SR_CLIP_HD void clip_normalise(double* q) {
+    const double len = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (len > 0.0) for (int c = 0; c < 4; c++) q[c] /= len;
+}
+template <int COMPS>
+SR_CLIP_HD void clip_sample_channel(const float* times, const float* values, uint32_t n, uint32_t interpolation, double time, float* out) {
+    uint32_t i = 0;
+    double u = 0.0;
+    if (time <= (double)times[0]) i = 0;
+    else if (time >= (double)times[n - 1]) i = n - 1;
+    else {
+        uint32_t lo = 0, hi = n - 1;                                              // times[lo] <= time < times[hi]
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if ((double)times[mid] <= time) lo = mid; else hi = mid; }
+        i = lo;
+        if (interpolation == kClipLinear) u = (time - (double)times[i]) / ((double)times[i + 1] - (double)times[i]);
+    }
+    double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, r[4];
+    for (int c = 0; c < COMPS; c++) { a[c] = values[(size_t)i * COMPS + c]; b[c] = values[(size_t)(u > 0.0 ? i + 1 : i) * COMPS + c]; }
+    if (COMPS == 3) {
+        for (int c = 0; c < 3; c++) out[c] = (float)(u > 0.0 ? a[c] + u * (b[c] - a[c]) : a[c]);
+        return;
+    }
+    clip_normalise(a);
+    for (int c = 0; c < 4; c++) r[c] = a[c];
+    if (u > 0.0) {
+        clip_normalise(b);
+        if (a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] < 0.0) for (int c = 0; c < 4; c++) b[c] = -b[c];
+        double d2 = 0.0, s2 = 0.0;
+        for (int c = 0; c < 4; c++) { d2 += (a[c] - b[c]) * (a[c] - b[c]); s2 += (a[c] + b[c]) * (a[c] + b[c]); }
+        const double theta = 2.0 * atan2(sqrt(d2), sqrt(s2));
+        if (theta < 1e-9) for (int c = 0; c < 4; c++) r[c] = a[c] + u * (b[c] - a[c]);
+        else {
+            const double wa = sin((1.0 - u) * theta) / sin(theta), wb = sin(u * theta) / sin(theta);
+            for (int c = 0; c < 4; c++) r[c] = wa * a[c] + wb * b[c];
+        }
+        clip_normalise(r);
+    }
+    for (int c = 0; c < 4; c++) out[c] = (float)r[c];
+}
+
+// trs_matrix: translation * rotation * scale, fp32, row-major 4x4.
+SR_CLIP_HD void clip_trs_matrix(const float* t, const float* q, const float* s, float* m) {
+    const float x = q[0], y = q[1], z = q[2], w = q[3];
+    const float x2 = x + x, y2 = y + y, z2 = z + z;
+    const float xx2 = x2 * x, xy2 = x2 * y, xz2 = x2 * z, yy2 = y2 * y, yz2 = y2 * z, zz2 = z2 * z;
+    const float sy2 = y2 * w, sz2 = z2 * w, sx2 = x2 * w;
+    const float R[9] = {1.0f - yy2 - zz2, xy2 - sz2, xz2 + sy2,
+                        xy2 + sz2, 1.0f - xx2 - zz2, yz2 - sx2,
+                        xz2 - sy2, yz2 + sx2, 1.0f - xx2 - yy2};
+    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) m[i * 4 + j] = R[i * 3 + j] * s[j]; m[i * 4 + 3] = t[i]; }
+    m[12] = 0.0f; m[13] = 0.0f; m[14] = 0.0f; m[15] = 1.0f;
+}
+
+// One row of mul(a, b): the loader's expression on 4x4, k = 0..3 in order.
+SR_CLIP_HD void clip_mul_row(const float* a_row, const float* b, float* out) {
+    for (int j = 0; j < 4; j++) out[j] = ((a_row[0] * b[j] + a_row[1] * b[4 + j]) + a_row[2] * b[8 + j]) + a_row[3] * b[12 + j];
+}
+SR_CLIP_HD void clip_mul(const float* a, const float* b, float* out) {
+    for (int i = 0; i < 4; i++) clip_mul_row(a + 4 * i, b, out + 4 * i);
+}
+SR_CLIP_HD void clip_identity(float* m) {
+    for (int i = 0; i < 16; i++) m[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+}
+// A 3x4 transform as the 4x4 the loader multiplies: the rows, then (0, 0, 0, 1).
+SR_CLIP_HD void clip_widen(const float* m12, float* m16) {
+    for (int i = 0; i < 12; i++) m16[i] = m12[i];
+    m16[12] = 0.0f; m16[13] = 0.0f; m16[14] = 0.0f; m16[15] = 1.0f;
+}
+
+// invert_affine: cofactors and determinant in double, rounded once to fp32; the three rows of the inverse. false: singular or
+// not finite.
+SR_CLIP_HD bool clip_finite(double v) { return v - v == 0.0; }
+SR_CLIP_HD bool clip_finite(float v) { return v - v == 0.0f; }
+SR_CLIP_HD bool clip_invert_affine(const float* M, float* inv) {
+    const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
+    const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+    const double det = a00 * c00 + a01 * c01 + a02 * c02;
+    const double id = 1.0 / det;
+    const double R[9] = {c00 * id, (a02 * a21 - a01 * a22) * id, (a01 * a12 - a02 * a11) * id,
+                         c01 * id, (a00 * a22 - a02 * a20) * id, (a02 * a10 - a00 * a12) * id,
+                         c02 * id, (a01 * a20 - a00 * a21) * id, (a00 * a11 - a01 * a10) * id};
+    const double T[3] = {M[3], M[7], M[11]};
+    bool finite = clip_finite(id) && det != 0.0;
+    for (int row = 0; row < 3; row++) {
+        for (int c = 0; c < 3; c++) inv[4 * row + c] = (float)R[3 * row + c];
+        inv[4 * row + 3] = (float)(-(R[3 * row] * T[0] + R[3 * row + 1] * T[1] + R[3 * row + 2] * T[2]));
+        for (int c = 0; c < 4; c++) finite = finite && clip_finite(inv[4 * row + c]);
+    }
+    return finite;
+}
+
+}  // namespace srd

@@ -9,6 +9,7 @@
 // sites. Host-only code: no HIP here.
 #include <zlib.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -18,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "clip.h"
 #include "host.h"
 
 namespace {
@@ -1089,6 +1091,99 @@ struct GltfLoader {
         return true;
     }
 
+    // sr_gltf_bake_clip: everything pose() derives from the document for one animation, once, as flat tables (clip.h). The
+    // hierarchy is walked as globals_from walks it; the nodes are then grouped by depth, the walk's order kept within a level.
+    struct BakeVisit { long node; uint32_t parent, depth; };
+    bool bake_walk(long node_index, uint32_t parent, int depth, std::vector<BakeVisit>& visits) {
+        if (depth > 256) return fail("node hierarchy too deep (cycle?)");
+        const Json* node = element("nodes", node_index);
+        if (!node) return fail("scene refers to a missing node");
+        if (visits.size() >= (1u << 20)) return fail("the scene's roots reach more than 2^20 nodes", SR_ERR_UNSUPPORTED);
+        const uint32_t me = (uint32_t)visits.size();
+        visits.push_back(BakeVisit{node_index, parent, (uint32_t)depth});
+        const Json* children = node->get("children");
+        for (size_t c = 0; children && c < children->size(); c++)
+            if (!bake_walk(as_index(children->arr[c]), me, depth + 1, visits)) return false;
+        return true;
+    }
+    bool bake_clip(long anim, SrClip& clip) {
+        const Animation* a = nullptr;
+        if (anim >= 0) {
+            a = animation((uint32_t)anim);
+            if (!a) return false;
+            if (a->cubic) return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED);
+        }
+        std::vector<BakeVisit> visits;
+        long scene_index = doc.index("scene");
+        if (scene_index < 0) scene_index = 0;
+        const Json* scene = element("scenes", scene_index);
+        const Json* roots = scene ? scene->get("nodes") : nullptr;
+        for (size_t i = 0; roots && i < roots->size(); i++)
+            if (!bake_walk(as_index(roots->arr[i]), srd::kClipNoNode, 0, visits)) return false;
+        std::vector<uint32_t> clip_of(n_nodes(), srd::kClipNoNode);        // glTF node -> clip node
+        for (const BakeVisit& v : visits) {
+            if (clip_of[v.node] != srd::kClipNoNode) return fail("a node the scene's roots reach twice is not supported in a baked clip", SR_ERR_UNSUPPORTED);
+            clip_of[v.node] = 0;
+        }
+        if (visits.size() > srd::kClipMaxNodes)
+            return fail("a clip of " + std::to_string(visits.size()) + " nodes is not supported: the device kernel holds " + std::to_string(srd::kClipMaxNodes) + " nodes", SR_ERR_UNSUPPORTED);
+        srh::ClipParts p;
+        uint32_t n_levels = 0;
+        for (const BakeVisit& v : visits) n_levels = std::max(n_levels, v.depth + 1);
+        std::vector<uint32_t> order(visits.size(), 0);                      // visit -> clip node
+        p.levels.assign(n_levels + 1, 0);
+        for (const BakeVisit& v : visits) p.levels[v.depth + 1]++;
+        for (uint32_t l = 0; l < n_levels; l++) p.levels[l + 1] += p.levels[l];
+        { std::vector<uint32_t> next(p.levels.begin(), p.levels.end() - 1); for (size_t v = 0; v < visits.size(); v++) order[v] = next[visits[v].depth]++; }
+        p.nodes.resize(visits.size());
+        for (size_t v = 0; v < visits.size(); v++) {
+            srd::ClipNode& n = p.nodes[order[v]];
+            memset(&n, 0, sizeof(n));
+            const Json& node = *element("nodes", visits[v].node);
+            n.parent = visits[v].parent == srd::kClipNoNode ? srd::kClipNoNode : order[visits[v].parent];
+            n.gltf_node = (uint32_t)visits[v].node; n.level = visits[v].depth;
+            node_trs(node, n.trs, n.trs + 3, n.trs + 7);
+            const Mat4 m = node_matrix(node);
+            memcpy(n.matrix, m.m, 64);
+            clip_of[visits[v].node] = order[v];
+        }
+        for (size_t c = 0; a && c < a->channels.size(); c++) {
+            const Channel& k = a->channels[c];
+            const uint32_t node = clip_of[k.node];
+            if (node == srd::kClipNoNode) continue;                           // not part of the scene: pose() samples it for nobody
+            bool later = false;                                               // the host's loop leaves the later of two channels on one node and path
+            for (size_t e = c + 1; e < a->channels.size() && !later; e++) later = a->channels[e].node == k.node && a->channels[e].path == k.path;
+            if (later) continue;
+            const uint32_t comps = k.path == kPathRotation ? 4 : 3, nk = (uint32_t)k.times.size();
+            p.channels.push_back(srd::ClipChannel{node, (uint32_t)k.path, k.interpolation == kStep ? srd::kClipStep : srd::kClipLinear, nk, (uint32_t)p.times.size(), (uint32_t)p.values.size(), {0, 0}});
+            p.times.insert(p.times.end(), k.times.begin(), k.times.end());
+            p.values.insert(p.values.end(), k.values.begin(), k.values.begin() + (size_t)nk * comps);
+            p.nodes[node].animated |= 1u << k.path;
+            clip.duration = std::fmax(clip.duration, k.times[nk - 1]);
+        }
+        for (srd::ClipNode& n : p.nodes) memcpy(&n.trs[10], &n.animated, 4);
+        std::map<long, long> mesh_node_of;                                    // skin -> the first instanced node that wears it
+        for (const GltfScene::InstanceSource& src : out.instance_sources) {
+            const Json* node = element("nodes", src.node);
+            if (node && node->has("skin") && node->index("skin") >= 0) mesh_node_of.emplace(node->index("skin"), src.node);
+            p.instances.push_back(clip_of[src.node]);
+        }
+        for (const auto& sk : mesh_node_of) {
+            const SkinData* sd = skin_data((uint32_t)sk.first);
+            if (!sd) return false;
+            p.skins.push_back(srd::ClipSkin{(uint32_t)sk.first, clip_of[sk.second], (uint32_t)sd->joint_nodes.size(), (uint32_t)p.joint_nodes.size()});
+            for (size_t j = 0; j < sd->joint_nodes.size(); j++) {
+                if (clip_of[sd->joint_nodes[j]] == srd::kClipNoNode) return fail("a joint node of the skin is not part of the scene");
+                p.joint_nodes.push_back(clip_of[sd->joint_nodes[j]]);
+                p.joint_skins.push_back((uint32_t)p.skins.size() - 1);
+                p.inverse_bind.push_back(sd->inverse_bind[j]);
+            }
+        }
+        clip.animation = (int32_t)anim;
+        srh::clip_assemble(p, clip);
+        return true;
+    }
+
     bool build() {
         // samplers (gltf/mod.rs:90-99, scene.rs:68-83): absent filters default to LINEAR, wrap defaults to REPEAT (10497)
         const Json* smp = doc.get("samplers");
@@ -1356,6 +1451,16 @@ int sr_gltf_pose(const SrGltf* g, int32_t animation, float time_seconds, SrTrans
     if (animation < -1) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_pose: the animation is an index, or -1 for the file's static pose");
     srh::GltfLoader* L = rig_loader(g);
     if (!L->pose(animation, time_seconds, instance_transforms, skin, joint_matrices)) return srh::set_error(L->err_code, "sr_gltf_pose: " + L->err);
+    return SR_OK;
+}
+
+int sr_gltf_bake_clip(const SrGltf* g, int32_t animation, SrClip** out) {
+    if (!g || !out) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_bake_clip: null argument");
+    if (animation < -1) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_bake_clip: the animation is an index, or -1 for the file's static pose");
+    srh::GltfLoader* L = rig_loader(g);
+    std::unique_ptr<SrClip> clip(new SrClip());
+    if (!L->bake_clip(animation, *clip)) return srh::set_error(L->err_code, "sr_gltf_bake_clip: " + L->err);
+    *out = clip.release();
     return SR_OK;
 }
 

@@ -682,6 +682,31 @@ int sr_renderer_pose_meshes(SrRenderer* r, const SrPoseItem* items, uint32_t n_i
     return first_scene_poses(r, n_items, [&](uint32_t k) { return items[k].key; }, [&](SrScene* sc) { return sr_scene_pose_meshes(sc, items, n_items, stream); });
 }
 
+// Clips live on the first slot's scene only: that scene evaluates them and poses, the further replicas take the posed records
+// (first_scene_poses), and the instance transforms the clip kernel wrote belong to the first device.
+int sr_renderer_attach_clip(SrRenderer* r, const SrClip* clip, uint32_t* clip_id) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "attach_clip: null argument (the renderer)");
+    return sr_scene_attach_clip(r->slot[0].scene, clip, clip_id);
+}
+
+int sr_renderer_detach_clip(SrRenderer* r, uint32_t clip_id) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "detach_clip: null argument (the renderer)");
+    return sr_scene_detach_clip(r->slot[0].scene, clip_id);
+}
+
+int sr_renderer_pose_actors(SrRenderer* r, const SrClipActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items, SrTransform* d_instance_transforms,
+                            uint32_t flags, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "pose_actors: null argument (the renderer)");
+    if (n_items && !items) return rfail(SR_ERR_INVALID_ARG, "pose_actors: null argument (actors or items, with a count > 0)");
+    return first_scene_poses(r, n_items, [&](uint32_t k) { return items[k].key; },
+                             [&](SrScene* sc) { return sr_scene_pose_actors(sc, actors, n_actors, items, n_items, d_instance_transforms, flags, stream); });
+}
+
+int sr_renderer_actor_pose_info(const SrRenderer* r, SrActorPoseInfo* out) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_actor_pose_info: null argument (the renderer)");
+    return sr_scene_actor_pose_info(r->slot[0].scene, out);
+}
+
 // How sr_renderer_pose_scene poses (SR_POSE_BATCH_*).
 int sr_renderer_set_pose_batch(SrRenderer* r, uint32_t mode) {
     if (mode > SR_POSE_BATCH_ON) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_pose_batch: mode must be SR_POSE_BATCH_OFF or SR_POSE_BATCH_ON");

@@ -190,6 +190,142 @@ def _pose_items(items):
     return rows, C.c_uint32(len(items)), keep
 
 
+class ActorArgs:
+    """The arguments of pose_actors packed once (abi.SrClipActor / abi.SrActorPoseItem arrays and the numpy arrays they point
+    into): `actors` is a sequence of (clip id, time in seconds, placement [12] float32 or None, instance rows uint32 or None,
+    instance base), `items` one of (key, actor index, skin index or None, weights or None). set_times() rewrites the times in
+    place, so a crowd's per-frame work on the host is that and the call."""
+
+    def __init__(self, actors, items):
+        actors, items = [tuple(a) for a in actors], [tuple(i) for i in items]
+        self.actors, self.items, self.keep = (abi.SrClipActor * max(len(actors), 1))(), (abi.SrActorPoseItem * max(len(items), 1))(), []
+        self.n_actors, self.n_items = len(actors), len(items)
+        for a, ac in enumerate(actors):
+            if len(ac) != 5:
+                raise ValueError("pose_actors: actor %d: an actor is (clip id, time, placement, instance rows, instance base), %d values given" % (a, len(ac)))
+            row = self.actors[a]
+            row.clip_id, row.time_seconds, row.instance_base = int(ac[0]), float(ac[1]), int(ac[4])
+            if ac[2] is not None:
+                m = np.ascontiguousarray(ac[2])
+                if m.dtype not in (np.dtype(np.float32), abi.TRANSFORM) or m.nbytes != 48:
+                    raise ValueError("pose_actors: actor %d: the placement must be 12 float32 (row-major 3x4)" % a)
+                self.keep.append(m)
+                row.placement = m.ctypes.data
+            if ac[3] is not None:
+                r = np.ascontiguousarray(ac[3])
+                if r.dtype != np.dtype(np.uint32) or r.ndim != 1:
+                    raise ValueError("pose_actors: actor %d: the instance rows must be a one-dimensional numpy uint32 array" % a)
+                self.keep.append(r)
+                row.instance_rows = r.ctypes.data if len(r) else None
+        for i, it in enumerate(items):
+            if len(it) != 4:
+                raise ValueError("pose_actors: item %d: an item is (key, actor, skin, weights), %d values given" % (i, len(it)))
+            row = self.items[i]
+            row.key, row.actor, row.skin = int(it[0]), int(it[1]), abi.ACTOR_NO_SKIN if it[2] is None else int(it[2])
+            if it[3] is not None:
+                try:
+                    w, nt = _morph_weights(it[3])
+                except ValueError as e:
+                    raise ValueError("pose_actors: item %d: %s" % (i, e))
+                self.keep.append(w)
+                row.weights, row.n_targets = w.ctypes.data, nt
+
+    def set_times(self, times):
+        for a, t in enumerate(times):
+            self.actors[a].time_seconds = float(t)
+
+
+def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index):
+    args = actors if isinstance(actors, ActorArgs) else ActorArgs(actors, items)
+    ptr, stream = None, None
+    if tensor is not None:
+        import torch
+        if not getattr(tensor, "is_cuda", False) or tensor.device.index != device_index:
+            raise ValueError("pose_actors: the instance transforms must be a tensor on cuda:%d" % device_index)
+        if str(tensor.dtype) != "torch.float32" or not tensor.is_contiguous() or tensor.numel() % 12:
+            raise ValueError("pose_actors: the instance transforms must be contiguous float32, 12 a transform")
+        ptr, stream = C.c_void_p(tensor.data_ptr()), C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)
+    check(fn(handle, args.actors, C.c_uint32(args.n_actors), args.items, C.c_uint32(args.n_items), ptr,
+             C.c_uint32(abi.ACTORS_KEEP_NODES if keep_nodes else 0), stream))
+
+
+class Clip:
+    """A baked clip (sr_gltf_bake_clip): one animation of a file, or its static pose, as flat tables. Immutable; it does not
+    refer to the Gltf afterwards."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self.info = self._info()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().sr_clip_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _info(self):
+        info = abi.SrClipInfo()
+        check(lib().sr_clip_info(self._h, C.byref(info)))
+        return info
+
+    def skin(self, skin):
+        """-> (first matrix in the clip's concatenated joint list, joint count) of the file's skin `skin` (sr_clip_skin)."""
+        first, n = C.c_uint32(), C.c_uint32()
+        check(lib().sr_clip_skin(self._h, C.c_uint32(skin), C.byref(first), C.byref(n)))
+        return first.value, n.value
+
+    def layout(self):
+        """-> (abi.CLIP_NODE_INFO [n_nodes], abi.CLIP_CHANNEL_INFO [n_channels], clip node of every instance uint32) (sr_clip_layout)."""
+        i = self.info
+        nodes, chans = np.zeros(max(i.n_nodes, 1), abi.CLIP_NODE_INFO), np.zeros(max(i.n_channels, 1), abi.CLIP_CHANNEL_INFO)
+        inst = np.zeros(max(i.n_instances, 1), np.uint32)
+        check(lib().sr_clip_layout(self._h, _p(nodes), _p(chans), _p(inst)))
+        return nodes[:i.n_nodes], chans[:i.n_channels], inst[:i.n_instances]
+
+    def channel_keys(self, channel):
+        """-> (key times [n_keys], values [n_keys, 3 or 4]) of a channel, the file's float32 (sr_clip_channel_keys)."""
+        c = self.layout()[1][channel]
+        tp, vp = C.c_void_p(), C.c_void_p()
+        check(lib().sr_clip_channel_keys(self._h, C.c_uint32(channel), C.byref(tp), C.byref(vp)))
+        comps = 4 if c["path"] == 1 else 3
+        return _np_from(tp, int(c["n_keys"]), np.float32), _np_from(vp, int(c["n_keys"]) * comps, np.float32).reshape(-1, comps)
+
+    def sample_host(self, time_seconds):
+        """-> abi.NODE_TRS [n_nodes]: every clip node's TRS at `time_seconds` (sr_clip_sample_host)."""
+        trs = np.zeros(max(self.info.n_nodes, 1), abi.NODE_TRS)
+        check(lib().sr_clip_sample_host(self._h, C.c_float(time_seconds), _p(trs)))
+        return trs[:self.info.n_nodes]
+
+    def compose_host(self, trs, placement=None):
+        """abi.NODE_TRS records -> (joint matrices of all skins [n_joints, 12], instance transforms [n_instances, 12], the lowest
+        singular skin or None). A singular skin is reported, not raised (sr_clip_compose_host)."""
+        i = self.info
+        trs = np.ascontiguousarray(trs, dtype=abi.NODE_TRS)
+        if len(trs) != i.n_nodes:
+            raise ValueError("compose_host: %d records given, the clip has %d nodes" % (len(trs), i.n_nodes))
+        joints, xf, bad = np.zeros((max(i.n_joints, 1), 12), np.float32), np.zeros((max(i.n_instances, 1), 12), np.float32), C.c_uint32()
+        pl = None if placement is None else np.ascontiguousarray(placement, dtype=np.float32).reshape(12)
+        rc = lib().sr_clip_compose_host(self._h, _p(trs), None if pl is None else _p(pl), _p(joints), _p(xf), C.byref(bad))
+        if rc != 0 and bad.value == 0xFFFFFFFF:
+            check(rc)
+        return joints[:i.n_joints], xf[:i.n_instances], (None if bad.value == 0xFFFFFFFF else bad.value)
+
+    def pose_host(self, time_seconds, placement=None, joints=True):
+        """-> (joint matrices of all skins [n_joints, 12] or None, instance transforms [n_instances, 12]) at `time_seconds`:
+        sr_gltf_pose restated over the clip, bit for bit (sr_clip_pose_host)."""
+        i = self.info
+        jm = np.zeros((max(i.n_joints, 1), 12), np.float32) if joints else None
+        xf = np.zeros((max(i.n_instances, 1), 12), np.float32)
+        pl = None if placement is None else np.ascontiguousarray(placement, dtype=np.float32).reshape(12)
+        check(lib().sr_clip_pose_host(self._h, C.c_float(time_seconds), None if pl is None else _p(pl), None if jm is None else _p(jm), _p(xf)))
+        return (None if jm is None else jm[:i.n_joints]), xf[:i.n_instances]
+
+
 def pose_batch_plan(n_vertices):
     """The layout of a batch of meshes of these vertex counts -> (first_block uint32[n], vertex_base uint64[n], n_blocks): host
     only (sr_pose_batch_plan)."""
@@ -454,6 +590,41 @@ class Scene:
         info = abi.SrPoseBatchInfo()
         check(lib().sr_scene_pose_batch_info(self._h, C.byref(info)))
         return info
+
+    def attach_clip(self, clip):
+        """Uploads a baked clip's tables once -> its id on this scene (sr_scene_attach_clip)."""
+        cid = C.c_uint32()
+        check(lib().sr_scene_attach_clip(self._h, clip._h, C.byref(cid)))
+        return cid.value
+
+    def detach_clip(self, clip_id):
+        check(lib().sr_scene_detach_clip(self._h, C.c_uint32(clip_id)))
+
+    def pose_actors(self, actors, items=(), tensor=None, keep_nodes=False):
+        """pose_meshes with the joint matrices evaluated on the GPU from attached clips: `actors` and `items` as ActorArgs takes
+        them (or an ActorArgs), `tensor` a float32 torch tensor on the scene's device that takes the instance transforms at the
+        actors' rows, or None (sr_scene_pose_actors)."""
+        _actor_call(lib().sr_scene_pose_actors, self._h, actors, items, tensor, keep_nodes, self.device_index)
+
+    def actor_pose_info(self):
+        """-> abi.SrActorPoseInfo: the last pose_actors that reached the device (sr_scene_actor_pose_info)."""
+        info = abi.SrActorPoseInfo()
+        check(lib().sr_scene_actor_pose_info(self._h, C.byref(info)))
+        return info
+
+    def read_actor_nodes(self, actor, n_nodes):
+        """-> (abi.NODE_TRS [n_nodes], global matrices [n_nodes, 16] float32) of an actor of the last pose_actors with keep_nodes
+        (sr_scene_read_actor_nodes)."""
+        trs, g = np.zeros(max(n_nodes, 1), abi.NODE_TRS), np.zeros((max(n_nodes, 1), 16), np.float32)
+        check(lib().sr_scene_read_actor_nodes(self._h, C.c_uint32(actor), _p(trs), _p(g)))
+        return trs[:n_nodes], g[:n_nodes]
+
+    def read_actor_matrices(self, actor, n_joints):
+        """-> the joint matrices [n_joints, 12] float32 the posing kernel read for an actor of the last pose_actors
+        (sr_scene_read_actor_matrices)."""
+        m = np.zeros((max(n_joints, 1), 12), np.float32)
+        check(lib().sr_scene_read_actor_matrices(self._h, C.c_uint32(actor), _p(m)))
+        return m[:n_joints]
 
     def mesh_morph_info(self, key):
         """-> abi.SrMeshMorphInfo: the targets of the mesh's morph (0: none), the poses taken, the active targets, the refusal and
@@ -1036,6 +1207,20 @@ class Gltf:
         return xf[:self.n_instances], joints
 
 
+    def bake_clip(self, animation):
+        """Animation `animation` of the file (-1: its static pose) as a baked Clip (sr_gltf_bake_clip)."""
+        h = C.c_void_p()
+        check(lib().sr_gltf_bake_clip(self._h, C.c_int32(animation), C.byref(h)))
+        return Clip(h)
+
+    def instance_blases(self):
+        """-> the blas index of every instance, in sr_gltf_instance order (uint32)."""
+        out, b = np.zeros(self.n_instances, np.uint32), C.c_uint32()
+        for i in range(self.n_instances):
+            check(lib().sr_gltf_instance(self._h, C.c_uint32(i), C.byref(b), None))
+            out[i] = b.value
+        return out
+
     def sample_node(self, animation, time_seconds, node):
         """-> (translation [3], rotation [4], scale [3] float32, mask of the animated channels) node `node` composes from in pose()."""
         t, q, s, m = np.zeros(3, np.float32), np.zeros(4, np.float32), np.zeros(3, np.float32), C.c_uint32()
@@ -1055,7 +1240,8 @@ class LoadedScene:
         self.group = group.value
         self.keys, self.counts = _np_from(kp, nk.value, np.uint64), _np_from(cp, nk.value, np.uint32)
         self.n_transforms = nt.value
-        self.instances = self.grouped(_np_from(tp, nt.value * 12, np.float32).reshape(-1, 12))
+        self.instance_blas = None
+        self.instances =self.grouped(_np_from(tp, nt.value * 12, np.float32).reshape(-1, 12))
 
     def grouped(self, transforms):
         """[n_transforms, 12] in the loaded scene's order -> [(key, [3x4 transforms])], what Renderer.render takes."""
@@ -1064,6 +1250,21 @@ class LoadedScene:
             inst.append((int(k), [transforms[o + j].copy() for j in range(int(c))]))
             o += int(c)
         return inst
+
+    def instance_rows(self, base=0):
+        """-> uint32 [n_transforms]: for every instance in sr_gltf_instance order, its row in the order grouped() takes (by blas,
+        the file's order kept within one), counted from `base`: what an actor's instance_rows are when a crowd's transforms lie
+        copy after copy. Needs the scene to come from Renderer.load_scene, which notes the file's blas of every instance."""
+        if self.instance_blas is None:
+            raise ValueError("instance_rows: the loaded scene does not know the file's instance order (Renderer.load_scene notes it)")
+        order = np.argsort(self.instance_blas, kind="stable")
+        rows = np.zeros(len(order), np.uint32)
+        rows[order] = np.arange(len(order), dtype=np.uint32)
+        return (rows + np.uint32(base)).astype(np.uint32)
+
+    def layout(self):
+        """-> [(key, count), ...]: what set_instances_device / render_device_transforms take beside the tensor."""
+        return [(int(k), int(c)) for k, c in zip(self.keys, self.counts)]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1282,6 +1483,25 @@ class Renderer:
         rows, n, keep = _pose_items(items)
         check(lib().sr_renderer_pose_meshes(self._h, rows, n, None))
 
+    def attach_clip(self, clip):
+        """Scene.attach_clip on the first device slot's scene, which evaluates the clips (sr_renderer_attach_clip)."""
+        cid = C.c_uint32()
+        check(lib().sr_renderer_attach_clip(self._h, clip._h, C.byref(cid)))
+        return cid.value
+
+    def detach_clip(self, clip_id):
+        check(lib().sr_renderer_detach_clip(self._h, C.c_uint32(clip_id)))
+
+    def pose_actors(self, actors, items=(), tensor=None, keep_nodes=False):
+        """Scene.pose_actors on the first device slot; every further slot takes each item's posed vertices by a device copy.
+        `tensor` lives on the first slot's GPU: render_device_transforms takes it from there (sr_renderer_pose_actors)."""
+        _actor_call(lib().sr_renderer_pose_actors, self._h, actors, items, tensor, keep_nodes, self.devices[0])
+
+    def actor_pose_info(self):
+        info = abi.SrActorPoseInfo()
+        check(lib().sr_renderer_actor_pose_info(self._h, C.byref(info)))
+        return info
+
     def set_pose_batch(self, on):
         """Whether pose_scene poses the file's rigged and morphed meshes by one pose_meshes (sr_renderer_set_pose_batch). Off by
         default; SR_POSE_BATCH=on in the environment turns it on at creation."""
@@ -1321,7 +1541,9 @@ class Renderer:
         """Renderer::load_scene for an open Gltf -> LoadedScene (sr_renderer_load_scene)."""
         ls = C.c_void_p()
         check(lib().sr_renderer_load_scene(self._h, gltf._h, C.byref(ls)))
-        return LoadedScene(ls)
+        loaded = LoadedScene(ls)
+        loaded.instance_blas = gltf.instance_blases()
+        return loaded
 
     def attach_skins(self, gltf, loaded):
         """Attaches the rig of every skinned mesh of a loaded scene and makes those meshes BUILD_RAPIDLY_CHANGING
