@@ -4,10 +4,14 @@ frame Renderer.pose_scene samples the joint and the weight channels, blends the 
 library's kernels (morph first, then skin; the posed vertices never visit the host) and returns the instance transforms for the
 frame. Writes the last frame as a PNG.
 
-    python examples/morph_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out morph.png] [--device-lights]
+    python examples/morph_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out morph.png] [--device-lights] [--device-clips]
 
 --device-lights: the frame's light table is built on the device (Renderer.set_light_table_build("device")), so that a posed mesh
 with an emissive material never visits the host either.
+
+--device-clips: the animation is baked once (Gltf.bake_clip) and attached, and every frame is one Renderer.pose_actors: the GPU samples
+the joint channels and the weight channels of the clip (ClipWeights), so neither the joint matrices, nor the morph weights, nor the
+instance transforms come from host memory. A mesh whose weight channel the loader refuses (CUBICSPLINE) is left unmorphed.
 
 Default file: tests/golden/morph_bar.glb. Needs a GPU: the product path has no CPU fallback.
 """
@@ -30,6 +34,7 @@ def main():
     ap.add_argument("--out", default="morph.png")
     ap.add_argument("--camera", default="0.8,1.4,7.0,0.8,1.0,0.0,45", help="position, target, vertical field of view in degrees")
     ap.add_argument("--device-lights", action="store_true")
+    ap.add_argument("--device-clips", action="store_true")
     ap.add_argument("--batch-trees", action="store_true", help="build the small meshes' trees in one batched device launch when their ninth update asks for a fast build")
     args = ap.parse_args()
     from sunray_amd import runtime as rt
@@ -54,9 +59,34 @@ def main():
     r.attach_skins(gltf, loaded)
     r.attach_morphs(gltf, loaded)
     instances = loaded.instances
-    for f in range(args.frames):
-        instances = r.pose_scene(gltf, loaded, args.animation, duration * f / max(args.frames - 1, 1))
-        r.wait_frame(r.render(camera, instances))
+    if args.device_clips:
+        import torch
+        clip = gltf.bake_clip(args.animation)
+        cid = r.attach_clip(clip)
+        items = []
+        for b, d in morphed:
+            skin = gltf.blas_skin(b)[0]
+            weights = None
+            if d is not None:
+                m = clip.morph(b)
+                if m["state"] == 2:         # abi.CLIP_MORPH_UNAVAILABLE
+                    print("mesh %d: its weights are not played: %s" % (b, m["error"]))
+                else:
+                    weights = rt.ClipWeights(b)
+            if skin >= 0 or weights is not None:
+                items.append((int(loaded.keys[b]), 0, skin if skin >= 0 else None, weights))
+        out = torch.zeros((loaded.n_transforms, 12), dtype=torch.float32, device="cuda:%d" % r.devices[0])
+        rows = loaded.instance_rows(0)
+        for f in range(args.frames):
+            r.pose_actors([(cid, duration * f / max(args.frames - 1, 1), None, rows, 0)], items, out)
+            r.wait_frame(r.render_device_transforms(camera, loaded.layout(), out))
+        info = r.actor_pose_info()
+        print("pose_actors: %d launches, %d read-back, %d bytes uploaded a frame, %d item(s) with clip weights" % (info.launches, info.read_backs, info.upload_bytes, info.weight_items))
+        instances = loaded.grouped(out.cpu().numpy())
+    else:
+        for f in range(args.frames):
+            instances = r.pose_scene(gltf, loaded, args.animation, duration * f / max(args.frames - 1, 1))
+            r.wait_frame(r.render(camera, instances))
     for b, d in morphed:
         if d is not None:
             info = r.replica_scene(0).mesh_morph_info(int(loaded.keys[b]))

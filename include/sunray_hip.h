@@ -1271,6 +1271,35 @@ int sr_clip_skin(const SrClip* clip, uint32_t skin, uint32_t* first_matrix, uint
 int sr_clip_layout(const SrClip* clip, SrClipNodeInfo* nodes, SrClipChannelInfo* channels, uint32_t* instance_nodes);
 /* Channel `channel`'s keys as the clip holds them: n_keys times and n_keys x 3 (rotation: x 4) values; valid until sr_clip_destroy. */
 int sr_clip_channel_keys(const SrClip* clip, uint32_t channel, const float** times, const float** values);
+/* The morph sets of a clip: one for every blas of the file that has morph targets, holding what
+ * sr_gltf_morph_weights(gltf, animation, t, blas, ...) derives from the document: the blas and its first instancing node, the
+ * default weights, and where the baked animation has a `weights` channel on that node (the first one) its interpolation, key
+ * times and n_keys x n_targets values, the file's fp32 bytes. They are further tables of the clip's one block. SrClipInfo's
+ * n_channels, n_keys and duration_seconds and sr_clip_layout count the translation / rotation / scale channels only.
+ * A set sr_gltf_morph_weights would refuse (a CUBICSPLINE sampler on that channel, a sampler error, a short output accessor, the
+ * morph parse of the blas failing) does not refuse the bake: it is kept as SR_CLIP_MORPH_UNAVAILABLE with the loader's status and
+ * words, and naming it later refuses in those.
+ * sr_clip_morph_count: the number of sets. sr_clip_morph: the set of blas `blas`; for an unavailable set the call succeeds and
+ * sr_last_error() holds the loader's words. A blas without morph targets: SR_ERR_INVALID_ARG.
+ * sr_clip_morph_keys: the set's n_keys times and n_keys x n_targets values (NULL without a channel) and its n_targets default
+ * weights, valid until sr_clip_destroy; an unavailable set refuses with its status and words.
+ * sr_clip_weights_host: the host rule, sr_gltf_morph_weights restated over the set and held to it bit for bit, in its statuses
+ * and words too (a time that is not finite, another n_targets). The device kernel (clip_weights_kernel) includes the same
+ * arithmetic (csrc/clip_rule.h): +, -, x, / on fp32 and fp64 only, so the device equals it bit for bit without exception. */
+#define SR_CLIP_MORPH_CHANNEL 0u       /* a LINEAR or STEP `weights` channel */
+#define SR_CLIP_MORPH_DEFAULTS 1u      /* no channel (or the static pose): the default weights at every time */
+#define SR_CLIP_MORPH_UNAVAILABLE 2u
+typedef struct SrClipMorphInfo {
+    uint32_t blas, gltf_node /* 0xFFFFFFFF: the morph parse failed */, n_targets, n_keys;
+    uint32_t interpolation;            /* 0 LINEAR, 1 STEP */
+    uint32_t state;                    /* SR_CLIP_MORPH_* */
+    int32_t status;                    /* SR_OK, or what refused an unavailable set */
+    uint32_t reserved;
+} SrClipMorphInfo;                     /* 32 bytes */
+int sr_clip_morph_count(const SrClip* clip, uint32_t* n_sets);
+int sr_clip_morph(const SrClip* clip, uint32_t blas, SrClipMorphInfo* out);
+int sr_clip_morph_keys(const SrClip* clip, uint32_t blas, const float** times, const float** values, const float** default_weights);
+int sr_clip_weights_host(const SrClip* clip, float time_seconds, uint32_t blas, float* weights_out, uint32_t n_targets);
 /* The host rule: sr_gltf_pose restated over the baked clip, held to it bit for bit. The device kernel includes the same
  * arithmetic (csrc/clip_rule.h); host and device are built without contraction.
  * sr_clip_sample_host: n_nodes records, clip-node order: every node's TRS at time_seconds (sr_gltf_sample_node's values for the
@@ -1296,14 +1325,24 @@ int sr_clip_pose_host(const SrClip* clip, float time_seconds, const SrTransform*
  * On `stream`: the check words are preset; ONE upload (item rows, block table, active lists, actor rows, instance rows; no joint
  * matrices: the region the clip kernel writes lies outside the uploaded bytes); clip_pose_kernel; the posing kernel; ONE
  * read-back (two words per item, one per actor).
+ * Morph weights from the clip: an item whose `morph` is SR_ACTOR_CLIP_WEIGHTS(blas) takes the weights of that morph set of its
+ * actor's clip at the actor's time, evaluated on the device: clip_weights_kernel (one wave per such item, launched between the
+ * two kernels above and only when an item asks for it) samples the set, leaves out the weights that are +-0 and writes the
+ * item's active list (ascending target order) and its count where the posing kernel reads them. The upload then holds one more
+ * row of 32 bytes per such item and no weights; each such item has a slot of n_targets entries in the active arrays, outside
+ * the uploaded bytes unless the call also has items with host weights; the read-back takes one more word per such item, the
+ * count, which SrMeshMorphInfo.n_active reports. The active list is bit equal to the compaction of sr_clip_weights_host.
+ * sr_scene_read_item_active reads an item's list back as the posing kernel read it.
  * Numerics: translation, scale and STEP samples, samples at clamped and exact key times and everything composed from a TRS are
  * bit equal to sr_clip_pose_host. An interpolated rotation passes through atan2 and sin, where the device's libm and the host's
  * are not bit-identical: a component is the host's, its neighbouring fp32 value, or within 2^-44 of it.
  * Refused on the host before any device work, behind "pose_actors: actor <i>: " or "pose_actors: item <i>: ": an unknown clip id,
  * a time that is not finite (sr_gltf_pose's words), instance_rows or instance_base without d_instance_transforms, an actor or
  * skin index out of range, a skin whose joint count is not that of the mesh's attached rig, a key named twice, an item with
- * neither stage, and everything sr_scene_pose_meshes refuses for an item. The instance rows are the caller's to keep inside
- * d_instance_transforms.
+ * neither stage, and everything sr_scene_pose_meshes refuses for an item; for an item with clip weights: `weights` given as
+ * well, an actor out of range, a blas the clip has no set for, an unavailable set (its kept status and the loader's words), a set
+ * whose n_targets is not that of the mesh's attached morph, a mesh without a morph. The instance rows are the caller's to keep
+ * inside d_instance_transforms.
  * Refused on the device, all or nothing: a singular mesh-node transform (the actor's check word): sr_gltf_pose's status and
  * words for the lowest such actor; no mesh has changed. d_instance_transforms MAY HAVE BEEN WRITTEN by then: do not hand it to
  * sr_scene_set_instances_device after a refusal. A non-finite posed vertex refuses as in sr_scene_pose_meshes. */
@@ -1315,19 +1354,22 @@ typedef struct SrClipActor {           /* one character: a clip at a time. 32 by
 } SrClipActor;
 typedef struct SrActorPoseItem {       /* one mesh: what SrPoseItem is, with the joint matrices named rather than given. 32 bytes */
     uint64_t key; uint32_t actor, skin;        /* skin: the file's skin index, or SR_ACTOR_NO_SKIN: no skin stage */
-    const float* weights; uint32_t n_targets, reserved;   /* morph stage as in SrPoseItem: host weights, or NULL */
-} SrActorPoseItem;
+    const float* weights; uint32_t n_targets, morph;      /* morph stage as in SrPoseItem: host weights, or NULL; morph 0, or */
+} SrActorPoseItem;                                        /* SR_ACTOR_CLIP_WEIGHTS(blas): the actor's clip gives the weights (weights NULL) */
 #define SR_ACTOR_NO_SKIN 0xFFFFFFFFu
+#define SR_ACTOR_CLIP_WEIGHTS(blas) ((uint32_t)(blas) + 1u)
 #define SR_ACTORS_KEEP_NODES 1u        /* flags: also store every actor's sampled TRS and global matrices (sr_scene_read_actor_nodes) */
 typedef struct SrActorPoseInfo {       /* the last sr_scene_pose_actors that reached the device (a host refusal leaves it alone) */
     uint32_t actors, items;
     uint64_t nodes, channels;          /* nodes evaluated, channels sampled, over all actors */
     uint64_t upload_bytes;             /* the one upload */
-    uint32_t launches;                 /* 3 accepted (clip, pose, scatter), 2 refused */
+    uint32_t launches;                 /* 3 accepted (clip, pose, scatter), 2 refused; one more where clip_weights_kernel ran */
     uint32_t read_backs;               /* 1 */
     uint32_t calls;                    /* calls that reached the device since the scene was created */
-    uint32_t refused_actor, refused_item, reserved;   /* 0xFFFFFFFF: none */
-    double clip_ms, pose_ms, scatter_ms;   /* events, only while sr_scene_enable_timing is on; pose_ms includes the read-back */
+    uint32_t refused_actor, refused_item;      /* 0xFFFFFFFF: none */
+    uint32_t weight_items;             /* items whose weights came from their actor's clip */
+    double clip_ms, pose_ms, scatter_ms;   /* events, only while sr_scene_enable_timing is on; clip_ms: clip_pose_kernel and, where it
+                                            * ran, clip_weights_kernel; pose_ms includes the read-back */
     double host_ms;                    /* the whole call, wall clock */
 } SrActorPoseInfo;                     /* 88 bytes */
 int sr_scene_attach_clip(SrScene* scene, const SrClip* clip, uint32_t* clip_id);
@@ -1342,6 +1384,10 @@ int sr_scene_actor_pose_info(const SrScene* scene, SrActorPoseInfo* out);
  * block since. Both wait for the device. */
 int sr_scene_read_actor_nodes(const SrScene* scene, uint32_t actor, SrNodeTrs* trs, float* globals16);
 int sr_scene_read_actor_matrices(const SrScene* scene, uint32_t actor, SrTransform* joint_matrices);
+/* After a sr_scene_pose_actors that reached the device: item `item`'s active list as the posing kernel read it, whether the host
+ * or clip_weights_kernel wrote it: *n_active, then that many target indices and weights (room for the mesh's n_targets each;
+ * either may be NULL). An item without a morph stage has 0. SR_ERR_STATE under the rule of sr_scene_read_actor_matrices. */
+int sr_scene_read_item_active(const SrScene* scene, uint32_t item, uint32_t* index_out, float* weight_out, uint32_t* n_active);
 
 /* What Renderer::load_gltf / load_scene return (lib.rs:779-846): the asset group and the scene's instances
  * grouped per BLAS key in BLAS order. Keys are ResourceKey{group, index} packed as group << 32 | index

@@ -48,6 +48,7 @@ SYMBOLS = [
     "sr_probe_helper", "sr_probe_helper_layout",
     "sr_scene_pose_meshes", "sr_scene_pose_batch_info", "sr_pose_batch_plan", "sr_renderer_pose_meshes", "sr_renderer_set_pose_batch",
     "sr_gltf_bake_clip", "sr_clip_destroy", "sr_clip_info", "sr_clip_skin", "sr_clip_layout", "sr_clip_channel_keys","sr_clip_sample_host", "sr_clip_compose_host", "sr_clip_pose_host",
+    "sr_clip_morph_count", "sr_clip_morph", "sr_clip_morph_keys", "sr_clip_weights_host", "sr_scene_read_item_active",
     "sr_scene_attach_clip", "sr_scene_detach_clip", "sr_scene_pose_actors", "sr_scene_actor_pose_info", "sr_scene_read_actor_nodes", "sr_scene_read_actor_matrices",
     "sr_renderer_attach_clip", "sr_renderer_detach_clip", "sr_renderer_pose_actors", "sr_renderer_actor_pose_info",
 ]

@@ -236,6 +236,20 @@ CLIP_CHANNEL_INFO = np.dtype([("node", "<u4"), ("path", "<u4"), ("interpolation"
 NODE_TRS = np.dtype([("translation", "<f4", 3), ("rotation", "<f4", 4), ("scale", "<f4", 3), ("animated", "<u4"), ("reserved", "<u4")])  # SrNodeTrs, 48 B
 assert NODE_TRS.itemsize == 48
 CLIP_MAX_NODES, CLIP_NO_NODE, ACTOR_NO_SKIN, ACTORS_KEEP_NODES = 384, 0xFFFFFFFF, 0xFFFFFFFF, 1
+CLIP_MORPH_CHANNEL, CLIP_MORPH_DEFAULTS, CLIP_MORPH_UNAVAILABLE = 0, 1, 2  # SrClipMorphInfo.state
+
+
+def actor_clip_weights(blas):
+    """SR_ACTOR_CLIP_WEIGHTS(blas): SrActorPoseItem.morph of an item whose weights are that morph set of its actor's clip."""
+    return int(blas) + 1
+
+
+class SrClipMorphInfo(C.Structure):  # one morph set of a baked clip (sr_clip_morph), 32 B
+    _fields_ = [("blas", C.c_uint32), ("gltf_node", C.c_uint32), ("n_targets", C.c_uint32), ("n_keys", C.c_uint32), ("interpolation", C.c_uint32),
+                ("state", C.c_uint32), ("status", C.c_int32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(SrClipMorphInfo) == 32
 
 
 class SrClipActor(C.Structure):  # one character of sr_scene_pose_actors: a clip at a time, 32 B
@@ -244,13 +258,13 @@ class SrClipActor(C.Structure):  # one character of sr_scene_pose_actors: a clip
 
 
 class SrActorPoseItem(C.Structure):  # one mesh of sr_scene_pose_actors: SrPoseItem with the joint matrices named, 32 B
-    _fields_ = [("key", C.c_uint64), ("actor", C.c_uint32), ("skin", C.c_uint32), ("weights", C.c_void_p), ("n_targets", C.c_uint32), ("reserved", C.c_uint32)]
+    _fields_ = [("key", C.c_uint64), ("actor", C.c_uint32), ("skin", C.c_uint32), ("weights", C.c_void_p), ("n_targets", C.c_uint32), ("morph", C.c_uint32)]
 
 
 class SrActorPoseInfo(C.Structure):  # the last sr_scene_pose_actors that reached the device (sr_scene_actor_pose_info), 88 B
     _fields_ = [("actors", C.c_uint32), ("items", C.c_uint32), ("nodes", C.c_uint64), ("channels", C.c_uint64), ("upload_bytes", C.c_uint64),
                 ("launches", C.c_uint32), ("read_backs", C.c_uint32), ("calls", C.c_uint32), ("refused_actor", C.c_uint32), ("refused_item", C.c_uint32),
-                ("reserved", C.c_uint32), ("clip_ms", C.c_double), ("pose_ms", C.c_double), ("scatter_ms", C.c_double), ("host_ms", C.c_double)]
+                ("weight_items", C.c_uint32), ("clip_ms", C.c_double), ("pose_ms", C.c_double), ("scatter_ms", C.c_double), ("host_ms", C.c_double)]
 
 
 assert C.sizeof(SrClipInfo) == 40 and C.sizeof(SrClipActor) == 32 and C.sizeof(SrActorPoseItem) == 32 and C.sizeof(SrActorPoseInfo) == 88

@@ -28,6 +28,7 @@
 #include "pose_batch.h"
 #include "clip.h"
 #include "clip_pose.h"
+#include "clip_weights.h"
 #include "tl_record.h"
 
 namespace {
@@ -277,6 +278,9 @@ struct SrScene {
     SrActorPoseInfo actor_info{0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0.0, 0.0, 0.0, 0.0};
     struct ActorRecord { uint64_t matrix_byte; uint32_t n_joints, node_base, n_nodes; };
     std::vector<ActorRecord> actor_records;
+    // ... and each item's row and its slice of the active arrays (sr_scene_read_item_active); capacity: the entries of the slice
+    struct ItemActiveRecord { uint64_t row_byte, index_byte, weight_byte; uint32_t capacity; };
+    std::vector<ItemActiveRecord> item_active_records;
     bool actor_stage_current = false, actor_nodes_kept = false;
     DeviceBuffer d_actor_trs, d_actor_globals;
     // sr_scene_update_mesh_positions*: the face vectors of the last call (one or two 16-byte pieces per triangle), the uploaded
@@ -1013,15 +1017,17 @@ namespace {
 
 // What the pose path refuses on the host, before any device work, in the words of the entry point `who`: the mesh's slot into
 // *slot and the active list into `active` (2 * n_targets words: the indices of the targets whose weight is not 0, ascending,
-// then from word n_targets on their weights) and *n_active.
+// then from word n_targets on their weights) and *n_active. With `clip_targets` the morph stage takes its weights on the device,
+// from a morph set of *clip_targets targets: the mesh's morph is checked against that count, the list stays empty.
 int check_pose_args(SrScene* s, uint64_t key, const float* weights, uint32_t n_targets, bool joint_matrices, uint32_t n_joints, const char* who,
-                    uint32_t* slot, std::vector<uint32_t>& active, uint32_t* n_active) {
+                    uint32_t* slot, std::vector<uint32_t>& active, uint32_t* n_active, const uint32_t* clip_targets = nullptr) {
     int rc = find_mesh(s, key, who, slot);
     if (rc != SR_OK) return rc;
     const SrScene::MeshState::Morph& morph = s->mesh_state[*slot].morph;
     const SrScene::MeshState::Skin& skin = s->mesh_state[*slot].skin;
     char buf[200];
-    if (weights) {
+    if (clip_targets) n_targets = *clip_targets;
+    if (weights || clip_targets) {
         if (morph.n_targets == 0) return fail(SR_ERR_INVALID_ARG, "pose_mesh: the mesh has no morph targets (sr_scene_set_mesh_morph attaches them)");
         if (n_targets != morph.n_targets) {
             snprintf(buf, sizeof(buf), "pose_mesh: %u weights given, the morph was attached with %u targets", n_targets, morph.n_targets);
@@ -1113,6 +1119,10 @@ struct ActorFeed {
     uint32_t n_actors = 0, flags = 0;
     std::vector<srd::ClipActorRow> rows;
     std::vector<uint32_t> instance_rows, item_matrix, actor_joints, actor_nodes;
+    // an item whose weights come from its actor's clip: its row for clip_weights_kernel (0xFFFFFFFF: the weights are the host's,
+    // or none) and the set's n_targets; the rows (item, active_base and check_word are pose_items' to fill)
+    std::vector<uint32_t> item_weight_row, item_clip_targets;
+    std::vector<srd::ClipWeightRow> weight_rows;
     uint64_t n_matrices = 0, n_nodes = 0, n_channels = 0;
     SrTransform* d_instance_transforms = nullptr;
     SrActorPoseInfo* info = nullptr;
@@ -1132,6 +1142,12 @@ struct ActorFeed {
 // instance rows travel behind the batch's parts in the one upload, the clip kernel runs in front of the posing kernel, one more
 // check word per actor comes back in the one read-back (a singular mesh-node transform refuses like a non-finite vertex, before
 // it), and *feed->info takes the call's figures where *out takes the batch's.
+// An item of a feed may take its weights from its actor's clip (feed->item_weight_row): it has a morph stage without host weights.
+// Its row for clip_weights_kernel travels behind the actors' rows in the one upload, the kernel runs between the clip kernel and
+// the posing kernel and writes the item's active list into a slot of n_targets entries and its count into the uploaded item row,
+// and one more check word per such item brings the count back. In a call where no item has host weights the active arrays lie
+// behind everything else in the staging block, outside the upload, so the upload does not grow with the targets; where some
+// have, the slots follow the host's lists inside the arrays. A call without such an item is laid out and launched as ever.
 int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream, bool batch, SrPoseBatchInfo* out, ActorFeed* feed = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     const std::string who = feed ? "pose_actors" : batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
@@ -1139,6 +1155,10 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     // an item's skin stage: its matrices come from the caller's host pointer, or from the slice the clip kernel writes
     const auto fed = [feed](uint32_t i) { return feed && feed->item_matrix[i] != 0xFFFFFFFFu; };
     const auto skin_stage = [items, &fed](uint32_t i) { return items[i].joint_matrices != nullptr || fed(i); };
+    const auto clip_weighted = [feed](uint32_t i) { return feed && feed->item_weight_row[i] != 0xFFFFFFFFu; };
+    const auto morph_stage = [items, &clip_weighted](uint32_t i) { return items[i].weights != nullptr || clip_weighted(i); };
+    const uint32_t n_weight_items = feed ? (uint32_t)feed->weight_rows.size() : 0;
+    uint64_t n_slots = 0;                                     // entries of the clip-weighted items' slots
     std::vector<uint32_t> slots(n_items), counts(n_items), n_active(n_items), active_index, active;
     std::vector<float> active_weight;
     std::map<uint64_t, uint32_t> seen;
@@ -1146,9 +1166,11 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     int rc;
     for (uint32_t i = 0; i < n_items; i++) {
         const SrPoseItem& it = items[i];
-        if (!it.weights && !skin_stage(i)) return fail(SR_ERR_INVALID_ARG, prefix(i) + "pose_mesh: neither weights nor joint matrices given (one stage at least)");
-        rc = check_pose_args(s, it.key, it.weights, it.n_targets, skin_stage(i), it.n_joints, it.weights ? "pose_mesh" : "skin_mesh", &slots[i], active, &n_active[i]);
+        if (!morph_stage(i) && !skin_stage(i)) return fail(SR_ERR_INVALID_ARG, prefix(i) + "pose_mesh: neither weights nor joint matrices given (one stage at least)");
+        rc = check_pose_args(s, it.key, it.weights, it.n_targets, skin_stage(i), it.n_joints, morph_stage(i) ? "pose_mesh" : "skin_mesh", &slots[i], active, &n_active[i],
+                             clip_weighted(i) ? &feed->item_clip_targets[i] : nullptr);
         if (rc != SR_OK) return fail(rc, prefix(i) + g_last_error);
+        if (clip_weighted(i)) n_slots += feed->item_clip_targets[i];
         const auto first = seen.emplace(it.key, i);
         if (!first.second) return fail(SR_ERR_INVALID_ARG, prefix(i) + "the key is named twice in the batch (first by item " + std::to_string(first.first->second) + ")");
         counts[i] = s->meshes[slots[i]].n_vertices;
@@ -1156,22 +1178,30 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         for (uint32_t a = 0; a < n_active[i]; a++) { float w; memcpy(&w, &active[(size_t)it.n_targets + a], 4); active_weight.push_back(w); }
         if (it.joint_matrices) n_matrices += it.n_joints;
     }
-    if (n_matrices >= (1ull << 32) || active_index.size() >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_meshes: the batch holds 2^32 joint matrices or active targets or more");
+    if (n_matrices >= (1ull << 32) || active_index.size() + n_slots >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_meshes: the batch holds 2^32 joint matrices or active targets or more");
     std::vector<uint32_t> first_block(n_items);
     std::vector<uint64_t> vertex_base(n_items);
     uint32_t n_blocks = 0;
     if ((rc = sr_pose_batch_plan(counts.data(), n_items, first_block.data(), vertex_base.data(), &n_blocks)) != SR_OK) return rc;
     const uint64_t n_vertices = n_items ? vertex_base[n_items - 1] + counts[n_items - 1] : 0;
-    const srh::PoseBatchLayout lay = srh::pose_batch_layout(n_items, n_blocks, n_matrices, active_index.size());
+    const size_t n_host_active = active_index.size();
+    const bool slots_outside = n_weight_items && n_host_active == 0;      // the active arrays are the slots alone: behind the staging block's other parts
+    srh::PoseBatchLayout lay = srh::pose_batch_layout(n_items, n_blocks, n_matrices, slots_outside ? 0 : n_host_active + n_slots);
     // Actors add their rows and their instance rows behind the batch's parts: that is the upload. The matrices the clip kernel
     // writes follow it, outside the uploaded bytes, a whole number of matrices from lay.matrices so that matrix_base reaches them.
     const uint32_t n_actors = feed ? feed->n_actors : 0;
-    const size_t actor_rows_at = lay.bytes, inst_rows_at = actor_rows_at + sizeof(srd::ClipActorRow) * (size_t)n_actors;
+    const size_t actor_rows_at = lay.bytes, weight_rows_at = actor_rows_at + sizeof(srd::ClipActorRow) * (size_t)n_actors;
+    const size_t inst_rows_at = weight_rows_at + sizeof(srd::ClipWeightRow) * (size_t)n_weight_items;
     const size_t upload_bytes = inst_rows_at + ((4 * (feed ? feed->instance_rows.size() : 0) + 15u) & ~(size_t)15u);
     const uint64_t fed_first = (upload_bytes - lay.matrices + sizeof(SrTransform) - 1) / sizeof(SrTransform);
-    const size_t stage_bytes = feed ? lay.matrices + sizeof(SrTransform) * (size_t)(fed_first + feed->n_matrices) : lay.bytes;
+    size_t stage_bytes = feed ? lay.matrices + sizeof(SrTransform) * (size_t)(fed_first + feed->n_matrices) : lay.bytes;
     if (feed && fed_first + feed->n_matrices >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_actors: the call holds 2^32 joint matrices or more");
-    const size_t n_check = 2 * (size_t)n_items + n_actors;
+    if (slots_outside) {
+        const size_t slot_bytes = (4 * (size_t)n_slots + 15u) & ~(size_t)15u;
+        lay.active_index = (stage_bytes + 15u) & ~(size_t)15u; lay.active_weight = lay.active_index + slot_bytes;
+        stage_bytes = lay.active_weight + slot_bytes;
+    }
+    const size_t n_check = 2 * (size_t)n_items + n_actors + n_weight_items;
     if ((rc = bind_device(s)) != SR_OK) return rc;
     if ((rc = s->d_pose_stage.reserve(stage_bytes)) != SR_OK || (rc = s->d_pose_check.reserve(4 * n_check)) != SR_OK ||
         (rc = s->d_pose_scratch.reserve(sizeof(SrVertex) * (size_t)n_vertices)) != SR_OK) return rc;
@@ -1186,18 +1216,25 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         const SrPoseItem& it = items[i];
         const SrScene::MeshState& ms = s->mesh_state[slots[i]];
         srd::PoseBatchItem& row = rows[i];
-        row.src = it.weights ? ms.morph.d_base.p : ms.skin.d_bind.p;
-        row.deltas = it.weights ? ms.morph.d_deltas.p : nullptr;
+        row.src = morph_stage(i) ? ms.morph.d_base.p : ms.skin.d_bind.p;
+        row.deltas = morph_stage(i) ? ms.morph.d_deltas.p : nullptr;
         row.influences = skin_stage(i) ? ms.skin.d_influences.p : nullptr;
         row.dst = s->meshes[slots[i]].d_vertices;
         row.vertex_base = vertex_base[i];
         row.n_vertices = counts[i]; row.first_block = first_block[i];
         row.n_active = n_active[i]; row.active_base = active_base;
         row.matrix_base = fed(i) ? (uint32_t)fed_first + feed->item_matrix[i] : matrix_base;
-        row.stages = (it.weights ? srd::kPoseMorph : 0u) | (skin_stage(i) ? srd::kPoseSkin : 0u);
+        row.stages = (morph_stage(i) ? srd::kPoseMorph : 0u) | (skin_stage(i) ? srd::kPoseSkin : 0u);
         if (it.joint_matrices) { memcpy(stage.data() + lay.matrices + sizeof(SrTransform) * (size_t)matrix_base, it.joint_matrices, sizeof(SrTransform) * (size_t)it.n_joints); matrix_base += it.n_joints; }
         active_base += n_active[i];
-        (row.stages == 3u ? info.fused : it.weights ? info.morph_only : info.skin_only)++;
+        (row.stages == 3u ? info.fused : morph_stage(i) ? info.morph_only : info.skin_only)++;
+    }
+    for (uint32_t i = 0; i < n_items; i++) {                  // the slots follow the host's lists; the kernel writes n_active (0 until then)
+        if (!clip_weighted(i)) continue;
+        srd::ClipWeightRow& wr = feed->weight_rows[feed->item_weight_row[i]];
+        wr.item = i; wr.active_base = active_base; wr.check_word = (uint32_t)(2 * (size_t)n_items + n_actors + feed->item_weight_row[i]);
+        rows[i].active_base = active_base;
+        active_base += feed->item_clip_targets[i];
     }
     srh::pose_batch_block_table(first_block.data(), n_items, n_blocks, (uint32_t*)(stage.data() + lay.block_table));
     if (!active_index.empty()) {
@@ -1213,6 +1250,7 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     if (feed) {
         for (uint32_t a = 0; a < n_actors; a++) feed->rows[a].matrix_base += (uint32_t)fed_first;
         memcpy(stage.data() + actor_rows_at, feed->rows.data(), sizeof(srd::ClipActorRow) * (size_t)n_actors);
+        if (n_weight_items) memcpy(stage.data() + weight_rows_at, feed->weight_rows.data(), sizeof(srd::ClipWeightRow) * (size_t)n_weight_items);
         if (!feed->instance_rows.empty()) memcpy(stage.data() + inst_rows_at, feed->instance_rows.data(), 4 * feed->instance_rows.size());
     }
     s->actor_stage_current = false;                          // the block changes hands
@@ -1224,7 +1262,11 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
                                       (SrTransform*)(s->d_pose_stage.p ? (unsigned char*)s->d_pose_stage.p + lay.matrices : nullptr), feed->d_instance_transforms,
                                       (uint32_t*)s->d_pose_check.p + 2 * (size_t)n_items, keep_nodes ? (SrNodeTrs*)s->d_actor_trs.p : nullptr,
                                       keep_nodes ? (float*)s->d_actor_globals.p : nullptr, st);
-        clip_timer.end(st);
+        if (e == 0 && n_weight_items)
+            e = srk_clip_weights((const srd::ClipWeightRow*)(d_stage + weight_rows_at), n_weight_items, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
+                                 (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
+                                 (uint32_t*)s->d_pose_check.p, st);
+        clip_timer.end(st);                                   // both clip kernels
     }
     pose_timer.begin(st);
     if (e == 0) e = srk_pose_batch(d_rows, d_table, n_blocks, (const SrTransform*)(d_stage + lay.matrices), (const uint32_t*)(d_stage + lay.active_index),
@@ -1239,9 +1281,16 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         s->actor_records.clear();
         for (uint32_t a = 0; a < n_actors; a++)
             s->actor_records.push_back(SrScene::ActorRecord{lay.matrices + sizeof(SrTransform) * (uint64_t)feed->rows[a].matrix_base, feed->actor_joints[a], feed->rows[a].node_base, feed->actor_nodes[a]});
+        s->item_active_records.clear();
+        for (uint32_t i = 0; i < n_items; i++) {
+            n_active[i] = clip_weighted(i) ? std::min(bad[2 * (size_t)n_items + n_actors + feed->item_weight_row[i]], feed->item_clip_targets[i]) : n_active[i];   // the count that came back
+            s->item_active_records.push_back(SrScene::ItemActiveRecord{lay.items + sizeof(srd::PoseBatchItem) * (uint64_t)i, lay.active_index + 4 * (uint64_t)rows[i].active_base,
+                                                                       lay.active_weight + 4 * (uint64_t)rows[i].active_base,
+                                                                       clip_weighted(i) ? feed->item_clip_targets[i] : morph_stage(i) ? n_active[i] : 0u});
+        }
         s->actor_stage_current = true; s->actor_nodes_kept = keep_nodes;
         SrActorPoseInfo& ai = *feed->info;
-        ai = SrActorPoseInfo{n_actors, n_items, feed->n_nodes, feed->n_channels, upload_bytes, 2, 1, ai.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, clip_timer.ms(), info.pose_ms, 0.0, 0.0};
+        ai = SrActorPoseInfo{n_actors, n_items, feed->n_nodes, feed->n_channels, upload_bytes, n_weight_items ? 3u : 2u, 1, ai.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, n_weight_items, clip_timer.ms(), info.pose_ms, 0.0, 0.0};
         for (uint32_t a = 0; a < n_actors && ai.refused_actor == 0xFFFFFFFFu; a++) if (bad[2 * (size_t)n_items + a] != 0xFFFFFFFFu) ai.refused_actor = a;
         if (ai.refused_actor != 0xFFFFFFFFu) {                // a singular mesh-node transform: nothing has changed but the scratch
             s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();
@@ -1286,14 +1335,14 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         if ((rc = device_vertices_taken(s, slot, info.scatter_ms)) != SR_OK) return rc;
         s->meshes[slot].check_ms = 0.0;
         mesh_vertices_changed(s, slot);
-        if (items[i].weights) { ms.morph.first_bad = 0xFFFFFFFFu; ms.morph.n_active = n_active[i]; ms.morph.morph_ms = info.pose_ms; ms.morph.posed++; }
-        if (skin_stage(i)) { ms.skin.first_bad = 0xFFFFFFFFu; ms.skin.skin_ms = items[i].weights ? 0.0 : info.pose_ms; ms.skin.skinned++; }
+        if (morph_stage(i)) { ms.morph.first_bad = 0xFFFFFFFFu; ms.morph.n_active = n_active[i]; ms.morph.morph_ms = info.pose_ms; ms.morph.posed++; }
+        if (skin_stage(i)) { ms.skin.first_bad = 0xFFFFFFFFu; ms.skin.skin_ms = morph_stage(i) ? 0.0 : info.pose_ms; ms.skin.skinned++; }
         s->pose_batch_keys.push_back(items[i].key); s->pose_batch_vertex_base.push_back(vertex_base[i]);
     }
     note_update_times(s, t0, t1, t2);
     info.host_ms = ms_between(t0, std::chrono::steady_clock::now());
     *out = info;
-    if (feed) { feed->info->launches = 3; feed->info->scatter_ms = info.scatter_ms; feed->info->host_ms = info.host_ms; }
+    if (feed) { feed->info->launches = n_weight_items ? 4 : 3; feed->info->scatter_ms = info.scatter_ms; feed->info->host_ms = info.host_ms; }
     return SR_OK;
 }
 
@@ -1355,7 +1404,9 @@ int sr_scene_detach_clip(SrScene* s, uint32_t clip_id) {
 }
 
 // sr_scene_pose_meshes with the joint matrices named rather than given: the actors and what they name are checked here, on the
-// host; the rest is pose_items, which takes an actor-driven item's matrices from the slice clip_pose_kernel writes.
+// host; the rest is pose_items, which takes an actor-driven item's matrices from the slice clip_pose_kernel writes. An item may
+// name a morph set of its actor's clip as well (SR_ACTOR_CLIP_WEIGHTS): the set is looked up and checked here, and pose_items has
+// clip_weights_kernel write the item's active list on the device.
 int sr_scene_pose_actors(SrScene* s, const SrClipActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items, SrTransform* d_instance_transforms,
                          uint32_t flags, void* stream) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "pose_actors: null argument (the scene)");
@@ -1394,12 +1445,27 @@ int sr_scene_pose_actors(SrScene* s, const SrClipActor* actors, uint32_t n_actor
     }
     std::vector<SrPoseItem> pose(n_items);
     feed.item_matrix.assign(n_items, 0xFFFFFFFFu);
+    feed.item_weight_row.assign(n_items, 0xFFFFFFFFu); feed.item_clip_targets.assign(n_items, 0u);
     for (uint32_t i = 0; i < n_items; i++) {
         const SrActorPoseItem& it = items[i];
         const auto prefix = [i]() { return "pose_actors: item " + std::to_string(i) + ": "; };
         pose[i] = SrPoseItem{it.key, it.weights, nullptr, it.n_targets, 0};
-        if (it.skin == SR_ACTOR_NO_SKIN) continue;
+        if (it.morph && it.weights) return fail(SR_ERR_INVALID_ARG, prefix() + "host weights given together with SR_ACTOR_CLIP_WEIGHTS (one source of weights at most)");
+        if (it.skin == SR_ACTOR_NO_SKIN && !it.morph) continue;
         if (it.actor >= n_actors) return fail(SR_ERR_INVALID_ARG, prefix() + "actor " + std::to_string(it.actor) + " named, the call has " + std::to_string(n_actors) + " actors");
+        if (it.morph) {                                          // the weights of a morph set of the actor's clip, at the actor's time
+            const SrClip& clip = clip_of[it.actor]->host;
+            const uint32_t blas = it.morph - 1;
+            const int k = clip.find_morph_set(blas);
+            if (k < 0) return fail(SR_ERR_INVALID_ARG, prefix() + "the weights of blas " + std::to_string(blas) + " named, the actor's clip has no morph set for it");
+            const srd::ClipMorphSet& set = clip.morph_sets()[k];
+            if (set.state == srd::kClipMorphUnavailable) return fail((int32_t)set.status, prefix() + clip.morph_errors[k]);
+            srd::ClipWeightRow row{};
+            row.clip = clip_of[it.actor]->d_block.p; row.time_seconds = actors[it.actor].time_seconds; row.set = (uint32_t)k;
+            feed.item_weight_row[i] = (uint32_t)feed.weight_rows.size(); feed.item_clip_targets[i] = set.n_targets;
+            feed.weight_rows.push_back(row);
+        }
+        if (it.skin == SR_ACTOR_NO_SKIN) continue;
         uint32_t first = 0, n_joints = 0;
         if (sr_clip_skin(&clip_of[it.actor]->host, it.skin, &first, &n_joints) != SR_OK) return fail(SR_ERR_INVALID_ARG, prefix() + "skin " + std::to_string(it.skin) + " named, no instanced mesh of the actor's clip wears it");
         pose[i].n_joints = n_joints;
@@ -1437,6 +1503,24 @@ int sr_scene_read_actor_matrices(const SrScene* s, uint32_t actor, SrTransform* 
     if (rc != SR_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     if (r.n_joints) HIP_TRY(hipMemcpy(joint_matrices, (const unsigned char*)s->d_pose_stage.p + r.matrix_byte, sizeof(SrTransform) * (size_t)r.n_joints, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_scene_read_item_active(const SrScene* s, uint32_t item, uint32_t* index_out, float* weight_out, uint32_t* n_active) {
+    if (!s || !n_active) return fail(SR_ERR_INVALID_ARG, "read_item_active: null argument");
+    if (!s->actor_stage_current) return fail(SR_ERR_STATE, "read_item_active: the staging block does not hold a sr_scene_pose_actors call");
+    if (item >= s->item_active_records.size()) return fail(SR_ERR_INVALID_ARG, "read_item_active: item index out of range");
+    const SrScene::ItemActiveRecord& r = s->item_active_records[item];
+    const int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    const unsigned char* stage = (const unsigned char*)s->d_pose_stage.p;
+    srd::PoseBatchItem row;
+    HIP_TRY(hipMemcpy(&row, stage + r.row_byte, sizeof(row), hipMemcpyDeviceToHost));
+    const uint32_t n = (row.stages & srd::kPoseMorph) ? std::min(row.n_active, r.capacity) : 0u;      // never past the item's slice
+    if (index_out && n) HIP_TRY(hipMemcpy(index_out, stage + r.index_byte, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    if (weight_out && n) HIP_TRY(hipMemcpy(weight_out, stage + r.weight_byte, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    *n_active = n;
     return SR_OK;
 }
 

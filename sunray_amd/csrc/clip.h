@@ -29,6 +29,21 @@ struct SrClip {
     const uint32_t* instances() const { return table<uint32_t>(header().instances); }
     const float* times() const { return table<float>(header().times); }
     const float* values() const { return table<float>(header().values); }
+
+    // the morph sets (the second header, at ClipHeader.reserved; none where that is 0) and, host only, the loader's words for
+    // every unavailable set, by position
+    std::vector<std::string> morph_errors;
+    uint32_t n_morph_sets() const { return header().reserved ? morph_header().n_sets : 0u; }
+    const srd::ClipMorphHeader& morph_header() const { return *table<srd::ClipMorphHeader>(header().reserved); }
+    const srd::ClipMorphSet* morph_sets() const { return table<srd::ClipMorphSet>(morph_header().sets); }
+    const float* morph_times() const { return table<float>(morph_header().times); }
+    const float* morph_values() const { return table<float>(morph_header().values); }
+    const float* morph_defaults() const { return table<float>(morph_header().defaults); }
+    // the set of a blas -> its position, or -1
+    int find_morph_set(uint32_t blas) const {
+        for (uint32_t k = 0; k < n_morph_sets(); k++) if (morph_sets()[k].blas == blas) return (int)k;
+        return -1;
+    }
 };
 
 namespace srh {
@@ -44,6 +59,9 @@ struct ClipParts {
     std::vector<srd::ClipSkin> skins;
     std::vector<uint32_t> joint_nodes, joint_skins, instances;
     std::vector<SrTransform> inverse_bind;
+    std::vector<srd::ClipMorphSet> morph_sets;      // first_time / first_value / first_default index the three tables below
+    std::vector<float> morph_times, morph_values, morph_defaults;
+    std::vector<std::string> morph_errors;          // one per set; empty where the set is available
 };
 
 // One block from the parts: the header, then every table at a 16-byte boundary. Inline: the loader (gltf_load.cpp) links alone.
@@ -62,6 +80,15 @@ inline void clip_assemble(const ClipParts& p, SrClip& clip) {
     h.nodes = clip_place(bytes, p.nodes); h.levels = clip_place(bytes, p.levels); h.channels = clip_place(bytes, p.channels); h.skins = clip_place(bytes, p.skins);
     h.joint_nodes = clip_place(bytes, p.joint_nodes); h.joint_skins = clip_place(bytes, p.joint_skins); h.inverse_bind = clip_place(bytes, p.inverse_bind);
     h.instances = clip_place(bytes, p.instances); h.times = clip_place(bytes, p.times); h.values = clip_place(bytes, p.values);
+    if (!p.morph_sets.empty()) {                    // a clip without morph sets is the block it has always been
+        srd::ClipMorphHeader m{};
+        m.n_sets = (uint32_t)p.morph_sets.size(); m.n_times = (uint32_t)p.morph_times.size(); m.n_values = (uint32_t)p.morph_values.size(); m.n_defaults = (uint32_t)p.morph_defaults.size();
+        h.reserved = (uint32_t)bytes.size();
+        bytes.resize(bytes.size() + sizeof(m), 0);
+        m.sets = clip_place(bytes, p.morph_sets); m.times = clip_place(bytes, p.morph_times); m.values = clip_place(bytes, p.morph_values); m.defaults = clip_place(bytes, p.morph_defaults);
+        memcpy(bytes.data() + h.reserved, &m, sizeof(m));
+    }
+    clip.morph_errors = p.morph_errors;
     h.bytes = (uint32_t)bytes.size();
     memcpy(bytes.data(), &h, sizeof(h));
     clip.block.assign(bytes.size() / 4, 0u);

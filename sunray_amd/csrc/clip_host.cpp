@@ -46,6 +46,56 @@ int sr_clip_channel_keys(const SrClip* clip, uint32_t channel, const float** tim
     return SR_OK;
 }
 
+int sr_clip_morph_count(const SrClip* clip, uint32_t* n_sets) {
+    if (!clip || !n_sets) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_morph_count: null argument");
+    *n_sets = clip->n_morph_sets();
+    return SR_OK;
+}
+
+int sr_clip_morph(const SrClip* clip, uint32_t blas, SrClipMorphInfo* out) {
+    if (!clip || !out) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_morph: null argument");
+    const int k = clip->find_morph_set(blas);
+    if (k < 0) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_morph: the clip has no morph set for this blas (it has no morph targets)");
+    const srd::ClipMorphSet& s = clip->morph_sets()[k];
+    const bool unavailable = s.state == srd::kClipMorphUnavailable;
+    *out = SrClipMorphInfo{s.blas, s.gltf_node, s.n_targets, s.n_keys, s.interpolation,
+                           unavailable ? SR_CLIP_MORPH_UNAVAILABLE : s.n_keys ? SR_CLIP_MORPH_CHANNEL : SR_CLIP_MORPH_DEFAULTS, unavailable ? (int32_t)s.status : SR_OK, 0};
+    if (unavailable) srh::set_error((int32_t)s.status, clip->morph_errors[k]);      // the words, for whoever asks; the call itself succeeds
+    return SR_OK;
+}
+
+int sr_clip_morph_keys(const SrClip* clip, uint32_t blas, const float** times, const float** values, const float** default_weights) {
+    if (!clip) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_morph_keys: null argument");
+    const int k = clip->find_morph_set(blas);
+    if (k < 0) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_morph_keys: the clip has no morph set for this blas (it has no morph targets)");
+    const srd::ClipMorphSet& s = clip->morph_sets()[k];
+    if (s.state == srd::kClipMorphUnavailable) return srh::set_error((int32_t)s.status, "sr_clip_morph_keys: " + clip->morph_errors[k]);
+    if (times) *times = s.n_keys ? clip->morph_times() + s.first_time : nullptr;
+    if (values) *values = s.n_keys ? clip->morph_values() + s.first_value : nullptr;
+    if (default_weights) *default_weights = clip->morph_defaults() + s.first_default;
+    return SR_OK;
+}
+
+// sr_gltf_morph_weights restated over the baked set: its checks in its order, its statuses and its words.
+int sr_clip_weights_host(const SrClip* clip, float time_seconds, uint32_t blas, float* weights_out, uint32_t n_targets) {
+    if (!clip || (!weights_out && n_targets)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_host: null argument");
+    const int k = clip->find_morph_set(blas);
+    if (k < 0) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_host: the clip has no morph set for this blas (it has no morph targets)");
+    const srd::ClipMorphSet& s = clip->morph_sets()[k];
+    const bool unavailable = s.state == srd::kClipMorphUnavailable;
+    if (unavailable && s.n_targets == 0) return srh::set_error((int32_t)s.status, "sr_clip_weights_host: " + clip->morph_errors[k]);    // the morph parse itself
+    if (n_targets != s.n_targets) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_host: gltf: another number of weights asked for than the blas has morph targets");
+    if (clip->animation >= 0 && !std::isfinite(time_seconds)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_host: gltf: the time of a pose must be finite");
+    if (unavailable) return srh::set_error((int32_t)s.status, "sr_clip_weights_host: " + clip->morph_errors[k]);
+    if (s.n_keys == 0) { memcpy(weights_out, clip->morph_defaults() + s.first_default, 4 * (size_t)n_targets); return SR_OK; }
+    uint32_t i = 0;
+    double u = 0.0;
+    srd::clip_key_search(clip->morph_times() + s.first_time, s.n_keys, s.interpolation, (double)time_seconds, &i, &u);
+    const float* values = clip->morph_values() + s.first_value;
+    for (uint32_t t = 0; t < n_targets; t++) weights_out[t] = srd::clip_weight_at(values, n_targets, i, u, t);
+    return SR_OK;
+}
+
 int sr_clip_sample_host(const SrClip* clip, float time_seconds, SrNodeTrs* out) {
     if (!clip || !out) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_sample_host: null argument");
     if (clip->animation >= 0 && !std::isfinite(time_seconds)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_sample_host: gltf: the time of a pose must be finite");

@@ -53,6 +53,58 @@ struct ClipActorRow {
 };
 static_assert(sizeof(ClipActorRow) == 80, "five 16-byte pieces");
 
+// The morph sets of a clip: a second header at ClipHeader.reserved (0: the clip has no set) and its tables, in the same block.
+// A set is what morph_weights (gltf_load.cpp) derives for one blas with morph targets, flattened.
+constexpr uint32_t kClipMorphAvailable = 0, kClipMorphUnavailable = 1;
+struct ClipMorphHeader {
+    uint32_t n_sets, n_times, n_values, n_defaults;
+    uint32_t sets, times, values, defaults;             // ClipMorphSet[n_sets]; float[n_times]; float[n_values]; float[n_defaults]
+};
+static_assert(sizeof(ClipMorphHeader) == 32, "two 16-byte pieces");
+struct ClipMorphSet {
+    uint32_t blas, gltf_node, n_targets, n_keys;        // n_keys 0: no `weights` channel on the node, the defaults
+    uint32_t interpolation, first_time, first_value, first_default;   // n_keys times; n_keys x n_targets values, key-major; n_targets defaults
+    uint32_t state, status, reserved[2];                // kClipMorphUnavailable: the loader refused the set with `status`; never sampled
+};
+static_assert(sizeof(ClipMorphSet) == 48, "three 16-byte pieces");
+
+// One clip-weighted item of a call as clip_weights_kernel reads it, at wave-uniform addresses.
+struct ClipWeightRow {
+    const void* clip;           // device: the clip's block
+    float time_seconds;
+    uint32_t set;               // position in the clip's morph sets
+    uint32_t active_base;       // the item's slot of n_targets entries in the active arrays
+    uint32_t item;              // its PoseBatchItem, whose n_active the kernel writes
+    uint32_t check_word;        // the word of the check area that takes the count as well
+    uint32_t reserved;
+};
+static_assert(sizeof(ClipWeightRow) == 32, "two 16-byte pieces");
+
+// The key search of sample_channel / morph_weights: the key `i` at or before `time` (clamped to the first / last key) and the
+// fraction `u` towards key i + 1 (0: take key i as it is).
+SR_CLIP_HD void clip_key_search(const float* times, uint32_t n, uint32_t interpolation, double time, uint32_t* key, double* fraction) {
+    uint32_t i = 0;
+    double u = 0.0;
+    if (time <= (double)times[0]) i = 0;
+    else if (time >= (double)times[n - 1]) i = n - 1;
+    else {
+        uint32_t lo = 0, hi = n - 1;                                              // times[lo] <= time < times[hi]
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if ((double)times[mid] <= time) lo = mid; else hi = mid; }
+        i = lo;
+        if (interpolation == kClipLinear) u = (time - (double)times[i]) / ((double)times[i + 1] - (double)times[i]);
+    }
+    *key = i; *fraction = u;
+}
+// One weight of morph_weights from its two keys: in double from the fp32 keys, rounded once.
+SR_CLIP_HD float clip_weight(float key_a, float key_b, double u) {
+    const double a = key_a, b = key_b;
+    return (float)(u > 0.0 ? a + u * (b - a) : a);
+}
+// Target k of a set at key i and fraction u; `values` is the set's own slice.
+SR_CLIP_HD float clip_weight_at(const float* values, uint32_t n_targets, uint32_t i, double u, uint32_t k) {
+    return clip_weight(values[(size_t)i * n_targets + k], values[(size_t)(u > 0.0 ? i + 1 : i) * n_targets + k], u);
+}
+
 // sample_channel: one channel at `time` (clamped to the first / last key), in double from the fp32 keys, rounded once.
 // COMPS 3: translation / scale. COMPS 4: a rotation, slerp along the shorter arc between the normalised keys, normalised.
 SR_CLIP_HD void clip_normalise(double* q) {

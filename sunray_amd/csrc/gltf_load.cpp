@@ -1179,9 +1179,79 @@ struct GltfLoader {
                 p.inverse_bind.push_back(sd->inverse_bind[j]);
             }
         }
+        bake_morph_sets(anim, p);
         clip.animation = (int32_t)anim;
         srh::clip_assemble(p, clip);
         return true;
+    }
+
+    // The `weights` channel of a blas's node in animation `anim`, as morph_weights finds and validates it (the first one, the same
+    // checks in the same order, the same words), without sampling it: n_keys 0 where the node has no such channel. false: refused.
+    bool bake_morph_channel(long anim, const BlasMorph& bm, srd::ClipMorphSet& set, std::vector<float>& times, std::vector<float>& values) {
+        const Json* an = element("animations", anim);
+        if (!an) return fail("animation index out of range");
+        const Json* chans = an->get("channels");
+        const Json* samps = an->get("samplers");
+        for (size_t c = 0; chans && c < chans->size(); c++) {
+            const Json* target = chans->arr[c].get("target");
+            const Json* path = target ? target->get("path") : nullptr;
+            if (!target || !path || path->kind != Json::Str || path->str != "weights" || !target->has("node") || target->index("node") != bm.node) continue;
+            const long si = chans->arr[c].index("sampler");
+            if (!samps || si < 0 || (size_t)si >= samps->size()) return fail("animation channel refers to a missing sampler");
+            const Json& smp = samps->arr[si];
+            const Json* ip = smp.get("interpolation");
+            const std::string mode = ip && ip->kind == Json::Str ? ip->str : "LINEAR";
+            if (mode == "CUBICSPLINE") return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED);
+            if (mode != "LINEAR" && mode != "STEP") return fail("animation sampler with an unknown interpolation '" + mode + "'");
+            const Json* ia = element("accessors", smp.index("input"));
+            if (!ia || (int)ia->number("componentType", 0) != 5126) return fail("animation sampler input must be a float SCALAR accessor");
+            size_t nt = 0, nv = 0;
+            if (!read_floats(smp.index("input"), 1, times, &nt)) return false;
+            if (nt == 0) return fail("animation sampler without keys");
+            for (size_t t = 0; t < nt; t++)
+                if (!std::isfinite(times[t]) || times[t] < 0.0f || (t && !(times[t] > times[t - 1]))) return fail("animation key times must be finite, not negative and strictly increasing");
+            const Json* oa = element("accessors", smp.index("output"));
+            if (!oa || (int)oa->number("componentType", 0) != 5126) return fail("animation sampler output of a weights channel must be a float SCALAR accessor");
+            if (!read_floats(smp.index("output"), 1, values, &nv)) return false;
+            if (nv < nt * (size_t)bm.n_targets) return fail("animation sampler output holds fewer values than its input has keys times the morph targets");
+            for (size_t v = 0; v < nt * (size_t)bm.n_targets; v++)
+                if (!std::isfinite(values[v])) return fail("animation sampler output holds a non-finite value");
+            if (nt * (size_t)bm.n_targets >= (1ull << 31)) return fail("a weights channel of 2^31 values or more is not supported in a baked clip", SR_ERR_UNSUPPORTED);
+            times.resize(nt); values.resize(nt * (size_t)bm.n_targets);
+            set.n_keys = (uint32_t)nt;
+            set.interpolation = mode == "STEP" ? srd::kClipStep : srd::kClipLinear;
+            return true;
+        }
+        return true;
+    }
+
+    // One morph set for every blas of the file that has morph targets: what morph_weights(anim, t, blas) derives from the document,
+    // once. A set morph_weights would refuse (the morph parse of the blas, or the channel) is kept as unavailable, with the status
+    // and the words; it does not refuse the bake.
+    void bake_morph_sets(long anim, srh::ClipParts& p) {
+        for (uint32_t blas = 0; blas < out.blases.size(); blas++) {
+            err.clear(); err_code = SR_ERR_INVALID_ARG;
+            srd::ClipMorphSet set{};
+            set.blas = blas; set.gltf_node = srd::kClipNoNode;
+            const BlasMorph* bm = blas_morph(blas);
+            if (bm && bm->n_targets == 0) continue;
+            std::vector<float> times, values;
+            if (bm) {
+                set.gltf_node = (uint32_t)bm->node; set.n_targets = bm->n_targets;
+                set.first_default = (uint32_t)p.morph_defaults.size();
+                p.morph_defaults.insert(p.morph_defaults.end(), bm->default_weights.begin(), bm->default_weights.end());
+                if (anim >= 0) bake_morph_channel(anim, *bm, set, times, values);
+            }
+            if (!err.empty()) { set.state = srd::kClipMorphUnavailable; set.status = (uint32_t)err_code; set.n_keys = 0; }
+            else if (set.n_keys) {
+                set.first_time = (uint32_t)p.morph_times.size(); set.first_value = (uint32_t)p.morph_values.size();
+                p.morph_times.insert(p.morph_times.end(), times.begin(), times.end());
+                p.morph_values.insert(p.morph_values.end(), values.begin(), values.end());
+            }
+            p.morph_sets.push_back(set);
+            p.morph_errors.push_back(err);
+        }
+        err.clear(); err_code = SR_ERR_INVALID_ARG;
     }
 
     bool build() {

@@ -190,11 +190,22 @@ def _pose_items(items):
     return rows, C.c_uint32(len(items)), keep
 
 
+class ClipWeights:
+    """The fourth element of a pose_actors item whose morph weights come from its actor's clip, evaluated on the GPU: morph set
+    `blas` of that clip at the actor's time (SR_ACTOR_CLIP_WEIGHTS)."""
+
+    def __init__(self, blas):
+        self.blas = int(blas)
+        if self.blas < 0:
+            raise ValueError("ClipWeights: the blas is an index")
+
+
 class ActorArgs:
     """The arguments of pose_actors packed once (abi.SrClipActor / abi.SrActorPoseItem arrays and the numpy arrays they point
     into): `actors` is a sequence of (clip id, time in seconds, placement [12] float32 or None, instance rows uint32 or None,
-    instance base), `items` one of (key, actor index, skin index or None, weights or None). set_times() rewrites the times in
-    place, so a crowd's per-frame work on the host is that and the call."""
+    instance base), `items` one of (key, actor index, skin index or None, weights or ClipWeights(blas) or None; the actor index
+    may be None where neither a skin nor ClipWeights names it). set_times() rewrites the times in place, so a crowd's per-frame
+    work on the host is that and the call."""
 
     def __init__(self, actors, items):
         actors, items = [tuple(a) for a in actors], [tuple(i) for i in items]
@@ -221,8 +232,10 @@ class ActorArgs:
             if len(it) != 4:
                 raise ValueError("pose_actors: item %d: an item is (key, actor, skin, weights), %d values given" % (i, len(it)))
             row = self.items[i]
-            row.key, row.actor, row.skin = int(it[0]), int(it[1]), abi.ACTOR_NO_SKIN if it[2] is None else int(it[2])
-            if it[3] is not None:
+            row.key, row.actor, row.skin = int(it[0]), 0 if it[1] is None else int(it[1]), abi.ACTOR_NO_SKIN if it[2] is None else int(it[2])
+            if isinstance(it[3], ClipWeights):
+                row.morph = abi.actor_clip_weights(it[3].blas)
+            elif it[3] is not None:
                 try:
                     w, nt = _morph_weights(it[3])
                 except ValueError as e:
@@ -294,6 +307,38 @@ class Clip:
         check(lib().sr_clip_channel_keys(self._h, C.c_uint32(channel), C.byref(tp), C.byref(vp)))
         comps = 4 if c["path"] == 1 else 3
         return _np_from(tp, int(c["n_keys"]), np.float32), _np_from(vp, int(c["n_keys"]) * comps, np.float32).reshape(-1, comps)
+
+    def morph_count(self):
+        """-> the number of morph sets: one for every blas of the file that has morph targets (sr_clip_morph_count)."""
+        n = C.c_uint32()
+        check(lib().sr_clip_morph_count(self._h, C.byref(n)))
+        return n.value
+
+    def morph(self, blas):
+        """-> dict(blas, gltf_node, n_targets, n_keys, interpolation, state (abi.CLIP_MORPH_*), status, error) of the blas's morph
+        set; error: the loader's words where the set is unavailable, else None (sr_clip_morph)."""
+        info = abi.SrClipMorphInfo()
+        check(lib().sr_clip_morph(self._h, C.c_uint32(blas), C.byref(info)))
+        out = {name: getattr(info, name) for name, _ in abi.SrClipMorphInfo._fields_ if name != "reserved"}
+        out["error"] = lib().sr_last_error().decode("utf-8", "replace") if info.state == abi.CLIP_MORPH_UNAVAILABLE else None
+        return out
+
+    def morph_keys(self, blas):
+        """-> (key times [n_keys], values [n_keys, n_targets], default weights [n_targets]) of the blas's morph set, the file's
+        float32; without a channel the first two are empty (sr_clip_morph_keys)."""
+        m = self.morph(blas)
+        tp, vp, dp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sr_clip_morph_keys(self._h, C.c_uint32(blas), C.byref(tp), C.byref(vp), C.byref(dp)))
+        nk, nt = m["n_keys"], m["n_targets"]
+        return _np_from(tp, nk, np.float32), _np_from(vp, nk * nt, np.float32).reshape(nk, nt), _np_from(dp, nt, np.float32)
+
+    def weights_host(self, time_seconds, blas, n_targets=None):
+        """-> the weights [n_targets] float32 of the blas's morph set at `time_seconds`: sr_gltf_morph_weights restated over the
+        clip, bit for bit. n_targets: the set's own unless given (sr_clip_weights_host)."""
+        nt = self.morph(blas)["n_targets"] if n_targets is None else int(n_targets)
+        w = np.zeros(max(nt, 1), dtype=np.float32)
+        check(lib().sr_clip_weights_host(self._h, C.c_float(time_seconds), C.c_uint32(blas), _p(w), C.c_uint32(nt)))
+        return w[:nt]
 
     def sample_host(self, time_seconds):
         """-> abi.NODE_TRS [n_nodes]: every clip node's TRS at `time_seconds` (sr_clip_sample_host)."""
@@ -618,6 +663,13 @@ class Scene:
         trs, g = np.zeros(max(n_nodes, 1), abi.NODE_TRS), np.zeros((max(n_nodes, 1), 16), np.float32)
         check(lib().sr_scene_read_actor_nodes(self._h, C.c_uint32(actor), _p(trs), _p(g)))
         return trs[:n_nodes], g[:n_nodes]
+
+    def read_item_active(self, item, n_targets=65536):
+        """-> (target indices uint32 [n_active], weights float32 [n_active]): item `item`'s active list of the last pose_actors
+        as the posing kernel read it; n_targets: room for that many (sr_scene_read_item_active)."""
+        idx, w, n = np.zeros(max(n_targets, 1), np.uint32), np.zeros(max(n_targets, 1), np.float32), C.c_uint32()
+        check(lib().sr_scene_read_item_active(self._h, C.c_uint32(item), _p(idx), _p(w), C.byref(n)))
+        return idx[:n.value].copy(), w[:n.value].copy()
 
     def read_actor_matrices(self, actor, n_joints):
         """-> the joint matrices [n_joints, 12] float32 the posing kernel read for an actor of the last pose_actors
