@@ -413,6 +413,10 @@ int sr_scene_read_top_level(const SrScene* scene, uint32_t* nodes, uint32_t* tl_
 /* Node layout of the quantised wide BVH this build uses (csrc/bvh_layout.h): children per node, dwords per node, first
  * plane dword, first child dword. */
 int sr_bvh_layout(uint32_t* width, uint32_t* node_dwords, uint32_t* plane_offset, uint32_t* child_offset);
+/* What the device tree builders shape a tree of `n_prims` primitives of one SR_TREE_KIND_* by: primitives per leaf
+ * (csrc/bvh_layout.h) and the stack floor of the collapse before the build's cap bounds it (mesh: the host builder's depth for
+ * that size; top level: the median tree's depth; one level: the regular stack size). Either pointer may be NULL. */
+int sr_tree_build_limits(uint32_t kind, uint64_t n_prims, uint32_t* leaf_max, uint32_t* stack_floor);
 /* Debug read-back of the device tree: n_nodes x node_dwords dwords, n_triangles x 12 floats (either may be NULL). */
 int sr_scene_read_bvh(const SrScene* scene, uint32_t* nodes_out, float* tris_out);
 

@@ -3050,6 +3050,13 @@ int sr_bvh_layout(uint32_t* width, uint32_t* node_dwords, uint32_t* plane_offset
     return SR_OK;
 }
 
+int sr_tree_build_limits(uint32_t kind, uint64_t n_prims, uint32_t* leaf_max, uint32_t* stack_floor) {
+    if (kind > SR_TREE_KIND_MESH) return fail(SR_ERR_INVALID_ARG, "sr_tree_build_limits: kind must be SR_TREE_KIND_ONE_LEVEL, _TOP_LEVEL or _MESH");
+    if (leaf_max) *leaf_max = (uint32_t)srl::kLeafMax;
+    if (stack_floor) *stack_floor = kind == SR_TREE_KIND_MESH ? depth_for(n_prims) : kind == SR_TREE_KIND_TOP_LEVEL ? min_depth_for(n_prims) : (uint32_t)srd::kStackMax;
+    return SR_OK;
+}
+
 int sr_scene_read_bvh(const SrScene* s, uint32_t* nodes_out, float* tris_out) {
     if (!s || !s->built) return fail(SR_ERR_STATE, "sr_scene_read_bvh: scene not built");
     if (s->two_level) return fail(SR_ERR_UNSUPPORTED, "sr_scene_read_bvh: the scene is built in the two-level form");

@@ -84,8 +84,10 @@ struct VertPrims {
 };
 
 // Refit of one 4-wide node: child boxes from the primitives (leaf children) or from the already refitted child nodes
-// (node_box), then the same quantisation the host collapser applies (bvh_build.cpp Collapser::emit): origin = node min, per-axis
-// power-of-two grid, planes rounded outward and verified with the decode expression fmaf(q, 2^e, origin).
+// (node_box), then the same quantisation the host collapser applies (bvh_build.cpp Collapser::emit): origin = the next float below
+// node min - extent / 2048 (about 1/8 cell), per axis the smallest power-of-two grid from frexp(extent / 255) on at which every
+// child's upper plane fits in a byte, every plane the nearest cell that covers its box with a guard band of 1/32 cell, corrected
+// against the decode expression fmaf(q, 2^e, origin).
 constexpr double kGuardCells = 1.0 / 32.0;   // guard band around every quantised plane (see bvh_build.cpp, traverse.h)
 
 template <class Prims>

@@ -76,9 +76,8 @@ __global__ void flatten_slots_kernel(float4* tris, typename std::conditional<RES
 }
 
 // One thread per node of one tree level (deepest level first): child boxes from the primitives (leaf children) or
-// from the already refitted child nodes (node_box), then the same quantisation the host collapser applies
-// (bvh_build.cpp Collapser::emit): origin = node min, per-axis power-of-two grid, planes rounded outward and
-// verified with the decode expression fmaf(q, 2^e, origin).
+// from the already refitted child nodes (node_box), then the quantisation of refit_node (bvh_device.h), the one
+// the host collapser applies (bvh_build.cpp Collapser::emit).
 template <class Prims>
 __global__ void refit_level_kernel(uint32_t* nodes, const Prims prims, float* node_box, const uint32_t* level_nodes, uint32_t first, uint32_t count) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

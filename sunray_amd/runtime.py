@@ -446,6 +446,14 @@ def bvh_layout():
     return w.value, nd.value, po.value, co.value
 
 
+def tree_build_limits(kind, n_prims):
+    """(primitives per leaf, stack floor of the collapse before the build's cap bounds it) of a device-built tree of `n_prims`
+    primitives of one abi.TREE_KIND_* (sr_tree_build_limits)."""
+    leaf_max, floor = C.c_uint32(), C.c_uint32()
+    check(lib().sr_tree_build_limits(C.c_uint32(kind), C.c_uint64(n_prims), C.byref(leaf_max), C.byref(floor)))
+    return leaf_max.value, floor.value
+
+
 def host_bvh(v0_e1_e2):
     """Host-only BVH build (no GPU): returns (nodes[n, node_dwords] u32, tris[n,12] f32, max_depth, max_stack)."""
     v = np.ascontiguousarray(v0_e1_e2, dtype=np.float32).reshape(-1, 9)
