@@ -1050,7 +1050,6 @@ typedef enum SrProbeHelper {
 } SrProbeHelper;
 int sr_probe_helper(uint32_t fn, const uint32_t* in, uint32_t n, uint32_t* out, void* stream);
 int sr_probe_helper_layout(uint32_t fn, uint32_t* in_dwords, uint32_t* out_dwords);
-
 /* The "raytracing_ris" pass (lib.rs:1662-1705): one ray_gen_ris invocation per pixel
  * (ray_gen_ris.slang:12-440): G-buffer + ReSTIR-DI reservoir + ReSTIR-GI initial reservoir. */
 int sr_trace_ris(const SrRtParams* params, void* stream);
@@ -1516,6 +1515,11 @@ int sr_scene_set_tile_costs(SrScene* scene, int which, uint32_t x0, uint32_t wid
  * order has been derived for that geometry (no launch, no sr_scene_set_tile_costs). Waits for the device. */
 int sr_scene_read_tile_order(SrScene* scene, int which, uint32_t x0, uint32_t width, uint32_t y0, uint32_t rows, uint32_t* out,
                              uint32_t cap, uint32_t* order_cap);
+/* Test hook: the largest light table (emissive triangles of the instance list) that a wave of the RIS pass keeps in its LDS while
+ * it draws its candidates; a longer table is read from global memory, with the same results. It follows from the LDS a launch of
+ * this scene's passes takes (traversal stack of the built structure), so it can change with sr_scene_set_instances; 0 when the
+ * scene never stages (SR_LIGHT_STAGE=0 in the environment at sr_scene_create). */
+int sr_scene_light_stage_capacity(const SrScene* scene, uint32_t* lights);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Tile-parallel rendering across the GPUs of a node                               */

@@ -347,6 +347,7 @@ struct SrScene {
     int timing = 0;
     int n_cus = 256;
     int stack_entries = 8;   // LDS traversal-stack entries per lane this scene's tree needs (multiple of 4)
+    int light_stage = 1;     // the RIS pass may keep the light table in its waves' LDS between queries (SR_LIGHT_STAGE=0: never; A/B runs)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events[kNumKinds];
     size_t events_used[kNumKinds] = {0, 0, 0, 0};
     ~SrScene() { for (auto& pool : events) for (auto& e : pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); } }
@@ -770,6 +771,7 @@ int sr_scene_create(int device, SrScene** out) {
     if (const char* ev = getenv("SR_TL_BUILD")) s->tl_build_mode = !strcmp(ev, "host") ? SR_TL_BUILD_HOST : (!strcmp(ev, "device") ? SR_TL_BUILD_DEVICE : SR_TL_BUILD_AUTO);
     if (const char* ev = getenv("SR_BLAS_BATCH")) s->blas_batch_mode = !strcmp(ev, "on") ? SR_BLAS_BATCH_ON : SR_BLAS_BATCH_OFF;
     if (const char* ev = getenv("SR_BLAS_BUILD")) s->blas_build_mode = !strcmp(ev, "host") ? SR_MESH_TREE_BUILD_HOST : (!strcmp(ev, "device") ? SR_MESH_TREE_BUILD_DEVICE : SR_MESH_TREE_BUILD_AUTO);
+    if (const char* ev = getenv("SR_LIGHT_STAGE")) s->light_stage = atoi(ev) != 0;
     if (const char* ev = getenv("SR_LIGHT_TABLE")) s->light_mode = !strcmp(ev, "device") ? SR_LIGHTS_DEVICE : SR_LIGHTS_HOST;
     if (const char* ev = getenv("SR_FAST_BUILD_HEIGHT")) s->height_bound = !strcmp(ev, "rebalance") ? SR_HEIGHT_BOUND_REBALANCE : SR_HEIGHT_BOUND_REFUSE;
     if (const char* ev = getenv("SR_FAST_BUILD")) s->fast_build_ploc = !strcmp(ev, "lbvh") ? 0 : (!strncmp(ev, "ploc", 4) && atoi(ev + 4) > 0 ? atoi(ev + 4) : 16);
@@ -3290,6 +3292,7 @@ static int run_pass(const SrRtParams* p, int which, void* stream) {
     a.width = p->width; a.height = p->height;
     a.y0 = y0; a.y1 = y1; a.x0 = x0; a.x1 = x1;
     a.cfg = p->config;
+    a.light_lds_bytes = s->light_stage ? 0xFFFFFFFFu : 0u;   // srk_launch_pass lowers it to the launch's LDS size
     hipStream_t st = (hipStream_t)stream;
     // tile schedule of this launch geometry: order from the previous launch's costs, costs of this launch for the next
     SrScene::TileSchedule* sched = nullptr;
@@ -3398,6 +3401,13 @@ int sr_scene_read_tile_order(SrScene* s, int which, uint32_t x0, uint32_t width,
     if ((rc = bind_device(s)) != SR_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, sched->order.p, (size_t)*order_cap * 8 * 4, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+int sr_scene_light_stage_capacity(const SrScene* s, uint32_t* lights) {
+    if (!s || !lights) return fail(SR_ERR_INVALID_ARG, "sr_scene_light_stage_capacity: null argument");
+    if (!s->built) return fail(SR_ERR_STATE, "sr_scene_light_stage_capacity: call sr_scene_set_instances first");
+    *lights = s->light_stage ? (uint32_t)srk_lds_rows(s->stack_entries, s->two_level ? 1 : 0) * 64u * 4u / 64u : 0u;   // rows of 64 ints, 64-byte records
     return SR_OK;
 }
 

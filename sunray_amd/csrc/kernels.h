@@ -29,6 +29,9 @@ struct PassArgs {
     uint32_t x0, x1;              // columns [x0, x1) of the image are traced by this launch
     uint32_t tiles_x, tiles_y;    // pixel tiles covering (x1 - x0) x (y1 - y0); filled in by srk_launch_pass
     uint32_t order_cap;           // blocks per XCD = entries per XCD in tile_order (srk_pass_order_cap)
+    // Bytes of the wave's LDS the RIS pass may hold the light table in between two queries. The caller passes its upper bound
+    // (0 = read the table from global memory), srk_launch_pass lowers it to the launch's dynamic LDS size.
+    uint32_t light_lds_bytes;
     // cost-ordered tile schedule (kernels.hip): this launch's per-tile cost is written to tile_cost, the order derived
     // from the PREVIOUS launch's costs is read from tile_order (null on the first launch of a geometry)
     uint32_t* tile_cost;

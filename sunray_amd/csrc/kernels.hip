@@ -12,6 +12,7 @@
 // dispatch), XCD x owns column band x of the image, so its private 4 MiB L2 holds the part of the BVH under that band;
 // inside a band the rows are swept from the expensive end to the cheap end (thread_pixel, tile_order_kernel).
 #include <algorithm>
+#include <type_traits>
 #include "kernels.h"
 
 namespace srd {
@@ -218,13 +219,32 @@ SRD Payload load_payload(const SrRayPayload* p) {
 }
 
 SRD f3 light_emission(const DevScene& sc, uint32_t indirection_idx) { return ld3(sc.lights[indirection_idx].emission); }
+// Where DevLight records are read from: the table in global memory, or (STAGED) the copy a wave of the RIS pass keeps in its LDS
+// between two queries (stage_lights). The copy holds the four 16-byte parts of the records as four planes (part * n + idx):
+// ds_read_b128 banks by (address / 4) mod 64, so lanes that read the same part of different 64-byte records would meet in 4 groups
+// of banks; as planes they spread over all 16.
+struct LightTable { const DevLight* lights; const float4* staged; uint32_t n; };
+template <bool STAGED>
+SRD float4 light_part(const LightTable& t, uint32_t idx, uint32_t part) {
+    return STAGED ? t.staged[part * t.n + idx] : reinterpret_cast<const float4*>(t.lights + idx)[part];
+}
+// The wave's copy of the table: the lanes that are here (a tile at the image edge has fewer than 64) take the 16-byte parts in turn,
+// coalesced. Between two queries nothing lives in the wave's LDS (a query initialises its keys, writes a stack row before it reads it
+// and reads payload rows only under a key of its own), so the copy costs no LDS; the next query overwrites it.
+SRD void stage_lights(const LightTable& t, float4* lds) {
+    const unsigned long long here = ballot(true);
+    const uint32_t step = mask_count(here), n_parts = t.n * 4u;
+    const float4* src = reinterpret_cast<const float4*>(t.lights);
+    for (uint32_t q = lanes_below(here); q < n_parts; q += step) lds[(q & 3u) * t.n + (q >> 2)] = src[q];
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+}
 // Emissive triangle `idx` of the light list (ray_gen_ris.slang:191-210,346-362; ray_gen_final.slang:330-351):
 // world-space vertices, area and normal come precomputed from the scene build (DevLight). The random
 // draws stay at the call sites: their order is semantic.
 struct LightTri { f3 wv0, wv1, wv2, emission, normal; float area; };
-SRD LightTri fetch_light(const DevScene& sc, uint32_t idx) {
-    const float4* q = reinterpret_cast<const float4*>(sc.lights + idx);
-    const float4 a = q[0], b = q[1], c = q[2], e = q[3];
+template <bool STAGED>
+SRD LightTri fetch_light(const LightTable& t, uint32_t idx) {
+    const float4 a = light_part<STAGED>(t, idx, 0u), b = light_part<STAGED>(t, idx, 1u), c = light_part<STAGED>(t, idx, 2u), e = light_part<STAGED>(t, idx, 3u);
     LightTri r;
     r.wv0 = mk3(a.x, a.y, a.z); r.area = a.w;
     r.wv1 = mk3(b.x, b.y, b.z);
@@ -233,6 +253,7 @@ SRD LightTri fetch_light(const DevScene& sc, uint32_t idx) {
     r.normal = mk3(b.w, c.w, e.w);
     return r;
 }
+SRD LightTri fetch_light(const DevScene& sc, uint32_t idx) { return fetch_light<false>(LightTable{sc.lights, nullptr, sc.num_lights}, idx); }
 
 // Map this thread to its pixel. Returns false for threads outside the image / tile.
 // XCD-aware and load-balanced: the image is cut into 8 COLUMN bands, one per XCD (blocks b and b+8
@@ -469,23 +490,33 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void ris_kernel(const Pa
             }
         }
 
+        // The lanes of the tile are together again here, and the wave's LDS is idle until the next query: if some lane is going to
+        // draw RIS candidates and the light table fits, the wave copies it there, and the candidate loop (16 dependent gathers of a
+        // 64-byte record per lane) reads the copy instead of global memory. Wave-uniform; same records, same bits.
+        const uint32_t num_lights = sc.num_lights;
+        const LightTable lights{sc.lights, reinterpret_cast<const float4*>(s_stack), num_lights};
+        const bool staged = num_lights > 0 && a.cfg.ris_candidates > 0 && num_lights * (uint32_t)sizeof(DevLight) <= a.light_lds_bytes &&
+                            (ballot(found_diffuse_surface) & ballot(roughness > 0.2f)) != 0ull;
+        if (staged) stage_lights(lights, reinterpret_cast<float4*>(s_stack));
+
         if (!found_diffuse_surface) {
             store_gbuffer(a, pix, 100000.0f, splat(0.0f), 0.0f, splat(0.0f), 0.0f, 0.0f);
             SrReservoir empty; zero_reservoir(empty);
             store48(reservoir_cur + pix, empty);
         } else {
             SrReservoir current_r; zero_reservoir(current_r);
-            const uint32_t num_lights = sc.num_lights;
             if (num_lights > 0 && roughness > 0.2f) {
                 // Target function (max component of the unshadowed contribution) of the sample the reservoir holds. The reservoir
                 // weights below need it for a sample whose contribution was evaluated a moment ago from the very same operands
                 // (position and normal as stored, emission of the same light): it is carried along instead of evaluated again.
                 // No sample yet: position and normal are zero, for which eval_unshadowed_light gives exactly 0.
                 float p_hat_held = 0.0f;
+                // one definition of the loop, compiled for either source of the records (the choice is wave-uniform)
+                auto draw_candidates = [&](auto from_lds) {
                 for (uint32_t i = 0; i < a.cfg.ris_candidates; i++) {
                     uint32_t cand_idx = (uint32_t)(rnd(rng) * (float)num_lights);
                     if (cand_idx > num_lights - 1) cand_idx = num_lights - 1;
-                    const LightTri lt = fetch_light(sc, cand_idx);
+                    const LightTri lt = fetch_light<decltype(from_lds)::value>(lights, cand_idx);
                     const float cand_area = lt.area;
                     const float sqr1 = sqrtf(rnd(rng));
                     const float u = 1.0f - sqr1;
@@ -505,6 +536,8 @@ __global__ __launch_bounds__(kPassBlock, pass_waves(V)) void ris_kernel(const Pa
                         p_hat_held = p_hat;
                     }
                 }
+                };
+                if (staged) draw_candidates(std::true_type{}); else draw_candidates(std::false_type{});
                 if (current_r.w_sum > 0.0f) current_r.W = current_r.w_sum / fmaxf(current_r.M * p_hat_held, 0.0001f);
                 if (a.frame_count > 0 && prev_valid) {
                     const float ppx = prev_u * (float)W, ppy = prev_v * (float)H;
@@ -1039,6 +1072,7 @@ int srk_launch_pass(const PassArgs& args_in, int which, int stats, int textured,
     if (n_tiles == 0) return 0;
     dim3 grid(args.order_cap * 8), block(kPassBlock);
     const size_t lds = (size_t)(stack_entries + lds_extra_rows(two_level)) * kPassBlock * sizeof(int);
+    args.light_lds_bytes = std::min(args.light_lds_bytes, (uint32_t)lds);
     const int v = (stats ? 1 : 0) | (textured ? 2 : 0) | (two_level ? 4 : 0);
     if (which == 0) {
         switch (v) {

@@ -871,6 +871,13 @@ class Scene:
                                              _p(out), C.c_uint32(len(out)), C.byref(cap)))
         return out[:8 * cap.value].reshape(8, cap.value).copy(), cap.value
 
+    def light_stage_capacity(self):
+        """Test hook: the longest light table a wave of the RIS pass keeps in its LDS for the candidate loop, in lights
+        (sr_scene_light_stage_capacity); longer tables are read from global memory."""
+        n = C.c_uint32()
+        check(lib().sr_scene_light_stage_capacity(self._h, C.byref(n)))
+        return n.value
+
     def set_instancing(self, mode):
         """Form of the acceleration structure at the next set_instances: "auto" | "flat" | "two_level" (sr_scene_set_instancing)."""
         check(lib().sr_scene_set_instancing(self._h, C.c_uint32({"auto": 0, "flat": 1, "two_level": 2}[mode])))
