@@ -7,7 +7,10 @@ With --device-clips the animation is evaluated on the GPU too: the clip is baked
 (Renderer.attach_clip); a frame then sets every copy's time and calls Renderer.pose_actors, whose clip kernel writes the joint
 matrices where the posing kernel reads them and the instance transforms into a tensor that render_device_transforms takes.
 
-    python examples/skinned_crowd.py [--copies 64] [--frames 24] [--size 640x480] [--out crowd.png] [--device-clips]
+With --device-clips --crossfade SECONDS every copy fades from the file's static pose into its clip over the first SECONDS of the
+run, on the GPU as well: both are baked and attached, and a frame calls Renderer.pose_actors_blended with the clip's share so far.
+
+    python examples/skinned_crowd.py [--copies 64] [--frames 24] [--size 640x480] [--out crowd.png] [--device-clips [--crossfade SECONDS]]
 
 Needs a GPU: the product path has no CPU fallback.
 """
@@ -29,7 +32,10 @@ def main():
     ap.add_argument("--size", default="640x480")
     ap.add_argument("--out", default="crowd.png")
     ap.add_argument("--device-clips", action="store_true", help="evaluate the animation on the GPU from a baked clip")
+    ap.add_argument("--crossfade", type=float, default=0.0, metavar="SECONDS", help="with --device-clips: fade every copy from the static pose into its clip")
     args = ap.parse_args()
+    if args.crossfade and not args.device_clips:
+        ap.error("--crossfade needs --device-clips")
     from sunray_amd import runtime as rt
     w, h = (int(v) for v in args.size.split("x"))
     gltf = rt.Gltf(os.path.join(os.path.dirname(HERE), "tests", "golden", "skinned_bar.glb"))
@@ -81,11 +87,21 @@ def device_clips(args, rt, gltf, r, copies, skinned, duration, camera):
         actors.append((cid, 0.0, placement, loaded.instance_rows(c * n), 0))
         items += [(int(loaded.keys[b]), c, skin, None) for b, skin in skinned]
         layout += loaded.layout()
-    packed = rt.ActorArgs(actors, items)                      # packed once: a frame rewrites the times in place
+    if args.crossfade > 0.0:                                  # source A: the static pose; source B: the clip, at the share reached so far
+        still = r.attach_clip(gltf.bake_clip(-1))
+        packed = rt.BlendedActorArgs([(still, 0.0, cid, 0.0, 0.0) + ac[2:] for ac in actors], items)
+    else:
+        packed = rt.ActorArgs(actors, items)                  # packed once: a frame rewrites the times in place
     transforms = torch.zeros((len(copies) * n, 12), dtype=torch.float32, device="cuda:%d" % r.devices[0])
     for f in range(args.frames):
-        packed.set_times([(duration * f / max(args.frames - 1, 1) + duration * c / args.copies) % duration for c in range(len(copies))])
-        r.pose_actors(packed, tensor=transforms)
+        times = [(duration * f / max(args.frames - 1, 1) + duration * c / args.copies) % duration for c in range(len(copies))]
+        if args.crossfade > 0.0:
+            share = min(1.0, duration * f / max(args.frames - 1, 1) / args.crossfade)
+            packed.set_fades(times, [share] * len(copies))
+            r.pose_actors_blended(packed, tensor=transforms)
+        else:
+            packed.set_times(times)
+            r.pose_actors(packed, tensor=transforms)
         r.wait_frame(r.render_device_transforms(camera, layout, transforms))
     info = r.actor_pose_info()
     print("last call: %d actors, %d items, %d nodes and %d channels evaluated, %d bytes uploaded, %d launches, %d read-back, %.3f ms on the host" % (

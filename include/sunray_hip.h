@@ -1391,6 +1391,63 @@ int sr_scene_read_actor_matrices(const SrScene* scene, uint32_t actor, SrTransfo
  * or clip_weights_kernel wrote it: *n_active, then that many target indices and weights (room for the mesh's n_targets each;
  * either may be NULL). An item without a morph stage has 0. SR_ERR_STATE under the rule of sr_scene_read_actor_matrices. */
 int sr_scene_read_item_active(const SrScene* scene, uint32_t item, uint32_t* index_out, float* weight_out, uint32_t* n_active);
+/* Cross-fades: an actor between two baked clips, each at its own time, at the share `weight` of the second.
+ * The rule (csrc/clip_rule.h, shared by host and device, + - * / and sqrt in fp64 from the fp32 values, rounded once, no libm): two
+ * node records blend into one. weight 0: A's record, whole, its `animated` mask included; weight 1: B's, whole; so a blended call
+ * at the end weights is byte-equal to the plain call with that clip. Otherwise the mask is A's | B's; where that is 0 the record
+ * is A's and the node keeps composing from the file's matrix; where it is not, each of translation, rotation and scale is taken
+ * whole: a part whose bytes are equal in both records is copied (a clip blended with itself at one time is the identity at every
+ * weight), otherwise translation and scale are (float)(a + w (b - a)) and the rotation is a normalised lerp along the shorter arc
+ * (b negated where dot(a, b) < 0, r = a + w (b - a), normalised). nlerp and not slerp, on purpose: it keeps atan2 and sin out of
+ * the stage. A node's local matrix comes from its TRS where the record's mask is not 0, and from the file's matrix otherwise: a
+ * node the file gives by `matrix` that only one clip animates therefore jumps between its matrix and the glTF default TRS at the
+ * end weights (glTF forbids animating such nodes). Morph weights blend per target in the same form.
+ * sr_clip_blend_compatible: SR_OK where the two clips' blocks have equal n_nodes, level table and instance table, per node equal
+ * parent, gltf_node, level, file TRS and matrix (the animated masks may differ), and equal skins, joint nodes, joint skins and
+ * inverse bind matrices: in practice, bakes of one file. Otherwise SR_ERR_INVALID_ARG, the words naming the first table that
+ * differs.
+ * sr_clip_blend_host: the record rule over n_nodes records. sr_clip_compose_records_host: sr_clip_compose_host with each node's
+ * TRS-or-matrix decision taken from trs[n].animated in place of the clip's own mask (on sr_clip_sample_host's records: the same
+ * bytes). sr_clip_pose_blend_host: sample, sample, blend, compose (the clips must be compatible). sr_clip_blend_weights_host: the
+ * blended weights of the morph set of `blas`, which both clips must have available, in sr_clip_weights_host's statuses and words.
+ * A weight outside [0, 1] or NaN: SR_ERR_INVALID_ARG. */
+int sr_clip_blend_compatible(const SrClip* a, const SrClip* b);
+int sr_clip_blend_host(const SrNodeTrs* trs_a, const SrNodeTrs* trs_b, uint32_t n_nodes, float weight, SrNodeTrs* out);
+int sr_clip_compose_records_host(const SrClip* clip, const SrNodeTrs* trs, const SrTransform* placement, SrTransform* joint_matrices,
+                                 SrTransform* instance_transforms, uint32_t* singular_skin);
+int sr_clip_pose_blend_host(const SrClip* a, float time_a, const SrClip* b, float time_b, float weight, const SrTransform* placement,
+                            SrTransform* joint_matrices, SrTransform* instance_transforms);
+int sr_clip_blend_weights_host(const SrClip* a, float time_a, const SrClip* b, float time_b, float weight, uint32_t blas, float* weights_out,
+                               uint32_t n_targets);
+/* sr_scene_pose_actors_blended is sr_scene_pose_actors for such actors: clip_blend_kernel (one block per actor) stands where
+ * clip_pose_kernel stands: it samples both clips, blends the per-node records, composes the hierarchy once and writes the joint
+ * matrices and the instance transforms exactly where sr_scene_pose_actors writes them; for an item with SR_ACTOR_CLIP_WEIGHTS,
+ * clip_blend_weights_kernel stands where clip_weights_kernel stands and writes the blended weights' active list. Everything else is
+ * sr_scene_pose_actors': the one upload (an actor's row is 96 bytes, a clip-weighted item's 48), the launch sequence, the check
+ * words, the one read-back, all-or-nothing refusal, SrActorPoseInfo (`channels` counts A's plus B's; sr_scene_actor_pose_info
+ * reports the last call of either entry point) and the read-outs (the kept TRS is the blended record).
+ * Numerics: each source is sampled under sr_scene_pose_actors' contract against sr_clip_sample_host; the blended records are bit
+ * equal to sr_clip_blend_host of the device's own sources, and the globals, joint matrices and instance transforms to
+ * sr_clip_compose_records_host of the device's own blended records, without exception. The blended active list is bit equal to
+ * the compaction of sr_clip_blend_weights_host.
+ * Refused on the host before any device work, behind "pose_actors_blended: actor <i>: " or "pose_actors_blended: item <i>: ":
+ * everything sr_scene_pose_actors refuses, for both clips; a weight outside [0, 1] or NaN; clips that are not compatible
+ * (sr_clip_blend_compatible's words); for a clip-weighted item, either clip lacking the set, either set unavailable (its kept
+ * status and the loader's words), or sets of unequal n_targets. Refused on the device as sr_scene_pose_actors refuses.
+ * SR_ACTORS_KEEP_SOURCES: also store both sources' sampled TRS per actor; sr_scene_read_actor_sources reads them (n_nodes records
+ * each, either may be NULL; SR_ERR_STATE: the last call kept none). */
+typedef struct SrClipBlendActor {      /* one character between two clips. 48 bytes */
+    uint32_t clip_id; float time_seconds;          /* source A */
+    uint32_t clip_id_b; float time_seconds_b;      /* source B */
+    float weight; uint32_t reserved;               /* the share of B, in [0, 1] */
+    const SrTransform* placement;      /* as SrClipActor's */
+    const uint32_t* instance_rows;
+    uint32_t instance_base, reserved2;
+} SrClipBlendActor;
+#define SR_ACTORS_KEEP_SOURCES 2u      /* flags of sr_scene_pose_actors_blended: also store both sources' sampled TRS per actor */
+int sr_scene_pose_actors_blended(SrScene* scene, const SrClipBlendActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
+                                 SrTransform* d_instance_transforms, uint32_t flags, void* stream);
+int sr_scene_read_actor_sources(const SrScene* scene, uint32_t actor, SrNodeTrs* trs_a, SrNodeTrs* trs_b);
 
 /* What Renderer::load_gltf / load_scene return (lib.rs:779-846): the asset group and the scene's instances
  * grouped per BLAS key in BLAS order. Keys are ResourceKey{group, index} packed as group << 32 | index
@@ -1450,6 +1507,9 @@ int sr_renderer_attach_clip(SrRenderer* renderer, const SrClip* clip, uint32_t* 
 int sr_renderer_detach_clip(SrRenderer* renderer, uint32_t clip_id);
 int sr_renderer_pose_actors(SrRenderer* renderer, const SrClipActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
                             SrTransform* d_instance_transforms, uint32_t flags, void* stream);
+/* sr_scene_pose_actors_blended through the facade, by the same per-slot path as sr_renderer_pose_actors. */
+int sr_renderer_pose_actors_blended(SrRenderer* renderer, const SrClipBlendActor* actors, uint32_t n_actors, const SrActorPoseItem* items,
+                                    uint32_t n_items, SrTransform* d_instance_transforms, uint32_t flags, void* stream);
 int sr_renderer_actor_pose_info(const SrRenderer* renderer, SrActorPoseInfo* out);
 /* How sr_renderer_pose_scene poses a loaded scene's rigged and morphed meshes: SR_POSE_BATCH_OFF (the default), one
  * sr_renderer_skin_mesh / sr_renderer_pose_mesh per mesh (each a batch of one item); SR_POSE_BATCH_ON, all of them by one sr_renderer_pose_meshes.

@@ -51,6 +51,8 @@ SYMBOLS = [
     "sr_clip_morph_count", "sr_clip_morph", "sr_clip_morph_keys", "sr_clip_weights_host", "sr_scene_read_item_active",
     "sr_scene_attach_clip", "sr_scene_detach_clip", "sr_scene_pose_actors", "sr_scene_actor_pose_info", "sr_scene_read_actor_nodes", "sr_scene_read_actor_matrices",
     "sr_renderer_attach_clip", "sr_renderer_detach_clip", "sr_renderer_pose_actors", "sr_renderer_actor_pose_info",
+    "sr_clip_blend_compatible", "sr_clip_blend_host", "sr_clip_compose_records_host", "sr_clip_pose_blend_host", "sr_clip_blend_weights_host",
+    "sr_scene_pose_actors_blended", "sr_scene_read_actor_sources", "sr_renderer_pose_actors_blended",
 ]
 
 

@@ -270,6 +270,15 @@ class SrActorPoseInfo(C.Structure):  # the last sr_scene_pose_actors that reache
 assert C.sizeof(SrClipInfo) == 40 and C.sizeof(SrClipActor) == 32 and C.sizeof(SrActorPoseItem) == 32 and C.sizeof(SrActorPoseInfo) == 88
 
 
+class SrClipBlendActor(C.Structure):  # one character of sr_scene_pose_actors_blended: between two clips, 48 B
+    _fields_ = [("clip_id", C.c_uint32), ("time_seconds", C.c_float), ("clip_id_b", C.c_uint32), ("time_seconds_b", C.c_float), ("weight", C.c_float),
+                ("reserved", C.c_uint32), ("placement", C.c_void_p), ("instance_rows", C.c_void_p), ("instance_base", C.c_uint32), ("reserved2", C.c_uint32)]
+
+
+ACTORS_KEEP_SOURCES = 2  # SR_ACTORS_KEEP_SOURCES
+assert C.sizeof(SrClipBlendActor) == 48
+
+
 class SrMeshFrameInfo(C.Structure):  # one mesh's frame and its last position update (sr_scene_mesh_frame_info), 32 B
     _fields_ = [("flags", C.c_uint32), ("n_groups", C.c_uint32), ("n_entries", C.c_uint32), ("max_valence", C.c_uint32),
                 ("updates", C.c_uint32), ("first_bad", C.c_uint32), ("frame_ms", C.c_double)]

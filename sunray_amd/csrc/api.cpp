@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <set>
 #include <string>
 #include <chrono>
 #include <vector>
@@ -29,6 +30,7 @@
 #include "clip.h"
 #include "clip_pose.h"
 #include "clip_weights.h"
+#include "clip_blend.h"
 #include "tl_record.h"
 
 namespace {
@@ -283,6 +285,9 @@ struct SrScene {
     std::vector<ItemActiveRecord> item_active_records;
     bool actor_stage_current = false, actor_nodes_kept = false;
     DeviceBuffer d_actor_trs, d_actor_globals;
+    // after a sr_scene_pose_actors_blended with SR_ACTORS_KEEP_SOURCES: both sources' sampled TRS, at the kept nodes' places
+    bool actor_sources_kept = false;
+    DeviceBuffer d_actor_source_a, d_actor_source_b;
     // sr_scene_update_mesh_positions*: the face vectors of the last call (one or two 16-byte pieces per triangle), the uploaded
     // positions of the host-pointer form, and the records the mesh-frame producer wrote (scratch: the replicas of a renderer take
     // them from there)
@@ -1128,6 +1133,16 @@ struct ActorFeed {
     uint64_t n_matrices = 0, n_nodes = 0, n_channels = 0;
     SrTransform* d_instance_transforms = nullptr;
     SrActorPoseInfo* info = nullptr;
+    // a blended feed (sr_scene_pose_actors_blended): its rows for clip_blend_kernel and clip_blend_weights_kernel stand where
+    // `rows` and `weight_rows` stand in the upload, and the two kernels run where clip_pose_kernel and clip_weights_kernel run
+    bool blended = false;
+    std::vector<srd::ClipBlendActorRow> blend_rows;
+    std::vector<srd::ClipBlendWeightRow> blend_weight_rows;
+    uint32_t n_weight_rows() const { return (uint32_t)(blended ? blend_weight_rows.size() : weight_rows.size()); }
+    size_t actor_row_bytes() const { return blended ? sizeof(srd::ClipBlendActorRow) : sizeof(srd::ClipActorRow); }
+    size_t weight_row_bytes() const { return blended ? sizeof(srd::ClipBlendWeightRow) : sizeof(srd::ClipWeightRow); }
+    uint32_t& matrix_base(uint32_t a) { return blended ? blend_rows[a].matrix_base : rows[a].matrix_base; }
+    uint32_t node_base(uint32_t a) const { return blended ? blend_rows[a].node_base : rows[a].node_base; }
 };
 
 // The one posing path: sr_scene_pose_meshes (`batch`) and, with a list of one item, sr_scene_skin_mesh and sr_scene_pose_mesh.
@@ -1152,14 +1167,14 @@ struct ActorFeed {
 // have, the slots follow the host's lists inside the arrays. A call without such an item is laid out and launched as ever.
 int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream, bool batch, SrPoseBatchInfo* out, ActorFeed* feed = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
-    const std::string who = feed ? "pose_actors" : batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
+    const std::string who = feed ? (feed->blended ? "pose_actors_blended" : "pose_actors") : batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
     const auto prefix = [batch, &who](uint32_t i) { return batch ? who + ": item " + std::to_string(i) + ": " : std::string(); };
     // an item's skin stage: its matrices come from the caller's host pointer, or from the slice the clip kernel writes
     const auto fed = [feed](uint32_t i) { return feed && feed->item_matrix[i] != 0xFFFFFFFFu; };
     const auto skin_stage = [items, &fed](uint32_t i) { return items[i].joint_matrices != nullptr || fed(i); };
     const auto clip_weighted = [feed](uint32_t i) { return feed && feed->item_weight_row[i] != 0xFFFFFFFFu; };
     const auto morph_stage = [items, &clip_weighted](uint32_t i) { return items[i].weights != nullptr || clip_weighted(i); };
-    const uint32_t n_weight_items = feed ? (uint32_t)feed->weight_rows.size() : 0;
+    const uint32_t n_weight_items = feed ? feed->n_weight_rows() : 0;
     uint64_t n_slots = 0;                                     // entries of the clip-weighted items' slots
     std::vector<uint32_t> slots(n_items), counts(n_items), n_active(n_items), active_index, active;
     std::vector<float> active_weight;
@@ -1192,12 +1207,12 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     // Actors add their rows and their instance rows behind the batch's parts: that is the upload. The matrices the clip kernel
     // writes follow it, outside the uploaded bytes, a whole number of matrices from lay.matrices so that matrix_base reaches them.
     const uint32_t n_actors = feed ? feed->n_actors : 0;
-    const size_t actor_rows_at = lay.bytes, weight_rows_at = actor_rows_at + sizeof(srd::ClipActorRow) * (size_t)n_actors;
-    const size_t inst_rows_at = weight_rows_at + sizeof(srd::ClipWeightRow) * (size_t)n_weight_items;
+    const size_t actor_rows_at = lay.bytes, weight_rows_at = actor_rows_at + (feed ? feed->actor_row_bytes() : 0) * (size_t)n_actors;
+    const size_t inst_rows_at = weight_rows_at + (feed ? feed->weight_row_bytes() : 0) * (size_t)n_weight_items;
     const size_t upload_bytes = inst_rows_at + ((4 * (feed ? feed->instance_rows.size() : 0) + 15u) & ~(size_t)15u);
     const uint64_t fed_first = (upload_bytes - lay.matrices + sizeof(SrTransform) - 1) / sizeof(SrTransform);
     size_t stage_bytes = feed ? lay.matrices + sizeof(SrTransform) * (size_t)(fed_first + feed->n_matrices) : lay.bytes;
-    if (feed && fed_first + feed->n_matrices >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_actors: the call holds 2^32 joint matrices or more");
+    if (feed && fed_first + feed->n_matrices >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, who + ": the call holds 2^32 joint matrices or more");
     if (slots_outside) {
         const size_t slot_bytes = (4 * (size_t)n_slots + 15u) & ~(size_t)15u;
         lay.active_index = (stage_bytes + 15u) & ~(size_t)15u; lay.active_weight = lay.active_index + slot_bytes;
@@ -1209,6 +1224,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         (rc = s->d_pose_scratch.reserve(sizeof(SrVertex) * (size_t)n_vertices)) != SR_OK) return rc;
     const bool keep_nodes = feed && (feed->flags & SR_ACTORS_KEEP_NODES);
     if (keep_nodes && ((rc = s->d_actor_trs.reserve(sizeof(SrNodeTrs) * (size_t)feed->n_nodes)) != SR_OK || (rc = s->d_actor_globals.reserve(64 * (size_t)feed->n_nodes)) != SR_OK)) return rc;
+    const bool keep_sources = feed && feed->blended && (feed->flags & SR_ACTORS_KEEP_SOURCES);
+    if (keep_sources && ((rc = s->d_actor_source_a.reserve(sizeof(SrNodeTrs) * (size_t)feed->n_nodes)) != SR_OK ||
+                         (rc = s->d_actor_source_b.reserve(sizeof(SrNodeTrs) * (size_t)feed->n_nodes)) != SR_OK)) return rc;
     // the staging block: rows, block table, matrices, active lists; then the actors' rows and instance rows
     std::vector<unsigned char> stage(upload_bytes, 0);
     srd::PoseBatchItem* rows = (srd::PoseBatchItem*)(stage.data() + lay.items);
@@ -1233,8 +1251,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     }
     for (uint32_t i = 0; i < n_items; i++) {                  // the slots follow the host's lists; the kernel writes n_active (0 until then)
         if (!clip_weighted(i)) continue;
-        srd::ClipWeightRow& wr = feed->weight_rows[feed->item_weight_row[i]];
-        wr.item = i; wr.active_base = active_base; wr.check_word = (uint32_t)(2 * (size_t)n_items + n_actors + feed->item_weight_row[i]);
+        const uint32_t check_word = (uint32_t)(2 * (size_t)n_items + n_actors + feed->item_weight_row[i]);
+        if (feed->blended) { srd::ClipBlendWeightRow& wr = feed->blend_weight_rows[feed->item_weight_row[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
+        else { srd::ClipWeightRow& wr = feed->weight_rows[feed->item_weight_row[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
         rows[i].active_base = active_base;
         active_base += feed->item_clip_targets[i];
     }
@@ -1250,9 +1269,10 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     std::vector<uint32_t> bad(n_check, 0xFFFFFFFFu);
     EventPair pose_timer(s), scatter_timer(s), clip_timer(s);
     if (feed) {
-        for (uint32_t a = 0; a < n_actors; a++) feed->rows[a].matrix_base += (uint32_t)fed_first;
-        memcpy(stage.data() + actor_rows_at, feed->rows.data(), sizeof(srd::ClipActorRow) * (size_t)n_actors);
-        if (n_weight_items) memcpy(stage.data() + weight_rows_at, feed->weight_rows.data(), sizeof(srd::ClipWeightRow) * (size_t)n_weight_items);
+        for (uint32_t a = 0; a < n_actors; a++) feed->matrix_base(a) += (uint32_t)fed_first;
+        if (n_actors) memcpy(stage.data() + actor_rows_at, feed->blended ? (const void*)feed->blend_rows.data() : (const void*)feed->rows.data(), feed->actor_row_bytes() * (size_t)n_actors);
+        if (n_weight_items)
+            memcpy(stage.data() + weight_rows_at, feed->blended ? (const void*)feed->blend_weight_rows.data() : (const void*)feed->weight_rows.data(), feed->weight_row_bytes() * (size_t)n_weight_items);
         if (!feed->instance_rows.empty()) memcpy(stage.data() + inst_rows_at, feed->instance_rows.data(), 4 * feed->instance_rows.size());
     }
     s->actor_stage_current = false;                          // the block changes hands
@@ -1260,11 +1280,22 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     if (e == 0) e = (int)hipMemcpyAsync(s->d_pose_stage.p, stage.data(), upload_bytes, hipMemcpyHostToDevice, st);
     if (feed) {
         clip_timer.begin(st);
-        if (e == 0) e = srk_clip_pose((const srd::ClipActorRow*)(d_stage + actor_rows_at), n_actors, (const uint32_t*)(d_stage + inst_rows_at),
-                                      (SrTransform*)(s->d_pose_stage.p ? (unsigned char*)s->d_pose_stage.p + lay.matrices : nullptr), feed->d_instance_transforms,
-                                      (uint32_t*)s->d_pose_check.p + 2 * (size_t)n_items, keep_nodes ? (SrNodeTrs*)s->d_actor_trs.p : nullptr,
-                                      keep_nodes ? (float*)s->d_actor_globals.p : nullptr, st);
-        if (e == 0 && n_weight_items)
+        SrTransform* fed_matrices = (SrTransform*)(s->d_pose_stage.p ? (unsigned char*)s->d_pose_stage.p + lay.matrices : nullptr);
+        uint32_t* actor_check = (uint32_t*)s->d_pose_check.p + 2 * (size_t)n_items;
+        SrNodeTrs* kept_trs = keep_nodes ? (SrNodeTrs*)s->d_actor_trs.p : nullptr;
+        float* kept_globals = keep_nodes ? (float*)s->d_actor_globals.p : nullptr;
+        if (e == 0 && feed->blended)
+            e = srk_clip_blend((const srd::ClipBlendActorRow*)(d_stage + actor_rows_at), n_actors, (const uint32_t*)(d_stage + inst_rows_at), fed_matrices, feed->d_instance_transforms,
+                               actor_check, kept_trs, kept_globals, keep_sources ? (SrNodeTrs*)s->d_actor_source_a.p : nullptr,
+                               keep_sources ? (SrNodeTrs*)s->d_actor_source_b.p : nullptr, st);
+        else if (e == 0)
+            e = srk_clip_pose((const srd::ClipActorRow*)(d_stage + actor_rows_at), n_actors, (const uint32_t*)(d_stage + inst_rows_at), fed_matrices, feed->d_instance_transforms,
+                              actor_check, kept_trs, kept_globals, st);
+        if (e == 0 && n_weight_items && feed->blended)
+            e = srk_clip_blend_weights((const srd::ClipBlendWeightRow*)(d_stage + weight_rows_at), n_weight_items, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
+                                       (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
+                                       (uint32_t*)s->d_pose_check.p, st);
+        else if (e == 0 && n_weight_items)
             e = srk_clip_weights((const srd::ClipWeightRow*)(d_stage + weight_rows_at), n_weight_items, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
                                  (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
                                  (uint32_t*)s->d_pose_check.p, st);
@@ -1282,7 +1313,7 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     if (feed) {                                               // what the read-outs find, and the figures of a call that reached the device
         s->actor_records.clear();
         for (uint32_t a = 0; a < n_actors; a++)
-            s->actor_records.push_back(SrScene::ActorRecord{lay.matrices + sizeof(SrTransform) * (uint64_t)feed->rows[a].matrix_base, feed->actor_joints[a], feed->rows[a].node_base, feed->actor_nodes[a]});
+            s->actor_records.push_back(SrScene::ActorRecord{lay.matrices + sizeof(SrTransform) * (uint64_t)feed->matrix_base(a), feed->actor_joints[a], feed->node_base(a), feed->actor_nodes[a]});
         s->item_active_records.clear();
         for (uint32_t i = 0; i < n_items; i++) {
             n_active[i] = clip_weighted(i) ? std::min(bad[2 * (size_t)n_items + n_actors + feed->item_weight_row[i]], feed->item_clip_targets[i]) : n_active[i];   // the count that came back
@@ -1290,14 +1321,14 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
                                                                        lay.active_weight + 4 * (uint64_t)rows[i].active_base,
                                                                        clip_weighted(i) ? feed->item_clip_targets[i] : morph_stage(i) ? n_active[i] : 0u});
         }
-        s->actor_stage_current = true; s->actor_nodes_kept = keep_nodes;
+        s->actor_stage_current = true; s->actor_nodes_kept = keep_nodes; s->actor_sources_kept = keep_sources;
         SrActorPoseInfo& ai = *feed->info;
         ai = SrActorPoseInfo{n_actors, n_items, feed->n_nodes, feed->n_channels, upload_bytes, n_weight_items ? 3u : 2u, 1, ai.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, n_weight_items, clip_timer.ms(), info.pose_ms, 0.0, 0.0};
         for (uint32_t a = 0; a < n_actors && ai.refused_actor == 0xFFFFFFFFu; a++) if (bad[2 * (size_t)n_items + a] != 0xFFFFFFFFu) ai.refused_actor = a;
         if (ai.refused_actor != 0xFFFFFFFFu) {                // a singular mesh-node transform: nothing has changed but the scratch
             s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();
             ai.host_ms = ms_between(t0, std::chrono::steady_clock::now());
-            return fail(SR_ERR_UNSUPPORTED, "pose_actors: actor " + std::to_string(ai.refused_actor) + ": gltf: the transform of the skinned mesh's node is singular");
+            return fail(SR_ERR_UNSUPPORTED, who + ": actor " + std::to_string(ai.refused_actor) + ": gltf: the transform of the skinned mesh's node is singular");
         }
     }
     // all or nothing: the lowest item with a bad vertex refuses the call
@@ -1475,6 +1506,109 @@ int sr_scene_pose_actors(SrScene* s, const SrClipActor* actors, uint32_t n_actor
     }
     SrPoseBatchInfo dropped{};                                // sr_scene_pose_batch_info reads as before the call
     return pose_items(s, pose.data(), n_items, stream, true, &dropped, &feed);
+}
+
+// sr_scene_pose_actors for actors that cross-fade between two attached clips: the same checks, for both clips, and the pair's
+// compatibility (each pair of ids is compared once a call); the rest is pose_items with a blended feed.
+static_assert(sizeof(SrClipBlendActor) == 48, "the header states this size");
+int sr_scene_pose_actors_blended(SrScene* s, const SrClipBlendActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
+                                 SrTransform* d_instance_transforms, uint32_t flags, void* stream) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_actors_blended: null argument (the scene)");
+    if (flags & ~(SR_ACTORS_KEEP_NODES | SR_ACTORS_KEEP_SOURCES)) return fail(SR_ERR_INVALID_ARG, "pose_actors_blended: unknown flag bits (SR_ACTORS_KEEP_NODES and SR_ACTORS_KEEP_SOURCES are the flags)");
+    if (n_actors == 0 && n_items == 0) return SR_OK;
+    if ((n_actors && !actors) || (n_items && !items)) return fail(SR_ERR_INVALID_ARG, "pose_actors_blended: null argument (actors or items, with a count > 0)");
+    if (((uintptr_t)d_instance_transforms & 15u) != 0) return fail(SR_ERR_INVALID_ARG, "pose_actors_blended: the instance transforms are not 16-byte aligned");
+    ActorFeed feed;
+    feed.n_actors = n_actors; feed.flags = flags; feed.d_instance_transforms = d_instance_transforms; feed.info = &s->actor_info; feed.blended = true;
+    std::vector<const SrScene::AttachedClip*> clip_a(n_actors), clip_b(n_actors);
+    std::vector<uint32_t> first_matrix(n_actors);
+    std::set<std::pair<uint32_t, uint32_t>> compatible;
+    for (uint32_t a = 0; a < n_actors; a++) {
+        const SrClipBlendActor& ac = actors[a];
+        const auto prefix = [a](const std::string& text) { return "pose_actors_blended: actor " + std::to_string(a) + ": " + text; };
+        const auto ia = s->clips.find(ac.clip_id), ib = s->clips.find(ac.clip_id_b);
+        if (ia == s->clips.end() || ib == s->clips.end()) return fail(SR_ERR_INVALID_ARG, prefix("no clip is attached under this id"));
+        const SrClip& clip = ia->second.host;
+        const SrClip& other = ib->second.host;
+        const srd::ClipHeader& h = clip.header();
+        if ((clip.animation >= 0 && !std::isfinite(ac.time_seconds)) || (other.animation >= 0 && !std::isfinite(ac.time_seconds_b)))
+            return fail(SR_ERR_INVALID_ARG, prefix("gltf: the time of a pose must be finite"));
+        if (!(ac.weight >= 0.0f && ac.weight <= 1.0f)) return fail(SR_ERR_INVALID_ARG, prefix("the weight is not in [0, 1]"));
+        if (!d_instance_transforms && (ac.instance_rows || ac.instance_base)) return fail(SR_ERR_INVALID_ARG, prefix("instance rows or an instance base given without device instance transforms"));
+        for (int c = 0; ac.placement && c < 12; c++)
+            if (!std::isfinite(ac.placement->m[c])) return fail(SR_ERR_INVALID_ARG, prefix("the placement has a component that is not finite"));
+        if (!ac.instance_rows && (uint64_t)ac.instance_base + h.n_instances > 0xFFFFFFFFull) return fail(SR_ERR_INVALID_ARG, prefix("the instance base plus the clip's instances passes 2^32 rows"));
+        if (ac.clip_id != ac.clip_id_b && !compatible.count({ac.clip_id, ac.clip_id_b})) {
+            const int rc = sr_clip_blend_compatible(&clip, &other);
+            if (rc != SR_OK) return fail(rc, prefix(g_last_error));
+            compatible.insert({ac.clip_id, ac.clip_id_b});
+        }
+        srd::ClipBlendActorRow row{};
+        row.clip_a = ia->second.d_block.p; row.clip_b = ib->second.d_block.p;
+        row.time_a = ac.time_seconds; row.time_b = ac.time_seconds_b; row.weight = ac.weight;
+        row.flags = (ac.placement ? 1u : 0u) | (ac.instance_rows ? 2u : 0u);
+        row.matrix_base = (uint32_t)feed.n_matrices; row.instance_base = ac.instance_base; row.rows_base = (uint32_t)feed.instance_rows.size();
+        row.node_base = (uint32_t)feed.n_nodes;
+        if (ac.placement) memcpy(row.placement, ac.placement->m, 48);
+        if (ac.instance_rows) feed.instance_rows.insert(feed.instance_rows.end(), ac.instance_rows, ac.instance_rows + h.n_instances);
+        feed.blend_rows.push_back(row);
+        feed.actor_joints.push_back(h.n_joints); feed.actor_nodes.push_back(h.n_nodes);
+        clip_a[a] = &ia->second; clip_b[a] = &ib->second; first_matrix[a] = (uint32_t)feed.n_matrices;
+        feed.n_matrices += h.n_joints; feed.n_nodes += h.n_nodes; feed.n_channels += (uint64_t)h.n_channels + other.header().n_channels;
+        if (feed.n_matrices >= (1ull << 32) || feed.n_nodes >= (1ull << 32) || feed.instance_rows.size() >= (1ull << 32))
+            return fail(SR_ERR_UNSUPPORTED, "pose_actors_blended: the call holds 2^32 joint matrices, nodes or instance rows or more");
+    }
+    std::vector<SrPoseItem> pose(n_items);
+    feed.item_matrix.assign(n_items, 0xFFFFFFFFu);
+    feed.item_weight_row.assign(n_items, 0xFFFFFFFFu); feed.item_clip_targets.assign(n_items, 0u);
+    for (uint32_t i = 0; i < n_items; i++) {
+        const SrActorPoseItem& it = items[i];
+        const auto prefix = [i]() { return "pose_actors_blended: item " + std::to_string(i) + ": "; };
+        pose[i] = SrPoseItem{it.key, it.weights, nullptr, it.n_targets, 0};
+        if (it.morph && it.weights) return fail(SR_ERR_INVALID_ARG, prefix() + "host weights given together with SR_ACTOR_CLIP_WEIGHTS (one source of weights at most)");
+        if (it.skin == SR_ACTOR_NO_SKIN && !it.morph) continue;
+        if (it.actor >= n_actors) return fail(SR_ERR_INVALID_ARG, prefix() + "actor " + std::to_string(it.actor) + " named, the call has " + std::to_string(n_actors) + " actors");
+        if (it.morph) {                                          // the blended weights of a morph set both clips have, each at its own time
+            const uint32_t blas = it.morph - 1;
+            int k[2];
+            for (int side = 0; side < 2; side++) {
+                const SrClip& clip = (side ? clip_b : clip_a)[it.actor]->host;
+                k[side] = clip.find_morph_set(blas);
+                if (k[side] < 0) return fail(SR_ERR_INVALID_ARG, prefix() + "the weights of blas " + std::to_string(blas) + " named, the actor's clip has no morph set for it");
+                if (clip.morph_sets()[k[side]].state == srd::kClipMorphUnavailable) return fail((int32_t)clip.morph_sets()[k[side]].status, prefix() + clip.morph_errors[k[side]]);
+            }
+            const uint32_t n_targets = clip_a[it.actor]->host.morph_sets()[k[0]].n_targets;
+            if (n_targets != clip_b[it.actor]->host.morph_sets()[k[1]].n_targets)
+                return fail(SR_ERR_INVALID_ARG, prefix() + "the morph sets of blas " + std::to_string(blas) + " have another number of targets in the actor's two clips");
+            const SrClipBlendActor& ac = actors[it.actor];
+            srd::ClipBlendWeightRow row{};
+            row.clip_a = clip_a[it.actor]->d_block.p; row.clip_b = clip_b[it.actor]->d_block.p;
+            row.time_a = ac.time_seconds; row.time_b = ac.time_seconds_b; row.weight = ac.weight;
+            row.set_a = (uint32_t)k[0]; row.set_b = (uint32_t)k[1];
+            feed.item_weight_row[i] = (uint32_t)feed.blend_weight_rows.size(); feed.item_clip_targets[i] = n_targets;
+            feed.blend_weight_rows.push_back(row);
+        }
+        if (it.skin == SR_ACTOR_NO_SKIN) continue;
+        uint32_t first = 0, n_joints = 0;
+        if (sr_clip_skin(&clip_a[it.actor]->host, it.skin, &first, &n_joints) != SR_OK) return fail(SR_ERR_INVALID_ARG, prefix() + "skin " + std::to_string(it.skin) + " named, no instanced mesh of the actor's clip wears it");
+        pose[i].n_joints = n_joints;
+        feed.item_matrix[i] = first_matrix[it.actor] + first;
+    }
+    SrPoseBatchInfo dropped{};                                // sr_scene_pose_batch_info reads as before the call
+    return pose_items(s, pose.data(), n_items, stream, true, &dropped, &feed);
+}
+
+int sr_scene_read_actor_sources(const SrScene* s, uint32_t actor, SrNodeTrs* trs_a, SrNodeTrs* trs_b) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "read_actor_sources: null argument (the scene)");
+    if (!s->actor_sources_kept) return fail(SR_ERR_STATE, "read_actor_sources: the last call kept no sources (sr_scene_pose_actors_blended with SR_ACTORS_KEEP_SOURCES)");
+    if (actor >= s->actor_records.size()) return fail(SR_ERR_INVALID_ARG, "read_actor_sources: actor index out of range");
+    const SrScene::ActorRecord& r = s->actor_records[actor];
+    const int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (trs_a && r.n_nodes) HIP_TRY(hipMemcpy(trs_a, (const SrNodeTrs*)s->d_actor_source_a.p + r.node_base, sizeof(SrNodeTrs) * (size_t)r.n_nodes, hipMemcpyDeviceToHost));
+    if (trs_b && r.n_nodes) HIP_TRY(hipMemcpy(trs_b, (const SrNodeTrs*)s->d_actor_source_b.p + r.node_base, sizeof(SrNodeTrs) * (size_t)r.n_nodes, hipMemcpyDeviceToHost));
+    return SR_OK;
 }
 
 int sr_scene_actor_pose_info(const SrScene* s, SrActorPoseInfo* out) {

@@ -1,5 +1,7 @@
 // Baked clips: the read-outs and the host rule (sr_clip_sample_host, sr_clip_compose_host, sr_clip_pose_host), which
-// restates sr_gltf_pose over the flat tables with the arithmetic of clip_rule.h. No HIP in this file.
+// restates sr_gltf_pose over the flat tables with the arithmetic of clip_rule.h, and the host rule of cross-fades between two clips
+// (sr_clip_blend_compatible, sr_clip_blend_host, sr_clip_compose_records_host, sr_clip_pose_blend_host, sr_clip_blend_weights_host).
+// No HIP in this file.
 #include "clip.h"
 
 #include <cmath>
@@ -77,16 +79,16 @@ int sr_clip_morph_keys(const SrClip* clip, uint32_t blas, const float** times, c
 }
 
 // sr_gltf_morph_weights restated over the baked set: its checks in its order, its statuses and its words.
-int sr_clip_weights_host(const SrClip* clip, float time_seconds, uint32_t blas, float* weights_out, uint32_t n_targets) {
-    if (!clip || (!weights_out && n_targets)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_host: null argument");
+static int weights_of(const SrClip* clip, float time_seconds, uint32_t blas, float* weights_out, uint32_t n_targets, const std::string& who) {
+    if (!clip || (!weights_out && n_targets)) return srh::set_error(SR_ERR_INVALID_ARG, who + ": null argument");
     const int k = clip->find_morph_set(blas);
-    if (k < 0) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_host: the clip has no morph set for this blas (it has no morph targets)");
+    if (k < 0) return srh::set_error(SR_ERR_INVALID_ARG, who + ": the clip has no morph set for this blas (it has no morph targets)");
     const srd::ClipMorphSet& s = clip->morph_sets()[k];
     const bool unavailable = s.state == srd::kClipMorphUnavailable;
-    if (unavailable && s.n_targets == 0) return srh::set_error((int32_t)s.status, "sr_clip_weights_host: " + clip->morph_errors[k]);    // the morph parse itself
-    if (n_targets != s.n_targets) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_host: gltf: another number of weights asked for than the blas has morph targets");
-    if (clip->animation >= 0 && !std::isfinite(time_seconds)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_host: gltf: the time of a pose must be finite");
-    if (unavailable) return srh::set_error((int32_t)s.status, "sr_clip_weights_host: " + clip->morph_errors[k]);
+    if (unavailable && s.n_targets == 0) return srh::set_error((int32_t)s.status, who + ": " + clip->morph_errors[k]);    // the morph parse itself
+    if (n_targets != s.n_targets) return srh::set_error(SR_ERR_INVALID_ARG, who + ": gltf: another number of weights asked for than the blas has morph targets");
+    if (clip->animation >= 0 && !std::isfinite(time_seconds)) return srh::set_error(SR_ERR_INVALID_ARG, who + ": gltf: the time of a pose must be finite");
+    if (unavailable) return srh::set_error((int32_t)s.status, who + ": " + clip->morph_errors[k]);
     if (s.n_keys == 0) { memcpy(weights_out, clip->morph_defaults() + s.first_default, 4 * (size_t)n_targets); return SR_OK; }
     uint32_t i = 0;
     double u = 0.0;
@@ -94,6 +96,10 @@ int sr_clip_weights_host(const SrClip* clip, float time_seconds, uint32_t blas, 
     const float* values = clip->morph_values() + s.first_value;
     for (uint32_t t = 0; t < n_targets; t++) weights_out[t] = srd::clip_weight_at(values, n_targets, i, u, t);
     return SR_OK;
+}
+
+int sr_clip_weights_host(const SrClip* clip, float time_seconds, uint32_t blas, float* weights_out, uint32_t n_targets) {
+    return weights_of(clip, time_seconds, blas, weights_out, n_targets, "sr_clip_weights_host");
 }
 
 int sr_clip_sample_host(const SrClip* clip, float time_seconds, SrNodeTrs* out) {
@@ -112,9 +118,11 @@ int sr_clip_sample_host(const SrClip* clip, float time_seconds, SrNodeTrs* out) 
     return SR_OK;
 }
 
-int sr_clip_compose_host(const SrClip* clip, const SrNodeTrs* trs, const SrTransform* placement, SrTransform* joint_matrices, SrTransform* instance_transforms,
-                         uint32_t* singular_skin) {
-    if (!clip || !trs) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_compose_host: null argument");
+// The composition of both sr_clip_compose_host (a node composes from its TRS where the clip animates it) and
+// sr_clip_compose_records_host (where the record's own mask says so).
+static int compose(const SrClip* clip, const SrNodeTrs* trs, const SrTransform* placement, SrTransform* joint_matrices, SrTransform* instance_transforms,
+                   uint32_t* singular_skin, bool record_masks, const std::string& who) {
+    if (!clip || !trs) return srh::set_error(SR_ERR_INVALID_ARG, who + ": null argument");
     const srd::ClipHeader& h = clip->header();
     if (singular_skin) *singular_skin = 0xFFFFFFFFu;
     std::vector<float> global(16 * (size_t)h.n_nodes);
@@ -122,7 +130,7 @@ int sr_clip_compose_host(const SrClip* clip, const SrNodeTrs* trs, const SrTrans
     srd::clip_identity(ident);
     for (uint32_t n = 0; n < h.n_nodes; n++) {                  // parents come first, level by level
         const srd::ClipNode& c = clip->nodes()[n];
-        if (c.animated) srd::clip_trs_matrix(trs[n].translation, trs[n].rotation, trs[n].scale, local);
+        if (record_masks ? trs[n].animated : c.animated) srd::clip_trs_matrix(trs[n].translation, trs[n].rotation, trs[n].scale, local);
         else memcpy(local, c.matrix, 64);
         srd::clip_mul(c.parent == srd::kClipNoNode ? ident : &global[16 * (size_t)c.parent], local, &global[16 * (size_t)n]);
     }
@@ -149,8 +157,18 @@ int sr_clip_compose_host(const SrClip* clip, const SrNodeTrs* trs, const SrTrans
         }
     }
     if (singular_skin) *singular_skin = bad;
-    if (bad != 0xFFFFFFFFu) return srh::set_error(SR_ERR_UNSUPPORTED, "sr_clip_compose_host: gltf: the transform of the skinned mesh's node is singular");
+    if (bad != 0xFFFFFFFFu) return srh::set_error(SR_ERR_UNSUPPORTED, who + ": gltf: the transform of the skinned mesh's node is singular");
     return SR_OK;
+}
+
+int sr_clip_compose_host(const SrClip* clip, const SrNodeTrs* trs, const SrTransform* placement, SrTransform* joint_matrices, SrTransform* instance_transforms,
+                         uint32_t* singular_skin) {
+    return compose(clip, trs, placement, joint_matrices, instance_transforms, singular_skin, false, "sr_clip_compose_host");
+}
+
+int sr_clip_compose_records_host(const SrClip* clip, const SrNodeTrs* trs, const SrTransform* placement, SrTransform* joint_matrices,
+                                 SrTransform* instance_transforms, uint32_t* singular_skin) {
+    return compose(clip, trs, placement, joint_matrices, instance_transforms, singular_skin, true, "sr_clip_compose_records_host");
 }
 
 int sr_clip_pose_host(const SrClip* clip, float time_seconds, const SrTransform* placement, SrTransform* joint_matrices, SrTransform* instance_transforms) {
@@ -162,6 +180,69 @@ int sr_clip_pose_host(const SrClip* clip, float time_seconds, const SrTransform*
     rc = sr_clip_compose_host(clip, trs.data(), placement, joint_matrices, instance_transforms, nullptr);
     if (rc == SR_ERR_UNSUPPORTED) return srh::set_error(rc, "sr_clip_pose_host: gltf: the transform of the skinned mesh's node is singular");
     return rc;
+}
+
+// ---- cross-fades: the host rule of sr_scene_pose_actors_blended ---------------------------------------------------------------------
+// Two clips blend where everything but their channels and animated masks is equal: in practice, bakes of one file.
+int sr_clip_blend_compatible(const SrClip* a, const SrClip* b) {
+    if (!a || !b) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_blend_compatible: null argument");
+    const auto differ = [](const char* table) { return srh::set_error(SR_ERR_INVALID_ARG, std::string("sr_clip_blend_compatible: the clips differ in ") + table); };
+    const srd::ClipHeader& ha = a->header();
+    const srd::ClipHeader& hb = b->header();
+    if (ha.n_nodes != hb.n_nodes) return differ("the number of nodes");
+    if (ha.n_levels != hb.n_levels || memcmp(a->levels(), b->levels(), 4 * ((size_t)ha.n_levels + 1)) != 0) return differ("the level table");
+    if (ha.n_instances != hb.n_instances || memcmp(a->instances(), b->instances(), 4 * (size_t)ha.n_instances) != 0) return differ("the instance table");
+    for (uint32_t n = 0; n < ha.n_nodes; n++) {
+        const srd::ClipNode& x = a->nodes()[n];
+        const srd::ClipNode& y = b->nodes()[n];
+        if (x.parent != y.parent || x.gltf_node != y.gltf_node || x.level != y.level || memcmp(x.trs, y.trs, 40) != 0 || memcmp(x.matrix, y.matrix, 64) != 0)
+            return differ("the node table");
+    }
+    if (ha.n_skins != hb.n_skins || memcmp(a->skins(), b->skins(), sizeof(srd::ClipSkin) * (size_t)ha.n_skins) != 0) return differ("the skin table");
+    if (ha.n_joints != hb.n_joints || memcmp(a->joint_nodes(), b->joint_nodes(), 4 * (size_t)ha.n_joints) != 0) return differ("the joint nodes");
+    if (memcmp(a->joint_skins(), b->joint_skins(), 4 * (size_t)ha.n_joints) != 0) return differ("the joint skins");
+    if (memcmp(a->inverse_bind(), b->inverse_bind(), 48 * (size_t)ha.n_joints) != 0) return differ("the inverse bind matrices");
+    return SR_OK;
+}
+
+static bool blend_weight_ok(float weight) { return weight >= 0.0f && weight <= 1.0f; }     // false for a NaN
+
+int sr_clip_blend_host(const SrNodeTrs* trs_a, const SrNodeTrs* trs_b, uint32_t n_nodes, float weight, SrNodeTrs* out) {
+    if (n_nodes && (!trs_a || !trs_b || !out)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_blend_host: null argument");
+    if (!blend_weight_ok(weight)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_blend_host: the weight is not in [0, 1]");
+    for (uint32_t n = 0; n < n_nodes; n++) {
+        uint32_t a[srd::kClipTrsWords], b[srd::kClipTrsWords], r[srd::kClipTrsWords];
+        memcpy(a, &trs_a[n], sizeof(a)); memcpy(b, &trs_b[n], sizeof(b));
+        srd::clip_blend_record(a, b, (double)weight, r);
+        memcpy(&out[n], r, sizeof(r));
+    }
+    return SR_OK;
+}
+
+int sr_clip_pose_blend_host(const SrClip* a, float time_a, const SrClip* b, float time_b, float weight, const SrTransform* placement,
+                            SrTransform* joint_matrices, SrTransform* instance_transforms) {
+    if (!a || !b) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_pose_blend_host: null argument");
+    if ((a->animation >= 0 && !std::isfinite(time_a)) || (b->animation >= 0 && !std::isfinite(time_b)))
+        return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_pose_blend_host: gltf: the time of a pose must be finite");
+    if (!blend_weight_ok(weight)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_pose_blend_host: the weight is not in [0, 1]");
+    int rc = sr_clip_blend_compatible(a, b);
+    if (rc != SR_OK) return rc;
+    const uint32_t n = a->header().n_nodes;
+    std::vector<SrNodeTrs> ta(n), tb(n), blended(n);
+    if ((rc = sr_clip_sample_host(a, time_a, ta.data())) != SR_OK || (rc = sr_clip_sample_host(b, time_b, tb.data())) != SR_OK) return rc;
+    if ((rc = sr_clip_blend_host(ta.data(), tb.data(), n, weight, blended.data())) != SR_OK) return rc;
+    return compose(a, blended.data(), placement, joint_matrices, instance_transforms, nullptr, true, "sr_clip_pose_blend_host");
+}
+
+int sr_clip_blend_weights_host(const SrClip* a, float time_a, const SrClip* b, float time_b, float weight, uint32_t blas, float* weights_out, uint32_t n_targets) {
+    if (!a || !b || (!weights_out && n_targets)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_blend_weights_host: null argument");
+    if (!blend_weight_ok(weight)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_blend_weights_host: the weight is not in [0, 1]");
+    std::vector<float> wa(n_targets), wb(n_targets);
+    int rc;
+    if ((rc = weights_of(a, time_a, blas, wa.data(), n_targets, "sr_clip_blend_weights_host")) != SR_OK) return rc;
+    if ((rc = weights_of(b, time_b, blas, wb.data(), n_targets, "sr_clip_blend_weights_host")) != SR_OK) return rc;
+    for (uint32_t t = 0; t < n_targets; t++) weights_out[t] = srd::clip_blend_weight(wa[t], wb[t], (double)weight);
+    return SR_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Baked clips: the flat tables of a clip and the arithmetic of its evaluation, shared by the host rule (clip_host.cpp) and the
-// device kernel (clip_pose.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
+// device kernels (clip_pose.hip, clip_weights.hip, clip_blend.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
 // (gltf_load.cpp) term for term; host and device are built with -ffp-contract=off, so +, -, *, / and sqrt give the same bits on
 // both. atan2 and sin (interpolated rotations only) come from each side's own libm.
 // No HIP here beyond the function qualifiers.
@@ -80,6 +80,29 @@ struct ClipWeightRow {
 };
 static_assert(sizeof(ClipWeightRow) == 32, "two 16-byte pieces");
 
+// One actor of a blended call as clip_blend_kernel reads it, at wave-uniform addresses: two compatible clips (equal tables but
+// the channels and the animated masks), each at its own time, and the share of B.
+struct ClipBlendActorRow {
+    const void* clip_a;         // device: the blocks of the two sources
+    const void* clip_b;
+    float time_a, time_b, weight;
+    uint32_t flags;             // as ClipActorRow.flags
+    uint32_t matrix_base, instance_base, rows_base, node_base;      // as ClipActorRow's
+    float placement[12];
+};
+static_assert(sizeof(ClipBlendActorRow) == 96, "six 16-byte pieces");
+
+// One clip-weighted item of a blended call as clip_blend_weights_kernel reads it, at wave-uniform addresses.
+struct ClipBlendWeightRow {
+    const void* clip_a;         // device: the blocks of the two sources
+    const void* clip_b;
+    float time_a, time_b, weight;
+    uint32_t set_a;             // position in A's morph sets
+    uint32_t set_b;             // position in B's morph sets (equal n_targets)
+    uint32_t active_base, item, check_word;                         // as ClipWeightRow's
+};
+static_assert(sizeof(ClipBlendWeightRow) == 48, "three 16-byte pieces");
+
 // The key search of sample_channel / morph_weights: the key `i` at or before `time` (clamped to the first / last key) and the
 // fraction `u` towards key i + 1 (0: take key i as it is).
 SR_CLIP_HD void clip_key_search(const float* times, uint32_t n, uint32_t interpolation, double time, uint32_t* key, double* fraction) {
@@ -145,6 +168,49 @@ SR_CLIP_HD void clip_sample_channel(const float* times, const float* values, uin
         clip_normalise(r);
     }
     for (int c = 0; c < 4; c++) out[c] = (float)r[c];
+}
+
+// The cross-fade of two sampled records (SrNodeTrs as twelve words: t[3] q[4] s[3], the animated mask, 0) at the share `w` of B,
+// 0 <= w <= 1. Only + - * / and sqrt, in double from the fp32 values and rounded once: no libm, so host and device give the
+// same bits without exception.
+//   w == 0: A's record, whole, its mask included; w == 1: B's record, whole. Otherwise the mask is A's | B's; where that is 0 the
+//   record is A's and the node keeps composing from the file's matrix. Where it is not, each of translation, rotation and scale
+//   is taken whole: a part whose bytes are equal in both records is copied (a clip blended with itself at one time is the
+//   identity at every weight); otherwise translation and scale are (float)(a + w * (b - a)), and the rotation is a normalised
+//   lerp along the shorter arc: b negated where dot(a, b) < 0, r = a + w * (b - a), clip_normalise(r). nlerp and not slerp, on
+//   purpose: it keeps atan2 and sin out of the stage.
+// A node's local matrix comes from its TRS where the record's mask is not 0 and from the file's matrix otherwise. A node the file
+// gives by `matrix` that only one of the clips animates therefore jumps between that matrix and the glTF default TRS at the end
+// weights; glTF forbids animating such nodes.
+SR_CLIP_HD float clip_word_float(uint32_t v) { float f; __builtin_memcpy(&f, &v, 4); return f; }
+SR_CLIP_HD uint32_t clip_float_word(float f) { uint32_t v; __builtin_memcpy(&v, &f, 4); return v; }
+SR_CLIP_HD void clip_blend_record(const uint32_t* a, const uint32_t* b, double w, uint32_t* out) {
+    const uint32_t mask = a[10] | b[10];
+    if (w == 0.0 || w == 1.0 || mask == 0u) {
+        const uint32_t* src = w == 1.0 ? b : a;
+        for (int i = 0; i < 12; i++) out[i] = src[i];
+        return;
+    }
+    const int first[3] = {0, 3, 7}, count[3] = {3, 4, 3};
+    for (int part = 0; part < 3; part++) {
+        const int at = first[part], n = count[part];
+        bool equal = true;
+        for (int c = 0; c < n; c++) equal = equal && a[at + c] == b[at + c];
+        if (equal) { for (int c = 0; c < n; c++) out[at + c] = a[at + c]; continue; }
+        double x[4] = {0, 0, 0, 0}, y[4] = {0, 0, 0, 0}, r[4];
+        for (int c = 0; c < n; c++) { x[c] = (double)clip_word_float(a[at + c]); y[c] = (double)clip_word_float(b[at + c]); }
+        if (part == 1 && x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3] < 0.0) for (int c = 0; c < 4; c++) y[c] = -y[c];
+        for (int c = 0; c < 4; c++) r[c] = x[c] + w * (y[c] - x[c]);
+        if (part == 1) clip_normalise(r);
+        for (int c = 0; c < n; c++) out[at + c] = clip_float_word((float)r[c]);
+    }
+    out[10] = mask; out[11] = a[11];
+}
+// One morph weight of a cross-fade from the two sources' weights: the same form.
+SR_CLIP_HD float clip_blend_weight(float wa, float wb, double w) {
+    if (w == 0.0 || clip_float_word(wa) == clip_float_word(wb)) return wa;
+    if (w == 1.0) return wb;
+    return (float)((double)wa + w * ((double)wb - (double)wa));
 }
 
 // trs_matrix: translation * rotation * scale, fp32, row-major 4x4.

@@ -702,6 +702,14 @@ int sr_renderer_pose_actors(SrRenderer* r, const SrClipActor* actors, uint32_t n
                              [&](SrScene* sc) { return sr_scene_pose_actors(sc, actors, n_actors, items, n_items, d_instance_transforms, flags, stream); });
 }
 
+int sr_renderer_pose_actors_blended(SrRenderer* r, const SrClipBlendActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
+                                    SrTransform* d_instance_transforms, uint32_t flags, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "pose_actors_blended: null argument (the renderer)");
+    if (n_items && !items) return rfail(SR_ERR_INVALID_ARG, "pose_actors_blended: null argument (actors or items, with a count > 0)");
+    return first_scene_poses(r, n_items, [&](uint32_t k) { return items[k].key; },
+                             [&](SrScene* sc) { return sr_scene_pose_actors_blended(sc, actors, n_actors, items, n_items, d_instance_transforms, flags, stream); });
+}
+
 int sr_renderer_actor_pose_info(const SrRenderer* r, SrActorPoseInfo* out) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_actor_pose_info: null argument (the renderer)");
     return sr_scene_actor_pose_info(r->slot[0].scene, out);

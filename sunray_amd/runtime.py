@@ -207,30 +207,40 @@ class ActorArgs:
     may be None where neither a skin nor ClipWeights names it). set_times() rewrites the times in place, so a crowd's per-frame
     work on the host is that and the call."""
 
+    WHO, ROW = "pose_actors", abi.SrClipActor
+
     def __init__(self, actors, items):
         actors, items = [tuple(a) for a in actors], [tuple(i) for i in items]
-        self.actors, self.items, self.keep = (abi.SrClipActor * max(len(actors), 1))(), (abi.SrActorPoseItem * max(len(items), 1))(), []
+        self.actors, self.items, self.keep = (self.ROW * max(len(actors), 1))(), (abi.SrActorPoseItem * max(len(items), 1))(), []
         self.n_actors, self.n_items = len(actors), len(items)
         for a, ac in enumerate(actors):
-            if len(ac) != 5:
-                raise ValueError("pose_actors: actor %d: an actor is (clip id, time, placement, instance rows, instance base), %d values given" % (a, len(ac)))
-            row = self.actors[a]
-            row.clip_id, row.time_seconds, row.instance_base = int(ac[0]), float(ac[1]), int(ac[4])
-            if ac[2] is not None:
-                m = np.ascontiguousarray(ac[2])
-                if m.dtype not in (np.dtype(np.float32), abi.TRANSFORM) or m.nbytes != 48:
-                    raise ValueError("pose_actors: actor %d: the placement must be 12 float32 (row-major 3x4)" % a)
-                self.keep.append(m)
-                row.placement = m.ctypes.data
-            if ac[3] is not None:
-                r = np.ascontiguousarray(ac[3])
-                if r.dtype != np.dtype(np.uint32) or r.ndim != 1:
-                    raise ValueError("pose_actors: actor %d: the instance rows must be a one-dimensional numpy uint32 array" % a)
-                self.keep.append(r)
-                row.instance_rows = r.ctypes.data if len(r) else None
+            self._actor(a, ac, self.actors[a])
+        self._items(items)
+
+    def _actor(self, a, ac, row):
+        if len(ac) != 5:
+            raise ValueError("pose_actors: actor %d: an actor is (clip id, time, placement, instance rows, instance base), %d values given" % (a, len(ac)))
+        row.clip_id, row.time_seconds, row.instance_base = int(ac[0]), float(ac[1]), int(ac[4])
+        self._placed(a, row, ac[2], ac[3])
+
+    def _placed(self, a, row, placement, rows):
+        if placement is not None:
+            m = np.ascontiguousarray(placement)
+            if m.dtype not in (np.dtype(np.float32), abi.TRANSFORM) or m.nbytes != 48:
+                raise ValueError("%s: actor %d: the placement must be 12 float32 (row-major 3x4)" % (self.WHO, a))
+            self.keep.append(m)
+            row.placement = m.ctypes.data
+        if rows is not None:
+            r = np.ascontiguousarray(rows)
+            if r.dtype != np.dtype(np.uint32) or r.ndim != 1:
+                raise ValueError("%s: actor %d: the instance rows must be a one-dimensional numpy uint32 array" % (self.WHO, a))
+            self.keep.append(r)
+            row.instance_rows = r.ctypes.data if len(r) else None
+
+    def _items(self, items):
         for i, it in enumerate(items):
             if len(it) != 4:
-                raise ValueError("pose_actors: item %d: an item is (key, actor, skin, weights), %d values given" % (i, len(it)))
+                raise ValueError("%s: item %d: an item is (key, actor, skin, weights), %d values given" % (self.WHO, i, len(it)))
             row = self.items[i]
             row.key, row.actor, row.skin = int(it[0]), 0 if it[1] is None else int(it[1]), abi.ACTOR_NO_SKIN if it[2] is None else int(it[2])
             if isinstance(it[3], ClipWeights):
@@ -239,7 +249,7 @@ class ActorArgs:
                 try:
                     w, nt = _morph_weights(it[3])
                 except ValueError as e:
-                    raise ValueError("pose_actors: item %d: %s" % (i, e))
+                    raise ValueError("%s: item %d: %s" % (self.WHO, i, e))
                 self.keep.append(w)
                 row.weights, row.n_targets = w.ctypes.data, nt
 
@@ -248,18 +258,38 @@ class ActorArgs:
             self.actors[a].time_seconds = float(t)
 
 
-def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index):
-    args = actors if isinstance(actors, ActorArgs) else ActorArgs(actors, items)
+class BlendedActorArgs(ActorArgs):
+    """The arguments of pose_actors_blended packed once: ActorArgs with `actors` a sequence of (clip id a, time a, clip id b,
+    time b, weight: the share of b in [0, 1], placement, instance rows, instance base). set_times() rewrites A's times,
+    set_fades() B's times and the weights."""
+    WHO, ROW = "pose_actors_blended", abi.SrClipBlendActor
+
+    def _actor(self, a, ac, row):
+        if len(ac) != 8:
+            raise ValueError("pose_actors_blended: actor %d: an actor is (clip id a, time a, clip id b, time b, weight, placement, instance rows, instance base), "
+                             "%d values given" % (a, len(ac)))
+        row.clip_id, row.time_seconds, row.clip_id_b, row.time_seconds_b, row.weight, row.instance_base = int(ac[0]), float(ac[1]), int(ac[2]), float(ac[3]), float(ac[4]), int(ac[7])
+        self._placed(a, row, ac[5], ac[6])
+
+    def set_fades(self, times_b, weights):
+        for a, (t, w) in enumerate(zip(times_b, weights)):
+            self.actors[a].time_seconds_b, self.actors[a].weight = float(t), float(w)
+
+
+def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index, keep_sources=False, packed=ActorArgs):
+    if isinstance(actors, ActorArgs) and type(actors) is not packed:
+        raise ValueError("%s: the packed arguments are those of another entry point (%s)" % (packed.WHO, type(actors).__name__))
+    args = actors if isinstance(actors, packed) else packed(actors, items)
     ptr, stream = None, None
     if tensor is not None:
         import torch
         if not getattr(tensor, "is_cuda", False) or tensor.device.index != device_index:
-            raise ValueError("pose_actors: the instance transforms must be a tensor on cuda:%d" % device_index)
+            raise ValueError("%s: the instance transforms must be a tensor on cuda:%d" % (packed.WHO, device_index))
         if str(tensor.dtype) != "torch.float32" or not tensor.is_contiguous() or tensor.numel() % 12:
-            raise ValueError("pose_actors: the instance transforms must be contiguous float32, 12 a transform")
+            raise ValueError("%s: the instance transforms must be contiguous float32, 12 a transform" % packed.WHO)
         ptr, stream = C.c_void_p(tensor.data_ptr()), C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)
     check(fn(handle, args.actors, C.c_uint32(args.n_actors), args.items, C.c_uint32(args.n_items), ptr,
-             C.c_uint32(abi.ACTORS_KEEP_NODES if keep_nodes else 0), stream))
+             C.c_uint32((abi.ACTORS_KEEP_NODES if keep_nodes else 0) | (abi.ACTORS_KEEP_SOURCES if keep_sources else 0)), stream))
 
 
 class Clip:
@@ -346,7 +376,7 @@ class Clip:
         check(lib().sr_clip_sample_host(self._h, C.c_float(time_seconds), _p(trs)))
         return trs[:self.info.n_nodes]
 
-    def compose_host(self, trs, placement=None):
+    def compose_host(self, trs, placement=None, fn=None):
         """abi.NODE_TRS records -> (joint matrices of all skins [n_joints, 12], instance transforms [n_instances, 12], the lowest
         singular skin or None). A singular skin is reported, not raised (sr_clip_compose_host)."""
         i = self.info
@@ -355,10 +385,40 @@ class Clip:
             raise ValueError("compose_host: %d records given, the clip has %d nodes" % (len(trs), i.n_nodes))
         joints, xf, bad = np.zeros((max(i.n_joints, 1), 12), np.float32), np.zeros((max(i.n_instances, 1), 12), np.float32), C.c_uint32()
         pl = None if placement is None else np.ascontiguousarray(placement, dtype=np.float32).reshape(12)
-        rc = lib().sr_clip_compose_host(self._h, _p(trs), None if pl is None else _p(pl), _p(joints), _p(xf), C.byref(bad))
+        rc = (fn or lib().sr_clip_compose_host)(self._h, _p(trs), None if pl is None else _p(pl), _p(joints), _p(xf), C.byref(bad))
         if rc != 0 and bad.value == 0xFFFFFFFF:
             check(rc)
         return joints[:i.n_joints], xf[:i.n_instances], (None if bad.value == 0xFFFFFFFF else bad.value)
+
+    def blend_compatible(self, other):
+        """Raises unless this clip and `other` may be cross-faded: equal tables but the channels and the animated masks, in
+        practice bakes of one file (sr_clip_blend_compatible)."""
+        check(lib().sr_clip_blend_compatible(self._h, other._h))
+        return True
+
+    def compose_records_host(self, trs, placement=None):
+        """compose_host with each node's TRS-or-matrix decision taken from the record's own `animated` word, as blended records
+        need it (sr_clip_compose_records_host)."""
+        return self.compose_host(trs, placement, fn=lib().sr_clip_compose_records_host)
+
+    def pose_blend_host(self, time_seconds, other, time_other, weight, placement=None, joints=True):
+        """-> (joint matrices or None, instance transforms) of the cross-fade from this clip at `time_seconds` to `other` at
+        `time_other`, at the share `weight` of `other`: sample, sample, blend, compose (sr_clip_pose_blend_host)."""
+        i = self.info
+        jm = np.zeros((max(i.n_joints, 1), 12), np.float32) if joints else None
+        xf = np.zeros((max(i.n_instances, 1), 12), np.float32)
+        pl = None if placement is None else np.ascontiguousarray(placement, dtype=np.float32).reshape(12)
+        check(lib().sr_clip_pose_blend_host(self._h, C.c_float(time_seconds), other._h, C.c_float(time_other), C.c_float(weight), None if pl is None else _p(pl),
+                                            None if jm is None else _p(jm), _p(xf)))
+        return (None if jm is None else jm[:i.n_joints]), xf[:i.n_instances]
+
+    def blend_weights_host(self, time_seconds, other, time_other, weight, blas, n_targets=None):
+        """-> the blended weights [n_targets] float32 of the blas's morph set, which both clips must have
+        (sr_clip_blend_weights_host)."""
+        nt = self.morph(blas)["n_targets"] if n_targets is None else int(n_targets)
+        w = np.zeros(max(nt, 1), dtype=np.float32)
+        check(lib().sr_clip_blend_weights_host(self._h, C.c_float(time_seconds), other._h, C.c_float(time_other), C.c_float(weight), C.c_uint32(blas), _p(w), C.c_uint32(nt)))
+        return w[:nt]
 
     def pose_host(self, time_seconds, placement=None, joints=True):
         """-> (joint matrices of all skins [n_joints, 12] or None, instance transforms [n_instances, 12]) at `time_seconds`:
@@ -369,6 +429,16 @@ class Clip:
         pl = None if placement is None else np.ascontiguousarray(placement, dtype=np.float32).reshape(12)
         check(lib().sr_clip_pose_host(self._h, C.c_float(time_seconds), None if pl is None else _p(pl), None if jm is None else _p(jm), _p(xf)))
         return (None if jm is None else jm[:i.n_joints]), xf[:i.n_instances]
+
+
+def clip_blend_host(trs_a, trs_b, weight):
+    """abi.NODE_TRS records of two sources -> the blended records at the share `weight` of the second (sr_clip_blend_host)."""
+    a, b = np.ascontiguousarray(trs_a, dtype=abi.NODE_TRS), np.ascontiguousarray(trs_b, dtype=abi.NODE_TRS)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError("clip_blend_host: the two sources must hold the same number of records")
+    out = np.zeros(max(len(a), 1), abi.NODE_TRS)
+    check(lib().sr_clip_blend_host(_p(a) if len(a) else None, _p(b) if len(b) else None, C.c_uint32(len(a)), C.c_float(weight), _p(out)))
+    return out[:len(a)]
 
 
 def pose_batch_plan(n_vertices):
@@ -658,6 +728,19 @@ class Scene:
         them (or an ActorArgs), `tensor` a float32 torch tensor on the scene's device that takes the instance transforms at the
         actors' rows, or None (sr_scene_pose_actors)."""
         _actor_call(lib().sr_scene_pose_actors, self._h, actors, items, tensor, keep_nodes, self.device_index)
+
+    def pose_actors_blended(self, actors, items=(), tensor=None, keep_nodes=False, keep_sources=False):
+        """pose_actors for actors that cross-fade between two attached clips: `actors` as BlendedActorArgs takes them (or a
+        BlendedActorArgs), the rest as pose_actors; keep_sources also stores both sources' sampled TRS for read_actor_sources
+        (sr_scene_pose_actors_blended)."""
+        _actor_call(lib().sr_scene_pose_actors_blended, self._h, actors, items, tensor, keep_nodes, self.device_index, keep_sources, BlendedActorArgs)
+
+    def read_actor_sources(self, actor, n_nodes):
+        """-> (abi.NODE_TRS [n_nodes], abi.NODE_TRS [n_nodes]): both sources' sampled TRS of an actor of the last
+        pose_actors_blended with keep_sources (sr_scene_read_actor_sources)."""
+        a, b = np.zeros(max(n_nodes, 1), abi.NODE_TRS), np.zeros(max(n_nodes, 1), abi.NODE_TRS)
+        check(lib().sr_scene_read_actor_sources(self._h, C.c_uint32(actor), _p(a), _p(b)))
+        return a[:n_nodes], b[:n_nodes]
 
     def actor_pose_info(self):
         """-> abi.SrActorPoseInfo: the last pose_actors that reached the device (sr_scene_actor_pose_info)."""
@@ -1563,6 +1646,10 @@ class Renderer:
         """Scene.pose_actors on the first device slot; every further slot takes each item's posed vertices by a device copy.
         `tensor` lives on the first slot's GPU: render_device_transforms takes it from there (sr_renderer_pose_actors)."""
         _actor_call(lib().sr_renderer_pose_actors, self._h, actors, items, tensor, keep_nodes, self.devices[0])
+
+    def pose_actors_blended(self, actors, items=(), tensor=None, keep_nodes=False, keep_sources=False):
+        """Scene.pose_actors_blended on the first device slot, as pose_actors (sr_renderer_pose_actors_blended)."""
+        _actor_call(lib().sr_renderer_pose_actors_blended, self._h, actors, items, tensor, keep_nodes, self.devices[0], keep_sources, BlendedActorArgs)
 
     def actor_pose_info(self):
         info = abi.SrActorPoseInfo()
