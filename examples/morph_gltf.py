@@ -4,7 +4,7 @@ frame Renderer.pose_scene samples the joint and the weight channels, blends the 
 library's kernels (morph first, then skin; the posed vertices never visit the host) and returns the instance transforms for the
 frame. Writes the last frame as a PNG.
 
-    python examples/morph_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out morph.png] [--device-lights] [--device-clips]
+    python examples/morph_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out morph.png] [--device-lights] [--device-clips] [--cubicspline]
 
 --device-lights: the frame's light table is built on the device (Renderer.set_light_table_build("device")), so that a posed mesh
 with an emissive material never visits the host either.
@@ -12,6 +12,9 @@ with an emissive material never visits the host either.
 --device-clips: the animation is baked once (Gltf.bake_clip) and attached, and every frame is one Renderer.pose_actors: the GPU samples
 the joint channels and the weight channels of the clip (ClipWeights), so neither the joint matrices, nor the morph weights, nor the
 instance transforms come from host memory. A mesh whose weight channel the loader refuses (CUBICSPLINE) is left unmorphed.
+
+--cubicspline: CUBICSPLINE samplers are sampled instead of refused (Gltf.set_cubicspline, before anything is posed or baked):
+--animation 1 --cubicspline plays the fixture's "spline" animation, on either path.
 
 Default file: tests/golden/morph_bar.glb. Needs a GPU: the product path has no CPU fallback.
 """
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--out", default="morph.png")
     ap.add_argument("--camera", default="0.8,1.4,7.0,0.8,1.0,0.0,45", help="position, target, vertical field of view in degrees")
     ap.add_argument("--device-lights", action="store_true")
+    ap.add_argument("--cubicspline", action="store_true", help="sample CUBICSPLINE animation samplers (Gltf.set_cubicspline) instead of refusing them; animation 1 of the fixture has one")
     ap.add_argument("--device-clips", action="store_true")
     ap.add_argument("--batch-trees", action="store_true", help="build the small meshes' trees in one batched device launch when their ninth update asks for a fast build")
     args = ap.parse_args()
@@ -42,6 +46,8 @@ def main():
     c = [float(v) for v in args.camera.split(",")]
     camera = (tuple(c[0:3]), tuple(c[3:6]), c[6])
     gltf = rt.Gltf(args.file)
+    if args.cubicspline:                             # before anything is posed or baked
+        gltf.set_cubicspline(True)
     n_skins, n_animations = gltf.rig_counts()
     if not 0 <= args.animation < n_animations:
         sys.exit("%s has %d animation(s); --animation %d is not one of them" % (args.file, n_animations, args.animation))

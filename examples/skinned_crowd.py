@@ -10,7 +10,10 @@ matrices where the posing kernel reads them and the instance transforms into a t
 With --device-clips --crossfade SECONDS every copy fades from the file's static pose into its clip over the first SECONDS of the
 run, on the GPU as well: both are baked and attached, and a frame calls Renderer.pose_actors_blended with the clip's share so far.
 
-    python examples/skinned_crowd.py [--copies 64] [--frames 24] [--size 640x480] [--out crowd.png] [--device-clips [--crossfade SECONDS]]
+    python examples/skinned_crowd.py [--copies 64] [--frames 24] [--size 640x480] [--out crowd.png] [--device-clips [--crossfade SECONDS]] [--animation 1 --cubicspline]
+
+With --cubicspline the file's CUBICSPLINE samplers are sampled instead of refused (Gltf.set_cubicspline, before anything is posed
+or baked): --animation 1 --cubicspline plays the fixture's "spline" animation, on either path.
 
 Needs a GPU: the product path has no CPU fallback.
 """
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--size", default="640x480")
     ap.add_argument("--out", default="crowd.png")
     ap.add_argument("--device-clips", action="store_true", help="evaluate the animation on the GPU from a baked clip")
+    ap.add_argument("--animation", type=int, default=0)
+    ap.add_argument("--cubicspline", action="store_true", help="sample CUBICSPLINE animation samplers (Gltf.set_cubicspline) instead of refusing them; animation 1 of the fixture has one")
     ap.add_argument("--crossfade", type=float, default=0.0, metavar="SECONDS", help="with --device-clips: fade every copy from the static pose into its clip")
     args = ap.parse_args()
     if args.crossfade and not args.device_clips:
@@ -39,7 +44,9 @@ def main():
     from sunray_amd import runtime as rt
     w, h = (int(v) for v in args.size.split("x"))
     gltf = rt.Gltf(os.path.join(os.path.dirname(HERE), "tests", "golden", "skinned_bar.glb"))
-    name, duration, _, _ = gltf.animation(0)
+    if args.cubicspline:                             # before anything is posed or baked
+        gltf.set_cubicspline(True)
+    name, duration, _, _ = gltf.animation(args.animation)
     skinned = [(b, gltf.blas_skin(b)[0]) for b in range(gltf.n_blases) if gltf.blas_skin(b)[0] >= 0]
     r = rt.Renderer((w, h))
     r.set_mesh_tree_build("device")
@@ -60,8 +67,8 @@ def main():
         for c, (loaded, dx, dz) in enumerate(copies):
             t = (duration * f / max(args.frames - 1, 1) + duration * c / args.copies) % duration       # every copy at its own time
             for b, skin in skinned:
-                items.append((int(loaded.keys[b]), None, gltf.pose(0, t, skin)[1]))
-            xf = gltf.pose(0, t)[0].copy()
+                items.append((int(loaded.keys[b]), None, gltf.pose(args.animation, t, skin)[1]))
+            xf = gltf.pose(args.animation, t)[0].copy()
             xf[:, 3] += dx
             xf[:, 11] += dz
             instances += loaded.grouped(xf)
@@ -78,7 +85,7 @@ def device_clips(args, rt, gltf, r, copies, skinned, duration, camera):
     """The frames of --device-clips: bake once, attach once; per frame the times, one pose_actors, one render."""
     import numpy as np
     import torch
-    clip = gltf.bake_clip(0)
+    clip = gltf.bake_clip(args.animation)
     cid = r.attach_clip(clip)
     n = copies[0][0].n_transforms
     layout, actors, items = [], [], []

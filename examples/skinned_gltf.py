@@ -3,10 +3,13 @@ Renderer.attach_skins gives every skinned mesh its bind pose and influences, and
 animation, skins the meshes with the library's kernel (the posed vertices never visit the host) and returns the instance
 transforms for the frame. Writes the last frame as a PNG.
 
-    python examples/skinned_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out skinned.png] [--device-lights]
+    python examples/skinned_gltf.py [file.glb] [--animation 0] [--frames 48] [--size 640x480] [--out skinned.png] [--device-lights] [--cubicspline]
 
 --device-lights: the frame's light table is built on the device (Renderer.set_light_table_build("device")), so that a skinned
 mesh with an emissive material never visits the host either.
+
+--cubicspline: CUBICSPLINE samplers are sampled instead of refused (Gltf.set_cubicspline, before anything is posed):
+--animation 1 --cubicspline plays the fixture's "spline" animation.
 
 Default file: tests/golden/skinned_bar.glb. Needs a GPU: the product path has no CPU fallback.
 """
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--out", default="skinned.png")
     ap.add_argument("--camera", default="0.8,1.4,7.0,0.8,1.0,0.0,45", help="position, target, vertical field of view in degrees")
     ap.add_argument("--device-lights", action="store_true")
+    ap.add_argument("--cubicspline", action="store_true", help="sample CUBICSPLINE animation samplers (Gltf.set_cubicspline) instead of refusing them; animation 1 of the fixture has one")
     ap.add_argument("--batch-trees", action="store_true", help="build the small meshes' trees in one batched device launch when their ninth update asks for a fast build")
     args = ap.parse_args()
     from sunray_amd import runtime as rt
@@ -36,6 +40,8 @@ def main():
     c = [float(v) for v in args.camera.split(",")]
     camera = (tuple(c[0:3]), tuple(c[3:6]), c[6])
     gltf = rt.Gltf(args.file)
+    if args.cubicspline:                             # before anything is posed or baked
+        gltf.set_cubicspline(True)
     n_skins, n_animations = gltf.rig_counts()
     if not 0 <= args.animation < n_animations:
         sys.exit("%s has %d animation(s); --animation %d is not one of them" % (args.file, n_animations, args.animation))

@@ -1199,12 +1199,32 @@ int sr_gltf_skin(const SrGltf* gltf, uint32_t i, uint32_t* n_joints, const SrTra
  * them): sr_gltf_animation_ignored_channels counts them. */
 int sr_gltf_animation(const SrGltf* gltf, uint32_t i, const char** name, float* duration_seconds, uint32_t* n_channels);
 int sr_gltf_animation_ignored_channels(const SrGltf* gltf, uint32_t i, uint32_t* n_weights_channels);
+/* CUBICSPLINE samplers, per opened file. SR_CUBICSPLINE_REFUSE (the default) answers them as ever: sr_gltf_pose,
+ * sr_gltf_sample_node, sr_gltf_morph_weights and sr_gltf_bake_clip return SR_ERR_UNSUPPORTED, and a cubic `weights` channel makes
+ * a clip's morph set SR_CLIP_MORPH_UNAVAILABLE. Under SR_CUBICSPLINE_SAMPLE the four calls sample them (the rule: sr_gltf_pose).
+ * The mode is read where a call meets such a sampler; what the file's animations parsed to does not depend on it, so it may be
+ * switched back and forth. A clip keeps what it was baked with. No environment variable selects it. Another value:
+ * SR_ERR_INVALID_ARG. sr_gltf_animation_cubic: how many translation / rotation / scale channels and how many `weights` channels
+ * of animation i name a CUBICSPLINE sampler (either may be NULL), in either mode: 0 and 0 where the animation needs no mode. */
+#define SR_CUBICSPLINE_REFUSE 0u
+#define SR_CUBICSPLINE_SAMPLE 1u
+int sr_gltf_set_cubicspline(SrGltf* gltf, uint32_t mode);
+int sr_gltf_cubicspline(const SrGltf* gltf, uint32_t* mode);
+int sr_gltf_animation_cubic(const SrGltf* gltf, uint32_t i, uint32_t* n_cubic_trs_channels, uint32_t* n_cubic_weights_channels);
 /* The file's nodes at `time_seconds` of animation `animation` (-1: the file's static pose, time ignored): the world transform
  * of every instance of sr_gltf_instance, in its order, into instance_transforms (n_instances, may be NULL), and the joint matrices
  * of skin `skin` into joint_matrices (that skin's n_joints, may be NULL; `skin` is not looked at then).
  * Sampling: every translation / rotation / scale channel at time_seconds clamped to its sampler's first / last key; STEP and LINEAR
  * (rotations: spherical linear interpolation along the shorter arc between the normalised keys, the result normalised), computed
- * in double from the fp32 keys and rounded once to fp32 TRS; a CUBICSPLINE sampler anywhere in the animation: SR_ERR_UNSUPPORTED.
+ * in double from the fp32 keys and rounded once to fp32 TRS; a CUBICSPLINE sampler anywhere in the animation: SR_ERR_UNSUPPORTED,
+ * unless sr_gltf_set_cubicspline(gltf, SR_CUBICSPLINE_SAMPLE) has been called. Then a cubic sampler, whose output holds per key
+ * an in-tangent a_k, a value v_k and an out-tangent b_k, is sampled between keys i and i + 1 at u = (time - t_i) / td,
+ * td = t_{i+1} - t_i, per component as
+ *   u2 = u*u; u3 = u2*u;  h00 = (2*u3 - 3*u2) + 1;  h10 = (u3 - 2*u2) + u;  h01 = 3*u2 - 2*u3;  h11 = u3 - u2;
+ *   r = ((h00*v_i + h10*(td*b_i)) + h01*v_{i+1}) + h11*(td*a_{i+1})
+ * in double with this grouping, rounded once; at a key, below the first and above the last (u == 0) r is the key's value. The
+ * keys of a cubic rotation are taken as the file gives them, neither normalised nor sign-flipped; r is normalised in every case,
+ * and a zero r stays zero, which composes as the identity rotation.
  * Composition: a node with an animated channel composes from its TRS (the file's, or the glTF defaults) even if the file gave it a
  * `matrix`; local and world matrices are composed as the load composes them, in fp32 and in the same order, so the static pose
  * returns the transforms of sr_gltf_instance bit for bit.
@@ -1235,7 +1255,9 @@ int sr_gltf_blas_morph(const SrGltf* gltf, uint32_t blas_index, uint32_t* n_targ
 /* The weights of blas i's targets at `time_seconds` of animation `animation` into weights_out (n_targets must be the blas's):
  * the first `weights` channel that targets the blas's first instancing node, under sr_gltf_pose's sampling rules: time clamped to
  * the sampler's first / last key, STEP and LINEAR, computed in double from the fp32 keys and rounded once to fp32; a CUBICSPLINE
- * sampler on that channel: SR_ERR_UNSUPPORTED. The output accessor holds n_keys * n_targets float scalars; a shorter one, key
+ * sampler on that channel: SR_ERR_UNSUPPORTED, or under SR_CUBICSPLINE_SAMPLE sr_gltf_pose's cubic rule per target, its output
+ * accessor holding 3 * n_keys * n_targets float scalars (per key n_targets in-tangents, values, out-tangents; a shorter one:
+ * SR_ERR_INVALID_ARG). The output accessor holds n_keys * n_targets float scalars; a shorter one, key
  * times that are not finite, negative or not strictly increasing, a value that is not finite: SR_ERR_INVALID_ARG. animation == -1,
  * or no such channel: the default weights of sr_gltf_blas_morph. */
 int sr_gltf_morph_weights(const SrGltf* gltf, int32_t animation, float time_seconds, uint32_t blas_index, float* weights_out, uint32_t n_targets);
@@ -1250,6 +1272,9 @@ int sr_gltf_morph_weights(const SrGltf* gltf, int32_t animation, float time_seco
  *   skins      every skin an instanced node wears, in file order: joint nodes, inverse bind matrices, the mesh node (the first
  *              instanced node wearing it) and its offset in the clip's concatenated joint list;
  *   instances  the clip node of every instance, in sr_gltf_instance order.
+ * A CUBICSPLINE channel is baked under SR_CUBICSPLINE_SAMPLE only, with three rows a key (in-tangent, value, out-tangent, the
+ * file's order); the clip keeps it whatever the file's mode becomes later, and a clip without such a channel is byte for byte
+ * the block it is under SR_CUBICSPLINE_REFUSE.
  * Refused in sr_gltf_pose's statuses and words behind "sr_gltf_bake_clip: ": a CUBICSPLINE sampler (SR_ERR_UNSUPPORTED), a joint
  * node that is not part of the scene, a hierarchy that is too deep, every sampler error the loader reports. Refused as well
  * (SR_ERR_UNSUPPORTED): a node the roots reach twice, and a clip of more than SR_CLIP_MAX_NODES nodes (the text gives both
@@ -1263,7 +1288,10 @@ typedef struct SrClipInfo {
     uint32_t device_bytes;             /* the one block sr_scene_attach_clip uploads */
 } SrClipInfo;                          /* 40 bytes */
 typedef struct SrClipNodeInfo { uint32_t parent /* clip node, 0xFFFFFFFF: a root */, gltf_node, animated, level; } SrClipNodeInfo;
-typedef struct SrClipChannelInfo { uint32_t node /* clip node */, path /* 0 translation, 1 rotation, 2 scale */, interpolation /* 0 LINEAR, 1 STEP */, n_keys; } SrClipChannelInfo;
+typedef struct SrClipChannelInfo { uint32_t node /* clip node */, path /* 0 translation, 1 rotation, 2 scale */, interpolation /* SR_CLIP_LINEAR 0, SR_CLIP_STEP 1, SR_CLIP_CUBICSPLINE 2 */, n_keys; } SrClipChannelInfo;
+#define SR_CLIP_LINEAR 0u
+#define SR_CLIP_STEP 1u
+#define SR_CLIP_CUBICSPLINE 2u
 int sr_gltf_bake_clip(const SrGltf* gltf, int32_t animation, SrClip** out);
 int sr_clip_destroy(SrClip* clip);
 int sr_clip_info(const SrClip* clip, SrClipInfo* out);
@@ -1272,7 +1300,8 @@ int sr_clip_info(const SrClip* clip, SrClipInfo* out);
 int sr_clip_skin(const SrClip* clip, uint32_t skin, uint32_t* first_matrix, uint32_t* n_joints);
 /* The layout, for inspection: n_nodes node records, n_channels channel records, the clip node of every instance (any may be NULL). */
 int sr_clip_layout(const SrClip* clip, SrClipNodeInfo* nodes, SrClipChannelInfo* channels, uint32_t* instance_nodes);
-/* Channel `channel`'s keys as the clip holds them: n_keys times and n_keys x 3 (rotation: x 4) values; valid until sr_clip_destroy. */
+/* Channel `channel`'s keys as the clip holds them: n_keys times and n_keys x 3 (rotation: x 4) values; a SR_CLIP_CUBICSPLINE
+ * channel: n_keys x 3 rows of that width, per key its in-tangent, value and out-tangent; valid until sr_clip_destroy. */
 int sr_clip_channel_keys(const SrClip* clip, uint32_t channel, const float** times, const float** values);
 /* The morph sets of a clip: one for every blas of the file that has morph targets, holding what
  * sr_gltf_morph_weights(gltf, animation, t, blas, ...) derives from the document: the blas and its first instancing node, the
@@ -1285,16 +1314,18 @@ int sr_clip_channel_keys(const SrClip* clip, uint32_t channel, const float** tim
  * sr_clip_morph_count: the number of sets. sr_clip_morph: the set of blas `blas`; for an unavailable set the call succeeds and
  * sr_last_error() holds the loader's words. A blas without morph targets: SR_ERR_INVALID_ARG.
  * sr_clip_morph_keys: the set's n_keys times and n_keys x n_targets values (NULL without a channel) and its n_targets default
- * weights, valid until sr_clip_destroy; an unavailable set refuses with its status and words.
+ * weights, valid until sr_clip_destroy; an unavailable set refuses with its status and words. A SR_CLIP_CUBICSPLINE set (a cubic
+ * `weights` channel baked under SR_CUBICSPLINE_SAMPLE; under SR_CUBICSPLINE_REFUSE it is unavailable) is SR_CLIP_MORPH_CHANNEL
+ * and holds n_keys x 3 x n_targets values: per key n_targets in-tangents, values, out-tangents.
  * sr_clip_weights_host: the host rule, sr_gltf_morph_weights restated over the set and held to it bit for bit, in its statuses
  * and words too (a time that is not finite, another n_targets). The device kernel (clip_weights_kernel) includes the same
  * arithmetic (csrc/clip_rule.h): +, -, x, / on fp32 and fp64 only, so the device equals it bit for bit without exception. */
-#define SR_CLIP_MORPH_CHANNEL 0u       /* a LINEAR or STEP `weights` channel */
+#define SR_CLIP_MORPH_CHANNEL 0u       /* a LINEAR or STEP `weights` channel, or a CUBICSPLINE one baked under SR_CUBICSPLINE_SAMPLE */
 #define SR_CLIP_MORPH_DEFAULTS 1u      /* no channel (or the static pose): the default weights at every time */
 #define SR_CLIP_MORPH_UNAVAILABLE 2u
 typedef struct SrClipMorphInfo {
     uint32_t blas, gltf_node /* 0xFFFFFFFF: the morph parse failed */, n_targets, n_keys;
-    uint32_t interpolation;            /* 0 LINEAR, 1 STEP */
+    uint32_t interpolation;            /* SR_CLIP_LINEAR 0, SR_CLIP_STEP 1, SR_CLIP_CUBICSPLINE 2 */
     uint32_t state;                    /* SR_CLIP_MORPH_* */
     int32_t status;                    /* SR_OK, or what refused an unavailable set */
     uint32_t reserved;
@@ -1338,7 +1369,11 @@ int sr_clip_pose_host(const SrClip* clip, float time_seconds, const SrTransform*
  * sr_scene_read_item_active reads an item's list back as the posing kernel read it.
  * Numerics: translation, scale and STEP samples, samples at clamped and exact key times and everything composed from a TRS are
  * bit equal to sr_clip_pose_host. An interpolated rotation passes through atan2 and sin, where the device's libm and the host's
- * are not bit-identical: a component is the host's, its neighbouring fp32 value, or within 2^-44 of it.
+ * are not bit-identical: a component is the host's, its neighbouring fp32 value, or within 2^-44 of it. Cubic samples
+ * (SR_CLIP_CUBICSPLINE channels and sets) need + - * / and one sqrt only: they are bit equal without exception.
+ * Cubic morph sets: an item whose set is SR_CLIP_CUBICSPLINE is a spline row; clip_spline_weights_kernel (one wave per such row)
+ * runs behind clip_weights_kernel, which keeps the other rows, and writes what that kernel writes. Both kinds of row travel in
+ * the one upload; each kernel is launched only where it has a row. SrSplinePoseInfo counts them.
  * Refused on the host before any device work, behind "pose_actors: actor <i>: " or "pose_actors: item <i>: ": an unknown clip id,
  * a time that is not finite (sr_gltf_pose's words), instance_rows or instance_base without d_instance_transforms, an actor or
  * skin index out of range, a skin whose joint count is not that of the mesh's attached rig, a key named twice, an item with
@@ -1366,13 +1401,14 @@ typedef struct SrActorPoseInfo {       /* the last sr_scene_pose_actors that rea
     uint32_t actors, items;
     uint64_t nodes, channels;          /* nodes evaluated, channels sampled, over all actors */
     uint64_t upload_bytes;             /* the one upload */
-    uint32_t launches;                 /* 3 accepted (clip, pose, scatter), 2 refused; one more where clip_weights_kernel ran */
+    uint32_t launches;                 /* 3 accepted (clip, pose, scatter), 2 refused; one more for each weights kernel that ran
+                                        * (clip_weights_kernel or the blended one, clip_spline_weights_kernel) */
     uint32_t read_backs;               /* 1 */
     uint32_t calls;                    /* calls that reached the device since the scene was created */
     uint32_t refused_actor, refused_item;      /* 0xFFFFFFFF: none */
-    uint32_t weight_items;             /* items whose weights came from their actor's clip */
-    double clip_ms, pose_ms, scatter_ms;   /* events, only while sr_scene_enable_timing is on; clip_ms: clip_pose_kernel and, where it
-                                            * ran, clip_weights_kernel; pose_ms includes the read-back */
+    uint32_t weight_items;             /* items whose weights came from their actor's clip, plain and spline rows */
+    double clip_ms, pose_ms, scatter_ms;   /* events, only while sr_scene_enable_timing is on; clip_ms: clip_pose_kernel and, where they
+                                            * ran, clip_weights_kernel and clip_spline_weights_kernel; pose_ms includes the read-back */
     double host_ms;                    /* the whole call, wall clock */
 } SrActorPoseInfo;                     /* 88 bytes */
 int sr_scene_attach_clip(SrScene* scene, const SrClip* clip, uint32_t* clip_id);
@@ -1380,6 +1416,16 @@ int sr_scene_detach_clip(SrScene* scene, uint32_t clip_id);
 int sr_scene_pose_actors(SrScene* scene, const SrClipActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
                          SrTransform* d_instance_transforms, uint32_t flags, void* stream);
 int sr_scene_actor_pose_info(const SrScene* scene, SrActorPoseInfo* out);
+/* The cubic side of the last sr_scene_pose_actors or sr_scene_pose_actors_blended that reached the device. */
+typedef struct SrSplinePoseInfo {
+    uint32_t spline_weight_rows;       /* clip-weighted items that clip_spline_weights_kernel evaluated: a cubic set, or for a blended item
+                                        * a cubic set in at least one source */
+    uint32_t plain_weight_rows;        /* those clip_weights_kernel or clip_blend_weights_kernel evaluated */
+    uint64_t cubic_channels;           /* SR_CLIP_CUBICSPLINE channels among SrActorPoseInfo.channels */
+    double spline_weights_ms;          /* clip_spline_weights_kernel alone; events, only while sr_scene_enable_timing is on */
+    uint64_t reserved;
+} SrSplinePoseInfo;                    /* 32 bytes */
+int sr_scene_spline_pose_info(const SrScene* scene, SrSplinePoseInfo* out);
 /* After a call with SR_ACTORS_KEEP_NODES that reached the device: actor `actor`'s sampled TRS (n_nodes records) and global
  * matrices (n_nodes x 16 floats, row-major), clip-node order. Either may be NULL. SR_ERR_STATE: the last call kept no nodes.
  * sr_scene_read_actor_matrices: after any call that reached the device, the actor's joint matrices as the posing kernel read
@@ -1511,6 +1557,7 @@ int sr_renderer_pose_actors(SrRenderer* renderer, const SrClipActor* actors, uin
 int sr_renderer_pose_actors_blended(SrRenderer* renderer, const SrClipBlendActor* actors, uint32_t n_actors, const SrActorPoseItem* items,
                                     uint32_t n_items, SrTransform* d_instance_transforms, uint32_t flags, void* stream);
 int sr_renderer_actor_pose_info(const SrRenderer* renderer, SrActorPoseInfo* out);
+int sr_renderer_spline_pose_info(const SrRenderer* renderer, SrSplinePoseInfo* out);
 /* How sr_renderer_pose_scene poses a loaded scene's rigged and morphed meshes: SR_POSE_BATCH_OFF (the default), one
  * sr_renderer_skin_mesh / sr_renderer_pose_mesh per mesh (each a batch of one item); SR_POSE_BATCH_ON, all of them by one sr_renderer_pose_meshes.
  * SR_POSE_BATCH=on|off in the environment sets the initial mode when the renderer is created. */

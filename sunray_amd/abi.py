@@ -237,6 +237,8 @@ NODE_TRS = np.dtype([("translation", "<f4", 3), ("rotation", "<f4", 4), ("scale"
 assert NODE_TRS.itemsize == 48
 CLIP_MAX_NODES, CLIP_NO_NODE, ACTOR_NO_SKIN, ACTORS_KEEP_NODES = 384, 0xFFFFFFFF, 0xFFFFFFFF, 1
 CLIP_MORPH_CHANNEL, CLIP_MORPH_DEFAULTS, CLIP_MORPH_UNAVAILABLE = 0, 1, 2  # SrClipMorphInfo.state
+CLIP_LINEAR, CLIP_STEP, CLIP_CUBICSPLINE = 0, 1, 2  # SrClipChannelInfo.interpolation, SrClipMorphInfo.interpolation
+CUBICSPLINE_REFUSE, CUBICSPLINE_SAMPLE = 0, 1  # sr_gltf_set_cubicspline
 
 
 def actor_clip_weights(blas):
@@ -268,6 +270,14 @@ class SrActorPoseInfo(C.Structure):  # the last sr_scene_pose_actors that reache
 
 
 assert C.sizeof(SrClipInfo) == 40 and C.sizeof(SrClipActor) == 32 and C.sizeof(SrActorPoseItem) == 32 and C.sizeof(SrActorPoseInfo) == 88
+
+
+class SrSplinePoseInfo(C.Structure):  # the cubic side of the last pose_actors / pose_actors_blended that reached the device, 32 B
+    _fields_ = [("spline_weight_rows", C.c_uint32), ("plain_weight_rows", C.c_uint32), ("cubic_channels", C.c_uint64),
+                ("spline_weights_ms", C.c_double), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(SrSplinePoseInfo) == 32
 
 
 class SrClipBlendActor(C.Structure):  # one character of sr_scene_pose_actors_blended: between two clips, 48 B

@@ -31,6 +31,7 @@
 #include "clip_pose.h"
 #include "clip_weights.h"
 #include "clip_blend.h"
+#include "clip_spline_weights.h"
 #include "tl_record.h"
 
 namespace {
@@ -278,6 +279,7 @@ struct SrScene {
     std::map<uint32_t, AttachedClip> clips;
     uint32_t next_clip_id = 1;
     SrActorPoseInfo actor_info{0, 0, 0, 0, 0, 0, 0, 0, 0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0.0, 0.0, 0.0, 0.0};
+    SrSplinePoseInfo spline_info{0, 0, 0, 0.0, 0};
     struct ActorRecord { uint64_t matrix_byte; uint32_t n_joints, node_base, n_nodes; };
     std::vector<ActorRecord> actor_records;
     // ... and each item's row and its slice of the active arrays (sr_scene_read_item_active); capacity: the entries of the slice
@@ -1121,16 +1123,20 @@ namespace {
 // What sr_scene_pose_actors adds to a batch: the actors' rows for clip_pose_kernel (matrix_base counted from the first matrix the
 // kernel writes; pose_items moves it behind the upload), the instance rows of the actors that gave some, and per item its first
 // matrix among those the kernel writes (0xFFFFFFFF: the item has no skin stage).
-static_assert(sizeof(SrClipActor) == 32 && sizeof(SrActorPoseItem) == 32 && sizeof(SrActorPoseInfo) == 88 && sizeof(SrClipInfo) == 40, "the header states these sizes");
+static_assert(sizeof(SrClipActor) == 32 && sizeof(SrActorPoseItem) == 32 && sizeof(SrActorPoseInfo) == 88 && sizeof(SrClipInfo) == 40 && sizeof(SrSplinePoseInfo) == 32, "the header states these sizes");
 struct ActorFeed {
     uint32_t n_actors = 0, flags = 0;
     std::vector<srd::ClipActorRow> rows;
     std::vector<uint32_t> instance_rows, item_matrix, actor_joints, actor_nodes;
-    // an item whose weights come from its actor's clip: its row for clip_weights_kernel (0xFFFFFFFF: the weights are the host's,
-    // or none) and the set's n_targets; the rows (item, active_base and check_word are pose_items' to fill)
-    std::vector<uint32_t> item_weight_row, item_clip_targets;
+    // an item whose weights come from its actor's clip: its place among such items, which is its check word's (0xFFFFFFFF: the
+    // weights are the host's, or none), and the set's n_targets; the rows (item, active_base and check_word are pose_items' to
+    // fill). A row is a plain one, for clip_weights_kernel (or the blended one), or where a set of the item is kClipCubic a spline
+    // row, for clip_spline_weights_kernel: item_row_at is the row's position in its own list.
+    std::vector<uint32_t> item_weight_row, item_clip_targets, item_row_at;
+    std::vector<char> item_spline;
     std::vector<srd::ClipWeightRow> weight_rows;
-    uint64_t n_matrices = 0, n_nodes = 0, n_channels = 0;
+    std::vector<srd::ClipSplineWeightRow> spline_rows;
+    uint64_t n_matrices = 0, n_nodes = 0, n_channels = 0, n_cubic_channels = 0;
     SrTransform* d_instance_transforms = nullptr;
     SrActorPoseInfo* info = nullptr;
     // a blended feed (sr_scene_pose_actors_blended): its rows for clip_blend_kernel and clip_blend_weights_kernel stand where
@@ -1138,7 +1144,15 @@ struct ActorFeed {
     bool blended = false;
     std::vector<srd::ClipBlendActorRow> blend_rows;
     std::vector<srd::ClipBlendWeightRow> blend_weight_rows;
-    uint32_t n_weight_rows() const { return (uint32_t)(blended ? blend_weight_rows.size() : weight_rows.size()); }
+    uint32_t n_plain_rows() const { return (uint32_t)(blended ? blend_weight_rows.size() : weight_rows.size()); }
+    uint32_t n_weight_rows() const { return n_plain_rows() + (uint32_t)spline_rows.size(); }
+    void add_weight_item(uint32_t i, uint32_t n_targets, bool spline) {
+        item_weight_row[i] = n_weight_rows(); item_clip_targets[i] = n_targets; item_spline[i] = spline ? 1 : 0;
+        item_row_at[i] = spline ? (uint32_t)spline_rows.size() : n_plain_rows();
+    }
+    void count_cubic_channels(const SrClip& clip) {
+        for (uint32_t k = 0; k < clip.header().n_channels; k++) n_cubic_channels += clip.channels()[k].interpolation == srd::kClipCubic ? 1u : 0u;
+    }
     size_t actor_row_bytes() const { return blended ? sizeof(srd::ClipBlendActorRow) : sizeof(srd::ClipActorRow); }
     size_t weight_row_bytes() const { return blended ? sizeof(srd::ClipBlendWeightRow) : sizeof(srd::ClipWeightRow); }
     uint32_t& matrix_base(uint32_t a) { return blended ? blend_rows[a].matrix_base : rows[a].matrix_base; }
@@ -1165,6 +1179,8 @@ struct ActorFeed {
 // and one more check word per such item brings the count back. In a call where no item has host weights the active arrays lie
 // behind everything else in the staging block, outside the upload, so the upload does not grow with the targets; where some
 // have, the slots follow the host's lists inside the arrays. A call without such an item is laid out and launched as ever.
+// Such an item with a kClipCubic set is a spline row: the spline rows travel behind the plain rows in the same upload and
+// clip_spline_weights_kernel runs behind the plain rows' kernel; either kernel is launched only where it has a row.
 int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream, bool batch, SrPoseBatchInfo* out, ActorFeed* feed = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     const std::string who = feed ? (feed->blended ? "pose_actors_blended" : "pose_actors") : batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
@@ -1208,7 +1224,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     // writes follow it, outside the uploaded bytes, a whole number of matrices from lay.matrices so that matrix_base reaches them.
     const uint32_t n_actors = feed ? feed->n_actors : 0;
     const size_t actor_rows_at = lay.bytes, weight_rows_at = actor_rows_at + (feed ? feed->actor_row_bytes() : 0) * (size_t)n_actors;
-    const size_t inst_rows_at = weight_rows_at + (feed ? feed->weight_row_bytes() : 0) * (size_t)n_weight_items;
+    const uint32_t n_plain_rows = feed ? feed->n_plain_rows() : 0, n_spline_rows = n_weight_items - n_plain_rows;
+    const size_t spline_rows_at = weight_rows_at + (feed ? feed->weight_row_bytes() : 0) * (size_t)n_plain_rows;
+    const size_t inst_rows_at = spline_rows_at + sizeof(srd::ClipSplineWeightRow) * (size_t)n_spline_rows;
     const size_t upload_bytes = inst_rows_at + ((4 * (feed ? feed->instance_rows.size() : 0) + 15u) & ~(size_t)15u);
     const uint64_t fed_first = (upload_bytes - lay.matrices + sizeof(SrTransform) - 1) / sizeof(SrTransform);
     size_t stage_bytes = feed ? lay.matrices + sizeof(SrTransform) * (size_t)(fed_first + feed->n_matrices) : lay.bytes;
@@ -1252,8 +1270,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     for (uint32_t i = 0; i < n_items; i++) {                  // the slots follow the host's lists; the kernel writes n_active (0 until then)
         if (!clip_weighted(i)) continue;
         const uint32_t check_word = (uint32_t)(2 * (size_t)n_items + n_actors + feed->item_weight_row[i]);
-        if (feed->blended) { srd::ClipBlendWeightRow& wr = feed->blend_weight_rows[feed->item_weight_row[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
-        else { srd::ClipWeightRow& wr = feed->weight_rows[feed->item_weight_row[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
+        if (feed->item_spline[i]) { srd::ClipSplineWeightRow& wr = feed->spline_rows[feed->item_row_at[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
+        else if (feed->blended) { srd::ClipBlendWeightRow& wr = feed->blend_weight_rows[feed->item_row_at[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
+        else { srd::ClipWeightRow& wr = feed->weight_rows[feed->item_row_at[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
         rows[i].active_base = active_base;
         active_base += feed->item_clip_targets[i];
     }
@@ -1267,12 +1286,13 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     const srd::PoseBatchItem* d_rows = (const srd::PoseBatchItem*)(d_stage + lay.items);
     const uint32_t* d_table = (const uint32_t*)(d_stage + lay.block_table);
     std::vector<uint32_t> bad(n_check, 0xFFFFFFFFu);
-    EventPair pose_timer(s), scatter_timer(s), clip_timer(s);
+    EventPair pose_timer(s), scatter_timer(s), clip_timer(s), spline_timer(s);
     if (feed) {
         for (uint32_t a = 0; a < n_actors; a++) feed->matrix_base(a) += (uint32_t)fed_first;
         if (n_actors) memcpy(stage.data() + actor_rows_at, feed->blended ? (const void*)feed->blend_rows.data() : (const void*)feed->rows.data(), feed->actor_row_bytes() * (size_t)n_actors);
-        if (n_weight_items)
-            memcpy(stage.data() + weight_rows_at, feed->blended ? (const void*)feed->blend_weight_rows.data() : (const void*)feed->weight_rows.data(), feed->weight_row_bytes() * (size_t)n_weight_items);
+        if (n_plain_rows)
+            memcpy(stage.data() + weight_rows_at, feed->blended ? (const void*)feed->blend_weight_rows.data() : (const void*)feed->weight_rows.data(), feed->weight_row_bytes() * (size_t)n_plain_rows);
+        if (n_spline_rows) memcpy(stage.data() + spline_rows_at, feed->spline_rows.data(), sizeof(srd::ClipSplineWeightRow) * (size_t)n_spline_rows);
         if (!feed->instance_rows.empty()) memcpy(stage.data() + inst_rows_at, feed->instance_rows.data(), 4 * feed->instance_rows.size());
     }
     s->actor_stage_current = false;                          // the block changes hands
@@ -1291,15 +1311,23 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         else if (e == 0)
             e = srk_clip_pose((const srd::ClipActorRow*)(d_stage + actor_rows_at), n_actors, (const uint32_t*)(d_stage + inst_rows_at), fed_matrices, feed->d_instance_transforms,
                               actor_check, kept_trs, kept_globals, st);
-        if (e == 0 && n_weight_items && feed->blended)
-            e = srk_clip_blend_weights((const srd::ClipBlendWeightRow*)(d_stage + weight_rows_at), n_weight_items, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
+        if (e == 0 && n_plain_rows && feed->blended)
+            e = srk_clip_blend_weights((const srd::ClipBlendWeightRow*)(d_stage + weight_rows_at), n_plain_rows, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
                                        (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
                                        (uint32_t*)s->d_pose_check.p, st);
-        else if (e == 0 && n_weight_items)
-            e = srk_clip_weights((const srd::ClipWeightRow*)(d_stage + weight_rows_at), n_weight_items, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
+        else if (e == 0 && n_plain_rows)
+            e = srk_clip_weights((const srd::ClipWeightRow*)(d_stage + weight_rows_at), n_plain_rows, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
                                  (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
                                  (uint32_t*)s->d_pose_check.p, st);
-        clip_timer.end(st);                                   // both clip kernels
+        if (n_spline_rows) {
+            spline_timer.begin(st);
+            if (e == 0)
+                e = srk_clip_spline_weights((const srd::ClipSplineWeightRow*)(d_stage + spline_rows_at), n_spline_rows, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
+                                            (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
+                                            (uint32_t*)s->d_pose_check.p, st);
+            spline_timer.end(st);
+        }
+        clip_timer.end(st);                                   // the clip kernels
     }
     pose_timer.begin(st);
     if (e == 0) e = srk_pose_batch(d_rows, d_table, n_blocks, (const SrTransform*)(d_stage + lay.matrices), (const uint32_t*)(d_stage + lay.active_index),
@@ -1310,6 +1338,7 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     if (e != 0) return fail(SR_ERR_HIP, who + (batch ? ": the posing kernel failed: " : items[0].weights ? ": a posing kernel failed: " : ": the skinning kernel failed: ") +
                                         hipGetErrorString((hipError_t)e));
     info.launches = 1; info.read_backs = 1; info.pose_ms = pose_timer.ms();
+    const uint32_t weight_launches = (n_plain_rows ? 1u : 0u) + (n_spline_rows ? 1u : 0u);
     if (feed) {                                               // what the read-outs find, and the figures of a call that reached the device
         s->actor_records.clear();
         for (uint32_t a = 0; a < n_actors; a++)
@@ -1323,7 +1352,8 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         }
         s->actor_stage_current = true; s->actor_nodes_kept = keep_nodes; s->actor_sources_kept = keep_sources;
         SrActorPoseInfo& ai = *feed->info;
-        ai = SrActorPoseInfo{n_actors, n_items, feed->n_nodes, feed->n_channels, upload_bytes, n_weight_items ? 3u : 2u, 1, ai.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, n_weight_items, clip_timer.ms(), info.pose_ms, 0.0, 0.0};
+        ai = SrActorPoseInfo{n_actors, n_items, feed->n_nodes, feed->n_channels, upload_bytes, 2u + weight_launches, 1, ai.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, n_weight_items, clip_timer.ms(), info.pose_ms, 0.0, 0.0};
+        s->spline_info = SrSplinePoseInfo{n_spline_rows, n_plain_rows, feed->n_cubic_channels, n_spline_rows ? spline_timer.ms() : 0.0, 0};
         for (uint32_t a = 0; a < n_actors && ai.refused_actor == 0xFFFFFFFFu; a++) if (bad[2 * (size_t)n_items + a] != 0xFFFFFFFFu) ai.refused_actor = a;
         if (ai.refused_actor != 0xFFFFFFFFu) {                // a singular mesh-node transform: nothing has changed but the scratch
             s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();
@@ -1375,7 +1405,7 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     note_update_times(s, t0, t1, t2);
     info.host_ms = ms_between(t0, std::chrono::steady_clock::now());
     *out = info;
-    if (feed) { feed->info->launches = n_weight_items ? 4 : 3; feed->info->scatter_ms = info.scatter_ms; feed->info->host_ms = info.host_ms; }
+    if (feed) { feed->info->launches = 3 + weight_launches; feed->info->scatter_ms = info.scatter_ms; feed->info->host_ms = info.host_ms; }
     return SR_OK;
 }
 
@@ -1474,11 +1504,13 @@ int sr_scene_pose_actors(SrScene* s, const SrClipActor* actors, uint32_t n_actor
         feed.actor_joints.push_back(h.n_joints); feed.actor_nodes.push_back(h.n_nodes);
         clip_of[a] = &it->second; first_matrix[a] = (uint32_t)feed.n_matrices;
         feed.n_matrices += h.n_joints; feed.n_nodes += h.n_nodes; feed.n_channels += h.n_channels;
+        feed.count_cubic_channels(clip);
         if (feed.n_matrices >= (1ull << 32) || feed.n_nodes >= (1ull << 32) || feed.instance_rows.size() >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_actors: the call holds 2^32 joint matrices, nodes or instance rows or more");
     }
     std::vector<SrPoseItem> pose(n_items);
     feed.item_matrix.assign(n_items, 0xFFFFFFFFu);
     feed.item_weight_row.assign(n_items, 0xFFFFFFFFu); feed.item_clip_targets.assign(n_items, 0u);
+    feed.item_row_at.assign(n_items, 0u); feed.item_spline.assign(n_items, 0);
     for (uint32_t i = 0; i < n_items; i++) {
         const SrActorPoseItem& it = items[i];
         const auto prefix = [i]() { return "pose_actors: item " + std::to_string(i) + ": "; };
@@ -1493,10 +1525,17 @@ int sr_scene_pose_actors(SrScene* s, const SrClipActor* actors, uint32_t n_actor
             if (k < 0) return fail(SR_ERR_INVALID_ARG, prefix() + "the weights of blas " + std::to_string(blas) + " named, the actor's clip has no morph set for it");
             const srd::ClipMorphSet& set = clip.morph_sets()[k];
             if (set.state == srd::kClipMorphUnavailable) return fail((int32_t)set.status, prefix() + clip.morph_errors[k]);
-            srd::ClipWeightRow row{};
-            row.clip = clip_of[it.actor]->d_block.p; row.time_seconds = actors[it.actor].time_seconds; row.set = (uint32_t)k;
-            feed.item_weight_row[i] = (uint32_t)feed.weight_rows.size(); feed.item_clip_targets[i] = set.n_targets;
-            feed.weight_rows.push_back(row);
+            const bool spline = set.n_keys && set.interpolation == srd::kClipCubic;
+            feed.add_weight_item(i, set.n_targets, spline);
+            if (spline) {
+                srd::ClipSplineWeightRow row{};
+                row.clip_a = clip_of[it.actor]->d_block.p; row.time_a = actors[it.actor].time_seconds; row.set_a = (uint32_t)k;
+                feed.spline_rows.push_back(row);
+            } else {
+                srd::ClipWeightRow row{};
+                row.clip = clip_of[it.actor]->d_block.p; row.time_seconds = actors[it.actor].time_seconds; row.set = (uint32_t)k;
+                feed.weight_rows.push_back(row);
+            }
         }
         if (it.skin == SR_ACTOR_NO_SKIN) continue;
         uint32_t first = 0, n_joints = 0;
@@ -1555,12 +1594,14 @@ int sr_scene_pose_actors_blended(SrScene* s, const SrClipBlendActor* actors, uin
         feed.actor_joints.push_back(h.n_joints); feed.actor_nodes.push_back(h.n_nodes);
         clip_a[a] = &ia->second; clip_b[a] = &ib->second; first_matrix[a] = (uint32_t)feed.n_matrices;
         feed.n_matrices += h.n_joints; feed.n_nodes += h.n_nodes; feed.n_channels += (uint64_t)h.n_channels + other.header().n_channels;
+        feed.count_cubic_channels(clip); feed.count_cubic_channels(other);
         if (feed.n_matrices >= (1ull << 32) || feed.n_nodes >= (1ull << 32) || feed.instance_rows.size() >= (1ull << 32))
             return fail(SR_ERR_UNSUPPORTED, "pose_actors_blended: the call holds 2^32 joint matrices, nodes or instance rows or more");
     }
     std::vector<SrPoseItem> pose(n_items);
     feed.item_matrix.assign(n_items, 0xFFFFFFFFu);
     feed.item_weight_row.assign(n_items, 0xFFFFFFFFu); feed.item_clip_targets.assign(n_items, 0u);
+    feed.item_row_at.assign(n_items, 0u); feed.item_spline.assign(n_items, 0);
     for (uint32_t i = 0; i < n_items; i++) {
         const SrActorPoseItem& it = items[i];
         const auto prefix = [i]() { return "pose_actors_blended: item " + std::to_string(i) + ": "; };
@@ -1581,12 +1622,25 @@ int sr_scene_pose_actors_blended(SrScene* s, const SrClipBlendActor* actors, uin
             if (n_targets != clip_b[it.actor]->host.morph_sets()[k[1]].n_targets)
                 return fail(SR_ERR_INVALID_ARG, prefix() + "the morph sets of blas " + std::to_string(blas) + " have another number of targets in the actor's two clips");
             const SrClipBlendActor& ac = actors[it.actor];
-            srd::ClipBlendWeightRow row{};
-            row.clip_a = clip_a[it.actor]->d_block.p; row.clip_b = clip_b[it.actor]->d_block.p;
-            row.time_a = ac.time_seconds; row.time_b = ac.time_seconds_b; row.weight = ac.weight;
-            row.set_a = (uint32_t)k[0]; row.set_b = (uint32_t)k[1];
-            feed.item_weight_row[i] = (uint32_t)feed.blend_weight_rows.size(); feed.item_clip_targets[i] = n_targets;
-            feed.blend_weight_rows.push_back(row);
+            bool spline = false;                                 // a cubic set in at least one source
+            for (int side = 0; side < 2; side++) {
+                const srd::ClipMorphSet& set = (side ? clip_b : clip_a)[it.actor]->host.morph_sets()[k[side]];
+                spline = spline || (set.n_keys && set.interpolation == srd::kClipCubic);
+            }
+            feed.add_weight_item(i, n_targets, spline);
+            if (spline) {
+                srd::ClipSplineWeightRow row{};
+                row.clip_a = clip_a[it.actor]->d_block.p; row.clip_b = clip_b[it.actor]->d_block.p;
+                row.time_a = ac.time_seconds; row.time_b = ac.time_seconds_b; row.weight = ac.weight;
+                row.set_a = (uint32_t)k[0]; row.set_b = (uint32_t)k[1];
+                feed.spline_rows.push_back(row);
+            } else {
+                srd::ClipBlendWeightRow row{};
+                row.clip_a = clip_a[it.actor]->d_block.p; row.clip_b = clip_b[it.actor]->d_block.p;
+                row.time_a = ac.time_seconds; row.time_b = ac.time_seconds_b; row.weight = ac.weight;
+                row.set_a = (uint32_t)k[0]; row.set_b = (uint32_t)k[1];
+                feed.blend_weight_rows.push_back(row);
+            }
         }
         if (it.skin == SR_ACTOR_NO_SKIN) continue;
         uint32_t first = 0, n_joints = 0;
@@ -1614,6 +1668,12 @@ int sr_scene_read_actor_sources(const SrScene* s, uint32_t actor, SrNodeTrs* trs
 int sr_scene_actor_pose_info(const SrScene* s, SrActorPoseInfo* out) {
     if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_actor_pose_info: null argument");
     *out = s->actor_info;
+    return SR_OK;
+}
+
+int sr_scene_spline_pose_info(const SrScene* s, SrSplinePoseInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_spline_pose_info: null argument");
+    *out = s->spline_info;
     return SR_OK;
 }
 

@@ -91,9 +91,14 @@ static int weights_of(const SrClip* clip, float time_seconds, uint32_t blas, flo
     if (unavailable) return srh::set_error((int32_t)s.status, who + ": " + clip->morph_errors[k]);
     if (s.n_keys == 0) { memcpy(weights_out, clip->morph_defaults() + s.first_default, 4 * (size_t)n_targets); return SR_OK; }
     uint32_t i = 0;
-    double u = 0.0;
-    srd::clip_key_search(clip->morph_times() + s.first_time, s.n_keys, s.interpolation, (double)time_seconds, &i, &u);
+    double u = 0.0, td = 0.0;
     const float* values = clip->morph_values() + s.first_value;
+    if (s.interpolation == srd::kClipCubic) {
+        srd::clip_spline_key_search(clip->morph_times() + s.first_time, s.n_keys, (double)time_seconds, &i, &u, &td);
+        for (uint32_t t = 0; t < n_targets; t++) weights_out[t] = srd::clip_spline_weight_at(values, n_targets, i, u, td, t);
+        return SR_OK;
+    }
+    srd::clip_key_search(clip->morph_times() + s.first_time, s.n_keys, s.interpolation, (double)time_seconds, &i, &u);
     for (uint32_t t = 0; t < n_targets; t++) weights_out[t] = srd::clip_weight_at(values, n_targets, i, u, t);
     return SR_OK;
 }

@@ -1,7 +1,8 @@
 // Baked clips: the flat tables of a clip and the arithmetic of its evaluation, shared by the host rule (clip_host.cpp) and the
-// device kernels (clip_pose.hip, clip_weights.hip, clip_blend.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
+// device kernels (clip_pose.hip, clip_weights.hip, clip_blend.hip, clip_spline_weights.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
 // (gltf_load.cpp) term for term; host and device are built with -ffp-contract=off, so +, -, *, / and sqrt give the same bits on
-// both. atan2 and sin (interpolated rotations only) come from each side's own libm.
+// both. atan2 and sin (LINEAR rotations between two keys only) come from each side's own libm; a CUBICSPLINE sample (clip_hermite)
+// needs neither, so it is bit equal between host and device without exception.
 // No HIP here beyond the function qualifiers.
 #pragma once
 #include <cmath>
@@ -18,7 +19,7 @@ namespace srd {
 constexpr uint32_t kClipMaxNodes = 384;     // SR_CLIP_MAX_NODES: clip_pose_kernel keeps 12 + 16 floats a node in static LDS (42 KiB)
 constexpr uint32_t kClipNoNode = 0xFFFFFFFFu;
 constexpr uint32_t kClipTranslation = 0, kClipRotation = 1, kClipScale = 2;
-constexpr uint32_t kClipLinear = 0, kClipStep = 1;
+constexpr uint32_t kClipLinear = 0, kClipStep = 1, kClipCubic = 2;   // kClipCubic: a key is three rows, in-tangent, value, out-tangent
 constexpr uint32_t kClipTrsWords = 12;      // SrNodeTrs: t[3] q[4] s[3] animated reserved
 
 // One block, as the device holds it: the header, then the tables at the header's byte offsets (each 16-byte aligned).
@@ -36,6 +37,7 @@ struct ClipNode {
     float matrix[16];                                   // node_matrix of the file, row-major (a node no channel animates composes from it)
 };
 static_assert(sizeof(ClipNode) == 128, "eight 16-byte pieces");
+// first_value: n_keys x COMPS floats (3, or 4 for a rotation); kClipCubic: n_keys x 3 x COMPS, per key in-tangent, value, out-tangent
 struct ClipChannel { uint32_t node, path, interpolation, n_keys, first_time, first_value, reserved[2]; };
 static_assert(sizeof(ClipChannel) == 32, "two 16-byte pieces");
 struct ClipSkin { uint32_t skin, mesh_node, n_joints, first_joint; };   // the file's skin index; clip node; its slice of the joint list
@@ -64,6 +66,7 @@ static_assert(sizeof(ClipMorphHeader) == 32, "two 16-byte pieces");
 struct ClipMorphSet {
     uint32_t blas, gltf_node, n_targets, n_keys;        // n_keys 0: no `weights` channel on the node, the defaults
     uint32_t interpolation, first_time, first_value, first_default;   // n_keys times; n_keys x n_targets values, key-major; n_targets defaults
+                                                        // kClipCubic: n_keys x 3 x n_targets, per key n_targets in-tangents, values, out-tangents
     uint32_t state, status, reserved[2];                // kClipMorphUnavailable: the loader refused the set with `status`; never sampled
 };
 static_assert(sizeof(ClipMorphSet) == 48, "three 16-byte pieces");
@@ -103,6 +106,18 @@ struct ClipBlendWeightRow {
 };
 static_assert(sizeof(ClipBlendWeightRow) == 48, "three 16-byte pieces");
 
+// One clip-weighted item with a kClipCubic set among its sources as clip_spline_weights_kernel reads it, at wave-uniform
+// addresses: an item of a plain call (clip_b is null; time_b, weight and set_b are 0) or of a blended one.
+struct ClipSplineWeightRow {
+    const void* clip_a;         // device: the block of the source, or of source A
+    const void* clip_b;         // device: the block of source B; null for an item of a plain call
+    float time_a, time_b, weight;                                   // weight: the share of B
+    uint32_t set_a;             // position in A's morph sets
+    uint32_t set_b;             // position in B's morph sets (equal n_targets)
+    uint32_t active_base, item, check_word;                         // as ClipWeightRow's
+};
+static_assert(sizeof(ClipSplineWeightRow) == 48, "three 16-byte pieces");
+
 // The key search of sample_channel / morph_weights: the key `i` at or before `time` (clamped to the first / last key) and the
 // fraction `u` towards key i + 1 (0: take key i as it is).
 SR_CLIP_HD void clip_key_search(const float* times, uint32_t n, uint32_t interpolation, double time, uint32_t* key, double* fraction) {
@@ -128,8 +143,36 @@ SR_CLIP_HD float clip_weight_at(const float* values, uint32_t n_targets, uint32_
     return clip_weight(values[(size_t)i * n_targets + k], values[(size_t)(u > 0.0 ? i + 1 : i) * n_targets + k], u);
 }
 
+
+// CUBICSPLINE (glTF 2.0, appendix C) between key i (value v0, out-tangent b0) and key i + 1 (in-tangent a1, value v1) at the
+// fraction u, 0 < u < 1, with td = t[i + 1] - t[i]: the Hermite form in double with exactly this grouping, + - * only. The
+// caller rounds the sum once.
+SR_CLIP_HD double clip_hermite(double v0, double b0, double v1, double a1, double u, double td) {
+    const double u2 = u * u, u3 = u2 * u;
+    const double h00 = (2.0 * u3 - 3.0 * u2) + 1.0, h10 = (u3 - 2.0 * u2) + u, h01 = 3.0 * u2 - 2.0 * u3, h11 = u3 - u2;
+    return ((h00 * v0 + h10 * (td * b0)) + h01 * v1) + h11 * (td * a1);
+}
+// clip_key_search for a kClipCubic channel: the same key and fraction as a LINEAR one, and the keys' distance `td`.
+SR_CLIP_HD void clip_spline_key_search(const float* times, uint32_t n, double time, uint32_t* key, double* fraction, double* distance) {
+    clip_key_search(times, n, kClipLinear, time, key, fraction);
+    *distance = *fraction > 0.0 ? (double)times[*key + 1] - (double)times[*key] : 0.0;
+}
+// One weight of a kClipCubic set from the two keys' rows: u == 0 is the key's value.
+SR_CLIP_HD float clip_spline_weight(float v0, float b0, float v1, float a1, double u, double td) {
+    return u > 0.0 ? (float)clip_hermite((double)v0, (double)b0, (double)v1, (double)a1, u, td) : v0;
+}
+// Target k of a kClipCubic set at key i, fraction u and distance td; `values` is the set's own slice, per key n_targets
+// in-tangents, values, out-tangents.
+SR_CLIP_HD float clip_spline_weight_at(const float* values, uint32_t n_targets, uint32_t i, double u, double td, uint32_t k) {
+    const float* key = values + (size_t)i * 3 * n_targets;
+    const float* next = u > 0.0 ? key + (size_t)3 * n_targets : key;
+    return clip_spline_weight(key[(size_t)n_targets + k], key[(size_t)2 * n_targets + k], next[(size_t)n_targets + k], next[k], u, td);
+}
+
 // sample_channel: one channel at `time` (clamped to the first / last key), in double from the fp32 keys, rounded once.
 // COMPS 3: translation / scale. COMPS 4: a rotation, slerp along the shorter arc between the normalised keys, normalised.
+// kClipCubic: clip_hermite per component of the keys as the file gives them (neither normalised nor sign-flipped); a rotation is
+// normalised afterwards in every case, at a key too, and a zero sum stays zero (clip_trs_matrix makes it the identity rotation).
 SR_CLIP_HD void clip_normalise(double* q) {
     const double len = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     if (len > 0.0) for (int c = 0; c < 4; c++) q[c] /= len;
@@ -137,16 +180,26 @@ SR_CLIP_HD void clip_normalise(double* q) {
 template <int COMPS>
 SR_CLIP_HD void clip_sample_channel(const float* times, const float* values, uint32_t n, uint32_t interpolation, double time, float* out) {
     uint32_t i = 0;
-    double u = 0.0;
+    double u = 0.0, td = 0.0;
     if (time <= (double)times[0]) i = 0;
     else if (time >= (double)times[n - 1]) i = n - 1;
     else {
         uint32_t lo = 0, hi = n - 1;                                              // times[lo] <= time < times[hi]
         while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if ((double)times[mid] <= time) lo = mid; else hi = mid; }
         i = lo;
-        if (interpolation == kClipLinear) u = (time - (double)times[i]) / ((double)times[i + 1] - (double)times[i]);
+        if (interpolation != kClipStep) { td = (double)times[i + 1] - (double)times[i]; u = (time - (double)times[i]) / td; }
     }
     double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, r[4];
+    if (interpolation == kClipCubic) {
+        const float* key = values + (size_t)i * 3 * COMPS;                        // in-tangent, value, out-tangent
+        const float* next = u > 0.0 ? key + 3 * COMPS : key;                      // never past the channel's last key
+        for (int c = 0; c < 4; c++) r[c] = 0.0;
+        for (int c = 0; c < COMPS; c++)
+            r[c] = u > 0.0 ? clip_hermite((double)key[COMPS + c], (double)key[2 * COMPS + c], (double)next[COMPS + c], (double)next[c], u, td) : (double)key[COMPS + c];
+        if (COMPS == 4) clip_normalise(r);
+        for (int c = 0; c < COMPS; c++) out[c] = (float)r[c];
+        return;
+    }
     for (int c = 0; c < COMPS; c++) { a[c] = values[(size_t)i * COMPS + c]; b[c] = values[(size_t)(u > 0.0 ? i + 1 : i) * COMPS + c]; }
     if (COMPS == 3) {
         for (int c = 0; c < 3; c++) out[c] = (float)(u > 0.0 ? a[c] + u * (b[c] - a[c]) : a[c]);

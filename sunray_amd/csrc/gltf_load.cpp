@@ -679,8 +679,11 @@ struct GltfLoader {
     struct BlasSkin { int32_t skin = -1; std::vector<SrSkinInfluence> influences; };
     enum { kPathTranslation = 0, kPathRotation = 1, kPathScale = 2 };
     enum { kLinear = 0, kStep = 1, kCubicSpline = 2 };
-    struct Channel { long node = -1; int path = 0, interpolation = 0; std::vector<float> times, values; };   // values: 3 or 4 floats per key
-    struct Animation { std::string name; float duration = 0.0f; uint32_t n_channels = 0, n_weights_channels = 0; bool cubic = false; std::vector<Channel> channels; };
+    struct Channel { long node = -1; int path = 0, interpolation = 0; std::vector<float> times, values; };   // values: 3 or 4 floats per key; kCubicSpline: three such rows per key
+    struct Animation { std::string name; float duration = 0.0f; uint32_t n_channels = 0, n_weights_channels = 0, n_cubic_trs = 0, n_cubic_weights = 0; bool cubic = false; std::vector<Channel> channels; };
+    // sr_gltf_set_cubicspline: read where a call meets a CUBICSPLINE sampler, never by the parse, so the kept animations serve both modes
+    uint32_t cubicspline = SR_CUBICSPLINE_REFUSE;
+    bool refuse_cubic() { return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED); }
     std::map<uint32_t, SkinData> skins;
     std::map<uint32_t, BlasSkin> blas_skins;
     std::map<uint32_t, Animation> animations;
@@ -786,7 +789,13 @@ struct GltfLoader {
             const Json* path = target ? target->get("path") : nullptr;
             if (!target || !path || path->kind != Json::Str) { fail("animation channel without a target path"); return nullptr; }
             Channel k;
-            if (path->str == "weights") { r.n_weights_channels++; continue; }       // morph targets: ignored, counted
+            if (path->str == "weights") {                                           // morph targets: ignored, counted
+                r.n_weights_channels++;
+                const long wsi = ch.index("sampler");
+                const Json* wip = samps && wsi >= 0 && (size_t)wsi < samps->size() ? samps->arr[wsi].get("interpolation") : nullptr;
+                if (wip && wip->kind == Json::Str && wip->str == "CUBICSPLINE") r.n_cubic_weights++;
+                continue;
+            }
             if (path->str == "translation") k.path = kPathTranslation;
             else if (path->str == "rotation") k.path = kPathRotation;
             else if (path->str == "scale") k.path = kPathScale;
@@ -798,7 +807,7 @@ struct GltfLoader {
             const std::string mode = ip && ip->kind == Json::Str ? ip->str : "LINEAR";
             if (mode == "LINEAR") k.interpolation = kLinear;
             else if (mode == "STEP") k.interpolation = kStep;
-            else if (mode == "CUBICSPLINE") { k.interpolation = kCubicSpline; r.cubic = true; }
+            else if (mode == "CUBICSPLINE") { k.interpolation = kCubicSpline; r.cubic = true; r.n_cubic_trs++; }
             else { fail("animation sampler with an unknown interpolation '" + mode + "'"); return nullptr; }
             const Json* ia = element("accessors", smp.index("input"));
             if (!ia || (int)ia->number("componentType", 0) != 5126) { fail("animation sampler input must be a float SCALAR accessor"); return nullptr; }
@@ -926,8 +935,9 @@ struct GltfLoader {
             const Json& smp = samps->arr[si];
             const Json* ip = smp.get("interpolation");
             const std::string mode = ip && ip->kind == Json::Str ? ip->str : "LINEAR";
-            if (mode == "CUBICSPLINE") return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED);
-            if (mode != "LINEAR" && mode != "STEP") return fail("animation sampler with an unknown interpolation '" + mode + "'");
+            const bool cubic = mode == "CUBICSPLINE";
+            if (cubic && cubicspline != SR_CUBICSPLINE_SAMPLE) return refuse_cubic();
+            if (!cubic && mode != "LINEAR" && mode != "STEP") return fail("animation sampler with an unknown interpolation '" + mode + "'");
             const Json* ia = element("accessors", smp.index("input"));
             if (!ia || (int)ia->number("componentType", 0) != 5126) return fail("animation sampler input must be a float SCALAR accessor");
             std::vector<float> times, values;
@@ -939,20 +949,26 @@ struct GltfLoader {
             const Json* oa = element("accessors", smp.index("output"));
             if (!oa || (int)oa->number("componentType", 0) != 5126) return fail("animation sampler output of a weights channel must be a float SCALAR accessor");
             if (!read_floats(smp.index("output"), 1, values, &nv)) return false;
+            if (cubic && nv < 3 * nt * (size_t)n_targets) return fail("CUBICSPLINE animation sampler output holds fewer values than three times its input's keys times the morph targets");
             if (nv < nt * (size_t)n_targets) return fail("animation sampler output holds fewer values than its input has keys times the morph targets");
-            for (size_t v = 0; v < nt * (size_t)n_targets; v++)
+            for (size_t v = 0; v < (cubic ? 3 : 1) * nt * (size_t)n_targets; v++)
                 if (!std::isfinite(values[v])) return fail("animation sampler output holds a non-finite value");
             const double time = (double)time_seconds;
             size_t i = 0;
-            double u = 0.0;
+            double u = 0.0, td = 0.0;
             if (time <= (double)times[0]) i = 0;
             else if (time >= (double)times[nt - 1]) i = nt - 1;
             else {
                 size_t lo = 0, hi = nt - 1;                                          // times[lo] <= time < times[hi]
                 while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if ((double)times[mid] <= time) lo = mid; else hi = mid; }
                 i = lo;
-                if (mode == "LINEAR") u = (time - (double)times[i]) / ((double)times[i + 1] - (double)times[i]);
+                if (mode != "STEP") { td = (double)times[i + 1] - (double)times[i]; u = (time - (double)times[i]) / td; }
             }
+            for (uint32_t k = 0; cubic && k < n_targets; k++) {                       // per key: n_targets in-tangents, values, out-tangents
+                const float* key = &values[i * 3 * n_targets];
+                weights_out[k] = u > 0.0 ? (float)hermite(key[n_targets + k], key[2 * (size_t)n_targets + k], key[4 * (size_t)n_targets + k], key[3 * (size_t)n_targets + k], u, td) : key[n_targets + k];
+            }
+            if (cubic) return true;
             for (uint32_t k = 0; k < n_targets; k++) {
                 const double a = values[i * n_targets + k], b = values[(u > 0.0 ? i + 1 : i) * n_targets + k];
                 weights_out[k] = (float)(u > 0.0 ? a + u * (b - a) : a);
@@ -964,29 +980,47 @@ struct GltfLoader {
 
     // One channel at `time` (clamped to the first / last key), in double from the fp32 keys, rounded once: out[3] or out[4].
     // Rotations: spherical linear interpolation along the shorter arc between the normalised keys; every sampled rotation is normalised.
+    // CUBICSPLINE (glTF 2.0, appendix C) between key i (value v0, out-tangent b0) and key i + 1 (in-tangent a1, value v1) at the
+    // fraction u of their distance td: the Hermite form in double, with exactly this grouping; the caller rounds once.
+    static double hermite(double v0, double b0, double v1, double a1, double u, double td) {
+        const double u2 = u * u, u3 = u2 * u;
+        const double h00 = (2.0 * u3 - 3.0 * u2) + 1.0, h10 = (u3 - 2.0 * u2) + u, h01 = 3.0 * u2 - 2.0 * u3, h11 = u3 - u2;
+        return ((h00 * v0 + h10 * (td * b0)) + h01 * v1) + h11 * (td * a1);
+    }
+    // A CUBICSPLINE channel's keys are three rows each (in-tangent, value, out-tangent), taken as the file gives them: neither
+    // normalised nor sign-flipped. A rotation is normalised afterwards in every case, at a key too; a zero sum stays zero.
     static void sample_channel(const Channel& k, double time, float* out) {
         const int comps = k.path == kPathRotation ? 4 : 3;
         const size_t n = k.times.size();
         size_t i = 0;
-        double u = 0.0;
+        double u = 0.0, td = 0.0;
         if (time <= (double)k.times[0]) i = 0;
         else if (time >= (double)k.times[n - 1]) i = n - 1;
         else {
             size_t lo = 0, hi = n - 1;                                            // times[lo] <= time < times[hi]
             while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if ((double)k.times[mid] <= time) lo = mid; else hi = mid; }
             i = lo;
-            if (k.interpolation == kLinear) u = (time - (double)k.times[i]) / ((double)k.times[i + 1] - (double)k.times[i]);
+            if (k.interpolation != kStep) { td = (double)k.times[i + 1] - (double)k.times[i]; u = (time - (double)k.times[i]) / td; }
         }
         double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0}, r[4];
+        auto normalise = [](double* q) {
+            const double len = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+            if (len > 0.0) for (int c = 0; c < 4; c++) q[c] /= len;
+        };
+        if (k.interpolation == kCubicSpline) {
+            const float* key = &k.values[i * 3 * comps];
+            for (int c = 0; c < 4; c++) r[c] = 0.0;
+            for (int c = 0; c < comps; c++)
+                r[c] = u > 0.0 ? hermite(key[comps + c], key[2 * comps + c], key[4 * comps + c], key[3 * comps + c], u, td) : (double)key[comps + c];
+            if (k.path == kPathRotation) normalise(r);
+            for (int c = 0; c < comps; c++) out[c] = (float)r[c];
+            return;
+        }
         for (int c = 0; c < comps; c++) { a[c] = k.values[i * comps + c]; b[c] = k.values[(u > 0.0 ? i + 1 : i) * comps + c]; }
         if (k.path != kPathRotation) {
             for (int c = 0; c < comps; c++) out[c] = (float)(u > 0.0 ? a[c] + u * (b[c] - a[c]) : a[c]);
             return;
         }
-        auto normalise = [](double* q) {
-            const double len = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-            if (len > 0.0) for (int c = 0; c < 4; c++) q[c] /= len;
-        };
         normalise(a);
         for (int c = 0; c < 4; c++) r[c] = a[c];
         if (u > 0.0) {
@@ -1033,7 +1067,7 @@ struct GltfLoader {
         if (anim < 0) return true;
         const Animation* a = animation((uint32_t)anim);
         if (!a) return false;
-        if (a->cubic) return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED);
+        if (a->cubic && cubicspline != SR_CUBICSPLINE_SAMPLE) return refuse_cubic();
         if (!std::isfinite(time_seconds)) return fail("the time of a pose must be finite");
         for (const Channel& k : a->channels) {
             NodeTrs& n = trs[k.node];
@@ -1111,7 +1145,7 @@ struct GltfLoader {
         if (anim >= 0) {
             a = animation((uint32_t)anim);
             if (!a) return false;
-            if (a->cubic) return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED);
+            if (a->cubic && cubicspline != SR_CUBICSPLINE_SAMPLE) return refuse_cubic();
         }
         std::vector<BakeVisit> visits;
         long scene_index = doc.index("scene");
@@ -1155,9 +1189,10 @@ struct GltfLoader {
             for (size_t e = c + 1; e < a->channels.size() && !later; e++) later = a->channels[e].node == k.node && a->channels[e].path == k.path;
             if (later) continue;
             const uint32_t comps = k.path == kPathRotation ? 4 : 3, nk = (uint32_t)k.times.size();
-            p.channels.push_back(srd::ClipChannel{node, (uint32_t)k.path, k.interpolation == kStep ? srd::kClipStep : srd::kClipLinear, nk, (uint32_t)p.times.size(), (uint32_t)p.values.size(), {0, 0}});
+            const uint32_t mode = k.interpolation == kStep ? srd::kClipStep : k.interpolation == kCubicSpline ? srd::kClipCubic : srd::kClipLinear;
+            p.channels.push_back(srd::ClipChannel{node, (uint32_t)k.path, mode, nk, (uint32_t)p.times.size(), (uint32_t)p.values.size(), {0, 0}});
             p.times.insert(p.times.end(), k.times.begin(), k.times.end());
-            p.values.insert(p.values.end(), k.values.begin(), k.values.begin() + (size_t)nk * comps);
+            p.values.insert(p.values.end(), k.values.begin(), k.values.begin() + (size_t)nk * comps * (mode == srd::kClipCubic ? 3 : 1));   // a cubic key: three rows
             p.nodes[node].animated |= 1u << k.path;
             clip.duration = std::fmax(clip.duration, k.times[nk - 1]);
         }
@@ -1201,8 +1236,9 @@ struct GltfLoader {
             const Json& smp = samps->arr[si];
             const Json* ip = smp.get("interpolation");
             const std::string mode = ip && ip->kind == Json::Str ? ip->str : "LINEAR";
-            if (mode == "CUBICSPLINE") return fail("CUBICSPLINE animation samplers are not supported", SR_ERR_UNSUPPORTED);
-            if (mode != "LINEAR" && mode != "STEP") return fail("animation sampler with an unknown interpolation '" + mode + "'");
+            const bool cubic = mode == "CUBICSPLINE";
+            if (cubic && cubicspline != SR_CUBICSPLINE_SAMPLE) return refuse_cubic();
+            if (!cubic && mode != "LINEAR" && mode != "STEP") return fail("animation sampler with an unknown interpolation '" + mode + "'");
             const Json* ia = element("accessors", smp.index("input"));
             if (!ia || (int)ia->number("componentType", 0) != 5126) return fail("animation sampler input must be a float SCALAR accessor");
             size_t nt = 0, nv = 0;
@@ -1213,13 +1249,15 @@ struct GltfLoader {
             const Json* oa = element("accessors", smp.index("output"));
             if (!oa || (int)oa->number("componentType", 0) != 5126) return fail("animation sampler output of a weights channel must be a float SCALAR accessor");
             if (!read_floats(smp.index("output"), 1, values, &nv)) return false;
+            const size_t rows = cubic ? 3 : 1;                                       // a cubic key: in-tangents, values, out-tangents
+            if (cubic && nv < 3 * nt * (size_t)bm.n_targets) return fail("CUBICSPLINE animation sampler output holds fewer values than three times its input's keys times the morph targets");
             if (nv < nt * (size_t)bm.n_targets) return fail("animation sampler output holds fewer values than its input has keys times the morph targets");
-            for (size_t v = 0; v < nt * (size_t)bm.n_targets; v++)
+            for (size_t v = 0; v < rows * nt * (size_t)bm.n_targets; v++)
                 if (!std::isfinite(values[v])) return fail("animation sampler output holds a non-finite value");
-            if (nt * (size_t)bm.n_targets >= (1ull << 31)) return fail("a weights channel of 2^31 values or more is not supported in a baked clip", SR_ERR_UNSUPPORTED);
-            times.resize(nt); values.resize(nt * (size_t)bm.n_targets);
+            if (rows * nt * (size_t)bm.n_targets >= (1ull << 31)) return fail("a weights channel of 2^31 values or more is not supported in a baked clip", SR_ERR_UNSUPPORTED);
+            times.resize(nt); values.resize(rows * nt * (size_t)bm.n_targets);
             set.n_keys = (uint32_t)nt;
-            set.interpolation = mode == "STEP" ? srd::kClipStep : srd::kClipLinear;
+            set.interpolation = mode == "STEP" ? srd::kClipStep : cubic ? srd::kClipCubic : srd::kClipLinear;
             return true;
         }
         return true;
@@ -1499,6 +1537,30 @@ int sr_gltf_animation_ignored_channels(const SrGltf* g, uint32_t i, uint32_t* n_
     const srh::GltfLoader::Animation* a = L->animation(i);
     if (!a) return srh::set_error(L->err_code, "sr_gltf_animation_ignored_channels: " + L->err);
     *n_weights_channels = a->n_weights_channels;
+    return SR_OK;
+}
+
+int sr_gltf_set_cubicspline(SrGltf* g, uint32_t mode) {
+    if (!g) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_set_cubicspline: null argument");
+    if (mode != SR_CUBICSPLINE_REFUSE && mode != SR_CUBICSPLINE_SAMPLE)
+        return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_set_cubicspline: the mode is SR_CUBICSPLINE_REFUSE or SR_CUBICSPLINE_SAMPLE");
+    g->loader->cubicspline = mode;
+    return SR_OK;
+}
+
+int sr_gltf_cubicspline(const SrGltf* g, uint32_t* mode) {
+    if (!g || !mode) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_cubicspline: null argument");
+    *mode = g->loader->cubicspline;
+    return SR_OK;
+}
+
+int sr_gltf_animation_cubic(const SrGltf* g, uint32_t i, uint32_t* n_cubic_trs_channels, uint32_t* n_cubic_weights_channels) {
+    if (!g) return srh::set_error(SR_ERR_INVALID_ARG, "sr_gltf_animation_cubic: null argument");
+    srh::GltfLoader* L = rig_loader(g);
+    const srh::GltfLoader::Animation* a = L->animation(i);
+    if (!a) return srh::set_error(L->err_code, "sr_gltf_animation_cubic: " + L->err);
+    if (n_cubic_trs_channels) *n_cubic_trs_channels = a->n_cubic_trs;
+    if (n_cubic_weights_channels) *n_cubic_weights_channels = a->n_cubic_weights;
     return SR_OK;
 }
 

@@ -331,12 +331,14 @@ class Clip:
         return nodes[:i.n_nodes], chans[:i.n_channels], inst[:i.n_instances]
 
     def channel_keys(self, channel):
-        """-> (key times [n_keys], values [n_keys, 3 or 4]) of a channel, the file's float32 (sr_clip_channel_keys)."""
+        """-> (key times [n_keys], values [n_keys, 3 or 4]) of a channel, the file's float32; a CUBICSPLINE channel's values
+        are [3 * n_keys, 3 or 4]: per key its in-tangent, value and out-tangent (sr_clip_channel_keys)."""
         c = self.layout()[1][channel]
         tp, vp = C.c_void_p(), C.c_void_p()
         check(lib().sr_clip_channel_keys(self._h, C.c_uint32(channel), C.byref(tp), C.byref(vp)))
         comps = 4 if c["path"] == 1 else 3
-        return _np_from(tp, int(c["n_keys"]), np.float32), _np_from(vp, int(c["n_keys"]) * comps, np.float32).reshape(-1, comps)
+        rows = int(c["n_keys"]) * (3 if c["interpolation"] == abi.CLIP_CUBICSPLINE else 1)
+        return _np_from(tp, int(c["n_keys"]), np.float32), _np_from(vp, rows * comps, np.float32).reshape(-1, comps)
 
     def morph_count(self):
         """-> the number of morph sets: one for every blas of the file that has morph targets (sr_clip_morph_count)."""
@@ -355,12 +357,14 @@ class Clip:
 
     def morph_keys(self, blas):
         """-> (key times [n_keys], values [n_keys, n_targets], default weights [n_targets]) of the blas's morph set, the file's
-        float32; without a channel the first two are empty (sr_clip_morph_keys)."""
+        float32; without a channel the first two are empty; a CUBICSPLINE set's values are [3 * n_keys, n_targets]: per key its
+        in-tangents, values and out-tangents (sr_clip_morph_keys)."""
         m = self.morph(blas)
         tp, vp, dp = C.c_void_p(), C.c_void_p(), C.c_void_p()
         check(lib().sr_clip_morph_keys(self._h, C.c_uint32(blas), C.byref(tp), C.byref(vp), C.byref(dp)))
         nk, nt = m["n_keys"], m["n_targets"]
-        return _np_from(tp, nk, np.float32), _np_from(vp, nk * nt, np.float32).reshape(nk, nt), _np_from(dp, nt, np.float32)
+        rows = nk * (3 if m["interpolation"] == abi.CLIP_CUBICSPLINE else 1)
+        return _np_from(tp, nk, np.float32), _np_from(vp, rows * nt, np.float32).reshape(rows, nt), _np_from(dp, nt, np.float32)
 
     def weights_host(self, time_seconds, blas, n_targets=None):
         """-> the weights [n_targets] float32 of the blas's morph set at `time_seconds`: sr_gltf_morph_weights restated over the
@@ -746,6 +750,13 @@ class Scene:
         """-> abi.SrActorPoseInfo: the last pose_actors that reached the device (sr_scene_actor_pose_info)."""
         info = abi.SrActorPoseInfo()
         check(lib().sr_scene_actor_pose_info(self._h, C.byref(info)))
+        return info
+
+    def spline_pose_info(self):
+        """-> abi.SrSplinePoseInfo: the cubic side of the last pose_actors / pose_actors_blended that reached the device: rows
+        of each weights kernel, CUBICSPLINE channels, the spline weights kernel's time (sr_scene_spline_pose_info)."""
+        info = abi.SrSplinePoseInfo()
+        check(lib().sr_scene_spline_pose_info(self._h, C.byref(info)))
         return info
 
     def read_actor_nodes(self, actor, n_nodes):
@@ -1345,6 +1356,26 @@ class Gltf:
         check(lib().sr_gltf_animation_ignored_channels(self._h, C.c_uint32(i), C.byref(nw)))
         return (name.value or b"").decode("utf-8", "replace"), dur.value, nc.value, nw.value
 
+    def set_cubicspline(self, sample):
+        """CUBICSPLINE samplers of this file: True samples them (SR_CUBICSPLINE_SAMPLE), False refuses them as ever
+        (SR_CUBICSPLINE_REFUSE, the default). Read by pose, sample_node, morph_weights and bake_clip when they meet one; a clip
+        keeps what it was baked with (sr_gltf_set_cubicspline)."""
+        check(lib().sr_gltf_set_cubicspline(self._h, C.c_uint32(abi.CUBICSPLINE_SAMPLE if sample else abi.CUBICSPLINE_REFUSE)))
+
+    @property
+    def cubicspline(self):
+        """True while CUBICSPLINE samplers are sampled (sr_gltf_cubicspline)."""
+        mode = C.c_uint32()
+        check(lib().sr_gltf_cubicspline(self._h, C.byref(mode)))
+        return mode.value == abi.CUBICSPLINE_SAMPLE
+
+    def animation_cubic(self, i):
+        """-> (translation / rotation / scale channels, `weights` channels) of animation i that name a CUBICSPLINE sampler, in
+        either mode: (0, 0) where the animation does not need set_cubicspline (sr_gltf_animation_cubic)."""
+        nc, nw = C.c_uint32(), C.c_uint32()
+        check(lib().sr_gltf_animation_cubic(self._h, C.c_uint32(i), C.byref(nc), C.byref(nw)))
+        return nc.value, nw.value
+
     def pose(self, animation, time_seconds, skin=None):
         """The file at `time_seconds` of `animation` (-1: its static pose) -> (instance transforms [n_instances, 12] float32, joint
         matrices [n_joints, 12] float32 of `skin`, or None without one) (sr_gltf_pose)."""
@@ -1654,6 +1685,12 @@ class Renderer:
     def actor_pose_info(self):
         info = abi.SrActorPoseInfo()
         check(lib().sr_renderer_actor_pose_info(self._h, C.byref(info)))
+        return info
+
+    def spline_pose_info(self):
+        """Scene.spline_pose_info of the first device slot (sr_renderer_spline_pose_info)."""
+        info = abi.SrSplinePoseInfo()
+        check(lib().sr_renderer_spline_pose_info(self._h, C.byref(info)))
         return info
 
     def set_pose_batch(self, on):
