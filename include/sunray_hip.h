@@ -1050,6 +1050,46 @@ typedef enum SrProbeHelper {
 } SrProbeHelper;
 int sr_probe_helper(uint32_t fn, const uint32_t* in, uint32_t n, uint32_t* out, void* stream);
 int sr_probe_helper_layout(uint32_t fn, uint32_t* in_dwords, uint32_t* out_dwords);
+
+/* The node step of the traversal on hand-made nodes, one per ray — a test hook (tests/test_gpu_node_step.py): the box tests of a
+ * quantised node, the ray set-up, the entry into an instance and the padded box tests of the two-level form are reached by no
+ * other hook. Row i is a whole scene of its own: a tree of ONE node whose single used child is a leaf of ONE triangle (the
+ * two-level kinds: a top-level node whose leaf holds one instance, the root node of that instance's mesh, the raw instance
+ * record). Every child dword of every node must be ~((0 << 3) | 1) in exactly one slot and -1 in the other three, or the call
+ * is refused: such a walk pushes nothing, so `tris` of a row is 1 exactly when every box test on the way to the leaf accepted,
+ * else 0, and `boxes` is 4 per node stepped. The traversal is the ray-list tracers' (per-ray tmin / tmax, counting variant).
+ * rows / out are HOST pointers to n records; the call validates, uploads the rows as they are (blas_root and tri_offset of the
+ * instance record are uploaded as 0), launches once and copies the results back. A refused call (unknown kind, null pointer
+ * with n > 0, a node that breaks the rule above) returns SR_ERR_INVALID_ARG, launches nothing and writes nothing.
+ * SR_NODE_PROBE_KEY runs no traversal: it applies the order-preserving key of the closest-hit minimum (ord_f32 / unord_f32) to
+ * ray.origin[0] (a float) and ray.origin[1] (a key, by its bits): boxes = ord(f), tris = bits of unord(ord(f)), hit.tri = bits
+ * of unord(key). */
+typedef enum SrNodeProbeKind {
+    SR_NODE_PROBE_CLOSEST = 0,
+    SR_NODE_PROBE_ANY,
+    SR_NODE_PROBE_CLOSEST_TL,
+    SR_NODE_PROBE_ANY_TL,
+    SR_NODE_PROBE_KEY,
+    SR_NODE_PROBE_COUNT
+} SrNodeProbeKind;
+typedef struct SrNodeProbeRow {   /* 336 B */
+    SrRay ray;
+    uint32_t node[16];        /* the tree's only node (two-level kinds: the top-level tree's) */
+    uint32_t tri[12];         /* the leaf's triangle record: v0, e1, e2, global index (two-level kinds: v0, v1, v2 in object space) */
+    uint32_t mesh_node[16];   /* two-level kinds: the root node of the mesh's tree */
+    uint32_t instance[32];    /* two-level kinds: the instance record as it lies in device memory (sr_scene_read_top_level) */
+} SrNodeProbeRow;
+typedef struct SrNodeProbeOut {   /* 24 B */
+    uint32_t boxes, tris;     /* the row's traversal counters */
+    SrHit hit;                /* closest kinds: the committed hit (t = -1, tri = 0xFFFFFFFF: miss); any kinds: tri = occluded, t u v = 0 */
+} SrNodeProbeOut;
+int sr_probe_node_step(uint32_t kind, const SrNodeProbeRow* rows, uint32_t n, SrNodeProbeOut* out);
+/* The instance record of the two-level form for one transform (host only): csrc/tl_record.h's arithmetic with the library's own
+ * baking limit, as the host and the device build call it. record_out: 128 bytes (w2o, o2w, pad_a, pad_b and — baked — flags
+ * bit 0 and the identity w2o are set as the host build sets them; the other words 0); result_out: 0 = ok, 1 = no finite box,
+ * 2 = baked. */
+int sr_probe_tl_record(const float* o2w, const float* mesh_lo, const float* mesh_hi, float max_abs_vertex, float max_edge_sum,
+                       void* record_out, uint32_t* result_out);
 /* The "raytracing_ris" pass (lib.rs:1662-1705): one ray_gen_ris invocation per pixel
  * (ray_gen_ris.slang:12-440): G-buffer + ReSTIR-DI reservoir + ReSTIR-GI initial reservoir. */
 int sr_trace_ris(const SrRtParams* params, void* stream);
@@ -1761,6 +1801,7 @@ static_assert(sizeof(SrRay) == 32 && sizeof(SrHit) == 16, "ray/hit");
 static_assert(sizeof(SrTraceConfig) == 40 && sizeof(SrRtParams) == 184, "T9");
 static_assert(sizeof(SrPostParams) == 104, "post params");
 static_assert(sizeof(SrStripTransfer) == 16 && sizeof(SrStripRects) == 56 && sizeof(SrStripPlane) == 16, "strip plans");
+static_assert(sizeof(SrNodeProbeRow) == 336 && sizeof(SrNodeProbeOut) == 24, "node probe rows");
 #endif
 
 #endif /* SUNRAY_HIP_H */

@@ -45,7 +45,7 @@ SYMBOLS = [
     "sr_renderer_set_light_table_build", "sr_renderer_light_table_info",
     "sr_scene_set_instances_device", "sr_scene_instance_update_info", "sr_scene_read_instance_tables", "sr_instance_tables_host",
     "sr_renderer_render_device_transforms",
-    "sr_probe_helper", "sr_probe_helper_layout", "sr_scene_light_stage_capacity",
+    "sr_probe_helper", "sr_probe_helper_layout", "sr_probe_node_step", "sr_probe_tl_record", "sr_scene_light_stage_capacity",
     "sr_scene_pose_meshes", "sr_scene_pose_batch_info", "sr_pose_batch_plan", "sr_renderer_pose_meshes", "sr_renderer_set_pose_batch",
     "sr_gltf_bake_clip", "sr_clip_destroy", "sr_clip_info", "sr_clip_skin", "sr_clip_layout", "sr_clip_channel_keys","sr_clip_sample_host", "sr_clip_compose_host", "sr_clip_pose_host",
     "sr_clip_morph_count", "sr_clip_morph", "sr_clip_morph_keys", "sr_clip_weights_host", "sr_scene_read_item_active",

@@ -353,3 +353,11 @@ PROBE_HELPERS = ("sincos", "exp", "log", "pow", "pow5", "smoothstep", "f32_to_f1
                  "pack_rgba8_snorm", "unsnorm8", "pack_b10g11r11", "unpack_b10g11r11", "pcg_hash", "init_rng", "rnd", "norm3", "reflect3",
                  "refract3", "build_onb", "smith_v_ggx", "smith_g1_ggx", "random_bounce", "sample_ggx_vndf", "eval_light", "gi_target_pdf",
                  "merge", "merge_gi", "transform_point", "intersect_tri")
+
+# SrNodeProbeKind, and the host rows of sr_probe_node_step: SrNodeProbeRow 336 B, SrNodeProbeOut 24 B
+NODE_PROBE_CLOSEST, NODE_PROBE_ANY, NODE_PROBE_CLOSEST_TL, NODE_PROBE_ANY_TL, NODE_PROBE_KEY, NODE_PROBE_COUNT = range(6)
+NODE_PROBE_ROW = np.dtype([("origin", np.float32, 3), ("tmin", np.float32), ("dir", np.float32, 3), ("tmax", np.float32),
+                           ("node", np.uint32, 16), ("tri", np.uint32, 12), ("mesh_node", np.uint32, 16), ("instance", np.uint32, 32)])
+NODE_PROBE_OUT = np.dtype([("boxes", np.uint32), ("tris", np.uint32), ("t", np.float32), ("u", np.float32), ("v", np.float32),
+                           ("tri", np.uint32)])
+TL_RECORD_OK, TL_RECORD_NO_FINITE_BOX, TL_RECORD_BAKED = 0, 1, 2   # sr_probe_tl_record's result (csrc/tl_record.h)

@@ -2815,6 +2815,26 @@ int apply_instance_list(SrScene* s);
 
 }  // namespace
 
+// Test hook (tests/node_step_reference.py): the instance record host_tl_records writes for one transform — tl_record with the
+// library's baking limit, the same words set around it — without a scene. Host only.
+int sr_probe_tl_record(const float* o2w, const float* mesh_lo, const float* mesh_hi, float max_abs_vertex, float max_edge_sum,
+                       void* record_out, uint32_t* result_out) {
+    if (!o2w || !mesh_lo || !mesh_hi || !record_out || !result_out) return fail(SR_ERR_INVALID_ARG, "sr_probe_tl_record: null pointer");
+    srd::DevTlInstance r;
+    memset(&r, 0, sizeof(r));
+    memcpy(r.o2w, o2w, 48);
+    float lo[3], hi[3];
+    const srd::TlRecordResult res = srd::tl_record(o2w, mesh_lo, mesh_hi, max_abs_vertex, max_edge_sum, kTlMaxCondition, r.w2o, lo, hi, &r.pad_a, &r.pad_b);
+    if (res == srd::kTlRecordBaked) {
+        memset(r.w2o, 0, sizeof(r.w2o));
+        r.w2o[0] = r.w2o[5] = r.w2o[10] = 1.0f;
+        r.flags = 1u;
+    }
+    memcpy(record_out, &r, sizeof(r));
+    *result_out = (uint32_t)res;
+    return SR_OK;
+}
+
 int sr_scene_set_instances(SrScene* s, const uint64_t* keys, const uint32_t* counts, uint32_t n_keys, const SrTransform* transforms) {
     uint64_t n_inst = 0;
     int rc = check_instance_list(s, keys, counts, n_keys, transforms, &n_inst);

@@ -1179,6 +1179,26 @@ def probe_helper(fn, rows, out):
     return n
 
 
+def probe_node_step(kind, rows):
+    """sr_probe_node_step: the traversal of kind abi.NODE_PROBE_* on the host rows `rows` (abi.NODE_PROBE_ROW), one hand-made
+    node per ray -> abi.NODE_PROBE_OUT per row (test hook: tests/test_gpu_node_step.py)."""
+    rows = np.ascontiguousarray(rows, dtype=abi.NODE_PROBE_ROW)
+    out = np.zeros(len(rows), dtype=abi.NODE_PROBE_OUT)
+    check(lib().sr_probe_node_step(C.c_uint32(kind), _p(rows), C.c_uint32(len(rows)), _p(out)))
+    return out
+
+
+def probe_tl_record(o2w, mesh_lo, mesh_hi, max_abs_vertex=0.0, max_edge_sum=0.0):
+    """sr_probe_tl_record: (record as one abi.TL_INSTANCE, abi.TL_RECORD_* result) of the instance transform `o2w` (3 x 4) over a
+    mesh with the root box mesh_lo .. mesh_hi. Host only."""
+    m = np.ascontiguousarray(o2w, dtype=np.float32).reshape(12)
+    lo, hi = np.ascontiguousarray(mesh_lo, dtype=np.float32).reshape(3), np.ascontiguousarray(mesh_hi, dtype=np.float32).reshape(3)
+    rec = np.zeros(1, dtype=abi.TL_INSTANCE)
+    res = C.c_uint32()
+    check(lib().sr_probe_tl_record(_p(m), _p(lo), _p(hi), C.c_float(max_abs_vertex), C.c_float(max_edge_sum), _p(rec), C.byref(res)))
+    return rec[0], res.value
+
+
 def post_chain(frame, frame_count, exposure=1.0, denoise_passes=4):
     """temporal_accumulation -> denoise_0..N-1 -> postprocess on the current stream (lib.rs:1576-1615)."""
     p = abi.post_params(frame, frame_count, lambda t: t.data_ptr(), exposure, denoise_passes)
