@@ -1534,6 +1534,95 @@ typedef struct SrClipBlendActor {      /* one character between two clips. 48 by
 int sr_scene_pose_actors_blended(SrScene* scene, const SrClipBlendActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
                                  SrTransform* d_instance_transforms, uint32_t flags, void* stream);
 int sr_scene_read_actor_sources(const SrScene* scene, uint32_t actor, SrNodeTrs* trs_a, SrNodeTrs* trs_b);
+/* Layers: an actor as a stack of 1..SR_CLIP_MAX_LAYERS layers over compatible clips (sr_clip_blend_compatible with layer 0's),
+ * applied in order onto one accumulated record per node: a walk on the legs while the arms wave (an override layer under a node
+ * mask), a breathing or hit-reaction clip added on top of whatever plays (an additive layer), more than two sources at once.
+ * The rule (csrc/clip_rule.h, shared by host and device; + - * / and sqrt in fp64 from the fp32 values, rounded once per part, no
+ * libm, so host and device agree bit for bit without exception):
+ *   Node n of layer l has the effective weight w = (double)weight_l * (double)mask_l[n] (exact); mask_l[n] is 1 without a mask.
+ *   Layer 0 is the base: its sampled records are the accumulator. It must be SR_LAYER_OVERRIDE, without a mask, at weight 1.
+ *   SR_LAYER_OVERRIDE: acc[n] = the cross-fade rule above (sr_clip_blend_host's) of acc[n] and cur[n] at w; cur is the layer's
+ *   clip sampled at time_seconds.
+ *   SR_LAYER_ADDITIVE: with ref the same clip sampled at ref_time_seconds: where w == 0 or the clip does not animate the node,
+ *   acc[n] stays, whole. Otherwise each of translation, rotation and scale is taken whole; a part whose bytes are equal in cur
+ *   and ref is copied from acc (an additive layer at its own reference time is the identity at every weight); translation and
+ *   scale are (float)(acc + w (cur - ref)) per component (a sum for scale too, on purpose: no division); the rotation is
+ *   acc (x) e normalised, with d = conj(ref) (x) cur negated where d.w < 0 and e = (w d.x, w d.y, w d.z, 1 + w (d.w - 1))
+ *   normalised, (x) the Hamilton product with each component's four terms summed left to right. The record's mask becomes
+ *   acc's | cur's | ref's.
+ * Morph weights are not layered: an item with SR_ACTOR_CLIP_WEIGHTS(blas) takes its weights from the base layer's clip at the
+ * base layer's time, by clip_weights_kernel / clip_spline_weights_kernel as in sr_scene_pose_actors.
+ * Node masks: sr_scene_attach_node_mask uploads one float per clip node, in clip-node order, each in [0, 1] (anything else, a
+ * NaN included: SR_ERR_INVALID_ARG), once, and hands out an id; sr_scene_detach_node_mask frees it (it waits for the device). A
+ * mask belongs to no clip: its length is checked against the clip's n_nodes where a layer names it. sr_clip_subtree_mask fills
+ * `out` (n_nodes floats, the clip's n_nodes) with `inside` for the clip node of glTF node `gltf_node` and everything below it in
+ * the clip's parent table and `outside` elsewhere; a node the clip does not hold: SR_ERR_INVALID_ARG.
+ * sr_clip_layers_host: the record rule over caller-given sampled records: cur[l] and ref[l] are n_nodes records each (ref[l] is
+ * read for additive layers only and may be NULL otherwise; `ref` itself may be NULL where no layer is additive). It refuses
+ * n_layers 0 or above SR_CLIP_MAX_LAYERS, a weight or a mask value outside [0, 1] or NaN, an unknown mode, an additive layer
+ * without ref, and a base layer that is additive, masked or not at weight 1.
+ * sr_clip_pose_layers_host: sample, stack, compose: clips[l] is layer l's clip; masks[l] its host mask or NULL (`masks` may be
+ * NULL); clip_id and mask_id of the layers are not read. It refuses what sr_clip_layers_host refuses, a time that is not finite
+ * (time_seconds, and ref_time_seconds of an additive layer; unless the clip is the static pose) and a clip that is not compatible
+ * with clips[0]. One layer: sr_clip_pose_host's bytes; two unmasked override layers: sr_clip_pose_blend_host's.
+ * sr_scene_pose_actors_layered is sr_scene_pose_actors for such actors: clip_layers_kernel (one block per actor) stands where
+ * clip_pose_kernel stands: it samples the layers in order, applies the rule, composes the hierarchy once and writes the joint
+ * matrices and the instance transforms exactly where sr_scene_pose_actors writes them. Everything else is sr_scene_pose_actors':
+ * the one upload (an actor's row is 80 bytes; the layers travel as a table of their own, 32 bytes a layer, in the same upload, and 64 bytes more
+ * tell the kernel where its results go), the
+ * launch sequence (3 launches accepted), the check words, the one read-back, all-or-nothing refusal, SrActorPoseInfo (`channels`
+ * counts every sample taken, so an additive layer's clip counts twice) and the read-outs (the kept TRS is the final record).
+ * Numerics: each sampled source is under sr_scene_pose_actors' contract against sr_clip_sample_host; the final records are bit
+ * equal to sr_clip_layers_host of the device's own sources, and everything composed to sr_clip_compose_records_host of the
+ * device's own records, without exception.
+ * Refused on the host before any device work, behind "pose_actors_layered: actor <i>: layer <l>: " ("actor <i>: " for what is the
+ * actor's, "item <i>: " for items); the scene is unchanged: everything sr_scene_pose_actors refuses, for every layer's clip;
+ * n_layers 0 or above SR_CLIP_MAX_LAYERS; a clip not compatible with layer 0's (sr_clip_blend_compatible's words); a weight
+ * outside [0, 1] or NaN; an unknown mode; an unknown mask id, or a mask whose length is not the clip's n_nodes; a time_seconds, or
+ * an additive layer's ref_time_seconds, that is not finite; a base layer that is additive, masked or not at weight 1.
+ * SR_ACTORS_KEEP_LAYERS: also store every layer's sampled `cur`, and `ref` for additive layers; sr_scene_read_actor_layer reads
+ * them (n_nodes records each, either may be NULL; `ref` of an override layer is left alone; SR_ERR_STATE: the last call kept
+ * none). */
+#define SR_CLIP_MAX_LAYERS 8u
+#define SR_LAYER_OVERRIDE 0u
+#define SR_LAYER_ADDITIVE 1u
+#define SR_LAYER_NO_MASK 0xFFFFFFFFu
+typedef struct SrClipLayer {           /* one layer of an actor. 32 bytes */
+    uint32_t clip_id; float time_seconds;
+    float weight; uint32_t mode;       /* weight in [0, 1]; SR_LAYER_OVERRIDE or SR_LAYER_ADDITIVE */
+    uint32_t mask_id;                  /* sr_scene_attach_node_mask's, or SR_LAYER_NO_MASK */
+    float ref_time_seconds;            /* SR_LAYER_ADDITIVE: the clip's reference time */
+    uint32_t reserved[2];
+} SrClipLayer;
+typedef struct SrClipLayerActor {      /* one character as a stack of layers. 40 bytes */
+    const SrClipLayer* layers;         /* host, n_layers of them; layers[0] is the base */
+    uint32_t n_layers, instance_base;  /* instance_base as SrClipActor's */
+    const SrTransform* placement;      /* as SrClipActor's */
+    const uint32_t* instance_rows;     /* as SrClipActor's, with the base clip's n_instances */
+    uint64_t reserved;
+} SrClipLayerActor;
+typedef struct SrClipLayerRule {       /* one layer of sr_clip_layers_host. 16 bytes */
+    float weight; uint32_t mode;
+    const float* mask;                 /* host, n_nodes floats in [0, 1], or NULL */
+} SrClipLayerRule;
+typedef struct SrLayerPoseInfo {       /* the last sr_scene_pose_actors_layered that reached the device. 32 bytes */
+    uint32_t layers, additive_layers, masked_layers;   /* over all actors; the base layers are among `layers` */
+    uint32_t max_layers;               /* the tallest stack of the call */
+    uint64_t layer_table_bytes;        /* the layer table's share of SrActorPoseInfo.upload_bytes */
+    uint64_t reserved;
+} SrLayerPoseInfo;
+#define SR_ACTORS_KEEP_LAYERS 4u       /* flags of sr_scene_pose_actors_layered: also store every layer's sampled records */
+int sr_clip_subtree_mask(const SrClip* clip, uint32_t gltf_node, float inside, float outside, float* out, uint32_t n_nodes);
+int sr_clip_layers_host(const SrNodeTrs* const* cur, const SrNodeTrs* const* ref, const SrClipLayerRule* rule, uint32_t n_layers, uint32_t n_nodes,
+                        SrNodeTrs* out);
+int sr_clip_pose_layers_host(const SrClip* const* clips, const SrClipLayer* layers, const float* const* masks, uint32_t n_layers,
+                             const SrTransform* placement, SrTransform* joint_matrices, SrTransform* instance_transforms);
+int sr_scene_attach_node_mask(SrScene* scene, const float* weights, uint32_t n_nodes, uint32_t* mask_id);
+int sr_scene_detach_node_mask(SrScene* scene, uint32_t mask_id);
+int sr_scene_pose_actors_layered(SrScene* scene, const SrClipLayerActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
+                                 SrTransform* d_instance_transforms, uint32_t flags, void* stream);
+int sr_scene_layer_pose_info(const SrScene* scene, SrLayerPoseInfo* out);
+int sr_scene_read_actor_layer(const SrScene* scene, uint32_t actor, uint32_t layer, SrNodeTrs* cur, SrNodeTrs* ref);
 
 /* What Renderer::load_gltf / load_scene return (lib.rs:779-846): the asset group and the scene's instances
  * grouped per BLAS key in BLAS order. Keys are ResourceKey{group, index} packed as group << 32 | index
@@ -1595,6 +1684,12 @@ int sr_renderer_pose_actors(SrRenderer* renderer, const SrClipActor* actors, uin
                             SrTransform* d_instance_transforms, uint32_t flags, void* stream);
 /* sr_scene_pose_actors_blended through the facade, by the same per-slot path as sr_renderer_pose_actors. */
 int sr_renderer_pose_actors_blended(SrRenderer* renderer, const SrClipBlendActor* actors, uint32_t n_actors, const SrActorPoseItem* items,
+                                    uint32_t n_items, SrTransform* d_instance_transforms, uint32_t flags, void* stream);
+/* sr_scene_attach_node_mask / sr_scene_detach_node_mask / sr_scene_pose_actors_layered through the facade: the masks live on the
+ * first device slot's scene, as the clips do, and the call takes the same per-slot path as sr_renderer_pose_actors. */
+int sr_renderer_attach_node_mask(SrRenderer* renderer, const float* weights, uint32_t n_nodes, uint32_t* mask_id);
+int sr_renderer_detach_node_mask(SrRenderer* renderer, uint32_t mask_id);
+int sr_renderer_pose_actors_layered(SrRenderer* renderer, const SrClipLayerActor* actors, uint32_t n_actors, const SrActorPoseItem* items,
                                     uint32_t n_items, SrTransform* d_instance_transforms, uint32_t flags, void* stream);
 int sr_renderer_actor_pose_info(const SrRenderer* renderer, SrActorPoseInfo* out);
 int sr_renderer_spline_pose_info(const SrRenderer* renderer, SrSplinePoseInfo* out);

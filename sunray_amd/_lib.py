@@ -54,6 +54,9 @@ SYMBOLS = [
     "sr_clip_blend_compatible", "sr_clip_blend_host", "sr_clip_compose_records_host", "sr_clip_pose_blend_host", "sr_clip_blend_weights_host",
     "sr_scene_pose_actors_blended", "sr_scene_read_actor_sources", "sr_renderer_pose_actors_blended",
     "sr_gltf_set_cubicspline", "sr_gltf_cubicspline", "sr_gltf_animation_cubic", "sr_scene_spline_pose_info", "sr_renderer_spline_pose_info",
+    "sr_clip_subtree_mask", "sr_clip_layers_host", "sr_clip_pose_layers_host", "sr_scene_attach_node_mask", "sr_scene_detach_node_mask",
+    "sr_scene_pose_actors_layered", "sr_scene_layer_pose_info", "sr_scene_read_actor_layer",
+    "sr_renderer_attach_node_mask", "sr_renderer_detach_node_mask", "sr_renderer_pose_actors_layered",
 ]
 
 

@@ -289,6 +289,29 @@ ACTORS_KEEP_SOURCES = 2  # SR_ACTORS_KEEP_SOURCES
 assert C.sizeof(SrClipBlendActor) == 48
 
 
+class SrClipLayer(C.Structure):  # one layer of an actor of sr_scene_pose_actors_layered, 32 B
+    _fields_ = [("clip_id", C.c_uint32), ("time_seconds", C.c_float), ("weight", C.c_float), ("mode", C.c_uint32), ("mask_id", C.c_uint32),
+                ("ref_time_seconds", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class SrClipLayerActor(C.Structure):  # one character as a stack of layers, 40 B
+    _fields_ = [("layers", C.c_void_p), ("n_layers", C.c_uint32), ("instance_base", C.c_uint32), ("placement", C.c_void_p), ("instance_rows", C.c_void_p),
+                ("reserved", C.c_uint64)]
+
+
+class SrClipLayerRule(C.Structure):  # one layer of sr_clip_layers_host, 16 B
+    _fields_ = [("weight", C.c_float), ("mode", C.c_uint32), ("mask", C.c_void_p)]
+
+
+class SrLayerPoseInfo(C.Structure):  # the last sr_scene_pose_actors_layered that reached the device (sr_scene_layer_pose_info), 32 B
+    _fields_ = [("layers", C.c_uint32), ("additive_layers", C.c_uint32), ("masked_layers", C.c_uint32), ("max_layers", C.c_uint32),
+                ("layer_table_bytes", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+CLIP_MAX_LAYERS, LAYER_OVERRIDE, LAYER_ADDITIVE, LAYER_NO_MASK, ACTORS_KEEP_LAYERS = 8, 0, 1, 0xFFFFFFFF, 4
+assert C.sizeof(SrClipLayer) == 32 and C.sizeof(SrClipLayerActor) == 40 and C.sizeof(SrClipLayerRule) == 16 and C.sizeof(SrLayerPoseInfo) == 32
+
+
 class SrMeshFrameInfo(C.Structure):  # one mesh's frame and its last position update (sr_scene_mesh_frame_info), 32 B
     _fields_ = [("flags", C.c_uint32), ("n_groups", C.c_uint32), ("n_entries", C.c_uint32), ("max_valence", C.c_uint32),
                 ("updates", C.c_uint32), ("first_bad", C.c_uint32), ("frame_ms", C.c_double)]

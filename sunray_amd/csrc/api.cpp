@@ -31,6 +31,7 @@
 #include "clip_pose.h"
 #include "clip_weights.h"
 #include "clip_blend.h"
+#include "clip_layers.h"
 #include "clip_spline_weights.h"
 #include "tl_record.h"
 
@@ -290,6 +291,17 @@ struct SrScene {
     // after a sr_scene_pose_actors_blended with SR_ACTORS_KEEP_SOURCES: both sources' sampled TRS, at the kept nodes' places
     bool actor_sources_kept = false;
     DeviceBuffer d_actor_source_a, d_actor_source_b;
+    // layer stacks (sr_scene_pose_actors_layered): every attached node mask's host copy and device floats, by id (ids count up and
+    // are never handed out again); the figures of the last such call that reached the device; after SR_ACTORS_KEEP_LAYERS every
+    // layer's sampled records (and those at an additive layer's reference time), at layer_base + layer * n_nodes of its actor
+    struct AttachedMask { std::vector<float> host; DeviceBuffer d_weights; };
+    std::map<uint32_t, AttachedMask> node_masks;
+    uint32_t next_mask_id = 1;
+    SrLayerPoseInfo layer_info{0, 0, 0, 0, 0, 0};
+    struct ActorLayerRecord { uint64_t layer_base; uint32_t n_layers, additive; };      // additive: bit l set where layer l is
+    std::vector<ActorLayerRecord> actor_layer_records;
+    bool actor_layers_kept = false;
+    DeviceBuffer d_actor_layer_cur, d_actor_layer_ref;
     // sr_scene_update_mesh_positions*: the face vectors of the last call (one or two 16-byte pieces per triangle), the uploaded
     // positions of the host-pointer form, and the records the mesh-frame producer wrote (scratch: the replicas of a renderer take
     // them from there)
@@ -1144,6 +1156,14 @@ struct ActorFeed {
     bool blended = false;
     std::vector<srd::ClipBlendActorRow> blend_rows;
     std::vector<srd::ClipBlendWeightRow> blend_weight_rows;
+    // a layered feed (sr_scene_pose_actors_layered): its actor rows for clip_layers_kernel stand where `rows` stand, the layer
+    // table travels behind the weight rows, and its clip-weighted items are plain ones, built from the base layers
+    bool layered = false;
+    std::vector<srd::ClipLayerActorRow> layer_actor_rows;
+    std::vector<srd::ClipLayerRow> layer_rows;
+    std::vector<SrScene::ActorLayerRecord> layer_records;
+    uint64_t n_layer_nodes = 0;
+    SrLayerPoseInfo layer_info{0, 0, 0, 0, 0, 0};
     uint32_t n_plain_rows() const { return (uint32_t)(blended ? blend_weight_rows.size() : weight_rows.size()); }
     uint32_t n_weight_rows() const { return n_plain_rows() + (uint32_t)spline_rows.size(); }
     void add_weight_item(uint32_t i, uint32_t n_targets, bool spline) {
@@ -1153,10 +1173,11 @@ struct ActorFeed {
     void count_cubic_channels(const SrClip& clip) {
         for (uint32_t k = 0; k < clip.header().n_channels; k++) n_cubic_channels += clip.channels()[k].interpolation == srd::kClipCubic ? 1u : 0u;
     }
-    size_t actor_row_bytes() const { return blended ? sizeof(srd::ClipBlendActorRow) : sizeof(srd::ClipActorRow); }
+    size_t actor_row_bytes() const { return blended ? sizeof(srd::ClipBlendActorRow) : layered ? sizeof(srd::ClipLayerActorRow) : sizeof(srd::ClipActorRow); }
+    const void* actor_row_data() const { return blended ? (const void*)blend_rows.data() : layered ? (const void*)layer_actor_rows.data() : (const void*)rows.data(); }
     size_t weight_row_bytes() const { return blended ? sizeof(srd::ClipBlendWeightRow) : sizeof(srd::ClipWeightRow); }
-    uint32_t& matrix_base(uint32_t a) { return blended ? blend_rows[a].matrix_base : rows[a].matrix_base; }
-    uint32_t node_base(uint32_t a) const { return blended ? blend_rows[a].node_base : rows[a].node_base; }
+    uint32_t& matrix_base(uint32_t a) { return blended ? blend_rows[a].matrix_base : layered ? layer_actor_rows[a].matrix_base : rows[a].matrix_base; }
+    uint32_t node_base(uint32_t a) const { return blended ? blend_rows[a].node_base : layered ? layer_actor_rows[a].node_base : rows[a].node_base; }
 };
 
 // The one posing path: sr_scene_pose_meshes (`batch`) and, with a list of one item, sr_scene_skin_mesh and sr_scene_pose_mesh.
@@ -1183,7 +1204,7 @@ struct ActorFeed {
 // clip_spline_weights_kernel runs behind the plain rows' kernel; either kernel is launched only where it has a row.
 int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stream, bool batch, SrPoseBatchInfo* out, ActorFeed* feed = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
-    const std::string who = feed ? (feed->blended ? "pose_actors_blended" : "pose_actors") : batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
+    const std::string who = feed ? (feed->blended ? "pose_actors_blended" : feed->layered ? "pose_actors_layered" : "pose_actors") : batch ? "pose_meshes" : items[0].weights ? "pose_mesh" : "skin_mesh";
     const auto prefix = [batch, &who](uint32_t i) { return batch ? who + ": item " + std::to_string(i) + ": " : std::string(); };
     // an item's skin stage: its matrices come from the caller's host pointer, or from the slice the clip kernel writes
     const auto fed = [feed](uint32_t i) { return feed && feed->item_matrix[i] != 0xFFFFFFFFu; };
@@ -1226,7 +1247,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     const size_t actor_rows_at = lay.bytes, weight_rows_at = actor_rows_at + (feed ? feed->actor_row_bytes() : 0) * (size_t)n_actors;
     const uint32_t n_plain_rows = feed ? feed->n_plain_rows() : 0, n_spline_rows = n_weight_items - n_plain_rows;
     const size_t spline_rows_at = weight_rows_at + (feed ? feed->weight_row_bytes() : 0) * (size_t)n_plain_rows;
-    const size_t inst_rows_at = spline_rows_at + sizeof(srd::ClipSplineWeightRow) * (size_t)n_spline_rows;
+    const size_t layer_rows_at = spline_rows_at + sizeof(srd::ClipSplineWeightRow) * (size_t)n_spline_rows;      // a layered feed's layer table
+    const size_t layer_targets_at = layer_rows_at + sizeof(srd::ClipLayerRow) * (feed ? feed->layer_rows.size() : 0);   // ... and where its results go
+    const size_t inst_rows_at = layer_targets_at + (feed && feed->layered ? sizeof(srd::ClipLayerTargets) : 0);
     const size_t upload_bytes = inst_rows_at + ((4 * (feed ? feed->instance_rows.size() : 0) + 15u) & ~(size_t)15u);
     const uint64_t fed_first = (upload_bytes - lay.matrices + sizeof(SrTransform) - 1) / sizeof(SrTransform);
     size_t stage_bytes = feed ? lay.matrices + sizeof(SrTransform) * (size_t)(fed_first + feed->n_matrices) : lay.bytes;
@@ -1245,6 +1268,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     const bool keep_sources = feed && feed->blended && (feed->flags & SR_ACTORS_KEEP_SOURCES);
     if (keep_sources && ((rc = s->d_actor_source_a.reserve(sizeof(SrNodeTrs) * (size_t)feed->n_nodes)) != SR_OK ||
                          (rc = s->d_actor_source_b.reserve(sizeof(SrNodeTrs) * (size_t)feed->n_nodes)) != SR_OK)) return rc;
+    const bool keep_layers = feed && feed->layered && (feed->flags & SR_ACTORS_KEEP_LAYERS);
+    if (keep_layers && ((rc = s->d_actor_layer_cur.reserve(sizeof(SrNodeTrs) * (size_t)feed->n_layer_nodes)) != SR_OK ||
+                        (rc = s->d_actor_layer_ref.reserve(sizeof(SrNodeTrs) * (size_t)feed->n_layer_nodes)) != SR_OK)) return rc;
     // the staging block: rows, block table, matrices, active lists; then the actors' rows and instance rows
     std::vector<unsigned char> stage(upload_bytes, 0);
     srd::PoseBatchItem* rows = (srd::PoseBatchItem*)(stage.data() + lay.items);
@@ -1289,7 +1315,18 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     EventPair pose_timer(s), scatter_timer(s), clip_timer(s), spline_timer(s);
     if (feed) {
         for (uint32_t a = 0; a < n_actors; a++) feed->matrix_base(a) += (uint32_t)fed_first;
-        if (n_actors) memcpy(stage.data() + actor_rows_at, feed->blended ? (const void*)feed->blend_rows.data() : (const void*)feed->rows.data(), feed->actor_row_bytes() * (size_t)n_actors);
+        if (n_actors) memcpy(stage.data() + actor_rows_at, feed->actor_row_data(), feed->actor_row_bytes() * (size_t)n_actors);
+        if (!feed->layer_rows.empty()) memcpy(stage.data() + layer_rows_at, feed->layer_rows.data(), sizeof(srd::ClipLayerRow) * feed->layer_rows.size());
+        if (feed->layered) {                                  // what srk_clip_pose takes as arguments, clip_layers_kernel reads from the upload
+            srd::ClipLayerTargets to{};
+            to.rows = (const uint32_t*)(d_stage + inst_rows_at);
+            to.matrices = (unsigned char*)s->d_pose_stage.p + lay.matrices;
+            to.instance_transforms = feed->d_instance_transforms;
+            to.check = (uint32_t*)s->d_pose_check.p + 2 * (size_t)n_items;
+            to.keep_trs = keep_nodes ? s->d_actor_trs.p : nullptr; to.keep_globals = keep_nodes ? s->d_actor_globals.p : nullptr;
+            to.keep_cur = keep_layers ? s->d_actor_layer_cur.p : nullptr; to.keep_ref = keep_layers ? s->d_actor_layer_ref.p : nullptr;
+            memcpy(stage.data() + layer_targets_at, &to, sizeof(to));
+        }
         if (n_plain_rows)
             memcpy(stage.data() + weight_rows_at, feed->blended ? (const void*)feed->blend_weight_rows.data() : (const void*)feed->weight_rows.data(), feed->weight_row_bytes() * (size_t)n_plain_rows);
         if (n_spline_rows) memcpy(stage.data() + spline_rows_at, feed->spline_rows.data(), sizeof(srd::ClipSplineWeightRow) * (size_t)n_spline_rows);
@@ -1308,6 +1345,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
             e = srk_clip_blend((const srd::ClipBlendActorRow*)(d_stage + actor_rows_at), n_actors, (const uint32_t*)(d_stage + inst_rows_at), fed_matrices, feed->d_instance_transforms,
                                actor_check, kept_trs, kept_globals, keep_sources ? (SrNodeTrs*)s->d_actor_source_a.p : nullptr,
                                keep_sources ? (SrNodeTrs*)s->d_actor_source_b.p : nullptr, st);
+        else if (e == 0 && feed->layered)
+            e = srk_clip_layers((const srd::ClipLayerActorRow*)(d_stage + actor_rows_at), n_actors, (const srd::ClipLayerRow*)(d_stage + layer_rows_at),
+                                (const srd::ClipLayerTargets*)(d_stage + layer_targets_at), st);
         else if (e == 0)
             e = srk_clip_pose((const srd::ClipActorRow*)(d_stage + actor_rows_at), n_actors, (const uint32_t*)(d_stage + inst_rows_at), fed_matrices, feed->d_instance_transforms,
                               actor_check, kept_trs, kept_globals, st);
@@ -1351,6 +1391,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
                                                                        clip_weighted(i) ? feed->item_clip_targets[i] : morph_stage(i) ? n_active[i] : 0u});
         }
         s->actor_stage_current = true; s->actor_nodes_kept = keep_nodes; s->actor_sources_kept = keep_sources;
+        s->actor_layers_kept = keep_layers;
+        s->actor_layer_records = feed->layer_records;
+        if (feed->layered) { s->layer_info = feed->layer_info; s->layer_info.layer_table_bytes = sizeof(srd::ClipLayerRow) * (uint64_t)feed->layer_rows.size(); }
         SrActorPoseInfo& ai = *feed->info;
         ai = SrActorPoseInfo{n_actors, n_items, feed->n_nodes, feed->n_channels, upload_bytes, 2u + weight_launches, 1, ai.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, n_weight_items, clip_timer.ms(), info.pose_ms, 0.0, 0.0};
         s->spline_info = SrSplinePoseInfo{n_spline_rows, n_plain_rows, feed->n_cubic_channels, n_spline_rows ? spline_timer.ms() : 0.0, 0};
@@ -1662,6 +1705,177 @@ int sr_scene_read_actor_sources(const SrScene* s, uint32_t actor, SrNodeTrs* trs
     HIP_TRY(hipDeviceSynchronize());
     if (trs_a && r.n_nodes) HIP_TRY(hipMemcpy(trs_a, (const SrNodeTrs*)s->d_actor_source_a.p + r.node_base, sizeof(SrNodeTrs) * (size_t)r.n_nodes, hipMemcpyDeviceToHost));
     if (trs_b && r.n_nodes) HIP_TRY(hipMemcpy(trs_b, (const SrNodeTrs*)s->d_actor_source_b.p + r.node_base, sizeof(SrNodeTrs) * (size_t)r.n_nodes, hipMemcpyDeviceToHost));
+    return SR_OK;
+}
+
+// ---- layer stacks ------------------------------------------------------------------------------------------------------------------
+int sr_scene_attach_node_mask(SrScene* s, const float* weights, uint32_t n_nodes, uint32_t* mask_id) {
+    if (!s || !weights || !mask_id) return fail(SR_ERR_INVALID_ARG, "attach_node_mask: null argument");
+    if (n_nodes == 0 || n_nodes > SR_CLIP_MAX_NODES) return fail(SR_ERR_INVALID_ARG, "attach_node_mask: the number of nodes is not in [1, SR_CLIP_MAX_NODES]");
+    for (uint32_t n = 0; n < n_nodes; n++)
+        if (!(weights[n] >= 0.0f && weights[n] <= 1.0f)) return fail(SR_ERR_INVALID_ARG, "attach_node_mask: node " + std::to_string(n) + ": the value is not in [0, 1]");
+    if (s->next_mask_id == 0xFFFFFFFFu) return fail(SR_ERR_UNSUPPORTED, "attach_node_mask: the scene has handed out 2^32 - 2 mask ids");
+    int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    SrScene::AttachedMask m;
+    m.host.assign(weights, weights + n_nodes);
+    if ((rc = m.d_weights.upload(weights, 4 * (size_t)n_nodes)) != SR_OK) return rc;
+    *mask_id = s->next_mask_id++;
+    s->node_masks.emplace(*mask_id, std::move(m));
+    return SR_OK;
+}
+
+int sr_scene_detach_node_mask(SrScene* s, uint32_t mask_id) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "detach_node_mask: null argument (the scene)");
+    const auto it = s->node_masks.find(mask_id);
+    if (it == s->node_masks.end()) return fail(SR_ERR_INVALID_ARG, "detach_node_mask: no node mask is attached under this id");
+    const int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());                          // a clip kernel in flight reads the mask
+    s->node_masks.erase(it);
+    return SR_OK;
+}
+
+// sr_scene_pose_actors for actors that are stacks of layers: the same checks, for every layer's clip, the stack's own (the rule's
+// constraints, the masks, the compatibility with the base clip: each pair of ids is compared once a call); the rest is pose_items
+// with a layered feed. Every table the kernel reads beside the layers' channels is the base clip's. A clip-weighted item is the
+// plain call's, from the base layer: morph weights are not layered.
+int sr_scene_pose_actors_layered(SrScene* s, const SrClipLayerActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
+                                 SrTransform* d_instance_transforms, uint32_t flags, void* stream) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: null argument (the scene)");
+    if (flags & ~(SR_ACTORS_KEEP_NODES | SR_ACTORS_KEEP_LAYERS)) return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: unknown flag bits (SR_ACTORS_KEEP_NODES and SR_ACTORS_KEEP_LAYERS are the flags)");
+    if (n_actors == 0 && n_items == 0) return SR_OK;
+    if ((n_actors && !actors) || (n_items && !items)) return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: null argument (actors or items, with a count > 0)");
+    if (((uintptr_t)d_instance_transforms & 15u) != 0) return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: the instance transforms are not 16-byte aligned");
+    ActorFeed feed;
+    feed.n_actors = n_actors; feed.flags = flags; feed.d_instance_transforms = d_instance_transforms; feed.info = &s->actor_info; feed.layered = true;
+    std::vector<const SrScene::AttachedClip*> base_of(n_actors);
+    std::vector<uint32_t> first_matrix(n_actors);
+    std::set<std::pair<uint32_t, uint32_t>> compatible;
+    for (uint32_t a = 0; a < n_actors; a++) {
+        const SrClipLayerActor& ac = actors[a];
+        const auto prefix = [a](const std::string& text) { return "pose_actors_layered: actor " + std::to_string(a) + ": " + text; };
+        if (ac.n_layers == 0 || ac.n_layers > SR_CLIP_MAX_LAYERS) return fail(SR_ERR_INVALID_ARG, prefix("the number of layers is not in [1, SR_CLIP_MAX_LAYERS]"));
+        if (!ac.layers) return fail(SR_ERR_INVALID_ARG, prefix("null argument (the layers)"));
+        SrScene::ActorLayerRecord record{feed.n_layer_nodes, ac.n_layers, 0u};
+        const SrScene::AttachedClip* base = nullptr;
+        for (uint32_t l = 0; l < ac.n_layers; l++) {
+            const SrClipLayer& ly = ac.layers[l];
+            const auto layer = [a, l](const std::string& text) { return "pose_actors_layered: actor " + std::to_string(a) + ": layer " + std::to_string(l) + ": " + text; };
+            const auto ic = s->clips.find(ly.clip_id);
+            if (ic == s->clips.end()) return fail(SR_ERR_INVALID_ARG, layer("no clip is attached under this id"));
+            const SrClip& clip = ic->second.host;
+            if (l == 0) base = &ic->second;
+            if (!(ly.weight >= 0.0f && ly.weight <= 1.0f)) return fail(SR_ERR_INVALID_ARG, layer("the weight is not in [0, 1]"));
+            if (ly.mode != SR_LAYER_OVERRIDE && ly.mode != SR_LAYER_ADDITIVE) return fail(SR_ERR_INVALID_ARG, layer("unknown mode (SR_LAYER_OVERRIDE and SR_LAYER_ADDITIVE are the modes)"));
+            const bool additive = ly.mode == SR_LAYER_ADDITIVE;
+            if (l == 0 && (additive || ly.mask_id != SR_LAYER_NO_MASK || ly.weight != 1.0f))
+                return fail(SR_ERR_INVALID_ARG, layer("the base layer must be SR_LAYER_OVERRIDE, without a mask, at weight 1"));
+            if (clip.animation >= 0 && (!std::isfinite(ly.time_seconds) || (additive && !std::isfinite(ly.ref_time_seconds))))
+                return fail(SR_ERR_INVALID_ARG, layer("gltf: the time of a pose must be finite"));
+            if (l && ly.clip_id != ac.layers[0].clip_id && !compatible.count({ac.layers[0].clip_id, ly.clip_id})) {
+                const int rc = sr_clip_blend_compatible(&base->host, &clip);
+                if (rc != SR_OK) return fail(rc, layer(g_last_error));
+                compatible.insert({ac.layers[0].clip_id, ly.clip_id});
+            }
+            const float* d_mask = nullptr;
+            if (ly.mask_id != SR_LAYER_NO_MASK) {
+                const auto im = s->node_masks.find(ly.mask_id);
+                if (im == s->node_masks.end()) return fail(SR_ERR_INVALID_ARG, layer("no node mask is attached under this id"));
+                if (im->second.host.size() != clip.header().n_nodes)
+                    return fail(SR_ERR_INVALID_ARG, layer("the mask has " + std::to_string(im->second.host.size()) + " values, the clip " + std::to_string(clip.header().n_nodes) + " nodes"));
+                d_mask = (const float*)im->second.d_weights.p;
+                feed.layer_info.masked_layers++;
+            }
+            srd::ClipLayerRow row{};
+            row.clip = ic->second.d_block.p; row.mask = d_mask;
+            row.time_seconds = ly.time_seconds; row.ref_time_seconds = additive ? ly.ref_time_seconds : 0.0f; row.weight = ly.weight; row.mode = ly.mode;
+            feed.layer_rows.push_back(row);
+            feed.n_channels += (uint64_t)clip.header().n_channels * (additive ? 2u : 1u);
+            feed.count_cubic_channels(clip);
+            if (additive) { feed.count_cubic_channels(clip); feed.layer_info.additive_layers++; record.additive |= 1u << l; }
+        }
+        const srd::ClipHeader& h = base->host.header();
+        if (!d_instance_transforms && (ac.instance_rows || ac.instance_base)) return fail(SR_ERR_INVALID_ARG, prefix("instance rows or an instance base given without device instance transforms"));
+        for (int c = 0; ac.placement && c < 12; c++)
+            if (!std::isfinite(ac.placement->m[c])) return fail(SR_ERR_INVALID_ARG, prefix("the placement has a component that is not finite"));
+        if (!ac.instance_rows && (uint64_t)ac.instance_base + h.n_instances > 0xFFFFFFFFull) return fail(SR_ERR_INVALID_ARG, prefix("the instance base plus the clip's instances passes 2^32 rows"));
+        srd::ClipLayerActorRow row{};
+        row.first_layer = (uint32_t)(feed.layer_rows.size() - ac.n_layers); row.n_layers = ac.n_layers;
+        row.flags = (ac.placement ? 1u : 0u) | (ac.instance_rows ? 2u : 0u);
+        row.matrix_base = (uint32_t)feed.n_matrices; row.instance_base = ac.instance_base; row.rows_base = (uint32_t)feed.instance_rows.size();
+        row.node_base = (uint32_t)feed.n_nodes; row.layer_node_base = (uint32_t)feed.n_layer_nodes;
+        if (ac.placement) memcpy(row.placement, ac.placement->m, 48);
+        if (ac.instance_rows) feed.instance_rows.insert(feed.instance_rows.end(), ac.instance_rows, ac.instance_rows + h.n_instances);
+        feed.layer_actor_rows.push_back(row);
+        feed.layer_records.push_back(record);
+        feed.actor_joints.push_back(h.n_joints); feed.actor_nodes.push_back(h.n_nodes);
+        base_of[a] = base; first_matrix[a] = (uint32_t)feed.n_matrices;
+        feed.n_matrices += h.n_joints; feed.n_nodes += h.n_nodes; feed.n_layer_nodes += (uint64_t)h.n_nodes * ac.n_layers;
+        feed.layer_info.layers += ac.n_layers; feed.layer_info.max_layers = std::max(feed.layer_info.max_layers, ac.n_layers);
+        if (feed.n_matrices >= (1ull << 32) || feed.n_layer_nodes >= (1ull << 32) || feed.instance_rows.size() >= (1ull << 32))
+            return fail(SR_ERR_UNSUPPORTED, "pose_actors_layered: the call holds 2^32 joint matrices, layer nodes or instance rows or more");
+    }
+    std::vector<SrPoseItem> pose(n_items);
+    feed.item_matrix.assign(n_items, 0xFFFFFFFFu);
+    feed.item_weight_row.assign(n_items, 0xFFFFFFFFu); feed.item_clip_targets.assign(n_items, 0u);
+    feed.item_row_at.assign(n_items, 0u); feed.item_spline.assign(n_items, 0);
+    for (uint32_t i = 0; i < n_items; i++) {
+        const SrActorPoseItem& it = items[i];
+        const auto prefix = [i]() { return "pose_actors_layered: item " + std::to_string(i) + ": "; };
+        pose[i] = SrPoseItem{it.key, it.weights, nullptr, it.n_targets, 0};
+        if (it.morph && it.weights) return fail(SR_ERR_INVALID_ARG, prefix() + "host weights given together with SR_ACTOR_CLIP_WEIGHTS (one source of weights at most)");
+        if (it.skin == SR_ACTOR_NO_SKIN && !it.morph) continue;
+        if (it.actor >= n_actors) return fail(SR_ERR_INVALID_ARG, prefix() + "actor " + std::to_string(it.actor) + " named, the call has " + std::to_string(n_actors) + " actors");
+        if (it.morph) {                                          // the weights of a morph set of the base layer's clip, at the base layer's time
+            const SrClip& clip = base_of[it.actor]->host;
+            const float time_seconds = actors[it.actor].layers[0].time_seconds;
+            const uint32_t blas = it.morph - 1;
+            const int k = clip.find_morph_set(blas);
+            if (k < 0) return fail(SR_ERR_INVALID_ARG, prefix() + "the weights of blas " + std::to_string(blas) + " named, the actor's clip has no morph set for it");
+            const srd::ClipMorphSet& set = clip.morph_sets()[k];
+            if (set.state == srd::kClipMorphUnavailable) return fail((int32_t)set.status, prefix() + clip.morph_errors[k]);
+            const bool spline = set.n_keys && set.interpolation == srd::kClipCubic;
+            feed.add_weight_item(i, set.n_targets, spline);
+            if (spline) {
+                srd::ClipSplineWeightRow row{};
+                row.clip_a = base_of[it.actor]->d_block.p; row.time_a = time_seconds; row.set_a = (uint32_t)k;
+                feed.spline_rows.push_back(row);
+            } else {
+                srd::ClipWeightRow row{};
+                row.clip = base_of[it.actor]->d_block.p; row.time_seconds = time_seconds; row.set = (uint32_t)k;
+                feed.weight_rows.push_back(row);
+            }
+        }
+        if (it.skin == SR_ACTOR_NO_SKIN) continue;
+        uint32_t first = 0, n_joints = 0;
+        if (sr_clip_skin(&base_of[it.actor]->host, it.skin, &first, &n_joints) != SR_OK) return fail(SR_ERR_INVALID_ARG, prefix() + "skin " + std::to_string(it.skin) + " named, no instanced mesh of the actor's clip wears it");
+        pose[i].n_joints = n_joints;
+        feed.item_matrix[i] = first_matrix[it.actor] + first;
+    }
+    SrPoseBatchInfo dropped{};                                // sr_scene_pose_batch_info reads as before the call
+    return pose_items(s, pose.data(), n_items, stream, true, &dropped, &feed);
+}
+
+int sr_scene_layer_pose_info(const SrScene* s, SrLayerPoseInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_layer_pose_info: null argument");
+    *out = s->layer_info;
+    return SR_OK;
+}
+
+int sr_scene_read_actor_layer(const SrScene* s, uint32_t actor, uint32_t layer, SrNodeTrs* cur, SrNodeTrs* ref) {
+    if (!s) return fail(SR_ERR_INVALID_ARG, "read_actor_layer: null argument (the scene)");
+    if (!s->actor_layers_kept) return fail(SR_ERR_STATE, "read_actor_layer: the last call kept no layers (sr_scene_pose_actors_layered with SR_ACTORS_KEEP_LAYERS)");
+    if (actor >= s->actor_layer_records.size() || actor >= s->actor_records.size()) return fail(SR_ERR_INVALID_ARG, "read_actor_layer: actor index out of range");
+    const SrScene::ActorLayerRecord& lr = s->actor_layer_records[actor];
+    if (layer >= lr.n_layers) return fail(SR_ERR_INVALID_ARG, "read_actor_layer: layer index out of range");
+    const uint32_t n_nodes = s->actor_records[actor].n_nodes;
+    const size_t at = (size_t)lr.layer_base + (size_t)layer * n_nodes;
+    const int rc = bind_device(s);
+    if (rc != SR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (cur && n_nodes) HIP_TRY(hipMemcpy(cur, (const SrNodeTrs*)s->d_actor_layer_cur.p + at, sizeof(SrNodeTrs) * (size_t)n_nodes, hipMemcpyDeviceToHost));
+    if (ref && n_nodes && (lr.additive >> layer & 1u)) HIP_TRY(hipMemcpy(ref, (const SrNodeTrs*)s->d_actor_layer_ref.p + at, sizeof(SrNodeTrs) * (size_t)n_nodes, hipMemcpyDeviceToHost));
     return SR_OK;
 }
 

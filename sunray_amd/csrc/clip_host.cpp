@@ -1,6 +1,7 @@
 // Baked clips: the read-outs and the host rule (sr_clip_sample_host, sr_clip_compose_host, sr_clip_pose_host), which
 // restates sr_gltf_pose over the flat tables with the arithmetic of clip_rule.h, and the host rule of cross-fades between two clips
-// (sr_clip_blend_compatible, sr_clip_blend_host, sr_clip_compose_records_host, sr_clip_pose_blend_host, sr_clip_blend_weights_host).
+// (sr_clip_blend_compatible, sr_clip_blend_host, sr_clip_compose_records_host, sr_clip_pose_blend_host, sr_clip_blend_weights_host),
+// and the host rule of layer stacks (sr_clip_subtree_mask, sr_clip_layers_host, sr_clip_pose_layers_host).
 // No HIP in this file.
 #include "clip.h"
 
@@ -248,6 +249,96 @@ int sr_clip_blend_weights_host(const SrClip* a, float time_a, const SrClip* b, f
     if ((rc = weights_of(b, time_b, blas, wb.data(), n_targets, "sr_clip_blend_weights_host")) != SR_OK) return rc;
     for (uint32_t t = 0; t < n_targets; t++) weights_out[t] = srd::clip_blend_weight(wa[t], wb[t], (double)weight);
     return SR_OK;
+}
+
+// ---- layers: the host rule of sr_scene_pose_actors_layered -----------------------------------------------------------------------
+static_assert(SR_CLIP_MAX_LAYERS == srd::kClipMaxLayers && SR_LAYER_OVERRIDE == srd::kClipLayerOverride && SR_LAYER_ADDITIVE == srd::kClipLayerAdditive,
+              "the header states the rule's constants");
+static_assert(sizeof(SrClipLayer) == 32 && sizeof(SrClipLayerRule) == 16 && sizeof(SrClipLayerActor) == 40 && sizeof(SrLayerPoseInfo) == 32, "the header states these sizes");
+
+int sr_clip_subtree_mask(const SrClip* clip, uint32_t gltf_node, float inside, float outside, float* out, uint32_t n_nodes) {
+    if (!clip || !out) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_subtree_mask: null argument");
+    const srd::ClipHeader& h = clip->header();
+    if (n_nodes != h.n_nodes) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_subtree_mask: room for another number of nodes than the clip has");
+    bool found = false;
+    std::vector<char> in(h.n_nodes, 0);
+    for (uint32_t n = 0; n < h.n_nodes; n++) {                  // parents come first
+        const srd::ClipNode& c = clip->nodes()[n];
+        in[n] = c.gltf_node == gltf_node || (c.parent != srd::kClipNoNode && in[c.parent]);
+        found = found || c.gltf_node == gltf_node;
+    }
+    if (!found) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_subtree_mask: the clip does not hold this glTF node");
+    for (uint32_t n = 0; n < h.n_nodes; n++) out[n] = in[n] ? inside : outside;
+    return SR_OK;
+}
+
+// What a stack's rule refuses, wherever the stack comes from: `who` names the caller, `layer` the words in front of a layer's refusal.
+static int check_layer_rule(uint32_t l, float weight, uint32_t mode, bool masked, const std::string& who) {
+    if (!blend_weight_ok(weight)) return srh::set_error(SR_ERR_INVALID_ARG, who + "the weight is not in [0, 1]");
+    if (mode != SR_LAYER_OVERRIDE && mode != SR_LAYER_ADDITIVE) return srh::set_error(SR_ERR_INVALID_ARG, who + "unknown mode (SR_LAYER_OVERRIDE and SR_LAYER_ADDITIVE are the modes)");
+    if (l == 0 && (mode != SR_LAYER_OVERRIDE || masked || weight != 1.0f))
+        return srh::set_error(SR_ERR_INVALID_ARG, who + "the base layer must be SR_LAYER_OVERRIDE, without a mask, at weight 1");
+    return SR_OK;
+}
+static bool mask_values_ok(const float* mask, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) if (!blend_weight_ok(mask[i])) return false;
+    return true;
+}
+
+int sr_clip_layers_host(const SrNodeTrs* const* cur, const SrNodeTrs* const* ref, const SrClipLayerRule* rule, uint32_t n_layers, uint32_t n_nodes, SrNodeTrs* out) {
+    if (!cur || !rule || (n_nodes && !out)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_layers_host: null argument");
+    if (n_layers == 0 || n_layers > SR_CLIP_MAX_LAYERS) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_layers_host: the number of layers is not in [1, SR_CLIP_MAX_LAYERS]");
+    for (uint32_t l = 0; l < n_layers; l++) {
+        const std::string who = "sr_clip_layers_host: layer " + std::to_string(l) + ": ";
+        const int rc = check_layer_rule(l, rule[l].weight, rule[l].mode, rule[l].mask != nullptr, who);
+        if (rc != SR_OK) return rc;
+        if (n_nodes && (!cur[l] || (rule[l].mode == SR_LAYER_ADDITIVE && (!ref || !ref[l])))) return srh::set_error(SR_ERR_INVALID_ARG, who + "null argument (the sampled records)");
+        if (rule[l].mask && !mask_values_ok(rule[l].mask, n_nodes)) return srh::set_error(SR_ERR_INVALID_ARG, who + "the mask has a value that is not in [0, 1]");
+    }
+    for (uint32_t n = 0; n < n_nodes; n++) {
+        uint32_t acc[srd::kClipTrsWords], c[srd::kClipTrsWords], r[srd::kClipTrsWords], next[srd::kClipTrsWords];
+        memcpy(acc, &cur[0][n], sizeof(acc));
+        for (uint32_t l = 1; l < n_layers; l++) {
+            const double w = srd::clip_layer_weight(rule[l].weight, rule[l].mask, n);
+            memcpy(c, &cur[l][n], sizeof(c));
+            if (rule[l].mode == SR_LAYER_ADDITIVE) { memcpy(r, &ref[l][n], sizeof(r)); srd::clip_additive_record(acc, c, r, w, next); }
+            else srd::clip_blend_record(acc, c, w, next);
+            memcpy(acc, next, sizeof(acc));
+        }
+        memcpy(&out[n], acc, sizeof(acc));
+    }
+    return SR_OK;
+}
+
+int sr_clip_pose_layers_host(const SrClip* const* clips, const SrClipLayer* layers, const float* const* masks, uint32_t n_layers, const SrTransform* placement,
+                             SrTransform* joint_matrices, SrTransform* instance_transforms) {
+    if (!clips || !layers) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_pose_layers_host: null argument");
+    if (n_layers == 0 || n_layers > SR_CLIP_MAX_LAYERS) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_pose_layers_host: the number of layers is not in [1, SR_CLIP_MAX_LAYERS]");
+    for (uint32_t l = 0; l < n_layers; l++) if (!clips[l]) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_pose_layers_host: null argument");
+    const uint32_t n = clips[0]->header().n_nodes;
+    std::vector<std::vector<SrNodeTrs>> cur(n_layers), ref(n_layers);
+    std::vector<const SrNodeTrs*> cur_at(n_layers), ref_at(n_layers, nullptr);
+    std::vector<SrClipLayerRule> rule(n_layers);
+    int rc;
+    for (uint32_t l = 0; l < n_layers; l++) {
+        const std::string who = "sr_clip_pose_layers_host: layer " + std::to_string(l) + ": ";
+        const SrClipLayer& ly = layers[l];
+        const float* mask = masks ? masks[l] : nullptr;
+        if ((rc = check_layer_rule(l, ly.weight, ly.mode, mask != nullptr, who)) != SR_OK) return rc;
+        const bool additive = ly.mode == SR_LAYER_ADDITIVE;
+        if (clips[l]->animation >= 0 && (!std::isfinite(ly.time_seconds) || (additive && !std::isfinite(ly.ref_time_seconds))))
+            return srh::set_error(SR_ERR_INVALID_ARG, who + "gltf: the time of a pose must be finite");
+        if (l && clips[l] != clips[0] && (rc = sr_clip_blend_compatible(clips[0], clips[l])) != SR_OK) return rc;      // in that function's words
+        if (mask && !mask_values_ok(mask, n)) return srh::set_error(SR_ERR_INVALID_ARG, who + "the mask has a value that is not in [0, 1]");
+        cur[l].resize(n);
+        if ((rc = sr_clip_sample_host(clips[l], ly.time_seconds, cur[l].data())) != SR_OK) return rc;
+        if (additive) { ref[l].resize(n); if ((rc = sr_clip_sample_host(clips[l], ly.ref_time_seconds, ref[l].data())) != SR_OK) return rc; ref_at[l] = ref[l].data(); }
+        cur_at[l] = cur[l].data();
+        rule[l] = SrClipLayerRule{ly.weight, ly.mode, mask};
+    }
+    std::vector<SrNodeTrs> stacked(n);
+    if ((rc = sr_clip_layers_host(cur_at.data(), ref_at.data(), rule.data(), n_layers, n, stacked.data())) != SR_OK) return rc;
+    return compose(clips[0], stacked.data(), placement, joint_matrices, instance_transforms, nullptr, true, "sr_clip_pose_layers_host");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Baked clips: the flat tables of a clip and the arithmetic of its evaluation, shared by the host rule (clip_host.cpp) and the
-// device kernels (clip_pose.hip, clip_weights.hip, clip_blend.hip, clip_spline_weights.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
+// device kernels (clip_pose.hip, clip_weights.hip, clip_blend.hip, clip_spline_weights.hip, clip_layers.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
 // (gltf_load.cpp) term for term; host and device are built with -ffp-contract=off, so +, -, *, / and sqrt give the same bits on
 // both. atan2 and sin (LINEAR rotations between two keys only) come from each side's own libm; a CUBICSPLINE sample (clip_hermite)
 // needs neither, so it is bit equal between host and device without exception.
@@ -117,6 +117,41 @@ struct ClipSplineWeightRow {
     uint32_t active_base, item, check_word;                         // as ClipWeightRow's
 };
 static_assert(sizeof(ClipSplineWeightRow) == 48, "three 16-byte pieces");
+
+// A layer stack (sr_scene_pose_actors_layered): an actor has 1..kClipMaxLayers layers over compatible clips, applied in order
+// onto one accumulated record per node (the rule: clip_additive_record below and clip_blend_record).
+constexpr uint32_t kClipMaxLayers = 8;      // SR_CLIP_MAX_LAYERS
+constexpr uint32_t kClipLayerOverride = 0, kClipLayerAdditive = 1;   // SR_LAYER_OVERRIDE, SR_LAYER_ADDITIVE
+// One layer as clip_layers_kernel reads it, at wave-uniform addresses.
+struct ClipLayerRow {
+    const void* clip;           // device: the layer's clip block
+    const float* mask;          // device: one float per clip node in [0, 1], or null: 1 everywhere
+    float time_seconds, ref_time_seconds, weight;      // ref_time_seconds: an additive layer's reference time
+    uint32_t mode;              // kClipLayerOverride / kClipLayerAdditive
+};
+static_assert(sizeof(ClipLayerRow) == 32, "two 16-byte pieces");
+// One actor of a layered call: its slice of the call's layer table, and what ClipActorRow holds beside the clip and the time.
+struct ClipLayerActorRow {
+    uint32_t first_layer, n_layers;                    // layers[first_layer .. first_layer + n_layers); layer 0 is the base
+    uint32_t flags;             // as ClipActorRow.flags
+    uint32_t matrix_base, instance_base, rows_base, node_base;      // as ClipActorRow's
+    uint32_t layer_node_base;   // first of its n_layers x n_nodes records in the kept-layers buffers, layer-major
+    float placement[12];
+};
+static_assert(sizeof(ClipLayerActorRow) == 80, "five 16-byte pieces");
+// Where a layered call's results go: one per call, in the upload like the rows, read at wave-uniform addresses where each is
+// needed (ten pointers as kernel arguments would stay in scalar registers through the whole sampling loop).
+struct ClipLayerTargets {
+    const uint32_t* rows;       // the instance rows of the actors that gave some
+    void* matrices;             // 48 bytes a matrix: what clip_pose_kernel's `matrices` is
+    void* instance_transforms;  // or null: none are written
+    uint32_t* check;            // one word per actor
+    void* keep_trs;             // or null; SrNodeTrs per node: the final records
+    void* keep_globals;         // or null, with keep_trs; 64 bytes per node
+    void* keep_cur;             // or null; SrNodeTrs per layer and node: every layer's sampled records
+    void* keep_ref;             // or null, with keep_cur; an additive layer's records at its reference time
+};
+static_assert(sizeof(ClipLayerTargets) == 64, "four 16-byte pieces");
 
 // The key search of sample_channel / morph_weights: the key `i` at or before `time` (clamped to the first / last key) and the
 // fraction `u` towards key i + 1 (0: take key i as it is).
@@ -265,6 +300,67 @@ SR_CLIP_HD float clip_blend_weight(float wa, float wb, double w) {
     if (w == 1.0) return wb;
     return (float)((double)wa + w * ((double)wb - (double)wa));
 }
+
+// Layers. An actor has n_layers layers, 1 <= n_layers <= kClipMaxLayers, applied in order onto one accumulated record per node.
+// All arithmetic is + - * / and sqrt in double from the fp32 values, rounded once per part, in the grouping written here: no
+// libm, so host and device give the same bits without exception, as for clip_blend_record.
+//   Effective weight: node n of layer l has w = (double)weight_l * (double)mask_l[n]; the product of two fp32 values is exact in
+//   double. mask_l[n] is 1 where the layer has no mask.
+//   Layer 0 is the base: its sampled records are the accumulator (override, no mask, weight 1).
+//   Override layer: acc[n] = clip_blend_record(acc[n], cur[n], w); cur is the layer's clip sampled at its time.
+//   Additive layer: acc[n] = clip_additive_record(acc[n], cur[n], ref[n], w); ref is the same clip sampled at the layer's
+//   reference time.
+//     1. Where w == 0 or (cur[10] | ref[10]) == 0, out is acc, whole.
+//     2. Otherwise each of translation, rotation and scale is taken whole. A part whose bytes are equal in cur and ref is copied
+//        from acc: an additive layer at its own reference time is the identity at every weight.
+//     3. Translation and scale: (float)(acc + w * (cur - ref)) per component. Additive scale is a sum on purpose: no division,
+//        so a zero reference scale is harmless.
+//     4. Rotation, q = (x, y, z, w), Hamilton product p (x) q with each component's four terms summed left to right
+//        (clip_quat_mul): d = conj(ref) (x) cur; d is negated where d.w < 0; e = (w d.x, w d.y, w d.z, 1 + w (d.w - 1)),
+//        clip_normalise(e); out = acc (x) e, clip_normalise(out), rounded to float once.
+//     5. out[10] = acc[10] | cur[10] | ref[10]; out[11] = acc[11].
+//   A clip's channels never share a node and path, and a part without a channel has equal bytes in cur and ref; so applying
+//   clip_additive_part3 / clip_additive_rotation channel by channel onto the accumulator (clip_layers_kernel) gives the node-wise
+//   rule's bytes.
+// Morph weights are not layered: an item with SR_ACTOR_CLIP_WEIGHTS(blas) takes its weights from the base layer's clip at the base
+// layer's time (clip_weights_kernel / clip_spline_weights_kernel, from rows the host builds from layer 0).
+SR_CLIP_HD void clip_quat_mul(const double* p, const double* q, double* r) {
+    r[0] = ((p[3] * q[0] + p[0] * q[3]) + p[1] * q[2]) - p[2] * q[1];
+    r[1] = ((p[3] * q[1] - p[0] * q[2]) + p[1] * q[3]) + p[2] * q[0];
+    r[2] = ((p[3] * q[2] + p[0] * q[1]) - p[1] * q[0]) + p[2] * q[3];
+    r[3] = ((p[3] * q[3] - p[0] * q[0]) - p[1] * q[1]) - p[2] * q[2];
+}
+// Translation or scale of an additive layer: three words each; w != 0.
+SR_CLIP_HD void clip_additive_part3(const uint32_t* acc, const uint32_t* cur, const uint32_t* ref, double w, uint32_t* out) {
+    if (cur[0] == ref[0] && cur[1] == ref[1] && cur[2] == ref[2]) { for (int c = 0; c < 3; c++) out[c] = acc[c]; return; }
+    for (int c = 0; c < 3; c++)
+        out[c] = clip_float_word((float)((double)clip_word_float(acc[c]) + w * ((double)clip_word_float(cur[c]) - (double)clip_word_float(ref[c]))));
+}
+// The rotation of an additive layer: four words each; w != 0.
+SR_CLIP_HD void clip_additive_rotation(const uint32_t* acc, const uint32_t* cur, const uint32_t* ref, double w, uint32_t* out) {
+    if (cur[0] == ref[0] && cur[1] == ref[1] && cur[2] == ref[2] && cur[3] == ref[3]) { for (int c = 0; c < 4; c++) out[c] = acc[c]; return; }
+    double a[4], conj[4], now[4], d[4], e[4], r[4];
+    for (int c = 0; c < 4; c++) { a[c] = (double)clip_word_float(acc[c]); now[c] = (double)clip_word_float(cur[c]); }
+    for (int c = 0; c < 3; c++) conj[c] = -(double)clip_word_float(ref[c]);
+    conj[3] = (double)clip_word_float(ref[3]);
+    clip_quat_mul(conj, now, d);
+    if (d[3] < 0.0) for (int c = 0; c < 4; c++) d[c] = -d[c];
+    e[0] = w * d[0]; e[1] = w * d[1]; e[2] = w * d[2]; e[3] = 1.0 + w * (d[3] - 1.0);
+    clip_normalise(e);
+    clip_quat_mul(a, e, r);
+    clip_normalise(r);
+    for (int c = 0; c < 4; c++) out[c] = clip_float_word((float)r[c]);
+}
+SR_CLIP_HD void clip_additive_record(const uint32_t* acc, const uint32_t* cur, const uint32_t* ref, double w, uint32_t* out) {
+    const uint32_t mask = cur[10] | ref[10];
+    if (w == 0.0 || mask == 0u) { for (int i = 0; i < 12; i++) out[i] = acc[i]; return; }
+    clip_additive_part3(acc, cur, ref, w, out);
+    clip_additive_rotation(acc + 3, cur + 3, ref + 3, w, out + 3);
+    clip_additive_part3(acc + 7, cur + 7, ref + 7, w, out + 7);
+    out[10] = acc[10] | mask; out[11] = acc[11];
+}
+// The effective weight of a node of a layer.
+SR_CLIP_HD double clip_layer_weight(float weight, const float* mask, uint32_t node) { return (double)weight * (double)(mask ? mask[node] : 1.0f); }
 
 // trs_matrix: translation * rotation * scale, fp32, row-major 4x4.
 SR_CLIP_HD void clip_trs_matrix(const float* t, const float* q, const float* s, float* m) {

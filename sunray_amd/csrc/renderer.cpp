@@ -710,6 +710,25 @@ int sr_renderer_pose_actors_blended(SrRenderer* r, const SrClipBlendActor* actor
                              [&](SrScene* sc) { return sr_scene_pose_actors_blended(sc, actors, n_actors, items, n_items, d_instance_transforms, flags, stream); });
 }
 
+// Node masks live on the first slot's scene only, as the clips do.
+int sr_renderer_attach_node_mask(SrRenderer* r, const float* weights, uint32_t n_nodes, uint32_t* mask_id) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "attach_node_mask: null argument (the renderer)");
+    return sr_scene_attach_node_mask(r->slot[0].scene, weights, n_nodes, mask_id);
+}
+
+int sr_renderer_detach_node_mask(SrRenderer* r, uint32_t mask_id) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "detach_node_mask: null argument (the renderer)");
+    return sr_scene_detach_node_mask(r->slot[0].scene, mask_id);
+}
+
+int sr_renderer_pose_actors_layered(SrRenderer* r, const SrClipLayerActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
+                                    SrTransform* d_instance_transforms, uint32_t flags, void* stream) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "pose_actors_layered: null argument (the renderer)");
+    if (n_items && !items) return rfail(SR_ERR_INVALID_ARG, "pose_actors_layered: null argument (actors or items, with a count > 0)");
+    return first_scene_poses(r, n_items, [&](uint32_t k) { return items[k].key; },
+                             [&](SrScene* sc) { return sr_scene_pose_actors_layered(sc, actors, n_actors, items, n_items, d_instance_transforms, flags, stream); });
+}
+
 int sr_renderer_actor_pose_info(const SrRenderer* r, SrActorPoseInfo* out) {
     if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_actor_pose_info: null argument (the renderer)");
     return sr_scene_actor_pose_info(r->slot[0].scene, out);

@@ -276,7 +276,58 @@ class BlendedActorArgs(ActorArgs):
             self.actors[a].time_seconds_b, self.actors[a].weight = float(t), float(w)
 
 
-def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index, keep_sources=False, packed=ActorArgs):
+class LayeredActorArgs(ActorArgs):
+    """The arguments of pose_actors_layered packed once: ActorArgs with `actors` a sequence of (layers, placement, instance rows,
+    instance base), `layers` a sequence of 1..abi.CLIP_MAX_LAYERS of (clip id, time, weight in [0, 1], mode: "override" /
+    "additive" or abi.LAYER_*, mask id or None, reference time of an additive layer); the first is the base. The layers of all
+    actors lie in one array; set_times() rewrites every layer's time in place (one sequence per actor, one time per layer),
+    set_layer() one layer's time, weight and reference time."""
+    WHO, ROW = "pose_actors_layered", abi.SrClipLayerActor
+    MODES = {"override": abi.LAYER_OVERRIDE, "additive": abi.LAYER_ADDITIVE}
+
+    def __init__(self, actors, items):
+        actors = [tuple(a) for a in actors]
+        for a, ac in enumerate(actors):
+            if len(ac) != 4:
+                raise ValueError("pose_actors_layered: actor %d: an actor is (layers, placement, instance rows, instance base), %d values given" % (a, len(ac)))
+        stacks = [[tuple(ly) for ly in ac[0]] for ac in actors]
+        self.layers = (abi.SrClipLayer * max(sum(len(st) for st in stacks), 1))()
+        self.first_layer, at = [], 0
+        for a, st in enumerate(stacks):
+            self.first_layer.append(at)
+            for l, ly in enumerate(st):
+                if len(ly) != 6:
+                    raise ValueError("pose_actors_layered: actor %d: layer %d: a layer is (clip id, time, weight, mode, mask id, reference time), %d values given"
+                                     % (a, l, len(ly)))
+                row = self.layers[at + l]
+                row.clip_id, row.time_seconds, row.weight = int(ly[0]), float(ly[1]), float(ly[2])
+                row.mode = self.MODES[ly[3]] if isinstance(ly[3], str) else int(ly[3])
+                row.mask_id, row.ref_time_seconds = abi.LAYER_NO_MASK if ly[4] is None else int(ly[4]), float(ly[5])
+            at += len(st)
+        self.n_layers = [len(st) for st in stacks]
+        super().__init__(actors, items)
+
+    def _actor(self, a, ac, row):
+        row.layers = C.addressof(self.layers) + C.sizeof(abi.SrClipLayer) * self.first_layer[a]
+        row.n_layers, row.instance_base = self.n_layers[a], int(ac[3])
+        self._placed(a, row, ac[1], ac[2])
+
+    def set_times(self, times):
+        for a, per_layer in enumerate(times):
+            for l, t in enumerate(per_layer):
+                self.layers[self.first_layer[a] + l].time_seconds = float(t)
+
+    def set_layer(self, actor, layer, time_seconds=None, weight=None, ref_time_seconds=None):
+        row = self.layers[self.first_layer[actor] + layer]
+        if time_seconds is not None:
+            row.time_seconds = float(time_seconds)
+        if weight is not None:
+            row.weight = float(weight)
+        if ref_time_seconds is not None:
+            row.ref_time_seconds = float(ref_time_seconds)
+
+
+def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index, keep_sources=False, packed=ActorArgs, keep_layers=False):
     if isinstance(actors, ActorArgs) and type(actors) is not packed:
         raise ValueError("%s: the packed arguments are those of another entry point (%s)" % (packed.WHO, type(actors).__name__))
     args = actors if isinstance(actors, packed) else packed(actors, items)
@@ -289,7 +340,8 @@ def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index, kee
             raise ValueError("%s: the instance transforms must be contiguous float32, 12 a transform" % packed.WHO)
         ptr, stream = C.c_void_p(tensor.data_ptr()), C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)
     check(fn(handle, args.actors, C.c_uint32(args.n_actors), args.items, C.c_uint32(args.n_items), ptr,
-             C.c_uint32((abi.ACTORS_KEEP_NODES if keep_nodes else 0) | (abi.ACTORS_KEEP_SOURCES if keep_sources else 0)), stream))
+             C.c_uint32((abi.ACTORS_KEEP_NODES if keep_nodes else 0) | (abi.ACTORS_KEEP_SOURCES if keep_sources else 0) |
+                        (abi.ACTORS_KEEP_LAYERS if keep_layers else 0)), stream))
 
 
 class Clip:
@@ -424,6 +476,37 @@ class Clip:
         check(lib().sr_clip_blend_weights_host(self._h, C.c_float(time_seconds), other._h, C.c_float(time_other), C.c_float(weight), C.c_uint32(blas), _p(w), C.c_uint32(nt)))
         return w[:nt]
 
+    def subtree_mask(self, gltf_node, inside=1.0, outside=0.0):
+        """-> a node mask float32 [n_nodes]: `inside` for the clip node of glTF node `gltf_node` and everything below it in the
+        clip's parent table, `outside` elsewhere (sr_clip_subtree_mask)."""
+        out = np.zeros(max(self.info.n_nodes, 1), np.float32)
+        check(lib().sr_clip_subtree_mask(self._h, C.c_uint32(gltf_node), C.c_float(inside), C.c_float(outside), _p(out), C.c_uint32(self.info.n_nodes)))
+        return out[:self.info.n_nodes]
+
+    def pose_layers_host(self, layers, placement=None, joints=True):
+        """-> (joint matrices or None, instance transforms) of a stack of layers whose base is this clip: `layers` is a sequence
+        of (clip, time, weight, mode: "override" / "additive" or abi.LAYER_*, host mask float32 [n_nodes] or None, reference
+        time); the first is the base and names this clip: sample, stack, compose (sr_clip_pose_layers_host)."""
+        layers = [tuple(ly) for ly in layers]
+        n = len(layers)
+        clips, rows, masks, keep = (C.c_void_p * max(n, 1))(), (abi.SrClipLayer * max(n, 1))(), (C.c_void_p * max(n, 1))(), []
+        for l, ly in enumerate(layers):
+            if len(ly) != 6:
+                raise ValueError("pose_layers_host: layer %d: a layer is (clip, time, weight, mode, mask, reference time), %d values given" % (l, len(ly)))
+            clips[l] = ly[0]._h if isinstance(ly[0], Clip) else ly[0]
+            rows[l].time_seconds, rows[l].weight, rows[l].ref_time_seconds, rows[l].mask_id = float(ly[1]), float(ly[2]), float(ly[5]), abi.LAYER_NO_MASK
+            rows[l].mode = LayeredActorArgs.MODES[ly[3]] if isinstance(ly[3], str) else int(ly[3])
+            if ly[4] is not None:
+                m = _node_mask(ly[4], "pose_layers_host: layer %d" % l)
+                keep.append(m)
+                masks[l] = m.ctypes.data
+        i = self.info
+        jm = np.zeros((max(i.n_joints, 1), 12), np.float32) if joints else None
+        xf = np.zeros((max(i.n_instances, 1), 12), np.float32)
+        pl = None if placement is None else np.ascontiguousarray(placement, dtype=np.float32).reshape(12)
+        check(lib().sr_clip_pose_layers_host(clips, rows, masks, C.c_uint32(n), None if pl is None else _p(pl), None if jm is None else _p(jm), _p(xf)))
+        return (None if jm is None else jm[:i.n_joints]), xf[:i.n_instances]
+
     def pose_host(self, time_seconds, placement=None, joints=True):
         """-> (joint matrices of all skins [n_joints, 12] or None, instance transforms [n_instances, 12]) at `time_seconds`:
         sr_gltf_pose restated over the clip, bit for bit (sr_clip_pose_host)."""
@@ -443,6 +526,48 @@ def clip_blend_host(trs_a, trs_b, weight):
     out = np.zeros(max(len(a), 1), abi.NODE_TRS)
     check(lib().sr_clip_blend_host(_p(a) if len(a) else None, _p(b) if len(b) else None, C.c_uint32(len(a)), C.c_float(weight), _p(out)))
     return out[:len(a)]
+
+
+def _node_mask(mask, who):
+    """A node mask as a contiguous one-dimensional float32 array; ValueError for another dtype (no silent narrowing) or shape."""
+    if not isinstance(mask, np.ndarray) or mask.dtype != np.dtype(np.float32) or mask.ndim != 1 or len(mask) == 0:
+        raise ValueError("%s: a node mask must be a one-dimensional numpy float32 array, one value per clip node" % who)
+    return np.ascontiguousarray(mask)
+
+
+def clip_layers_host(cur, rules, ref=None):
+    """The layer rule over sampled records: `cur` a sequence of abi.NODE_TRS arrays, one per layer (the first is the base), `rules`
+    one (weight, mode: "override" / "additive" or abi.LAYER_*, host mask float32 [n_nodes] or None) per layer, `ref` a sequence
+    with an additive layer's records at its reference time (None elsewhere), or None -> the final records
+    (sr_clip_layers_host)."""
+    cur = [np.ascontiguousarray(c, dtype=abi.NODE_TRS) for c in cur]
+    rules = [tuple(r) for r in rules]
+    n = len(cur)
+    if len(rules) != n or (ref is not None and len(ref) != n):
+        raise ValueError("clip_layers_host: one rule (and, where given, one reference entry) per layer")
+    n_nodes = len(cur[0]) if n else 0
+    if any(c.ndim != 1 or len(c) != n_nodes for c in cur):
+        raise ValueError("clip_layers_host: every layer must hold the same number of records")
+    refs = [None if ref is None or r is None else np.ascontiguousarray(r, dtype=abi.NODE_TRS) for r in (ref or [None] * n)]
+    if any(r is not None and (r.ndim != 1 or len(r) != n_nodes) for r in refs):
+        raise ValueError("clip_layers_host: every layer must hold the same number of records")
+    cp, rp, rows, keep = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))(), (abi.SrClipLayerRule * max(n, 1))(), []
+    for l in range(n):
+        if len(rules[l]) != 3:
+            raise ValueError("clip_layers_host: layer %d: a rule is (weight, mode, mask), %d values given" % (l, len(rules[l])))
+        cp[l] = cur[l].ctypes.data if n_nodes else None
+        rp[l] = refs[l].ctypes.data if refs[l] is not None and n_nodes else None
+        rows[l].weight = float(rules[l][0])
+        rows[l].mode = LayeredActorArgs.MODES[rules[l][1]] if isinstance(rules[l][1], str) else int(rules[l][1])
+        if rules[l][2] is not None:
+            m = _node_mask(rules[l][2], "clip_layers_host: layer %d" % l)
+            if len(m) != n_nodes:
+                raise ValueError("clip_layers_host: layer %d: the mask has %d values, the layers %d records" % (l, len(m), n_nodes))
+            keep.append(m)
+            rows[l].mask = m.ctypes.data
+    out = np.zeros(max(n_nodes, 1), abi.NODE_TRS)
+    check(lib().sr_clip_layers_host(cp, rp, rows, C.c_uint32(n), C.c_uint32(n_nodes), _p(out)))
+    return out[:n_nodes]
 
 
 def pose_batch_plan(n_vertices):
@@ -738,6 +863,37 @@ class Scene:
         BlendedActorArgs), the rest as pose_actors; keep_sources also stores both sources' sampled TRS for read_actor_sources
         (sr_scene_pose_actors_blended)."""
         _actor_call(lib().sr_scene_pose_actors_blended, self._h, actors, items, tensor, keep_nodes, self.device_index, keep_sources, BlendedActorArgs)
+
+    def attach_node_mask(self, weights):
+        """Uploads a node mask once, one float32 in [0, 1] per clip node in clip-node order -> its id on this scene
+        (sr_scene_attach_node_mask)."""
+        m, mid = _node_mask(weights, "attach_node_mask"), C.c_uint32()
+        check(lib().sr_scene_attach_node_mask(self._h, _p(m), C.c_uint32(len(m)), C.byref(mid)))
+        return mid.value
+
+    def detach_node_mask(self, mask_id):
+        check(lib().sr_scene_detach_node_mask(self._h, C.c_uint32(mask_id)))
+
+    def pose_actors_layered(self, actors, items=(), tensor=None, keep_nodes=False, keep_layers=False):
+        """pose_actors for actors that are stacks of layers over attached clips: `actors` as LayeredActorArgs takes them (or a
+        LayeredActorArgs), the rest as pose_actors; keep_layers also stores every layer's sampled records for read_actor_layer
+        (sr_scene_pose_actors_layered)."""
+        _actor_call(lib().sr_scene_pose_actors_layered, self._h, actors, items, tensor, keep_nodes, self.device_index, False, LayeredActorArgs, keep_layers)
+
+    def read_actor_layer(self, actor, layer, n_nodes):
+        """-> (abi.NODE_TRS [n_nodes], abi.NODE_TRS [n_nodes]): layer `layer`'s sampled records of an actor of the last
+        pose_actors_layered with keep_layers, and those at its reference time (zeros for an override layer)
+        (sr_scene_read_actor_layer)."""
+        cur, ref = np.zeros(max(n_nodes, 1), abi.NODE_TRS), np.zeros(max(n_nodes, 1), abi.NODE_TRS)
+        check(lib().sr_scene_read_actor_layer(self._h, C.c_uint32(actor), C.c_uint32(layer), _p(cur), _p(ref)))
+        return cur[:n_nodes], ref[:n_nodes]
+
+    def layer_pose_info(self):
+        """-> abi.SrLayerPoseInfo: the layers, additive layers, masked layers and layer-table bytes of the last
+        pose_actors_layered that reached the device (sr_scene_layer_pose_info)."""
+        info = abi.SrLayerPoseInfo()
+        check(lib().sr_scene_layer_pose_info(self._h, C.byref(info)))
+        return info
 
     def read_actor_sources(self, actor, n_nodes):
         """-> (abi.NODE_TRS [n_nodes], abi.NODE_TRS [n_nodes]): both sources' sampled TRS of an actor of the last
@@ -1701,6 +1857,19 @@ class Renderer:
     def pose_actors_blended(self, actors, items=(), tensor=None, keep_nodes=False, keep_sources=False):
         """Scene.pose_actors_blended on the first device slot, as pose_actors (sr_renderer_pose_actors_blended)."""
         _actor_call(lib().sr_renderer_pose_actors_blended, self._h, actors, items, tensor, keep_nodes, self.devices[0], keep_sources, BlendedActorArgs)
+
+    def attach_node_mask(self, weights):
+        """Scene.attach_node_mask on the first device slot's scene (sr_renderer_attach_node_mask)."""
+        m, mid = _node_mask(weights, "attach_node_mask"), C.c_uint32()
+        check(lib().sr_renderer_attach_node_mask(self._h, _p(m), C.c_uint32(len(m)), C.byref(mid)))
+        return mid.value
+
+    def detach_node_mask(self, mask_id):
+        check(lib().sr_renderer_detach_node_mask(self._h, C.c_uint32(mask_id)))
+
+    def pose_actors_layered(self, actors, items=(), tensor=None, keep_nodes=False, keep_layers=False):
+        """Scene.pose_actors_layered on the first device slot, as pose_actors (sr_renderer_pose_actors_layered)."""
+        _actor_call(lib().sr_renderer_pose_actors_layered, self._h, actors, items, tensor, keep_nodes, self.devices[0], False, LayeredActorArgs, keep_layers)
 
     def actor_pose_info(self):
         info = abi.SrActorPoseInfo()
