@@ -1550,8 +1550,9 @@ int sr_scene_read_actor_sources(const SrScene* scene, uint32_t actor, SrNodeTrs*
  *   acc (x) e normalised, with d = conj(ref) (x) cur negated where d.w < 0 and e = (w d.x, w d.y, w d.z, 1 + w (d.w - 1))
  *   normalised, (x) the Hamilton product with each component's four terms summed left to right. The record's mask becomes
  *   acc's | cur's | ref's.
- * Morph weights are not layered: an item with SR_ACTOR_CLIP_WEIGHTS(blas) takes its weights from the base layer's clip at the
- * base layer's time, by clip_weights_kernel / clip_spline_weights_kernel as in sr_scene_pose_actors.
+ * Morph weights: without SR_ACTORS_LAYER_WEIGHTS they are not layered: an item with SR_ACTOR_CLIP_WEIGHTS(blas) takes its weights
+ * from the base layer's clip at the base layer's time, by clip_weights_kernel / clip_spline_weights_kernel as in
+ * sr_scene_pose_actors. With the flag they go through the stack (see SR_ACTORS_LAYER_WEIGHTS below).
  * Node masks: sr_scene_attach_node_mask uploads one float per clip node, in clip-node order, each in [0, 1] (anything else, a
  * NaN included: SR_ERR_INVALID_ARG), once, and hands out an id; sr_scene_detach_node_mask frees it (it waits for the device). A
  * mask belongs to no clip: its length is checked against the clip's n_nodes where a layer names it. sr_clip_subtree_mask fills
@@ -1623,6 +1624,51 @@ int sr_scene_pose_actors_layered(SrScene* scene, const SrClipLayerActor* actors,
                                  SrTransform* d_instance_transforms, uint32_t flags, void* stream);
 int sr_scene_layer_pose_info(const SrScene* scene, SrLayerPoseInfo* out);
 int sr_scene_read_actor_layer(const SrScene* scene, uint32_t actor, uint32_t layer, SrNodeTrs* cur, SrNodeTrs* ref);
+/* Layered morph weights. SR_ACTORS_LAYER_WEIGHTS is a flag of sr_scene_pose_actors_layered and sr_renderer_pose_actors_layered
+ * only (the plain and blended calls refuse the bit). With it every item whose `morph` is SR_ACTOR_CLIP_WEIGHTS(blas) takes the
+ * stack's weights for that blas: a blink, a breath or a viseme clip as an additive layer over whatever the body plays. Without it
+ * the call is byte for byte what it was: same rows, same kernels, same launch count, same info.
+ * The rule (csrc/clip_rule.h, shared by host and device, no libm), per morph set (per blas) and per target k, on fp32 weights, in
+ * fp64 in exactly this grouping, each layer's result rounded to fp32 once:
+ *   cur_l[k] is layer l's clip's set for the blas sampled at time_seconds as sr_clip_weights_host samples it (LINEAR, STEP,
+ *   CUBICSPLINE, or the defaults where the set has no keys); an additive layer also has ref_l[k], sampled at ref_time_seconds.
+ *   w_l = (double)weight_l * (double)m (exact), m the layer's mask value at the clip node whose gltf_node is the set's gltf_node;
+ *   m is 1 where the layer has no mask or the clip holds no such node.
+ *   acc = cur_0. SR_LAYER_OVERRIDE: acc[k] = the cross-fade rule of sr_clip_blend_weights_host of acc[k] and cur_l[k] at w_l.
+ *   SR_LAYER_ADDITIVE: acc[k] stays where w_l == 0 or cur_l[k] and ref_l[k] are the same word (an additive layer at its own
+ *   reference time is the identity at every weight); otherwise (float)(acc[k] + w_l (cur_l[k] - ref_l[k])).
+ *   After the last layer the targets whose weight is +0 or -0 are left out, the rest kept in ascending target order.
+ * sr_clip_layer_weights_host: the rule over caller-given weight vectors: cur[l] and ref[l] are n_targets floats each (ref[l] is
+ * read for additive layers only and may be NULL otherwise; `ref` itself may be NULL where no layer is additive); weight, mode and
+ * mask_value are arrays of n_layers; mask_value may be NULL: all 1. It refuses what sr_clip_layers_host refuses, with "mask value"
+ * for a mask: a mask value outside [0, 1] or NaN, and a base layer whose mask value is not 1.
+ * sr_clip_weights_layers_host: sample, resolve each mask's node, stack: clips, layers and masks as sr_clip_pose_layers_host takes
+ * them. A clip without a set for the blas, an unavailable set and a wrong n_targets are refused in sr_clip_weights_host's statuses
+ * and words behind "layer <l>: "; so are a clip not compatible with clips[0] and sets of unequal n_targets across the layers. One
+ * layer: sr_clip_weights_host's bytes; two unmasked override layers: sr_clip_blend_weights_host's.
+ * On the device clip_layer_weights_kernel (one wave per item, one launch per call, behind clip_layers_kernel and in front of the
+ * posing kernel) stands where clip_weights_kernel and clip_spline_weights_kernel stand: a row of 32 bytes per item and an entry of
+ * 16 bytes per item and layer travel in the one upload. SrActorPoseInfo.weight_items counts the rows, `launches` is 4 for an
+ * accepted call with a row, and SrSplinePoseInfo reports 0 plain and 0 spline rows, since neither older kernel ran. The active
+ * lists are bit equal to the compaction of sr_clip_weights_layers_host, without exception; sr_scene_read_item_active reads them.
+ * Refused on the host before any device work, behind "pose_actors_layered: item <i>: layer <l>: ": a layer's clip without a set
+ * for the blas, or with the set unavailable (its kept status and the loader's words); the base layer's set ("layer 0: ") whose
+ * n_targets is not the mesh's attached morph's; a layer's set whose n_targets is not the base layer's. A layer at weight 0 is
+ * checked like any other (the kernel does not sample it). A mesh without a morph is refused in sr_scene_pose_actors' words.
+ * SrLayerWeightsInfo: the figures of the last layered call that reached the device (all 0 where it had no flag or no such item). */
+#define SR_ACTORS_LAYER_WEIGHTS 8u     /* flags of sr_scene_pose_actors_layered: clip-weighted items take the stack's weights */
+typedef struct SrLayerWeightsInfo {    /* 32 bytes */
+    uint32_t rows;                     /* items posed with the stack's weights */
+    uint32_t samples, cubic_samples;   /* set samples taken (an additive layer counts twice); those of CUBICSPLINE sets */
+    uint32_t reserved;
+    uint64_t table_bytes;              /* the rows' and entries' share of SrActorPoseInfo.upload_bytes */
+    double weights_ms;                 /* clip_layer_weights_kernel, from events; 0 unless sr_scene_enable_timing is on */
+} SrLayerWeightsInfo;
+int sr_clip_layer_weights_host(const float* const* cur, const float* const* ref, const float* weight, const uint32_t* mode, const float* mask_value,
+                               uint32_t n_layers, uint32_t n_targets, float* out);
+int sr_clip_weights_layers_host(const SrClip* const* clips, const SrClipLayer* layers, const float* const* masks, uint32_t n_layers, uint32_t blas,
+                                float* weights_out, uint32_t n_targets);
+int sr_scene_layer_weights_info(const SrScene* scene, SrLayerWeightsInfo* out);
 
 /* What Renderer::load_gltf / load_scene return (lib.rs:779-846): the asset group and the scene's instances
  * grouped per BLAS key in BLAS order. Keys are ResourceKey{group, index} packed as group << 32 | index
@@ -1692,6 +1738,7 @@ int sr_renderer_detach_node_mask(SrRenderer* renderer, uint32_t mask_id);
 int sr_renderer_pose_actors_layered(SrRenderer* renderer, const SrClipLayerActor* actors, uint32_t n_actors, const SrActorPoseItem* items,
                                     uint32_t n_items, SrTransform* d_instance_transforms, uint32_t flags, void* stream);
 int sr_renderer_actor_pose_info(const SrRenderer* renderer, SrActorPoseInfo* out);
+int sr_renderer_layer_weights_info(const SrRenderer* renderer, SrLayerWeightsInfo* out);
 int sr_renderer_spline_pose_info(const SrRenderer* renderer, SrSplinePoseInfo* out);
 /* How sr_renderer_pose_scene poses a loaded scene's rigged and morphed meshes: SR_POSE_BATCH_OFF (the default), one
  * sr_renderer_skin_mesh / sr_renderer_pose_mesh per mesh (each a batch of one item); SR_POSE_BATCH_ON, all of them by one sr_renderer_pose_meshes.

@@ -57,6 +57,7 @@ SYMBOLS = [
     "sr_clip_subtree_mask", "sr_clip_layers_host", "sr_clip_pose_layers_host", "sr_scene_attach_node_mask", "sr_scene_detach_node_mask",
     "sr_scene_pose_actors_layered", "sr_scene_layer_pose_info", "sr_scene_read_actor_layer",
     "sr_renderer_attach_node_mask", "sr_renderer_detach_node_mask", "sr_renderer_pose_actors_layered",
+    "sr_clip_layer_weights_host", "sr_clip_weights_layers_host", "sr_scene_layer_weights_info", "sr_renderer_layer_weights_info",
 ]
 
 

@@ -312,6 +312,15 @@ CLIP_MAX_LAYERS, LAYER_OVERRIDE, LAYER_ADDITIVE, LAYER_NO_MASK, ACTORS_KEEP_LAYE
 assert C.sizeof(SrClipLayer) == 32 and C.sizeof(SrClipLayerActor) == 40 and C.sizeof(SrClipLayerRule) == 16 and C.sizeof(SrLayerPoseInfo) == 32
 
 
+class SrLayerWeightsInfo(C.Structure):  # the clip-weighted items of the last layered call that reached the device (sr_scene_layer_weights_info), 32 B
+    _fields_ = [("rows", C.c_uint32), ("samples", C.c_uint32), ("cubic_samples", C.c_uint32), ("reserved", C.c_uint32),
+                ("table_bytes", C.c_uint64), ("weights_ms", C.c_double)]
+
+
+ACTORS_LAYER_WEIGHTS = 8  # SR_ACTORS_LAYER_WEIGHTS
+assert C.sizeof(SrLayerWeightsInfo) == 32
+
+
 class SrMeshFrameInfo(C.Structure):  # one mesh's frame and its last position update (sr_scene_mesh_frame_info), 32 B
     _fields_ = [("flags", C.c_uint32), ("n_groups", C.c_uint32), ("n_entries", C.c_uint32), ("max_valence", C.c_uint32),
                 ("updates", C.c_uint32), ("first_bad", C.c_uint32), ("frame_ms", C.c_double)]

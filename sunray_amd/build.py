@@ -14,10 +14,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsunray_hip.so")
-SOURCES = ["kernels.hip", "post.hip", "bvh_gpu.hip", "blas_batch.hip", "pose_batch.hip", "clip_pose.hip", "clip_weights.hip", "clip_blend.hip", "clip_spline_weights.hip", "clip_layers.hip", "normals.hip", "lights.hip", "instances.hip", "helper_probe.hip", "node_probe.hip", "node_probe_rows.cpp", "api.cpp", "renderer.cpp", "multi_renderer.cpp", "strip_copy.hip", "multi_gpu.cpp", "gltf_load.cpp", "jpeg_decode.cpp", "host_prep.cpp", "bvh_build.cpp", "mesh_frame.cpp", "pose_batch_plan.cpp", "clip_host.cpp"]
-HEADERS = ["rt_device.h", "traverse.h", "bvh_layout.h", "kernels.h", "host.h", "bvh_gpu.h", "bvh_device.h", "blas_batch.h", "pose_device.h", "pose_batch.h", "pose_batch_plan.h", "clip_rule.h", "clip.h", "clip_pose.h", "clip_weights.h", "clip_blend.h", "clip_spline_weights.h", "clip_layers.h", "normals.h", "mesh_frame.h", "vertex_tile.h", "lights.h", "instances.h", "tl_record.h", "node_probe.h", "renderer.h", "strip_copy.h", os.path.join("..", "..", "include", "sunray_hip.h")]
+SOURCES = ["kernels.hip", "post.hip", "bvh_gpu.hip", "blas_batch.hip", "pose_batch.hip", "clip_pose.hip", "clip_weights.hip", "clip_blend.hip", "clip_spline_weights.hip", "clip_layers.hip", "clip_layer_weights.hip", "normals.hip", "lights.hip", "instances.hip", "helper_probe.hip", "node_probe.hip", "node_probe_rows.cpp", "api.cpp", "renderer.cpp", "multi_renderer.cpp", "strip_copy.hip", "multi_gpu.cpp", "gltf_load.cpp", "jpeg_decode.cpp", "host_prep.cpp", "bvh_build.cpp", "mesh_frame.cpp", "pose_batch_plan.cpp", "clip_host.cpp"]
+HEADERS = ["rt_device.h", "traverse.h", "bvh_layout.h", "kernels.h", "host.h", "bvh_gpu.h", "bvh_device.h", "blas_batch.h", "pose_device.h", "pose_batch.h", "pose_batch_plan.h", "clip_rule.h", "clip.h", "clip_pose.h", "clip_weights.h", "clip_blend.h", "clip_spline_weights.h", "clip_layers.h", "clip_layer_weights.h", "normals.h", "mesh_frame.h", "vertex_tile.h", "lights.h", "instances.h", "tl_record.h", "node_probe.h", "renderer.h", "strip_copy.h", os.path.join("..", "..", "include", "sunray_hip.h")]
 RESOURCES = os.path.join(HERE, "_obj", "kernels.hip.resources.txt")     # the compiler's per-kernel register / scratch report
-REPORTED = ("kernels.hip", "bvh_gpu.hip", "blas_batch.hip", "pose_batch.hip", "clip_pose.hip", "clip_weights.hip", "clip_blend.hip", "clip_spline_weights.hip", "clip_layers.hip", "normals.hip", "lights.hip", "instances.hip")   # sources whose report is kept: the pass kernels, the builder kernels, the batched mesh-tree build, posing, the clip evaluation, the clips' morph weights, the clips' cross-fades, the clips' cubic morph weights, the clips' layer stacks, the mesh frame, the light table, the instance tables
+REPORTED = ("kernels.hip", "bvh_gpu.hip", "blas_batch.hip", "pose_batch.hip", "clip_pose.hip", "clip_weights.hip", "clip_blend.hip", "clip_spline_weights.hip", "clip_layers.hip", "clip_layer_weights.hip", "normals.hip", "lights.hip", "instances.hip")   # sources whose report is kept: the pass kernels, the builder kernels, the batched mesh-tree build, posing, the clip evaluation, the clips' morph weights, the clips' cross-fades, the clips' cubic morph weights, the clips' layer stacks, the stacks' morph weights, the mesh frame, the light table, the instance tables
 
 
 def resources_path(source):

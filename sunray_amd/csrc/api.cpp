@@ -33,6 +33,7 @@
 #include "clip_blend.h"
 #include "clip_layers.h"
 #include "clip_spline_weights.h"
+#include "clip_layer_weights.h"
 #include "tl_record.h"
 
 namespace {
@@ -298,6 +299,7 @@ struct SrScene {
     std::map<uint32_t, AttachedMask> node_masks;
     uint32_t next_mask_id = 1;
     SrLayerPoseInfo layer_info{0, 0, 0, 0, 0, 0};
+    SrLayerWeightsInfo layer_weights_info{0, 0, 0, 0, 0, 0.0};      // ... with SR_ACTORS_LAYER_WEIGHTS: its clip-weighted items
     struct ActorLayerRecord { uint64_t layer_base; uint32_t n_layers, additive; };      // additive: bit l set where layer l is
     std::vector<ActorLayerRecord> actor_layer_records;
     bool actor_layers_kept = false;
@@ -1164,7 +1166,13 @@ struct ActorFeed {
     std::vector<SrScene::ActorLayerRecord> layer_records;
     uint64_t n_layer_nodes = 0;
     SrLayerPoseInfo layer_info{0, 0, 0, 0, 0, 0};
-    uint32_t n_plain_rows() const { return (uint32_t)(blended ? blend_weight_rows.size() : weight_rows.size()); }
+    // ... with SR_ACTORS_LAYER_WEIGHTS: its clip-weighted items are rows for clip_layer_weights_kernel, which stand where
+    // `weight_rows` stand (there are no spline rows), and their entries, one per row and layer, travel behind the layer table
+    bool layer_weights = false;
+    std::vector<srd::ClipLayerWeightRow> layer_weight_rows;
+    std::vector<srd::ClipLayerWeightEntry> layer_weight_entries;
+    SrLayerWeightsInfo layer_weights_info{0, 0, 0, 0, 0, 0.0};
+    uint32_t n_plain_rows() const { return (uint32_t)(blended ? blend_weight_rows.size() : layer_weights ? layer_weight_rows.size() : weight_rows.size()); }
     uint32_t n_weight_rows() const { return n_plain_rows() + (uint32_t)spline_rows.size(); }
     void add_weight_item(uint32_t i, uint32_t n_targets, bool spline) {
         item_weight_row[i] = n_weight_rows(); item_clip_targets[i] = n_targets; item_spline[i] = spline ? 1 : 0;
@@ -1175,7 +1183,8 @@ struct ActorFeed {
     }
     size_t actor_row_bytes() const { return blended ? sizeof(srd::ClipBlendActorRow) : layered ? sizeof(srd::ClipLayerActorRow) : sizeof(srd::ClipActorRow); }
     const void* actor_row_data() const { return blended ? (const void*)blend_rows.data() : layered ? (const void*)layer_actor_rows.data() : (const void*)rows.data(); }
-    size_t weight_row_bytes() const { return blended ? sizeof(srd::ClipBlendWeightRow) : sizeof(srd::ClipWeightRow); }
+    size_t weight_row_bytes() const { return blended ? sizeof(srd::ClipBlendWeightRow) : layer_weights ? sizeof(srd::ClipLayerWeightRow) : sizeof(srd::ClipWeightRow); }
+    const void* weight_row_data() const { return blended ? (const void*)blend_weight_rows.data() : layer_weights ? (const void*)layer_weight_rows.data() : (const void*)weight_rows.data(); }
     uint32_t& matrix_base(uint32_t a) { return blended ? blend_rows[a].matrix_base : layered ? layer_actor_rows[a].matrix_base : rows[a].matrix_base; }
     uint32_t node_base(uint32_t a) const { return blended ? blend_rows[a].node_base : layered ? layer_actor_rows[a].node_base : rows[a].node_base; }
 };
@@ -1249,7 +1258,8 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     const size_t spline_rows_at = weight_rows_at + (feed ? feed->weight_row_bytes() : 0) * (size_t)n_plain_rows;
     const size_t layer_rows_at = spline_rows_at + sizeof(srd::ClipSplineWeightRow) * (size_t)n_spline_rows;      // a layered feed's layer table
     const size_t layer_targets_at = layer_rows_at + sizeof(srd::ClipLayerRow) * (feed ? feed->layer_rows.size() : 0);   // ... and where its results go
-    const size_t inst_rows_at = layer_targets_at + (feed && feed->layered ? sizeof(srd::ClipLayerTargets) : 0);
+    const size_t layer_entries_at = layer_targets_at + (feed && feed->layered ? sizeof(srd::ClipLayerTargets) : 0);    // ... and its layer-weight entries
+    const size_t inst_rows_at = layer_entries_at + sizeof(srd::ClipLayerWeightEntry) * (feed ? feed->layer_weight_entries.size() : 0);
     const size_t upload_bytes = inst_rows_at + ((4 * (feed ? feed->instance_rows.size() : 0) + 15u) & ~(size_t)15u);
     const uint64_t fed_first = (upload_bytes - lay.matrices + sizeof(SrTransform) - 1) / sizeof(SrTransform);
     size_t stage_bytes = feed ? lay.matrices + sizeof(SrTransform) * (size_t)(fed_first + feed->n_matrices) : lay.bytes;
@@ -1298,6 +1308,7 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         const uint32_t check_word = (uint32_t)(2 * (size_t)n_items + n_actors + feed->item_weight_row[i]);
         if (feed->item_spline[i]) { srd::ClipSplineWeightRow& wr = feed->spline_rows[feed->item_row_at[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
         else if (feed->blended) { srd::ClipBlendWeightRow& wr = feed->blend_weight_rows[feed->item_row_at[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
+        else if (feed->layer_weights) { srd::ClipLayerWeightRow& wr = feed->layer_weight_rows[feed->item_row_at[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
         else { srd::ClipWeightRow& wr = feed->weight_rows[feed->item_row_at[i]]; wr.item = i; wr.active_base = active_base; wr.check_word = check_word; }
         rows[i].active_base = active_base;
         active_base += feed->item_clip_targets[i];
@@ -1312,7 +1323,7 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
     const srd::PoseBatchItem* d_rows = (const srd::PoseBatchItem*)(d_stage + lay.items);
     const uint32_t* d_table = (const uint32_t*)(d_stage + lay.block_table);
     std::vector<uint32_t> bad(n_check, 0xFFFFFFFFu);
-    EventPair pose_timer(s), scatter_timer(s), clip_timer(s), spline_timer(s);
+    EventPair pose_timer(s), scatter_timer(s), clip_timer(s), spline_timer(s), layer_weights_timer(s);
     if (feed) {
         for (uint32_t a = 0; a < n_actors; a++) feed->matrix_base(a) += (uint32_t)fed_first;
         if (n_actors) memcpy(stage.data() + actor_rows_at, feed->actor_row_data(), feed->actor_row_bytes() * (size_t)n_actors);
@@ -1328,7 +1339,9 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
             memcpy(stage.data() + layer_targets_at, &to, sizeof(to));
         }
         if (n_plain_rows)
-            memcpy(stage.data() + weight_rows_at, feed->blended ? (const void*)feed->blend_weight_rows.data() : (const void*)feed->weight_rows.data(), feed->weight_row_bytes() * (size_t)n_plain_rows);
+            memcpy(stage.data() + weight_rows_at, feed->weight_row_data(), feed->weight_row_bytes() * (size_t)n_plain_rows);
+        if (!feed->layer_weight_entries.empty())
+            memcpy(stage.data() + layer_entries_at, feed->layer_weight_entries.data(), sizeof(srd::ClipLayerWeightEntry) * feed->layer_weight_entries.size());
         if (n_spline_rows) memcpy(stage.data() + spline_rows_at, feed->spline_rows.data(), sizeof(srd::ClipSplineWeightRow) * (size_t)n_spline_rows);
         if (!feed->instance_rows.empty()) memcpy(stage.data() + inst_rows_at, feed->instance_rows.data(), 4 * feed->instance_rows.size());
     }
@@ -1355,7 +1368,15 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
             e = srk_clip_blend_weights((const srd::ClipBlendWeightRow*)(d_stage + weight_rows_at), n_plain_rows, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
                                        (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
                                        (uint32_t*)s->d_pose_check.p, st);
-        else if (e == 0 && n_plain_rows)
+        else if (n_plain_rows && feed->layer_weights) {
+            layer_weights_timer.begin(st);
+            if (e == 0)
+                e = srk_clip_layer_weights((const srd::ClipLayerWeightRow*)(d_stage + weight_rows_at), n_plain_rows, (const srd::ClipLayerRow*)(d_stage + layer_rows_at),
+                                           (const srd::ClipLayerWeightEntry*)(d_stage + layer_entries_at), (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
+                                           (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
+                                           (uint32_t*)s->d_pose_check.p, st);
+            layer_weights_timer.end(st);
+        } else if (e == 0 && n_plain_rows)
             e = srk_clip_weights((const srd::ClipWeightRow*)(d_stage + weight_rows_at), n_plain_rows, (srd::PoseBatchItem*)((unsigned char*)s->d_pose_stage.p + lay.items),
                                  (uint32_t*)((unsigned char*)s->d_pose_stage.p + lay.active_index), (float*)((unsigned char*)s->d_pose_stage.p + lay.active_weight),
                                  (uint32_t*)s->d_pose_check.p, st);
@@ -1393,10 +1414,15 @@ int pose_items(SrScene* s, const SrPoseItem* items, uint32_t n_items, void* stre
         s->actor_stage_current = true; s->actor_nodes_kept = keep_nodes; s->actor_sources_kept = keep_sources;
         s->actor_layers_kept = keep_layers;
         s->actor_layer_records = feed->layer_records;
-        if (feed->layered) { s->layer_info = feed->layer_info; s->layer_info.layer_table_bytes = sizeof(srd::ClipLayerRow) * (uint64_t)feed->layer_rows.size(); }
+        if (feed->layered) {
+            s->layer_info = feed->layer_info; s->layer_info.layer_table_bytes = sizeof(srd::ClipLayerRow) * (uint64_t)feed->layer_rows.size();
+            s->layer_weights_info = feed->layer_weights_info;
+            s->layer_weights_info.table_bytes = sizeof(srd::ClipLayerWeightRow) * (uint64_t)feed->layer_weight_rows.size() + sizeof(srd::ClipLayerWeightEntry) * (uint64_t)feed->layer_weight_entries.size();
+            s->layer_weights_info.weights_ms = feed->layer_weight_rows.empty() ? 0.0 : layer_weights_timer.ms();
+        }
         SrActorPoseInfo& ai = *feed->info;
         ai = SrActorPoseInfo{n_actors, n_items, feed->n_nodes, feed->n_channels, upload_bytes, 2u + weight_launches, 1, ai.calls + 1, 0xFFFFFFFFu, 0xFFFFFFFFu, n_weight_items, clip_timer.ms(), info.pose_ms, 0.0, 0.0};
-        s->spline_info = SrSplinePoseInfo{n_spline_rows, n_plain_rows, feed->n_cubic_channels, n_spline_rows ? spline_timer.ms() : 0.0, 0};
+        s->spline_info = SrSplinePoseInfo{n_spline_rows, feed->layer_weights ? 0u : n_plain_rows, feed->n_cubic_channels, n_spline_rows ? spline_timer.ms() : 0.0, 0};
         for (uint32_t a = 0; a < n_actors && ai.refused_actor == 0xFFFFFFFFu; a++) if (bad[2 * (size_t)n_items + a] != 0xFFFFFFFFu) ai.refused_actor = a;
         if (ai.refused_actor != 0xFFFFFFFFu) {                // a singular mesh-node transform: nothing has changed but the scratch
             s->pose_batch_keys.clear(); s->pose_batch_vertex_base.clear();
@@ -1739,16 +1765,21 @@ int sr_scene_detach_node_mask(SrScene* s, uint32_t mask_id) {
 // sr_scene_pose_actors for actors that are stacks of layers: the same checks, for every layer's clip, the stack's own (the rule's
 // constraints, the masks, the compatibility with the base clip: each pair of ids is compared once a call); the rest is pose_items
 // with a layered feed. Every table the kernel reads beside the layers' channels is the base clip's. A clip-weighted item is the
-// plain call's, from the base layer: morph weights are not layered.
+// plain call's, from the base layer: morph weights are not layered. With SR_ACTORS_LAYER_WEIGHTS such an item is a row for
+// clip_layer_weights_kernel instead: every layer's set for the blas is looked up and checked here, the mask's node resolved.
 int sr_scene_pose_actors_layered(SrScene* s, const SrClipLayerActor* actors, uint32_t n_actors, const SrActorPoseItem* items, uint32_t n_items,
                                  SrTransform* d_instance_transforms, uint32_t flags, void* stream) {
     if (!s) return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: null argument (the scene)");
-    if (flags & ~(SR_ACTORS_KEEP_NODES | SR_ACTORS_KEEP_LAYERS)) return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: unknown flag bits (SR_ACTORS_KEEP_NODES and SR_ACTORS_KEEP_LAYERS are the flags)");
+    if (flags & ~(SR_ACTORS_KEEP_NODES | SR_ACTORS_KEEP_LAYERS | SR_ACTORS_LAYER_WEIGHTS))
+        return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: unknown flag bits (SR_ACTORS_KEEP_NODES, SR_ACTORS_KEEP_LAYERS and SR_ACTORS_LAYER_WEIGHTS are the flags)");
     if (n_actors == 0 && n_items == 0) return SR_OK;
     if ((n_actors && !actors) || (n_items && !items)) return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: null argument (actors or items, with a count > 0)");
     if (((uintptr_t)d_instance_transforms & 15u) != 0) return fail(SR_ERR_INVALID_ARG, "pose_actors_layered: the instance transforms are not 16-byte aligned");
     ActorFeed feed;
     feed.n_actors = n_actors; feed.flags = flags; feed.d_instance_transforms = d_instance_transforms; feed.info = &s->actor_info; feed.layered = true;
+    feed.layer_weights = (flags & SR_ACTORS_LAYER_WEIGHTS) != 0;
+    struct StackLayer { const SrClip* clip; bool masked; };   // what a layer-weight row asks of a layer: beside feed.layer_rows, with the flag only
+    std::vector<StackLayer> stack;
     std::vector<const SrScene::AttachedClip*> base_of(n_actors);
     std::vector<uint32_t> first_matrix(n_actors);
     std::set<std::pair<uint32_t, uint32_t>> compatible;
@@ -1779,6 +1810,7 @@ int sr_scene_pose_actors_layered(SrScene* s, const SrClipLayerActor* actors, uin
                 compatible.insert({ac.layers[0].clip_id, ly.clip_id});
             }
             const float* d_mask = nullptr;
+            if (feed.layer_weights) stack.push_back(StackLayer{&clip, ly.mask_id != SR_LAYER_NO_MASK});
             if (ly.mask_id != SR_LAYER_NO_MASK) {
                 const auto im = s->node_masks.find(ly.mask_id);
                 if (im == s->node_masks.end()) return fail(SR_ERR_INVALID_ARG, layer("no node mask is attached under this id"));
@@ -1827,7 +1859,39 @@ int sr_scene_pose_actors_layered(SrScene* s, const SrClipLayerActor* actors, uin
         if (it.morph && it.weights) return fail(SR_ERR_INVALID_ARG, prefix() + "host weights given together with SR_ACTOR_CLIP_WEIGHTS (one source of weights at most)");
         if (it.skin == SR_ACTOR_NO_SKIN && !it.morph) continue;
         if (it.actor >= n_actors) return fail(SR_ERR_INVALID_ARG, prefix() + "actor " + std::to_string(it.actor) + " named, the call has " + std::to_string(n_actors) + " actors");
-        if (it.morph) {                                          // the weights of a morph set of the base layer's clip, at the base layer's time
+        if (it.morph && feed.layer_weights) {                    // the stack's weights: every layer's set for the blas, checked here
+            const uint32_t blas = it.morph - 1;
+            const SrClipLayer* layers = actors[it.actor].layers;
+            srd::ClipLayerWeightRow row{};
+            row.first_layer = feed.layer_actor_rows[it.actor].first_layer; row.n_layers = feed.layer_actor_rows[it.actor].n_layers;
+            row.first_entry = (uint32_t)feed.layer_weight_entries.size();
+            uint32_t n_targets = 0;
+            for (uint32_t l = 0; l < row.n_layers; l++) {
+                const auto layer = [i, l](const std::string& text) { return "pose_actors_layered: item " + std::to_string(i) + ": layer " + std::to_string(l) + ": " + text; };
+                const SrClip& clip = *stack[row.first_layer + l].clip;
+                const int k = clip.find_morph_set(blas);
+                if (k < 0) return fail(SR_ERR_INVALID_ARG, layer("the weights of blas " + std::to_string(blas) + " named, the layer's clip has no morph set for it"));
+                const srd::ClipMorphSet& set = clip.morph_sets()[k];
+                if (set.state == srd::kClipMorphUnavailable) return fail((int32_t)set.status, layer(clip.morph_errors[k]));
+                if (l == 0) {                                    // the base's set against the mesh's attached morph (a mesh without one is pose_items' to refuse)
+                    n_targets = set.n_targets;
+                    const auto im = s->slots.find(it.key);
+                    const uint32_t attached = im == s->slots.end() ? 0u : s->mesh_state[im->second].morph.n_targets;
+                    if (attached && attached != n_targets)
+                        return fail(SR_ERR_INVALID_ARG, layer("the set has " + std::to_string(n_targets) + " targets, the mesh's morph was attached with " + std::to_string(attached)));
+                }
+                if (set.n_targets != n_targets)
+                    return fail(SR_ERR_INVALID_ARG, layer("the set has " + std::to_string(set.n_targets) + " targets, the base layer's " + std::to_string(n_targets)));
+                const bool additive = layers[l].mode == SR_LAYER_ADDITIVE, cubic = set.n_keys && set.interpolation == srd::kClipCubic;
+                feed.layer_weights_info.samples += additive ? 2u : 1u;
+                feed.layer_weights_info.cubic_samples += cubic ? (additive ? 2u : 1u) : 0u;
+                feed.layer_weight_entries.push_back(srd::ClipLayerWeightEntry{(uint32_t)k, stack[row.first_layer + l].masked ? clip.find_node(set.gltf_node) : srd::kClipNoNode, {0u, 0u}});
+            }
+            if (feed.layer_weight_entries.size() >= (1ull << 32)) return fail(SR_ERR_UNSUPPORTED, "pose_actors_layered: the call holds 2^32 layer-weight entries or more");
+            feed.add_weight_item(i, n_targets, false);
+            feed.layer_weight_rows.push_back(row);
+            feed.layer_weights_info.rows++;
+        } else if (it.morph) {                                   // the weights of a morph set of the base layer's clip, at the base layer's time
             const SrClip& clip = base_of[it.actor]->host;
             const float time_seconds = actors[it.actor].layers[0].time_seconds;
             const uint32_t blas = it.morph - 1;
@@ -1855,6 +1919,12 @@ int sr_scene_pose_actors_layered(SrScene* s, const SrClipLayerActor* actors, uin
     }
     SrPoseBatchInfo dropped{};                                // sr_scene_pose_batch_info reads as before the call
     return pose_items(s, pose.data(), n_items, stream, true, &dropped, &feed);
+}
+
+int sr_scene_layer_weights_info(const SrScene* s, SrLayerWeightsInfo* out) {
+    if (!s || !out) return fail(SR_ERR_INVALID_ARG, "sr_scene_layer_weights_info: null argument");
+    *out = s->layer_weights_info;
+    return SR_OK;
 }
 
 int sr_scene_layer_pose_info(const SrScene* s, SrLayerPoseInfo* out) {

@@ -44,6 +44,11 @@ struct SrClip {
         for (uint32_t k = 0; k < n_morph_sets(); k++) if (morph_sets()[k].blas == blas) return (int)k;
         return -1;
     }
+    // the clip node of a glTF node (the first in clip-node order), or kClipNoNode
+    uint32_t find_node(uint32_t gltf_node) const {
+        for (uint32_t n = 0; n < header().n_nodes; n++) if (nodes()[n].gltf_node == gltf_node) return n;
+        return srd::kClipNoNode;
+    }
 };
 
 namespace srh {

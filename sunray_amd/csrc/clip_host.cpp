@@ -1,7 +1,8 @@
 // Baked clips: the read-outs and the host rule (sr_clip_sample_host, sr_clip_compose_host, sr_clip_pose_host), which
 // restates sr_gltf_pose over the flat tables with the arithmetic of clip_rule.h, and the host rule of cross-fades between two clips
 // (sr_clip_blend_compatible, sr_clip_blend_host, sr_clip_compose_records_host, sr_clip_pose_blend_host, sr_clip_blend_weights_host),
-// and the host rule of layer stacks (sr_clip_subtree_mask, sr_clip_layers_host, sr_clip_pose_layers_host).
+// and the host rule of layer stacks (sr_clip_subtree_mask, sr_clip_layers_host, sr_clip_pose_layers_host) and of their morph
+// weights (sr_clip_layer_weights_host, sr_clip_weights_layers_host).
 // No HIP in this file.
 #include "clip.h"
 
@@ -339,6 +340,69 @@ int sr_clip_pose_layers_host(const SrClip* const* clips, const SrClipLayer* laye
     std::vector<SrNodeTrs> stacked(n);
     if ((rc = sr_clip_layers_host(cur_at.data(), ref_at.data(), rule.data(), n_layers, n, stacked.data())) != SR_OK) return rc;
     return compose(clips[0], stacked.data(), placement, joint_matrices, instance_transforms, nullptr, true, "sr_clip_pose_layers_host");
+}
+
+// ---- layered morph weights: the host rule of sr_scene_pose_actors_layered with SR_ACTORS_LAYER_WEIGHTS ----------------------------
+static_assert(SR_ACTORS_LAYER_WEIGHTS == 8u && sizeof(SrLayerWeightsInfo) == 32, "the header states these");
+
+int sr_clip_layer_weights_host(const float* const* cur, const float* const* ref, const float* weight, const uint32_t* mode, const float* mask_value,
+                               uint32_t n_layers, uint32_t n_targets, float* out) {
+    if (!cur || !weight || !mode || (n_targets && !out)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_layer_weights_host: null argument");
+    if (n_layers == 0 || n_layers > SR_CLIP_MAX_LAYERS) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_layer_weights_host: the number of layers is not in [1, SR_CLIP_MAX_LAYERS]");
+    for (uint32_t l = 0; l < n_layers; l++) {
+        const std::string who = "sr_clip_layer_weights_host: layer " + std::to_string(l) + ": ";
+        // a mask value of 1 is what a layer without a mask has: the base layer may state it
+        const int rc = check_layer_rule(l, weight[l], mode[l], l == 0 && mask_value && mask_value[0] != 1.0f, who);
+        if (rc != SR_OK) return rc;
+        if (n_targets && (!cur[l] || (mode[l] == SR_LAYER_ADDITIVE && (!ref || !ref[l])))) return srh::set_error(SR_ERR_INVALID_ARG, who + "null argument (the sampled weights)");
+        if (mask_value && !blend_weight_ok(mask_value[l])) return srh::set_error(SR_ERR_INVALID_ARG, who + "the mask value is not in [0, 1]");
+    }
+    for (uint32_t k = 0; k < n_targets; k++) {
+        float acc = cur[0][k];
+        for (uint32_t l = 1; l < n_layers; l++) {
+            const double w = srd::clip_layer_set_weight(weight[l], mask_value ? mask_value[l] : 1.0f);
+            acc = mode[l] == SR_LAYER_ADDITIVE ? srd::clip_additive_weight(acc, cur[l][k], ref[l][k], w) : srd::clip_blend_weight(acc, cur[l][k], w);
+        }
+        out[k] = acc;
+    }
+    return SR_OK;
+}
+
+int sr_clip_weights_layers_host(const SrClip* const* clips, const SrClipLayer* layers, const float* const* masks, uint32_t n_layers, uint32_t blas,
+                                float* weights_out, uint32_t n_targets) {
+    if (!clips || !layers || (!weights_out && n_targets)) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_layers_host: null argument");
+    if (n_layers == 0 || n_layers > SR_CLIP_MAX_LAYERS) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_layers_host: the number of layers is not in [1, SR_CLIP_MAX_LAYERS]");
+    for (uint32_t l = 0; l < n_layers; l++) if (!clips[l]) return srh::set_error(SR_ERR_INVALID_ARG, "sr_clip_weights_layers_host: null argument");
+    std::vector<std::vector<float>> cur(n_layers), ref(n_layers);
+    std::vector<const float*> cur_at(n_layers), ref_at(n_layers, nullptr);
+    std::vector<float> weight(n_layers), mask_value(n_layers, 1.0f);
+    std::vector<uint32_t> mode(n_layers);
+    int rc;
+    for (uint32_t l = 0; l < n_layers; l++) {
+        const std::string who = "sr_clip_weights_layers_host: layer " + std::to_string(l);
+        const SrClipLayer& ly = layers[l];
+        const SrClip& clip = *clips[l];
+        const float* mask = masks ? masks[l] : nullptr;
+        if ((rc = check_layer_rule(l, ly.weight, ly.mode, mask != nullptr, who + ": ")) != SR_OK) return rc;
+        const bool additive = ly.mode == SR_LAYER_ADDITIVE;
+        if (clip.animation >= 0 && (!std::isfinite(ly.time_seconds) || (additive && !std::isfinite(ly.ref_time_seconds))))
+            return srh::set_error(SR_ERR_INVALID_ARG, who + ": gltf: the time of a pose must be finite");
+        if (l && clips[l] != clips[0] && (rc = sr_clip_blend_compatible(clips[0], clips[l])) != SR_OK) return rc;      // in that function's words
+        if (mask && !mask_values_ok(mask, clip.header().n_nodes)) return srh::set_error(SR_ERR_INVALID_ARG, who + ": the mask has a value that is not in [0, 1]");
+        const int k = clip.find_morph_set(blas);
+        if (l && k >= 0 && clip.morph_sets()[k].state != srd::kClipMorphUnavailable && clip.morph_sets()[k].n_targets != n_targets)
+            return srh::set_error(SR_ERR_INVALID_ARG, who + ": the set has " + std::to_string(clip.morph_sets()[k].n_targets) + " targets, the base layer's " + std::to_string(n_targets));
+        cur[l].resize(n_targets);
+        if ((rc = weights_of(&clip, ly.time_seconds, blas, cur[l].data(), n_targets, who)) != SR_OK) return rc;
+        if (additive) { ref[l].resize(n_targets); if ((rc = weights_of(&clip, ly.ref_time_seconds, blas, ref[l].data(), n_targets, who)) != SR_OK) return rc; ref_at[l] = ref[l].data(); }
+        cur_at[l] = cur[l].data();
+        weight[l] = ly.weight; mode[l] = ly.mode;
+        if (mask) {                                              // the clip node of the set's glTF node; a clip without it: 1
+            const uint32_t node = clip.find_node(clip.morph_sets()[k].gltf_node);
+            if (node != srd::kClipNoNode) mask_value[l] = mask[node];
+        }
+    }
+    return sr_clip_layer_weights_host(cur_at.data(), ref_at.data(), weight.data(), mode.data(), mask_value.data(), n_layers, n_targets, weights_out);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // Baked clips: the flat tables of a clip and the arithmetic of its evaluation, shared by the host rule (clip_host.cpp) and the
-// device kernels (clip_pose.hip, clip_weights.hip, clip_blend.hip, clip_spline_weights.hip, clip_layers.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
+// device kernels (clip_pose.hip, clip_weights.hip, clip_blend.hip, clip_spline_weights.hip, clip_layers.hip, clip_layer_weights.hip). The arithmetic restates GltfLoader::sample_channel, trs_matrix, mul and invert_affine
 // (gltf_load.cpp) term for term; host and device are built with -ffp-contract=off, so +, -, *, / and sqrt give the same bits on
 // both. atan2 and sin (LINEAR rotations between two keys only) come from each side's own libm; a CUBICSPLINE sample (clip_hermite)
 // needs neither, so it is bit equal between host and device without exception.
@@ -322,8 +322,41 @@ SR_CLIP_HD float clip_blend_weight(float wa, float wb, double w) {
 //   A clip's channels never share a node and path, and a part without a channel has equal bytes in cur and ref; so applying
 //   clip_additive_part3 / clip_additive_rotation channel by channel onto the accumulator (clip_layers_kernel) gives the node-wise
 //   rule's bytes.
-// Morph weights are not layered: an item with SR_ACTOR_CLIP_WEIGHTS(blas) takes its weights from the base layer's clip at the base
-// layer's time (clip_weights_kernel / clip_spline_weights_kernel, from rows the host builds from layer 0).
+// Morph weights. Without SR_ACTORS_LAYER_WEIGHTS they are not layered: an item with SR_ACTOR_CLIP_WEIGHTS(blas) takes its weights
+// from the base layer's clip at the base layer's time (clip_weights_kernel / clip_spline_weights_kernel, from rows the host builds
+// from layer 0). With the flag they go through the stack (clip_layer_weights_kernel, sr_clip_weights_layers_host), per morph set
+// (per blas) and per target k, on fp32 weights, in double in exactly this grouping, each layer's result rounded to fp32 once:
+//   Sampling: cur_l[k] is layer l's clip's set for the blas at time_seconds: clip_key_search + clip_weight_at (LINEAR / STEP),
+//   clip_spline_key_search + clip_spline_weight_at (cubic), the defaults where n_keys == 0. An additive layer also has ref_l[k],
+//   sampled the same way at ref_time_seconds.
+//   Effective weight: w_l = (double)weight_l * (double)m, exact; m is layer l's mask value at the clip node whose gltf_node is the
+//   set's gltf_node, and 1.0f where the layer has no mask or the clip holds no such node. The host resolves the node once per
+//   row (ClipLayerWeightEntry.mask_node); the kernel reads mask[node] only.
+//   Base: acc = cur_0. Override layer: acc[k] = clip_blend_weight(acc[k], cur_l[k], w_l). Additive layer: acc[k] =
+//   clip_additive_weight(acc[k], cur_l[k], ref_l[k], w_l): acc where w == 0 or the words of cur and ref are equal (an additive
+//   layer at its own reference time is the identity at every weight, as for nodes), (float)(acc + w * (cur - ref)) otherwise.
+//   Compaction: after the last layer the targets whose weight is +0 or -0 are left out; the rest in ascending target order.
+SR_CLIP_HD float clip_additive_weight(float acc, float cur, float ref, double w) {
+    if (w == 0.0 || clip_float_word(cur) == clip_float_word(ref)) return acc;
+    return (float)((double)acc + w * ((double)cur - (double)ref));
+}
+// The effective weight of a morph set of a layer from the mask value at the set's node.
+SR_CLIP_HD double clip_layer_set_weight(float weight, float mask_value) { return (double)weight * (double)mask_value; }
+// One clip-weighted item of a layered call with SR_ACTORS_LAYER_WEIGHTS as clip_layer_weights_kernel reads it, at wave-uniform
+// addresses: its actor's slice of the call's ClipLayerRow table and, per layer, an entry of a second table.
+struct ClipLayerWeightRow {
+    uint32_t first_layer, n_layers;                    // layers[first_layer .. first_layer + n_layers), the actor's
+    uint32_t first_entry;                              // entries[first_entry + l] is layer l's
+    uint32_t active_base, item, check_word;            // as ClipWeightRow's
+    uint32_t reserved[2];
+};
+static_assert(sizeof(ClipLayerWeightRow) == 32, "two 16-byte pieces");
+struct ClipLayerWeightEntry {
+    uint32_t set;               // position in the layer's clip's morph sets
+    uint32_t mask_node;         // the clip node whose mask value weighs the set, or kClipNoNode: 1
+    uint32_t reserved[2];
+};
+static_assert(sizeof(ClipLayerWeightEntry) == 16, "one 16-byte piece");
 SR_CLIP_HD void clip_quat_mul(const double* p, const double* q, double* r) {
     r[0] = ((p[3] * q[0] + p[0] * q[3]) + p[1] * q[2]) - p[2] * q[1];
     r[1] = ((p[3] * q[1] - p[0] * q[2]) + p[1] * q[3]) + p[2] * q[0];

@@ -739,6 +739,11 @@ int sr_renderer_spline_pose_info(const SrRenderer* r, SrSplinePoseInfo* out) {
     return sr_scene_spline_pose_info(r->slot[0].scene, out);
 }
 
+int sr_renderer_layer_weights_info(const SrRenderer* r, SrLayerWeightsInfo* out) {
+    if (!r) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_layer_weights_info: null argument (the renderer)");
+    return sr_scene_layer_weights_info(r->slot[0].scene, out);
+}
+
 // How sr_renderer_pose_scene poses (SR_POSE_BATCH_*).
 int sr_renderer_set_pose_batch(SrRenderer* r, uint32_t mode) {
     if (mode > SR_POSE_BATCH_ON) return rfail(SR_ERR_INVALID_ARG, "sr_renderer_set_pose_batch: mode must be SR_POSE_BATCH_OFF or SR_POSE_BATCH_ON");

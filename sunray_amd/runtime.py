@@ -327,7 +327,7 @@ class LayeredActorArgs(ActorArgs):
             row.ref_time_seconds = float(ref_time_seconds)
 
 
-def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index, keep_sources=False, packed=ActorArgs, keep_layers=False):
+def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index, keep_sources=False, packed=ActorArgs, keep_layers=False, layer_weights=False):
     if isinstance(actors, ActorArgs) and type(actors) is not packed:
         raise ValueError("%s: the packed arguments are those of another entry point (%s)" % (packed.WHO, type(actors).__name__))
     args = actors if isinstance(actors, packed) else packed(actors, items)
@@ -341,7 +341,7 @@ def _actor_call(fn, handle, actors, items, tensor, keep_nodes, device_index, kee
         ptr, stream = C.c_void_p(tensor.data_ptr()), C.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)
     check(fn(handle, args.actors, C.c_uint32(args.n_actors), args.items, C.c_uint32(args.n_items), ptr,
              C.c_uint32((abi.ACTORS_KEEP_NODES if keep_nodes else 0) | (abi.ACTORS_KEEP_SOURCES if keep_sources else 0) |
-                        (abi.ACTORS_KEEP_LAYERS if keep_layers else 0)), stream))
+                        (abi.ACTORS_KEEP_LAYERS if keep_layers else 0) | (abi.ACTORS_LAYER_WEIGHTS if layer_weights else 0)), stream))
 
 
 class Clip:
@@ -568,6 +568,60 @@ def clip_layers_host(cur, rules, ref=None):
     out = np.zeros(max(n_nodes, 1), abi.NODE_TRS)
     check(lib().sr_clip_layers_host(cp, rp, rows, C.c_uint32(n), C.c_uint32(n_nodes), _p(out)))
     return out[:n_nodes]
+
+
+def clip_layer_weights_host(cur, rules, ref=None):
+    """The layer rule over sampled morph weights: `cur` a sequence of float32 arrays [n_targets], one per layer (the first is the
+    base), `rules` one (weight, mode: "override" / "additive" or abi.LAYER_*, mask value in [0, 1] or None: 1) per layer, `ref`
+    a sequence with an additive layer's weights at its reference time (None elsewhere), or None -> the stacked weights, zeros
+    included (sr_clip_layer_weights_host)."""
+    cur = [np.ascontiguousarray(c, dtype=np.float32) for c in cur]
+    rules = [tuple(r) for r in rules]
+    n = len(cur)
+    if len(rules) != n or (ref is not None and len(ref) != n):
+        raise ValueError("clip_layer_weights_host: one rule (and, where given, one reference entry) per layer")
+    n_targets = len(cur[0]) if n else 0
+    refs = [None if ref is None or r is None else np.ascontiguousarray(r, dtype=np.float32) for r in (ref or [None] * n)]
+    if any(c.ndim != 1 or len(c) != n_targets for c in cur) or any(r is not None and (r.ndim != 1 or len(r) != n_targets) for r in refs):
+        raise ValueError("clip_layer_weights_host: every layer must hold the same number of weights")
+    if any(len(r) != 3 for r in rules):
+        raise ValueError("clip_layer_weights_host: a rule is (weight, mode, mask value)")
+    cp, rp = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+    for l in range(n):
+        cp[l] = cur[l].ctypes.data if n_targets else None
+        rp[l] = refs[l].ctypes.data if refs[l] is not None and n_targets else None
+    weight, mode, mask_value = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.uint32), np.ones(max(n, 1), np.float32)
+    for l, r in enumerate(rules):
+        weight[l], mode[l] = r[0], LayeredActorArgs.MODES[r[1]] if isinstance(r[1], str) else int(r[1])
+        mask_value[l] = 1.0 if r[2] is None else r[2]
+    masked = any(r[2] is not None for r in rules)
+    out = np.zeros(max(n_targets, 1), np.float32)
+    check(lib().sr_clip_layer_weights_host(cp, rp, _p(weight), _p(mode), _p(mask_value) if masked else None,
+                                           C.c_uint32(n), C.c_uint32(n_targets), _p(out)))
+    return out[:n_targets]
+
+
+def clip_weights_layers_host(layers, blas, n_targets=None):
+    """-> the weights [n_targets] float32, zeros included, of the blas's morph set through a stack of layers: `layers` as
+    Clip.pose_layers_host takes them, (clip, time, weight, mode, host mask float32 [n_nodes] or None, reference time), the first
+    the base: sample every layer's set, resolve each mask at the set's node, stack (sr_clip_weights_layers_host)."""
+    layers = [tuple(ly) for ly in layers]
+    n = len(layers)
+    clips, rows, masks, keep = (C.c_void_p * max(n, 1))(), (abi.SrClipLayer * max(n, 1))(), (C.c_void_p * max(n, 1))(), []
+    for l, ly in enumerate(layers):
+        if len(ly) != 6:
+            raise ValueError("clip_weights_layers_host: layer %d: a layer is (clip, time, weight, mode, mask, reference time), %d values given" % (l, len(ly)))
+        clips[l] = ly[0]._h if isinstance(ly[0], Clip) else ly[0]
+        rows[l].time_seconds, rows[l].weight, rows[l].ref_time_seconds, rows[l].mask_id = float(ly[1]), float(ly[2]), float(ly[5]), abi.LAYER_NO_MASK
+        rows[l].mode = LayeredActorArgs.MODES[ly[3]] if isinstance(ly[3], str) else int(ly[3])
+        if ly[4] is not None:
+            m = _node_mask(ly[4], "clip_weights_layers_host: layer %d" % l)
+            keep.append(m)
+            masks[l] = m.ctypes.data
+    nt = layers[0][0].morph(blas)["n_targets"] if n_targets is None else int(n_targets)
+    w = np.zeros(max(nt, 1), dtype=np.float32)
+    check(lib().sr_clip_weights_layers_host(clips, rows, masks, C.c_uint32(n), C.c_uint32(blas), _p(w), C.c_uint32(nt)))
+    return w[:nt]
 
 
 def pose_batch_plan(n_vertices):
@@ -874,11 +928,20 @@ class Scene:
     def detach_node_mask(self, mask_id):
         check(lib().sr_scene_detach_node_mask(self._h, C.c_uint32(mask_id)))
 
-    def pose_actors_layered(self, actors, items=(), tensor=None, keep_nodes=False, keep_layers=False):
+    def pose_actors_layered(self, actors, items=(), tensor=None, keep_nodes=False, keep_layers=False, layer_weights=False):
         """pose_actors for actors that are stacks of layers over attached clips: `actors` as LayeredActorArgs takes them (or a
-        LayeredActorArgs), the rest as pose_actors; keep_layers also stores every layer's sampled records for read_actor_layer
-        (sr_scene_pose_actors_layered)."""
-        _actor_call(lib().sr_scene_pose_actors_layered, self._h, actors, items, tensor, keep_nodes, self.device_index, False, LayeredActorArgs, keep_layers)
+        LayeredActorArgs), the rest as pose_actors; keep_layers also stores every layer's sampled records for read_actor_layer;
+        layer_weights has every clip-weighted item take the stack's morph weights, not the base layer's
+        (sr_scene_pose_actors_layered, SR_ACTORS_LAYER_WEIGHTS)."""
+        _actor_call(lib().sr_scene_pose_actors_layered, self._h, actors, items, tensor, keep_nodes, self.device_index, False, LayeredActorArgs, keep_layers,
+                    layer_weights)
+
+    def layer_weights_info(self):
+        """-> abi.SrLayerWeightsInfo: the rows, set samples, cubic samples, table bytes and kernel time of the clip-weighted items
+        of the last pose_actors_layered that reached the device (sr_scene_layer_weights_info)."""
+        info = abi.SrLayerWeightsInfo()
+        check(lib().sr_scene_layer_weights_info(self._h, C.byref(info)))
+        return info
 
     def read_actor_layer(self, actor, layer, n_nodes):
         """-> (abi.NODE_TRS [n_nodes], abi.NODE_TRS [n_nodes]): layer `layer`'s sampled records of an actor of the last
@@ -1867,9 +1930,16 @@ class Renderer:
     def detach_node_mask(self, mask_id):
         check(lib().sr_renderer_detach_node_mask(self._h, C.c_uint32(mask_id)))
 
-    def pose_actors_layered(self, actors, items=(), tensor=None, keep_nodes=False, keep_layers=False):
+    def pose_actors_layered(self, actors, items=(), tensor=None, keep_nodes=False, keep_layers=False, layer_weights=False):
         """Scene.pose_actors_layered on the first device slot, as pose_actors (sr_renderer_pose_actors_layered)."""
-        _actor_call(lib().sr_renderer_pose_actors_layered, self._h, actors, items, tensor, keep_nodes, self.devices[0], False, LayeredActorArgs, keep_layers)
+        _actor_call(lib().sr_renderer_pose_actors_layered, self._h, actors, items, tensor, keep_nodes, self.devices[0], False, LayeredActorArgs, keep_layers,
+                    layer_weights)
+
+    def layer_weights_info(self):
+        """Scene.layer_weights_info of the first device slot (sr_renderer_layer_weights_info)."""
+        info = abi.SrLayerWeightsInfo()
+        check(lib().sr_renderer_layer_weights_info(self._h, C.byref(info)))
+        return info
 
     def actor_pose_info(self):
         info = abi.SrActorPoseInfo()
